@@ -17,16 +17,23 @@ Three ways to start it (config.launch_mode says which one ran):
          bench.py --gpus N --steps K --warmup W                      one process per GPU: srt_comm_init_rank; torch.distributed carries
                                                                      the 128-byte communicator id, the barriers and the statistics
 
-Wall-clock budget of one invocation (the driver allows 600 s): import torch on a fresh box <= 120 s; scene build + tree tuning <= 3 s;
-communicator + verification frame <= 30 s; (W + K) headline frames of <= 0.36 s each at N = 1 (less at N > 1); one builder's-tree frame;
-N = 1 only: CPU baseline ~ 35 s and the three other configurations ~ 3 s; the cfg 5 sub-record 12.8 s / N (+ 1 s build).  Whatever
-happened before it (a communicator that fell back, a slow box), the cfg 5 sub-record is SKIPPED -- and the line says so -- when its
-estimated cost would carry the process past --time-budget seconds (default 420) since it started: the headline line is always printed.
+A plain run does only what the headline needs: scene build + tree tuning (<= 3 s), (N > 1) the communicator and its verification
+frame, W warm-up and K timed steps (<= 0.36 s each at N = 1, less at N > 1), and ONE JSON line on rank 0: metric, value, unit,
+higher_is_better, dtype, ms_per_step (milliseconds of one timed step), steps, warmup, the workload and kernel_ms_per_step.
+--dump-outputs DIR writes what the last timed step computed, the image as a caller receives it (see dump_outputs).
 
-Rank 0 prints ONE JSON line.  Besides the headline it carries
-  cfg5            one frame of BASELINE cfg 5 as specified (100k-triangle mesh, 3840x2160, 4096 spp) on the same N GPUs,
+--full adds everything else, each piece outside the timed region (the --no-* options switch parts of it off):
+  V, T, rays per path, bytes per ray (an instrumented 4-spp frame), fb_checksum and the D2H time of the framebuffer,
+  roofline        the render kernel against what binds it (see below; N = 1: the issue-rate and copy-rate calibration),
+  builders_tree   the headline workload on the SAH builder's untuned tree (value_builders_tree),
+  cpu_baseline    (N = 1) the CPU oracle on this box's host cores, with a parity check of both kernel builds,
   other_configs   (N = 1) cfg 2, cfg 4 and cfg 5's scene at 512 spp, each with V, T, kernel time and its own roofline entry,
-  roofline        the render kernel against what binds it (see below), cpu_baseline (N = 1) the CPU oracle on this box's host cores.
+  cfg5            one frame of BASELINE cfg 5 as specified (100k-triangle mesh, 3840x2160, 4096 spp) on the same N GPUs.
+Wall-clock budget of a --full invocation (600 s allowed): import torch on a fresh box <= 120 s; communicator + verification frame
+<= 30 s; one builder's-tree frame; N = 1 only: CPU baseline ~ 35 s and the three other configurations ~ 3 s; the cfg 5 sub-record
+12.8 s / N (+ 1 s build).  Whatever happened before it (a communicator that fell back, a slow box), the cfg 5 sub-record is SKIPPED --
+and the line says so -- when its estimated cost would carry the process past --time-budget seconds (default 420) since it started:
+the headline line is always printed.
 
 `roofline` prices the render kernel against what actually binds it.  The scene is LDS / L2 resident, so HBM is
 not the roof (the SURVEY 8(d) HBM figure is kept under roofline.hbm, against the copy bandwidth measured in this
@@ -594,6 +601,29 @@ def timed_frames(job, W, H, spp, depth, steps, warmup, label=""):
     return dict(elapsed=elapsed, total_rays=total_rays, rows=rows, kms=max(x[0] for x in rows), rays_rank0=rows[0][1])
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000      # all files of one dump together, .npy headers included
+
+
+def dump_outputs(root, W, H, rays, outdir):
+    """What the timed path computed in its last step, as a caller of it receives it: the three quantised framebuffer planes in
+    row-major order (fb_r, fb_g, fb_b: H x W float32) and the number of rays the step traced (rays: float64).  An image too large for
+    64 MB is written as a fixed, seeded sample of its pixels, with their row-major indices (pixel_index: float64)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    planes = root.read_fb_rowmajor(W, H)
+    arrays = {"rays": np.array([rays], np.float64)}
+    if 3 * W * H * 4 + 4096 <= DUMP_MAX_BYTES:
+        arrays.update((name, p.reshape(H, W)) for name, p in zip(("fb_r", "fb_g", "fb_b"), planes))
+    else:
+        n = (DUMP_MAX_BYTES - 4096) // (3 * 4 + 8)
+        idx = np.sort(np.random.default_rng(1984).choice(W * H, n, replace=False))
+        arrays["pixel_index"] = idx.astype(np.float64)
+        arrays.update((name, p[idx]) for name, p in zip(("fb_r", "fb_g", "fb_b"), planes))
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    log("outputs of the last timed step written to %s (%s)" % (outdir, ", ".join(sorted(arrays))))
+
+
 def lane_ops_entry(scene_id, tree=None):
     """the committed PMC entry of a scene: "scene_<id>", or -- when the run traverses another tree of the same scene (the builder's
     tree of a chain-bound launch next to the throughput-tuned one) -- the entry "scene_<id>_*" that was taken on that tree"""
@@ -764,6 +794,10 @@ def main():
     ap.add_argument("--spp", type=int, default=1024)
     ap.add_argument("--depth", type=int, default=16)
     ap.add_argument("--bvh", type=int, default=1)              # SRT_BVH_SAH for the synthetic scenes
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: V / T, roofline and calibration, fb_checksum, the builder's-tree comparison, the CPU baseline, "
+                         "the other configurations and the cfg 5 sub-record (the --no-* options below switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed to DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-calibration", action="store_true", help="skip the issue-rate microkernel and the copy-rate measurement (profiling passes)")
     ap.add_argument("--no-profile-order", action="store_true", help="keep the SAH builder's child order (nearer child to the camera first) instead of the profiled one")
@@ -776,6 +810,8 @@ def main():
     ap.add_argument("--rehearse-gloo", action="store_true",
                     help="rehearsal of the process-per-GPU control flow on ONE GPU: every rank uses cuda:0, torch.distributed runs on gloo and the gather goes through host memory (never used for reported numbers)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     global PROFILE_ORDER
     PROFILE_ORDER = not args.no_profile_order
 
@@ -830,11 +866,11 @@ def main():
     job.upload(scene, cam)
 
     # ---- V, T from the instrumented kernel, outside the timed region
-    tc = traversal_counts(job, W, H, args.depth)
+    tc = traversal_counts(job, W, H, args.depth) if args.full else None
 
     # ---- calibration of the roofs, outside the timed region (rank 0, N = 1) -------------------------------------------
     calib, copy_gbs = None, None
-    if job.world == 1 and not args.no_calibration:
+    if args.full and job.world == 1 and not args.no_calibration:
         calib = job.root.calibrate(0, 4, 40000)            # v_add_f32, 4 waves / SIMD, one workgroup per CU
         copy_gbs = measure_hbm_copy_gbs(torch)
         log("calibration: %.1f G wave-instr/s (%.3f / cycle / SIMD at %.2f GHz; wave Mcycles min/mean/max %.2f/%.2f/%.2f); copy %.0f GB/s" %
@@ -850,11 +886,36 @@ def main():
     tf = timed_frames(job, W, H, args.spp, args.depth, args.steps, args.warmup)
     elapsed, total_rays, kms = tf["elapsed"], tf["total_rays"], tf["kms"]
 
+    if args.dump_outputs:
+        last_rays = job.reduce_sum([float(sum(r.stats()["rays"] for r in job.local))])[0]
+        if job.rank == 0:
+            dump_outputs(job.root, W, H, last_rays, args.dump_outputs)
+
     out = None
     if job.rank == 0:
-        steps = max(args.steps, 1)
-        headline = job.world == 1 and (args.scene, W, H, args.spp, args.depth, args.bvh) == (100, 1920, 1080, 1024, 16, 1)
+        steps = args.steps
         mray = total_rays / elapsed / 1e6
+        out = {
+            "metric": "Mray/s", "value": mray, "unit": "Mray/s", "n_gpus": job.world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": elapsed / steps * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "%s (%d tris, %d BVH nodes), %dx%d, %d spp, depth %d" %
+                                   (SCENE_NAMES.get(args.scene, "scene %d" % args.scene), scene.n_tris, scene.n_nodes, W, H, args.spp, args.depth),
+                       "scene_id": args.scene,
+                       "bvh": BVH_NAMES.get(args.bvh, str(args.bvh)), "child_order": order_note, "tree_sha256": scene_tree,
+                       "tree_build_s": tree_info["tree_build_s"], "tree_tuning_s": tree_info["tree_tuning_s"],
+                       "tiles": "8x8 px per wave, rank = tile % n_gpus", "gather": job.gather_via, "launch_mode": job.launch_mode},
+            "mpath_per_s": (W * H * args.spp * steps) / elapsed / 1e6,
+            "kernel_ms_per_step": kms,
+        }
+        if job.world > 1:
+            rows = tf["rows"]
+            out["per_rank"] = {"kernel_ms": [round(x[0], 3) for x in rows], "rays_per_frame": [int(x[1]) for x in rows],
+                               "exchange_ms_after_own_kernel": [round(x[2], 3) for x in rows] if "ncclGather" in job.gather_via else None}
+            out["gather_check"] = job.gather_check
+
+    if out is not None and args.full:
+        headline = job.world == 1 and (args.scene, W, H, args.spp, args.depth, args.bvh) == (100, 1920, 1080, 1024, 16, 1)
         rays_per_launch_rank0 = tf["rays_rank0"]
         b_ray = tc["b_ray_layout"]
         # ---- roofline of the dominant kernel (render_kernel) on this rank -------------------------------------------
@@ -901,37 +962,22 @@ def main():
         t_d2h = time.perf_counter()
         checksum = checksum_of(job.root)       # outside the timed region: image checksum, identical for every N
         d2h_ms = (time.perf_counter() - t_d2h) * 1e3
-        out = {
-            "metric": "Mray/s", "value": mray, "unit": "Mray/s", "n_gpus": job.world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / steps * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "%s (%d tris, %d BVH nodes), %dx%d, %d spp, depth %d" %
-                                   (SCENE_NAMES.get(args.scene, "scene %d" % args.scene), scene.n_tris, scene.n_nodes, W, H, args.spp, args.depth),
-                       "scene_id": args.scene,
-                       "bvh": BVH_NAMES.get(args.bvh, str(args.bvh)), "child_order": order_note, "tree_sha256": scene_tree,
-                       "tree_build_s": tree_info["tree_build_s"], "tree_tuning_s": tree_info["tree_tuning_s"],
-                       "nan_direction_rays": "%.2f %% of the counted rays have a NaN direction (Sellmeier quirk Q1) and are answered 'miss' without walking the tree" % (100.0 * tc["nan_share"]),
-                       "tiles": "8x8 px per wave, rank = tile % n_gpus", "gather": job.gather_via, "launch_mode": job.launch_mode},
-            "mpath_per_s": (W * H * args.spp * steps) / elapsed / 1e6,
+        out["config"]["nan_direction_rays"] = "%.2f %% of the counted rays have a NaN direction (Sellmeier quirk Q1) and are answered 'miss' without walking the tree" % (100.0 * tc["nan_share"])
+        out.update({
             "rays_per_path": tc["rays_per_path"], "node_records_per_ray_V": tc["V"], "tri_tests_per_ray_T": tc["T"],
-            "kernel_ms_per_step": kms, "fb_checksum": checksum,
+            "fb_checksum": checksum,
             # SURVEY 8(d)'s wall clock includes the hand-over of the framebuffer to the host; `value` / `ms_per_step` end with the
             # image in HBM (the boundary returns device memory), this adds the synchronous D2H of the three quantised planes
             "d2h_ms": d2h_ms, "ms_per_step_incl_d2h": elapsed / steps * 1e3 + d2h_ms,
             "mray_per_s_incl_d2h": total_rays / steps / (elapsed / steps + d2h_ms * 1e-3) / 1e6,
             "roofline": roof,
-        }
+        })
         out.update(bytes_fields(tc))
-        if job.world > 1:
-            rows = tf["rows"]
-            out["per_rank"] = {"kernel_ms": [round(x[0], 3) for x in rows], "rays_per_frame": [int(x[1]) for x in rows],
-                               "exchange_ms_after_own_kernel": [round(x[2], 3) for x in rows] if "ncclGather" in job.gather_via else None}
-            out["gather_check"] = job.gather_check
 
     # ---- the same workload on the BUILDER's tree (no tuning): keeps the scene-side gain apart from the kernel-side one, round over round.
     # Every rank takes part (collectives inside); outside the timed region; the tuned scene is uploaded again afterwards.
     builders = None
-    if tree_info["tuned"] and not args.no_builders_tree:
+    if args.full and tree_info["tuned"] and not args.no_builders_tree:
         try:
             scene_b, note_b, _ = build_scene(srt, job, args.scene, args.bvh, W, H, args.depth, tune=False)
             job.upload(scene_b, cam)
@@ -945,7 +991,7 @@ def main():
             log("builder's-tree frame failed: %r" % (e,))
             builders = {"value": None, "error": repr(e)}
         job.upload(scene, cam)
-    if out is not None:
+    if out is not None and args.full:
         if builders is not None:
             out["value_builders_tree"] = builders.get("value")
             out["builders_tree"] = builders
@@ -954,7 +1000,7 @@ def main():
             out["builders_tree"] = {"note": "the headline was measured on the builder's tree itself (no throughput tuning for this launch)", "tree_sha256": scene_tree}
 
     # ---- the CPU baseline (N = 1 only), while the headline scene is still uploaded -------------------------------------------
-    if out is not None and not args.no_cpu_baseline and job.world == 1:
+    if out is not None and args.full and not args.no_cpu_baseline and job.world == 1:
         try:
             out["cpu_baseline"] = cpu_baseline(srt, scene, cam, W, H, args.depth, args.bvh, gpu_renderer=job.root)
             # the extrapolated wall time of ONE frame of this workload on those host cores (the rate is spp independent)
@@ -970,7 +1016,7 @@ def main():
 
     # ---- the other BASELINE configurations, one frame each, after the timed region (every rank takes part: collectives inside) ----
     others, cfg5 = [], None
-    if job.world == 1 and not args.no_other_configs:
+    if args.full and job.world == 1 and not args.no_other_configs:
         for sid, bvh, w, h, spp, depth, name in ((100, 1, 1280, 720, 256, 16, "cfg 2"), (1, 0, 1920, 1080, 2048, 16, "cfg 4"), (101, 1, 3840, 2160, 512, 16, "cfg 5's scene at 512 spp")):
             try:
                 rec = secondary_workload(srt, job, sid, bvh, w, h, spp, depth)
@@ -978,6 +1024,8 @@ def main():
             except Exception as e:      # noqa: BLE001
                 rec = {"baseline_config": name, "value": None, "error": repr(e)}
             others.append(rec)
+    if not args.full:
+        args.cfg5_spp = 0
     if args.cfg5_spp > 0:
         cw, ch = [int(x) for x in args.cfg5_size.lower().split("x")]
         # (estimated cost: 13 s per 3840x2160 x 4096 spp frame on one GPU, shared by the ranks, x 1.5 + set-up; every rank takes the same

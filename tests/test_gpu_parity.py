@@ -821,7 +821,7 @@ def test_bench_single_process_two_ranks_mock_transport():
     mock = os.path.join(root, "tests", "cpp", "_build", "libmock_rccl.so")
     if not os.path.exists(mock):
         pytest.skip("tests/cpp/_build/libmock_rccl.so not built (__graft_entry__.build())")
-    common = ["--width", "200", "--height", "120", "--spp", "24", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-calibration",
+    common = ["--full", "--width", "200", "--height", "120", "--spp", "24", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-calibration",
               "--no-other-configs", "--cfg5-spp", "12", "--cfg5-size", "160x90"]
 
     def run(gpus, env):

@@ -1,8 +1,10 @@
-"""Pinning of the host-side rows f1 / f2 / f3 against the REFERENCE ITSELF, as far as it compiles in this image without stand-ins:
+"""Pinning of the host-side rows f1 / f2 / f3 against the REFERENCE ITSELF, as far as it compiles without stand-ins:
 primitives/transform.cu, io/params.cpp (+ io/params.h), _log_/log_context.cpp (+ utils/utility.h), image/image.cpp and
-io/save_image.cpp (+ the vendored CImg.h) build unmodified with hipcc -x hip from where they lie under /root/reference (recipe:
-oracle/Makefile target `ref`; harnesses of ours: oracle/ref_host_driver.cpp, oracle/ref_image_driver.cpp; outputs
-oracle/_ref/libref_host.so, libref_image.so, git-ignored, built by __graft_entry__.build() where the reference is mounted).
+io/save_image.cpp (+ the vendored CImg.h) build unmodified with hipcc -x hip (recipe: oracle/Makefile target `ref`; harnesses of
+ours: oracle/ref_host_driver.cpp, oracle/ref_image_driver.cpp; outputs oracle/_ref/libref_host.so, libref_image.so, git-ignored).
+What those compiled functions return for the inputs below is stored under tests/golden/ (ref_host_vectors.json, ref_arrays.npz;
+regenerated from the oracle/_ref libraries by tests/golden/make_ref_vectors.py), so the suite needs neither the reference sources
+nor oracle/_ref: the product is compared with the stored reference outputs.
 
   * transform::assign_rot_matrix (transform.cu:4-34)  == srt_rotation_matrix (the matrix Builder::rotate_about_origin uses), bit for bit
   * param_manager::parseArgs (io/params.h:236-304)    == srt_cli::parseArgs (csrc/srt_cli.hpp, what srt_render parses with) on a table of argv's
@@ -12,6 +14,8 @@ oracle/_ref/libref_host.so, libref_image.so, git-ignored, built by __graft_entry
 The product side of the last three is reached through tests/cpp/cli_driver.cpp (the header srt_render is built from) and, for the
 parser, through the srt_render binary itself (--dump-params)."""
 import ctypes as C
+import hashlib
+import json
 import os
 import re
 import subprocess
@@ -20,8 +24,8 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_HOST = os.path.join(ROOT, "oracle", "_ref", "libref_host.so")
-REF_IMAGE = os.path.join(ROOT, "oracle", "_ref", "libref_image.so")
+GOLDEN_JSON = os.path.join(ROOT, "tests", "golden", "ref_host_vectors.json")
+GOLDEN_NPZ = os.path.join(ROOT, "tests", "golden", "ref_arrays.npz")
 CLI_SO = os.path.join(ROOT, "tests", "cpp", "_build", "libcli_driver.so")
 SRT_RENDER = os.path.join(ROOT, "cuda-spectral-ray-tracer_amd", "srt_render")
 
@@ -37,16 +41,22 @@ class Params(C.Structure):
         return d
 
 
-def _build_ref():
-    if os.path.isdir("/root/reference/io") and not (os.path.exists(REF_HOST) and os.path.exists(REF_IMAGE)):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "ref"])
+def _golden():
+    with open(GOLDEN_JSON) as f:
+        return json.load(f)
 
 
-def _ref_host():
-    _build_ref()
-    if not os.path.exists(REF_HOST):
-        pytest.skip("oracle/_ref/libref_host.so not built (the reference is not mounted here)")
-    return C.CDLL(REF_HOST)
+def _golden_arrays():
+    with np.load(GOLDEN_NPZ) as z:
+        return {k: z[k] for k in z.files}
+
+
+def inputs_digest(*arrays):
+    """sha256 over the bytes of the inputs a stored vector was made from: a changed input generator fails loudly, not as a mismatch"""
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
 
 
 def _cli():
@@ -60,26 +70,42 @@ def _deg2rad(d):      # degrees_to_radians, utils/cuda_utility.cuh:40-43 with PI
     return np.float32(np.float32(np.float32(d) * np.float32(3.1415926535897932385)) / np.float32(180.0))
 
 
-def test_rotation_matrix_equals_reference_function(srt):
-    """transform::assign_rot_matrix compiled from the reference == srt_rotation_matrix for X / Y / Z, the three angles the built-in
-    scenes use (+25, -18, +10 degrees: scene/scene.cu:116,121,127,166) and a sweep, bit for bit -- layout and sense of the matrix
-    (f1) rest on reference code.  An unknown axis leaves the matrix untouched on both sides."""
-    R = _ref_host()
-    L = srt.binding.lib()
-    fp = C.POINTER(C.c_float)
+def rotation_cases():
+    """(axis, theta, start matrix) of the rotation pin, in order: the three angles the built-in scenes use (+25, -18, +10 degrees:
+    scene/scene.cu:116,121,127,166), edge angles and a sweep, for X / Y / Z and two unknown axis ids"""
     rng = np.random.default_rng(3)
     angles = [_deg2rad(25.0), _deg2rad(-18.0), _deg2rad(10.0), np.float32(0.0), np.float32(-0.0), np.float32(np.pi), np.float32(1e-8), np.float32(1e8)]
     angles += list(rng.uniform(-10, 10, 500).astype(np.float32))
+    cases = []
     for axis in (0, 1, 2, 3, 7):
         for th in angles:
             start = rng.uniform(-1, 1, 9).astype(np.float32) if axis in (0, 7) else np.eye(3, dtype=np.float32).reshape(9)
-            a, b = start.copy(), start.copy()
-            assert R.ref_rot_matrix(C.c_float(float(th)), axis, a.ctypes.data_as(fp)) == 0
-            assert L.srt_rotation_matrix(C.c_float(float(th)), axis, b.ctypes.data_as(fp)) == 0
-            assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), (axis, float(th), a, b)
+            cases.append((axis, np.float32(th), start))
+    return cases
+
+
+def rotation_inputs_digest(cases):
+    return inputs_digest(np.array([c[0] for c in cases], np.int32), np.array([c[1] for c in cases], np.float32), np.stack([c[2] for c in cases]))
+
+
+def test_rotation_matrix_equals_reference_function(srt):
+    """transform::assign_rot_matrix compiled from the reference (stored outputs) == srt_rotation_matrix for X / Y / Z, the three angles
+    the built-in scenes use (+25, -18, +10 degrees: scene/scene.cu:116,121,127,166) and a sweep, bit for bit -- layout and sense of the
+    matrix (f1) rest on reference code.  An unknown axis leaves the matrix untouched on both sides."""
+    G = _golden_arrays()
+    L = srt.binding.lib()
+    fp = C.POINTER(C.c_float)
+    cases = rotation_cases()
+    assert rotation_inputs_digest(cases) == str(G["rot_inputs_sha256"]), "the inputs differ from the ones the stored outputs were made from"
+    ref = G["rot_matrix_bits"]
+    assert ref.shape == (len(cases), 9)
+    for k, (axis, th, start) in enumerate(cases):
+        b = start.copy()
+        assert L.srt_rotation_matrix(C.c_float(float(th)), axis, b.ctypes.data_as(fp)) == 0
+        assert np.array_equal(ref[k], b.view(np.uint32)), (axis, float(th), ref[k].view(np.float32), b)
     # the sense of the Y rotation, spelled out: vec3::matrix_mul (math/vec3.cuh:80-91) maps (1, 0, 0) to (cos, 0, -sin)
-    m = np.eye(3, dtype=np.float32).reshape(9)
-    R.ref_rot_matrix(C.c_float(float(_deg2rad(25.0))), 2, m.ctypes.data_as(fp))
+    k = next(k for k, (axis, th, _) in enumerate(cases) if axis == 2 and th == _deg2rad(25.0))
+    m = ref[k].view(np.float32)
     v = m.reshape(3, 3) @ np.array([1.0, 0.0, 0.0], np.float32)
     assert v[0] > 0.9 and v[2] < -0.4 and v[1] == 0.0
 
@@ -134,25 +160,37 @@ ARGV_TABLE = [
 ]
 
 
-@pytest.mark.parametrize("argv", ARGV_TABLE, ids=lambda a: " ".join(a) or "defaults")
+def argv_key(argv):
+    return " ".join(argv) or "defaults"
+
+
+def params_to_json(d):
+    return {k: (v.decode() if isinstance(v, bytes) else v) for k, v in d.items()}
+
+
+def params_from_json(d):
+    return {k: (v.encode() if k in ("title", "log_subdir") else v) for k, v in d.items()}
+
+
+@pytest.mark.parametrize("argv", ARGV_TABLE, ids=argv_key)
 def test_parse_args_equals_reference_param_manager(argv):
-    """param_manager::parseArgs (compiled from io/params.h) vs srt_cli::parseArgs on the same argv: every parsed value incl. the
-    defaults (xres 600, AR 1, spp 500, bounce 10), yres = uint(xres / ar), the xcsize / ycsize defaulting rules, flags that miss
-    their value, values that do not parse (previous value kept), repeated flags, unknown flags."""
-    R, P = _ref_host(), _cli()
+    """param_manager::parseArgs (compiled from io/params.h; stored result) vs srt_cli::parseArgs on the same argv: every parsed value
+    incl. the defaults (xres 600, AR 1, spp 500, bounce 10), yres = uint(xres / ar), the xcsize / ycsize defaulting rules, flags that
+    miss their value, values that do not parse (previous value kept), repeated flags, unknown flags."""
+    P = _cli()
+    rec = _golden()["parse_args"][argv_key(argv)]
+    assert rec["argv"] == argv
+    d = params_from_json(rec["params"])
     full = [b"prog"] + [a.encode() for a in argv]
     arr = (C.c_char_p * len(full))(*full)
-    a, b = Params(), Params()
-    for fn in (R.ref_parse_args, P.cli_parse_args):
-        fn.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(Params)]
-    assert R.ref_parse_args(len(full), arr, C.byref(a)) == 0
+    b = Params()
+    P.cli_parse_args.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(Params)]
     assert P.cli_parse_args(len(full), arr, C.byref(b)) == 0
-    assert a.as_dict() == b.as_dict()
+    assert d == b.as_dict()
     # ... and the binary itself (reference flags only: its own flags are not in this table)
     out = subprocess.run([SRT_RENDER, "--dump-params"] + argv, capture_output=True, text=True, timeout=60)
     assert out.returncode == 0, out.stderr[-500:]
     kv = dict(l.split("=", 1) for l in out.stdout.splitlines() if re.match(r"^[a-z_]+=", l))
-    d = a.as_dict()
     if d["scene"] < 3 or d["title"]:
         assert kv["title"] == d["title"].decode()
     assert kv["log_subdir"] == d["log_subdir"].decode()
@@ -161,42 +199,49 @@ def test_parse_args_equals_reference_param_manager(argv):
     assert np.float32(float(kv["ar"])).view(np.uint32).item() == d["ar"]
 
 
-def _log_both(tmp_path, title, subdir, entries):
-    R, P = _ref_host(), _cli()
+def run_log(fn, directory, title, subdir, entries):
+    """one run log through `fn` (the reference's ref_log_to_file or the product's cli_log_to_file) with `directory` as the current
+    directory: (the one file it wrote, relative to `directory`; its content; the content the call returned)"""
     n = len(entries)
     names = (C.c_char_p * n)(*[e[0].encode() for e in entries])
     kinds = (C.c_int * n)(*[e[1] for e in entries])
     svals = (C.c_char_p * n)(*[(e[2] if isinstance(e[2], str) else "").encode() for e in entries])
     dvals = (C.c_double * n)(*[(float(e[2]) if not isinstance(e[2], str) else 0.0) for e in entries])
-    res = {}
-    for tag, fn in (("ref", R.ref_log_to_file), ("own", P.cli_log_to_file)):
-        fn.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.c_char_p, C.c_size_t]
-        d = tmp_path / tag
-        d.mkdir()
-        cwd = os.getcwd()
-        os.chdir(d)
-        try:
-            buf = C.create_string_buffer(1 << 16)
-            assert fn(title.encode(), subdir.encode(), n, names, kinds, svals, dvals, buf, C.sizeof(buf)) == 0
-        finally:
-            os.chdir(cwd)
-        files = sorted(str(p.relative_to(d)) for p in d.rglob("*") if p.is_file())
-        assert len(files) == 1, files
-        res[tag] = (files[0], (d / files[0]).read_text(), buf.value.decode())
+    fn.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.c_char_p, C.c_size_t]
+    cwd = os.getcwd()
+    os.chdir(directory)
+    try:
+        buf = C.create_string_buffer(1 << 16)
+        assert fn(title.encode(), subdir.encode(), n, names, kinds, svals, dvals, buf, C.sizeof(buf)) == 0
+    finally:
+        os.chdir(cwd)
+    files = sorted(str(p.relative_to(directory)) for p in directory.rglob("*") if p.is_file())
+    assert len(files) == 1, files
+    return files[0], (directory / files[0]).read_text(), buf.value.decode()
+
+
+def _log_both(tmp_path, title, subdir, entries):
+    res = {"ref": tuple(_golden()["run_log"]["%s|%s" % (title, subdir)])}
+    d = tmp_path / "own"
+    d.mkdir()
+    res["own"] = run_log(_cli().cli_log_to_file, d, title, subdir, entries)
     return res
 
 
-@pytest.mark.parametrize("title,subdir", [("Cornell Box", ""), ("My Render 01", "runs/Batch A"), ("UPPER lower", "x"), ("t", "a/b/c")])
-def test_run_log_equals_reference_log_context(tmp_path, title, subdir):
-    """The run log as main.cpp:158-160 sets it up and to_file() writes it (log_context.cpp:5-65): directory logs[/<subdir>], file name
-    <epoch ms>_<title>_log.txt lower-cased with blanks as underscores, one `key: value` line per entry in insertion order; integers via
-    to_string, float with 7 and double with 16 significant digits, a key added twice printed twice with its last value, sum_value."""
-    entries = [("image width", 1, 1920), ("image height", 1, 1080), ("scene type", 0, "Cornell Box"), ("# primitives", 2, 42), ("# materials", 2, 7),
+LOG_CASES = [("Cornell Box", ""), ("My Render 01", "runs/Batch A"), ("UPPER lower", "x"), ("t", "a/b/c")]
+LOG_ENTRIES = [("image width", 1, 1920), ("image height", 1, 1080), ("scene type", 0, "Cornell Box"), ("# primitives", 2, 42), ("# materials", 2, 7),
                ("samples per pixel", 1, 1024), ("bounce limit", 1, 16), ("chunk width", 1, 1920), ("chunk total byte size", 2, 1920 * 1080 * 12),
                ("signed", 3, -5), ("a float", 4, 0.1), ("another float", 4, 123456.789), ("tiny float", 4, 1.5e-12), ("huge float", 4, 3.0e30),
                ("total rendering time (seconds)", 5, 0.36143217), ("a double", 5, 1.0 / 3.0), ("big double", 5, 1.0e22), ("whole double", 5, 12.0),
                ("chunk width", 1, 640), ("acc", 6, 1.25), ("acc", 6, 2.5), ("acc", 6, 1e-3), ("scene type", 6, 1.0), ("empty", 0, "")]
-    res = _log_both(tmp_path, title, subdir, entries)
+
+
+@pytest.mark.parametrize("title,subdir", LOG_CASES)
+def test_run_log_equals_reference_log_context(tmp_path, title, subdir):
+    """The run log as main.cpp:158-160 sets it up and to_file() writes it (log_context.cpp:5-65): directory logs[/<subdir>], file name
+    <epoch ms>_<title>_log.txt lower-cased with blanks as underscores, one `key: value` line per entry in insertion order; integers via
+    to_string, float with 7 and double with 16 significant digits, a key added twice printed twice with its last value, sum_value."""
+    res = _log_both(tmp_path, title, subdir, LOG_ENTRIES)
     (rf, rtext, rbuf), (of, otext, obuf) = res["ref"], res["own"]
     strip = lambda f: re.sub(r"(^|/)\d{10,}_", r"\1<ms>_", f)
     assert re.search(r"(^|/)\d{13}_", rf) and re.search(r"(^|/)\d{13}_", of)          # epoch milliseconds lead the name
@@ -205,34 +250,42 @@ def test_run_log_equals_reference_log_context(tmp_path, title, subdir):
     assert strip(rf).endswith("<ms>_" + title.lower().replace(" ", "_") + "_log.txt") and strip(rf).startswith("logs/")
 
 
-def test_bmp_writer_equals_reference_cimg_output(tmp_path):
-    """get_image + save_img of the reference (image/image.cpp:3-18, io/save_image.cpp:8-20; CImg's BMP writer) vs srt_cli::save_img
-    for the same uchar planes: renders/<name>.bmp, the same bytes -- odd widths (row padding), 1 x 1, a gradient, noise."""
-    _build_ref()
-    if not os.path.exists(REF_IMAGE):
-        pytest.skip("oracle/_ref/libref_image.so not built (the reference is not mounted here)")
-    try:
-        R = C.CDLL(REF_IMAGE)
-    except OSError as e:      # (libX11 is a link-time dependency of the vendored CImg.h)
-        pytest.skip("libref_image.so does not load here: %s" % e)
-    P = _cli()
-    up = C.POINTER(C.c_ubyte)
+def bmp_cases():
+    """(width, height, r, g, b planes) of the BMP pin: odd widths (row padding), 1 x 1, a gradient, noise"""
     rng = np.random.default_rng(11)
+    cases = []
     for k, (w, h) in enumerate(((1, 1), (2, 3), (5, 4), (7, 1), (64, 48), (251, 13))):
         planes = [rng.integers(0, 256, w * h, dtype=np.uint8) for _ in range(3)]
         if k == 4:
             planes = [(np.arange(w * h) * (c + 1) % 256).astype(np.uint8) for c in range(3)]
-        name = "img %d.bmp" % k
-        out = {}
-        for tag, fn in (("ref", R.ref_save_image), ("own", P.cli_save_image)):
-            fn.argtypes = [up, up, up, C.c_uint, C.c_uint, C.c_char_p]
-            d = tmp_path / ("%s%d" % (tag, k))
-            d.mkdir()
-            cwd = os.getcwd()
-            os.chdir(d)
-            try:
-                assert fn(planes[0].ctypes.data_as(up), planes[1].ctypes.data_as(up), planes[2].ctypes.data_as(up), w, h, name.encode()) == 0
-            finally:
-                os.chdir(cwd)
-            out[tag] = (d / "renders" / name).read_bytes()
-        assert out["ref"] == out["own"], (w, h, len(out["ref"]), len(out["own"]), out["ref"][:54].hex(), out["own"][:54].hex())
+        cases.append((w, h, planes))
+    return cases
+
+
+def save_image(fn, directory, planes, w, h, name):
+    """renders/<name> as `fn` (the reference's ref_save_image or the product's cli_save_image) writes it below `directory`: its bytes"""
+    up = C.POINTER(C.c_ubyte)
+    fn.argtypes = [up, up, up, C.c_uint, C.c_uint, C.c_char_p]
+    cwd = os.getcwd()
+    os.chdir(directory)
+    try:
+        assert fn(planes[0].ctypes.data_as(up), planes[1].ctypes.data_as(up), planes[2].ctypes.data_as(up), w, h, name.encode()) == 0
+    finally:
+        os.chdir(cwd)
+    return (directory / "renders" / name).read_bytes()
+
+
+def test_bmp_writer_equals_reference_cimg_output(tmp_path):
+    """get_image + save_img of the reference (image/image.cpp:3-18, io/save_image.cpp:8-20; CImg's BMP writer; stored as the sha256,
+    length and 54-byte header of each file) vs srt_cli::save_img for the same uchar planes: renders/<name>.bmp, the same bytes --
+    odd widths (row padding), 1 x 1, a gradient, noise."""
+    P = _cli()
+    golden = _golden()["bmp"]
+    cases = bmp_cases()
+    assert len(golden) == len(cases)
+    for k, ((w, h, planes), ref) in enumerate(zip(cases, golden)):
+        assert (ref["width"], ref["height"]) == (w, h) and ref["planes_sha256"] == inputs_digest(*planes)
+        d = tmp_path / ("own%d" % k)
+        d.mkdir()
+        own = save_image(P.cli_save_image, d, planes, w, h, "img %d.bmp" % k)
+        assert hashlib.sha256(own).hexdigest() == ref["sha256"] and len(own) == ref["length"], (w, h, ref["length"], len(own), ref["header"], own[:54].hex())

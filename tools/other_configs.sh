@@ -3,9 +3,9 @@
 # plus the instrumented phase split and the SQ/TCC counter passes for cfg 4 and cfg 5's scene.
 cd "$GRAFT_REPO_ROOT"
 O=${1:-gpurun_out/r02_other}; mkdir -p $O; OUT=$O/other_configs.jsonl; : > $OUT
-timeout -k 10 300 python bench.py --scene 100 --width 1280 --height 720 --spp 256 --steps 3 --warmup 1 --no-cpu-baseline --no-calibration 2>/dev/null >> $OUT
-timeout -k 10 300 python bench.py --scene 1 --bvh 0 --width 1920 --height 1080 --spp 2048 --steps 2 --warmup 1 --no-cpu-baseline --no-calibration 2>/dev/null >> $OUT
-timeout -k 10 600 python bench.py --scene 101 --width 3840 --height 2160 --spp ${CFG5_SPP:-512} --steps 1 --warmup 0 --no-cpu-baseline --no-calibration 2>/dev/null >> $OUT
+timeout -k 10 300 python bench.py --full --scene 100 --width 1280 --height 720 --spp 256 --steps 3 --warmup 1 --no-cpu-baseline --no-calibration 2>/dev/null >> $OUT
+timeout -k 10 300 python bench.py --full --scene 1 --bvh 0 --width 1920 --height 1080 --spp 2048 --steps 2 --warmup 1 --no-cpu-baseline --no-calibration 2>/dev/null >> $OUT
+timeout -k 10 600 python bench.py --full --scene 101 --width 3840 --height 2160 --spp ${CFG5_SPP:-512} --steps 1 --warmup 0 --no-cpu-baseline --no-calibration 2>/dev/null >> $OUT
 python - $OUT <<'PY'
 import sys, json
 for l in open(sys.argv[1]):

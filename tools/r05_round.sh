@@ -13,9 +13,9 @@ L=$O/lane_ops_per_ray.json
 case $PART in
 A)
   timeout -k 10 600 python -m pytest tests -m gpu -q > $O/gpu_tests.log 2>&1; echo "gpu tests rc=$?"; tail -2 $O/gpu_tests.log
-  timeout -k 10 500 python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
+  timeout -k 10 500 python bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
   bash tools/profile_round.sh $TAG > $O/profile_round.log 2>&1; cp -r gpurun_out/prof_$TAG $O/prof; tail -4 $O/profile_round.log
-  SRT_RCCL_LIB=$PWD/tests/cpp/_build/libmock_rccl.so SRT_COMM_TEST_SAME_DEVICE=1 SRT_TEST_KNOBS=1 timeout -k 10 300 python bench.py --gpus 2 --steps 2 --warmup 1 --no-cpu-baseline --no-calibration --cfg5-spp 64 > $O/bench_gpus2_rehearsal.json 2> $O/bench_gpus2_rehearsal.err; echo "bench --gpus 2 (rehearsal, one GPU, test transport) rc=$?"
+  SRT_RCCL_LIB=$PWD/tests/cpp/_build/libmock_rccl.so SRT_COMM_TEST_SAME_DEVICE=1 SRT_TEST_KNOBS=1 timeout -k 10 300 python bench.py --full --gpus 2 --steps 2 --warmup 1 --no-cpu-baseline --no-calibration --cfg5-spp 64 > $O/bench_gpus2_rehearsal.json 2> $O/bench_gpus2_rehearsal.err; echo "bench --gpus 2 (rehearsal, one GPU, test transport) rc=$?"
   ;;
 B)
   bash tools/pmc_passes.sh $O/pmc_cfg3 > $O/pmc_cfg3.log 2>&1
@@ -38,7 +38,7 @@ D)
   timeout -k 10 300 python tools/diag.py --scene 101 --width 3840 --height 2160 --spp 128 --reps 1 > $O/diag_cfg5_128spp.json 2>&1
   timeout -k 10 300 python tools/diag.py --spp 64 > $O/diag_cfg3_64spp.json 2>&1
   timeout -k 10 500 python tools/world_emulation.py --worlds 1,2,4,8 --reps 3 2>&1 | grep -v amdgpu.ids > $O/world_emulation_cfg3.txt; grep "^world" $O/world_emulation_cfg3.txt
-  timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --rehearse-gloo --spp 64 --steps 2 --warmup 1 --cfg5-spp 16 --cfg5-size 640x360 > $O/bench_torchrun2_gloo_rehearsal.json 2> $O/bench_torchrun2_gloo_rehearsal.err; echo "torchrun rehearsal rc=$?"
+  timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --rehearse-gloo --spp 64 --steps 2 --warmup 1 --cfg5-spp 16 --cfg5-size 640x360 > $O/bench_torchrun2_gloo_rehearsal.json 2> $O/bench_torchrun2_gloo_rehearsal.err; echo "torchrun rehearsal rc=$?"
   ;;
 E)
   # cfg 5 as specified on one rank of eight (all eight, one after the other) and on one GPU: the strong-scaling emulation of the largest configuration
