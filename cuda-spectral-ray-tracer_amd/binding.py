@@ -97,6 +97,9 @@ PROTOTYPES = {
     "srt_set_partition": (_i, [_vp, _u32, _u32]),
     "srt_render_chunk": (_i, [_vp, _u32, _u32, _u32, _u32, _vp]),
     "srt_synchronize": (_i, [_vp]),
+    "srt_accum_reset": (_i, [_vp]),
+    "srt_render_chunk_accum": (_i, [_vp, _u32, _u32, _u32, _u32, _u32, _vp]),
+    "srt_accum_samples": (_i, [_vp, C.POINTER(_u32)]),
     "srt_set_gather_planes": (_i, [_vp, _u32]),
     "srt_tile_buffer": (_i, [_vp, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_u32), C.POINTER(_u32)]),
     "srt_copy_tile_buffer": (_i, [_vp, _vp, _vp]),
@@ -132,6 +135,8 @@ PROTOTYPES = {
     "srt_comm_set_camera": (_i, [_vp, C.POINTER(CameraData)]),
     "srt_comm_init_device_params": (_i, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u64]),
     "srt_render_frame_multi": (_i, [_vp, _u32, _u32, _u32, _u32]),
+    "srt_comm_accum_reset": (_i, [_vp]),
+    "srt_render_frame_multi_accum": (_i, [_vp, _u32, _u32, _u32, _u32, _u32]),
     "srt_comm_synchronize": (_i, [_vp]),
     "srt_comm_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_f)]),
 }

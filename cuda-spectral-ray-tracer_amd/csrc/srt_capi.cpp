@@ -84,6 +84,13 @@ struct srt_ctx {
     uint32_t *d_wave_debug = nullptr;                   // instrumented launches: 4 words per wave
     uint32_t wave_debug_waves = 0;
     uint32_t rowmajor_w = 0, rowmajor_h = 0;
+    uint32_t stats_spp = 0;                             // samples per pixel of the last launch when it was an accumulating pass (0: c->spp)
+    // progressive rendering (srt_render_chunk_accum): [AccumHeader | pad to 256 B | three planes of n_lanes floats], allocated on first use
+    char *d_accum = nullptr;
+    uint64_t accum_lanes = 0;                           // lanes d_accum's planes hold
+    enum { kAccumInvalid, kAccumEmpty, kAccumBound } accum_state = kAccumInvalid;   // Empty: reset, no pass yet; Bound: passes of one chunk
+    uint32_t accum_total = 0;                           // samples per pixel in the sums
+    uint32_t accum_w = 0, accum_h = 0, accum_offx = 0, accum_offy = 0;   // the chunk of the first pass
 };
 
 namespace {
@@ -206,7 +213,7 @@ void srt_destroy(srt_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    void *bufs[] = {c->d_nodes, c->d_nodes_sw, c->d_fringe, c->d_tris, c->d_mat_sd, c->d_mat_par, c->d_shade, c->d_cmf, c->d_rng, c->d_fb, c->d_tiles, c->d_counters, c->d_tile_cost, c->d_tile_order, c->d_rowmajor, c->d_wave_debug};
+    void *bufs[] = {c->d_nodes, c->d_nodes_sw, c->d_fringe, c->d_tris, c->d_mat_sd, c->d_mat_par, c->d_shade, c->d_cmf, c->d_rng, c->d_fb, c->d_tiles, c->d_counters, c->d_tile_cost, c->d_tile_order, c->d_rowmajor, c->d_wave_debug, c->d_accum};
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -220,6 +227,7 @@ const char *srt_last_error(const srt_ctx *ctx) { return ctx ? ctx->err.c_str() :
 
 int srt_upload_scene(srt_ctx *c, const srt_scene *s) {
     if (!c || !s) return fail(c, SRT_ERR_INVALID, "srt_upload_scene: null argument");
+    c->accum_state = srt_ctx::kAccumInvalid;
     HIP_TRY(c, hipSetDevice(c->device));
     FlatScene f;
     int rc = flatten_scene(*s, f);
@@ -261,6 +269,7 @@ int srt_upload_scene(srt_ctx *c, const srt_scene *s) {
 
 int srt_set_camera(srt_ctx *c, const srt_camera_data *cam) {
     if (!c || !cam) return fail(c, SRT_ERR_INVALID, "srt_set_camera: null argument");
+    c->accum_state = srt_ctx::kAccumInvalid;
     c->cam = *cam;
     c->camera_ready = true;
     return SRT_OK;
@@ -318,6 +327,7 @@ int srt_internal_init_device_params(srt_ctx *c, uint32_t tx, uint32_t ty, uint32
     if (!c) return fail(c, SRT_ERR_INVALID, "srt_init_device_params: null ctx");
     if (tx == 0 || ty == 0 || bx == 0 || by == 0 || chunk_w == 0 || chunk_h == 0)
         return fail(c, SRT_ERR_INVALID, "srt_init_device_params: zero dimension");
+    c->accum_state = srt_ctx::kAccumInvalid;
     const uint64_t lanes = (uint64_t)tx * ty * bx * by;
     if (lanes > 0x7fffffffull) return fail(c, SRT_ERR_INVALID, "srt_init_device_params: grid too large");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -347,6 +357,7 @@ int srt_init_device_params(srt_ctx *c, uint32_t tx, uint32_t ty, uint32_t bx, ui
 
 int srt_set_partition(srt_ctx *c, uint32_t rank, uint32_t world) {
     if (!c || world == 0 || rank >= world) return fail(c, SRT_ERR_INVALID, "srt_set_partition: need rank < world");
+    c->accum_state = srt_ctx::kAccumInvalid;
     c->rank = rank; c->world = world;
     return SRT_OK;
 }
@@ -359,14 +370,15 @@ int srt_set_gather_planes(srt_ctx *c, uint32_t planes) {
     return SRT_OK;
 }
 
-int srt_render_chunk(srt_ctx *c, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy, void *stream) {
-    if (!c) return fail(c, SRT_ERR_INVALID, "srt_render_chunk: null ctx");
-    // reference: "Device parameters were not initialized, render aborted" (rendering.cu:247-250)
-    if (!c->scene_ready || !c->camera_ready || !c->params_ready)
-        return fail(c, SRT_ERR_INVALID, "srt_render_chunk: scene, camera and device parameters must be set first");
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t st = (hipStream_t)stream;
-    width = (uint16_t)width; height = (uint16_t)height; offx = (uint16_t)offx; offy = (uint16_t)offy;   // rendering.cu:245 (Q17)
+}  // extern "C"
+
+namespace {
+
+// srt_render_chunk's body.  spp_add == 0: a plain launch of c->spp samples (MODE 0, or MODE 1 when counting); spp_add > 0: an
+// accumulating pass of spp_add samples (MODE 3) whose caller has checked the accumulation and enqueued its header.
+// width .. offy are already narrowed to 16 bit.
+int render_chunk_impl(srt_ctx *c, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy, uint32_t spp_add, hipStream_t st) {
+    const bool accum = spp_add != 0;
     c->last_w = width; c->last_h = height; c->last_offx = offx; c->last_offy = offy;
     // Tiles cover every pixel the reference grid can address, whatever the size of THIS chunk: the tile number of a lane
     // idx -- and with it the rank that owns the lane's persistent RNG stream (Q13) -- must not move when a ragged edge
@@ -387,6 +399,7 @@ int srt_render_chunk(srt_ctx *c, uint32_t width, uint32_t height, uint32_t offx,
     HIP_TRY(c, hipMemsetAsync(c->d_counters, 0, (kCounters + 1) * sizeof(unsigned long long), st));
     RenderParams p;
     fill_params(c, p);
+    if (accum) p.spp = spp_add;      // the samples this pass adds (the running total is in the header)
     p.width = width; p.height = height; p.offx = offx; p.offy = offy;
     p.tiles_x = c->tiles_x; p.tiles_y = c->tiles_y; p.n_tiles = c->n_tiles;
     p.tiles_local = c->tiles_local;
@@ -410,8 +423,19 @@ int srt_render_chunk(srt_ctx *c, uint32_t width, uint32_t height, uint32_t offx,
     // (longest-processing-time-first), the most expensive ones split over several waves when the launch is chain-bound.
     p.tile_order = nullptr; p.tile_cost = nullptr; p.queue_rows = nullptr; p.queue_rows_bound = c->tiles_local;
     p.debug_lane_limit = c->debug_lane_limit;
-    const bool ordered = c->probe_spp > 0 && c->spp > 4 * c->probe_spp && c->tiles_local > 1 && c->tiles_local <= 0x3fffffu;   // 22-bit tile field of a queue row
-    if (ordered) {
+    // (accumulating passes: the probe runs on the FIRST pass whatever its sample count -- short passes would otherwise run an unordered
+    // queue -- and the later passes of the accumulation reuse its queue: a tile's cost depends on its geometry, not on the sample index,
+    // and nothing else writes the schedule buffers before the accumulation is invalidated)
+    const bool schedulable = c->probe_spp > 0 && c->tiles_local > 1 && c->tiles_local <= 0x3fffffu;   // 22-bit tile field of a queue row
+    const bool ordered = schedulable && (accum || c->spp > 4 * c->probe_spp);
+    const bool reuse_order = ordered && accum && c->accum_state == srt_ctx::kAccumBound;
+    if (reuse_order) {
+        uint32_t *rows = c->d_tile_order, *sorted = rows + (size_t)c->tile_sched_capacity * 64, *queue_info = sorted + c->tile_sched_capacity;
+        p.tile_order = rows;
+        p.queue_rows = queue_info;
+        p.prio_cost = c->d_tile_cost;
+        if (c->split_load_pct) p.queue_rows_bound = (uint32_t)std::min<uint64_t>((uint64_t)c->tiles_local * 64, 0x7fffffffull);
+    } else if (ordered) {
         if (c->tiles_local > c->tile_sched_capacity) {
             if (c->d_tile_cost) { (void)hipFree(c->d_tile_cost); c->d_tile_cost = nullptr; }
             if (c->d_tile_order) { (void)hipFree(c->d_tile_order); c->d_tile_order = nullptr; }
@@ -453,12 +477,84 @@ int srt_render_chunk(srt_ctx *c, uint32_t width, uint32_t height, uint32_t offx,
     RoctxRange range_render("srt render_kernel");
     HIP_TRY(c, hipEventRecord(c->ev0, st));     // ev0..ev1 bracket the render kernel alone (roofline.achieved)
     uint32_t waves_launched = 0;
-    HIP_TRY(c, launch_render(p, c->knobs, (uint32_t)c->n_cu, c->count_traversal ? 1 : 0, st, &waves_launched));
+    if (accum) p.wave_debug = reinterpret_cast<uint32_t *>(c->d_accum);      // MODE 3 reads its AccumHeader there
+    HIP_TRY(c, launch_render(p, c->knobs, (uint32_t)c->n_cu, accum ? 3 : (c->count_traversal ? 1 : 0), st, &waves_launched));
     if (c->count_traversal && waves_launched > c->wave_debug_waves)
         return fail(c, SRT_ERR_HIP, "srt_render_chunk: the launch started more waves than the debug buffer holds (launch plan and launcher disagree)");
     HIP_TRY(c, hipEventRecord(c->ev1, st));
     c->timed = true;
     c->last_paths = 0;   // filled by srt_get_stats from the tile ownership
+    c->stats_spp = spp_add;
+    return SRT_OK;
+}
+
+constexpr size_t kAccumHeaderBytes = 256;      // the sum planes start behind the header, 256-byte aligned
+
+}  // namespace
+
+extern "C" {
+
+int srt_render_chunk(srt_ctx *c, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy, void *stream) {
+    if (!c) return fail(c, SRT_ERR_INVALID, "srt_render_chunk: null ctx");
+    // reference: "Device parameters were not initialized, render aborted" (rendering.cu:247-250)
+    if (!c->scene_ready || !c->camera_ready || !c->params_ready)
+        return fail(c, SRT_ERR_INVALID, "srt_render_chunk: scene, camera and device parameters must be set first");
+    c->accum_state = srt_ctx::kAccumInvalid;      // its launch moves the RNG streams (and may rewrite the pixel queue) behind the sums
+    HIP_TRY(c, hipSetDevice(c->device));
+    width = (uint16_t)width; height = (uint16_t)height; offx = (uint16_t)offx; offy = (uint16_t)offy;   // rendering.cu:245 (Q17)
+    return render_chunk_impl(c, width, height, offx, offy, 0u, (hipStream_t)stream);
+}
+
+int srt_accum_reset(srt_ctx *c) {
+    if (!c) return fail(c, SRT_ERR_INVALID, "srt_accum_reset: null ctx");
+    if (!c->params_ready) return fail(c, SRT_ERR_INVALID, "srt_accum_reset: device parameters must be set first (srt_init_device_params)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->accum_state = srt_ctx::kAccumInvalid;
+    const uint64_t lanes = c->n_lanes;
+    if (!c->d_accum || c->accum_lanes != lanes) {
+        if (c->d_accum) { HIP_TRY(c, hipDeviceSynchronize()); (void)hipFree(c->d_accum); c->d_accum = nullptr; c->accum_lanes = 0; }
+        HIP_TRY(c, hipMalloc((void **)&c->d_accum, kAccumHeaderBytes + 3 * lanes * sizeof(float)));
+        c->accum_lanes = lanes;
+    }
+    // (null stream, then a wait: a pass on any stream of the caller's finds the sums zeroed)
+    HIP_TRY(c, hipMemset(c->d_accum + kAccumHeaderBytes, 0, 3 * lanes * sizeof(float)));
+    HIP_TRY(c, hipDeviceSynchronize());
+    c->accum_total = 0;
+    c->accum_state = srt_ctx::kAccumEmpty;
+    return SRT_OK;
+}
+
+int srt_accum_samples(const srt_ctx *c, uint32_t *spp_total) {
+    if (!c || !spp_total) return fail(nullptr, SRT_ERR_INVALID, "srt_accum_samples: null argument");
+    *spp_total = c->accum_state == srt_ctx::kAccumInvalid ? 0u : c->accum_total;
+    return SRT_OK;
+}
+
+int srt_render_chunk_accum(srt_ctx *c, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy, uint32_t spp_add, void *stream) {
+    if (!c) return fail(c, SRT_ERR_INVALID, "srt_render_chunk_accum: null ctx");
+    // every refusal comes before anything is enqueued: a refused pass leaves sums, RNG state and framebuffer as they were
+    if (!c->scene_ready || !c->camera_ready || !c->params_ready)
+        return fail(c, SRT_ERR_INVALID, "srt_render_chunk_accum: scene, camera and device parameters must be set first");
+    if (c->count_traversal)
+        return fail(c, SRT_ERR_UNSUPPORTED, "srt_render_chunk_accum: no instrumented accumulating kernel (srt_set_count_traversal(ctx, 0) first)");
+    if (c->accum_state == srt_ctx::kAccumInvalid)
+        return fail(c, SRT_ERR_INVALID, "srt_render_chunk_accum: no accumulation (srt_accum_reset first; scene, camera, device parameters, partition "
+                                        "and a plain srt_render_chunk invalidate it)");
+    if (spp_add == 0) return fail(c, SRT_ERR_INVALID, "srt_render_chunk_accum: spp_add must be > 0");
+    if ((uint64_t)c->accum_total + spp_add > 0xffffu)
+        return fail(c, SRT_ERR_INVALID, "srt_render_chunk_accum: the total would exceed 65535 samples per pixel (16-bit spp, Q17)");
+    width = (uint16_t)width; height = (uint16_t)height; offx = (uint16_t)offx; offy = (uint16_t)offy;   // rendering.cu:245 (Q17)
+    if (c->accum_state == srt_ctx::kAccumBound && (width != c->accum_w || height != c->accum_h || offx != c->accum_offx || offy != c->accum_offy))
+        return fail(c, SRT_ERR_INVALID, "srt_render_chunk_accum: the accumulation belongs to another chunk (one accumulation per context)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    // (the header travels by value in the arguments of a one-lane kernel on the pass's stream: stream-ordered, no host buffer to keep alive)
+    HIP_TRY(c, launch_accum_header(reinterpret_cast<AccumHeader *>(c->d_accum), reinterpret_cast<float *>(c->d_accum + kAccumHeaderBytes), c->accum_total + spp_add, st));
+    const int rc = render_chunk_impl(c, width, height, offx, offy, spp_add, st);
+    if (rc != SRT_OK) { c->accum_state = srt_ctx::kAccumInvalid; return rc; }      // (a launch that failed half-way leaves the sums undefined)
+    c->accum_total += spp_add;
+    c->accum_w = width; c->accum_h = height; c->accum_offx = offx; c->accum_offy = offy;
+    c->accum_state = srt_ctx::kAccumBound;
     return SRT_OK;
 }
 
@@ -594,7 +690,7 @@ int srt_get_stats(srt_ctx *c, srt_stats *out) {
         const uint32_t w = tx0 < lim_w ? std::min<uint32_t>(8, lim_w - tx0) : 0, hgt = ty0 < lim_h ? std::min<uint32_t>(8, lim_h - ty0) : 0;
         pixels += (uint64_t)w * hgt;
     }
-    out->paths = pixels * c->spp;
+    out->paths = pixels * (c->stats_spp ? c->stats_spp : c->spp);
     return SRT_OK;
 }
 
@@ -621,6 +717,7 @@ int srt_order_children_by_profile(srt_ctx *c, srt_scene *s, uint32_t width, uint
                                   uint32_t min_samples, uint32_t *n_swapped) {
     if (n_swapped) *n_swapped = 0;
     if (!c || !s || !s->bvh_valid) return fail(c, SRT_ERR_INVALID, "srt_order_children_by_profile: null argument / BVH not built");
+    c->accum_state = srt_ctx::kAccumInvalid;
     if (!c->camera_ready) return fail(c, SRT_ERR_INVALID, "srt_order_children_by_profile: set the camera first (srt_set_camera)");
     if (width == 0 || height == 0 || spp == 0) return fail(c, SRT_ERR_INVALID, "srt_order_children_by_profile: empty probe frame");
     const size_t n_nodes = s->nodes.size(), n_tris = s->raw.size();

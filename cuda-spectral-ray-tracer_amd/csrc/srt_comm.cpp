@@ -270,11 +270,15 @@ int srt_comm_init_device_params(srt_comm *c, uint32_t tx, uint32_t ty, uint32_t 
     return SRT_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
 // render_manager::step's device half for W GPUs: every local rank renders its tiles on its own stream, ONE gather brings
 // the compact tile buffers to rank 0, rank 0 scatters them into its block-linear framebuffer.  Asynchronous: returns once
-// everything is enqueued; srt_comm_synchronize waits.
-int srt_render_frame_multi(srt_comm *c, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy) {
-    if (!c) return cfail(c, SRT_ERR_INVALID, "srt_render_frame_multi: null comm");
+// everything is enqueued; srt_comm_synchronize waits.  spp_add > 0: every rank makes an accumulating pass (srt_render_chunk_accum)
+// instead of a plain launch; the exchange is the same.
+int render_frame_multi(srt_comm *c, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy, uint32_t spp_add) {
     RcclApi &R = rccl();
     const size_t n_local = c->ctx.size();
     if (c->world > 1 && !c->owns_ctx) {
@@ -296,7 +300,8 @@ int srt_render_frame_multi(srt_comm *c, uint32_t width, uint32_t height, uint32_
         c->gather_planes = mine;
     }
     for (size_t i = 0; i < n_local; i++) {
-        int rc = srt_render_chunk(c->ctx[i], width, height, offx, offy, c->stream[i]);
+        int rc = spp_add ? srt_render_chunk_accum(c->ctx[i], width, height, offx, offy, spp_add, c->stream[i])
+                         : srt_render_chunk(c->ctx[i], width, height, offx, offy, c->stream[i]);
         if (rc != SRT_OK) return cfail(c, rc, srt_last_error(c->ctx[i]));
     }
     // every rank's exchange unit has the same size: tiles_padded * gather_planes * 64 floats (the first plane groups of its buffer)
@@ -336,6 +341,27 @@ int srt_render_frame_multi(srt_comm *c, uint32_t width, uint32_t height, uint32_
         COMM_HIP(c, hipEventRecord(c->ev_g1[i], c->stream[i]));
     }
     c->gather_timed = true;
+    return SRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int srt_render_frame_multi(srt_comm *c, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy) {
+    if (!c) return cfail(c, SRT_ERR_INVALID, "srt_render_frame_multi: null comm");
+    return render_frame_multi(c, width, height, offx, offy, 0u);
+}
+
+int srt_render_frame_multi_accum(srt_comm *c, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy, uint32_t spp_add) {
+    if (!c) return cfail(c, SRT_ERR_INVALID, "srt_render_frame_multi_accum: null comm");
+    if (spp_add == 0) return cfail(c, SRT_ERR_INVALID, "srt_render_frame_multi_accum: spp_add must be > 0");
+    return render_frame_multi(c, width, height, offx, offy, spp_add);
+}
+
+int srt_comm_accum_reset(srt_comm *c) {
+    if (!c) return cfail(c, SRT_ERR_INVALID, "srt_comm_accum_reset: null comm");
+    for (srt_ctx *x : c->ctx) { int rc = srt_accum_reset(x); if (rc != SRT_OK) return cfail(c, rc, srt_last_error(x)); }
     return SRT_OK;
 }
 

@@ -81,6 +81,17 @@ struct OrderProfile {
 };
 constexpr unsigned long long kOrderProfileMagic = 0x5352544f52444552ull;
 
+// Accumulating launch (render_kernel MODE 3, srt_render_chunk_accum): RenderParams::wave_debug -- which no other production launch
+// reads -- points at this header instead of the instrumented build's OrderProfile, so that RenderParams and with it the machine code of
+// the plain production kernels stay as they are.  sums: three planes of n_lanes floats (X, Y, Z), indexed by the block-linear idx like
+// the RNG planes; a pixel starts from its stored sum and stores it back when its samples of the pass are done.  spp_total: the samples
+// per pixel the sums hold after this pass (the normalisation of the written framebuffer).
+struct AccumHeader {
+    float *sums;
+    uint32_t spp_total;
+    uint32_t pad;
+};
+
 struct ScatterParams {
     const float *gathered;     // [rank][group (groups of them)][tiles_padded][plane of the group][lane]
     uint32_t groups;           // 1: only the quantised framebuffer was gathered (12 B / pixel); 3: the parity planes too
@@ -94,8 +105,9 @@ hipError_t launch_init_rng(uint32_t *rng, uint32_t n_lanes, uint64_t seed, hipSt
 // Test knobs of a context (srt_set_test_knobs; from the environment only under SRT_TEST_KNOBS=1, read once at srt_create): they pick
 // the kernel variant / cache size a launch plan would not pick by itself, so that every instantiated variant can be held to the CPU oracle by the tests.
 struct PlanKnobs { bool wide_refs = false; int lds_cache_max = -1; };
-// mode 0 render, 1 instrumented, 2 cost probe; waves_launched (optional) = persistent waves of the launch
+// mode 0 render, 1 instrumented, 2 cost probe, 3 accumulating render (p.wave_debug -> AccumHeader); waves_launched (optional) = persistent waves of the launch
 hipError_t launch_render(const RenderParams &p, const PlanKnobs &knobs, uint32_t n_cu, int mode, hipStream_t st, uint32_t *waves_launched = nullptr);
+hipError_t launch_accum_header(AccumHeader *dst, float *sums, uint32_t spp_total, hipStream_t st);      // writes *dst on the stream
 hipError_t launch_order_tiles(const uint32_t *cost, uint32_t *sorted, uint32_t *rows, uint32_t n, uint32_t n_waves,
                               uint32_t split_load_pct, uint32_t *queue_info, uint32_t order_max_pct, hipStream_t st);
 hipError_t launch_scatter(const ScatterParams &p, hipStream_t st);

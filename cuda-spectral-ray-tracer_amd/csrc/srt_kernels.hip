@@ -133,7 +133,9 @@ __global__ void init_rng_kernel(uint32_t *rng, uint32_t n_lanes, uint64_t seed) 
 // out by one wave-aggregated atomic per refill; which lane renders a pixel has no influence on the result (the RNG
 // stream belongs to the pixel).
 // MODE 0: production; MODE 1: instrumented (counts V / T / utilisation); MODE 2: cost probe -- renders P.spp samples per
-// pixel from a COPY of the RNG state, writes nothing but the per-tile traversal cost used to order the pixel queue.
+// pixel from a COPY of the RNG state, writes nothing but the per-tile traversal cost used to order the pixel queue.  MODE 3:
+// production that accumulates across launches -- a pixel starts from its stored XYZ sum instead of zero, stores the sum back when its
+// P.spp samples are done and normalises by the running total (AccumHeader behind P.wave_debug, srt_render_chunk_accum); the rest is MODE 0.
 // ALL_CACHED: the whole inner tree fits the LDS cache (n_cached == n_inner): the INNER step has no global fall-back path.
 // PAIRED (instantiated for <., 1, 1> and <., 0, 0>): every FRINGE record holds two triangles (srt_scene_is_paired): the visit has no box test.
 template <int MODE, bool NARROW, bool ALL_CACHED, bool PAIRED>
@@ -141,6 +143,7 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
     constexpr bool COUNT = (MODE == 1);
     constexpr bool PROBE = (MODE == 2);
     constexpr bool ITERS = COUNT || PROBE;
+    constexpr bool ACCUM = (MODE == 3);
     extern __shared__ float4 lds4[];
     lds_uniforms *U = (lds_uniforms *)lds4;
     float4 *s_cmf = lds4 + kLdsUniF4;
@@ -171,6 +174,11 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
         U->first_row_taken = 0u;
         split_ptr(P.prio_cost, U->prio_cost);
         U->prio_full = __float_as_uint(P.queue_rows && P.prio_cost ? (float)P.queue_rows[1] * (float)P.spp : 0.f);
+        if constexpr (ACCUM) {
+            const AccumHeader *ah = reinterpret_cast<const AccumHeader *>(P.wave_debug);
+            split_ptr(ah->sums, U->accum_sums);
+            U->spp_total = ah->spp_total;
+        }
     }
     for (uint32_t k = threadIdx.x; k < kLdsCmfF4; k += blockDim.x) s_cmf[k] = P.cmf[k];
     for (uint32_t k = threadIdx.x; k < nc; k += blockDim.x) {
@@ -408,8 +416,14 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
                         rng[0 * nl + idx] = rs.d; rng[1 * nl + idx] = rs.v0; rng[2 * nl + idx] = rs.v1;
                         rng[3 * nl + idx] = rs.v2; rng[4 * nl + idx] = rs.v3; rng[5 * nl + idx] = rs.v4;
                     }
+                    if constexpr (ACCUM) {      // the running sum goes back to its planes: the next pass continues it
+                        float *sums = join_ptr<float>(U->accum_sums[0], U->accum_sums[1]);
+                        const size_t nl = U->n_lanes;
+                        sums[0 * nl + idx] = acc.x; sums[1 * nl + idx] = acc.y; sums[2 * nl + idx] = acc.z;
+                    }
                     // pixel_color / float(spp) -> (1/spp) * v ; XYZ_to_sRGB (color.cu:35-41, vec3.cuh:80-91)
-                    const float inv_spp = 1.0f / (float)spp;
+                    // (accumulating: the sum holds spp_total samples, of which this launch drew the last P.spp)
+                    const float inv_spp = 1.0f / (float)(ACCUM ? U->spp_total : spp);
                     const V3 c = inv_spp * acc;
                     const float r_lin = (SRT_XYZ2RGB_00 * c.x) + (SRT_XYZ2RGB_01 * c.y) + (SRT_XYZ2RGB_02 * c.z);
                     const float g_lin = (SRT_XYZ2RGB_10 * c.x) + (SRT_XYZ2RGB_11 * c.y) + (SRT_XYZ2RGB_12 * c.z);
@@ -495,7 +509,13 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
                                 rs.d = rng[0 * nl + idx]; rs.v0 = rng[1 * nl + idx]; rs.v1 = rng[2 * nl + idx];
                                 rs.v2 = rng[3 * nl + idx]; rs.v3 = rng[4 * nl + idx]; rs.v4 = rng[5 * nl + idx];
                             }
-                            acc = mk(0.f, 0.f, 0.f);
+                            if constexpr (ACCUM) {      // continue the pixel's sum of the earlier passes (zero after srt_accum_reset)
+                                const float *sums = join_ptr<const float>(U->accum_sums[0], U->accum_sums[1]);
+                                const size_t nl = U->n_lanes;
+                                acc = mk(sums[0 * nl + idx], sums[1 * nl + idx], sums[2 * nl + idx]);
+                            } else {
+                                acc = mk(0.f, 0.f, 0.f);
+                            }
                             sample = 0;
                             if (PROBE) { cur_tile_local = tile_local; pixel_iters0 = ts.n_iters; }
                             if (COUNT) { pixel_iters0 = ts.n_iters; pixel_rays0 = n_rays; }
@@ -1039,7 +1059,9 @@ hipError_t launch_render(const RenderParams &p, const PlanKnobs &knobs, uint32_t
     const bool narrow = render_narrow_refs(p.n_records, knobs);
     if (mode == 1) return narrow ? launch_render_mode<1, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<1, false>(p, knobs, n_cu, st, waves_launched);
     if (mode == 2) return narrow ? launch_render_mode<2, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<2, false>(p, knobs, n_cu, st, waves_launched);
-    return narrow ? launch_render_mode<0, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<0, false>(p, knobs, n_cu, st, waves_launched);
+    if (mode != 3) return narrow ? launch_render_mode<0, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<0, false>(p, knobs, n_cu, st, waves_launched);
+    // (instantiated after the production variants: their place in the object, and so the labels of their ISA listing, stay as they were)
+    return narrow ? launch_render_mode<3, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<3, false>(p, knobs, n_cu, st, waves_launched);
 }
 
 hipError_t launch_order_tiles(const uint32_t *cost, uint32_t *sorted, uint32_t *rows, uint32_t n, uint32_t n_waves,
@@ -1075,6 +1097,18 @@ hipError_t launch_trace(const RenderParams &p, const float *rays, size_t n, floa
 hipError_t launch_op_sweep(int which, const float *a, const float *b, size_t n, float *out, hipStream_t st) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(op_sweep_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, which, a, b, (uint32_t)n, out);
+    return hipGetLastError();
+}
+
+// The header of an accumulating launch (AccumHeader, srt_render_chunk_accum), written on the pass's stream.  (A template, instantiated
+// here at the end of the unit: a plain kernel would be emitted ahead of the render kernels and renumber the labels of their ISA listing.)
+template <int>
+__global__ void accum_header_kernel(AccumHeader *dst, float *sums, uint32_t spp_total) {
+    if (threadIdx.x == 0) { dst->sums = sums; dst->spp_total = spp_total; dst->pad = 0u; }
+}
+
+hipError_t launch_accum_header(AccumHeader *dst, float *sums, uint32_t spp_total, hipStream_t st) {
+    hipLaunchKernelGGL(accum_header_kernel<0>, dim3(1), dim3(64), 0, st, dst, sums, spp_total);
     return hipGetLastError();
 }
 

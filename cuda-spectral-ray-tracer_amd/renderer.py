@@ -84,6 +84,22 @@ class Renderer:
     def synchronize(self):
         self._ck(B.lib().srt_synchronize(self._h))
 
+    def accum_reset(self):
+        """start a progressive accumulation: zero the per-pixel XYZ sums and the sample total (the RNG streams are not re-seeded)"""
+        self._ck(B.lib().srt_accum_reset(self._h))
+
+    def render_chunk_accum(self, width, height, spp_add, offx=0, offy=0, stream=None):
+        """add spp_add samples per pixel to the accumulation and write the running mean to the tile buffer (srt_c_api.h): after
+        accum_reset, passes of s1 .. sk samples equal one render_chunk of s1 + .. + sk samples bit for bit"""
+        self._ck(B.lib().srt_render_chunk_accum(self._h, width, height, offx, offy, spp_add, C.c_void_p(stream or 0)))
+
+    @property
+    def accum_samples(self):
+        """samples per pixel the accumulation holds (0 after accum_reset, or when there is none)"""
+        n = C.c_uint32()
+        self._ck(B.lib().srt_accum_samples(self._h, C.byref(n)))
+        return n.value
+
     def set_gather_planes(self, planes):
         """3 (default): the exchange unit is the quantised framebuffer; 9: + the parity planes (unquantised sRGB, XYZ sums)"""
         self._ck(B.lib().srt_set_gather_planes(self._h, planes))
@@ -281,6 +297,14 @@ class Comm:
     def render_frame(self, width, height, offx=0, offy=0):
         self._ck(B.lib().srt_render_frame_multi(self._h, width, height, offx, offy))
 
+    def accum_reset(self):
+        """Renderer.accum_reset on every local rank"""
+        self._ck(B.lib().srt_comm_accum_reset(self._h))
+
+    def render_frame_accum(self, width, height, spp_add, offx=0, offy=0):
+        """render_frame with an accumulating pass of spp_add samples on every rank (Renderer.render_chunk_accum)"""
+        self._ck(B.lib().srt_render_frame_multi_accum(self._h, width, height, offx, offy, spp_add))
+
     def synchronize(self):
         self._ck(B.lib().srt_comm_synchronize(self._h))
 
@@ -349,3 +373,51 @@ def render_image(scene, cam, width, height, spp, bounce_limit, seed=1984, device
     if renderer is None:
         r.close()
     return out
+
+
+MAX_SPP = 65535      # the reference's spp is a short_uint (Q17): a progressive total cannot pass it either
+
+
+def progressive_schedule(passes):
+    """the samples of every pass as a list of ints, checked: at least one pass, every pass > 0, total <= MAX_SPP"""
+    sched = [int(s) for s in passes]
+    if not sched:
+        raise ValueError("render_progressive: empty schedule (give the samples of at least one pass)")
+    if any(s <= 0 for s in sched) or any(s != p for s, p in zip(sched, passes)):
+        raise ValueError("render_progressive: every pass must add a positive whole number of samples, got %r" % (list(passes),))
+    if sum(sched) > MAX_SPP:
+        raise ValueError("render_progressive: %d samples in all, more than %d (16-bit spp)" % (sum(sched), MAX_SPP))
+    return sched
+
+
+def render_progressive(scene, cam, width, height, passes, bounce_limit, seed=1984, device=0, renderer=None):
+    """Progressive whole-image render on one GPU: a generator that renders passes[0], passes[1], ... samples per pixel into one
+    accumulation and yields (spp_total, result) after each pass, `result` with the keys of render_image.  After the pass that
+    brings the total to N the result is bit-identical to render_image(..., spp=N, ...) (srt_render_chunk_accum).  The schedule is
+    checked here, when the generator is made, before any device is touched."""
+    sched = progressive_schedule(passes)
+    return _progressive_passes(scene, cam, width, height, sched, bounce_limit, seed, device, renderer)
+
+
+def _progressive_passes(scene, cam, width, height, sched, bounce_limit, seed, device, renderer):
+    r = renderer or Renderer(device)
+    planes_before = r.gather_planes
+    try:
+        r.upload_scene(scene)
+        r.set_camera(cam)
+        r.init_device_params(width, height, sum(sched), bounce_limit, seed)
+        r.set_partition(0, 1)
+        r.set_count_traversal(False)
+        r.set_gather_planes(9)            # the parity planes (unquantised sRGB, XYZ sums) are part of what this returns
+        r.accum_reset()
+        for spp_add in sched:
+            r.render_chunk_accum(width, height, spp_add)
+            r.scatter_tiles()
+            out = dict(fb=r.read_fb(), lin=r.read_fb_aux(1), xyz=r.read_fb_aux(2), rowmajor=r.read_fb_rowmajor(width, height),
+                       stats=r.stats(), kernel_ms=r.last_kernel_ms(), geom=dict(r.geom))
+            yield r.accum_samples, out
+    finally:
+        if r._h:
+            r.set_gather_planes(planes_before)
+        if renderer is None:
+            r.close()

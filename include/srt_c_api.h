@@ -236,6 +236,22 @@ SRT_API int srt_set_partition(srt_ctx *ctx, uint32_t rank, uint32_t world);
 SRT_API int srt_render_chunk(srt_ctx *ctx, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy, void *stream);
 SRT_API int srt_synchronize(srt_ctx *ctx);
 
+/* Progressive rendering (no reference counterpart: the reference renders all spp samples of a chunk in one launch).  The context
+ * keeps one accumulation: a per-pixel XYZ sum (12 B per lane of the grid, allocated on first use) and its running sample total.
+ * srt_accum_reset zeroes both (no re-seeding); each srt_render_chunk_accum adds spp_add samples per pixel to the sums, continuing
+ * the per-pixel RNG streams, and writes the tile buffer (and so, after a scatter, the framebuffer, the parity planes and the
+ * row-major read-back) from the running mean.  Reset + passes of s1 .. sk samples leave framebuffer, parity planes, row-major
+ * image and RNG state bit-identical to ONE srt_render_chunk with spp = s1 + .. + sk issued at the moment of the reset.
+ * The accumulation belongs to the chunk (width, height, offx, offy) and the partition of its first pass.  It is invalidated by
+ * srt_init_device_params, srt_set_partition, srt_upload_scene, srt_set_camera, srt_order_children_by_profile and a plain
+ * srt_render_chunk: the next pass then fails with SRT_ERR_INVALID until srt_accum_reset.  Refused with nothing changed on the device:
+ * spp_add == 0, a total above 65535 (the 16-bit spp, Q17), another chunk or offset (SRT_ERR_INVALID), an instrumented context
+ * (srt_set_count_traversal on: SRT_ERR_UNSUPPORTED).  srt_get_stats after a pass reports that pass (paths = pixels x spp_add).
+ * The spp of srt_init_device_params plays no part in a pass. */
+SRT_API int srt_accum_reset(srt_ctx *ctx);
+SRT_API int srt_render_chunk_accum(srt_ctx *ctx, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy, uint32_t spp_add, void *stream);
+SRT_API int srt_accum_samples(const srt_ctx *ctx, uint32_t *spp_total);     /* samples per pixel the sums hold (0 right after a reset) */
+
 /* Compact tile buffer of this rank (device memory): three plane GROUPS of tiles_padded * 3 * 64 floats each,
  * [group][tile][plane][lane] -- group 0 = quantised r,g,b (the reference's frame_buffer values, 12 B / pixel), group 1 =
  * unquantised sRGB r,g,b, group 2 = XYZ sums (parity planes).  tiles_padded = ceil(n_tiles/world), so every rank's buffer has
@@ -278,7 +294,7 @@ SRT_API int srt_get_tile_costs(srt_ctx *ctx, uint32_t *out, size_t n);
  * probe used the context's RNG state).  n_swapped may be NULL. */
 SRT_API int srt_order_children_by_profile(srt_ctx *ctx, srt_scene *scene, uint32_t width, uint32_t height, uint32_t spp,
                                           uint32_t bounce_limit, uint32_t min_samples, uint32_t *n_swapped);
-SRT_API int srt_get_stats(srt_ctx *ctx, srt_stats *out);       /* counters of the last srt_render_chunk */
+SRT_API int srt_get_stats(srt_ctx *ctx, srt_stats *out);       /* counters of the last srt_render_chunk (or _accum pass) */
 SRT_API int srt_set_count_traversal(srt_ctx *ctx, int on);     /* 1: instrumented kernel also counts V / T */
 /* Instrumented launches only (diagnostics of the tail of a launch): 4 words per persistent wave -- [0] its life time and [1] the
  * moment the pixel queue first came back empty for it (both in units of 256 shader cycles since the wave started; [1] = 2^32-1 if
@@ -339,6 +355,10 @@ SRT_API int srt_comm_init_device_params(srt_comm *comm, uint32_t tx, uint32_t ty
  * buffers to rank 0, one scatter kernel there.  Asynchronous; srt_comm_synchronize waits for the local streams.
  * Afterwards rank 0's context answers srt_read_fb / srt_read_fb_rowmajor / srt_dev_fb as after srt_render_chunk. */
 SRT_API int srt_render_frame_multi(srt_comm *comm, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy);
+/* Progressive rendering on W GPUs: srt_accum_reset on every local context; then srt_render_frame_multi with an accumulating pass
+ * (srt_render_chunk_accum, spp_add samples) on every rank's own tiles.  The gather moves the tile buffers exactly as for a plain frame. */
+SRT_API int srt_comm_accum_reset(srt_comm *comm);
+SRT_API int srt_render_frame_multi_accum(srt_comm *comm, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy, uint32_t spp_add);
 SRT_API int srt_comm_synchronize(srt_comm *comm);
 /* Closest-hit queries / paths of the last frame summed over the local ranks, and the slowest local render kernel. */
 SRT_API int srt_comm_stats(srt_comm *comm, uint64_t *rays, uint64_t *paths, float *max_kernel_ms);

@@ -1,0 +1,353 @@
+"""Progressive rendering (srt_accum_reset / srt_render_chunk_accum, render_kernel MODE 3): passes of s1 .. sk samples accumulated into
+one frame are bit-identical to a one-shot render of s1 + .. + sk samples -- framebuffer, parity planes, row-major image and RNG state.
+The one-shot frames are themselves held to the CPU oracle and to the frozen digests by the parity suite, so every comparison here is
+against an exact reference."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from helpers import (DIGEST_PLANES, assert_planes_equal, custom_scene, digest_of_render, digest_workloads,
+                     oracle_scene_for)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SPLITS = [[12], [5, 7], [1, 1, 10], [4, 4, 4]]
+ERR_INVALID, ERR_UNSUPPORTED = -1, -5
+
+
+def _dielectric_scene(srt):
+    """glass triangles in front of a lambertian floor and a light: refraction, total internal reflection and the valid-wavelength
+    cut of dispersive paths"""
+    tris = [((-4, -1, -4), (4, -1, -4), (4, -1, 4), 0, 0), ((-4, -1, -4), (4, -1, 4), (-4, -1, 4), 0, 0),
+            ((-1.5, -0.8, 0.5), (1.5, -0.8, 0.5), (0.0, 1.8, 0.0), 1, 0), ((-1.2, -0.8, -0.6), (1.4, -0.8, -0.4), (0.1, 1.5, 0.9), 1, 0),
+            ((-2, 3, -2), (2, 3, -2), (0, 3, 2), 2, 0), ((2.5, -1, -1), (3.5, -1, 0), (3.0, 1.0, -0.5), 3, 0)]
+    mats = [(0, (0.73, 0.73, 0.73), 0.0, 0.0), (2, (1.0, 1.0, 1.0), 0.0, 0.0), (4, (1.0, 1.0, 1.0), 0.0, 3.0), (1, (0.8, 0.8, 0.8), 0.1, 0.0)]
+    return custom_scene(srt, tris, mats, (0.5, 0.5, 0.5)).build_bvh(srt.BVH_SAH, 1984)      # (grey: no rgb2spec table)
+
+
+def _soup(srt, seed, n):
+    """n small random triangles (lambertian, metallic, dielectric, emissive): an even n gives a PAIRED SAH tree"""
+    rng = np.random.default_rng(7000 + seed)
+    c = rng.uniform(-6, 6, (n, 3))
+    v = [(c + rng.normal(0, 0.3, (n, 3))).astype(np.float32).astype(np.float64) for _ in range(3)]
+    mat = rng.integers(0, 4, n)
+    tris = [(tuple(v[0][k]), tuple(v[1][k]), tuple(v[2][k]), int(mat[k]), 0) for k in range(n)]
+    mats = [(0, (0.6, 0.6, 0.6), 0.0, 0.0), (1, (1.0, 1.0, 1.0), 0.2, 0.0), (2, (1.0, 1.0, 1.0), 0.0, 0.0), (4, (1.0, 1.0, 1.0), 0.0, 2.0)]
+    return custom_scene(srt, tris, mats, (0.5, 0.5, 0.5))
+
+
+def _workload(srt, name):
+    if name == "prism":
+        sc = srt.Scene.builtin(srt.SCENE_PRISM).build_bvh(srt.BVH_REFERENCE, 1984)
+        return sc, sc.default_camera(48, 40), 48, 40, 8, 0
+    if name == "cornell":
+        sc = srt.Scene.builtin(srt.SCENE_CORNELL).build_bvh(srt.BVH_REFERENCE, 1984)
+        return sc, sc.default_camera(64, 48), 64, 48, 8, 0
+    if name == "random_spheres":
+        sc = srt.Scene.builtin(srt.SCENE_RANDOM_SPHERES).build_bvh(srt.BVH_SAH, 1984)
+        return sc, sc.default_camera(80, 45), 80, 45, 16, 1       # defocus lens, sky background
+    sc = _dielectric_scene(srt)
+    return sc, srt.camera_init(56, 40, 45.0, (0.5, 0.8, 7.0), (0.0, 0.3, 0.0)), 56, 40, 12, 1
+
+
+def _split(spp):
+    """spp in two or three passes (one pass when spp == 1)"""
+    k = min(3, spp)
+    base, rem = divmod(spp, k)
+    return [base + (1 if i < rem else 0) for i in range(k)]
+
+
+def _assert_same_image(got, want, what, rowmajor=True):
+    assert_planes_equal(got["fb"], want["fb"], what + " fb")
+    assert_planes_equal(got["lin"], want["lin"], what + " unquantised sRGB")
+    assert_planes_equal(got["xyz"], want["xyz"], what + " XYZ sums")
+    if rowmajor:
+        assert_planes_equal(got["rowmajor"], want["rowmajor"], what + " row-major")
+
+
+def _progressive(srt, gpu, scene, cam, W, H, passes, depth):
+    """runs render_progressive to the end; returns the list of (spp_total, result)"""
+    return list(srt.render_progressive(scene, cam, W, H, passes, depth, renderer=gpu))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["prism", "cornell", "random_spheres", "dielectric"])
+def test_split_equals_one_shot_bit_for_bit(srt, gpu, orc, name):
+    scene, cam, W, H, depth, mode = _workload(srt, name)
+    one_shot = srt.render_image(scene, cam, W, H, 12, depth, renderer=gpu)
+    for passes in SPLITS:
+        steps = _progressive(srt, gpu, scene, cam, W, H, passes, depth)
+        assert [t for t, _ in steps] == list(np.cumsum(passes)), steps
+        total, last = steps[-1]
+        _assert_same_image(last, one_shot, "%s split %r" % (name, passes))
+        assert set(last) == set(one_shot)
+        pixels = W * H
+        assert last["stats"]["paths"] == pixels * passes[-1], (last["stats"], passes)     # the stats of the last pass
+        assert last["kernel_ms"] > 0.0
+    if name == "prism":     # once directly against the CPU oracle as well
+        ref = oracle_scene_for(orc, scene, mode).render(cam, W, H, 12, depth)
+        for k in ("fb", "lin", "xyz"):
+            assert_planes_equal(last[k], ref[k], "prism [4, 4, 4] vs oracle " + k)
+
+
+@pytest.mark.gpu
+def test_intermediate_passes_equal_one_shot_of_their_total(srt, gpu):
+    """every yielded frame, not only the last, is the one-shot frame of the samples so far"""
+    scene, cam, W, H, depth, _ = _workload(srt, "prism")
+    steps = _progressive(srt, gpu, scene, cam, W, H, [2, 3, 7], depth)
+    for total, res in steps:
+        _assert_same_image(res, srt.render_image(scene, cam, W, H, total, depth, renderer=gpu), "after %d samples" % total)
+
+
+@pytest.mark.gpu
+def test_frozen_digests_in_several_passes(srt, gpu):
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "oracle_digests.json")))
+    for name, (scene, cam, W, H, spp, depth, _) in sorted(digest_workloads(srt).items()):
+        passes = _split(spp)
+        total, res = _progressive(srt, gpu, scene, cam, W, H, passes, depth)[-1]
+        assert total == spp == golden[name]["spp"]
+        got = digest_of_render(res)
+        for plane in DIGEST_PLANES:
+            assert got[plane] == golden[name][plane], (name, passes, plane)
+
+
+def _forced_variant_case(srt, gpu, scene, cam, W, H, depth, knobs, expect):
+    gpu.set_test_knobs(**knobs)
+    try:
+        one_shot = srt.render_image(scene, cam, W, H, 12, depth, renderer=gpu)
+        plan = gpu.launch_plan()
+        shape = (int(plan["narrow_refs"]), int(plan["all_cached"]), int(plan["paired"]))
+        assert shape == expect, (plan, knobs)
+        for passes in ([5, 7], [1, 1, 10]):
+            _, last = _progressive(srt, gpu, scene, cam, W, H, passes, depth)[-1]
+            _assert_same_image(last, one_shot, "shape %r split %r" % (expect, passes))
+    finally:
+        gpu.set_test_knobs()
+        gpu.upload_scene(scene)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("knobs,paired,expect", [
+    (dict(), True, (1, 1, 1)),                                   # PAIRED, LDS resident, 16-bit references (the headline's shape)
+    (dict(wide_refs=True, lds_cache_max=3), True, (0, 0, 1)),    # PAIRED, 32-bit references, inner tree partly from L2 (cfg 5's shape)
+    (dict(), False, (1, 1, 0)),
+    (dict(lds_cache_max=3), False, (1, 0, 0)),
+    (dict(wide_refs=True), False, (0, 1, 0)),
+    (dict(wide_refs=True, lds_cache_max=0), False, (0, 0, 0)),
+], ids=["narrow-cached-paired", "wide-partial-paired", "narrow-cached", "narrow-partial", "wide-cached", "wide-partial"])
+def test_every_accumulating_shape_is_exact(srt, gpu, knobs, paired, expect):
+    n = 600 if paired else 601          # the SAH builder pairs an even triangle count
+    scene = _soup(srt, n, n).build_bvh(srt.BVH_SAH, 1984)
+    assert scene.is_paired == paired
+    W, H, depth = 48, 32, 8
+    cam = srt.camera_init(W, H, 50.0, (0.5, 1.0, 16.0), (0.0, 0.0, 0.0), defocus_angle=0.6, focus_dist=14.0)
+    _forced_variant_case(srt, gpu, scene, cam, W, H, depth, knobs, expect)
+
+
+@pytest.mark.gpu
+def test_partition_and_offset_chunk(srt, gpu):
+    """ranks 0..W-1 of a partition, each accumulated on its own and scattered together, equal the one-shot frame; so does a chunk at a
+    non-zero offset of a larger image"""
+    import torch
+    scene, cam, W, H, depth, _ = _workload(srt, "prism")
+    ref = srt.render_image(scene, cam, W, H, 12, depth, renderer=gpu)
+    for world in (2, 3):
+        parts = []
+        for rank in range(world):
+            gpu.upload_scene(scene); gpu.set_camera(cam)
+            gpu.init_device_params(W, H, 12, depth, 1984)
+            gpu.set_partition(rank, world)
+            gpu.accum_reset()
+            for s in (5, 7):
+                gpu.render_chunk_accum(W, H, s)
+            gpu.synchronize()
+            _, n_floats, _, _ = gpu.tile_buffer()
+            staging = torch.empty(n_floats, dtype=torch.float32, device="cuda")
+            gpu.copy_tile_buffer(staging.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+            parts.append(staging.cpu().numpy().copy())
+        gathered = torch.from_numpy(np.concatenate(parts)).cuda()
+        gpu.scatter_tiles(gathered.data_ptr())
+        gpu.synchronize()
+        assert_planes_equal(gpu.read_fb(), ref["fb"], "world %d fb" % world)
+        assert_planes_equal(gpu.read_fb_aux(1), ref["lin"], "world %d lin" % world)
+        assert_planes_equal(gpu.read_fb_aux(2), ref["xyz"], "world %d xyz" % world)
+    gpu.set_partition(0, 1)
+
+    # a 30 x 20 chunk at (17, 9) of a 64 x 40 image
+    IW, IH, cw, ch, ox, oy = 64, 40, 30, 20, 17, 9
+    cam = scene.default_camera(IW, IH)
+
+    def chunk(accumulate):
+        gpu.upload_scene(scene); gpu.set_camera(cam)
+        gpu.init_device_params(cw, ch, 12, depth, 1984)
+        if accumulate:
+            gpu.accum_reset()
+            for s in (1, 4, 7):
+                gpu.render_chunk_accum(cw, ch, s, ox, oy)
+        else:
+            gpu.render_chunk(cw, ch, ox, oy)
+        gpu.scatter_tiles()
+        return dict(fb=gpu.read_fb(), lin=gpu.read_fb_aux(1), xyz=gpu.read_fb_aux(2), rowmajor=gpu.read_fb_rowmajor(IW, IH))
+    _assert_same_image(chunk(True), chunk(False), "offset chunk")
+
+
+@pytest.mark.gpu
+def test_comm_two_and_three_ranks_one_gpu_mock_transport():
+    """srt_comm_accum_reset / srt_render_frame_multi_accum at W = 2 and 3 on ONE GPU over the test transport (tests/cpp/mock_rccl.cpp,
+    as the parity suite's communicator test does; the library caches its RCCL handle per process, so this runs in a child process)"""
+    mock = os.path.join(ROOT, "tests", "cpp", "_build", "libmock_rccl.so")
+    assert os.path.exists(mock), "tests/cpp/_build/libmock_rccl.so is built by __graft_entry__.build()"
+    code = """
+import importlib, sys
+sys.path.insert(0, %r); sys.path.insert(0, %r)
+srt = importlib.import_module('cuda-spectral-ray-tracer_amd')
+from helpers import assert_planes_equal
+scene = srt.Scene.builtin(srt.SCENE_RANDOM_SPHERES).build_bvh(srt.BVH_SAH, 1984)
+W, H, depth = 150, 90, 16
+cam = scene.default_camera(W, H)
+ref = srt.render_image(scene, cam, W, H, 12, depth)
+for world in (2, 3):
+    comm = srt.Comm.init_all([0] * world)
+    for planes in (3, 9):
+        comm.set_gather_planes(planes)
+        comm.upload_scene(scene); comm.set_camera(cam)
+        comm.init_device_params(W, H, 12, depth, 1984)
+        comm.accum_reset()
+        for s in (5, 7):
+            comm.render_frame_accum(W, H, s)
+        comm.synchronize()
+        root = comm.root
+        assert all(r.accum_samples == 12 for r in comm.renderers)
+        assert_planes_equal(root.read_fb(), ref['fb'], 'world %%d planes %%d fb' %% (world, planes))
+        if planes == 9:
+            assert_planes_equal(root.read_fb_aux(1), ref['lin'], 'world %%d lin' %% world)
+            assert_planes_equal(root.read_fb_aux(2), ref['xyz'], 'world %%d xyz' %% world)
+        st = comm.stats()
+        assert st['paths'] == W * H * 7, st
+    comm.close()
+print('progressive mock transport ok')
+""" % (ROOT, os.path.join(ROOT, "tests"))
+    env = dict(os.environ, SRT_RCCL_LIB=mock, SRT_COMM_TEST_SAME_DEVICE="1", SRT_TEST_KNOBS="1")
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "progressive mock transport ok" in out.stdout, (out.stdout[-1500:], out.stderr[-3000:])
+
+
+@pytest.mark.gpu
+def test_plain_render_after_accumulation_continues_rng_streams(srt, gpu, orc):
+    """the RNG state an accumulation leaves is the one-shot's: a plain launch after [5, 7] equals the oracle continued from the states
+    after 12 samples"""
+    import ctypes as C
+    scene, cam, W, H, depth, mode = _workload(srt, "prism")
+    spp_next = 3
+    gpu.upload_scene(scene); gpu.set_camera(cam); gpu.set_partition(0, 1)
+    gpu.init_device_params(W, H, spp_next, depth, 1984)
+    gpu.accum_reset()
+    for s in (5, 7):
+        gpu.render_chunk_accum(W, H, s)
+    gpu.render_chunk(W, H)
+    gpu.scatter_tiles()
+    after = dict(fb=gpu.read_fb(), xyz=gpu.read_fb_aux(2))
+    osc = oracle_scene_for(orc, scene, mode)
+    n = gpu.geom["n_lanes"]
+    states = np.zeros(6 * n, np.uint32)
+    for idx in range(n):
+        s = orc.Rng()
+        orc.lib().orc_rng_init(1984 + idx, C.byref(s))
+        states[6 * idx: 6 * idx + 6] = [s.d] + list(s.v)
+    osc.render(cam, W, H, 12, depth, states=states)           # the accumulation's 12 samples
+    ref = osc.render(cam, W, H, spp_next, depth, states=states)
+    assert_planes_equal(after["xyz"], ref["xyz"], "plain launch after the accumulation, XYZ")
+    assert_planes_equal(after["fb"], ref["fb"], "plain launch after the accumulation, fb")
+
+
+def _expect_error(srt, fn, code, what):
+    with pytest.raises(srt.SrtError) as e:
+        fn()
+    assert e.value.code == code, (what, e.value)
+
+
+@pytest.mark.gpu
+def test_refused_calls_and_invalidation(srt, gpu):
+    scene, cam, W, H, depth, _ = _workload(srt, "prism")
+    one_shot = srt.render_image(scene, cam, W, H, 12, depth, renderer=gpu)
+
+    def fresh():
+        gpu.upload_scene(scene); gpu.set_camera(cam); gpu.set_partition(0, 1)
+        gpu.init_device_params(W, H, 12, depth, 1984)
+
+    def frame():
+        gpu.scatter_tiles()
+        return dict(fb=gpu.read_fb(), lin=gpu.read_fb_aux(1), xyz=gpu.read_fb_aux(2), rowmajor=gpu.read_fb_rowmajor(W, H))
+
+    # no accumulation yet
+    fresh()
+    _expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 4), ERR_INVALID, "pass before srt_accum_reset")
+    assert gpu.accum_samples == 0
+    gpu.accum_reset()
+    assert gpu.accum_samples == 0
+    _expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 65536), ERR_INVALID, "total above 65535")
+    gpu.render_chunk_accum(W, H, 5)
+    assert gpu.accum_samples == 5 and gpu.stats()["paths"] == W * H * 5
+    after_first = frame()
+
+    # refusals: nothing changes on the device (framebuffer, tile buffer, sums, RNG state)
+    refusals = [
+        (lambda: gpu.render_chunk_accum(W, H, 0), ERR_INVALID, "spp_add 0"),
+        (lambda: gpu.render_chunk_accum(W, H, 65531), ERR_INVALID, "total 65536"),
+        (lambda: gpu.render_chunk_accum(W - 1, H, 7), ERR_INVALID, "another chunk width"),
+        (lambda: gpu.render_chunk_accum(W, H - 8, 7), ERR_INVALID, "another chunk height"),
+        (lambda: gpu.render_chunk_accum(W, H, 7, 1, 0), ERR_INVALID, "another offset"),
+        (lambda: gpu.render_chunk_accum(W, H, 7, 0, 2), ERR_INVALID, "another offset"),
+    ]
+    for fn, code, what in refusals:
+        _expect_error(srt, fn, code, what)
+        assert gpu.accum_samples == 5, what
+    gpu.set_count_traversal(True)
+    _expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 7), ERR_UNSUPPORTED, "instrumented context")
+    gpu.set_count_traversal(False)
+    _assert_same_image(frame(), after_first, "framebuffer after the refused calls")
+    gpu.render_chunk_accum(W, H, 7)               # the sums and the RNG states were untouched: the total is the one-shot frame
+    assert gpu.accum_samples == 12
+    _assert_same_image(frame(), one_shot, "accumulation continued after the refused calls")
+
+    # invalidation: each of these calls ends the accumulation until the next reset
+    invalidators = [
+        ("srt_init_device_params", lambda: gpu.init_device_params(W, H, 12, depth, 1984)),
+        ("srt_set_partition", lambda: gpu.set_partition(0, 1)),
+        ("srt_upload_scene", lambda: gpu.upload_scene(scene)),
+        ("srt_set_camera", lambda: gpu.set_camera(cam)),
+        ("srt_render_chunk", lambda: gpu.render_chunk(W, H)),
+    ]
+    for what, call in invalidators:
+        fresh()
+        gpu.accum_reset()
+        gpu.render_chunk_accum(W, H, 2)
+        call()
+        _expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 2), ERR_INVALID, what)
+        assert gpu.accum_samples == 0, what
+        gpu.accum_reset()
+        gpu.render_chunk_accum(W, H, 2)       # a reset makes the context usable again
+        assert gpu.accum_samples == 2, what
+    # srt_order_children_by_profile (on a scene of its own: it re-orders the tree in place) uploads a scene and spends the RNG state
+    fresh()
+    gpu.accum_reset()
+    gpu.render_chunk_accum(W, H, 2)
+    other = srt.Scene.builtin(srt.SCENE_PRISM).build_bvh(srt.BVH_REFERENCE, 1984)
+    try:
+        gpu.order_children_by_profile(other, W, H, 2, depth, 1)
+    except srt.SrtError:
+        pass            # (a probe frame that records nothing is declined: the accumulation is dropped before anything else)
+    _expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 2), ERR_INVALID, "srt_order_children_by_profile")
+    assert gpu.accum_samples == 0
+
+    # a refused pass after a plain launch leaves the plain frame alone
+    fresh()
+    gpu.render_chunk(W, H)
+    plain = frame()
+    _expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 3), ERR_INVALID, "after a plain launch")
+    _assert_same_image(frame(), plain, "plain frame after a refused pass")
+    _assert_same_image(plain, one_shot, "plain frame")
