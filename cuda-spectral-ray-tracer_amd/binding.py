@@ -48,6 +48,12 @@ class Calibration(C.Structure):
                 ("reserved", C.c_uint32), ("wave_cycles_min", C.c_double)]
 
 
+class Adaptive(C.Structure):
+    """srt_adaptive: the stopping criterion of an adaptive accumulation (srt_c_api.h)"""
+    _fields_ = [("rel_tol", C.c_float), ("abs_tol", C.c_float), ("min_spp", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(Adaptive) == 16
 assert C.sizeof(Material) == 428 and C.sizeof(CameraData) == 84 and C.sizeof(TriIn) == 44
 
 # every symbol include/srt_c_api.h declares: name -> (restype, argtypes)
@@ -100,6 +106,9 @@ PROTOTYPES = {
     "srt_accum_reset": (_i, [_vp]),
     "srt_render_chunk_accum": (_i, [_vp, _u32, _u32, _u32, _u32, _u32, _vp]),
     "srt_accum_samples": (_i, [_vp, C.POINTER(_u32)]),
+    "srt_accum_reset_adaptive": (_i, [_vp, C.POINTER(Adaptive)]),
+    "srt_accum_active": (_i, [_vp, C.POINTER(_u64)]),
+    "srt_read_accum_stats": (_i, [_vp, C.POINTER(_u32), _fp, _fp, _u32, _u32]),
     "srt_set_gather_planes": (_i, [_vp, _u32]),
     "srt_tile_buffer": (_i, [_vp, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_u32), C.POINTER(_u32)]),
     "srt_copy_tile_buffer": (_i, [_vp, _vp, _vp]),
@@ -137,6 +146,8 @@ PROTOTYPES = {
     "srt_render_frame_multi": (_i, [_vp, _u32, _u32, _u32, _u32]),
     "srt_comm_accum_reset": (_i, [_vp]),
     "srt_render_frame_multi_accum": (_i, [_vp, _u32, _u32, _u32, _u32, _u32]),
+    "srt_comm_accum_reset_adaptive": (_i, [_vp, C.POINTER(Adaptive)]),
+    "srt_comm_accum_active": (_i, [_vp, C.POINTER(_u64)]),
     "srt_comm_synchronize": (_i, [_vp]),
     "srt_comm_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_f)]),
 }

@@ -6,6 +6,8 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
+#include <cstddef>
 #include <string>
 #include <vector>
 
@@ -91,6 +93,14 @@ struct srt_ctx {
     enum { kAccumInvalid, kAccumEmpty, kAccumBound } accum_state = kAccumInvalid;   // Empty: reset, no pass yet; Bound: passes of one chunk
     uint32_t accum_total = 0;                           // samples per pixel in the sums
     uint32_t accum_w = 0, accum_h = 0, accum_offx = 0, accum_offy = 0;   // the chunk of the first pass
+    // adaptive sampling (srt_accum_reset_adaptive): [S2 plane | state plane] of accum_lanes words, allocated on first use
+    bool accum_adaptive = false;                        // the current accumulation is adaptive (MODE 4 passes)
+    char *d_adapt = nullptr;
+    uint64_t adapt_lanes = 0;
+    // pixel queue of the next adaptive pass: [queue_info 4 words | counts: 1 x u64 + pad | rows | flags], adapt_queue_rows rows each
+    uint32_t *d_adapt_queue = nullptr;
+    size_t adapt_queue_rows = 0;
+    bool stats_adaptive = false;                        // the last launch was an adaptive pass: srt_get_stats reads its pixel count
 };
 
 namespace {
@@ -213,7 +223,7 @@ void srt_destroy(srt_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    void *bufs[] = {c->d_nodes, c->d_nodes_sw, c->d_fringe, c->d_tris, c->d_mat_sd, c->d_mat_par, c->d_shade, c->d_cmf, c->d_rng, c->d_fb, c->d_tiles, c->d_counters, c->d_tile_cost, c->d_tile_order, c->d_rowmajor, c->d_wave_debug, c->d_accum};
+    void *bufs[] = {c->d_nodes, c->d_nodes_sw, c->d_fringe, c->d_tris, c->d_mat_sd, c->d_mat_par, c->d_shade, c->d_cmf, c->d_rng, c->d_fb, c->d_tiles, c->d_counters, c->d_tile_cost, c->d_tile_order, c->d_rowmajor, c->d_wave_debug, c->d_accum, c->d_adapt, c->d_adapt_queue};
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -366,6 +376,8 @@ uint32_t srt_internal_gather_planes(const srt_ctx *c) { return c ? c->gather_pla
 
 int srt_set_gather_planes(srt_ctx *c, uint32_t planes) {
     if (!c || (planes != 3 && planes != 9)) return fail(c, SRT_ERR_INVALID, "srt_set_gather_planes: planes must be 3 or 9");
+    // (an adaptive pass writes only the slots of its active pixels: the converged ones would keep planes of another set)
+    if (c->accum_adaptive) c->accum_state = srt_ctx::kAccumInvalid;
     c->gather_planes = planes;
     return SRT_OK;
 }
@@ -379,6 +391,8 @@ namespace {
 // width .. offy are already narrowed to 16 bit.
 int render_chunk_impl(srt_ctx *c, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy, uint32_t spp_add, hipStream_t st) {
     const bool accum = spp_add != 0;
+    const bool adapt = accum && c->accum_adaptive;      // MODE 4
+    const bool adapt_later = adapt && c->accum_state == srt_ctx::kAccumBound;
     c->last_w = width; c->last_h = height; c->last_offx = offx; c->last_offy = offy;
     // Tiles cover every pixel the reference grid can address, whatever the size of THIS chunk: the tile number of a lane
     // idx -- and with it the rank that owns the lane's persistent RNG stream (Q13) -- must not move when a ragged edge
@@ -394,8 +408,9 @@ int render_chunk_impl(srt_ctx *c, uint32_t width, uint32_t height, uint32_t offx
         HIP_TRY(c, hipMalloc((void **)&c->d_tiles, need * sizeof(float)));
         c->tiles_capacity = need;
     }
-    // (only the plane groups this launch writes: group 0, or all three when the parity planes were asked for)
-    HIP_TRY(c, hipMemsetAsync(c->d_tiles, 0, (size_t)std::max<uint32_t>(c->tiles_padded, 1) * c->gather_planes * kTileLanes * sizeof(float), st));
+    // (only the plane groups this launch writes: group 0, or all three when the parity planes were asked for.  Not on the later passes
+    // of an adaptive accumulation: their converged pixels keep the slots they wrote last)
+    if (!adapt_later) HIP_TRY(c, hipMemsetAsync(c->d_tiles, 0,(size_t)std::max<uint32_t>(c->tiles_padded, 1) * c->gather_planes * kTileLanes * sizeof(float), st));
     HIP_TRY(c, hipMemsetAsync(c->d_counters, 0, (kCounters + 1) * sizeof(unsigned long long), st));
     RenderParams p;
     fill_params(c, p);
@@ -429,7 +444,25 @@ int render_chunk_impl(srt_ctx *c, uint32_t width, uint32_t height, uint32_t offx
     const bool schedulable = c->probe_spp > 0 && c->tiles_local > 1 && c->tiles_local <= 0x3fffffu;   // 22-bit tile field of a queue row
     const bool ordered = schedulable && (accum || c->spp > 4 * c->probe_spp);
     const bool reuse_order = ordered && accum && c->accum_state == srt_ctx::kAccumBound;
-    if (reuse_order) {
+    // (adaptive passes after the first: the queue the previous pass compacted -- the probe's rows, or the identity order, whose tiles
+    // still hold an active pixel.  A queue row has a 22-bit tile field: beyond that the pass runs the plain identity queue, and its
+    // converged pixels are only skipped at the fetch)
+    const bool adapt_compact = adapt && c->tiles_local <= 0x3fffffu;
+    const uint32_t adapt_bound = ordered && c->split_load_pct ? (uint32_t)std::min<uint64_t>((uint64_t)c->tiles_local * 64, 0x7fffffffull) : c->tiles_local;
+    if (adapt) {
+        if (c->adapt_queue_rows < std::max<uint32_t>(adapt_bound, 1u)) {
+            if (c->d_adapt_queue) { HIP_TRY(c, hipDeviceSynchronize()); (void)hipFree(c->d_adapt_queue); c->d_adapt_queue = nullptr; c->adapt_queue_rows = 0; }
+            const size_t rows = std::max<uint32_t>(adapt_bound, 1u);
+            HIP_TRY(c, hipMalloc((void **)&c->d_adapt_queue, (8 + 2 * rows) * sizeof(uint32_t)));
+            c->adapt_queue_rows = rows;
+        }
+    }
+    if (adapt_later && adapt_compact) {
+        p.tile_order = c->d_adapt_queue + 8;
+        p.queue_rows = c->d_adapt_queue;
+        p.prio_cost = ordered ? c->d_tile_cost : nullptr;
+        p.queue_rows_bound = adapt_bound;
+    } else if (reuse_order) {
         uint32_t *rows = c->d_tile_order, *sorted = rows + (size_t)c->tile_sched_capacity * 64, *queue_info = sorted + c->tile_sched_capacity;
         p.tile_order = rows;
         p.queue_rows = queue_info;
@@ -477,14 +510,32 @@ int render_chunk_impl(srt_ctx *c, uint32_t width, uint32_t height, uint32_t offx
     RoctxRange range_render("srt render_kernel");
     HIP_TRY(c, hipEventRecord(c->ev0, st));     // ev0..ev1 bracket the render kernel alone (roofline.achieved)
     uint32_t waves_launched = 0;
-    if (accum) p.wave_debug = reinterpret_cast<uint32_t *>(c->d_accum);      // MODE 3 reads its AccumHeader there
-    HIP_TRY(c, launch_render(p, c->knobs, (uint32_t)c->n_cu, accum ? 3 : (c->count_traversal ? 1 : 0), st, &waves_launched));
+    if (accum) p.wave_debug = reinterpret_cast<uint32_t *>(c->d_accum);      // MODE 3 / 4 read their AccumHeader there
+    HIP_TRY(c, launch_render(p, c->knobs, (uint32_t)c->n_cu, adapt ? 4 : accum ? 3 : (c->count_traversal ? 1 : 0), st, &waves_launched));
     if (c->count_traversal && waves_launched > c->wave_debug_waves)
         return fail(c, SRT_ERR_HIP, "srt_render_chunk: the launch started more waves than the debug buffer holds (launch plan and launcher disagree)");
     HIP_TRY(c, hipEventRecord(c->ev1, st));
+    if (adapt) {
+        // the next pass's queue, from the probe's queue (kept intact for the whole accumulation) or the identity order; the same
+        // kernels count the pixels that rendered in this pass and those still active (srt_get_stats, srt_accum_active)
+        uint32_t *rows = c->d_tile_order, *sorted = rows ? rows + (size_t)c->tile_sched_capacity * 64 : nullptr, *queue_info = sorted ? sorted + c->tile_sched_capacity : nullptr;
+        AdaptQueueParams q;
+        memset(&q, 0, sizeof(q));
+        q.src_rows = ordered ? rows : nullptr; q.src_info = ordered ? queue_info : nullptr; q.n_identity = c->tiles_local;
+        q.dst_info = c->d_adapt_queue; q.dst_rows = c->d_adapt_queue + 8; q.flags = q.dst_rows + c->adapt_queue_rows;
+        q.counts = reinterpret_cast<unsigned long long *>(c->d_adapt_queue + 4);
+        q.state = reinterpret_cast<const uint32_t *>(c->d_adapt + c->adapt_lanes * sizeof(float));
+        q.spp_total = c->accum_total + spp_add;
+        q.width = width; q.height = height; q.tx = c->tx; q.ty = c->ty; q.bx = c->bx; q.by = c->by;
+        q.tiles_x = c->tiles_x; q.n_tiles = c->n_tiles; q.rank = c->rank; q.world = c->world;
+        q.lane_limit = c->debug_lane_limit ? c->debug_lane_limit : 64u;
+        HIP_TRY(c, hipMemsetAsync(q.counts, 0, sizeof(unsigned long long), st));
+        HIP_TRY(c, launch_adapt_queue(q, adapt_bound, st));
+    }
     c->timed = true;
-    c->last_paths = 0;   // filled by srt_get_stats from the tile ownership
+    c->last_paths = 0;   // filled by srt_get_stats from the tile ownership (adaptive passes: from the device's count)
     c->stats_spp = spp_add;
+    c->stats_adaptive = adapt;
     return SRT_OK;
 }
 
@@ -520,7 +571,57 @@ int srt_accum_reset(srt_ctx *c) {
     HIP_TRY(c, hipMemset(c->d_accum + kAccumHeaderBytes, 0, 3 * lanes * sizeof(float)));
     HIP_TRY(c, hipDeviceSynchronize());
     c->accum_total = 0;
+    c->accum_adaptive = false;
     c->accum_state = srt_ctx::kAccumEmpty;
+    return SRT_OK;
+}
+
+int srt_accum_reset_adaptive(srt_ctx *c, const srt_adaptive *cfg) {
+    if (!c) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_adaptive: null ctx");
+    // refusals first: a refused call leaves the context's accumulation as it was
+    if (!cfg) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_adaptive: null cfg");
+    if (!std::isfinite(cfg->rel_tol) || !std::isfinite(cfg->abs_tol) || cfg->rel_tol < 0.f || cfg->abs_tol < 0.f || !(cfg->rel_tol + cfg->abs_tol > 0.f))
+        return fail(c, SRT_ERR_INVALID, "srt_accum_reset_adaptive: rel_tol and abs_tol must be finite and >= 0, and not both 0");
+    if (cfg->min_spp < 2) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_adaptive: min_spp must be >= 2 (the variance of the mean needs two samples)");
+    if (cfg->reserved != 0) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_adaptive: reserved must be 0");
+    if (c->count_traversal)
+        return fail(c, SRT_ERR_UNSUPPORTED, "srt_accum_reset_adaptive: no instrumented accumulating kernel (srt_set_count_traversal(ctx, 0) first)");
+    if (!c->params_ready) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_adaptive: device parameters must be set first (srt_init_device_params)");
+    int rc = srt_accum_reset(c);
+    if (rc != SRT_OK) return rc;
+    c->accum_state = srt_ctx::kAccumInvalid;      // (until the adaptive planes are in place)
+    const uint64_t lanes = c->n_lanes;
+    if (!c->d_adapt || c->adapt_lanes != lanes) {
+        if (c->d_adapt) { (void)hipFree(c->d_adapt); c->d_adapt = nullptr; c->adapt_lanes = 0; }
+        HIP_TRY(c, hipMalloc((void **)&c->d_adapt, 2 * lanes * sizeof(float)));
+        c->adapt_lanes = lanes;
+    }
+    HIP_TRY(c, hipMemset(c->d_adapt, 0, 2 * lanes * sizeof(float)));
+    // the adaptive half of the header (the per-pass kernel rewrites only sums and spp_total)
+    AccumHeader h;
+    memset(&h, 0, sizeof(h));
+    h.sum2 = reinterpret_cast<float *>(c->d_adapt);
+    h.state = reinterpret_cast<uint32_t *>(c->d_adapt + lanes * sizeof(float));
+    h.rel_tol = cfg->rel_tol; h.abs_tol = cfg->abs_tol; h.min_spp = cfg->min_spp;
+    const size_t tail = offsetof(AccumHeader, sum2);
+    HIP_TRY(c, hipMemcpy(c->d_accum + tail, reinterpret_cast<const char *>(&h) + tail, sizeof(h) - tail, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipDeviceSynchronize());
+    c->accum_adaptive = true;
+    c->accum_state = srt_ctx::kAccumEmpty;
+    return SRT_OK;
+}
+
+int srt_accum_active(srt_ctx *c, uint64_t *active) {
+    if (!c || !active) return fail(c, SRT_ERR_INVALID, "srt_accum_active: null argument");
+    if (!c->accum_adaptive || c->accum_state == srt_ctx::kAccumInvalid)
+        return fail(c, SRT_ERR_INVALID, "srt_accum_active: no adaptive accumulation (srt_accum_reset_adaptive first)");
+    *active = 0;
+    if (c->accum_state == srt_ctx::kAccumEmpty) return SRT_OK;      // (the first pass binds the chunk)
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipDeviceSynchronize());
+    unsigned long long counts = 0;
+    HIP_TRY(c, hipMemcpy(&counts, c->d_adapt_queue + 4, sizeof(counts), hipMemcpyDeviceToHost));
+    *active = counts >> 32;
     return SRT_OK;
 }
 
@@ -631,8 +732,11 @@ int srt_read_fb_aux(srt_ctx *c, int which, float *p0, float *p1, float *p2) {
     return read_planes(c, 3 * which, p0, p1, p2);
 }
 
-int srt_read_fb_rowmajor(srt_ctx *c, float *r, float *g, float *b, uint32_t image_width, uint32_t image_height) {
-    if (!c || !c->d_fb || !r || !g || !b || image_width == 0 || image_height == 0) return fail(c, SRT_ERR_INVALID, "srt_read_fb_rowmajor: bad argument");
+}  // extern "C"
+
+// Three block-linear planes of n_lanes words (bits copied as they are) -> the last chunk's rectangle of three row-major host images.
+// A null host plane is not copied (its source plane may be any valid one).
+static int read_rowmajor(srt_ctx *c, const float *const src[3], float *const host[3], uint32_t image_width, uint32_t image_height) {
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t n = (size_t)image_width * image_height;
     // context-owned row-major staging image: the un-swizzle writes the chunk's pixels into it on the device and only the
@@ -643,18 +747,49 @@ int srt_read_fb_rowmajor(srt_ctx *c, float *r, float *g, float *b, uint32_t imag
         HIP_TRY(c, hipMemset(c->d_rowmajor, 0, 3 * n * sizeof(float)));
         c->rowmajor_w = image_width; c->rowmajor_h = image_height;
     }
-    const float *src[3] = {c->d_fb, c->d_fb + (size_t)c->n_lanes, c->d_fb + 2 * (size_t)c->n_lanes};
     float *dst[3] = {c->d_rowmajor, c->d_rowmajor + n, c->d_rowmajor + 2 * n};
     HIP_TRY(c, launch_unswizzle(src, dst, c->tx, c->ty, c->bx, c->by, c->last_w, c->last_h, c->last_offx, c->last_offy, image_width, image_height, nullptr));
     if (c->last_offx < image_width && c->last_offy < image_height) {
         const uint32_t w = std::min<uint32_t>(std::min<uint32_t>(c->last_w, c->tx * c->bx), image_width - c->last_offx);
         const uint32_t h = std::min<uint32_t>(std::min<uint32_t>(c->last_h, c->ty * c->by), image_height - c->last_offy);
         const size_t first = (size_t)c->last_offy * image_width + c->last_offx, pitch = (size_t)image_width * sizeof(float);
-        float *host[3] = {r, g, b};
         for (int k = 0; k < 3 && w && h; k++)
-            HIP_TRY(c, hipMemcpy2D(host[k] + first, pitch, dst[k] + first, pitch, (size_t)w * sizeof(float), h, hipMemcpyDeviceToHost));
+            if (host[k]) HIP_TRY(c, hipMemcpy2D(host[k] + first, pitch, dst[k] + first, pitch, (size_t)w * sizeof(float), h, hipMemcpyDeviceToHost));
     }
     HIP_TRY(c, hipDeviceSynchronize());
+    return SRT_OK;
+}
+
+extern "C" {
+
+int srt_read_fb_rowmajor(srt_ctx *c, float *r, float *g, float *b, uint32_t image_width, uint32_t image_height) {
+    if (!c || !c->d_fb || !r || !g || !b || image_width == 0 || image_height == 0) return fail(c, SRT_ERR_INVALID, "srt_read_fb_rowmajor: bad argument");
+    const float *src[3] = {c->d_fb, c->d_fb + (size_t)c->n_lanes, c->d_fb + 2 * (size_t)c->n_lanes};
+    float *const host[3] = {r, g, b};
+    return read_rowmajor(c, src, host, image_width, image_height);
+}
+
+int srt_read_accum_stats(srt_ctx *c, uint32_t *samples, float *sum_y, float *sum_y2, uint32_t image_width, uint32_t image_height) {
+    if (!c || image_width == 0 || image_height == 0) return fail(c, SRT_ERR_INVALID, "srt_read_accum_stats: bad argument");
+    if (c->accum_state != srt_ctx::kAccumBound)
+        return fail(c, SRT_ERR_INVALID, "srt_read_accum_stats: no accumulation with a pass (srt_accum_reset[_adaptive] and srt_render_chunk_accum first)");
+    if ((samples || sum_y2) && !c->accum_adaptive)
+        return fail(c, SRT_ERR_INVALID, "srt_read_accum_stats: sample counts and S2 belong to an adaptive accumulation (srt_accum_reset_adaptive)");
+    const size_t nl = c->n_lanes;
+    const float *y = reinterpret_cast<const float *>(c->d_accum + kAccumHeaderBytes) + nl;
+    const float *s2 = c->accum_adaptive ? reinterpret_cast<const float *>(c->d_adapt) : y;
+    const float *st = c->accum_adaptive ? reinterpret_cast<const float *>(c->d_adapt) + nl : y;
+    const float *src[3] = {st, y, s2};
+    float *const host[3] = {reinterpret_cast<float *>(samples), sum_y, sum_y2};
+    const int rc = read_rowmajor(c, src, host, image_width, image_height);
+    if (rc != SRT_OK || !samples) return rc;
+    // the state words carry the converged flag in bit 31: the map holds the sample counts alone
+    if (c->last_offx < image_width && c->last_offy < image_height) {
+        const uint32_t w = std::min<uint32_t>(std::min<uint32_t>(c->last_w, c->tx * c->bx), image_width - c->last_offx);
+        const uint32_t h = std::min<uint32_t>(std::min<uint32_t>(c->last_h, c->ty * c->by), image_height - c->last_offy);
+        for (uint32_t j = 0; j < h; j++)
+            for (uint32_t i = 0; i < w; i++) samples[(size_t)(c->last_offy + j) * image_width + c->last_offx + i] &= ~kAdaptConverged;
+    }
     return SRT_OK;
 }
 
@@ -682,6 +817,12 @@ int srt_get_stats(srt_ctx *c, srt_stats *out) {
     for (int k = 0; k < 4; k++) out->shade[k] = h[15 + k];
     for (int k = 0; k < 4; k++) out->waves[k] = h[19 + k];   // instrumented: waves, sum / max of their life times, drain time
     out->hits = h[24];
+    if (c->stats_adaptive) {      // an adaptive pass: the pixels that rendered in it, counted on the device (adapt_flag_kernel)
+        unsigned long long counts = 0;
+        HIP_TRY(c, hipMemcpy(&counts, c->d_adapt_queue + 4, sizeof(counts), hipMemcpyDeviceToHost));
+        out->paths = (counts & 0xffffffffull) * c->stats_spp;
+        return SRT_OK;
+    }
     // paths = spp * pixels owned by this rank
     uint64_t pixels = 0;
     for (uint32_t t = c->rank; t < c->n_tiles; t += c->world) {

@@ -365,6 +365,28 @@ int srt_comm_accum_reset(srt_comm *c) {
     return SRT_OK;
 }
 
+int srt_comm_accum_reset_adaptive(srt_comm *c, const srt_adaptive *cfg) {
+    if (!c) return cfail(c, SRT_ERR_INVALID, "srt_comm_accum_reset_adaptive: null comm");
+    if (!c->owns_ctx)
+        return cfail(c, SRT_ERR_UNSUPPORTED, "srt_comm_accum_reset_adaptive: not on a process-per-GPU communicator (a stop decision would need a "
+                                             "reduction across processes)");
+    for (srt_ctx *x : c->ctx) { int rc = srt_accum_reset_adaptive(x, cfg); if (rc != SRT_OK) return cfail(c, rc, srt_last_error(x)); }
+    return SRT_OK;
+}
+
+int srt_comm_accum_active(srt_comm *c, uint64_t *active) {
+    if (!c || !active) return cfail(c, SRT_ERR_INVALID, "srt_comm_accum_active: null argument");
+    uint64_t sum = 0;
+    for (srt_ctx *x : c->ctx) {
+        uint64_t a = 0;
+        int rc = srt_accum_active(x, &a);
+        if (rc != SRT_OK) return cfail(c, rc, srt_last_error(x));
+        sum += a;
+    }
+    *active = sum;
+    return SRT_OK;
+}
+
 // time the local ranks spent between the end of their render kernel and the end of the exchange of the last frame (the gather,
 // plus the scatter on rank 0; includes waiting for the slowest rank): max over the local contexts, ms.  0 for a 1-rank world.
 int srt_comm_last_gather_ms(srt_comm *c, float *ms) {

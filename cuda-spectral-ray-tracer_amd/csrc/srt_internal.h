@@ -86,11 +86,24 @@ constexpr unsigned long long kOrderProfileMagic = 0x5352544f52444552ull;
 // the plain production kernels stay as they are.  sums: three planes of n_lanes floats (X, Y, Z), indexed by the block-linear idx like
 // the RNG planes; a pixel starts from its stored sum and stores it back when its samples of the pass are done.  spp_total: the samples
 // per pixel the sums hold after this pass (the normalisation of the written framebuffer).
+// Adaptive accumulations (MODE 4, srt_accum_reset_adaptive) read the fields behind `pad` as well: sum2, the plane of per-pixel sums of
+// the squared per-sample luminance, and state, the plane of per-pixel state words (samples held | kAdaptConverged); the stopping
+// criterion's parameters.  srt_accum_reset_adaptive writes them once; the per-pass kernel rewrites only sums and spp_total.
 struct AccumHeader {
     float *sums;
     uint32_t spp_total;
     uint32_t pad;
+    float *sum2;
+    uint32_t *state;
+    float rel_tol, abs_tol;
+    uint32_t min_spp, pad2;
 };
+constexpr uint32_t kAdaptConverged = 0x80000000u;      // state word: the pixel has stopped (the low 31 bits: the samples it holds)
+
+// The stopping test of render_kernel MODE 4 (srt_kernels.hip, adaptive_converged), fp32 without contraction, in this order
+// (n = spp_total, S1 = the pixel's Y sum, S2 = its sum of squared per-sample Y):
+//   mean = S1 / n;  v = S2 / n - mean * mean;  v = max(v, 0);  var_mean = v / (n - 1);  tol = rel_tol * mean + abs_tol
+//   converged = n >= min_spp && var_mean <= tol * tol, and not converged when S1, S2, mean * mean or tol * tol is NaN or infinite
 
 struct ScatterParams {
     const float *gathered;     // [rank][group (groups of them)][tiles_padded][plane of the group][lane]
@@ -105,9 +118,22 @@ hipError_t launch_init_rng(uint32_t *rng, uint32_t n_lanes, uint64_t seed, hipSt
 // Test knobs of a context (srt_set_test_knobs; from the environment only under SRT_TEST_KNOBS=1, read once at srt_create): they pick
 // the kernel variant / cache size a launch plan would not pick by itself, so that every instantiated variant can be held to the CPU oracle by the tests.
 struct PlanKnobs { bool wide_refs = false; int lds_cache_max = -1; };
-// mode 0 render, 1 instrumented, 2 cost probe, 3 accumulating render (p.wave_debug -> AccumHeader); waves_launched (optional) = persistent waves of the launch
+// mode 0 render, 1 instrumented, 2 cost probe, 3 accumulating render (p.wave_debug -> AccumHeader), 4 adaptive accumulating render; waves_launched (optional) = persistent waves of the launch
 hipError_t launch_render(const RenderParams &p, const PlanKnobs &knobs, uint32_t n_cu, int mode, hipStream_t st, uint32_t *waves_launched = nullptr);
 hipError_t launch_accum_header(AccumHeader *dst, float *sums, uint32_t spp_total, hipStream_t st);      // writes *dst on the stream
+// Pixel queue of the next adaptive pass (see adapt_flag_kernel): the rows of `src_rows` (src_info[0] of them; nullptr: the identity
+// queue of n_identity local tiles) whose share of the tile still holds an active pixel, in their order, into dst_rows / dst_info[0..1];
+// counts[0] += pixels that rendered in the pass that just ended, counts[1] += pixels still active.  flags: one word per source row.
+struct AdaptQueueParams {
+    const uint32_t *src_rows, *src_info;
+    uint32_t n_identity;
+    uint32_t *dst_rows, *dst_info, *flags;
+    unsigned long long *counts;
+    const uint32_t *state;
+    uint32_t spp_total;
+    uint32_t width, height, tx, ty, bx, by, tiles_x, n_tiles, rank, world, lane_limit;
+};
+hipError_t launch_adapt_queue(const AdaptQueueParams &p, uint32_t n_rows_bound, hipStream_t st);
 hipError_t launch_order_tiles(const uint32_t *cost, uint32_t *sorted, uint32_t *rows, uint32_t n, uint32_t n_waves,
                               uint32_t split_load_pct, uint32_t *queue_info, uint32_t order_max_pct, hipStream_t st);
 hipError_t launch_scatter(const ScatterParams &p, hipStream_t st);

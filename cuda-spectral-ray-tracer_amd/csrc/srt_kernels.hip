@@ -120,6 +120,21 @@ __global__ void init_rng_kernel(uint32_t *rng, uint32_t n_lanes, uint64_t seed) 
     rng[5 * (size_t)n_lanes + idx] = s.v4;
 }
 
+// The stopping test of an adaptive accumulation (srt_internal.h next to AccumHeader): fp32, no contraction (the build's
+// -ffp-contract=off), correctly rounded divisions, in exactly this order -- tests/test_adaptive*.py restate it in numpy float32 and
+// must reproduce every decision.  s1 = the pixel's Y sum, s2 = its sum of squared per-sample Y, both over n samples.
+__device__ __forceinline__ bool adaptive_converged(float s1, float s2, uint32_t n_samples, uint32_t min_spp, float rel_tol, float abs_tol) {
+    const float n = (float)n_samples;
+    const float mean = s1 / n;
+    const float mm = mean * mean;
+    float v = s2 / n - mm;
+    v = v > 0.0f ? v : 0.0f;
+    const float var_mean = v / (n - 1.0f);
+    const float tol = rel_tol * mean + abs_tol;
+    const float tt = tol * tol;
+    const bool finite = __builtin_isfinite(s1) && __builtin_isfinite(s2) && __builtin_isfinite(mm) && __builtin_isfinite(tt);
+    return n_samples >= min_spp && finite && var_mean <= tt;
+}
 
 // One lane = a small state machine that owns one pixel at a time:
 //   TRAV   (tv.node >= 0)                 walking the BVH for its current ray
@@ -136,6 +151,9 @@ __global__ void init_rng_kernel(uint32_t *rng, uint32_t n_lanes, uint64_t seed) 
 // pixel from a COPY of the RNG state, writes nothing but the per-tile traversal cost used to order the pixel queue.  MODE 3:
 // production that accumulates across launches -- a pixel starts from its stored XYZ sum instead of zero, stores the sum back when its
 // P.spp samples are done and normalises by the running total (AccumHeader behind P.wave_debug, srt_render_chunk_accum); the rest is MODE 0.
+// MODE 4: MODE 3 of an adaptive accumulation -- a pixel whose state word says "converged" is skipped at the fetch like a pixel outside
+// the chunk; a pixel also carries the sum of its squared per-sample Y (acc2) across passes, and at the pixel switch it tests the
+// stopping criterion (adaptive_converged) and writes its state word.
 // ALL_CACHED: the whole inner tree fits the LDS cache (n_cached == n_inner): the INNER step has no global fall-back path.
 // PAIRED (instantiated for <., 1, 1> and <., 0, 0>): every FRINGE record holds two triangles (srt_scene_is_paired): the visit has no box test.
 template <int MODE, bool NARROW, bool ALL_CACHED, bool PAIRED>
@@ -143,7 +161,12 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
     constexpr bool COUNT = (MODE == 1);
     constexpr bool PROBE = (MODE == 2);
     constexpr bool ITERS = COUNT || PROBE;
-    constexpr bool ACCUM = (MODE == 3);
+    constexpr bool ACCUM = (MODE == 3 || MODE == 4);
+    constexpr bool ADAPT = (MODE == 4);
+    // (S2 of the current pixel: in a register -- acc2 -- except in the wide-reference, partly-L2, unpaired shape, which is at the
+    // 128-VGPR limit already and would spill it to scratch: there each path end adds its y * y to the pixel's own S2 word in memory.
+    // The same additions in the same order: the result is the same bits.  profiles/adaptive/mode4_resource_usage.txt)
+    constexpr bool S2_MEM = ADAPT && !NARROW && !ALL_CACHED && !PAIRED;
     extern __shared__ float4 lds4[];
     lds_uniforms *U = (lds_uniforms *)lds4;
     float4 *s_cmf = lds4 + kLdsUniF4;
@@ -178,6 +201,11 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
             const AccumHeader *ah = reinterpret_cast<const AccumHeader *>(P.wave_debug);
             split_ptr(ah->sums, U->accum_sums);
             U->spp_total = ah->spp_total;
+        }
+        if constexpr (ADAPT) {
+            const AccumHeader *ah = reinterpret_cast<const AccumHeader *>(P.wave_debug);
+            split_ptr(ah->sum2, U->accum_sum2); split_ptr(ah->state, U->accum_state);
+            U->min_spp = ah->min_spp; U->rel_tol = ah->rel_tol; U->abs_tol = ah->abs_tol;
         }
     }
     for (uint32_t k = threadIdx.x; k < kLdsCmfF4; k += blockDim.x) s_cmf[k] = P.cmf[k];
@@ -222,6 +250,7 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
     uint32_t pixel_ij = 0;                  // chunk-relative column | row << 16 (both are 16-bit quantities, Q17)
     Rng rs; rs.d = rs.v0 = rs.v1 = rs.v2 = rs.v3 = rs.v4 = 0u;
     V3 acc = mk(0.f, 0.f, 0.f);             // pixel_color (rendering.cu:212)
+    float acc2 = 0.f;                       // MODE 4: sum of the squared per-sample Y of the current pixel
     uint32_t sample = 0, bounce = 0, valid = 0;
     V3 ro = mk(0.f, 0.f, 0.f), rd = mk(0.f, 0.f, 1.f), inv = mk(0.f, 0.f, 1.f);
     float hero = kLambdaMin;
@@ -392,6 +421,13 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
             // ---- S2: path end: pixel_color += dev_spectrum_to_XYZ(...) (rendering.cu:227, color.cu:88-104) --------
             if (end_path) {
                 acc = acc + mk(xyz_x, xyz_y, xyz_z);
+                // (a bounce-limit end adds 0: xyz_y is 0 then)
+                if constexpr (S2_MEM) {
+                    float *s2 = join_ptr<float>(U->accum_sum2[0], U->accum_sum2[1]) + idx;
+                    *s2 = *s2 + xyz_y * xyz_y;
+                } else if constexpr (ADAPT) {
+                    acc2 = acc2 + xyz_y * xyz_y;
+                }
                 have_path = false;
             }
 
@@ -420,6 +456,14 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
                         float *sums = join_ptr<float>(U->accum_sums[0], U->accum_sums[1]);
                         const size_t nl = U->n_lanes;
                         sums[0 * nl + idx] = acc.x; sums[1 * nl + idx] = acc.y; sums[2 * nl + idx] = acc.z;
+                    }
+                    if constexpr (ADAPT) {      // S2 goes back with the sums; the pixel's decision for the next pass
+                        float *s2 = join_ptr<float>(U->accum_sum2[0], U->accum_sum2[1]) + idx;
+                        if constexpr (S2_MEM) acc2 = *s2;
+                        else *s2 = acc2;
+                        const uint32_t total = U->spp_total;
+                        const bool stop = adaptive_converged(acc.y, acc2, total, U->min_spp, U->rel_tol, U->abs_tol);
+                        join_ptr<uint32_t>(U->accum_state[0], U->accum_state[1])[idx] = total | (stop ? kAdaptConverged : 0u);
                     }
                     // pixel_color / float(spp) -> (1/spp) * v ; XYZ_to_sRGB (color.cu:35-41, vec3.cuh:80-91)
                     // (accumulating: the sum holds spp_total samples, of which this launch drew the last P.spp)
@@ -500,6 +544,10 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
                         const uint32_t gtx = U->tx, gty = U->ty, gbx = U->bx;
                         // pixels outside the chunk (or the reference grid) never touch RNG or output (rendering.cu:205)
                         if ((tile < U->n_tiles) && (lt < U->lane_limit) && (i < U->width) && (j < U->height) && (i / gtx < gbx) && (j / gty < U->by)) {
+                            if constexpr (ADAPT) {      // a converged pixel is left alone (no RNG draw, no store): fetch again
+                                const uint32_t *state = join_ptr<const uint32_t>(U->accum_state[0], U->accum_state[1]);
+                                if (state[block_linear_idx(i, j, gtx, gty, gbx)] & kAdaptConverged) continue;
+                            }
                             idx = block_linear_idx(i, j, gtx, gty, gbx);
                             out_slot = tile_local * (uint32_t)(kGroupPlanes * kTileLanes) + lt;
                             pixel_ij = i | (j << 16);
@@ -513,6 +561,7 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
                                 const float *sums = join_ptr<const float>(U->accum_sums[0], U->accum_sums[1]);
                                 const size_t nl = U->n_lanes;
                                 acc = mk(sums[0 * nl + idx], sums[1 * nl + idx], sums[2 * nl + idx]);
+                                if constexpr (ADAPT && !S2_MEM) acc2 = join_ptr<const float>(U->accum_sum2[0], U->accum_sum2[1])[idx];
                             } else {
                                 acc = mk(0.f, 0.f, 0.f);
                             }
@@ -1059,9 +1108,11 @@ hipError_t launch_render(const RenderParams &p, const PlanKnobs &knobs, uint32_t
     const bool narrow = render_narrow_refs(p.n_records, knobs);
     if (mode == 1) return narrow ? launch_render_mode<1, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<1, false>(p, knobs, n_cu, st, waves_launched);
     if (mode == 2) return narrow ? launch_render_mode<2, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<2, false>(p, knobs, n_cu, st, waves_launched);
-    if (mode != 3) return narrow ? launch_render_mode<0, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<0, false>(p, knobs, n_cu, st, waves_launched);
+    if (mode != 3 && mode != 4) return narrow ? launch_render_mode<0, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<0, false>(p, knobs, n_cu, st, waves_launched);
     // (instantiated after the production variants: their place in the object, and so the labels of their ISA listing, stay as they were)
-    return narrow ? launch_render_mode<3, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<3, false>(p, knobs, n_cu, st, waves_launched);
+    if (mode == 3) return narrow ? launch_render_mode<3, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<3, false>(p, knobs, n_cu, st, waves_launched);
+    // (and the adaptive ones after the accumulating ones, for the same reason)
+    return narrow ? launch_render_mode<4, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<4, false>(p, knobs, n_cu, st, waves_launched);
 }
 
 hipError_t launch_order_tiles(const uint32_t *cost, uint32_t *sorted, uint32_t *rows, uint32_t n, uint32_t n_waves,
@@ -1109,6 +1160,70 @@ __global__ void accum_header_kernel(AccumHeader *dst, float *sums, uint32_t spp_
 
 hipError_t launch_accum_header(AccumHeader *dst, float *sums, uint32_t spp_total, hipStream_t st) {
     hipLaunchKernelGGL(accum_header_kernel<0>, dim3(1), dim3(64), 0, st, dst, sums, spp_total);
+    return hipGetLastError();
+}
+
+// Pixel queue of the next adaptive pass (MODE 4), built on the device right after the pass: no host synchronisation between passes.
+// adapt_flag_kernel: one wave per source row (the probe's cost-descending queue, or the identity order of the local tiles when the
+// accumulation runs unordered); a lane looks at the state word of its slot of the row's share, exactly as render_kernel's fetch maps
+// slots to pixels.  The row stays when a pixel of its share is still active.  The same pass counts the pixels that rendered in the pass
+// just ended (their sample count is the new total: every other pixel stopped earlier) and those still active: one 64-bit
+// wave-aggregated atomic per wave, rendered in the low word, active in the high word (a rank holds fewer than 2^32 pixels, Q17).
+// adapt_scan_kernel: one workgroup keeps the flagged rows in their order (contiguous pieces per thread, then a scan, as
+// order_tiles_kernel does).  Templates, instantiated here at the end of the unit (see accum_header_kernel).
+template <int>
+__global__ __launch_bounds__(256) void adapt_flag_kernel(const AdaptQueueParams P) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
+    const uint32_t n_rows = P.src_info ? P.src_info[0] : P.n_identity;
+    uint32_t rendered = 0, active = 0;
+    for (uint32_t r = wave; r < n_rows; r += n_waves) {
+        const uint32_t row = P.src_rows ? P.src_rows[r] : r;
+        const uint32_t tile_local = P.src_rows ? (row & 0x3fffffu) : r;
+        const uint32_t part = P.src_rows ? (row >> 22) & 63u : 0u, s = P.src_rows ? (row >> 28) & 7u : 0u;
+        const uint32_t tile = P.rank + P.world * tile_local;
+        const uint32_t i = (tile % P.tiles_x) * 8u + (lane & 7u), j = (tile / P.tiles_x) * 8u + (lane >> 3);
+        bool rend = false, act = false;
+        if ((lane >> (6u - s)) == part && tile < P.n_tiles && lane < P.lane_limit && i < P.width && j < P.height && i / P.tx < P.bx && j / P.ty < P.by) {
+            const uint32_t st = P.state[block_linear_idx(i, j, P.tx, P.ty, P.bx)];
+            rend = (st & ~kAdaptConverged) == P.spp_total;
+            act = rend && (st & kAdaptConverged) == 0u;
+        }
+        const unsigned long long ma = __ballot(act);
+        rendered += (uint32_t)__popcll(__ballot(rend));
+        active += (uint32_t)__popcll(ma);
+        if (lane == 0) P.flags[r] = ma != 0ull ? 1u : 0u;
+    }
+    if (lane == 0 && rendered) atomicAdd(P.counts, (unsigned long long)rendered | ((unsigned long long)active << 32));
+}
+
+template <int>
+__global__ __launch_bounds__(1024) void adapt_scan_kernel(const AdaptQueueParams P) {
+    __shared__ uint32_t s_scan[1024];
+    const uint32_t t = threadIdx.x;
+    const uint32_t n = P.src_info ? P.src_info[0] : P.n_identity;
+    const uint32_t per = (n + 1023u) / 1024u;
+    const uint32_t lo = min(n, t * per), hi = min(n, lo + per);
+    uint32_t mine = 0;
+    for (uint32_t k = lo; k < hi; k++) mine += P.flags[k];
+    s_scan[t] = mine;
+    __syncthreads();
+    if (t == 0) {
+        uint32_t acc = 0;
+        for (uint32_t b = 0; b < 1024u; b++) { const uint32_t c = s_scan[b]; s_scan[b] = acc; acc += c; }
+        P.dst_info[0] = acc;
+        P.dst_info[1] = P.src_info ? P.src_info[1] : 0u;      // the most expensive tile's probe cost: the wave priorities keep their scale
+    }
+    __syncthreads();
+    uint32_t at = s_scan[t];
+    for (uint32_t k = lo; k < hi; k++)
+        if (P.flags[k]) P.dst_rows[at++] = P.src_rows ? P.src_rows[k] : k;
+}
+
+hipError_t launch_adapt_queue(const AdaptQueueParams &p, uint32_t n_rows_bound, hipStream_t st) {
+    const uint32_t waves = n_rows_bound < 1u ? 1u : (n_rows_bound > 4096u ? 4096u : n_rows_bound);
+    hipLaunchKernelGGL(adapt_flag_kernel<0>, dim3((waves + 3u) / 4u), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(adapt_scan_kernel<0>, dim3(1), dim3(1024), 0, st, p);
     return hipGetLastError();
 }
 

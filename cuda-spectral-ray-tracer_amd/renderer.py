@@ -100,6 +100,28 @@ class Renderer:
         self._ck(B.lib().srt_accum_samples(self._h, C.byref(n)))
         return n.value
 
+    def accum_reset_adaptive(self, rel_tol, abs_tol=0.0, min_spp=16):
+        """start an ADAPTIVE accumulation (srt_c_api.h): like accum_reset, and each later pass adds its samples only to the pixels that
+        have not converged -- a pixel stops once the variance of its mean luminance is at most (rel_tol * mean + abs_tol)^2, after at
+        least min_spp samples.  A pixel that stopped after n samples holds exactly the plain n-spp render's value."""
+        self._ck(B.lib().srt_accum_reset_adaptive(self._h, C.byref(adaptive_config(rel_tol, abs_tol, min_spp))))
+
+    @property
+    def accum_active(self):
+        """pixels of this rank still active after the last adaptive pass (0 before the first pass); synchronises"""
+        n = C.c_uint64()
+        self._ck(B.lib().srt_accum_active(self._h, C.byref(n)))
+        return n.value
+
+    def accum_stats(self, image_width, image_height):
+        """row-major maps of the adaptive accumulation's chunk: dict(samples=uint32, sum_y=float32, sum_y2=float32), each of
+        image_width * image_height entries; only the chunk's rectangle is written (zeros elsewhere, and at pixels of other ranks)"""
+        n = image_width * image_height
+        samples, sum_y, sum_y2 = np.zeros(n, np.uint32), np.zeros(n, np.float32), np.zeros(n, np.float32)
+        self._ck(B.lib().srt_read_accum_stats(self._h, samples.ctypes.data_as(C.POINTER(C.c_uint32)), B.fptr(sum_y), B.fptr(sum_y2),
+                                              image_width, image_height))
+        return dict(samples=samples, sum_y=sum_y, sum_y2=sum_y2)
+
     def set_gather_planes(self, planes):
         """3 (default): the exchange unit is the quantised framebuffer; 9: + the parity planes (unquantised sRGB, XYZ sums)"""
         self._ck(B.lib().srt_set_gather_planes(self._h, planes))
@@ -301,6 +323,17 @@ class Comm:
         """Renderer.accum_reset on every local rank"""
         self._ck(B.lib().srt_comm_accum_reset(self._h))
 
+    def accum_reset_adaptive(self, rel_tol, abs_tol=0.0, min_spp=16):
+        """Renderer.accum_reset_adaptive on every local rank (not on a process-per-GPU communicator: SrtError)"""
+        self._ck(B.lib().srt_comm_accum_reset_adaptive(self._h, C.byref(adaptive_config(rel_tol, abs_tol, min_spp))))
+
+    @property
+    def accum_active(self):
+        """active pixels summed over the local ranks"""
+        n = C.c_uint64()
+        self._ck(B.lib().srt_comm_accum_active(self._h, C.byref(n)))
+        return n.value
+
     def render_frame_accum(self, width, height, spp_add, offx=0, offy=0):
         """render_frame with an accumulating pass of spp_add samples on every rank (Renderer.render_chunk_accum)"""
         self._ck(B.lib().srt_render_frame_multi_accum(self._h, width, height, offx, offy, spp_add))
@@ -416,6 +449,80 @@ def _progressive_passes(scene, cam, width, height, sched, bounce_limit, seed, de
             out = dict(fb=r.read_fb(), lin=r.read_fb_aux(1), xyz=r.read_fb_aux(2), rowmajor=r.read_fb_rowmajor(width, height),
                        stats=r.stats(), kernel_ms=r.last_kernel_ms(), geom=dict(r.geom))
             yield r.accum_samples, out
+    finally:
+        if r._h:
+            r.set_gather_planes(planes_before)
+        if renderer is None:
+            r.close()
+
+
+def adaptive_config(rel_tol, abs_tol=0.0, min_spp=16):
+    """srt_adaptive from Python numbers, checked as the library checks it (ValueError): min_spp a whole number >= 2, both tolerances
+    finite and >= 0 in float32, and not both 0"""
+    import math
+    try:
+        with np.errstate(over="ignore"):          # (a value beyond float32 becomes inf, refused below)
+            rel, ab = float(np.float32(rel_tol)), float(np.float32(abs_tol))
+    except (TypeError, ValueError):
+        raise ValueError("adaptive sampling: rel_tol and abs_tol must be numbers, got %r, %r" % (rel_tol, abs_tol))
+    if not (math.isfinite(rel) and math.isfinite(ab)) or rel < 0.0 or ab < 0.0 or not (rel + ab > 0.0):
+        raise ValueError("adaptive sampling: rel_tol and abs_tol must be finite and >= 0, and not both 0; got %r, %r" % (rel_tol, abs_tol))
+    if isinstance(min_spp, bool) or int(min_spp) != min_spp or not 2 <= int(min_spp) <= MAX_SPP:
+        raise ValueError("adaptive sampling: min_spp must be a whole number in [2, %d], got %r" % (MAX_SPP, min_spp))
+    return B.Adaptive(rel, ab, int(min_spp), 0)
+
+
+def adaptive_schedule(min_spp, step, max_spp):
+    """the samples of every pass of render_adaptive: max(min_spp, step) first, then step, the last pass clipped so that the total reaches
+    max_spp exactly (fewer passes run when every pixel stops earlier).  Checked (ValueError)."""
+    for name, v in (("min_spp", min_spp), ("step", step), ("max_spp", max_spp)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("render_adaptive: %s must be a whole number, got %r" % (name, v))
+    if step <= 0:
+        raise ValueError("render_adaptive: step must be > 0, got %r" % (step,))
+    if not 2 <= min_spp <= max_spp:
+        raise ValueError("render_adaptive: need 2 <= min_spp <= max_spp, got min_spp %r, max_spp %r" % (min_spp, max_spp))
+    if max_spp > MAX_SPP:
+        raise ValueError("render_adaptive: max_spp %d is more than %d (16-bit spp)" % (max_spp, MAX_SPP))
+    sched = [min(max(min_spp, step), max_spp)]
+    while sum(sched) < max_spp:
+        sched.append(min(step, max_spp - sum(sched)))
+    return [int(s) for s in sched]
+
+
+def render_adaptive(scene, cam, width, height, bounce_limit, rel_tol, abs_tol=0.0, min_spp=16, step=16, max_spp=1024, seed=1984, device=0,
+                    renderer=None):
+    """Adaptive whole-image render on one GPU: a generator of (spp_total, active_pixels, result) after each pass, `result` with the keys
+    of render_image plus `samples` (row-major uint32 map of the samples each pixel holds).  The first pass adds max(min_spp, step)
+    samples, every later one `step` (the last clipped to reach max_spp); a pixel stops once the variance of its mean luminance is at
+    most (rel_tol * mean + abs_tol)^2 (srt_c_api.h).  Stops when no pixel is active or max_spp is reached.  A pixel holding n samples is
+    bit-identical to render_image(..., spp=n, ...) there.  The arguments are checked here, before any device is touched."""
+    cfg = adaptive_config(rel_tol, abs_tol, min_spp)
+    sched = adaptive_schedule(min_spp, step, max_spp)
+    return _adaptive_passes(scene, cam, width, height, bounce_limit, cfg, sched, seed, device, renderer)
+
+
+def _adaptive_passes(scene, cam, width, height, bounce_limit, cfg, sched, seed, device, renderer):
+    r = renderer or Renderer(device)
+    planes_before = r.gather_planes
+    try:
+        r.upload_scene(scene)
+        r.set_camera(cam)
+        r.init_device_params(width, height, sum(sched), bounce_limit, seed)
+        r.set_partition(0, 1)
+        r.set_count_traversal(False)
+        r.set_gather_planes(9)            # before the reset: a change of the planes ends an adaptive accumulation
+        r._ck(B.lib().srt_accum_reset_adaptive(r._h, C.byref(cfg)))
+        for spp_add in sched:
+            r.render_chunk_accum(width, height, spp_add)
+            r.scatter_tiles()
+            active = r.accum_active
+            out = dict(fb=r.read_fb(), lin=r.read_fb_aux(1), xyz=r.read_fb_aux(2), rowmajor=r.read_fb_rowmajor(width, height),
+                       stats=r.stats(), kernel_ms=r.last_kernel_ms(), geom=dict(r.geom),
+                       samples=r.accum_stats(width, height)["samples"])
+            yield r.accum_samples, active, out
+            if active == 0:
+                break
     finally:
         if r._h:
             r.set_gather_planes(planes_before)

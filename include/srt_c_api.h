@@ -252,6 +252,36 @@ SRT_API int srt_accum_reset(srt_ctx *ctx);
 SRT_API int srt_render_chunk_accum(srt_ctx *ctx, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy, uint32_t spp_add, void *stream);
 SRT_API int srt_accum_samples(const srt_ctx *ctx, uint32_t *spp_total);     /* samples per pixel the sums hold (0 right after a reset) */
 
+/* Adaptive sampling (no reference counterpart).  An ADAPTIVE accumulation also keeps, per pixel, S2 -- the sum of the squared
+ * per-sample luminance (the Y each sample's path adds to the pixel's XYZ sum; 0 for a path ended by the bounce limit) -- and a
+ * state word: the samples the pixel holds and a "converged" flag.  Each srt_render_chunk_accum adds spp_add samples to the ACTIVE
+ * pixels only; a converged pixel is left alone (no RNG draw, sums, S2 and tile-buffer slots unchanged), so every active pixel holds
+ * the running total.  At the end of a pass every pixel that rendered in it tests, in fp32 without contraction and in this order
+ * (n = (float)spp_total, S1 = its Y sum):
+ *     mean = S1 / n;  v = S2 / n - mean * mean;  v = v > 0 ? v : 0;  var_mean = v / (n - 1);  tol = rel_tol * mean + abs_tol;
+ *     converged = spp_total >= min_spp && var_mean <= tol * tol     (never when S1, S2, mean * mean or tol * tol is NaN or inf)
+ * A pixel that stopped after n samples holds exactly what a plain launch of n spp gives it: quantised and parity planes, XYZ sums
+ * and RNG state.  Decisions depend on the pixel's own sums alone, so the image does not depend on partition, world size or launch.
+ * After each pass the next pass's pixel queue is compacted on the device (rows of tiles with an active pixel, in the probe's
+ * order); the tile buffer is not cleared between adaptive passes (converged pixels keep their slots).
+ *   srt_accum_reset_adaptive  srt_accum_reset + zeroed S2 and state planes (allocated on first use, 8 B per lane of the grid).
+ *                             cfg: min_spp >= 2, rel_tol >= 0, abs_tol >= 0, rel_tol + abs_tol > 0, all finite, reserved == 0 --
+ *                             else SRT_ERR_INVALID with nothing changed; an instrumented context: SRT_ERR_UNSUPPORTED.
+ *                             srt_accum_reset makes the next accumulation a plain one again.  srt_set_gather_planes invalidates
+ *                             an adaptive accumulation (converged pixels would keep stale planes); the other invalidations are
+ *                             those of srt_accum_reset.  A pass with no active pixel is legal: it changes nothing but the total.
+ *   srt_accum_active          pixels still active after the last pass (synchronises); 0 before the first pass, which binds the
+ *                             chunk.  SRT_ERR_INVALID when the context holds no adaptive accumulation.
+ *   srt_read_accum_stats      row-major maps of the accumulation's chunk, placed like srt_read_fb_rowmajor (only the chunk's
+ *                             rectangle of the caller's arrays is written): samples per pixel, Y sums, S2.  Any pointer may be
+ *                             NULL; samples and sum_y2 need an adaptive accumulation, sum_y any accumulation with a pass.  Pixels
+ *                             owned by other ranks read as 0.
+ * srt_get_stats after an adaptive pass: paths = pixels that rendered in it x spp_add, counted on the device. */
+typedef struct { float rel_tol, abs_tol; uint32_t min_spp, reserved; } srt_adaptive;
+SRT_API int srt_accum_reset_adaptive(srt_ctx *ctx, const srt_adaptive *cfg);
+SRT_API int srt_accum_active(srt_ctx *ctx, uint64_t *active);
+SRT_API int srt_read_accum_stats(srt_ctx *ctx, uint32_t *samples, float *sum_y, float *sum_y2, uint32_t image_width, uint32_t image_height);
+
 /* Compact tile buffer of this rank (device memory): three plane GROUPS of tiles_padded * 3 * 64 floats each,
  * [group][tile][plane][lane] -- group 0 = quantised r,g,b (the reference's frame_buffer values, 12 B / pixel), group 1 =
  * unquantised sRGB r,g,b, group 2 = XYZ sums (parity planes).  tiles_padded = ceil(n_tiles/world), so every rank's buffer has
@@ -359,6 +389,11 @@ SRT_API int srt_render_frame_multi(srt_comm *comm, uint32_t width, uint32_t heig
  * (srt_render_chunk_accum, spp_add samples) on every rank's own tiles.  The gather moves the tile buffers exactly as for a plain frame. */
 SRT_API int srt_comm_accum_reset(srt_comm *comm);
 SRT_API int srt_render_frame_multi_accum(srt_comm *comm, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy, uint32_t spp_add);
+/* Adaptive sampling on W GPUs: srt_accum_reset_adaptive on every local context (then srt_render_frame_multi_accum as above), and the
+ * active pixels summed over the local contexts.  A process-per-GPU communicator (srt_comm_init_rank) returns SRT_ERR_UNSUPPORTED: a
+ * stop decision there would need a reduction across processes. */
+SRT_API int srt_comm_accum_reset_adaptive(srt_comm *comm, const srt_adaptive *cfg);
+SRT_API int srt_comm_accum_active(srt_comm *comm, uint64_t *active);
 SRT_API int srt_comm_synchronize(srt_comm *comm);
 /* Closest-hit queries / paths of the last frame summed over the local ranks, and the slowest local render kernel. */
 SRT_API int srt_comm_stats(srt_comm *comm, uint64_t *rays, uint64_t *paths, float *max_kernel_ms);

@@ -1,0 +1,461 @@
+"""Adaptive sampling (srt_accum_reset_adaptive + srt_render_chunk_accum, render_kernel MODE 4).  A pixel that stopped after n samples
+holds exactly what a plain n-spp launch gives it (the RNG stream belongs to the pixel), so the adaptive image is a patchwork of exact
+one-shot frames; every comparison here is bit for bit, and every stop decision is reproduced by a numpy float32 restatement of the
+criterion (test_adaptive_api.converged_f32)."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from helpers import assert_planes_equal, bits, oracle_scene_for
+from test_adaptive_api import converged_f32
+from test_progressive import _soup, _workload
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ERR_INVALID, ERR_UNSUPPORTED = -1, -5
+SCHED, MIN_SPP = [8, 4, 4, 4, 4], 8
+NEVER = 1e-30          # a relative tolerance no pixel with any variance meets (tol^2 underflows to 0)
+
+
+def _lane_of(geom, W, H):
+    """block-linear lane of every row-major pixel of a W x H chunk at (0, 0) (rendering.cu:156-165)"""
+    tx, ty, bx = geom["tx"], geom["ty"], geom["bx"]
+    j, i = np.divmod(np.arange(W * H), W)
+    gbx, gby = i // tx, j // ty
+    return (j - gby * ty) * tx + (i - gbx * tx) + tx * ty * (gby * bx + gbx)
+
+
+def _fresh(gpu, scene, cam, W, H, depth, spp=12):
+    gpu.upload_scene(scene); gpu.set_camera(cam); gpu.set_partition(0, 1); gpu.set_count_traversal(False)
+    gpu.set_gather_planes(9)
+    gpu.init_device_params(W, H, spp, depth, 1984)
+
+
+def _frame(gpu, W, H):
+    gpu.scatter_tiles()
+    return dict(fb=gpu.read_fb(), lin=gpu.read_fb_aux(1), xyz=gpu.read_fb_aux(2), rowmajor=gpu.read_fb_rowmajor(W, H))
+
+
+def _adaptive(gpu, scene, cam, W, H, depth, rel_tol, sched=SCHED, min_spp=MIN_SPP, abs_tol=0.0):
+    """an adaptive run; per pass: dict(total, active, paths, stats (accum_stats), frame)"""
+    _fresh(gpu, scene, cam, W, H, depth)
+    gpu.accum_reset_adaptive(rel_tol, abs_tol, min_spp)
+    assert gpu.accum_active == 0
+    out = []
+    for s in sched:
+        gpu.render_chunk_accum(W, H, s)
+        out.append(dict(total=gpu.accum_samples, active=gpu.accum_active, paths=gpu.stats()["paths"], stats=gpu.accum_stats(W, H),
+                        frame=_frame(gpu, W, H)))
+    return out
+
+
+def _predict(never, rel_tol, abs_tol=0.0, min_spp=MIN_SPP):
+    """samples map after every pass, from a run that never stops (its S1 / S2 at every boundary are those of every run)"""
+    n_pix = never[0]["stats"]["sum_y"].size
+    stop = np.zeros(n_pix, np.int64)           # 0: still active
+    maps, actives = [], []
+    for p in never:
+        t = p["total"]
+        conv = converged_f32(p["stats"]["sum_y"], p["stats"]["sum_y2"], t, min_spp, rel_tol, abs_tol)
+        stop[(stop == 0) & conv] = t
+        maps.append(np.where(stop == 0, t, stop))
+        actives.append(int((stop == 0).sum()))
+    return maps, stop, actives
+
+
+def _pick_tolerance(never):
+    """the relative tolerance (on a fine geometric grid) under which the schedule ends with the most distinct sample counts while some
+    pixels are still active: scenes with much background (constant luminance: those pixels stop at min_spp) have few pixels to spread"""
+    best, best_n = None, 0
+    for rel in np.geomspace(1e-4, 10.0, 241):
+        maps, stop, _ = _predict(never, float(rel))
+        n = len(np.unique(maps[-1]))
+        if (stop == 0).any() and n > best_n:
+            best, best_n = float(rel), n
+    assert best is not None, "no tolerance leaves a pixel active"
+    return best
+
+
+def _assert_pixels_equal(got, want, mask, lane, what):
+    """the pixels of `mask` (row-major) are bit-identical in the quantised, sRGB and XYZ planes and in the row-major image"""
+    for k in ("fb", "lin", "xyz"):
+        for c in range(3):
+            a, b = bits(got[k][c])[lane[mask]], bits(want[k][c])[lane[mask]]
+            assert np.array_equal(a, b), "%s %s plane %d: %d of %d pixels differ" % (what, k, c, int((a != b).sum()), a.size)
+    for c in range(3):
+        a, b = bits(got["rowmajor"][c])[mask], bits(want["rowmajor"][c])[mask]
+        assert np.array_equal(a, b), "%s row-major plane %d: %d of %d pixels differ" % (what, c, int((a != b).sum()), a.size)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["prism", "cornell", "random_spheres", "dielectric"])
+def test_each_pixel_equals_the_one_shot_frame_of_its_count(srt, gpu, orc, name):
+    scene, cam, W, H, depth, mode = _workload(srt, name)
+    never = _adaptive(gpu, scene, cam, W, H, depth, NEVER)
+    rel = _pick_tolerance(never)
+    run = _adaptive(gpu, scene, cam, W, H, depth, rel)
+    last = run[-1]
+    counts = last["stats"]["samples"]
+    assert last["total"] == sum(SCHED) and last["active"] > 0
+    assert len(np.unique(counts)) >= 3, np.unique(counts)
+    lane = _lane_of(gpu.geom, W, H)
+    osc = oracle_scene_for(orc, scene, mode) if name in ("prism", "cornell") else None
+    for c in np.unique(counts):
+        mask = counts == c
+        one_shot = srt.render_image(scene, cam, W, H, int(c), depth, renderer=gpu)
+        _assert_pixels_equal(last["frame"], one_shot, mask, lane, "%s: %d pixels at %d spp" % (name, mask.sum(), c))
+        if osc is not None:
+            ref = osc.render(cam, W, H, int(c), depth)
+            for k in ("fb", "lin", "xyz"):
+                for p in range(3):
+                    assert np.array_equal(bits(last["frame"][k][p])[lane[mask]], bits(ref[k][p])[lane[mask]]), (name, c, k, p)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["prism", "dielectric"])
+def test_decisions_match_the_float32_restatement(srt, gpu, name):
+    """which pixels stop at which boundary, after every pass, with no tolerance; and the sums a pixel holds are those of the run that
+    never stops at the same count (S1, S2 exact across runs)"""
+    scene, cam, W, H, depth, _ = _workload(srt, name)
+    never = _adaptive(gpu, scene, cam, W, H, depth, NEVER)
+    for rel, ab in ((_pick_tolerance(never), 0.0), (0.05, 1e-3), (0.5, 0.0)):
+        run = _adaptive(gpu, scene, cam, W, H, depth, rel, abs_tol=ab)
+        maps, _, actives = _predict(never, rel, ab)
+        for k, (p, want, act) in enumerate(zip(run, maps, actives)):
+            got = p["stats"]["samples"]
+            assert np.array_equal(got, want), "rel %g abs %g pass %d: %d pixels differ" % (rel, ab, k, int((got != want).sum()))
+            assert p["active"] == act, (rel, ab, k, p["active"], act)
+        final = run[-1]["stats"]
+        for k, p in enumerate(never):
+            at = final["samples"] == p["total"]
+            for key in ("sum_y", "sum_y2"):
+                assert np.array_equal(bits(final[key])[at], bits(p["stats"][key])[at]), (rel, key, k)
+
+
+@pytest.mark.gpu
+def test_s2_is_the_sequential_float32_sum_of_squares(srt, gpu):
+    scene, cam, W, H, depth, _ = _workload(srt, "dielectric")
+    N = 12
+    _fresh(gpu, scene, cam, W, H, depth)
+    ys = []
+    for _ in range(N):           # accum_reset zeroes the sums and does not re-seed: pass k's Y sum is sample k's Y
+        gpu.accum_reset()
+        gpu.render_chunk_accum(W, H, 1)
+        ys.append(_sum_y(gpu, W, H))
+    ys = np.array(ys, np.float32)
+    run = _adaptive(gpu, scene, cam, W, H, depth, NEVER, sched=[2, 4, 6], min_spp=2)
+    st = run[-1]["stats"]
+    s1 = np.zeros(W * H, np.float32); s2 = np.zeros(W * H, np.float32)
+    want1 = np.zeros(W * H, np.float32); want2 = np.zeros(W * H, np.float32)
+    for k in range(N):
+        s1 = s1 + ys[k]
+        s2 = s2 + ys[k] * ys[k]
+        at = st["samples"] == k + 1
+        want1[at], want2[at] = s1[at], s2[at]
+    assert (st["samples"] == N).sum() > W * H // 2
+    assert np.array_equal(bits(st["sum_y"]), bits(want1))
+    assert np.array_equal(bits(st["sum_y2"]), bits(want2))
+
+
+def _sum_y(gpu, W, H):
+    """Y sums of a plain accumulation (sum_y needs no adaptive one)"""
+    y = np.zeros(W * H, np.float32)
+    gpu._ck(gpu_lib().srt_read_accum_stats(gpu._h, None, y.ctypes.data_as(C.POINTER(C.c_float)), None, W, H))
+    return y
+
+
+def gpu_lib():
+    import importlib
+    return importlib.import_module("cuda-spectral-ray-tracer_amd").binding.lib()
+
+
+@pytest.mark.gpu
+def test_plain_render_after_adaptive_run_continues_each_pixels_stream(srt, gpu, orc):
+    """a plain launch after an adaptive run equals the oracle continued from each pixel's RNG state after its own count"""
+    scene, cam, W, H, depth, mode = _workload(srt, "prism")
+    never = _adaptive(gpu, scene, cam, W, H, depth, NEVER)
+    rel = _pick_tolerance(never)
+    spp_next = 3
+    _fresh(gpu, scene, cam, W, H, depth, spp=spp_next)
+    gpu.accum_reset_adaptive(rel, 0.0, MIN_SPP)
+    for s in SCHED:
+        gpu.render_chunk_accum(W, H, s)
+    counts = gpu.accum_stats(W, H)["samples"]
+    assert len(np.unique(counts)) >= 3
+    gpu.render_chunk(W, H)
+    after = _frame(gpu, W, H)
+    osc = oracle_scene_for(orc, scene, mode)
+    n = gpu.geom["n_lanes"]
+    init = np.zeros(6 * n, np.uint32)
+    for idx in range(n):
+        s = orc.Rng()
+        orc.lib().orc_rng_init(1984 + idx, C.byref(s))
+        init[6 * idx: 6 * idx + 6] = [s.d] + list(s.v)
+    states = init.copy()
+    lane = _lane_of(gpu.geom, W, H)
+    for c in np.unique(counts):
+        st = init.copy()
+        osc.render(cam, W, H, int(c), depth, states=st)
+        for p in lane[counts == c]:
+            states[6 * p: 6 * p + 6] = st[6 * p: 6 * p + 6]
+    ref = osc.render(cam, W, H, spp_next, depth, states=states)
+    assert_planes_equal(after["xyz"], ref["xyz"], "plain launch after the adaptive run, XYZ")
+    assert_planes_equal(after["fb"], ref["fb"], "plain launch after the adaptive run, fb")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("knobs,paired,expect", [
+    (dict(), True, (1, 1, 1)),
+    (dict(wide_refs=True, lds_cache_max=3), True, (0, 0, 1)),
+    (dict(), False, (1, 1, 0)),
+    (dict(lds_cache_max=3), False, (1, 0, 0)),
+    (dict(wide_refs=True), False, (0, 1, 0)),
+    (dict(wide_refs=True, lds_cache_max=0), False, (0, 0, 0)),
+], ids=["narrow-cached-paired", "wide-partial-paired", "narrow-cached", "narrow-partial", "wide-cached", "wide-partial"])
+def test_every_adaptive_shape_gives_the_same_image(srt, gpu, knobs, paired, expect):
+    n = 600 if paired else 601
+    scene = _soup(srt, n, n).build_bvh(srt.BVH_SAH, 1984)
+    assert scene.is_paired == paired
+    W, H, depth = 48, 32, 8
+    cam = srt.camera_init(W, H, 50.0, (0.5, 1.0, 16.0), (0.0, 0.0, 0.0), defocus_angle=0.6, focus_dist=14.0)
+    gpu.set_test_knobs()
+    ref = _adaptive(gpu, scene, cam, W, H, depth, 0.2)[-1]
+    assert len(np.unique(ref["stats"]["samples"])) >= 2
+    gpu.set_test_knobs(**knobs)
+    try:
+        got = _adaptive(gpu, scene, cam, W, H, depth, 0.2)[-1]
+        plan = gpu.launch_plan()
+        assert (int(plan["narrow_refs"]), int(plan["all_cached"]), int(plan["paired"])) == expect, plan
+    finally:
+        gpu.set_test_knobs()
+        gpu.upload_scene(scene)
+    assert np.array_equal(got["stats"]["samples"], ref["stats"]["samples"])
+    for k in ("fb", "lin", "xyz", "rowmajor"):
+        assert_planes_equal(got["frame"][k], ref["frame"][k], "shape %r %s" % (expect, k))
+    assert got["active"] == ref["active"]
+
+
+@pytest.mark.gpu
+def test_partitions_and_offset_chunk(srt, gpu):
+    import torch
+    scene, cam, W, H, depth, _ = _workload(srt, "random_spheres")
+    rel = 0.1
+    ref = _adaptive(gpu, scene, cam, W, H, depth, rel)[-1]
+    assert len(np.unique(ref["stats"]["samples"])) >= 2
+    for world in (2, 3):
+        parts, samples, active = [], np.zeros(W * H, np.uint32), 0
+        for rank in range(world):
+            _fresh(gpu, scene, cam, W, H, depth)
+            gpu.set_partition(rank, world)
+            gpu.accum_reset_adaptive(rel, 0.0, MIN_SPP)
+            for s in SCHED:
+                gpu.render_chunk_accum(W, H, s)
+            gpu.synchronize()
+            samples += gpu.accum_stats(W, H)["samples"]      # (pixels of the other ranks read 0)
+            active += gpu.accum_active
+            _, n_floats, _, _ = gpu.tile_buffer()
+            staging = torch.empty(n_floats, dtype=torch.float32, device="cuda")
+            gpu.copy_tile_buffer(staging.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+            parts.append(staging.cpu().numpy().copy())
+        gathered = torch.from_numpy(np.concatenate(parts)).cuda()
+        gpu.scatter_tiles(gathered.data_ptr())
+        gpu.synchronize()
+        assert np.array_equal(samples, ref["stats"]["samples"]), world
+        assert active == ref["active"], world
+        assert_planes_equal(gpu.read_fb(), ref["frame"]["fb"], "world %d fb" % world)
+        assert_planes_equal(gpu.read_fb_aux(1), ref["frame"]["lin"], "world %d lin" % world)
+        assert_planes_equal(gpu.read_fb_aux(2), ref["frame"]["xyz"], "world %d xyz" % world)
+    gpu.set_partition(0, 1)
+
+    # a 30 x 20 chunk at (17, 9) of a 64 x 40 image: each pixel of the chunk equals the one-shot chunk of its count
+    IW, IH, cw, ch, ox, oy = 64, 40, 30, 20, 17, 9
+    cam = scene.default_camera(IW, IH)
+
+    def chunk(spp=None):
+        _fresh(gpu, scene, cam, cw, ch, depth, spp=spp or 12)
+        if spp is None:
+            gpu.accum_reset_adaptive(rel, 0.0, MIN_SPP)
+            for s in SCHED:
+                gpu.render_chunk_accum(cw, ch, s, ox, oy)
+        else:
+            gpu.render_chunk(cw, ch, ox, oy)
+        gpu.scatter_tiles()
+        return dict(fb=gpu.read_fb(), lin=gpu.read_fb_aux(1), xyz=gpu.read_fb_aux(2), rowmajor=gpu.read_fb_rowmajor(IW, IH),
+                    samples=gpu.accum_stats(IW, IH)["samples"] if spp is None else None)
+    got = chunk()
+    counts = got["samples"]
+    inside = np.zeros((IH, IW), bool); inside[oy:oy + ch, ox:ox + cw] = True
+    inside = inside.ravel()
+    assert (counts[~inside] == 0).all() and (counts[inside] > 0).all()
+    j, i = np.divmod(np.arange(IW * IH), IW)
+    lane = np.zeros(IW * IH, np.int64)
+    geom = gpu.geom
+    ci, cj = i[inside] - ox, j[inside] - oy
+    lane_c = _lane_of(geom, cw, ch)
+    lane[inside] = lane_c[cj * cw + ci]
+    for c in np.unique(counts[inside]):
+        mask = inside & (counts == c)
+        _assert_pixels_equal(got, chunk(int(c)), mask, lane, "offset chunk, %d spp" % c)
+
+
+@pytest.mark.gpu
+def test_comm_two_and_three_ranks_one_gpu_mock_transport():
+    mock = os.path.join(ROOT, "tests", "cpp", "_build", "libmock_rccl.so")
+    assert os.path.exists(mock), "tests/cpp/_build/libmock_rccl.so is built by __graft_entry__.build()"
+    code = """
+import importlib, sys
+import numpy as np
+sys.path.insert(0, %r); sys.path.insert(0, %r)
+srt = importlib.import_module('cuda-spectral-ray-tracer_amd')
+from helpers import assert_planes_equal
+scene = srt.Scene.builtin(srt.SCENE_RANDOM_SPHERES).build_bvh(srt.BVH_SAH, 1984)
+W, H, depth, rel = 150, 90, 16, 0.1
+cam = scene.default_camera(W, H)
+steps = list(srt.render_adaptive(scene, cam, W, H, depth, rel, min_spp=8, step=4, max_spp=24))
+total, active, ref = steps[-1]
+assert total == 24 and active > 0 and len(np.unique(ref['samples'])) >= 2, (total, active)
+for world in (2, 3):
+    comm = srt.Comm.init_all([0] * world)
+    comm.set_gather_planes(9)
+    comm.upload_scene(scene); comm.set_camera(cam)
+    comm.init_device_params(W, H, 24, depth, 1984)
+    comm.accum_reset_adaptive(rel, 0.0, 8)
+    assert comm.accum_active == 0
+    for s in (8, 4, 4, 4, 4):
+        comm.render_frame_accum(W, H, s)
+    comm.synchronize()
+    assert comm.accum_active == active, (world, comm.accum_active, active)
+    root = comm.root
+    assert_planes_equal(root.read_fb(), ref['fb'], 'world %%d fb' %% world)
+    assert_planes_equal(root.read_fb_aux(1), ref['lin'], 'world %%d lin' %% world)
+    assert_planes_equal(root.read_fb_aux(2), ref['xyz'], 'world %%d xyz' %% world)
+    samples = sum(r.accum_stats(W, H)['samples'] for r in comm.renderers)
+    assert np.array_equal(samples, ref['samples']), world
+    comm.close()
+r = srt.Renderer(0)
+c1 = srt.Comm.init_rank(r, srt.Comm.unique_id(), 0, 1)
+c1.upload_scene(scene); c1.set_camera(cam); c1.init_device_params(W, H, 24, depth, 1984)
+try:
+    c1.accum_reset_adaptive(rel)
+    raise SystemExit('process-per-GPU adaptive reset was accepted')
+except srt.SrtError as e:
+    assert e.code == -5, e
+c1.close(); r.close()
+print('adaptive mock transport ok')
+""" % (ROOT, os.path.join(ROOT, "tests"))
+    env = dict(os.environ, SRT_RCCL_LIB=mock, SRT_COMM_TEST_SAME_DEVICE="1", SRT_TEST_KNOBS="1")
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "adaptive mock transport ok" in out.stdout, (out.stdout[-1500:], out.stderr[-3000:])
+
+
+@pytest.mark.gpu
+def test_compaction_counts_and_the_pass_after_convergence(srt, gpu):
+    scene, cam, W, H, depth, _ = _workload(srt, "dielectric")
+    never = _adaptive(gpu, scene, cam, W, H, depth, NEVER)
+    run = _adaptive(gpu, scene, cam, W, H, depth, _pick_tolerance(never))
+    before = W * H
+    for p, s in zip(run, SCHED):
+        assert p["paths"] == before * s, (p["total"], p["paths"], before, s)
+        before = p["active"]
+    # everything stops after the first pass (min_spp samples); a later pass renders nothing and changes nothing but the total
+    spp_next = 3
+    _fresh(gpu, scene, cam, W, H, depth, spp=spp_next)
+    gpu.accum_reset_adaptive(1e3, 1e3, MIN_SPP)
+    gpu.render_chunk_accum(W, H, MIN_SPP)
+    first = _frame(gpu, W, H)
+    assert gpu.accum_active == 0 and gpu.stats()["paths"] == W * H * MIN_SPP
+    stats_first = gpu.accum_stats(W, H)
+    gpu.render_chunk_accum(W, H, 4)
+    assert gpu.stats()["paths"] == 0 and gpu.accum_active == 0 and gpu.accum_samples == MIN_SPP + 4
+    again = _frame(gpu, W, H)
+    for k in ("fb", "lin", "xyz", "rowmajor"):
+        assert_planes_equal(again[k], first[k], "pass after convergence " + k)
+    stats_again = gpu.accum_stats(W, H)
+    for k in ("samples", "sum_y", "sum_y2"):
+        assert np.array_equal(stats_again[k].view(np.uint32), stats_first[k].view(np.uint32)), k
+    gpu.render_chunk(W, H)           # the RNG states are those after MIN_SPP samples: a plain launch continues from there
+    after = _frame(gpu, W, H)
+    _fresh(gpu, scene, cam, W, H, depth, spp=spp_next)
+    gpu.accum_reset()
+    gpu.render_chunk_accum(W, H, MIN_SPP)
+    gpu.render_chunk(W, H)
+    want = _frame(gpu, W, H)
+    for k in ("fb", "lin", "xyz", "rowmajor"):
+        assert_planes_equal(after[k], want[k], "plain launch after the converged adaptive run " + k)
+
+
+def _expect_error(srt, fn, code, what):
+    with pytest.raises(srt.SrtError) as e:
+        fn()
+    assert e.value.code == code, (what, e.value)
+
+
+@pytest.mark.gpu
+def test_refusals_and_invalidation(srt, gpu):
+    scene, cam, W, H, depth, _ = _workload(srt, "prism")
+    one_shot = srt.render_image(scene, cam, W, H, 12, depth, renderer=gpu)
+    L = gpu_lib()
+    _fresh(gpu, scene, cam, W, H, depth)
+    _expect_error(srt, lambda: gpu.accum_active, ERR_INVALID, "accum_active without an adaptive accumulation")
+    gpu.accum_reset_adaptive(0.1, 0.0, 4)
+    gpu.render_chunk_accum(W, H, 4)
+    first = _frame(gpu, W, H)
+    active = gpu.accum_active
+    bad = [(0.0, 0.0, 4, 0), (-0.1, 0.0, 4, 0), (0.1, -1.0, 4, 0), (float("nan"), 0.0, 4, 0), (float("inf"), 0.0, 4, 0),
+           (0.1, 0.0, 1, 0), (0.1, 0.0, 0, 0), (0.1, 0.0, 4, 1)]
+    for rel, ab, mn, res in bad:        # straight through the C-ABI: the Python check would refuse most of them first
+        cfg = srt.binding.Adaptive(rel, ab, mn, res)
+        rc = L.srt_accum_reset_adaptive(gpu._h, C.byref(cfg))
+        assert rc == ERR_INVALID, (rel, ab, mn, res, rc)
+        assert gpu.accum_samples == 4 and gpu.accum_active == active, (rel, ab, mn, res)
+    assert L.srt_accum_reset_adaptive(gpu._h, None) == ERR_INVALID
+    gpu.set_count_traversal(True)
+    _expect_error(srt, lambda: gpu.accum_reset_adaptive(0.1), ERR_UNSUPPORTED, "instrumented context")
+    _expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 4), ERR_UNSUPPORTED, "instrumented pass")
+    gpu.set_count_traversal(False)
+    for k, v in _frame(gpu, W, H).items():
+        assert_planes_equal(v, first[k], "after the refusals " + k)
+    gpu.render_chunk_accum(W, H, 4)         # the accumulation survived the refusals
+    assert gpu.accum_samples == 8
+    # srt_set_gather_planes ends an adaptive accumulation (not a plain one: test_progressive)
+    gpu.set_gather_planes(9)
+    _expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 4), ERR_INVALID, "pass after srt_set_gather_planes")
+    _expect_error(srt, lambda: gpu.accum_active, ERR_INVALID, "accum_active after srt_set_gather_planes")
+    # the other invalidations of an accumulation hold for an adaptive one too
+    for what, call in (("srt_set_camera", lambda: gpu.set_camera(cam)), ("srt_render_chunk", lambda: gpu.render_chunk(W, H))):
+        _fresh(gpu, scene, cam, W, H, depth)
+        gpu.accum_reset_adaptive(0.1, 0.0, 4)
+        gpu.render_chunk_accum(W, H, 4)
+        call()
+        _expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 4), ERR_INVALID, what)
+    # a plain accumulation after an adaptive one behaves as before: passes of 5 + 7 are the one-shot 12-spp frame
+    _fresh(gpu, scene, cam, W, H, depth)
+    gpu.accum_reset_adaptive(0.1, 0.0, 4)
+    gpu.render_chunk_accum(W, H, 4)
+    _fresh(gpu, scene, cam, W, H, depth)
+    gpu.accum_reset()
+    _expect_error(srt, lambda: gpu.accum_active, ERR_INVALID, "accum_active on a plain accumulation")
+    for s in (5, 7):
+        gpu.render_chunk_accum(W, H, s)
+    assert gpu.stats()["paths"] == W * H * 7
+    got = _frame(gpu, W, H)
+    for k in ("fb", "lin", "xyz", "rowmajor"):
+        assert_planes_equal(got[k], one_shot[k], "plain accumulation after an adaptive one " + k)
+    gpu.set_gather_planes(3)
+
+
+@pytest.mark.gpu
+def test_render_adaptive_generator(srt, gpu):
+    scene, cam, W, H, depth, _ = _workload(srt, "cornell")
+    steps = list(srt.render_adaptive(scene, cam, W, H, depth, 0.05, min_spp=8, step=4, max_spp=24, renderer=gpu))
+    assert [t for t, _, _ in steps] == [8, 12, 16, 20, 24][:len(steps)]
+    for t, active, res in steps:
+        assert set(res) == {"fb", "lin", "xyz", "rowmajor", "stats", "kernel_ms", "geom", "samples"}
+        assert res["samples"].max() == t and 0 < active <= int((res["samples"] == t).sum())
+    # a tolerance every pixel meets at once: one pass, then stop
+    steps = list(srt.render_adaptive(scene, cam, W, H, depth, 1e3, abs_tol=1e3, min_spp=8, step=4, max_spp=24, renderer=gpu))
+    assert len(steps) == 1 and steps[0][:2] == (8, 0)
