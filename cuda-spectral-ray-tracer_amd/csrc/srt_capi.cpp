@@ -101,6 +101,13 @@ struct srt_ctx {
     uint32_t *d_adapt_queue = nullptr;
     size_t adapt_queue_rows = 0;
     bool stats_adaptive = false;                        // the last launch was an adaptive pass: srt_get_stats reads its pixel count
+    // spectral film (srt_accum_reset_spectral): kFilmStride floats per lane of film_lanes, allocated on first use; the row-major staging
+    // buffer of srt_read_spectral (film_staging_floats of them)
+    bool accum_spectral = false;                        // the current accumulation keeps a film (MODE 5 passes)
+    float *d_film = nullptr;
+    uint64_t film_lanes = 0;
+    float *d_film_staging = nullptr;
+    size_t film_staging_floats = 0;
 };
 
 namespace {
@@ -223,7 +230,7 @@ void srt_destroy(srt_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    void *bufs[] = {c->d_nodes, c->d_nodes_sw, c->d_fringe, c->d_tris, c->d_mat_sd, c->d_mat_par, c->d_shade, c->d_cmf, c->d_rng, c->d_fb, c->d_tiles, c->d_counters, c->d_tile_cost, c->d_tile_order, c->d_rowmajor, c->d_wave_debug, c->d_accum, c->d_adapt, c->d_adapt_queue};
+    void *bufs[] = {c->d_nodes, c->d_nodes_sw, c->d_fringe, c->d_tris, c->d_mat_sd, c->d_mat_par, c->d_shade, c->d_cmf, c->d_rng, c->d_fb, c->d_tiles, c->d_counters, c->d_tile_cost, c->d_tile_order, c->d_rowmajor, c->d_wave_debug, c->d_accum, c->d_adapt, c->d_adapt_queue, c->d_film, c->d_film_staging};
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -393,6 +400,7 @@ int render_chunk_impl(srt_ctx *c, uint32_t width, uint32_t height, uint32_t offx
     const bool accum = spp_add != 0;
     const bool adapt = accum && c->accum_adaptive;      // MODE 4
     const bool adapt_later = adapt && c->accum_state == srt_ctx::kAccumBound;
+    const bool spectral = accum && c->accum_spectral;   // MODE 5
     c->last_w = width; c->last_h = height; c->last_offx = offx; c->last_offy = offy;
     // Tiles cover every pixel the reference grid can address, whatever the size of THIS chunk: the tile number of a lane
     // idx -- and with it the rank that owns the lane's persistent RNG stream (Q13) -- must not move when a ragged edge
@@ -510,8 +518,8 @@ int render_chunk_impl(srt_ctx *c, uint32_t width, uint32_t height, uint32_t offx
     RoctxRange range_render("srt render_kernel");
     HIP_TRY(c, hipEventRecord(c->ev0, st));     // ev0..ev1 bracket the render kernel alone (roofline.achieved)
     uint32_t waves_launched = 0;
-    if (accum) p.wave_debug = reinterpret_cast<uint32_t *>(c->d_accum);      // MODE 3 / 4 read their AccumHeader there
-    HIP_TRY(c, launch_render(p, c->knobs, (uint32_t)c->n_cu, adapt ? 4 : accum ? 3 : (c->count_traversal ? 1 : 0), st, &waves_launched));
+    if (accum) p.wave_debug = reinterpret_cast<uint32_t *>(c->d_accum);      // MODE 3 / 4 / 5 read their AccumHeader there
+    HIP_TRY(c, launch_render(p, c->knobs, (uint32_t)c->n_cu, adapt ? 4 : spectral ? 5 : accum ? 3 : (c->count_traversal ? 1 : 0), st, &waves_launched));
     if (c->count_traversal && waves_launched > c->wave_debug_waves)
         return fail(c, SRT_ERR_HIP, "srt_render_chunk: the launch started more waves than the debug buffer holds (launch plan and launcher disagree)");
     HIP_TRY(c, hipEventRecord(c->ev1, st));
@@ -572,6 +580,36 @@ int srt_accum_reset(srt_ctx *c) {
     HIP_TRY(c, hipDeviceSynchronize());
     c->accum_total = 0;
     c->accum_adaptive = false;
+    c->accum_spectral = false;
+    c->accum_state = srt_ctx::kAccumEmpty;
+    return SRT_OK;
+}
+
+int srt_accum_reset_spectral(srt_ctx *c) {
+    if (!c) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_spectral: null ctx");
+    // refusals first: a refused call leaves the context's accumulation as it was
+    if (c->count_traversal)
+        return fail(c, SRT_ERR_UNSUPPORTED, "srt_accum_reset_spectral: no instrumented accumulating kernel (srt_set_count_traversal(ctx, 0) first)");
+    if (!c->params_ready) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_spectral: device parameters must be set first (srt_init_device_params)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint64_t lanes = c->n_lanes;
+    if (!c->d_film || c->film_lanes != lanes) {
+        // (the new film is allocated before the old one goes: a failed allocation changes nothing)
+        float *film = nullptr;
+        HIP_TRY(c, hipMalloc((void **)&film, lanes * kFilmStride * sizeof(float)));
+        if (c->d_film) { (void)hipDeviceSynchronize(); (void)hipFree(c->d_film); }
+        c->d_film = film;
+        c->film_lanes = lanes;
+    }
+    int rc = srt_accum_reset(c);
+    if (rc != SRT_OK) return rc;
+    c->accum_state = srt_ctx::kAccumInvalid;      // (until the film is in place)
+    HIP_TRY(c, hipMemset(c->d_film, 0, lanes * kFilmStride * sizeof(float)));
+    // the film's slot of the header (the per-pass kernel rewrites only sums and spp_total)
+    float *film = c->d_film;
+    HIP_TRY(c, hipMemcpy(c->d_accum + offsetof(AccumHeader, film), &film, sizeof(film), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipDeviceSynchronize());
+    c->accum_spectral = true;
     c->accum_state = srt_ctx::kAccumEmpty;
     return SRT_OK;
 }
@@ -790,6 +828,35 @@ int srt_read_accum_stats(srt_ctx *c, uint32_t *samples, float *sum_y, float *sum
         for (uint32_t j = 0; j < h; j++)
             for (uint32_t i = 0; i < w; i++) samples[(size_t)(c->last_offy + j) * image_width + c->last_offx + i] &= ~kAdaptConverged;
     }
+    return SRT_OK;
+}
+
+int srt_read_spectral(srt_ctx *c, uint32_t first, uint32_t count, float *out, uint32_t image_width, uint32_t image_height) {
+    if (!c || !out || image_width == 0 || image_height == 0) return fail(c, SRT_ERR_INVALID, "srt_read_spectral: bad argument");
+    if (count == 0 || (uint64_t)first + count > kFilmSamples)
+        return fail(c, SRT_ERR_INVALID, "srt_read_spectral: the range [first, first + count) must be a non-empty part of the 95 grid samples");
+    if (!c->accum_spectral || c->accum_state != srt_ctx::kAccumBound)
+        return fail(c, SRT_ERR_INVALID, "srt_read_spectral: no spectral accumulation with a pass (srt_accum_reset_spectral and srt_render_chunk_accum first)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->last_offx < image_width && c->last_offy < image_height) {
+        // the chunk's rectangle, clipped to the reference grid and the image (srt_read_fb_rowmajor's placement): un-swizzled on the device
+        // into a [h][w][count] staging block, then one 2-D copy into the caller's [image_height][image_width][count] array
+        const uint32_t w = std::min<uint32_t>(std::min<uint32_t>(c->last_w, c->tx * c->bx), image_width - c->last_offx);
+        const uint32_t h = std::min<uint32_t>(std::min<uint32_t>(c->last_h, c->ty * c->by), image_height - c->last_offy);
+        const size_t n = (size_t)w * h * count;
+        if (n) {
+            if (c->film_staging_floats < n) {
+                if (c->d_film_staging) { HIP_TRY(c, hipDeviceSynchronize()); (void)hipFree(c->d_film_staging); c->d_film_staging = nullptr; c->film_staging_floats = 0; }
+                HIP_TRY(c, hipMalloc((void **)&c->d_film_staging, n * sizeof(float)));
+                c->film_staging_floats = n;
+            }
+            HIP_TRY(c, launch_film_unswizzle(c->d_film, c->d_film_staging, first, count, w, h, c->tx, c->ty, c->bx, nullptr));
+            const size_t row = (size_t)w * count * sizeof(float), pitch = (size_t)image_width * count * sizeof(float);
+            float *dst = out + ((size_t)c->last_offy * image_width + c->last_offx) * count;
+            HIP_TRY(c, hipMemcpy2D(dst, pitch, c->d_film_staging, row, row, h, hipMemcpyDeviceToHost));
+        }
+    }
+    HIP_TRY(c, hipDeviceSynchronize());
     return SRT_OK;
 }
 

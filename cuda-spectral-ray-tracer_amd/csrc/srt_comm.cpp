@@ -374,6 +374,12 @@ int srt_comm_accum_reset_adaptive(srt_comm *c, const srt_adaptive *cfg) {
     return SRT_OK;
 }
 
+int srt_comm_accum_reset_spectral(srt_comm *c) {
+    if (!c) return cfail(c, SRT_ERR_INVALID, "srt_comm_accum_reset_spectral: null comm");
+    for (srt_ctx *x : c->ctx) { int rc = srt_accum_reset_spectral(x); if (rc != SRT_OK) return cfail(c, rc, srt_last_error(x)); }
+    return SRT_OK;
+}
+
 int srt_comm_accum_active(srt_comm *c, uint64_t *active) {
     if (!c || !active) return cfail(c, SRT_ERR_INVALID, "srt_comm_accum_active: null argument");
     uint64_t sum = 0;

@@ -97,7 +97,12 @@ struct AccumHeader {
     uint32_t *state;
     float rel_tol, abs_tol;
     uint32_t min_spp, pad2;
+    float *film;
 };
+// Spectral accumulations (MODE 5, srt_accum_reset_spectral) read `film` as well: kFilmStride floats per lane of the grid, indexed by the
+// block-linear idx, of which the first kFilmSamples are the raw sums on the CIE grid (360 + 5 j nm); srt_accum_reset_spectral writes it once.
+constexpr uint32_t kFilmSamples = 95;
+constexpr uint32_t kFilmStride = 96;      // 384 B: three 128-B lines per pixel, the last word unused
 constexpr uint32_t kAdaptConverged = 0x80000000u;      // state word: the pixel has stopped (the low 31 bits: the samples it holds)
 
 // The stopping test of render_kernel MODE 4 (srt_kernels.hip, adaptive_converged), fp32 without contraction, in this order
@@ -118,7 +123,7 @@ hipError_t launch_init_rng(uint32_t *rng, uint32_t n_lanes, uint64_t seed, hipSt
 // Test knobs of a context (srt_set_test_knobs; from the environment only under SRT_TEST_KNOBS=1, read once at srt_create): they pick
 // the kernel variant / cache size a launch plan would not pick by itself, so that every instantiated variant can be held to the CPU oracle by the tests.
 struct PlanKnobs { bool wide_refs = false; int lds_cache_max = -1; };
-// mode 0 render, 1 instrumented, 2 cost probe, 3 accumulating render (p.wave_debug -> AccumHeader), 4 adaptive accumulating render; waves_launched (optional) = persistent waves of the launch
+// mode 0 render, 1 instrumented, 2 cost probe, 3 accumulating render (p.wave_debug -> AccumHeader), 4 adaptive accumulating render, 5 spectral accumulating render; waves_launched (optional) = persistent waves of the launch
 hipError_t launch_render(const RenderParams &p, const PlanKnobs &knobs, uint32_t n_cu, int mode, hipStream_t st, uint32_t *waves_launched = nullptr);
 hipError_t launch_accum_header(AccumHeader *dst, float *sums, uint32_t spp_total, hipStream_t st);      // writes *dst on the stream
 // Pixel queue of the next adaptive pass (see adapt_flag_kernel): the rows of `src_rows` (src_info[0] of them; nullptr: the identity
@@ -134,6 +139,9 @@ struct AdaptQueueParams {
     uint32_t width, height, tx, ty, bx, by, tiles_x, n_tiles, rank, world, lane_limit;
 };
 hipError_t launch_adapt_queue(const AdaptQueueParams &p, uint32_t n_rows_bound, hipStream_t st);
+// The film's grid samples [first, first + count) of the w x h pixels at the chunk's origin -> dst[((y * w) + x) * count + (j - first)].
+hipError_t launch_film_unswizzle(const float *film, float *dst, uint32_t first, uint32_t count, uint32_t w, uint32_t h, uint32_t tx,
+                                 uint32_t ty, uint32_t bx, hipStream_t st);
 hipError_t launch_order_tiles(const uint32_t *cost, uint32_t *sorted, uint32_t *rows, uint32_t n, uint32_t n_waves,
                               uint32_t split_load_pct, uint32_t *queue_info, uint32_t order_max_pct, hipStream_t st);
 hipError_t launch_scatter(const ScatterParams &p, hipStream_t st);

@@ -154,6 +154,9 @@ __device__ __forceinline__ bool adaptive_converged(float s1, float s2, uint32_t 
 // MODE 4: MODE 3 of an adaptive accumulation -- a pixel whose state word says "converged" is skipped at the fetch like a pixel outside
 // the chunk; a pixel also carries the sum of its squared per-sample Y (acc2) across passes, and at the pixel switch it tests the
 // stopping criterion (adaptive_converged) and writes its state word.
+// MODE 5: MODE 3 of a spectral accumulation -- every path end that is converted to XYZ (the ends_here block of S1) also adds its
+// seven powers to the pixel's film, 95 fp32 sums on the CIE grid (AccumHeader::film, kFilmStride floats per lane): the hat pair
+// (off_k, off_k + 1) of wavelength k gets ((1 - w_k) * p_k, w_k * p_k), p_k the power the XYZ conversion uses (+0 for k >= valid).
 // ALL_CACHED: the whole inner tree fits the LDS cache (n_cached == n_inner): the INNER step has no global fall-back path.
 // PAIRED (instantiated for <., 1, 1> and <., 0, 0>): every FRINGE record holds two triangles (srt_scene_is_paired): the visit has no box test.
 template <int MODE, bool NARROW, bool ALL_CACHED, bool PAIRED>
@@ -161,8 +164,9 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
     constexpr bool COUNT = (MODE == 1);
     constexpr bool PROBE = (MODE == 2);
     constexpr bool ITERS = COUNT || PROBE;
-    constexpr bool ACCUM = (MODE == 3 || MODE == 4);
+    constexpr bool ACCUM = (MODE == 3 || MODE == 4 || MODE == 5);
     constexpr bool ADAPT = (MODE == 4);
+    constexpr bool FILM = (MODE == 5);
     // (S2 of the current pixel: in a register -- acc2 -- except in the wide-reference, partly-L2, unpaired shape, which is at the
     // 128-VGPR limit already and would spill it to scratch: there each path end adds its y * y to the pixel's own S2 word in memory.
     // The same additions in the same order: the result is the same bits.  profiles/adaptive/mode4_resource_usage.txt)
@@ -207,6 +211,7 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
             split_ptr(ah->sum2, U->accum_sum2); split_ptr(ah->state, U->accum_state);
             U->min_spp = ah->min_spp; U->rel_tol = ah->rel_tol; U->abs_tol = ah->abs_tol;
         }
+        if constexpr (FILM) split_ptr(reinterpret_cast<const AccumHeader *>(P.wave_debug)->film, U->accum_film);
     }
     for (uint32_t k = threadIdx.x; k < kLdsCmfF4; k += blockDim.x) s_cmf[k] = P.cmf[k];
     for (uint32_t k = threadIdx.x; k < nc; k += blockDim.x) {
@@ -405,6 +410,22 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
                         xyz_x += ((1.0f - w) * r0.x + w * r1.x) * power * delta_lambda;
                         xyz_y += ((1.0f - w) * r0.y + w * r1.y) * power * delta_lambda;
                         xyz_z += ((1.0f - w) * r0.z + w * r1.z) * power * delta_lambda;
+                    }
+                    if constexpr (FILM) {
+                        // the film deposit (srt_c_api.h, srt_accum_reset_spectral): one 8-byte read-modify-write per wavelength on the
+                        // pixel's own kFilmStride-float row.  The seven hat pairs never overlap (the wavelengths are 470/7 nm apart),
+                        // so the seven loads go out together; only this lane writes this pixel's row in a launch: no atomics.
+                        float *row = join_ptr<float>(U->accum_film[0], U->accum_film[1]) + (size_t)idx * kFilmStride;
+                        float2 fp[kWavelengths];
+#pragma unroll
+                        for (int k = 0; k < kWavelengths; k++) __builtin_memcpy(&fp[k], row + off[k], sizeof(float2));
+#pragma unroll
+                        for (int k = 0; k < kWavelengths; k++) {
+                            const float w = wgt[k], power = (uint32_t)k < valid ? pw[k] : 0.0f;
+                            fp[k].x = fp[k].x + (1.0f - w) * power;
+                            fp[k].y = fp[k].y + w * power;
+                            __builtin_memcpy(row + off[k], &fp[k], sizeof(float2));
+                        }
                     }
                 }
                 if (was_hit) {
@@ -1108,11 +1129,12 @@ hipError_t launch_render(const RenderParams &p, const PlanKnobs &knobs, uint32_t
     const bool narrow = render_narrow_refs(p.n_records, knobs);
     if (mode == 1) return narrow ? launch_render_mode<1, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<1, false>(p, knobs, n_cu, st, waves_launched);
     if (mode == 2) return narrow ? launch_render_mode<2, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<2, false>(p, knobs, n_cu, st, waves_launched);
-    if (mode != 3 && mode != 4) return narrow ? launch_render_mode<0, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<0, false>(p, knobs, n_cu, st, waves_launched);
+    if (mode < 3 || mode > 5) return narrow ? launch_render_mode<0, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<0, false>(p, knobs, n_cu, st, waves_launched);
     // (instantiated after the production variants: their place in the object, and so the labels of their ISA listing, stay as they were)
     if (mode == 3) return narrow ? launch_render_mode<3, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<3, false>(p, knobs, n_cu, st, waves_launched);
-    // (and the adaptive ones after the accumulating ones, for the same reason)
-    return narrow ? launch_render_mode<4, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<4, false>(p, knobs, n_cu, st, waves_launched);
+    // (and the adaptive ones after the accumulating ones, the spectral ones after those, for the same reason)
+    if (mode == 4) return narrow ? launch_render_mode<4, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<4, false>(p, knobs, n_cu, st, waves_launched);
+    return narrow ? launch_render_mode<5, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<5, false>(p, knobs, n_cu, st, waves_launched);
 }
 
 hipError_t launch_order_tiles(const uint32_t *cost, uint32_t *sorted, uint32_t *rows, uint32_t n, uint32_t n_waves,
@@ -1224,6 +1246,28 @@ hipError_t launch_adapt_queue(const AdaptQueueParams &p, uint32_t n_rows_bound, 
     const uint32_t waves = n_rows_bound < 1u ? 1u : (n_rows_bound > 4096u ? 4096u : n_rows_bound);
     hipLaunchKernelGGL(adapt_flag_kernel<0>, dim3((waves + 3u) / 4u), dim3(256), 0, st, p);
     hipLaunchKernelGGL(adapt_scan_kernel<0>, dim3(1), dim3(1024), 0, st, p);
+    return hipGetLastError();
+}
+
+// The spectral film (MODE 5) -> the caller's row-major [row][col][count] layout: grid samples [first, first + count) of the
+// w x h pixels at the chunk's origin, one thread per (pixel, sample); the rows of dst are w * count floats apart.  A template,
+// instantiated here at the end of the unit (see accum_header_kernel).
+template <int>
+__global__ __launch_bounds__(256) void film_unswizzle_kernel(const float *film, float *dst, uint32_t first, uint32_t count, uint32_t w,
+                                                             uint32_t h, uint32_t tx, uint32_t ty, uint32_t bx) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (size_t)w * h * count) return;
+    const size_t pix = t / count;
+    const uint32_t s = (uint32_t)(t - pix * count);
+    const uint32_t y = (uint32_t)(pix / w), x = (uint32_t)(pix - (size_t)y * w);
+    dst[t] = film[(size_t)block_linear_idx(x, y, tx, ty, bx) * kFilmStride + first + s];
+}
+
+hipError_t launch_film_unswizzle(const float *film, float *dst, uint32_t first, uint32_t count, uint32_t w, uint32_t h, uint32_t tx,
+                                 uint32_t ty, uint32_t bx, hipStream_t st) {
+    const size_t n = (size_t)w * h * count;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(film_unswizzle_kernel<0>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, film, dst, first, count, w, h, tx, ty, bx);
     return hipGetLastError();
 }
 

@@ -8,6 +8,7 @@ import numpy as np
 from . import binding as B
 
 DEFAULT_TX, DEFAULT_TY = 28, 16   # render_manager.cu:93-94
+FILM_SAMPLES = 95                 # the spectral film's grid: 360 + 5 j nm, j = 0 .. 94 (srt_c_api.h, srt_accum_reset_spectral)
 
 
 def reference_grid(chunk_w, chunk_h, tx=DEFAULT_TX, ty=DEFAULT_TY):
@@ -121,6 +122,19 @@ class Renderer:
         self._ck(B.lib().srt_read_accum_stats(self._h, samples.ctypes.data_as(C.POINTER(C.c_uint32)), B.fptr(sum_y), B.fptr(sum_y2),
                                               image_width, image_height))
         return dict(samples=samples, sum_y=sum_y, sum_y2=sum_y2)
+
+    def accum_reset_spectral(self):
+        """start a SPECTRAL accumulation (srt_c_api.h): like accum_reset, and each later pass also adds every path's seven powers to
+        the pixel's film, 95 raw float32 sums on the 5 nm CIE grid (read_spectral; spectral_radiance normalises them).  Never adaptive."""
+        self._ck(B.lib().srt_accum_reset_spectral(self._h))
+
+    def read_spectral(self, image_width, image_height, first=0, count=FILM_SAMPLES, into=None):
+        """raw film sums of grid samples [first, first + count) as float32 (image_height, image_width, count): only the chunk's
+        rectangle is written (zeros elsewhere, and at pixels of other ranks)"""
+        out = np.zeros((image_height, image_width, count), np.float32) if into is None else into
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == image_width * image_height * count
+        self._ck(B.lib().srt_read_spectral(self._h, int(first), int(count), B.fptr(out), image_width, image_height))
+        return out
 
     def set_gather_planes(self, planes):
         """3 (default): the exchange unit is the quantised framebuffer; 9: + the parity planes (unquantised sRGB, XYZ sums)"""
@@ -334,6 +348,21 @@ class Comm:
         self._ck(B.lib().srt_comm_accum_active(self._h, C.byref(n)))
         return n.value
 
+    def accum_reset_spectral(self):
+        """Renderer.accum_reset_spectral on every local rank"""
+        self._ck(B.lib().srt_comm_accum_reset_spectral(self._h))
+
+    def read_spectral(self, image_width, image_height, first=0, count=None):
+        """the film of the frame (Renderer.read_spectral): on a single-process communicator (init_all) the sum of the local ranks' films,
+        which is exact -- every pixel is owned by one rank and reads +0 on the others; on a process-per-GPU communicator (init_rank) THIS
+        rank's film only (its own pixels, +0 elsewhere): there is no gathered film"""
+        count = FILM_SAMPLES - first if count is None else count
+        out = None
+        for r in self.renderers:
+            f = r.read_spectral(image_width, image_height, first, count)
+            out = f if out is None else out + f
+        return out
+
     def render_frame_accum(self, width, height, spp_add, offx=0, offy=0):
         """render_frame with an accumulating pass of spp_add samples on every rank (Renderer.render_chunk_accum)"""
         self._ck(B.lib().srt_render_frame_multi_accum(self._h, width, height, offx, offy, spp_add))
@@ -523,6 +552,75 @@ def _adaptive_passes(scene, cam, width, height, bounce_limit, cfg, sched, seed, 
             yield r.accum_samples, active, out
             if active == 0:
                 break
+    finally:
+        if r._h:
+            r.set_gather_planes(planes_before)
+        if renderer is None:
+            r.close()
+
+
+def spectral_wavelengths():
+    """the 95 wavelengths of the spectral film's grid, 360 .. 830 nm in steps of 5, as float32"""
+    return (360.0 + 5.0 * np.arange(FILM_SAMPLES)).astype(np.float32)
+
+
+def spectral_radiance(film, samples, first=0):
+    """mean spectral radiance per pixel from raw film sums (srt_c_api.h): L_j = F_j * 470 / (35 n) for 0 < j < 94 and twice that at the
+    grid's ends j = 0 and j = 94, whose hats are half as wide.  film: (..., count) raw sums of grid samples first .. first + count - 1;
+    samples: the samples n each pixel holds, a scalar or an array broadcastable to film[..., 0].  float64; NaN where n == 0."""
+    film = np.asarray(film)
+    j = first + np.arange(film.shape[-1])
+    if first < 0 or j[-1] >= FILM_SAMPLES:
+        raise ValueError("spectral_radiance: grid samples %d .. %d are outside 0 .. %d" % (first, j[-1], FILM_SAMPLES - 1))
+    edge = np.where((j == 0) | (j == FILM_SAMPLES - 1), 2.0, 1.0)
+    n = np.asarray(samples, np.float64)[..., None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return film.astype(np.float64) * (470.0 / 35.0) * edge / n
+
+
+def film_to_xyz(film):
+    """XYZ sums from a full film (..., 95): d * sum_j F_j * (x_j, y_j, z_j) with d = 470/7 (the kernel's float32 value) and the colour-matching
+    rows of srt_color_tables, in float64.  Equals the accumulation's XYZ sums up to the reassociation of the float32 sums.  The same
+    contraction with another sensor's curves on the grid is how a non-CIE response is applied."""
+    film = np.asarray(film)
+    if film.shape[-1] != FILM_SAMPLES:
+        raise ValueError("film_to_xyz: needs all %d grid samples, got %d" % (FILM_SAMPLES, film.shape[-1]))
+    cmf = np.zeros(FILM_SAMPLES * 4, np.float32)
+    m = np.zeros(9, np.float32)
+    B.check(B.lib().srt_color_tables(B.fptr(cmf), B.fptr(m)))
+    xyz = cmf.reshape(FILM_SAMPLES, 4)[:, :3].astype(np.float64)
+    return (film.astype(np.float64) @ xyz) * float(np.float32(470.0) / np.float32(7.0))
+
+
+def render_spectral(scene, cam, width, height, passes, bounce_limit, seed=1984, device=0, renderer=None, first=0, count=FILM_SAMPLES):
+    """Progressive whole-image render with a spectral film on one GPU: a generator of (spp_total, result, radiance) after each pass,
+    `result` with the keys of render_image plus `film` (raw sums of grid samples [first, first + count), float32 (H, W, count)) and
+    `radiance` = spectral_radiance(film, spp_total, first).  The colour planes after the pass that brings the total to N are
+    bit-identical to render_image(..., spp=N, ...), as for render_progressive.  Checked before any device is touched."""
+    sched = progressive_schedule(passes)
+    if not (isinstance(first, (int, np.integer)) and isinstance(count, (int, np.integer))) or count <= 0 or first < 0 or first + count > FILM_SAMPLES:
+        raise ValueError("render_spectral: [first, first + count) must be a non-empty part of 0 .. %d, got %r, %r" % (FILM_SAMPLES, first, count))
+    return _spectral_passes(scene, cam, width, height, sched, bounce_limit, seed, device, renderer, int(first), int(count))
+
+
+def _spectral_passes(scene, cam, width, height, sched, bounce_limit, seed, device, renderer, first, count):
+    r = renderer or Renderer(device)
+    planes_before = r.gather_planes
+    try:
+        r.upload_scene(scene)
+        r.set_camera(cam)
+        r.init_device_params(width, height, sum(sched), bounce_limit, seed)
+        r.set_partition(0, 1)
+        r.set_count_traversal(False)
+        r.set_gather_planes(9)            # the parity planes (unquantised sRGB, XYZ sums) are part of what this returns
+        r.accum_reset_spectral()
+        for spp_add in sched:
+            r.render_chunk_accum(width, height, spp_add)
+            r.scatter_tiles()
+            out = dict(fb=r.read_fb(), lin=r.read_fb_aux(1), xyz=r.read_fb_aux(2), rowmajor=r.read_fb_rowmajor(width, height),
+                       stats=r.stats(), kernel_ms=r.last_kernel_ms(), geom=dict(r.geom),
+                       film=r.read_spectral(width, height, first, count))
+            yield r.accum_samples, out, spectral_radiance(out["film"], r.accum_samples, first)
     finally:
         if r._h:
             r.set_gather_planes(planes_before)

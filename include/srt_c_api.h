@@ -282,6 +282,35 @@ SRT_API int srt_accum_reset_adaptive(srt_ctx *ctx, const srt_adaptive *cfg);
 SRT_API int srt_accum_active(srt_ctx *ctx, uint64_t *active);
 SRT_API int srt_read_accum_stats(srt_ctx *ctx, uint32_t *samples, float *sum_y, float *sum_y2, uint32_t image_width, uint32_t image_height);
 
+/* Spectral film (no reference counterpart).  A SPECTRAL accumulation is a plain progressive accumulation (srt_accum_reset semantics:
+ * passes of s1 .. sk samples equal one launch of their sum in every output above) that also keeps a FILM: 95 raw fp32 sums per pixel,
+ * one per sample of the CIE grid the material spectra and colour tables use, F_j at lambda_j = 360 + 5 j nm, j = 0 .. 94.
+ * The deposit rule (render_kernel MODE 5):
+ *   - at every path end that is converted to XYZ -- a miss, or a hit that does not scatter -- and only there: a path ended by the bounce
+ *     limit deposits nothing, as it adds nothing to XYZ;
+ *   - for each of the path's 7 wavelengths k: (off_k, w_k) = the interpolation coordinates of wl[k] on the grid (the ones its XYZ
+ *     conversion uses: off = (int)((wl - 360) * (94 / 470)) clamped to [0, 93], w = (wl - 360) * (94 / 470) - off), p_k = the path's
+ *     power at wl[k] when k < valid (the wavelengths still valid), +0 otherwise;
+ *   - F[off_k] += (1 - w_k) * p_k;  F[off_k + 1] += w_k * p_k   (fp32, no contraction, each product rounded once).
+ * Paths are added in sample order; a pixel's film is written only by the lane that renders it (no atomics), so the film is the same bits
+ * in every run, launch shape and partition.  The 7 wavelengths of a path lie 470/7 nm apart and never share a grid sample.  With
+ * d = 470/7 and x, y, z the colour-matching rows of srt_color_tables, d * sum_j F_j * (x_j, y_j, z_j) equals the XYZ sums up to
+ * reassociation.  The device stores raw sums; the mean spectral radiance at lambda_j of a pixel holding n samples is estimated by
+ *   L_j = F_j * 470 / (35 n)  for 0 < j < 94, and twice that at j = 0 and j = 94 (their hats are half as wide).
+ *   srt_accum_reset_spectral  srt_accum_reset + a zeroed film (allocated on first use and when n_lanes changes, kFilmStride = 96 floats
+ *                             = 384 B per lane of the grid).  Later srt_render_chunk_accum passes run MODE 5.  An instrumented context:
+ *                             SRT_ERR_UNSUPPORTED; device parameters not set: SRT_ERR_INVALID; a failed allocation: SRT_ERR_HIP -- in
+ *                             every refusal the previous accumulation is unchanged.  Always a PLAIN (non-adaptive) accumulation:
+ *                             adaptive + spectral is not supported.  srt_accum_reset and srt_accum_reset_adaptive make the next
+ *                             accumulation non-spectral again.  Invalidation, the 65535-sample limit and the chunk binding are those of
+ *                             srt_accum_reset; srt_get_stats after a spectral pass reports that pass.
+ *   srt_read_spectral         the raw sums of grid samples [first, first + count) of the accumulation's chunk, row-major:
+ *                             out[((y * image_width) + x) * count + (j - first)]; only the chunk's rectangle is written (the placement
+ *                             of srt_read_fb_rowmajor), pixels owned by other ranks read +0.  Synchronises.  SRT_ERR_INVALID without a
+ *                             spectral accumulation with at least one pass, for count == 0, first + count > 95 or a null out. */
+SRT_API int srt_accum_reset_spectral(srt_ctx *ctx);
+SRT_API int srt_read_spectral(srt_ctx *ctx, uint32_t first, uint32_t count, float *out, uint32_t image_width, uint32_t image_height);
+
 /* Compact tile buffer of this rank (device memory): three plane GROUPS of tiles_padded * 3 * 64 floats each,
  * [group][tile][plane][lane] -- group 0 = quantised r,g,b (the reference's frame_buffer values, 12 B / pixel), group 1 =
  * unquantised sRGB r,g,b, group 2 = XYZ sums (parity planes).  tiles_padded = ceil(n_tiles/world), so every rank's buffer has
@@ -394,6 +423,9 @@ SRT_API int srt_render_frame_multi_accum(srt_comm *comm, uint32_t width, uint32_
  * stop decision there would need a reduction across processes. */
 SRT_API int srt_comm_accum_reset_adaptive(srt_comm *comm, const srt_adaptive *cfg);
 SRT_API int srt_comm_accum_active(srt_comm *comm, uint64_t *active);
+/* Spectral film on W GPUs: srt_accum_reset_spectral on every local context; srt_render_frame_multi_accum then runs MODE 5 on each rank.
+ * The films stay with their ranks (srt_read_spectral per context; each pixel is owned by one rank and reads +0 on the others). */
+SRT_API int srt_comm_accum_reset_spectral(srt_comm *comm);
 SRT_API int srt_comm_synchronize(srt_comm *comm);
 /* Closest-hit queries / paths of the last frame summed over the local ranks, and the slowest local render kernel. */
 SRT_API int srt_comm_stats(srt_comm *comm, uint64_t *rays, uint64_t *paths, float *max_kernel_ms);

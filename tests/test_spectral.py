@@ -1,0 +1,388 @@
+"""Spectral film (srt_accum_reset_spectral + srt_render_chunk_accum, render_kernel MODE 5).  The film holds, per pixel, the raw fp32 sums
+of every path end's seven powers deposited on the 5 nm CIE grid by the rule of srt_c_api.h.  Contracted with the colour-matching rows it
+gives the accumulation's XYZ sums (up to reassociation), on a miss-only frame it is restated bit for bit in numpy float32, and it is
+additive: the colour planes, XYZ sums and RNG state of a spectral accumulation are those of a plain one, and the film itself is the same
+bits for every split of the samples, every launch shape and every partition."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from helpers import assert_planes_equal, bits, custom_scene, fuzz_case
+from test_adaptive import _fresh, _frame, _lane_of, _expect_error, gpu_lib
+from test_gpu_parity import _xorwow_host
+from test_progressive import _soup, _workload
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ERR_INVALID, ERR_UNSUPPORTED = -1, -5
+N_GRID = 95
+
+
+def _spectral(gpu, scene, cam, W, H, depth, passes, spp=12):
+    """a spectral accumulation of `passes`; returns (frame after the last pass, film (H, W, 95))"""
+    _fresh(gpu, scene, cam, W, H, depth, spp=spp)
+    gpu.accum_reset_spectral()
+    for s in passes:
+        gpu.render_chunk_accum(W, H, s)
+    return _frame(gpu, W, H), gpu.read_spectral(W, H)
+
+
+def _fuzz_with_lens(srt):
+    """the first fuzz case with a defocus lens, at least three material types and a few bounces"""
+    for seed in range(200):
+        scene, cam, W, H, spp, depth, _, _ = fuzz_case(srt, seed)
+        if (cam.defocus_angle > 0 and len({m.material_type for m in scene.materials()}) >= 3 and depth >= 3
+                and scene.background().max() > 0):
+            return scene, cam, W, H, max(spp, 3), depth
+    raise AssertionError("no fuzz case with a lens")
+
+
+def _miss_scene(srt, bg):
+    """one small triangle far behind a camera that looks down -z: every camera ray misses; background spectrum `bg` (95 floats)"""
+    sc = custom_scene(srt, [((-1, -1, 60), (1, -1, 60), (0, 1, 60), 0, 0)], [(0, (0.5, 0.5, 0.5), 0.0, 0.0)])
+    bg = np.ascontiguousarray(bg, np.float32)
+    srt.binding.check(srt.binding.lib().srt_scene_set_background(sc.handle, srt.binding.fptr(bg)))
+    sc.build_bvh(srt.BVH_SAH, 1984)
+    return sc
+
+
+def _miss_camera(srt, W, H):
+    return srt.camera_init(W, H, 40.0, (0.0, 0.0, 5.0), (0.0, 0.0, 0.0))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["cornell", "prism", "fuzz", "random_spheres"])
+def test_film_contracts_to_the_xyz_sums(srt, gpu, name):
+    if name == "fuzz":
+        scene, cam, W, H, spp, depth = _fuzz_with_lens(srt)
+    else:
+        scene, cam, W, H, depth, _ = _workload(srt, name)
+        spp = 6
+    frame, film = _spectral(gpu, scene, cam, W, H, depth, [spp])
+    lane = _lane_of(gpu.geom, W, H)
+    want = np.stack([frame["xyz"][c][lane] for c in range(3)], axis=-1).reshape(H, W, 3).astype(np.float64)
+    y = np.zeros(W * H, np.float32)
+    gpu._ck(gpu_lib().srt_read_accum_stats(gpu._h, None, y.ctypes.data_as(C.POINTER(C.c_float)), None, W, H))
+    assert np.array_equal(bits(y), bits(want[..., 1].astype(np.float32).ravel()))
+    got = srt.film_to_xyz(film)
+    assert np.array_equal(np.isnan(got), np.isnan(want)), name
+    ok = ~np.isnan(want)
+    assert np.abs(want[ok]).max() > 0, name
+    np.testing.assert_allclose(got[ok], want[ok], rtol=2e-4, atol=1e-9, err_msg=name)
+    assert (film[~np.isnan(film)] >= 0).all()
+    assert gpu.stats()["paths"] == W * H * spp
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("passes", [[1], [2, 3], [4]], ids=["1", "2+3", "4"])
+def test_miss_only_film_equals_the_float32_restatement(srt, gpu, orc, passes):
+    """every sample draws two jitter floats and a hero wavelength, misses, and deposits the interpolated background at 7 wavelengths"""
+    f = np.float32
+    lam_grid = np.arange(N_GRID, dtype=np.float64)
+    bg = (0.2 + 0.6 * (0.5 + 0.5 * np.sin(lam_grid / 7.0)) + 0.01 * lam_grid / N_GRID).astype(f)
+    scene = _miss_scene(srt, bg)
+    W, H, depth = 23, 14, 4
+    cam = _miss_camera(srt, W, H)
+    frame, film = _spectral(gpu, scene, cam, W, H, depth, passes)
+    assert gpu.stats()["rays"] == W * H * passes[-1]
+    seeds = 1984 + _lane_of(gpu.geom, W, H).astype(np.uint64)
+    st, nxt = _xorwow_host(seeds)
+    every = np.ones(seeds.size, bool)
+
+    def unit(r):      # fma((float)r, 2^-32, 2^-33): one rounding
+        return (r.astype(f).astype(np.float64) * 2.0 ** -32 + 2.0 ** -33).astype(f)
+    step, scale = f(470.0) / f(7.0), f(94.0) / f(470.0)
+    want = np.zeros((seeds.size, N_GRID), f)
+    rows = np.arange(seeds.size)
+    bg_p = bg.ctypes.data_as(C.POINTER(C.c_float))
+    with np.errstate(over="ignore"):
+        for _ in range(sum(passes)):
+            nxt(every); nxt(every)                             # the pixel jitter
+            hero = unit(nxt(every)) * f(470.0) + f(360.0)      # rng_range(360, 830), two roundings
+            lam = hero
+            for k in range(7):
+                if k:
+                    lam = lam + step
+                    lam = np.where(lam > f(830.0), f(360.0) + (lam - f(830.0)), lam).astype(f)
+                x = (lam - f(360.0)) * scale
+                off = np.clip(x.astype(np.int32), 0, 93)
+                w = x - off.astype(f)
+                p = (f(1.0) - w) * bg[off] + w * bg[off + 1]
+                for q in range(0, seeds.size, 37):               # the interpolation is the oracle's spectrum_interp
+                    assert bits(np.float32(orc.lib().orc_spectrum_interp(bg_p, float(lam[q]), N_GRID))) == bits(p[q])
+                p = f(1.0) * p                                   # the path's power starts at 1
+                want[rows, off] = want[rows, off] + (f(1.0) - w) * p
+                want[rows, off + 1] = want[rows, off + 1] + w * p
+    want = want.reshape(H, W, N_GRID)
+    assert np.array_equal(bits(film), bits(want)), "%d of %d sums differ" % (int((bits(film) != bits(want)).sum()), film.size)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["prism", "dielectric"])
+def test_film_is_additive_and_split_invariant(srt, gpu, name):
+    scene, cam, W, H, depth, _ = _workload(srt, name)
+    one, film_one = _spectral(gpu, scene, cam, W, H, depth, [32], spp=3)
+    split, film_split = _spectral(gpu, scene, cam, W, H, depth, [8, 8, 16], spp=3)
+    assert np.array_equal(bits(film_split), bits(film_one)), name
+    sum_y = np.zeros(W * H, np.float32)
+    gpu._ck(gpu_lib().srt_read_accum_stats(gpu._h, None, sum_y.ctypes.data_as(C.POINTER(C.c_float)), None, W, H))
+    gpu.render_chunk(W, H)                # continues every pixel's RNG stream from where the passes left it
+    after = _frame(gpu, W, H)
+    # the same passes of a plain accumulation
+    _fresh(gpu, scene, cam, W, H, depth, spp=3)
+    gpu.accum_reset()
+    for s in (8, 8, 16):
+        gpu.render_chunk_accum(W, H, s)
+    plain = _frame(gpu, W, H)
+    plain_y = np.zeros(W * H, np.float32)
+    gpu._ck(gpu_lib().srt_read_accum_stats(gpu._h, None, plain_y.ctypes.data_as(C.POINTER(C.c_float)), None, W, H))
+    gpu.render_chunk(W, H)
+    plain_after = _frame(gpu, W, H)
+    for k in ("fb", "lin", "xyz", "rowmajor"):
+        assert_planes_equal(split[k], plain[k], "%s spectral vs plain %s" % (name, k))
+        assert_planes_equal(one[k], plain[k], "%s one-pass spectral vs plain %s" % (name, k))
+        assert_planes_equal(after[k], plain_after[k], "%s RNG state: plain launch after the passes, %s" % (name, k))
+    assert np.array_equal(bits(sum_y), bits(plain_y))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("knobs,paired,expect", [
+    (dict(), True, (1, 1, 1)),
+    (dict(wide_refs=True, lds_cache_max=3), True, (0, 0, 1)),
+    (dict(), False, (1, 1, 0)),
+    (dict(lds_cache_max=3), False, (1, 0, 0)),
+    (dict(wide_refs=True), False, (0, 1, 0)),
+    (dict(wide_refs=True, lds_cache_max=0), False, (0, 0, 0)),
+], ids=["narrow-cached-paired", "wide-partial-paired", "narrow-cached", "narrow-partial", "wide-cached", "wide-partial"])
+def test_every_spectral_shape_gives_the_same_film(srt, gpu, knobs, paired, expect):
+    n = 600 if paired else 601
+    scene = _soup(srt, n, n).build_bvh(srt.BVH_SAH, 1984)
+    assert scene.is_paired == paired
+    W, H, depth = 48, 32, 8
+    cam = srt.camera_init(W, H, 50.0, (0.5, 1.0, 16.0), (0.0, 0.0, 0.0), defocus_angle=0.6, focus_dist=14.0)
+    gpu.set_test_knobs()
+    ref, film_ref = _spectral(gpu, scene, cam, W, H, depth, [3, 5])
+    gpu.set_test_knobs(**knobs)
+    try:
+        got, film = _spectral(gpu, scene, cam, W, H, depth, [3, 5])
+        plan = gpu.launch_plan()
+        assert (int(plan["narrow_refs"]), int(plan["all_cached"]), int(plan["paired"])) == expect, plan
+    finally:
+        gpu.set_test_knobs()
+        gpu.upload_scene(scene)
+    assert np.array_equal(bits(film), bits(film_ref)), expect
+    assert film_ref.max() > 0
+    for k in ("fb", "lin", "xyz", "rowmajor"):
+        assert_planes_equal(got[k], ref[k], "shape %r %s" % (expect, k))
+
+
+@pytest.mark.gpu
+def test_partitions_offset_chunk_and_sub_range(srt, gpu):
+    scene, cam, W, H, depth, _ = _workload(srt, "random_spheres")
+    passes = [3, 4]
+    _, ref = _spectral(gpu, scene, cam, W, H, depth, passes)
+    assert ref.max() > 0
+    for world in (2, 3):
+        films = []
+        for rank in range(world):
+            _fresh(gpu, scene, cam, W, H, depth)
+            gpu.set_partition(rank, world)
+            gpu.accum_reset_spectral()
+            for s in passes:
+                gpu.render_chunk_accum(W, H, s)
+            films.append(gpu.read_spectral(W, H))
+        total = films[0]
+        for f_ in films[1:]:
+            total = total + f_
+        assert np.array_equal(bits(total), bits(ref)), world
+        # every pixel belongs to one rank: on all the others its 95 sums are +0
+        nonzero = np.stack([(bits(f_) != 0).any(axis=-1) for f_ in films])
+        owners = np.stack([(bits(f_) == 0).all(axis=-1) for f_ in films])
+        assert (nonzero.sum(axis=0) <= 1).all() and ((~owners).sum(axis=0) <= 1).all(), world
+        assert nonzero.any(axis=0).sum() > 0.9 * W * H
+    gpu.set_partition(0, 1)
+
+    # sub-ranges of the full read
+    _, full = _spectral(gpu, scene, cam, W, H, depth, passes)
+    for first, count in ((0, 1), (10, 17), (94, 1), (0, 95), (47, 48)):
+        part = gpu.read_spectral(W, H, first, count)
+        assert part.shape == (H, W, count)
+        assert np.array_equal(bits(part), bits(full[..., first:first + count])), (first, count)
+
+    # a 30 x 20 chunk at (17, 9) of a 64 x 40 image writes its rectangle of the caller's array and nothing else
+    IW, IH, cw, ch, ox, oy = 64, 40, 30, 20, 17, 9
+    cam = scene.default_camera(IW, IH)
+    _fresh(gpu, scene, cam, cw, ch, depth)
+    gpu.accum_reset_spectral()
+    for s in passes:
+        gpu.render_chunk_accum(cw, ch, s, ox, oy)
+    sentinel = np.float32(-7.0)
+    out = np.full((IH, IW, 12), sentinel, np.float32)
+    gpu.read_spectral(IW, IH, 40, 12, into=out)
+    inside = np.zeros((IH, IW), bool)
+    inside[oy:oy + ch, ox:ox + cw] = True
+    assert (out[~inside] == sentinel).all()
+    assert (out[inside] >= 0).all() and out[inside].max() > 0
+    full = gpu.read_spectral(IW, IH)
+    assert np.array_equal(bits(out[inside]), bits(full[inside][:, 40:52]))
+    y = np.zeros(IW * IH, np.float32)
+    gpu._ck(gpu_lib().srt_read_accum_stats(gpu._h, None, y.ctypes.data_as(C.POINTER(C.c_float)), None, IW, IH))
+    y = y.reshape(IH, IW)
+    got_y = srt.film_to_xyz(full)[..., 1]
+    np.testing.assert_allclose(got_y[inside], y[inside], rtol=2e-4, atol=1e-9)
+    assert (full[~inside] == 0).all()
+
+
+@pytest.mark.gpu
+def test_comm_two_and_three_ranks_one_gpu_mock_transport():
+    mock = os.path.join(ROOT, "tests", "cpp", "_build", "libmock_rccl.so")
+    assert os.path.exists(mock), "tests/cpp/_build/libmock_rccl.so is built by __graft_entry__.build()"
+    code = """
+import importlib, sys
+import numpy as np
+sys.path.insert(0, %r); sys.path.insert(0, %r)
+srt = importlib.import_module('cuda-spectral-ray-tracer_amd')
+from helpers import assert_planes_equal, bits
+scene = srt.Scene.builtin(srt.SCENE_RANDOM_SPHERES).build_bvh(srt.BVH_SAH, 1984)
+W, H, depth = 150, 90, 16
+cam = scene.default_camera(W, H)
+steps = list(srt.render_spectral(scene, cam, W, H, [4, 4], depth))
+total, ref, _ = steps[-1]
+assert total == 8 and ref['film'].max() > 0
+for world in (2, 3):
+    comm = srt.Comm.init_all([0] * world)
+    comm.set_gather_planes(9)
+    comm.upload_scene(scene); comm.set_camera(cam)
+    comm.init_device_params(W, H, 8, depth, 1984)
+    comm.accum_reset_spectral()
+    for s in (4, 4):
+        comm.render_frame_accum(W, H, s)
+    comm.synchronize()
+    root = comm.root
+    assert_planes_equal(root.read_fb(), ref['fb'], 'world %%d fb' %% world)
+    assert_planes_equal(root.read_fb_aux(2), ref['xyz'], 'world %%d xyz' %% world)
+    film = comm.read_spectral(W, H)
+    assert np.array_equal(bits(film), bits(ref['film'])), world
+    part = comm.read_spectral(W, H, 30, 5)
+    assert np.array_equal(bits(part), bits(ref['film'][..., 30:35])), world
+    comm.close()
+r = srt.Renderer(0)
+c1 = srt.Comm.init_rank(r, srt.Comm.unique_id(), 0, 1)
+c1.set_gather_planes(9)
+c1.upload_scene(scene); c1.set_camera(cam); c1.init_device_params(W, H, 8, depth, 1984)
+c1.accum_reset_spectral()
+for s in (4, 4):
+    c1.render_frame_accum(W, H, s)
+c1.synchronize()
+assert np.array_equal(bits(c1.read_spectral(W, H)), bits(ref['film']))
+c1.close(); r.close()
+print('spectral mock transport ok')
+""" % (ROOT, os.path.join(ROOT, "tests"))
+    env = dict(os.environ, SRT_RCCL_LIB=mock, SRT_COMM_TEST_SAME_DEVICE="1", SRT_TEST_KNOBS="1")
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "spectral mock transport ok" in out.stdout, (out.stdout[-1500:], out.stderr[-3000:])
+
+
+@pytest.mark.gpu
+def test_estimator_recovers_a_constant_background(srt, gpu):
+    """A miss-only frame under a constant background c: the image-mean spectral_radiance is c at every grid sample, the half-width end
+    samples (edge factor 2) included.  (At 64 x 64 x 64 spp the standard error of one sample's mean is about 0.55 % inside the grid and
+    0.8 % at its ends -- a 1 % bound would be a 1.3-1.8 sigma test; 128 x 128 x 256 spp brings it to 0.07 / 0.1 %.)"""
+    c = 0.75
+    scene = _miss_scene(srt, np.full(N_GRID, c, np.float32))
+    W = H = 128
+    spp = 256
+    _, film = _spectral(gpu, scene, _miss_camera(srt, W, H), W, H, 4, [spp])
+    L = srt.spectral_radiance(film, spp).reshape(-1, N_GRID).mean(axis=0)
+    rel = np.abs(L / c - 1.0)
+    assert rel.max() < 0.01, (int(rel.argmax()), float(rel.max()))
+    assert rel[0] < 0.01 and rel[94] < 0.01
+    # without the edge factor the ends would read c / 2
+    raw = film.reshape(-1, N_GRID).mean(axis=0).astype(np.float64) * 470.0 / (35.0 * spp)
+    assert abs(raw[0] / c - 0.5) < 0.01 and abs(raw[94] / c - 0.5) < 0.01
+
+
+@pytest.mark.gpu
+def test_refusals_and_invalidation(srt, gpu):
+    scene, cam, W, H, depth, _ = _workload(srt, "prism")
+    L = gpu_lib()
+    buf = np.zeros(W * H * N_GRID, np.float32)
+    fp = buf.ctypes.data_as(C.POINTER(C.c_float))
+    # device parameters not set
+    fresh = srt.Renderer(0)
+    try:
+        assert L.srt_accum_reset_spectral(fresh._h) == ERR_INVALID
+    finally:
+        fresh.close()
+    _fresh(gpu, scene, cam, W, H, depth)
+    # a plain accumulation has no film
+    gpu.accum_reset()
+    gpu.render_chunk_accum(W, H, 2)
+    _expect_error(srt, lambda: gpu.read_spectral(W, H), ERR_INVALID, "read of a plain accumulation")
+    gpu.accum_reset_spectral()
+    _expect_error(srt, lambda: gpu.read_spectral(W, H), ERR_INVALID, "read before the first pass")
+    gpu.render_chunk_accum(W, H, 4)
+    first = gpu.read_spectral(W, H)
+    frame = _frame(gpu, W, H)
+    for f0, n in ((0, 0), (90, 6), (95, 1), (0, 96), (0xffffffff, 2)):
+        assert L.srt_read_spectral(gpu._h, f0, n, fp, W, H) == ERR_INVALID, (f0, n)
+    assert L.srt_read_spectral(gpu._h, 0, 95, None, W, H) == ERR_INVALID
+    assert L.srt_read_spectral(gpu._h, 0, 95, fp, 0, H) == ERR_INVALID
+    # a refused reset (instrumented context) leaves the accumulation usable
+    gpu.set_count_traversal(True)
+    _expect_error(srt, lambda: gpu.accum_reset_spectral(), ERR_UNSUPPORTED, "instrumented context")
+    gpu.set_count_traversal(False)
+    assert gpu.accum_samples == 4
+    assert np.array_equal(bits(gpu.read_spectral(W, H)), bits(first))
+    for k, v in _frame(gpu, W, H).items():
+        assert_planes_equal(v, frame[k], "after the refusal " + k)
+    gpu.render_chunk_accum(W, H, 4)
+    assert gpu.accum_samples == 8 and gpu.stats()["paths"] == W * H * 4
+    _, want = _spectral(gpu, scene, cam, W, H, depth, [8])
+    _fresh(gpu, scene, cam, W, H, depth)
+    gpu.accum_reset_spectral()
+    gpu.render_chunk_accum(W, H, 4)
+    gpu.set_count_traversal(True)
+    _expect_error(srt, lambda: gpu.accum_reset_spectral(), ERR_UNSUPPORTED, "instrumented context")
+    gpu.set_count_traversal(False)
+    gpu.render_chunk_accum(W, H, 4)
+    assert np.array_equal(bits(gpu.read_spectral(W, H)), bits(want))
+    # every invalidation of an accumulation makes the film unreadable
+    for what, call in (("srt_set_camera", lambda: gpu.set_camera(cam)), ("srt_render_chunk", lambda: gpu.render_chunk(W, H)),
+                       ("srt_upload_scene", lambda: gpu.upload_scene(scene)), ("srt_set_partition", lambda: gpu.set_partition(0, 1)),
+                       ("srt_init_device_params", lambda: gpu.init_device_params(W, H, 12, depth, 1984)),
+                       ("srt_accum_reset", lambda: gpu.accum_reset()),
+                       ("srt_accum_reset_adaptive", lambda: gpu.accum_reset_adaptive(0.1, 0.0, 4))):
+        _fresh(gpu, scene, cam, W, H, depth)
+        gpu.accum_reset_spectral()
+        gpu.render_chunk_accum(W, H, 2)
+        gpu.read_spectral(W, H)
+        call()
+        if what.startswith("srt_accum_reset"):
+            gpu.render_chunk_accum(W, H, 2)      # a pass of the new accumulation, which keeps no film
+        _expect_error(srt, lambda: gpu.read_spectral(W, H), ERR_INVALID, what)
+    gpu.set_gather_planes(9)
+
+
+@pytest.mark.gpu
+def test_render_spectral_generator(srt, gpu):
+    scene, cam, W, H, depth, _ = _workload(srt, "cornell")
+    steps = list(srt.render_spectral(scene, cam, W, H, [3, 5], depth, renderer=gpu))
+    assert [t for t, _, _ in steps] == [3, 8]
+    for t, res, rad in steps:
+        assert set(res) == {"fb", "lin", "xyz", "rowmajor", "stats", "kernel_ms", "geom", "film"}
+        assert res["film"].shape == (H, W, N_GRID) and rad.shape == (H, W, N_GRID)
+        np.testing.assert_array_equal(rad, srt.spectral_radiance(res["film"], t))
+    one_shot = srt.render_image(scene, cam, W, H, 8, depth, renderer=gpu)
+    for k in ("fb", "lin", "xyz", "rowmajor"):
+        assert_planes_equal(steps[-1][1][k], one_shot[k], "render_spectral vs render_image " + k)
+    # a single pass is the one-shot spectral image; a sub-range reads the same sums
+    (t, res, rad), = srt.render_spectral(scene, cam, W, H, [8], depth, renderer=gpu, first=20, count=30)
+    assert t == 8 and res["film"].shape == (H, W, 30)
+    assert np.array_equal(bits(res["film"]), bits(steps[-1][1]["film"][..., 20:50]))
+    np.testing.assert_array_equal(rad, srt.spectral_radiance(res["film"], 8, first=20))
+    for k in ("fb", "lin", "xyz"):
+        assert_planes_equal(res[k], one_shot[k], "one-pass render_spectral " + k)

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""Identity of the accumulating (MODE 3) and adaptive (MODE 4) render kernels, the way tools/kernel_id.py identifies the production
+"""Identity of the accumulating (MODE 3), adaptive (MODE 4) and spectral (MODE 5) render kernels, the way tools/kernel_id.py identifies the production
 (MODE 0) ones: sha256 of each kernel's position-independent machine code in the gfx950 code object of a library, and sha256 of its
 body in an ISA listing (comments and file / ident / loc directives removed).  kernel_id.py's own output is left to the production
 kernels (bench.py reads it).
 
 Usage: python tools/accum_kernel_id.py [--against OTHER_LIB OTHER_LISTING]
-  prints the hashes of MODE 0, 3 and 4 of the in-tree build; with --against, also those of another build (e.g. the parent commit's)
-  and whether the MODE 0 and MODE 3 kernels are unchanged (exit status 1 if one differs)."""
+  prints the hashes of MODE 0, 3, 4 and 5 of the in-tree build; with --against, also those of another build (e.g. the parent commit's)
+  and whether the MODE 0, 3 and 4 kernels are unchanged (exit status 1 if one differs; a build without MODE 4 compares 0 and 3 only)."""
 import hashlib
 import os
 import re
@@ -15,8 +15,8 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kernel_id as K  # noqa: E402
 
-SYM = re.compile(r"^_ZN3srt13render_kernelILi([034])ELb([01])ELb([01])ELb([01])EEEvNS_12RenderParamsE$")
-LABEL = re.compile(r"^_ZN3srt13render_kernelILi([034])ELb([01])ELb([01])ELb([01])EEEvNS_12RenderParamsE:")
+SYM = re.compile(r"^_ZN3srt13render_kernelILi([0345])ELb([01])ELb([01])ELb([01])EEEvNS_12RenderParamsE$")
+LABEL = re.compile(r"^_ZN3srt13render_kernelILi([0345])ELb([01])ELb([01])ELb([01])EEEvNS_12RenderParamsE:")
 
 
 def code_hashes(lib):
@@ -71,21 +71,22 @@ def main(argv):
     if len(argv) == 3 and argv[0] == "--against":
         other = (code_hashes(argv[1]), listing_hashes(argv[2]))
     differ = 0
+    checked = (0, 3, 4) if other is not None and any(x[0] == 4 for x in other[0]) else (0, 3)
     for kind, k in (("code", 0), ("listing", 1)):
         for key in sorted(here[k]):
             line = "%-7s %-28s %s" % (kind, name(key), here[k][key])
-            if other is not None and key[0] in (0, 3):
+            if other is not None and key[0] in checked:
                 same = other[k].get(key) == here[k][key]
                 differ += 0 if same else 1
                 line += "  %s" % ("same as the other build" if same else "DIFFERS from the other build (%s)" % other[k].get(key))
             print(line)
     if other is not None:
         for k in (0, 1):
-            missing = sorted(set(x for x in other[k] if x[0] in (0, 3)) - set(here[k]))
+            missing = sorted(set(x for x in other[k] if x[0] in checked) - set(here[k]))
             differ += len(missing)
             for key in missing:
                 print("missing %s" % name(key))
-        print("MODE 0 and MODE 3 kernels: %s" % ("unchanged" if differ == 0 else "%d hashes differ" % differ))
+        print("MODE %s kernels: %s" % (", ".join(str(m) for m in checked), "unchanged" if differ == 0 else "%d hashes differ" % differ))
     return 1 if differ else 0
 
 
