@@ -23,11 +23,38 @@ static constexpr uint32_t kFringeStrideL2 = SRT_FRINGE_STRIDE_L2;
 // step-choice weights when the inner tree exceeds the LDS cache (256 = an INNER visit)
 static constexpr uint32_t kScoreShadeL2 = 320u, kScoreFringeL2 = 800u;   // FRINGE record stride for trees that do not fit LDS
 
+// An owning device allocation: a pointer and its size in bytes, move-only, freed by the destructor.
+// The policy of every buffer of this file, stated once:
+//  * reserve() never shrinks.  When it has to grow it releases the old block first and the contents are gone; a caller that must survive
+//    a refused allocation reserves a fresh buffer and moves it in (the film, srt_accum_reset_spectral).
+//  * hipFree waits for the device before it releases, so no site synchronises before a buffer grows or goes.
+//  * The device of the owning context must be current: every entry point selects it before it touches a buffer, srt_destroy before the
+//    context -- and with it every buffer -- dies.
+struct DeviceBuffer {
+    void *ptr = nullptr;
+    size_t bytes = 0;
+    DeviceBuffer() = default;
+    DeviceBuffer(DeviceBuffer &&o) noexcept { swap(o); }
+    DeviceBuffer &operator=(DeviceBuffer &&o) noexcept { swap(o); return *this; }      // (the old block goes with o)
+    ~DeviceBuffer() { release(); }
+    void swap(DeviceBuffer &o) { std::swap(ptr, o.ptr); std::swap(bytes, o.bytes); }
+    void release() { if (ptr) (void)hipFree(ptr); ptr = nullptr; bytes = 0; }
+    hipError_t reserve(size_t n) {
+        if (n <= bytes) return hipSuccess;
+        release();
+        const hipError_t e = hipMalloc(&ptr, n);
+        if (e == hipSuccess) bytes = n; else ptr = nullptr;
+        return e;
+    }
+    template <typename T> T *as() const { return static_cast<T *>(ptr); }
+    explicit operator bool() const { return ptr != nullptr; }
+};
+
 struct srt_ctx {
     int device = 0;
     std::string err;
-    // scene images in HBM
-    float *d_nodes = nullptr, *d_nodes_sw = nullptr, *d_fringe = nullptr, *d_tris = nullptr, *d_mat_sd = nullptr, *d_mat_par = nullptr, *d_shade = nullptr, *d_cmf = nullptr;
+    // scene images in HBM (floats)
+    DeviceBuffer d_nodes, d_nodes_sw, d_fringe, d_tris, d_mat_sd, d_mat_par, d_shade, d_cmf;
     int root_ref = 0, stack_depth = 1, n_inner = 0, n_records = 0;
     bool paired = false;               // the uploaded tree has no node with exactly one leaf child (srt_scene_is_paired)
     uint32_t fringe_stride = 96;       // bytes between FRINGE records in d_fringe
@@ -46,11 +73,10 @@ struct srt_ctx {
     uint32_t last_w = 0, last_h = 0, last_offx = 0, last_offy = 0;
     uint32_t tiles_x = 0, tiles_y = 0, n_tiles = 0, tiles_local = 0, tiles_padded = 0;
     // buffers
-    uint32_t *d_rng = nullptr;
-    float *d_fb = nullptr;          // 9 block-linear planes of n_lanes floats
-    float *d_tiles = nullptr;       // compact tile buffer
-    size_t tiles_capacity = 0;      // floats
-    unsigned long long *d_counters = nullptr;     // [kCounters] statistics + 1 word pixel-queue head behind them
+    DeviceBuffer d_rng;             // 6 planes of n_lanes words
+    DeviceBuffer d_fb;              // 9 block-linear planes of n_lanes floats
+    DeviceBuffer d_tiles;           // compact tile buffer (floats)
+    DeviceBuffer d_counters;        // [kCounters] u64 statistics + 1 word pixel-queue head behind them
     int n_cu = 256;
     uint32_t waves_per_cu = 0;                         // experiment knob (env SRT_WAVES_PER_CU)
     // step choice of a wave: serve the kind of work (shade / fringe / inner) with the most waiting lanes per unit of cost;
@@ -73,41 +99,35 @@ struct srt_ctx {
     // trees: cfg 3 at W = 2 187 -> 196 ms, cfg 2 44.8 -> 45.4 ms).
     // env SRT_ORDER_MAX_PCT
     int order_max_pct = -1;
-    uint32_t *d_tile_cost = nullptr, *d_tile_order = nullptr;
-    size_t tile_sched_capacity = 0;
-    uint64_t lanes_allocated = 0;                       // size of d_rng / d_fb in lanes
-    float last_probe_ms = 0.f;
+    DeviceBuffer d_tile_cost, d_tile_order;            // the cost probe's schedule (TileSchedule)
     bool count_traversal = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
-    uint64_t last_paths = 0;
-    float *d_rowmajor = nullptr;                        // row-major staging image of srt_read_fb_rowmajor (3 planes)
-    OrderProfile order_profile = {};                    // non-zero magic: the next instrumented launch collects the child-order profile
-    uint32_t *d_wave_debug = nullptr;                   // instrumented launches: 4 words per wave
-    uint32_t wave_debug_waves = 0;
+    DeviceBuffer d_rowmajor;                            // row-major staging image of srt_read_fb_rowmajor (3 planes), zeroed when its size changes
     uint32_t rowmajor_w = 0, rowmajor_h = 0;
+    OrderProfile order_profile = {};                    // non-zero magic: the next instrumented launch collects the child-order profile
+    DeviceBuffer d_wave_debug;                          // instrumented launches: [OrderProfile header][4 words per wave]
     uint32_t stats_spp = 0;                             // samples per pixel of the last launch when it was an accumulating pass (0: c->spp)
-    // progressive rendering (srt_render_chunk_accum): [AccumHeader | pad to 256 B | three planes of n_lanes floats], allocated on first use
-    char *d_accum = nullptr;
-    uint64_t accum_lanes = 0;                           // lanes d_accum's planes hold
-    enum { kAccumInvalid, kAccumEmpty, kAccumBound } accum_state = kAccumInvalid;   // Empty: reset, no pass yet; Bound: passes of one chunk
-    uint32_t accum_total = 0;                           // samples per pixel in the sums
-    uint32_t accum_w = 0, accum_h = 0, accum_offx = 0, accum_offy = 0;   // the chunk of the first pass
-    // adaptive sampling (srt_accum_reset_adaptive): [S2 plane | state plane] of accum_lanes words, allocated on first use
-    bool accum_adaptive = false;                        // the current accumulation is adaptive (MODE 4 passes)
-    char *d_adapt = nullptr;
-    uint64_t adapt_lanes = 0;
-    // pixel queue of the next adaptive pass: [queue_info 4 words | counts: 1 x u64 + pad | rows | flags], adapt_queue_rows rows each
-    uint32_t *d_adapt_queue = nullptr;
-    size_t adapt_queue_rows = 0;
     bool stats_adaptive = false;                        // the last launch was an adaptive pass: srt_get_stats reads its pixel count
-    // spectral film (srt_accum_reset_spectral): kFilmStride floats per lane of film_lanes, allocated on first use; the row-major staging
-    // buffer of srt_read_spectral (film_staging_floats of them)
-    bool accum_spectral = false;                        // the current accumulation keeps a film (MODE 5 passes)
-    float *d_film = nullptr;
-    uint64_t film_lanes = 0;
-    float *d_film_staging = nullptr;
-    size_t film_staging_floats = 0;
+    // The one accumulation of a context (srt_accum_reset*, srt_render_chunk_accum).
+    struct Accumulation {
+        enum class State { Invalid, Empty, Bound } state = State::Invalid;   // Empty: reset, no pass yet; Bound: passes of one chunk
+        enum class Kind { Plain, Adaptive, Spectral } kind = Kind::Plain;    // MODE 3 / 4 / 5 passes (never adaptive AND spectral)
+        uint32_t total = 0;                             // samples per pixel in the sums
+        uint32_t w = 0, h = 0, offx = 0, offy = 0;      // the chunk of the first pass
+        void invalidate() { state = State::Invalid; }
+        void begin(Kind k) { kind = k; state = State::Empty; }      // (srt_accum_reset has zeroed the total)
+        bool valid() const { return state != State::Invalid; }
+        bool bound() const { return state == State::Bound; }
+        bool adaptive() const { return kind == Kind::Adaptive; }
+        bool spectral() const { return kind == Kind::Spectral; }
+    } accum;
+    // the buffers behind it, allocated on first use:
+    DeviceBuffer d_accum;                               // progressive rendering (AccumLayout)
+    DeviceBuffer d_adapt;                               // adaptive sampling (srt_accum_reset_adaptive, AdaptPlanes)
+    DeviceBuffer d_adapt_queue;                         // pixel queue of the next adaptive pass (AdaptQueue)
+    DeviceBuffer d_film;                                // spectral film (srt_accum_reset_spectral): kFilmStride floats per lane
+    DeviceBuffer d_film_staging;                        // row-major staging block of srt_read_spectral
 };
 
 namespace {
@@ -142,25 +162,94 @@ int fail(srt_ctx *ctx, int code, const std::string &msg) {
 int hip_fail(srt_ctx *ctx, hipError_t e, const char *what) {
     return fail(ctx, SRT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
-#define HIP_TRY(ctx, expr)                                     \
-    do {                                                       \
-        hipError_t _e = (expr);                                \
-        if (_e != hipSuccess) return hip_fail(ctx, _e, #expr); \
-    } while (0)
+#define HIP_TRY_AS(ctx, what, expr) do { if (hipError_t _e = (expr)) return hip_fail(ctx, _e, what); } while (0)
+#define HIP_TRY(ctx, expr) HIP_TRY_AS(ctx, #expr, expr)
 
-template <typename T>
-int upload(srt_ctx *ctx, T **dst, const std::vector<float> &src) {
-    if (*dst) { (void)hipFree(*dst); *dst = nullptr; }
-    HIP_TRY(ctx, hipMalloc((void **)dst, src.size() * sizeof(float)));
-    HIP_TRY(ctx, hipMemcpy(*dst, src.data(), src.size() * sizeof(float), hipMemcpyHostToDevice));
+int upload(srt_ctx *ctx, DeviceBuffer &dst, const std::vector<float> &src) {
+    HIP_TRY(ctx, dst.reserve(src.size() * sizeof(float)));
+    HIP_TRY(ctx, hipMemcpy(dst.ptr, src.data(), src.size() * sizeof(float), hipMemcpyHostToDevice));
     return SRT_OK;
 }
 
+// ---- the layouts of the composite buffers: each is taken apart here and nowhere else ------------------------------------------
+
+// The cost probe's schedule.  d_tile_order: [rows: up to 64 per tile][sorted tile ids][queue_info 4 words]; d_tile_cost: per local tile
+// its cost, then the cost of its most expensive pixel.
+struct TileSchedule {
+    uint32_t *rows = nullptr, *sorted = nullptr, *info = nullptr, *cost = nullptr;
+    static size_t order_bytes(size_t tiles) { return (tiles * 65 + 4) * sizeof(uint32_t); }
+    static size_t cost_bytes(size_t tiles) { return 2 * tiles * sizeof(uint32_t); }
+    explicit TileSchedule(const srt_ctx *c) : cost(c->d_tile_cost.as<uint32_t>()) {
+        if (!c->d_tile_order) return;
+        const size_t tiles = (c->d_tile_order.bytes / sizeof(uint32_t) - 4) / 65;      // the tiles the buffer was reserved for
+        rows = c->d_tile_order.as<uint32_t>(); sorted = rows + tiles * 64; info = sorted + tiles;
+    }
+};
+
+// Pixel queue of the next adaptive pass: [queue_info 4 words | counts: 1 x u64 + pad | rows | flags], as many flags as rows.
+// counts: the pixels that rendered in the pass that just ended in the low half, those still active in the high half (adapt_flag_kernel).
+struct AdaptQueue {
+    uint32_t *info, *rows, *flags;
+    unsigned long long *counts;
+    static size_t bytes(size_t n_rows) { return (8 + 2 * n_rows) * sizeof(uint32_t); }
+    explicit AdaptQueue(const DeviceBuffer &d_adapt_queue)      // (an allocated one)
+        : info(d_adapt_queue.as<uint32_t>()), rows(info + 8), flags(rows + (d_adapt_queue.bytes / sizeof(uint32_t) - 8) / 2),
+          counts(reinterpret_cast<unsigned long long *>(info + 4)) {}
+};
+int read_adapt_counts(srt_ctx *c, uint64_t *rendered, uint64_t *active) {      // (either may be null)
+    unsigned long long counts = 0;
+    HIP_TRY(c, hipMemcpy(&counts, AdaptQueue(c->d_adapt_queue).counts, sizeof(counts), hipMemcpyDeviceToHost));
+    if (rendered) *rendered = counts & 0xffffffffull;
+    if (active) *active = counts >> 32;
+    return SRT_OK;
+}
+
+// Progressive rendering: [AccumHeader | pad to 256 B | X Y Z planes of n_lanes floats]
+struct AccumLayout {
+    static constexpr size_t kAccumHeaderBytes = 256;      // the sum planes start behind the header, 256-byte aligned
+    AccumHeader *header;
+    float *sums, *y;
+    static size_t sums_bytes(size_t lanes) { return 3 * lanes * sizeof(float); }
+    static size_t bytes(size_t lanes) { return kAccumHeaderBytes + sums_bytes(lanes); }
+    explicit AccumLayout(const srt_ctx *c)
+        : header(c->d_accum.as<AccumHeader>()), sums(reinterpret_cast<float *>(c->d_accum.as<char>() + kAccumHeaderBytes)), y(sums + c->n_lanes) {}
+};
+// MODE 3 / 4 / 5 read their AccumHeader where the instrumented build keeps its debug words (srt_internal.h, AccumHeader)
+void set_accum_header(RenderParams &p, AccumHeader *h) { p.wave_debug = reinterpret_cast<uint32_t *>(h); }
+
+// Adaptive sampling: [S2 plane | state plane] of n_lanes words
+struct AdaptPlanes {
+    float *sum2;
+    uint32_t *state;
+    static size_t bytes(size_t lanes) { return 2 * lanes * sizeof(float); }
+    explicit AdaptPlanes(const srt_ctx *c) : sum2(c->d_adapt.as<float>()), state(c->d_adapt.as<uint32_t>() + c->n_lanes) {}
+};
+
+// The last chunk clipped to the reference grid, and its rectangle clipped to an image as well: w x h pixels whose first one has index
+// `first` in the row-major image (w = h = 0: the chunk lies outside the image).
+uint32_t clipped_w(const srt_ctx *c) { return std::min<uint32_t>(c->last_w, c->tx * c->bx); }
+uint32_t clipped_h(const srt_ctx *c) { return std::min<uint32_t>(c->last_h, c->ty * c->by); }
+struct ChunkRect { uint32_t w, h; size_t first; };
+ChunkRect chunk_rect(const srt_ctx *c, uint32_t image_width, uint32_t image_height) {
+    if (c->last_offx >= image_width || c->last_offy >= image_height) return {0, 0, 0};
+    return {std::min<uint32_t>(clipped_w(c), image_width - c->last_offx), std::min<uint32_t>(clipped_h(c), image_height - c->last_offy),
+            (size_t)c->last_offy * image_width + c->last_offx};
+}
+
+// Instrumented launches: the waves d_wave_debug has words for behind its OrderProfile header
+size_t wave_debug_bytes(size_t n_waves) { return sizeof(OrderProfile) + n_waves * 4 * sizeof(uint32_t); }
+uint32_t wave_debug_waves(const srt_ctx *c) { return c->d_wave_debug ? (uint32_t)((c->d_wave_debug.bytes - sizeof(OrderProfile)) / (4 * sizeof(uint32_t))) : 0u; }
+
+float *fb_plane(const srt_ctx *c, int k) { return c->d_fb.as<float>() + (size_t)k * c->n_lanes; }      // 0 .. 8: r g b | lin r g b | X Y Z
+
+// what launch_render will do for the uploaded scene
+LaunchPlan plan_of(const srt_ctx *c) { LaunchPlan lp; render_launch_plan(c->stack_depth, c->n_records, c->n_inner, c->knobs, lp); return lp; }
+
 void fill_params(const srt_ctx *c, RenderParams &p) {
     memset(&p, 0, sizeof(p));
-    p.nodes = (const float4 *)c->d_nodes; p.nodes_sw = c->d_nodes_sw; p.fringe = (const float4 *)c->d_fringe; p.tris = (const float4 *)c->d_tris;
-    p.mat_sd = (const float2 *)c->d_mat_sd; p.mat_par = (const float4 *)c->d_mat_par;
-    p.shade = (const float4 *)c->d_shade; p.cmf = (const float4 *)c->d_cmf;
+    p.nodes = c->d_nodes.as<const float4>(); p.nodes_sw = c->d_nodes_sw.as<const float>(); p.fringe = c->d_fringe.as<const float4>(); p.tris = c->d_tris.as<const float4>();
+    p.mat_sd = c->d_mat_sd.as<const float2>(); p.mat_par = c->d_mat_par.as<const float4>();
+    p.shade = c->d_shade.as<const float4>(); p.cmf = c->d_cmf.as<const float4>();
     p.root_ref = c->root_ref; p.stack_depth = c->stack_depth; p.n_materials = c->n_materials;
     p.n_inner = c->n_inner; p.n_cached = 0;   // n_cached is set by the launcher
     p.n_tris = c->n_tris; p.n_records = c->n_records; p.fringe_stride = c->fringe_stride;
@@ -173,10 +262,222 @@ void fill_params(const srt_ctx *c, RenderParams &p) {
     p.tx = c->tx; p.ty = c->ty; p.bx = c->bx; p.by = c->by;
     p.spp = c->spp; p.bounce_limit = c->bounce;
     p.rank = c->rank; p.world = c->world;
-    p.rng = c->d_rng; p.n_lanes = c->n_lanes;
-    p.tile_out = c->d_tiles; p.counters = c->d_counters;
+    p.rng = c->d_rng.as<uint32_t>(); p.n_lanes = c->n_lanes;
+    p.tile_out = c->d_tiles.as<float>(); p.counters = c->d_counters.as<unsigned long long>();
     p.tile_group_stride = c->tiles_padded * (uint32_t)(kGroupPlanes * kTileLanes);
     p.write_parity = c->gather_planes == (uint32_t)kTilePlanes ? 1u : 0u;
+}
+
+// ---- srt_render_chunk's body, in phases.  Each takes the context, what the phases share (Pass) and the RenderParams under construction.
+
+struct Pass {
+    uint32_t spp_add;          // 0: a plain launch of c->spp samples; > 0: an accumulating pass of spp_add samples
+    hipStream_t st;
+    RenderMode mode;           // of the render launch
+    bool later;                // a pass of a Bound accumulation: not its first
+    LaunchPlan plan;
+    bool ordered;              // the launch runs the cost probe's queue, fresh or reused (choose_queue)
+    uint32_t adapt_bound;      // adaptive passes: host-side bound of the rows of their queues (choose_queue)
+};
+
+uint32_t split_rows_bound(const srt_ctx *c) { return (uint32_t)std::min<uint64_t>((uint64_t)c->tiles_local * 64, 0x7fffffffull); }
+
+// Tile geometry and the compact tile buffer.
+int prepare_tiles(srt_ctx *c, const Pass &ps) {
+    // Tiles cover every pixel the reference grid can address, whatever the size of THIS chunk: the tile number of a lane
+    // idx -- and with it the rank that owns the lane's persistent RNG stream (Q13) -- must not move when a ragged edge
+    // chunk is narrower than the one before.  Tiles (partly) outside the chunk just skip those pixels (rendering.cu:205).
+    const uint32_t cover_w = c->tx * c->bx, cover_h = c->ty * c->by;
+    c->tiles_x = (cover_w + 7) / 8; c->tiles_y = (cover_h + 7) / 8;
+    c->n_tiles = c->tiles_x * c->tiles_y;
+    c->tiles_padded = (c->n_tiles + c->world - 1) / c->world;
+    c->tiles_local = c->n_tiles > c->rank ? (c->n_tiles - c->rank + c->world - 1) / c->world : 0;
+    const size_t tile_floats = (size_t)std::max<uint32_t>(c->tiles_padded, 1) * kTileLanes;      // per plane
+    HIP_TRY(c, c->d_tiles.reserve(tile_floats * kTilePlanes * sizeof(float)));
+    // (only the plane groups this launch writes: group 0, or all three when the parity planes were asked for.  Not on the later passes
+    // of an adaptive accumulation: their converged pixels keep the slots they wrote last)
+    if (!(ps.mode == Adaptive && ps.later)) HIP_TRY(c, hipMemsetAsync(c->d_tiles.ptr, 0, tile_floats * c->gather_planes * sizeof(float), ps.st));
+    HIP_TRY(c, hipMemsetAsync(c->d_counters.ptr, 0, (kCounters + 1) * sizeof(unsigned long long), ps.st));
+    return SRT_OK;
+}
+
+// The launch's parameters up to the pixel queue, which starts as the identity order.
+void chunk_params(const srt_ctx *c, const Pass &ps, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy, RenderParams &p) {
+    fill_params(c, p);
+    if (ps.spp_add) p.spp = ps.spp_add;      // the samples this pass adds (the running total is in the header)
+    p.width = width; p.height = height; p.offx = offx; p.offy = offy;
+    p.tiles_x = c->tiles_x; p.tiles_y = c->tiles_y; p.n_tiles = c->n_tiles;
+    p.tiles_local = c->tiles_local;
+    p.pixel_counter = reinterpret_cast<uint32_t *>(c->d_counters.as<unsigned long long>() + kCounters);
+    p.waves_per_cu_override = c->waves_per_cu;
+    const bool all_cached = ps.plan.all_cached;
+    // (inner records that come from L2 make an INNER visit ~2x as expensive, so shading and FRINGE visits weigh more:
+    // plateau 280-400 / 560-1100 on cfg 5's scene, 60-85 / 280-340 on cfg 2 / 3 / 4, profiles/r02/knob_sweeps.txt)
+    p.score_shade = c->score_shade ? c->score_shade : (all_cached ? 70u : kScoreShadeL2);
+    // (the PAIRED variant's FRINGE visit is a fifth cheaper: plateau 340-480 on cfg 3, profiles/r05/experiments/weights_paired.txt)
+    const bool paired = render_paired_variant(c->paired, render_narrow_refs(c->n_records, c->knobs), all_cached);
+    p.score_fringe = c->score_fringe ? c->score_fringe : (all_cached ? (paired ? 400u : 280u) : kScoreFringeL2);
+    p.tile_order = nullptr; p.tile_cost = nullptr; p.queue_rows = nullptr; p.queue_rows_bound = c->tiles_local;
+    p.debug_lane_limit = c->debug_lane_limit;
+}
+
+// The cost probe: probe_spp samples per pixel from a copy of the RNG state, nothing written, then the queue built on the device.
+// `p`: the launch's parameters with the identity queue.
+int run_cost_probe(srt_ctx *c, const Pass &ps, const RenderParams &p) {
+    HIP_TRY(c, c->d_tile_cost.reserve(TileSchedule::cost_bytes(c->tiles_local)));
+    HIP_TRY(c, c->d_tile_order.reserve(TileSchedule::order_bytes(c->tiles_local)));
+    const TileSchedule sched(c);
+    HIP_TRY(c, hipMemsetAsync(sched.cost, 0, TileSchedule::cost_bytes(c->tiles_local), ps.st));
+    RenderParams pp = p;
+    pp.spp = c->probe_spp; pp.tile_cost = sched.cost;
+    RoctxRange range_probe("srt cost probe + pixel queue");
+    HIP_TRY(c, launch_render(pp, c->knobs, (uint32_t)c->n_cu, Probe, ps.st));
+    const uint32_t n_waves_plan = (uint32_t)c->n_cu * (uint32_t)ps.plan.waves_per_cu;
+    const uint32_t order_pct = c->order_max_pct >= 0 ? (uint32_t)c->order_max_pct : ((!ps.plan.all_cached && (uint64_t)c->tiles_local < 6ull * n_waves_plan) ? 100u : 0u);
+    HIP_TRY(c, launch_order_tiles(sched.cost, sched.sorted, sched.rows, c->tiles_local, n_waves_plan, c->split_load_pct, sched.info, order_pct, ps.st));   // device-side, no host sync
+    HIP_TRY(c, hipMemsetAsync(c->d_counters.as<unsigned long long>() + kCounters, 0, sizeof(unsigned long long), ps.st));   // rewind the queue head
+    return SRT_OK;
+}
+
+// ---- cost-ordered pixel queue --------------------------------------------------------------------------------
+// A pixel is one sequential RNG stream, so the launch cannot finish before its most expensive pixel does.  A short
+// probe (probe_spp samples per pixel from a copy of the RNG state, nothing written) measures the traversal cost of
+// every tile; order_tiles_kernel then builds the queue on the device: tiles in descending cost order
+// (longest-processing-time-first), the most expensive ones split over several waves when the launch is chain-bound.
+enum class QueueSource { Identity, FreshProbe, ReusedProbe, Compacted };
+
+QueueSource queue_source(const srt_ctx *c, const Pass &ps) {
+    // (adaptive passes after the first: the queue the previous pass compacted -- the probe's rows, or the identity order, whose tiles
+    // still hold an active pixel.  A queue row has a 22-bit tile field: beyond that the pass runs the plain identity queue, and its
+    // converged pixels are only skipped at the fetch)
+    if (ps.mode == Adaptive && ps.later && c->tiles_local <= 0x3fffffu) return QueueSource::Compacted;
+    if (!ps.ordered) return QueueSource::Identity;
+    // (accumulating passes: the probe runs on the FIRST pass whatever its sample count -- short passes would otherwise run an unordered
+    // queue -- and the later passes of the accumulation reuse its queue: a tile's cost depends on its geometry, not on the sample index,
+    // and nothing else writes the schedule buffers before the accumulation is invalidated)
+    return ps.later ? QueueSource::ReusedProbe : QueueSource::FreshProbe;
+}
+
+int choose_queue(srt_ctx *c, Pass &ps, RenderParams &p) {
+    const bool schedulable = c->probe_spp > 0 && c->tiles_local > 1 && c->tiles_local <= 0x3fffffu;   // 22-bit tile field of a queue row
+    ps.ordered = schedulable && (ps.spp_add || c->spp > 4 * c->probe_spp);
+    ps.adapt_bound = ps.ordered && c->split_load_pct ? split_rows_bound(c) : c->tiles_local;
+    if (ps.mode == Adaptive) HIP_TRY(c, c->d_adapt_queue.reserve(AdaptQueue::bytes(std::max<uint32_t>(ps.adapt_bound, 1u))));
+    const QueueSource src = queue_source(c, ps);
+    if (src == QueueSource::Compacted) {
+        const AdaptQueue q(c->d_adapt_queue);
+        p.tile_order = q.rows;
+        p.queue_rows = q.info;
+        p.prio_cost = ps.ordered ? c->d_tile_cost.as<uint32_t>() : nullptr;
+        p.queue_rows_bound = ps.adapt_bound;
+    } else if (src != QueueSource::Identity) {      // (the identity queue: chunk_params)
+        if (src == QueueSource::FreshProbe)
+            if (const int rc = run_cost_probe(c, ps, p)) return rc;
+        const TileSchedule sched(c);
+        p.tile_order = sched.rows;
+        p.queue_rows = sched.info;
+        p.prio_cost = sched.cost;      // wave priorities of the render launch (render_kernel, LDS-resident trees)
+        if (c->split_load_pct) p.queue_rows_bound = split_rows_bound(c);
+    }
+    return SRT_OK;
+}
+
+// The instrumented launch's debug buffer.
+int bind_wave_debug(srt_ctx *c, const Pass &ps, RenderParams &p) {
+    if (!c->count_traversal) return SRT_OK;
+    const uint32_t n_waves = (uint32_t)c->n_cu * (uint32_t)ps.plan.waves_per_cu;
+    // layout of the debug buffer: [OrderProfile header][4 words per wave]: the header sits at a FIXED place, so the kernel finds it
+    // whatever number of waves the launcher ends up starting
+    HIP_TRY(c, c->d_wave_debug.reserve(wave_debug_bytes(n_waves)));
+    HIP_TRY(c, hipMemsetAsync(c->d_wave_debug.ptr, 0, c->d_wave_debug.bytes, ps.st));
+    p.wave_debug = c->d_wave_debug.as<uint32_t>();
+    if (c->order_profile.magic == kOrderProfileMagic)
+        HIP_TRY(c, hipMemcpyAsync(c->d_wave_debug.ptr, &c->order_profile, sizeof(OrderProfile), hipMemcpyHostToDevice, ps.st));
+    return SRT_OK;
+}
+
+int launch_pass(srt_ctx *c, const Pass &ps, RenderParams &p) {
+    HIP_TRY(c, hipEventRecord(c->ev0, ps.st));     // ev0..ev1 bracket the render kernel alone (roofline.achieved)
+    uint32_t waves_launched = 0;
+    if (ps.spp_add) set_accum_header(p, AccumLayout(c).header);
+    HIP_TRY(c, launch_render(p, c->knobs, (uint32_t)c->n_cu, ps.mode, ps.st, &waves_launched));
+    if (c->count_traversal && waves_launched > wave_debug_waves(c))
+        return fail(c, SRT_ERR_HIP, "srt_render_chunk: the launch started more waves than the debug buffer holds (launch plan and launcher disagree)");
+    HIP_TRY(c, hipEventRecord(c->ev1, ps.st));
+    return SRT_OK;
+}
+
+// After an adaptive pass: the next pass's queue, from the probe's queue (kept intact for the whole accumulation) or the identity order;
+// the same kernels count the pixels that rendered in this pass and those still active (srt_get_stats, srt_accum_active)
+int compact_adaptive_queue(srt_ctx *c, const Pass &ps, const RenderParams &p) {
+    const TileSchedule sched(c);
+    const AdaptQueue dst(c->d_adapt_queue);
+    AdaptQueueParams q = {};
+    q.src_rows = ps.ordered ? sched.rows : nullptr; q.src_info = ps.ordered ? sched.info : nullptr; q.n_identity = c->tiles_local;
+    q.dst_info = dst.info; q.dst_rows = dst.rows; q.flags = dst.flags; q.counts = dst.counts;
+    q.state = AdaptPlanes(c).state;
+    q.spp_total = c->accum.total + ps.spp_add;
+    q.width = p.width; q.height = p.height; q.tx = c->tx; q.ty = c->ty; q.bx = c->bx; q.by = c->by;
+    q.tiles_x = c->tiles_x; q.n_tiles = c->n_tiles; q.rank = c->rank; q.world = c->world;
+    q.lane_limit = c->debug_lane_limit ? c->debug_lane_limit : 64u;
+    HIP_TRY(c, hipMemsetAsync(q.counts, 0, sizeof(unsigned long long), ps.st));
+    HIP_TRY(c, launch_adapt_queue(q, ps.adapt_bound, ps.st));
+    return SRT_OK;
+}
+
+// spp_add == 0: a plain launch of c->spp samples (Plain, or Counting when instrumented); spp_add > 0: an accumulating pass of spp_add
+// samples (Accum / Adaptive / Spectral) whose caller has checked the accumulation and enqueued its header.
+// width .. offy are already narrowed to 16 bit.
+int render_chunk_impl(srt_ctx *c, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy, uint32_t spp_add, hipStream_t st) {
+    Pass ps = {};
+    ps.spp_add = spp_add; ps.st = st;
+    ps.mode = !spp_add ? (c->count_traversal ? Counting : Plain) : c->accum.adaptive() ? Adaptive : c->accum.spectral() ? Spectral : Accum;
+    ps.later = spp_add && c->accum.bound(); ps.plan = plan_of(c);
+    c->last_w = width; c->last_h = height; c->last_offx = offx; c->last_offy = offy;
+    RenderParams p;
+    if (const int rc = prepare_tiles(c, ps)) return rc;
+    chunk_params(c, ps, width, height, offx, offy, p);
+    if (const int rc = choose_queue(c, ps, p)) return rc;
+    if (const int rc = bind_wave_debug(c, ps, p)) return rc;
+    RoctxRange range_render("srt render_kernel");
+    if (const int rc = launch_pass(c, ps, p)) return rc;
+    if (ps.mode == Adaptive)
+        if (const int rc = compact_adaptive_queue(c, ps, p)) return rc;
+    c->timed = true;
+    c->stats_spp = spp_add;
+    c->stats_adaptive = ps.mode == Adaptive;
+    return SRT_OK;
+}
+
+int read_planes(srt_ctx *c, int first_plane, float *p0, float *p1, float *p2) {
+    if (!c || !c->d_fb) return fail(c, SRT_ERR_INVALID, "read: device parameters not initialised");
+    if (const int rc = srt_synchronize(c)) return rc;
+    float *dst[3] = {p0, p1, p2};
+    for (int k = 0; k < 3; k++)
+        if (dst[k]) HIP_TRY(c, hipMemcpy(dst[k], fb_plane(c, first_plane + k), (size_t)c->n_lanes * sizeof(float), hipMemcpyDeviceToHost));
+    return SRT_OK;
+}
+
+// Three block-linear planes of n_lanes words (bits copied as they are) -> the last chunk's rectangle of three row-major host images.
+// A null host plane is not copied (its source plane may be any valid one).
+int read_rowmajor(srt_ctx *c, const float *const src[3], float *const host[3], uint32_t image_width, uint32_t image_height) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = (size_t)image_width * image_height;
+    // context-owned row-major staging image: the un-swizzle writes the chunk's pixels into it on the device and only the
+    // chunk's rectangle travels to the caller's planes (update_fb touches nothing else either, render_manager.cuh:68-142)
+    if (c->rowmajor_w != image_width || c->rowmajor_h != image_height || !c->d_rowmajor) {
+        HIP_TRY(c, c->d_rowmajor.reserve(3 * n * sizeof(float)));
+        HIP_TRY(c, hipMemset(c->d_rowmajor.ptr, 0, 3 * n * sizeof(float)));
+        c->rowmajor_w = image_width; c->rowmajor_h = image_height;
+    }
+    float *dst[3] = {c->d_rowmajor.as<float>(), c->d_rowmajor.as<float>() + n, c->d_rowmajor.as<float>() + 2 * n};
+    HIP_TRY(c, launch_unswizzle(src, dst, c->tx, c->ty, c->bx, c->by, c->last_w, c->last_h, c->last_offx, c->last_offy, image_width, image_height, nullptr));
+    const ChunkRect rect = chunk_rect(c, image_width, image_height);
+    const size_t pitch = (size_t)image_width * sizeof(float);
+    for (int k = 0; k < 3 && rect.w && rect.h; k++)
+        if (host[k]) HIP_TRY(c, hipMemcpy2D(host[k] + rect.first, pitch, dst[k] + rect.first, pitch, (size_t)rect.w * sizeof(float), rect.h, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipDeviceSynchronize());
+    return SRT_OK;
 }
 
 }  // namespace
@@ -213,10 +514,10 @@ int srt_create(int device, srt_ctx **out) {
     }
     std::vector<float> rows(96 * 4);
     cmf_rows(rows.data());
-    int rc = upload(c, &c->d_cmf, rows);
+    int rc = upload(c, c->d_cmf, rows);
     if (rc != SRT_OK) { delete c; return rc; }
-    if ((e = hipMalloc((void **)&c->d_counters, (kCounters + 1) * sizeof(unsigned long long))) != hipSuccess ||
-        (e = hipMemset(c->d_counters, 0, (kCounters + 1) * sizeof(unsigned long long))) != hipSuccess ||
+    if ((e = c->d_counters.reserve((kCounters + 1) * sizeof(unsigned long long))) != hipSuccess ||
+        (e = hipMemset(c->d_counters.ptr, 0, (kCounters + 1) * sizeof(unsigned long long))) != hipSuccess ||
         (e = hipEventCreate(&c->ev0)) != hipSuccess || (e = hipEventCreate(&c->ev1)) != hipSuccess) {
         int r = hip_fail(nullptr, e, "srt_create");
         srt_destroy(c);
@@ -230,11 +531,9 @@ void srt_destroy(srt_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    void *bufs[] = {c->d_nodes, c->d_nodes_sw, c->d_fringe, c->d_tris, c->d_mat_sd, c->d_mat_par, c->d_shade, c->d_cmf, c->d_rng, c->d_fb, c->d_tiles, c->d_counters, c->d_tile_cost, c->d_tile_order, c->d_rowmajor, c->d_wave_debug, c->d_accum, c->d_adapt, c->d_adapt_queue, c->d_film, c->d_film_staging};
-    for (void *b : bufs) if (b) (void)hipFree(b);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
-    delete c;
+    delete c;      // (every DeviceBuffer frees itself, on the device selected above)
 }
 
 int srt_ctx_device(const srt_ctx *ctx) { return ctx ? ctx->device : -1; }
@@ -244,13 +543,13 @@ const char *srt_last_error(const srt_ctx *ctx) { return ctx ? ctx->err.c_str() :
 
 int srt_upload_scene(srt_ctx *c, const srt_scene *s) {
     if (!c || !s) return fail(c, SRT_ERR_INVALID, "srt_upload_scene: null argument");
-    c->accum_state = srt_ctx::kAccumInvalid;
+    c->accum.invalidate();
     HIP_TRY(c, hipSetDevice(c->device));
     FlatScene f;
     int rc = flatten_scene(*s, f);
     if (rc != SRT_OK) return fail(c, rc, global_error());
     if (render_lds_bytes(f.stack_depth, 1, 0, f.n_records, c->knobs) > 64 * 1024) return fail(c, SRT_ERR_BVH, "srt_upload_scene: BVH too deep for the LDS traversal stack");
-    if ((rc = upload(c, &c->d_nodes, f.nodes)) != SRT_OK) return rc;
+    if ((rc = upload(c, c->d_nodes, f.nodes)) != SRT_OK) return rc;
     {
         // FRINGE records are 96 B.  Packed, every second one straddles two 128-byte cache lines; when the tree is too large for
         // LDS every visit is an L2 round trip and a record that lies in ONE line halves the lines a FRINGE visit pulls through the
@@ -260,23 +559,22 @@ int srt_upload_scene(srt_ctx *c, const srt_scene *s) {
         uint32_t stride = plan.all_cached ? 96u : kFringeStrideL2;
         if (const char *ev = getenv("SRT_FRINGE_STRIDE")) stride = (atoi(ev) == 128 && !plan.all_cached) ? 128u : 96u;
         if ((uint64_t)(f.n_records - f.n_inner + 1) * stride >= (1ull << 31)) stride = 96u;
-        if (stride == 96u) {
-            if ((rc = upload(c, &c->d_fringe, f.fringe)) != SRT_OK) return rc;
-        } else {
+        std::vector<float> padded;
+        if (stride != 96u) {
             const size_t n_fr = f.fringe.size() / 24;
-            std::vector<float> padded(n_fr * 32, 0.f);
+            padded.assign(n_fr * 32, 0.f);
             for (size_t k = 0; k < n_fr; k++) memcpy(&padded[32 * k], &f.fringe[24 * k], 24 * sizeof(float));
-            if ((rc = upload(c, &c->d_fringe, padded)) != SRT_OK) return rc;
         }
+        if ((rc = upload(c, c->d_fringe, stride == 96u ? f.fringe : padded)) != SRT_OK) return rc;
         c->fringe_stride = stride;
         // (the pre-swizzled copy of the INNER records: only trees whose INNER visits read memory need it)
-        if (c->d_nodes_sw) { (void)hipFree(c->d_nodes_sw); c->d_nodes_sw = nullptr; }
-        if (!plan.all_cached && (rc = upload(c, &c->d_nodes_sw, f.nodes_sw)) != SRT_OK) return rc;
+        c->d_nodes_sw.release();
+        if (!plan.all_cached && (rc = upload(c, c->d_nodes_sw, f.nodes_sw)) != SRT_OK) return rc;
     }
-    if ((rc = upload(c, &c->d_tris, f.tris)) != SRT_OK) return rc;
-    if ((rc = upload(c, &c->d_mat_sd, f.mat_sd)) != SRT_OK) return rc;
-    if ((rc = upload(c, &c->d_mat_par, f.mat_par)) != SRT_OK) return rc;
-    if ((rc = upload(c, &c->d_shade, f.shade)) != SRT_OK) return rc;
+    if ((rc = upload(c, c->d_tris, f.tris)) != SRT_OK) return rc;
+    if ((rc = upload(c, c->d_mat_sd, f.mat_sd)) != SRT_OK) return rc;
+    if ((rc = upload(c, c->d_mat_par, f.mat_par)) != SRT_OK) return rc;
+    if ((rc = upload(c, c->d_shade, f.shade)) != SRT_OK) return rc;
     c->root_ref = f.root_ref; c->stack_depth = f.stack_depth; c->n_materials = (uint32_t)s->mats.size();
     c->n_inner = f.n_inner; c->n_records = f.n_records; c->n_tris = (uint32_t)s->raw.size();
     c->paired = tree_is_paired(*s);
@@ -286,7 +584,7 @@ int srt_upload_scene(srt_ctx *c, const srt_scene *s) {
 
 int srt_set_camera(srt_ctx *c, const srt_camera_data *cam) {
     if (!c || !cam) return fail(c, SRT_ERR_INVALID, "srt_set_camera: null argument");
-    c->accum_state = srt_ctx::kAccumInvalid;
+    c->accum.invalidate();
     c->cam = *cam;
     c->camera_ready = true;
     return SRT_OK;
@@ -294,8 +592,7 @@ int srt_set_camera(srt_ctx *c, const srt_camera_data *cam) {
 
 int srt_launch_plan(const srt_ctx *c, int *waves_per_cu, int *n_cached, int *all_cached, int *narrow_refs) {
     if (!c || !c->scene_ready) return fail(nullptr, SRT_ERR_INVALID, "srt_launch_plan: no scene uploaded");
-    LaunchPlan plan;
-    render_launch_plan(c->stack_depth, c->n_records, c->n_inner, c->knobs, plan);
+    const LaunchPlan plan = plan_of(c);
     if (waves_per_cu) *waves_per_cu = plan.waves_per_cu;
     if (n_cached) *n_cached = plan.n_cached;
     if (all_cached) *all_cached = plan.all_cached ? 1 : 0;
@@ -305,16 +602,14 @@ int srt_launch_plan(const srt_ctx *c, int *waves_per_cu, int *n_cached, int *all
 
 int srt_launch_paired(const srt_ctx *c, int *paired) {
     if (!c || !c->scene_ready || !paired) return fail(nullptr, SRT_ERR_INVALID, "srt_launch_paired: no scene uploaded / null argument");
-    LaunchPlan plan;
-    render_launch_plan(c->stack_depth, c->n_records, c->n_inner, c->knobs, plan);
+    const LaunchPlan plan = plan_of(c);
     *paired = render_paired_variant(c->paired, render_narrow_refs(c->n_records, c->knobs), plan.all_cached) ? 1 : 0;
     return SRT_OK;
 }
 
 int srt_launch_lds_bytes(const srt_ctx *c, size_t *bytes) {
     if (!c || !c->scene_ready || !bytes) return fail(nullptr, SRT_ERR_INVALID, "srt_launch_lds_bytes: no scene uploaded / null argument");
-    LaunchPlan plan;
-    render_launch_plan(c->stack_depth, c->n_records, c->n_inner, c->knobs, plan);
+    const LaunchPlan plan = plan_of(c);
     *bytes = render_lds_bytes(c->stack_depth, plan.waves_per_block, plan.n_cached, c->n_records, c->knobs);
     return SRT_OK;
 }
@@ -344,23 +639,18 @@ int srt_internal_init_device_params(srt_ctx *c, uint32_t tx, uint32_t ty, uint32
     if (!c) return fail(c, SRT_ERR_INVALID, "srt_init_device_params: null ctx");
     if (tx == 0 || ty == 0 || bx == 0 || by == 0 || chunk_w == 0 || chunk_h == 0)
         return fail(c, SRT_ERR_INVALID, "srt_init_device_params: zero dimension");
-    c->accum_state = srt_ctx::kAccumInvalid;
+    c->accum.invalidate();
     const uint64_t lanes = (uint64_t)tx * ty * bx * by;
     if (lanes > 0x7fffffffull) return fail(c, SRT_ERR_INVALID, "srt_init_device_params: grid too large");
     HIP_TRY(c, hipSetDevice(c->device));
     c->tx = tx; c->ty = ty; c->bx = bx; c->by = by; c->chunk_w = chunk_w; c->chunk_h = chunk_h;
     c->spp = (uint16_t)spp; c->bounce = (uint16_t)bounce_limit;     // short_uint, rendering.cu:154 (Q17)
     c->seed = seed; c->n_lanes = (uint32_t)lanes;
-    if (lanes != c->lanes_allocated) {   // a new frame of the same grid re-seeds in place
-        if (c->d_rng) { (void)hipFree(c->d_rng); c->d_rng = nullptr; }
-        if (c->d_fb) { (void)hipFree(c->d_fb); c->d_fb = nullptr; }
-        c->lanes_allocated = 0;
-        HIP_TRY(c, hipMalloc((void **)&c->d_rng, 6 * lanes * sizeof(uint32_t)));
-        HIP_TRY(c, hipMalloc((void **)&c->d_fb, kTilePlanes * lanes * sizeof(float)));
-        c->lanes_allocated = lanes;
-    }
-    HIP_TRY(c, hipMemset(c->d_fb, 0, kTilePlanes * lanes * sizeof(float)));
-    HIP_TRY(c, launch_init_rng(c->d_rng, c->n_lanes, seed, nullptr));   // init_random_states, rendering.cu:330
+    // (a new frame of the same grid -- or of a smaller one -- re-seeds in place)
+    HIP_TRY(c, c->d_rng.reserve(6 * lanes * sizeof(uint32_t)));
+    HIP_TRY(c, c->d_fb.reserve(kTilePlanes * lanes * sizeof(float)));
+    HIP_TRY(c, hipMemset(c->d_fb.ptr, 0, kTilePlanes * lanes * sizeof(float)));
+    HIP_TRY(c, launch_init_rng(c->d_rng.as<uint32_t>(), c->n_lanes, seed, nullptr));   // init_random_states, rendering.cu:330
     if (wait) HIP_TRY(c, hipDeviceSynchronize());
     c->fb_groups_valid = (uint32_t)kTileGroups;      // all nine planes are zero
     c->params_ready = true;
@@ -374,7 +664,7 @@ int srt_init_device_params(srt_ctx *c, uint32_t tx, uint32_t ty, uint32_t bx, ui
 
 int srt_set_partition(srt_ctx *c, uint32_t rank, uint32_t world) {
     if (!c || world == 0 || rank >= world) return fail(c, SRT_ERR_INVALID, "srt_set_partition: need rank < world");
-    c->accum_state = srt_ctx::kAccumInvalid;
+    c->accum.invalidate();
     c->rank = rank; c->world = world;
     return SRT_OK;
 }
@@ -384,181 +674,17 @@ uint32_t srt_internal_gather_planes(const srt_ctx *c) { return c ? c->gather_pla
 int srt_set_gather_planes(srt_ctx *c, uint32_t planes) {
     if (!c || (planes != 3 && planes != 9)) return fail(c, SRT_ERR_INVALID, "srt_set_gather_planes: planes must be 3 or 9");
     // (an adaptive pass writes only the slots of its active pixels: the converged ones would keep planes of another set)
-    if (c->accum_adaptive) c->accum_state = srt_ctx::kAccumInvalid;
+    if (c->accum.adaptive()) c->accum.invalidate();
     c->gather_planes = planes;
     return SRT_OK;
 }
-
-}  // extern "C"
-
-namespace {
-
-// srt_render_chunk's body.  spp_add == 0: a plain launch of c->spp samples (MODE 0, or MODE 1 when counting); spp_add > 0: an
-// accumulating pass of spp_add samples (MODE 3) whose caller has checked the accumulation and enqueued its header.
-// width .. offy are already narrowed to 16 bit.
-int render_chunk_impl(srt_ctx *c, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy, uint32_t spp_add, hipStream_t st) {
-    const bool accum = spp_add != 0;
-    const bool adapt = accum && c->accum_adaptive;      // MODE 4
-    const bool adapt_later = adapt && c->accum_state == srt_ctx::kAccumBound;
-    const bool spectral = accum && c->accum_spectral;   // MODE 5
-    c->last_w = width; c->last_h = height; c->last_offx = offx; c->last_offy = offy;
-    // Tiles cover every pixel the reference grid can address, whatever the size of THIS chunk: the tile number of a lane
-    // idx -- and with it the rank that owns the lane's persistent RNG stream (Q13) -- must not move when a ragged edge
-    // chunk is narrower than the one before.  Tiles (partly) outside the chunk just skip those pixels (rendering.cu:205).
-    const uint32_t cover_w = c->tx * c->bx, cover_h = c->ty * c->by;
-    c->tiles_x = (cover_w + 7) / 8; c->tiles_y = (cover_h + 7) / 8;
-    c->n_tiles = c->tiles_x * c->tiles_y;
-    c->tiles_padded = (c->n_tiles + c->world - 1) / c->world;
-    c->tiles_local = c->n_tiles > c->rank ? (c->n_tiles - c->rank + c->world - 1) / c->world : 0;
-    const size_t need = (size_t)std::max<uint32_t>(c->tiles_padded, 1) * kTilePlanes * kTileLanes;
-    if (need > c->tiles_capacity) {
-        if (c->d_tiles) { (void)hipFree(c->d_tiles); c->d_tiles = nullptr; }
-        HIP_TRY(c, hipMalloc((void **)&c->d_tiles, need * sizeof(float)));
-        c->tiles_capacity = need;
-    }
-    // (only the plane groups this launch writes: group 0, or all three when the parity planes were asked for.  Not on the later passes
-    // of an adaptive accumulation: their converged pixels keep the slots they wrote last)
-    if (!adapt_later) HIP_TRY(c, hipMemsetAsync(c->d_tiles, 0,(size_t)std::max<uint32_t>(c->tiles_padded, 1) * c->gather_planes * kTileLanes * sizeof(float), st));
-    HIP_TRY(c, hipMemsetAsync(c->d_counters, 0, (kCounters + 1) * sizeof(unsigned long long), st));
-    RenderParams p;
-    fill_params(c, p);
-    if (accum) p.spp = spp_add;      // the samples this pass adds (the running total is in the header)
-    p.width = width; p.height = height; p.offx = offx; p.offy = offy;
-    p.tiles_x = c->tiles_x; p.tiles_y = c->tiles_y; p.n_tiles = c->n_tiles;
-    p.tiles_local = c->tiles_local;
-    p.pixel_counter = (uint32_t *)(c->d_counters + kCounters);
-    p.waves_per_cu_override = c->waves_per_cu;
-    LaunchPlan plan;
-    render_launch_plan(c->stack_depth, c->n_records, c->n_inner, c->knobs, plan);
-    {
-        const bool all_cached = plan.all_cached;
-        // (inner records that come from L2 make an INNER visit ~2x as expensive, so shading and FRINGE visits weigh more:
-        // plateau 280-400 / 560-1100 on cfg 5's scene, 60-85 / 280-340 on cfg 2 / 3 / 4, profiles/r02/knob_sweeps.txt)
-        p.score_shade = c->score_shade ? c->score_shade : (all_cached ? 70u : kScoreShadeL2);
-        // (the PAIRED variant's FRINGE visit is a fifth cheaper: plateau 340-480 on cfg 3, profiles/r05/experiments/weights_paired.txt)
-        const bool paired = render_paired_variant(c->paired, render_narrow_refs(c->n_records, c->knobs), all_cached);
-        p.score_fringe = c->score_fringe ? c->score_fringe : (all_cached ? (paired ? 400u : 280u) : kScoreFringeL2);
-    }
-    // ---- cost-ordered pixel queue --------------------------------------------------------------------------------
-    // A pixel is one sequential RNG stream, so the launch cannot finish before its most expensive pixel does.  A short
-    // probe (probe_spp samples per pixel from a copy of the RNG state, nothing written) measures the traversal cost of
-    // every tile; order_tiles_kernel then builds the queue on the device: tiles in descending cost order
-    // (longest-processing-time-first), the most expensive ones split over several waves when the launch is chain-bound.
-    p.tile_order = nullptr; p.tile_cost = nullptr; p.queue_rows = nullptr; p.queue_rows_bound = c->tiles_local;
-    p.debug_lane_limit = c->debug_lane_limit;
-    // (accumulating passes: the probe runs on the FIRST pass whatever its sample count -- short passes would otherwise run an unordered
-    // queue -- and the later passes of the accumulation reuse its queue: a tile's cost depends on its geometry, not on the sample index,
-    // and nothing else writes the schedule buffers before the accumulation is invalidated)
-    const bool schedulable = c->probe_spp > 0 && c->tiles_local > 1 && c->tiles_local <= 0x3fffffu;   // 22-bit tile field of a queue row
-    const bool ordered = schedulable && (accum || c->spp > 4 * c->probe_spp);
-    const bool reuse_order = ordered && accum && c->accum_state == srt_ctx::kAccumBound;
-    // (adaptive passes after the first: the queue the previous pass compacted -- the probe's rows, or the identity order, whose tiles
-    // still hold an active pixel.  A queue row has a 22-bit tile field: beyond that the pass runs the plain identity queue, and its
-    // converged pixels are only skipped at the fetch)
-    const bool adapt_compact = adapt && c->tiles_local <= 0x3fffffu;
-    const uint32_t adapt_bound = ordered && c->split_load_pct ? (uint32_t)std::min<uint64_t>((uint64_t)c->tiles_local * 64, 0x7fffffffull) : c->tiles_local;
-    if (adapt) {
-        if (c->adapt_queue_rows < std::max<uint32_t>(adapt_bound, 1u)) {
-            if (c->d_adapt_queue) { HIP_TRY(c, hipDeviceSynchronize()); (void)hipFree(c->d_adapt_queue); c->d_adapt_queue = nullptr; c->adapt_queue_rows = 0; }
-            const size_t rows = std::max<uint32_t>(adapt_bound, 1u);
-            HIP_TRY(c, hipMalloc((void **)&c->d_adapt_queue, (8 + 2 * rows) * sizeof(uint32_t)));
-            c->adapt_queue_rows = rows;
-        }
-    }
-    if (adapt_later && adapt_compact) {
-        p.tile_order = c->d_adapt_queue + 8;
-        p.queue_rows = c->d_adapt_queue;
-        p.prio_cost = ordered ? c->d_tile_cost : nullptr;
-        p.queue_rows_bound = adapt_bound;
-    } else if (reuse_order) {
-        uint32_t *rows = c->d_tile_order, *sorted = rows + (size_t)c->tile_sched_capacity * 64, *queue_info = sorted + c->tile_sched_capacity;
-        p.tile_order = rows;
-        p.queue_rows = queue_info;
-        p.prio_cost = c->d_tile_cost;
-        if (c->split_load_pct) p.queue_rows_bound = (uint32_t)std::min<uint64_t>((uint64_t)c->tiles_local * 64, 0x7fffffffull);
-    } else if (ordered) {
-        if (c->tiles_local > c->tile_sched_capacity) {
-            if (c->d_tile_cost) { (void)hipFree(c->d_tile_cost); c->d_tile_cost = nullptr; }
-            if (c->d_tile_order) { (void)hipFree(c->d_tile_order); c->d_tile_order = nullptr; }
-            HIP_TRY(c, hipMalloc((void **)&c->d_tile_cost, 2 * (size_t)c->tiles_local * sizeof(uint32_t)));      // cost | most expensive pixel
-            // [rows: up to 64 per tile][sorted tile ids][queue_info]
-            HIP_TRY(c, hipMalloc((void **)&c->d_tile_order, ((size_t)c->tiles_local * 65 + 4) * sizeof(uint32_t)));
-            c->tile_sched_capacity = c->tiles_local;
-        }
-        uint32_t *rows = c->d_tile_order, *sorted = rows + (size_t)c->tile_sched_capacity * 64, *queue_info = sorted + c->tile_sched_capacity;
-        HIP_TRY(c, hipMemsetAsync(c->d_tile_cost, 0, 2 * (size_t)c->tiles_local * sizeof(uint32_t), st));
-        RenderParams pp = p;
-        pp.spp = c->probe_spp; pp.tile_cost = c->d_tile_cost;
-        RoctxRange range_probe("srt cost probe + pixel queue");
-        HIP_TRY(c, launch_render(pp, c->knobs, (uint32_t)c->n_cu, 2, st));
-        const uint32_t split_pct = c->split_load_pct;
-        const uint32_t n_waves_plan = (uint32_t)c->n_cu * (uint32_t)plan.waves_per_cu;
-        const uint32_t order_pct = c->order_max_pct >= 0 ? (uint32_t)c->order_max_pct : ((!plan.all_cached && (uint64_t)c->tiles_local < 6ull * n_waves_plan) ? 100u : 0u);
-        HIP_TRY(c, launch_order_tiles(c->d_tile_cost, sorted, rows, c->tiles_local, (uint32_t)c->n_cu * (uint32_t)plan.waves_per_cu, split_pct, queue_info, order_pct, st));   // device-side, no host sync
-        HIP_TRY(c, hipMemsetAsync(c->d_counters + kCounters, 0, sizeof(unsigned long long), st));   // rewind the queue head
-        p.tile_order = rows;
-        p.queue_rows = queue_info;
-        p.prio_cost = c->d_tile_cost;      // wave priorities of the render launch (render_kernel, LDS-resident trees)
-        if (split_pct) p.queue_rows_bound = (uint32_t)std::min<uint64_t>((uint64_t)c->tiles_local * 64, 0x7fffffffull);
-    }
-    if (c->count_traversal) {
-        const uint32_t n_waves = (uint32_t)c->n_cu * (uint32_t)plan.waves_per_cu;
-        // layout of the debug buffer: [OrderProfile header][4 words per wave]: the header sits at a FIXED place, so the kernel finds it
-        // whatever number of waves the launcher ends up starting
-        if (n_waves > c->wave_debug_waves) {
-            if (c->d_wave_debug) { (void)hipFree(c->d_wave_debug); c->d_wave_debug = nullptr; c->wave_debug_waves = 0; }
-            HIP_TRY(c, hipMalloc((void **)&c->d_wave_debug, sizeof(OrderProfile) + (size_t)n_waves * 4 * sizeof(uint32_t)));
-            c->wave_debug_waves = n_waves;
-        }
-        HIP_TRY(c, hipMemsetAsync(c->d_wave_debug, 0, sizeof(OrderProfile) + (size_t)c->wave_debug_waves * 4 * sizeof(uint32_t), st));
-        p.wave_debug = c->d_wave_debug;
-        if (c->order_profile.magic == kOrderProfileMagic)
-            HIP_TRY(c, hipMemcpyAsync(c->d_wave_debug, &c->order_profile, sizeof(OrderProfile), hipMemcpyHostToDevice, st));
-    }
-    RoctxRange range_render("srt render_kernel");
-    HIP_TRY(c, hipEventRecord(c->ev0, st));     // ev0..ev1 bracket the render kernel alone (roofline.achieved)
-    uint32_t waves_launched = 0;
-    if (accum) p.wave_debug = reinterpret_cast<uint32_t *>(c->d_accum);      // MODE 3 / 4 / 5 read their AccumHeader there
-    HIP_TRY(c, launch_render(p, c->knobs, (uint32_t)c->n_cu, adapt ? 4 : spectral ? 5 : accum ? 3 : (c->count_traversal ? 1 : 0), st, &waves_launched));
-    if (c->count_traversal && waves_launched > c->wave_debug_waves)
-        return fail(c, SRT_ERR_HIP, "srt_render_chunk: the launch started more waves than the debug buffer holds (launch plan and launcher disagree)");
-    HIP_TRY(c, hipEventRecord(c->ev1, st));
-    if (adapt) {
-        // the next pass's queue, from the probe's queue (kept intact for the whole accumulation) or the identity order; the same
-        // kernels count the pixels that rendered in this pass and those still active (srt_get_stats, srt_accum_active)
-        uint32_t *rows = c->d_tile_order, *sorted = rows ? rows + (size_t)c->tile_sched_capacity * 64 : nullptr, *queue_info = sorted ? sorted + c->tile_sched_capacity : nullptr;
-        AdaptQueueParams q;
-        memset(&q, 0, sizeof(q));
-        q.src_rows = ordered ? rows : nullptr; q.src_info = ordered ? queue_info : nullptr; q.n_identity = c->tiles_local;
-        q.dst_info = c->d_adapt_queue; q.dst_rows = c->d_adapt_queue + 8; q.flags = q.dst_rows + c->adapt_queue_rows;
-        q.counts = reinterpret_cast<unsigned long long *>(c->d_adapt_queue + 4);
-        q.state = reinterpret_cast<const uint32_t *>(c->d_adapt + c->adapt_lanes * sizeof(float));
-        q.spp_total = c->accum_total + spp_add;
-        q.width = width; q.height = height; q.tx = c->tx; q.ty = c->ty; q.bx = c->bx; q.by = c->by;
-        q.tiles_x = c->tiles_x; q.n_tiles = c->n_tiles; q.rank = c->rank; q.world = c->world;
-        q.lane_limit = c->debug_lane_limit ? c->debug_lane_limit : 64u;
-        HIP_TRY(c, hipMemsetAsync(q.counts, 0, sizeof(unsigned long long), st));
-        HIP_TRY(c, launch_adapt_queue(q, adapt_bound, st));
-    }
-    c->timed = true;
-    c->last_paths = 0;   // filled by srt_get_stats from the tile ownership (adaptive passes: from the device's count)
-    c->stats_spp = spp_add;
-    c->stats_adaptive = adapt;
-    return SRT_OK;
-}
-
-constexpr size_t kAccumHeaderBytes = 256;      // the sum planes start behind the header, 256-byte aligned
-
-}  // namespace
-
-extern "C" {
 
 int srt_render_chunk(srt_ctx *c, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy, void *stream) {
     if (!c) return fail(c, SRT_ERR_INVALID, "srt_render_chunk: null ctx");
     // reference: "Device parameters were not initialized, render aborted" (rendering.cu:247-250)
     if (!c->scene_ready || !c->camera_ready || !c->params_ready)
         return fail(c, SRT_ERR_INVALID, "srt_render_chunk: scene, camera and device parameters must be set first");
-    c->accum_state = srt_ctx::kAccumInvalid;      // its launch moves the RNG streams (and may rewrite the pixel queue) behind the sums
+    c->accum.invalidate();      // its launch moves the RNG streams (and may rewrite the pixel queue) behind the sums
     HIP_TRY(c, hipSetDevice(c->device));
     width = (uint16_t)width; height = (uint16_t)height; offx = (uint16_t)offx; offy = (uint16_t)offy;   // rendering.cu:245 (Q17)
     return render_chunk_impl(c, width, height, offx, offy, 0u, (hipStream_t)stream);
@@ -568,20 +694,13 @@ int srt_accum_reset(srt_ctx *c) {
     if (!c) return fail(c, SRT_ERR_INVALID, "srt_accum_reset: null ctx");
     if (!c->params_ready) return fail(c, SRT_ERR_INVALID, "srt_accum_reset: device parameters must be set first (srt_init_device_params)");
     HIP_TRY(c, hipSetDevice(c->device));
-    c->accum_state = srt_ctx::kAccumInvalid;
-    const uint64_t lanes = c->n_lanes;
-    if (!c->d_accum || c->accum_lanes != lanes) {
-        if (c->d_accum) { HIP_TRY(c, hipDeviceSynchronize()); (void)hipFree(c->d_accum); c->d_accum = nullptr; c->accum_lanes = 0; }
-        HIP_TRY(c, hipMalloc((void **)&c->d_accum, kAccumHeaderBytes + 3 * lanes * sizeof(float)));
-        c->accum_lanes = lanes;
-    }
+    c->accum.invalidate();
+    HIP_TRY(c, c->d_accum.reserve(AccumLayout::bytes(c->n_lanes)));
     // (null stream, then a wait: a pass on any stream of the caller's finds the sums zeroed)
-    HIP_TRY(c, hipMemset(c->d_accum + kAccumHeaderBytes, 0, 3 * lanes * sizeof(float)));
+    HIP_TRY(c, hipMemset(AccumLayout(c).sums, 0, AccumLayout::sums_bytes(c->n_lanes)));
     HIP_TRY(c, hipDeviceSynchronize());
-    c->accum_total = 0;
-    c->accum_adaptive = false;
-    c->accum_spectral = false;
-    c->accum_state = srt_ctx::kAccumEmpty;
+    c->accum.total = 0;
+    c->accum.begin(srt_ctx::Accumulation::Kind::Plain);
     return SRT_OK;
 }
 
@@ -592,25 +711,22 @@ int srt_accum_reset_spectral(srt_ctx *c) {
         return fail(c, SRT_ERR_UNSUPPORTED, "srt_accum_reset_spectral: no instrumented accumulating kernel (srt_set_count_traversal(ctx, 0) first)");
     if (!c->params_ready) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_spectral: device parameters must be set first (srt_init_device_params)");
     HIP_TRY(c, hipSetDevice(c->device));
-    const uint64_t lanes = c->n_lanes;
-    if (!c->d_film || c->film_lanes != lanes) {
+    const size_t film_bytes = (size_t)c->n_lanes * kFilmStride * sizeof(float);
+    if (c->d_film.bytes < film_bytes) {
         // (the new film is allocated before the old one goes: a failed allocation changes nothing)
-        float *film = nullptr;
-        HIP_TRY(c, hipMalloc((void **)&film, lanes * kFilmStride * sizeof(float)));
-        if (c->d_film) { (void)hipDeviceSynchronize(); (void)hipFree(c->d_film); }
-        c->d_film = film;
-        c->film_lanes = lanes;
+        DeviceBuffer film;
+        HIP_TRY(c, film.reserve(film_bytes));
+        c->d_film = std::move(film);
     }
     int rc = srt_accum_reset(c);
     if (rc != SRT_OK) return rc;
-    c->accum_state = srt_ctx::kAccumInvalid;      // (until the film is in place)
-    HIP_TRY(c, hipMemset(c->d_film, 0, lanes * kFilmStride * sizeof(float)));
+    c->accum.invalidate();      // (until the film is in place)
+    HIP_TRY(c, hipMemset(c->d_film.ptr, 0, film_bytes));
     // the film's slot of the header (the per-pass kernel rewrites only sums and spp_total)
-    float *film = c->d_film;
-    HIP_TRY(c, hipMemcpy(c->d_accum + offsetof(AccumHeader, film), &film, sizeof(film), hipMemcpyHostToDevice));
+    float *film = c->d_film.as<float>();
+    HIP_TRY(c, hipMemcpy(&AccumLayout(c).header->film, &film, sizeof(film), hipMemcpyHostToDevice));
     HIP_TRY(c, hipDeviceSynchronize());
-    c->accum_spectral = true;
-    c->accum_state = srt_ctx::kAccumEmpty;
+    c->accum.begin(srt_ctx::Accumulation::Kind::Spectral);
     return SRT_OK;
 }
 
@@ -627,45 +743,33 @@ int srt_accum_reset_adaptive(srt_ctx *c, const srt_adaptive *cfg) {
     if (!c->params_ready) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_adaptive: device parameters must be set first (srt_init_device_params)");
     int rc = srt_accum_reset(c);
     if (rc != SRT_OK) return rc;
-    c->accum_state = srt_ctx::kAccumInvalid;      // (until the adaptive planes are in place)
-    const uint64_t lanes = c->n_lanes;
-    if (!c->d_adapt || c->adapt_lanes != lanes) {
-        if (c->d_adapt) { (void)hipFree(c->d_adapt); c->d_adapt = nullptr; c->adapt_lanes = 0; }
-        HIP_TRY(c, hipMalloc((void **)&c->d_adapt, 2 * lanes * sizeof(float)));
-        c->adapt_lanes = lanes;
-    }
-    HIP_TRY(c, hipMemset(c->d_adapt, 0, 2 * lanes * sizeof(float)));
+    c->accum.invalidate();      // (until the adaptive planes are in place)
+    HIP_TRY(c, c->d_adapt.reserve(AdaptPlanes::bytes(c->n_lanes)));
+    HIP_TRY(c, hipMemset(c->d_adapt.ptr, 0, AdaptPlanes::bytes(c->n_lanes)));
     // the adaptive half of the header (the per-pass kernel rewrites only sums and spp_total)
-    AccumHeader h;
-    memset(&h, 0, sizeof(h));
-    h.sum2 = reinterpret_cast<float *>(c->d_adapt);
-    h.state = reinterpret_cast<uint32_t *>(c->d_adapt + lanes * sizeof(float));
+    AccumHeader h = {};
+    h.sum2 = AdaptPlanes(c).sum2; h.state = AdaptPlanes(c).state;
     h.rel_tol = cfg->rel_tol; h.abs_tol = cfg->abs_tol; h.min_spp = cfg->min_spp;
     const size_t tail = offsetof(AccumHeader, sum2);
-    HIP_TRY(c, hipMemcpy(c->d_accum + tail, reinterpret_cast<const char *>(&h) + tail, sizeof(h) - tail, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(&AccumLayout(c).header->sum2, reinterpret_cast<const char *>(&h) + tail, sizeof(h) - tail, hipMemcpyHostToDevice));
     HIP_TRY(c, hipDeviceSynchronize());
-    c->accum_adaptive = true;
-    c->accum_state = srt_ctx::kAccumEmpty;
+    c->accum.begin(srt_ctx::Accumulation::Kind::Adaptive);
     return SRT_OK;
 }
 
 int srt_accum_active(srt_ctx *c, uint64_t *active) {
     if (!c || !active) return fail(c, SRT_ERR_INVALID, "srt_accum_active: null argument");
-    if (!c->accum_adaptive || c->accum_state == srt_ctx::kAccumInvalid)
+    if (!c->accum.adaptive() || !c->accum.valid())
         return fail(c, SRT_ERR_INVALID, "srt_accum_active: no adaptive accumulation (srt_accum_reset_adaptive first)");
     *active = 0;
-    if (c->accum_state == srt_ctx::kAccumEmpty) return SRT_OK;      // (the first pass binds the chunk)
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipDeviceSynchronize());
-    unsigned long long counts = 0;
-    HIP_TRY(c, hipMemcpy(&counts, c->d_adapt_queue + 4, sizeof(counts), hipMemcpyDeviceToHost));
-    *active = counts >> 32;
-    return SRT_OK;
+    if (!c->accum.bound()) return SRT_OK;      // (the first pass binds the chunk)
+    if (const int rc = srt_synchronize(c)) return rc;
+    return read_adapt_counts(c, nullptr, active);
 }
 
 int srt_accum_samples(const srt_ctx *c, uint32_t *spp_total) {
     if (!c || !spp_total) return fail(nullptr, SRT_ERR_INVALID, "srt_accum_samples: null argument");
-    *spp_total = c->accum_state == srt_ctx::kAccumInvalid ? 0u : c->accum_total;
+    *spp_total = c->accum.valid() ? c->accum.total : 0u;
     return SRT_OK;
 }
 
@@ -676,24 +780,24 @@ int srt_render_chunk_accum(srt_ctx *c, uint32_t width, uint32_t height, uint32_t
         return fail(c, SRT_ERR_INVALID, "srt_render_chunk_accum: scene, camera and device parameters must be set first");
     if (c->count_traversal)
         return fail(c, SRT_ERR_UNSUPPORTED, "srt_render_chunk_accum: no instrumented accumulating kernel (srt_set_count_traversal(ctx, 0) first)");
-    if (c->accum_state == srt_ctx::kAccumInvalid)
+    if (!c->accum.valid())
         return fail(c, SRT_ERR_INVALID, "srt_render_chunk_accum: no accumulation (srt_accum_reset first; scene, camera, device parameters, partition "
                                         "and a plain srt_render_chunk invalidate it)");
     if (spp_add == 0) return fail(c, SRT_ERR_INVALID, "srt_render_chunk_accum: spp_add must be > 0");
-    if ((uint64_t)c->accum_total + spp_add > 0xffffu)
+    if ((uint64_t)c->accum.total + spp_add > 0xffffu)
         return fail(c, SRT_ERR_INVALID, "srt_render_chunk_accum: the total would exceed 65535 samples per pixel (16-bit spp, Q17)");
     width = (uint16_t)width; height = (uint16_t)height; offx = (uint16_t)offx; offy = (uint16_t)offy;   // rendering.cu:245 (Q17)
-    if (c->accum_state == srt_ctx::kAccumBound && (width != c->accum_w || height != c->accum_h || offx != c->accum_offx || offy != c->accum_offy))
+    if (c->accum.bound() && (width != c->accum.w || height != c->accum.h || offx != c->accum.offx || offy != c->accum.offy))
         return fail(c, SRT_ERR_INVALID, "srt_render_chunk_accum: the accumulation belongs to another chunk (one accumulation per context)");
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     // (the header travels by value in the arguments of a one-lane kernel on the pass's stream: stream-ordered, no host buffer to keep alive)
-    HIP_TRY(c, launch_accum_header(reinterpret_cast<AccumHeader *>(c->d_accum), reinterpret_cast<float *>(c->d_accum + kAccumHeaderBytes), c->accum_total + spp_add, st));
+    HIP_TRY(c, launch_accum_header(AccumLayout(c).header, AccumLayout(c).sums, c->accum.total + spp_add, st));
     const int rc = render_chunk_impl(c, width, height, offx, offy, spp_add, st);
-    if (rc != SRT_OK) { c->accum_state = srt_ctx::kAccumInvalid; return rc; }      // (a launch that failed half-way leaves the sums undefined)
-    c->accum_total += spp_add;
-    c->accum_w = width; c->accum_h = height; c->accum_offx = offx; c->accum_offy = offy;
-    c->accum_state = srt_ctx::kAccumBound;
+    if (rc != SRT_OK) { c->accum.invalidate(); return rc; }      // (a launch that failed half-way leaves the sums undefined)
+    c->accum.total += spp_add;
+    c->accum.w = width; c->accum.h = height; c->accum.offx = offx; c->accum.offy = offy;
+    c->accum.state = srt_ctx::Accumulation::State::Bound;
     return SRT_OK;
 }
 
@@ -706,7 +810,7 @@ int srt_synchronize(srt_ctx *c) {
 
 int srt_tile_buffer(srt_ctx *c, void **dev_ptr, size_t *n_floats, uint32_t *tiles_local, uint32_t *tiles_padded) {
     if (!c || !c->d_tiles) return fail(c, SRT_ERR_INVALID, "srt_tile_buffer: nothing rendered yet");
-    if (dev_ptr) *dev_ptr = c->d_tiles;
+    if (dev_ptr) *dev_ptr = c->d_tiles.ptr;
     if (n_floats) *n_floats = (size_t)c->tiles_padded * c->gather_planes * kTileLanes;      // the exchange unit: the first 1 or 3 plane groups
     if (tiles_local) *tiles_local = c->tiles_local;
     if (tiles_padded) *tiles_padded = c->tiles_padded;
@@ -716,7 +820,7 @@ int srt_tile_buffer(srt_ctx *c, void **dev_ptr, size_t *n_floats, uint32_t *tile
 int srt_copy_tile_buffer(srt_ctx *c, void *dst_dev, void *stream) {
     if (!c || !c->d_tiles || !dst_dev) return fail(c, SRT_ERR_INVALID, "srt_copy_tile_buffer: nothing rendered yet / null destination");
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(dst_dev, c->d_tiles, (size_t)c->tiles_padded * c->gather_planes * kTileLanes * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HIP_TRY(c, hipMemcpyAsync(dst_dev, c->d_tiles.ptr, (size_t)c->tiles_padded * c->gather_planes * kTileLanes * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return SRT_OK;
 }
 
@@ -725,14 +829,13 @@ int srt_scatter_tiles(srt_ctx *c, const void *dev_gathered, void *stream) {
     uint32_t groups = c->gather_planes / (uint32_t)kGroupPlanes;
     if (!dev_gathered) {
         if (c->world != 1) return fail(c, SRT_ERR_INVALID, "srt_scatter_tiles: a gathered buffer is required when world > 1");
-        dev_gathered = c->d_tiles;      // the context's own tile buffer: group 0, and the parity groups when they were asked for
+        dev_gathered = c->d_tiles.ptr;      // the context's own tile buffer: group 0, and the parity groups when they were asked for
     }
     HIP_TRY(c, hipSetDevice(c->device));
-    ScatterParams sp;
-    memset(&sp, 0, sizeof(sp));
+    ScatterParams sp = {};
     sp.gathered = (const float *)dev_gathered;
     sp.groups = groups;
-    for (int p = 0; p < kTilePlanes; p++) sp.fb[p] = c->d_fb + (size_t)p * c->n_lanes;
+    for (int p = 0; p < kTilePlanes; p++) sp.fb[p] = fb_plane(c, p);
     sp.width = c->last_w; sp.height = c->last_h;
     sp.tx = c->tx; sp.ty = c->ty; sp.bx = c->bx; sp.by = c->by;
     sp.tiles_x = c->tiles_x; sp.n_tiles = c->n_tiles; sp.world = c->world; sp.tiles_padded = c->tiles_padded;
@@ -743,20 +846,10 @@ int srt_scatter_tiles(srt_ctx *c, const void *dev_gathered, void *stream) {
 
 int srt_dev_fb(srt_ctx *c, void **r, void **g, void **b, size_t *n_floats) {
     if (!c || !c->d_fb) return fail(c, SRT_ERR_INVALID, "srt_dev_fb: device parameters not initialised");
-    if (r) *r = c->d_fb;
-    if (g) *g = c->d_fb + (size_t)c->n_lanes;
-    if (b) *b = c->d_fb + 2 * (size_t)c->n_lanes;
+    if (r) *r = fb_plane(c, 0);
+    if (g) *g = fb_plane(c, 1);
+    if (b) *b = fb_plane(c, 2);
     if (n_floats) *n_floats = c->n_lanes;
-    return SRT_OK;
-}
-
-static int read_planes(srt_ctx *c, int first_plane, float *p0, float *p1, float *p2) {
-    if (!c || !c->d_fb) return fail(c, SRT_ERR_INVALID, "read: device parameters not initialised");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipDeviceSynchronize());
-    float *dst[3] = {p0, p1, p2};
-    for (int k = 0; k < 3; k++)
-        if (dst[k]) HIP_TRY(c, hipMemcpy(dst[k], c->d_fb + (size_t)(first_plane + k) * c->n_lanes, (size_t)c->n_lanes * sizeof(float), hipMemcpyDeviceToHost));
     return SRT_OK;
 }
 
@@ -770,64 +863,30 @@ int srt_read_fb_aux(srt_ctx *c, int which, float *p0, float *p1, float *p2) {
     return read_planes(c, 3 * which, p0, p1, p2);
 }
 
-}  // extern "C"
-
-// Three block-linear planes of n_lanes words (bits copied as they are) -> the last chunk's rectangle of three row-major host images.
-// A null host plane is not copied (its source plane may be any valid one).
-static int read_rowmajor(srt_ctx *c, const float *const src[3], float *const host[3], uint32_t image_width, uint32_t image_height) {
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n = (size_t)image_width * image_height;
-    // context-owned row-major staging image: the un-swizzle writes the chunk's pixels into it on the device and only the
-    // chunk's rectangle travels to the caller's planes (update_fb touches nothing else either, render_manager.cuh:68-142)
-    if (c->rowmajor_w != image_width || c->rowmajor_h != image_height || !c->d_rowmajor) {
-        if (c->d_rowmajor) { (void)hipFree(c->d_rowmajor); c->d_rowmajor = nullptr; }
-        HIP_TRY(c, hipMalloc((void **)&c->d_rowmajor, 3 * n * sizeof(float)));
-        HIP_TRY(c, hipMemset(c->d_rowmajor, 0, 3 * n * sizeof(float)));
-        c->rowmajor_w = image_width; c->rowmajor_h = image_height;
-    }
-    float *dst[3] = {c->d_rowmajor, c->d_rowmajor + n, c->d_rowmajor + 2 * n};
-    HIP_TRY(c, launch_unswizzle(src, dst, c->tx, c->ty, c->bx, c->by, c->last_w, c->last_h, c->last_offx, c->last_offy, image_width, image_height, nullptr));
-    if (c->last_offx < image_width && c->last_offy < image_height) {
-        const uint32_t w = std::min<uint32_t>(std::min<uint32_t>(c->last_w, c->tx * c->bx), image_width - c->last_offx);
-        const uint32_t h = std::min<uint32_t>(std::min<uint32_t>(c->last_h, c->ty * c->by), image_height - c->last_offy);
-        const size_t first = (size_t)c->last_offy * image_width + c->last_offx, pitch = (size_t)image_width * sizeof(float);
-        for (int k = 0; k < 3 && w && h; k++)
-            if (host[k]) HIP_TRY(c, hipMemcpy2D(host[k] + first, pitch, dst[k] + first, pitch, (size_t)w * sizeof(float), h, hipMemcpyDeviceToHost));
-    }
-    HIP_TRY(c, hipDeviceSynchronize());
-    return SRT_OK;
-}
-
-extern "C" {
-
 int srt_read_fb_rowmajor(srt_ctx *c, float *r, float *g, float *b, uint32_t image_width, uint32_t image_height) {
     if (!c || !c->d_fb || !r || !g || !b || image_width == 0 || image_height == 0) return fail(c, SRT_ERR_INVALID, "srt_read_fb_rowmajor: bad argument");
-    const float *src[3] = {c->d_fb, c->d_fb + (size_t)c->n_lanes, c->d_fb + 2 * (size_t)c->n_lanes};
+    const float *src[3] = {fb_plane(c, 0), fb_plane(c, 1), fb_plane(c, 2)};
     float *const host[3] = {r, g, b};
     return read_rowmajor(c, src, host, image_width, image_height);
 }
 
 int srt_read_accum_stats(srt_ctx *c, uint32_t *samples, float *sum_y, float *sum_y2, uint32_t image_width, uint32_t image_height) {
     if (!c || image_width == 0 || image_height == 0) return fail(c, SRT_ERR_INVALID, "srt_read_accum_stats: bad argument");
-    if (c->accum_state != srt_ctx::kAccumBound)
+    if (!c->accum.bound())
         return fail(c, SRT_ERR_INVALID, "srt_read_accum_stats: no accumulation with a pass (srt_accum_reset[_adaptive] and srt_render_chunk_accum first)");
-    if ((samples || sum_y2) && !c->accum_adaptive)
+    if ((samples || sum_y2) && !c->accum.adaptive())
         return fail(c, SRT_ERR_INVALID, "srt_read_accum_stats: sample counts and S2 belong to an adaptive accumulation (srt_accum_reset_adaptive)");
-    const size_t nl = c->n_lanes;
-    const float *y = reinterpret_cast<const float *>(c->d_accum + kAccumHeaderBytes) + nl;
-    const float *s2 = c->accum_adaptive ? reinterpret_cast<const float *>(c->d_adapt) : y;
-    const float *st = c->accum_adaptive ? reinterpret_cast<const float *>(c->d_adapt) + nl : y;
+    const float *y = AccumLayout(c).y;
+    const float *s2 = c->accum.adaptive() ? AdaptPlanes(c).sum2 : y;
+    const float *st = c->accum.adaptive() ? reinterpret_cast<const float *>(AdaptPlanes(c).state) : y;
     const float *src[3] = {st, y, s2};
     float *const host[3] = {reinterpret_cast<float *>(samples), sum_y, sum_y2};
     const int rc = read_rowmajor(c, src, host, image_width, image_height);
     if (rc != SRT_OK || !samples) return rc;
     // the state words carry the converged flag in bit 31: the map holds the sample counts alone
-    if (c->last_offx < image_width && c->last_offy < image_height) {
-        const uint32_t w = std::min<uint32_t>(std::min<uint32_t>(c->last_w, c->tx * c->bx), image_width - c->last_offx);
-        const uint32_t h = std::min<uint32_t>(std::min<uint32_t>(c->last_h, c->ty * c->by), image_height - c->last_offy);
-        for (uint32_t j = 0; j < h; j++)
-            for (uint32_t i = 0; i < w; i++) samples[(size_t)(c->last_offy + j) * image_width + c->last_offx + i] &= ~kAdaptConverged;
-    }
+    const ChunkRect rect = chunk_rect(c, image_width, image_height);
+    for (uint32_t j = 0; j < rect.h; j++)
+        for (uint32_t i = 0; i < rect.w; i++) samples[rect.first + (size_t)j * image_width + i] &= ~kAdaptConverged;
     return SRT_OK;
 }
 
@@ -835,26 +894,17 @@ int srt_read_spectral(srt_ctx *c, uint32_t first, uint32_t count, float *out, ui
     if (!c || !out || image_width == 0 || image_height == 0) return fail(c, SRT_ERR_INVALID, "srt_read_spectral: bad argument");
     if (count == 0 || (uint64_t)first + count > kFilmSamples)
         return fail(c, SRT_ERR_INVALID, "srt_read_spectral: the range [first, first + count) must be a non-empty part of the 95 grid samples");
-    if (!c->accum_spectral || c->accum_state != srt_ctx::kAccumBound)
+    if (!c->accum.spectral() || !c->accum.bound())
         return fail(c, SRT_ERR_INVALID, "srt_read_spectral: no spectral accumulation with a pass (srt_accum_reset_spectral and srt_render_chunk_accum first)");
     HIP_TRY(c, hipSetDevice(c->device));
-    if (c->last_offx < image_width && c->last_offy < image_height) {
-        // the chunk's rectangle, clipped to the reference grid and the image (srt_read_fb_rowmajor's placement): un-swizzled on the device
-        // into a [h][w][count] staging block, then one 2-D copy into the caller's [image_height][image_width][count] array
-        const uint32_t w = std::min<uint32_t>(std::min<uint32_t>(c->last_w, c->tx * c->bx), image_width - c->last_offx);
-        const uint32_t h = std::min<uint32_t>(std::min<uint32_t>(c->last_h, c->ty * c->by), image_height - c->last_offy);
-        const size_t n = (size_t)w * h * count;
-        if (n) {
-            if (c->film_staging_floats < n) {
-                if (c->d_film_staging) { HIP_TRY(c, hipDeviceSynchronize()); (void)hipFree(c->d_film_staging); c->d_film_staging = nullptr; c->film_staging_floats = 0; }
-                HIP_TRY(c, hipMalloc((void **)&c->d_film_staging, n * sizeof(float)));
-                c->film_staging_floats = n;
-            }
-            HIP_TRY(c, launch_film_unswizzle(c->d_film, c->d_film_staging, first, count, w, h, c->tx, c->ty, c->bx, nullptr));
-            const size_t row = (size_t)w * count * sizeof(float), pitch = (size_t)image_width * count * sizeof(float);
-            float *dst = out + ((size_t)c->last_offy * image_width + c->last_offx) * count;
-            HIP_TRY(c, hipMemcpy2D(dst, pitch, c->d_film_staging, row, row, h, hipMemcpyDeviceToHost));
-        }
+    // the chunk's rectangle, clipped to the reference grid and the image (srt_read_fb_rowmajor's placement): un-swizzled on the device
+    // into a [h][w][count] staging block, then one 2-D copy into the caller's [image_height][image_width][count] array
+    const ChunkRect rect = chunk_rect(c, image_width, image_height);
+    if (const size_t n = (size_t)rect.w * rect.h * count) {
+        HIP_TRY(c, c->d_film_staging.reserve(n * sizeof(float)));
+        HIP_TRY(c, launch_film_unswizzle(c->d_film.as<float>(), c->d_film_staging.as<float>(), first, count, rect.w, rect.h, c->tx, c->ty, c->bx, nullptr));
+        const size_t row = (size_t)rect.w * count * sizeof(float), pitch = (size_t)image_width * count * sizeof(float);
+        HIP_TRY(c, hipMemcpy2D(out + rect.first * count, pitch, c->d_film_staging.ptr, row, row, rect.h, hipMemcpyDeviceToHost));
     }
     HIP_TRY(c, hipDeviceSynchronize());
     return SRT_OK;
@@ -863,18 +913,16 @@ int srt_read_spectral(srt_ctx *c, uint32_t first, uint32_t count, float *out, ui
 int srt_get_tile_costs(srt_ctx *c, uint32_t *out, size_t n) {
     // n = tiles_local: the probe's cost per local tile; n = 2 * tiles_local: followed by the cost of each tile's most expensive pixel
     if (!c || !out || !c->d_tile_cost || (n > c->tiles_local && n != 2 * (size_t)c->tiles_local)) return fail(c, SRT_ERR_INVALID, "srt_get_tile_costs: no probe has run / bad size");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipDeviceSynchronize());
-    HIP_TRY(c, hipMemcpy(out, c->d_tile_cost, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (const int rc = srt_synchronize(c)) return rc;
+    HIP_TRY(c, hipMemcpy(out, c->d_tile_cost.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return SRT_OK;
 }
 
 int srt_get_stats(srt_ctx *c, srt_stats *out) {
     if (!c || !out) return fail(c, SRT_ERR_INVALID, "srt_get_stats: null argument");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipDeviceSynchronize());
+    if (const int rc = srt_synchronize(c)) return rc;
     unsigned long long h[kCounters];
-    HIP_TRY(c, hipMemcpy(h, c->d_counters, sizeof(h), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(h, c->d_counters.ptr, sizeof(h), hipMemcpyDeviceToHost));
     if (h[23] != 0)      // instrumented launches: render_kernel S3's invariant (a wave's first fetch is made by all 64 lanes)
         return fail(c, SRT_ERR_HIP, "srt_get_stats: a wave made a partial first fetch from the pixel queue: its assigned first row was not rendered");
     memset(out, 0, sizeof(*out));
@@ -885,16 +933,16 @@ int srt_get_stats(srt_ctx *c, srt_stats *out) {
     for (int k = 0; k < 4; k++) out->waves[k] = h[19 + k];   // instrumented: waves, sum / max of their life times, drain time
     out->hits = h[24];
     if (c->stats_adaptive) {      // an adaptive pass: the pixels that rendered in it, counted on the device (adapt_flag_kernel)
-        unsigned long long counts = 0;
-        HIP_TRY(c, hipMemcpy(&counts, c->d_adapt_queue + 4, sizeof(counts), hipMemcpyDeviceToHost));
-        out->paths = (counts & 0xffffffffull) * c->stats_spp;
-        return SRT_OK;
+        uint64_t rendered = 0;
+        const int rc = read_adapt_counts(c, &rendered, nullptr);
+        out->paths = rendered * c->stats_spp;
+        return rc;
     }
     // paths = spp * pixels owned by this rank
     uint64_t pixels = 0;
+    const uint32_t lim_w = clipped_w(c), lim_h = clipped_h(c);
     for (uint32_t t = c->rank; t < c->n_tiles; t += c->world) {
         const uint32_t tx0 = (t % c->tiles_x) * 8, ty0 = (t / c->tiles_x) * 8;
-        const uint32_t lim_w = std::min<uint32_t>(c->last_w, c->tx * c->bx), lim_h = std::min<uint32_t>(c->last_h, c->ty * c->by);
         const uint32_t w = tx0 < lim_w ? std::min<uint32_t>(8, lim_w - tx0) : 0, hgt = ty0 < lim_h ? std::min<uint32_t>(8, lim_h - ty0) : 0;
         pixels += (uint64_t)w * hgt;
     }
@@ -903,10 +951,9 @@ int srt_get_stats(srt_ctx *c, srt_stats *out) {
 }
 
 int srt_get_wave_debug(srt_ctx *c, uint32_t *out, size_t n_waves) {
-    if (!c || !out || !c->d_wave_debug || n_waves > c->wave_debug_waves) return fail(c, SRT_ERR_INVALID, "srt_get_wave_debug: no instrumented launch yet / bad size");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipDeviceSynchronize());
-    HIP_TRY(c, hipMemcpy(out, reinterpret_cast<const char *>(c->d_wave_debug) + sizeof(OrderProfile), n_waves * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (!c || !out || !c->d_wave_debug || n_waves > wave_debug_waves(c)) return fail(c, SRT_ERR_INVALID, "srt_get_wave_debug: no instrumented launch yet / bad size");
+    if (const int rc = srt_synchronize(c)) return rc;
+    HIP_TRY(c, hipMemcpy(out, c->d_wave_debug.as<const char>() + sizeof(OrderProfile), n_waves * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return SRT_OK;
 }
 
@@ -925,7 +972,7 @@ int srt_order_children_by_profile(srt_ctx *c, srt_scene *s, uint32_t width, uint
                                   uint32_t min_samples, uint32_t *n_swapped) {
     if (n_swapped) *n_swapped = 0;
     if (!c || !s || !s->bvh_valid) return fail(c, SRT_ERR_INVALID, "srt_order_children_by_profile: null argument / BVH not built");
-    c->accum_state = srt_ctx::kAccumInvalid;
+    c->accum.invalidate();
     if (!c->camera_ready) return fail(c, SRT_ERR_INVALID, "srt_order_children_by_profile: set the camera first (srt_set_camera)");
     if (width == 0 || height == 0 || spp == 0) return fail(c, SRT_ERR_INVALID, "srt_order_children_by_profile: empty probe frame");
     const size_t n_nodes = s->nodes.size(), n_tris = s->raw.size();
@@ -940,18 +987,17 @@ int srt_order_children_by_profile(srt_ctx *c, srt_scene *s, uint32_t width, uint
         memcpy(&sibbox[6 * (size_t)nd.left], s->nodes[(size_t)nd.right].box, 6 * sizeof(float));
         memcpy(&sibbox[6 * (size_t)nd.right], s->nodes[(size_t)nd.left].box, 6 * sizeof(float));
     }
-    int32_t *d_leaf = nullptr, *d_up = nullptr; float *d_sib = nullptr; uint32_t *d_cnt = nullptr;
-    auto release = [&]() { (void)hipFree(d_leaf); (void)hipFree(d_up); (void)hipFree(d_sib); (void)hipFree(d_cnt); c->order_profile = OrderProfile{}; };
     HIP_TRY(c, hipSetDevice(c->device));
-    hipError_t e = hipMalloc((void **)&d_leaf, std::max<size_t>(n_tris, 1) * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_up, n_nodes * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_sib, 6 * n_nodes * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_cnt, 2 * n_nodes * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemcpy(d_leaf, leaf.data(), n_tris * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_up, up.data(), n_nodes * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_sib, sibbox.data(), 6 * n_nodes * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(d_cnt, 0, 2 * n_nodes * sizeof(uint32_t));
-    if (e != hipSuccess) { release(); return hip_fail(c, e, "srt_order_children_by_profile: device buffers"); }
+    DeviceBuffer d_leaf, d_up, d_sib, d_cnt;      // (the probe frames' c->order_profile points at them: probe_frame clears it before it returns)
+    const char *what = "srt_order_children_by_profile: device buffers";
+    HIP_TRY_AS(c, what, d_leaf.reserve(std::max<size_t>(n_tris, 1) * sizeof(int32_t)));
+    HIP_TRY_AS(c, what, d_up.reserve(n_nodes * sizeof(int32_t)));
+    HIP_TRY_AS(c, what, d_sib.reserve(6 * n_nodes * sizeof(float)));
+    HIP_TRY_AS(c, what, d_cnt.reserve(2 * n_nodes * sizeof(uint32_t)));
+    HIP_TRY_AS(c, what, hipMemcpy(d_leaf.ptr, leaf.data(), n_tris * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY_AS(c, what, hipMemcpy(d_up.ptr, up.data(), n_nodes * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY_AS(c, what, hipMemcpy(d_sib.ptr, sibbox.data(), 6 * n_nodes * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY_AS(c, what, hipMemset(d_cnt.ptr, 0, 2 * n_nodes * sizeof(uint32_t)));
     // instrumented probe frames on this context alone (its partition and counter setting are restored afterwards)
     const bool counting = c->count_traversal;
     const uint32_t rank = c->rank, world = c->world;
@@ -959,8 +1005,8 @@ int srt_order_children_by_profile(srt_ctx *c, srt_scene *s, uint32_t width, uint
     auto probe_frame = [&](bool collect, unsigned long long &work) -> int {
         c->order_profile = OrderProfile{};
         if (collect) {
-            c->order_profile.magic = kOrderProfileMagic; c->order_profile.leaf = d_leaf; c->order_profile.up = d_up;
-            c->order_profile.sibbox = d_sib; c->order_profile.cnt = d_cnt; c->order_profile.n_nodes = n_nodes;
+            c->order_profile.magic = kOrderProfileMagic; c->order_profile.leaf = d_leaf.as<int32_t>(); c->order_profile.up = d_up.as<int32_t>();
+            c->order_profile.sibbox = d_sib.as<float>(); c->order_profile.cnt = d_cnt.as<uint32_t>(); c->order_profile.n_nodes = n_nodes;
         }
         c->count_traversal = true; c->rank = 0; c->world = 1;
         int r = srt_init_device_params(c, tx, ty, bx, by, width, height, spp, bounce_limit, 1984);
@@ -971,22 +1017,20 @@ int srt_order_children_by_profile(srt_ctx *c, srt_scene *s, uint32_t width, uint
         c->params_ready = false;      // (the probe's RNG state and grid are not the caller's: srt_init_device_params comes next)
         if (r != SRT_OK) return r;
         unsigned long long h[kCounters];
-        const hipError_t he = hipMemcpy(h, c->d_counters, sizeof(h), hipMemcpyDeviceToHost);
-        if (he != hipSuccess) return hip_fail(c, he, "srt_order_children_by_profile: counters");
+        HIP_TRY_AS(c, "srt_order_children_by_profile: counters", hipMemcpy(h, c->d_counters.ptr, sizeof(h), hipMemcpyDeviceToHost));
         work = h[1] + 2ull * h[2];      // node records visited + 2 x triangle tests
         return SRT_OK;
     };
     unsigned long long work_before = 0, work_after = 0;
-    rc = probe_frame(true, work_before);
+    if ((rc = probe_frame(true, work_before)) != SRT_OK) return rc;
     std::vector<uint32_t> cnt(2 * n_nodes, 0u);
-    if (rc == SRT_OK) { e = hipMemcpy(cnt.data(), d_cnt, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost); if (e != hipSuccess) rc = hip_fail(c, e, "srt_order_children_by_profile: read back"); }
-    if (rc != SRT_OK) { release(); return rc; }
+    HIP_TRY_AS(c, "srt_order_children_by_profile: read back", hipMemcpy(cnt.data(), d_cnt.ptr, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     {
         // a collecting launch that recorded nothing (header not seen by the kernel, or a probe frame without a single hit) must not read
         // as "the order was already the cheapest"
         unsigned long long samples = 0;
         for (uint32_t v : cnt) samples += v;
-        if (samples == 0) { release(); return fail(c, SRT_ERR_INVALID, "srt_order_children_by_profile: the probe frame recorded no samples (no closest hit with the sibling's box beyond it)"); }
+        if (samples == 0) return fail(c, SRT_ERR_INVALID, "srt_order_children_by_profile: the probe frame recorded no samples (no closest hit with the sibling's box beyond it)");
     }
     const uint32_t *won = cnt.data();      // [node * 2 + side]: hits under that child with the sibling's box beyond the hit
     std::vector<uint32_t> swapped_nodes;
@@ -1005,7 +1049,6 @@ int srt_order_children_by_profile(srt_ctx *c, srt_scene *s, uint32_t width, uint
             rc = srt_upload_scene(c, s);
         }
     }
-    release();
     if (rc == SRT_OK && n_swapped) *n_swapped = (uint32_t)swapped_nodes.size();
     return rc;
 }
@@ -1028,18 +1071,15 @@ int srt_trace_rays(srt_ctx *c, const float *rays, size_t n, float *out) {
     if (!c || !c->scene_ready || (!rays && n) || (!out && n)) return fail(c, SRT_ERR_INVALID, "srt_trace_rays: scene not uploaded / bad argument");
     if (n == 0) return SRT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    float *d_in = nullptr, *d_out = nullptr;
-    HIP_TRY(c, hipMalloc((void **)&d_in, 6 * n * sizeof(float)));
-    hipError_t e = hipMalloc((void **)&d_out, 4 * n * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(d_in, rays, 6 * n * sizeof(float), hipMemcpyHostToDevice);
+    DeviceBuffer d_in, d_out;
+    HIP_TRY_AS(c, "srt_trace_rays", d_in.reserve(6 * n * sizeof(float)));
+    HIP_TRY_AS(c, "srt_trace_rays", d_out.reserve(4 * n * sizeof(float)));
+    HIP_TRY_AS(c, "srt_trace_rays", hipMemcpy(d_in.ptr, rays, 6 * n * sizeof(float), hipMemcpyHostToDevice));
     RenderParams p;
     fill_params(c, p);
-    if (e == hipSuccess) e = launch_trace(p, d_in, n, d_out, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(out, d_out, 4 * n * sizeof(float), hipMemcpyDeviceToHost);
-    (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (e != hipSuccess) return hip_fail(c, e, "srt_trace_rays");
+    HIP_TRY_AS(c, "srt_trace_rays", launch_trace(p, d_in.as<float>(), n, d_out.as<float>(), nullptr));
+    HIP_TRY_AS(c, "srt_trace_rays", hipDeviceSynchronize());
+    HIP_TRY_AS(c, "srt_trace_rays", hipMemcpy(out, d_out.ptr, 4 * n * sizeof(float), hipMemcpyDeviceToHost));
     return SRT_OK;
 }
 
@@ -1047,15 +1087,14 @@ int srt_device_op_sweep(srt_ctx *c, int which, const float *a, const float *b, s
     if (!c || !a || !b || !out) return fail(c, SRT_ERR_INVALID, "srt_device_op_sweep: null argument");
     if (n == 0) return SRT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    float *d = nullptr;
-    HIP_TRY(c, hipMalloc((void **)&d, 3 * n * sizeof(float)));
-    hipError_t e = hipMemcpy(d, a, n * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d + n, b, n * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch_op_sweep(which, d, d + n, n, d + 2 * n, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(out, d + 2 * n, n * sizeof(float), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return hip_fail(c, e, "srt_device_op_sweep");
+    DeviceBuffer buf;      // a | b | out
+    HIP_TRY_AS(c, "srt_device_op_sweep", buf.reserve(3 * n * sizeof(float)));
+    float *d = buf.as<float>();
+    HIP_TRY_AS(c, "srt_device_op_sweep", hipMemcpy(d, a, n * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY_AS(c, "srt_device_op_sweep", hipMemcpy(d + n, b, n * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY_AS(c, "srt_device_op_sweep", launch_op_sweep(which, d, d + n, n, d + 2 * n, nullptr));
+    HIP_TRY_AS(c, "srt_device_op_sweep", hipDeviceSynchronize());
+    HIP_TRY_AS(c, "srt_device_op_sweep", hipMemcpy(out, d + 2 * n, n * sizeof(float), hipMemcpyDeviceToHost));
     return SRT_OK;
 }
 
@@ -1064,32 +1103,27 @@ int srt_calibrate(srt_ctx *c, int kind, uint32_t waves_per_simd, uint32_t iters,
         return fail(c, SRT_ERR_INVALID, "srt_calibrate: bad argument");
     HIP_TRY(c, hipSetDevice(c->device));
     const uint32_t threads = waves_per_simd * 256u, n_blocks = (uint32_t)c->n_cu, n_waves = n_blocks * threads / 64u;
-    unsigned long long *d_cyc = nullptr;
-    float *d_sink = nullptr;
-    HIP_TRY(c, hipMalloc((void **)&d_cyc, n_waves * sizeof(unsigned long long)));
-    hipError_t e = hipMalloc((void **)&d_sink, 1024 * sizeof(float));
+    DeviceBuffer d_cyc, d_sink, d_table;
+    HIP_TRY_AS(c, "srt_calibrate", d_cyc.reserve(n_waves * sizeof(unsigned long long)));
+    HIP_TRY_AS(c, "srt_calibrate", d_sink.reserve(1024 * sizeof(float)));
     // kinds 11+: a 16 MB table of 64-byte records (the size of the 100k-triangle mesh's tree: served by L2 / MALL)
     const uint32_t n_table = 1u << 18;
-    float4 *d_table = nullptr;
-    if (e == hipSuccess && kind >= 11) { e = hipMalloc((void **)&d_table, (size_t)n_table * 64); if (e == hipSuccess) e = hipMemset(d_table, 0, (size_t)n_table * 64); }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (e == hipSuccess) e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = launch_calib(kind, n_blocks, threads, iters / 8u + 1u, d_sink, d_cyc, d_table, n_table, nullptr);   // warm-up (clocks, code)
-    if (e == hipSuccess) e = hipEventRecord(e0, nullptr);
-    if (e == hipSuccess) e = launch_calib(kind, n_blocks, threads, iters, d_sink, d_cyc, d_table, n_table, nullptr);
-    if (e == hipSuccess) e = hipEventRecord(e1, nullptr);
-    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    if (kind >= 11) {
+        HIP_TRY_AS(c, "srt_calibrate", d_table.reserve((size_t)n_table * 64));
+        HIP_TRY_AS(c, "srt_calibrate", hipMemset(d_table.ptr, 0, (size_t)n_table * 64));
+    }
+    struct Event { hipEvent_t ev = nullptr; ~Event() { if (ev) (void)hipEventDestroy(ev); } } e0, e1;
+    HIP_TRY_AS(c, "srt_calibrate", hipEventCreate(&e0.ev));
+    HIP_TRY_AS(c, "srt_calibrate", hipEventCreate(&e1.ev));
+    HIP_TRY_AS(c, "srt_calibrate", launch_calib(kind, n_blocks, threads, iters / 8u + 1u, d_sink.as<float>(), d_cyc.as<unsigned long long>(), d_table.as<float4>(), n_table, nullptr));   // warm-up (clocks, code)
+    HIP_TRY_AS(c, "srt_calibrate", hipEventRecord(e0.ev, nullptr));
+    HIP_TRY_AS(c, "srt_calibrate", launch_calib(kind, n_blocks, threads, iters, d_sink.as<float>(), d_cyc.as<unsigned long long>(), d_table.as<float4>(), n_table, nullptr));
+    HIP_TRY_AS(c, "srt_calibrate", hipEventRecord(e1.ev, nullptr));
+    HIP_TRY_AS(c, "srt_calibrate", hipEventSynchronize(e1.ev));
     float ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+    HIP_TRY_AS(c, "srt_calibrate", hipEventElapsedTime(&ms, e0.ev, e1.ev));
     std::vector<unsigned long long> h(n_waves);
-    if (e == hipSuccess) e = hipMemcpy(h.data(), d_cyc, n_waves * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(d_cyc);
-    if (d_sink) (void)hipFree(d_sink);
-    if (d_table) (void)hipFree(d_table);
-    if (e != hipSuccess) return hip_fail(c, e, "srt_calibrate");
+    HIP_TRY_AS(c, "srt_calibrate", hipMemcpy(h.data(), d_cyc.ptr, n_waves * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     double sum = 0, mx = 0, mn = 1e300;
     for (unsigned long long v : h) { sum += (double)v; mx = std::max(mx, (double)v); mn = std::min(mn, (double)v); }
     memset(out, 0, sizeof(*out));

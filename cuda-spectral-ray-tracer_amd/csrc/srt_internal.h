@@ -123,8 +123,11 @@ hipError_t launch_init_rng(uint32_t *rng, uint32_t n_lanes, uint64_t seed, hipSt
 // Test knobs of a context (srt_set_test_knobs; from the environment only under SRT_TEST_KNOBS=1, read once at srt_create): they pick
 // the kernel variant / cache size a launch plan would not pick by itself, so that every instantiated variant can be held to the CPU oracle by the tests.
 struct PlanKnobs { bool wide_refs = false; int lds_cache_max = -1; };
-// mode 0 render, 1 instrumented, 2 cost probe, 3 accumulating render (p.wave_debug -> AccumHeader), 4 adaptive accumulating render, 5 spectral accumulating render; waves_launched (optional) = persistent waves of the launch
-hipError_t launch_render(const RenderParams &p, const PlanKnobs &knobs, uint32_t n_cu, int mode, hipStream_t st, uint32_t *waves_launched = nullptr);
+// The render launch's variant; the values are render_kernel's MODE template argument.  Plain: render; Counting: instrumented; Probe: cost
+// probe; Accum: accumulating render (p.wave_debug -> AccumHeader); Adaptive / Spectral: adaptive / spectral accumulating render.
+enum RenderMode { Plain = 0, Counting = 1, Probe = 2, Accum = 3, Adaptive = 4, Spectral = 5 };
+// waves_launched (optional) = persistent waves of the launch
+hipError_t launch_render(const RenderParams &p, const PlanKnobs &knobs, uint32_t n_cu, RenderMode mode, hipStream_t st, uint32_t *waves_launched = nullptr);
 hipError_t launch_accum_header(AccumHeader *dst, float *sums, uint32_t spp_total, hipStream_t st);      // writes *dst on the stream
 // Pixel queue of the next adaptive pass (see adapt_flag_kernel): the rows of `src_rows` (src_info[0] of them; nullptr: the identity
 // queue of n_identity local tiles) whose share of the tile still holds an active pixel, in their order, into dst_rows / dst_info[0..1];

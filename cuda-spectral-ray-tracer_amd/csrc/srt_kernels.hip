@@ -1123,7 +1123,7 @@ static hipError_t launch_render_mode(const RenderParams &p, const PlanKnobs &kno
     return lp.all_cached ? launch_render_cached<MODE, NARROW, true>(p, lp, knobs, n_cu, st, waves_launched) : launch_render_cached<MODE, NARROW, false>(p, lp, knobs, n_cu, st, waves_launched);
 }
 
-hipError_t launch_render(const RenderParams &p, const PlanKnobs &knobs, uint32_t n_cu, int mode, hipStream_t st, uint32_t *waves_launched) {
+hipError_t launch_render(const RenderParams &p, const PlanKnobs &knobs, uint32_t n_cu, RenderMode mode, hipStream_t st, uint32_t *waves_launched) {
     if (waves_launched) *waves_launched = 0;
     if (p.tiles_local == 0) return hipSuccess;
     const bool narrow = render_narrow_refs(p.n_records, knobs);

@@ -1,6 +1,7 @@
 """Device renderer handle (srt_ctx): the `renderer` / render_manager::step pair of the reference
 (rendering/rendering.cuh:39-155, rendering/render_manager.cu:3-66) over the C-ABI.  All compute happens in
 libsrt_hip.so on the GPU; this module only moves pointers."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -419,22 +420,38 @@ def profile_child_order(renderer, scene, width, height, bounce_limit):
 def render_image(scene, cam, width, height, spp, bounce_limit, seed=1984, device=0, count_traversal=False, renderer=None):
     """Whole-image single-chunk render on one GPU (the reference's default configuration, Q13).
     Returns dict with block-linear planes, row-major quantised planes, stats and kernel ms."""
+    with _image_session(scene, cam, width, height, spp, bounce_limit, seed, device, renderer, count_traversal) as r:
+        r.render_chunk(width, height, 0, 0)
+        r.scatter_tiles()
+        return _collect(r, width, height)
+
+
+@contextlib.contextmanager
+def _image_session(scene, cam, width, height, spp, bounce_limit, seed, device, renderer, count_traversal=False):
+    """The set-up and tear-down every whole-image render on one GPU shares: `renderer` (or a new one on `device`, closed on exit) with
+    scene, camera and device parameters in place, the whole frame as its partition and all nine planes as its exchange unit (restored
+    on exit).  The planes are set before the caller's reset: a change of the planes ends an adaptive accumulation."""
     r = renderer or Renderer(device)
-    r.upload_scene(scene)
-    r.set_camera(cam)
-    r.init_device_params(width, height, spp, bounce_limit, seed)
-    r.set_partition(0, 1)
-    r.set_count_traversal(count_traversal)
     planes_before = r.gather_planes
-    r.set_gather_planes(9)            # the parity planes (unquantised sRGB, XYZ sums) are part of what this returns
-    r.render_chunk(width, height, 0, 0)
-    r.scatter_tiles()
-    r.set_gather_planes(planes_before)
-    out = dict(fb=r.read_fb(), lin=r.read_fb_aux(1), xyz=r.read_fb_aux(2), rowmajor=r.read_fb_rowmajor(width, height),
-               stats=r.stats(), kernel_ms=r.last_kernel_ms(), geom=dict(r.geom))
-    if renderer is None:
-        r.close()
-    return out
+    try:
+        r.upload_scene(scene)
+        r.set_camera(cam)
+        r.init_device_params(width, height, spp, bounce_limit, seed)
+        r.set_partition(0, 1)
+        r.set_count_traversal(count_traversal)
+        r.set_gather_planes(9)            # the parity planes (unquantised sRGB, XYZ sums) are part of what the callers return
+        yield r
+    finally:
+        if r._h:
+            r.set_gather_planes(planes_before)
+        if renderer is None:
+            r.close()
+
+
+def _collect(r, width, height):
+    """the result dict of render_image from the frame `r` has just scattered"""
+    return dict(fb=r.read_fb(), lin=r.read_fb_aux(1), xyz=r.read_fb_aux(2), rowmajor=r.read_fb_rowmajor(width, height),
+                stats=r.stats(), kernel_ms=r.last_kernel_ms(), geom=dict(r.geom))
 
 
 MAX_SPP = 65535      # the reference's spp is a short_uint (Q17): a progressive total cannot pass it either
@@ -462,27 +479,12 @@ def render_progressive(scene, cam, width, height, passes, bounce_limit, seed=198
 
 
 def _progressive_passes(scene, cam, width, height, sched, bounce_limit, seed, device, renderer):
-    r = renderer or Renderer(device)
-    planes_before = r.gather_planes
-    try:
-        r.upload_scene(scene)
-        r.set_camera(cam)
-        r.init_device_params(width, height, sum(sched), bounce_limit, seed)
-        r.set_partition(0, 1)
-        r.set_count_traversal(False)
-        r.set_gather_planes(9)            # the parity planes (unquantised sRGB, XYZ sums) are part of what this returns
+    with _image_session(scene, cam, width, height, sum(sched), bounce_limit, seed, device, renderer) as r:
         r.accum_reset()
         for spp_add in sched:
             r.render_chunk_accum(width, height, spp_add)
             r.scatter_tiles()
-            out = dict(fb=r.read_fb(), lin=r.read_fb_aux(1), xyz=r.read_fb_aux(2), rowmajor=r.read_fb_rowmajor(width, height),
-                       stats=r.stats(), kernel_ms=r.last_kernel_ms(), geom=dict(r.geom))
-            yield r.accum_samples, out
-    finally:
-        if r._h:
-            r.set_gather_planes(planes_before)
-        if renderer is None:
-            r.close()
+            yield r.accum_samples, _collect(r, width, height)
 
 
 def adaptive_config(rel_tol, abs_tol=0.0, min_spp=16):
@@ -532,31 +534,17 @@ def render_adaptive(scene, cam, width, height, bounce_limit, rel_tol, abs_tol=0.
 
 
 def _adaptive_passes(scene, cam, width, height, bounce_limit, cfg, sched, seed, device, renderer):
-    r = renderer or Renderer(device)
-    planes_before = r.gather_planes
-    try:
-        r.upload_scene(scene)
-        r.set_camera(cam)
-        r.init_device_params(width, height, sum(sched), bounce_limit, seed)
-        r.set_partition(0, 1)
-        r.set_count_traversal(False)
-        r.set_gather_planes(9)            # before the reset: a change of the planes ends an adaptive accumulation
-        r._ck(B.lib().srt_accum_reset_adaptive(r._h, C.byref(cfg)))
+    with _image_session(scene, cam, width, height, sum(sched), bounce_limit, seed, device, renderer) as r:
+        r._ck(B.lib().srt_accum_reset_adaptive(r._h, C.byref(cfg)))      # (after the session has set the planes)
         for spp_add in sched:
             r.render_chunk_accum(width, height, spp_add)
             r.scatter_tiles()
             active = r.accum_active
-            out = dict(fb=r.read_fb(), lin=r.read_fb_aux(1), xyz=r.read_fb_aux(2), rowmajor=r.read_fb_rowmajor(width, height),
-                       stats=r.stats(), kernel_ms=r.last_kernel_ms(), geom=dict(r.geom),
-                       samples=r.accum_stats(width, height)["samples"])
+            out = _collect(r, width, height)
+            out["samples"] = r.accum_stats(width, height)["samples"]
             yield r.accum_samples, active, out
             if active == 0:
                 break
-    finally:
-        if r._h:
-            r.set_gather_planes(planes_before)
-        if renderer is None:
-            r.close()
 
 
 def spectral_wavelengths():
@@ -604,25 +592,11 @@ def render_spectral(scene, cam, width, height, passes, bounce_limit, seed=1984, 
 
 
 def _spectral_passes(scene, cam, width, height, sched, bounce_limit, seed, device, renderer, first, count):
-    r = renderer or Renderer(device)
-    planes_before = r.gather_planes
-    try:
-        r.upload_scene(scene)
-        r.set_camera(cam)
-        r.init_device_params(width, height, sum(sched), bounce_limit, seed)
-        r.set_partition(0, 1)
-        r.set_count_traversal(False)
-        r.set_gather_planes(9)            # the parity planes (unquantised sRGB, XYZ sums) are part of what this returns
+    with _image_session(scene, cam, width, height, sum(sched), bounce_limit, seed, device, renderer) as r:
         r.accum_reset_spectral()
         for spp_add in sched:
             r.render_chunk_accum(width, height, spp_add)
             r.scatter_tiles()
-            out = dict(fb=r.read_fb(), lin=r.read_fb_aux(1), xyz=r.read_fb_aux(2), rowmajor=r.read_fb_rowmajor(width, height),
-                       stats=r.stats(), kernel_ms=r.last_kernel_ms(), geom=dict(r.geom),
-                       film=r.read_spectral(width, height, first, count))
+            out = _collect(r, width, height)
+            out["film"] = r.read_spectral(width, height, first, count)
             yield r.accum_samples, out, spectral_radiance(out["film"], r.accum_samples, first)
-    finally:
-        if r._h:
-            r.set_gather_planes(planes_before)
-        if renderer is None:
-            r.close()
