@@ -350,7 +350,7 @@ QueueSource queue_source(const srt_ctx *c, const Pass &ps) {
     // (adaptive passes after the first: the queue the previous pass compacted -- the probe's rows, or the identity order, whose tiles
     // still hold an active pixel.  A queue row has a 22-bit tile field: beyond that the pass runs the plain identity queue, and its
     // converged pixels are only skipped at the fetch)
-    if (ps.mode == Adaptive && ps.later && c->tiles_local <= 0x3fffffu) return QueueSource::Compacted;
+    if (ps.mode == Adaptive && ps.later && c->tiles_local <= kQueueTileMask) return QueueSource::Compacted;
     if (!ps.ordered) return QueueSource::Identity;
     // (accumulating passes: the probe runs on the FIRST pass whatever its sample count -- short passes would otherwise run an unordered
     // queue -- and the later passes of the accumulation reuse its queue: a tile's cost depends on its geometry, not on the sample index,
@@ -359,7 +359,7 @@ QueueSource queue_source(const srt_ctx *c, const Pass &ps) {
 }
 
 int choose_queue(srt_ctx *c, Pass &ps, RenderParams &p) {
-    const bool schedulable = c->probe_spp > 0 && c->tiles_local > 1 && c->tiles_local <= 0x3fffffu;   // 22-bit tile field of a queue row
+    const bool schedulable = c->probe_spp > 0 && c->tiles_local > 1 && c->tiles_local <= kQueueTileMask;   // the tile field of a queue row
     ps.ordered = schedulable && (ps.spp_add || c->spp > 4 * c->probe_spp);
     ps.adapt_bound = ps.ordered && c->split_load_pct ? split_rows_bound(c) : c->tiles_local;
     if (ps.mode == Adaptive) HIP_TRY(c, c->d_adapt_queue.reserve(AdaptQueue::bytes(std::max<uint32_t>(ps.adapt_bound, 1u))));

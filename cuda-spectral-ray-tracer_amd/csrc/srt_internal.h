@@ -18,6 +18,12 @@ constexpr int kGroupPlanes = 3;
 constexpr int kTileLanes = 64;      // one wave = one 8x8 pixel tile
 constexpr int kCounters = 32;       // rays, node_visits, tri_tests, box_tests, utilisation counters (instrumented build); [23] queue invariant, [24] hits
 
+// Row of a launch's pixel queue: local tile | part << 22 | level << 28 (queue_row_pack, srt_kernel_common.h).  A rank whose local tiles
+// do not fit the tile field renders unordered: without a queue the row IS the local tile.
+constexpr uint32_t kQueueTileBits = 22, kQueueTileMask = (1u << kQueueTileBits) - 1u;
+constexpr uint32_t kQueuePartShift = kQueueTileBits, kQueuePartMask = 63u;
+constexpr uint32_t kQueueLevelShift = 28, kQueueLevelMask = 7u;
+
 // Kernel arguments of one render launch.  All pointers are device pointers.
 struct RenderParams {
     // scene (HBM layout: DESIGN.md)

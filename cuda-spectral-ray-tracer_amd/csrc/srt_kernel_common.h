@@ -70,4 +70,31 @@ __device__ __forceinline__ uint32_t block_linear_idx(uint32_t i, uint32_t j, uin
     return ly * tx + lx + tx * ty * (gby * bx + gbx);
 }
 
+// Pixel queue.  A row stands for 64 slots of one 8x8 tile: row = tile | part << 22 | s << 28 with the rank's LOCAL tile, and the row's
+// share of the tile is the slots [part * (64 >> s), (part + 1) * (64 >> s)) (s = 0: the whole tile; order_tiles_kernel splits an
+// expensive tile into 2^s rows, each taken by a different wave).  Slot lt of local tile t is pixel (lt & 7, lt >> 3) of global tile
+// rank + world * t, tiles in row-major order over the chunk.  (Two helpers, not one: render_kernel reads rank and world, then tiles_x.)
+struct QueueRow { uint32_t tile_local, part, s; };
+__host__ __device__ __forceinline__ uint32_t queue_row_pack(uint32_t tile_local, uint32_t part, uint32_t s) {
+    return tile_local | (part << kQueuePartShift) | (s << kQueueLevelShift);
+}
+__host__ __device__ __forceinline__ QueueRow queue_row_unpack(uint32_t row) {
+    return {row & kQueueTileMask, (row >> kQueuePartShift) & kQueuePartMask, (row >> kQueueLevelShift) & kQueueLevelMask};
+}
+__device__ __forceinline__ bool queue_slot_in_share(uint32_t lt, uint32_t part, uint32_t s) { return (lt >> (6u - s)) == part; }
+
+struct PixelIJ { uint32_t i, j; };      // chunk-relative column and row (rendering.cu:156-157)
+__device__ __forceinline__ uint32_t queue_global_tile(uint32_t tile_local, uint32_t rank, uint32_t world) { return rank + world * tile_local; }
+__device__ __forceinline__ PixelIJ tile_slot_pixel(uint32_t tile, uint32_t lt, uint32_t tiles_x) {
+    const uint32_t tile_x = tile % tiles_x, tile_y = tile / tiles_x;
+    return {tile_x * 8u + (lt & 7u), tile_y * 8u + (lt >> 3)};
+}
+// Is slot lt of global tile `tile`, at pixel px, a pixel of the chunk?  Slots outside the chunk (or the reference grid) never touch RNG
+// or output (rendering.cu:205).  render_kernel's fetch spells this test out with lazy reads of its LDS uniforms: with the eight values
+// read up front for a call, every render kernel compiles to other machine code.
+__device__ __forceinline__ bool queue_slot_in_chunk(uint32_t tile, uint32_t lt, PixelIJ px, uint32_t n_tiles, uint32_t lane_limit, uint32_t width,
+                                                    uint32_t height, uint32_t tx, uint32_t ty, uint32_t bx, uint32_t by) {
+    return (tile < n_tiles) && (lt < lane_limit) && (px.i < width) && (px.j < height) && (px.i / tx < bx) && (px.j / ty < by);
+}
+
 }  // namespace srt

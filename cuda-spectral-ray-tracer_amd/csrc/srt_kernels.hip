@@ -539,31 +539,28 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
                     const uint32_t pix = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
                     if (pix >= U->n_rows * 64u) { dead = true; searching = false; if (COUNT && t_dry == 0) t_dry = __builtin_amdgcn_s_memtime(); }
                     else {
-                        // queue row = tile | part << 22 | s << 28: the row covers lanes [part * (64 >> s), (part + 1) * (64 >> s))
-                        // of the tile (s = 0: the whole tile).  Cost-descending order, see order_tiles_kernel.
+                        // decode of the queue row and of the slot: srt_kernel_common.h (cost-descending order, see order_tiles_kernel)
                         const uint32_t *tile_order = join_ptr<const uint32_t>(U->tile_order[0], U->tile_order[1]);
                         // (no ordered queue: the row IS the local tile, whatever its magnitude -- nothing to decode)
-                        const uint32_t row = tile_order ? tile_order[pix >> 6] : 0u;
-                        const uint32_t tile_local = tile_order ? (row & 0x3fffffu) : (pix >> 6);
-                        const uint32_t row_part = (row >> 22) & 63u, row_s = (row >> 28) & 7u;
+                        const QueueRow qr = queue_row_unpack(tile_order ? tile_order[pix >> 6] : 0u);
+                        const uint32_t tile_local = tile_order ? qr.tile_local : (pix >> 6);
+                        const uint32_t row_s = qr.s;
                         const uint32_t lt = pix & 63u;
                         // A split row is meant for a wave that takes it whole (all 64 lanes fetch together: first fill, or
                         // after an exclusive row).  Then the lanes outside the row's share park.  A lane that refills on its own
                         // and lands in a split row just skips a slot that is not the row's share, and renders one that is like
                         // any other pixel.
                         const bool whole_wave = m == ~0ull;
-                        if ((lt >> (6u - row_s)) != row_part) {
+                        if (!queue_slot_in_share(lt, qr.part, row_s)) {
                             if (whole_wave) { parked = true; searching = false; }
                             continue;
                         }
                         exclusive = whole_wave && row_s != 0u;
-                        const uint32_t tile = U->rank + U->world * tile_local;
-                        const uint32_t tiles_x = U->tiles_x;
-                        const uint32_t tile_x = tile % tiles_x, tile_y = tile / tiles_x;
-                        const uint32_t i = tile_x * 8u + (lt & 7u);          // chunk-relative column (rendering.cu:156)
-                        const uint32_t j = tile_y * 8u + (lt >> 3);          // chunk-relative row    (rendering.cu:157)
+                        const uint32_t tile = queue_global_tile(tile_local, U->rank, U->world);
+                        const PixelIJ px = tile_slot_pixel(tile, lt, U->tiles_x);
+                        const uint32_t i = px.i, j = px.j;
                         const uint32_t gtx = U->tx, gty = U->ty, gbx = U->bx;
-                        // pixels outside the chunk (or the reference grid) never touch RNG or output (rendering.cu:205)
+                        // queue_slot_in_chunk, spelt out (see there): the uniforms are read only as far as the test gets
                         if ((tile < U->n_tiles) && (lt < U->lane_limit) && (i < U->width) && (j < U->height) && (i / gtx < gbx) && (j / gty < U->by)) {
                             if constexpr (ADAPT) {      // a converged pixel is left alone (no RNG draw, no store): fetch again
                                 const uint32_t *state = join_ptr<const uint32_t>(U->accum_state[0], U->accum_state[1]);
@@ -820,7 +817,7 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
 //    rank's share of a multi-GPU frame -- the tiles whose estimated latency exceeds the launch's estimated makespan are
 //    split into 2^s rows of 64 >> s pixels, each row taken by a different wave.  With many tiles per wave (one GPU, full
 //    frame) the makespan estimate is far above any tile and nothing is split.
-//    queue row = tile | part << 22 | s << 28;  queue_info[0] = number of rows.
+//    Row format: queue_row_pack (srt_kernel_common.h);  queue_info[0] = number of rows.
 __global__ __launch_bounds__(1024) void order_tiles_kernel(const uint32_t *__restrict__ cost, uint32_t *__restrict__ sorted,
                                                           uint32_t *__restrict__ rows, uint32_t n, uint32_t n_waves,
                                                           uint32_t split_load_pct, uint32_t *__restrict__ queue_info, uint32_t order_max_pct) {
@@ -926,7 +923,7 @@ __global__ __launch_bounds__(1024) void order_tiles_kernel(const uint32_t *__res
     uint32_t at = s_scan[t];
     for (uint32_t k = lo; k < hi; k++) {
         const uint32_t tile = sorted[k], s = level_of(tile);
-        for (uint32_t part = 0; part < (1u << s); part++) rows[at++] = tile | (part << 22) | (s << 28);
+        for (uint32_t part = 0; part < (1u << s); part++) rows[at++] = queue_row_pack(tile, part, s);
     }
 }
 
@@ -934,11 +931,9 @@ __global__ __launch_bounds__(1024) void order_tiles_kernel(const uint32_t *__res
 __global__ __launch_bounds__(64) void scatter_tiles_kernel(const ScatterParams P) {
     const uint32_t tile = blockIdx.x;
     const uint32_t lane = threadIdx.x;
-    if (tile >= P.n_tiles) return;
-    const uint32_t tile_x = tile % P.tiles_x, tile_y = tile / P.tiles_x;
-    const uint32_t i = tile_x * 8u + (lane & 7u), j = tile_y * 8u + (lane >> 3);
-    if (i >= P.width || j >= P.height || i / P.tx >= P.bx || j / P.ty >= P.by) return;
-    const uint32_t idx = block_linear_idx(i, j, P.tx, P.ty, P.bx);
+    const PixelIJ px = tile_slot_pixel(tile, lane, P.tiles_x);      // the pixel queue's slot -> pixel map (srt_kernel_common.h)
+    if (!queue_slot_in_chunk(tile, lane, px, P.n_tiles, kTileLanes, P.width, P.height, P.tx, P.ty, P.bx, P.by)) return;
+    const uint32_t idx = block_linear_idx(px.i, px.j, P.tx, P.ty, P.bx);
     const uint32_t rank = tile % P.world, local = tile / P.world;
     for (uint32_t g = 0; g < P.groups; g++) {
         const float *src = P.gathered + (((size_t)rank * P.groups + g) * P.tiles_padded + local) * (kGroupPlanes * kTileLanes) + lane;
@@ -1187,8 +1182,8 @@ hipError_t launch_accum_header(AccumHeader *dst, float *sums, uint32_t spp_total
 
 // Pixel queue of the next adaptive pass (MODE 4), built on the device right after the pass: no host synchronisation between passes.
 // adapt_flag_kernel: one wave per source row (the probe's cost-descending queue, or the identity order of the local tiles when the
-// accumulation runs unordered); a lane looks at the state word of its slot of the row's share, exactly as render_kernel's fetch maps
-// slots to pixels.  The row stays when a pixel of its share is still active.  The same pass counts the pixels that rendered in the pass
+// accumulation runs unordered); a lane looks at the state word of its slot of the row's share, through the decode that render_kernel's
+// fetch uses (srt_kernel_common.h).  The row stays when a pixel of its share is still active.  The same pass counts the pixels that rendered in the pass
 // just ended (their sample count is the new total: every other pixel stopped earlier) and those still active: one 64-bit
 // wave-aggregated atomic per wave, rendered in the low word, active in the high word (a rank holds fewer than 2^32 pixels, Q17).
 // adapt_scan_kernel: one workgroup keeps the flagged rows in their order (contiguous pieces per thread, then a scan, as
@@ -1200,14 +1195,12 @@ __global__ __launch_bounds__(256) void adapt_flag_kernel(const AdaptQueueParams 
     const uint32_t n_rows = P.src_info ? P.src_info[0] : P.n_identity;
     uint32_t rendered = 0, active = 0;
     for (uint32_t r = wave; r < n_rows; r += n_waves) {
-        const uint32_t row = P.src_rows ? P.src_rows[r] : r;
-        const uint32_t tile_local = P.src_rows ? (row & 0x3fffffu) : r;
-        const uint32_t part = P.src_rows ? (row >> 22) & 63u : 0u, s = P.src_rows ? (row >> 28) & 7u : 0u;
-        const uint32_t tile = P.rank + P.world * tile_local;
-        const uint32_t i = (tile % P.tiles_x) * 8u + (lane & 7u), j = (tile / P.tiles_x) * 8u + (lane >> 3);
+        const QueueRow qr = P.src_rows ? queue_row_unpack(P.src_rows[r]) : QueueRow{r, 0u, 0u};      // (srt_kernel_common.h)
+        const uint32_t tile = queue_global_tile(qr.tile_local, P.rank, P.world);
+        const PixelIJ px = tile_slot_pixel(tile, lane, P.tiles_x);
         bool rend = false, act = false;
-        if ((lane >> (6u - s)) == part && tile < P.n_tiles && lane < P.lane_limit && i < P.width && j < P.height && i / P.tx < P.bx && j / P.ty < P.by) {
-            const uint32_t st = P.state[block_linear_idx(i, j, P.tx, P.ty, P.bx)];
+        if (queue_slot_in_share(lane, qr.part, qr.s) && queue_slot_in_chunk(tile, lane, px, P.n_tiles, P.lane_limit, P.width, P.height, P.tx, P.ty, P.bx, P.by)) {
+            const uint32_t st = P.state[block_linear_idx(px.i, px.j, P.tx, P.ty, P.bx)];
             rend = (st & ~kAdaptConverged) == P.spp_total;
             act = rend && (st & kAdaptConverged) == 0u;
         }

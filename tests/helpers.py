@@ -1,3 +1,5 @@
+import os
+
 import numpy as np
 
 
@@ -104,3 +106,51 @@ def digest_of_render(res):
     d = {name: hashlib.sha256(bits(p).tobytes()).hexdigest() for name, p in zip(DIGEST_PLANES, planes)}
     d["rays"] = int(res["stats"]["rays"]); d["paths"] = int(res["stats"]["paths"])
     return d
+
+
+# ---- shared by the parity suite and the accumulation suites ------------------------------------------------------------------
+def _xorwow_host(seeds):
+    """cuRAND XORWOW (curand_init(seed, 0, 0) + curand()) on arrays of seeds: returns (state dict, next()) -- numpy restatement of srt_device.h's
+    rng_seed / rng_next (the oracle restates the same published definition in C)."""
+    u = np.uint32
+    s0 = seeds.astype(u) ^ u(0xaad26b49); s1 = np.zeros_like(s0) ^ u(0xf7dcefdd)
+    t0 = u(1099087573) * s0; t1 = u(2591861531) * s1
+    st = {"d": u(6615241) + t1 + t0, "v": [u(123456789) + t0, u(362436069) ^ t0, u(521288629) + t1, u(88675123) ^ t1, u(5783321) + t0]}
+    def nxt(mask):
+        v = st["v"]
+        t = v[0] ^ (v[0] >> u(2))
+        n4 = (v[4] ^ (v[4] << u(4))) ^ (t ^ (t << u(1)))
+        new = [v[1], v[2], v[3], v[4], n4]
+        for k in range(5): v[k] = np.where(mask, new[k], v[k])
+        st["d"] = np.where(mask, st["d"] + u(362437), st["d"])
+        return v[4] + st["d"]
+    return st, nxt
+
+
+def _blocks_bit_exact(srt, gpu, orc, sid, mode, W, H, spp, depth, block_lo, stride, max_blocks):
+    """a full-size frame of a built-in scene rendered on the GPU; its 28 x 16 blocks block_lo, block_lo + stride, .. against the oracle
+    at full spp, bit for bit in the quantised and XYZ planes.  Returns the number of blocks compared (the frame stays in the context)."""
+    scene = srt.Scene.builtin(sid, 0).build_bvh(mode, 1984)
+    cam = scene.default_camera(W, H)
+    gpu.upload_scene(scene); gpu.set_camera(cam); gpu.set_partition(0, 1)
+    gpu.init_device_params(W, H, spp, depth, 1984)
+    gpu.set_count_traversal(False)
+    gpu.render_chunk(W, H)
+    gpu.scatter_tiles()
+    fb, xyz = gpu.read_fb(), gpu.read_fb_aux(2)
+    g = gpu.geom
+    n_blocks = g["bx"] * g["by"]
+    osc = oracle_scene_for(orc, scene, mode)
+    threads = min(os.cpu_count() or 1, 16)
+    ref = osc.render(cam, W, H, spp, depth, block_lo=block_lo, block_stride=stride, threads=threads)
+    checked = 0
+    for b in range(block_lo, n_blocks, stride):
+        sl = slice(b * 448, (b + 1) * 448)
+        for c in range(3):
+            assert np.array_equal(bits(xyz[c][sl]), bits(ref["xyz"][c][sl])), ("block", b, "plane", c)
+            assert np.array_equal(fb[c][sl], ref["fb"][c][sl]), ("block", b, "plane", c)
+        checked += 1
+    assert 1 <= checked <= max_blocks
+    rm = gpu.read_fb_rowmajor(W, H)
+    assert all(np.isfinite(p).all() for p in rm)
+    return checked

@@ -7,23 +7,16 @@ into a small-frame test.  The references are those of the small-frame suites: on
 the frozen digests), the numpy float32 restatement of every stop decision, the oracle on 28 x 16 blocks, and the contraction of the
 film to the XYZ sums."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from helpers import assert_planes_equal, bits, oracle_scene_for
-from test_adaptive import (MIN_SPP, NEVER, SCHED, _adaptive, _assert_pixels_equal, _frame, _fresh, _lane_of, _pick_tolerance, _predict,
-                           gpu_lib)
-from test_gpu_parity import _blocks_bit_exact
-from test_progressive import _assert_same_image
-from test_spectral import N_GRID, _spectral
+from accum_helpers import (MIN_SPP, N_GRID, NEVER, SCHED, _adaptive, _assert_pixels_equal, _assert_same_image, _frame, _fresh, _lane_of,
+                           _pick_tolerance, _predict, _spectral, gpu_lib, run_mock_transport_child)
+from helpers import _blocks_bit_exact, assert_planes_equal, bits, oracle_scene_for
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HW, HH, HSPP, HDEPTH = 1920, 1080, 1024, 16      # the headline frame (bench.py's flagship workload)
 HEADLINE_CHECKSUM = 895685025                    # test_oracle_digests.test_headline_frame_checksum_is_frozen
 HEADLINE_PASSES = [16, 48, 960]
@@ -122,7 +115,7 @@ def _blocks_at_counts(r, orc, scene, mode, cam, W, H, depth, frame, counts, bloc
 
 
 def _check_adaptive_run(srt, r, run, never, rel, scene, cam, W, H, depth, one_shots, what):
-    """run (test_adaptive._adaptive) against the float32 restatement: samples map and active count after every pass, the paths of
+    """run (accum_helpers._adaptive) against the float32 restatement: samples map and active count after every pass, the paths of
     every pass; and every pixel against the one-shot frame of its count (one_shots: count -> frame, filled on demand)"""
     maps, _, actives = _predict(never, rel)
     before = W * H
@@ -433,13 +426,8 @@ def test_partitions_full_size(srt, gpu, headline, world):
 def test_comm_three_ranks_full_size_mock_transport(headline):
     """srt_comm_* at W = 3 on one GPU over the test transport (tests/cpp/mock_rccl.cpp; in a child process, as the small-frame
     communicator tests): an adaptive and a spectral accumulation of the 1080p headline scene equal those of one renderer"""
-    mock = os.path.join(ROOT, "tests", "cpp", "_build", "libmock_rccl.so")
-    assert os.path.exists(mock), "tests/cpp/_build/libmock_rccl.so is built by __graft_entry__.build()"
-    code = """
-import importlib, sys
+    run_mock_transport_child("""
 import numpy as np
-sys.path.insert(0, %r); sys.path.insert(0, %r)
-srt = importlib.import_module('cuda-spectral-ray-tracer_amd')
 from helpers import assert_planes_equal, bits
 scene = srt.Scene.builtin(srt.SCENE_RANDOM_SPHERES, 0).build_bvh(srt.BVH_SAH, 1984)
 W, H, depth, rel, world = %d, %d, %d, %r, 3
@@ -476,7 +464,4 @@ assert np.array_equal(bits(comm.read_spectral(W, H)), bits(ref['film']))
 assert np.array_equal(bits(comm.read_spectral(W, H, 94, 1)), bits(ref['film'][..., 94:95]))
 comm.close()
 print('full-size mock transport ok')
-""" % (ROOT, os.path.join(ROOT, "tests"), HW, HH, HDEPTH, headline["rel"])
-    env = dict(os.environ, SRT_RCCL_LIB=mock, SRT_COMM_TEST_SAME_DEVICE="1", SRT_TEST_KNOBS="1")
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and "full-size mock transport ok" in out.stdout, (out.stdout[-1500:], out.stderr[-3000:])
+""" % (HW, HH, HDEPTH, headline["rel"]), "full-size mock transport ok", timeout=600)

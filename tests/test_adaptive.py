@@ -1,93 +1,16 @@
 """Adaptive sampling (srt_accum_reset_adaptive + srt_render_chunk_accum, render_kernel MODE 4).  A pixel that stopped after n samples
 holds exactly what a plain n-spp launch gives it (the RNG stream belongs to the pixel), so the adaptive image is a patchwork of exact
 one-shot frames; every comparison here is bit for bit, and every stop decision is reproduced by a numpy float32 restatement of the
-criterion (test_adaptive_api.converged_f32)."""
+criterion (accum_helpers.converged_f32)."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from accum_helpers import (ERR_INVALID, ERR_UNSUPPORTED, EVERY_SHAPE_CASES, EVERY_SHAPE_IDS, MIN_SPP, NEVER, SCHED, _adaptive,
+                           _assert_pixels_equal, _expect_error, _frame, _fresh, _lane_of, _pick_tolerance, _predict, _soup, _sum_y,
+                           _workload, gpu_lib, run_mock_transport_child)
 from helpers import assert_planes_equal, bits, oracle_scene_for
-from test_adaptive_api import converged_f32
-from test_progressive import _soup, _workload
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ERR_INVALID, ERR_UNSUPPORTED = -1, -5
-SCHED, MIN_SPP = [8, 4, 4, 4, 4], 8
-NEVER = 1e-30          # a relative tolerance no pixel with any variance meets (tol^2 underflows to 0)
-
-
-def _lane_of(geom, W, H):
-    """block-linear lane of every row-major pixel of a W x H chunk at (0, 0) (rendering.cu:156-165)"""
-    tx, ty, bx = geom["tx"], geom["ty"], geom["bx"]
-    j, i = np.divmod(np.arange(W * H), W)
-    gbx, gby = i // tx, j // ty
-    return (j - gby * ty) * tx + (i - gbx * tx) + tx * ty * (gby * bx + gbx)
-
-
-def _fresh(gpu, scene, cam, W, H, depth, spp=12):
-    gpu.upload_scene(scene); gpu.set_camera(cam); gpu.set_partition(0, 1); gpu.set_count_traversal(False)
-    gpu.set_gather_planes(9)
-    gpu.init_device_params(W, H, spp, depth, 1984)
-
-
-def _frame(gpu, W, H):
-    gpu.scatter_tiles()
-    return dict(fb=gpu.read_fb(), lin=gpu.read_fb_aux(1), xyz=gpu.read_fb_aux(2), rowmajor=gpu.read_fb_rowmajor(W, H))
-
-
-def _adaptive(gpu, scene, cam, W, H, depth, rel_tol, sched=SCHED, min_spp=MIN_SPP, abs_tol=0.0):
-    """an adaptive run; per pass: dict(total, active, paths, stats (accum_stats), frame)"""
-    _fresh(gpu, scene, cam, W, H, depth)
-    gpu.accum_reset_adaptive(rel_tol, abs_tol, min_spp)
-    assert gpu.accum_active == 0
-    out = []
-    for s in sched:
-        gpu.render_chunk_accum(W, H, s)
-        out.append(dict(total=gpu.accum_samples, active=gpu.accum_active, paths=gpu.stats()["paths"], stats=gpu.accum_stats(W, H),
-                        frame=_frame(gpu, W, H)))
-    return out
-
-
-def _predict(never, rel_tol, abs_tol=0.0, min_spp=MIN_SPP):
-    """samples map after every pass, from a run that never stops (its S1 / S2 at every boundary are those of every run)"""
-    n_pix = never[0]["stats"]["sum_y"].size
-    stop = np.zeros(n_pix, np.int64)           # 0: still active
-    maps, actives = [], []
-    for p in never:
-        t = p["total"]
-        conv = converged_f32(p["stats"]["sum_y"], p["stats"]["sum_y2"], t, min_spp, rel_tol, abs_tol)
-        stop[(stop == 0) & conv] = t
-        maps.append(np.where(stop == 0, t, stop))
-        actives.append(int((stop == 0).sum()))
-    return maps, stop, actives
-
-
-def _pick_tolerance(never):
-    """the relative tolerance (on a fine geometric grid) under which the schedule ends with the most distinct sample counts while some
-    pixels are still active: scenes with much background (constant luminance: those pixels stop at min_spp) have few pixels to spread"""
-    best, best_n = None, 0
-    for rel in np.geomspace(1e-4, 10.0, 241):
-        maps, stop, _ = _predict(never, float(rel))
-        n = len(np.unique(maps[-1]))
-        if (stop == 0).any() and n > best_n:
-            best, best_n = float(rel), n
-    assert best is not None, "no tolerance leaves a pixel active"
-    return best
-
-
-def _assert_pixels_equal(got, want, mask, lane, what):
-    """the pixels of `mask` (row-major) are bit-identical in the quantised, sRGB and XYZ planes and in the row-major image"""
-    for k in ("fb", "lin", "xyz"):
-        for c in range(3):
-            a, b = bits(got[k][c])[lane[mask]], bits(want[k][c])[lane[mask]]
-            assert np.array_equal(a, b), "%s %s plane %d: %d of %d pixels differ" % (what, k, c, int((a != b).sum()), a.size)
-    for c in range(3):
-        a, b = bits(got["rowmajor"][c])[mask], bits(want["rowmajor"][c])[mask]
-        assert np.array_equal(a, b), "%s row-major plane %d: %d of %d pixels differ" % (what, c, int((a != b).sum()), a.size)
 
 
 @pytest.mark.gpu
@@ -160,18 +83,6 @@ def test_s2_is_the_sequential_float32_sum_of_squares(srt, gpu):
     assert np.array_equal(bits(st["sum_y2"]), bits(want2))
 
 
-def _sum_y(gpu, W, H):
-    """Y sums of a plain accumulation (sum_y needs no adaptive one)"""
-    y = np.zeros(W * H, np.float32)
-    gpu._ck(gpu_lib().srt_read_accum_stats(gpu._h, None, y.ctypes.data_as(C.POINTER(C.c_float)), None, W, H))
-    return y
-
-
-def gpu_lib():
-    import importlib
-    return importlib.import_module("cuda-spectral-ray-tracer_amd").binding.lib()
-
-
 @pytest.mark.gpu
 def test_plain_render_after_adaptive_run_continues_each_pixels_stream(srt, gpu, orc):
     """a plain launch after an adaptive run equals the oracle continued from each pixel's RNG state after its own count"""
@@ -207,14 +118,7 @@ def test_plain_render_after_adaptive_run_continues_each_pixels_stream(srt, gpu, 
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("knobs,paired,expect", [
-    (dict(), True, (1, 1, 1)),
-    (dict(wide_refs=True, lds_cache_max=3), True, (0, 0, 1)),
-    (dict(), False, (1, 1, 0)),
-    (dict(lds_cache_max=3), False, (1, 0, 0)),
-    (dict(wide_refs=True), False, (0, 1, 0)),
-    (dict(wide_refs=True, lds_cache_max=0), False, (0, 0, 0)),
-], ids=["narrow-cached-paired", "wide-partial-paired", "narrow-cached", "narrow-partial", "wide-cached", "wide-partial"])
+@pytest.mark.parametrize("knobs,paired,expect", EVERY_SHAPE_CASES, ids=EVERY_SHAPE_IDS)
 def test_every_adaptive_shape_gives_the_same_image(srt, gpu, knobs, paired, expect):
     n = 600 if paired else 601
     scene = _soup(srt, n, n).build_bvh(srt.BVH_SAH, 1984)
@@ -304,13 +208,8 @@ def test_partitions_and_offset_chunk(srt, gpu):
 
 @pytest.mark.gpu
 def test_comm_two_and_three_ranks_one_gpu_mock_transport():
-    mock = os.path.join(ROOT, "tests", "cpp", "_build", "libmock_rccl.so")
-    assert os.path.exists(mock), "tests/cpp/_build/libmock_rccl.so is built by __graft_entry__.build()"
-    code = """
-import importlib, sys
+    run_mock_transport_child("""
 import numpy as np
-sys.path.insert(0, %r); sys.path.insert(0, %r)
-srt = importlib.import_module('cuda-spectral-ray-tracer_amd')
 from helpers import assert_planes_equal
 scene = srt.Scene.builtin(srt.SCENE_RANDOM_SPHERES).build_bvh(srt.BVH_SAH, 1984)
 W, H, depth, rel = 150, 90, 16, 0.1
@@ -330,9 +229,9 @@ for world in (2, 3):
     comm.synchronize()
     assert comm.accum_active == active, (world, comm.accum_active, active)
     root = comm.root
-    assert_planes_equal(root.read_fb(), ref['fb'], 'world %%d fb' %% world)
-    assert_planes_equal(root.read_fb_aux(1), ref['lin'], 'world %%d lin' %% world)
-    assert_planes_equal(root.read_fb_aux(2), ref['xyz'], 'world %%d xyz' %% world)
+    assert_planes_equal(root.read_fb(), ref['fb'], 'world %d fb' % world)
+    assert_planes_equal(root.read_fb_aux(1), ref['lin'], 'world %d lin' % world)
+    assert_planes_equal(root.read_fb_aux(2), ref['xyz'], 'world %d xyz' % world)
     samples = sum(r.accum_stats(W, H)['samples'] for r in comm.renderers)
     assert np.array_equal(samples, ref['samples']), world
     comm.close()
@@ -346,10 +245,7 @@ except srt.SrtError as e:
     assert e.code == -5, e
 c1.close(); r.close()
 print('adaptive mock transport ok')
-""" % (ROOT, os.path.join(ROOT, "tests"))
-    env = dict(os.environ, SRT_RCCL_LIB=mock, SRT_COMM_TEST_SAME_DEVICE="1", SRT_TEST_KNOBS="1")
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "adaptive mock transport ok" in out.stdout, (out.stdout[-1500:], out.stderr[-3000:])
+""", "adaptive mock transport ok", timeout=300)
 
 
 @pytest.mark.gpu
@@ -386,12 +282,6 @@ def test_compaction_counts_and_the_pass_after_convergence(srt, gpu):
     want = _frame(gpu, W, H)
     for k in ("fb", "lin", "xyz", "rowmajor"):
         assert_planes_equal(after[k], want[k], "plain launch after the converged adaptive run " + k)
-
-
-def _expect_error(srt, fn, code, what):
-    with pytest.raises(srt.SrtError) as e:
-        fn()
-    assert e.value.code == code, (what, e.value)
 
 
 @pytest.mark.gpu

@@ -10,31 +10,10 @@ import re
 import numpy as np
 import pytest
 
-from test_progressive_api import SHAPES, _gfx950_function_names, _kernel_id
+from accum_helpers import ROOT, SHAPES, _kernel_id, converged_f32
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("srt_accum_reset_adaptive", "srt_accum_active", "srt_read_accum_stats", "srt_comm_accum_reset_adaptive", "srt_comm_accum_active")
 ADAPT_SYM = re.compile(r"^_ZN3srt13render_kernelILi4ELb([01])ELb([01])ELb([01])EEEvNS_12RenderParamsE$")
-
-
-def converged_f32(s1, s2, n, min_spp, rel_tol, abs_tol):
-    """render_kernel MODE 4's stopping test (srt_c_api.h, srt_kernels.hip adaptive_converged) in numpy float32, operation by operation:
-    mean = S1 / n; v = S2 / n - mean * mean; v = max(v, 0); var_mean = v / (n - 1); tol = rel_tol * mean + abs_tol;
-    converged = n >= min_spp && var_mean <= tol * tol, never when S1, S2, mean * mean or tol * tol is NaN or infinite.
-    s1, s2: float32 arrays (or scalars); n: the samples (int array or scalar)."""
-    f = np.float32
-    s1 = np.asarray(s1, f); s2 = np.asarray(s2, f); n_i = np.asarray(n, np.int64)
-    with np.errstate(all="ignore"):
-        nf = n_i.astype(f)
-        mean = s1 / nf
-        mm = mean * mean
-        v = s2 / nf - mm
-        v = np.where(v > f(0), v, f(0)).astype(f)
-        var_mean = v / (nf - f(1))
-        tol = f(rel_tol) * mean + f(abs_tol)
-        tt = tol * tol
-        finite = np.isfinite(s1) & np.isfinite(s2) & np.isfinite(mm) & np.isfinite(tt)
-        return (n_i >= min_spp) & finite & (var_mean <= tt)
 
 
 def test_new_symbols_are_declared_bound_and_exported(srt):
@@ -55,7 +34,7 @@ def test_new_symbols_are_declared_bound_and_exported(srt):
 
 def test_code_object_holds_every_adaptive_variant(srt):
     found = set()
-    for name in _gfx950_function_names(srt.binding.LIB_PATH):
+    for name, _ in _kernel_id().gfx950_functions(srt.binding.LIB_PATH):
         m = ADAPT_SYM.match(name)
         if m:
             found.add(tuple(int(g) for g in m.groups()))

@@ -5,7 +5,8 @@ import os
 import numpy as np
 import pytest
 
-from helpers import assert_planes_equal, bits, oracle_scene_for
+from accum_helpers import run_mock_transport_child
+from helpers import _blocks_bit_exact, _xorwow_host, assert_planes_equal, bits, oracle_scene_for
 
 pytestmark = pytest.mark.gpu
 
@@ -74,24 +75,6 @@ def test_primitive_op_sweep(gpu, orc):
     assert 0 < want_cw.sum() < n and 0 < want_ccw.sum() < n
     small = (rng.random(n).astype(np.float32) * 600.0 - 100.0).astype(np.float32)
     assert _same(gpu.op_sweep(7, small, b), np.trunc(small).astype(np.int32).astype(np.float32))
-
-
-def _xorwow_host(seeds):
-    """cuRAND XORWOW (curand_init(seed, 0, 0) + curand()) on arrays of seeds: returns (state dict, next()) -- numpy restatement of srt_device.h's
-    rng_seed / rng_next (the oracle restates the same published definition in C)."""
-    u = np.uint32
-    s0 = seeds.astype(u) ^ u(0xaad26b49); s1 = np.zeros_like(s0) ^ u(0xf7dcefdd)
-    t0 = u(1099087573) * s0; t1 = u(2591861531) * s1
-    st = {"d": u(6615241) + t1 + t0, "v": [u(123456789) + t0, u(362436069) ^ t0, u(521288629) + t1, u(88675123) ^ t1, u(5783321) + t0]}
-    def nxt(mask):
-        v = st["v"]
-        t = v[0] ^ (v[0] >> u(2))
-        n4 = (v[4] ^ (v[4] << u(4))) ^ (t ^ (t << u(1)))
-        new = [v[1], v[2], v[3], v[4], n4]
-        for k in range(5): v[k] = np.where(mask, new[k], v[k])
-        st["d"] = np.where(mask, st["d"] + u(362437), st["d"])
-        return v[4] + st["d"]
-    return st, nxt
 
 
 def test_rejection_loops_in_assembly_match_host_restatement(gpu):
@@ -503,34 +486,6 @@ def test_full_frame_full_spp_bit_exact(srt, gpu, orc):
     assert checked == n_blocks and differing == 0
 
 
-def _blocks_bit_exact(srt, gpu, orc, sid, mode, W, H, spp, depth, block_lo, stride, max_blocks):
-    import os
-    scene = srt.Scene.builtin(sid, 0).build_bvh(mode, 1984)
-    cam = scene.default_camera(W, H)
-    gpu.upload_scene(scene); gpu.set_camera(cam); gpu.set_partition(0, 1)
-    gpu.init_device_params(W, H, spp, depth, 1984)
-    gpu.set_count_traversal(False)
-    gpu.render_chunk(W, H)
-    gpu.scatter_tiles()
-    fb, xyz = gpu.read_fb(), gpu.read_fb_aux(2)
-    g = gpu.geom
-    n_blocks = g["bx"] * g["by"]
-    osc = oracle_scene_for(orc, scene, mode)
-    threads = min(os.cpu_count() or 1, 16)
-    ref = osc.render(cam, W, H, spp, depth, block_lo=block_lo, block_stride=stride, threads=threads)
-    checked = 0
-    for b in range(block_lo, n_blocks, stride):
-        sl = slice(b * 448, (b + 1) * 448)
-        for c in range(3):
-            assert np.array_equal(bits(xyz[c][sl]), bits(ref["xyz"][c][sl])), ("block", b, "plane", c)
-            assert np.array_equal(fb[c][sl], ref["fb"][c][sl]), ("block", b, "plane", c)
-        checked += 1
-    assert 1 <= checked <= max_blocks
-    rm = gpu.read_fb_rowmajor(W, H)
-    assert all(np.isfinite(p).all() for p in rm)
-    return checked
-
-
 def test_full_size_prism_blocks_bit_exact(srt, gpu, orc):
     """BASELINE cfg 4 at FULL size: the reference's PRISM scene (Sellmeier flint with quirk Q1, hero wavelengths, reference
     BVH builder), 1920x1080, 2048 spp, depth 16; four of the 28x16 blocks through the middle of the image against the
@@ -657,17 +612,12 @@ def test_comm_two_and_three_ranks_one_gpu_mock_transport():
     HIP copies (tests/cpp/mock_rccl.cpp, loaded through SRT_RCCL_LIB; the hook is honoured only for a transport that exports the
     mock's marker symbol).  Everything but RCCL itself.  The library caches its RCCL
     handle per process, so this runs in a child process."""
-    import subprocess
-    import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     mock = os.path.join(root, "tests", "cpp", "_build", "libmock_rccl.so")
     if not os.path.exists(mock):
         pytest.skip("tests/cpp/_build/libmock_rccl.so not built (__graft_entry__.build())")
-    code = """
-import importlib, sys
+    run_mock_transport_child("""
 import numpy as np
-sys.path.insert(0, %r); sys.path.insert(0, %r)
-srt = importlib.import_module('cuda-spectral-ray-tracer_amd')
 from helpers import assert_planes_equal
 scene = srt.Scene.builtin(srt.SCENE_RANDOM_SPHERES).build_bvh(srt.BVH_SAH, 1984)
 W, H, spp, depth = 150, 90, 12, 16
@@ -682,10 +632,10 @@ for world in (2, 3):
         comm.init_device_params(W, H, spp, depth, 1984)
         comm.render_frame(W, H); comm.synchronize()
         root = comm.root
-        assert_planes_equal(root.read_fb(), ref['fb'], 'world %%d planes %%d fb' %% (world, planes))
+        assert_planes_equal(root.read_fb(), ref['fb'], 'world %d planes %d fb' % (world, planes))
         if planes == 9:
-            assert_planes_equal(root.read_fb_aux(2), ref['xyz'], 'world %%d xyz' %% world)
-            assert_planes_equal(root.read_fb_aux(1), ref['lin'], 'world %%d lin' %% world)
+            assert_planes_equal(root.read_fb_aux(2), ref['xyz'], 'world %d xyz' % world)
+            assert_planes_equal(root.read_fb_aux(1), ref['lin'], 'world %d lin' % world)
         else:
             # the parity planes did not travel: asking for them is an error, not stale data (ADVICE r3)
             try:
@@ -698,10 +648,7 @@ for world in (2, 3):
         assert comm.last_gather_ms() > 0.0
     comm.close()
 print('mock transport ok')
-""" % (root, os.path.join(root, "tests"))
-    env = dict(os.environ, SRT_RCCL_LIB=mock, SRT_COMM_TEST_SAME_DEVICE="1", SRT_TEST_KNOBS="1")
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "mock transport ok" in out.stdout, (out.stdout[-1500:], out.stderr[-3000:])
+""", "mock transport ok", timeout=300)
 
 
 def test_comm_process_per_gpu_ranks_agree_or_fail_together_mock_transport():

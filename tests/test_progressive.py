@@ -4,73 +4,15 @@ The one-shot frames are themselves held to the CPU oracle and to the frozen dige
 against an exact reference."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from helpers import (DIGEST_PLANES, assert_planes_equal, custom_scene, digest_of_render, digest_workloads,
-                     oracle_scene_for)
+from accum_helpers import (ERR_INVALID, ERR_UNSUPPORTED, EVERY_SHAPE_CASES, EVERY_SHAPE_IDS, ROOT, _assert_same_image, _expect_error,
+                           _progressive, _soup, _split, _workload, run_mock_transport_child)
+from helpers import DIGEST_PLANES, assert_planes_equal, digest_of_render, digest_workloads, oracle_scene_for
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SPLITS = [[12], [5, 7], [1, 1, 10], [4, 4, 4]]
-ERR_INVALID, ERR_UNSUPPORTED = -1, -5
-
-
-def _dielectric_scene(srt):
-    """glass triangles in front of a lambertian floor and a light: refraction, total internal reflection and the valid-wavelength
-    cut of dispersive paths"""
-    tris = [((-4, -1, -4), (4, -1, -4), (4, -1, 4), 0, 0), ((-4, -1, -4), (4, -1, 4), (-4, -1, 4), 0, 0),
-            ((-1.5, -0.8, 0.5), (1.5, -0.8, 0.5), (0.0, 1.8, 0.0), 1, 0), ((-1.2, -0.8, -0.6), (1.4, -0.8, -0.4), (0.1, 1.5, 0.9), 1, 0),
-            ((-2, 3, -2), (2, 3, -2), (0, 3, 2), 2, 0), ((2.5, -1, -1), (3.5, -1, 0), (3.0, 1.0, -0.5), 3, 0)]
-    mats = [(0, (0.73, 0.73, 0.73), 0.0, 0.0), (2, (1.0, 1.0, 1.0), 0.0, 0.0), (4, (1.0, 1.0, 1.0), 0.0, 3.0), (1, (0.8, 0.8, 0.8), 0.1, 0.0)]
-    return custom_scene(srt, tris, mats, (0.5, 0.5, 0.5)).build_bvh(srt.BVH_SAH, 1984)      # (grey: no rgb2spec table)
-
-
-def _soup(srt, seed, n):
-    """n small random triangles (lambertian, metallic, dielectric, emissive): an even n gives a PAIRED SAH tree"""
-    rng = np.random.default_rng(7000 + seed)
-    c = rng.uniform(-6, 6, (n, 3))
-    v = [(c + rng.normal(0, 0.3, (n, 3))).astype(np.float32).astype(np.float64) for _ in range(3)]
-    mat = rng.integers(0, 4, n)
-    tris = [(tuple(v[0][k]), tuple(v[1][k]), tuple(v[2][k]), int(mat[k]), 0) for k in range(n)]
-    mats = [(0, (0.6, 0.6, 0.6), 0.0, 0.0), (1, (1.0, 1.0, 1.0), 0.2, 0.0), (2, (1.0, 1.0, 1.0), 0.0, 0.0), (4, (1.0, 1.0, 1.0), 0.0, 2.0)]
-    return custom_scene(srt, tris, mats, (0.5, 0.5, 0.5))
-
-
-def _workload(srt, name):
-    if name == "prism":
-        sc = srt.Scene.builtin(srt.SCENE_PRISM).build_bvh(srt.BVH_REFERENCE, 1984)
-        return sc, sc.default_camera(48, 40), 48, 40, 8, 0
-    if name == "cornell":
-        sc = srt.Scene.builtin(srt.SCENE_CORNELL).build_bvh(srt.BVH_REFERENCE, 1984)
-        return sc, sc.default_camera(64, 48), 64, 48, 8, 0
-    if name == "random_spheres":
-        sc = srt.Scene.builtin(srt.SCENE_RANDOM_SPHERES).build_bvh(srt.BVH_SAH, 1984)
-        return sc, sc.default_camera(80, 45), 80, 45, 16, 1       # defocus lens, sky background
-    sc = _dielectric_scene(srt)
-    return sc, srt.camera_init(56, 40, 45.0, (0.5, 0.8, 7.0), (0.0, 0.3, 0.0)), 56, 40, 12, 1
-
-
-def _split(spp):
-    """spp in two or three passes (one pass when spp == 1)"""
-    k = min(3, spp)
-    base, rem = divmod(spp, k)
-    return [base + (1 if i < rem else 0) for i in range(k)]
-
-
-def _assert_same_image(got, want, what, rowmajor=True):
-    assert_planes_equal(got["fb"], want["fb"], what + " fb")
-    assert_planes_equal(got["lin"], want["lin"], what + " unquantised sRGB")
-    assert_planes_equal(got["xyz"], want["xyz"], what + " XYZ sums")
-    if rowmajor:
-        assert_planes_equal(got["rowmajor"], want["rowmajor"], what + " row-major")
-
-
-def _progressive(srt, gpu, scene, cam, W, H, passes, depth):
-    """runs render_progressive to the end; returns the list of (spp_total, result)"""
-    return list(srt.render_progressive(scene, cam, W, H, passes, depth, renderer=gpu))
 
 
 @pytest.mark.gpu
@@ -130,14 +72,7 @@ def _forced_variant_case(srt, gpu, scene, cam, W, H, depth, knobs, expect):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("knobs,paired,expect", [
-    (dict(), True, (1, 1, 1)),                                   # PAIRED, LDS resident, 16-bit references (the headline's shape)
-    (dict(wide_refs=True, lds_cache_max=3), True, (0, 0, 1)),    # PAIRED, 32-bit references, inner tree partly from L2 (cfg 5's shape)
-    (dict(), False, (1, 1, 0)),
-    (dict(lds_cache_max=3), False, (1, 0, 0)),
-    (dict(wide_refs=True), False, (0, 1, 0)),
-    (dict(wide_refs=True, lds_cache_max=0), False, (0, 0, 0)),
-], ids=["narrow-cached-paired", "wide-partial-paired", "narrow-cached", "narrow-partial", "wide-cached", "wide-partial"])
+@pytest.mark.parametrize("knobs,paired,expect", EVERY_SHAPE_CASES, ids=EVERY_SHAPE_IDS)
 def test_every_accumulating_shape_is_exact(srt, gpu, knobs, paired, expect):
     n = 600 if paired else 601          # the SAH builder pairs an even triangle count
     scene = _soup(srt, n, n).build_bvh(srt.BVH_SAH, 1984)
@@ -199,12 +134,7 @@ def test_partition_and_offset_chunk(srt, gpu):
 def test_comm_two_and_three_ranks_one_gpu_mock_transport():
     """srt_comm_accum_reset / srt_render_frame_multi_accum at W = 2 and 3 on ONE GPU over the test transport (tests/cpp/mock_rccl.cpp,
     as the parity suite's communicator test does; the library caches its RCCL handle per process, so this runs in a child process)"""
-    mock = os.path.join(ROOT, "tests", "cpp", "_build", "libmock_rccl.so")
-    assert os.path.exists(mock), "tests/cpp/_build/libmock_rccl.so is built by __graft_entry__.build()"
-    code = """
-import importlib, sys
-sys.path.insert(0, %r); sys.path.insert(0, %r)
-srt = importlib.import_module('cuda-spectral-ray-tracer_amd')
+    run_mock_transport_child("""
 from helpers import assert_planes_equal
 scene = srt.Scene.builtin(srt.SCENE_RANDOM_SPHERES).build_bvh(srt.BVH_SAH, 1984)
 W, H, depth = 150, 90, 16
@@ -222,18 +152,15 @@ for world in (2, 3):
         comm.synchronize()
         root = comm.root
         assert all(r.accum_samples == 12 for r in comm.renderers)
-        assert_planes_equal(root.read_fb(), ref['fb'], 'world %%d planes %%d fb' %% (world, planes))
+        assert_planes_equal(root.read_fb(), ref['fb'], 'world %d planes %d fb' % (world, planes))
         if planes == 9:
-            assert_planes_equal(root.read_fb_aux(1), ref['lin'], 'world %%d lin' %% world)
-            assert_planes_equal(root.read_fb_aux(2), ref['xyz'], 'world %%d xyz' %% world)
+            assert_planes_equal(root.read_fb_aux(1), ref['lin'], 'world %d lin' % world)
+            assert_planes_equal(root.read_fb_aux(2), ref['xyz'], 'world %d xyz' % world)
         st = comm.stats()
         assert st['paths'] == W * H * 7, st
     comm.close()
 print('progressive mock transport ok')
-""" % (ROOT, os.path.join(ROOT, "tests"))
-    env = dict(os.environ, SRT_RCCL_LIB=mock, SRT_COMM_TEST_SAME_DEVICE="1", SRT_TEST_KNOBS="1")
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "progressive mock transport ok" in out.stdout, (out.stdout[-1500:], out.stderr[-3000:])
+""", "progressive mock transport ok", timeout=300)
 
 
 @pytest.mark.gpu
@@ -262,12 +189,6 @@ def test_plain_render_after_accumulation_continues_rng_streams(srt, gpu, orc):
     ref = osc.render(cam, W, H, spp_next, depth, states=states)
     assert_planes_equal(after["xyz"], ref["xyz"], "plain launch after the accumulation, XYZ")
     assert_planes_equal(after["fb"], ref["fb"], "plain launch after the accumulation, fb")
-
-
-def _expect_error(srt, fn, code, what):
-    with pytest.raises(srt.SrtError) as e:
-        fn()
-    assert e.value.code == code, (what, e.value)
 
 
 @pytest.mark.gpu

@@ -2,45 +2,16 @@
 object holds the accumulating render kernel (render_kernel<3, ...>) for every shape the launcher picks, and render_progressive
 checks its schedule before any device is touched."""
 import ctypes as C
-import importlib.util
 import os
 import re
-import struct
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from accum_helpers import ROOT, SHAPES, _kernel_id
+
 NEW_SYMBOLS = ("srt_accum_reset", "srt_render_chunk_accum", "srt_accum_samples", "srt_comm_accum_reset", "srt_render_frame_multi_accum")
-# render_kernel<3, NARROW, ALL_CACHED, PAIRED> (tools/kernel_id.py matches the production MODE 0 only)
+# render_kernel<3, NARROW, ALL_CACHED, PAIRED>
 ACCUM_SYM = re.compile(r"^_ZN3srt13render_kernelILi3ELb([01])ELb([01])ELb([01])EEEvNS_12RenderParamsE$")
-# the six shapes launch_render_mode can pick: (narrow, all_cached, paired)
-SHAPES = {(1, 1, 1), (0, 0, 1), (1, 1, 0), (1, 0, 0), (0, 1, 0), (0, 0, 0)}
-
-
-def _kernel_id():
-    spec = importlib.util.spec_from_file_location("kernel_id", os.path.join(ROOT, "tools", "kernel_id.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def _gfx950_function_names(lib_path):
-    """names of the functions in the gfx950 code objects of the library's offload bundles"""
-    K = _kernel_id()
-    data = open(lib_path, "rb").read()
-    names = set()
-    pos = data.find(K.BUNDLE_MAGIC)
-    while pos >= 0:
-        n, = struct.unpack_from("<Q", data, pos + len(K.BUNDLE_MAGIC))
-        o = pos + len(K.BUNDLE_MAGIC) + 8
-        for _ in range(min(n, 16)):
-            off, size, tlen = struct.unpack_from("<QQQ", data, o)
-            triple = data[o + 24:o + 24 + tlen]
-            o += 24 + tlen
-            if b"gfx950" in triple and size:
-                names.update(K._elf_function_bytes(data[pos + off:pos + off + size]))
-        pos = data.find(K.BUNDLE_MAGIC, pos + 1)
-    return names
 
 
 def test_new_symbols_are_declared_bound_and_exported(srt):
@@ -60,7 +31,7 @@ def test_new_symbols_are_declared_bound_and_exported(srt):
 
 def test_code_object_holds_every_accumulating_variant(srt):
     found = set()
-    for name in _gfx950_function_names(srt.binding.LIB_PATH):
+    for name, _ in _kernel_id().gfx950_functions(srt.binding.LIB_PATH):
         m = ACCUM_SYM.match(name)
         if m:
             found.add(tuple(int(g) for g in m.groups()))

@@ -4,30 +4,13 @@ gives the accumulation's XYZ sums (up to reassociation), on a miss-only frame it
 additive: the colour planes, XYZ sums and RNG state of a spectral accumulation are those of a plain one, and the film itself is the same
 bits for every split of the samples, every launch shape and every partition."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from helpers import assert_planes_equal, bits, custom_scene, fuzz_case
-from test_adaptive import _fresh, _frame, _lane_of, _expect_error, gpu_lib
-from test_gpu_parity import _xorwow_host
-from test_progressive import _soup, _workload
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ERR_INVALID, ERR_UNSUPPORTED = -1, -5
-N_GRID = 95
-
-
-def _spectral(gpu, scene, cam, W, H, depth, passes, spp=12):
-    """a spectral accumulation of `passes`; returns (frame after the last pass, film (H, W, 95))"""
-    _fresh(gpu, scene, cam, W, H, depth, spp=spp)
-    gpu.accum_reset_spectral()
-    for s in passes:
-        gpu.render_chunk_accum(W, H, s)
-    return _frame(gpu, W, H), gpu.read_spectral(W, H)
+from accum_helpers import (ERR_INVALID, ERR_UNSUPPORTED, EVERY_SHAPE_CASES, EVERY_SHAPE_IDS, N_GRID, _expect_error, _frame, _fresh,
+                           _lane_of, _soup, _spectral, _workload, gpu_lib, run_mock_transport_child)
+from helpers import _xorwow_host, assert_planes_equal, bits, custom_scene, fuzz_case
 
 
 def _fuzz_with_lens(srt):
@@ -149,14 +132,7 @@ def test_film_is_additive_and_split_invariant(srt, gpu, name):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("knobs,paired,expect", [
-    (dict(), True, (1, 1, 1)),
-    (dict(wide_refs=True, lds_cache_max=3), True, (0, 0, 1)),
-    (dict(), False, (1, 1, 0)),
-    (dict(lds_cache_max=3), False, (1, 0, 0)),
-    (dict(wide_refs=True), False, (0, 1, 0)),
-    (dict(wide_refs=True, lds_cache_max=0), False, (0, 0, 0)),
-], ids=["narrow-cached-paired", "wide-partial-paired", "narrow-cached", "narrow-partial", "wide-cached", "wide-partial"])
+@pytest.mark.parametrize("knobs,paired,expect", EVERY_SHAPE_CASES, ids=EVERY_SHAPE_IDS)
 def test_every_spectral_shape_gives_the_same_film(srt, gpu, knobs, paired, expect):
     n = 600 if paired else 601
     scene = _soup(srt, n, n).build_bvh(srt.BVH_SAH, 1984)
@@ -238,13 +214,8 @@ def test_partitions_offset_chunk_and_sub_range(srt, gpu):
 
 @pytest.mark.gpu
 def test_comm_two_and_three_ranks_one_gpu_mock_transport():
-    mock = os.path.join(ROOT, "tests", "cpp", "_build", "libmock_rccl.so")
-    assert os.path.exists(mock), "tests/cpp/_build/libmock_rccl.so is built by __graft_entry__.build()"
-    code = """
-import importlib, sys
+    run_mock_transport_child("""
 import numpy as np
-sys.path.insert(0, %r); sys.path.insert(0, %r)
-srt = importlib.import_module('cuda-spectral-ray-tracer_amd')
 from helpers import assert_planes_equal, bits
 scene = srt.Scene.builtin(srt.SCENE_RANDOM_SPHERES).build_bvh(srt.BVH_SAH, 1984)
 W, H, depth = 150, 90, 16
@@ -262,8 +233,8 @@ for world in (2, 3):
         comm.render_frame_accum(W, H, s)
     comm.synchronize()
     root = comm.root
-    assert_planes_equal(root.read_fb(), ref['fb'], 'world %%d fb' %% world)
-    assert_planes_equal(root.read_fb_aux(2), ref['xyz'], 'world %%d xyz' %% world)
+    assert_planes_equal(root.read_fb(), ref['fb'], 'world %d fb' % world)
+    assert_planes_equal(root.read_fb_aux(2), ref['xyz'], 'world %d xyz' % world)
     film = comm.read_spectral(W, H)
     assert np.array_equal(bits(film), bits(ref['film'])), world
     part = comm.read_spectral(W, H, 30, 5)
@@ -280,10 +251,7 @@ c1.synchronize()
 assert np.array_equal(bits(c1.read_spectral(W, H)), bits(ref['film']))
 c1.close(); r.close()
 print('spectral mock transport ok')
-""" % (ROOT, os.path.join(ROOT, "tests"))
-    env = dict(os.environ, SRT_RCCL_LIB=mock, SRT_COMM_TEST_SAME_DEVICE="1", SRT_TEST_KNOBS="1")
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "spectral mock transport ok" in out.stdout, (out.stdout[-1500:], out.stderr[-3000:])
+""", "spectral mock transport ok", timeout=300)
 
 
 @pytest.mark.gpu

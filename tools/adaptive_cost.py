@@ -10,31 +10,16 @@
    frame whose spp is chosen to take the adaptive run's wall time (measured, printed next to it).
 
 Usage: python tools/adaptive_cost.py [--reps 3] [--out FILE]"""
-import argparse
-import importlib
 import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-srt = importlib.import_module("cuda-spectral-ray-tracer_amd")
+from _cost_common import DEPTH, H, W, best_of, headline_renderer, parse_args, srt, timed, write_report
 
-W, H, DEPTH = 1920, 1080, 16
 STEP, MAX_SPP, MIN_SPP = 64, 1024, 64
 TOLERANCES = (0.05, 0.02)
 NEVER = 1e-30
-
-
-def timed(r, fn):
-    r.synchronize()
-    t0 = time.perf_counter()
-    fn()
-    r.synchronize()
-    return (time.perf_counter() - t0) * 1e3
 
 
 def pass_pair(r, adaptive):
@@ -83,16 +68,8 @@ def rmse(a, b):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--out", default=None, help="also write the report to this file")
-    args = ap.parse_args()
-    r = srt.Renderer(0)
-    scene = srt.Scene.builtin(srt.SCENE_RANDOM_SPHERES, 0).build_bvh(srt.BVH_SAH, 1984)
-    note = srt.tune_tree_for_throughput(r, scene, W, H, DEPTH)
-    r.upload_scene(scene)
-    r.set_camera(scene.default_camera(W, H))
-    r.set_partition(0, 1)
+    args = parse_args()
+    r, note = headline_renderer()
     r.set_gather_planes(9)
     lines = ["adaptive_cost: random spheres %dx%d, depth %d; tree: %s" % (W, H, DEPTH, note), "plan: %r" % (r.launch_plan(),)]
     report = {"workload": "random spheres %dx%d depth %d" % (W, H, DEPTH), "reps": args.reps}
@@ -120,7 +97,7 @@ def main():
     r.render_chunk(W, H)
     ref = lin_image(r)
     r.init_device_params(W, H, 1024, DEPTH, 1984)
-    plain_1024_ms = min(timed(r, lambda: r.render_chunk(W, H)) for _ in range(2))
+    plain_1024_ms = best_of(2, lambda: timed(r, lambda: r.render_chunk(W, H)))
     plain_1024 = lin_image(r)
     lines.append("plain 1024 spp: %.2f ms, RMSE vs 4096 spp %.6f" % (plain_1024_ms, rmse(plain_1024, ref)))
     report["plain_1024"] = dict(ms=round(plain_1024_ms, 2), rmse=rmse(plain_1024, ref))
@@ -154,17 +131,12 @@ def main():
     r.accum_reset_adaptive(1e3, 1e3, MIN_SPP)
     r.render_chunk_accum(W, H, MIN_SPP)
     assert r.accum_active == 0
-    empty = min(timed(r, lambda: r.render_chunk_accum(W, H, 1)) for _ in range(args.reps))
+    empty = best_of(args.reps, lambda: timed(r, lambda: r.render_chunk_accum(W, H, 1)))
     lines.append("pass with no active pixel: %.3f ms (kernel %.3f ms)" % (empty, r.last_kernel_ms()))
     report["empty_pass_ms"] = round(empty, 3)
 
     lines.append(json.dumps(report))
-    text = "\n".join(lines)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    write_report(lines, args.out)
     r.close()
 
 

@@ -12,8 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 srt = importlib.import_module("cuda-spectral-ray-tracer_amd")
 import oracle_binding as orc
-from helpers import oracle_scene_for, bits
-import test_gpu_parity as T
+from helpers import custom_scene, oracle_scene_for, bits
 
 first = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 count = int(sys.argv[2]) if len(sys.argv) > 2 else 200
@@ -47,7 +46,7 @@ for seed in range(first, first + count):
         tris.append((tuple(float(x) for x in v0), tuple(float(x) for x in v1), tuple(float(x) for x in v2), int(rng.integers(0, n_mats)), int(rng.choice([0, 0, 1, 2, 3]))))
     bg = float(rng.choice([0.5, 1.0, 0.5, 0.0]))
     mode = int(rng.integers(0, 2))
-    scene = T._custom_scene(srt, tris, mats, (bg, bg, bg)).build_bvh(mode, 1984)
+    scene = custom_scene(srt, tris, mats, (bg, bg, bg)).build_bvh(mode, 1984)
     W, H, spp, depth = int(rng.integers(9, 90)), int(rng.integers(9, 60)), int(rng.integers(1, 12)), int(rng.integers(1, 17))
     cam = srt.camera_init(W, H, float(rng.uniform(20, 90)), tuple(rng.uniform(-12, 12, 3)), tuple(rng.uniform(-2, 2, 3)),
                           defocus_angle=float(rng.choice([0.0, 0.0, 1.5])), focus_dist=float(rng.uniform(5, 15)))

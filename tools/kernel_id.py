@@ -26,16 +26,20 @@ OBJ = os.path.join(ROOT, "cuda-spectral-ray-tracer_amd", "csrc", "_build", "srt_
 LIB = os.path.join(ROOT, "cuda-spectral-ray-tracer_amd", "libsrt_hip.so")
 
 
-# render_kernel<0, NARROW, ALL_CACHED[, PAIRED]>: the production builds (PAIRED is round 5's fourth template argument; listings / libraries of
-# earlier rounds have three)
-RENDER = re.compile(r"^_ZN3srt13render_kernelILi0ELb([01])ELb([01])E(?:Lb([01])E)?\w*:")
-RENDER_SYM = re.compile(r"^_ZN3srt13render_kernelILi0ELb([01])ELb([01])E(?:Lb([01])E)?EEv\w*$")
+# render_kernel<MODE, NARROW, ALL_CACHED[, PAIRED]> of all six modes, as a symbol of the code object and (followed by ':') as a label
+# of the listing (PAIRED is round 5's fourth template argument; listings / libraries of earlier rounds have three)
+RENDER = re.compile(r"_ZN3srt13render_kernelILi([0-5])ELb([01])ELb([01])E(?:Lb([01])E)?EEv\w*")
 
 
-def _key(m):
-    """(narrow, all_cached) for the general variant, (narrow, all_cached, 1) for the PAIRED one"""
-    k = (int(m.group(1)), int(m.group(2)))
-    return k + (1,) if m.group(3) == "1" else k
+def _render_key(name):
+    """(mode, narrow, all_cached, paired) of a render kernel's mangled name, None for any other name"""
+    m = RENDER.fullmatch(name)
+    return m and tuple(int(g or 0) for g in m.groups())
+
+
+def _production(hs):
+    """the MODE 0 entries under the keys bench.py knows: (narrow, all_cached) for the general variant, (narrow, all_cached, 1) for the PAIRED one"""
+    return {k[1:] if k[3] else k[1:3]: v for k, v in hs.items() if k[0] == 0}
 BUNDLE_MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
 
@@ -85,14 +89,13 @@ def position_independent(code):
     return struct.pack("<%dI" % n, *w) + code[4 * n:]
 
 
-def code_hashes(lib=LIB):
-    """{(narrow, all_cached): sha256 of the kernel's position-independent machine code} for the production render kernels of a built
-    library; {} when the file is missing or holds no gfx950 code object with them"""
-    out = {}
+def gfx950_functions(lib):
+    """(symbol name, bytes) of every function in the gfx950 code objects of a built library: its .hip_fatbin section holds clang offload
+    bundles, each bundle a list of (offset, size, target triple) entries.  Nothing when the file is missing."""
     try:
         data = open(lib, "rb").read()
     except OSError:
-        return out
+        return
     pos = data.find(BUNDLE_MAGIC)
     while pos >= 0:
         n, = struct.unpack_from("<Q", data, pos + len(BUNDLE_MAGIC))
@@ -102,12 +105,42 @@ def code_hashes(lib=LIB):
             triple = data[o + 24:o + 24 + tlen]
             o += 24 + tlen
             if b"gfx950" in triple and size:
-                for name, code in _elf_function_bytes(data[pos + off:pos + off + size]).items():
-                    m = RENDER_SYM.match(name)
-                    if m:
-                        out[_key(m)] = hashlib.sha256(position_independent(code)).hexdigest()
+                yield from _elf_function_bytes(data[pos + off:pos + off + size]).items()
         pos = data.find(BUNDLE_MAGIC, pos + 1)
+
+
+def render_code_hashes(lib=LIB):
+    """{(mode, narrow, all_cached, paired): sha256 of the kernel's position-independent machine code} for every render kernel of a
+    built library; {} when the file is missing or holds no gfx950 code object with them"""
+    return {_render_key(name): hashlib.sha256(position_independent(code)).hexdigest()
+            for name, code in gfx950_functions(lib) if _render_key(name)}
+
+
+def render_listing_hashes(path=ISA):
+    """{(mode, narrow, all_cached, paired): sha256} over the body (label .. s_endpgm, comments and file / ident / loc directives
+    removed) of every render kernel in an ISA listing.  Empty when the listing is missing."""
+    out, h, key = {}, None, None
+    if not os.path.exists(path):
+        return out
+    for line in open(path, errors="replace"):
+        if h is None:
+            label, colon, _ = line.partition(":")
+            key = colon and _render_key(label)
+            if not key:
+                continue
+            h = hashlib.sha256()
+        body = re.sub(r";.*$", "", line).rstrip()
+        if body and not re.match(r"\s*\.(file|ident|loc)\b", body):
+            h.update(body.encode() + b"\n")
+        if re.match(r"\s*s_endpgm", body):
+            out[key] = h.hexdigest()
+            h = None
     return out
+
+
+def code_hashes(lib=LIB):
+    """{(narrow, all_cached[, 1 = PAIRED]): machine-code hash} of the production (MODE 0) render kernels of a built library"""
+    return _production(render_code_hashes(lib))
 
 
 def variant_name(narrow, all_cached, paired=0):
@@ -124,26 +157,10 @@ def code_hash(lib=LIB, narrow=1, all_cached=1, paired=0):
 
 
 def isa_hashes():
-    """{(narrow, all_cached): sha256} over the body (label .. s_endpgm) of every production render kernel in the listing: helper
-    kernels of the same translation unit (op sweep, scatter, ...) and the OTHER variants may change without invalidating a counter
-    pass of one variant.  Empty when the listing is missing."""
-    out = {}
-    if not os.path.exists(ISA):
-        return out
-    h, key = None, None
-    for line in open(ISA, errors="replace"):
-        if h is None:
-            m = RENDER.match(line)
-            if not m:
-                continue
-            h, key = hashlib.sha256(), _key(m)
-        body = re.sub(r";.*$", "", line).rstrip()
-        if body and not re.match(r"\s*\.(file|ident|loc)\b", body):
-            h.update(body.encode() + b"\n")
-        if re.match(r"\s*s_endpgm", body):
-            out[key] = h.hexdigest()
-            h = None
-    return out
+    """{(narrow, all_cached[, 1 = PAIRED]): listing hash} of the production render kernels in the build's listing: helper kernels of
+    the same translation unit (op sweep, scatter, ...) and the OTHER variants may change without invalidating a counter pass of one
+    variant."""
+    return _production(render_listing_hashes(ISA))
 
 
 def isa_hash(narrow=1, all_cached=1, paired=0):

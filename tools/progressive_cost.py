@@ -7,18 +7,12 @@ probe and header writes included), ms per pass, and the render kernels' own ms (
 accumulation is exact, so a differing checksum is an error, not noise.  Prints one line per schedule and a JSON line.
 
 Usage: python tools/progressive_cost.py [--reps 3] [--out FILE]"""
-import argparse
-import importlib
 import json
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-srt = importlib.import_module("cuda-spectral-ray-tracer_amd")
+from _cost_common import DEPTH, H, W, best_of, checksum, headline_renderer, parse_args, write_report
 
-W, H, DEPTH, SPP = 1920, 1080, 16, 1024
+SPP = 1024
 SCHEDULES = [("plain", 1, 1024), ("accum", 1, 1024), ("accum", 4, 256), ("accum", 16, 64), ("accum", 64, 16)]
 
 
@@ -40,32 +34,15 @@ def frame(r, kind, n_pass, spp):
     return (time.perf_counter() - t0) * 1e3, kms
 
 
-def checksum(r):
-    r.scatter_tiles()
-    return int(sum(int(p.astype("int64").sum()) for p in r.read_fb()))
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--out", default=None, help="also write the report to this file")
-    args = ap.parse_args()
-    r = srt.Renderer(0)
-    scene = srt.Scene.builtin(srt.SCENE_RANDOM_SPHERES, 0).build_bvh(srt.BVH_SAH, 1984)
-    note = srt.tune_tree_for_throughput(r, scene, W, H, DEPTH)
-    r.upload_scene(scene)
-    r.set_camera(scene.default_camera(W, H))
-    r.set_partition(0, 1)
+    args = parse_args()
+    r, note = headline_renderer()
     lines = ["progressive_cost: random spheres %dx%d, depth %d, %d spp; tree: %s" % (W, H, DEPTH, SPP, note),
              "plan: %r" % (r.launch_plan(),)]
     frame(r, "plain", 1, SPP)          # warm-up (code objects, clocks)
     rows, ref_sum = [], None
     for kind, n_pass, spp in SCHEDULES:
-        best = None
-        for _ in range(args.reps):
-            wall, kms = frame(r, kind, n_pass, spp)
-            if best is None or wall < best[0]:
-                best = (wall, kms)
+        best = best_of(args.reps, lambda: frame(r, kind, n_pass, spp))
         cs = checksum(r)
         ref_sum = cs if ref_sum is None else ref_sum
         row = dict(schedule="%s %dx%d" % (kind, n_pass, spp), frame_ms=round(best[0], 2), ms_per_pass=round(best[0] / n_pass, 3),
@@ -79,12 +56,7 @@ def main():
         lines.append("%-16s frame %9.2f ms (%+6.2f %% vs plain)  per pass %8.3f ms  kernel %9.2f ms (%8.3f per pass)  checksum %d" %
                      (row["schedule"], row["frame_ms"], row["frame_vs_plain_pct"], row["ms_per_pass"], row["kernel_ms"], row["kernel_ms_per_pass"], row["fb_checksum"]))
     lines.append(json.dumps({"workload": "random spheres %dx%d depth %d %d spp" % (W, H, DEPTH, SPP), "reps": args.reps, "rows": rows}))
-    text = "\n".join(lines)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    write_report(lines, args.out)
     r.close()
 
 

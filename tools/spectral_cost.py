@@ -7,20 +7,14 @@ is purely additive).  Then the time and bytes of a full-frame srt_read_spectral 
 host), the best of --reps reads.  Prints one line per row and a JSON line.
 
 Usage: python tools/spectral_cost.py [--reps 3] [--out FILE]"""
-import argparse
-import importlib
+import ctypes as C
 import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-srt = importlib.import_module("cuda-spectral-ray-tracer_amd")
+from _cost_common import DEPTH, H, W, best_of, checksum, headline_renderer, parse_args, srt, write_report
 
-W, H, DEPTH = 1920, 1080, 16
 SCHEDULES = [("accum", 1, 1024), ("spectral", 1, 1024), ("accum", 1, 64), ("spectral", 1, 64)]
 
 
@@ -41,31 +35,14 @@ def frame(r, kind, n_pass, spp):
     return (time.perf_counter() - t0) * 1e3, kms
 
 
-def checksum(r):
-    r.scatter_tiles()
-    return int(sum(int(p.astype("int64").sum()) for p in r.read_fb()))
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--out", default=None, help="also write the report to this file")
-    args = ap.parse_args()
-    r = srt.Renderer(0)
-    scene = srt.Scene.builtin(srt.SCENE_RANDOM_SPHERES, 0).build_bvh(srt.BVH_SAH, 1984)
-    note = srt.tune_tree_for_throughput(r, scene, W, H, DEPTH)
-    r.upload_scene(scene)
-    r.set_camera(scene.default_camera(W, H))
-    r.set_partition(0, 1)
+    args = parse_args()
+    r, note = headline_renderer()
     lines = ["spectral_cost: random spheres %dx%d, depth %d; tree: %s" % (W, H, DEPTH, note), "plan: %r" % (r.launch_plan(),)]
     frame(r, "spectral", 1, 16)          # warm-up (code objects, clocks, the film's first allocation)
     rows, sums = [], {}
     for kind, n_pass, spp in SCHEDULES:
-        best = None
-        for _ in range(args.reps):
-            wall, kms = frame(r, kind, n_pass, spp)
-            if best is None or wall < best[0]:
-                best = (wall, kms)
+        best = best_of(args.reps, lambda: frame(r, kind, n_pass, spp))
         cs = checksum(r)
         key = n_pass * spp
         sums.setdefault(key, cs)
@@ -80,27 +57,20 @@ def main():
                      (row["schedule"], row["frame_ms"], row["frame_vs_mode3_pct"], row["kernel_ms"], row["kernel_vs_mode3_pct"], row["fb_checksum"]))
     # the last frame is a spectral one: read its whole film
     out = np.zeros((H, W, 95), np.float32)
-    best = None
-    for _ in range(args.reps):
+    def read():
         t0 = time.perf_counter()
         r.read_spectral(W, H, into=out)
-        t = (time.perf_counter() - t0) * 1e3
-        best = t if best is None else min(best, t)
+        return (time.perf_counter() - t0) * 1e3
+    best = best_of(args.reps, read)
     nbytes = out.nbytes
     y = np.zeros(W * H, np.float32)
-    import ctypes as C
     r._ck(srt.binding.lib().srt_read_accum_stats(r._h, None, y.ctypes.data_as(C.POINTER(C.c_float)), None, W, H))
     rel = abs(float(srt.film_to_xyz(out)[..., 1].sum()) / float(y.astype(np.float64).sum()) - 1.0)
     read = dict(ms=round(best, 2), bytes=nbytes, gb_per_s=round(nbytes / (best * 1e-3) / 1e9, 2), y_sum_rel_diff=rel)
     lines.append("srt_read_spectral full frame, 95 samples: %.2f ms for %d bytes (%.2f GB/s to host memory); film Y vs XYZ sums: %.1e relative"
                  % (read["ms"], nbytes, read["gb_per_s"], rel))
     lines.append(json.dumps({"workload": "random spheres %dx%d depth %d" % (W, H, DEPTH), "reps": args.reps, "rows": rows, "read_spectral": read}))
-    text = "\n".join(lines)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    write_report(lines, args.out)
     r.close()
 
 
