@@ -53,7 +53,14 @@ class Adaptive(C.Structure):
     _fields_ = [("rel_tol", C.c_float), ("abs_tol", C.c_float), ("min_spp", C.c_uint32), ("reserved", C.c_uint32)]
 
 
-assert C.sizeof(Adaptive) == 16
+class TreeTuning(C.Structure):
+    """srt_tree_tuning: what srt_tune_tree_for_throughput found and did (srt_c_api.h)"""
+    _fields_ = [("pixels_per_lane", C.c_double), ("throughput_bound", C.c_uint32), ("reinsertion", C.c_uint32),
+                ("probe_width", C.c_uint32), ("probe_height", C.c_uint32), ("probe_spp", C.c_uint32), ("nodes_swapped", C.c_uint32),
+                ("order_status", C.c_int32)]
+
+
+assert C.sizeof(Adaptive) == 16 and C.sizeof(TreeTuning) == 40
 assert C.sizeof(Material) == 428 and C.sizeof(CameraData) == 84 and C.sizeof(TriIn) == 44
 
 # every symbol include/srt_c_api.h declares: name -> (restype, argtypes)
@@ -121,6 +128,8 @@ PROTOTYPES = {
     "srt_read_fb_aux": (_i, [_vp, _i, _fp, _fp, _fp]),
     "srt_get_tile_costs": (_i, [_vp, C.POINTER(C.c_uint32), _sz]),
     "srt_order_children_by_profile": (_i, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "srt_pixels_per_lane": (_i, [_vp, _u32, _u32, _u32, C.POINTER(C.c_double)]),
+    "srt_tune_tree_for_throughput": (_i, [_vp, _vp, _u32, _u32, _u32, _u32, _i, C.POINTER(TreeTuning)]),
     "srt_get_stats": (_i, [_vp, C.POINTER(Stats)]),
     "srt_set_count_traversal": (_i, [_vp, _i]),
     "srt_get_wave_debug": (_i, [_vp, C.POINTER(C.c_uint32), _sz]),

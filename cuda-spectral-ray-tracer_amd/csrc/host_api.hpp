@@ -134,46 +134,24 @@ public:
     int getYres() const { return yr; }
     size_t getWorldSize() const { return srt_scene_tri_count(s); }
     size_t getNumMaterials() const { return srt_scene_material_count(s); }
-    // Tree tuning for a THROUGHPUT-bound render of the whole image on n_gpus devices (no reference counterpart: the tree is an
-    // input of bvh::hit, bvh/bvh.cu:98-166): when a rank's launch has at least 6 pixels per persistent lane, the
-    // SAH tree is post-optimised by reinsertion (up to 8 192 triangles) and its child order is measured on one instrumented
-    // probe frame of the scene's camera at a quarter of the size, 8 samples per pixel (srt_order_children_by_profile, which undoes itself when
-    // the probe frame did not get cheaper).  Launches with fewer pixels per lane are bound by their longest pixel and keep the
-    // tree as built.  Call before the renderer is created (it uploads the scene).  Returns what was done, for the log.
+    // Tree tuning for a THROUGHPUT-bound render of the whole image on n_gpus devices: srt_tune_tree_for_throughput (srt_c_api.h holds the
+    // recipe) on a probe context of its own, for launches with at least 6 pixels per lane.  Call before the renderer is created.
+    // Returns what was done, for the log.
     std::string tune_tree_for_throughput(uint bounce_limit, int device = 0, int n_gpus = 1) {
         if (!world_inited) return "no scene";
         srt_ctx *probe = nullptr;
         if (srt_create(device, &probe) != SRT_OK) return std::string("no tuning: ") + srt_last_error(nullptr);
         std::string what = "tree as built";
-        int waves = 0;
-        if (srt_upload_scene(probe, s) == SRT_OK && srt_launch_plan(probe, &waves, nullptr, nullptr, nullptr) == SRT_OK) {
-            const double lanes = (double)srt_ctx_cu_count(probe) * waves * 64.0;
-            const double per_lane = (double)xr * yr / (double)(n_gpus < 1 ? 1 : n_gpus) / (lanes > 0 ? lanes : 1.0);
-            if (per_lane >= 6.0) {
-                what = "";
-                if (srt_scene_tri_count(s) <= 8192) {
-                    int resident = 0, still = 0;
-                    srt_launch_plan(probe, nullptr, nullptr, &resident, nullptr);
-                    if (srt_scene_optimise_bvh(s, 3) == SRT_OK && srt_upload_scene(probe, s) == SRT_OK &&
-                        srt_launch_plan(probe, nullptr, nullptr, &still, nullptr) == SRT_OK) {
-                        if (resident && !still) {      // (a deeper tree needs deeper LDS stacks: it no longer fits LDS -- not worth it)
-                            srt_scene_build_bvh(s, SRT_BVH_SAH, SRT_DEFAULT_SEED);
-                            what = "reinsertion undone (the deeper tree would no longer be LDS resident); ";
-                        } else what = "3 reinsertion passes; ";
-                    }
-                }
-                // ONE probe recipe for every front end (bench.py / the Python binding's profile_child_order use the same): the scene's
-                // camera at a quarter of the frame's size (at least 32 x 32), 8 samples per pixel, nodes with at least 16 deciding rays --
-                // so srt_render --sah and bench.py traverse the same tree for the same workload
-                const int pw = std::max(xr / 4, 32), ph = std::max(yr / 4, 32);
-                srt_camera_data probe_cam{};
-                uint32_t swapped = 0;
-                if (srt_scene_default_camera(s, pw, ph, &probe_cam) == SRT_OK && srt_set_camera(probe, &probe_cam) == SRT_OK &&
-                    srt_order_children_by_profile(probe, s, (uint32_t)pw, (uint32_t)ph, 8, bounce_limit, 16, &swapped) == SRT_OK)
-                    what += (swapped ? "child order profiled (" + std::to_string(pw) + "x" + std::to_string(ph) + " x 8 spp probe): " + std::to_string(swapped) + " nodes swapped"
-                                     : std::string("builder's child order kept"));
-                else what += std::string("child order not profiled: ") + srt_last_error(probe);
-            } else what = "tree as built (chain-bound launch: fewer than 6 pixels per lane)";
+        srt_tree_tuning t{};
+        if (srt_tune_tree_for_throughput(probe, s, (uint32_t)xr, (uint32_t)yr, (uint32_t)(n_gpus < 1 ? 1 : n_gpus), bounce_limit, 1, &t) == SRT_OK) {
+            if (!t.throughput_bound) what = "tree as built (chain-bound launch: fewer than 6 pixels per lane)";
+            else {
+                what = t.reinsertion == 1 ? "3 reinsertion passes; " : t.reinsertion == 2 ? "reinsertion undone (the deeper tree would no longer be LDS resident); " : "";
+                if (t.order_status != SRT_OK) what += std::string("child order not profiled: ") + srt_last_error(probe);
+                else what += (t.nodes_swapped ? "child order profiled (" + std::to_string(t.probe_width) + "x" + std::to_string(t.probe_height) + " x " + std::to_string(t.probe_spp) +
+                                                    " spp probe): " + std::to_string(t.nodes_swapped) + " nodes swapped"
+                                              : std::string("builder's child order kept"));
+            }
         }
         srt_destroy(probe);
         return what;

@@ -2,6 +2,7 @@
 // (replaces `renderer`, rendering/rendering.cuh:39-155, and the device half of render_manager::step).
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
+#include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -385,10 +386,11 @@ int choose_queue(srt_ctx *c, Pass &ps, RenderParams &p) {
 // The instrumented launch's debug buffer.
 int bind_wave_debug(srt_ctx *c, const Pass &ps, RenderParams &p) {
     if (!c->count_traversal) return SRT_OK;
-    const uint32_t n_waves = (uint32_t)c->n_cu * (uint32_t)ps.plan.waves_per_cu;
     // layout of the debug buffer: [OrderProfile header][4 words per wave]: the header sits at a FIXED place, so the kernel finds it
-    // whatever number of waves the launcher ends up starting
-    HIP_TRY(c, c->d_wave_debug.reserve(wave_debug_bytes(n_waves)));
+    // whatever number of waves the launcher ends up starting.  Sized from the launcher's own grid arithmetic WITHOUT the clamp to the
+    // queue's rows (every CU filled, rounded up to whole workgroups): no queue of this plan can start more waves
+    const uint32_t most_waves = render_launch_grid(ps.plan, (uint32_t)c->n_cu, p.waves_per_cu_override, UINT32_MAX).waves;
+    HIP_TRY(c, c->d_wave_debug.reserve(wave_debug_bytes(most_waves)));
     HIP_TRY(c, hipMemsetAsync(c->d_wave_debug.ptr, 0, c->d_wave_debug.bytes, ps.st));
     p.wave_debug = c->d_wave_debug.as<uint32_t>();
     if (c->order_profile.magic == kOrderProfileMagic)
@@ -397,12 +399,12 @@ int bind_wave_debug(srt_ctx *c, const Pass &ps, RenderParams &p) {
 }
 
 int launch_pass(srt_ctx *c, const Pass &ps, RenderParams &p) {
-    HIP_TRY(c, hipEventRecord(c->ev0, ps.st));     // ev0..ev1 bracket the render kernel alone (roofline.achieved)
-    uint32_t waves_launched = 0;
-    if (ps.spp_add) set_accum_header(p, AccumLayout(c).header);
-    HIP_TRY(c, launch_render(p, c->knobs, (uint32_t)c->n_cu, ps.mode, ps.st, &waves_launched));
-    if (c->count_traversal && waves_launched > wave_debug_waves(c))
+    // (nothing is enqueued for a launch whose waves the debug buffer cannot hold: the kernel writes 4 words per wave it starts)
+    if (c->count_traversal && render_launch_grid(ps.plan, (uint32_t)c->n_cu, p.waves_per_cu_override, p.queue_rows_bound).waves > wave_debug_waves(c))
         return fail(c, SRT_ERR_HIP, "srt_render_chunk: the launch started more waves than the debug buffer holds (launch plan and launcher disagree)");
+    HIP_TRY(c, hipEventRecord(c->ev0, ps.st));     // ev0..ev1 bracket the render kernel alone (roofline.achieved)
+    if (ps.spp_add) set_accum_header(p, AccumLayout(c).header);
+    HIP_TRY(c, launch_render(p, c->knobs, (uint32_t)c->n_cu, ps.mode, ps.st));
     HIP_TRY(c, hipEventRecord(c->ev1, ps.st));
     return SRT_OK;
 }
@@ -1009,7 +1011,7 @@ int srt_order_children_by_profile(srt_ctx *c, srt_scene *s, uint32_t width, uint
             c->order_profile.sibbox = d_sib.as<float>(); c->order_profile.cnt = d_cnt.as<uint32_t>(); c->order_profile.n_nodes = n_nodes;
         }
         c->count_traversal = true; c->rank = 0; c->world = 1;
-        int r = srt_init_device_params(c, tx, ty, bx, by, width, height, spp, bounce_limit, 1984);
+        int r = srt_init_device_params(c, tx, ty, bx, by, width, height, spp, bounce_limit, SRT_DEFAULT_SEED);
         if (r == SRT_OK) r = srt_render_chunk(c, width, height, 0, 0, nullptr);
         if (r == SRT_OK) r = srt_synchronize(c);
         c->count_traversal = counting; c->rank = rank; c->world = world;
@@ -1051,6 +1053,49 @@ int srt_order_children_by_profile(srt_ctx *c, srt_scene *s, uint32_t width, uint
     }
     if (rc == SRT_OK && n_swapped) *n_swapped = (uint32_t)swapped_nodes.size();
     return rc;
+}
+
+int srt_pixels_per_lane(const srt_ctx *c, uint32_t width, uint32_t height, uint32_t world, double *out) {
+    if (!c || !c->scene_ready || !out) return fail(nullptr, SRT_ERR_INVALID, "srt_pixels_per_lane: no scene uploaded / null argument");
+    const double lanes = (double)c->n_cu * plan_of(c).waves_per_cu * 64.0;
+    *out = (double)width * height / (double)std::max<uint32_t>(world, 1u) / (lanes > 0 ? lanes : 1.0);
+    return SRT_OK;
+}
+
+// The throughput tree-tuning recipe (include/srt_c_api.h): every constant of it, once.
+static constexpr double kTunePixelsPerLane = 6.0;        // fewer: the launch is bound by its longest pixel chain and keeps the tree as built
+static constexpr size_t kTuneReinsertionMaxTris = 8192;  // larger trees: measured no gain from reinsertion
+static constexpr int kTuneReinsertionPasses = 3;         // (they converge)
+static constexpr uint32_t kTuneProbeDivisor = 4, kTuneProbeMinSide = 32, kTuneProbeSpp = 8;      // probe frame: a quarter of the frame's size, 8 spp
+static constexpr uint32_t kTuneDecidingRays = 16;        // a node's children are re-ordered from at least this many deciding rays
+
+int srt_tune_tree_for_throughput(srt_ctx *c, srt_scene *s, uint32_t width, uint32_t height, uint32_t world, uint32_t bounce_limit,
+                                 int only_if_throughput_bound, srt_tree_tuning *out) {
+    if (out) memset(out, 0, sizeof(*out));
+    if (!c || !s || !out || !s->bvh_valid || width == 0 || height == 0)
+        return fail(c, SRT_ERR_INVALID, "srt_tune_tree_for_throughput: null argument / BVH not built / empty frame");
+    int rc = srt_upload_scene(c, s);
+    if (rc == SRT_OK) rc = srt_pixels_per_lane(c, width, height, world, &out->pixels_per_lane);
+    if (rc != SRT_OK) return rc;
+    out->throughput_bound = out->pixels_per_lane >= kTunePixelsPerLane ? 1u : 0u;
+    if (only_if_throughput_bound && !out->throughput_bound) return SRT_OK;
+    if (s->raw.size() <= kTuneReinsertionMaxTris) {
+        // (reinsertion may deepen the tree: deeper LDS stacks, fewer cached records -- a tree that just fitted LDS no longer does, which
+        // costs far more than the passes return.  The plan is a host function of the flattened tree: nothing is uploaded to decide)
+        auto resident = [&](const FlatScene &f) { LaunchPlan lp; render_launch_plan(f.stack_depth, f.n_records, f.n_inner, c->knobs, lp); return lp.all_cached; };
+        const bool kept = optimise_bvh_unless(*s, kTuneReinsertionPasses, [&](const FlatScene &before, const FlatScene &after) { return !(resident(before) && !resident(after)); });
+        out->reinsertion = kept ? 1u : 2u;
+    }
+    const uint32_t pw = std::max(width / kTuneProbeDivisor, kTuneProbeMinSide), ph = std::max(height / kTuneProbeDivisor, kTuneProbeMinSide);
+    srt_camera_data probe_cam{};
+    rc = srt_scene_default_camera(s, (int)pw, (int)ph, &probe_cam);
+    if (rc == SRT_OK) rc = srt_set_camera(c, &probe_cam);
+    if (rc == SRT_OK) {
+        out->probe_width = pw; out->probe_height = ph; out->probe_spp = kTuneProbeSpp;
+        rc = srt_order_children_by_profile(c, s, pw, ph, kTuneProbeSpp, bounce_limit, kTuneDecidingRays, &out->nodes_swapped);
+    } else fail(c, rc, global_error());      // (the scene's message, where the front ends look for it)
+    out->order_status = rc;
+    return SRT_OK;
 }
 
 int srt_set_count_traversal(srt_ctx *c, int on) {

@@ -362,6 +362,22 @@ static void optimise_built_tree(srt_scene &s, int passes) {
         if (nd.prim < 0 && dist2(s.nodes[nd.right].box) < dist2(s.nodes[nd.left].box)) std::swap(nd.left, nd.right);
 }
 
+bool optimise_bvh_unless(srt_scene &s, int passes, const std::function<bool(const FlatScene &before, const FlatScene &after)> &keep) {
+    const std::vector<BvhNode> nodes = s.nodes;
+    const int32_t root = s.root;
+    const int depth = s.depth;
+    const bool has_order_eye = s.has_order_eye;
+    float order_eye[3];
+    memcpy(order_eye, s.order_eye, sizeof(order_eye));
+    FlatScene before, after;
+    const bool flat_before = flatten_scene(s, before) == SRT_OK;
+    if (flat_before && passes > 0) optimise_built_tree(s, passes);
+    if (flat_before && flatten_scene(s, after) == SRT_OK && keep(before, after)) return true;
+    s.nodes = nodes; s.root = root; s.depth = depth; s.has_order_eye = has_order_eye;
+    memcpy(s.order_eye, order_eye, sizeof(order_eye));
+    return false;
+}
+
 // This build's own builder for the large synthetic scenes: binned SAH over all three axes (the reference
 // builder never splits on z and sorts by box minimum).  Same node semantics, better tree.
 int build_bvh_sah(srt_scene &s) {

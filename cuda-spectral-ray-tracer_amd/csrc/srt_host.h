@@ -2,6 +2,7 @@
 // scene/scene.cuh:103-176).  No HIP in here: everything below runs before upload.
 #pragma once
 #include <stdint.h>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -91,6 +92,10 @@ struct FlatScene {
     int n_records = 0;
 };
 int flatten_scene(const srt_scene &s, FlatScene &out);
+// srt_scene_optimise_bvh with a veto: runs its `passes` rounds, flattens the tree as it was and as it has become, and keeps the new
+// tree only if `keep` says so (or if a tree cannot be flattened: then the old one stays) -- otherwise nodes, root, depth and ordering
+// viewpoint are put back exactly as they were.  Returns whether the optimised tree was kept.  Host only: no upload, no device.
+bool optimise_bvh_unless(srt_scene &s, int passes, const std::function<bool(const FlatScene &before, const FlatScene &after)> &keep);
 void cmf_rows(float *rows96x4);   // { x_bar, y_bar, z_bar, D65n } per 5 nm sample
 
 }  // namespace srt

@@ -132,8 +132,7 @@ struct PlanKnobs { bool wide_refs = false; int lds_cache_max = -1; };
 // The render launch's variant; the values are render_kernel's MODE template argument.  Plain: render; Counting: instrumented; Probe: cost
 // probe; Accum: accumulating render (p.wave_debug -> AccumHeader); Adaptive / Spectral: adaptive / spectral accumulating render.
 enum RenderMode { Plain = 0, Counting = 1, Probe = 2, Accum = 3, Adaptive = 4, Spectral = 5 };
-// waves_launched (optional) = persistent waves of the launch
-hipError_t launch_render(const RenderParams &p, const PlanKnobs &knobs, uint32_t n_cu, RenderMode mode, hipStream_t st, uint32_t *waves_launched = nullptr);
+hipError_t launch_render(const RenderParams &p, const PlanKnobs &knobs, uint32_t n_cu, RenderMode mode, hipStream_t st);
 hipError_t launch_accum_header(AccumHeader *dst, float *sums, uint32_t spp_total, hipStream_t st);      // writes *dst on the stream
 // Pixel queue of the next adaptive pass (see adapt_flag_kernel): the rows of `src_rows` (src_info[0] of them; nullptr: the identity
 // queue of n_identity local tiles) whose share of the tile still holds an active pixel, in their order, into dst_rows / dst_info[0..1];
@@ -168,5 +167,10 @@ size_t render_lds_bytes(int stack_depth, int waves_per_block, int n_cached, int 
 void render_launch_shape(int stack_depth, int n_records, int n_inner, const PlanKnobs &k, int &waves_per_block, int &n_cached);
 struct LaunchPlan { int waves_per_block, blocks_per_cu, waves_per_cu, waves_per_eu, n_cached; bool all_cached; };
 void render_launch_plan(int stack_depth, int n_records, int n_inner, const PlanKnobs &k, LaunchPlan &lp);   // what launch_render will do for this scene
+// The grid launch_render starts for a plan: workgroups of waves_per_block waves, `waves` = n_blocks * waves_per_block persistent waves in
+// all -- every CU filled, never more waves than queue rows (queue_rows_bound: RenderParams'), rounded up to whole workgroups.
+// waves_per_cu_override: RenderParams' experiment knob.  The launcher and whoever sizes a per-wave buffer both ask this function.
+struct RenderGrid { int waves_per_block; uint32_t n_blocks, waves; };
+RenderGrid render_launch_grid(const LaunchPlan &lp, uint32_t n_cu, uint32_t waves_per_cu_override, uint32_t queue_rows_bound);
 
 }  // namespace srt

@@ -85,6 +85,22 @@ void render_launch_plan(int stack_depth, int n_records, int n_inner, const PlanK
     lp.blocks_per_cu = 16 / lp.waves_per_block;
     lp.waves_per_cu = lp.waves_per_block * lp.blocks_per_cu;
 }
+RenderGrid render_launch_grid(const LaunchPlan &lp, uint32_t n_cu, uint32_t waves_per_cu_override, uint32_t queue_rows_bound) {
+    RenderGrid g;
+    g.waves_per_block = lp.waves_per_block;
+    uint32_t waves_per_cu = (uint32_t)lp.waves_per_cu;
+    if (waves_per_cu_override > 0 && waves_per_cu_override < 16 && g.waves_per_block == 16) {
+        // experiment knob: fewer waves per CU (one smaller workgroup per CU, same LDS cache), e.g. 8 = two waves per SIMD
+        g.waves_per_block = (int)waves_per_cu_override;
+        waves_per_cu = waves_per_cu_override;
+    }
+    // persistent waves: fill every CU (waves_per_cu at this build's register budget), never more waves than queue rows
+    uint32_t n_waves = n_cu * waves_per_cu;
+    if (n_waves > queue_rows_bound) n_waves = queue_rows_bound;     // (upper bound known to the host)
+    g.n_blocks = (n_waves + (uint32_t)g.waves_per_block - 1) / (uint32_t)g.waves_per_block;
+    g.waves = g.n_blocks * (uint32_t)g.waves_per_block;
+    return g;
+}
 
 #ifndef SRT_PAIRED_VARIANT
 #define SRT_PAIRED_VARIANT 1      /* 0: kernel experiments -- paired trees run the general variant too */
@@ -1078,34 +1094,23 @@ hipError_t launch_init_rng(uint32_t *rng, uint32_t n_lanes, uint64_t seed, hipSt
 }
 
 template <int MODE, bool NARROW, bool ALL_CACHED, bool PAIRED = false>
-static hipError_t launch_render_cached(const RenderParams &p_in, const LaunchPlan &lp, const PlanKnobs &knobs, uint32_t n_cu, hipStream_t st, uint32_t *waves_launched) {
+static hipError_t launch_render_cached(const RenderParams &p_in, const LaunchPlan &lp, const PlanKnobs &knobs, uint32_t n_cu, hipStream_t st) {
     RenderParams p = p_in;
-    int wpb = lp.waves_per_block;
-    uint32_t waves_per_cu = (uint32_t)lp.waves_per_cu;
-    if (p.waves_per_cu_override > 0 && p.waves_per_cu_override < 16 && wpb == 16) {
-        // experiment knob: fewer waves per CU (one smaller workgroup per CU, same LDS cache), e.g. 8 = two waves per SIMD
-        wpb = (int)p.waves_per_cu_override;
-        waves_per_cu = p.waves_per_cu_override;
-    }
+    const RenderGrid grid = render_launch_grid(lp, n_cu, p.waves_per_cu_override, p.queue_rows_bound);
     p.n_cached = lp.n_cached;
-    const size_t lds = render_lds_bytes(p.stack_depth, wpb, lp.n_cached, p.n_records, knobs);
+    const size_t lds = render_lds_bytes(p.stack_depth, grid.waves_per_block, lp.n_cached, p.n_records, knobs);
     // per launch, not once per process: the attribute belongs to the function ON THE CURRENT DEVICE, and one process may
     // drive several GPUs (srt_comm_init_all); the call is a host-side table update
     {
         const hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void *>(&render_kernel<MODE, NARROW, ALL_CACHED, PAIRED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget);
         if (ae != hipSuccess) return ae;
     }
-    // persistent waves: fill every CU (waves_per_cu at this build's register budget), never more waves than queue rows
-    uint32_t n_waves = n_cu * waves_per_cu;
-    if (n_waves > p.queue_rows_bound) n_waves = p.queue_rows_bound;     // (upper bound known to the host)
-    const uint32_t n_blocks = (n_waves + (uint32_t)wpb - 1) / (uint32_t)wpb;
-    if (waves_launched) *waves_launched = n_blocks * (uint32_t)wpb;
-    hipLaunchKernelGGL((render_kernel<MODE, NARROW, ALL_CACHED, PAIRED>), dim3(n_blocks), dim3(64 * wpb), lds, st, p);
+    hipLaunchKernelGGL((render_kernel<MODE, NARROW, ALL_CACHED, PAIRED>), dim3(grid.n_blocks), dim3(64 * grid.waves_per_block), lds, st, p);
     return hipGetLastError();
 }
 
 template <int MODE, bool NARROW>
-static hipError_t launch_render_mode(const RenderParams &p, const PlanKnobs &knobs, uint32_t n_cu, hipStream_t st, uint32_t *waves_launched) {
+static hipError_t launch_render_mode(const RenderParams &p, const PlanKnobs &knobs, uint32_t n_cu, hipStream_t st) {
     LaunchPlan lp;
     render_launch_plan(p.stack_depth, p.n_records, p.n_inner, knobs, lp);
     // (the ALL_CACHED variant reads packed 96-byte FRINGE records by a literal stride: never pick it for a scene that was uploaded
@@ -1113,23 +1118,22 @@ static hipError_t launch_render_mode(const RenderParams &p, const PlanKnobs &kno
     if (lp.all_cached && p.fringe_stride != 96u) lp.all_cached = false;
     // a paired tree (no node with one leaf child) that is LDS resident with 16-bit references runs the variant without the FRINGE box test
     if (render_paired_variant(p.paired != 0u, NARROW, lp.all_cached))
-        return NARROW ? launch_render_cached<MODE, true, true, true>(p, lp, knobs, n_cu, st, waves_launched)
-                      : launch_render_cached<MODE, false, false, true>(p, lp, knobs, n_cu, st, waves_launched);
-    return lp.all_cached ? launch_render_cached<MODE, NARROW, true>(p, lp, knobs, n_cu, st, waves_launched) : launch_render_cached<MODE, NARROW, false>(p, lp, knobs, n_cu, st, waves_launched);
+        return NARROW ? launch_render_cached<MODE, true, true, true>(p, lp, knobs, n_cu, st)
+                      : launch_render_cached<MODE, false, false, true>(p, lp, knobs, n_cu, st);
+    return lp.all_cached ? launch_render_cached<MODE, NARROW, true>(p, lp, knobs, n_cu, st) : launch_render_cached<MODE, NARROW, false>(p, lp, knobs, n_cu, st);
 }
 
-hipError_t launch_render(const RenderParams &p, const PlanKnobs &knobs, uint32_t n_cu, RenderMode mode, hipStream_t st, uint32_t *waves_launched) {
-    if (waves_launched) *waves_launched = 0;
+hipError_t launch_render(const RenderParams &p, const PlanKnobs &knobs, uint32_t n_cu, RenderMode mode, hipStream_t st) {
     if (p.tiles_local == 0) return hipSuccess;
     const bool narrow = render_narrow_refs(p.n_records, knobs);
-    if (mode == 1) return narrow ? launch_render_mode<1, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<1, false>(p, knobs, n_cu, st, waves_launched);
-    if (mode == 2) return narrow ? launch_render_mode<2, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<2, false>(p, knobs, n_cu, st, waves_launched);
-    if (mode < 3 || mode > 5) return narrow ? launch_render_mode<0, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<0, false>(p, knobs, n_cu, st, waves_launched);
+    if (mode == 1) return narrow ? launch_render_mode<1, true>(p, knobs, n_cu, st) : launch_render_mode<1, false>(p, knobs, n_cu, st);
+    if (mode == 2) return narrow ? launch_render_mode<2, true>(p, knobs, n_cu, st) : launch_render_mode<2, false>(p, knobs, n_cu, st);
+    if (mode < 3 || mode > 5) return narrow ? launch_render_mode<0, true>(p, knobs, n_cu, st) : launch_render_mode<0, false>(p, knobs, n_cu, st);
     // (instantiated after the production variants: their place in the object, and so the labels of their ISA listing, stay as they were)
-    if (mode == 3) return narrow ? launch_render_mode<3, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<3, false>(p, knobs, n_cu, st, waves_launched);
+    if (mode == 3) return narrow ? launch_render_mode<3, true>(p, knobs, n_cu, st) : launch_render_mode<3, false>(p, knobs, n_cu, st);
     // (and the adaptive ones after the accumulating ones, the spectral ones after those, for the same reason)
-    if (mode == 4) return narrow ? launch_render_mode<4, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<4, false>(p, knobs, n_cu, st, waves_launched);
-    return narrow ? launch_render_mode<5, true>(p, knobs, n_cu, st, waves_launched) : launch_render_mode<5, false>(p, knobs, n_cu, st, waves_launched);
+    if (mode == 4) return narrow ? launch_render_mode<4, true>(p, knobs, n_cu, st) : launch_render_mode<4, false>(p, knobs, n_cu, st);
+    return narrow ? launch_render_mode<5, true>(p, knobs, n_cu, st) : launch_render_mode<5, false>(p, knobs, n_cu, st);
 }
 
 hipError_t launch_order_tiles(const uint32_t *cost, uint32_t *sorted, uint32_t *rows, uint32_t n, uint32_t n_waves,

@@ -380,41 +380,48 @@ class Comm:
 def pixels_per_lane(renderer, width, height, world=1):
     """pixels of a width x height frame per persistent lane of one rank's launch (CUs x waves per CU x 64 lanes; scene uploaded):
     below about 6 a launch is bound by its longest pixel chain, above by total work"""
-    lanes = B.lib().srt_ctx_cu_count(renderer._h) * renderer.launch_plan()["waves_per_cu"] * 64
-    return width * height / float(max(world, 1)) / max(lanes, 1)
+    out = C.c_double()
+    renderer._ck(B.lib().srt_pixels_per_lane(renderer._h, width, height, max(world, 1), C.byref(out)))
+    return out.value
 
 
-def tune_tree_for_throughput(renderer, scene, width, height, bounce_limit):
-    """Tree preparation for a THROUGHPUT-bound launch of a width x height frame on this build's own SAH tree: insertion-based topology
-    optimisation (trees of up to 8 192 triangles: measured no gain above) and the child order from a probe frame.  Not for launches
-    with few pixels per lane (see pixels_per_lane): less total work is not a cheaper longest pixel -- measured 5-10 % slower there.
+def tree_tuning(renderer, scene, width, height, bounce_limit, world=1, gate=False):
+    """srt_tune_tree_for_throughput (srt_c_api.h holds the recipe) as a dict of srt_tree_tuning's fields; gate: leave the tree of a
+    launch with fewer than 6 pixels per lane untouched.  The scene is left uploaded; init_device_params comes next."""
+    t = B.TreeTuning()
+    renderer._ck(B.lib().srt_tune_tree_for_throughput(renderer._h, scene.handle, width, height, max(world, 1), bounce_limit, 1 if gate else 0, C.byref(t)))
+    return {name: getattr(t, name) for name, _ in B.TreeTuning._fields_}
+
+
+def tune_tree_for_throughput(renderer, scene, width, height, bounce_limit, world=1, gate=False):
+    """Tree preparation for a THROUGHPUT-bound launch of a width x height frame on this build's own SAH tree (tree_tuning): insertion-based
+    topology optimisation and the child order from a probe frame.  Not for launches with few pixels per lane (see pixels_per_lane): less
+    total work is not a cheaper longest pixel -- measured 5-10 % slower there; gate=True leaves their tree as built.
     Returns a description for the record.  Deterministic: every rank arrives at the same tree."""
-    notes = []
-    if scene.n_tris <= 8192:
-        renderer.upload_scene(scene)
-        resident = renderer.launch_plan()["all_cached"]
-        scene.optimise_bvh(3)
-        renderer.upload_scene(scene)
-        if resident and not renderer.launch_plan()["all_cached"]:
-            # (reinsertion may deepen the tree: deeper LDS stacks, fewer cached records -- a tree that just fitted LDS no longer does,
-            # which costs far more than the passes return)
-            scene.build_bvh(B.BVH_SAH, 1984)
-            notes.append("reinsertion undone (the deeper tree would no longer be LDS resident)")
-        else:
-            notes.append("3 reinsertion passes")
-    n, (pw, ph, ps) = profile_child_order(renderer, scene, width, height, bounce_limit)
-    notes.append(("child order profiled on a %dx%d x %d spp probe frame: %d nodes swapped" % (pw, ph, ps, n)) if n else
-                 ("builder's child order kept (the %dx%d x %d spp probe frame was not cheaper with the profiled one)" % (pw, ph, ps)))
+    t = tree_tuning(renderer, scene, width, height, bounce_limit, world, gate)
+    if gate and not t["throughput_bound"]:
+        return "tree as built (chain-bound launch: fewer than 6 pixels per lane)"
+    renderer._ck(t["order_status"])
+    notes = {1: ["3 reinsertion passes"], 2: ["reinsertion undone (the deeper tree would no longer be LDS resident)"]}.get(t["reinsertion"], [])
+    probe = (t["probe_width"], t["probe_height"], t["probe_spp"])
+    notes.append(("child order profiled on a %dx%d x %d spp probe frame: %d nodes swapped" % (probe + (t["nodes_swapped"],))) if t["nodes_swapped"] else
+                 ("builder's child order kept (the %dx%d x %d spp probe frame was not cheaper with the profiled one)" % probe))
     return "; ".join(notes)
 
 
+# the recipe's probe frame for profile_child_order alone (tree_tuning takes it from the library): a quarter of the frame's size, at least
+# 32 x 32, 8 spp, nodes with at least 16 deciding rays
+PROFILE_PROBE = (4, 32, 8, 16)
+
+
 def profile_child_order(renderer, scene, width, height, bounce_limit):
-    """The standard use of srt_order_children_by_profile for a frame of width x height: probe frame at a quarter of the size, 8 spp,
-    nodes with at least 16 deciding rays, from the scene's default camera.  Returns the number of nodes whose children were swapped
-    (0: the probe frame was not cheaper with the profiled order and the builder's order was kept).  Deterministic."""
-    pw, ph = max(width // 4, 32), max(height // 4, 32)
+    """The tuning recipe's child-order step alone for a frame of width x height (tree_tuning, minus the reinsertion passes): the probe
+    frame of the scene's default camera that srt_tune_tree_for_throughput uses.  Returns the number of nodes whose children were swapped
+    (0: the probe frame was not cheaper with the profiled order and the builder's order was kept) and (probe width, height, spp)."""
+    divisor, min_side, spp, min_samples = PROFILE_PROBE
+    pw, ph = max(width // divisor, min_side), max(height // divisor, min_side)
     renderer.set_camera(scene.default_camera(pw, ph))
-    return renderer.order_children_by_profile(scene, pw, ph, 8, bounce_limit, 16), (pw, ph, 8)
+    return renderer.order_children_by_profile(scene, pw, ph, spp, bounce_limit, min_samples), (pw, ph, spp)
 
 
 def render_image(scene, cam, width, height, spp, bounce_limit, seed=1984, device=0, count_traversal=False, renderer=None):

@@ -353,6 +353,31 @@ SRT_API int srt_get_tile_costs(srt_ctx *ctx, uint32_t *out, size_t n);
  * probe used the context's RNG state).  n_swapped may be NULL. */
 SRT_API int srt_order_children_by_profile(srt_ctx *ctx, srt_scene *scene, uint32_t width, uint32_t height, uint32_t spp,
                                           uint32_t bounce_limit, uint32_t min_samples, uint32_t *n_swapped);
+/* Pixels of a width x height frame per persistent lane of one of `world` ranks' launches of the uploaded scene on ctx: below about 6 a
+ * launch is bound by its longest pixel chain, above by total work. */
+SRT_API int srt_pixels_per_lane(const srt_ctx *ctx, uint32_t width, uint32_t height, uint32_t world, double *out);
+/* What srt_tune_tree_for_throughput found and did. */
+typedef struct srt_tree_tuning {
+    double   pixels_per_lane;      /* width*height / world / (CUs * waves per CU * 64) of the scene's launch on ctx */
+    uint32_t throughput_bound;     /* pixels_per_lane >= 6 */
+    uint32_t reinsertion;          /* 0 not tried (more than 8192 triangles, or not tuned), 1 kept (3 passes), 2 undone: tree restored */
+    uint32_t probe_width, probe_height, probe_spp;   /* 0 when no probe frame ran */
+    uint32_t nodes_swapped;
+    int32_t  order_status;         /* SRT_OK, or what srt_order_children_by_profile returned (its message in srt_last_error) */
+} srt_tree_tuning;
+/* Tree tuning for a THROUGHPUT-bound render of a width x height frame on `world` ranks (no reference counterpart: the tree is an
+ * input of bvh::hit, bvh/bvh.cu:98-166) -- the one recipe of every front end, so that they traverse the same tree for
+ * the same workload.  When a rank's launch has at least 6 pixels per persistent lane, a tree of up to 8 192 triangles is post-optimised
+ * by 3 reinsertion passes (srt_scene_optimise_bvh; put back exactly as it was if the deeper tree would no longer be LDS resident) and
+ * the child order is measured on one instrumented probe frame of the scene's default camera at a quarter of the frame's size (at least
+ * 32 x 32), 8 samples per pixel, nodes with at least 16 deciding rays (srt_order_children_by_profile, which undoes itself when the
+ * probe frame did not get cheaper).  Launches with fewer pixels per lane are bound by their longest pixel, which a tree with less total
+ * work does not shorten: with only_if_throughput_bound != 0 they keep the tree untouched (out->throughput_bound == 0).  Deterministic.
+ * A failing profile call is reported in out->order_status; the return value covers the arguments and the first upload.
+ * Side effects on ctx are srt_order_children_by_profile's: the scene is left uploaded, the camera is replaced by the probe's, any
+ * accumulation is invalidated, and srt_init_device_params comes next. */
+SRT_API int srt_tune_tree_for_throughput(srt_ctx *ctx, srt_scene *scene, uint32_t width, uint32_t height, uint32_t world,
+                                         uint32_t bounce_limit, int only_if_throughput_bound, srt_tree_tuning *out);
 SRT_API int srt_get_stats(srt_ctx *ctx, srt_stats *out);       /* counters of the last srt_render_chunk (or _accum pass) */
 SRT_API int srt_set_count_traversal(srt_ctx *ctx, int on);     /* 1: instrumented kernel also counts V / T */
 /* Instrumented launches only (diagnostics of the tail of a launch): 4 words per persistent wave -- [0] its life time and [1] the

@@ -58,6 +58,44 @@ static int exercise(srt_scene *s, int mode, size_t expect_tris) {
     return 0;
 }
 
+// srt_scene_get_bvh's dump plus the depth: what "the same tree" means below (compared byte for byte)
+struct TreeDump {
+    std::vector<int32_t> l, r, p;
+    std::vector<float> boxes;
+    int depth = 0;
+    bool read(const srt_scene *s) {
+        const size_t nodes = srt_scene_node_count(s);
+        l.assign(nodes, 0); r.assign(nodes, 0); p.assign(nodes, 0); boxes.assign(6 * nodes, 0.f);
+        depth = srt_scene_bvh_depth(s);
+        return nodes > 0 && srt_scene_get_bvh(s, l.data(), r.data(), p.data(), boxes.data()) == SRT_OK;
+    }
+    bool same(const TreeDump &o) const {
+        return depth == o.depth && l == o.l && r == o.r && p == o.p && boxes.size() == o.boxes.size() &&
+               memcmp(boxes.data(), o.boxes.data(), boxes.size() * sizeof(float)) == 0;
+    }
+};
+
+// optimise_bvh_unless (the reinsertion step of srt_tune_tree_for_throughput): a refused optimisation leaves the tree it found, byte for
+// byte -- whatever built or ordered it -- and an accepted one is srt_scene_optimise_bvh.  expect_change: the passes do alter this tree,
+// so the refusal has something to put back.
+static int veto_restores(srt_scene *s, bool expect_change) {
+    TreeDump before, refused, accepted, plain;
+    CHECK(before.read(s));
+    const bool had_eye = s->has_order_eye;
+    float eye[3];
+    memcpy(eye, s->order_eye, sizeof(eye));
+    srt_scene a = *s, b = *s;
+    int asked = 0;
+    CHECK(!srt::optimise_bvh_unless(*s, 3, [&](const srt::FlatScene &, const srt::FlatScene &) { asked++; return false; }));
+    CHECK(asked == 1 && refused.read(s) && refused.same(before));
+    CHECK(s->has_order_eye == had_eye && memcmp(s->order_eye, eye, sizeof(eye)) == 0);
+    CHECK(srt::optimise_bvh_unless(a, 3, [](const srt::FlatScene &, const srt::FlatScene &) { return true; }));
+    CHECK(srt_scene_optimise_bvh(&b, 3) == SRT_OK);
+    CHECK(accepted.read(&a) && plain.read(&b) && accepted.same(plain));
+    CHECK(!expect_change || !accepted.same(before));
+    return 0;
+}
+
 int main(int argc, char **argv) {
     const bool big = argc > 1 && atoi(argv[1]) != 0;
     const int ids[] = {0, 1, 2, 100, 101};
@@ -70,6 +108,19 @@ int main(int argc, char **argv) {
             if (exercise(s, mode, 0)) return 1;
             srt_scene_destroy(s);
         }
+    }
+    {
+        // the trees a rebuild with the SAH builder and the default seed would have replaced: the reference builder's with another seed,
+        // and a SAH tree re-ordered for another viewpoint
+        srt_scene *cornell = srt_scene_builtin(0, 0);
+        CHECK(cornell != nullptr && srt_scene_build_bvh(cornell, SRT_BVH_REFERENCE, 7) == SRT_OK);
+        if (veto_restores(cornell, true)) return 1;
+        srt_scene_destroy(cornell);
+        srt_scene *spheres = srt_scene_builtin(100, 0);
+        const float eye[3] = {-3.f, 7.f, 21.f};
+        CHECK(spheres != nullptr && srt_scene_build_bvh(spheres, SRT_BVH_SAH, 1984) == SRT_OK && srt_scene_order_children(spheres, eye) == SRT_OK);
+        if (veto_restores(spheres, true)) return 1;
+        srt_scene_destroy(spheres);
     }
     // raw-array scenes: one triangle (leaf root), two triangles, degenerate triangles, 40 materials, bad material index
     for (int n : {1, 2, 3, 40}) {
@@ -91,8 +142,10 @@ int main(int argc, char **argv) {
         CHECK(srt_background_spectrum(grey, bg) == SRT_OK);
         CHECK(srt_scene_set_triangles(s, t.data(), t.size()) == SRT_OK && srt_scene_set_materials(s, m.data(), m.size()) == SRT_OK);
         CHECK(srt_scene_set_background(s, bg) == SRT_OK);
-        for (int mode = 0; mode < 2; mode++)
+        for (int mode = 0; mode < 2; mode++) {
             if (exercise(s, mode, (size_t)n)) return 1;
+            if (n <= 2 && veto_restores(s, false)) return 1;      // the leaf root and the two-triangle tree
+        }
         t[0].mat_index = 99;                                   // missing material: flatten must refuse, not index out of range
         CHECK(srt_scene_set_triangles(s, t.data(), t.size()) == SRT_OK);
         CHECK(srt_scene_build_bvh(s, 1, 1984) == SRT_OK);

@@ -906,6 +906,96 @@ def test_profiled_child_order_never_makes_the_probe_frame_worse(srt, gpu, orc):
         srt.Renderer(0).order_children_by_profile(scene, 32, 32, 1, 4)      # no camera set on that context
 
 
+def _tree(scene):
+    return [np.array(a).copy() for a in scene.bvh()] + [scene.bvh_depth]
+
+
+def _same_tree(a, b):
+    return a[-1] == b[-1] and all(x.shape == y.shape and x.tobytes() == y.tobytes() for x, y in zip(a[:-1], b[:-1]))
+
+
+@pytest.mark.gpu
+def test_tree_tuning_is_its_steps(srt, gpu):
+    """srt_tune_tree_for_throughput, ungated, on a 128 x 96 frame of the random spheres: the tree it leaves equals, array for array, a
+    second copy of the scene taken through the recipe's steps by hand -- 3 reinsertion passes (none when the deeper tree would leave
+    LDS), the scene's camera at the 32 x 32 probe size, the child order from an 8 spp probe frame with 16 deciding rays."""
+    W, H, depth = 128, 96, 8
+    scene = srt.Scene.builtin(srt.SCENE_RANDOM_SPHERES, 0).build_bvh(srt.BVH_SAH, 1984)
+    hand = srt.Scene.builtin(srt.SCENE_RANDOM_SPHERES, 0).build_bvh(srt.BVH_SAH, 1984)
+    built = _tree(hand)
+    assert scene.n_tris <= 8192
+    t = srt.tree_tuning(gpu, scene, W, H, depth)
+    assert (t["probe_width"], t["probe_height"], t["probe_spp"]) == (32, 32, 8) and t["order_status"] == 0 and t["throughput_bound"] == 0
+    # the reinsertion step, consistent with the launch plans of the tree before and after the passes
+    gpu.upload_scene(hand)
+    resident = gpu.launch_plan()["all_cached"]
+    hand.optimise_bvh(3)
+    gpu.upload_scene(hand)
+    still = gpu.launch_plan()["all_cached"]
+    assert t["reinsertion"] == (2 if resident and not still else 1)
+    if t["reinsertion"] == 2:
+        hand = srt.Scene.builtin(srt.SCENE_RANDOM_SPHERES, 0).build_bvh(srt.BVH_SAH, 1984)
+    else:
+        assert not _same_tree(_tree(hand), built)
+    gpu.set_camera(hand.default_camera(32, 32))
+    n = gpu.order_children_by_profile(hand, 32, 32, 8, depth, 16)
+    print("tree tuning: %r, by hand %d nodes swapped" % (t, n))
+    assert t["nodes_swapped"] == n
+    assert _same_tree(_tree(scene), _tree(hand))
+    assert ("%d nodes swapped" % n if n else "builder's child order kept") in srt.tune_tree_for_throughput(gpu, hand, W, H, depth, gate=False)
+
+
+@pytest.mark.gpu
+def test_tree_tuning_gated_leaves_a_chain_bound_launch_alone(srt, gpu):
+    """only_if_throughput_bound: the same frame has far fewer than 6 pixels per lane -- nothing is tried, no probe frame runs and the tree
+    is byte-identical; pixels_per_lane is width * height over the lanes of the scene's launch."""
+    W, H, depth = 128, 96, 8
+    scene = srt.Scene.builtin(srt.SCENE_RANDOM_SPHERES, 0).build_bvh(srt.BVH_SAH, 1984)
+    built = _tree(scene)
+    t = srt.tree_tuning(gpu, scene, W, H, depth, gate=True)
+    lanes = srt.binding.lib().srt_ctx_cu_count(gpu._h) * gpu.launch_plan()["waves_per_cu"] * 64
+    print("gated tree tuning: %r, %d lanes" % (t, lanes))
+    assert t["pixels_per_lane"] == W * H / lanes == srt.pixels_per_lane(gpu, W, H)
+    assert t["throughput_bound"] == 0 and t["reinsertion"] == 0 and t["nodes_swapped"] == 0 and t["order_status"] == 0
+    assert (t["probe_width"], t["probe_height"], t["probe_spp"]) == (0, 0, 0)
+    assert _same_tree(_tree(scene), built)
+    assert "chain-bound launch" in srt.tune_tree_for_throughput(gpu, scene, W, H, depth, gate=True) and _same_tree(_tree(scene), built)
+
+
+@pytest.mark.gpu
+def test_instrumented_launch_fits_its_debug_buffer(srt, gpu):
+    """The per-wave debug words of an instrumented launch are sized from the launcher's own grid arithmetic and checked before anything
+    is enqueued: the waves the kernel counts, the rows srt_get_wave_debug returns and the grid -- every CU filled, never more waves than
+    queue rows, whole workgroups (16 waves for the Cornell box's shallow tree) -- agree, for an identity queue (4 spp: 88 tiles = 88
+    rows) and for the cost probe's split queue (12 spp: up to 64 rows per tile), with and without a lane limit; the buffer holds the
+    unclamped count, CUs x waves per CU, and no more."""
+    import ctypes as C
+    scene = srt.Scene.builtin(srt.SCENE_CORNELL, 0).build_bvh(srt.BVH_REFERENCE, 1984)
+    W, H, depth = 64, 48, 8
+    cam = scene.default_camera(W, H)
+    cus = srt.binding.lib().srt_ctx_cu_count(gpu._h)
+    try:
+        for lane_limit in (0, 24):
+            gpu.set_test_knobs(lane_limit=lane_limit)
+            for spp, rows in ((4, 88), (12, 88 * 64)):
+                out = srt.render_image(scene, cam, W, H, spp, depth, renderer=gpu, count_traversal=True)
+                plan = gpu.launch_plan()
+                assert plan["waves_per_cu"] == 16 and plan["test_knobs"]["lane_limit"] == lane_limit
+                most = cus * plan["waves_per_cu"]
+                grid_waves = -(-min(most, rows) // 16) * 16
+                dbg = gpu.wave_debug()
+                print("lane limit %d, %d spp: kernel counted %d waves, grid %d, buffer for %d" % (lane_limit, spp, out["stats"]["waves"][0], grid_waves, most))
+                assert out["stats"]["waves"][0] == grid_waves == dbg.shape[0]
+                words = np.zeros((most + 1, 4), np.uint32)
+                ptr = words.ctypes.data_as(C.POINTER(C.c_uint32))
+                assert srt.binding.lib().srt_get_wave_debug(gpu._h, ptr, most) == 0
+                assert srt.binding.lib().srt_get_wave_debug(gpu._h, ptr, most + 1) == -1
+    finally:
+        gpu.set_test_knobs()
+        gpu.set_count_traversal(False)
+        gpu.upload_scene(scene)
+
+
 def _soup(srt, seed, n, spread=6.0, size=0.25):
     """n small random triangles in a box, 6 materials (lambertian, metallic, dielectric, emissive), sky background"""
     rng = np.random.default_rng(4000 + seed)

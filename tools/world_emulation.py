@@ -16,16 +16,12 @@ scene = srt.Scene.builtin(a.scene, 0).build_bvh(a.bvh, 1984)
 cam = scene.default_camera(a.width, a.height)
 r = srt.Renderer(0)
 # the trees bench.py renders with: the SAH builder's for chain-bound launches (fewer than 6 pixels per lane), tuned for throughput otherwise
-tuned = None
 def scene_for(world):
-    global tuned
-    r.upload_scene(scene)
-    if a.bvh != 1 or os.environ.get("SRT_TOOL_NO_TUNING") == "1" or srt.pixels_per_lane(r, a.width, a.height, world) < 6.0:
+    if a.bvh != 1 or os.environ.get("SRT_TOOL_NO_TUNING") == "1":
         return scene
-    if tuned is None:
-        tuned = srt.Scene.builtin(a.scene, 0).build_bvh(a.bvh, 1984)
-        srt.tune_tree_for_throughput(r, tuned, a.width, a.height, a.depth)
-    return tuned
+    s = srt.Scene.builtin(a.scene, 0).build_bvh(a.bvh, 1984)
+    srt.tune_tree_for_throughput(r, s, a.width, a.height, a.depth, world=world, gate=True)      # (a chain-bound launch's tree stays as built)
+    return s
 r.upload_scene(scene); r.set_camera(cam)
 r.set_partition(0, 1); r.init_device_params(a.width, a.height, 8, a.depth, 1984); r.render_chunk(a.width, a.height); r.synchronize()   # warm-up
 out = {}
