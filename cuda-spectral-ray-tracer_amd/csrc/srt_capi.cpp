@@ -113,15 +113,17 @@ struct srt_ctx {
     // The one accumulation of a context (srt_accum_reset*, srt_render_chunk_accum).
     struct Accumulation {
         enum class State { Invalid, Empty, Bound } state = State::Invalid;   // Empty: reset, no pass yet; Bound: passes of one chunk
-        enum class Kind { Plain, Adaptive, Spectral } kind = Kind::Plain;    // MODE 3 / 4 / 5 passes (never adaptive AND spectral)
-        uint32_t total = 0;                             // samples per pixel in the sums
+        enum class Kind { Plain, Adaptive, Spectral, Streams } kind = Kind::Plain;    // MODE 3 / 4 / 5 / 6 passes (never two of the last three)
+        uint32_t total = 0;                             // samples per pixel in the sums (streamed: over all streams)
+        uint32_t n_streams = 1;                         // streamed: the RNG streams per pixel (K); 1 otherwise
         uint32_t w = 0, h = 0, offx = 0, offy = 0;      // the chunk of the first pass
         void invalidate() { state = State::Invalid; }
-        void begin(Kind k) { kind = k; state = State::Empty; }      // (srt_accum_reset has zeroed the total)
+        void begin(Kind k, uint32_t streams_per_pixel = 1) { kind = k; n_streams = streams_per_pixel; state = State::Empty; }      // (srt_accum_reset has zeroed the total)
         bool valid() const { return state != State::Invalid; }
         bool bound() const { return state == State::Bound; }
         bool adaptive() const { return kind == Kind::Adaptive; }
         bool spectral() const { return kind == Kind::Spectral; }
+        bool streamed() const { return kind == Kind::Streams; }
     } accum;
     // the buffers behind it, allocated on first use:
     DeviceBuffer d_accum;                               // progressive rendering (AccumLayout)
@@ -129,6 +131,8 @@ struct srt_ctx {
     DeviceBuffer d_adapt_queue;                         // pixel queue of the next adaptive pass (AdaptQueue)
     DeviceBuffer d_film;                                // spectral film (srt_accum_reset_spectral): kFilmStride floats per lane
     DeviceBuffer d_film_staging;                        // row-major staging block of srt_read_spectral
+    DeviceBuffer d_streams;                             // sample-parallel pixels (srt_accum_reset_streams, StreamPlanes)
+    uint32_t streams_seeded = 0;                        // the K whose RNG streams d_streams holds, seeded since the last srt_init_device_params (0: none)
 };
 
 namespace {
@@ -226,6 +230,16 @@ struct AdaptPlanes {
     explicit AdaptPlanes(const srt_ctx *c) : sum2(c->d_adapt.as<float>()), state(c->d_adapt.as<uint32_t>() + c->n_lanes) {}
 };
 
+// Sample-parallel pixels (AccumHeader::stream_planes): [RNG state: 6 planes | XYZ sums: 3 planes] of K * n_lanes words, stream k of lane
+// idx at k * n_lanes + idx
+struct StreamPlanes {
+    uint32_t *rng;
+    float *sums;
+    static size_t sums_bytes(size_t lanes, size_t k) { return 3 * k * lanes * sizeof(float); }
+    static size_t bytes(size_t lanes, size_t k) { return kStreamSumPlane * k * lanes * sizeof(uint32_t) + sums_bytes(lanes, k); }
+    StreamPlanes(const DeviceBuffer &d_streams, size_t lanes, size_t k) : rng(d_streams.as<uint32_t>()), sums(d_streams.as<float>() + kStreamSumPlane * k * lanes) {}
+};
+
 // The last chunk clipped to the reference grid, and its rectangle clipped to an image as well: w x h pixels whose first one has index
 // `first` in the row-major image (w = h = 0: the chunk lies outside the image).
 uint32_t clipped_w(const srt_ctx *c) { return std::min<uint32_t>(c->last_w, c->tx * c->bx); }
@@ -279,12 +293,18 @@ struct Pass {
     LaunchPlan plan;
     bool ordered;              // the launch runs the cost probe's queue, fresh or reused (choose_queue)
     uint32_t adapt_bound;      // adaptive passes: host-side bound of the rows of their queues (choose_queue)
+    uint32_t streams;          // streamed passes: K, the copies of every queue row (one per stream); 1 otherwise
 };
 
 uint32_t split_rows_bound(const srt_ctx *c) { return (uint32_t)std::min<uint64_t>((uint64_t)c->tiles_local * 64, 0x7fffffffull); }
+// The queue head is a 32-bit pixel-slot counter, and a streamed pass runs K copies of every row: its tiles are split only where even
+// the finest split of every tile stays below 2^32 slots; srt_render_chunk_accum refuses a pass whose UNsplit rows do not.
+constexpr uint64_t kQueueSlots = 1ull << 32;
+bool queue_may_split(const srt_ctx *c, uint32_t streams) { return c->split_load_pct && (streams == 1 || (uint64_t)split_rows_bound(c) * streams * 64 < kQueueSlots); }
 
 // Tile geometry and the compact tile buffer.
-int prepare_tiles(srt_ctx *c, const Pass &ps) {
+// (the geometry: a function of the grid and the partition alone: a pass can be refused on it before anything is enqueued)
+void tile_geometry(srt_ctx *c) {
     // Tiles cover every pixel the reference grid can address, whatever the size of THIS chunk: the tile number of a lane
     // idx -- and with it the rank that owns the lane's persistent RNG stream (Q13) -- must not move when a ragged edge
     // chunk is narrower than the one before.  Tiles (partly) outside the chunk just skip those pixels (rendering.cu:205).
@@ -293,6 +313,10 @@ int prepare_tiles(srt_ctx *c, const Pass &ps) {
     c->n_tiles = c->tiles_x * c->tiles_y;
     c->tiles_padded = (c->n_tiles + c->world - 1) / c->world;
     c->tiles_local = c->n_tiles > c->rank ? (c->n_tiles - c->rank + c->world - 1) / c->world : 0;
+}
+
+int prepare_tiles(srt_ctx *c, const Pass &ps) {
+    tile_geometry(c);
     const size_t tile_floats = (size_t)std::max<uint32_t>(c->tiles_padded, 1) * kTileLanes;      // per plane
     HIP_TRY(c, c->d_tiles.reserve(tile_floats * kTilePlanes * sizeof(float)));
     // (only the plane groups this launch writes: group 0, or all three when the parity planes were asked for.  Not on the later passes
@@ -305,7 +329,7 @@ int prepare_tiles(srt_ctx *c, const Pass &ps) {
 // The launch's parameters up to the pixel queue, which starts as the identity order.
 void chunk_params(const srt_ctx *c, const Pass &ps, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy, RenderParams &p) {
     fill_params(c, p);
-    if (ps.spp_add) p.spp = ps.spp_add;      // the samples this pass adds (the running total is in the header)
+    if (ps.spp_add) p.spp = ps.spp_add / ps.streams;      // the samples this pass adds, per stream (the running total is in the header)
     p.width = width; p.height = height; p.offx = offx; p.offy = offy;
     p.tiles_x = c->tiles_x; p.tiles_y = c->tiles_y; p.n_tiles = c->n_tiles;
     p.tiles_local = c->tiles_local;
@@ -333,9 +357,11 @@ int run_cost_probe(srt_ctx *c, const Pass &ps, const RenderParams &p) {
     pp.spp = c->probe_spp; pp.tile_cost = sched.cost;
     RoctxRange range_probe("srt cost probe + pixel queue");
     HIP_TRY(c, launch_render(pp, c->knobs, (uint32_t)c->n_cu, Probe, ps.st));
-    const uint32_t n_waves_plan = (uint32_t)c->n_cu * (uint32_t)ps.plan.waves_per_cu;
+    // (a streamed pass runs K copies of every row, each a chain of 1/K of the pixel's samples: the split policy's latency and capacity
+    // constraints, with T the makespan of the UNsplit streams, are those of a machine of n_waves / K waves -- order_tiles_kernel)
+    const uint32_t n_waves_plan = std::max<uint32_t>((uint32_t)c->n_cu * (uint32_t)ps.plan.waves_per_cu / ps.streams, 1u);
     const uint32_t order_pct = c->order_max_pct >= 0 ? (uint32_t)c->order_max_pct : ((!ps.plan.all_cached && (uint64_t)c->tiles_local < 6ull * n_waves_plan) ? 100u : 0u);
-    HIP_TRY(c, launch_order_tiles(sched.cost, sched.sorted, sched.rows, c->tiles_local, n_waves_plan, c->split_load_pct, sched.info, order_pct, ps.st));   // device-side, no host sync
+    HIP_TRY(c, launch_order_tiles(sched.cost, sched.sorted, sched.rows, c->tiles_local, n_waves_plan, queue_may_split(c, ps.streams) ? c->split_load_pct : 0u, sched.info, order_pct, ps.st));   // device-side, no host sync
     HIP_TRY(c, hipMemsetAsync(c->d_counters.as<unsigned long long>() + kCounters, 0, sizeof(unsigned long long), ps.st));   // rewind the queue head
     return SRT_OK;
 }
@@ -362,7 +388,7 @@ QueueSource queue_source(const srt_ctx *c, const Pass &ps) {
 int choose_queue(srt_ctx *c, Pass &ps, RenderParams &p) {
     const bool schedulable = c->probe_spp > 0 && c->tiles_local > 1 && c->tiles_local <= kQueueTileMask;   // the tile field of a queue row
     ps.ordered = schedulable && (ps.spp_add || c->spp > 4 * c->probe_spp);
-    ps.adapt_bound = ps.ordered && c->split_load_pct ? split_rows_bound(c) : c->tiles_local;
+    ps.adapt_bound = ps.ordered && c->split_load_pct ? split_rows_bound(c) : c->tiles_local;      // (adaptive passes are never streamed)
     if (ps.mode == Adaptive) HIP_TRY(c, c->d_adapt_queue.reserve(AdaptQueue::bytes(std::max<uint32_t>(ps.adapt_bound, 1u))));
     const QueueSource src = queue_source(c, ps);
     if (src == QueueSource::Compacted) {
@@ -378,8 +404,9 @@ int choose_queue(srt_ctx *c, Pass &ps, RenderParams &p) {
         p.tile_order = sched.rows;
         p.queue_rows = sched.info;
         p.prio_cost = sched.cost;      // wave priorities of the render launch (render_kernel, LDS-resident trees)
-        if (c->split_load_pct) p.queue_rows_bound = split_rows_bound(c);
+        if (queue_may_split(c, ps.streams)) p.queue_rows_bound = split_rows_bound(c);
     }
+    p.queue_rows_bound *= ps.streams;      // (after the probe, which walks the tiles themselves)
     return SRT_OK;
 }
 
@@ -427,14 +454,28 @@ int compact_adaptive_queue(srt_ctx *c, const Pass &ps, const RenderParams &p) {
     return SRT_OK;
 }
 
+// After a streamed pass: the K sums of every pixel added in stream order, and the tile buffer written from the result
+int combine_streams(srt_ctx *c, const Pass &ps, const RenderParams &p) {
+    StreamCombineParams q = {};
+    q.stream_sums = StreamPlanes(c->d_streams, c->n_lanes, ps.streams).sums; q.sums = AccumLayout(c).sums; q.tile_out = p.tile_out;
+    q.streams = ps.streams; q.spp_total = c->accum.total + ps.spp_add; q.n_lanes = c->n_lanes;
+    q.tile_group_stride = p.tile_group_stride; q.write_parity = p.write_parity; q.tiles_local = c->tiles_local;
+    q.width = p.width; q.height = p.height; q.tx = c->tx; q.ty = c->ty; q.bx = c->bx; q.by = c->by;
+    q.tiles_x = c->tiles_x; q.n_tiles = c->n_tiles; q.rank = c->rank; q.world = c->world;
+    q.lane_limit = c->debug_lane_limit ? c->debug_lane_limit : 64u;
+    HIP_TRY(c, launch_stream_combine(q, ps.st));
+    return SRT_OK;
+}
+
 // spp_add == 0: a plain launch of c->spp samples (Plain, or Counting when instrumented); spp_add > 0: an accumulating pass of spp_add
-// samples (Accum / Adaptive / Spectral) whose caller has checked the accumulation and enqueued its header.
+// samples (Accum / Adaptive / Spectral / Streams) whose caller has checked the accumulation and enqueued its header.
 // width .. offy are already narrowed to 16 bit.
 int render_chunk_impl(srt_ctx *c, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy, uint32_t spp_add, hipStream_t st) {
     Pass ps = {};
     ps.spp_add = spp_add; ps.st = st;
-    ps.mode = !spp_add ? (c->count_traversal ? Counting : Plain) : c->accum.adaptive() ? Adaptive : c->accum.spectral() ? Spectral : Accum;
+    ps.mode = !spp_add ? (c->count_traversal ? Counting : Plain) : c->accum.adaptive() ? Adaptive : c->accum.spectral() ? Spectral : c->accum.streamed() ? Streams : Accum;
     ps.later = spp_add && c->accum.bound(); ps.plan = plan_of(c);
+    ps.streams = ps.mode == Streams ? c->accum.n_streams : 1u;
     c->last_w = width; c->last_h = height; c->last_offx = offx; c->last_offy = offy;
     RenderParams p;
     if (const int rc = prepare_tiles(c, ps)) return rc;
@@ -445,6 +486,8 @@ int render_chunk_impl(srt_ctx *c, uint32_t width, uint32_t height, uint32_t offx
     if (const int rc = launch_pass(c, ps, p)) return rc;
     if (ps.mode == Adaptive)
         if (const int rc = compact_adaptive_queue(c, ps, p)) return rc;
+    if (ps.mode == Streams)
+        if (const int rc = combine_streams(c, ps, p)) return rc;
     c->timed = true;
     c->stats_spp = spp_add;
     c->stats_adaptive = ps.mode == Adaptive;
@@ -648,6 +691,7 @@ int srt_internal_init_device_params(srt_ctx *c, uint32_t tx, uint32_t ty, uint32
     c->tx = tx; c->ty = ty; c->bx = bx; c->by = by; c->chunk_w = chunk_w; c->chunk_h = chunk_h;
     c->spp = (uint16_t)spp; c->bounce = (uint16_t)bounce_limit;     // short_uint, rendering.cu:154 (Q17)
     c->seed = seed; c->n_lanes = (uint32_t)lanes;
+    c->streams_seeded = 0;      // streams 1 .. K-1 start from this seed again at the next srt_accum_reset_streams
     // (a new frame of the same grid -- or of a smaller one -- re-seeds in place)
     HIP_TRY(c, c->d_rng.reserve(6 * lanes * sizeof(uint32_t)));
     HIP_TRY(c, c->d_fb.reserve(kTilePlanes * lanes * sizeof(float)));
@@ -732,6 +776,54 @@ int srt_accum_reset_spectral(srt_ctx *c) {
     return SRT_OK;
 }
 
+int srt_accum_reset_streams(srt_ctx *c, uint32_t streams) {
+    if (!c) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_streams: null ctx");
+    // refusals first: a refused call leaves the context's accumulation as it was
+    if (streams == 0 || streams > kMaxStreams) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_streams: streams must be in 1 .. SRT_MAX_STREAMS (16)");
+    if (c->count_traversal)
+        return fail(c, SRT_ERR_UNSUPPORTED, "srt_accum_reset_streams: no instrumented accumulating kernel (srt_set_count_traversal(ctx, 0) first)");
+    if (!c->params_ready) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_streams: device parameters must be set first (srt_init_device_params)");
+    if ((uint64_t)streams * c->n_lanes > 0x7fffffffull)
+        return fail(c, SRT_ERR_INVALID, "srt_accum_reset_streams: streams x lanes of the grid must stay below 2^31 (the stream planes have 32-bit indices)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = StreamPlanes::bytes(c->n_lanes, streams);
+    const bool seeded = c->streams_seeded == streams && c->d_streams.bytes >= bytes;
+    if (c->d_streams.bytes < bytes) {
+        // (the new planes are allocated before the old ones go: a failed allocation changes nothing)
+        DeviceBuffer planes;
+        HIP_TRY(c, planes.reserve(bytes));
+        c->d_streams = std::move(planes);
+        c->streams_seeded = 0;
+    }
+    int rc = srt_accum_reset(c);
+    if (rc != SRT_OK) return rc;
+    c->accum.invalidate();      // (until the stream planes are in place)
+    const StreamPlanes sp(c->d_streams, c->n_lanes, streams);
+    // streams 1 .. K-1 of lane idx: XORWOW(seed + k * n_lanes + idx), the state that lane has in a context initialised with seed + k * n_lanes.
+    // Once per srt_init_device_params and K: like stream 0, they continue across resets.  (The planes of another K are laid out
+    // differently: a reset with another K seeds them afresh.)
+    if (!seeded) {
+        c->streams_seeded = 0;
+        HIP_TRY(c, launch_init_rng(sp.rng, streams * c->n_lanes, c->seed, nullptr));
+    }
+    HIP_TRY(c, hipMemset(sp.sums, 0, StreamPlanes::sums_bytes(c->n_lanes, streams)));
+    // the streamed part of the header (the per-pass kernel rewrites only sums and spp_total)
+    AccumHeader h = {};
+    h.stream_planes = sp.rng; h.streams = streams;
+    const size_t tail = offsetof(AccumHeader, stream_planes);
+    HIP_TRY(c, hipMemcpy(&AccumLayout(c).header->stream_planes, reinterpret_cast<const char *>(&h) + tail, sizeof(h) - tail, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipDeviceSynchronize());
+    c->streams_seeded = streams;
+    c->accum.begin(srt_ctx::Accumulation::Kind::Streams, streams);
+    return SRT_OK;
+}
+
+int srt_accum_streams(const srt_ctx *c, uint32_t *streams) {
+    if (!c || !streams) return fail(nullptr, SRT_ERR_INVALID, "srt_accum_streams: null argument");
+    *streams = c->accum.valid() && c->accum.streamed() ? c->accum.n_streams : 0u;
+    return SRT_OK;
+}
+
 int srt_accum_reset_adaptive(srt_ctx *c, const srt_adaptive *cfg) {
     if (!c) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_adaptive: null ctx");
     // refusals first: a refused call leaves the context's accumulation as it was
@@ -788,6 +880,14 @@ int srt_render_chunk_accum(srt_ctx *c, uint32_t width, uint32_t height, uint32_t
     if (spp_add == 0) return fail(c, SRT_ERR_INVALID, "srt_render_chunk_accum: spp_add must be > 0");
     if ((uint64_t)c->accum.total + spp_add > 0xffffu)
         return fail(c, SRT_ERR_INVALID, "srt_render_chunk_accum: the total would exceed 65535 samples per pixel (16-bit spp, Q17)");
+    if (c->accum.streamed()) {
+        const uint32_t k = c->accum.n_streams;
+        if (spp_add % k != 0)
+            return fail(c, SRT_ERR_INVALID, "srt_render_chunk_accum: spp_add must be a multiple of the accumulation's streams (every stream draws spp_add / K samples)");
+        tile_geometry(c);
+        if ((uint64_t)c->tiles_local * k * 64 >= kQueueSlots)
+            return fail(c, SRT_ERR_INVALID, "srt_render_chunk_accum: tiles x streams x 64 must stay below 2^32 (the pixel queue's 32-bit slot counter)");
+    }
     width = (uint16_t)width; height = (uint16_t)height; offx = (uint16_t)offx; offy = (uint16_t)offy;   // rendering.cu:245 (Q17)
     if (c->accum.bound() && (width != c->accum.w || height != c->accum.h || offx != c->accum.offx || offy != c->accum.offy))
         return fail(c, SRT_ERR_INVALID, "srt_render_chunk_accum: the accumulation belongs to another chunk (one accumulation per context)");

@@ -104,9 +104,19 @@ struct AccumHeader {
     float rel_tol, abs_tol;
     uint32_t min_spp, pad2;
     float *film;
+    uint32_t *stream_planes;
+    uint32_t streams, pad3;
 };
 // Spectral accumulations (MODE 5, srt_accum_reset_spectral) read `film` as well: kFilmStride floats per lane of the grid, indexed by the
 // block-linear idx, of which the first kFilmSamples are the raw sums on the CIE grid (360 + 5 j nm); srt_accum_reset_spectral writes it once.
+// Streamed accumulations (MODE 6, srt_accum_reset_streams) read the two fields behind `film` instead: a pixel has `streams` = K RNG
+// streams, and the launch's work item is (pixel, stream k).  stream_planes: nine planes of K * n_lanes words, entry idx' = k * n_lanes +
+// idx of a plane belonging to stream k of lane idx -- planes 0 .. 5 its RNG state (except stream 0, which is the context's own state,
+// RenderParams::rng: the k = 0 entries of these six planes are not used), planes 6 .. 8 (kStreamSumPlane) its XYZ sum.  MODE 6 writes no
+// tile-buffer slot: stream_combine_kernel adds the K sums in stream order into `sums` and converts.  srt_accum_reset_streams writes the
+// two fields once.
+constexpr uint32_t kStreamSumPlane = 6;
+constexpr uint32_t kMaxStreams = 16;      // SRT_MAX_STREAMS (srt_c_api.h)
 constexpr uint32_t kFilmSamples = 95;
 constexpr uint32_t kFilmStride = 96;      // 384 B: three 128-B lines per pixel, the last word unused
 constexpr uint32_t kAdaptConverged = 0x80000000u;      // state word: the pixel has stopped (the low 31 bits: the samples it holds)
@@ -125,13 +135,15 @@ struct ScatterParams {
     uint32_t tiles_x, n_tiles, world, tiles_padded;
 };
 
+// XORWOW(seed + idx) for idx < n_lanes into six planes of n_lanes words.  (The streams of a streamed accumulation are one call: its planes
+// hold K * n_lanes states, and stream k of lane idx is entry k * n_lanes + idx.)
 hipError_t launch_init_rng(uint32_t *rng, uint32_t n_lanes, uint64_t seed, hipStream_t st);
 // Test knobs of a context (srt_set_test_knobs; from the environment only under SRT_TEST_KNOBS=1, read once at srt_create): they pick
 // the kernel variant / cache size a launch plan would not pick by itself, so that every instantiated variant can be held to the CPU oracle by the tests.
 struct PlanKnobs { bool wide_refs = false; int lds_cache_max = -1; };
 // The render launch's variant; the values are render_kernel's MODE template argument.  Plain: render; Counting: instrumented; Probe: cost
-// probe; Accum: accumulating render (p.wave_debug -> AccumHeader); Adaptive / Spectral: adaptive / spectral accumulating render.
-enum RenderMode { Plain = 0, Counting = 1, Probe = 2, Accum = 3, Adaptive = 4, Spectral = 5 };
+// probe; Accum: accumulating render (p.wave_debug -> AccumHeader); Adaptive / Spectral / Streams: adaptive / spectral / streamed accumulating render.
+enum RenderMode { Plain = 0, Counting = 1, Probe = 2, Accum = 3, Adaptive = 4, Spectral = 5, Streams = 6 };
 hipError_t launch_render(const RenderParams &p, const PlanKnobs &knobs, uint32_t n_cu, RenderMode mode, hipStream_t st);
 hipError_t launch_accum_header(AccumHeader *dst, float *sums, uint32_t spp_total, hipStream_t st);      // writes *dst on the stream
 // Pixel queue of the next adaptive pass (see adapt_flag_kernel): the rows of `src_rows` (src_info[0] of them; nullptr: the identity
@@ -150,6 +162,18 @@ hipError_t launch_adapt_queue(const AdaptQueueParams &p, uint32_t n_rows_bound, 
 // The film's grid samples [first, first + count) of the w x h pixels at the chunk's origin -> dst[((y * w) + x) * count + (j - first)].
 hipError_t launch_film_unswizzle(const float *film, float *dst, uint32_t first, uint32_t count, uint32_t w, uint32_t h, uint32_t tx,
                                  uint32_t ty, uint32_t bx, hipStream_t st);
+// After a streamed pass (MODE 6): every pixel of this rank's share of the chunk adds its K stream sums in stream order into the
+// accumulation's sum planes and writes its tile-buffer slots from them, as MODE 3's pixel switch does.
+struct StreamCombineParams {
+    const float *stream_sums;      // planes kStreamSumPlane .. of AccumHeader::stream_planes
+    float *sums;                   // AccumHeader::sums
+    float *tile_out;
+    uint32_t streams, spp_total, n_lanes;
+    uint32_t tile_group_stride, write_parity;
+    uint32_t tiles_local;
+    uint32_t width, height, tx, ty, bx, by, tiles_x, n_tiles, rank, world, lane_limit;
+};
+hipError_t launch_stream_combine(const StreamCombineParams &p, hipStream_t st);
 hipError_t launch_order_tiles(const uint32_t *cost, uint32_t *sorted, uint32_t *rows, uint32_t n, uint32_t n_waves,
                               uint32_t split_load_pct, uint32_t *queue_info, uint32_t order_max_pct, hipStream_t st);
 hipError_t launch_scatter(const ScatterParams &p, hipStream_t st);

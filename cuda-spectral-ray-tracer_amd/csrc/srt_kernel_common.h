@@ -30,6 +30,7 @@ struct LdsUniforms {
     uint32_t accum_sum2[2], accum_state[2], min_spp;     // adaptive launches (MODE 4) only: AccumHeader's S2 and state planes, the criterion
     float rel_tol, abs_tol;
     uint32_t accum_film[2];      // spectral launches (MODE 5) only: AccumHeader's film
+    uint32_t streams;            // streamed launches (MODE 6) only: AccumHeader's K; accum_sums holds its stream planes (the block is full now)
 };
 static_assert(sizeof(LdsUniforms) <= kLdsUniF4 * 16, "uniform block too large");
 typedef __attribute__((address_space(3))) LdsUniforms lds_uniforms;

@@ -173,6 +173,11 @@ __device__ __forceinline__ bool adaptive_converged(float s1, float s2, uint32_t 
 // MODE 5: MODE 3 of a spectral accumulation -- every path end that is converted to XYZ (the ends_here block of S1) also adds its
 // seven powers to the pixel's film, 95 fp32 sums on the CIE grid (AccumHeader::film, kFilmStride floats per lane): the hat pair
 // (off_k, off_k + 1) of wavelength k gets ((1 - w_k) * p_k, w_k * p_k), p_k the power the XYZ conversion uses (+0 for k >= valid).
+// MODE 6: MODE 3 of a streamed accumulation (srt_accum_reset_streams) -- the work item is (pixel, stream): queue row q stands for stream
+// q % K of the tile of row q / K of the launch's queue (the K copies of a row are adjacent, so the first-row assignment and the shared
+// counter hand the K streams of an expensive tile to K different workgroups), and the lane's idx is idx' = k * n_lanes + idx, its slot in
+// the stream planes (AccumHeader::stream_planes; stream 0 -- idx' < n_lanes -- keeps its RNG state in the context's own planes).  The
+// pixel switch stores RNG state and sums and nothing else: stream_combine_kernel adds the streams and writes the tile buffer.
 // ALL_CACHED: the whole inner tree fits the LDS cache (n_cached == n_inner): the INNER step has no global fall-back path.
 // PAIRED (instantiated for <., 1, 1> and <., 0, 0>): every FRINGE record holds two triangles (srt_scene_is_paired): the visit has no box test.
 template <int MODE, bool NARROW, bool ALL_CACHED, bool PAIRED>
@@ -183,6 +188,7 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
     constexpr bool ACCUM = (MODE == 3 || MODE == 4 || MODE == 5);
     constexpr bool ADAPT = (MODE == 4);
     constexpr bool FILM = (MODE == 5);
+    constexpr bool STREAMS = (MODE == 6);
     // (S2 of the current pixel: in a register -- acc2 -- except in the wide-reference, partly-L2, unpaired shape, which is at the
     // 128-VGPR limit already and would spill it to scratch: there each path end adds its y * y to the pixel's own S2 word in memory.
     // The same additions in the same order: the result is the same bits.  profiles/adaptive/mode4_resource_usage.txt)
@@ -228,6 +234,12 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
             U->min_spp = ah->min_spp; U->rel_tol = ah->rel_tol; U->abs_tol = ah->abs_tol;
         }
         if constexpr (FILM) split_ptr(reinterpret_cast<const AccumHeader *>(P.wave_debug)->film, U->accum_film);
+        if constexpr (STREAMS) {
+            const AccumHeader *ah = reinterpret_cast<const AccumHeader *>(P.wave_debug);
+            split_ptr(ah->stream_planes, U->accum_sums);
+            U->streams = ah->streams;
+            U->n_rows *= ah->streams;      // (the host keeps rows x K x 64 below 2^32: srt_render_chunk_accum)
+        }
     }
     for (uint32_t k = threadIdx.x; k < kLdsCmfF4; k += blockDim.x) s_cmf[k] = P.cmf[k];
     for (uint32_t k = threadIdx.x; k < nc; k += blockDim.x) {
@@ -481,7 +493,21 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
                     have_pixel = false;
                 }
                 if (have_pixel && COUNT) { max_pix_iters = max(max_pix_iters, ts.n_iters - pixel_iters0); max_pix_rays = max(max_pix_rays, n_rays - pixel_rays0); }
-                if (have_pixel && !PROBE) {
+                if constexpr (STREAMS) {
+                    if (have_pixel) {      // the stream's RNG state and sum go back to their planes; stream_combine_kernel converts the pixel
+                        const size_t nl0 = U->n_lanes, nlk = nl0 * U->streams;
+                        const bool stream0 = idx < nl0;
+                        uint32_t *planes = join_ptr<uint32_t>(U->accum_sums[0], U->accum_sums[1]);
+                        uint32_t *rng = stream0 ? join_ptr<uint32_t>(U->rng[0], U->rng[1]) : planes;
+                        const size_t nl = stream0 ? nl0 : nlk;
+                        rng[0 * nl + idx] = rs.d; rng[1 * nl + idx] = rs.v0; rng[2 * nl + idx] = rs.v1;
+                        rng[3 * nl + idx] = rs.v2; rng[4 * nl + idx] = rs.v3; rng[5 * nl + idx] = rs.v4;
+                        float *sums = reinterpret_cast<float *>(planes + kStreamSumPlane * nlk);
+                        sums[0 * nlk + idx] = acc.x; sums[1 * nlk + idx] = acc.y; sums[2 * nlk + idx] = acc.z;
+                        have_pixel = false;
+                    }
+                }
+                if (have_pixel && !PROBE && !STREAMS) {
                     // store RNG state (rendering.cu:232) and save_to_fb (rendering.cu:140-149)
                     {
                         uint32_t *rng = join_ptr<uint32_t>(U->rng[0], U->rng[1]);
@@ -558,8 +584,17 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
                         // decode of the queue row and of the slot: srt_kernel_common.h (cost-descending order, see order_tiles_kernel)
                         const uint32_t *tile_order = join_ptr<const uint32_t>(U->tile_order[0], U->tile_order[1]);
                         // (no ordered queue: the row IS the local tile, whatever its magnitude -- nothing to decode)
-                        const QueueRow qr = queue_row_unpack(tile_order ? tile_order[pix >> 6] : 0u);
-                        const uint32_t tile_local = tile_order ? qr.tile_local : (pix >> 6);
+                        QueueRow qr;
+                        uint32_t tile_local, stream = 0u;
+                        if constexpr (STREAMS) {      // K adjacent copies of every row of the launch's queue, one per stream
+                            const uint32_t src_row = (pix >> 6) / U->streams;
+                            stream = (pix >> 6) - src_row * U->streams;
+                            qr = queue_row_unpack(tile_order ? tile_order[src_row] : 0u);
+                            tile_local = tile_order ? qr.tile_local : src_row;
+                        } else {
+                            qr = queue_row_unpack(tile_order ? tile_order[pix >> 6] : 0u);
+                            tile_local = tile_order ? qr.tile_local : (pix >> 6);
+                        }
                         const uint32_t row_s = qr.s;
                         const uint32_t lt = pix & 63u;
                         // A split row is meant for a wave that takes it whole (all 64 lanes fetch together: first fill, or
@@ -585,13 +620,25 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
                             idx = block_linear_idx(i, j, gtx, gty, gbx);
                             out_slot = tile_local * (uint32_t)(kGroupPlanes * kTileLanes) + lt;
                             pixel_ij = i | (j << 16);
-                            {
+                            if constexpr (STREAMS) {      // stream k of the pixel: its slot, RNG state and sum so far
+                                const size_t nl0 = U->n_lanes, nlk = nl0 * U->streams;
+                                idx += stream * U->n_lanes;
+                                const bool stream0 = stream == 0u;
+                                const uint32_t *planes = join_ptr<const uint32_t>(U->accum_sums[0], U->accum_sums[1]);
+                                const uint32_t *rng = stream0 ? join_ptr<const uint32_t>(U->rng[0], U->rng[1]) : planes;
+                                const size_t nl = stream0 ? nl0 : nlk;
+                                rs.d = rng[0 * nl + idx]; rs.v0 = rng[1 * nl + idx]; rs.v1 = rng[2 * nl + idx];
+                                rs.v2 = rng[3 * nl + idx]; rs.v3 = rng[4 * nl + idx]; rs.v4 = rng[5 * nl + idx];
+                                const float *sums = reinterpret_cast<const float *>(planes + kStreamSumPlane * nlk);
+                                acc = mk(sums[0 * nlk + idx], sums[1 * nlk + idx], sums[2 * nlk + idx]);
+                            } else {
                                 const uint32_t *rng = join_ptr<const uint32_t>(U->rng[0], U->rng[1]);      // rendering.cu:209
                                 const size_t nl = U->n_lanes;
                                 rs.d = rng[0 * nl + idx]; rs.v0 = rng[1 * nl + idx]; rs.v1 = rng[2 * nl + idx];
                                 rs.v2 = rng[3 * nl + idx]; rs.v3 = rng[4 * nl + idx]; rs.v4 = rng[5 * nl + idx];
                             }
-                            if constexpr (ACCUM) {      // continue the pixel's sum of the earlier passes (zero after srt_accum_reset)
+                            if constexpr (STREAMS) {
+                            } else if constexpr (ACCUM) {      // continue the pixel's sum of the earlier passes (zero after srt_accum_reset)
                                 const float *sums = join_ptr<const float>(U->accum_sums[0], U->accum_sums[1]);
                                 const size_t nl = U->n_lanes;
                                 acc = mk(sums[0 * nl + idx], sums[1 * nl + idx], sums[2 * nl + idx]);
@@ -1128,12 +1175,13 @@ hipError_t launch_render(const RenderParams &p, const PlanKnobs &knobs, uint32_t
     const bool narrow = render_narrow_refs(p.n_records, knobs);
     if (mode == 1) return narrow ? launch_render_mode<1, true>(p, knobs, n_cu, st) : launch_render_mode<1, false>(p, knobs, n_cu, st);
     if (mode == 2) return narrow ? launch_render_mode<2, true>(p, knobs, n_cu, st) : launch_render_mode<2, false>(p, knobs, n_cu, st);
-    if (mode < 3 || mode > 5) return narrow ? launch_render_mode<0, true>(p, knobs, n_cu, st) : launch_render_mode<0, false>(p, knobs, n_cu, st);
+    if (mode < 3 || mode > 6) return narrow ? launch_render_mode<0, true>(p, knobs, n_cu, st) : launch_render_mode<0, false>(p, knobs, n_cu, st);
     // (instantiated after the production variants: their place in the object, and so the labels of their ISA listing, stay as they were)
     if (mode == 3) return narrow ? launch_render_mode<3, true>(p, knobs, n_cu, st) : launch_render_mode<3, false>(p, knobs, n_cu, st);
     // (and the adaptive ones after the accumulating ones, the spectral ones after those, for the same reason)
     if (mode == 4) return narrow ? launch_render_mode<4, true>(p, knobs, n_cu, st) : launch_render_mode<4, false>(p, knobs, n_cu, st);
-    return narrow ? launch_render_mode<5, true>(p, knobs, n_cu, st) : launch_render_mode<5, false>(p, knobs, n_cu, st);
+    if (mode == 5) return narrow ? launch_render_mode<5, true>(p, knobs, n_cu, st) : launch_render_mode<5, false>(p, knobs, n_cu, st);
+    return narrow ? launch_render_mode<6, true>(p, knobs, n_cu, st) : launch_render_mode<6, false>(p, knobs, n_cu, st);
 }
 
 hipError_t launch_order_tiles(const uint32_t *cost, uint32_t *sorted, uint32_t *rows, uint32_t n, uint32_t n_waves,
@@ -1265,6 +1313,51 @@ hipError_t launch_film_unswizzle(const float *film, float *dst, uint32_t first, 
     const size_t n = (size_t)w * h * count;
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(film_unswizzle_kernel<0>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, film, dst, first, count, w, h, tx, ty, bx);
+    return hipGetLastError();
+}
+
+// After a streamed pass (MODE 6, StreamCombineParams): one wave per local tile, one lane per slot, the slot -> pixel map and chunk test
+// of the pixel queue.  The pixel's sum is ((S_0 + S_1) + S_2) + ... + S_{K-1} per component (fp32; the build does not contract), stored
+// to the accumulation's sum planes and converted into the slots MODE 3 would have written: render_kernel's pixel switch (S3) restated
+// expression by expression on the same device functions and constants -- with K = 1 the same bits (render_kernel keeps its own copy:
+// calling a shared function there changes the machine code of every existing variant).  A template, instantiated here at the end of
+// the unit (see accum_header_kernel).
+template <int>
+__global__ __launch_bounds__(256) void stream_combine_kernel(const StreamCombineParams P) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t tile_local = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (tile_local >= P.tiles_local) return;
+    const uint32_t tile = queue_global_tile(tile_local, P.rank, P.world);
+    const PixelIJ px = tile_slot_pixel(tile, lane, P.tiles_x);
+    if (!queue_slot_in_chunk(tile, lane, px, P.n_tiles, P.lane_limit, P.width, P.height, P.tx, P.ty, P.bx, P.by)) return;
+    const uint32_t idx = block_linear_idx(px.i, px.j, P.tx, P.ty, P.bx);
+    const size_t nl = P.n_lanes, nlk = nl * P.streams;
+    V3 acc = mk(P.stream_sums[0 * nlk + idx], P.stream_sums[1 * nlk + idx], P.stream_sums[2 * nlk + idx]);
+    for (uint32_t k = 1; k < P.streams; k++) {
+        const size_t at = (size_t)k * nl + idx;
+        acc = acc + mk(P.stream_sums[0 * nlk + at], P.stream_sums[1 * nlk + at], P.stream_sums[2 * nlk + at]);
+    }
+    P.sums[0 * nl + idx] = acc.x; P.sums[1 * nl + idx] = acc.y; P.sums[2 * nl + idx] = acc.z;
+    const float inv_spp = 1.0f / (float)P.spp_total;
+    const V3 c = inv_spp * acc;
+    const float r_lin = (SRT_XYZ2RGB_00 * c.x) + (SRT_XYZ2RGB_01 * c.y) + (SRT_XYZ2RGB_02 * c.z);
+    const float g_lin = (SRT_XYZ2RGB_10 * c.x) + (SRT_XYZ2RGB_11 * c.y) + (SRT_XYZ2RGB_12 * c.z);
+    const float b_lin = (SRT_XYZ2RGB_20 * c.x) + (SRT_XYZ2RGB_21 * c.y) + (SRT_XYZ2RGB_22 * c.z);
+    const float r = correct_channel(r_lin), g = correct_channel(g_lin), b = correct_channel(b_lin);
+    float *o = P.tile_out + (size_t)tile_local * (uint32_t)(kGroupPlanes * kTileLanes) + lane;
+    const size_t gs = P.tile_group_stride;
+    o[0 * kTileLanes] = (float)(int)(r * 255.99f);      // expand_sRGB (color.cu:43-49, Q15)
+    o[1 * kTileLanes] = (float)(int)(g * 255.99f);
+    o[2 * kTileLanes] = (float)(int)(b * 255.99f);
+    if (P.write_parity) {
+        o[gs + 0 * kTileLanes] = r; o[gs + 1 * kTileLanes] = g; o[gs + 2 * kTileLanes] = b;
+        o[2 * gs + 0 * kTileLanes] = acc.x; o[2 * gs + 1 * kTileLanes] = acc.y; o[2 * gs + 2 * kTileLanes] = acc.z;
+    }
+}
+
+hipError_t launch_stream_combine(const StreamCombineParams &p, hipStream_t st) {
+    if (p.tiles_local == 0) return hipSuccess;
+    hipLaunchKernelGGL(stream_combine_kernel<0>, dim3((p.tiles_local + 3u) / 4u), dim3(256), 0, st, p);
     return hipGetLastError();
 }
 

@@ -137,6 +137,19 @@ class Renderer:
         self._ck(B.lib().srt_read_spectral(self._h, int(first), int(count), B.fptr(out), image_width, image_height))
         return out
 
+    def accum_reset_streams(self, k):
+        """start a STREAMED accumulation (srt_c_api.h): every pixel has k independent RNG streams (1 <= k <= MAX_STREAMS), stream j of lane
+        idx seeded XORWOW(seed + j * n_lanes + idx); a pass of spp_add samples (a multiple of k) draws spp_add / k from every stream, and
+        the pixel's XYZ sum is ((S_0 + S_1) + ..) + S_{k-1}, S_j the sum of a plain accumulation of a context seeded seed + j * n_lanes"""
+        self._ck(B.lib().srt_accum_reset_streams(self._h, int(k)))
+
+    @property
+    def accum_streams(self):
+        """the streams per pixel of a streamed accumulation; 0 when the accumulation is not streamed (or there is none)"""
+        n = C.c_uint32()
+        self._ck(B.lib().srt_accum_streams(self._h, C.byref(n)))
+        return n.value
+
     def set_gather_planes(self, planes):
         """3 (default): the exchange unit is the quantised framebuffer; 9: + the parity planes (unquantised sRGB, XYZ sums)"""
         self._ck(B.lib().srt_set_gather_planes(self._h, planes))
@@ -353,6 +366,10 @@ class Comm:
         """Renderer.accum_reset_spectral on every local rank"""
         self._ck(B.lib().srt_comm_accum_reset_spectral(self._h))
 
+    def accum_reset_streams(self, k):
+        """Renderer.accum_reset_streams on every local rank (any communicator: no decision crosses ranks)"""
+        self._ck(B.lib().srt_comm_accum_reset_streams(self._h, int(k)))
+
     def read_spectral(self, image_width, image_height, first=0, count=None):
         """the film of the frame (Renderer.read_spectral): on a single-process communicator (init_all) the sum of the local ranks' films,
         which is exact -- every pixel is owned by one rank and reads +0 on the others; on a process-per-GPU communicator (init_rank) THIS
@@ -488,6 +505,41 @@ def render_progressive(scene, cam, width, height, passes, bounce_limit, seed=198
 def _progressive_passes(scene, cam, width, height, sched, bounce_limit, seed, device, renderer):
     with _image_session(scene, cam, width, height, sum(sched), bounce_limit, seed, device, renderer) as r:
         r.accum_reset()
+        for spp_add in sched:
+            r.render_chunk_accum(width, height, spp_add)
+            r.scatter_tiles()
+            yield r.accum_samples, _collect(r, width, height)
+
+
+MAX_STREAMS = 16      # SRT_MAX_STREAMS (srt_c_api.h)
+
+
+def streams_schedule(passes, streams):
+    """progressive_schedule for a streamed accumulation of `streams` streams per pixel, checked as the library checks it (ValueError):
+    streams a whole number in [1, MAX_STREAMS] that divides every pass"""
+    if isinstance(streams, bool) or not isinstance(streams, (int, np.integer)) or not 1 <= streams <= MAX_STREAMS:
+        raise ValueError("render_streams: streams must be a whole number in [1, %d], got %r" % (MAX_STREAMS, streams))
+    sched = progressive_schedule(passes)
+    if any(s % streams for s in sched):
+        raise ValueError("render_streams: every pass must be a multiple of the %d streams (each draws pass / streams samples), got %r" % (streams, sched))
+    return sched
+
+
+def render_streams(scene, cam, width, height, passes, bounce_limit, streams, seed=1984, device=0, renderer=None):
+    """Progressive whole-image render with sample-parallel pixels on one GPU: a generator that renders passes[0], passes[1], ... samples
+    per pixel, split evenly over `streams` independent RNG streams per pixel, into one accumulation and yields (spp_total, result)
+    after each pass, as render_progressive does.  After the pass that brings the total to N, with n_lanes the lanes of the grid
+    (result["geom"]), the XYZ sums are ((S_0 + S_1) + S_2) + ... in float32, S_k the XYZ sums of
+    render_image(..., spp=N // streams, seed=seed + k * n_lanes), and the sRGB planes their plain conversion (srt_accum_reset_streams);
+    streams=1 is render_progressive bit for bit.  The schedule is checked here, when the generator is made, before any device is
+    touched."""
+    sched = streams_schedule(passes, streams)
+    return _streams_passes(scene, cam, width, height, sched, bounce_limit, int(streams), seed, device, renderer)
+
+
+def _streams_passes(scene, cam, width, height, sched, bounce_limit, streams, seed, device, renderer):
+    with _image_session(scene, cam, width, height, sum(sched), bounce_limit, seed, device, renderer) as r:
+        r.accum_reset_streams(streams)
         for spp_add in sched:
             r.render_chunk_accum(width, height, spp_add)
             r.scatter_tiles()

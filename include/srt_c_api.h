@@ -311,6 +311,41 @@ SRT_API int srt_read_accum_stats(srt_ctx *ctx, uint32_t *samples, float *sum_y, 
 SRT_API int srt_accum_reset_spectral(srt_ctx *ctx);
 SRT_API int srt_read_spectral(srt_ctx *ctx, uint32_t first, uint32_t count, float *out, uint32_t image_width, uint32_t image_height);
 
+/* Sample-parallel pixels (no reference counterpart; a deliberate departure from its one RNG stream per pixel, so opt-in).  A STREAMED
+ * accumulation gives every pixel K independent RNG streams, each with its own state and its own XYZ sum, so that any lane of any wave
+ * can render a stream while others render the pixel's other streams: the longest sequential chain of a pass is spp_add / K samples.
+ * Streams.  With n_lanes = tx * bx * ty * by of srt_init_device_params, stream k of lane idx is XORWOW(seed + k * n_lanes + idx): exactly
+ *   the state that lane has in a context initialised with seed_k = seed + k * n_lanes.  Stream 0 is the context's own RNG state.  Streams
+ *   1 .. K-1 are kept by the context (stream-major planes of K * n_lanes words), seeded from the seed of the last srt_init_device_params at
+ *   the first streamed reset after it, and they continue across resets and accumulations until the next srt_init_device_params, as
+ *   stream 0 does: stream k behaves as the RNG state of a context initialised with seed_k that has rendered the same launches.  (A reset
+ *   with ANOTHER K re-lays the planes and seeds streams 1 .. K-1 afresh from seed_k; stream 0 continues.)
+ * Passes.  srt_render_chunk_accum on a streamed accumulation needs spp_add % K == 0; every stream of every pixel of the chunk draws
+ *   spp_add / K samples.  srt_accum_samples reports the total over the streams, and the 65535 limit applies to that total.
+ * Result after passes totalling n samples.  S_k = the XYZ sum a plain accumulation (srt_accum_reset) of a context seeded seed_k holds
+ *   after n / K samples, same bits.  The pixel's sum is ((S_0 + S_1) + S_2) + ... + S_{K-1}, per component, fp32, not contracted: the XYZ
+ *   parity group, srt_read_accum_stats' sum_y and everything derived from them use it.  The unquantised and quantised sRGB planes are the
+ *   plain conversion of (1.0f / (float)n) * sum, the one every render launch applies.  So a K-stream frame is, bit for bit, a fixed-order
+ *   fp32 sum of K plain frames, and K = 1 equals srt_accum_reset in every output.  The result does not depend on partition, world size,
+ *   launch shape, queue order or the split into passes.  A plain srt_render_chunk after a streamed accumulation continues stream 0.
+ * Queue.  A pass runs the cost probe's queue with every row repeated K times, one copy per stream, the copies adjacent, so that the K
+ *   streams of an expensive tile start on K different workgroups (render_kernel MODE 6); a kernel after the pass adds the K sums of
+ *   every pixel in stream order and writes the tile buffer.  The probe itself walks a copy of stream 0, as ever.
+ *   srt_accum_reset_streams   srt_accum_reset + zeroed per-stream sum planes (12 B x K per lane of the grid) and the per-stream RNG states
+ *                             (24 B x K per lane), allocated on first use and when K or n_lanes grows.  1 <= K <= SRT_MAX_STREAMS.
+ *                             Refused with the previous accumulation unchanged: K == 0 or K > 16, device parameters not set, K x n_lanes
+ *                             >= 2^31 (SRT_ERR_INVALID); an instrumented context (SRT_ERR_UNSUPPORTED); a failed allocation (SRT_ERR_HIP).
+ *                             srt_accum_reset, srt_accum_reset_adaptive and srt_accum_reset_spectral make the next accumulation
+ *                             non-streamed again.  Streams combined with adaptive sampling or with the spectral film are NOT supported
+ *                             (adaptive streams are the obvious next step).  Invalidation and the chunk binding are those of
+ *                             srt_accum_reset.  A pass is refused with nothing changed on the device (SRT_ERR_INVALID) when spp_add is
+ *                             no multiple of K, the total would pass 65535, the chunk or offset is another one, or local tiles x K x 64
+ *                             reaches 2^32 (the queue's slot counter); srt_get_stats after a pass: paths = pixels x spp_add.
+ *   srt_accum_streams         K of the context's streamed accumulation; 0 when its accumulation is not streamed (or there is none). */
+#define SRT_MAX_STREAMS 16
+SRT_API int srt_accum_reset_streams(srt_ctx *ctx, uint32_t streams);
+SRT_API int srt_accum_streams(const srt_ctx *ctx, uint32_t *streams);
+
 /* Compact tile buffer of this rank (device memory): three plane GROUPS of tiles_padded * 3 * 64 floats each,
  * [group][tile][plane][lane] -- group 0 = quantised r,g,b (the reference's frame_buffer values, 12 B / pixel), group 1 =
  * unquantised sRGB r,g,b, group 2 = XYZ sums (parity planes).  tiles_padded = ceil(n_tiles/world), so every rank's buffer has
@@ -451,6 +486,9 @@ SRT_API int srt_comm_accum_active(srt_comm *comm, uint64_t *active);
 /* Spectral film on W GPUs: srt_accum_reset_spectral on every local context; srt_render_frame_multi_accum then runs MODE 5 on each rank.
  * The films stay with their ranks (srt_read_spectral per context; each pixel is owned by one rank and reads +0 on the others). */
 SRT_API int srt_comm_accum_reset_spectral(srt_comm *comm);
+/* Sample-parallel pixels on W GPUs: srt_accum_reset_streams on every local context; srt_render_frame_multi_accum then runs MODE 6 on each
+ * rank.  On process-per-GPU communicators too: no decision crosses ranks (every rank resets with the same K). */
+SRT_API int srt_comm_accum_reset_streams(srt_comm *comm, uint32_t streams);
 SRT_API int srt_comm_synchronize(srt_comm *comm);
 /* Closest-hit queries / paths of the last frame summed over the local ranks, and the slowest local render kernel. */
 SRT_API int srt_comm_stats(srt_comm *comm, uint64_t *rays, uint64_t *paths, float *max_kernel_ms);

@@ -1,4 +1,4 @@
-"""The skeleton of the accumulation cost tools (progressive_cost.py, adaptive_cost.py, spectral_cost.py): the headline workload
+"""The skeleton of the accumulation cost tools (progressive_cost.py, adaptive_cost.py, spectral_cost.py, streams_cost.py): the headline workload
 (random spheres, the throughput-tuned SAH tree, 1920x1080, depth 16) on one device context, the framebuffer checksum as bench.py
 prints it, the best of --reps measurements, and the report (printed, and written with --out)."""
 import argparse
@@ -14,10 +14,13 @@ srt = importlib.import_module("cuda-spectral-ray-tracer_amd")
 W, H, DEPTH = 1920, 1080, 16
 
 
-def parse_args():
+def parse_args(more=None):
+    """--reps and --out; more(parser) adds a tool's own arguments"""
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None, help="also write the report to this file")
+    if more:
+        more(ap)
     return ap.parse_args()
 
 
