@@ -60,7 +60,13 @@ class TreeTuning(C.Structure):
                 ("order_status", C.c_int32)]
 
 
-assert C.sizeof(Adaptive) == 16 and C.sizeof(TreeTuning) == 40
+class TileScheduleInfo(C.Structure):
+    """srt_tile_schedule_info: the scheduler's arguments for the context's pixel queue and what it answered (srt_c_api.h)"""
+    _fields_ = [("tiles_local", C.c_uint32), ("n_rows", C.c_uint32), ("cost_max", C.c_uint32), ("n_waves_plan", C.c_uint32),
+                ("split_load_pct", C.c_uint32), ("order_max_pct", C.c_uint32), ("streams", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(Adaptive) == 16 and C.sizeof(TreeTuning) == 40 and C.sizeof(TileScheduleInfo) == 32
 assert C.sizeof(Material) == 428 and C.sizeof(CameraData) == 84 and C.sizeof(TriIn) == 44
 
 # every symbol include/srt_c_api.h declares: name -> (restype, argtypes)
@@ -138,6 +144,8 @@ PROTOTYPES = {
     "srt_last_kernel_ms": (_i, [_vp, C.POINTER(_f)]),
     "srt_trace_rays": (_i, [_vp, _fp, _sz, _fp]),
     "srt_device_op_sweep": (_i, [_vp, _i, _fp, _fp, _sz, _fp]),
+    "srt_order_tiles_kat": (_i, [_vp, C.POINTER(_u32), _u32, _u32, _u32, _u32, C.POINTER(_u32), _sz, C.POINTER(_u32), C.POINTER(_u32)]),
+    "srt_read_tile_schedule": (_i, [_vp, _i, C.POINTER(_u32), _sz, C.POINTER(TileScheduleInfo)]),
     "srt_calibrate": (_i, [_vp, _i, _u32, _u32, C.POINTER(Calibration)]),
     "srt_ctx_device": (_i, [_vp]),
     "srt_ctx_cu_count": (_i, [_vp]),

@@ -101,6 +101,10 @@ struct srt_ctx {
     // env SRT_ORDER_MAX_PCT
     int order_max_pct = -1;
     DeviceBuffer d_tile_cost, d_tile_order;            // the cost probe's schedule (TileSchedule)
+    // what srt_read_tile_schedule reports: the scheduler's arguments, noted when the probe ran (n_rows and cost_max stay on the device),
+    // and which queues the LAST launch ran or left behind (choose_queue)
+    srt_tile_schedule_info sched_note = {};
+    bool sched_probe_queue = false, sched_compacted_queue = false;
     bool count_traversal = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
@@ -361,7 +365,11 @@ int run_cost_probe(srt_ctx *c, const Pass &ps, const RenderParams &p) {
     // constraints, with T the makespan of the UNsplit streams, are those of a machine of n_waves / K waves -- order_tiles_kernel)
     const uint32_t n_waves_plan = std::max<uint32_t>((uint32_t)c->n_cu * (uint32_t)ps.plan.waves_per_cu / ps.streams, 1u);
     const uint32_t order_pct = c->order_max_pct >= 0 ? (uint32_t)c->order_max_pct : ((!ps.plan.all_cached && (uint64_t)c->tiles_local < 6ull * n_waves_plan) ? 100u : 0u);
-    HIP_TRY(c, launch_order_tiles(sched.cost, sched.sorted, sched.rows, c->tiles_local, n_waves_plan, queue_may_split(c, ps.streams) ? c->split_load_pct : 0u, sched.info, order_pct, ps.st));   // device-side, no host sync
+    const uint32_t split_pct = queue_may_split(c, ps.streams) ? c->split_load_pct : 0u;
+    HIP_TRY(c, launch_order_tiles(sched.cost, sched.sorted, sched.rows, c->tiles_local, n_waves_plan, split_pct, sched.info, order_pct, ps.st));   // device-side, no host sync
+    c->sched_note = {};
+    c->sched_note.tiles_local = c->tiles_local; c->sched_note.n_waves_plan = n_waves_plan; c->sched_note.split_load_pct = split_pct;
+    c->sched_note.order_max_pct = order_pct; c->sched_note.streams = ps.streams;
     HIP_TRY(c, hipMemsetAsync(c->d_counters.as<unsigned long long>() + kCounters, 0, sizeof(unsigned long long), ps.st));   // rewind the queue head
     return SRT_OK;
 }
@@ -391,6 +399,7 @@ int choose_queue(srt_ctx *c, Pass &ps, RenderParams &p) {
     ps.adapt_bound = ps.ordered && c->split_load_pct ? split_rows_bound(c) : c->tiles_local;      // (adaptive passes are never streamed)
     if (ps.mode == Adaptive) HIP_TRY(c, c->d_adapt_queue.reserve(AdaptQueue::bytes(std::max<uint32_t>(ps.adapt_bound, 1u))));
     const QueueSource src = queue_source(c, ps);
+    c->sched_probe_queue = false; c->sched_compacted_queue = false;      // (srt_read_tile_schedule: set again below and by compact_adaptive_queue)
     if (src == QueueSource::Compacted) {
         const AdaptQueue q(c->d_adapt_queue);
         p.tile_order = q.rows;
@@ -406,6 +415,7 @@ int choose_queue(srt_ctx *c, Pass &ps, RenderParams &p) {
         p.prio_cost = sched.cost;      // wave priorities of the render launch (render_kernel, LDS-resident trees)
         if (queue_may_split(c, ps.streams)) p.queue_rows_bound = split_rows_bound(c);
     }
+    c->sched_probe_queue = ps.ordered && src != QueueSource::Identity;      // (a compacted queue of an ordered accumulation: the probe's is its source)
     p.queue_rows_bound *= ps.streams;      // (after the probe, which walks the tiles themselves)
     return SRT_OK;
 }
@@ -451,6 +461,7 @@ int compact_adaptive_queue(srt_ctx *c, const Pass &ps, const RenderParams &p) {
     q.lane_limit = c->debug_lane_limit ? c->debug_lane_limit : 64u;
     HIP_TRY(c, hipMemsetAsync(q.counts, 0, sizeof(unsigned long long), ps.st));
     HIP_TRY(c, launch_adapt_queue(q, ps.adapt_bound, ps.st));
+    c->sched_compacted_queue = true;
     return SRT_OK;
 }
 
@@ -589,6 +600,7 @@ const char *srt_last_error(const srt_ctx *ctx) { return ctx ? ctx->err.c_str() :
 int srt_upload_scene(srt_ctx *c, const srt_scene *s) {
     if (!c || !s) return fail(c, SRT_ERR_INVALID, "srt_upload_scene: null argument");
     c->accum.invalidate();
+    c->sched_probe_queue = false; c->sched_compacted_queue = false;      // (the queues of the last launch belong to the old set-up)
     HIP_TRY(c, hipSetDevice(c->device));
     FlatScene f;
     int rc = flatten_scene(*s, f);
@@ -685,6 +697,7 @@ int srt_internal_init_device_params(srt_ctx *c, uint32_t tx, uint32_t ty, uint32
     if (tx == 0 || ty == 0 || bx == 0 || by == 0 || chunk_w == 0 || chunk_h == 0)
         return fail(c, SRT_ERR_INVALID, "srt_init_device_params: zero dimension");
     c->accum.invalidate();
+    c->sched_probe_queue = false; c->sched_compacted_queue = false;      // (the queues of the last launch belong to the old set-up)
     const uint64_t lanes = (uint64_t)tx * ty * bx * by;
     if (lanes > 0x7fffffffull) return fail(c, SRT_ERR_INVALID, "srt_init_device_params: grid too large");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -711,6 +724,7 @@ int srt_init_device_params(srt_ctx *c, uint32_t tx, uint32_t ty, uint32_t bx, ui
 int srt_set_partition(srt_ctx *c, uint32_t rank, uint32_t world) {
     if (!c || world == 0 || rank >= world) return fail(c, SRT_ERR_INVALID, "srt_set_partition: need rank < world");
     c->accum.invalidate();
+    c->sched_probe_queue = false; c->sched_compacted_queue = false;      // (the queues of the last launch belong to the old set-up)
     c->rank = rank; c->world = world;
     return SRT_OK;
 }
@@ -1240,6 +1254,51 @@ int srt_device_op_sweep(srt_ctx *c, int which, const float *a, const float *b, s
     HIP_TRY_AS(c, "srt_device_op_sweep", launch_op_sweep(which, d, d + n, n, d + 2 * n, nullptr));
     HIP_TRY_AS(c, "srt_device_op_sweep", hipDeviceSynchronize());
     HIP_TRY_AS(c, "srt_device_op_sweep", hipMemcpy(out, d + 2 * n, n * sizeof(float), hipMemcpyDeviceToHost));
+    return SRT_OK;
+}
+
+int srt_order_tiles_kat(srt_ctx *c, const uint32_t *cost, uint32_t n, uint32_t n_waves, uint32_t split_load_pct, uint32_t order_max_pct,
+                        uint32_t *rows_out, size_t rows_cap, uint32_t *sorted_out, uint32_t *info_out) {
+    if (!c || !cost || !rows_out || !sorted_out || !info_out) return fail(c, SRT_ERR_INVALID, "srt_order_tiles_kat: null argument");
+    // (beyond 2^20 tiles the kernel must not split; one that wrongly did would write past any buffer sized for what it should do)
+    if (n == 0 || n > (1u << 20)) return fail(c, SRT_ERR_INVALID, "srt_order_tiles_kat: n must be in 1 .. 2^20");
+    if (rows_cap < (size_t)n * 64 + 64) return fail(c, SRT_ERR_INVALID, "srt_order_tiles_kat: rows_cap must be at least 64 * n + 64 (the largest queue and 64 guard words)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    DeviceBuffer d_cost, d_rows, d_sorted, d_info;
+    HIP_TRY_AS(c, "srt_order_tiles_kat", d_cost.reserve(TileSchedule::cost_bytes(n)));
+    HIP_TRY_AS(c, "srt_order_tiles_kat", d_rows.reserve(rows_cap * sizeof(uint32_t)));
+    HIP_TRY_AS(c, "srt_order_tiles_kat", d_sorted.reserve(n * sizeof(uint32_t)));
+    HIP_TRY_AS(c, "srt_order_tiles_kat", d_info.reserve(4 * sizeof(uint32_t)));
+    HIP_TRY_AS(c, "srt_order_tiles_kat", hipMemcpy(d_cost.ptr, cost, TileSchedule::cost_bytes(n), hipMemcpyHostToDevice));
+    HIP_TRY_AS(c, "srt_order_tiles_kat", hipMemset(d_rows.ptr, 0xff, rows_cap * sizeof(uint32_t)));      // unwritten words stay visible
+    HIP_TRY_AS(c, "srt_order_tiles_kat", hipMemset(d_sorted.ptr, 0xff, n * sizeof(uint32_t)));
+    HIP_TRY_AS(c, "srt_order_tiles_kat", hipMemset(d_info.ptr, 0xff, 4 * sizeof(uint32_t)));
+    HIP_TRY_AS(c, "srt_order_tiles_kat", launch_order_tiles(d_cost.as<uint32_t>(), d_sorted.as<uint32_t>(), d_rows.as<uint32_t>(), n, n_waves, split_load_pct,
+                                                            d_info.as<uint32_t>(), order_max_pct, nullptr));
+    HIP_TRY_AS(c, "srt_order_tiles_kat", hipDeviceSynchronize());
+    HIP_TRY_AS(c, "srt_order_tiles_kat", hipMemcpy(rows_out, d_rows.ptr, rows_cap * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY_AS(c, "srt_order_tiles_kat", hipMemcpy(sorted_out, d_sorted.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY_AS(c, "srt_order_tiles_kat", hipMemcpy(info_out, d_info.ptr, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return SRT_OK;
+}
+
+int srt_read_tile_schedule(srt_ctx *c, int which, uint32_t *rows_out, size_t rows_cap, srt_tile_schedule_info *info) {
+    if (!c || !info || (!rows_out && rows_cap) || (which != 0 && which != 1)) return fail(c, SRT_ERR_INVALID, "srt_read_tile_schedule: bad argument");
+    if (which == 0 ? !c->sched_probe_queue : !c->sched_compacted_queue)
+        return fail(c, SRT_ERR_INVALID, which == 0 ? "srt_read_tile_schedule: the last launch ran no cost probe's queue (no probe, or too few samples or tiles for one)"
+                                                   : "srt_read_tile_schedule: the last launch was no adaptive pass: no compacted queue");
+    if (const int rc = srt_synchronize(c)) return rc;
+    const uint32_t *d_rows = which == 0 ? TileSchedule(c).rows : AdaptQueue(c->d_adapt_queue).rows;
+    const uint32_t *d_info = which == 0 ? TileSchedule(c).info : AdaptQueue(c->d_adapt_queue).info;
+    uint32_t head[2] = {0u, 0u};      // queue_info: rows, the largest tile cost
+    HIP_TRY(c, hipMemcpy(head, d_info, sizeof(head), hipMemcpyDeviceToHost));
+    // (a compacted queue of an accumulation that runs unordered has the identity order as its source: no probe, nothing noted)
+    srt_tile_schedule_info out = c->sched_probe_queue ? c->sched_note : srt_tile_schedule_info{};
+    if (!c->sched_probe_queue) { out.tiles_local = c->tiles_local; out.streams = 1u; }
+    out.n_rows = head[0]; out.cost_max = head[1];
+    if (rows_cap < out.n_rows) return fail(c, SRT_ERR_INVALID, "srt_read_tile_schedule: rows_cap is smaller than the queue");
+    if (out.n_rows) HIP_TRY(c, hipMemcpy(rows_out, d_rows, (size_t)out.n_rows * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    *info = out;
     return SRT_OK;
 }
 

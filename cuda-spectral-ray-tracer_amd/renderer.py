@@ -259,6 +259,27 @@ class Renderer:
         self._ck(B.lib().srt_device_op_sweep(self._h, which, B.fptr(a), B.fptr(b), a.size, B.fptr(out)))
         return out
 
+    def order_tiles_kat(self, cost, n_waves, split_load_pct=200, order_max_pct=0, guard=64):
+        """the tile scheduler on explicit costs (srt_order_tiles_kat): cost = uint32[2 n], per-tile cost then the cost of each tile's most
+        expensive pixel.  Returns (rows, sorted, info): the whole row buffer of 64 n + guard words, every word 0xffffffff before the
+        kernel ran; the n tiles in queue order; [rows written, largest tile cost, 2 unused words]"""
+        cost = np.ascontiguousarray(cost, np.uint32)
+        n = cost.size // 2
+        u32p = C.POINTER(C.c_uint32)
+        rows, order, info = np.zeros(64 * n + guard, np.uint32), np.zeros(n, np.uint32), np.zeros(4, np.uint32)
+        self._ck(B.lib().srt_order_tiles_kat(self._h, cost.ctypes.data_as(u32p), n, int(n_waves), int(split_load_pct), int(order_max_pct),
+                                             rows.ctypes.data_as(u32p), rows.size, order.ctypes.data_as(u32p), info.ctypes.data_as(u32p)))
+        return rows, order, info
+
+    def tile_schedule(self, which=0):
+        """the pixel queue of the last launch (srt_read_tile_schedule): which = 0 the cost probe's, which = 1 the compacted queue an
+        adaptive pass left for the next one.  Returns (rows, info): uint32 queue rows and a dict of srt_tile_schedule_info's fields.
+        SrtError when the last launch has no such queue.  Synchronises."""
+        _, _, tl, _ = self.tile_buffer()
+        rows, info = np.zeros(64 * tl, np.uint32), B.TileScheduleInfo()
+        self._ck(B.lib().srt_read_tile_schedule(self._h, int(which), rows.ctypes.data_as(C.POINTER(C.c_uint32)), rows.size, C.byref(info)))
+        return rows[:info.n_rows].copy(), {name: getattr(info, name) for name, _ in B.TileScheduleInfo._fields_ if name != "reserved"}
+
 
 class Comm:
     """Multi-GPU communicator (srt_comm): W ranks render interleaved 8x8 tiles of a chunk, one RCCL gather to rank 0.

@@ -427,6 +427,31 @@ SRT_API int srt_trace_rays(srt_ctx *ctx, const float *rays, size_t n, float *out
 /* Device arithmetic self-test: evaluates op `which` on n operand pairs on the GPU (see DESIGN.md "primitive-op
  * sweep"); used to prove the device's + - * / sqrt fmin cast and srt_powf bits equal the host's. */
 SRT_API int srt_device_op_sweep(srt_ctx *ctx, int which, const float *a, const float *b, size_t n, float *out);
+/* The tile scheduler on explicit costs -- KAT entry point (no reference counterpart: the pixel queue is scheduling only).  Runs the
+ * kernel that builds a launch's pixel queue on cost[2 * n] (per-tile cost, then the cost of each tile's most expensive pixel) for a
+ * machine of n_waves waves, in buffers of its own: the context's schedule is not touched.  rows_out receives rows_cap words of a row
+ * buffer that held 0xffffffff in every word before the kernel ran (row = local tile | part << 22 | level << 28), sorted_out the n
+ * tile numbers in queue order, info_out 4 words: [0] the number of rows, [1] the largest tile cost.  SRT_ERR_INVALID, with nothing
+ * enqueued, for n == 0, n > 2^20 (beyond that the scheduler never splits; left out here) and rows_cap < 64 * n + 64 (the largest
+ * possible queue and 64 guard words behind it). */
+SRT_API int srt_order_tiles_kat(srt_ctx *ctx, const uint32_t *cost, uint32_t n, uint32_t n_waves, uint32_t split_load_pct,
+                                uint32_t order_max_pct, uint32_t *rows_out, size_t rows_cap, uint32_t *sorted_out, uint32_t *info_out);
+/* What the host knew when the cost probe built the context's current schedule (srt_read_tile_schedule). */
+typedef struct srt_tile_schedule_info {
+    uint32_t tiles_local;         /* local tiles the probe measured */
+    uint32_t n_rows;              /* rows of the queue that was read (filled in from the device) */
+    uint32_t cost_max;            /* the largest tile cost, as the render kernel's wave priorities see it (from the device) */
+    uint32_t n_waves_plan;        /* waves of the machine the split policy planned for (a streamed pass: divided by its streams) */
+    uint32_t split_load_pct;      /* as passed to the scheduler: 0 when the launch may not split */
+    uint32_t order_max_pct;       /* as passed to the scheduler */
+    uint32_t streams;             /* RNG streams per pixel of the pass that ran the probe (1 unless streamed) */
+    uint32_t reserved;
+} srt_tile_schedule_info;
+/* The pixel queue a launch ran -- tests and diagnostics, like srt_get_tile_costs; synchronises.  which = 0: the queue the cost probe
+ * built for the last launch (or for the accumulation that launch belongs to); which = 1: the compacted queue the last adaptive pass
+ * left for the next one.  Copies info->n_rows rows to rows_out.  SRT_ERR_INVALID when the last launch has no such queue or rows_cap
+ * is smaller than its row count. */
+SRT_API int srt_read_tile_schedule(srt_ctx *ctx, int which, uint32_t *rows_out, size_t rows_cap, srt_tile_schedule_info *info);
 
 SRT_API int srt_ctx_device(const srt_ctx *ctx);                 /* HIP device index of the context */
 /* compute units of the context's GPU (a render launch keeps srt_launch_plan's waves_per_cu x 64 pixels in flight on each) */
