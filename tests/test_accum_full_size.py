@@ -6,13 +6,11 @@ Every case asserts the size property that makes it worth running, so that a chan
 into a small-frame test.  The references are those of the small-frame suites: one-shot frames (themselves held to the oracle and
 the frozen digests), the numpy float32 restatement of every stop decision, the oracle on 28 x 16 blocks, and the contraction of the
 film to the XYZ sums."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
-from accum_helpers import (MIN_SPP, N_GRID, NEVER, SCHED, _adaptive, _assert_pixels_equal, _assert_same_image, _frame, _fresh, _lane_of,
-                           _pick_tolerance, _predict, _spectral, gpu_lib, run_mock_transport_child)
+from accum_helpers import (MIN_SPP, NEVER, N_GRID, SCHED, adaptive_run, assert_pixels_equal, assert_same_image, fresh_context, gather_ranks,
+                           lane_of, pick_tolerance, predict_stops, read_frame, read_sum_y, run_mock_transport_child, spectral_run)
 from helpers import _blocks_bit_exact, assert_planes_equal, bits, oracle_scene_for
 
 pytestmark = pytest.mark.gpu
@@ -83,7 +81,7 @@ def _contract_and_check(srt, r, W, H, frame, what, step=5, other=None, full=None
             del want
         got += part.astype(np.float64) @ rows[first:first + count]
         del part
-    want = _xyz_rowmajor(frame, _lane_of(r.geom, W, H), W, H)
+    want = _xyz_rowmajor(frame, lane_of(r.geom, W, H), W, H)
     _assert_xyz_close(got, want, what)
     if edges:
         _assert_xyz_close(got[-8:], want[-8:], what + ": the last 8 rows")
@@ -95,7 +93,7 @@ def _blocks_at_counts(r, orc, scene, mode, cam, W, H, depth, frame, counts, bloc
     bit in the quantised and XYZ planes"""
     g = r.geom
     lane_counts = np.zeros(g["n_lanes"], np.int64)
-    lane_counts[_lane_of(g, W, H)] = counts
+    lane_counts[lane_of(g, W, H)] = counts
     blocks = list(range(block_lo, g["bx"] * g["by"], stride))
     assert 1 <= len(blocks) <= max_blocks, blocks
     osc = oracle_scene_for(orc, scene, mode)
@@ -115,9 +113,9 @@ def _blocks_at_counts(r, orc, scene, mode, cam, W, H, depth, frame, counts, bloc
 
 
 def _check_adaptive_run(srt, r, run, never, rel, scene, cam, W, H, depth, one_shots, what):
-    """run (accum_helpers._adaptive) against the float32 restatement: samples map and active count after every pass, the paths of
+    """run (accum_helpers.adaptive_run) against the float32 restatement: samples map and active count after every pass, the paths of
     every pass; and every pixel against the one-shot frame of its count (one_shots: count -> frame, filled on demand)"""
-    maps, _, actives = _predict(never, rel)
+    maps, _, actives = predict_stops(never, rel)
     before = W * H
     for k, (p, want, act) in enumerate(zip(run, maps, actives)):
         got = p["stats"]["samples"]
@@ -127,12 +125,12 @@ def _check_adaptive_run(srt, r, run, never, rel, scene, cam, W, H, depth, one_sh
         before = act
     last = run[-1]
     counts = last["stats"]["samples"]
-    lane = _lane_of(r.geom, W, H)
+    lane = lane_of(r.geom, W, H)
     for c in np.unique(counts):
         if int(c) not in one_shots:
             one_shots[int(c)] = srt.render_image(scene, cam, W, H, int(c), depth, renderer=r)
         mask = counts == c
-        _assert_pixels_equal(last["frame"], one_shots[int(c)], mask, lane, "%s: %d pixels at %d spp" % (what, mask.sum(), c))
+        assert_pixels_equal(last["frame"], one_shots[int(c)], mask, lane, "%s: %d pixels at %d spp" % (what, mask.sum(), c))
     return counts
 
 
@@ -146,16 +144,16 @@ def _lean(run):
 @pytest.fixture(scope="module")
 def headline(srt, gpu):
     """the headline scene at 1080p: a never-stopping adaptive run of SCHED (its sums at every boundary are those of every run), the
-    tolerance _pick_tolerance takes, and one under which about 1 % of the pixels render in the last pass"""
+    tolerance pick_tolerance takes, and one under which about 1 % of the pixels render in the last pass"""
     scene = _headline_scene(srt)
     cam = scene.default_camera(HW, HH)
-    never = _lean(_adaptive(gpu, scene, cam, HW, HH, HDEPTH, NEVER))
+    never = _lean(adaptive_run(gpu, scene, cam, HW, HH, HDEPTH, NEVER))
     never[-1].pop("frame")
-    rel = _pick_tolerance(never)
+    rel = pick_tolerance(never)
     n = HW * HH
     best, best_d = None, None
     for cand in np.geomspace(1e-4, 10.0, 241):
-        _, _, actives = _predict(never, float(cand))
+        _, _, actives = predict_stops(never, float(cand))
         d = abs(actives[-2] / n - 0.01)          # the queue the last pass renders from
         if actives[-1] > 0 and (best is None or d < best_d):
             best, best_d = float(cand), d
@@ -171,7 +169,7 @@ def test_headline_frame_checksum_through_every_accumulating_mode(srt, gpu):
     assert sum(HEADLINE_PASSES) == HSPP and len(set(HEADLINE_PASSES)) == len(HEADLINE_PASSES)
 
     # plain (MODE 3)
-    _fresh(gpu, scene, cam, HW, HH, HDEPTH, spp=HSPP)
+    fresh_context(gpu, scene, cam, HW, HH, HDEPTH, spp=HSPP)
     gpu.accum_reset()
     for s in HEADLINE_PASSES:
         gpu.render_chunk_accum(HW, HH, s)
@@ -182,7 +180,7 @@ def test_headline_frame_checksum_through_every_accumulating_mode(srt, gpu):
     assert _tiles_local(gpu) > 4096
 
     # adaptive (MODE 4) with a tolerance nothing meets: every pixel renders every pass
-    _fresh(gpu, scene, cam, HW, HH, HDEPTH, spp=HSPP)
+    fresh_context(gpu, scene, cam, HW, HH, HDEPTH, spp=HSPP)
     gpu.accum_reset_adaptive(NEVER, 0.0, MIN_SPP)
     for s in HEADLINE_PASSES:
         gpu.render_chunk_accum(HW, HH, s)
@@ -194,13 +192,13 @@ def test_headline_frame_checksum_through_every_accumulating_mode(srt, gpu):
     assert _checksum(gpu) == HEADLINE_CHECKSUM, "adaptive accumulation, rel_tol = NEVER"
 
     # spectral (MODE 5): the checksum, and the film (807 MB) contracts to the XYZ sums
-    _fresh(gpu, scene, cam, HW, HH, HDEPTH, spp=HSPP)
+    fresh_context(gpu, scene, cam, HW, HH, HDEPTH, spp=HSPP)
     gpu.accum_reset_spectral()
     for s in HEADLINE_PASSES:
         gpu.render_chunk_accum(HW, HH, s)
         assert gpu.stats()["paths"] == n_pix * s
     assert _film_bytes(gpu) > 2 ** 29
-    frame = _frame(gpu, HW, HH)
+    frame = read_frame(gpu, HW, HH)
     assert _checksum(gpu) == HEADLINE_CHECKSUM, "spectral accumulation"
     full = gpu.read_spectral(HW, HH)
     _contract_and_check(srt, gpu, HW, HH, frame, "headline film", step=5, full=full)
@@ -221,7 +219,7 @@ def test_adaptive_full_size_queues(srt, orc, headline, monkeypatch, env, kind):
     The ordered queue holds at least one row per tile, so adapt_scan_kernel's threads compact runs of several rows.  With splitting
     on (SRT_SPLIT_LOAD, default 200) the queue is bounded by 64 rows per tile and its rows carry the part / split-level fields of a
     split tile (whether order_tiles_kernel actually splits a tile here depends on the probe's costs: it is not visible through the
-    C-ABI).  Each run: the tolerance _pick_tolerance takes, and one under which about 1 % of the pixels stay active, so that the
+    C-ABI).  Each run: the tolerance pick_tolerance takes, and one under which about 1 % of the pixels stay active, so that the
     queue of the last pass is long, sparse and interleaved."""
     for k in ("SRT_SPLIT_LOAD", "SRT_PROBE_SPP"):
         monkeypatch.delenv(k, raising=False)
@@ -233,7 +231,7 @@ def test_adaptive_full_size_queues(srt, orc, headline, monkeypatch, env, kind):
         one_shots = {}
         for rel, tag in ((headline["rel"], "picked tolerance"), (headline["rel_sparse"], "~1 % active")):
             what = "%s queue, %s" % (kind, tag)
-            run = _lean(_adaptive(r, scene, cam, HW, HH, HDEPTH, rel))
+            run = _lean(adaptive_run(r, scene, cam, HW, HH, HDEPTH, rel))
             tiles = _tiles_local(r)
             assert tiles > 4096, tiles                     # the identity queue's rows; a lower bound of the ordered queue's
             assert -(-tiles // 1024) > 1                   # adapt_scan_kernel: rows per thread
@@ -261,38 +259,38 @@ def test_mesh100k_4k_partly_cached_shape(srt, gpu, orc):
     assert not plan["all_cached"] and plan["n_cached"] > 0 and not plan["narrow_refs"], plan
 
     # progressive split == one-shot, and the one-shot's blocks against the oracle (_blocks_bit_exact renders it)
-    _fresh(gpu, scene, cam, W, H, depth, spp=8)
+    fresh_context(gpu, scene, cam, W, H, depth, spp=8)
     gpu.accum_reset()
     for s in (3, 5):
         gpu.render_chunk_accum(W, H, s)
         assert gpu.stats()["paths"] == W * H * s
-    split = _frame(gpu, W, H)
+    split = read_frame(gpu, W, H)
     assert _tiles_local(gpu) > 4096
     assert _blocks_bit_exact(srt, gpu, orc, srt.SCENE_MESH100K, srt.BVH_SAH, W, H, 8, depth, 2000, 4100, 6) >= 4
     one_shot = dict(fb=gpu.read_fb(), lin=gpu.read_fb_aux(1), xyz=gpu.read_fb_aux(2), rowmajor=gpu.read_fb_rowmajor(W, H))
-    _assert_same_image(split, one_shot, "4K mesh [3, 5] vs one-shot 8 spp")
+    assert_same_image(split, one_shot, "4K mesh [3, 5] vs one-shot 8 spp")
     del split, one_shot
     gpu.upload_scene(scene)
     assert not gpu.launch_plan()["all_cached"]
 
     # adaptive, as in the 1080p test (a shorter schedule)
     sched = [8, 4, 4]
-    never = _lean(_adaptive(gpu, scene, cam, W, H, depth, NEVER, sched=sched))
+    never = _lean(adaptive_run(gpu, scene, cam, W, H, depth, NEVER, sched=sched))
     never[-1].pop("frame")
-    rel = _pick_tolerance(never)
-    run = _lean(_adaptive(gpu, scene, cam, W, H, depth, rel, sched=sched))
+    rel = pick_tolerance(never)
+    run = _lean(adaptive_run(gpu, scene, cam, W, H, depth, rel, sched=sched))
     counts = _check_adaptive_run(srt, gpu, run, never, rel, scene, cam, W, H, depth, {}, "4K mesh adaptive")
     assert len(np.unique(counts)) >= 2, np.unique(counts)
     _blocks_at_counts(gpu, orc, scene, srt.BVH_SAH, cam, W, H, depth, run[-1]["frame"], counts, 3001, 9000, 2)
     del run
 
     # spectral: a 3.2 GB film contracts to the XYZ sums
-    _fresh(gpu, scene, cam, W, H, depth, spp=4)
+    fresh_context(gpu, scene, cam, W, H, depth, spp=4)
     gpu.accum_reset_spectral()
     for s in (2, 2):
         gpu.render_chunk_accum(W, H, s)
     assert _film_bytes(gpu) > 2 ** 31
-    _contract_and_check(srt, gpu, W, H, _frame(gpu, W, H), "4K mesh film", edges=False)    # (its bottom rows are black)
+    _contract_and_check(srt, gpu, W, H, read_frame(gpu, W, H), "4K mesh film", edges=False)    # (its bottom rows are black)
 
 
 # ---- 4. a film of more than 2^32 bytes ------------------------------------------------------------------------------------
@@ -306,24 +304,24 @@ def test_film_above_4_gib(srt, gpu):
     cam = scene.default_camera(W, H)
     other = srt.Renderer(0)
     try:
-        _fresh(other, scene, cam, W, H, depth, spp=2)
+        fresh_context(other, scene, cam, W, H, depth, spp=2)
         other.accum_reset_spectral()
         other.render_chunk_accum(W, H, 2)
-        _fresh(gpu, scene, cam, W, H, depth, spp=2)
+        fresh_context(gpu, scene, cam, W, H, depth, spp=2)
         gpu.accum_reset_spectral()
         for s in (1, 1):
             gpu.render_chunk_accum(W, H, s)
         assert _film_bytes(gpu) > 2 ** 32, _film_bytes(gpu)
-        last_lane = int(_lane_of(gpu.geom, W, H)[-1])
+        last_lane = int(lane_of(gpu.geom, W, H)[-1])
         assert last_lane * FILM_BYTES_PER_LANE > 2 ** 32                  # the last pixel's row lies past 2^32 bytes
-        _contract_and_check(srt, gpu, W, H, _frame(gpu, W, H), "4.6 GB film", step=5, other=other)
+        _contract_and_check(srt, gpu, W, H, read_frame(gpu, W, H), "4.6 GB film", step=5, other=other)
     finally:
         other.close()
 
     # a 1000 x 600 chunk at the bottom-right corner of the 4608 x 2592 image
     cw, ch = 1000, 600
     ox, oy = W - cw - 3, H - ch - 5
-    _fresh(gpu, scene, cam, cw, ch, depth, spp=2)
+    fresh_context(gpu, scene, cam, cw, ch, depth, spp=2)
     gpu.accum_reset_spectral()
     gpu.render_chunk_accum(cw, ch, 2, ox, oy)
     inside = np.zeros((H, W), bool)
@@ -340,31 +338,12 @@ def test_film_above_4_gib(srt, gpu):
         assert (part[~inside] == 0).all(), first
         got_y += part[inside].astype(np.float64) @ rows[first:first + part.shape[-1], 1]
         del part
-    y = np.zeros(W * H, np.float32)          # the Y sums (srt_read_accum_stats: a spectral accumulation has no sample map)
-    gpu._ck(gpu_lib().srt_read_accum_stats(gpu._h, None, y.ctypes.data_as(C.POINTER(C.c_float)), None, W, H))
-    want_y = y.reshape(H, W)[inside].astype(np.float64)
+    want_y = read_sum_y(gpu, W, H).reshape(H, W)[inside].astype(np.float64)      # (a spectral accumulation has no sample map)
     assert want_y.max() > 0
     np.testing.assert_allclose(got_y, want_y, rtol=2e-4, atol=1e-9)
 
 
 # ---- 5. partitions and the communicator at full size ---------------------------------------------------------------------
-
-def _gather_scatter(gpu, parts):
-    import torch
-    gathered = torch.from_numpy(np.concatenate(parts)).cuda()
-    gpu.scatter_tiles(gathered.data_ptr())
-    gpu.synchronize()
-
-
-def _tile_buffer_copy(gpu):
-    import torch
-    gpu.synchronize()
-    _, n_floats, _, _ = gpu.tile_buffer()
-    staging = torch.empty(n_floats, dtype=torch.float32, device="cuda")
-    gpu.copy_tile_buffer(staging.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    return staging.cpu().numpy().copy()
-
 
 def _owner_mask(W, H, geom, rank, world):
     """row-major pixels whose 8 x 8 tile belongs to `rank` (tile % world, tiles over the reference grid's cover)"""
@@ -378,34 +357,30 @@ def test_partitions_full_size(srt, gpu, headline, world):
     """ragged tile shares (32 912 tiles over 3 or 7 ranks): the merged adaptive frame, its samples map and active count, and the
     merged spectral frame and film are bit-identical to world 1"""
     scene, cam, rel = headline["scene"], headline["cam"], headline["rel"]
-    ref = _adaptive(gpu, scene, cam, HW, HH, HDEPTH, rel)[-1]
-    parts, samples, active = [], np.zeros(HW * HH, np.uint32), 0
-    for rank in range(world):
-        _fresh(gpu, scene, cam, HW, HH, HDEPTH)
+    ref = adaptive_run(gpu, scene, cam, HW, HH, HDEPTH, rel)[-1]
+
+    def adaptive_rank(rank):
+        fresh_context(gpu, scene, cam, HW, HH, HDEPTH)
         gpu.set_partition(rank, world)
         gpu.accum_reset_adaptive(rel, 0.0, MIN_SPP)
         for s in SCHED:
             gpu.render_chunk_accum(HW, HH, s)
         assert _tiles_local(gpu) > 4096
-        samples += gpu.accum_stats(HW, HH)["samples"]
-        active += gpu.accum_active
-        parts.append(_tile_buffer_copy(gpu))
-    _gather_scatter(gpu, parts)
-    del parts
-    assert np.array_equal(samples, ref["stats"]["samples"]), world
-    assert active == ref["active"], world
+        return gpu.accum_stats(HW, HH)["samples"], gpu.accum_active
+    samples, actives = zip(*gather_ranks(gpu, world, adaptive_rank))
+    assert np.array_equal(sum(samples), ref["stats"]["samples"]), world
+    assert sum(actives) == ref["active"], world
     assert_planes_equal(gpu.read_fb(), ref["frame"]["fb"], "adaptive world %d fb" % world)
     assert_planes_equal(gpu.read_fb_aux(1), ref["frame"]["lin"], "adaptive world %d lin" % world)
     assert_planes_equal(gpu.read_fb_aux(2), ref["frame"]["xyz"], "adaptive world %d xyz" % world)
-    gpu.set_partition(0, 1)
     del ref
 
     passes = [4, 8]
-    ref_frame, ref_film = _spectral(gpu, scene, cam, HW, HH, HDEPTH, passes)
+    ref_frame, ref_film = spectral_run(gpu, scene, cam, HW, HH, HDEPTH, passes)
     assert ref_film.max() > 0
-    parts = []
-    for rank in range(world):
-        _fresh(gpu, scene, cam, HW, HH, HDEPTH)
+
+    def spectral_rank(rank):
+        fresh_context(gpu, scene, cam, HW, HH, HDEPTH)
         gpu.set_partition(rank, world)
         gpu.accum_reset_spectral()
         for s in passes:
@@ -414,13 +389,10 @@ def test_partitions_full_size(srt, gpu, headline, world):
         own = _owner_mask(HW, HH, gpu.geom, rank, world)
         assert np.array_equal(bits(film[own]), bits(ref_film[own])), (world, rank)
         assert (bits(film[~own]) == 0).all(), (world, rank)
-        del film
-        parts.append(_tile_buffer_copy(gpu))
-    _gather_scatter(gpu, parts)
+    gather_ranks(gpu, world, spectral_rank)
     for k, i in (("fb", 0), ("lin", 1), ("xyz", 2)):
         got = gpu.read_fb() if i == 0 else gpu.read_fb_aux(i)
         assert_planes_equal(got, ref_frame[k], "spectral world %d %s" % (world, k))
-    gpu.set_partition(0, 1)
 
 
 def test_comm_three_ranks_full_size_mock_transport(headline):

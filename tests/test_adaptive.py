@@ -7,29 +7,29 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from accum_helpers import (ERR_INVALID, ERR_UNSUPPORTED, EVERY_SHAPE_CASES, EVERY_SHAPE_IDS, MIN_SPP, NEVER, SCHED, _adaptive,
-                           _assert_pixels_equal, _expect_error, _frame, _fresh, _lane_of, _pick_tolerance, _predict, _soup, _sum_y,
-                           _workload, gpu_lib, run_mock_transport_child)
+from accum_helpers import (ERR_INVALID, ERR_UNSUPPORTED, EVERY_SHAPE_CASES, EVERY_SHAPE_IDS, MIN_SPP, NEVER, SCHED, adaptive_run,
+                           assert_pixels_equal, expect_error, forced_shape, fresh_context, gather_ranks, gpu_lib, lane_of, named_workload,
+                           pick_tolerance, predict_stops, read_frame, read_sum_y, run_mock_transport_child, shape_case)
 from helpers import assert_planes_equal, bits, oracle_scene_for
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["prism", "cornell", "random_spheres", "dielectric"])
 def test_each_pixel_equals_the_one_shot_frame_of_its_count(srt, gpu, orc, name):
-    scene, cam, W, H, depth, mode = _workload(srt, name)
-    never = _adaptive(gpu, scene, cam, W, H, depth, NEVER)
-    rel = _pick_tolerance(never)
-    run = _adaptive(gpu, scene, cam, W, H, depth, rel)
+    scene, cam, W, H, depth, mode = named_workload(srt, name)
+    never = adaptive_run(gpu, scene, cam, W, H, depth, NEVER)
+    rel = pick_tolerance(never)
+    run = adaptive_run(gpu, scene, cam, W, H, depth, rel)
     last = run[-1]
     counts = last["stats"]["samples"]
     assert last["total"] == sum(SCHED) and last["active"] > 0
     assert len(np.unique(counts)) >= 3, np.unique(counts)
-    lane = _lane_of(gpu.geom, W, H)
+    lane = lane_of(gpu.geom, W, H)
     osc = oracle_scene_for(orc, scene, mode) if name in ("prism", "cornell") else None
     for c in np.unique(counts):
         mask = counts == c
         one_shot = srt.render_image(scene, cam, W, H, int(c), depth, renderer=gpu)
-        _assert_pixels_equal(last["frame"], one_shot, mask, lane, "%s: %d pixels at %d spp" % (name, mask.sum(), c))
+        assert_pixels_equal(last["frame"], one_shot, mask, lane, "%s: %d pixels at %d spp" % (name, mask.sum(), c))
         if osc is not None:
             ref = osc.render(cam, W, H, int(c), depth)
             for k in ("fb", "lin", "xyz"):
@@ -42,11 +42,11 @@ def test_each_pixel_equals_the_one_shot_frame_of_its_count(srt, gpu, orc, name):
 def test_decisions_match_the_float32_restatement(srt, gpu, name):
     """which pixels stop at which boundary, after every pass, with no tolerance; and the sums a pixel holds are those of the run that
     never stops at the same count (S1, S2 exact across runs)"""
-    scene, cam, W, H, depth, _ = _workload(srt, name)
-    never = _adaptive(gpu, scene, cam, W, H, depth, NEVER)
-    for rel, ab in ((_pick_tolerance(never), 0.0), (0.05, 1e-3), (0.5, 0.0)):
-        run = _adaptive(gpu, scene, cam, W, H, depth, rel, abs_tol=ab)
-        maps, _, actives = _predict(never, rel, ab)
+    scene, cam, W, H, depth, _ = named_workload(srt, name)
+    never = adaptive_run(gpu, scene, cam, W, H, depth, NEVER)
+    for rel, ab in ((pick_tolerance(never), 0.0), (0.05, 1e-3), (0.5, 0.0)):
+        run = adaptive_run(gpu, scene, cam, W, H, depth, rel, abs_tol=ab)
+        maps, _, actives = predict_stops(never, rel, ab)
         for k, (p, want, act) in enumerate(zip(run, maps, actives)):
             got = p["stats"]["samples"]
             assert np.array_equal(got, want), "rel %g abs %g pass %d: %d pixels differ" % (rel, ab, k, int((got != want).sum()))
@@ -60,16 +60,16 @@ def test_decisions_match_the_float32_restatement(srt, gpu, name):
 
 @pytest.mark.gpu
 def test_s2_is_the_sequential_float32_sum_of_squares(srt, gpu):
-    scene, cam, W, H, depth, _ = _workload(srt, "dielectric")
+    scene, cam, W, H, depth, _ = named_workload(srt, "dielectric")
     N = 12
-    _fresh(gpu, scene, cam, W, H, depth)
+    fresh_context(gpu, scene, cam, W, H, depth)
     ys = []
     for _ in range(N):           # accum_reset zeroes the sums and does not re-seed: pass k's Y sum is sample k's Y
         gpu.accum_reset()
         gpu.render_chunk_accum(W, H, 1)
-        ys.append(_sum_y(gpu, W, H))
+        ys.append(read_sum_y(gpu, W, H))
     ys = np.array(ys, np.float32)
-    run = _adaptive(gpu, scene, cam, W, H, depth, NEVER, sched=[2, 4, 6], min_spp=2)
+    run = adaptive_run(gpu, scene, cam, W, H, depth, NEVER, sched=[2, 4, 6], min_spp=2)
     st = run[-1]["stats"]
     s1 = np.zeros(W * H, np.float32); s2 = np.zeros(W * H, np.float32)
     want1 = np.zeros(W * H, np.float32); want2 = np.zeros(W * H, np.float32)
@@ -86,18 +86,18 @@ def test_s2_is_the_sequential_float32_sum_of_squares(srt, gpu):
 @pytest.mark.gpu
 def test_plain_render_after_adaptive_run_continues_each_pixels_stream(srt, gpu, orc):
     """a plain launch after an adaptive run equals the oracle continued from each pixel's RNG state after its own count"""
-    scene, cam, W, H, depth, mode = _workload(srt, "prism")
-    never = _adaptive(gpu, scene, cam, W, H, depth, NEVER)
-    rel = _pick_tolerance(never)
+    scene, cam, W, H, depth, mode = named_workload(srt, "prism")
+    never = adaptive_run(gpu, scene, cam, W, H, depth, NEVER)
+    rel = pick_tolerance(never)
     spp_next = 3
-    _fresh(gpu, scene, cam, W, H, depth, spp=spp_next)
+    fresh_context(gpu, scene, cam, W, H, depth, spp=spp_next)
     gpu.accum_reset_adaptive(rel, 0.0, MIN_SPP)
     for s in SCHED:
         gpu.render_chunk_accum(W, H, s)
     counts = gpu.accum_stats(W, H)["samples"]
     assert len(np.unique(counts)) >= 3
     gpu.render_chunk(W, H)
-    after = _frame(gpu, W, H)
+    after = read_frame(gpu, W, H)
     osc = oracle_scene_for(orc, scene, mode)
     n = gpu.geom["n_lanes"]
     init = np.zeros(6 * n, np.uint32)
@@ -106,7 +106,7 @@ def test_plain_render_after_adaptive_run_continues_each_pixels_stream(srt, gpu, 
         orc.lib().orc_rng_init(1984 + idx, C.byref(s))
         init[6 * idx: 6 * idx + 6] = [s.d] + list(s.v)
     states = init.copy()
-    lane = _lane_of(gpu.geom, W, H)
+    lane = lane_of(gpu.geom, W, H)
     for c in np.unique(counts):
         st = init.copy()
         osc.render(cam, W, H, int(c), depth, states=st)
@@ -120,22 +120,12 @@ def test_plain_render_after_adaptive_run_continues_each_pixels_stream(srt, gpu, 
 @pytest.mark.gpu
 @pytest.mark.parametrize("knobs,paired,expect", EVERY_SHAPE_CASES, ids=EVERY_SHAPE_IDS)
 def test_every_adaptive_shape_gives_the_same_image(srt, gpu, knobs, paired, expect):
-    n = 600 if paired else 601
-    scene = _soup(srt, n, n).build_bvh(srt.BVH_SAH, 1984)
-    assert scene.is_paired == paired
-    W, H, depth = 48, 32, 8
-    cam = srt.camera_init(W, H, 50.0, (0.5, 1.0, 16.0), (0.0, 0.0, 0.0), defocus_angle=0.6, focus_dist=14.0)
+    scene, cam, W, H, depth = shape_case(srt, paired)
     gpu.set_test_knobs()
-    ref = _adaptive(gpu, scene, cam, W, H, depth, 0.2)[-1]
+    ref = adaptive_run(gpu, scene, cam, W, H, depth, 0.2)[-1]
     assert len(np.unique(ref["stats"]["samples"])) >= 2
-    gpu.set_test_knobs(**knobs)
-    try:
-        got = _adaptive(gpu, scene, cam, W, H, depth, 0.2)[-1]
-        plan = gpu.launch_plan()
-        assert (int(plan["narrow_refs"]), int(plan["all_cached"]), int(plan["paired"])) == expect, plan
-    finally:
-        gpu.set_test_knobs()
-        gpu.upload_scene(scene)
+    with forced_shape(gpu, scene, knobs, expect):
+        got = adaptive_run(gpu, scene, cam, W, H, depth, 0.2)[-1]
     assert np.array_equal(got["stats"]["samples"], ref["stats"]["samples"])
     for k in ("fb", "lin", "xyz", "rowmajor"):
         assert_planes_equal(got["frame"][k], ref["frame"][k], "shape %r %s" % (expect, k))
@@ -144,52 +134,39 @@ def test_every_adaptive_shape_gives_the_same_image(srt, gpu, knobs, paired, expe
 
 @pytest.mark.gpu
 def test_partitions_and_offset_chunk(srt, gpu):
-    import torch
-    scene, cam, W, H, depth, _ = _workload(srt, "random_spheres")
+    scene, cam, W, H, depth, _ = named_workload(srt, "random_spheres")
     rel = 0.1
-    ref = _adaptive(gpu, scene, cam, W, H, depth, rel)[-1]
+    ref = adaptive_run(gpu, scene, cam, W, H, depth, rel)[-1]
     assert len(np.unique(ref["stats"]["samples"])) >= 2
     for world in (2, 3):
-        parts, samples, active = [], np.zeros(W * H, np.uint32), 0
-        for rank in range(world):
-            _fresh(gpu, scene, cam, W, H, depth)
+        def one_rank(rank):
+            fresh_context(gpu, scene, cam, W, H, depth)
             gpu.set_partition(rank, world)
             gpu.accum_reset_adaptive(rel, 0.0, MIN_SPP)
             for s in SCHED:
                 gpu.render_chunk_accum(W, H, s)
             gpu.synchronize()
-            samples += gpu.accum_stats(W, H)["samples"]      # (pixels of the other ranks read 0)
-            active += gpu.accum_active
-            _, n_floats, _, _ = gpu.tile_buffer()
-            staging = torch.empty(n_floats, dtype=torch.float32, device="cuda")
-            gpu.copy_tile_buffer(staging.data_ptr(), torch.cuda.current_stream().cuda_stream)
-            torch.cuda.synchronize()
-            parts.append(staging.cpu().numpy().copy())
-        gathered = torch.from_numpy(np.concatenate(parts)).cuda()
-        gpu.scatter_tiles(gathered.data_ptr())
-        gpu.synchronize()
-        assert np.array_equal(samples, ref["stats"]["samples"]), world
-        assert active == ref["active"], world
+            return gpu.accum_stats(W, H)["samples"], gpu.accum_active      # (pixels of the other ranks read 0)
+        samples, actives = zip(*gather_ranks(gpu, world, one_rank))
+        assert np.array_equal(sum(samples), ref["stats"]["samples"]), world
+        assert sum(actives) == ref["active"], world
         assert_planes_equal(gpu.read_fb(), ref["frame"]["fb"], "world %d fb" % world)
         assert_planes_equal(gpu.read_fb_aux(1), ref["frame"]["lin"], "world %d lin" % world)
         assert_planes_equal(gpu.read_fb_aux(2), ref["frame"]["xyz"], "world %d xyz" % world)
-    gpu.set_partition(0, 1)
 
     # a 30 x 20 chunk at (17, 9) of a 64 x 40 image: each pixel of the chunk equals the one-shot chunk of its count
     IW, IH, cw, ch, ox, oy = 64, 40, 30, 20, 17, 9
     cam = scene.default_camera(IW, IH)
 
     def chunk(spp=None):
-        _fresh(gpu, scene, cam, cw, ch, depth, spp=spp or 12)
+        fresh_context(gpu, scene, cam, cw, ch, depth, spp=spp or 12)
         if spp is None:
             gpu.accum_reset_adaptive(rel, 0.0, MIN_SPP)
             for s in SCHED:
                 gpu.render_chunk_accum(cw, ch, s, ox, oy)
         else:
             gpu.render_chunk(cw, ch, ox, oy)
-        gpu.scatter_tiles()
-        return dict(fb=gpu.read_fb(), lin=gpu.read_fb_aux(1), xyz=gpu.read_fb_aux(2), rowmajor=gpu.read_fb_rowmajor(IW, IH),
-                    samples=gpu.accum_stats(IW, IH)["samples"] if spp is None else None)
+        return dict(read_frame(gpu, IW, IH), samples=gpu.accum_stats(IW, IH)["samples"] if spp is None else None)
     got = chunk()
     counts = got["samples"]
     inside = np.zeros((IH, IW), bool); inside[oy:oy + ch, ox:ox + cw] = True
@@ -199,17 +176,18 @@ def test_partitions_and_offset_chunk(srt, gpu):
     lane = np.zeros(IW * IH, np.int64)
     geom = gpu.geom
     ci, cj = i[inside] - ox, j[inside] - oy
-    lane_c = _lane_of(geom, cw, ch)
+    lane_c = lane_of(geom, cw, ch)
     lane[inside] = lane_c[cj * cw + ci]
     for c in np.unique(counts[inside]):
         mask = inside & (counts == c)
-        _assert_pixels_equal(got, chunk(int(c)), mask, lane, "offset chunk, %d spp" % c)
+        assert_pixels_equal(got, chunk(int(c)), mask, lane, "offset chunk, %d spp" % c)
 
 
 @pytest.mark.gpu
 def test_comm_two_and_three_ranks_one_gpu_mock_transport():
     run_mock_transport_child("""
 import numpy as np
+from accum_helpers import comm_accumulations
 from helpers import assert_planes_equal
 scene = srt.Scene.builtin(srt.SCENE_RANDOM_SPHERES).build_bvh(srt.BVH_SAH, 1984)
 W, H, depth, rel = 150, 90, 16, 0.1
@@ -217,24 +195,18 @@ cam = scene.default_camera(W, H)
 steps = list(srt.render_adaptive(scene, cam, W, H, depth, rel, min_spp=8, step=4, max_spp=24))
 total, active, ref = steps[-1]
 assert total == 24 and active > 0 and len(np.unique(ref['samples'])) >= 2, (total, active)
-for world in (2, 3):
-    comm = srt.Comm.init_all([0] * world)
-    comm.set_gather_planes(9)
-    comm.upload_scene(scene); comm.set_camera(cam)
-    comm.init_device_params(W, H, 24, depth, 1984)
+def reset(comm):
     comm.accum_reset_adaptive(rel, 0.0, 8)
     assert comm.accum_active == 0
-    for s in (8, 4, 4, 4, 4):
-        comm.render_frame_accum(W, H, s)
-    comm.synchronize()
-    assert comm.accum_active == active, (world, comm.accum_active, active)
-    root = comm.root
-    assert_planes_equal(root.read_fb(), ref['fb'], 'world %d fb' % world)
-    assert_planes_equal(root.read_fb_aux(1), ref['lin'], 'world %d lin' % world)
-    assert_planes_equal(root.read_fb_aux(2), ref['xyz'], 'world %d xyz' % world)
-    samples = sum(r.accum_stats(W, H)['samples'] for r in comm.renderers)
-    assert np.array_equal(samples, ref['samples']), world
-    comm.close()
+for world in (2, 3):
+    for _, comm in comm_accumulations(srt, world, (9,), scene, cam, W, H, depth, 24, reset, (8, 4, 4, 4, 4)):
+        assert comm.accum_active == active, (world, comm.accum_active, active)
+        root = comm.root
+        assert_planes_equal(root.read_fb(), ref['fb'], 'world %d fb' % world)
+        assert_planes_equal(root.read_fb_aux(1), ref['lin'], 'world %d lin' % world)
+        assert_planes_equal(root.read_fb_aux(2), ref['xyz'], 'world %d xyz' % world)
+        samples = sum(r.accum_stats(W, H)['samples'] for r in comm.renderers)
+        assert np.array_equal(samples, ref['samples']), world
 r = srt.Renderer(0)
 c1 = srt.Comm.init_rank(r, srt.Comm.unique_id(), 0, 1)
 c1.upload_scene(scene); c1.set_camera(cam); c1.init_device_params(W, H, 24, depth, 1984)
@@ -250,50 +222,50 @@ print('adaptive mock transport ok')
 
 @pytest.mark.gpu
 def test_compaction_counts_and_the_pass_after_convergence(srt, gpu):
-    scene, cam, W, H, depth, _ = _workload(srt, "dielectric")
-    never = _adaptive(gpu, scene, cam, W, H, depth, NEVER)
-    run = _adaptive(gpu, scene, cam, W, H, depth, _pick_tolerance(never))
+    scene, cam, W, H, depth, _ = named_workload(srt, "dielectric")
+    never = adaptive_run(gpu, scene, cam, W, H, depth, NEVER)
+    run = adaptive_run(gpu, scene, cam, W, H, depth, pick_tolerance(never))
     before = W * H
     for p, s in zip(run, SCHED):
         assert p["paths"] == before * s, (p["total"], p["paths"], before, s)
         before = p["active"]
     # everything stops after the first pass (min_spp samples); a later pass renders nothing and changes nothing but the total
     spp_next = 3
-    _fresh(gpu, scene, cam, W, H, depth, spp=spp_next)
+    fresh_context(gpu, scene, cam, W, H, depth, spp=spp_next)
     gpu.accum_reset_adaptive(1e3, 1e3, MIN_SPP)
     gpu.render_chunk_accum(W, H, MIN_SPP)
-    first = _frame(gpu, W, H)
+    first = read_frame(gpu, W, H)
     assert gpu.accum_active == 0 and gpu.stats()["paths"] == W * H * MIN_SPP
     stats_first = gpu.accum_stats(W, H)
     gpu.render_chunk_accum(W, H, 4)
     assert gpu.stats()["paths"] == 0 and gpu.accum_active == 0 and gpu.accum_samples == MIN_SPP + 4
-    again = _frame(gpu, W, H)
+    again = read_frame(gpu, W, H)
     for k in ("fb", "lin", "xyz", "rowmajor"):
         assert_planes_equal(again[k], first[k], "pass after convergence " + k)
     stats_again = gpu.accum_stats(W, H)
     for k in ("samples", "sum_y", "sum_y2"):
         assert np.array_equal(stats_again[k].view(np.uint32), stats_first[k].view(np.uint32)), k
     gpu.render_chunk(W, H)           # the RNG states are those after MIN_SPP samples: a plain launch continues from there
-    after = _frame(gpu, W, H)
-    _fresh(gpu, scene, cam, W, H, depth, spp=spp_next)
+    after = read_frame(gpu, W, H)
+    fresh_context(gpu, scene, cam, W, H, depth, spp=spp_next)
     gpu.accum_reset()
     gpu.render_chunk_accum(W, H, MIN_SPP)
     gpu.render_chunk(W, H)
-    want = _frame(gpu, W, H)
+    want = read_frame(gpu, W, H)
     for k in ("fb", "lin", "xyz", "rowmajor"):
         assert_planes_equal(after[k], want[k], "plain launch after the converged adaptive run " + k)
 
 
 @pytest.mark.gpu
 def test_refusals_and_invalidation(srt, gpu):
-    scene, cam, W, H, depth, _ = _workload(srt, "prism")
+    scene, cam, W, H, depth, _ = named_workload(srt, "prism")
     one_shot = srt.render_image(scene, cam, W, H, 12, depth, renderer=gpu)
     L = gpu_lib()
-    _fresh(gpu, scene, cam, W, H, depth)
-    _expect_error(srt, lambda: gpu.accum_active, ERR_INVALID, "accum_active without an adaptive accumulation")
+    fresh_context(gpu, scene, cam, W, H, depth)
+    expect_error(srt, lambda: gpu.accum_active, ERR_INVALID, "accum_active without an adaptive accumulation")
     gpu.accum_reset_adaptive(0.1, 0.0, 4)
     gpu.render_chunk_accum(W, H, 4)
-    first = _frame(gpu, W, H)
+    first = read_frame(gpu, W, H)
     active = gpu.accum_active
     bad = [(0.0, 0.0, 4, 0), (-0.1, 0.0, 4, 0), (0.1, -1.0, 4, 0), (float("nan"), 0.0, 4, 0), (float("inf"), 0.0, 4, 0),
            (0.1, 0.0, 1, 0), (0.1, 0.0, 0, 0), (0.1, 0.0, 4, 1)]
@@ -304,35 +276,35 @@ def test_refusals_and_invalidation(srt, gpu):
         assert gpu.accum_samples == 4 and gpu.accum_active == active, (rel, ab, mn, res)
     assert L.srt_accum_reset_adaptive(gpu._h, None) == ERR_INVALID
     gpu.set_count_traversal(True)
-    _expect_error(srt, lambda: gpu.accum_reset_adaptive(0.1), ERR_UNSUPPORTED, "instrumented context")
-    _expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 4), ERR_UNSUPPORTED, "instrumented pass")
+    expect_error(srt, lambda: gpu.accum_reset_adaptive(0.1), ERR_UNSUPPORTED, "instrumented context")
+    expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 4), ERR_UNSUPPORTED, "instrumented pass")
     gpu.set_count_traversal(False)
-    for k, v in _frame(gpu, W, H).items():
+    for k, v in read_frame(gpu, W, H).items():
         assert_planes_equal(v, first[k], "after the refusals " + k)
     gpu.render_chunk_accum(W, H, 4)         # the accumulation survived the refusals
     assert gpu.accum_samples == 8
     # srt_set_gather_planes ends an adaptive accumulation (not a plain one: test_progressive)
     gpu.set_gather_planes(9)
-    _expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 4), ERR_INVALID, "pass after srt_set_gather_planes")
-    _expect_error(srt, lambda: gpu.accum_active, ERR_INVALID, "accum_active after srt_set_gather_planes")
+    expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 4), ERR_INVALID, "pass after srt_set_gather_planes")
+    expect_error(srt, lambda: gpu.accum_active, ERR_INVALID, "accum_active after srt_set_gather_planes")
     # the other invalidations of an accumulation hold for an adaptive one too
     for what, call in (("srt_set_camera", lambda: gpu.set_camera(cam)), ("srt_render_chunk", lambda: gpu.render_chunk(W, H))):
-        _fresh(gpu, scene, cam, W, H, depth)
+        fresh_context(gpu, scene, cam, W, H, depth)
         gpu.accum_reset_adaptive(0.1, 0.0, 4)
         gpu.render_chunk_accum(W, H, 4)
         call()
-        _expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 4), ERR_INVALID, what)
+        expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 4), ERR_INVALID, what)
     # a plain accumulation after an adaptive one behaves as before: passes of 5 + 7 are the one-shot 12-spp frame
-    _fresh(gpu, scene, cam, W, H, depth)
+    fresh_context(gpu, scene, cam, W, H, depth)
     gpu.accum_reset_adaptive(0.1, 0.0, 4)
     gpu.render_chunk_accum(W, H, 4)
-    _fresh(gpu, scene, cam, W, H, depth)
+    fresh_context(gpu, scene, cam, W, H, depth)
     gpu.accum_reset()
-    _expect_error(srt, lambda: gpu.accum_active, ERR_INVALID, "accum_active on a plain accumulation")
+    expect_error(srt, lambda: gpu.accum_active, ERR_INVALID, "accum_active on a plain accumulation")
     for s in (5, 7):
         gpu.render_chunk_accum(W, H, s)
     assert gpu.stats()["paths"] == W * H * 7
-    got = _frame(gpu, W, H)
+    got = read_frame(gpu, W, H)
     for k in ("fb", "lin", "xyz", "rowmajor"):
         assert_planes_equal(got[k], one_shot[k], "plain accumulation after an adaptive one " + k)
     gpu.set_gather_planes(3)
@@ -340,7 +312,7 @@ def test_refusals_and_invalidation(srt, gpu):
 
 @pytest.mark.gpu
 def test_render_adaptive_generator(srt, gpu):
-    scene, cam, W, H, depth, _ = _workload(srt, "cornell")
+    scene, cam, W, H, depth, _ = named_workload(srt, "cornell")
     steps = list(srt.render_adaptive(scene, cam, W, H, depth, 0.05, min_spp=8, step=4, max_spp=24, renderer=gpu))
     assert [t for t, _, _ in steps] == [8, 12, 16, 20, 24][:len(steps)]
     for t, active, res in steps:

@@ -10,7 +10,7 @@ import re
 import numpy as np
 import pytest
 
-from accum_helpers import ROOT, SHAPES, _kernel_id, converged_f32
+from accum_helpers import ROOT, SHAPES, converged_f32, kernel_id
 
 NEW_SYMBOLS = ("srt_accum_reset_adaptive", "srt_accum_active", "srt_read_accum_stats", "srt_comm_accum_reset_adaptive", "srt_comm_accum_active")
 ADAPT_SYM = re.compile(r"^_ZN3srt13render_kernelILi4ELb([01])ELb([01])ELb([01])EEEvNS_12RenderParamsE$")
@@ -34,7 +34,7 @@ def test_new_symbols_are_declared_bound_and_exported(srt):
 
 def test_code_object_holds_every_adaptive_variant(srt):
     found = set()
-    for name, _ in _kernel_id().gfx950_functions(srt.binding.LIB_PATH):
+    for name, _ in kernel_id().gfx950_functions(srt.binding.LIB_PATH):
         m = ADAPT_SYM.match(name)
         if m:
             found.add(tuple(int(g) for g in m.groups()))
@@ -42,7 +42,7 @@ def test_code_object_holds_every_adaptive_variant(srt):
 
 
 def test_production_kernels_are_still_found_by_kernel_id(srt):
-    hs = _kernel_id().code_hashes(srt.binding.LIB_PATH)
+    hs = kernel_id().code_hashes(srt.binding.LIB_PATH)
     assert set(hs) == {(1, 1, 1), (0, 0, 1), (1, 1), (1, 0), (0, 1), (0, 0)}, sorted(hs)
 
 

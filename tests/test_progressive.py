@@ -8,8 +8,9 @@ import os
 import numpy as np
 import pytest
 
-from accum_helpers import (ERR_INVALID, ERR_UNSUPPORTED, EVERY_SHAPE_CASES, EVERY_SHAPE_IDS, ROOT, _assert_same_image, _expect_error,
-                           _progressive, _soup, _split, _workload, run_mock_transport_child)
+from accum_helpers import (ERR_INVALID, ERR_UNSUPPORTED, EVERY_SHAPE_CASES, EVERY_SHAPE_IDS, ROOT, assert_same_image, expect_error,
+                           forced_shape, gather_ranks, named_workload, progressive_steps, read_frame, run_mock_transport_child, shape_case,
+                           split_passes)
 from helpers import DIGEST_PLANES, assert_planes_equal, digest_of_render, digest_workloads, oracle_scene_for
 
 SPLITS = [[12], [5, 7], [1, 1, 10], [4, 4, 4]]
@@ -18,13 +19,13 @@ SPLITS = [[12], [5, 7], [1, 1, 10], [4, 4, 4]]
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["prism", "cornell", "random_spheres", "dielectric"])
 def test_split_equals_one_shot_bit_for_bit(srt, gpu, orc, name):
-    scene, cam, W, H, depth, mode = _workload(srt, name)
+    scene, cam, W, H, depth, mode = named_workload(srt, name)
     one_shot = srt.render_image(scene, cam, W, H, 12, depth, renderer=gpu)
     for passes in SPLITS:
-        steps = _progressive(srt, gpu, scene, cam, W, H, passes, depth)
+        steps = progressive_steps(srt, gpu, scene, cam, W, H, passes, depth)
         assert [t for t, _ in steps] == list(np.cumsum(passes)), steps
         total, last = steps[-1]
-        _assert_same_image(last, one_shot, "%s split %r" % (name, passes))
+        assert_same_image(last, one_shot, "%s split %r" % (name, passes))
         assert set(last) == set(one_shot)
         pixels = W * H
         assert last["stats"]["paths"] == pixels * passes[-1], (last["stats"], passes)     # the stats of the last pass
@@ -38,79 +39,53 @@ def test_split_equals_one_shot_bit_for_bit(srt, gpu, orc, name):
 @pytest.mark.gpu
 def test_intermediate_passes_equal_one_shot_of_their_total(srt, gpu):
     """every yielded frame, not only the last, is the one-shot frame of the samples so far"""
-    scene, cam, W, H, depth, _ = _workload(srt, "prism")
-    steps = _progressive(srt, gpu, scene, cam, W, H, [2, 3, 7], depth)
+    scene, cam, W, H, depth, _ = named_workload(srt, "prism")
+    steps = progressive_steps(srt, gpu, scene, cam, W, H, [2, 3, 7], depth)
     for total, res in steps:
-        _assert_same_image(res, srt.render_image(scene, cam, W, H, total, depth, renderer=gpu), "after %d samples" % total)
+        assert_same_image(res, srt.render_image(scene, cam, W, H, total, depth, renderer=gpu), "after %d samples" % total)
 
 
 @pytest.mark.gpu
 def test_frozen_digests_in_several_passes(srt, gpu):
     golden = json.load(open(os.path.join(ROOT, "tests", "golden", "oracle_digests.json")))
     for name, (scene, cam, W, H, spp, depth, _) in sorted(digest_workloads(srt).items()):
-        passes = _split(spp)
-        total, res = _progressive(srt, gpu, scene, cam, W, H, passes, depth)[-1]
+        passes = split_passes(spp)
+        total, res = progressive_steps(srt, gpu, scene, cam, W, H, passes, depth)[-1]
         assert total == spp == golden[name]["spp"]
         got = digest_of_render(res)
         for plane in DIGEST_PLANES:
             assert got[plane] == golden[name][plane], (name, passes, plane)
 
 
-def _forced_variant_case(srt, gpu, scene, cam, W, H, depth, knobs, expect):
-    gpu.set_test_knobs(**knobs)
-    try:
-        one_shot = srt.render_image(scene, cam, W, H, 12, depth, renderer=gpu)
-        plan = gpu.launch_plan()
-        shape = (int(plan["narrow_refs"]), int(plan["all_cached"]), int(plan["paired"]))
-        assert shape == expect, (plan, knobs)
-        for passes in ([5, 7], [1, 1, 10]):
-            _, last = _progressive(srt, gpu, scene, cam, W, H, passes, depth)[-1]
-            _assert_same_image(last, one_shot, "shape %r split %r" % (expect, passes))
-    finally:
-        gpu.set_test_knobs()
-        gpu.upload_scene(scene)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("knobs,paired,expect", EVERY_SHAPE_CASES, ids=EVERY_SHAPE_IDS)
 def test_every_accumulating_shape_is_exact(srt, gpu, knobs, paired, expect):
-    n = 600 if paired else 601          # the SAH builder pairs an even triangle count
-    scene = _soup(srt, n, n).build_bvh(srt.BVH_SAH, 1984)
-    assert scene.is_paired == paired
-    W, H, depth = 48, 32, 8
-    cam = srt.camera_init(W, H, 50.0, (0.5, 1.0, 16.0), (0.0, 0.0, 0.0), defocus_angle=0.6, focus_dist=14.0)
-    _forced_variant_case(srt, gpu, scene, cam, W, H, depth, knobs, expect)
+    scene, cam, W, H, depth = shape_case(srt, paired)
+    with forced_shape(gpu, scene, knobs, expect):
+        one_shot = srt.render_image(scene, cam, W, H, 12, depth, renderer=gpu)
+        for passes in ([5, 7], [1, 1, 10]):
+            _, last = progressive_steps(srt, gpu, scene, cam, W, H, passes, depth)[-1]
+            assert_same_image(last, one_shot, "shape %r split %r" % (expect, passes))
 
 
 @pytest.mark.gpu
 def test_partition_and_offset_chunk(srt, gpu):
     """ranks 0..W-1 of a partition, each accumulated on its own and scattered together, equal the one-shot frame; so does a chunk at a
     non-zero offset of a larger image"""
-    import torch
-    scene, cam, W, H, depth, _ = _workload(srt, "prism")
+    scene, cam, W, H, depth, _ = named_workload(srt, "prism")
     ref = srt.render_image(scene, cam, W, H, 12, depth, renderer=gpu)
     for world in (2, 3):
-        parts = []
-        for rank in range(world):
+        def one_rank(rank):         # (not fresh_context: the gather planes and the counting stay as the session left them)
             gpu.upload_scene(scene); gpu.set_camera(cam)
             gpu.init_device_params(W, H, 12, depth, 1984)
             gpu.set_partition(rank, world)
             gpu.accum_reset()
             for s in (5, 7):
                 gpu.render_chunk_accum(W, H, s)
-            gpu.synchronize()
-            _, n_floats, _, _ = gpu.tile_buffer()
-            staging = torch.empty(n_floats, dtype=torch.float32, device="cuda")
-            gpu.copy_tile_buffer(staging.data_ptr(), torch.cuda.current_stream().cuda_stream)
-            torch.cuda.synchronize()
-            parts.append(staging.cpu().numpy().copy())
-        gathered = torch.from_numpy(np.concatenate(parts)).cuda()
-        gpu.scatter_tiles(gathered.data_ptr())
-        gpu.synchronize()
+        gather_ranks(gpu, world, one_rank)
         assert_planes_equal(gpu.read_fb(), ref["fb"], "world %d fb" % world)
         assert_planes_equal(gpu.read_fb_aux(1), ref["lin"], "world %d lin" % world)
         assert_planes_equal(gpu.read_fb_aux(2), ref["xyz"], "world %d xyz" % world)
-    gpu.set_partition(0, 1)
 
     # a 30 x 20 chunk at (17, 9) of a 64 x 40 image
     IW, IH, cw, ch, ox, oy = 64, 40, 30, 20, 17, 9
@@ -125,9 +100,8 @@ def test_partition_and_offset_chunk(srt, gpu):
                 gpu.render_chunk_accum(cw, ch, s, ox, oy)
         else:
             gpu.render_chunk(cw, ch, ox, oy)
-        gpu.scatter_tiles()
-        return dict(fb=gpu.read_fb(), lin=gpu.read_fb_aux(1), xyz=gpu.read_fb_aux(2), rowmajor=gpu.read_fb_rowmajor(IW, IH))
-    _assert_same_image(chunk(True), chunk(False), "offset chunk")
+        return read_frame(gpu, IW, IH)
+    assert_same_image(chunk(True), chunk(False), "offset chunk")
 
 
 @pytest.mark.gpu
@@ -135,21 +109,14 @@ def test_comm_two_and_three_ranks_one_gpu_mock_transport():
     """srt_comm_accum_reset / srt_render_frame_multi_accum at W = 2 and 3 on ONE GPU over the test transport (tests/cpp/mock_rccl.cpp,
     as the parity suite's communicator test does; the library caches its RCCL handle per process, so this runs in a child process)"""
     run_mock_transport_child("""
+from accum_helpers import comm_accumulations
 from helpers import assert_planes_equal
 scene = srt.Scene.builtin(srt.SCENE_RANDOM_SPHERES).build_bvh(srt.BVH_SAH, 1984)
 W, H, depth = 150, 90, 16
 cam = scene.default_camera(W, H)
 ref = srt.render_image(scene, cam, W, H, 12, depth)
 for world in (2, 3):
-    comm = srt.Comm.init_all([0] * world)
-    for planes in (3, 9):
-        comm.set_gather_planes(planes)
-        comm.upload_scene(scene); comm.set_camera(cam)
-        comm.init_device_params(W, H, 12, depth, 1984)
-        comm.accum_reset()
-        for s in (5, 7):
-            comm.render_frame_accum(W, H, s)
-        comm.synchronize()
+    for planes, comm in comm_accumulations(srt, world, (3, 9), scene, cam, W, H, depth, 12, lambda c: c.accum_reset(), (5, 7)):
         root = comm.root
         assert all(r.accum_samples == 12 for r in comm.renderers)
         assert_planes_equal(root.read_fb(), ref['fb'], 'world %d planes %d fb' % (world, planes))
@@ -158,7 +125,6 @@ for world in (2, 3):
             assert_planes_equal(root.read_fb_aux(2), ref['xyz'], 'world %d xyz' % world)
         st = comm.stats()
         assert st['paths'] == W * H * 7, st
-    comm.close()
 print('progressive mock transport ok')
 """, "progressive mock transport ok", timeout=300)
 
@@ -168,7 +134,7 @@ def test_plain_render_after_accumulation_continues_rng_streams(srt, gpu, orc):
     """the RNG state an accumulation leaves is the one-shot's: a plain launch after [5, 7] equals the oracle continued from the states
     after 12 samples"""
     import ctypes as C
-    scene, cam, W, H, depth, mode = _workload(srt, "prism")
+    scene, cam, W, H, depth, mode = named_workload(srt, "prism")
     spp_next = 3
     gpu.upload_scene(scene); gpu.set_camera(cam); gpu.set_partition(0, 1)
     gpu.init_device_params(W, H, spp_next, depth, 1984)
@@ -193,27 +159,23 @@ def test_plain_render_after_accumulation_continues_rng_streams(srt, gpu, orc):
 
 @pytest.mark.gpu
 def test_refused_calls_and_invalidation(srt, gpu):
-    scene, cam, W, H, depth, _ = _workload(srt, "prism")
+    scene, cam, W, H, depth, _ = named_workload(srt, "prism")
     one_shot = srt.render_image(scene, cam, W, H, 12, depth, renderer=gpu)
 
     def fresh():
         gpu.upload_scene(scene); gpu.set_camera(cam); gpu.set_partition(0, 1)
         gpu.init_device_params(W, H, 12, depth, 1984)
 
-    def frame():
-        gpu.scatter_tiles()
-        return dict(fb=gpu.read_fb(), lin=gpu.read_fb_aux(1), xyz=gpu.read_fb_aux(2), rowmajor=gpu.read_fb_rowmajor(W, H))
-
     # no accumulation yet
     fresh()
-    _expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 4), ERR_INVALID, "pass before srt_accum_reset")
+    expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 4), ERR_INVALID, "pass before srt_accum_reset")
     assert gpu.accum_samples == 0
     gpu.accum_reset()
     assert gpu.accum_samples == 0
-    _expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 65536), ERR_INVALID, "total above 65535")
+    expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 65536), ERR_INVALID, "total above 65535")
     gpu.render_chunk_accum(W, H, 5)
     assert gpu.accum_samples == 5 and gpu.stats()["paths"] == W * H * 5
-    after_first = frame()
+    after_first = read_frame(gpu, W, H)
 
     # refusals: nothing changes on the device (framebuffer, tile buffer, sums, RNG state)
     refusals = [
@@ -225,15 +187,15 @@ def test_refused_calls_and_invalidation(srt, gpu):
         (lambda: gpu.render_chunk_accum(W, H, 7, 0, 2), ERR_INVALID, "another offset"),
     ]
     for fn, code, what in refusals:
-        _expect_error(srt, fn, code, what)
+        expect_error(srt, fn, code, what)
         assert gpu.accum_samples == 5, what
     gpu.set_count_traversal(True)
-    _expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 7), ERR_UNSUPPORTED, "instrumented context")
+    expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 7), ERR_UNSUPPORTED, "instrumented context")
     gpu.set_count_traversal(False)
-    _assert_same_image(frame(), after_first, "framebuffer after the refused calls")
+    assert_same_image(read_frame(gpu, W, H), after_first, "framebuffer after the refused calls")
     gpu.render_chunk_accum(W, H, 7)               # the sums and the RNG states were untouched: the total is the one-shot frame
     assert gpu.accum_samples == 12
-    _assert_same_image(frame(), one_shot, "accumulation continued after the refused calls")
+    assert_same_image(read_frame(gpu, W, H), one_shot, "accumulation continued after the refused calls")
 
     # invalidation: each of these calls ends the accumulation until the next reset
     invalidators = [
@@ -248,7 +210,7 @@ def test_refused_calls_and_invalidation(srt, gpu):
         gpu.accum_reset()
         gpu.render_chunk_accum(W, H, 2)
         call()
-        _expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 2), ERR_INVALID, what)
+        expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 2), ERR_INVALID, what)
         assert gpu.accum_samples == 0, what
         gpu.accum_reset()
         gpu.render_chunk_accum(W, H, 2)       # a reset makes the context usable again
@@ -262,13 +224,13 @@ def test_refused_calls_and_invalidation(srt, gpu):
         gpu.order_children_by_profile(other, W, H, 2, depth, 1)
     except srt.SrtError:
         pass            # (a probe frame that records nothing is declined: the accumulation is dropped before anything else)
-    _expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 2), ERR_INVALID, "srt_order_children_by_profile")
+    expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 2), ERR_INVALID, "srt_order_children_by_profile")
     assert gpu.accum_samples == 0
 
     # a refused pass after a plain launch leaves the plain frame alone
     fresh()
     gpu.render_chunk(W, H)
-    plain = frame()
-    _expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 3), ERR_INVALID, "after a plain launch")
-    _assert_same_image(frame(), plain, "plain frame after a refused pass")
-    _assert_same_image(plain, one_shot, "plain frame")
+    plain = read_frame(gpu, W, H)
+    expect_error(srt, lambda: gpu.render_chunk_accum(W, H, 3), ERR_INVALID, "after a plain launch")
+    assert_same_image(read_frame(gpu, W, H), plain, "plain frame after a refused pass")
+    assert_same_image(plain, one_shot, "plain frame")

@@ -7,7 +7,7 @@ import re
 
 import pytest
 
-from accum_helpers import ROOT, SHAPES, _kernel_id
+from accum_helpers import ROOT, SHAPES, kernel_id
 
 NEW_SYMBOLS = ("srt_accum_reset", "srt_render_chunk_accum", "srt_accum_samples", "srt_comm_accum_reset", "srt_render_frame_multi_accum")
 # render_kernel<3, NARROW, ALL_CACHED, PAIRED>
@@ -31,7 +31,7 @@ def test_new_symbols_are_declared_bound_and_exported(srt):
 
 def test_code_object_holds_every_accumulating_variant(srt):
     found = set()
-    for name, _ in _kernel_id().gfx950_functions(srt.binding.LIB_PATH):
+    for name, _ in kernel_id().gfx950_functions(srt.binding.LIB_PATH):
         m = ACCUM_SYM.match(name)
         if m:
             found.add(tuple(int(g) for g in m.groups()))
@@ -40,7 +40,7 @@ def test_code_object_holds_every_accumulating_variant(srt):
 
 def test_production_kernels_are_still_found_by_kernel_id(srt):
     """the accumulating variant is a separate instantiation: the six MODE 0 kernels are all still there for bench.py's hash tie"""
-    hs = _kernel_id().code_hashes(srt.binding.LIB_PATH)
+    hs = kernel_id().code_hashes(srt.binding.LIB_PATH)
     assert set(hs) == {(1, 1, 1), (0, 0, 1), (1, 1), (1, 0), (0, 1), (0, 0)}, sorted(hs)
 
 

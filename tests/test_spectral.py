@@ -8,8 +8,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from accum_helpers import (ERR_INVALID, ERR_UNSUPPORTED, EVERY_SHAPE_CASES, EVERY_SHAPE_IDS, N_GRID, _expect_error, _frame, _fresh,
-                           _lane_of, _soup, _spectral, _workload, gpu_lib, run_mock_transport_child)
+from accum_helpers import (ERR_INVALID, ERR_UNSUPPORTED, EVERY_SHAPE_CASES, EVERY_SHAPE_IDS, N_GRID, expect_error, forced_shape,
+                           fresh_context, gpu_lib, lane_of, named_workload, read_frame, read_sum_y, run_mock_transport_child, shape_case,
+                           spectral_run)
 from helpers import _xorwow_host, assert_planes_equal, bits, custom_scene, fuzz_case
 
 
@@ -42,14 +43,12 @@ def test_film_contracts_to_the_xyz_sums(srt, gpu, name):
     if name == "fuzz":
         scene, cam, W, H, spp, depth = _fuzz_with_lens(srt)
     else:
-        scene, cam, W, H, depth, _ = _workload(srt, name)
+        scene, cam, W, H, depth, _ = named_workload(srt, name)
         spp = 6
-    frame, film = _spectral(gpu, scene, cam, W, H, depth, [spp])
-    lane = _lane_of(gpu.geom, W, H)
+    frame, film = spectral_run(gpu, scene, cam, W, H, depth, [spp])
+    lane = lane_of(gpu.geom, W, H)
     want = np.stack([frame["xyz"][c][lane] for c in range(3)], axis=-1).reshape(H, W, 3).astype(np.float64)
-    y = np.zeros(W * H, np.float32)
-    gpu._ck(gpu_lib().srt_read_accum_stats(gpu._h, None, y.ctypes.data_as(C.POINTER(C.c_float)), None, W, H))
-    assert np.array_equal(bits(y), bits(want[..., 1].astype(np.float32).ravel()))
+    assert np.array_equal(bits(read_sum_y(gpu, W, H)), bits(want[..., 1].astype(np.float32).ravel()))
     got = srt.film_to_xyz(film)
     assert np.array_equal(np.isnan(got), np.isnan(want)), name
     ok = ~np.isnan(want)
@@ -69,9 +68,9 @@ def test_miss_only_film_equals_the_float32_restatement(srt, gpu, orc, passes):
     scene = _miss_scene(srt, bg)
     W, H, depth = 23, 14, 4
     cam = _miss_camera(srt, W, H)
-    frame, film = _spectral(gpu, scene, cam, W, H, depth, passes)
+    frame, film = spectral_run(gpu, scene, cam, W, H, depth, passes)
     assert gpu.stats()["rays"] == W * H * passes[-1]
-    seeds = 1984 + _lane_of(gpu.geom, W, H).astype(np.uint64)
+    seeds = 1984 + lane_of(gpu.geom, W, H).astype(np.uint64)
     st, nxt = _xorwow_host(seeds)
     every = np.ones(seeds.size, bool)
 
@@ -106,24 +105,22 @@ def test_miss_only_film_equals_the_float32_restatement(srt, gpu, orc, passes):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["prism", "dielectric"])
 def test_film_is_additive_and_split_invariant(srt, gpu, name):
-    scene, cam, W, H, depth, _ = _workload(srt, name)
-    one, film_one = _spectral(gpu, scene, cam, W, H, depth, [32], spp=3)
-    split, film_split = _spectral(gpu, scene, cam, W, H, depth, [8, 8, 16], spp=3)
+    scene, cam, W, H, depth, _ = named_workload(srt, name)
+    one, film_one = spectral_run(gpu, scene, cam, W, H, depth, [32], spp=3)
+    split, film_split = spectral_run(gpu, scene, cam, W, H, depth, [8, 8, 16], spp=3)
     assert np.array_equal(bits(film_split), bits(film_one)), name
-    sum_y = np.zeros(W * H, np.float32)
-    gpu._ck(gpu_lib().srt_read_accum_stats(gpu._h, None, sum_y.ctypes.data_as(C.POINTER(C.c_float)), None, W, H))
+    sum_y = read_sum_y(gpu, W, H)
     gpu.render_chunk(W, H)                # continues every pixel's RNG stream from where the passes left it
-    after = _frame(gpu, W, H)
+    after = read_frame(gpu, W, H)
     # the same passes of a plain accumulation
-    _fresh(gpu, scene, cam, W, H, depth, spp=3)
+    fresh_context(gpu, scene, cam, W, H, depth, spp=3)
     gpu.accum_reset()
     for s in (8, 8, 16):
         gpu.render_chunk_accum(W, H, s)
-    plain = _frame(gpu, W, H)
-    plain_y = np.zeros(W * H, np.float32)
-    gpu._ck(gpu_lib().srt_read_accum_stats(gpu._h, None, plain_y.ctypes.data_as(C.POINTER(C.c_float)), None, W, H))
+    plain = read_frame(gpu, W, H)
+    plain_y = read_sum_y(gpu, W, H)
     gpu.render_chunk(W, H)
-    plain_after = _frame(gpu, W, H)
+    plain_after = read_frame(gpu, W, H)
     for k in ("fb", "lin", "xyz", "rowmajor"):
         assert_planes_equal(split[k], plain[k], "%s spectral vs plain %s" % (name, k))
         assert_planes_equal(one[k], plain[k], "%s one-pass spectral vs plain %s" % (name, k))
@@ -134,21 +131,11 @@ def test_film_is_additive_and_split_invariant(srt, gpu, name):
 @pytest.mark.gpu
 @pytest.mark.parametrize("knobs,paired,expect", EVERY_SHAPE_CASES, ids=EVERY_SHAPE_IDS)
 def test_every_spectral_shape_gives_the_same_film(srt, gpu, knobs, paired, expect):
-    n = 600 if paired else 601
-    scene = _soup(srt, n, n).build_bvh(srt.BVH_SAH, 1984)
-    assert scene.is_paired == paired
-    W, H, depth = 48, 32, 8
-    cam = srt.camera_init(W, H, 50.0, (0.5, 1.0, 16.0), (0.0, 0.0, 0.0), defocus_angle=0.6, focus_dist=14.0)
+    scene, cam, W, H, depth = shape_case(srt, paired)
     gpu.set_test_knobs()
-    ref, film_ref = _spectral(gpu, scene, cam, W, H, depth, [3, 5])
-    gpu.set_test_knobs(**knobs)
-    try:
-        got, film = _spectral(gpu, scene, cam, W, H, depth, [3, 5])
-        plan = gpu.launch_plan()
-        assert (int(plan["narrow_refs"]), int(plan["all_cached"]), int(plan["paired"])) == expect, plan
-    finally:
-        gpu.set_test_knobs()
-        gpu.upload_scene(scene)
+    ref, film_ref = spectral_run(gpu, scene, cam, W, H, depth, [3, 5])
+    with forced_shape(gpu, scene, knobs, expect):
+        got, film = spectral_run(gpu, scene, cam, W, H, depth, [3, 5])
     assert np.array_equal(bits(film), bits(film_ref)), expect
     assert film_ref.max() > 0
     for k in ("fb", "lin", "xyz", "rowmajor"):
@@ -157,14 +144,14 @@ def test_every_spectral_shape_gives_the_same_film(srt, gpu, knobs, paired, expec
 
 @pytest.mark.gpu
 def test_partitions_offset_chunk_and_sub_range(srt, gpu):
-    scene, cam, W, H, depth, _ = _workload(srt, "random_spheres")
+    scene, cam, W, H, depth, _ = named_workload(srt, "random_spheres")
     passes = [3, 4]
-    _, ref = _spectral(gpu, scene, cam, W, H, depth, passes)
+    _, ref = spectral_run(gpu, scene, cam, W, H, depth, passes)
     assert ref.max() > 0
     for world in (2, 3):
         films = []
         for rank in range(world):
-            _fresh(gpu, scene, cam, W, H, depth)
+            fresh_context(gpu, scene, cam, W, H, depth)
             gpu.set_partition(rank, world)
             gpu.accum_reset_spectral()
             for s in passes:
@@ -182,7 +169,7 @@ def test_partitions_offset_chunk_and_sub_range(srt, gpu):
     gpu.set_partition(0, 1)
 
     # sub-ranges of the full read
-    _, full = _spectral(gpu, scene, cam, W, H, depth, passes)
+    _, full = spectral_run(gpu, scene, cam, W, H, depth, passes)
     for first, count in ((0, 1), (10, 17), (94, 1), (0, 95), (47, 48)):
         part = gpu.read_spectral(W, H, first, count)
         assert part.shape == (H, W, count)
@@ -191,7 +178,7 @@ def test_partitions_offset_chunk_and_sub_range(srt, gpu):
     # a 30 x 20 chunk at (17, 9) of a 64 x 40 image writes its rectangle of the caller's array and nothing else
     IW, IH, cw, ch, ox, oy = 64, 40, 30, 20, 17, 9
     cam = scene.default_camera(IW, IH)
-    _fresh(gpu, scene, cam, cw, ch, depth)
+    fresh_context(gpu, scene, cam, cw, ch, depth)
     gpu.accum_reset_spectral()
     for s in passes:
         gpu.render_chunk_accum(cw, ch, s, ox, oy)
@@ -204,9 +191,7 @@ def test_partitions_offset_chunk_and_sub_range(srt, gpu):
     assert (out[inside] >= 0).all() and out[inside].max() > 0
     full = gpu.read_spectral(IW, IH)
     assert np.array_equal(bits(out[inside]), bits(full[inside][:, 40:52]))
-    y = np.zeros(IW * IH, np.float32)
-    gpu._ck(gpu_lib().srt_read_accum_stats(gpu._h, None, y.ctypes.data_as(C.POINTER(C.c_float)), None, IW, IH))
-    y = y.reshape(IH, IW)
+    y = read_sum_y(gpu, IW, IH).reshape(IH, IW)
     got_y = srt.film_to_xyz(full)[..., 1]
     np.testing.assert_allclose(got_y[inside], y[inside], rtol=2e-4, atol=1e-9)
     assert (full[~inside] == 0).all()
@@ -216,6 +201,7 @@ def test_partitions_offset_chunk_and_sub_range(srt, gpu):
 def test_comm_two_and_three_ranks_one_gpu_mock_transport():
     run_mock_transport_child("""
 import numpy as np
+from accum_helpers import comm_accumulations
 from helpers import assert_planes_equal, bits
 scene = srt.Scene.builtin(srt.SCENE_RANDOM_SPHERES).build_bvh(srt.BVH_SAH, 1984)
 W, H, depth = 150, 90, 16
@@ -224,22 +210,14 @@ steps = list(srt.render_spectral(scene, cam, W, H, [4, 4], depth))
 total, ref, _ = steps[-1]
 assert total == 8 and ref['film'].max() > 0
 for world in (2, 3):
-    comm = srt.Comm.init_all([0] * world)
-    comm.set_gather_planes(9)
-    comm.upload_scene(scene); comm.set_camera(cam)
-    comm.init_device_params(W, H, 8, depth, 1984)
-    comm.accum_reset_spectral()
-    for s in (4, 4):
-        comm.render_frame_accum(W, H, s)
-    comm.synchronize()
-    root = comm.root
-    assert_planes_equal(root.read_fb(), ref['fb'], 'world %d fb' % world)
-    assert_planes_equal(root.read_fb_aux(2), ref['xyz'], 'world %d xyz' % world)
-    film = comm.read_spectral(W, H)
-    assert np.array_equal(bits(film), bits(ref['film'])), world
-    part = comm.read_spectral(W, H, 30, 5)
-    assert np.array_equal(bits(part), bits(ref['film'][..., 30:35])), world
-    comm.close()
+    for _, comm in comm_accumulations(srt, world, (9,), scene, cam, W, H, depth, 8, lambda c: c.accum_reset_spectral(), (4, 4)):
+        root = comm.root
+        assert_planes_equal(root.read_fb(), ref['fb'], 'world %d fb' % world)
+        assert_planes_equal(root.read_fb_aux(2), ref['xyz'], 'world %d xyz' % world)
+        film = comm.read_spectral(W, H)
+        assert np.array_equal(bits(film), bits(ref['film'])), world
+        part = comm.read_spectral(W, H, 30, 5)
+        assert np.array_equal(bits(part), bits(ref['film'][..., 30:35])), world
 r = srt.Renderer(0)
 c1 = srt.Comm.init_rank(r, srt.Comm.unique_id(), 0, 1)
 c1.set_gather_planes(9)
@@ -263,7 +241,7 @@ def test_estimator_recovers_a_constant_background(srt, gpu):
     scene = _miss_scene(srt, np.full(N_GRID, c, np.float32))
     W = H = 128
     spp = 256
-    _, film = _spectral(gpu, scene, _miss_camera(srt, W, H), W, H, 4, [spp])
+    _, film = spectral_run(gpu, scene, _miss_camera(srt, W, H), W, H, 4, [spp])
     L = srt.spectral_radiance(film, spp).reshape(-1, N_GRID).mean(axis=0)
     rel = np.abs(L / c - 1.0)
     assert rel.max() < 0.01, (int(rel.argmax()), float(rel.max()))
@@ -275,7 +253,7 @@ def test_estimator_recovers_a_constant_background(srt, gpu):
 
 @pytest.mark.gpu
 def test_refusals_and_invalidation(srt, gpu):
-    scene, cam, W, H, depth, _ = _workload(srt, "prism")
+    scene, cam, W, H, depth, _ = named_workload(srt, "prism")
     L = gpu_lib()
     buf = np.zeros(W * H * N_GRID, np.float32)
     fp = buf.ctypes.data_as(C.POINTER(C.c_float))
@@ -285,36 +263,36 @@ def test_refusals_and_invalidation(srt, gpu):
         assert L.srt_accum_reset_spectral(fresh._h) == ERR_INVALID
     finally:
         fresh.close()
-    _fresh(gpu, scene, cam, W, H, depth)
+    fresh_context(gpu, scene, cam, W, H, depth)
     # a plain accumulation has no film
     gpu.accum_reset()
     gpu.render_chunk_accum(W, H, 2)
-    _expect_error(srt, lambda: gpu.read_spectral(W, H), ERR_INVALID, "read of a plain accumulation")
+    expect_error(srt, lambda: gpu.read_spectral(W, H), ERR_INVALID, "read of a plain accumulation")
     gpu.accum_reset_spectral()
-    _expect_error(srt, lambda: gpu.read_spectral(W, H), ERR_INVALID, "read before the first pass")
+    expect_error(srt, lambda: gpu.read_spectral(W, H), ERR_INVALID, "read before the first pass")
     gpu.render_chunk_accum(W, H, 4)
     first = gpu.read_spectral(W, H)
-    frame = _frame(gpu, W, H)
+    frame = read_frame(gpu, W, H)
     for f0, n in ((0, 0), (90, 6), (95, 1), (0, 96), (0xffffffff, 2)):
         assert L.srt_read_spectral(gpu._h, f0, n, fp, W, H) == ERR_INVALID, (f0, n)
     assert L.srt_read_spectral(gpu._h, 0, 95, None, W, H) == ERR_INVALID
     assert L.srt_read_spectral(gpu._h, 0, 95, fp, 0, H) == ERR_INVALID
     # a refused reset (instrumented context) leaves the accumulation usable
     gpu.set_count_traversal(True)
-    _expect_error(srt, lambda: gpu.accum_reset_spectral(), ERR_UNSUPPORTED, "instrumented context")
+    expect_error(srt, lambda: gpu.accum_reset_spectral(), ERR_UNSUPPORTED, "instrumented context")
     gpu.set_count_traversal(False)
     assert gpu.accum_samples == 4
     assert np.array_equal(bits(gpu.read_spectral(W, H)), bits(first))
-    for k, v in _frame(gpu, W, H).items():
+    for k, v in read_frame(gpu, W, H).items():
         assert_planes_equal(v, frame[k], "after the refusal " + k)
     gpu.render_chunk_accum(W, H, 4)
     assert gpu.accum_samples == 8 and gpu.stats()["paths"] == W * H * 4
-    _, want = _spectral(gpu, scene, cam, W, H, depth, [8])
-    _fresh(gpu, scene, cam, W, H, depth)
+    _, want = spectral_run(gpu, scene, cam, W, H, depth, [8])
+    fresh_context(gpu, scene, cam, W, H, depth)
     gpu.accum_reset_spectral()
     gpu.render_chunk_accum(W, H, 4)
     gpu.set_count_traversal(True)
-    _expect_error(srt, lambda: gpu.accum_reset_spectral(), ERR_UNSUPPORTED, "instrumented context")
+    expect_error(srt, lambda: gpu.accum_reset_spectral(), ERR_UNSUPPORTED, "instrumented context")
     gpu.set_count_traversal(False)
     gpu.render_chunk_accum(W, H, 4)
     assert np.array_equal(bits(gpu.read_spectral(W, H)), bits(want))
@@ -324,20 +302,20 @@ def test_refusals_and_invalidation(srt, gpu):
                        ("srt_init_device_params", lambda: gpu.init_device_params(W, H, 12, depth, 1984)),
                        ("srt_accum_reset", lambda: gpu.accum_reset()),
                        ("srt_accum_reset_adaptive", lambda: gpu.accum_reset_adaptive(0.1, 0.0, 4))):
-        _fresh(gpu, scene, cam, W, H, depth)
+        fresh_context(gpu, scene, cam, W, H, depth)
         gpu.accum_reset_spectral()
         gpu.render_chunk_accum(W, H, 2)
         gpu.read_spectral(W, H)
         call()
         if what.startswith("srt_accum_reset"):
             gpu.render_chunk_accum(W, H, 2)      # a pass of the new accumulation, which keeps no film
-        _expect_error(srt, lambda: gpu.read_spectral(W, H), ERR_INVALID, what)
+        expect_error(srt, lambda: gpu.read_spectral(W, H), ERR_INVALID, what)
     gpu.set_gather_planes(9)
 
 
 @pytest.mark.gpu
 def test_render_spectral_generator(srt, gpu):
-    scene, cam, W, H, depth, _ = _workload(srt, "cornell")
+    scene, cam, W, H, depth, _ = named_workload(srt, "cornell")
     steps = list(srt.render_spectral(scene, cam, W, H, [3, 5], depth, renderer=gpu))
     assert [t for t, _, _ in steps] == [3, 8]
     for t, res, rad in steps:

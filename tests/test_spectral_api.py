@@ -8,7 +8,7 @@ import re
 import numpy as np
 import pytest
 
-from accum_helpers import ERR_INVALID, ROOT, SHAPES, _kernel_id
+from accum_helpers import ERR_INVALID, ROOT, SHAPES, kernel_id
 
 NEW_SYMBOLS = ("srt_accum_reset_spectral", "srt_read_spectral", "srt_comm_accum_reset_spectral")
 SPECTRAL_SYM = re.compile(r"^_ZN3srt13render_kernelILi5ELb([01])ELb([01])ELb([01])EEEvNS_12RenderParamsE$")
@@ -39,7 +39,7 @@ def test_new_symbols_are_declared_bound_and_exported(srt):
 
 def test_code_object_holds_every_spectral_variant(srt):
     found = set()
-    for name, _ in _kernel_id().gfx950_functions(srt.binding.LIB_PATH):
+    for name, _ in kernel_id().gfx950_functions(srt.binding.LIB_PATH):
         m = SPECTRAL_SYM.match(name)
         if m:
             found.add(tuple(int(g) for g in m.groups()))

@@ -7,7 +7,7 @@ import re
 
 import pytest
 
-from accum_helpers import ROOT, SHAPES, _kernel_id
+from accum_helpers import ROOT, SHAPES, kernel_id
 
 NEW_SYMBOLS = ("srt_accum_reset_streams", "srt_accum_streams", "srt_comm_accum_reset_streams")
 # render_kernel<6, NARROW, ALL_CACHED, PAIRED>
@@ -32,18 +32,18 @@ def test_new_symbols_are_declared_bound_and_exported(srt):
 
 def test_code_object_holds_every_streamed_variant(srt):
     found = set()
-    for name, _ in _kernel_id().gfx950_functions(srt.binding.LIB_PATH):
+    for name, _ in kernel_id().gfx950_functions(srt.binding.LIB_PATH):
         m = STREAMS_SYM.match(name)
         if m:
             found.add(tuple(int(g) for g in m.groups()))
     assert found == SHAPES, sorted(found)
     # ... and the tool that compares two builds kernel by kernel sees them
-    assert {k[1:] for k in _kernel_id().render_code_hashes(srt.binding.LIB_PATH) if k[0] == 6} == SHAPES
+    assert {k[1:] for k in kernel_id().render_code_hashes(srt.binding.LIB_PATH) if k[0] == 6} == SHAPES
 
 
 def test_production_kernels_are_still_found_by_kernel_id(srt):
     """the streamed variant is a separate instantiation: the six MODE 0 kernels are all still there for bench.py's hash tie"""
-    hs = _kernel_id().code_hashes(srt.binding.LIB_PATH)
+    hs = kernel_id().code_hashes(srt.binding.LIB_PATH)
     assert set(hs) == {(1, 1, 1), (0, 0, 1), (1, 1), (1, 0), (0, 1), (0, 0)}, sorted(hs)
 
 

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import schedule_policy as SP
-from accum_helpers import NEVER, _adaptive, _fresh, _predict, _workload
+from accum_helpers import NEVER, adaptive_run, fresh_context, named_workload, predict_stops
 
 ERR_INVALID = -1
 # The kernel sums at most 4097 positive float32 terms with atomics in any order: relative error at most n * 2^-24 = 2.4e-4.  A halving
@@ -391,14 +391,14 @@ def test_streamed_pass_plans_for_a_quarter_of_the_waves(srt, gpu):
 def test_compacted_queue_keeps_the_probes_order(srt, gpu):
     """Three adaptive passes of 16 samples.  After pass p the compacted queue is the probe's rows whose share holds a pixel that
     pass p + 1 then renders (its sample count grows), in the probe's order, once each; the second compaction removes rows again."""
-    scene, cam, W, H, depth, _ = _workload(srt, "dielectric")
+    scene, cam, W, H, depth, _ = named_workload(srt, "dielectric")
     # the tolerance: the middle one of a grid under which, by the criterion's restatement on a run that never stops, fewer pixels are
     # active after every pass and some still are after the second
-    never = _adaptive(gpu, scene, cam, W, H, depth, NEVER, sched=[16, 16], min_spp=16)
-    shrinking = [float(rel) for rel in np.geomspace(1e-3, 10.0, 81) if W * H > _predict(never, float(rel), min_spp=16)[2][0] > _predict(never, float(rel), min_spp=16)[2][1] > 0]
+    never = adaptive_run(gpu, scene, cam, W, H, depth, NEVER, sched=[16, 16], min_spp=16)
+    shrinking = [float(rel) for rel in np.geomspace(1e-3, 10.0, 81) if W * H > predict_stops(never, float(rel), min_spp=16)[2][0] > predict_stops(never, float(rel), min_spp=16)[2][1] > 0]
     assert shrinking, "no tolerance lets the active pixels shrink over two passes"
     rel_tol = shrinking[len(shrinking) // 2]
-    _fresh(gpu, scene, cam, W, H, depth, spp=48)
+    fresh_context(gpu, scene, cam, W, H, depth, spp=48)
     gpu.accum_reset_adaptive(rel_tol, 0.0, 16)
     grid = SP.TileGrid(gpu.geom, W, H)
     gpu.render_chunk_accum(W, H, 16)
