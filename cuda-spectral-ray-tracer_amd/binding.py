@@ -124,6 +124,8 @@ PROTOTYPES = {
     "srt_read_accum_stats": (_i, [_vp, C.POINTER(_u32), _fp, _fp, _u32, _u32]),
     "srt_accum_reset_spectral": (_i, [_vp]),
     "srt_read_spectral": (_i, [_vp, _u32, _u32, _fp, _u32, _u32]),
+    "srt_accum_reset_features": (_i, [_vp]),
+    "srt_read_features": (_i, [_vp, _fp, _u32, _u32]),
     "srt_accum_reset_streams": (_i, [_vp, _u32]),
     "srt_accum_streams": (_i, [_vp, C.POINTER(_u32)]),
     "srt_set_gather_planes": (_i, [_vp, _u32]),
@@ -170,6 +172,7 @@ PROTOTYPES = {
     "srt_comm_accum_reset_adaptive": (_i, [_vp, C.POINTER(Adaptive)]),
     "srt_comm_accum_active": (_i, [_vp, C.POINTER(_u64)]),
     "srt_comm_accum_reset_spectral": (_i, [_vp]),
+    "srt_comm_accum_reset_features": (_i, [_vp]),
     "srt_comm_accum_reset_streams": (_i, [_vp, _u32]),
     "srt_comm_synchronize": (_i, [_vp]),
     "srt_comm_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_f)]),

@@ -56,6 +56,7 @@ struct srt_ctx {
     std::string err;
     // scene images in HBM (floats)
     DeviceBuffer d_nodes, d_nodes_sw, d_fringe, d_tris, d_mat_sd, d_mat_par, d_shade, d_cmf;
+    DeviceBuffer d_mat_col;            // per material one float4 (srt_material.col, 0): the albedo of the first-hit features (MODE 7)
     int root_ref = 0, stack_depth = 1, n_inner = 0, n_records = 0;
     bool paired = false;               // the uploaded tree has no node with exactly one leaf child (srt_scene_is_paired)
     uint32_t fringe_stride = 96;       // bytes between FRINGE records in d_fringe
@@ -117,7 +118,7 @@ struct srt_ctx {
     // The one accumulation of a context (srt_accum_reset*, srt_render_chunk_accum).
     struct Accumulation {
         enum class State { Invalid, Empty, Bound } state = State::Invalid;   // Empty: reset, no pass yet; Bound: passes of one chunk
-        enum class Kind { Plain, Adaptive, Spectral, Streams } kind = Kind::Plain;    // MODE 3 / 4 / 5 / 6 passes (never two of the last three)
+        enum class Kind { Plain, Adaptive, Spectral, Streams, Features } kind = Kind::Plain;    // MODE 3 / 4 / 5 / 6 / 7 passes (never two of the last four)
         uint32_t total = 0;                             // samples per pixel in the sums (streamed: over all streams)
         uint32_t n_streams = 1;                         // streamed: the RNG streams per pixel (K); 1 otherwise
         uint32_t w = 0, h = 0, offx = 0, offy = 0;      // the chunk of the first pass
@@ -128,6 +129,7 @@ struct srt_ctx {
         bool adaptive() const { return kind == Kind::Adaptive; }
         bool spectral() const { return kind == Kind::Spectral; }
         bool streamed() const { return kind == Kind::Streams; }
+        bool featured() const { return kind == Kind::Features; }
     } accum;
     // the buffers behind it, allocated on first use:
     DeviceBuffer d_accum;                               // progressive rendering (AccumLayout)
@@ -135,6 +137,8 @@ struct srt_ctx {
     DeviceBuffer d_adapt_queue;                         // pixel queue of the next adaptive pass (AdaptQueue)
     DeviceBuffer d_film;                                // spectral film (srt_accum_reset_spectral): kFilmStride floats per lane
     DeviceBuffer d_film_staging;                        // row-major staging block of srt_read_spectral
+    DeviceBuffer d_features;                            // first-hit features (srt_accum_reset_features): kFeatureStride floats per lane
+    DeviceBuffer d_features_staging;                    // row-major staging block of srt_read_features
     DeviceBuffer d_streams;                             // sample-parallel pixels (srt_accum_reset_streams, StreamPlanes)
     uint32_t streams_seeded = 0;                        // the K whose RNG streams d_streams holds, seeded since the last srt_init_device_params (0: none)
 };
@@ -479,12 +483,12 @@ int combine_streams(srt_ctx *c, const Pass &ps, const RenderParams &p) {
 }
 
 // spp_add == 0: a plain launch of c->spp samples (Plain, or Counting when instrumented); spp_add > 0: an accumulating pass of spp_add
-// samples (Accum / Adaptive / Spectral / Streams) whose caller has checked the accumulation and enqueued its header.
+// samples (Accum / Adaptive / Spectral / Streams / Features) whose caller has checked the accumulation and enqueued its header.
 // width .. offy are already narrowed to 16 bit.
 int render_chunk_impl(srt_ctx *c, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy, uint32_t spp_add, hipStream_t st) {
     Pass ps = {};
     ps.spp_add = spp_add; ps.st = st;
-    ps.mode = !spp_add ? (c->count_traversal ? Counting : Plain) : c->accum.adaptive() ? Adaptive : c->accum.spectral() ? Spectral : c->accum.streamed() ? Streams : Accum;
+    ps.mode = !spp_add ? (c->count_traversal ? Counting : Plain) : c->accum.adaptive() ? Adaptive : c->accum.spectral() ? Spectral : c->accum.streamed() ? Streams : c->accum.featured() ? Features : Accum;
     ps.later = spp_add && c->accum.bound(); ps.plan = plan_of(c);
     ps.streams = ps.mode == Streams ? c->accum.n_streams : 1u;
     c->last_w = width; c->last_h = height; c->last_offx = offx; c->last_offy = offy;
@@ -632,6 +636,12 @@ int srt_upload_scene(srt_ctx *c, const srt_scene *s) {
     if ((rc = upload(c, c->d_mat_sd, f.mat_sd)) != SRT_OK) return rc;
     if ((rc = upload(c, c->d_mat_par, f.mat_par)) != SRT_OK) return rc;
     if ((rc = upload(c, c->d_shade, f.shade)) != SRT_OK) return rc;
+    {
+        std::vector<float> col(4 * s->mats.size(), 0.f);
+        for (size_t m = 0; m < s->mats.size(); m++)
+            for (int k = 0; k < 3; k++) col[4 * m + k] = s->mats[m].col[k];
+        if ((rc = upload(c, c->d_mat_col, col)) != SRT_OK) return rc;
+    }
     c->root_ref = f.root_ref; c->stack_depth = f.stack_depth; c->n_materials = (uint32_t)s->mats.size();
     c->n_inner = f.n_inner; c->n_records = f.n_records; c->n_tris = (uint32_t)s->raw.size();
     c->paired = tree_is_paired(*s);
@@ -787,6 +797,34 @@ int srt_accum_reset_spectral(srt_ctx *c) {
     HIP_TRY(c, hipMemcpy(&AccumLayout(c).header->film, &film, sizeof(film), hipMemcpyHostToDevice));
     HIP_TRY(c, hipDeviceSynchronize());
     c->accum.begin(srt_ctx::Accumulation::Kind::Spectral);
+    return SRT_OK;
+}
+
+int srt_accum_reset_features(srt_ctx *c) {
+    if (!c) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_features: null ctx");
+    // refusals first: a refused call leaves the context's accumulation as it was
+    if (c->count_traversal)
+        return fail(c, SRT_ERR_UNSUPPORTED, "srt_accum_reset_features: no instrumented accumulating kernel (srt_set_count_traversal(ctx, 0) first)");
+    if (!c->params_ready) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_features: device parameters must be set first (srt_init_device_params)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)c->n_lanes * kFeatureStride * sizeof(float);
+    if (c->d_features.bytes < bytes) {
+        // (the new rows are allocated before the old ones go: a failed allocation changes nothing)
+        DeviceBuffer rows;
+        HIP_TRY(c, rows.reserve(bytes));
+        c->d_features = std::move(rows);
+    }
+    int rc = srt_accum_reset(c);
+    if (rc != SRT_OK) return rc;
+    c->accum.invalidate();      // (until the rows are in place)
+    HIP_TRY(c, hipMemset(c->d_features.ptr, 0, bytes));
+    // the featured part of the header (the per-pass kernel rewrites only sums and spp_total)
+    AccumHeader h = {};
+    h.features = c->d_features.as<float>(); h.mat_col = c->d_mat_col.as<const float>();
+    const size_t tail = offsetof(AccumHeader, features);
+    HIP_TRY(c, hipMemcpy(&AccumLayout(c).header->features, reinterpret_cast<const char *>(&h) + tail, sizeof(h) - tail, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipDeviceSynchronize());
+    c->accum.begin(srt_ctx::Accumulation::Kind::Features);
     return SRT_OK;
 }
 
@@ -1021,6 +1059,24 @@ int srt_read_spectral(srt_ctx *c, uint32_t first, uint32_t count, float *out, ui
         HIP_TRY(c, launch_film_unswizzle(c->d_film.as<float>(), c->d_film_staging.as<float>(), first, count, rect.w, rect.h, c->tx, c->ty, c->bx, nullptr));
         const size_t row = (size_t)rect.w * count * sizeof(float), pitch = (size_t)image_width * count * sizeof(float);
         HIP_TRY(c, hipMemcpy2D(out + rect.first * count, pitch, c->d_film_staging.ptr, row, row, rect.h, hipMemcpyDeviceToHost));
+    }
+    HIP_TRY(c, hipDeviceSynchronize());
+    return SRT_OK;
+}
+
+int srt_read_features(srt_ctx *c, float *out, uint32_t image_width, uint32_t image_height) {
+    if (!c || !out || image_width == 0 || image_height == 0) return fail(c, SRT_ERR_INVALID, "srt_read_features: bad argument");
+    if (!c->accum.featured() || !c->accum.bound())
+        return fail(c, SRT_ERR_INVALID, "srt_read_features: no featured accumulation with a pass (srt_accum_reset_features and srt_render_chunk_accum first)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the chunk's rectangle, clipped to the reference grid and the image (srt_read_fb_rowmajor's placement): un-swizzled on the device
+    // into a [h][w][8] staging block, then one 2-D copy into the caller's [image_height][image_width][8] array
+    const ChunkRect rect = chunk_rect(c, image_width, image_height);
+    if (const size_t n = (size_t)rect.w * rect.h * kFeatureStride) {
+        HIP_TRY(c, c->d_features_staging.reserve(n * sizeof(float)));
+        HIP_TRY(c, launch_features_unswizzle(c->d_features.as<float>(), c->d_features_staging.as<float>(), rect.w, rect.h, c->tx, c->ty, c->bx, nullptr));
+        const size_t row = (size_t)rect.w * kFeatureStride * sizeof(float), pitch = (size_t)image_width * kFeatureStride * sizeof(float);
+        HIP_TRY(c, hipMemcpy2D(out + rect.first * kFeatureStride, pitch, c->d_features_staging.ptr, row, row, rect.h, hipMemcpyDeviceToHost));
     }
     HIP_TRY(c, hipDeviceSynchronize());
     return SRT_OK;

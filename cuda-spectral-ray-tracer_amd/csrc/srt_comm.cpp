@@ -380,6 +380,12 @@ int srt_comm_accum_reset_spectral(srt_comm *c) {
     return SRT_OK;
 }
 
+int srt_comm_accum_reset_features(srt_comm *c) {
+    if (!c) return cfail(c, SRT_ERR_INVALID, "srt_comm_accum_reset_features: null comm");
+    for (srt_ctx *x : c->ctx) { int rc = srt_accum_reset_features(x); if (rc != SRT_OK) return cfail(c, rc, srt_last_error(x)); }
+    return SRT_OK;
+}
+
 int srt_comm_accum_reset_streams(srt_comm *c, uint32_t streams) {
     if (!c) return cfail(c, SRT_ERR_INVALID, "srt_comm_accum_reset_streams: null comm");
     for (srt_ctx *x : c->ctx) { int rc = srt_accum_reset_streams(x, streams); if (rc != SRT_OK) return cfail(c, rc, srt_last_error(x)); }

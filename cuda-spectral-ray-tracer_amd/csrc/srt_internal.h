@@ -106,6 +106,8 @@ struct AccumHeader {
     float *film;
     uint32_t *stream_planes;
     uint32_t streams, pad3;
+    float *features;
+    const float *mat_col;
 };
 // Spectral accumulations (MODE 5, srt_accum_reset_spectral) read `film` as well: kFilmStride floats per lane of the grid, indexed by the
 // block-linear idx, of which the first kFilmSamples are the raw sums on the CIE grid (360 + 5 j nm); srt_accum_reset_spectral writes it once.
@@ -115,6 +117,11 @@ struct AccumHeader {
 // RenderParams::rng: the k = 0 entries of these six planes are not used), planes 6 .. 8 (kStreamSumPlane) its XYZ sum.  MODE 6 writes no
 // tile-buffer slot: stream_combine_kernel adds the K sums in stream order into `sums` and converts.  srt_accum_reset_streams writes the
 // two fields once.
+// Featured accumulations (MODE 7, srt_accum_reset_features) read the two fields behind `pad3` instead: features, kFeatureStride floats per
+// lane of the grid indexed by the block-linear idx -- the raw first-hit sums [0..2] normal, [3..5] albedo, [6] distance, [7] hits -- and
+// mat_col, the scene's per-material colour table (one float4 per material: srt_material.col, 0), uploaded with the scene.
+// srt_accum_reset_features writes the two fields once.
+constexpr uint32_t kFeatureStride = 8;      // 32 B per pixel: two 16-byte accesses
 constexpr uint32_t kStreamSumPlane = 6;
 constexpr uint32_t kMaxStreams = 16;      // SRT_MAX_STREAMS (srt_c_api.h)
 constexpr uint32_t kFilmSamples = 95;
@@ -142,8 +149,9 @@ hipError_t launch_init_rng(uint32_t *rng, uint32_t n_lanes, uint64_t seed, hipSt
 // the kernel variant / cache size a launch plan would not pick by itself, so that every instantiated variant can be held to the CPU oracle by the tests.
 struct PlanKnobs { bool wide_refs = false; int lds_cache_max = -1; };
 // The render launch's variant; the values are render_kernel's MODE template argument.  Plain: render; Counting: instrumented; Probe: cost
-// probe; Accum: accumulating render (p.wave_debug -> AccumHeader); Adaptive / Spectral / Streams: adaptive / spectral / streamed accumulating render.
-enum RenderMode { Plain = 0, Counting = 1, Probe = 2, Accum = 3, Adaptive = 4, Spectral = 5, Streams = 6 };
+// probe; Accum: accumulating render (p.wave_debug -> AccumHeader); Adaptive / Spectral / Streams / Features: adaptive / spectral / streamed /
+// featured accumulating render.
+enum RenderMode { Plain = 0, Counting = 1, Probe = 2, Accum = 3, Adaptive = 4, Spectral = 5, Streams = 6, Features = 7 };
 hipError_t launch_render(const RenderParams &p, const PlanKnobs &knobs, uint32_t n_cu, RenderMode mode, hipStream_t st);
 hipError_t launch_accum_header(AccumHeader *dst, float *sums, uint32_t spp_total, hipStream_t st);      // writes *dst on the stream
 // Pixel queue of the next adaptive pass (see adapt_flag_kernel): the rows of `src_rows` (src_info[0] of them; nullptr: the identity
@@ -162,6 +170,8 @@ hipError_t launch_adapt_queue(const AdaptQueueParams &p, uint32_t n_rows_bound, 
 // The film's grid samples [first, first + count) of the w x h pixels at the chunk's origin -> dst[((y * w) + x) * count + (j - first)].
 hipError_t launch_film_unswizzle(const float *film, float *dst, uint32_t first, uint32_t count, uint32_t w, uint32_t h, uint32_t tx,
                                  uint32_t ty, uint32_t bx, hipStream_t st);
+// The feature rows of the w x h pixels at the chunk's origin -> dst[((y * w) + x) * 8 + c].
+hipError_t launch_features_unswizzle(const float *rows, float *dst, uint32_t w, uint32_t h, uint32_t tx, uint32_t ty, uint32_t bx, hipStream_t st);
 // After a streamed pass (MODE 6): every pixel of this rank's share of the chunk adds its K stream sums in stream order into the
 // accumulation's sum planes and writes its tile-buffer slots from them, as MODE 3's pixel switch does.
 struct StreamCombineParams {

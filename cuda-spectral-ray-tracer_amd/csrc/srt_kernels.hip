@@ -178,6 +178,9 @@ __device__ __forceinline__ bool adaptive_converged(float s1, float s2, uint32_t 
 // counter hand the K streams of an expensive tile to K different workgroups), and the lane's idx is idx' = k * n_lanes + idx, its slot in
 // the stream planes (AccumHeader::stream_planes; stream 0 -- idx' < n_lanes -- keeps its RNG state in the context's own planes).  The
 // pixel switch stores RNG state and sums and nothing else: stream_combine_kernel adds the streams and writes the tile buffer.
+// MODE 7: MODE 3 of a featured accumulation (srt_accum_reset_features) -- the shading of a sample's FIRST closest-hit query (bounce == 0)
+// that found a triangle also adds (face-forwarded normal, the material's colour, t * |d|, 1) to the pixel's own row of eight fp32 sums
+// (AccumHeader::features, kFeatureStride floats per lane): a read-modify-write in memory, like the film's, drawing nothing from the RNG.
 // ALL_CACHED: the whole inner tree fits the LDS cache (n_cached == n_inner): the INNER step has no global fall-back path.
 // PAIRED (instantiated for <., 1, 1> and <., 0, 0>): every FRINGE record holds two triangles (srt_scene_is_paired): the visit has no box test.
 template <int MODE, bool NARROW, bool ALL_CACHED, bool PAIRED>
@@ -185,10 +188,11 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
     constexpr bool COUNT = (MODE == 1);
     constexpr bool PROBE = (MODE == 2);
     constexpr bool ITERS = COUNT || PROBE;
-    constexpr bool ACCUM = (MODE == 3 || MODE == 4 || MODE == 5);
+    constexpr bool ACCUM = (MODE == 3 || MODE == 4 || MODE == 5 || MODE == 7);
     constexpr bool ADAPT = (MODE == 4);
     constexpr bool FILM = (MODE == 5);
     constexpr bool STREAMS = (MODE == 6);
+    constexpr bool FEATURES = (MODE == 7);
     // (S2 of the current pixel: in a register -- acc2 -- except in the wide-reference, partly-L2, unpaired shape, which is at the
     // 128-VGPR limit already and would spill it to scratch: there each path end adds its y * y to the pixel's own S2 word in memory.
     // The same additions in the same order: the result is the same bits.  profiles/adaptive/mode4_resource_usage.txt)
@@ -234,6 +238,10 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
             U->min_spp = ah->min_spp; U->rel_tol = ah->rel_tol; U->abs_tol = ah->abs_tol;
         }
         if constexpr (FILM) split_ptr(reinterpret_cast<const AccumHeader *>(P.wave_debug)->film, U->accum_film);
+        if constexpr (FEATURES) {      // (the uniform block is full: MODE 7 never runs with MODE 4 or 5, whose pointer slots carry its two)
+            const AccumHeader *ah = reinterpret_cast<const AccumHeader *>(P.wave_debug);
+            split_ptr(ah->features, U->accum_film); split_ptr(ah->mat_col, U->accum_sum2);
+        }
         if constexpr (STREAMS) {
             const AccumHeader *ah = reinterpret_cast<const AccumHeader *>(P.wave_debug);
             split_ptr(ah->stream_planes, U->accum_sums);
@@ -397,6 +405,36 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
                         } else {
                             scatter_direction = n + ruv;                                   // lambertian_scatter, :8-19
                             if (near_zero(scatter_direction)) scatter_direction = n;
+                        }
+                    }
+                    if constexpr (FEATURES) {
+                        // the first-hit deposit (srt_c_api.h, srt_accum_reset_features), behind the scatter, whose operands are dead by now: rd is
+                        // still the camera ray's unnormalised direction and tv.c the accepted hit parameter.  Two 16-byte read-modify-writes on
+                        // the pixel's own row, which only this lane writes in a launch: no atomics, and no register lives across the traversal
+                        // for it.  The colour comes through a range-checked buffer load: a material index beyond the table adds +0.
+                        if (bounce == 0u) {
+                            // (the two pointers are wave-uniform: read through readfirstlane, the descriptor is built in scalar registers)
+                            const uint32_t rows_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)U->accum_film[0]), rows_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)U->accum_film[1]);
+                            const uint32_t col_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)U->accum_sum2[0]), col_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)U->accum_sum2[1]);
+                            float4 *row = join_ptr<float4>(rows_lo, rows_hi) + (size_t)idx * (kFeatureStride / 4u);
+                            const buf_rsrc col_rsrc = make_rsrc(join_ptr<const float>(col_lo, col_hi), P.n_materials * 16u);
+                            const uint32_t col_off = (mat < P.n_materials ? mat : P.n_materials) * 16u;
+                            // (one half of the row after the other, each with the part of the colour it needs: the wide / partly-cached /
+                            // unpaired shape has no registers left for both halves at once)
+                            {
+                                float4 f = row[0];
+                                const float red = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(col_rsrc, (int)col_off, 0, 0));
+                                f.x = f.x + n.x; f.y = f.y + n.y; f.z = f.z + n.z; f.w = f.w + red;
+                                row[0] = f;
+                            }
+                            asm volatile("" ::: "memory");
+                            {
+                                float4 f = row[1];
+                                const float2 gb = buf_load8(col_rsrc, col_off + 4u);
+                                const float dist = tv.c * sqrtf((rd.x * rd.x + rd.y * rd.y) + rd.z * rd.z);
+                                f.x = f.x + gb.x; f.y = f.y + gb.y; f.z = f.z + dist; f.w = f.w + 1.0f;
+                                row[1] = f;
+                            }
                         }
                     }
                     sd_table = mat;
@@ -1175,13 +1213,14 @@ hipError_t launch_render(const RenderParams &p, const PlanKnobs &knobs, uint32_t
     const bool narrow = render_narrow_refs(p.n_records, knobs);
     if (mode == 1) return narrow ? launch_render_mode<1, true>(p, knobs, n_cu, st) : launch_render_mode<1, false>(p, knobs, n_cu, st);
     if (mode == 2) return narrow ? launch_render_mode<2, true>(p, knobs, n_cu, st) : launch_render_mode<2, false>(p, knobs, n_cu, st);
-    if (mode < 3 || mode > 6) return narrow ? launch_render_mode<0, true>(p, knobs, n_cu, st) : launch_render_mode<0, false>(p, knobs, n_cu, st);
+    if (mode < 3 || mode > 7) return narrow ? launch_render_mode<0, true>(p, knobs, n_cu, st) : launch_render_mode<0, false>(p, knobs, n_cu, st);
     // (instantiated after the production variants: their place in the object, and so the labels of their ISA listing, stay as they were)
     if (mode == 3) return narrow ? launch_render_mode<3, true>(p, knobs, n_cu, st) : launch_render_mode<3, false>(p, knobs, n_cu, st);
     // (and the adaptive ones after the accumulating ones, the spectral ones after those, for the same reason)
     if (mode == 4) return narrow ? launch_render_mode<4, true>(p, knobs, n_cu, st) : launch_render_mode<4, false>(p, knobs, n_cu, st);
     if (mode == 5) return narrow ? launch_render_mode<5, true>(p, knobs, n_cu, st) : launch_render_mode<5, false>(p, knobs, n_cu, st);
-    return narrow ? launch_render_mode<6, true>(p, knobs, n_cu, st) : launch_render_mode<6, false>(p, knobs, n_cu, st);
+    if (mode == 6) return narrow ? launch_render_mode<6, true>(p, knobs, n_cu, st) : launch_render_mode<6, false>(p, knobs, n_cu, st);
+    return narrow ? launch_render_mode<7, true>(p, knobs, n_cu, st) : launch_render_mode<7, false>(p, knobs, n_cu, st);
 }
 
 hipError_t launch_order_tiles(const uint32_t *cost, uint32_t *sorted, uint32_t *rows, uint32_t n, uint32_t n_waves,
@@ -1358,6 +1397,25 @@ __global__ __launch_bounds__(256) void stream_combine_kernel(const StreamCombine
 hipError_t launch_stream_combine(const StreamCombineParams &p, hipStream_t st) {
     if (p.tiles_local == 0) return hipSuccess;
     hipLaunchKernelGGL(stream_combine_kernel<0>, dim3((p.tiles_local + 3u) / 4u), dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+
+// The feature rows (MODE 7) -> the caller's row-major [row][col][8] layout: the w x h pixels at the chunk's origin, one thread per pixel,
+// two 16-byte copies.  A template, instantiated here at the end of the unit (see accum_header_kernel).
+template <int>
+__global__ __launch_bounds__(256) void features_unswizzle_kernel(const float4 *rows, float4 *dst, uint32_t w, uint32_t h, uint32_t tx, uint32_t ty, uint32_t bx) {
+    const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= (size_t)w * h) return;
+    const uint32_t y = (uint32_t)(pix / w), x = (uint32_t)(pix - (size_t)y * w);
+    const size_t src = (size_t)block_linear_idx(x, y, tx, ty, bx) * (kFeatureStride / 4u);
+    dst[2 * pix + 0] = rows[src + 0]; dst[2 * pix + 1] = rows[src + 1];
+}
+
+hipError_t launch_features_unswizzle(const float *rows, float *dst, uint32_t w, uint32_t h, uint32_t tx, uint32_t ty, uint32_t bx, hipStream_t st) {
+    const size_t n = (size_t)w * h;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(features_unswizzle_kernel<0>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const float4 *>(rows),
+                       reinterpret_cast<float4 *>(dst), w, h, tx, ty, bx);
     return hipGetLastError();
 }
 

@@ -9,6 +9,7 @@ import numpy as np
 from . import binding as B
 
 DEFAULT_TX, DEFAULT_TY = 28, 16   # render_manager.cu:93-94
+FEATURE_CHANNELS = 8              # first-hit sums per pixel: normal xyz, albedo rgb, distance, hits (srt_c_api.h, srt_accum_reset_features)
 FILM_SAMPLES = 95                 # the spectral film's grid: 360 + 5 j nm, j = 0 .. 94 (srt_c_api.h, srt_accum_reset_spectral)
 
 
@@ -136,6 +137,19 @@ class Renderer:
         assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == image_width * image_height * count
         self._ck(B.lib().srt_read_spectral(self._h, int(first), int(count), B.fptr(out), image_width, image_height))
         return out
+
+    def accum_reset_features(self):
+        """start a FEATURED accumulation (srt_c_api.h): like accum_reset, and each later pass also adds, at the first hit of every
+        sample's camera ray, the face-forwarded normal, the hit material's colour, the distance and 1 to the pixel's eight raw float32
+        sums (read_features; feature_means normalises them).  Never adaptive, spectral or streamed."""
+        self._ck(B.lib().srt_accum_reset_features(self._h))
+
+    def read_features(self, image_width, image_height):
+        """raw first-hit sums of the featured accumulation's chunk, float32: dict(normal (H, W, 3), albedo (H, W, 3), distance (H, W),
+        hits (H, W)); only the chunk's rectangle is written (zeros elsewhere, and at pixels of other ranks)"""
+        out = np.zeros((image_height, image_width, FEATURE_CHANNELS), np.float32)
+        self._ck(B.lib().srt_read_features(self._h, B.fptr(out), image_width, image_height))
+        return split_features(out)
 
     def accum_reset_streams(self, k):
         """start a STREAMED accumulation (srt_c_api.h): every pixel has k independent RNG streams (1 <= k <= MAX_STREAMS), stream j of lane
@@ -386,6 +400,11 @@ class Comm:
     def accum_reset_spectral(self):
         """Renderer.accum_reset_spectral on every local rank"""
         self._ck(B.lib().srt_comm_accum_reset_spectral(self._h))
+
+    def accum_reset_features(self):
+        """Renderer.accum_reset_features on every local rank (any communicator: no decision crosses ranks); the rows stay with their
+        ranks (Renderer.read_features per context: each pixel is owned by one rank and reads +0 on the others)"""
+        self._ck(B.lib().srt_comm_accum_reset_features(self._h))
 
     def accum_reset_streams(self, k):
         """Renderer.accum_reset_streams on every local rank (any communicator: no decision crosses ranks)"""
@@ -680,3 +699,41 @@ def _spectral_passes(scene, cam, width, height, sched, bounce_limit, seed, devic
             out = _collect(r, width, height)
             out["film"] = r.read_spectral(width, height, first, count)
             yield r.accum_samples, out, spectral_radiance(out["film"], r.accum_samples, first)
+
+
+def split_features(rows):
+    """(..., 8) first-hit rows -> dict(normal (..., 3), albedo (..., 3), distance (...), hits (...)), contiguous copies"""
+    rows = np.asarray(rows)
+    if rows.shape[-1] != FEATURE_CHANNELS:
+        raise ValueError("split_features: needs rows of %d channels, got %d" % (FEATURE_CHANNELS, rows.shape[-1]))
+    return dict(normal=np.ascontiguousarray(rows[..., 0:3]), albedo=np.ascontiguousarray(rows[..., 3:6]),
+                distance=np.ascontiguousarray(rows[..., 6]), hits=np.ascontiguousarray(rows[..., 7]))
+
+
+def feature_means(features, samples):
+    """per-pixel means from the raw first-hit sums of read_features (srt_c_api.h), float64: normal and albedo divided by the samples n the
+    pixel holds (a miss counts as a zero vector, so both fade with the coverage), distance divided by the hits (inf where no sample
+    hit), and coverage = hits / n.  samples: a scalar or an array broadcastable to features["hits"]; NaN where n == 0."""
+    n = np.asarray(samples, np.float64)
+    hits = np.asarray(features["hits"], np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return dict(normal=np.asarray(features["normal"], np.float64) / n[..., None], albedo=np.asarray(features["albedo"], np.float64) / n[..., None],
+                    distance=np.where(hits == 0, np.inf, np.asarray(features["distance"], np.float64) / hits), coverage=hits / n)
+
+
+def render_features(scene, cam, width, height, passes, bounce_limit, seed=1984, device=0, renderer=None):
+    """Progressive whole-image render with first-hit feature buffers on one GPU: a generator of (spp_total, result, features) after
+    each pass, `result` with the keys of render_image and `features` the raw sums of read_features (feature_means(features, spp_total)
+    normalises them).  The colour planes after the pass that brings the total to N are bit-identical to render_image(..., spp=N, ...),
+    as for render_progressive.  Checked before any device is touched."""
+    sched = progressive_schedule(passes)
+    return _features_passes(scene, cam, width, height, sched, bounce_limit, seed, device, renderer)
+
+
+def _features_passes(scene, cam, width, height, sched, bounce_limit, seed, device, renderer):
+    with _image_session(scene, cam, width, height, sum(sched), bounce_limit, seed, device, renderer) as r:
+        r.accum_reset_features()
+        for spp_add in sched:
+            r.render_chunk_accum(width, height, spp_add)
+            r.scatter_tiles()
+            yield r.accum_samples, _collect(r, width, height), r.read_features(width, height)

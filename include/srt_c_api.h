@@ -311,6 +311,40 @@ SRT_API int srt_read_accum_stats(srt_ctx *ctx, uint32_t *samples, float *sum_y, 
 SRT_API int srt_accum_reset_spectral(srt_ctx *ctx);
 SRT_API int srt_read_spectral(srt_ctx *ctx, uint32_t first, uint32_t count, float *out, uint32_t image_width, uint32_t image_height);
 
+/* First-hit feature buffers (no reference counterpart): the geometric side channels a denoiser or compositor takes as input.  A FEATURED
+ * accumulation is a plain progressive accumulation (the semantics of srt_accum_reset: passes of s1 .. sk samples equal one launch of
+ * their sum in every output above, RNG state included) that also keeps, per pixel, 8 raw fp32 sums F[0..7]:
+ *   F[0..2] normal, F[3..5] albedo, F[6] distance, F[7] hits.
+ * The deposit rule (render_kernel MODE 7):
+ *   - at the shading of the FIRST closest-hit query of every sample (the camera ray's, bounce 0), and only when that query found a
+ *     triangle: nothing on a miss, nothing for a query answered without traversal because its direction holds a NaN, nothing on later
+ *     bounces, and nothing at all with bounce_limit == 0;
+ *   - normal: the face-forwarded normal the shading forms (front_face ? n_geo : -n_geo);
+ *   - albedo: the hit material's srt_material.col, from a per-material table uploaded with the scene and read with a range-checked
+ *     load: a material index beyond the table adds +0;
+ *   - distance: t * sqrtf(dx*dx + dy*dy + dz*dz), t the accepted hit parameter and d the camera ray's unnormalised direction, the sum
+ *     left to right, fp32, not contracted;
+ *   - hits: 1.0f;
+ *   - F[c] = F[c] + f[c] in fp32, in sample order.
+ * The deposit draws nothing from the RNG and touches neither the image nor the path.  A pixel's row is written only by the lane that
+ * renders it (no atomics), so the eight sums are the same bits for every split into passes, launch shape, partition and world size.
+ * The device stores raw sums; with n the samples a pixel holds, normal / n and albedo / n are the means over all samples (a miss counts
+ * as zero), distance / hits the mean hit distance and hits / n the pixel's coverage.
+ *   srt_accum_reset_features  srt_accum_reset + zeroed feature rows (allocated on first use and when n_lanes grows, 32 B per lane of the
+ *                             grid).  Later srt_render_chunk_accum passes run MODE 7.  Refused with the previous accumulation unchanged:
+ *                             device parameters not set (SRT_ERR_INVALID); an instrumented context (SRT_ERR_UNSUPPORTED); a failed
+ *                             allocation (SRT_ERR_HIP).  Always a PLAIN accumulation: features combined with adaptive sampling, the
+ *                             spectral film or streams are NOT supported (adaptive + features is the intended next step: its output is
+ *                             what a denoiser takes).  srt_accum_reset, srt_accum_reset_adaptive, srt_accum_reset_spectral and
+ *                             srt_accum_reset_streams make the next accumulation non-featured again.  Invalidation, the 65535-sample
+ *                             limit and the chunk binding are those of srt_accum_reset.
+ *   srt_read_features         the raw sums of the accumulation's chunk, row-major: out[((y * image_width) + x) * 8 + c]; only the
+ *                             chunk's rectangle is written (the placement of srt_read_fb_rowmajor), pixels owned by other ranks read
+ *                             +0.  Synchronises.  SRT_ERR_INVALID without a featured accumulation with at least one pass, or for a
+ *                             null out. */
+SRT_API int srt_accum_reset_features(srt_ctx *ctx);
+SRT_API int srt_read_features(srt_ctx *ctx, float *out, uint32_t image_width, uint32_t image_height);
+
 /* Sample-parallel pixels (no reference counterpart; a deliberate departure from its one RNG stream per pixel, so opt-in).  A STREAMED
  * accumulation gives every pixel K independent RNG streams, each with its own state and its own XYZ sum, so that any lane of any wave
  * can render a stream while others render the pixel's other streams: the longest sequential chain of a pass is spp_add / K samples.
@@ -511,6 +545,10 @@ SRT_API int srt_comm_accum_active(srt_comm *comm, uint64_t *active);
 /* Spectral film on W GPUs: srt_accum_reset_spectral on every local context; srt_render_frame_multi_accum then runs MODE 5 on each rank.
  * The films stay with their ranks (srt_read_spectral per context; each pixel is owned by one rank and reads +0 on the others). */
 SRT_API int srt_comm_accum_reset_spectral(srt_comm *comm);
+/* First-hit features on W GPUs: srt_accum_reset_features on every local context; srt_render_frame_multi_accum then runs MODE 7 on each
+ * rank.  The rows stay with their ranks (srt_read_features per context; each pixel is owned by one rank and reads +0 on the others).  On
+ * process-per-GPU communicators too: no decision crosses ranks. */
+SRT_API int srt_comm_accum_reset_features(srt_comm *comm);
 /* Sample-parallel pixels on W GPUs: srt_accum_reset_streams on every local context; srt_render_frame_multi_accum then runs MODE 6 on each
  * rank.  On process-per-GPU communicators too: no decision crosses ranks (every rank resets with the same K). */
 SRT_API int srt_comm_accum_reset_streams(srt_comm *comm, uint32_t streams);
