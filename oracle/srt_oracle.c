@@ -837,6 +837,8 @@ static void ray_bounce(const orc_scene *sc, ray_t *r, uint32_t bounce_limit, orc
     r->valid_wavelengths = 0;
 }
 
+#define ORC_PATH_END_WORDS (2 * N_RAY_WAVELENGTHS + 1)   /* wavelengths[7], power_distr[7], valid_wavelengths (a uint32 word) */
+
 typedef struct {
     const orc_scene *sc;
     const orc_camera_data *cam;
@@ -849,6 +851,7 @@ typedef struct {
     float *fb_r, *fb_g, *fb_b;       /* block-linear, grid sized, quantised 0..255 */
     float *lin_r, *lin_g, *lin_b;    /* optional: sRGB in [0,1] before expand_sRGB */
     float *xyz_x, *xyz_y, *xyz_z;    /* optional: raw XYZ sums */
+    float *path_ends;                /* optional: ORC_PATH_END_WORDS words per lane and sample (orc_render_path_ends) */
     uint32_t block_lo, block_hi, block_stride; /* this call renders blocks b with b%stride==lo?  see worker */
     volatile uint32_t *next_block;
     orc_stats stats;
@@ -875,6 +878,12 @@ static void render_block_row(render_job *J, uint32_t block_idx, uint32_t tyi) {
                     get_ray(&r, J->offx + i, J->offy + j, J->cam, &rs);
                     J->stats.paths++;
                     ray_bounce(J->sc, &r, J->bounce_limit, &rs, &J->stats);
+                    if (J->path_ends) {                               /* what dev_spectrum_to_XYZ receives below */
+                        float *e = J->path_ends + ((size_t)idx * J->spp + k) * ORC_PATH_END_WORDS;
+                        memcpy(e, r.wavelengths, sizeof(r.wavelengths));
+                        memcpy(e + N_RAY_WAVELENGTHS, r.power_distr, sizeof(r.power_distr));
+                        memcpy(e + 2 * N_RAY_WAVELENGTHS, &r.valid_wavelengths, sizeof(uint32_t));
+                    }
                     pixel_color = vadd(pixel_color,
                                        dev_spectrum_to_XYZ(r.wavelengths, r.power_distr, N_RAY_WAVELENGTHS, r.valid_wavelengths));
                 }
@@ -1018,11 +1027,11 @@ ORC_API void orc_scene_get_tris(const orc_scene *sc, float *out) {
 /* One chunk of the image (render_manager.cu:3-66 -> rendering.cu:244-277), all blocks b with
  * b % block_stride == block_lo (block_stride = 1 renders everything; >1 is the multi-rank split).
  * Buffers are block-linear and grid sized (tx*bx*ty*by floats each).  states may be NULL. */
-ORC_API int orc_render(const orc_scene *sc, const orc_camera_data *cam, uint32_t spp, uint32_t bounce_limit, uint32_t tx,
-                       uint32_t ty, uint32_t bx, uint32_t by, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy,
-                       uint64_t seed_base, int reseed, orc_rng *states, uint32_t block_lo, uint32_t block_stride, float *fb_r,
-                       float *fb_g, float *fb_b, float *lin_r, float *lin_g, float *lin_b, float *xyz_x, float *xyz_y,
-                       float *xyz_z, int n_threads, orc_stats *stats_out) {
+static int render_chunk(const orc_scene *sc, const orc_camera_data *cam, uint32_t spp, uint32_t bounce_limit, uint32_t tx,
+                        uint32_t ty, uint32_t bx, uint32_t by, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy,
+                        uint64_t seed_base, int reseed, orc_rng *states, uint32_t block_lo, uint32_t block_stride, float *fb_r,
+                        float *fb_g, float *fb_b, float *lin_r, float *lin_g, float *lin_b, float *xyz_x, float *xyz_y,
+                        float *xyz_z, float *path_ends, int n_threads, orc_stats *stats_out) {
     if (!sc || !cam || !fb_r || !fb_g || !fb_b || tx == 0 || ty == 0 || block_stride == 0) return -1;
     if (!reseed && !states) return -2;
     /* Q17: the reference narrows these to 16 bit (rendering.cu:154,245) */
@@ -1042,6 +1051,7 @@ ORC_API int orc_render(const orc_scene *sc, const orc_camera_data *cam, uint32_t
         J->fb_r = fb_r; J->fb_g = fb_g; J->fb_b = fb_b;
         J->lin_r = lin_r; J->lin_g = lin_g; J->lin_b = lin_b;
         J->xyz_x = xyz_x; J->xyz_y = xyz_y; J->xyz_z = xyz_z;
+        J->path_ends = path_ends;
         J->block_lo = block_lo; J->block_hi = bx * by; J->block_stride = block_stride;
         J->next_block = &next;
     }
@@ -1061,6 +1071,29 @@ ORC_API int orc_render(const orc_scene *sc, const orc_camera_data *cam, uint32_t
     }
     free(jobs); free(th);
     return 0;
+}
+
+ORC_API int orc_render(const orc_scene *sc, const orc_camera_data *cam, uint32_t spp, uint32_t bounce_limit, uint32_t tx,
+                       uint32_t ty, uint32_t bx, uint32_t by, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy,
+                       uint64_t seed_base, int reseed, orc_rng *states, uint32_t block_lo, uint32_t block_stride, float *fb_r,
+                       float *fb_g, float *fb_b, float *lin_r, float *lin_g, float *lin_b, float *xyz_x, float *xyz_y,
+                       float *xyz_z, int n_threads, orc_stats *stats_out) {
+    return render_chunk(sc, cam, spp, bounce_limit, tx, ty, bx, by, width, height, offx, offy, seed_base, reseed, states, block_lo,
+                        block_stride, fb_r, fb_g, fb_b, lin_r, lin_g, lin_b, xyz_x, xyz_y, xyz_z, NULL, n_threads, stats_out);
+}
+
+/* orc_render, which also records the state of every path at its end -- what dev_spectrum_to_XYZ receives in render_block_row:
+ * path_ends holds ORC_PATH_END_WORDS words per lane of the grid and per sample, [lane][sample][wavelengths[7], power_distr[7],
+ * valid_wavelengths], tx*bx*ty*by * (uint16_t)spp * 15 words, zeroed by the caller: lanes outside the chunk (and blocks this call
+ * does not render) are not written.  The film deposit, the XYZ conversion and S2 are fixed functions of these words. */
+ORC_API int orc_render_path_ends(const orc_scene *sc, const orc_camera_data *cam, uint32_t spp, uint32_t bounce_limit, uint32_t tx,
+                                 uint32_t ty, uint32_t bx, uint32_t by, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy,
+                                 uint64_t seed_base, int reseed, orc_rng *states, uint32_t block_lo, uint32_t block_stride,
+                                 float *fb_r, float *fb_g, float *fb_b, float *lin_r, float *lin_g, float *lin_b, float *xyz_x,
+                                 float *xyz_y, float *xyz_z, float *path_ends, int n_threads, orc_stats *stats_out) {
+    if (!path_ends) return -1;
+    return render_chunk(sc, cam, spp, bounce_limit, tx, ty, bx, by, width, height, offx, offy, seed_base, reseed, states, block_lo,
+                        block_stride, fb_r, fb_g, fb_b, lin_r, lin_g, lin_b, xyz_x, xyz_y, xyz_z, path_ends, n_threads, stats_out);
 }
 
 /* render_manager.cuh:68-142: block-linear chunk buffer -> row-major image */

@@ -80,6 +80,53 @@ def fuzz_case(srt, seed):
     return scene, cam, W, H, spp, depth, mode, n
 
 
+EDGE_CASES = ["one_triangle", "two_triangles", "degenerate_and_odd_materials", "forty_materials"]
+
+
+def edge_case_scene(srt, case):
+    """Scenes that come in through srt_scene_set_* (not the built-ins): a BVH whose root is a leaf (bvh.cu:114-119), a two-leaf
+    tree (one FRINGE record, no INNER record), zero-area / needle triangles (NaN normal: every test on them fails, as in the
+    reference), material types the switch sends to its default branch (NO_MAT = 6, an unknown id), an emissive surface, and more
+    than 32 materials (the reference would read its 32-entry shared copy out of bounds, Q16; the build indexes the real table).
+    Returns scene (reference BVH built), camera, W, H, spp, depth."""
+    XY, NONE = 1, 0
+    wall = lambda z, m: [((-4, -4, z), (4, -4, z), (4, 4, z), m, NONE), ((-4, -4, z), (4, 4, z), (-4, 4, z), m, NONE)]
+    if case == "one_triangle":
+        tris = [((-3, -2, 0), (3, -2, 0), (0, 3, 0), 0, NONE)]
+        mats = [(srt.binding.MAT_LAMBERTIAN, (0.5, 0.5, 0.5), 0.0, 0.0)]
+    elif case == "two_triangles":
+        tris = wall(0.0, 0)
+        mats = [(srt.binding.MAT_METALLIC, (1.0, 1.0, 1.0), 0.3, 0.0)]
+    elif case == "degenerate_and_odd_materials":
+        tris = wall(0.0, 0) + wall(-1.5, 1) + [((0, 0, 1), (0, 0, 1), (0, 0, 1), 2, NONE),          # a point
+                                               ((-1, 0, 2), (0, 0, 2), (1, 0, 2), 3, NONE),          # a needle (collinear vertices)
+                                               ((-2, -2, 3), (2, -2, 3), (0, 2, 3), 4, XY)]
+        mats = [(srt.binding.MAT_NO_MAT, (1.0, 1.0, 1.0), 0.0, 0.0), (srt.binding.MAT_EMISSIVE, (1.0, 1.0, 1.0), 0.0, 3.0),
+                (srt.binding.MAT_DIELECTRIC, (1.0, 1.0, 1.0), 0.0, 0.0), (17, (0.5, 0.5, 0.5), 0.0, 0.0),
+                (srt.binding.MAT_DIELECTRIC, (1.0, 1.0, 1.0), 0.0, 0.0)]
+    else:
+        assert case == "forty_materials", case
+        tris, mats = [], []
+        for k in range(40):
+            x = -3.9 + 0.2 * k
+            tris.append(((x, -3, 0.1 * k), (x + 0.19, -3, 0.1 * k), (x + 0.1, 3, 0.1 * k), k, NONE))
+            mats.append(((srt.binding.MAT_LAMBERTIAN, srt.binding.MAT_METALLIC, srt.binding.MAT_DIELECTRIC)[k % 3], (0.5, 0.5, 0.5) if k % 2 else (1.0, 1.0, 1.0), 0.1 * (k % 4), 0.0))
+    scene = custom_scene(srt, tris, mats).build_bvh(srt.BVH_REFERENCE, 1984)
+    W, H, spp, depth = 45, 37, 6, 6
+    cam = srt.camera_init(W, H, 60.0, (0.3, 0.2, 9.0), (0.0, 0.0, 0.0))
+    return scene, cam, W, H, spp, depth
+
+
+def fuzz_with_lens(srt):
+    """the first fuzz case with a defocus lens, at least three material types and a few bounces: scene, cam, W, H, spp, depth, mode"""
+    for seed in range(200):
+        scene, cam, W, H, spp, depth, mode, _ = fuzz_case(srt, seed)
+        if (cam.defocus_angle > 0 and len({m.material_type for m in scene.materials()}) >= 3 and depth >= 3
+                and scene.background().max() > 0):
+            return scene, cam, W, H, max(spp, 3), depth, mode
+    raise AssertionError("no fuzz case with a lens")
+
+
 # ---- frozen outputs of the CPU oracle (tests/golden/oracle_digests.json) ---------------------------------------------------
 DIGEST_PLANES = ("fb_r", "fb_g", "fb_b", "srgb_r", "srgb_g", "srgb_b", "xyz_x", "xyz_y", "xyz_z")
 

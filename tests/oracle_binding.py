@@ -36,6 +36,7 @@ class Stats(C.Structure):
 
 
 _fp = C.POINTER(C.c_float)
+PATH_END_WORDS = 15      # orc_render_path_ends: wavelengths[7], power_distr[7], valid_wavelengths
 _lib = None
 
 
@@ -89,6 +90,8 @@ def lib():
         L.orc_scene_get_tris.argtypes = [C.c_void_p, _fp]
         L.orc_render.argtypes = [C.c_void_p, C.POINTER(CameraData)] + [C.c_uint32] * 10 + [C.c_uint64, C.c_int, C.c_void_p,
                                  C.c_uint32, C.c_uint32] + [_fp] * 9 + [C.c_int, C.POINTER(Stats)]
+        L.orc_render_path_ends.argtypes = [C.c_void_p, C.POINTER(CameraData)] + [C.c_uint32] * 10 + [C.c_uint64, C.c_int, C.c_void_p,
+                                           C.c_uint32, C.c_uint32] + [_fp] * 10 + [C.c_int, C.POINTER(Stats)]
         L.orc_unswizzle.argtypes = [_fp, _fp] + [C.c_uint32] * 9
         L.orc_camera_init.argtypes = [C.c_int, C.c_int, C.c_float, _fp, _fp, _fp, C.c_float, C.c_float, C.POINTER(CameraData)]
         L.orc_bake_sigmoid_spectrum.argtypes = [_fp, C.c_float, C.c_int, _fp]
@@ -152,20 +155,29 @@ class OracleScene:
         return out
 
     def render(self, cam, width, height, spp, bounce, tx=28, ty=16, bx=None, by=None, offx=0, offy=0, seed=1984,
-               states=None, block_lo=0, block_stride=1, threads=8):
+               states=None, block_lo=0, block_stride=1, threads=8, path_ends=False):
+        """path_ends: also return `ends`, (n_lanes, spp, 15) uint32 words of orc_render_path_ends -- wavelengths[7] and power_distr[7]
+        (float32 bits) and valid_wavelengths of every path at its end, in sample order; lanes outside the chunk stay zero"""
         if bx is None:
             bx, by = width // tx + 1, height // ty + 1
         n = tx * ty * bx * by
         planes = [np.zeros(n, np.float32) for _ in range(9)]
         st = Stats()
         ocam = CameraData.from_buffer_copy(bytes(cam))
-        rc = lib().orc_render(self.h, C.byref(ocam), spp, bounce, tx, ty, bx, by, width, height, offx, offy, seed,
-                              1 if states is None else 0, None if states is None else states.ctypes.data, block_lo, block_stride,
-                              *[fptr(p) for p in planes], threads, C.byref(st))
+        head = (self.h, C.byref(ocam), spp, bounce, tx, ty, bx, by, width, height, offx, offy, seed,
+                1 if states is None else 0, None if states is None else states.ctypes.data, block_lo, block_stride)
+        if path_ends:
+            ends = np.zeros((n, spp & 0xffff, PATH_END_WORDS), np.uint32)
+            rc = lib().orc_render_path_ends(*head, *[fptr(p) for p in planes], C.cast(ends.ctypes.data, _fp), threads, C.byref(st))
+        else:
+            rc = lib().orc_render(*head, *[fptr(p) for p in planes], threads, C.byref(st))
         assert rc == 0, rc
-        return dict(fb=tuple(planes[0:3]), lin=tuple(planes[3:6]), xyz=tuple(planes[6:9]),
-                    stats={k: getattr(st, k) for k in ("rays", "paths", "trav_iters", "box_tests", "tri_tests", "max_stack")},
-                    geom=dict(tx=tx, ty=ty, bx=bx, by=by, n_lanes=n))
+        out = dict(fb=tuple(planes[0:3]), lin=tuple(planes[3:6]), xyz=tuple(planes[6:9]),
+                   stats={k: getattr(st, k) for k in ("rays", "paths", "trav_iters", "box_tests", "tri_tests", "max_stack")},
+                   geom=dict(tx=tx, ty=ty, bx=bx, by=by, n_lanes=n))
+        if path_ends:
+            out["ends"] = ends
+        return out
 
     def trace(self, o, d):
         out = np.zeros(9, np.float32)

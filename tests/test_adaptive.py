@@ -1,7 +1,8 @@
 """Adaptive sampling (srt_accum_reset_adaptive + srt_render_chunk_accum, render_kernel MODE 4).  A pixel that stopped after n samples
 holds exactly what a plain n-spp launch gives it (the RNG stream belongs to the pixel), so the adaptive image is a patchwork of exact
 one-shot frames; every comparison here is bit for bit, and every stop decision is reproduced by a numpy float32 restatement of the
-criterion (accum_helpers.converged_f32)."""
+criterion (accum_helpers.converged_f32).  S1 and S2 themselves, and with them the stop map, are held to the CPU oracle: each sample's Y is
+orc_spectrum_to_XYZ of the oracle's path end (tests/path_ends_reference.py), summed and squared sequentially in float32."""
 import ctypes as C
 
 import numpy as np
@@ -11,6 +12,7 @@ from accum_helpers import (ERR_INVALID, ERR_UNSUPPORTED, EVERY_SHAPE_CASES, EVER
                            assert_pixels_equal, expect_error, forced_shape, fresh_context, gather_ranks, gpu_lib, lane_of, named_workload,
                            pick_tolerance, predict_stops, read_frame, read_sum_y, run_mock_transport_child, shape_case)
 from helpers import assert_planes_equal, bits, oracle_scene_for
+from path_ends_reference import assert_sums_at_counts, boundary_sums, cached_ends
 
 
 @pytest.mark.gpu
@@ -81,6 +83,48 @@ def test_s2_is_the_sequential_float32_sum_of_squares(srt, gpu):
     assert (st["samples"] == N).sum() > W * H // 2
     assert np.array_equal(bits(st["sum_y"]), bits(want1))
     assert np.array_equal(bits(st["sum_y2"]), bits(want2))
+
+
+def _oracle_sums(srt, orc, name):
+    """(scene, cam, W, H, depth) of a named workload and, per pass boundary of SCHED, dict(total, stats = dict(sum_y, sum_y2)) from the
+    oracle's path ends alone -- the layout predict_stops and pick_tolerance take"""
+    scene, cam, W, H, depth, mode = named_workload(srt, name)
+    n = sum(SCHED)
+    ends = cached_ends(orc, ("named", name, n), lambda: oracle_scene_for(orc, scene, mode), cam, W, H, n, depth)
+    sums = boundary_sums(orc, ends, SCHED)
+    return (scene, cam, W, H, depth), sums
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["dielectric", "prism"])
+def test_sums_equal_the_oracles_at_every_pass_boundary(srt, gpu, orc, name):
+    """tolerance NEVER: only a pixel without any variance stops (at min_spp, as the criterion on the oracle's sums says); every other
+    one holds the oracle's S1 and S2 of the pass total, after every pass"""
+    wl, oracle = _oracle_sums(srt, orc, name)
+    maps, _, actives = predict_stops(oracle, NEVER)
+    assert actives[-1] >= 100, actives          # (prism is mostly black background: those pixels stop at min_spp)
+    run = adaptive_run(gpu, *wl, NEVER)
+    for p, o, want, act in zip(run, oracle, maps, actives):
+        assert p["total"] == o["total"] and p["active"] == act
+        assert np.array_equal(p["stats"]["samples"], want), "pass to %d: %d pixels differ" % (o["total"], int((p["stats"]["samples"] != want).sum()))
+        assert_sums_at_counts(p["stats"], oracle, "%s after %d samples" % (name, o["total"]))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["dielectric", "prism"])
+def test_stop_map_equals_the_criterion_on_the_oracles_sums(srt, gpu, orc, name):
+    """the stop map and the active count after every pass == converged_f32 applied to the oracle's S1 and S2: nothing in the
+    prediction is read from the GPU"""
+    wl, oracle = _oracle_sums(srt, orc, name)
+    for rel, ab in ((pick_tolerance(oracle), 0.0), (0.05, 1e-3)):
+        maps, _, actives = predict_stops(oracle, rel, ab)
+        run = adaptive_run(gpu, *wl, rel, abs_tol=ab)
+        for k, (p, want, act) in enumerate(zip(run, maps, actives)):
+            got = p["stats"]["samples"]
+            assert np.array_equal(got, want), "rel %g abs %g pass %d: %d pixels differ" % (rel, ab, k, int((got != want).sum()))
+            assert p["active"] == act, (rel, ab, k, p["active"], act)
+        assert len(np.unique(maps[-1])) >= 2, (rel, ab)
+        assert_sums_at_counts(run[-1]["stats"], oracle, "%s rel %g abs %g" % (name, rel, ab))
 
 
 @pytest.mark.gpu

@@ -795,40 +795,14 @@ def test_bench_single_process_two_ranks_mock_transport():
     assert "nan_direction_rays" in two["config"]
 
 
-from helpers import custom_scene as _custom_scene, fuzz_case      # noqa: E402  (shared with tests/test_oracle_digests.py)
+from helpers import EDGE_CASES, custom_scene as _custom_scene, edge_case_scene, fuzz_case      # noqa: E402  (shared with tests/test_oracle_digests.py)
 
 
 @pytest.mark.parametrize("count_traversal", VARIANTS)
-@pytest.mark.parametrize("case", ["one_triangle", "two_triangles", "degenerate_and_odd_materials", "forty_materials"])
+@pytest.mark.parametrize("case", EDGE_CASES)
 def test_custom_scenes_edge_cases(srt, gpu, orc, case, count_traversal):
-    """Scenes that come in through srt_scene_set_* (not the built-ins): a BVH whose root is a leaf (bvh.cu:114-119), a two-leaf
-    tree (one FRINGE record, no INNER record), zero-area / needle triangles (NaN normal: every test on them fails, as in the
-    reference), material types the switch sends to its default branch (NO_MAT = 6, an unknown id), an emissive surface, and more
-    than 32 materials (the reference would read its 32-entry shared copy out of bounds, Q16; the build indexes the real table)."""
-    XY, NONE = 1, 0
-    wall = lambda z, m: [((-4, -4, z), (4, -4, z), (4, 4, z), m, NONE), ((-4, -4, z), (4, 4, z), (-4, 4, z), m, NONE)]
-    if case == "one_triangle":
-        tris = [((-3, -2, 0), (3, -2, 0), (0, 3, 0), 0, NONE)]
-        mats = [(srt.binding.MAT_LAMBERTIAN, (0.5, 0.5, 0.5), 0.0, 0.0)]
-    elif case == "two_triangles":
-        tris = wall(0.0, 0)
-        mats = [(srt.binding.MAT_METALLIC, (1.0, 1.0, 1.0), 0.3, 0.0)]
-    elif case == "degenerate_and_odd_materials":
-        tris = wall(0.0, 0) + wall(-1.5, 1) + [((0, 0, 1), (0, 0, 1), (0, 0, 1), 2, NONE),          # a point
-                                               ((-1, 0, 2), (0, 0, 2), (1, 0, 2), 3, NONE),          # a needle (collinear vertices)
-                                               ((-2, -2, 3), (2, -2, 3), (0, 2, 3), 4, XY)]
-        mats = [(srt.binding.MAT_NO_MAT, (1.0, 1.0, 1.0), 0.0, 0.0), (srt.binding.MAT_EMISSIVE, (1.0, 1.0, 1.0), 0.0, 3.0),
-                (srt.binding.MAT_DIELECTRIC, (1.0, 1.0, 1.0), 0.0, 0.0), (17, (0.5, 0.5, 0.5), 0.0, 0.0),
-                (srt.binding.MAT_DIELECTRIC, (1.0, 1.0, 1.0), 0.0, 0.0)]
-    else:
-        tris, mats = [], []
-        for k in range(40):
-            x = -3.9 + 0.2 * k
-            tris.append(((x, -3, 0.1 * k), (x + 0.19, -3, 0.1 * k), (x + 0.1, 3, 0.1 * k), k, NONE))
-            mats.append(((srt.binding.MAT_LAMBERTIAN, srt.binding.MAT_METALLIC, srt.binding.MAT_DIELECTRIC)[k % 3], (0.5, 0.5, 0.5) if k % 2 else (1.0, 1.0, 1.0), 0.1 * (k % 4), 0.0))
-    scene = _custom_scene(srt, tris, mats).build_bvh(srt.BVH_REFERENCE, 1984)
-    W, H, spp, depth = 45, 37, 6, 6
-    cam = srt.camera_init(W, H, 60.0, (0.3, 0.2, 9.0), (0.0, 0.0, 0.0))
+    """the adversarial scenes of helpers.edge_case_scene, both kernel builds: GPU == oracle bit for bit"""
+    scene, cam, W, H, spp, depth = edge_case_scene(srt, case)
     out = srt.render_image(scene, cam, W, H, spp, depth, renderer=gpu, count_traversal=count_traversal)
     osc = oracle_scene_for(orc, scene, 0)
     ref = osc.render(cam, W, H, spp, depth)

@@ -1,8 +1,10 @@
 """Spectral film (srt_accum_reset_spectral + srt_render_chunk_accum, render_kernel MODE 5).  The film holds, per pixel, the raw fp32 sums
 of every path end's seven powers deposited on the 5 nm CIE grid by the rule of srt_c_api.h.  Contracted with the colour-matching rows it
-gives the accumulation's XYZ sums (up to reassociation), on a miss-only frame it is restated bit for bit in numpy float32, and it is
-additive: the colour planes, XYZ sums and RNG state of a spectral accumulation are those of a plain one, and the film itself is the same
-bits for every split of the samples, every launch shape and every partition."""
+gives the accumulation's XYZ sums (up to reassociation), and it is additive: the colour planes, XYZ sums and RNG state of a spectral
+accumulation are those of a plain one.  The film itself is held bit for bit to the deposit rule applied in numpy float32 to the CPU
+oracle's path ends (tests/path_ends_reference.py): on six workloads that together cover dispersive paths, emitter ends, bounce-limit
+ends, the first and the clamped last bin pair and every bin, for a split of the samples, every launch shape, a partition and an offset
+chunk; and on a miss-only frame to the same rule applied to a numpy restatement of the RNG."""
 import ctypes as C
 
 import numpy as np
@@ -10,18 +12,10 @@ import pytest
 
 from accum_helpers import (ERR_INVALID, ERR_UNSUPPORTED, EVERY_SHAPE_CASES, EVERY_SHAPE_IDS, N_GRID, expect_error, forced_shape,
                            fresh_context, gpu_lib, lane_of, named_workload, read_frame, read_sum_y, run_mock_transport_child, shape_case,
-                           spectral_run)
-from helpers import _xorwow_host, assert_planes_equal, bits, custom_scene, fuzz_case
-
-
-def _fuzz_with_lens(srt):
-    """the first fuzz case with a defocus lens, at least three material types and a few bounces"""
-    for seed in range(200):
-        scene, cam, W, H, spp, depth, _, _ = fuzz_case(srt, seed)
-        if (cam.defocus_angle > 0 and len({m.material_type for m in scene.materials()}) >= 3 and depth >= 3
-                and scene.background().max() > 0):
-            return scene, cam, W, H, max(spp, 3), depth
-    raise AssertionError("no fuzz case with a lens")
+                           spectral_run, split_passes)
+from helpers import _xorwow_host, assert_planes_equal, bits, custom_scene, fuzz_with_lens, oracle_scene_for
+from path_ends_reference import (FILM_WORKLOADS, assert_film_coverage, assert_same_floats, cached_ends, deposit, shape_ends,
+                                 workload_ends)
 
 
 def _miss_scene(srt, bg):
@@ -41,7 +35,7 @@ def _miss_camera(srt, W, H):
 @pytest.mark.parametrize("name", ["cornell", "prism", "fuzz", "random_spheres"])
 def test_film_contracts_to_the_xyz_sums(srt, gpu, name):
     if name == "fuzz":
-        scene, cam, W, H, spp, depth = _fuzz_with_lens(srt)
+        scene, cam, W, H, spp, depth, _ = fuzz_with_lens(srt)
     else:
         scene, cam, W, H, depth, _ = named_workload(srt, name)
         spp = 6
@@ -78,13 +72,13 @@ def test_miss_only_film_equals_the_float32_restatement(srt, gpu, orc, passes):
         return (r.astype(f).astype(np.float64) * 2.0 ** -32 + 2.0 ** -33).astype(f)
     step, scale = f(470.0) / f(7.0), f(94.0) / f(470.0)
     want = np.zeros((seeds.size, N_GRID), f)
-    rows = np.arange(seeds.size)
     bg_p = bg.ctypes.data_as(C.POINTER(C.c_float))
     with np.errstate(over="ignore"):
         for _ in range(sum(passes)):
             nxt(every); nxt(every)                             # the pixel jitter
             hero = unit(nxt(every)) * f(470.0) + f(360.0)      # rng_range(360, 830), two roundings
             lam = hero
+            lams, powers = np.zeros((seeds.size, 7), f), np.zeros((seeds.size, 7), f)
             for k in range(7):
                 if k:
                     lam = lam + step
@@ -95,11 +89,73 @@ def test_miss_only_film_equals_the_float32_restatement(srt, gpu, orc, passes):
                 p = (f(1.0) - w) * bg[off] + w * bg[off + 1]
                 for q in range(0, seeds.size, 37):               # the interpolation is the oracle's spectrum_interp
                     assert bits(np.float32(orc.lib().orc_spectrum_interp(bg_p, float(lam[q]), N_GRID))) == bits(p[q])
-                p = f(1.0) * p                                   # the path's power starts at 1
-                want[rows, off] = want[rows, off] + (f(1.0) - w) * p
-                want[rows, off + 1] = want[rows, off + 1] + w * p
+                lams[:, k], powers[:, k] = lam, f(1.0) * p       # the path's power starts at 1
+            deposit(want, lams, powers)                          # all seven wavelengths valid (path_ends_reference: the deposit rule)
     want = want.reshape(H, W, N_GRID)
     assert np.array_equal(bits(film), bits(want)), "%d of %d sums differ" % (int((bits(film) != bits(want)).sum()), film.size)
+
+
+def _film_of(gpu, scene, cam, W, H, depth, passes, offx=0, offy=0):
+    fresh_context(gpu, scene, cam, W, H, depth)
+    gpu.accum_reset_spectral()
+    for s in passes:
+        gpu.render_chunk_accum(W, H, s, offx, offy)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", FILM_WORKLOADS)
+def test_film_equals_the_deposits_of_the_oracles_path_ends(srt, gpu, orc, name):
+    """every one of the 95 sums of every pixel == the deposit rule applied to the oracle's path ends, bit for bit (or both NaN)"""
+    assert_film_coverage(srt, orc)             # ... of all the workloads together, before the GPU runs
+    (scene, cam, W, H, n, depth, _), ends = workload_ends(srt, orc, name)
+    frame, film = spectral_run(gpu, scene, cam, W, H, depth, [n])
+    assert_same_floats(film, ends["film"], name + " film")
+    assert_planes_equal(frame["xyz"], ends["render"]["xyz"], name + " XYZ sums")
+    assert gpu.stats()["paths"] == W * H * n
+
+
+@pytest.mark.gpu
+def test_film_prediction_holds_for_a_split_a_partition_and_an_offset_chunk(srt, gpu, orc):
+    (scene, cam, W, H, n, depth, _), ends = workload_ends(srt, orc, "dielectric")
+    _, film = spectral_run(gpu, scene, cam, W, H, depth, split_passes(n))
+    assert_same_floats(film, ends["film"], "dielectric in passes %r" % (split_passes(n),))
+    # three ranks: every pixel's row is on its tile's owner and +0 elsewhere, so the sum over the ranks is the prediction
+    (scene, cam, W, H, n, depth, mode), ends = workload_ends(srt, orc, "random_spheres")
+    total = np.zeros((H, W, N_GRID), np.float32)
+    for rank in range(3):
+        fresh_context(gpu, scene, cam, W, H, depth)
+        gpu.set_partition(rank, 3)
+        gpu.accum_reset_spectral()
+        for s in (2, n - 2):
+            gpu.render_chunk_accum(W, H, s)
+        part = gpu.read_spectral(W, H)
+        assert bits(part).any()
+        total = total + part
+    gpu.set_partition(0, 1)
+    assert_same_floats(total, ends["film"], "random_spheres, rows summed over 3 ranks")
+    # a 30 x 21 chunk (no multiple of 8 x 8 or 28 x 16) at (17, 9) of a 64 x 40 image
+    IW, IH, cw, ch, ox, oy = 64, 40, 30, 21, 17, 9
+    cam = scene.default_camera(IW, IH)
+    ends = cached_ends(orc, ("random_spheres chunk", cw, ch, ox, oy), lambda: oracle_scene_for(orc, scene, mode), cam, cw, ch, 4, depth,
+                       offx=ox, offy=oy)
+    assert ends["film"].max() > 0
+    _film_of(gpu, scene, cam, cw, ch, depth, (1, 3), ox, oy)
+    full = gpu.read_spectral(IW, IH)
+    assert_same_floats(full[oy:oy + ch, ox:ox + cw], ends["film"], "offset chunk")
+    inside = np.zeros((IH, IW), bool)
+    inside[oy:oy + ch, ox:ox + cw] = True
+    assert not bits(full[~inside]).any()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("knobs,paired,expect", EVERY_SHAPE_CASES, ids=EVERY_SHAPE_IDS)
+def test_every_spectral_shape_equals_the_prediction(srt, gpu, orc, knobs, paired, expect):
+    n = 4
+    (scene, cam, W, H, depth), ends = shape_ends(srt, orc, paired, n)
+    assert ends["film"].max() > 0 and {1, 7} <= set(np.unique(ends["valid"]).tolist())
+    with forced_shape(gpu, scene, knobs, expect):
+        _, film = spectral_run(gpu, scene, cam, W, H, depth, [1, 3])
+    assert_same_floats(film, ends["film"], "shape %r" % (expect,))
 
 
 @pytest.mark.gpu
