@@ -53,6 +53,12 @@ class Adaptive(C.Structure):
     _fields_ = [("rel_tol", C.c_float), ("abs_tol", C.c_float), ("min_spp", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class Denoise(C.Structure):
+    """srt_denoise: levels and sigmas of the a-trous denoiser (srt_c_api.h)"""
+    _fields_ = [("levels", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float),
+                ("sigma_depth", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
 class TreeTuning(C.Structure):
     """srt_tree_tuning: what srt_tune_tree_for_throughput found and did (srt_c_api.h)"""
     _fields_ = [("pixels_per_lane", C.c_double), ("throughput_bound", C.c_uint32), ("reinsertion", C.c_uint32),
@@ -66,6 +72,7 @@ class TileScheduleInfo(C.Structure):
                 ("split_load_pct", C.c_uint32), ("order_max_pct", C.c_uint32), ("streams", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+assert C.sizeof(Denoise) == 32
 assert C.sizeof(Adaptive) == 16 and C.sizeof(TreeTuning) == 40 and C.sizeof(TileScheduleInfo) == 32
 assert C.sizeof(Material) == 428 and C.sizeof(CameraData) == 84 and C.sizeof(TriIn) == 44
 
@@ -126,6 +133,9 @@ PROTOTYPES = {
     "srt_read_spectral": (_i, [_vp, _u32, _u32, _fp, _u32, _u32]),
     "srt_accum_reset_features": (_i, [_vp]),
     "srt_read_features": (_i, [_vp, _fp, _u32, _u32]),
+    "srt_denoise_features": (_i, [_vp, C.POINTER(Denoise), _fp, _fp, _fp, _u32, _u32]),
+    "srt_denoise_kat": (_i, [_vp, C.POINTER(Denoise), _fp, _fp, _u32, _u32, _u32, _fp]),
+    "srt_denoise_last_ms": (_i, [_vp, _fp, _fp, _fp, C.POINTER(_u32)]),
     "srt_accum_reset_streams": (_i, [_vp, _u32]),
     "srt_accum_streams": (_i, [_vp, C.POINTER(_u32)]),
     "srt_set_gather_planes": (_i, [_vp, _u32]),

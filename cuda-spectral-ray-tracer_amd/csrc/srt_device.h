@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "srt_color_consts.h"
 #include "srt_powf.h"
 
 namespace srt {
@@ -266,6 +267,20 @@ __device__ __forceinline__ float correct_channel(float value) {   // :15-22
     return value < 0.0f ? 0.0f
          : (value < 0.0031308f ? 12.92f * value
          : (value < 1.0f ? ((1.055f * dev_powf(value, 0.416666f)) - 0.055f) : 1.0f));
+}
+// A pixel's XYZ mean -> its unquantised sRGB (XYZ_to_sRGB, color.cu:35-41) and the quantised value (expand_sRGB, :43-49, Q15): the
+// conversion at the end of render_kernel's pixel switch, as one function for the kernels outside the render unit (the denoiser's
+// epilogue).  render_kernel and stream_combine_kernel spell the same expressions out in place: their machine code is pinned.
+struct SrgbPixel { V3 lin, q; };
+__device__ __forceinline__ SrgbPixel xyz_mean_to_srgb(V3 c) {
+    const float r_lin = (SRT_XYZ2RGB_00 * c.x) + (SRT_XYZ2RGB_01 * c.y) + (SRT_XYZ2RGB_02 * c.z);
+    const float g_lin = (SRT_XYZ2RGB_10 * c.x) + (SRT_XYZ2RGB_11 * c.y) + (SRT_XYZ2RGB_12 * c.z);
+    const float b_lin = (SRT_XYZ2RGB_20 * c.x) + (SRT_XYZ2RGB_21 * c.y) + (SRT_XYZ2RGB_22 * c.z);
+    const float r = correct_channel(r_lin), g = correct_channel(g_lin), b = correct_channel(b_lin);
+    SrgbPixel o;
+    o.lin = mk(r, g, b);
+    o.q = mk((float)(int)(r * 255.99f), (float)(int)(g * 255.99f), (float)(int)(b * 255.99f));
+    return o;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -184,6 +184,31 @@ struct StreamCombineParams {
     uint32_t width, height, tx, ty, bx, by, tiles_x, n_tiles, rank, world, lane_limit;
 };
 hipError_t launch_stream_combine(const StreamCombineParams &p, hipStream_t st);
+// The denoiser (srt_denoise.hip; the filter is stated in srt_c_api.h at srt_denoise_features).  All images are row-major w x h.
+// Prepass: pixel (x, y) reads lane idx = block_linear_idx(x, y, tx, ty, bx) -- its XYZ sum at sums[idx * sum_pixel_stride + c *
+// sum_comp_stride] (an accumulation's planes: 1 and n_lanes; a caller's [h][w][3] array with tx = w, ty = h, bx = 1, which makes idx
+// row-major: 3 and 1) and its feature row at rows[idx * 2] -- and writes colour[pix] = (c.xyz, 0), guides[2 pix] = (N.xyz, z),
+// guides[2 pix + 1] = (A.xyz, coverage).
+struct DenoisePrepassParams {
+    const float *sums;
+    size_t sum_pixel_stride, sum_comp_stride;
+    const float4 *rows;
+    uint32_t tx, ty, bx;
+    uint32_t w, h, samples;
+    float4 *guides, *colour;
+};
+hipError_t launch_denoise_prepass(const DenoisePrepassParams &p, hipStream_t st);
+// One level at step `step` (1 .. 128) from src to dst (never the same buffer); kn .. kc: the level's squared sigmas.
+struct DenoiseLevelParams {
+    const float4 *guides, *src;
+    float4 *dst;
+    uint32_t w, h, step;
+    uint32_t tiles_x;      // filled in by the launcher
+    float kn, ka, kz, kc;
+};
+hipError_t launch_denoise_level(const DenoiseLevelParams &p, hipStream_t st);
+// colour (float4 per pixel) -> out_xyz / out_lin / out_q, n pixels of three floats each.
+hipError_t launch_denoise_epilogue(const float *colour, float *out_xyz, float *out_lin, float *out_q, size_t n, hipStream_t st);
 hipError_t launch_order_tiles(const uint32_t *cost, uint32_t *sorted, uint32_t *rows, uint32_t n, uint32_t n_waves,
                               uint32_t split_load_pct, uint32_t *queue_info, uint32_t order_max_pct, hipStream_t st);
 hipError_t launch_scatter(const ScatterParams &p, hipStream_t st);

@@ -151,6 +151,35 @@ class Renderer:
         self._ck(B.lib().srt_read_features(self._h, B.fptr(out), image_width, image_height))
         return split_features(out)
 
+    def denoise(self, image_width, image_height, **cfg):
+        """the a-trous denoiser over the context's featured accumulation (srt_denoise_features; cfg: the keywords of denoise_config):
+        dict(xyz, lin, fb) of (image_height, image_width, 3) float32 arrays -- the filtered XYZ mean, its unquantised and its quantised
+        sRGB -- written in the chunk's rectangle only (the placement of read_features), zeros elsewhere.  Reads the accumulation,
+        changes nothing of it."""
+        c = denoise_config(**cfg)
+        out = [np.zeros((image_height, image_width, 3), np.float32) for _ in range(3)]
+        self._ck(B.lib().srt_denoise_features(self._h, C.byref(c), B.fptr(out[0]), B.fptr(out[1]), B.fptr(out[2]), image_width, image_height))
+        return dict(xyz=out[0], lin=out[1], fb=out[2])
+
+    def denoise_kat(self, xyz_sums, features, samples, **cfg):
+        """the denoiser's device path on explicit inputs (srt_denoise_kat): xyz_sums (h, w, 3) and features (h, w, 8) raw float32 sums
+        of `samples` samples -> the filtered XYZ mean (h, w, 3).  Needs no scene and no accumulation."""
+        c = denoise_config(**cfg)
+        sums = np.ascontiguousarray(xyz_sums, np.float32)
+        rows = np.ascontiguousarray(features, np.float32)
+        if sums.ndim != 3 or sums.shape[2] != 3 or rows.shape != sums.shape[:2] + (FEATURE_CHANNELS,):
+            raise ValueError("denoise_kat: needs xyz_sums (h, w, 3) and features (h, w, %d), got %r and %r" % (FEATURE_CHANNELS, sums.shape, rows.shape))
+        out = np.zeros(sums.shape, np.float32)
+        self._ck(B.lib().srt_denoise_kat(self._h, C.byref(c), B.fptr(sums), B.fptr(rows), int(samples), sums.shape[1], sums.shape[0], B.fptr(out)))
+        return out
+
+    def denoise_last_ms(self):
+        """kernel-only ms of the last denoise on this context (srt_denoise_last_ms): dict(prepass, levels=[ms per level], epilogue)"""
+        pre, epi, n = C.c_float(), C.c_float(), C.c_uint32()
+        lv = (C.c_float * 8)()
+        self._ck(B.lib().srt_denoise_last_ms(self._h, C.byref(pre), lv, C.byref(epi), C.byref(n)))
+        return dict(prepass=pre.value, levels=[lv[i] for i in range(n.value)], epilogue=epi.value)
+
     def accum_reset_streams(self, k):
         """start a STREAMED accumulation (srt_c_api.h): every pixel has k independent RNG streams (1 <= k <= MAX_STREAMS), stream j of lane
         idx seeded XORWOW(seed + j * n_lanes + idx); a pass of spp_add samples (a multiple of k) draws spp_add / k from every stream, and
@@ -737,3 +766,45 @@ def _features_passes(scene, cam, width, height, sched, bounce_limit, seed, devic
             r.render_chunk_accum(width, height, spp_add)
             r.scatter_tiles()
             yield r.accum_samples, _collect(r, width, height), r.read_features(width, height)
+
+
+MAX_DENOISE_LEVELS = 8
+
+
+def denoise_config(levels=5, sigma_color=1.0, sigma_normal=0.5, sigma_albedo=0.25, sigma_depth=0.1):
+    """srt_denoise from Python numbers, checked as the library checks it (ValueError): levels a whole number in [0, 8]; every sigma > 0
+    in float32 and not NaN (inf switches its term off).  sigma_color is the level-0 width in XYZ units and halves with every level;
+    sigma_depth is relative (a fraction of the larger of two hit distances).  The defaults are starting values, not measurements."""
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or not 0 <= levels <= MAX_DENOISE_LEVELS:
+        raise ValueError("denoise: levels must be a whole number in [0, %d], got %r" % (MAX_DENOISE_LEVELS, levels))
+    sig = []
+    for name, v in (("sigma_color", sigma_color), ("sigma_normal", sigma_normal), ("sigma_albedo", sigma_albedo), ("sigma_depth", sigma_depth)):
+        try:
+            if isinstance(v, bool):
+                raise TypeError
+            with np.errstate(over="ignore"):          # (a value beyond float32 becomes inf, which is allowed)
+                f = float(np.float32(v))
+        except (TypeError, ValueError):
+            raise ValueError("denoise: %s must be a number, got %r" % (name, v))
+        if not f > 0.0:
+            raise ValueError("denoise: %s must be > 0 in float32 (inf switches the term off), got %r" % (name, v))
+        sig.append(f)
+    return B.Denoise(int(levels), sig[0], sig[1], sig[2], sig[3], (C.c_uint32 * 3)(0, 0, 0))
+
+
+def render_denoised(scene, cam, width, height, passes, bounce_limit, seed=1984, device=0, renderer=None, **cfg):
+    """render_features with the denoiser behind every pass: a generator of (spp_total, result, features, denoised), `denoised` the dict
+    of Renderer.denoise (cfg: the keywords of denoise_config) for the samples held so far.  The denoiser only reads the accumulation, so
+    result and features are render_features' bit for bit.  Schedule and cfg are checked here, before any device is touched."""
+    sched = progressive_schedule(passes)
+    denoise_config(**cfg)
+    return _denoised_passes(scene, cam, width, height, sched, bounce_limit, seed, device, renderer, cfg)
+
+
+def _denoised_passes(scene, cam, width, height, sched, bounce_limit, seed, device, renderer, cfg):
+    with _image_session(scene, cam, width, height, sum(sched), bounce_limit, seed, device, renderer) as r:
+        r.accum_reset_features()
+        for spp_add in sched:
+            r.render_chunk_accum(width, height, spp_add)
+            r.scatter_tiles()
+            yield r.accum_samples, _collect(r, width, height), r.read_features(width, height), r.denoise(width, height, **cfg)

@@ -334,8 +334,8 @@ SRT_API int srt_read_spectral(srt_ctx *ctx, uint32_t first, uint32_t count, floa
  *                             grid).  Later srt_render_chunk_accum passes run MODE 7.  Refused with the previous accumulation unchanged:
  *                             device parameters not set (SRT_ERR_INVALID); an instrumented context (SRT_ERR_UNSUPPORTED); a failed
  *                             allocation (SRT_ERR_HIP).  Always a PLAIN accumulation: features combined with adaptive sampling, the
- *                             spectral film or streams are NOT supported (adaptive + features is the intended next step: its output is
- *                             what a denoiser takes).  srt_accum_reset, srt_accum_reset_adaptive, srt_accum_reset_spectral and
+ *                             spectral film or streams are NOT supported (adaptive + features is the intended next step; the
+ *                             denoiser below, srt_denoise_features, takes a plain featured accumulation).  srt_accum_reset, srt_accum_reset_adaptive, srt_accum_reset_spectral and
  *                             srt_accum_reset_streams make the next accumulation non-featured again.  Invalidation, the 65535-sample
  *                             limit and the chunk binding are those of srt_accum_reset.
  *   srt_read_features         the raw sums of the accumulation's chunk, row-major: out[((y * image_width) + x) * 8 + c]; only the
@@ -344,6 +344,53 @@ SRT_API int srt_read_spectral(srt_ctx *ctx, uint32_t first, uint32_t count, floa
  *                             null out. */
 SRT_API int srt_accum_reset_features(srt_ctx *ctx);
 SRT_API int srt_read_features(srt_ctx *ctx, float *out, uint32_t image_width, uint32_t image_height);
+
+/* Edge-avoiding a-trous denoiser over the first-hit feature buffers (no reference counterpart; kernels in csrc/srt_denoise.hip).  It
+ * consumes a FEATURED accumulation: the XYZ sums are filtered by `levels` passes of a 5x5 B3-spline stencil whose taps are weighted down
+ * where normal, albedo, hit distance or the colour itself differ.  The filter, operation by operation -- everything fp32, not contracted,
+ * evaluated left to right as written, so that a float32 restatement (tests/denoise_reference.py) predicts the device's bits:
+ *   Inputs, for the w x h rectangle of the accumulation's chunk (clipped to the grid of srt_init_device_params): S[p][3] the XYZ sums,
+ *     F[p][8] the raw feature sums, n = the accumulation's sample total.
+ *   Prepass, per pixel:  inv = 1.0f / (float)n;  c_p = inv * S_p;  N_p = inv * F[0..2];  A_p = inv * F[3..5];
+ *     z_p = F[7] > 0 ? F[6] / F[7] : 0.  A sample that missed counts as a zero vector: N and A fade with coverage, which so needs no
+ *     term of its own.
+ *   Level i = 0 .. levels-1: step s = 1 << i; taps h = {1/16, 1/4, 3/8, 1/4, 1/16} at offsets (dx * s, dy * s), dy = -2 .. 2 in the
+ *     outer loop, dx = -2 .. 2 in the inner one; a tap outside the rectangle is skipped.  Per-level constants, computed on the host in
+ *     fp32: kn = sigma_normal * sigma_normal, ka = sigma_albedo * sigma_albedo, kz = sigma_depth * sigma_depth, kc = sc * sc with
+ *     sc = sigma_color * 2^-i (an exact scaling: the colour term tightens as the stencil widens).
+ *     Edge term  e(d2, k):  t = 1 - d2 / k;  t = (t > 0) ? t : 0;  return t * t.     (NaN gives 0, an infinite k gives 1.)
+ *     For tap q of pixel p:
+ *       dn = (N_p.x - N_q.x)^2 + (N_p.y - N_q.y)^2 + (N_p.z - N_q.z)^2;   da the same on A;   dc the same on the level's input colour;
+ *       m = z_p > z_q ? z_p : z_q;   r = m > 0 ? (z_p - z_q) / m : 0;   dz = r * r;
+ *       wt = h[dy+2] * h[dx+2];  wt = wt * e(dn, kn);  wt = wt * e(da, ka);  wt = wt * e(dz, kz);  wt = wt * e(dc, kc);
+ *       if (wt > 0) { sw += wt;  sx += wt * c_q.x;  sy += wt * c_q.y;  sz += wt * c_q.z; }
+ *     Output of the level:  sw > 0 ? (sx / sw, sy / sw, sz / sw) : c_p.  Levels ping-pong between two images; levels == 0 returns c_p.
+ *     (A pixel whose colour is NaN keeps it -- every one of its taps has wt = 0 -- and no neighbour takes it in.)
+ *   Epilogue: the filtered XYZ mean goes through the render kernel's own conversion (XYZ -> linear sRGB rows, correct_channel,
+ *     (float)(int)(v * 255.99f)): out_lin the unquantised, out_q the quantised sRGB.
+ *   srt_denoise_features  filters the context's featured accumulation and writes out[((y * image_width) + x) * 3 + c] with the placement
+ *                         of srt_read_features: only the chunk's rectangle is written (the filter always runs on the whole chunk; the
+ *                         image clips only what is copied).  Any of the three outputs may be NULL, not all.  Synchronises.  It only
+ *                         READS the accumulation: later passes, the frame, the feature rows and the RNG state are what they would be
+ *                         without the call.  Working images (100 B per pixel of the chunk) belong to the context, are reused and grow
+ *                         with the chunk.  Refused, the accumulation unchanged: null ctx / cfg, all outputs NULL, no featured accumulation
+ *                         with at least one pass, levels > 8, a sigma that is NaN or <= 0 (+inf is allowed and switches its term off),
+ *                         non-zero reserved words (SRT_ERR_INVALID); a partition other than (0, 1) (SRT_ERR_UNSUPPORTED: the neighbours
+ *                         other ranks own read +0 here; a gathered denoise is out of scope, and srt_comm has no entry point for it); a
+ *                         failed allocation (SRT_ERR_HIP).
+ *   srt_denoise_kat       KAT entry point, like srt_order_tiles_kat: the same prepass, level and epilogue kernels on caller-supplied
+ *                         row-major host arrays xyz_sums[h][w][3] and features[h][w][8] holding `samples` samples; out_xyz[h][w][3]
+ *                         receives the filtered XYZ mean.  Needs neither a scene nor an accumulation and touches neither.
+ *                         SRT_ERR_INVALID for a null argument, a cfg as above, samples == 0, an empty image or w x h >= 2^31. */
+typedef struct srt_denoise { uint32_t levels; float sigma_color, sigma_normal, sigma_albedo, sigma_depth; uint32_t reserved[3]; } srt_denoise;
+SRT_API int srt_denoise_features(srt_ctx *ctx, const srt_denoise *cfg, float *out_xyz, float *out_lin, float *out_q,
+                                 uint32_t image_width, uint32_t image_height);
+SRT_API int srt_denoise_kat(srt_ctx *ctx, const srt_denoise *cfg, const float *xyz_sums, const float *features,
+                            uint32_t samples, uint32_t w, uint32_t h, float *out_xyz);
+/* Kernel-only times of the context's last denoise (either entry point) in ms, from HIP events around each kernel: the prepass, level i in
+ * level_ms[i] (8 entries; 0 from the call's `levels` on, which *levels receives), the epilogue.  Any pointer may be NULL.  Measurement
+ * support (tools/denoise_cost.py), like srt_last_kernel_ms.  SRT_ERR_INVALID before the first denoise. */
+SRT_API int srt_denoise_last_ms(srt_ctx *ctx, float *prepass_ms, float level_ms[8], float *epilogue_ms, uint32_t *levels);
 
 /* Sample-parallel pixels (no reference counterpart; a deliberate departure from its one RNG stream per pixel, so opt-in).  A STREAMED
  * accumulation gives every pixel K independent RNG streams, each with its own state and its own XYZ sum, so that any lane of any wave
