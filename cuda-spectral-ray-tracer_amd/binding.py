@@ -59,6 +59,12 @@ class Denoise(C.Structure):
                 ("sigma_depth", C.c_float), ("reserved", C.c_uint32 * 3)]
 
 
+class DenoiseVG(C.Structure):
+    """srt_denoise_vg: levels, sigmas and variance floor of the variance-guided a-trous denoiser (srt_c_api.h)"""
+    _fields_ = [("levels", C.c_uint32), ("sigma_variance", C.c_float), ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float),
+                ("sigma_depth", C.c_float), ("variance_floor", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
 class TreeTuning(C.Structure):
     """srt_tree_tuning: what srt_tune_tree_for_throughput found and did (srt_c_api.h)"""
     _fields_ = [("pixels_per_lane", C.c_double), ("throughput_bound", C.c_uint32), ("reinsertion", C.c_uint32),
@@ -72,7 +78,7 @@ class TileScheduleInfo(C.Structure):
                 ("split_load_pct", C.c_uint32), ("order_max_pct", C.c_uint32), ("streams", C.c_uint32), ("reserved", C.c_uint32)]
 
 
-assert C.sizeof(Denoise) == 32
+assert C.sizeof(Denoise) == 32 and C.sizeof(DenoiseVG) == 32
 assert C.sizeof(Adaptive) == 16 and C.sizeof(TreeTuning) == 40 and C.sizeof(TileScheduleInfo) == 32
 assert C.sizeof(Material) == 428 and C.sizeof(CameraData) == 84 and C.sizeof(TriIn) == 44
 
@@ -136,6 +142,9 @@ PROTOTYPES = {
     "srt_denoise_features": (_i, [_vp, C.POINTER(Denoise), _fp, _fp, _fp, _u32, _u32]),
     "srt_denoise_kat": (_i, [_vp, C.POINTER(Denoise), _fp, _fp, _u32, _u32, _u32, _fp]),
     "srt_denoise_last_ms": (_i, [_vp, _fp, _fp, _fp, C.POINTER(_u32)]),
+    "srt_denoise_features_vg": (_i, [_vp, C.POINTER(DenoiseVG), _fp, _fp, _fp, _fp, _u32, _u32]),
+    "srt_denoise_vg_kat": (_i, [_vp, C.POINTER(DenoiseVG), _fp, _fp, _u32, _u32, _u32, _fp, _fp]),
+    "srt_denoise_estimate_last_ms": (_i, [_vp, _fp]),
     "srt_accum_reset_streams": (_i, [_vp, _u32]),
     "srt_accum_streams": (_i, [_vp, C.POINTER(_u32)]),
     "srt_set_gather_planes": (_i, [_vp, _u32]),

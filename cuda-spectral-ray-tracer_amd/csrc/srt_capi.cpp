@@ -141,8 +141,9 @@ struct srt_ctx {
     DeviceBuffer d_features_staging;                    // row-major staging block of srt_read_features
     DeviceBuffer d_denoise;                             // the denoiser's working images (DenoiseLayout), grown when the rectangle grows
     DeviceBuffer d_denoise_in;                          // srt_denoise_kat: the caller's sums and feature rows
-    hipEvent_t denoise_ev[11] = {};                     // around the kernels of the last denoise: prepass | levels | epilogue (created on first use)
+    hipEvent_t denoise_ev[12] = {};                     // around the kernels of the last denoise: prepass | (estimator) | levels | epilogue (created on first use)
     uint32_t denoise_timed_levels = 0;                  // levels the events of the last denoise bracket
+    uint32_t denoise_level_ev = 1;                      // the event level 0 starts at: 1, or 2 after a variance-guided denoise
     bool denoise_timed = false;
     DeviceBuffer d_streams;                             // sample-parallel pixels (srt_accum_reset_streams, StreamPlanes)
     uint32_t streams_seeded = 0;                        // the K whose RNG streams d_streams holds, seeded since the last srt_init_device_params (0: none)
@@ -1091,15 +1092,26 @@ int srt_read_features(srt_ctx *c, float *out, uint32_t image_width, uint32_t ima
 // ---- the denoiser (srt_denoise.hip) ---------------------------------------------------------------------------------------------
 namespace {
 
-// d_denoise: [guides: 2 float4 per pixel | colour A | colour B: 1 float4 per pixel each | out_xyz | out_lin | out_q: 3 floats per pixel each]
+// d_denoise: [guides: 2 float4 per pixel | colour A | colour B: 1 float4 per pixel each | out_xyz | out_lin | out_q: 3 floats per pixel each
+//             | variance-guided only: out_var: 2 floats per pixel]
 struct DenoiseLayout {
     float4 *guides, *colour[2];
-    float *out[3];
-    static size_t bytes(size_t pixels) { return pixels * (4 * sizeof(float4) + 9 * sizeof(float)); }
+    float *out[3], *var;
+    static size_t bytes(size_t pixels, bool vg) { return pixels * (4 * sizeof(float4) + 9 * sizeof(float) + (vg ? 2 * sizeof(float) : 0)); }
     DenoiseLayout(const DeviceBuffer &d, size_t pixels) : guides(d.as<float4>()) {
         colour[0] = guides + 2 * pixels; colour[1] = colour[0] + pixels;
         out[0] = reinterpret_cast<float *>(colour[1] + pixels); out[1] = out[0] + 3 * pixels; out[2] = out[1] + 3 * pixels;
+        var = out[2] + 3 * pixels;      // (inside the buffer only when it was reserved with vg)
     }
+};
+
+// What either configuration struct asks of the kernels: the plain filter's sigma_color, or the variance-guided filter's two constants.
+struct DenoisePlan {
+    bool vg;
+    uint32_t levels;
+    float kn, ka, kz;
+    float sigma_color;      // plain
+    float ks, floor;        // variance-guided: sigma_variance * sigma_variance (formed once, here), variance_floor
 };
 
 const char *denoise_cfg_error(const srt_denoise *cfg) {
@@ -1110,9 +1122,35 @@ const char *denoise_cfg_error(const srt_denoise *cfg) {
     return nullptr;
 }
 
-// Prepass (its sources in `pre`; the outputs are set here), cfg->levels level kernels ping-ponging between the two colour images, the
-// epilogue: the three row-major results are left in DenoiseLayout::out.  Enqueues on the default stream; the caller synchronises.
-int run_denoise(srt_ctx *c, const char *who, const srt_denoise *cfg, DenoisePrepassParams pre) {
+const char *denoise_vg_cfg_error(const srt_denoise_vg *cfg) {
+    if (cfg->levels > 8) return "levels must be in 0 .. 8";
+    if (!(cfg->sigma_variance > 0.0f) || std::isinf(cfg->sigma_variance)) return "sigma_variance must be greater than 0 and finite";
+    for (const float s : {cfg->sigma_normal, cfg->sigma_albedo, cfg->sigma_depth})
+        if (!(s > 0.0f)) return "every guide sigma must be greater than 0 (+inf switches its term off)";
+    if (!(cfg->variance_floor > 0.0f)) return "variance_floor must be greater than 0 (+inf switches the luminance term off)";
+    if (cfg->reserved[0] | cfg->reserved[1]) return "reserved words must be 0";
+    return nullptr;
+}
+
+DenoisePlan denoise_plan(const srt_denoise *cfg) {
+    DenoisePlan p = {};
+    p.vg = false; p.levels = cfg->levels; p.sigma_color = cfg->sigma_color;
+    p.kn = cfg->sigma_normal * cfg->sigma_normal; p.ka = cfg->sigma_albedo * cfg->sigma_albedo; p.kz = cfg->sigma_depth * cfg->sigma_depth;
+    return p;
+}
+
+DenoisePlan denoise_vg_plan(const srt_denoise_vg *cfg) {
+    DenoisePlan p = {};
+    p.vg = true; p.levels = cfg->levels; p.ks = cfg->sigma_variance * cfg->sigma_variance; p.floor = cfg->variance_floor;
+    p.kn = cfg->sigma_normal * cfg->sigma_normal; p.ka = cfg->sigma_albedo * cfg->sigma_albedo; p.kz = cfg->sigma_depth * cfg->sigma_depth;
+    return p;
+}
+
+// Prepass (its sources in `pre`; the outputs are set here), variance-guided: the estimator, plan.levels level kernels ping-ponging between
+// the two colour images, the epilogue (variance-guided: and the variance after the last level): the row-major results are left in
+// DenoiseLayout::out / var.  Enqueues on the default stream; the caller synchronises.
+// Events: [0] prepass [1] (variance-guided: estimator [2]) level 0 .. epilogue: denoise_level_ev is the event level 0 starts at.
+int run_denoise(srt_ctx *c, const char *who, const DenoisePlan &plan, DenoisePrepassParams pre) {
     const size_t pixels = (size_t)pre.w * pre.h;
     const DenoiseLayout L(c->d_denoise, pixels);
     pre.guides = L.guides; pre.colour = L.colour[0];
@@ -1122,22 +1160,93 @@ int run_denoise(srt_ctx *c, const char *who, const srt_denoise *cfg, DenoisePrep
     HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
     HIP_TRY_AS(c, who, launch_denoise_prepass(pre, nullptr));
     HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
+    if (plan.vg) {
+        DenoiseVarianceParams vp = {};
+        vp.guides = L.guides; vp.colour = reinterpret_cast<float *>(L.colour[0]); vp.out_var = L.var;
+        vp.w = pre.w; vp.h = pre.h; vp.kn = plan.kn; vp.ka = plan.ka; vp.kz = plan.kz;
+        HIP_TRY_AS(c, who, launch_denoise_variance(vp, nullptr));
+        HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
+    }
+    const uint32_t level_ev = n_ev - 1;
     uint32_t cur = 0;
-    for (uint32_t i = 0; i < cfg->levels; i++) {
-        // the level's constants, fp32 on the host: sigma_color halves with every level (an exact scaling)
-        const float sc = ldexpf(cfg->sigma_color, -(int)i);
-        DenoiseLevelParams lp = {};
-        lp.guides = L.guides; lp.src = L.colour[cur]; lp.dst = L.colour[cur ^ 1u];
-        lp.w = pre.w; lp.h = pre.h; lp.step = 1u << i;
-        lp.kn = cfg->sigma_normal * cfg->sigma_normal; lp.ka = cfg->sigma_albedo * cfg->sigma_albedo;
-        lp.kz = cfg->sigma_depth * cfg->sigma_depth; lp.kc = sc * sc;
-        HIP_TRY_AS(c, who, launch_denoise_level(lp, nullptr));
+    for (uint32_t i = 0; i < plan.levels; i++) {
+        if (plan.vg) {
+            DenoiseLevelVgParams lp = {};
+            lp.guides = L.guides; lp.src = L.colour[cur]; lp.dst = L.colour[cur ^ 1u];
+            lp.w = pre.w; lp.h = pre.h; lp.step = 1u << i;
+            lp.kn = plan.kn; lp.ka = plan.ka; lp.kz = plan.kz; lp.ks = plan.ks; lp.floor = plan.floor;
+            HIP_TRY_AS(c, who, launch_denoise_level_vg(lp, nullptr));
+        } else {
+            // the level's constants, fp32 on the host: sigma_color halves with every level (an exact scaling)
+            const float sc = ldexpf(plan.sigma_color, -(int)i);
+            DenoiseLevelParams lp = {};
+            lp.guides = L.guides; lp.src = L.colour[cur]; lp.dst = L.colour[cur ^ 1u];
+            lp.w = pre.w; lp.h = pre.h; lp.step = 1u << i;
+            lp.kn = plan.kn; lp.ka = plan.ka; lp.kz = plan.kz; lp.kc = sc * sc;
+            HIP_TRY_AS(c, who, launch_denoise_level(lp, nullptr));
+        }
         HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
         cur ^= 1u;
     }
     HIP_TRY_AS(c, who, launch_denoise_epilogue(reinterpret_cast<const float *>(L.colour[cur]), L.out[0], L.out[1], L.out[2], pixels, nullptr));
+    if (plan.vg) HIP_TRY_AS(c, who, launch_denoise_var_out(reinterpret_cast<const float *>(L.colour[cur]), L.var, pixels, nullptr));
     HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
-    c->denoise_timed_levels = cfg->levels; c->denoise_timed = true;
+    c->denoise_timed_levels = plan.levels; c->denoise_level_ev = level_ev; c->denoise_timed = true;
+    return SRT_OK;
+}
+
+// srt_denoise_features / srt_denoise_features_vg behind their argument checks: host[0 .. 2] the three colour outputs, host[3] the variance
+int denoise_features(srt_ctx *c, const char *who, const DenoisePlan &plan, float *const host[4], uint32_t image_width, uint32_t image_height) {
+    const std::string w_(who);
+    if (!c->accum.featured() || !c->accum.bound())
+        return fail(c, SRT_ERR_INVALID, w_ + ": no featured accumulation with a pass (srt_accum_reset_features and srt_render_chunk_accum first)");
+    if (c->rank != 0 || c->world != 1)
+        return fail(c, SRT_ERR_UNSUPPORTED, w_ + ": needs the whole chunk on this context (partition (0, 1)): pixels of other ranks read +0");
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the filter runs on the chunk's rectangle (clipped to the reference grid); the image clips only what is copied out
+    const uint32_t w = clipped_w(c), h = clipped_h(c);
+    const size_t pixels = (size_t)w * h;
+    if (pixels) {
+        HIP_TRY(c, c->d_denoise.reserve(DenoiseLayout::bytes(pixels, plan.vg)));
+        DenoisePrepassParams pre = {};
+        pre.sums = AccumLayout(c).sums; pre.sum_pixel_stride = 1; pre.sum_comp_stride = c->n_lanes;
+        pre.rows = c->d_features.as<const float4>();
+        pre.tx = c->tx; pre.ty = c->ty; pre.bx = c->bx; pre.w = w; pre.h = h; pre.samples = c->accum.total;
+        if (const int rc = run_denoise(c, who, plan, pre)) return rc;
+        const ChunkRect rect = chunk_rect(c, image_width, image_height);
+        const DenoiseLayout L(c->d_denoise, pixels);
+        for (int k = 0; k < 4; k++) {
+            const size_t ch = k < 3 ? 3 : 2;      // floats per pixel
+            const float *src = k < 3 ? L.out[k] : L.var;
+            const size_t row = (size_t)rect.w * ch * sizeof(float), src_pitch = (size_t)w * ch * sizeof(float), pitch = (size_t)image_width * ch * sizeof(float);
+            if (host[k] && rect.w && rect.h) HIP_TRY(c, hipMemcpy2D(host[k] + rect.first * ch, pitch, src, src_pitch, row, rect.h, hipMemcpyDeviceToHost));
+        }
+    }
+    HIP_TRY(c, hipDeviceSynchronize());
+    return SRT_OK;
+}
+
+// srt_denoise_kat / srt_denoise_vg_kat behind their configuration checks (out_var: variance-guided only)
+int denoise_kat(srt_ctx *c, const char *who, const DenoisePlan &plan, const float *xyz_sums, const float *features, uint32_t samples, uint32_t w, uint32_t h,
+                float *out_xyz, float *out_var) {
+    if (samples == 0 || w == 0 || h == 0 || (uint64_t)w * h > 0x7fffffffull) return fail(c, SRT_ERR_INVALID, std::string(who) + ": samples, w and h must be positive, w x h below 2^31");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t pixels = (size_t)w * h;
+    HIP_TRY_AS(c, who, c->d_denoise.reserve(DenoiseLayout::bytes(pixels, plan.vg)));
+    HIP_TRY_AS(c, who, c->d_denoise_in.reserve(pixels * (kFeatureStride + 3) * sizeof(float)));
+    float *d_rows = c->d_denoise_in.as<float>(), *d_sums = d_rows + pixels * kFeatureStride;
+    HIP_TRY_AS(c, who, hipMemcpy(d_rows, features, pixels * kFeatureStride * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY_AS(c, who, hipMemcpy(d_sums, xyz_sums, pixels * 3 * sizeof(float), hipMemcpyHostToDevice));
+    // a grid of one w x h block makes the prepass's block-linear lane the row-major pixel
+    DenoisePrepassParams pre = {};
+    pre.sums = d_sums; pre.sum_pixel_stride = 3; pre.sum_comp_stride = 1;
+    pre.rows = reinterpret_cast<const float4 *>(d_rows);
+    pre.tx = w; pre.ty = h; pre.bx = 1; pre.w = w; pre.h = h; pre.samples = samples;
+    if (const int rc = run_denoise(c, who, plan, pre)) return rc;
+    const DenoiseLayout L(c->d_denoise, pixels);
+    HIP_TRY_AS(c, who, hipMemcpy(out_xyz, L.out[0], pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_var) HIP_TRY_AS(c, who, hipMemcpy(out_var, L.var, pixels * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY_AS(c, who, hipDeviceSynchronize());
     return SRT_OK;
 }
 
@@ -1147,71 +1256,57 @@ int srt_denoise_features(srt_ctx *c, const srt_denoise *cfg, float *out_xyz, flo
     if (!c || !cfg) return fail(c, SRT_ERR_INVALID, "srt_denoise_features: null argument");
     if ((!out_xyz && !out_lin && !out_q) || image_width == 0 || image_height == 0) return fail(c, SRT_ERR_INVALID, "srt_denoise_features: no output / empty image");
     if (const char *why = denoise_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_denoise_features: ") + why);
-    if (!c->accum.featured() || !c->accum.bound())
-        return fail(c, SRT_ERR_INVALID, "srt_denoise_features: no featured accumulation with a pass (srt_accum_reset_features and srt_render_chunk_accum first)");
-    if (c->rank != 0 || c->world != 1)
-        return fail(c, SRT_ERR_UNSUPPORTED, "srt_denoise_features: needs the whole chunk on this context (partition (0, 1)): pixels of other ranks read +0");
-    HIP_TRY(c, hipSetDevice(c->device));
-    // the filter runs on the chunk's rectangle (clipped to the reference grid); the image clips only what is copied out
-    const uint32_t w = clipped_w(c), h = clipped_h(c);
-    const size_t pixels = (size_t)w * h;
-    if (pixels) {
-        HIP_TRY(c, c->d_denoise.reserve(DenoiseLayout::bytes(pixels)));
-        DenoisePrepassParams pre = {};
-        pre.sums = AccumLayout(c).sums; pre.sum_pixel_stride = 1; pre.sum_comp_stride = c->n_lanes;
-        pre.rows = c->d_features.as<const float4>();
-        pre.tx = c->tx; pre.ty = c->ty; pre.bx = c->bx; pre.w = w; pre.h = h; pre.samples = c->accum.total;
-        if (const int rc = run_denoise(c, "srt_denoise_features", cfg, pre)) return rc;
-        const ChunkRect rect = chunk_rect(c, image_width, image_height);
-        const DenoiseLayout L(c->d_denoise, pixels);
-        float *const host[3] = {out_xyz, out_lin, out_q};
-        const size_t row = (size_t)rect.w * 3 * sizeof(float), src_pitch = (size_t)w * 3 * sizeof(float), pitch = (size_t)image_width * 3 * sizeof(float);
-        for (int k = 0; k < 3; k++)
-            if (host[k] && rect.w && rect.h) HIP_TRY(c, hipMemcpy2D(host[k] + rect.first * 3, pitch, L.out[k], src_pitch, row, rect.h, hipMemcpyDeviceToHost));
-    }
-    HIP_TRY(c, hipDeviceSynchronize());
-    return SRT_OK;
+    float *const host[4] = {out_xyz, out_lin, out_q, nullptr};
+    return denoise_features(c, "srt_denoise_features", denoise_plan(cfg), host, image_width, image_height);
+}
+
+int srt_denoise_features_vg(srt_ctx *c, const srt_denoise_vg *cfg, float *out_xyz, float *out_lin, float *out_q, float *out_var, uint32_t image_width, uint32_t image_height) {
+    if (!c || !cfg) return fail(c, SRT_ERR_INVALID, "srt_denoise_features_vg: null argument");
+    if ((!out_xyz && !out_lin && !out_q && !out_var) || image_width == 0 || image_height == 0) return fail(c, SRT_ERR_INVALID, "srt_denoise_features_vg: no output / empty image");
+    if (const char *why = denoise_vg_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_denoise_features_vg: ") + why);
+    float *const host[4] = {out_xyz, out_lin, out_q, out_var};
+    return denoise_features(c, "srt_denoise_features_vg", denoise_vg_plan(cfg), host, image_width, image_height);
 }
 
 int srt_denoise_kat(srt_ctx *c, const srt_denoise *cfg, const float *xyz_sums, const float *features, uint32_t samples, uint32_t w, uint32_t h, float *out_xyz) {
     if (!c || !cfg || !xyz_sums || !features || !out_xyz) return fail(c, SRT_ERR_INVALID, "srt_denoise_kat: null argument");
     if (const char *why = denoise_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_denoise_kat: ") + why);
-    if (samples == 0 || w == 0 || h == 0 || (uint64_t)w * h > 0x7fffffffull) return fail(c, SRT_ERR_INVALID, "srt_denoise_kat: samples, w and h must be positive, w x h below 2^31");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t pixels = (size_t)w * h;
-    HIP_TRY_AS(c, "srt_denoise_kat", c->d_denoise.reserve(DenoiseLayout::bytes(pixels)));
-    HIP_TRY_AS(c, "srt_denoise_kat", c->d_denoise_in.reserve(pixels * (kFeatureStride + 3) * sizeof(float)));
-    float *d_rows = c->d_denoise_in.as<float>(), *d_sums = d_rows + pixels * kFeatureStride;
-    HIP_TRY_AS(c, "srt_denoise_kat", hipMemcpy(d_rows, features, pixels * kFeatureStride * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY_AS(c, "srt_denoise_kat", hipMemcpy(d_sums, xyz_sums, pixels * 3 * sizeof(float), hipMemcpyHostToDevice));
-    // a grid of one w x h block makes the prepass's block-linear lane the row-major pixel
-    DenoisePrepassParams pre = {};
-    pre.sums = d_sums; pre.sum_pixel_stride = 3; pre.sum_comp_stride = 1;
-    pre.rows = reinterpret_cast<const float4 *>(d_rows);
-    pre.tx = w; pre.ty = h; pre.bx = 1; pre.w = w; pre.h = h; pre.samples = samples;
-    if (const int rc = run_denoise(c, "srt_denoise_kat", cfg, pre)) return rc;
-    HIP_TRY_AS(c, "srt_denoise_kat", hipMemcpy(out_xyz, DenoiseLayout(c->d_denoise, pixels).out[0], pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY_AS(c, "srt_denoise_kat", hipDeviceSynchronize());
-    return SRT_OK;
+    return denoise_kat(c, "srt_denoise_kat", denoise_plan(cfg), xyz_sums, features, samples, w, h, out_xyz, nullptr);
+}
+
+int srt_denoise_vg_kat(srt_ctx *c, const srt_denoise_vg *cfg, const float *xyz_sums, const float *features, uint32_t samples, uint32_t w, uint32_t h,
+                       float *out_xyz, float *out_var) {
+    if (!c || !cfg || !xyz_sums || !features || !out_xyz || !out_var) return fail(c, SRT_ERR_INVALID, "srt_denoise_vg_kat: null argument");
+    if (const char *why = denoise_vg_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_denoise_vg_kat: ") + why);
+    return denoise_kat(c, "srt_denoise_vg_kat", denoise_vg_plan(cfg), xyz_sums, features, samples, w, h, out_xyz, out_var);
 }
 
 int srt_denoise_last_ms(srt_ctx *c, float *prepass_ms, float *level_ms, float *epilogue_ms, uint32_t *levels) {
     if (!c) return fail(c, SRT_ERR_INVALID, "srt_denoise_last_ms: null ctx");
     if (!c->denoise_timed) return fail(c, SRT_ERR_INVALID, "srt_denoise_last_ms: no denoise has run on this context");
     HIP_TRY(c, hipSetDevice(c->device));
-    const uint32_t n = c->denoise_timed_levels;
-    HIP_TRY(c, hipEventSynchronize(c->denoise_ev[n + 2]));
+    const uint32_t n = c->denoise_timed_levels, l0 = c->denoise_level_ev;
+    HIP_TRY(c, hipEventSynchronize(c->denoise_ev[l0 + n + 1]));
     float ms = 0.0f;
     HIP_TRY(c, hipEventElapsedTime(&ms, c->denoise_ev[0], c->denoise_ev[1]));
     if (prepass_ms) *prepass_ms = ms;
     for (uint32_t i = 0; i < 8; i++) {
         ms = 0.0f;
-        if (i < n) HIP_TRY(c, hipEventElapsedTime(&ms, c->denoise_ev[1 + i], c->denoise_ev[2 + i]));
+        if (i < n) HIP_TRY(c, hipEventElapsedTime(&ms, c->denoise_ev[l0 + i], c->denoise_ev[l0 + 1 + i]));
         if (level_ms) level_ms[i] = ms;
     }
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->denoise_ev[n + 1], c->denoise_ev[n + 2]));
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->denoise_ev[l0 + n], c->denoise_ev[l0 + n + 1]));
     if (epilogue_ms) *epilogue_ms = ms;
     if (levels) *levels = n;
+    return SRT_OK;
+}
+
+int srt_denoise_estimate_last_ms(srt_ctx *c, float *ms) {
+    if (!c || !ms) return fail(c, SRT_ERR_INVALID, "srt_denoise_estimate_last_ms: null argument");
+    if (!c->denoise_timed || c->denoise_level_ev != 2) return fail(c, SRT_ERR_INVALID, "srt_denoise_estimate_last_ms: the context's last denoise was not variance-guided");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipEventSynchronize(c->denoise_ev[2]));
+    HIP_TRY(c, hipEventElapsedTime(ms, c->denoise_ev[1], c->denoise_ev[2]));
     return SRT_OK;
 }
 

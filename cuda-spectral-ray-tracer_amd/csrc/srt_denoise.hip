@@ -16,6 +16,18 @@
 //                            for 256), so the taps come straight from L2 / HBM: the lanes of a row read contiguous 16-byte runs.
 //   denoise_epilogue_kernel  the filtered XYZ mean -> unquantised and quantised sRGB through xyz_mean_to_srgb (srt_device.h), three
 //                            row-major [h][w][3] outputs
+// The variance-guided path (srt_denoise_features_vg) adds three kernels and leaves the three above as they are:
+//   denoise_variance_kernel  the spatial estimator: the guide-weighted variance of Y over a 7x7 window at distance 1.  The 32 x 8 tile and
+//                            its halo of 3 pixels are staged in LDS -- 38 x 14 pixels of the two guide float4 and Y, 19 152 B -- so a
+//                            pixel's 49 taps are two ds_read_b128 (a row's lanes read neighbouring 16-byte slots: the 16 lanes of a
+//                            ds_read_b128 group cover 16 distinct slots of the 256-B bank row) and one ds_read_b32 (32 consecutive
+//                            dwords per half wave) each: conflict free at any row pitch, so the rows are not padded.  Reads Y and
+//                            writes v as 4-byte accesses of the colour image's second and fourth lane: no block reads a word that
+//                            another writes.
+//   denoise_level_vg_kernel  the sibling of denoise_level_kernel, tiled and direct, both through denoise_vg_tap: the colour float4
+//                            carries the variance in .w, the luminance term's width comes from a 3x3 blur of it (tiled: nine more
+//                            LDS reads inside the halo of 2 s >= 2; direct: nine 4-byte loads of .w)
+//   denoise_var_out_kernel   the variance after the last level -> channel 1 of the [h][w][2] variance output
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -139,6 +151,186 @@ __global__ __launch_bounds__(256) void denoise_level_kernel(const DenoiseLevelPa
     P.dst[p] = o;
 }
 
+// ---- the variance-guided path --------------------------------------------------------------------------------------------------------
+constexpr uint32_t kDnVarHalo = 3;                                                // the estimator's 7x7 window
+constexpr uint32_t kDnVarLdsW = kDnTileW + 2 * kDnVarHalo, kDnVarLdsH = kDnTileH + 2 * kDnVarHalo;      // 38 x 14 = 532 pixels x 36 B
+constexpr uint32_t kDnVarLdsPixels = kDnVarLdsW * kDnVarLdsH;
+
+// the variance blur's tap weight b[k], k = d + 1: {1/4, 1/2, 1/4}
+__device__ __forceinline__ constexpr float blur_tap(int k) { return k == 1 ? 0.5f : 0.25f; }
+
+// e(dn, kn), e(da, ka), e(dz, kz) of a tap, multiplied into w0 left to right (dn, da, dz as in denoise_tap)
+__device__ __forceinline__ float guide_weight(float w0, float4 p_g0, float4 p_g1, float4 q_g0, float4 q_g1, float kn, float ka, float kz) {
+    const float dn = dist2(p_g0, q_g0);
+    const float da = dist2(p_g1, q_g1);
+    const float zp = p_g0.w, zq = q_g0.w;
+    const float m = (zp > zq) ? zp : zq;
+    const float r = (m > 0.0f) ? (zp - zq) / m : 0.0f;
+    const float dz = r * r;
+    float wt = w0;
+    wt = wt * edge_term(dn, kn);
+    wt = wt * edge_term(da, ka);
+    wt = wt * edge_term(dz, kz);
+    return wt;
+}
+
+struct VarSums { float s0, s1, s2; };
+// one tap of the estimator (srt_c_api.h, "Estimator"): counted only with a finite Y_q
+__device__ __forceinline__ void variance_tap(VarSums &s, float4 p_g0, float4 p_g1, float4 q_g0, float4 q_g1, float yq, float kn, float ka, float kz) {
+    const float g = guide_weight(1.0f, p_g0, p_g1, q_g0, q_g1, kn, ka, kz);      // (1 * e is e: the first product is exact)
+    if (g > 0.0f && (yq - yq) == 0.0f) {
+        s.s0 += g;
+        s.s1 += g * yq;
+        s.s2 += g * (yq * yq);
+    }
+}
+
+struct VgTapSums { float sw, sx, sy, sz, sv; };
+// one tap q of pixel p of a variance-guided level (srt_c_api.h, "Variance-guided level"): c = (colour.xyz, variance)
+__device__ __forceinline__ void denoise_vg_tap(VgTapSums &s, float h2, float4 p_g0, float4 p_g1, float4 p_c, float4 q_g0, float4 q_g1, float4 q_c,
+                                               float kn, float ka, float kz, float kc) {
+    const float dc = dist2(p_c, q_c);
+    const float d = p_c.y - q_c.y;
+    const float dl = d * d;
+    float wt = guide_weight(h2, p_g0, p_g1, q_g0, q_g1, kn, ka, kz);
+    wt = wt * edge_term(dl, kc);
+    if (wt > 0.0f && (dc - dc) == 0.0f) {
+        s.sw += wt;
+        s.sx += wt * q_c.x; s.sy += wt * q_c.y; s.sz += wt * q_c.z;
+        s.sv += (wt * wt) * q_c.w;
+    }
+}
+
+__global__ __launch_bounds__(256) void denoise_variance_kernel(const DenoiseVarianceParams P) {
+    const uint32_t tile_y = blockIdx.x / P.tiles_x, tile_x = blockIdx.x - tile_y * P.tiles_x;
+    const uint32_t lx = threadIdx.x & (kDnTileW - 1u), ly = threadIdx.x / kDnTileW;
+    const uint32_t x0 = tile_x * kDnTileW, y0 = tile_y * kDnTileH;
+    const uint32_t x = x0 + lx, y = y0 + ly;
+
+    __shared__ float4 t_g0[kDnVarLdsPixels], t_g1[kDnVarLdsPixels];
+    __shared__ float t_y[kDnVarLdsPixels];
+    for (uint32_t i = threadIdx.x; i < kDnVarLdsPixels; i += 256u) {
+        const uint32_t ty = i / kDnVarLdsW, tx = i - ty * kDnVarLdsW;
+        const long long gx = (long long)x0 + tx - kDnVarHalo, gy = (long long)y0 + ty - kDnVarHalo;
+        float4 g0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), g1 = g0;      // outside the rectangle: never read as a tap
+        float yv = 0.0f;
+        if (gx >= 0 && gx < (long long)P.w && gy >= 0 && gy < (long long)P.h) {
+            const size_t q = (size_t)gy * P.w + (size_t)gx;
+            g0 = P.guides[2 * q + 0]; g1 = P.guides[2 * q + 1]; yv = P.colour[4 * q + 1];
+        }
+        t_g0[i] = g0; t_g1[i] = g1; t_y[i] = yv;
+    }
+    __syncthreads();
+    if (x >= P.w || y >= P.h) return;
+
+    const uint32_t ip = (ly + kDnVarHalo) * kDnVarLdsW + lx + kDnVarHalo;
+    const float4 p_g0 = t_g0[ip], p_g1 = t_g1[ip];
+    VarSums s = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int dy = -3; dy <= 3; dy++) {
+        const long long qy = (long long)y + dy;
+        if (qy < 0 || qy >= (long long)P.h) continue;
+#pragma unroll
+        for (int dx = -3; dx <= 3; dx++) {
+            const long long qx = (long long)x + dx;
+            if (qx < 0 || qx >= (long long)P.w) continue;
+            const uint32_t i = (uint32_t)((int)ip + dy * (int)kDnVarLdsW + dx);
+            variance_tap(s, p_g0, p_g1, t_g0[i], t_g1[i], t_y[i], P.kn, P.ka, P.kz);
+        }
+    }
+    const float mu = s.s1 / s.s0, m2 = s.s2 / s.s0;
+    const float v = m2 - mu * mu;
+    const float o = (s.s0 > 0.0f && v > 0.0f) ? v : 0.0f;
+    const size_t p = (size_t)y * P.w + x;
+    P.colour[4 * p + 3] = o;
+    P.out_var[2 * p + 0] = o;
+}
+
+template <bool TILED>
+__global__ __launch_bounds__(256) void denoise_level_vg_kernel(const DenoiseLevelVgParams P) {
+    const uint32_t tile_y = blockIdx.x / P.tiles_x, tile_x = blockIdx.x - tile_y * P.tiles_x;
+    const uint32_t lx = threadIdx.x & (kDnTileW - 1u), ly = threadIdx.x / kDnTileW;
+    const uint32_t x0 = tile_x * kDnTileW, y0 = tile_y * kDnTileH;
+    const uint32_t x = x0 + lx, y = y0 + ly;
+    const int step = (int)P.step;
+
+    __shared__ float4 t_g0[TILED ? kDnLdsPixels : 1], t_g1[TILED ? kDnLdsPixels : 1], t_c[TILED ? kDnLdsPixels : 1];
+    const uint32_t halo = 2u * P.step, lw = kDnTileW + 2u * halo, lh = kDnTileH + 2u * halo;      // (TILED: step <= 2, lw * lh <= kDnLdsPixels)
+    if constexpr (TILED) {
+        for (uint32_t i = threadIdx.x; i < lw * lh; i += 256u) {
+            const uint32_t ty = i / lw, tx = i - ty * lw;
+            const long long gx = (long long)x0 + tx - halo, gy = (long long)y0 + ty - halo;
+            float4 g0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), g1 = g0, c = g0;      // outside the rectangle: never read as a tap
+            if (gx >= 0 && gx < (long long)P.w && gy >= 0 && gy < (long long)P.h) {
+                const size_t q = (size_t)gy * P.w + (size_t)gx;
+                g0 = P.guides[2 * q + 0]; g1 = P.guides[2 * q + 1]; c = P.src[q];
+            }
+            t_g0[i] = g0; t_g1[i] = g1; t_c[i] = c;
+        }
+        __syncthreads();
+    }
+    if (x >= P.w || y >= P.h) return;
+
+    const size_t p = (size_t)y * P.w + x;
+    const uint32_t ip = (ly + halo) * lw + lx + halo;      // (TILED only)
+    float4 p_g0, p_g1, p_c;
+    if constexpr (TILED) {
+        p_g0 = t_g0[ip]; p_g1 = t_g1[ip]; p_c = t_c[ip];
+    } else {
+        p_g0 = P.guides[2 * p + 0]; p_g1 = P.guides[2 * p + 1]; p_c = P.src[p];
+    }
+    // the luminance term's width: the 3x3 blur of the input variance at distance 1 (the halo is 2 s >= 2 pixels wide)
+    float bk = 0.0f, bv = 0.0f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; dy++) {
+        const long long qy = (long long)y + dy;
+        if (qy < 0 || qy >= (long long)P.h) continue;
+#pragma unroll
+        for (int dx = -1; dx <= 1; dx++) {
+            const long long qx = (long long)x + dx;
+            if (qx < 0 || qx >= (long long)P.w) continue;
+            float vq;
+            if constexpr (TILED) vq = t_c[(uint32_t)((int)ip + dy * (int)lw + dx)].w;
+            else vq = reinterpret_cast<const float *>(P.src)[4 * ((size_t)qy * P.w + (size_t)qx) + 3];
+            const float k = blur_tap(dy + 1) * blur_tap(dx + 1);
+            bk += k;
+            bv += k * vq;
+        }
+    }
+    const float vb = bv / bk;
+    const float kc = P.ks * vb + P.floor;
+
+    VgTapSums s = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+        const long long qy = (long long)y + dy * step;
+        if (qy < 0 || qy >= (long long)P.h) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const long long qx = (long long)x + dx * step;
+            if (qx < 0 || qx >= (long long)P.w) continue;
+            float4 q_g0, q_g1, q_c;
+            if constexpr (TILED) {
+                const uint32_t i = (uint32_t)((int)(ly + halo) + dy * step) * lw + (uint32_t)((int)(lx + halo) + dx * step);
+                q_g0 = t_g0[i]; q_g1 = t_g1[i]; q_c = t_c[i];
+            } else {
+                const size_t q = (size_t)qy * P.w + (size_t)qx;
+                q_g0 = P.guides[2 * q + 0]; q_g1 = P.guides[2 * q + 1]; q_c = P.src[q];
+            }
+            denoise_vg_tap(s, b3_tap(dy + 2) * b3_tap(dx + 2), p_g0, p_g1, p_c, q_g0, q_g1, q_c, P.kn, P.ka, P.kz, kc);
+        }
+    }
+    float4 o = p_c;
+    if (s.sw > 0.0f) o = make_float4(s.sx / s.sw, s.sy / s.sw, s.sz / s.sw, s.sv / (s.sw * s.sw));
+    P.dst[p] = o;
+}
+
+__global__ __launch_bounds__(256) void denoise_var_out_kernel(const float4 *colour, float *out_var, size_t n) {
+    const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= n) return;
+    out_var[2 * pix + 1] = colour[pix].w;
+}
+
 __global__ __launch_bounds__(256) void denoise_epilogue_kernel(const float4 *colour, float *out_xyz, float *out_lin, float *out_q, size_t n) {
     const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= n) return;
@@ -173,6 +365,33 @@ hipError_t launch_denoise_epilogue(const float *colour, float *out_xyz, float *o
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(denoise_epilogue_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const float4 *>(colour), out_xyz,
                        out_lin, out_q, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_denoise_variance(const DenoiseVarianceParams &p_in, hipStream_t st) {
+    DenoiseVarianceParams p = p_in;
+    if (p.w == 0 || p.h == 0) return hipSuccess;
+    p.tiles_x = (p.w + kDnTileW - 1u) / kDnTileW;
+    const uint64_t blocks = (uint64_t)p.tiles_x * ((p.h + kDnTileH - 1u) / kDnTileH);
+    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(denoise_variance_kernel, dim3((uint32_t)blocks), dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_denoise_level_vg(const DenoiseLevelVgParams &p_in, hipStream_t st) {
+    DenoiseLevelVgParams p = p_in;
+    if (p.w == 0 || p.h == 0) return hipSuccess;
+    p.tiles_x = (p.w + kDnTileW - 1u) / kDnTileW;
+    const uint64_t blocks = (uint64_t)p.tiles_x * ((p.h + kDnTileH - 1u) / kDnTileH);
+    if (blocks > 0x7fffffffull || p.step == 0 || p.step > 128u) return hipErrorInvalidValue;
+    if (p.step <= kDnTiledMaxStep) hipLaunchKernelGGL(denoise_level_vg_kernel<true>, dim3((uint32_t)blocks), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(denoise_level_vg_kernel<false>, dim3((uint32_t)blocks), dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_denoise_var_out(const float *colour, float *out_var, size_t n, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(denoise_var_out_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const float4 *>(colour), out_var, n);
     return hipGetLastError();
 }
 

@@ -209,6 +209,28 @@ struct DenoiseLevelParams {
 hipError_t launch_denoise_level(const DenoiseLevelParams &p, hipStream_t st);
 // colour (float4 per pixel) -> out_xyz / out_lin / out_q, n pixels of three floats each.
 hipError_t launch_denoise_epilogue(const float *colour, float *out_xyz, float *out_lin, float *out_q, size_t n, hipStream_t st);
+// The variance-guided path (srt_denoise_features_vg).  The estimator reads Y = colour[4 p + 1] and the guides, and writes the variance to
+// colour[4 p + 3] and out_var[2 p]; kn .. kz: the squared guide sigmas.
+struct DenoiseVarianceParams {
+    const float4 *guides;
+    float *colour, *out_var;
+    uint32_t w, h;
+    uint32_t tiles_x;      // filled in by the launcher
+    float kn, ka, kz;
+};
+hipError_t launch_denoise_variance(const DenoiseVarianceParams &p, hipStream_t st);
+// One variance-guided level at step `step` (1 .. 128) from src to dst (never the same buffer), (colour.xyz, variance) per pixel;
+// ks = sigma_variance * sigma_variance, floor = variance_floor.
+struct DenoiseLevelVgParams {
+    const float4 *guides, *src;
+    float4 *dst;
+    uint32_t w, h, step;
+    uint32_t tiles_x;      // filled in by the launcher
+    float kn, ka, kz, ks, floor;
+};
+hipError_t launch_denoise_level_vg(const DenoiseLevelVgParams &p, hipStream_t st);
+// out_var[2 p + 1] = colour[p].w, n pixels.
+hipError_t launch_denoise_var_out(const float *colour, float *out_var, size_t n, hipStream_t st);
 hipError_t launch_order_tiles(const uint32_t *cost, uint32_t *sorted, uint32_t *rows, uint32_t n, uint32_t n_waves,
                               uint32_t split_load_pct, uint32_t *queue_info, uint32_t order_max_pct, hipStream_t st);
 hipError_t launch_scatter(const ScatterParams &p, hipStream_t st);

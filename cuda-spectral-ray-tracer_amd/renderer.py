@@ -180,6 +180,36 @@ class Renderer:
         self._ck(B.lib().srt_denoise_last_ms(self._h, C.byref(pre), lv, C.byref(epi), C.byref(n)))
         return dict(prepass=pre.value, levels=[lv[i] for i in range(n.value)], epilogue=epi.value)
 
+    def denoise_vg(self, image_width, image_height, **cfg):
+        """the variance-guided denoiser over the context's featured accumulation (srt_denoise_features_vg; cfg: the keywords of
+        denoise_vg_config): dict(xyz, lin, fb, var) -- the three (image_height, image_width, 3) arrays of denoise and var
+        (image_height, image_width, 2): the estimator's variance of Y and the variance after the last level.  Placement as denoise."""
+        c = denoise_vg_config(**cfg)
+        out = [np.zeros((image_height, image_width, 3), np.float32) for _ in range(3)]
+        var = np.zeros((image_height, image_width, 2), np.float32)
+        self._ck(B.lib().srt_denoise_features_vg(self._h, C.byref(c), B.fptr(out[0]), B.fptr(out[1]), B.fptr(out[2]), B.fptr(var), image_width, image_height))
+        return dict(xyz=out[0], lin=out[1], fb=out[2], var=var)
+
+    def denoise_vg_kat(self, xyz_sums, features, samples, **cfg):
+        """the variance-guided denoiser's device path on explicit inputs (srt_denoise_vg_kat; the inputs of denoise_kat) -> (the
+        filtered XYZ mean (h, w, 3), var (h, w, 2))"""
+        c = denoise_vg_config(**cfg)
+        sums = np.ascontiguousarray(xyz_sums, np.float32)
+        rows = np.ascontiguousarray(features, np.float32)
+        if sums.ndim != 3 or sums.shape[2] != 3 or rows.shape != sums.shape[:2] + (FEATURE_CHANNELS,):
+            raise ValueError("denoise_vg_kat: needs xyz_sums (h, w, 3) and features (h, w, %d), got %r and %r" % (FEATURE_CHANNELS, sums.shape, rows.shape))
+        out = np.zeros(sums.shape, np.float32)
+        var = np.zeros(sums.shape[:2] + (2,), np.float32)
+        self._ck(B.lib().srt_denoise_vg_kat(self._h, C.byref(c), B.fptr(sums), B.fptr(rows), int(samples), sums.shape[1], sums.shape[0], B.fptr(out), B.fptr(var)))
+        return out, var
+
+    def denoise_estimate_last_ms(self):
+        """kernel-only ms of the variance estimator of the last denoise on this context, which must have been variance-guided
+        (srt_denoise_estimate_last_ms)"""
+        ms = C.c_float()
+        self._ck(B.lib().srt_denoise_estimate_last_ms(self._h, C.byref(ms)))
+        return ms.value
+
     def accum_reset_streams(self, k):
         """start a STREAMED accumulation (srt_c_api.h): every pixel has k independent RNG streams (1 <= k <= MAX_STREAMS), stream j of lane
         idx seeded XORWOW(seed + j * n_lanes + idx); a pass of spp_add samples (a multiple of k) draws spp_add / k from every stream, and
@@ -792,19 +822,58 @@ def denoise_config(levels=5, sigma_color=1.0, sigma_normal=0.5, sigma_albedo=0.2
     return B.Denoise(int(levels), sig[0], sig[1], sig[2], sig[3], (C.c_uint32 * 3)(0, 0, 0))
 
 
-def render_denoised(scene, cam, width, height, passes, bounce_limit, seed=1984, device=0, renderer=None, **cfg):
+def _denoise_number(name, v):
+    """v as a float32 held in a Python float (a value beyond float32 becomes inf); ValueError for what is no number"""
+    try:
+        if isinstance(v, bool):
+            raise TypeError
+        with np.errstate(over="ignore"):
+            return float(np.float32(v))
+    except (TypeError, ValueError):
+        raise ValueError("denoise: %s must be a number, got %r" % (name, v))
+
+
+def denoise_vg_config(levels=5, sigma_variance=2.0, sigma_normal=0.5, sigma_albedo=0.25, sigma_depth=0.1, variance_floor=1e-8):
+    """srt_denoise_vg from Python numbers, checked as the library checks it (ValueError): levels a whole number in [0, 8]; sigma_variance
+    > 0 and finite in float32 -- the luminance term's width in standard deviations of the pixel's estimated noise; the three guide sigmas
+    as in denoise_config (inf switches a guide off); variance_floor > 0 in float32, in squared XYZ units -- the luminance term's width
+    where the estimate is 0 (inf switches the term off).  sigma_variance and variance_floor are starting values, not tuned, like the
+    other defaults."""
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or not 0 <= levels <= MAX_DENOISE_LEVELS:
+        raise ValueError("denoise: levels must be a whole number in [0, %d], got %r" % (MAX_DENOISE_LEVELS, levels))
+    sv = _denoise_number("sigma_variance", sigma_variance)
+    if not sv > 0.0 or sv == float("inf"):
+        raise ValueError("denoise: sigma_variance must be > 0 and finite in float32, got %r" % (sigma_variance,))
+    sig = []
+    for name, v in (("sigma_normal", sigma_normal), ("sigma_albedo", sigma_albedo), ("sigma_depth", sigma_depth)):
+        f = _denoise_number(name, v)
+        if not f > 0.0:
+            raise ValueError("denoise: %s must be > 0 in float32 (inf switches the term off), got %r" % (name, v))
+        sig.append(f)
+    vf = _denoise_number("variance_floor", variance_floor)
+    if not vf > 0.0:
+        raise ValueError("denoise: variance_floor must be > 0 in float32 (inf switches the luminance term off), got %r" % (variance_floor,))
+    return B.DenoiseVG(int(levels), sv, sig[0], sig[1], sig[2], vf, (C.c_uint32 * 2)(0, 0))
+
+
+def render_denoised(scene, cam, width, height, passes, bounce_limit, seed=1984, device=0, renderer=None, variance_guided=False, **cfg):
     """render_features with the denoiser behind every pass: a generator of (spp_total, result, features, denoised), `denoised` the dict
-    of Renderer.denoise (cfg: the keywords of denoise_config) for the samples held so far.  The denoiser only reads the accumulation, so
-    result and features are render_features' bit for bit.  Schedule and cfg are checked here, before any device is touched."""
+    of Renderer.denoise (cfg: the keywords of denoise_config) for the samples held so far -- with variance_guided=True the dict of
+    Renderer.denoise_vg (cfg: the keywords of denoise_vg_config).  The denoiser only reads the accumulation, so result and features are
+    render_features' bit for bit.  Schedule and cfg are checked here, before any device is touched."""
     sched = progressive_schedule(passes)
-    denoise_config(**cfg)
-    return _denoised_passes(scene, cam, width, height, sched, bounce_limit, seed, device, renderer, cfg)
+    if variance_guided:
+        denoise_vg_config(**cfg)
+    else:
+        denoise_config(**cfg)
+    return _denoised_passes(scene, cam, width, height, sched, bounce_limit, seed, device, renderer, cfg, bool(variance_guided))
 
 
-def _denoised_passes(scene, cam, width, height, sched, bounce_limit, seed, device, renderer, cfg):
+def _denoised_passes(scene, cam, width, height, sched, bounce_limit, seed, device, renderer, cfg, variance_guided=False):
     with _image_session(scene, cam, width, height, sum(sched), bounce_limit, seed, device, renderer) as r:
         r.accum_reset_features()
         for spp_add in sched:
             r.render_chunk_accum(width, height, spp_add)
             r.scatter_tiles()
-            yield r.accum_samples, _collect(r, width, height), r.read_features(width, height), r.denoise(width, height, **cfg)
+            den = r.denoise_vg(width, height, **cfg) if variance_guided else r.denoise(width, height, **cfg)
+            yield r.accum_samples, _collect(r, width, height), r.read_features(width, height), den

@@ -392,6 +392,55 @@ SRT_API int srt_denoise_kat(srt_ctx *ctx, const srt_denoise *cfg, const float *x
  * support (tools/denoise_cost.py), like srt_last_kernel_ms.  SRT_ERR_INVALID before the first denoise. */
 SRT_API int srt_denoise_last_ms(srt_ctx *ctx, float *prepass_ms, float level_ms[8], float *epilogue_ms, uint32_t *levels);
 
+/* Variance-guided mode of the a-trous denoiser (opt-in; the entry points above and their results are what they were).  The plain filter
+ * stops at colour edges with one absolute width, sigma_color, so the same picture rendered four times brighter is filtered differently.
+ * This mode compares a luminance difference to the pixel's own noise instead, as SVGF does (Schied et al. 2017, sections 4.2 - 4.4): it
+ * estimates a per-pixel variance of the luminance, carries it through the levels, and scales the edge-stopping width with it.  The
+ * featured accumulation keeps no second moments, so the estimate is SPATIAL (SVGF's answer for pixels without history): the
+ * guide-weighted variance of Y over a 7x7 window.  Scaling the XYZ sums by a power of two s and variance_floor by s * s scales the
+ * filtered XYZ by s and both variances by s * s, exactly (barring overflow and underflow).
+ * The filter, operation by operation -- everything fp32, not contracted, left to right as written, selects and not fmax; the restatement
+ * is tests/denoise_vg_reference.py.  Prepass, e(d2, k), dn, da, dz, kn, ka, kz and the B3 taps h are those of srt_denoise_features above;
+ * Y is the colour's second component (XYZ's Y is luminance); dc is the plain filter's, on the level's input colour.
+ *   Host constants, fp32: ks = sigma_variance * sigma_variance (formed once), vf = variance_floor.
+ *   Estimator, per pixel p: taps q at offsets (dx, dy), dy = -3 .. 3 in the outer loop, dx = -3 .. 3 in the inner one (distance 1, the
+ *     centre included); a tap outside the rectangle is skipped.
+ *       g = e(dn, kn);  g = g * e(da, ka);  g = g * e(dz, kz);
+ *       if (g > 0 && (Y_q - Y_q) == 0) { s0 += g;  s1 += g * Y_q;  s2 += g * (Y_q * Y_q); }       ((Y_q - Y_q) == 0: Y_q is finite.
+ *         Without the clause one NaN or inf pixel would zero the variance of its whole 7x7 neighbourhood.)
+ *       mu = s1 / s0;  m2 = s2 / s0;  v = m2 - mu * mu;  v_p = (s0 > 0 && v > 0) ? v : 0.        (NaN goes to 0.)
+ *   Variance-guided level i = 0 .. levels-1, step s = 1 << i, from (c, v) to (c, v):
+ *       vb_p: the 3x3 blur of the level's input v at distance 1 (not s), b = {1/4, 1/2, 1/4}, dy = -1 .. 1 outer, dx inner, a tap
+ *         outside the rectangle skipped:  k = b[dy+1] * b[dx+1];  bk += k;  bv += k * v_q;   vb_p = bv / bk.
+ *       kc_p = ks * vb_p + vf.
+ *       For tap q of pixel p (the 25 taps of the plain level, in its order):
+ *         d = Y_p - Y_q;  dl = d * d;
+ *         wt = h[dy+2] * h[dx+2];  wt = wt * e(dn, kn);  wt = wt * e(da, ka);  wt = wt * e(dz, kz);  wt = wt * e(dl, kc_p);
+ *         if (wt > 0 && (dc - dc) == 0) { sw += wt;  sx += wt * c_q.x;  sy += wt * c_q.y;  sz += wt * c_q.z;  sv += (wt * wt) * v_q; }
+ *       Output of the level:  sw > 0 ? (sx / sw, sy / sw, sz / sw, sv / (sw * sw)) : (c_p, v_p).
+ *       ((dc - dc) == 0: the colour difference is finite in all three components.  dl sees Y alone, so without the clause a pixel whose
+ *        X or Z is inf or NaN would be taken in by its neighbours.  With it, a non-finite pixel keeps its colour and its variance and no
+ *        neighbour takes it in, and at variance_floor = +inf -- e(dl, +inf) is 1 for a finite dl -- the colour output IS
+ *        srt_denoise_features' at sigma_color = +inf, bit for bit, on every input: the plain filter is a special case.)
+ *   Epilogue: unchanged.  levels == 0 returns (c_p, the estimate).
+ *   srt_denoise_features_vg  srt_denoise_features in this mode: placement, clipping, synchronisation, the read-only behaviour towards the
+ *                         accumulation and the partition refusal are its.  out_var[((y * image_width) + x) * 2 + k]: k = 0 the
+ *                         estimator's variance, k = 1 the variance after the last level (equal at levels == 0).  Any of the four
+ *                         outputs may be NULL, not all.  Working images: 108 B per pixel of the chunk.  Refused as srt_denoise_features
+ *                         refuses, the accumulation unchanged, and for: levels > 8; sigma_variance NaN, <= 0 or infinite; a guide sigma
+ *                         NaN or <= 0 (+inf still switches a guide off); variance_floor NaN or <= 0 (+inf is allowed and switches the
+ *                         luminance term off); non-zero reserved words.
+ *   srt_denoise_vg_kat    srt_denoise_kat in this mode; out_var[h][w][2] as above.  No argument may be NULL.
+ *   srt_denoise_last_ms   works after either kind of denoise; after this one the epilogue's time includes the kernel that copies the
+ *                         final variance out.  srt_denoise_estimate_last_ms gives the estimator kernel's time: SRT_ERR_INVALID when the
+ *                         context's last denoise was not variance-guided (or none has run). */
+typedef struct srt_denoise_vg { uint32_t levels; float sigma_variance, sigma_normal, sigma_albedo, sigma_depth, variance_floor; uint32_t reserved[2]; } srt_denoise_vg;
+SRT_API int srt_denoise_features_vg(srt_ctx *ctx, const srt_denoise_vg *cfg, float *out_xyz, float *out_lin, float *out_q, float *out_var,
+                                    uint32_t image_width, uint32_t image_height);
+SRT_API int srt_denoise_vg_kat(srt_ctx *ctx, const srt_denoise_vg *cfg, const float *xyz_sums, const float *features,
+                               uint32_t samples, uint32_t w, uint32_t h, float *out_xyz, float *out_var);
+SRT_API int srt_denoise_estimate_last_ms(srt_ctx *ctx, float *ms);
+
 /* Sample-parallel pixels (no reference counterpart; a deliberate departure from its one RNG stream per pixel, so opt-in).  A STREAMED
  * accumulation gives every pixel K independent RNG streams, each with its own state and its own XYZ sum, so that any lane of any wave
  * can render a stream while others render the pixel's other streams: the longest sequential chain of a pass is spp_add / K samples.
