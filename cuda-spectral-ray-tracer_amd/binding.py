@@ -139,12 +139,15 @@ PROTOTYPES = {
     "srt_read_spectral": (_i, [_vp, _u32, _u32, _fp, _u32, _u32]),
     "srt_accum_reset_features": (_i, [_vp]),
     "srt_read_features": (_i, [_vp, _fp, _u32, _u32]),
+    "srt_accum_reset_adaptive_features": (_i, [_vp, C.POINTER(Adaptive)]),
     "srt_denoise_features": (_i, [_vp, C.POINTER(Denoise), _fp, _fp, _fp, _u32, _u32]),
     "srt_denoise_kat": (_i, [_vp, C.POINTER(Denoise), _fp, _fp, _u32, _u32, _u32, _fp]),
     "srt_denoise_last_ms": (_i, [_vp, _fp, _fp, _fp, C.POINTER(_u32)]),
     "srt_denoise_features_vg": (_i, [_vp, C.POINTER(DenoiseVG), _fp, _fp, _fp, _fp, _u32, _u32]),
     "srt_denoise_vg_kat": (_i, [_vp, C.POINTER(DenoiseVG), _fp, _fp, _u32, _u32, _u32, _fp, _fp]),
     "srt_denoise_estimate_last_ms": (_i, [_vp, _fp]),
+    "srt_denoise_features_mv": (_i, [_vp, C.POINTER(DenoiseVG), _fp, _fp, _fp, _fp, _u32, _u32]),
+    "srt_denoise_mv_kat": (_i, [_vp, C.POINTER(DenoiseVG), _fp, _fp, C.POINTER(_u32), _fp, _u32, _u32, _fp, _fp]),
     "srt_accum_reset_streams": (_i, [_vp, _u32]),
     "srt_accum_streams": (_i, [_vp, C.POINTER(_u32)]),
     "srt_set_gather_planes": (_i, [_vp, _u32]),
@@ -192,6 +195,7 @@ PROTOTYPES = {
     "srt_comm_accum_active": (_i, [_vp, C.POINTER(_u64)]),
     "srt_comm_accum_reset_spectral": (_i, [_vp]),
     "srt_comm_accum_reset_features": (_i, [_vp]),
+    "srt_comm_accum_reset_adaptive_features": (_i, [_vp, C.POINTER(Adaptive)]),
     "srt_comm_accum_reset_streams": (_i, [_vp, _u32]),
     "srt_comm_synchronize": (_i, [_vp]),
     "srt_comm_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_f)]),

@@ -118,7 +118,7 @@ struct srt_ctx {
     // The one accumulation of a context (srt_accum_reset*, srt_render_chunk_accum).
     struct Accumulation {
         enum class State { Invalid, Empty, Bound } state = State::Invalid;   // Empty: reset, no pass yet; Bound: passes of one chunk
-        enum class Kind { Plain, Adaptive, Spectral, Streams, Features } kind = Kind::Plain;    // MODE 3 / 4 / 5 / 6 / 7 passes (never two of the last four)
+        enum class Kind { Plain, Adaptive, Spectral, Streams, Features, AdaptiveFeatures } kind = Kind::Plain;    // MODE 3 / 4 / 5 / 6 / 7 / 8 passes (adaptive + features is the one combination)
         uint32_t total = 0;                             // samples per pixel in the sums (streamed: over all streams)
         uint32_t n_streams = 1;                         // streamed: the RNG streams per pixel (K); 1 otherwise
         uint32_t w = 0, h = 0, offx = 0, offy = 0;      // the chunk of the first pass
@@ -126,10 +126,10 @@ struct srt_ctx {
         void begin(Kind k, uint32_t streams_per_pixel = 1) { kind = k; n_streams = streams_per_pixel; state = State::Empty; }      // (srt_accum_reset has zeroed the total)
         bool valid() const { return state != State::Invalid; }
         bool bound() const { return state == State::Bound; }
-        bool adaptive() const { return kind == Kind::Adaptive; }
+        bool adaptive() const { return kind == Kind::Adaptive || kind == Kind::AdaptiveFeatures; }
         bool spectral() const { return kind == Kind::Spectral; }
         bool streamed() const { return kind == Kind::Streams; }
-        bool featured() const { return kind == Kind::Features; }
+        bool featured() const { return kind == Kind::Features || kind == Kind::AdaptiveFeatures; }
     } accum;
     // the buffers behind it, allocated on first use:
     DeviceBuffer d_accum;                               // progressive rendering (AccumLayout)
@@ -310,6 +310,7 @@ struct Pass {
     uint32_t streams;          // streamed passes: K, the copies of every queue row (one per stream); 1 otherwise
 };
 
+bool adaptive_mode(RenderMode m) { return m == Adaptive || m == AdaptiveFeatures; }      // MODE 4 and MODE 8 share everything around the launch
 uint32_t split_rows_bound(const srt_ctx *c) { return (uint32_t)std::min<uint64_t>((uint64_t)c->tiles_local * 64, 0x7fffffffull); }
 // The queue head is a 32-bit pixel-slot counter, and a streamed pass runs K copies of every row: its tiles are split only where even
 // the finest split of every tile stays below 2^32 slots; srt_render_chunk_accum refuses a pass whose UNsplit rows do not.
@@ -335,7 +336,7 @@ int prepare_tiles(srt_ctx *c, const Pass &ps) {
     HIP_TRY(c, c->d_tiles.reserve(tile_floats * kTilePlanes * sizeof(float)));
     // (only the plane groups this launch writes: group 0, or all three when the parity planes were asked for.  Not on the later passes
     // of an adaptive accumulation: their converged pixels keep the slots they wrote last)
-    if (!(ps.mode == Adaptive && ps.later)) HIP_TRY(c, hipMemsetAsync(c->d_tiles.ptr, 0, tile_floats * c->gather_planes * sizeof(float), ps.st));
+    if (!(adaptive_mode(ps.mode) && ps.later)) HIP_TRY(c, hipMemsetAsync(c->d_tiles.ptr, 0, tile_floats * c->gather_planes * sizeof(float), ps.st));
     HIP_TRY(c, hipMemsetAsync(c->d_counters.ptr, 0, (kCounters + 1) * sizeof(unsigned long long), ps.st));
     return SRT_OK;
 }
@@ -395,7 +396,7 @@ QueueSource queue_source(const srt_ctx *c, const Pass &ps) {
     // (adaptive passes after the first: the queue the previous pass compacted -- the probe's rows, or the identity order, whose tiles
     // still hold an active pixel.  A queue row has a 22-bit tile field: beyond that the pass runs the plain identity queue, and its
     // converged pixels are only skipped at the fetch)
-    if (ps.mode == Adaptive && ps.later && c->tiles_local <= kQueueTileMask) return QueueSource::Compacted;
+    if (adaptive_mode(ps.mode) && ps.later && c->tiles_local <= kQueueTileMask) return QueueSource::Compacted;
     if (!ps.ordered) return QueueSource::Identity;
     // (accumulating passes: the probe runs on the FIRST pass whatever its sample count -- short passes would otherwise run an unordered
     // queue -- and the later passes of the accumulation reuse its queue: a tile's cost depends on its geometry, not on the sample index,
@@ -407,7 +408,7 @@ int choose_queue(srt_ctx *c, Pass &ps, RenderParams &p) {
     const bool schedulable = c->probe_spp > 0 && c->tiles_local > 1 && c->tiles_local <= kQueueTileMask;   // the tile field of a queue row
     ps.ordered = schedulable && (ps.spp_add || c->spp > 4 * c->probe_spp);
     ps.adapt_bound = ps.ordered && c->split_load_pct ? split_rows_bound(c) : c->tiles_local;      // (adaptive passes are never streamed)
-    if (ps.mode == Adaptive) HIP_TRY(c, c->d_adapt_queue.reserve(AdaptQueue::bytes(std::max<uint32_t>(ps.adapt_bound, 1u))));
+    if (adaptive_mode(ps.mode)) HIP_TRY(c, c->d_adapt_queue.reserve(AdaptQueue::bytes(std::max<uint32_t>(ps.adapt_bound, 1u))));
     const QueueSource src = queue_source(c, ps);
     c->sched_probe_queue = false; c->sched_compacted_queue = false;      // (srt_read_tile_schedule: set again below and by compact_adaptive_queue)
     if (src == QueueSource::Compacted) {
@@ -489,12 +490,12 @@ int combine_streams(srt_ctx *c, const Pass &ps, const RenderParams &p) {
 }
 
 // spp_add == 0: a plain launch of c->spp samples (Plain, or Counting when instrumented); spp_add > 0: an accumulating pass of spp_add
-// samples (Accum / Adaptive / Spectral / Streams / Features) whose caller has checked the accumulation and enqueued its header.
+// samples (Accum / Adaptive / Spectral / Streams / Features / AdaptiveFeatures) whose caller has checked the accumulation and enqueued its header.
 // width .. offy are already narrowed to 16 bit.
 int render_chunk_impl(srt_ctx *c, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy, uint32_t spp_add, hipStream_t st) {
     Pass ps = {};
     ps.spp_add = spp_add; ps.st = st;
-    ps.mode = !spp_add ? (c->count_traversal ? Counting : Plain) : c->accum.adaptive() ? Adaptive : c->accum.spectral() ? Spectral : c->accum.streamed() ? Streams : c->accum.featured() ? Features : Accum;
+    ps.mode = !spp_add ? (c->count_traversal ? Counting : Plain) : c->accum.adaptive() ? (c->accum.featured() ? AdaptiveFeatures : Adaptive) : c->accum.spectral() ? Spectral : c->accum.streamed() ? Streams : c->accum.featured() ? Features : Accum;
     ps.later = spp_add && c->accum.bound(); ps.plan = plan_of(c);
     ps.streams = ps.mode == Streams ? c->accum.n_streams : 1u;
     c->last_w = width; c->last_h = height; c->last_offx = offx; c->last_offy = offy;
@@ -505,13 +506,13 @@ int render_chunk_impl(srt_ctx *c, uint32_t width, uint32_t height, uint32_t offx
     if (const int rc = bind_wave_debug(c, ps, p)) return rc;
     RoctxRange range_render("srt render_kernel");
     if (const int rc = launch_pass(c, ps, p)) return rc;
-    if (ps.mode == Adaptive)
+    if (adaptive_mode(ps.mode))
         if (const int rc = compact_adaptive_queue(c, ps, p)) return rc;
     if (ps.mode == Streams)
         if (const int rc = combine_streams(c, ps, p)) return rc;
     c->timed = true;
     c->stats_spp = spp_add;
-    c->stats_adaptive = ps.mode == Adaptive;
+    c->stats_adaptive = adaptive_mode(ps.mode);
     return SRT_OK;
 }
 
@@ -883,32 +884,49 @@ int srt_accum_streams(const srt_ctx *c, uint32_t *streams) {
     return SRT_OK;
 }
 
-int srt_accum_reset_adaptive(srt_ctx *c, const srt_adaptive *cfg) {
-    if (!c) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_adaptive: null ctx");
+// srt_accum_reset_adaptive and srt_accum_reset_adaptive_features (`features`): one body, so that validation, refusals and invalidation
+// of the second are those of the first by construction; the featured one adds srt_accum_reset_features' allocation rule and rows
+static int accum_reset_adaptive(srt_ctx *c, const srt_adaptive *cfg, bool features, const char *who) {
+    const std::string w_(who);
+    if (!c) return fail(c, SRT_ERR_INVALID, w_ + ": null ctx");
     // refusals first: a refused call leaves the context's accumulation as it was
-    if (!cfg) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_adaptive: null cfg");
+    if (!cfg) return fail(c, SRT_ERR_INVALID, w_ + ": null cfg");
     if (!std::isfinite(cfg->rel_tol) || !std::isfinite(cfg->abs_tol) || cfg->rel_tol < 0.f || cfg->abs_tol < 0.f || !(cfg->rel_tol + cfg->abs_tol > 0.f))
-        return fail(c, SRT_ERR_INVALID, "srt_accum_reset_adaptive: rel_tol and abs_tol must be finite and >= 0, and not both 0");
-    if (cfg->min_spp < 2) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_adaptive: min_spp must be >= 2 (the variance of the mean needs two samples)");
-    if (cfg->reserved != 0) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_adaptive: reserved must be 0");
+        return fail(c, SRT_ERR_INVALID, w_ + ": rel_tol and abs_tol must be finite and >= 0, and not both 0");
+    if (cfg->min_spp < 2) return fail(c, SRT_ERR_INVALID, w_ + ": min_spp must be >= 2 (the variance of the mean needs two samples)");
+    if (cfg->reserved != 0) return fail(c, SRT_ERR_INVALID, w_ + ": reserved must be 0");
     if (c->count_traversal)
-        return fail(c, SRT_ERR_UNSUPPORTED, "srt_accum_reset_adaptive: no instrumented accumulating kernel (srt_set_count_traversal(ctx, 0) first)");
-    if (!c->params_ready) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_adaptive: device parameters must be set first (srt_init_device_params)");
+        return fail(c, SRT_ERR_UNSUPPORTED, w_ + ": no instrumented accumulating kernel (srt_set_count_traversal(ctx, 0) first)");
+    if (!c->params_ready) return fail(c, SRT_ERR_INVALID, w_ + ": device parameters must be set first (srt_init_device_params)");
+    const size_t row_bytes = (size_t)c->n_lanes * kFeatureStride * sizeof(float);
+    if (features && c->d_features.bytes < row_bytes) {
+        // (the new rows are allocated before the old ones go: a failed allocation changes nothing)
+        HIP_TRY(c, hipSetDevice(c->device));
+        DeviceBuffer rows;
+        HIP_TRY(c, rows.reserve(row_bytes));
+        c->d_features = std::move(rows);
+    }
     int rc = srt_accum_reset(c);
     if (rc != SRT_OK) return rc;
     c->accum.invalidate();      // (until the adaptive planes are in place)
     HIP_TRY(c, c->d_adapt.reserve(AdaptPlanes::bytes(c->n_lanes)));
     HIP_TRY(c, hipMemset(c->d_adapt.ptr, 0, AdaptPlanes::bytes(c->n_lanes)));
-    // the adaptive half of the header (the per-pass kernel rewrites only sums and spp_total)
+    if (features) HIP_TRY(c, hipMemset(c->d_features.ptr, 0, row_bytes));
+    // the adaptive half of the header, and the featured part behind it (the per-pass kernel rewrites only sums and spp_total)
     AccumHeader h = {};
     h.sum2 = AdaptPlanes(c).sum2; h.state = AdaptPlanes(c).state;
     h.rel_tol = cfg->rel_tol; h.abs_tol = cfg->abs_tol; h.min_spp = cfg->min_spp;
+    if (features) { h.features = c->d_features.as<float>(); h.mat_col = c->d_mat_col.as<const float>(); }
     const size_t tail = offsetof(AccumHeader, sum2);
     HIP_TRY(c, hipMemcpy(&AccumLayout(c).header->sum2, reinterpret_cast<const char *>(&h) + tail, sizeof(h) - tail, hipMemcpyHostToDevice));
     HIP_TRY(c, hipDeviceSynchronize());
-    c->accum.begin(srt_ctx::Accumulation::Kind::Adaptive);
+    c->accum.begin(features ? srt_ctx::Accumulation::Kind::AdaptiveFeatures : srt_ctx::Accumulation::Kind::Adaptive);
     return SRT_OK;
 }
+
+int srt_accum_reset_adaptive(srt_ctx *c, const srt_adaptive *cfg) { return accum_reset_adaptive(c, cfg, false, "srt_accum_reset_adaptive"); }
+
+int srt_accum_reset_adaptive_features(srt_ctx *c, const srt_adaptive *cfg) { return accum_reset_adaptive(c, cfg, true, "srt_accum_reset_adaptive_features"); }
 
 int srt_accum_active(srt_ctx *c, uint64_t *active) {
     if (!c || !active) return fail(c, SRT_ERR_INVALID, "srt_accum_active: null argument");
@@ -1108,6 +1126,7 @@ struct DenoiseLayout {
 // What either configuration struct asks of the kernels: the plain filter's sigma_color, or the variance-guided filter's two constants.
 struct DenoisePlan {
     bool vg;
+    bool measured;          // variance-guided with the measured per-pixel estimator (srt_denoise_features_mv) in the spatial one's place
     uint32_t levels;
     float kn, ka, kz;
     float sigma_color;      // plain
@@ -1150,7 +1169,8 @@ DenoisePlan denoise_vg_plan(const srt_denoise_vg *cfg) {
 // the two colour images, the epilogue (variance-guided: and the variance after the last level): the row-major results are left in
 // DenoiseLayout::out / var.  Enqueues on the default stream; the caller synchronises.
 // Events: [0] prepass [1] (variance-guided: estimator [2]) level 0 .. epilogue: denoise_level_ev is the event level 0 starts at.
-int run_denoise(srt_ctx *c, const char *who, const DenoisePlan &plan, DenoisePrepassParams pre) {
+// sum_y2: the S2 words of a measured plan (indexed like pre.counts), else unused.
+int run_denoise(srt_ctx *c, const char *who, const DenoisePlan &plan, DenoisePrepassParams pre, const float *sum_y2 = nullptr) {
     const size_t pixels = (size_t)pre.w * pre.h;
     const DenoiseLayout L(c->d_denoise, pixels);
     pre.guides = L.guides; pre.colour = L.colour[0];
@@ -1160,7 +1180,14 @@ int run_denoise(srt_ctx *c, const char *who, const DenoisePlan &plan, DenoisePre
     HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
     HIP_TRY_AS(c, who, launch_denoise_prepass(pre, nullptr));
     HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
-    if (plan.vg) {
+    if (plan.vg && plan.measured) {
+        DenoiseMeasuredParams mp = {};
+        mp.sum_y = pre.sums + pre.sum_comp_stride; mp.sum_y2 = sum_y2; mp.counts = pre.counts; mp.sum_pixel_stride = pre.sum_pixel_stride;
+        mp.tx = pre.tx; mp.ty = pre.ty; mp.bx = pre.bx; mp.w = pre.w; mp.h = pre.h;
+        mp.colour = reinterpret_cast<float *>(L.colour[0]); mp.out_var = L.var;
+        HIP_TRY_AS(c, who, launch_denoise_measured(mp, nullptr));
+        HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
+    } else if (plan.vg) {
         DenoiseVarianceParams vp = {};
         vp.guides = L.guides; vp.colour = reinterpret_cast<float *>(L.colour[0]); vp.out_var = L.var;
         vp.w = pre.w; vp.h = pre.h; vp.kn = plan.kn; vp.ka = plan.ka; vp.kz = plan.kz;
@@ -1200,6 +1227,9 @@ int denoise_features(srt_ctx *c, const char *who, const DenoisePlan &plan, float
     const std::string w_(who);
     if (!c->accum.featured() || !c->accum.bound())
         return fail(c, SRT_ERR_INVALID, w_ + ": no featured accumulation with a pass (srt_accum_reset_features and srt_render_chunk_accum first)");
+    if (plan.measured && (!c->accum.adaptive() || c->accum.total < 2))
+        return fail(c, SRT_ERR_INVALID, w_ + ": needs an adaptive featured accumulation holding at least 2 samples (srt_accum_reset_adaptive_features; the "
+                                             "measured variance of the mean needs S2 and two samples)");
     if (c->rank != 0 || c->world != 1)
         return fail(c, SRT_ERR_UNSUPPORTED, w_ + ": needs the whole chunk on this context (partition (0, 1)): pixels of other ranks read +0");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1212,7 +1242,9 @@ int denoise_features(srt_ctx *c, const char *who, const DenoisePlan &plan, float
         pre.sums = AccumLayout(c).sums; pre.sum_pixel_stride = 1; pre.sum_comp_stride = c->n_lanes;
         pre.rows = c->d_features.as<const float4>();
         pre.tx = c->tx; pre.ty = c->ty; pre.bx = c->bx; pre.w = w; pre.h = h; pre.samples = c->accum.total;
-        if (const int rc = run_denoise(c, who, plan, pre)) return rc;
+        // (an adaptive featured accumulation: every pixel of the chunk is normalised by its own count, the samples field of its state word)
+        if (c->accum.adaptive()) pre.counts = AdaptPlanes(c).state;
+        if (const int rc = run_denoise(c, who, plan, pre, c->accum.adaptive() ? AdaptPlanes(c).sum2 : nullptr)) return rc;
         const ChunkRect rect = chunk_rect(c, image_width, image_height);
         const DenoiseLayout L(c->d_denoise, pixels);
         for (int k = 0; k < 4; k++) {
@@ -1227,22 +1259,31 @@ int denoise_features(srt_ctx *c, const char *who, const DenoisePlan &plan, float
 }
 
 // srt_denoise_kat / srt_denoise_vg_kat behind their configuration checks (out_var: variance-guided only)
+// (a measured plan: sample_map[h][w] and sum_y2[h][w] in the place of the scalar `samples`, which is not read)
 int denoise_kat(srt_ctx *c, const char *who, const DenoisePlan &plan, const float *xyz_sums, const float *features, uint32_t samples, uint32_t w, uint32_t h,
-                float *out_xyz, float *out_var) {
+                float *out_xyz, float *out_var, const uint32_t *sample_map = nullptr, const float *sum_y2 = nullptr) {
     if (samples == 0 || w == 0 || h == 0 || (uint64_t)w * h > 0x7fffffffull) return fail(c, SRT_ERR_INVALID, std::string(who) + ": samples, w and h must be positive, w x h below 2^31");
-    HIP_TRY(c, hipSetDevice(c->device));
     const size_t pixels = (size_t)w * h;
+    if (sample_map)
+        for (size_t k = 0; k < pixels; k++)
+            if ((sample_map[k] & ~kAdaptConverged) == 0) return fail(c, SRT_ERR_INVALID, std::string(who) + ": a zero in samples (every pixel must hold at least one sample)");
+    HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY_AS(c, who, c->d_denoise.reserve(DenoiseLayout::bytes(pixels, plan.vg)));
-    HIP_TRY_AS(c, who, c->d_denoise_in.reserve(pixels * (kFeatureStride + 3) * sizeof(float)));
-    float *d_rows = c->d_denoise_in.as<float>(), *d_sums = d_rows + pixels * kFeatureStride;
+    HIP_TRY_AS(c, who, c->d_denoise_in.reserve(pixels * (kFeatureStride + 3 + 2) * sizeof(float)));
+    float *d_rows = c->d_denoise_in.as<float>(), *d_sums = d_rows + pixels * kFeatureStride, *d_map = d_sums + pixels * 3, *d_s2 = d_map + pixels;
     HIP_TRY_AS(c, who, hipMemcpy(d_rows, features, pixels * kFeatureStride * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY_AS(c, who, hipMemcpy(d_sums, xyz_sums, pixels * 3 * sizeof(float), hipMemcpyHostToDevice));
+    if (sample_map) {
+        HIP_TRY_AS(c, who, hipMemcpy(d_map, sample_map, pixels * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY_AS(c, who, hipMemcpy(d_s2, sum_y2, pixels * sizeof(float), hipMemcpyHostToDevice));
+    }
     // a grid of one w x h block makes the prepass's block-linear lane the row-major pixel
     DenoisePrepassParams pre = {};
     pre.sums = d_sums; pre.sum_pixel_stride = 3; pre.sum_comp_stride = 1;
     pre.rows = reinterpret_cast<const float4 *>(d_rows);
     pre.tx = w; pre.ty = h; pre.bx = 1; pre.w = w; pre.h = h; pre.samples = samples;
-    if (const int rc = run_denoise(c, who, plan, pre)) return rc;
+    if (sample_map) pre.counts = reinterpret_cast<const uint32_t *>(d_map);
+    if (const int rc = run_denoise(c, who, plan, pre, sample_map ? d_s2 : nullptr)) return rc;
     const DenoiseLayout L(c->d_denoise, pixels);
     HIP_TRY_AS(c, who, hipMemcpy(out_xyz, L.out[0], pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
     if (out_var) HIP_TRY_AS(c, who, hipMemcpy(out_var, L.var, pixels * 2 * sizeof(float), hipMemcpyDeviceToHost));
@@ -1279,6 +1320,25 @@ int srt_denoise_vg_kat(srt_ctx *c, const srt_denoise_vg *cfg, const float *xyz_s
     if (!c || !cfg || !xyz_sums || !features || !out_xyz || !out_var) return fail(c, SRT_ERR_INVALID, "srt_denoise_vg_kat: null argument");
     if (const char *why = denoise_vg_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_denoise_vg_kat: ") + why);
     return denoise_kat(c, "srt_denoise_vg_kat", denoise_vg_plan(cfg), xyz_sums, features, samples, w, h, out_xyz, out_var);
+}
+
+int srt_denoise_features_mv(srt_ctx *c, const srt_denoise_vg *cfg, float *out_xyz, float *out_lin, float *out_q, float *out_var, uint32_t image_width, uint32_t image_height) {
+    if (!c || !cfg) return fail(c, SRT_ERR_INVALID, "srt_denoise_features_mv: null argument");
+    if ((!out_xyz && !out_lin && !out_q && !out_var) || image_width == 0 || image_height == 0) return fail(c, SRT_ERR_INVALID, "srt_denoise_features_mv: no output / empty image");
+    if (const char *why = denoise_vg_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_denoise_features_mv: ") + why);
+    float *const host[4] = {out_xyz, out_lin, out_q, out_var};
+    DenoisePlan plan = denoise_vg_plan(cfg);
+    plan.measured = true;
+    return denoise_features(c, "srt_denoise_features_mv", plan, host, image_width, image_height);
+}
+
+int srt_denoise_mv_kat(srt_ctx *c, const srt_denoise_vg *cfg, const float *xyz_sums, const float *features, const uint32_t *samples, const float *sum_y2,
+                       uint32_t w, uint32_t h, float *out_xyz, float *out_var) {
+    if (!c || !cfg || !xyz_sums || !features || !samples || !sum_y2 || !out_xyz || !out_var) return fail(c, SRT_ERR_INVALID, "srt_denoise_mv_kat: null argument");
+    if (const char *why = denoise_vg_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_denoise_mv_kat: ") + why);
+    DenoisePlan plan = denoise_vg_plan(cfg);
+    plan.measured = true;
+    return denoise_kat(c, "srt_denoise_mv_kat", plan, xyz_sums, features, 1u, w, h, out_xyz, out_var, samples, sum_y2);
 }
 
 int srt_denoise_last_ms(srt_ctx *c, float *prepass_ms, float *level_ms, float *epilogue_ms, uint32_t *levels) {

@@ -27,6 +27,9 @@
 //   denoise_level_vg_kernel  the sibling of denoise_level_kernel, tiled and direct, both through denoise_vg_tap: the colour float4
 //                            carries the variance in .w, the luminance term's width comes from a 3x3 blur of it (tiled: nine more
 //                            LDS reads inside the halo of 2 s >= 2; direct: nine 4-byte loads of .w)
+//   denoise_prepass_counts_kernel / denoise_measured_kernel: an accumulation whose pixels hold different sample counts (adaptive +
+//                            features) -- the prepass with the pixel's own count, and the per-pixel estimator of srt_denoise_features_mv
+//                            (the variance of the mean from the pixel's measured S1 and S2); one thread per pixel, no neighbours
 //   denoise_var_out_kernel   the variance after the last level -> channel 1 of the [h][w][2] variance output
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -90,6 +93,43 @@ __global__ __launch_bounds__(256) void denoise_prepass_kernel(const DenoisePrepa
     P.colour[pix] = make_float4(inv * s[0], inv * s[P.sum_comp_stride], inv * s[2 * P.sum_comp_stride], 0.0f);
     P.guides[2 * pix + 0] = make_float4(inv * f0.x, inv * f0.y, inv * f0.z, z);
     P.guides[2 * pix + 1] = make_float4(inv * f0.w, inv * f1.x, inv * f1.y, inv * f1.w);
+}
+
+// the prepass of an accumulation whose pixels hold different sample counts (adaptive + features, srt_denoise_mv_kat): the kernel above
+// with the pixel's own count n_p = counts[idx] & ~kAdaptConverged in the place of the global total, and nothing else changed
+__global__ __launch_bounds__(256) void denoise_prepass_counts_kernel(const DenoisePrepassParams P) {
+    const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= (size_t)P.w * P.h) return;
+    const uint32_t y = (uint32_t)(pix / P.w), x = (uint32_t)(pix - (size_t)y * P.w);
+    const size_t idx = block_linear_idx(x, y, P.tx, P.ty, P.bx);
+    const float *s = P.sums + idx * P.sum_pixel_stride;
+    const float4 f0 = P.rows[idx * (kFeatureStride / 4u) + 0], f1 = P.rows[idx * (kFeatureStride / 4u) + 1];
+    const uint32_t n_p = P.counts[idx] & ~kAdaptConverged;
+    const float inv = 1.0f / (float)n_p;
+    const float z = (f1.w > 0.0f) ? f1.z / f1.w : 0.0f;
+    P.colour[pix] = make_float4(inv * s[0], inv * s[P.sum_comp_stride], inv * s[2 * P.sum_comp_stride], 0.0f);
+    P.guides[2 * pix + 0] = make_float4(inv * f0.x, inv * f0.y, inv * f0.z, z);
+    P.guides[2 * pix + 1] = make_float4(inv * f0.w, inv * f1.x, inv * f1.y, inv * f1.w);
+}
+
+// the measured estimator (srt_c_api.h, srt_denoise_features_mv): the variance of the pixel's mean luminance from its own S1, S2 and count
+// -- the first four operations of the stopping rule (adaptive_converged, srt_kernels.hip), in that order; no neighbour is read
+__global__ __launch_bounds__(256) void denoise_measured_kernel(const DenoiseMeasuredParams P) {
+    const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= (size_t)P.w * P.h) return;
+    const uint32_t y = (uint32_t)(pix / P.w), x = (uint32_t)(pix - (size_t)y * P.w);
+    const size_t idx = block_linear_idx(x, y, P.tx, P.ty, P.bx);
+    const uint32_t n_p = P.counts[idx] & ~kAdaptConverged;
+    const float s1 = P.sum_y[idx * P.sum_pixel_stride], s2 = P.sum_y2[idx];
+    const float n = (float)n_p;
+    const float mean = s1 / n;
+    const float mm = mean * mean;
+    float v = s2 / n - mm;
+    v = v > 0.0f ? v : 0.0f;
+    const float vm = v / (n - 1.0f);
+    const float o = (n_p >= 2u && (vm - vm) == 0.0f) ? vm : 0.0f;
+    P.colour[4 * pix + 3] = o;
+    P.out_var[2 * pix + 0] = o;
 }
 
 template <bool TILED>
@@ -346,7 +386,15 @@ __global__ __launch_bounds__(256) void denoise_epilogue_kernel(const float4 *col
 hipError_t launch_denoise_prepass(const DenoisePrepassParams &p, hipStream_t st) {
     const size_t n = (size_t)p.w * p.h;
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(denoise_prepass_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, p);
+    if (p.counts) hipLaunchKernelGGL(denoise_prepass_counts_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(denoise_prepass_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_denoise_measured(const DenoiseMeasuredParams &p, hipStream_t st) {
+    const size_t n = (size_t)p.w * p.h;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(denoise_measured_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, p);
     return hipGetLastError();
 }
 

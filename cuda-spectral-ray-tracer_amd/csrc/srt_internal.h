@@ -121,6 +121,7 @@ struct AccumHeader {
 // lane of the grid indexed by the block-linear idx -- the raw first-hit sums [0..2] normal, [3..5] albedo, [6] distance, [7] hits -- and
 // mat_col, the scene's per-material colour table (one float4 per material: srt_material.col, 0), uploaded with the scene.
 // srt_accum_reset_features writes the two fields once.
+// Adaptive featured accumulations (MODE 8, srt_accum_reset_adaptive_features) read the adaptive fields and the featured fields together.
 constexpr uint32_t kFeatureStride = 8;      // 32 B per pixel: two 16-byte accesses
 constexpr uint32_t kStreamSumPlane = 6;
 constexpr uint32_t kMaxStreams = 16;      // SRT_MAX_STREAMS (srt_c_api.h)
@@ -150,8 +151,8 @@ hipError_t launch_init_rng(uint32_t *rng, uint32_t n_lanes, uint64_t seed, hipSt
 struct PlanKnobs { bool wide_refs = false; int lds_cache_max = -1; };
 // The render launch's variant; the values are render_kernel's MODE template argument.  Plain: render; Counting: instrumented; Probe: cost
 // probe; Accum: accumulating render (p.wave_debug -> AccumHeader); Adaptive / Spectral / Streams / Features: adaptive / spectral / streamed /
-// featured accumulating render.
-enum RenderMode { Plain = 0, Counting = 1, Probe = 2, Accum = 3, Adaptive = 4, Spectral = 5, Streams = 6, Features = 7 };
+// featured accumulating render; AdaptiveFeatures: adaptive and featured at once.
+enum RenderMode { Plain = 0, Counting = 1, Probe = 2, Accum = 3, Adaptive = 4, Spectral = 5, Streams = 6, Features = 7, AdaptiveFeatures = 8 };
 hipError_t launch_render(const RenderParams &p, const PlanKnobs &knobs, uint32_t n_cu, RenderMode mode, hipStream_t st);
 hipError_t launch_accum_header(AccumHeader *dst, float *sums, uint32_t spp_total, hipStream_t st);      // writes *dst on the stream
 // Pixel queue of the next adaptive pass (see adapt_flag_kernel): the rows of `src_rows` (src_info[0] of them; nullptr: the identity
@@ -196,7 +197,9 @@ struct DenoisePrepassParams {
     uint32_t tx, ty, bx;
     uint32_t w, h, samples;
     float4 *guides, *colour;
+    const uint32_t *counts;      // null: every pixel holds `samples`; else the pixel's own count, counts[idx] & ~kAdaptConverged (> 0)
 };
+// counts == null: the kernel every plain featured accumulation has always run; else its per-pixel-count sibling (inv = 1 / (float)n_p)
 hipError_t launch_denoise_prepass(const DenoisePrepassParams &p, hipStream_t st);
 // One level at step `step` (1 .. 128) from src to dst (never the same buffer); kn .. kc: the level's squared sigmas.
 struct DenoiseLevelParams {
@@ -219,6 +222,18 @@ struct DenoiseVarianceParams {
     float kn, ka, kz;
 };
 hipError_t launch_denoise_variance(const DenoiseVarianceParams &p, hipStream_t st);
+// The measured estimator (srt_denoise_features_mv): pixel (x, y) reads lane idx as the prepass does -- its count counts[idx] &
+// ~kAdaptConverged, its Y sum sum_y[idx * sum_pixel_stride] and its S2 sum_y2[idx] -- and writes the variance of its mean to
+// colour[4 p + 3] and out_var[2 p].
+struct DenoiseMeasuredParams {
+    const float *sum_y, *sum_y2;
+    const uint32_t *counts;
+    size_t sum_pixel_stride;
+    uint32_t tx, ty, bx;
+    uint32_t w, h;
+    float *colour, *out_var;
+};
+hipError_t launch_denoise_measured(const DenoiseMeasuredParams &p, hipStream_t st);
 // One variance-guided level at step `step` (1 .. 128) from src to dst (never the same buffer), (colour.xyz, variance) per pixel;
 // ks = sigma_variance * sigma_variance, floor = variance_floor.
 struct DenoiseLevelVgParams {

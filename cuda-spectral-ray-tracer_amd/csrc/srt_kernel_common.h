@@ -31,6 +31,9 @@ struct LdsUniforms {
     float rel_tol, abs_tol;
     uint32_t accum_film[2];      // spectral launches (MODE 5) only: AccumHeader's film
     uint32_t streams;            // streamed launches (MODE 6) only: AccumHeader's K; accum_sums holds its stream planes (the block is full now)
+    // Featured launches borrow slots instead of growing the block (a larger block would move the LDS map of every kernel): MODE 7 keeps
+    // its feature rows in accum_film and its colour table in accum_sum2.  MODE 8 (adaptive + features) needs accum_sum2 for S2 itself:
+    // its rows stay in accum_film and its colour table goes to tile_cost, which only the cost probe (MODE 2) ever reads back.
 };
 static_assert(sizeof(LdsUniforms) <= kLdsUniF4 * 16, "uniform block too large");
 typedef __attribute__((address_space(3))) LdsUniforms lds_uniforms;

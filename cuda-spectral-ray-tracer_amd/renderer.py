@@ -141,8 +141,15 @@ class Renderer:
     def accum_reset_features(self):
         """start a FEATURED accumulation (srt_c_api.h): like accum_reset, and each later pass also adds, at the first hit of every
         sample's camera ray, the face-forwarded normal, the hit material's colour, the distance and 1 to the pixel's eight raw float32
-        sums (read_features; feature_means normalises them).  Never adaptive, spectral or streamed."""
+        sums (read_features; feature_means normalises them).  Never spectral or streamed; accum_reset_adaptive_features is the adaptive one."""
         self._ck(B.lib().srt_accum_reset_features(self._h))
+
+    def accum_reset_adaptive_features(self, rel_tol, abs_tol=0.0, min_spp=16):
+        """start an ADAPTIVE FEATURED accumulation (srt_c_api.h): accum_reset_adaptive with the feature rows of accum_reset_features.
+        Image, sums, S2, sample map and RNG state are accum_reset_adaptive's bit for bit; a pixel that stopped after n samples holds the
+        feature row of a plain featured n-spp frame.  accum_active, accum_stats and read_features all work on it, and denoise,
+        denoise_vg and denoise_mv take it (each pixel normalised by its own count)."""
+        self._ck(B.lib().srt_accum_reset_adaptive_features(self._h, C.byref(adaptive_config(rel_tol, abs_tol, min_spp))))
 
     def read_features(self, image_width, image_height):
         """raw first-hit sums of the featured accumulation's chunk, float32: dict(normal (H, W, 3), albedo (H, W, 3), distance (H, W),
@@ -201,6 +208,39 @@ class Renderer:
         out = np.zeros(sums.shape, np.float32)
         var = np.zeros(sums.shape[:2] + (2,), np.float32)
         self._ck(B.lib().srt_denoise_vg_kat(self._h, C.byref(c), B.fptr(sums), B.fptr(rows), int(samples), sums.shape[1], sums.shape[0], B.fptr(out), B.fptr(var)))
+        return out, var
+
+    def denoise_mv(self, image_width, image_height, **cfg):
+        """the measured-variance denoiser over the context's ADAPTIVE FEATURED accumulation of at least 2 samples
+        (srt_denoise_features_mv; cfg: the keywords of denoise_vg_config): the dict of denoise_vg, var[..., 0] being the variance of the
+        pixel's mean luminance the sampler measured -- max(S2 / n - (S1 / n)^2, 0) / (n - 1) from the pixel's own count, Y sum and S2 --
+        in the place of the spatial estimate."""
+        c = denoise_vg_config(**cfg)
+        out = [np.zeros((image_height, image_width, 3), np.float32) for _ in range(3)]
+        var = np.zeros((image_height, image_width, 2), np.float32)
+        self._ck(B.lib().srt_denoise_features_mv(self._h, C.byref(c), B.fptr(out[0]), B.fptr(out[1]), B.fptr(out[2]), B.fptr(var), image_width, image_height))
+        return dict(xyz=out[0], lin=out[1], fb=out[2], var=var)
+
+    def denoise_mv_kat(self, xyz_sums, features, samples, sum_y2, **cfg):
+        """the measured-variance denoiser's device path on explicit inputs (srt_denoise_mv_kat): xyz_sums (h, w, 3), features (h, w, 8),
+        samples (h, w) whole numbers >= 1 -- every pixel's own count -- and sum_y2 (h, w) -> (the filtered XYZ mean (h, w, 3), var
+        (h, w, 2)).  Checked here as the library checks it (ValueError): the shapes, and no zero in samples."""
+        c = denoise_vg_config(**cfg)
+        sums = np.ascontiguousarray(xyz_sums, np.float32)
+        rows = np.ascontiguousarray(features, np.float32)
+        if sums.ndim != 3 or sums.shape[2] != 3 or rows.shape != sums.shape[:2] + (FEATURE_CHANNELS,):
+            raise ValueError("denoise_mv_kat: needs xyz_sums (h, w, 3) and features (h, w, %d), got %r and %r" % (FEATURE_CHANNELS, sums.shape, rows.shape))
+        n_in = np.asarray(samples)
+        s2 = np.ascontiguousarray(sum_y2, np.float32)
+        if n_in.shape != sums.shape[:2] or s2.shape != sums.shape[:2]:
+            raise ValueError("denoise_mv_kat: samples and sum_y2 must be (h, w) = %r, got %r and %r" % (sums.shape[:2], n_in.shape, s2.shape))
+        if n_in.dtype.kind not in "iu" or (n_in < 1).any() or (n_in > 0x7fffffff).any():
+            raise ValueError("denoise_mv_kat: samples must be whole numbers in [1, 2^31 - 1] (every pixel holds at least one sample)")
+        n = np.ascontiguousarray(n_in, np.uint32)
+        out = np.zeros(sums.shape, np.float32)
+        var = np.zeros(sums.shape[:2] + (2,), np.float32)
+        self._ck(B.lib().srt_denoise_mv_kat(self._h, C.byref(c), B.fptr(sums), B.fptr(rows), n.ctypes.data_as(C.POINTER(C.c_uint32)), B.fptr(s2),
+                                            sums.shape[1], sums.shape[0], B.fptr(out), B.fptr(var)))
         return out, var
 
     def denoise_estimate_last_ms(self):
@@ -464,6 +504,11 @@ class Comm:
         """Renderer.accum_reset_features on every local rank (any communicator: no decision crosses ranks); the rows stay with their
         ranks (Renderer.read_features per context: each pixel is owned by one rank and reads +0 on the others)"""
         self._ck(B.lib().srt_comm_accum_reset_features(self._h))
+
+    def accum_reset_adaptive_features(self, rel_tol, abs_tol=0.0, min_spp=16):
+        """Renderer.accum_reset_adaptive_features on every local rank (not on a process-per-GPU communicator: SrtError); the rows stay
+        with their ranks, as for accum_reset_features"""
+        self._ck(B.lib().srt_comm_accum_reset_adaptive_features(self._h, C.byref(adaptive_config(rel_tol, abs_tol, min_spp))))
 
     def accum_reset_streams(self, k):
         """Renderer.accum_reset_streams on every local rank (any communicator: no decision crosses ranks)"""
@@ -877,3 +922,41 @@ def _denoised_passes(scene, cam, width, height, sched, bounce_limit, seed, devic
             r.scatter_tiles()
             den = r.denoise_vg(width, height, **cfg) if variance_guided else r.denoise(width, height, **cfg)
             yield r.accum_samples, _collect(r, width, height), r.read_features(width, height), den
+
+
+ADAPTIVE_DENOISE_VARIANCE = ("measured", "spatial", None)
+
+
+def render_adaptive_denoised(scene, cam, width, height, bounce_limit, rel_tol, abs_tol=0.0, min_spp=16, step=16, max_spp=1024, variance="measured",
+                             seed=1984, device=0, renderer=None, **cfg):
+    """render_adaptive on an adaptive featured accumulation with a denoiser behind every pass: a generator of (spp_total, active_pixels,
+    result, features, denoised).  result is render_adaptive's bit for bit (`samples` included), features the raw sums of read_features
+    (a pixel's row belongs to the samples that pixel holds: feature_means(features, result["samples"].reshape(height, width))), and
+    denoised the dict of Renderer.denoise_mv for variance="measured" (guided by the variance the sampler measured), of
+    Renderer.denoise_vg for "spatial" (cfg: the keywords of denoise_vg_config for both) or of Renderer.denoise for None (the plain
+    filter; cfg: the keywords of denoise_config).  Every denoiser divides a pixel by its own sample count.  Stops as render_adaptive
+    stops.  The arguments are checked here, before any device is touched."""
+    if variance not in ADAPTIVE_DENOISE_VARIANCE:
+        raise ValueError("render_adaptive_denoised: variance must be 'measured', 'spatial' or None, got %r" % (variance,))
+    acfg = adaptive_config(rel_tol, abs_tol, min_spp)
+    sched = adaptive_schedule(min_spp, step, max_spp)
+    if variance is None:
+        denoise_config(**cfg)
+    else:
+        denoise_vg_config(**cfg)
+    return _adaptive_denoised_passes(scene, cam, width, height, bounce_limit, acfg, sched, seed, device, renderer, variance, cfg)
+
+
+def _adaptive_denoised_passes(scene, cam, width, height, bounce_limit, acfg, sched, seed, device, renderer, variance, cfg):
+    with _image_session(scene, cam, width, height, sum(sched), bounce_limit, seed, device, renderer) as r:
+        r._ck(B.lib().srt_accum_reset_adaptive_features(r._h, C.byref(acfg)))      # (after the session has set the planes)
+        for spp_add in sched:
+            r.render_chunk_accum(width, height, spp_add)
+            r.scatter_tiles()
+            active = r.accum_active
+            out = _collect(r, width, height)
+            out["samples"] = r.accum_stats(width, height)["samples"]
+            den = r.denoise_mv(width, height, **cfg) if variance == "measured" else r.denoise_vg(width, height, **cfg) if variance == "spatial" else r.denoise(width, height, **cfg)
+            yield r.accum_samples, active, out, r.read_features(width, height), den
+            if active == 0:
+                break

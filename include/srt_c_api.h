@@ -333,9 +333,10 @@ SRT_API int srt_read_spectral(srt_ctx *ctx, uint32_t first, uint32_t count, floa
  *   srt_accum_reset_features  srt_accum_reset + zeroed feature rows (allocated on first use and when n_lanes grows, 32 B per lane of the
  *                             grid).  Later srt_render_chunk_accum passes run MODE 7.  Refused with the previous accumulation unchanged:
  *                             device parameters not set (SRT_ERR_INVALID); an instrumented context (SRT_ERR_UNSUPPORTED); a failed
- *                             allocation (SRT_ERR_HIP).  Always a PLAIN accumulation: features combined with adaptive sampling, the
- *                             spectral film or streams are NOT supported (adaptive + features is the intended next step; the
- *                             denoiser below, srt_denoise_features, takes a plain featured accumulation).  srt_accum_reset, srt_accum_reset_adaptive, srt_accum_reset_spectral and
+ *                             allocation (SRT_ERR_HIP).  Always a PLAIN accumulation: features combined with the spectral film or
+ *                             streams are NOT supported.  (This paragraph used to end "adaptive + features is the intended next step":
+ *                             that step is srt_accum_reset_adaptive_features, below, and both denoisers take either kind.)
+ *                             srt_accum_reset, srt_accum_reset_adaptive, srt_accum_reset_spectral and
  *                             srt_accum_reset_streams make the next accumulation non-featured again.  Invalidation, the 65535-sample
  *                             limit and the chunk binding are those of srt_accum_reset.
  *   srt_read_features         the raw sums of the accumulation's chunk, row-major: out[((y * image_width) + x) * 8 + c]; only the
@@ -345,12 +346,38 @@ SRT_API int srt_read_spectral(srt_ctx *ctx, uint32_t first, uint32_t count, floa
 SRT_API int srt_accum_reset_features(srt_ctx *ctx);
 SRT_API int srt_read_features(srt_ctx *ctx, float *out, uint32_t image_width, uint32_t image_height);
 
+/* Adaptive sampling and first-hit features in ONE accumulation (no reference counterpart): the frames whose noise differs from pixel to
+ * pixel are the ones a denoiser is for.  An ADAPTIVE FEATURED accumulation is an adaptive accumulation (srt_accum_reset_adaptive: the
+ * same cfg, stopping rule, state words, S2 and queue compaction) that also keeps the feature rows of srt_accum_reset_features (the same
+ * deposit rule).  Later srt_render_chunk_accum passes run render_kernel MODE 8: MODE 4 in every respect -- converged pixels are skipped
+ * at the fetch, the decision and the state word are written at the pixel switch, the pixel queue is compacted on the device between
+ * passes -- plus MODE 7's deposit at the first hit, which draws nothing from the RNG.  What holds, and is tested:
+ *   - under the same cfg and the same pass schedule the image, all nine planes, the XYZ sums, S2, the state words, the active counts and
+ *     the RNG state are bit-identical to an adaptive accumulation's (MODE 4);
+ *   - a pixel that stopped after n samples holds the feature row of a PLAIN featured n-spp frame at that pixel, bit for bit; an active
+ *     pixel holds the row of the running total;
+ *   - a converged pixel's row is not touched by later passes;
+ *   - the result is independent of partition, world size, launch shape and split into passes, as for either parent.
+ *   srt_accum_reset_adaptive_features  validation, refusals and invalidation are srt_accum_reset_adaptive's (cfg as there; an instrumented
+ *                             context; device parameters not set), the rows are allocated by srt_accum_reset_features' rule (on first use
+ *                             and when n_lanes grows; a failed allocation is SRT_ERR_HIP); every refusal leaves the previous
+ *                             accumulation unchanged.  The accumulation is adaptive AND featured: srt_accum_active,
+ *                             srt_read_accum_stats and srt_read_features all work on it, srt_set_gather_planes invalidates it, and
+ *                             srt_denoise_features / _vg / _mv take it.  srt_accum_reset, srt_accum_reset_adaptive,
+ *                             srt_accum_reset_features, srt_accum_reset_spectral and srt_accum_reset_streams make the next accumulation
+ *                             something else again.  (srt_read_features still refuses a plain adaptive accumulation, srt_accum_active a
+ *                             plain featured one.) */
+SRT_API int srt_accum_reset_adaptive_features(srt_ctx *ctx, const srt_adaptive *cfg);
+
 /* Edge-avoiding a-trous denoiser over the first-hit feature buffers (no reference counterpart; kernels in csrc/srt_denoise.hip).  It
  * consumes a FEATURED accumulation: the XYZ sums are filtered by `levels` passes of a 5x5 B3-spline stencil whose taps are weighted down
  * where normal, albedo, hit distance or the colour itself differ.  The filter, operation by operation -- everything fp32, not contracted,
  * evaluated left to right as written, so that a float32 restatement (tests/denoise_reference.py) predicts the device's bits:
  *   Inputs, for the w x h rectangle of the accumulation's chunk (clipped to the grid of srt_init_device_params): S[p][3] the XYZ sums,
  *     F[p][8] the raw feature sums, n = the accumulation's sample total.
+ *     (On an ADAPTIVE featured accumulation -- srt_accum_reset_adaptive_features -- n is the pixel's own count n_p, the samples field of
+ *     its state word: inv = 1.0f / (float)n_p, by a prepass kernel of its own; the global total is not used, and nothing else in the filter
+ *     changes.  With partition (0, 1) every pixel of the chunk holds at least the first pass's samples, so n_p > 0.)
  *   Prepass, per pixel:  inv = 1.0f / (float)n;  c_p = inv * S_p;  N_p = inv * F[0..2];  A_p = inv * F[3..5];
  *     z_p = F[7] > 0 ? F[6] / F[7] : 0.  A sample that missed counts as a zero vector: N and A fade with coverage, which so needs no
  *     term of its own.
@@ -396,7 +423,7 @@ SRT_API int srt_denoise_last_ms(srt_ctx *ctx, float *prepass_ms, float level_ms[
  * stops at colour edges with one absolute width, sigma_color, so the same picture rendered four times brighter is filtered differently.
  * This mode compares a luminance difference to the pixel's own noise instead, as SVGF does (Schied et al. 2017, sections 4.2 - 4.4): it
  * estimates a per-pixel variance of the luminance, carries it through the levels, and scales the edge-stopping width with it.  The
- * featured accumulation keeps no second moments, so the estimate is SPATIAL (SVGF's answer for pixels without history): the
+ * plain featured accumulation keeps no second moments, so the estimate is SPATIAL (SVGF's answer for pixels without history): the
  * guide-weighted variance of Y over a 7x7 window.  Scaling the XYZ sums by a power of two s and variance_floor by s * s scales the
  * filtered XYZ by s and both variances by s * s, exactly (barring overflow and underflow).
  * The filter, operation by operation -- everything fp32, not contracted, left to right as written, selects and not fmax; the restatement
@@ -440,6 +467,30 @@ SRT_API int srt_denoise_features_vg(srt_ctx *ctx, const srt_denoise_vg *cfg, flo
 SRT_API int srt_denoise_vg_kat(srt_ctx *ctx, const srt_denoise_vg *cfg, const float *xyz_sums, const float *features,
                                uint32_t samples, uint32_t w, uint32_t h, float *out_xyz, float *out_var);
 SRT_API int srt_denoise_estimate_last_ms(srt_ctx *ctx, float *ms);
+
+/* Measured-variance mode: the variance-guided filter above, guided by the variance the sampler MEASURED instead of a spatial guess.  An
+ * adaptive featured accumulation holds, per pixel, the count n_p, S1 (the Y sum) and S2 (the sum of squared per-sample Y): the stopping
+ * rule's inputs.  cfg, its validation, the levels, the 3x3 variance blur, the epilogue, the placement and the refusals are those of
+ * srt_denoise_features_vg; the prepass is the per-pixel-count one; only the estimator differs.  Per pixel, fp32, not contracted, left to
+ * right, with n = (float)n_p:
+ *       mean = S1 / n;  v = S2 / n - mean * mean;  v = v > 0 ? v : 0;  vm = v / (n - 1.0f);  v_p = (n_p >= 2 && (vm - vm) == 0) ? vm : 0
+ * -- the first four operations of the stopping rule above (srt_accum_reset_adaptive), so the filter is guided by the very number the
+ * sampler stopped on; a non-finite vm (a NaN or inf pixel) gives 0, as the spatial estimator does.
+ *   srt_denoise_features_mv  needs an ADAPTIVE FEATURED accumulation holding spp_total >= 2, else SRT_ERR_INVALID (a plain featured
+ *                         accumulation included): then every pixel holds at least two samples -- an active one the total, a converged one
+ *                         at least min_spp >= 2.  out_var[..][0] is the estimate above, out_var[..][1] the variance after the last level.
+ *                         At variance_floor = +inf the colour output equals srt_denoise_features at sigma_color = +inf on the same
+ *                         accumulation, bit for bit: the plain filter stays a special case.  srt_denoise_estimate_last_ms reports this
+ *                         estimator's kernel time.
+ *   srt_denoise_mv_kat    the same kernels on caller-supplied row-major host arrays: xyz_sums[h][w][3], features[h][w][8],
+ *                         samples[h][w] (the pixel's count in the low 31 bits, the layout of a state word) and sum_y2[h][w]; S1 is
+ *                         xyz_sums[..][1].  The synthetic door to the per-pixel-count prepass and to the estimator (a pixel with
+ *                         n_p = 1 gets v_p = 0).  A zero count anywhere in samples is SRT_ERR_INVALID, checked on the host; the other
+ *                         refusals are srt_denoise_vg_kat's.  No argument may be NULL. */
+SRT_API int srt_denoise_features_mv(srt_ctx *ctx, const srt_denoise_vg *cfg, float *out_xyz, float *out_lin, float *out_q, float *out_var,
+                                    uint32_t image_width, uint32_t image_height);
+SRT_API int srt_denoise_mv_kat(srt_ctx *ctx, const srt_denoise_vg *cfg, const float *xyz_sums, const float *features,
+                               const uint32_t *samples, const float *sum_y2, uint32_t w, uint32_t h, float *out_xyz, float *out_var);
 
 /* Sample-parallel pixels (no reference counterpart; a deliberate departure from its one RNG stream per pixel, so opt-in).  A STREAMED
  * accumulation gives every pixel K independent RNG streams, each with its own state and its own XYZ sum, so that any lane of any wave
@@ -645,6 +696,9 @@ SRT_API int srt_comm_accum_reset_spectral(srt_comm *comm);
  * rank.  The rows stay with their ranks (srt_read_features per context; each pixel is owned by one rank and reads +0 on the others).  On
  * process-per-GPU communicators too: no decision crosses ranks. */
 SRT_API int srt_comm_accum_reset_features(srt_comm *comm);
+/* srt_accum_reset_adaptive_features on every local rank; like srt_comm_accum_reset_adaptive, SRT_ERR_UNSUPPORTED on a process-per-GPU
+ * communicator.  The rows stay with their ranks, as for srt_comm_accum_reset_features. */
+SRT_API int srt_comm_accum_reset_adaptive_features(srt_comm *comm, const srt_adaptive *cfg);
 /* Sample-parallel pixels on W GPUs: srt_accum_reset_streams on every local context; srt_render_frame_multi_accum then runs MODE 6 on each
  * rank.  On process-per-GPU communicators too: no decision crosses ranks (every rank resets with the same K). */
 SRT_API int srt_comm_accum_reset_streams(srt_comm *comm, uint32_t streams);
