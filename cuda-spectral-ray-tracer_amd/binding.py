@@ -137,6 +137,10 @@ PROTOTYPES = {
     "srt_read_accum_stats": (_i, [_vp, C.POINTER(_u32), _fp, _fp, _u32, _u32]),
     "srt_accum_reset_spectral": (_i, [_vp]),
     "srt_read_spectral": (_i, [_vp, _u32, _u32, _fp, _u32, _u32]),
+    "srt_develop_spectral": (_i, [_vp, _fp, _u32, _f, _fp, _u32, _u32]),
+    "srt_develop_spectral_srgb": (_i, [_vp, _fp, _f, _fp, _fp, _fp, _u32, _u32]),
+    "srt_develop_kat": (_i, [_vp, _fp, _u32, _fp, _u32, _f, _fp]),
+    "srt_develop_last_ms": (_i, [_vp, _fp, _fp]),
     "srt_accum_reset_features": (_i, [_vp]),
     "srt_read_features": (_i, [_vp, _fp, _u32, _u32]),
     "srt_accum_reset_adaptive_features": (_i, [_vp, C.POINTER(Adaptive)]),

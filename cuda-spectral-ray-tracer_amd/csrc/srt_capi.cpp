@@ -145,6 +145,10 @@ struct srt_ctx {
     uint32_t denoise_timed_levels = 0;                  // levels the events of the last denoise bracket
     uint32_t denoise_level_ev = 1;                      // the event level 0 starts at: 1, or 2 after a variance-guided denoise
     bool denoise_timed = false;
+    DeviceBuffer d_develop;                             // the developed film's working blocks (DevelopLayout), grown when the rectangle or the channels grow
+    DeviceBuffer d_develop_in;                          // srt_develop_kat: the caller's film in 96-float rows
+    hipEvent_t develop_ev[3] = {};                      // around the kernels of the last develop: contraction | sRGB epilogue (created on first use)
+    bool develop_timed = false, develop_epilogue = false;
     DeviceBuffer d_streams;                             // sample-parallel pixels (srt_accum_reset_streams, StreamPlanes)
     uint32_t streams_seeded = 0;                        // the K whose RNG streams d_streams holds, seeded since the last srt_init_device_params (0: none)
 };
@@ -601,6 +605,7 @@ void srt_destroy(srt_ctx *c) {
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (hipEvent_t e : c->denoise_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->develop_ev) if (e) (void)hipEventDestroy(e);
     delete c;      // (every DeviceBuffer frees itself, on the device selected above)
 }
 
@@ -1104,6 +1109,153 @@ int srt_read_features(srt_ctx *c, float *out, uint32_t image_width, uint32_t ima
         HIP_TRY(c, hipMemcpy2D(out + rect.first * kFeatureStride, pitch, c->d_features_staging.ptr, row, row, rect.h, hipMemcpyDeviceToHost));
     }
     HIP_TRY(c, hipDeviceSynchronize());
+    return SRT_OK;
+}
+
+// ---- the developed film (srt_develop.hip) -----------------------------------------------------------------------------------------
+namespace {
+
+// d_develop: [the curves, transposed and padded: kFilmSamples x kMaxDevelopChannels floats | developed planes: `channels` floats per pixel
+//             | sRGB variant only: out_lin | out_q: 3 floats per pixel each]
+struct DevelopLayout {
+    float *resp, *out, *lin, *q;
+    static constexpr size_t kRespFloats = (size_t)kFilmSamples * kMaxDevelopChannels;
+    static size_t bytes(size_t pixels, uint32_t channels, bool srgb) { return (kRespFloats + pixels * (channels + (srgb ? 6u : 0u))) * sizeof(float); }
+    DevelopLayout(const DeviceBuffer &d, size_t pixels, uint32_t channels)
+        : resp(d.as<float>()), out(resp + kRespFloats), lin(out + pixels * channels), q(lin + 3 * pixels) {}      // (lin, q: inside the buffer only when reserved with srgb)
+};
+
+const char *develop_args_error(const float *response, uint32_t channels, float scale) {
+    if (channels == 0 || channels > kMaxDevelopChannels) return "channels must be in 1 .. SRT_MAX_DEVELOP_CHANNELS (16)";
+    if (!std::isfinite(scale)) return "scale must be finite";
+    for (size_t i = 0; i < (size_t)channels * kFilmSamples; i++)
+        if (!std::isfinite(response[i])) return "every response must be finite";
+    return nullptr;
+}
+
+// grows a working block; a refused allocation is SRT_ERR_HIP and leaves no error behind for the next launch's hipGetLastError
+int develop_reserve(srt_ctx *c, const char *who, DeviceBuffer &d, size_t bytes) {
+    if (const hipError_t e = d.reserve(bytes)) {
+        (void)hipGetLastError();
+        return hip_fail(c, e, who);
+    }
+    return SRT_OK;
+}
+
+// The contraction of the film rows `film` (the lanes of a tx x ty x bx grid, n_lanes of them) over the w x h rectangle into
+// DevelopLayout::out, then (samples > 0) the sRGB epilogue into lin / q.  d_develop is reserved by the caller.  Enqueues on the default
+// stream; the caller synchronises.  Events: [0] contraction [1] epilogue [2].
+int run_develop(srt_ctx *c, const char *who, const float *film, uint32_t n_lanes, uint32_t tx, uint32_t ty, uint32_t bx, uint32_t w, uint32_t h,
+                const float *response, uint32_t channels, float scale, uint32_t samples) {
+    const size_t pixels = (size_t)w * h;
+    const DevelopLayout L(c->d_develop, pixels, channels);
+    // the curves as the kernel reads them: [j][kc], the padding +0
+    const uint32_t kc = develop_padded_channels(channels);
+    std::vector<float> table((size_t)kFilmSamples * kc, 0.0f);
+    for (uint32_t k = 0; k < channels; k++)
+        for (uint32_t j = 0; j < kFilmSamples; j++) table[(size_t)j * kc + k] = response[(size_t)k * kFilmSamples + j];
+    HIP_TRY_AS(c, who, hipMemcpy(L.resp, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice));
+    c->develop_timed = false;
+    for (hipEvent_t &e : c->develop_ev) if (!e) HIP_TRY_AS(c, who, hipEventCreate(&e));
+    DevelopParams p = {};
+    p.film = film; p.response = L.resp; p.out = L.out; p.scale = scale; p.channels = channels;
+    p.n_lanes = n_lanes; p.tx = tx; p.ty = ty; p.bx = bx; p.w = w; p.h = h;
+    HIP_TRY_AS(c, who, hipEventRecord(c->develop_ev[0], nullptr));
+    HIP_TRY_AS(c, who, launch_develop(p, nullptr));
+    HIP_TRY_AS(c, who, hipEventRecord(c->develop_ev[1], nullptr));
+    if (samples) {
+        HIP_TRY_AS(c, who, launch_develop_srgb(L.out, L.lin, L.q, samples, pixels, nullptr));
+        HIP_TRY_AS(c, who, hipEventRecord(c->develop_ev[2], nullptr));
+    }
+    c->develop_epilogue = samples != 0; c->develop_timed = true;
+    return SRT_OK;
+}
+
+// srt_develop_spectral / srt_develop_spectral_srgb behind their argument checks: host[0] the developed planes, host[1 .. 2] the sRGB
+// variant's outputs (srgb: the accumulation's sample total normalises them)
+int develop_accumulation(srt_ctx *c, const char *who, const float *response, uint32_t channels, float scale, bool srgb, float *const host[3],
+                         uint32_t image_width, uint32_t image_height) {
+    if (!c->accum.spectral() || !c->accum.bound())
+        return fail(c, SRT_ERR_INVALID, std::string(who) + ": no spectral accumulation with a pass (srt_accum_reset_spectral and srt_render_chunk_accum first)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the kernel runs on the chunk's rectangle (clipped to the reference grid); the image clips only what is copied out
+    const uint32_t w = clipped_w(c), h = clipped_h(c);
+    const size_t pixels = (size_t)w * h;
+    if (pixels) {
+        if (const int rc = develop_reserve(c, who, c->d_develop, DevelopLayout::bytes(pixels, channels, srgb))) return rc;
+        if (const int rc = run_develop(c, who, c->d_film.as<float>(), c->n_lanes, c->tx, c->ty, c->bx, w, h, response, channels, scale, srgb ? c->accum.total : 0u)) return rc;
+        const ChunkRect rect = chunk_rect(c, image_width, image_height);
+        const DevelopLayout L(c->d_develop, pixels, channels);
+        const float *src[3] = {L.out, L.lin, L.q};
+        for (int k = 0; k < (srgb ? 3 : 1); k++) {
+            const size_t row = (size_t)rect.w * channels * sizeof(float), src_pitch = (size_t)w * channels * sizeof(float), pitch = (size_t)image_width * channels * sizeof(float);
+            if (host[k] && rect.w && rect.h) HIP_TRY(c, hipMemcpy2D(host[k] + rect.first * channels, pitch, src[k], src_pitch, row, rect.h, hipMemcpyDeviceToHost));
+        }
+    }
+    HIP_TRY(c, hipDeviceSynchronize());
+    return SRT_OK;
+}
+
+}  // namespace
+
+int srt_develop_spectral(srt_ctx *c, const float *response, uint32_t channels, float scale, float *out, uint32_t image_width, uint32_t image_height) {
+    if (!c || !response || !out) return fail(c, SRT_ERR_INVALID, "srt_develop_spectral: null argument");
+    if (image_width == 0 || image_height == 0) return fail(c, SRT_ERR_INVALID, "srt_develop_spectral: empty image");
+    if (const char *why = develop_args_error(response, channels, scale)) return fail(c, SRT_ERR_INVALID, std::string("srt_develop_spectral: ") + why);
+    float *const host[3] = {out, nullptr, nullptr};
+    return develop_accumulation(c, "srt_develop_spectral", response, channels, scale, false, host, image_width, image_height);
+}
+
+int srt_develop_spectral_srgb(srt_ctx *c, const float *response3, float scale, float *out_xyz, float *out_lin, float *out_q, uint32_t image_width, uint32_t image_height) {
+    if (!c) return fail(c, SRT_ERR_INVALID, "srt_develop_spectral_srgb: null ctx");
+    if ((!out_xyz && !out_lin && !out_q) || image_width == 0 || image_height == 0) return fail(c, SRT_ERR_INVALID, "srt_develop_spectral_srgb: no output / empty image");
+    // response3 == NULL: the colour-matching rows x, y, z of srt_color_tables
+    float cie[3 * kFilmSamples];
+    if (!response3) {
+        float rows[96 * 4];
+        cmf_rows(rows);
+        for (uint32_t k = 0; k < 3; k++)
+            for (uint32_t j = 0; j < kFilmSamples; j++) cie[k * kFilmSamples + j] = rows[4 * j + k];
+        response3 = cie;
+    }
+    if (const char *why = develop_args_error(response3, 3, scale)) return fail(c, SRT_ERR_INVALID, std::string("srt_develop_spectral_srgb: ") + why);
+    float *const host[3] = {out_xyz, out_lin, out_q};
+    return develop_accumulation(c, "srt_develop_spectral_srgb", response3, 3, scale, true, host, image_width, image_height);
+}
+
+int srt_develop_kat(srt_ctx *c, const float *film, uint32_t n_pixels, const float *response, uint32_t channels, float scale, float *out) {
+    if (!c || !film || !response || !out) return fail(c, SRT_ERR_INVALID, "srt_develop_kat: null argument");
+    if (n_pixels == 0 || n_pixels > 0x7fffffffu) return fail(c, SRT_ERR_INVALID, "srt_develop_kat: n_pixels must be in 1 .. 2^31 - 1");
+    if (const char *why = develop_args_error(response, channels, scale)) return fail(c, SRT_ERR_INVALID, std::string("srt_develop_kat: ") + why);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const char *who = "srt_develop_kat";
+    if (const int rc = develop_reserve(c, who, c->d_develop_in, (size_t)n_pixels * kFilmStride * sizeof(float))) return rc;      // (the larger block first)
+    if (const int rc = develop_reserve(c, who, c->d_develop, DevelopLayout::bytes(n_pixels, channels, false))) return rc;
+    // 96-float rows; the unused word is a NaN, which no result may show
+    std::vector<float> rows((size_t)n_pixels * kFilmStride);
+    for (size_t p = 0; p < n_pixels; p++) {
+        memcpy(&rows[p * kFilmStride], film + p * kFilmSamples, kFilmSamples * sizeof(float));
+        for (uint32_t j = kFilmSamples; j < kFilmStride; j++) rows[p * kFilmStride + j] = NAN;
+    }
+    HIP_TRY_AS(c, who, hipMemcpy(c->d_develop_in.ptr, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice));
+    // a grid of one n x 1 block makes the block-linear lane the pixel
+    if (const int rc = run_develop(c, who, c->d_develop_in.as<float>(), n_pixels, n_pixels, 1, 1, n_pixels, 1, response, channels, scale, 0)) return rc;
+    HIP_TRY_AS(c, who, hipMemcpy(out, DevelopLayout(c->d_develop, n_pixels, channels).out, (size_t)n_pixels * channels * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY_AS(c, who, hipDeviceSynchronize());
+    return SRT_OK;
+}
+
+int srt_develop_last_ms(srt_ctx *c, float *contract_ms, float *epilogue_ms) {
+    if (!c) return fail(c, SRT_ERR_INVALID, "srt_develop_last_ms: null ctx");
+    if (!c->develop_timed) return fail(c, SRT_ERR_INVALID, "srt_develop_last_ms: no develop has run on this context");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipEventSynchronize(c->develop_ev[c->develop_epilogue ? 2 : 1]));
+    float ms = 0.0f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->develop_ev[0], c->develop_ev[1]));
+    if (contract_ms) *contract_ms = ms;
+    ms = 0.0f;
+    if (c->develop_epilogue) HIP_TRY(c, hipEventElapsedTime(&ms, c->develop_ev[1], c->develop_ev[2]));
+    if (epilogue_ms) *epilogue_ms = ms;
     return SRT_OK;
 }
 

@@ -246,6 +246,24 @@ struct DenoiseLevelVgParams {
 hipError_t launch_denoise_level_vg(const DenoiseLevelVgParams &p, hipStream_t st);
 // out_var[2 p + 1] = colour[p].w, n pixels.
 hipError_t launch_denoise_var_out(const float *colour, float *out_var, size_t n, hipStream_t st);
+// The developed film (srt_develop.hip; the contraction is stated in srt_c_api.h at srt_develop_spectral).  Lane idx of the grid
+// [0, n_lanes) holds the film row film[idx * kFilmStride ..]; the lane of pixel (x, y) = the inverse of block_linear_idx(x, y, tx, ty, bx)
+// writes out[((y * w) + x) * channels + k] = (sum over j ascending of F_j * R[k][j]) * scale when x < w and y < h (a caller's
+// film[n][96] with tx = n, ty = 1, bx = 1, w = n, h = 1 makes the map the identity).  response: the curves transposed and padded with
+// +0, [kFilmSamples][develop_padded_channels(channels)], on the device.
+constexpr uint32_t kMaxDevelopChannels = 16;      // SRT_MAX_DEVELOP_CHANNELS (srt_c_api.h)
+struct DevelopParams {
+    const float *film, *response;
+    float *out;
+    float scale;
+    uint32_t channels;
+    uint32_t n_lanes, tx, ty, bx;
+    uint32_t w, h;
+};
+uint32_t develop_padded_channels(uint32_t channels);      // the kernel variant's channel count: the smallest of 1, 2, 3, 4, 8, 16 that holds them
+hipError_t launch_develop(const DevelopParams &p, hipStream_t st);
+// n pixels of three developed XYZ sums over `samples` samples -> out_lin / out_q (either may be null), three floats per pixel each.
+hipError_t launch_develop_srgb(const float *xyz, float *out_lin, float *out_q, uint32_t samples, size_t n, hipStream_t st);
 hipError_t launch_order_tiles(const uint32_t *cost, uint32_t *sorted, uint32_t *rows, uint32_t n, uint32_t n_waves,
                               uint32_t split_load_pct, uint32_t *queue_info, uint32_t order_max_pct, hipStream_t st);
 hipError_t launch_scatter(const ScatterParams &p, hipStream_t st);

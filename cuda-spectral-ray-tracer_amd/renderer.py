@@ -138,6 +138,53 @@ class Renderer:
         self._ck(B.lib().srt_read_spectral(self._h, int(first), int(count), B.fptr(out), image_width, image_height))
         return out
 
+    def develop_spectral(self, image_width, image_height, response, scale=1.0, filter=None):
+        """the film developed on the device (srt_develop_spectral): out[y, x, k] = (sum over j ascending of F_j * response[k][j]) * scale
+        in float32, (image_height, image_width, K) -- another sensor's curves, a colour filter (folded into the curves by
+        sensor_response), a band image.  Only the K planes leave the device; placement as read_spectral (the chunk's rectangle, zeros
+        elsewhere and at pixels of other ranks).  Reads the accumulation, changes nothing of it."""
+        resp = sensor_response(response, filter)
+        s = _develop_scale(scale)
+        out = np.zeros((image_height, image_width, resp.shape[0]), np.float32)
+        self._ck(B.lib().srt_develop_spectral(self._h, B.fptr(resp), resp.shape[0], s, B.fptr(out), image_width, image_height))
+        return out
+
+    def develop_spectral_srgb(self, image_width, image_height, response=None, scale=None, filter=None):
+        """three developed channels taken as XYZ sums (srt_develop_spectral_srgb): dict(xyz, lin, fb) of (image_height, image_width, 3)
+        float32 arrays -- the developed sums, and the unquantised and quantised sRGB the render kernel's conversion makes of them and the
+        accumulation's sample total.  response=None: the colour-matching rows of srt_color_tables; scale=None: the kernel's float32
+        470/7, with which the sums are the film's own XYZ sums up to reassociation.  filter: 95 transmittances in front of the lens."""
+        if response is None and filter is None:
+            resp, ptr = None, None
+        else:
+            resp = sensor_response(cie_response() if response is None else response, filter)
+            if resp.shape[0] != 3:
+                raise ValueError("develop_spectral_srgb: needs three response curves (taken as X, Y, Z), got %d" % resp.shape[0])
+            ptr = B.fptr(resp)
+        s = CIE_SCALE if scale is None else _develop_scale(scale)
+        out = [np.zeros((image_height, image_width, 3), np.float32) for _ in range(3)]
+        self._ck(B.lib().srt_develop_spectral_srgb(self._h, ptr, s, B.fptr(out[0]), B.fptr(out[1]), B.fptr(out[2]), image_width, image_height))
+        return dict(xyz=out[0], lin=out[1], fb=out[2])
+
+    def develop_kat(self, film, response, scale=1.0):
+        """the develop kernel on an explicit film (srt_develop_kat): film (n_pixels, 95) float32 -> (n_pixels, K).  Needs no scene and no
+        accumulation."""
+        resp = sensor_response(response)
+        s = _develop_scale(scale)
+        rows = np.ascontiguousarray(film, np.float32)
+        if rows.ndim != 2 or rows.shape[1] != FILM_SAMPLES or rows.shape[0] == 0:
+            raise ValueError("develop_kat: needs a film (n_pixels, %d) with n_pixels >= 1, got %r" % (FILM_SAMPLES, rows.shape))
+        out = np.zeros((rows.shape[0], resp.shape[0]), np.float32)
+        self._ck(B.lib().srt_develop_kat(self._h, B.fptr(rows), rows.shape[0], B.fptr(resp), resp.shape[0], s, B.fptr(out)))
+        return out
+
+    def develop_last_ms(self):
+        """kernel-only ms of the last develop on this context (srt_develop_last_ms): dict(contract, epilogue); epilogue is 0 unless it was
+        develop_spectral_srgb"""
+        a, b = C.c_float(), C.c_float()
+        self._ck(B.lib().srt_develop_last_ms(self._h, C.byref(a), C.byref(b)))
+        return dict(contract=a.value, epilogue=b.value)
+
     def accum_reset_features(self):
         """start a FEATURED accumulation (srt_c_api.h): like accum_reset, and each later pass also adds, at the first hit of every
         sample's camera ray, the face-forwarded normal, the hit material's colour, the distance and 1 to the pixel's eight raw float32
@@ -525,6 +572,17 @@ class Comm:
             out = f if out is None else out + f
         return out
 
+    def develop_spectral(self, image_width, image_height, response, scale=1.0, filter=None):
+        """the developed film of the frame (Renderer.develop_spectral): on a single-process communicator (init_all) the sum of the local
+        ranks' results, which is exact -- every pixel is non-zero on one rank only; on a process-per-GPU communicator (init_rank) THIS
+        rank's part (its own pixels, zeros elsewhere), as read_spectral documents for the film"""
+        resp = sensor_response(response, filter)
+        out = None
+        for r in self.renderers:
+            d = r.develop_spectral(image_width, image_height, resp, scale)
+            out = d if out is None else out + d
+        return out
+
     def render_frame_accum(self, width, height, spp_add, offx=0, offy=0):
         """render_frame with an accumulating pass of spp_add samples on every rank (Renderer.render_chunk_accum)"""
         self._ck(B.lib().srt_render_frame_multi_accum(self._h, width, height, offx, offy, spp_add))
@@ -781,6 +839,90 @@ def film_to_xyz(film):
     B.check(B.lib().srt_color_tables(B.fptr(cmf), B.fptr(m)))
     xyz = cmf.reshape(FILM_SAMPLES, 4)[:, :3].astype(np.float64)
     return (film.astype(np.float64) @ xyz) * float(np.float32(470.0) / np.float32(7.0))
+
+
+MAX_DEVELOP_CHANNELS = 16                                   # SRT_MAX_DEVELOP_CHANNELS (srt_c_api.h)
+CIE_SCALE = float(np.float32(470.0) / np.float32(7.0))      # the kernel's float32 470/7: film_to_xyz's d
+
+
+def cie_response():
+    """the colour-matching rows x, y, z of srt_color_tables as response curves, float32 (3, 95)"""
+    cmf = np.zeros(FILM_SAMPLES * 4, np.float32)
+    m = np.zeros(9, np.float32)
+    B.check(B.lib().srt_color_tables(B.fptr(cmf), B.fptr(m)))
+    return np.ascontiguousarray(cmf.reshape(FILM_SAMPLES, 4)[:, :3].T)
+
+
+def sensor_response(curves, filter=None):
+    """response curves for Renderer.develop_spectral as a contiguous float32 (K, 95) array, checked as the library checks them
+    (ValueError, before any device is touched): shape (K, 95) or (95,), 1 <= K <= MAX_DEVELOP_CHANNELS, every entry finite in float32.
+    filter: 95 transmittances of a colour filter in front of the lens, finite, folded into every curve -- one float32 product per
+    entry, R'[k][j] = R[k][j] * T_j."""
+    try:
+        with np.errstate(over="ignore"):
+            r = np.array(curves, dtype=np.float32, ndmin=2)
+    except (TypeError, ValueError):
+        raise ValueError("sensor_response: the curves must be numbers in a (K, %d) or (%d,) array" % (FILM_SAMPLES, FILM_SAMPLES))
+    if r.ndim != 2 or r.shape[1] != FILM_SAMPLES or not 1 <= r.shape[0] <= MAX_DEVELOP_CHANNELS:
+        raise ValueError("sensor_response: needs (K, %d) or (%d,) curves with 1 <= K <= %d, got shape %r" % (FILM_SAMPLES, FILM_SAMPLES, MAX_DEVELOP_CHANNELS, np.shape(curves)))
+    if not np.isfinite(r).all():
+        raise ValueError("sensor_response: every response must be finite in float32")
+    if filter is not None:
+        try:
+            with np.errstate(over="ignore"):
+                t = np.array(filter, dtype=np.float32)
+        except (TypeError, ValueError):
+            raise ValueError("sensor_response: the filter must be %d numbers" % FILM_SAMPLES)
+        if t.shape != (FILM_SAMPLES,) or not np.isfinite(t).all():
+            raise ValueError("sensor_response: the filter must be %d finite transmittances, got shape %r" % (FILM_SAMPLES, t.shape))
+        with np.errstate(over="ignore"):
+            r = (r * t).astype(np.float32)
+        if not np.isfinite(r).all():
+            raise ValueError("sensor_response: a filtered response overflows float32")
+    return np.ascontiguousarray(r)
+
+
+def _develop_scale(scale):
+    """scale as a finite float32 held in a Python float (ValueError otherwise)"""
+    try:
+        if isinstance(scale, bool):
+            raise TypeError
+        with np.errstate(over="ignore"):
+            s = float(np.float32(scale))
+    except (TypeError, ValueError):
+        raise ValueError("develop: scale must be a number, got %r" % (scale,))
+    if not np.isfinite(s):
+        raise ValueError("develop: scale must be finite in float32, got %r" % (scale,))
+    return s
+
+
+def render_developed(scene, cam, width, height, passes, bounce_limit, response=None, filter=None, scale=None, seed=1984, device=0, renderer=None):
+    """render_spectral's passes with the film developed on the device behind every pass, without reading the film back: a generator of
+    (spp_total, result, developed), `result` with the keys of render_image.  response=None: `developed` is the dict of
+    Renderer.develop_spectral_srgb (the colour-matching rows, scale=None the float32 470/7) -- the picture through `filter`; else the
+    (H, W, K) array of Renderer.develop_spectral(response, scale (None: 1), filter).  The develop only reads the accumulation, so result
+    is render_spectral's bit for bit.  Schedule, curves, filter and scale are checked here, before any device is touched."""
+    sched = progressive_schedule(passes)
+    if response is None:
+        resp = None if filter is None else sensor_response(cie_response(), filter)
+    else:
+        resp = sensor_response(response, filter)
+    s = None if scale is None else _develop_scale(scale)
+    return _developed_passes(scene, cam, width, height, sched, bounce_limit, seed, device, renderer, resp, response is None, s)
+
+
+def _developed_passes(scene, cam, width, height, sched, bounce_limit, seed, device, renderer, resp, srgb, scale):
+    with _image_session(scene, cam, width, height, sum(sched), bounce_limit, seed, device, renderer) as r:
+        r.accum_reset_spectral()
+        for spp_add in sched:
+            r.render_chunk_accum(width, height, spp_add)
+            r.scatter_tiles()
+            out = _collect(r, width, height)
+            if srgb:
+                dev = r.develop_spectral_srgb(width, height, resp, scale)
+            else:
+                dev = r.develop_spectral(width, height, resp, 1.0 if scale is None else scale)
+            yield r.accum_samples, out, dev
 
 
 def render_spectral(scene, cam, width, height, passes, bounce_limit, seed=1984, device=0, renderer=None, first=0, count=FILM_SAMPLES):

@@ -311,6 +311,50 @@ SRT_API int srt_read_accum_stats(srt_ctx *ctx, uint32_t *samples, float *sum_y, 
 SRT_API int srt_accum_reset_spectral(srt_ctx *ctx);
 SRT_API int srt_read_spectral(srt_ctx *ctx, uint32_t first, uint32_t count, float *out, uint32_t image_width, uint32_t image_height);
 
+/* The film developed on the device (no reference counterpart; kernels in csrc/srt_develop.hip).  Everything a film is used for is a
+ * contraction over its 95 grid samples -- another sensor's response curves, a colour filter in front of the lens, a band image, the
+ * colour-matching rows themselves -- and only the K resulting planes have to leave the device.  The operation, for a pixel's film row
+ * F_0 .. F_94, K response curves R[k][j] (row-major [K][95], fp32) and an fp32 scale -- everything fp32, not contracted, in this order,
+ * so that a float32 restatement (tests/develop_reference.py) predicts the device's bits:
+ *     a_k = +0.0f
+ *     for j = 0, 1, .., 94 in this order:   t = F_j * R[k][j];   a_k = a_k + t      (the product rounded, then the sum rounded)
+ *     out_k = a_k * scale
+ *   1 <= K <= SRT_MAX_DEVELOP_CHANNELS.  Every R[k][j] and scale must be finite (checked on the host); the film's own NaN and infinite
+ *   sums propagate as the arithmetic says (0 * inf = NaN: a pixel with a non-finite sum is non-finite in every channel, and no other pixel is).
+ *   The 96th word of a film row (the unused one of its 384 bytes) never enters.  A filter of transmittances T_j is folded into the curves
+ *   by the caller, R'[k][j] = R[k][j] * T_j, one fp32 product per entry.
+ *   srt_develop_spectral      develops the context's spectral accumulation: out[((y * image_width) + x) * channels + k]; only the chunk's
+ *                             rectangle is written, with the placement of srt_read_spectral; pixels owned by other ranks hold a zero
+ *                             film row and come out zero in value.  Synchronises.  It only READS the accumulation: later passes, the
+ *                             film, the frame and the RNG state are what they would be without the call.  Any partition is accepted (no
+ *                             pixel reads a neighbour).  Working blocks (the transposed curves and the developed planes) belong to the
+ *                             context, are reused and grow with the chunk.  Refused with nothing changed on the device: no spectral
+ *                             accumulation with at least one pass, a null pointer, channels == 0 or > SRT_MAX_DEVELOP_CHANNELS, an empty
+ *                             image, a response or scale that is NaN or infinite (SRT_ERR_INVALID); a failed allocation (SRT_ERR_HIP).
+ *   srt_develop_spectral_srgb three channels developed by the same kernel and taken as XYZ SUMS of the accumulation's n samples.
+ *                             response3 == NULL selects the colour-matching rows x, y, z of srt_color_tables (with scale = the fp32
+ *                             470/7 the sums are the accumulation's XYZ sums up to reassociation).  out_xyz receives the developed
+ *                             sums S; out_lin and out_q the conversion the render kernel applies to an accumulation's XYZ sums and its
+ *                             sample total:  inv = 1.0f / (float)n;  c = (inv * S.x, inv * S.y, inv * S.z);  then XYZ -> linear sRGB rows,
+ *                             correct_channel, (float)(int)(v * 255.99f) (xyz_mean_to_srgb, as the denoiser's epilogue).  Layout
+ *                             out[((y * image_width) + x) * 3 + c], placement as above.  Any of the three outputs may be NULL, not all.
+ *                             Refusals as above.
+ *   srt_develop_kat           KAT entry point: the same kernel on a caller-supplied host array film[n_pixels][95]; the library uploads it
+ *                             into 96-float rows (the 96th word set to a NaN: a kernel that let it enter would show) and the pixel
+ *                             mapping is the identity; out[n_pixels][channels].  Needs neither a scene nor an accumulation and touches
+ *                             neither.  SRT_ERR_INVALID for a null argument, n_pixels == 0 or >= 2^31, channels, response or scale as above.
+ *   srt_develop_last_ms       kernel-only times of the context's last develop (any entry point) in ms, from HIP events: the contraction,
+ *                             and the sRGB epilogue (0 when the call had none).  Either pointer may be NULL.  Measurement support
+ *                             (tools/develop_cost.py).  SRT_ERR_INVALID before the first develop. */
+#define SRT_MAX_DEVELOP_CHANNELS 16
+SRT_API int srt_develop_spectral(srt_ctx *ctx, const float *response, uint32_t channels, float scale, float *out,
+                                 uint32_t image_width, uint32_t image_height);
+SRT_API int srt_develop_spectral_srgb(srt_ctx *ctx, const float *response3, float scale, float *out_xyz, float *out_lin, float *out_q,
+                                      uint32_t image_width, uint32_t image_height);
+SRT_API int srt_develop_kat(srt_ctx *ctx, const float *film, uint32_t n_pixels, const float *response, uint32_t channels, float scale,
+                            float *out);
+SRT_API int srt_develop_last_ms(srt_ctx *ctx, float *contract_ms, float *epilogue_ms);
+
 /* First-hit feature buffers (no reference counterpart): the geometric side channels a denoiser or compositor takes as input.  A FEATURED
  * accumulation is a plain progressive accumulation (the semantics of srt_accum_reset: passes of s1 .. sk samples equal one launch of
  * their sum in every output above, RNG state included) that also keeps, per pixel, 8 raw fp32 sums F[0..7]:
