@@ -118,7 +118,7 @@ struct srt_ctx {
     // The one accumulation of a context (srt_accum_reset*, srt_render_chunk_accum).
     struct Accumulation {
         enum class State { Invalid, Empty, Bound } state = State::Invalid;   // Empty: reset, no pass yet; Bound: passes of one chunk
-        enum class Kind { Plain, Adaptive, Spectral, Streams, Features, AdaptiveFeatures } kind = Kind::Plain;    // MODE 3 / 4 / 5 / 6 / 7 / 8 passes (adaptive + features is the one combination)
+        enum class Kind { Plain, Adaptive, Spectral, Streams, Features, AdaptiveFeatures, SpectralFeatures } kind = Kind::Plain;    // MODE 3 / 4 / 5 / 6 / 7 / 8 / 9 passes (adaptive + features and spectral + features are the two combinations)
         uint32_t total = 0;                             // samples per pixel in the sums (streamed: over all streams)
         uint32_t n_streams = 1;                         // streamed: the RNG streams per pixel (K); 1 otherwise
         uint32_t w = 0, h = 0, offx = 0, offy = 0;      // the chunk of the first pass
@@ -127,9 +127,9 @@ struct srt_ctx {
         bool valid() const { return state != State::Invalid; }
         bool bound() const { return state == State::Bound; }
         bool adaptive() const { return kind == Kind::Adaptive || kind == Kind::AdaptiveFeatures; }
-        bool spectral() const { return kind == Kind::Spectral; }
+        bool spectral() const { return kind == Kind::Spectral || kind == Kind::SpectralFeatures; }
         bool streamed() const { return kind == Kind::Streams; }
-        bool featured() const { return kind == Kind::Features || kind == Kind::AdaptiveFeatures; }
+        bool featured() const { return kind == Kind::Features || kind == Kind::AdaptiveFeatures || kind == Kind::SpectralFeatures; }
     } accum;
     // the buffers behind it, allocated on first use:
     DeviceBuffer d_accum;                               // progressive rendering (AccumLayout)
@@ -141,6 +141,7 @@ struct srt_ctx {
     DeviceBuffer d_features_staging;                    // row-major staging block of srt_read_features
     DeviceBuffer d_denoise;                             // the denoiser's working images (DenoiseLayout), grown when the rectangle grows
     DeviceBuffer d_denoise_in;                          // srt_denoise_kat: the caller's sums and feature rows
+    DeviceBuffer d_denoise_dev;                         // srt_denoise_developed: the payload images (DenoiseDevLayout), grown when rectangle or channels grow
     hipEvent_t denoise_ev[12] = {};                     // around the kernels of the last denoise: prepass | (estimator) | levels | epilogue (created on first use)
     uint32_t denoise_timed_levels = 0;                  // levels the events of the last denoise bracket
     uint32_t denoise_level_ev = 1;                      // the event level 0 starts at: 1, or 2 after a variance-guided denoise
@@ -494,12 +495,12 @@ int combine_streams(srt_ctx *c, const Pass &ps, const RenderParams &p) {
 }
 
 // spp_add == 0: a plain launch of c->spp samples (Plain, or Counting when instrumented); spp_add > 0: an accumulating pass of spp_add
-// samples (Accum / Adaptive / Spectral / Streams / Features / AdaptiveFeatures) whose caller has checked the accumulation and enqueued its header.
+// samples (Accum / Adaptive / Spectral / Streams / Features / AdaptiveFeatures / SpectralFeatures) whose caller has checked the accumulation and enqueued its header.
 // width .. offy are already narrowed to 16 bit.
 int render_chunk_impl(srt_ctx *c, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy, uint32_t spp_add, hipStream_t st) {
     Pass ps = {};
     ps.spp_add = spp_add; ps.st = st;
-    ps.mode = !spp_add ? (c->count_traversal ? Counting : Plain) : c->accum.adaptive() ? (c->accum.featured() ? AdaptiveFeatures : Adaptive) : c->accum.spectral() ? Spectral : c->accum.streamed() ? Streams : c->accum.featured() ? Features : Accum;
+    ps.mode = !spp_add ? (c->count_traversal ? Counting : Plain) : c->accum.adaptive() ? (c->accum.featured() ? AdaptiveFeatures : Adaptive) : c->accum.spectral() ? (c->accum.featured() ? SpectralFeatures : Spectral) : c->accum.streamed() ? Streams : c->accum.featured() ? Features : Accum;
     ps.later = spp_add && c->accum.bound(); ps.plan = plan_of(c);
     ps.streams = ps.mode == Streams ? c->accum.n_streams : 1u;
     c->last_w = width; c->last_h = height; c->last_offx = offx; c->last_offy = offy;
@@ -838,6 +839,41 @@ int srt_accum_reset_features(srt_ctx *c) {
     HIP_TRY(c, hipMemcpy(&AccumLayout(c).header->features, reinterpret_cast<const char *>(&h) + tail, sizeof(h) - tail, hipMemcpyHostToDevice));
     HIP_TRY(c, hipDeviceSynchronize());
     c->accum.begin(srt_ctx::Accumulation::Kind::Features);
+    return SRT_OK;
+}
+
+int srt_accum_reset_spectral_features(srt_ctx *c) {
+    if (!c) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_spectral_features: null ctx");
+    // refusals first: a refused call leaves the context's accumulation as it was
+    if (c->count_traversal)
+        return fail(c, SRT_ERR_UNSUPPORTED, "srt_accum_reset_spectral_features: no instrumented accumulating kernel (srt_set_count_traversal(ctx, 0) first)");
+    if (!c->params_ready) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_spectral_features: device parameters must be set first (srt_init_device_params)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    // srt_accum_reset_spectral's rule for the film and srt_accum_reset_features' rule for the rows.  Both new blocks are allocated before
+    // either old one goes: a failed allocation changes nothing, and leaves no error behind for the next launch's hipGetLastError
+    const char *who = "srt_accum_reset_spectral_features";
+    const size_t film_bytes = (size_t)c->n_lanes * kFilmStride * sizeof(float), row_bytes = (size_t)c->n_lanes * kFeatureStride * sizeof(float);
+    DeviceBuffer film, rows;
+    if (c->d_film.bytes < film_bytes)
+        if (const hipError_t e = film.reserve(film_bytes)) { (void)hipGetLastError(); return hip_fail(c, e, who); }
+    if (c->d_features.bytes < row_bytes)
+        if (const hipError_t e = rows.reserve(row_bytes)) { (void)hipGetLastError(); return hip_fail(c, e, who); }
+    if (film) c->d_film = std::move(film);
+    if (rows) c->d_features = std::move(rows);
+    int rc = srt_accum_reset(c);
+    if (rc != SRT_OK) return rc;
+    c->accum.invalidate();      // (until film and rows are in place)
+    HIP_TRY(c, hipMemset(c->d_film.ptr, 0, film_bytes));
+    HIP_TRY(c, hipMemset(c->d_features.ptr, 0, row_bytes));
+    // the film's slot of the header and the featured part behind it (the per-pass kernel rewrites only sums and spp_total)
+    float *film_ptr = c->d_film.as<float>();
+    HIP_TRY(c, hipMemcpy(&AccumLayout(c).header->film, &film_ptr, sizeof(film_ptr), hipMemcpyHostToDevice));
+    AccumHeader h = {};
+    h.features = c->d_features.as<float>(); h.mat_col = c->d_mat_col.as<const float>();
+    const size_t tail = offsetof(AccumHeader, features);
+    HIP_TRY(c, hipMemcpy(&AccumLayout(c).header->features, reinterpret_cast<const char *>(&h) + tail, sizeof(h) - tail, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipDeviceSynchronize());
+    c->accum.begin(srt_ctx::Accumulation::Kind::SpectralFeatures);
     return SRT_OK;
 }
 
@@ -1491,6 +1527,132 @@ int srt_denoise_mv_kat(srt_ctx *c, const srt_denoise_vg *cfg, const float *xyz_s
     DenoisePlan plan = denoise_vg_plan(cfg);
     plan.measured = true;
     return denoise_kat(c, "srt_denoise_mv_kat", plan, xyz_sums, features, 1u, w, h, out_xyz, out_var, samples, sum_y2);
+}
+
+// ---- the developed payload (srt_denoise_developed) ------------------------------------------------------------------------------
+namespace {
+
+// d_denoise_dev: [payload A | payload B: `groups` float4 per pixel each, [group][pixel] | out_dev: `channels` floats per pixel
+//                 | srt_denoise_developed_kat only: the caller's developed planes, `channels` floats per pixel]
+struct DenoiseDevLayout {
+    float4 *payload[2];
+    float *out, *in;
+    static size_t bytes(size_t pixels, uint32_t channels, bool kat) {
+        return pixels * (2 * (size_t)denoise_payload_groups(channels) * sizeof(float4) + (size_t)channels * (kat ? 2u : 1u) * sizeof(float));
+    }
+    DenoiseDevLayout(const DeviceBuffer &d, size_t pixels, uint32_t channels) {
+        const size_t g = denoise_payload_groups(channels);
+        payload[0] = d.as<float4>(); payload[1] = payload[0] + g * pixels;
+        out = reinterpret_cast<float *>(payload[1] + g * pixels); in = out + pixels * channels;      // (in: inside the buffer only when reserved with kat)
+    }
+};
+
+// run_denoise's plain branch with the payload riding along: the prepass and the payload's prepass (developed: [pixel][channels] on the
+// device), plan.levels payload levels ping-ponging colour and payload, the epilogue and the payload's output kernel.  The results are
+// left in DenoiseLayout::out[0] and DenoiseDevLayout::out; d_denoise and d_denoise_dev are reserved by the caller.  Events as in
+// run_denoise: [0] both prepasses [1] level 0 .. both output kernels.
+int run_denoise_developed(srt_ctx *c, const char *who, const DenoisePlan &plan, DenoisePrepassParams pre, const float *developed, uint32_t channels) {
+    const size_t pixels = (size_t)pre.w * pre.h;
+    const uint32_t groups = denoise_payload_groups(channels);
+    const DenoiseLayout L(c->d_denoise, pixels);
+    const DenoiseDevLayout D(c->d_denoise_dev, pixels, channels);
+    pre.guides = L.guides; pre.colour = L.colour[0];
+    c->denoise_timed = false;
+    for (hipEvent_t &e : c->denoise_ev) if (!e) HIP_TRY_AS(c, who, hipEventCreate(&e));
+    uint32_t n_ev = 0;
+    HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
+    HIP_TRY_AS(c, who, launch_denoise_prepass(pre, nullptr));
+    DenoisePayloadPrepassParams pp = {};
+    pp.developed = developed; pp.payload = D.payload[0]; pp.pixels = pixels; pp.channels = channels; pp.groups = groups; pp.samples = pre.samples;
+    HIP_TRY_AS(c, who, launch_denoise_payload_prepass(pp, nullptr));
+    HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
+    const uint32_t level_ev = n_ev - 1;
+    uint32_t cur = 0;
+    for (uint32_t i = 0; i < plan.levels; i++) {
+        const float sc = ldexpf(plan.sigma_color, -(int)i);      // (as in run_denoise)
+        DenoiseLevelDevParams lp = {};
+        lp.guides = L.guides; lp.src = L.colour[cur]; lp.dst = L.colour[cur ^ 1u];
+        lp.psrc = D.payload[cur]; lp.pdst = D.payload[cur ^ 1u]; lp.groups = groups;
+        lp.w = pre.w; lp.h = pre.h; lp.step = 1u << i;
+        lp.kn = plan.kn; lp.ka = plan.ka; lp.kz = plan.kz; lp.kc = sc * sc;
+        HIP_TRY_AS(c, who, launch_denoise_level_dev(lp, nullptr));
+        HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
+        cur ^= 1u;
+    }
+    HIP_TRY_AS(c, who, launch_denoise_epilogue(reinterpret_cast<const float *>(L.colour[cur]), L.out[0], L.out[1], L.out[2], pixels, nullptr));
+    HIP_TRY_AS(c, who, launch_denoise_dev_out(D.payload[cur], D.out, channels, groups, pixels, nullptr));
+    HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
+    c->denoise_timed_levels = plan.levels; c->denoise_level_ev = level_ev; c->denoise_timed = true;
+    return SRT_OK;
+}
+
+}  // namespace
+
+int srt_denoise_developed(srt_ctx *c, const srt_denoise *cfg, const float *response, uint32_t channels, float scale, float *out_dev, float *out_xyz,
+                          uint32_t image_width, uint32_t image_height) {
+    const char *who = "srt_denoise_developed";
+    if (!c || !cfg || !response) return fail(c, SRT_ERR_INVALID, "srt_denoise_developed: null argument");
+    if ((!out_dev && !out_xyz) || image_width == 0 || image_height == 0) return fail(c, SRT_ERR_INVALID, "srt_denoise_developed: no output / empty image");
+    if (const char *why = denoise_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_denoise_developed: ") + why);
+    if (const char *why = develop_args_error(response, channels, scale)) return fail(c, SRT_ERR_INVALID, std::string("srt_denoise_developed: ") + why);
+    if (!c->accum.spectral() || !c->accum.featured() || !c->accum.bound())
+        return fail(c, SRT_ERR_INVALID, "srt_denoise_developed: no spectral featured accumulation with a pass (srt_accum_reset_spectral_features and srt_render_chunk_accum first)");
+    if (c->rank != 0 || c->world != 1)
+        return fail(c, SRT_ERR_UNSUPPORTED, "srt_denoise_developed: needs the whole chunk on this context (partition (0, 1)): pixels of other ranks read +0");
+    HIP_TRY(c, hipSetDevice(c->device));
+    // develop and filter run on the chunk's rectangle (clipped to the reference grid); the image clips only what is copied out
+    const uint32_t w = clipped_w(c), h = clipped_h(c);
+    const size_t pixels = (size_t)w * h;
+    if (pixels) {
+        if (const int rc = develop_reserve(c, who, c->d_develop, DevelopLayout::bytes(pixels, channels, false))) return rc;
+        if (const int rc = develop_reserve(c, who, c->d_denoise, DenoiseLayout::bytes(pixels, false))) return rc;
+        if (const int rc = develop_reserve(c, who, c->d_denoise_dev, DenoiseDevLayout::bytes(pixels, channels, false))) return rc;
+        if (const int rc = run_develop(c, who, c->d_film.as<float>(), c->n_lanes, c->tx, c->ty, c->bx, w, h, response, channels, scale, 0u)) return rc;
+        DenoisePrepassParams pre = {};
+        pre.sums = AccumLayout(c).sums; pre.sum_pixel_stride = 1; pre.sum_comp_stride = c->n_lanes;
+        pre.rows = c->d_features.as<const float4>();
+        pre.tx = c->tx; pre.ty = c->ty; pre.bx = c->bx; pre.w = w; pre.h = h; pre.samples = c->accum.total;
+        if (const int rc = run_denoise_developed(c, who, denoise_plan(cfg), pre, DevelopLayout(c->d_develop, pixels, channels).out, channels)) return rc;
+        const ChunkRect rect = chunk_rect(c, image_width, image_height);
+        const float *src[2] = {DenoiseDevLayout(c->d_denoise_dev, pixels, channels).out, DenoiseLayout(c->d_denoise, pixels).out[0]};
+        float *const host[2] = {out_dev, out_xyz};
+        for (int k = 0; k < 2; k++) {
+            const size_t ch = k == 0 ? channels : 3;      // floats per pixel
+            const size_t row = (size_t)rect.w * ch * sizeof(float), src_pitch = (size_t)w * ch * sizeof(float), pitch = (size_t)image_width * ch * sizeof(float);
+            if (host[k] && rect.w && rect.h) HIP_TRY(c, hipMemcpy2D(host[k] + rect.first * ch, pitch, src[k], src_pitch, row, rect.h, hipMemcpyDeviceToHost));
+        }
+    }
+    HIP_TRY(c, hipDeviceSynchronize());
+    return SRT_OK;
+}
+
+int srt_denoise_developed_kat(srt_ctx *c, const srt_denoise *cfg, const float *xyz_sums, const float *features, const float *developed, uint32_t channels,
+                              uint32_t samples, uint32_t w, uint32_t h, float *out_dev, float *out_xyz) {
+    const char *who = "srt_denoise_developed_kat";
+    if (!c || !cfg || !xyz_sums || !features || !developed || (!out_dev && !out_xyz)) return fail(c, SRT_ERR_INVALID, "srt_denoise_developed_kat: null argument");
+    if (const char *why = denoise_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_denoise_developed_kat: ") + why);
+    if (channels == 0 || channels > kMaxDevelopChannels) return fail(c, SRT_ERR_INVALID, "srt_denoise_developed_kat: channels must be in 1 .. SRT_MAX_DEVELOP_CHANNELS (16)");
+    if (samples == 0 || w == 0 || h == 0 || (uint64_t)w * h > 0x7fffffffull) return fail(c, SRT_ERR_INVALID, "srt_denoise_developed_kat: samples, w and h must be positive, w x h below 2^31");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t pixels = (size_t)w * h;
+    if (const int rc = develop_reserve(c, who, c->d_denoise, DenoiseLayout::bytes(pixels, false))) return rc;
+    if (const int rc = develop_reserve(c, who, c->d_denoise_dev, DenoiseDevLayout::bytes(pixels, channels, true))) return rc;
+    if (const int rc = develop_reserve(c, who, c->d_denoise_in, pixels * (kFeatureStride + 3) * sizeof(float))) return rc;
+    const DenoiseDevLayout D(c->d_denoise_dev, pixels, channels);
+    float *d_rows = c->d_denoise_in.as<float>(), *d_sums = d_rows + pixels * kFeatureStride;
+    HIP_TRY_AS(c, who, hipMemcpy(d_rows, features, pixels * kFeatureStride * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY_AS(c, who, hipMemcpy(d_sums, xyz_sums, pixels * 3 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY_AS(c, who, hipMemcpy(D.in, developed, pixels * channels * sizeof(float), hipMemcpyHostToDevice));
+    // a grid of one w x h block makes the prepass's block-linear lane the row-major pixel
+    DenoisePrepassParams pre = {};
+    pre.sums = d_sums; pre.sum_pixel_stride = 3; pre.sum_comp_stride = 1;
+    pre.rows = reinterpret_cast<const float4 *>(d_rows);
+    pre.tx = w; pre.ty = h; pre.bx = 1; pre.w = w; pre.h = h; pre.samples = samples;
+    if (const int rc = run_denoise_developed(c, who, denoise_plan(cfg), pre, D.in, channels)) return rc;
+    if (out_dev) HIP_TRY_AS(c, who, hipMemcpy(out_dev, D.out, pixels * channels * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_xyz) HIP_TRY_AS(c, who, hipMemcpy(out_xyz, DenoiseLayout(c->d_denoise, pixels).out[0], pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY_AS(c, who, hipDeviceSynchronize());
+    return SRT_OK;
 }
 
 int srt_denoise_last_ms(srt_ctx *c, float *prepass_ms, float *level_ms, float *epilogue_ms, uint32_t *levels) {

@@ -31,6 +31,17 @@
 //                            features) -- the prepass with the pixel's own count, and the per-pixel estimator of srt_denoise_features_mv
 //                            (the variance of the mean from the pixel's measured S1 and S2); one thread per pixel, no neighbours
 //   denoise_var_out_kernel   the variance after the last level -> channel 1 of the [h][w][2] variance output
+// The developed payload (srt_denoise_developed) adds three kernels behind all of the above and leaves them as they are:
+//   denoise_payload_prepass_kernel  the developed planes [h][w][K] -> d = inv * D as G = KC / 4 float4 groups, [group][pixel], KC the
+//                            smallest of {4, 8, 16} that holds K, the padding +0: the lanes of a row read contiguous 16-byte runs
+//   denoise_level_dev_kernel the plain level with the payload riding along.  The 25 weights of a pixel are computed ONCE, through
+//                            denoise_tap's arithmetic (which also filters the colour), and kept in 25 registers -- the tap loops are
+//                            fully unrolled -- then the groups are streamed one after the other: per group the same 25 taps, each read
+//                            only where its weight is > 0.  TILED (steps 1 and 2): guides and colour are staged as in
+//                            denoise_level_kernel<true> (30 720 B) and each group's tile and halo goes through a fourth 10 240-B array
+//                            between two barriers -- 40 960 B static, so four workgroups a CU whatever G is, where staging all groups
+//                            at once would need 71 680 B at G = 4.  From step 4 on the taps come from L2 / HBM.
+//   denoise_dev_out_kernel   the payload after the last level -> the row-major [h][w][K] output
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -381,6 +392,166 @@ __global__ __launch_bounds__(256) void denoise_epilogue_kernel(const float4 *col
     out_q[3 * pix + 0] = o.q.x; out_q[3 * pix + 1] = o.q.y; out_q[3 * pix + 2] = o.q.z;
 }
 
+// ---- the developed payload (srt_denoise_developed) -----------------------------------------------------------------------------------
+// one tap q of pixel p with the weight handed back: denoise_tap's operations in denoise_tap's order (the colour sums are its bits), and
+// the tap's weight where it counts, +0 where it does not -- the payload of such a tap is never multiplied
+__device__ __forceinline__ float denoise_tap_weight(TapSums &s, float h2, float4 p_g0, float4 p_g1, float4 p_c, float4 q_g0, float4 q_g1, float4 q_c,
+                                                    float kn, float ka, float kz, float kc) {
+    const float dn = dist2(p_g0, q_g0);
+    const float da = dist2(p_g1, q_g1);
+    const float dc = dist2(p_c, q_c);
+    const float zp = p_g0.w, zq = q_g0.w;
+    const float m = (zp > zq) ? zp : zq;
+    const float r = (m > 0.0f) ? (zp - zq) / m : 0.0f;
+    const float dz = r * r;
+    float wt = h2;
+    wt = wt * edge_term(dn, kn);
+    wt = wt * edge_term(da, ka);
+    wt = wt * edge_term(dz, kz);
+    wt = wt * edge_term(dc, kc);
+    if (wt > 0.0f) {
+        s.sw += wt;
+        s.sx += wt * q_c.x; s.sy += wt * q_c.y; s.sz += wt * q_c.z;
+        return wt;
+    }
+    return 0.0f;
+}
+
+__global__ __launch_bounds__(256) void denoise_payload_prepass_kernel(const DenoisePayloadPrepassParams P) {
+    const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= P.pixels) return;
+    const float inv = 1.0f / (float)P.samples;
+    const float *d = P.developed + pix * P.channels;
+    for (uint32_t g = 0; g < P.groups; g++) {
+        float v[4];
+#pragma unroll
+        for (uint32_t e = 0; e < 4u; e++) {
+            const uint32_t k = 4u * g + e;
+            v[e] = (k < P.channels) ? inv * d[k] : 0.0f;
+        }
+        P.payload[(size_t)g * P.pixels + pix] = make_float4(v[0], v[1], v[2], v[3]);
+    }
+}
+
+template <bool TILED>
+__global__ __launch_bounds__(256) void denoise_level_dev_kernel(const DenoiseLevelDevParams P) {
+    const uint32_t tile_y = blockIdx.x / P.tiles_x, tile_x = blockIdx.x - tile_y * P.tiles_x;
+    const uint32_t lx = threadIdx.x & (kDnTileW - 1u), ly = threadIdx.x / kDnTileW;
+    const uint32_t x0 = tile_x * kDnTileW, y0 = tile_y * kDnTileH;
+    const uint32_t x = x0 + lx, y = y0 + ly;
+    const int step = (int)P.step;
+    const size_t pixels = (size_t)P.w * P.h;
+
+    __shared__ float4 t_g0[TILED ? kDnLdsPixels : 1], t_g1[TILED ? kDnLdsPixels : 1], t_c[TILED ? kDnLdsPixels : 1], t_d[TILED ? kDnLdsPixels : 1];
+    const uint32_t halo = 2u * P.step, lw = kDnTileW + 2u * halo, lh = kDnTileH + 2u * halo;      // (TILED: step <= 2, lw * lh <= kDnLdsPixels)
+    if constexpr (TILED) {
+        for (uint32_t i = threadIdx.x; i < lw * lh; i += 256u) {
+            const uint32_t ty = i / lw, tx = i - ty * lw;
+            const long long gx = (long long)x0 + tx - halo, gy = (long long)y0 + ty - halo;
+            float4 g0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), g1 = g0, c = g0;      // outside the rectangle: never read as a tap
+            if (gx >= 0 && gx < (long long)P.w && gy >= 0 && gy < (long long)P.h) {
+                const size_t q = (size_t)gy * P.w + (size_t)gx;
+                g0 = P.guides[2 * q + 0]; g1 = P.guides[2 * q + 1]; c = P.src[q];
+            }
+            t_g0[i] = g0; t_g1[i] = g1; t_c[i] = c;
+        }
+        __syncthreads();
+    }
+    // (no early return: the lanes outside the rectangle stay for the barriers of the group loop, with 25 zero weights)
+    const bool mine = x < P.w && y < P.h;
+    const size_t p = mine ? (size_t)y * P.w + x : 0;
+    const uint32_t ip = (ly + halo) * lw + lx + halo;      // (TILED only)
+
+    float wts[25];
+    TapSums s = {0.0f, 0.0f, 0.0f, 0.0f};
+    float4 p_c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (mine) {
+        float4 p_g0, p_g1;
+        if constexpr (TILED) {
+            p_g0 = t_g0[ip]; p_g1 = t_g1[ip]; p_c = t_c[ip];
+        } else {
+            p_g0 = P.guides[2 * p + 0]; p_g1 = P.guides[2 * p + 1]; p_c = P.src[p];
+        }
+#pragma unroll
+        for (int dy = -2; dy <= 2; dy++) {
+            const long long qy = (long long)y + dy * step;
+#pragma unroll
+            for (int dx = -2; dx <= 2; dx++) {
+                const long long qx = (long long)x + dx * step;
+                float wt = 0.0f;
+                if (qy >= 0 && qy < (long long)P.h && qx >= 0 && qx < (long long)P.w) {
+                    float4 q_g0, q_g1, q_c;
+                    if constexpr (TILED) {
+                        const uint32_t i = (uint32_t)((int)ip + (dy * step) * (int)lw + dx * step);
+                        q_g0 = t_g0[i]; q_g1 = t_g1[i]; q_c = t_c[i];
+                    } else {
+                        const size_t q = (size_t)qy * P.w + (size_t)qx;
+                        q_g0 = P.guides[2 * q + 0]; q_g1 = P.guides[2 * q + 1]; q_c = P.src[q];
+                    }
+                    wt = denoise_tap_weight(s, b3_tap(dy + 2) * b3_tap(dx + 2), p_g0, p_g1, p_c, q_g0, q_g1, q_c, P.kn, P.ka, P.kz, P.kc);
+                }
+                wts[(dy + 2) * 5 + (dx + 2)] = wt;
+            }
+        }
+        float4 o = p_c;
+        if (s.sw > 0.0f) o = make_float4(s.sx / s.sw, s.sy / s.sw, s.sz / s.sw, 0.0f);
+        P.dst[p] = o;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 25; i++) wts[i] = 0.0f;
+    }
+
+    // the payload: group after group through the same 25 weights; a tap whose weight is not > 0 is not read (it may lie outside the rectangle)
+    for (uint32_t g = 0; g < P.groups; g++) {
+        const float4 *psrc = P.psrc + (size_t)g * pixels;
+        if constexpr (TILED) {
+            if (g) __syncthreads();      // (the previous group's taps have been read)
+            for (uint32_t i = threadIdx.x; i < lw * lh; i += 256u) {
+                const uint32_t ty = i / lw, tx = i - ty * lw;
+                const long long gx = (long long)x0 + tx - halo, gy = (long long)y0 + ty - halo;
+                float4 d = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (gx >= 0 && gx < (long long)P.w && gy >= 0 && gy < (long long)P.h) d = psrc[(size_t)gy * P.w + (size_t)gx];
+                t_d[i] = d;
+            }
+            __syncthreads();
+        }
+        if (!mine) continue;
+        float4 sd = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#pragma unroll
+        for (int dy = -2; dy <= 2; dy++) {
+#pragma unroll
+            for (int dx = -2; dx <= 2; dx++) {
+                const float wt = wts[(dy + 2) * 5 + (dx + 2)];
+                if (wt > 0.0f) {
+                    float4 d;
+                    if constexpr (TILED) d = t_d[(uint32_t)((int)ip + (dy * step) * (int)lw + dx * step)];
+                    else d = psrc[(size_t)((long long)y + dy * step) * P.w + (size_t)((long long)x + dx * step)];
+                    sd.x += wt * d.x; sd.y += wt * d.y; sd.z += wt * d.z; sd.w += wt * d.w;
+                }
+            }
+        }
+        float4 o;
+        if (s.sw > 0.0f) o = make_float4(sd.x / s.sw, sd.y / s.sw, sd.z / s.sw, sd.w / s.sw);
+        else if constexpr (TILED) o = t_d[ip];
+        else o = psrc[p];
+        P.pdst[(size_t)g * pixels + p] = o;
+    }
+}
+
+__global__ __launch_bounds__(256) void denoise_dev_out_kernel(const float4 *payload, float *out_dev, uint32_t channels, uint32_t groups, size_t n) {
+    const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= n) return;
+    float *o = out_dev + pix * channels;
+    for (uint32_t g = 0; g < groups; g++) {
+        const float4 d = payload[(size_t)g * n + pix];
+        const uint32_t k = 4u * g;
+        if (k + 0u < channels) o[k + 0u] = d.x;
+        if (k + 1u < channels) o[k + 1u] = d.y;
+        if (k + 2u < channels) o[k + 2u] = d.z;
+        if (k + 3u < channels) o[k + 3u] = d.w;
+    }
+}
+
 }  // namespace
 
 hipError_t launch_denoise_prepass(const DenoisePrepassParams &p, hipStream_t st) {
@@ -440,6 +611,36 @@ hipError_t launch_denoise_level_vg(const DenoiseLevelVgParams &p_in, hipStream_t
 hipError_t launch_denoise_var_out(const float *colour, float *out_var, size_t n, hipStream_t st) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(denoise_var_out_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const float4 *>(colour), out_var, n);
+    return hipGetLastError();
+}
+
+uint32_t denoise_payload_groups(uint32_t channels) {
+    for (const uint32_t kc : {4u, 8u, 16u})
+        if (channels <= kc) return kc / 4u;
+    return 0;
+}
+
+hipError_t launch_denoise_payload_prepass(const DenoisePayloadPrepassParams &p, hipStream_t st) {
+    if (p.channels == 0 || p.channels > kMaxDevelopChannels || p.groups != denoise_payload_groups(p.channels) || p.samples == 0) return hipErrorInvalidValue;
+    if (p.pixels == 0) return hipSuccess;
+    hipLaunchKernelGGL(denoise_payload_prepass_kernel, dim3((uint32_t)((p.pixels + 255) / 256)), dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_denoise_level_dev(const DenoiseLevelDevParams &p_in, hipStream_t st) {
+    DenoiseLevelDevParams p = p_in;
+    if (p.w == 0 || p.h == 0) return hipSuccess;
+    p.tiles_x = (p.w + kDnTileW - 1u) / kDnTileW;
+    const uint64_t blocks = (uint64_t)p.tiles_x * ((p.h + kDnTileH - 1u) / kDnTileH);
+    if (blocks > 0x7fffffffull || p.step == 0 || p.step > 128u || p.groups == 0 || p.groups > kMaxDevelopChannels / 4u) return hipErrorInvalidValue;
+    if (p.step <= kDnTiledMaxStep) hipLaunchKernelGGL(denoise_level_dev_kernel<true>, dim3((uint32_t)blocks), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(denoise_level_dev_kernel<false>, dim3((uint32_t)blocks), dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_denoise_dev_out(const float4 *payload, float *out_dev, uint32_t channels, uint32_t groups, size_t n, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(denoise_dev_out_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, payload, out_dev, channels, groups, n);
     return hipGetLastError();
 }
 

@@ -122,6 +122,7 @@ struct AccumHeader {
 // mat_col, the scene's per-material colour table (one float4 per material: srt_material.col, 0), uploaded with the scene.
 // srt_accum_reset_features writes the two fields once.
 // Adaptive featured accumulations (MODE 8, srt_accum_reset_adaptive_features) read the adaptive fields and the featured fields together.
+// Spectral featured accumulations (MODE 9, srt_accum_reset_spectral_features) read `film` and the featured fields together.
 constexpr uint32_t kFeatureStride = 8;      // 32 B per pixel: two 16-byte accesses
 constexpr uint32_t kStreamSumPlane = 6;
 constexpr uint32_t kMaxStreams = 16;      // SRT_MAX_STREAMS (srt_c_api.h)
@@ -151,8 +152,8 @@ hipError_t launch_init_rng(uint32_t *rng, uint32_t n_lanes, uint64_t seed, hipSt
 struct PlanKnobs { bool wide_refs = false; int lds_cache_max = -1; };
 // The render launch's variant; the values are render_kernel's MODE template argument.  Plain: render; Counting: instrumented; Probe: cost
 // probe; Accum: accumulating render (p.wave_debug -> AccumHeader); Adaptive / Spectral / Streams / Features: adaptive / spectral / streamed /
-// featured accumulating render; AdaptiveFeatures: adaptive and featured at once.
-enum RenderMode { Plain = 0, Counting = 1, Probe = 2, Accum = 3, Adaptive = 4, Spectral = 5, Streams = 6, Features = 7, AdaptiveFeatures = 8 };
+// featured accumulating render; AdaptiveFeatures: adaptive and featured at once; SpectralFeatures: spectral and featured at once.
+enum RenderMode { Plain = 0, Counting = 1, Probe = 2, Accum = 3, Adaptive = 4, Spectral = 5, Streams = 6, Features = 7, AdaptiveFeatures = 8, SpectralFeatures = 9 };
 hipError_t launch_render(const RenderParams &p, const PlanKnobs &knobs, uint32_t n_cu, RenderMode mode, hipStream_t st);
 hipError_t launch_accum_header(AccumHeader *dst, float *sums, uint32_t spp_total, hipStream_t st);      // writes *dst on the stream
 // Pixel queue of the next adaptive pass (see adapt_flag_kernel): the rows of `src_rows` (src_info[0] of them; nullptr: the identity
@@ -246,6 +247,32 @@ struct DenoiseLevelVgParams {
 hipError_t launch_denoise_level_vg(const DenoiseLevelVgParams &p, hipStream_t st);
 // out_var[2 p + 1] = colour[p].w, n pixels.
 hipError_t launch_denoise_var_out(const float *colour, float *out_var, size_t n, hipStream_t st);
+// The developed payload (srt_denoise_developed; stated in srt_c_api.h).  The payload images are G = denoise_payload_groups(K) float4 per
+// pixel, [group][pixel] over the row-major w x h pixels, channel k in lane k % 4 of group k / 4, the padding +0.
+uint32_t denoise_payload_groups(uint32_t channels);      // KC / 4 with KC the smallest of 4, 8, 16 that holds the channels (0: too many)
+// payload[g * pixels + pix] lane e = inv * developed[pix * channels + 4 g + e], inv = 1.0f / (float)samples
+struct DenoisePayloadPrepassParams {
+    const float *developed;      // [pixel][channels], row-major pixels
+    float4 *payload;
+    size_t pixels;
+    uint32_t channels, groups, samples;
+};
+hipError_t launch_denoise_payload_prepass(const DenoisePayloadPrepassParams &p, hipStream_t st);
+// One plain level (DenoiseLevelParams' fields mean what they mean there) that also filters the payload psrc -> pdst (never the same
+// buffer) with the colour's weights.
+struct DenoiseLevelDevParams {
+    const float4 *guides, *src;
+    float4 *dst;
+    const float4 *psrc;
+    float4 *pdst;
+    uint32_t w, h, step;
+    uint32_t tiles_x;      // filled in by the launcher
+    uint32_t groups;
+    float kn, ka, kz, kc;
+};
+hipError_t launch_denoise_level_dev(const DenoiseLevelDevParams &p, hipStream_t st);
+// out_dev[pix * channels + k] = channel k of the payload, n pixels.
+hipError_t launch_denoise_dev_out(const float4 *payload, float *out_dev, uint32_t channels, uint32_t groups, size_t n, hipStream_t st);
 // The developed film (srt_develop.hip; the contraction is stated in srt_c_api.h at srt_develop_spectral).  Lane idx of the grid
 // [0, n_lanes) holds the film row film[idx * kFilmStride ..]; the lane of pixel (x, y) = the inverse of block_linear_idx(x, y, tx, ty, bx)
 // writes out[((y * w) + x) * channels + k] = (sum over j ascending of F_j * R[k][j]) * scale when x < w and y < h (a caller's

@@ -34,6 +34,8 @@ struct LdsUniforms {
     // Featured launches borrow slots instead of growing the block (a larger block would move the LDS map of every kernel): MODE 7 keeps
     // its feature rows in accum_film and its colour table in accum_sum2.  MODE 8 (adaptive + features) needs accum_sum2 for S2 itself:
     // its rows stay in accum_film and its colour table goes to tile_cost, which only the cost probe (MODE 2) ever reads back.
+    // MODE 9 (spectral + features) keeps the film in accum_film as MODE 5 does: its rows go to accum_sum2 (free: it is not adaptive)
+    // and its colour table to tile_cost, as MODE 8's.
 };
 static_assert(sizeof(LdsUniforms) <= kLdsUniF4 * 16, "uniform block too large");
 typedef __attribute__((address_space(3))) LdsUniforms lds_uniforms;

@@ -188,7 +188,8 @@ class Renderer:
     def accum_reset_features(self):
         """start a FEATURED accumulation (srt_c_api.h): like accum_reset, and each later pass also adds, at the first hit of every
         sample's camera ray, the face-forwarded normal, the hit material's colour, the distance and 1 to the pixel's eight raw float32
-        sums (read_features; feature_means normalises them).  Never spectral or streamed; accum_reset_adaptive_features is the adaptive one."""
+        sums (read_features; feature_means normalises them).  Never streamed; accum_reset_adaptive_features is the adaptive one,
+        accum_reset_spectral_features the one with a film."""
         self._ck(B.lib().srt_accum_reset_features(self._h))
 
     def accum_reset_adaptive_features(self, rel_tol, abs_tol=0.0, min_spp=16):
@@ -197,6 +198,12 @@ class Renderer:
         feature row of a plain featured n-spp frame.  accum_active, accum_stats and read_features all work on it, and denoise,
         denoise_vg and denoise_mv take it (each pixel normalised by its own count)."""
         self._ck(B.lib().srt_accum_reset_adaptive_features(self._h, C.byref(adaptive_config(rel_tol, abs_tol, min_spp))))
+
+    def accum_reset_spectral_features(self):
+        """start a SPECTRAL FEATURED accumulation (srt_c_api.h): accum_reset_spectral with the feature rows of accum_reset_features.
+        Image, sums, RNG state and film are accum_reset_spectral's bit for bit, the rows accum_reset_features'.  read_spectral,
+        develop_spectral, read_features, denoise and denoise_vg all work on it, and denoise_developed needs it.  Never adaptive."""
+        self._ck(B.lib().srt_accum_reset_spectral_features(self._h))
 
     def read_features(self, image_width, image_height):
         """raw first-hit sums of the featured accumulation's chunk, float32: dict(normal (H, W, 3), albedo (H, W, 3), distance (H, W),
@@ -226,6 +233,40 @@ class Renderer:
         out = np.zeros(sums.shape, np.float32)
         self._ck(B.lib().srt_denoise_kat(self._h, C.byref(c), B.fptr(sums), B.fptr(rows), int(samples), sums.shape[1], sums.shape[0], B.fptr(out)))
         return out
+
+    def denoise_developed(self, image_width, image_height, response, scale=1.0, filter=None, **cfg):
+        """the film of the context's SPECTRAL FEATURED accumulation developed and denoised on the device (srt_denoise_developed; response,
+        scale and filter as develop_spectral, cfg: the keywords of denoise_config): dict(dev (image_height, image_width, K), xyz
+        (image_height, image_width, 3)) float32 -- the K developed planes as per-sample means, filtered with the weights the plain
+        filter forms from the XYZ colour and the guides, and the filtered XYZ mean, which is denoise()'s xyz bit for bit.  Written in the
+        chunk's rectangle only, zeros elsewhere.  Reads the accumulation, changes nothing of it."""
+        resp = sensor_response(response, filter)
+        s = _develop_scale(scale)
+        c = denoise_config(**cfg)
+        dev = np.zeros((image_height, image_width, resp.shape[0]), np.float32)
+        xyz = np.zeros((image_height, image_width, 3), np.float32)
+        self._ck(B.lib().srt_denoise_developed(self._h, C.byref(c), B.fptr(resp), resp.shape[0], s, B.fptr(dev), B.fptr(xyz), image_width, image_height))
+        return dict(dev=dev, xyz=xyz)
+
+    def denoise_developed_kat(self, xyz_sums, features, developed, samples, **cfg):
+        """the payload denoiser's device path on explicit inputs (srt_denoise_developed_kat): xyz_sums (h, w, 3), features (h, w, 8) and
+        developed (h, w, K), 1 <= K <= 16, raw float32 sums of `samples` samples -> (the filtered developed mean (h, w, K), the filtered
+        XYZ mean (h, w, 3)).  Needs no scene and no accumulation.  The shapes are checked here (ValueError)."""
+        c = denoise_config(**cfg)
+        sums = np.ascontiguousarray(xyz_sums, np.float32)
+        rows = np.ascontiguousarray(features, np.float32)
+        planes = np.ascontiguousarray(developed, np.float32)
+        if sums.ndim != 3 or sums.shape[2] != 3 or rows.shape != sums.shape[:2] + (FEATURE_CHANNELS,):
+            raise ValueError("denoise_developed_kat: needs xyz_sums (h, w, 3) and features (h, w, %d), got %r and %r" % (FEATURE_CHANNELS, sums.shape, rows.shape))
+        if planes.ndim != 3 or planes.shape[:2] != sums.shape[:2] or not 1 <= planes.shape[2] <= MAX_DEVELOP_CHANNELS:
+            raise ValueError("denoise_developed_kat: needs developed (h, w, K) with 1 <= K <= %d over the same pixels, got %r" % (MAX_DEVELOP_CHANNELS, planes.shape))
+        if isinstance(samples, bool) or not isinstance(samples, (int, np.integer)) or not 1 <= samples <= 0xffffffff:
+            raise ValueError("denoise_developed_kat: samples must be a whole number >= 1, got %r" % (samples,))
+        dev = np.zeros(planes.shape, np.float32)
+        xyz = np.zeros(sums.shape, np.float32)
+        self._ck(B.lib().srt_denoise_developed_kat(self._h, C.byref(c), B.fptr(sums), B.fptr(rows), B.fptr(planes), planes.shape[2], int(samples),
+                                                   sums.shape[1], sums.shape[0], B.fptr(dev), B.fptr(xyz)))
+        return dev, xyz
 
     def denoise_last_ms(self):
         """kernel-only ms of the last denoise on this context (srt_denoise_last_ms): dict(prepass, levels=[ms per level], epilogue)"""
@@ -556,6 +597,11 @@ class Comm:
         """Renderer.accum_reset_adaptive_features on every local rank (not on a process-per-GPU communicator: SrtError); the rows stay
         with their ranks, as for accum_reset_features"""
         self._ck(B.lib().srt_comm_accum_reset_adaptive_features(self._h, C.byref(adaptive_config(rel_tol, abs_tol, min_spp))))
+
+    def accum_reset_spectral_features(self):
+        """Renderer.accum_reset_spectral_features on every local rank; film and rows stay with their ranks, as for accum_reset_spectral
+        and accum_reset_features"""
+        self._ck(B.lib().srt_comm_accum_reset_spectral_features(self._h))
 
     def accum_reset_streams(self, k):
         """Renderer.accum_reset_streams on every local rank (any communicator: no decision crosses ranks)"""
@@ -1064,6 +1110,31 @@ def _denoised_passes(scene, cam, width, height, sched, bounce_limit, seed, devic
             r.scatter_tiles()
             den = r.denoise_vg(width, height, **cfg) if variance_guided else r.denoise(width, height, **cfg)
             yield r.accum_samples, _collect(r, width, height), r.read_features(width, height), den
+
+
+def render_developed_denoised(scene, cam, width, height, passes, bounce_limit, response=None, filter=None, scale=None, seed=1984, device=0, renderer=None, **cfg):
+    """render_developed and render_denoised in one spectral featured accumulation: a generator of (spp_total, result, developed,
+    denoised) after every pass -- `developed` the (H, W, K) planes of Renderer.develop_spectral (sums over the samples held so far),
+    `denoised` the dict(dev, xyz) of Renderer.denoise_developed for the same curves (means, filtered; cfg: the keywords of
+    denoise_config).  response=None: the colour-matching rows at scale=None, the float32 470/7, so that `developed` holds XYZ sums;
+    else scale=None is 1.  Neither call changes the accumulation, so result is render_spectral's bit for bit.  Schedule, curves,
+    filter, scale and cfg are checked here, before any device is touched."""
+    sched = progressive_schedule(passes)
+    resp = sensor_response(cie_response() if response is None else response, filter)
+    s = (CIE_SCALE if response is None else 1.0) if scale is None else _develop_scale(scale)
+    denoise_config(**cfg)
+    return _developed_denoised_passes(scene, cam, width, height, sched, bounce_limit, seed, device, renderer, resp, s, cfg)
+
+
+def _developed_denoised_passes(scene, cam, width, height, sched, bounce_limit, seed, device, renderer, resp, scale, cfg):
+    with _image_session(scene, cam, width, height, sum(sched), bounce_limit, seed, device, renderer) as r:
+        r.accum_reset_spectral_features()
+        for spp_add in sched:
+            r.render_chunk_accum(width, height, spp_add)
+            r.scatter_tiles()
+            out = _collect(r, width, height)
+            dev = r.develop_spectral(width, height, resp, scale)
+            yield r.accum_samples, out, dev, r.denoise_developed(width, height, resp, scale, **cfg)
 
 
 ADAPTIVE_DENOISE_VARIANCE = ("measured", "spatial", None)

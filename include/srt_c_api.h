@@ -301,7 +301,8 @@ SRT_API int srt_read_accum_stats(srt_ctx *ctx, uint32_t *samples, float *sum_y, 
  *                             = 384 B per lane of the grid).  Later srt_render_chunk_accum passes run MODE 5.  An instrumented context:
  *                             SRT_ERR_UNSUPPORTED; device parameters not set: SRT_ERR_INVALID; a failed allocation: SRT_ERR_HIP -- in
  *                             every refusal the previous accumulation is unchanged.  Always a PLAIN (non-adaptive) accumulation:
- *                             adaptive + spectral is not supported.  srt_accum_reset and srt_accum_reset_adaptive make the next
+ *                             adaptive + spectral is not supported.  (Spectral + features is an accumulation kind of its own:
+ *                             srt_accum_reset_spectral_features, below.)  srt_accum_reset and srt_accum_reset_adaptive make the next
  *                             accumulation non-spectral again.  Invalidation, the 65535-sample limit and the chunk binding are those of
  *                             srt_accum_reset; srt_get_stats after a spectral pass reports that pass.
  *   srt_read_spectral         the raw sums of grid samples [first, first + count) of the accumulation's chunk, row-major:
@@ -378,7 +379,8 @@ SRT_API int srt_develop_last_ms(srt_ctx *ctx, float *contract_ms, float *epilogu
  *                             grid).  Later srt_render_chunk_accum passes run MODE 7.  Refused with the previous accumulation unchanged:
  *                             device parameters not set (SRT_ERR_INVALID); an instrumented context (SRT_ERR_UNSUPPORTED); a failed
  *                             allocation (SRT_ERR_HIP).  Always a PLAIN accumulation: features combined with the spectral film or
- *                             streams are NOT supported.  (This paragraph used to end "adaptive + features is the intended next step":
+ *                             streams are NOT supported.  (Features with the spectral film have since become an accumulation kind of
+ *                             their own: srt_accum_reset_spectral_features, below.)  (This paragraph used to end "adaptive + features is the intended next step":
  *                             that step is srt_accum_reset_adaptive_features, below, and both denoisers take either kind.)
  *                             srt_accum_reset, srt_accum_reset_adaptive, srt_accum_reset_spectral and
  *                             srt_accum_reset_streams make the next accumulation non-featured again.  Invalidation, the 65535-sample
@@ -412,6 +414,27 @@ SRT_API int srt_read_features(srt_ctx *ctx, float *out, uint32_t image_width, ui
  *                             something else again.  (srt_read_features still refuses a plain adaptive accumulation, srt_accum_active a
  *                             plain featured one.) */
 SRT_API int srt_accum_reset_adaptive_features(srt_ctx *ctx, const srt_adaptive *cfg);
+
+/* The spectral film and first-hit features in ONE accumulation (no reference counterpart): the previews that most need a denoiser -- a
+ * few samples through a narrow band or another sensor -- are developed from a film, and the denoiser needs the feature rows.  A SPECTRAL
+ * FEATURED accumulation is a spectral accumulation (srt_accum_reset_spectral: the same film, the same deposit rule) that also keeps the
+ * feature rows of srt_accum_reset_features (the same deposit rule).  Later srt_render_chunk_accum passes run render_kernel MODE 9: MODE 5
+ * and MODE 7 at once.  MODE 7's deposit draws nothing from the RNG and MODE 5's deposit touches nothing MODE 7 reads, so no new code runs
+ * in the kernel body.  What holds, and is tested, under the same pass schedule and seed:
+ *   - the image, all nine planes, the XYZ sums, the RNG state and the 95 film sums are bit-identical to a spectral accumulation's (MODE 5);
+ *   - the eight feature sums are bit-identical to a featured accumulation's (MODE 7);
+ *   - the result is independent of partition, world size, launch shape and split into passes, as for either parent.
+ *   srt_accum_reset_spectral_features  srt_accum_reset + a zeroed film, allocated by srt_accum_reset_spectral's rule, + zeroed feature
+ *                             rows, allocated by srt_accum_reset_features' rule.  Refused with the previous accumulation unchanged: an
+ *                             instrumented context (SRT_ERR_UNSUPPORTED); device parameters not set (SRT_ERR_INVALID); a failed
+ *                             allocation (SRT_ERR_HIP; both blocks are allocated before either old one goes).  Invalidation, the
+ *                             65535-sample limit and the chunk binding are those of srt_accum_reset.  The accumulation is spectral AND
+ *                             featured: srt_read_spectral, srt_develop_spectral / _srgb, srt_read_features and srt_denoise_features /
+ *                             _vg return on it what they return on the single-kind accumulations, and srt_denoise_developed, below,
+ *                             needs it.  It is NOT adaptive: srt_accum_active, the sample map and S2 of srt_read_accum_stats and
+ *                             srt_denoise_features_mv keep refusing it.  Every other srt_accum_reset* makes the next accumulation
+ *                             something else again. */
+SRT_API int srt_accum_reset_spectral_features(srt_ctx *ctx);
 
 /* Edge-avoiding a-trous denoiser over the first-hit feature buffers (no reference counterpart; kernels in csrc/srt_denoise.hip).  It
  * consumes a FEATURED accumulation: the XYZ sums are filtered by `levels` passes of a 5x5 B3-spline stencil whose taps are weighted down
@@ -535,6 +558,44 @@ SRT_API int srt_denoise_features_mv(srt_ctx *ctx, const srt_denoise_vg *cfg, flo
                                     uint32_t image_width, uint32_t image_height);
 SRT_API int srt_denoise_mv_kat(srt_ctx *ctx, const srt_denoise_vg *cfg, const float *xyz_sums, const float *features,
                                const uint32_t *samples, const float *sum_y2, uint32_t w, uint32_t h, float *out_xyz, float *out_var);
+
+/* The developed film, denoised: the plain a-trous filter of srt_denoise_features with a K-channel PAYLOAD (kernels in
+ * csrc/srt_denoise.hip behind the others).  It needs a SPECTRAL FEATURED accumulation (srt_accum_reset_spectral_features): the film is
+ * developed through K response curves, and the K planes ride through the levels on the weights the XYZ colour and the guides produce.
+ * Operation by operation -- everything fp32, not contracted, left to right; the restatement is tests/denoise_developed_reference.py:
+ *   Develop:  D_p[k], k = 0 .. K-1, is the contraction stated at srt_develop_spectral (the same kernel): response[K][95], channels = K
+ *     and scale are validated as there, 1 <= K <= SRT_MAX_DEVELOP_CHANNELS.
+ *   Prepass:  srt_denoise_features' prepass, and in addition  d_p[k] = inv * D_p[k]  with the prepass's inv = 1.0f / (float)n.
+ *   Level i:  the plain filter's tap loop and weights, unchanged -- wt = h[dy+2] * h[dx+2], then * e(dn, kn), * e(da, ka), * e(dz, kz),
+ *     * e(dc, kc), dc on the level's XYZ colour, never on the payload -- and inside the same  if (wt > 0) { .. },  after sz:
+ *       sd[k] += wt * d_q[k]   for k = 0 .. K-1
+ *     Output of the level:  sw > 0 ? sd[k] / sw : d_p[k],  next to the unchanged colour output.  Colour and payload both ping-pong
+ *     through the levels; levels == 0 returns (c_p, d_p).
+ *     What follows: the weights never see the payload; every channel is filtered by the same stencil; a tap with wt == 0 never
+ *     multiplies its payload, so a non-finite payload there does not enter; a pixel whose colour is NaN keeps its own payload and no
+ *     neighbour takes it in; a payload NaN at a tap with wt > 0 propagates as the arithmetic says.
+ *   Outputs:  out_dev[((y * image_width) + x) * K + k] the filtered developed mean; out_xyz[((y * image_width) + x) * 3 + c] the
+ *     filtered XYZ mean, which is bit-identical to srt_denoise_features' out_xyz on the same accumulation and cfg.  Either may be NULL,
+ *     not both.
+ *   srt_denoise_developed placement, clipping, synchronisation, the read-only behaviour towards the accumulation and the partition
+ *                         refusal are srt_denoise_features'.  Refused, the accumulation unchanged: a null ctx / cfg / response, both
+ *                         outputs NULL, an empty image, a cfg as srt_denoise_features refuses it, response / channels / scale as
+ *                         srt_develop_spectral refuses them, an accumulation that is not spectral AND featured with at least one pass --
+ *                         a plain spectral, a plain featured and an adaptive featured one are all refused -- (SRT_ERR_INVALID); a
+ *                         partition other than (0, 1) (SRT_ERR_UNSUPPORTED); a failed allocation (SRT_ERR_HIP).  Working images: the
+ *                         plain filter's and the develop's, plus 2 * KC * 4 + K * 4 bytes per pixel of the chunk for the payload, KC
+ *                         the smallest of 4, 8, 16 that holds K.  srt_denoise_last_ms and srt_develop_last_ms report this call's
+ *                         kernels (prepass: both prepasses; level i: the payload level; epilogue: both output kernels).
+ *   srt_denoise_developed_kat  the same prepass, level and output kernels on caller-supplied row-major host arrays xyz_sums[h][w][3],
+ *                         features[h][w][8] and developed[h][w][K] (the planes D, sums over `samples` samples: no develop runs);
+ *                         out_dev[h][w][K] and out_xyz[h][w][3], either may be NULL, not both.  Needs neither a scene nor an
+ *                         accumulation and touches neither.  SRT_ERR_INVALID for a null input, a cfg as above, channels == 0 or >
+ *                         SRT_MAX_DEVELOP_CHANNELS, samples == 0, an empty image or w x h >= 2^31. */
+SRT_API int srt_denoise_developed(srt_ctx *ctx, const srt_denoise *cfg, const float *response, uint32_t channels, float scale,
+                                  float *out_dev, float *out_xyz, uint32_t image_width, uint32_t image_height);
+SRT_API int srt_denoise_developed_kat(srt_ctx *ctx, const srt_denoise *cfg, const float *xyz_sums, const float *features,
+                                      const float *developed, uint32_t channels, uint32_t samples, uint32_t w, uint32_t h,
+                                      float *out_dev, float *out_xyz);
 
 /* Sample-parallel pixels (no reference counterpart; a deliberate departure from its one RNG stream per pixel, so opt-in).  A STREAMED
  * accumulation gives every pixel K independent RNG streams, each with its own state and its own XYZ sum, so that any lane of any wave
@@ -743,6 +804,9 @@ SRT_API int srt_comm_accum_reset_features(srt_comm *comm);
 /* srt_accum_reset_adaptive_features on every local rank; like srt_comm_accum_reset_adaptive, SRT_ERR_UNSUPPORTED on a process-per-GPU
  * communicator.  The rows stay with their ranks, as for srt_comm_accum_reset_features. */
 SRT_API int srt_comm_accum_reset_adaptive_features(srt_comm *comm, const srt_adaptive *cfg);
+/* srt_accum_reset_spectral_features on every local rank (any communicator: no decision crosses ranks); film and rows stay with their
+ * ranks, as for srt_comm_accum_reset_spectral and srt_comm_accum_reset_features.  There is no srt_comm denoise: a gathered denoise is out of scope. */
+SRT_API int srt_comm_accum_reset_spectral_features(srt_comm *comm);
 /* Sample-parallel pixels on W GPUs: srt_accum_reset_streams on every local context; srt_render_frame_multi_accum then runs MODE 6 on each
  * rank.  On process-per-GPU communicators too: no decision crosses ranks (every rank resets with the same K). */
 SRT_API int srt_comm_accum_reset_streams(srt_comm *comm, uint32_t streams);

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Compares the render kernels of two builds: every instantiation of render_kernel (eight modes x six shapes), by the sha256 of its
+"""Compares the render kernels of two builds: every instantiation of render_kernel (every mode x six shapes), by the sha256 of its
 position-independent machine code in the gfx950 code object of the library and of its body in the ISA listing (both from
 tools/kernel_id.py, whose own output stays with the production MODE 0 kernels: bench.py reads it).
 

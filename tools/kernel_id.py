@@ -26,9 +26,9 @@ OBJ = os.path.join(ROOT, "cuda-spectral-ray-tracer_amd", "csrc", "_build", "srt_
 LIB = os.path.join(ROOT, "cuda-spectral-ray-tracer_amd", "libsrt_hip.so")
 
 
-# render_kernel<MODE, NARROW, ALL_CACHED[, PAIRED]> of all nine modes, as a symbol of the code object and (followed by ':') as a label
+# render_kernel<MODE, NARROW, ALL_CACHED[, PAIRED]> of all ten modes, as a symbol of the code object and (followed by ':') as a label
 # of the listing (PAIRED is round 5's fourth template argument; listings / libraries of earlier rounds have three)
-RENDER = re.compile(r"_ZN3srt13render_kernelILi([0-8])ELb([01])ELb([01])E(?:Lb([01])E)?EEv\w*")
+RENDER = re.compile(r"_ZN3srt13render_kernelILi([0-9])ELb([01])ELb([01])E(?:Lb([01])E)?EEv\w*")
 
 
 def _render_key(name):
