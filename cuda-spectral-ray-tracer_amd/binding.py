@@ -145,6 +145,9 @@ PROTOTYPES = {
     "srt_read_features": (_i, [_vp, _fp, _u32, _u32]),
     "srt_accum_reset_adaptive_features": (_i, [_vp, C.POINTER(Adaptive)]),
     "srt_accum_reset_spectral_features": (_i, [_vp]),
+    "srt_accum_reset_adaptive_spectral": (_i, [_vp, C.POINTER(Adaptive)]),
+    "srt_accum_reset_adaptive_spectral_features": (_i, [_vp, C.POINTER(Adaptive)]),
+    "srt_denoise_developed_counts_kat": (_i, [_vp, C.POINTER(Denoise), _fp, _fp, _fp, _u32, C.POINTER(_u32), _u32, _u32, _fp, _fp]),
     "srt_denoise_developed": (_i, [_vp, C.POINTER(Denoise), _fp, _u32, _f, _fp, _fp, _u32, _u32]),
     "srt_denoise_developed_kat": (_i, [_vp, C.POINTER(Denoise), _fp, _fp, _fp, _u32, _u32, _u32, _u32, _fp, _fp]),
     "srt_denoise_features": (_i, [_vp, C.POINTER(Denoise), _fp, _fp, _fp, _u32, _u32]),
@@ -204,6 +207,8 @@ PROTOTYPES = {
     "srt_comm_accum_reset_features": (_i, [_vp]),
     "srt_comm_accum_reset_adaptive_features": (_i, [_vp, C.POINTER(Adaptive)]),
     "srt_comm_accum_reset_spectral_features": (_i, [_vp]),
+    "srt_comm_accum_reset_adaptive_spectral": (_i, [_vp, C.POINTER(Adaptive)]),
+    "srt_comm_accum_reset_adaptive_spectral_features": (_i, [_vp, C.POINTER(Adaptive)]),
     "srt_comm_accum_reset_streams": (_i, [_vp, _u32]),
     "srt_comm_synchronize": (_i, [_vp]),
     "srt_comm_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_f)]),

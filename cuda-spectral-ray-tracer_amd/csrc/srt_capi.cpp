@@ -118,7 +118,7 @@ struct srt_ctx {
     // The one accumulation of a context (srt_accum_reset*, srt_render_chunk_accum).
     struct Accumulation {
         enum class State { Invalid, Empty, Bound } state = State::Invalid;   // Empty: reset, no pass yet; Bound: passes of one chunk
-        enum class Kind { Plain, Adaptive, Spectral, Streams, Features, AdaptiveFeatures, SpectralFeatures } kind = Kind::Plain;    // MODE 3 / 4 / 5 / 6 / 7 / 8 / 9 passes (adaptive + features and spectral + features are the two combinations)
+        enum class Kind { Plain, Adaptive, Spectral, Streams, Features, AdaptiveFeatures, SpectralFeatures, AdaptiveSpectral, AdaptiveSpectralFeatures } kind = Kind::Plain;    // MODE 3 .. 11 passes (streams combine with nothing)
         uint32_t total = 0;                             // samples per pixel in the sums (streamed: over all streams)
         uint32_t n_streams = 1;                         // streamed: the RNG streams per pixel (K); 1 otherwise
         uint32_t w = 0, h = 0, offx = 0, offy = 0;      // the chunk of the first pass
@@ -126,16 +126,16 @@ struct srt_ctx {
         void begin(Kind k, uint32_t streams_per_pixel = 1) { kind = k; n_streams = streams_per_pixel; state = State::Empty; }      // (srt_accum_reset has zeroed the total)
         bool valid() const { return state != State::Invalid; }
         bool bound() const { return state == State::Bound; }
-        bool adaptive() const { return kind == Kind::Adaptive || kind == Kind::AdaptiveFeatures; }
-        bool spectral() const { return kind == Kind::Spectral || kind == Kind::SpectralFeatures; }
+        bool adaptive() const { return kind == Kind::Adaptive || kind == Kind::AdaptiveFeatures || kind == Kind::AdaptiveSpectral || kind == Kind::AdaptiveSpectralFeatures; }
+        bool spectral() const { return kind == Kind::Spectral || kind == Kind::SpectralFeatures || kind == Kind::AdaptiveSpectral || kind == Kind::AdaptiveSpectralFeatures; }
         bool streamed() const { return kind == Kind::Streams; }
-        bool featured() const { return kind == Kind::Features || kind == Kind::AdaptiveFeatures || kind == Kind::SpectralFeatures; }
+        bool featured() const { return kind == Kind::Features || kind == Kind::AdaptiveFeatures || kind == Kind::SpectralFeatures || kind == Kind::AdaptiveSpectralFeatures; }
     } accum;
     // the buffers behind it, allocated on first use:
     DeviceBuffer d_accum;                               // progressive rendering (AccumLayout)
     DeviceBuffer d_adapt;                               // adaptive sampling (srt_accum_reset_adaptive, AdaptPlanes)
     DeviceBuffer d_adapt_queue;                         // pixel queue of the next adaptive pass (AdaptQueue)
-    DeviceBuffer d_film;                                // spectral film (srt_accum_reset_spectral): kFilmStride floats per lane
+    DeviceBuffer d_film;                                // spectral film (srt_accum_reset_spectral): kFilmStride floats per lane (adaptive + spectral + features: and the rows behind it)
     DeviceBuffer d_film_staging;                        // row-major staging block of srt_read_spectral
     DeviceBuffer d_features;                            // first-hit features (srt_accum_reset_features): kFeatureStride floats per lane
     DeviceBuffer d_features_staging;                    // row-major staging block of srt_read_features
@@ -315,7 +315,8 @@ struct Pass {
     uint32_t streams;          // streamed passes: K, the copies of every queue row (one per stream); 1 otherwise
 };
 
-bool adaptive_mode(RenderMode m) { return m == Adaptive || m == AdaptiveFeatures; }      // MODE 4 and MODE 8 share everything around the launch
+// MODE 4, 8, 10 and 11 share everything around the launch
+bool adaptive_mode(RenderMode m) { return m == Adaptive || m == AdaptiveFeatures || m == AdaptiveSpectral || m == AdaptiveSpectralFeatures; }
 uint32_t split_rows_bound(const srt_ctx *c) { return (uint32_t)std::min<uint64_t>((uint64_t)c->tiles_local * 64, 0x7fffffffull); }
 // The queue head is a 32-bit pixel-slot counter, and a streamed pass runs K copies of every row: its tiles are split only where even
 // the finest split of every tile stays below 2^32 slots; srt_render_chunk_accum refuses a pass whose UNsplit rows do not.
@@ -495,12 +496,12 @@ int combine_streams(srt_ctx *c, const Pass &ps, const RenderParams &p) {
 }
 
 // spp_add == 0: a plain launch of c->spp samples (Plain, or Counting when instrumented); spp_add > 0: an accumulating pass of spp_add
-// samples (Accum / Adaptive / Spectral / Streams / Features / AdaptiveFeatures / SpectralFeatures) whose caller has checked the accumulation and enqueued its header.
+// samples (Accum / Adaptive / Spectral / Streams / Features / AdaptiveFeatures / SpectralFeatures / AdaptiveSpectral / AdaptiveSpectralFeatures) whose caller has checked the accumulation and enqueued its header.
 // width .. offy are already narrowed to 16 bit.
 int render_chunk_impl(srt_ctx *c, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy, uint32_t spp_add, hipStream_t st) {
     Pass ps = {};
     ps.spp_add = spp_add; ps.st = st;
-    ps.mode = !spp_add ? (c->count_traversal ? Counting : Plain) : c->accum.adaptive() ? (c->accum.featured() ? AdaptiveFeatures : Adaptive) : c->accum.spectral() ? (c->accum.featured() ? SpectralFeatures : Spectral) : c->accum.streamed() ? Streams : c->accum.featured() ? Features : Accum;
+    ps.mode = !spp_add ? (c->count_traversal ? Counting : Plain) : c->accum.adaptive() ? (c->accum.spectral() ? (c->accum.featured() ? AdaptiveSpectralFeatures : AdaptiveSpectral) : c->accum.featured() ? AdaptiveFeatures : Adaptive) : c->accum.spectral() ? (c->accum.featured() ? SpectralFeatures : Spectral) : c->accum.streamed() ? Streams : c->accum.featured() ? Features : Accum;
     ps.later = spp_add && c->accum.bound(); ps.plan = plan_of(c);
     ps.streams = ps.mode == Streams ? c->accum.n_streams : 1u;
     c->last_w = width; c->last_h = height; c->last_offx = offx; c->last_offy = offy;
@@ -925,9 +926,11 @@ int srt_accum_streams(const srt_ctx *c, uint32_t *streams) {
     return SRT_OK;
 }
 
-// srt_accum_reset_adaptive and srt_accum_reset_adaptive_features (`features`): one body, so that validation, refusals and invalidation
-// of the second are those of the first by construction; the featured one adds srt_accum_reset_features' allocation rule and rows
-static int accum_reset_adaptive(srt_ctx *c, const srt_adaptive *cfg, bool features, const char *who) {
+// srt_accum_reset_adaptive, srt_accum_reset_adaptive_features (`features`), srt_accum_reset_adaptive_spectral (`spectral`) and
+// srt_accum_reset_adaptive_spectral_features (both): one body, so that validation, refusals and invalidation of the others are those of the
+// first by construction; the featured one adds srt_accum_reset_features' allocation rule and rows, the spectral ones
+// srt_accum_reset_spectral's rule and film.  With both, the rows lie behind the film in d_film (feature_rows): MODE 11 finds them there.
+static int accum_reset_adaptive(srt_ctx *c, const srt_adaptive *cfg, bool features, bool spectral, const char *who) {
     const std::string w_(who);
     if (!c) return fail(c, SRT_ERR_INVALID, w_ + ": null ctx");
     // refusals first: a refused call leaves the context's accumulation as it was
@@ -939,8 +942,18 @@ static int accum_reset_adaptive(srt_ctx *c, const srt_adaptive *cfg, bool featur
     if (c->count_traversal)
         return fail(c, SRT_ERR_UNSUPPORTED, w_ + ": no instrumented accumulating kernel (srt_set_count_traversal(ctx, 0) first)");
     if (!c->params_ready) return fail(c, SRT_ERR_INVALID, w_ + ": device parameters must be set first (srt_init_device_params)");
-    const size_t row_bytes = (size_t)c->n_lanes * kFeatureStride * sizeof(float);
-    if (features && c->d_features.bytes < row_bytes) {
+    const size_t row_bytes = (size_t)c->n_lanes * kFeatureStride * sizeof(float), film_bytes = (size_t)c->n_lanes * kFilmStride * sizeof(float);
+    if (spectral) {
+        // (film, and rows behind it: one block, allocated before the old one goes -- a failed allocation changes nothing, and leaves no
+        // error behind for the next launch's hipGetLastError)
+        const size_t bytes = film_bytes + (features ? row_bytes : 0);
+        if (c->d_film.bytes < bytes) {
+            HIP_TRY(c, hipSetDevice(c->device));
+            DeviceBuffer film;
+            if (const hipError_t e = film.reserve(bytes)) { (void)hipGetLastError(); return hip_fail(c, e, who); }
+            c->d_film = std::move(film);
+        }
+    } else if (features && c->d_features.bytes < row_bytes) {
         // (the new rows are allocated before the old ones go: a failed allocation changes nothing)
         HIP_TRY(c, hipSetDevice(c->device));
         DeviceBuffer rows;
@@ -952,22 +965,38 @@ static int accum_reset_adaptive(srt_ctx *c, const srt_adaptive *cfg, bool featur
     c->accum.invalidate();      // (until the adaptive planes are in place)
     HIP_TRY(c, c->d_adapt.reserve(AdaptPlanes::bytes(c->n_lanes)));
     HIP_TRY(c, hipMemset(c->d_adapt.ptr, 0, AdaptPlanes::bytes(c->n_lanes)));
-    if (features) HIP_TRY(c, hipMemset(c->d_features.ptr, 0, row_bytes));
-    // the adaptive half of the header, and the featured part behind it (the per-pass kernel rewrites only sums and spp_total)
+    float *const rows = !features ? nullptr : spectral ? c->d_film.as<float>() + (size_t)c->n_lanes * kFilmStride : c->d_features.as<float>();
+    if (spectral) HIP_TRY(c, hipMemset(c->d_film.ptr, 0, film_bytes));
+    if (features) HIP_TRY(c, hipMemset(rows, 0, row_bytes));
+    // the adaptive half of the header, and the film and the featured part behind it (the per-pass kernel rewrites only sums and spp_total)
     AccumHeader h = {};
     h.sum2 = AdaptPlanes(c).sum2; h.state = AdaptPlanes(c).state;
     h.rel_tol = cfg->rel_tol; h.abs_tol = cfg->abs_tol; h.min_spp = cfg->min_spp;
-    if (features) { h.features = c->d_features.as<float>(); h.mat_col = c->d_mat_col.as<const float>(); }
+    if (spectral) h.film = c->d_film.as<float>();
+    if (features) { h.features = rows; h.mat_col = c->d_mat_col.as<const float>(); }
     const size_t tail = offsetof(AccumHeader, sum2);
     HIP_TRY(c, hipMemcpy(&AccumLayout(c).header->sum2, reinterpret_cast<const char *>(&h) + tail, sizeof(h) - tail, hipMemcpyHostToDevice));
     HIP_TRY(c, hipDeviceSynchronize());
-    c->accum.begin(features ? srt_ctx::Accumulation::Kind::AdaptiveFeatures : srt_ctx::Accumulation::Kind::Adaptive);
+    using Kind = srt_ctx::Accumulation::Kind;
+    c->accum.begin(spectral ? (features ? Kind::AdaptiveSpectralFeatures : Kind::AdaptiveSpectral) : features ? Kind::AdaptiveFeatures : Kind::Adaptive);
     return SRT_OK;
 }
 
-int srt_accum_reset_adaptive(srt_ctx *c, const srt_adaptive *cfg) { return accum_reset_adaptive(c, cfg, false, "srt_accum_reset_adaptive"); }
+// the feature rows of the context's featured accumulation: d_features, except that an adaptive spectral featured accumulation keeps them
+// behind its film (accum_reset_adaptive)
+static float *feature_rows(const srt_ctx *c) {
+    return c->accum.kind == srt_ctx::Accumulation::Kind::AdaptiveSpectralFeatures ? c->d_film.as<float>() + (size_t)c->n_lanes * kFilmStride : c->d_features.as<float>();
+}
 
-int srt_accum_reset_adaptive_features(srt_ctx *c, const srt_adaptive *cfg) { return accum_reset_adaptive(c, cfg, true, "srt_accum_reset_adaptive_features"); }
+int srt_accum_reset_adaptive(srt_ctx *c, const srt_adaptive *cfg) { return accum_reset_adaptive(c, cfg, false, false, "srt_accum_reset_adaptive"); }
+
+int srt_accum_reset_adaptive_features(srt_ctx *c, const srt_adaptive *cfg) { return accum_reset_adaptive(c, cfg, true, false, "srt_accum_reset_adaptive_features"); }
+
+int srt_accum_reset_adaptive_spectral(srt_ctx *c, const srt_adaptive *cfg) { return accum_reset_adaptive(c, cfg, false, true, "srt_accum_reset_adaptive_spectral"); }
+
+int srt_accum_reset_adaptive_spectral_features(srt_ctx *c, const srt_adaptive *cfg) {
+    return accum_reset_adaptive(c, cfg, true, true, "srt_accum_reset_adaptive_spectral_features");
+}
 
 int srt_accum_active(srt_ctx *c, uint64_t *active) {
     if (!c || !active) return fail(c, SRT_ERR_INVALID, "srt_accum_active: null argument");
@@ -1140,7 +1169,7 @@ int srt_read_features(srt_ctx *c, float *out, uint32_t image_width, uint32_t ima
     const ChunkRect rect = chunk_rect(c, image_width, image_height);
     if (const size_t n = (size_t)rect.w * rect.h * kFeatureStride) {
         HIP_TRY(c, c->d_features_staging.reserve(n * sizeof(float)));
-        HIP_TRY(c, launch_features_unswizzle(c->d_features.as<float>(), c->d_features_staging.as<float>(), rect.w, rect.h, c->tx, c->ty, c->bx, nullptr));
+        HIP_TRY(c, launch_features_unswizzle(feature_rows(c), c->d_features_staging.as<float>(), rect.w, rect.h, c->tx, c->ty, c->bx, nullptr));
         const size_t row = (size_t)rect.w * kFeatureStride * sizeof(float), pitch = (size_t)image_width * kFeatureStride * sizeof(float);
         HIP_TRY(c, hipMemcpy2D(out + rect.first * kFeatureStride, pitch, c->d_features_staging.ptr, row, row, rect.h, hipMemcpyDeviceToHost));
     }
@@ -1181,8 +1210,9 @@ int develop_reserve(srt_ctx *c, const char *who, DeviceBuffer &d, size_t bytes) 
 // The contraction of the film rows `film` (the lanes of a tx x ty x bx grid, n_lanes of them) over the w x h rectangle into
 // DevelopLayout::out, then (samples > 0) the sRGB epilogue into lin / q.  d_develop is reserved by the caller.  Enqueues on the default
 // stream; the caller synchronises.  Events: [0] contraction [1] epilogue [2].
+// counts (with samples > 0): the state words of an adaptive accumulation, by lane -- the epilogue normalises each pixel by its own count.
 int run_develop(srt_ctx *c, const char *who, const float *film, uint32_t n_lanes, uint32_t tx, uint32_t ty, uint32_t bx, uint32_t w, uint32_t h,
-                const float *response, uint32_t channels, float scale, uint32_t samples) {
+                const float *response, uint32_t channels, float scale, uint32_t samples, const uint32_t *counts = nullptr) {
     const size_t pixels = (size_t)w * h;
     const DevelopLayout L(c->d_develop, pixels, channels);
     // the curves as the kernel reads them: [j][kc], the padding +0
@@ -1200,7 +1230,11 @@ int run_develop(srt_ctx *c, const char *who, const float *film, uint32_t n_lanes
     HIP_TRY_AS(c, who, launch_develop(p, nullptr));
     HIP_TRY_AS(c, who, hipEventRecord(c->develop_ev[1], nullptr));
     if (samples) {
-        HIP_TRY_AS(c, who, launch_develop_srgb(L.out, L.lin, L.q, samples, pixels, nullptr));
+        if (counts) {
+            DevelopSrgbCountsParams sp = {};
+            sp.xyz = L.out; sp.out_lin = L.lin; sp.out_q = L.q; sp.counts = counts; sp.tx = tx; sp.ty = ty; sp.bx = bx; sp.w = w; sp.h = h;
+            HIP_TRY_AS(c, who, launch_develop_srgb_counts(sp, nullptr));
+        } else HIP_TRY_AS(c, who, launch_develop_srgb(L.out, L.lin, L.q, samples, pixels, nullptr));
         HIP_TRY_AS(c, who, hipEventRecord(c->develop_ev[2], nullptr));
     }
     c->develop_epilogue = samples != 0; c->develop_timed = true;
@@ -1208,7 +1242,7 @@ int run_develop(srt_ctx *c, const char *who, const float *film, uint32_t n_lanes
 }
 
 // srt_develop_spectral / srt_develop_spectral_srgb behind their argument checks: host[0] the developed planes, host[1 .. 2] the sRGB
-// variant's outputs (srgb: the accumulation's sample total normalises them)
+// variant's outputs (srgb: the accumulation's sample total normalises them -- each pixel's own count when the accumulation is adaptive)
 int develop_accumulation(srt_ctx *c, const char *who, const float *response, uint32_t channels, float scale, bool srgb, float *const host[3],
                          uint32_t image_width, uint32_t image_height) {
     if (!c->accum.spectral() || !c->accum.bound())
@@ -1219,7 +1253,8 @@ int develop_accumulation(srt_ctx *c, const char *who, const float *response, uin
     const size_t pixels = (size_t)w * h;
     if (pixels) {
         if (const int rc = develop_reserve(c, who, c->d_develop, DevelopLayout::bytes(pixels, channels, srgb))) return rc;
-        if (const int rc = run_develop(c, who, c->d_film.as<float>(), c->n_lanes, c->tx, c->ty, c->bx, w, h, response, channels, scale, srgb ? c->accum.total : 0u)) return rc;
+        if (const int rc = run_develop(c, who, c->d_film.as<float>(), c->n_lanes, c->tx, c->ty, c->bx, w, h, response, channels, scale, srgb ? c->accum.total : 0u,
+                                       srgb && c->accum.adaptive() ? AdaptPlanes(c).state : nullptr)) return rc;
         const ChunkRect rect = chunk_rect(c, image_width, image_height);
         const DevelopLayout L(c->d_develop, pixels, channels);
         const float *src[3] = {L.out, L.lin, L.q};
@@ -1428,7 +1463,7 @@ int denoise_features(srt_ctx *c, const char *who, const DenoisePlan &plan, float
         HIP_TRY(c, c->d_denoise.reserve(DenoiseLayout::bytes(pixels, plan.vg)));
         DenoisePrepassParams pre = {};
         pre.sums = AccumLayout(c).sums; pre.sum_pixel_stride = 1; pre.sum_comp_stride = c->n_lanes;
-        pre.rows = c->d_features.as<const float4>();
+        pre.rows = reinterpret_cast<const float4 *>(feature_rows(c));
         pre.tx = c->tx; pre.ty = c->ty; pre.bx = c->bx; pre.w = w; pre.h = h; pre.samples = c->accum.total;
         // (an adaptive featured accumulation: every pixel of the chunk is normalised by its own count, the samples field of its state word)
         if (c->accum.adaptive()) pre.counts = AdaptPlanes(c).state;
@@ -1562,9 +1597,16 @@ int run_denoise_developed(srt_ctx *c, const char *who, const DenoisePlan &plan, 
     uint32_t n_ev = 0;
     HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
     HIP_TRY_AS(c, who, launch_denoise_prepass(pre, nullptr));
-    DenoisePayloadPrepassParams pp = {};
-    pp.developed = developed; pp.payload = D.payload[0]; pp.pixels = pixels; pp.channels = channels; pp.groups = groups; pp.samples = pre.samples;
-    HIP_TRY_AS(c, who, launch_denoise_payload_prepass(pp, nullptr));
+    if (pre.counts) {      // (pixels with different sample counts: both prepasses use the pixel's own)
+        DenoisePayloadPrepassCountsParams pp = {};
+        pp.developed = developed; pp.payload = D.payload[0]; pp.counts = pre.counts; pp.tx = pre.tx; pp.ty = pre.ty; pp.bx = pre.bx;
+        pp.w = pre.w; pp.h = pre.h; pp.channels = channels; pp.groups = groups;
+        HIP_TRY_AS(c, who, launch_denoise_payload_prepass_counts(pp, nullptr));
+    } else {
+        DenoisePayloadPrepassParams pp = {};
+        pp.developed = developed; pp.payload = D.payload[0]; pp.pixels = pixels; pp.channels = channels; pp.groups = groups; pp.samples = pre.samples;
+        HIP_TRY_AS(c, who, launch_denoise_payload_prepass(pp, nullptr));
+    }
     HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
     const uint32_t level_ev = n_ev - 1;
     uint32_t cur = 0;
@@ -1596,7 +1638,8 @@ int srt_denoise_developed(srt_ctx *c, const srt_denoise *cfg, const float *respo
     if (const char *why = denoise_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_denoise_developed: ") + why);
     if (const char *why = develop_args_error(response, channels, scale)) return fail(c, SRT_ERR_INVALID, std::string("srt_denoise_developed: ") + why);
     if (!c->accum.spectral() || !c->accum.featured() || !c->accum.bound())
-        return fail(c, SRT_ERR_INVALID, "srt_denoise_developed: no spectral featured accumulation with a pass (srt_accum_reset_spectral_features and srt_render_chunk_accum first)");
+        return fail(c, SRT_ERR_INVALID, "srt_denoise_developed: no spectral featured accumulation with a pass (srt_accum_reset_spectral_features or "
+                                        "srt_accum_reset_adaptive_spectral_features, and srt_render_chunk_accum first)");
     if (c->rank != 0 || c->world != 1)
         return fail(c, SRT_ERR_UNSUPPORTED, "srt_denoise_developed: needs the whole chunk on this context (partition (0, 1)): pixels of other ranks read +0");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1610,8 +1653,10 @@ int srt_denoise_developed(srt_ctx *c, const srt_denoise *cfg, const float *respo
         if (const int rc = run_develop(c, who, c->d_film.as<float>(), c->n_lanes, c->tx, c->ty, c->bx, w, h, response, channels, scale, 0u)) return rc;
         DenoisePrepassParams pre = {};
         pre.sums = AccumLayout(c).sums; pre.sum_pixel_stride = 1; pre.sum_comp_stride = c->n_lanes;
-        pre.rows = c->d_features.as<const float4>();
+        pre.rows = reinterpret_cast<const float4 *>(feature_rows(c));
         pre.tx = c->tx; pre.ty = c->ty; pre.bx = c->bx; pre.w = w; pre.h = h; pre.samples = c->accum.total;
+        // (an adaptive spectral featured accumulation: colour, guides and payload of a pixel are normalised by the pixel's own count)
+        if (c->accum.adaptive()) pre.counts = AdaptPlanes(c).state;
         if (const int rc = run_denoise_developed(c, who, denoise_plan(cfg), pre, DevelopLayout(c->d_develop, pixels, channels).out, channels)) return rc;
         const ChunkRect rect = chunk_rect(c, image_width, image_height);
         const float *src[2] = {DenoiseDevLayout(c->d_denoise_dev, pixels, channels).out, DenoiseLayout(c->d_denoise, pixels).out[0]};
@@ -1626,33 +1671,52 @@ int srt_denoise_developed(srt_ctx *c, const srt_denoise *cfg, const float *respo
     return SRT_OK;
 }
 
-int srt_denoise_developed_kat(srt_ctx *c, const srt_denoise *cfg, const float *xyz_sums, const float *features, const float *developed, uint32_t channels,
-                              uint32_t samples, uint32_t w, uint32_t h, float *out_dev, float *out_xyz) {
-    const char *who = "srt_denoise_developed_kat";
-    if (!c || !cfg || !xyz_sums || !features || !developed || (!out_dev && !out_xyz)) return fail(c, SRT_ERR_INVALID, "srt_denoise_developed_kat: null argument");
-    if (const char *why = denoise_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_denoise_developed_kat: ") + why);
-    if (channels == 0 || channels > kMaxDevelopChannels) return fail(c, SRT_ERR_INVALID, "srt_denoise_developed_kat: channels must be in 1 .. SRT_MAX_DEVELOP_CHANNELS (16)");
-    if (samples == 0 || w == 0 || h == 0 || (uint64_t)w * h > 0x7fffffffull) return fail(c, SRT_ERR_INVALID, "srt_denoise_developed_kat: samples, w and h must be positive, w x h below 2^31");
-    HIP_TRY(c, hipSetDevice(c->device));
+// srt_denoise_developed_kat / srt_denoise_developed_counts_kat behind their own null checks (sample_map: the second's [h][w] counts in the
+// place of the scalar `samples`, which is not read then)
+static int denoise_developed_kat(srt_ctx *c, const char *who, const srt_denoise *cfg, const float *xyz_sums, const float *features, const float *developed,
+                                 uint32_t channels, uint32_t samples, const uint32_t *sample_map, uint32_t w, uint32_t h, float *out_dev, float *out_xyz) {
+    const std::string w_(who);
+    if (const char *why = denoise_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, w_ + ": " + why);
+    if (channels == 0 || channels > kMaxDevelopChannels) return fail(c, SRT_ERR_INVALID, w_ + ": channels must be in 1 .. SRT_MAX_DEVELOP_CHANNELS (16)");
+    if (samples == 0 || w == 0 || h == 0 || (uint64_t)w * h > 0x7fffffffull) return fail(c, SRT_ERR_INVALID, w_ + ": samples, w and h must be positive, w x h below 2^31");
     const size_t pixels = (size_t)w * h;
+    if (sample_map)
+        for (size_t k = 0; k < pixels; k++)
+            if ((sample_map[k] & ~kAdaptConverged) == 0) return fail(c, SRT_ERR_INVALID, w_ + ": a zero in samples (every pixel must hold at least one sample)");
+    HIP_TRY(c, hipSetDevice(c->device));
     if (const int rc = develop_reserve(c, who, c->d_denoise, DenoiseLayout::bytes(pixels, false))) return rc;
     if (const int rc = develop_reserve(c, who, c->d_denoise_dev, DenoiseDevLayout::bytes(pixels, channels, true))) return rc;
-    if (const int rc = develop_reserve(c, who, c->d_denoise_in, pixels * (kFeatureStride + 3) * sizeof(float))) return rc;
+    if (const int rc = develop_reserve(c, who, c->d_denoise_in, pixels * (kFeatureStride + 3 + 1) * sizeof(float))) return rc;
     const DenoiseDevLayout D(c->d_denoise_dev, pixels, channels);
-    float *d_rows = c->d_denoise_in.as<float>(), *d_sums = d_rows + pixels * kFeatureStride;
+    float *d_rows = c->d_denoise_in.as<float>(), *d_sums = d_rows + pixels * kFeatureStride, *d_map = d_sums + pixels * 3;
     HIP_TRY_AS(c, who, hipMemcpy(d_rows, features, pixels * kFeatureStride * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY_AS(c, who, hipMemcpy(d_sums, xyz_sums, pixels * 3 * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY_AS(c, who, hipMemcpy(D.in, developed, pixels * channels * sizeof(float), hipMemcpyHostToDevice));
+    if (sample_map) HIP_TRY_AS(c, who, hipMemcpy(d_map, sample_map, pixels * sizeof(uint32_t), hipMemcpyHostToDevice));
     // a grid of one w x h block makes the prepass's block-linear lane the row-major pixel
     DenoisePrepassParams pre = {};
     pre.sums = d_sums; pre.sum_pixel_stride = 3; pre.sum_comp_stride = 1;
     pre.rows = reinterpret_cast<const float4 *>(d_rows);
     pre.tx = w; pre.ty = h; pre.bx = 1; pre.w = w; pre.h = h; pre.samples = samples;
+    if (sample_map) pre.counts = reinterpret_cast<const uint32_t *>(d_map);
     if (const int rc = run_denoise_developed(c, who, denoise_plan(cfg), pre, D.in, channels)) return rc;
     if (out_dev) HIP_TRY_AS(c, who, hipMemcpy(out_dev, D.out, pixels * channels * sizeof(float), hipMemcpyDeviceToHost));
     if (out_xyz) HIP_TRY_AS(c, who, hipMemcpy(out_xyz, DenoiseLayout(c->d_denoise, pixels).out[0], pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
     HIP_TRY_AS(c, who, hipDeviceSynchronize());
     return SRT_OK;
+}
+
+int srt_denoise_developed_kat(srt_ctx *c, const srt_denoise *cfg, const float *xyz_sums, const float *features, const float *developed, uint32_t channels,
+                              uint32_t samples, uint32_t w, uint32_t h, float *out_dev, float *out_xyz) {
+    if (!c || !cfg || !xyz_sums || !features || !developed || (!out_dev && !out_xyz)) return fail(c, SRT_ERR_INVALID, "srt_denoise_developed_kat: null argument");
+    return denoise_developed_kat(c, "srt_denoise_developed_kat", cfg, xyz_sums, features, developed, channels, samples, nullptr, w, h, out_dev, out_xyz);
+}
+
+int srt_denoise_developed_counts_kat(srt_ctx *c, const srt_denoise *cfg, const float *xyz_sums, const float *features, const float *developed, uint32_t channels,
+                                     const uint32_t *samples, uint32_t w, uint32_t h, float *out_dev, float *out_xyz) {
+    if (!c || !cfg || !xyz_sums || !features || !developed || !samples || (!out_dev && !out_xyz))
+        return fail(c, SRT_ERR_INVALID, "srt_denoise_developed_counts_kat: null argument");
+    return denoise_developed_kat(c, "srt_denoise_developed_counts_kat", cfg, xyz_sums, features, developed, channels, 1u, samples, w, h, out_dev, out_xyz);
 }
 
 int srt_denoise_last_ms(srt_ctx *c, float *prepass_ms, float *level_ms, float *epilogue_ms, uint32_t *levels) {

@@ -383,6 +383,24 @@ int srt_comm_accum_reset_adaptive_features(srt_comm *c, const srt_adaptive *cfg)
     return SRT_OK;
 }
 
+int srt_comm_accum_reset_adaptive_spectral(srt_comm *c, const srt_adaptive *cfg) {
+    if (!c) return cfail(c, SRT_ERR_INVALID, "srt_comm_accum_reset_adaptive_spectral: null comm");
+    if (!c->owns_ctx)
+        return cfail(c, SRT_ERR_UNSUPPORTED, "srt_comm_accum_reset_adaptive_spectral: not on a process-per-GPU communicator (a stop decision would need a "
+                                             "reduction across processes)");
+    for (srt_ctx *x : c->ctx) { int rc = srt_accum_reset_adaptive_spectral(x, cfg); if (rc != SRT_OK) return cfail(c, rc, srt_last_error(x)); }
+    return SRT_OK;
+}
+
+int srt_comm_accum_reset_adaptive_spectral_features(srt_comm *c, const srt_adaptive *cfg) {
+    if (!c) return cfail(c, SRT_ERR_INVALID, "srt_comm_accum_reset_adaptive_spectral_features: null comm");
+    if (!c->owns_ctx)
+        return cfail(c, SRT_ERR_UNSUPPORTED, "srt_comm_accum_reset_adaptive_spectral_features: not on a process-per-GPU communicator (a stop decision would need a "
+                                             "reduction across processes)");
+    for (srt_ctx *x : c->ctx) { int rc = srt_accum_reset_adaptive_spectral_features(x, cfg); if (rc != SRT_OK) return cfail(c, rc, srt_last_error(x)); }
+    return SRT_OK;
+}
+
 int srt_comm_accum_reset_spectral_features(srt_comm *c) {
     if (!c) return cfail(c, SRT_ERR_INVALID, "srt_comm_accum_reset_spectral_features: null comm");
     for (srt_ctx *x : c->ctx) { int rc = srt_accum_reset_spectral_features(x); if (rc != SRT_OK) return cfail(c, rc, srt_last_error(x)); }

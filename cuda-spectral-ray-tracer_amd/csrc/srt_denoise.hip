@@ -42,6 +42,9 @@
 //                            between two barriers -- 40 960 B static, so four workgroups a CU whatever G is, where staging all groups
 //                            at once would need 71 680 B at G = 4.  From step 4 on the taps come from L2 / HBM.
 //   denoise_dev_out_kernel   the payload after the last level -> the row-major [h][w][K] output
+// An adaptive spectral featured accumulation (pixels with different sample counts) adds one more, behind all of the above:
+//   denoise_payload_prepass_counts_kernel  denoise_payload_prepass_kernel with the pixel's own count n_p = counts[idx] & ~kAdaptConverged
+//                            in the place of the total (idx: the pixel's block-linear lane, as in denoise_prepass_counts_kernel)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -552,6 +555,29 @@ __global__ __launch_bounds__(256) void denoise_dev_out_kernel(const float4 *payl
     }
 }
 
+// the payload prepass of an accumulation whose pixels hold different sample counts (adaptive + spectral + features,
+// srt_denoise_developed_counts_kat): denoise_payload_prepass_kernel with the pixel's own count, read as denoise_prepass_counts_kernel
+// reads it, in the place of the global total, and nothing else changed
+__global__ __launch_bounds__(256) void denoise_payload_prepass_counts_kernel(const DenoisePayloadPrepassCountsParams P) {
+    const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= (size_t)P.w * P.h) return;
+    const size_t pixels = (size_t)P.w * P.h;
+    const uint32_t y = (uint32_t)(pix / P.w), x = (uint32_t)(pix - (size_t)y * P.w);
+    const size_t idx = block_linear_idx(x, y, P.tx, P.ty, P.bx);
+    const uint32_t n_p = P.counts[idx] & ~kAdaptConverged;
+    const float inv = 1.0f / (float)n_p;
+    const float *d = P.developed + pix * P.channels;
+    for (uint32_t g = 0; g < P.groups; g++) {
+        float v[4];
+#pragma unroll
+        for (uint32_t e = 0; e < 4u; e++) {
+            const uint32_t k = 4u * g + e;
+            v[e] = (k < P.channels) ? inv * d[k] : 0.0f;
+        }
+        P.payload[(size_t)g * pixels + pix] = make_float4(v[0], v[1], v[2], v[3]);
+    }
+}
+
 }  // namespace
 
 hipError_t launch_denoise_prepass(const DenoisePrepassParams &p, hipStream_t st) {
@@ -624,6 +650,15 @@ hipError_t launch_denoise_payload_prepass(const DenoisePayloadPrepassParams &p, 
     if (p.channels == 0 || p.channels > kMaxDevelopChannels || p.groups != denoise_payload_groups(p.channels) || p.samples == 0) return hipErrorInvalidValue;
     if (p.pixels == 0) return hipSuccess;
     hipLaunchKernelGGL(denoise_payload_prepass_kernel, dim3((uint32_t)((p.pixels + 255) / 256)), dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_denoise_payload_prepass_counts(const DenoisePayloadPrepassCountsParams &p, hipStream_t st) {
+    if (p.channels == 0 || p.channels > kMaxDevelopChannels || p.groups != denoise_payload_groups(p.channels) || !p.counts || p.tx == 0 || p.ty == 0 || p.bx == 0)
+        return hipErrorInvalidValue;
+    const size_t n = (size_t)p.w * p.h;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(denoise_payload_prepass_counts_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, p);
     return hipGetLastError();
 }
 

@@ -24,6 +24,9 @@
 //                         anything.  No atomics, no scratch.
 //   develop_srgb_kernel   three developed channels taken as XYZ sums of `samples` samples -> unquantised and quantised sRGB: the render
 //                         kernel's normalisation (inv = 1.0f / (float)samples; c = inv * sum) and xyz_mean_to_srgb (srt_device.h)
+// An adaptive spectral accumulation, whose pixels hold different sample counts, adds a third behind them and leaves them as they are:
+//   develop_srgb_counts_kernel  develop_srgb_kernel with the pixel's own count n_p = counts[idx] & ~kAdaptConverged in the place of the
+//                         total, idx the pixel's block-linear lane (the state words are indexed like the film), and nothing else changed
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -111,6 +114,21 @@ __global__ __launch_bounds__(256) void develop_srgb_kernel(const float *xyz, flo
     if (out_q) { out_q[3 * pix + 0] = o.q.x; out_q[3 * pix + 1] = o.q.y; out_q[3 * pix + 2] = o.q.z; }
 }
 
+// the epilogue of an accumulation whose pixels hold different sample counts (adaptive + spectral): the kernel above over the row-major
+// w x h rectangle with the pixel's own count in the place of the total.  A pixel that holds no sample (n_p == 0: a pixel of another
+// rank) has +0 sums and is normalised by 1: the 0 * inf of 1 / 0 never forms.
+__global__ __launch_bounds__(256) void develop_srgb_counts_kernel(const DevelopSrgbCountsParams P) {
+    const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= (size_t)P.w * P.h) return;
+    const uint32_t y = (uint32_t)(pix / P.w), x = (uint32_t)(pix - (size_t)y * P.w);
+    const size_t idx = block_linear_idx(x, y, P.tx, P.ty, P.bx);
+    const uint32_t n_p = P.counts[idx] & ~kAdaptConverged;
+    const float inv = 1.0f / (float)(n_p ? n_p : 1u);
+    const SrgbPixel o = xyz_mean_to_srgb(mk(inv * P.xyz[3 * pix + 0], inv * P.xyz[3 * pix + 1], inv * P.xyz[3 * pix + 2]));
+    if (P.out_lin) { P.out_lin[3 * pix + 0] = o.lin.x; P.out_lin[3 * pix + 1] = o.lin.y; P.out_lin[3 * pix + 2] = o.lin.z; }
+    if (P.out_q) { P.out_q[3 * pix + 0] = o.q.x; P.out_q[3 * pix + 1] = o.q.y; P.out_q[3 * pix + 2] = o.q.z; }
+}
+
 }  // namespace
 
 uint32_t develop_padded_channels(uint32_t channels) {
@@ -137,6 +155,14 @@ hipError_t launch_develop(const DevelopParams &p, hipStream_t st) {
 hipError_t launch_develop_srgb(const float *xyz, float *out_lin, float *out_q, uint32_t samples, size_t n, hipStream_t st) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(develop_srgb_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, xyz, out_lin, out_q, samples, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_develop_srgb_counts(const DevelopSrgbCountsParams &p, hipStream_t st) {
+    const size_t n = (size_t)p.w * p.h;
+    if (n == 0) return hipSuccess;
+    if (!p.counts || p.tx == 0 || p.ty == 0 || p.bx == 0 || (n + 255) / 256 > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(develop_srgb_counts_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, p);
     return hipGetLastError();
 }
 

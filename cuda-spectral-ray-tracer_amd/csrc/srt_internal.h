@@ -123,6 +123,10 @@ struct AccumHeader {
 // srt_accum_reset_features writes the two fields once.
 // Adaptive featured accumulations (MODE 8, srt_accum_reset_adaptive_features) read the adaptive fields and the featured fields together.
 // Spectral featured accumulations (MODE 9, srt_accum_reset_spectral_features) read `film` and the featured fields together.
+// Adaptive spectral accumulations (MODE 10, srt_accum_reset_adaptive_spectral) read the adaptive fields and `film` together.
+// Adaptive spectral featured accumulations (MODE 11, srt_accum_reset_adaptive_spectral_features) read the adaptive fields, `film` and
+// mat_col; their rows lie behind the film in the film's own allocation, features == film + n_lanes * kFilmStride, and the kernel derives
+// that address from `film` and n_lanes (LdsUniforms has no slot left for a fourth pointer).
 constexpr uint32_t kFeatureStride = 8;      // 32 B per pixel: two 16-byte accesses
 constexpr uint32_t kStreamSumPlane = 6;
 constexpr uint32_t kMaxStreams = 16;      // SRT_MAX_STREAMS (srt_c_api.h)
@@ -152,8 +156,10 @@ hipError_t launch_init_rng(uint32_t *rng, uint32_t n_lanes, uint64_t seed, hipSt
 struct PlanKnobs { bool wide_refs = false; int lds_cache_max = -1; };
 // The render launch's variant; the values are render_kernel's MODE template argument.  Plain: render; Counting: instrumented; Probe: cost
 // probe; Accum: accumulating render (p.wave_debug -> AccumHeader); Adaptive / Spectral / Streams / Features: adaptive / spectral / streamed /
-// featured accumulating render; AdaptiveFeatures: adaptive and featured at once; SpectralFeatures: spectral and featured at once.
-enum RenderMode { Plain = 0, Counting = 1, Probe = 2, Accum = 3, Adaptive = 4, Spectral = 5, Streams = 6, Features = 7, AdaptiveFeatures = 8, SpectralFeatures = 9 };
+// featured accumulating render; AdaptiveFeatures: adaptive and featured at once; SpectralFeatures: spectral and featured at once;
+// AdaptiveSpectral: adaptive and spectral at once; AdaptiveSpectralFeatures: all three.
+enum RenderMode { Plain = 0, Counting = 1, Probe = 2, Accum = 3, Adaptive = 4, Spectral = 5, Streams = 6, Features = 7, AdaptiveFeatures = 8, SpectralFeatures = 9, AdaptiveSpectral = 10,
+                  AdaptiveSpectralFeatures = 11 };
 hipError_t launch_render(const RenderParams &p, const PlanKnobs &knobs, uint32_t n_cu, RenderMode mode, hipStream_t st);
 hipError_t launch_accum_header(AccumHeader *dst, float *sums, uint32_t spp_total, hipStream_t st);      // writes *dst on the stream
 // Pixel queue of the next adaptive pass (see adapt_flag_kernel): the rows of `src_rows` (src_info[0] of them; nullptr: the identity
@@ -258,6 +264,17 @@ struct DenoisePayloadPrepassParams {
     uint32_t channels, groups, samples;
 };
 hipError_t launch_denoise_payload_prepass(const DenoisePayloadPrepassParams &p, hipStream_t st);
+// Its per-pixel-count sibling: pixel (x, y) of the row-major w x h rectangle is normalised by its own count, inv = 1.0f / (float)n_p with
+// n_p = counts[idx] & ~kAdaptConverged (> 0) and idx = block_linear_idx(x, y, tx, ty, bx), as DenoisePrepassParams::counts is read.
+struct DenoisePayloadPrepassCountsParams {
+    const float *developed;      // [pixel][channels], row-major pixels
+    float4 *payload;
+    const uint32_t *counts;
+    uint32_t tx, ty, bx;
+    uint32_t w, h;
+    uint32_t channels, groups;
+};
+hipError_t launch_denoise_payload_prepass_counts(const DenoisePayloadPrepassCountsParams &p, hipStream_t st);
 // One plain level (DenoiseLevelParams' fields mean what they mean there) that also filters the payload psrc -> pdst (never the same
 // buffer) with the colour's weights.
 struct DenoiseLevelDevParams {
@@ -291,6 +308,16 @@ uint32_t develop_padded_channels(uint32_t channels);      // the kernel variant'
 hipError_t launch_develop(const DevelopParams &p, hipStream_t st);
 // n pixels of three developed XYZ sums over `samples` samples -> out_lin / out_q (either may be null), three floats per pixel each.
 hipError_t launch_develop_srgb(const float *xyz, float *out_lin, float *out_q, uint32_t samples, size_t n, hipStream_t st);
+// Its per-pixel-count sibling (an adaptive spectral accumulation): pixel (x, y) of the row-major w x h rectangle is normalised by its own
+// count n_p = counts[idx] & ~kAdaptConverged, idx = block_linear_idx(x, y, tx, ty, bx); a pixel without a sample (n_p == 0) by 1.
+struct DevelopSrgbCountsParams {
+    const float *xyz;
+    float *out_lin, *out_q;
+    const uint32_t *counts;
+    uint32_t tx, ty, bx;
+    uint32_t w, h;
+};
+hipError_t launch_develop_srgb_counts(const DevelopSrgbCountsParams &p, hipStream_t st);
 hipError_t launch_order_tiles(const uint32_t *cost, uint32_t *sorted, uint32_t *rows, uint32_t n, uint32_t n_waves,
                               uint32_t split_load_pct, uint32_t *queue_info, uint32_t order_max_pct, hipStream_t st);
 hipError_t launch_scatter(const ScatterParams &p, hipStream_t st);

@@ -36,6 +36,9 @@ struct LdsUniforms {
     // its rows stay in accum_film and its colour table goes to tile_cost, which only the cost probe (MODE 2) ever reads back.
     // MODE 9 (spectral + features) keeps the film in accum_film as MODE 5 does: its rows go to accum_sum2 (free: it is not adaptive)
     // and its colour table to tile_cost, as MODE 8's.
+    // MODE 10 (adaptive + spectral) borrows nothing: accum_sum2, accum_state and accum_film each hold what they were made for.  MODE 11
+    // (all three) has no slot for its rows: they lie behind the film, at film + n_lanes * kFilmStride, which the kernel forms from
+    // accum_film and n_lanes; the colour table goes to tile_cost, as MODE 8's and 9's.
 };
 static_assert(sizeof(LdsUniforms) <= kLdsUniF4 * 16, "uniform block too large");
 typedef __attribute__((address_space(3))) LdsUniforms lds_uniforms;

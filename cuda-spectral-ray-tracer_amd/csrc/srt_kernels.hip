@@ -188,6 +188,11 @@ __device__ __forceinline__ bool adaptive_converged(float s1, float s2, uint32_t 
 // MODE 9: MODE 5 and MODE 7 at once, a spectral featured accumulation (srt_accum_reset_spectral_features) -- the film deposit at every
 // path end and the first-hit deposit at bounce == 0, both verbatim.  Neither draws from the RNG and neither reads what the other writes:
 // image, sums, RNG state and film are MODE 5's bits, the rows MODE 7's.
+// MODE 10: MODE 4 and MODE 5 at once, an adaptive spectral accumulation (srt_accum_reset_adaptive_spectral) -- MODE 4 in every respect plus
+// MODE 5's film deposit, verbatim.  The deposit draws nothing from the RNG and the stopping rule reads nothing of the film: image, sums,
+// S2, state words and RNG state are MODE 4's bits; a pixel's film row is the row of a plain spectral frame of the samples the pixel holds,
+// and a converged pixel's row is never touched again (the pixel is skipped at the fetch).
+// MODE 11: MODE 10 plus MODE 7's first-hit deposit (srt_accum_reset_adaptive_spectral_features): the rows are MODE 8's bits.
 // ALL_CACHED: the whole inner tree fits the LDS cache (n_cached == n_inner): the INNER step has no global fall-back path.
 // PAIRED (instantiated for <., 1, 1> and <., 0, 0>): every FRINGE record holds two triangles (srt_scene_is_paired): the visit has no box test.
 template <int MODE, bool NARROW, bool ALL_CACHED, bool PAIRED>
@@ -195,15 +200,17 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
     constexpr bool COUNT = (MODE == 1);
     constexpr bool PROBE = (MODE == 2);
     constexpr bool ITERS = COUNT || PROBE;
-    constexpr bool ACCUM = (MODE == 3 || MODE == 4 || MODE == 5 || MODE == 7 || MODE == 8 || MODE == 9);
-    constexpr bool ADAPT = (MODE == 4 || MODE == 8);
-    constexpr bool FILM = (MODE == 5 || MODE == 9);
+    constexpr bool ACCUM = (MODE == 3 || MODE == 4 || MODE == 5 || MODE == 7 || MODE == 8 || MODE == 9 || MODE == 10 || MODE == 11);
+    constexpr bool ADAPT = (MODE == 4 || MODE == 8 || MODE == 10 || MODE == 11);
+    constexpr bool FILM = (MODE == 5 || MODE == 9 || MODE == 10 || MODE == 11);
     constexpr bool STREAMS = (MODE == 6);
-    constexpr bool FEATURES = (MODE == 7 || MODE == 8 || MODE == 9);
+    constexpr bool FEATURES = (MODE == 7 || MODE == 8 || MODE == 9 || MODE == 11);
     // (S2 of the current pixel: in a register -- acc2 -- except in the wide-reference, partly-L2, unpaired shape, which is at the
     // 128-VGPR limit already and would spill it to scratch: there each path end adds its y * y to the pixel's own S2 word in memory.
     // The same additions in the same order: the result is the same bits.  profiles/adaptive/mode4_resource_usage.txt)
-    constexpr bool S2_MEM = ADAPT && !NARROW && !ALL_CACHED && !PAIRED;
+    // (With the film deposit compiled in -- MODE 10 and 11 -- the narrow all-cached shapes would spill acc2 as well: they take the same
+    // path.  profiles/adaptive_spectral/mode10_11_resource_usage.txt)
+    constexpr bool S2_MEM = ADAPT && ((!NARROW && !ALL_CACHED && !PAIRED) || (FILM && NARROW && ALL_CACHED));
     extern __shared__ float4 lds4[];
     lds_uniforms *U = (lds_uniforms *)lds4;
     float4 *s_cmf = lds4 + kLdsUniF4;
@@ -248,8 +255,9 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
         if constexpr (FEATURES) {      // (the uniform block is full: MODE 7 alone borrows the pointer slots of MODE 4 and MODE 5 for its two)
             const AccumHeader *ah = reinterpret_cast<const AccumHeader *>(P.wave_debug);
             // (MODE 9 keeps the film in accum_film: its rows go to accum_sum2, which only an adaptive launch needs for S2)
-            if constexpr (FILM) split_ptr(ah->features, U->accum_sum2);
-            else split_ptr(ah->features, U->accum_film);
+            // (MODE 11 has no slot left for its rows: they lie behind the film in the film's allocation, at film + n_lanes * kFilmStride)
+            if constexpr (FILM && !ADAPT) split_ptr(ah->features, U->accum_sum2);
+            else if constexpr (!FILM) split_ptr(ah->features, U->accum_film);
             // (MODE 8 needs accum_sum2 for S2, MODE 9 for the rows: their colour table goes to tile_cost, which only the probe reads -- LdsUniforms)
             if constexpr (ADAPT || FILM) split_ptr(ah->mat_col, U->tile_cost);
             else split_ptr(ah->mat_col, U->accum_sum2);
@@ -426,9 +434,11 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
                         // for it.  The colour comes through a range-checked buffer load: a material index beyond the table adds +0.
                         if (bounce == 0u) {
                             // (the two pointers are wave-uniform: read through readfirstlane, the descriptor is built in scalar registers)
-                            const uint32_t rows_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(FILM ? U->accum_sum2[0] : U->accum_film[0])), rows_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(FILM ? U->accum_sum2[1] : U->accum_film[1]));
+                            const uint32_t rows_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)((FILM && !ADAPT) ? U->accum_sum2[0] : U->accum_film[0])), rows_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)((FILM && !ADAPT) ? U->accum_sum2[1] : U->accum_film[1]));
                             const uint32_t col_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)((ADAPT || FILM) ? U->tile_cost[0] : U->accum_sum2[0])), col_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)((ADAPT || FILM) ? U->tile_cost[1] : U->accum_sum2[1]));
                             float4 *row = join_ptr<float4>(rows_lo, rows_hi) + (size_t)idx * (kFeatureStride / 4u);
+                            // (MODE 11: rows_lo / rows_hi are the film's, and the rows begin behind its n_lanes rows -- 16-byte aligned, as kFilmStride % 4 == 0)
+                            if constexpr (FILM && ADAPT) row += (size_t)U->n_lanes * (kFilmStride / 4u);
                             const buf_rsrc col_rsrc = make_rsrc(join_ptr<const float>(col_lo, col_hi), P.n_materials * 16u);
                             const uint32_t col_off = (mat < P.n_materials ? mat : P.n_materials) * 16u;
                             // (one half of the row after the other, each with the part of the colour it needs: the wide / partly-cached /
@@ -1225,7 +1235,7 @@ hipError_t launch_render(const RenderParams &p, const PlanKnobs &knobs, uint32_t
     const bool narrow = render_narrow_refs(p.n_records, knobs);
     if (mode == 1) return narrow ? launch_render_mode<1, true>(p, knobs, n_cu, st) : launch_render_mode<1, false>(p, knobs, n_cu, st);
     if (mode == 2) return narrow ? launch_render_mode<2, true>(p, knobs, n_cu, st) : launch_render_mode<2, false>(p, knobs, n_cu, st);
-    if (mode < 3 || mode > 9) return narrow ? launch_render_mode<0, true>(p, knobs, n_cu, st) : launch_render_mode<0, false>(p, knobs, n_cu, st);
+    if (mode < 3 || mode > 11) return narrow ? launch_render_mode<0, true>(p, knobs, n_cu, st) : launch_render_mode<0, false>(p, knobs, n_cu, st);
     // (instantiated after the production variants: their place in the object, and so the labels of their ISA listing, stay as they were)
     if (mode == 3) return narrow ? launch_render_mode<3, true>(p, knobs, n_cu, st) : launch_render_mode<3, false>(p, knobs, n_cu, st);
     // (and the adaptive ones after the accumulating ones, the spectral ones after those, for the same reason)
@@ -1234,7 +1244,9 @@ hipError_t launch_render(const RenderParams &p, const PlanKnobs &knobs, uint32_t
     if (mode == 6) return narrow ? launch_render_mode<6, true>(p, knobs, n_cu, st) : launch_render_mode<6, false>(p, knobs, n_cu, st);
     if (mode == 7) return narrow ? launch_render_mode<7, true>(p, knobs, n_cu, st) : launch_render_mode<7, false>(p, knobs, n_cu, st);
     if (mode == 8) return narrow ? launch_render_mode<8, true>(p, knobs, n_cu, st) : launch_render_mode<8, false>(p, knobs, n_cu, st);
-    return narrow ? launch_render_mode<9, true>(p, knobs, n_cu, st) : launch_render_mode<9, false>(p, knobs, n_cu, st);
+    if (mode == 9) return narrow ? launch_render_mode<9, true>(p, knobs, n_cu, st) : launch_render_mode<9, false>(p, knobs, n_cu, st);
+    if (mode == 10) return narrow ? launch_render_mode<10, true>(p, knobs, n_cu, st) : launch_render_mode<10, false>(p, knobs, n_cu, st);
+    return narrow ? launch_render_mode<11, true>(p, knobs, n_cu, st) : launch_render_mode<11, false>(p, knobs, n_cu, st);
 }
 
 hipError_t launch_order_tiles(const uint32_t *cost, uint32_t *sorted, uint32_t *rows, uint32_t n, uint32_t n_waves,

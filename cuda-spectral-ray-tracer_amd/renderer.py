@@ -127,7 +127,8 @@ class Renderer:
 
     def accum_reset_spectral(self):
         """start a SPECTRAL accumulation (srt_c_api.h): like accum_reset, and each later pass also adds every path's seven powers to
-        the pixel's film, 95 raw float32 sums on the 5 nm CIE grid (read_spectral; spectral_radiance normalises them).  Never adaptive."""
+        the pixel's film, 95 raw float32 sums on the 5 nm CIE grid (read_spectral; spectral_radiance normalises them).  Never adaptive:
+        accum_reset_adaptive_spectral is the adaptive one."""
         self._ck(B.lib().srt_accum_reset_spectral(self._h))
 
     def read_spectral(self, image_width, image_height, first=0, count=FILM_SAMPLES, into=None):
@@ -202,8 +203,22 @@ class Renderer:
     def accum_reset_spectral_features(self):
         """start a SPECTRAL FEATURED accumulation (srt_c_api.h): accum_reset_spectral with the feature rows of accum_reset_features.
         Image, sums, RNG state and film are accum_reset_spectral's bit for bit, the rows accum_reset_features'.  read_spectral,
-        develop_spectral, read_features, denoise and denoise_vg all work on it, and denoise_developed needs it.  Never adaptive."""
+        develop_spectral, read_features, denoise and denoise_vg all work on it, and denoise_developed needs it.  Never adaptive:
+        accum_reset_adaptive_spectral_features is the adaptive one."""
         self._ck(B.lib().srt_accum_reset_spectral_features(self._h))
+
+    def accum_reset_adaptive_spectral(self, rel_tol, abs_tol=0.0, min_spp=16):
+        """start an ADAPTIVE SPECTRAL accumulation (srt_c_api.h): accum_reset_adaptive (same arguments, same stopping rule) with the film of
+        accum_reset_spectral.  Image, sums, sample map, active counts and RNG state are accum_reset_adaptive's bit for bit; a pixel's film
+        row belongs to the samples that pixel holds (spectral_radiance(film, samples map)), and a converged pixel's row is never touched
+        again.  accum_active, accum_stats, read_spectral and develop_spectral take it; develop_spectral_srgb divides a pixel by its own count."""
+        self._ck(B.lib().srt_accum_reset_adaptive_spectral(self._h, C.byref(adaptive_config(rel_tol, abs_tol, min_spp))))
+
+    def accum_reset_adaptive_spectral_features(self, rel_tol, abs_tol=0.0, min_spp=16):
+        """start an ADAPTIVE SPECTRAL FEATURED accumulation (srt_c_api.h): accum_reset_adaptive_spectral with the feature rows of
+        accum_reset_adaptive_features, which they equal bit for bit.  read_features, denoise, denoise_vg and denoise_mv take it as they
+        take accum_reset_adaptive_features', and denoise_developed divides colour, guides and developed planes of a pixel by its own count."""
+        self._ck(B.lib().srt_accum_reset_adaptive_spectral_features(self._h, C.byref(adaptive_config(rel_tol, abs_tol, min_spp))))
 
     def read_features(self, image_width, image_height):
         """raw first-hit sums of the featured accumulation's chunk, float32: dict(normal (H, W, 3), albedo (H, W, 3), distance (H, W),
@@ -266,6 +281,30 @@ class Renderer:
         xyz = np.zeros(sums.shape, np.float32)
         self._ck(B.lib().srt_denoise_developed_kat(self._h, C.byref(c), B.fptr(sums), B.fptr(rows), B.fptr(planes), planes.shape[2], int(samples),
                                                    sums.shape[1], sums.shape[0], B.fptr(dev), B.fptr(xyz)))
+        return dev, xyz
+
+    def denoise_developed_counts_kat(self, xyz_sums, features, developed, samples, **cfg):
+        """denoise_developed_kat with a per-pixel sample map (srt_denoise_developed_counts_kat): samples (h, w) whole numbers >= 1, the
+        count each pixel's sums hold -- the kernels an adaptive spectral featured accumulation runs.  Shapes and map are checked here
+        (ValueError)."""
+        c = denoise_config(**cfg)
+        sums = np.ascontiguousarray(xyz_sums, np.float32)
+        rows = np.ascontiguousarray(features, np.float32)
+        planes = np.ascontiguousarray(developed, np.float32)
+        if sums.ndim != 3 or sums.shape[2] != 3 or rows.shape != sums.shape[:2] + (FEATURE_CHANNELS,):
+            raise ValueError("denoise_developed_counts_kat: needs xyz_sums (h, w, 3) and features (h, w, %d), got %r and %r" % (FEATURE_CHANNELS, sums.shape, rows.shape))
+        if planes.ndim != 3 or planes.shape[:2] != sums.shape[:2] or not 1 <= planes.shape[2] <= MAX_DEVELOP_CHANNELS:
+            raise ValueError("denoise_developed_counts_kat: needs developed (h, w, K) with 1 <= K <= %d over the same pixels, got %r" % (MAX_DEVELOP_CHANNELS, planes.shape))
+        raw = np.asarray(samples)
+        if raw.dtype == np.bool_ or not np.issubdtype(raw.dtype, np.integer) or raw.shape != sums.shape[:2]:
+            raise ValueError("denoise_developed_counts_kat: samples must be whole numbers of shape %r, got %s %r" % (sums.shape[:2], raw.dtype, raw.shape))
+        if raw.size and (int(raw.min()) < 1 or int(raw.max()) > 0x7fffffff):
+            raise ValueError("denoise_developed_counts_kat: every pixel must hold between 1 and 2^31 - 1 samples")
+        counts = np.ascontiguousarray(raw, np.uint32)
+        dev = np.zeros(planes.shape, np.float32)
+        xyz = np.zeros(sums.shape, np.float32)
+        self._ck(B.lib().srt_denoise_developed_counts_kat(self._h, C.byref(c), B.fptr(sums), B.fptr(rows), B.fptr(planes), planes.shape[2],
+                                                          counts.ctypes.data_as(C.POINTER(C.c_uint32)), sums.shape[1], sums.shape[0], B.fptr(dev), B.fptr(xyz)))
         return dev, xyz
 
     def denoise_last_ms(self):
@@ -602,6 +641,15 @@ class Comm:
         """Renderer.accum_reset_spectral_features on every local rank; film and rows stay with their ranks, as for accum_reset_spectral
         and accum_reset_features"""
         self._ck(B.lib().srt_comm_accum_reset_spectral_features(self._h))
+
+    def accum_reset_adaptive_spectral(self, rel_tol, abs_tol=0.0, min_spp=16):
+        """Renderer.accum_reset_adaptive_spectral on every local rank (single-process communicators only); the films stay with their ranks"""
+        self._ck(B.lib().srt_comm_accum_reset_adaptive_spectral(self._h, C.byref(adaptive_config(rel_tol, abs_tol, min_spp))))
+
+    def accum_reset_adaptive_spectral_features(self, rel_tol, abs_tol=0.0, min_spp=16):
+        """Renderer.accum_reset_adaptive_spectral_features on every local rank (single-process communicators only); films and rows stay
+        with their ranks"""
+        self._ck(B.lib().srt_comm_accum_reset_adaptive_spectral_features(self._h, C.byref(adaptive_config(rel_tol, abs_tol, min_spp))))
 
     def accum_reset_streams(self, k):
         """Renderer.accum_reset_streams on every local rank (any communicator: no decision crosses ranks)"""
@@ -1171,5 +1219,48 @@ def _adaptive_denoised_passes(scene, cam, width, height, bounce_limit, acfg, sch
             out["samples"] = r.accum_stats(width, height)["samples"]
             den = r.denoise_mv(width, height, **cfg) if variance == "measured" else r.denoise_vg(width, height, **cfg) if variance == "spatial" else r.denoise(width, height, **cfg)
             yield r.accum_samples, active, out, r.read_features(width, height), den
+            if active == 0:
+                break
+
+
+def render_adaptive_spectral(scene, cam, width, height, bounce_limit, rel_tol, abs_tol=0.0, min_spp=16, step=16, max_spp=1024, features=False,
+                             response=None, filter=None, scale=None, seed=1984, device=0, renderer=None, **cfg):
+    """render_adaptive on an adaptive spectral accumulation: a generator of (spp_total, active_pixels, result, radiance) after every pass
+    -- result is render_adaptive's bit for bit (`samples` included) and radiance spectral_radiance(film, result["samples"]), (H, W, 95):
+    every pixel's film divided by the samples that pixel holds.  features=True runs the adaptive spectral featured accumulation and yields
+    two more items, `developed` (Renderer.develop_spectral's (H, W, K) sums) and `denoised` (the dict of Renderer.denoise_developed;
+    response, filter and scale as render_developed_denoised, cfg: the keywords of denoise_config).  Without features there is nothing to
+    develop for: response, filter, scale and cfg must be left alone.  Stops as render_adaptive stops.  The arguments are checked here,
+    before any device is touched."""
+    acfg = adaptive_config(rel_tol, abs_tol, min_spp)
+    sched = adaptive_schedule(min_spp, step, max_spp)
+    if not isinstance(features, (bool, np.bool_)):
+        raise ValueError("render_adaptive_spectral: features must be True or False, got %r" % (features,))
+    resp, s = None, None
+    if features:
+        resp = sensor_response(cie_response() if response is None else response, filter)
+        s = (CIE_SCALE if response is None else 1.0) if scale is None else _develop_scale(scale)
+        denoise_config(**cfg)
+    elif response is not None or filter is not None or scale is not None or cfg:
+        raise ValueError("render_adaptive_spectral: response, filter, scale and the denoiser's keywords need features=True")
+    return _adaptive_spectral_passes(scene, cam, width, height, bounce_limit, acfg, sched, seed, device, renderer, bool(features), resp, s, cfg)
+
+
+def _adaptive_spectral_passes(scene, cam, width, height, bounce_limit, acfg, sched, seed, device, renderer, features, resp, scale, cfg):
+    with _image_session(scene, cam, width, height, sum(sched), bounce_limit, seed, device, renderer) as r:
+        reset = B.lib().srt_accum_reset_adaptive_spectral_features if features else B.lib().srt_accum_reset_adaptive_spectral
+        r._ck(reset(r._h, C.byref(acfg)))      # (after the session has set the planes)
+        for spp_add in sched:
+            r.render_chunk_accum(width, height, spp_add)
+            r.scatter_tiles()
+            active = r.accum_active
+            out = _collect(r, width, height)
+            out["samples"] = r.accum_stats(width, height)["samples"]
+            radiance = spectral_radiance(r.read_spectral(width, height), out["samples"].reshape(height, width))
+            if features:
+                dev = r.develop_spectral(width, height, resp, scale)
+                yield r.accum_samples, active, out, radiance, dev, r.denoise_developed(width, height, resp, scale, **cfg)
+            else:
+                yield r.accum_samples, active, out, radiance
             if active == 0:
                 break

@@ -300,8 +300,9 @@ SRT_API int srt_read_accum_stats(srt_ctx *ctx, uint32_t *samples, float *sum_y, 
  *   srt_accum_reset_spectral  srt_accum_reset + a zeroed film (allocated on first use and when n_lanes changes, kFilmStride = 96 floats
  *                             = 384 B per lane of the grid).  Later srt_render_chunk_accum passes run MODE 5.  An instrumented context:
  *                             SRT_ERR_UNSUPPORTED; device parameters not set: SRT_ERR_INVALID; a failed allocation: SRT_ERR_HIP -- in
- *                             every refusal the previous accumulation is unchanged.  Always a PLAIN (non-adaptive) accumulation:
- *                             adaptive + spectral is not supported.  (Spectral + features is an accumulation kind of its own:
+ *                             every refusal the previous accumulation is unchanged.  Always a PLAIN (non-adaptive) accumulation.
+ *                             (This sentence used to go on "adaptive + spectral is not supported": it is now, as an accumulation kind of
+ *                             its own -- srt_accum_reset_adaptive_spectral, below.  Spectral + features is another:
  *                             srt_accum_reset_spectral_features, below.)  srt_accum_reset and srt_accum_reset_adaptive make the next
  *                             accumulation non-spectral again.  Invalidation, the 65535-sample limit and the chunk binding are those of
  *                             srt_accum_reset; srt_get_stats after a spectral pass reports that pass.
@@ -436,6 +437,38 @@ SRT_API int srt_accum_reset_adaptive_features(srt_ctx *ctx, const srt_adaptive *
  *                             something else again. */
 SRT_API int srt_accum_reset_spectral_features(srt_ctx *ctx);
 
+/* Adaptive sampling of the spectral film (no reference counterpart).  The film deposit is the most expensive thing a pass does per path
+ * end, and adaptive sampling is what stops spending samples on pixels that have converged.  An ADAPTIVE SPECTRAL accumulation is an
+ * adaptive accumulation (srt_accum_reset_adaptive: the same cfg, the same stopping rule on Y, the same state words and sample map) that
+ * also keeps the film of srt_accum_reset_spectral (the same deposit rule); an ADAPTIVE SPECTRAL FEATURED accumulation keeps the feature
+ * rows of srt_accum_reset_features as well.  Later srt_render_chunk_accum passes run render_kernel MODE 10 / MODE 11: MODE 4 with MODE 5's
+ * deposit (and MODE 7's) compiled in, no new code in the hot loops (MODE 11's first-hit deposit adds one offset to its row address).  The
+ * deposits draw nothing from the RNG and the stopping rule reads neither film nor rows.  What holds, and is tested, under the same cfg, seed and pass schedule:
+ *   - the image, all nine planes, the XYZ sums, S2, the state words, the sample map, the active counts, srt_get_stats' paths and the RNG
+ *     state are bit-identical to an adaptive accumulation's (MODE 4);
+ *   - a pixel that stopped after n samples holds the film row of a plain spectral n-spp frame at that pixel, bit for bit; an active pixel
+ *     holds the row of the running total; a converged pixel's film row is never touched again;
+ *   - in the featured kind the eight feature sums are bit-identical to an adaptive featured accumulation's (MODE 8);
+ *   - none of this depends on launch shape, partition, world size, chunk offset or the split into passes.
+ *   srt_accum_reset_adaptive_spectral           validation, refusals and invalidation are srt_accum_reset_adaptive's (cfg as there; an
+ *   srt_accum_reset_adaptive_spectral_features  instrumented context: SRT_ERR_UNSUPPORTED; device parameters not set: SRT_ERR_INVALID;
+ *                             srt_set_gather_planes ends the accumulation); a failed allocation: SRT_ERR_HIP.  Every refusal leaves the
+ *                             previous accumulation unchanged.  Buffers: the adaptive planes, the film (384 B per lane) and, featured,
+ *                             the rows (32 B per lane; they live behind the film in the film's allocation).  The accumulation is adaptive
+ *                             AND spectral (AND featured): srt_accum_active, srt_read_accum_stats, srt_read_spectral and
+ *                             srt_develop_spectral (which still returns SUMS) take both kinds; srt_read_features and srt_denoise_features /
+ *                             _vg / _mv take the featured kind as they take srt_accum_reset_adaptive_features', and refuse the other.
+ *                             srt_develop_spectral_srgb on either kind normalises each pixel by its own count, n = n_p = the samples
+ *                             field of the pixel's state word (a kernel of its own; a non-adaptive accumulation runs the kernel it
+ *                             always ran; a pixel of another rank, n_p = 0, has +0 sums and is normalised by 1).  srt_denoise_developed
+ *                             takes the featured kind: both prepasses use n_p,  d_p[k] = inv_p * D_p[k]  with  inv_p = 1.0f / (float)n_p
+ *                             (the payload's by a kernel of its own), and out_xyz stays srt_denoise_features' out_xyz on the same
+ *                             accumulation, bit for bit.  Every other srt_accum_reset* makes the next accumulation something else again;
+ *                             a plain spectral accumulation still refuses srt_accum_active, a plain adaptive one srt_read_spectral.
+ *                             Streams stay uncombined. */
+SRT_API int srt_accum_reset_adaptive_spectral(srt_ctx *ctx, const srt_adaptive *cfg);
+SRT_API int srt_accum_reset_adaptive_spectral_features(srt_ctx *ctx, const srt_adaptive *cfg);
+
 /* Edge-avoiding a-trous denoiser over the first-hit feature buffers (no reference counterpart; kernels in csrc/srt_denoise.hip).  It
  * consumes a FEATURED accumulation: the XYZ sums are filtered by `levels` passes of a 5x5 B3-spline stencil whose taps are weighted down
  * where normal, albedo, hit distance or the colour itself differ.  The filter, operation by operation -- everything fp32, not contracted,
@@ -560,7 +593,8 @@ SRT_API int srt_denoise_mv_kat(srt_ctx *ctx, const srt_denoise_vg *cfg, const fl
                                const uint32_t *samples, const float *sum_y2, uint32_t w, uint32_t h, float *out_xyz, float *out_var);
 
 /* The developed film, denoised: the plain a-trous filter of srt_denoise_features with a K-channel PAYLOAD (kernels in
- * csrc/srt_denoise.hip behind the others).  It needs a SPECTRAL FEATURED accumulation (srt_accum_reset_spectral_features): the film is
+ * csrc/srt_denoise.hip behind the others).  It needs a SPECTRAL FEATURED accumulation (srt_accum_reset_spectral_features, or the adaptive
+ * srt_accum_reset_adaptive_spectral_features, on which n below is the pixel's own count n_p in both prepasses): the film is
  * developed through K response curves, and the K planes ride through the levels on the weights the XYZ colour and the guides produce.
  * Operation by operation -- everything fp32, not contracted, left to right; the restatement is tests/denoise_developed_reference.py:
  *   Develop:  D_p[k], k = 0 .. K-1, is the contraction stated at srt_develop_spectral (the same kernel): response[K][95], channels = K
@@ -590,12 +624,20 @@ SRT_API int srt_denoise_mv_kat(srt_ctx *ctx, const srt_denoise_vg *cfg, const fl
  *                         features[h][w][8] and developed[h][w][K] (the planes D, sums over `samples` samples: no develop runs);
  *                         out_dev[h][w][K] and out_xyz[h][w][3], either may be NULL, not both.  Needs neither a scene nor an
  *                         accumulation and touches neither.  SRT_ERR_INVALID for a null input, a cfg as above, channels == 0 or >
- *                         SRT_MAX_DEVELOP_CHANNELS, samples == 0, an empty image or w x h >= 2^31. */
+ *                         SRT_MAX_DEVELOP_CHANNELS, samples == 0, an empty image or w x h >= 2^31.
+ *   srt_denoise_developed_counts_kat  the same with a per-pixel sample map samples[h][w] (each >= 1; bit 31 is ignored, as in a state
+ *                         word) in the place of the scalar: the kernels an adaptive spectral featured accumulation runs -- both
+ *                         per-pixel-count prepasses, the same levels and output kernels.  With a constant map it equals
+ *                         srt_denoise_developed_kat bit for bit.  Checks as srt_denoise_developed_kat's, and as srt_denoise_mv_kat's for
+ *                         the map: a null map or a zero in it is SRT_ERR_INVALID. */
 SRT_API int srt_denoise_developed(srt_ctx *ctx, const srt_denoise *cfg, const float *response, uint32_t channels, float scale,
                                   float *out_dev, float *out_xyz, uint32_t image_width, uint32_t image_height);
 SRT_API int srt_denoise_developed_kat(srt_ctx *ctx, const srt_denoise *cfg, const float *xyz_sums, const float *features,
                                       const float *developed, uint32_t channels, uint32_t samples, uint32_t w, uint32_t h,
                                       float *out_dev, float *out_xyz);
+SRT_API int srt_denoise_developed_counts_kat(srt_ctx *ctx, const srt_denoise *cfg, const float *xyz_sums, const float *features,
+                                             const float *developed, uint32_t channels, const uint32_t *samples, uint32_t w, uint32_t h,
+                                             float *out_dev, float *out_xyz);
 
 /* Sample-parallel pixels (no reference counterpart; a deliberate departure from its one RNG stream per pixel, so opt-in).  A STREAMED
  * accumulation gives every pixel K independent RNG streams, each with its own state and its own XYZ sum, so that any lane of any wave
@@ -807,6 +849,10 @@ SRT_API int srt_comm_accum_reset_adaptive_features(srt_comm *comm, const srt_ada
 /* srt_accum_reset_spectral_features on every local rank (any communicator: no decision crosses ranks); film and rows stay with their
  * ranks, as for srt_comm_accum_reset_spectral and srt_comm_accum_reset_features.  There is no srt_comm denoise: a gathered denoise is out of scope. */
 SRT_API int srt_comm_accum_reset_spectral_features(srt_comm *comm);
+/* srt_accum_reset_adaptive_spectral / _features on every local rank; like srt_comm_accum_reset_adaptive, SRT_ERR_UNSUPPORTED on a
+ * process-per-GPU communicator.  Film and rows stay with their ranks; srt_comm_accum_active sums the active pixels. */
+SRT_API int srt_comm_accum_reset_adaptive_spectral(srt_comm *comm, const srt_adaptive *cfg);
+SRT_API int srt_comm_accum_reset_adaptive_spectral_features(srt_comm *comm, const srt_adaptive *cfg);
 /* Sample-parallel pixels on W GPUs: srt_accum_reset_streams on every local context; srt_render_frame_multi_accum then runs MODE 6 on each
  * rank.  On process-per-GPU communicators too: no decision crosses ranks (every rank resets with the same K). */
 SRT_API int srt_comm_accum_reset_streams(srt_comm *comm, uint32_t streams);

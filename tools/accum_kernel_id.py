@@ -19,10 +19,10 @@ def name(key):
 
 
 def main(argv):
-    here = (K.render_code_hashes(K.LIB), K.render_listing_hashes(K.ISA))
+    here = (K.render_code_hashes(K.LIB, K.RENDER_ALL), K.render_listing_hashes(K.ISA, K.RENDER_ALL))
     other = None
     if len(argv) == 3 and argv[0] == "--against":
-        other = (K.render_code_hashes(argv[1]), K.render_listing_hashes(argv[2]))
+        other = (K.render_code_hashes(argv[1], K.RENDER_ALL), K.render_listing_hashes(argv[2], K.RENDER_ALL))
     differ = 0
     for kind, k in (("code", 0), ("listing", 1)):
         for key in sorted(here[k]):

@@ -26,14 +26,17 @@ OBJ = os.path.join(ROOT, "cuda-spectral-ray-tracer_amd", "csrc", "_build", "srt_
 LIB = os.path.join(ROOT, "cuda-spectral-ray-tracer_amd", "libsrt_hip.so")
 
 
-# render_kernel<MODE, NARROW, ALL_CACHED[, PAIRED]> of all ten modes, as a symbol of the code object and (followed by ':') as a label
+# render_kernel<MODE, NARROW, ALL_CACHED[, PAIRED]> of the one-digit modes 0 .. 9, as a symbol of the code object and (followed by ':') as a label
 # of the listing (PAIRED is round 5's fourth template argument; listings / libraries of earlier rounds have three)
 RENDER = re.compile(r"_ZN3srt13render_kernelILi([0-9])ELb([01])ELb([01])E(?:Lb([01])E)?EEv\w*")
+# ... and of the two-digit modes as well (MODE 10, 11).  The functions below keep RENDER as their default: what they return without an
+# argument is the set of kernels the suites written before MODE 10 count and compare (tools/accum_kernel_id.py asks for RENDER_ALL).
+RENDER_ALL = re.compile(r"_ZN3srt13render_kernelILi(\d+)ELb([01])ELb([01])E(?:Lb([01])E)?EEv\w*")
 
 
-def _render_key(name):
+def _render_key(name, pattern=RENDER):
     """(mode, narrow, all_cached, paired) of a render kernel's mangled name, None for any other name"""
-    m = RENDER.fullmatch(name)
+    m = pattern.fullmatch(name)
     return m and tuple(int(g or 0) for g in m.groups())
 
 
@@ -109,14 +112,14 @@ def gfx950_functions(lib):
         pos = data.find(BUNDLE_MAGIC, pos + 1)
 
 
-def render_code_hashes(lib=LIB):
+def render_code_hashes(lib=LIB, pattern=RENDER):
     """{(mode, narrow, all_cached, paired): sha256 of the kernel's position-independent machine code} for every render kernel of a
     built library; {} when the file is missing or holds no gfx950 code object with them"""
-    return {_render_key(name): hashlib.sha256(position_independent(code)).hexdigest()
-            for name, code in gfx950_functions(lib) if _render_key(name)}
+    return {_render_key(name, pattern): hashlib.sha256(position_independent(code)).hexdigest()
+            for name, code in gfx950_functions(lib) if _render_key(name, pattern)}
 
 
-def render_listing_hashes(path=ISA):
+def render_listing_hashes(path=ISA, pattern=RENDER):
     """{(mode, narrow, all_cached, paired): sha256} over the body (label .. s_endpgm, comments and file / ident / loc directives
     removed) of every render kernel in an ISA listing.  Empty when the listing is missing."""
     out, h, key = {}, None, None
@@ -125,7 +128,7 @@ def render_listing_hashes(path=ISA):
     for line in open(path, errors="replace"):
         if h is None:
             label, colon, _ = line.partition(":")
-            key = colon and _render_key(label)
+            key = colon and _render_key(label, pattern)
             if not key:
                 continue
             h = hashlib.sha256()
