@@ -65,6 +65,28 @@ class DenoiseVG(C.Structure):
                 ("sigma_depth", C.c_float), ("variance_floor", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
+class Meter(C.Structure):
+    """srt_meter: the metered rectangle (all zero: the whole chunk), the percentile, the key it is anchored at and the gain clamps (srt_c_api.h)"""
+    _fields_ = [("x0", C.c_uint32), ("y0", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32), ("percentile_ppm", C.c_uint32),
+                ("key", C.c_float), ("gain_min", C.c_float), ("gain_max", C.c_float), ("reserved", C.c_uint32 * 4)]
+
+
+class MeterResult(C.Structure):
+    """srt_meter_result: the pixel counts of a metering, the reference bin, its midpoint luminance and the gain decided (srt_c_api.h)"""
+    _fields_ = [("metered", C.c_uint64), ("dark", C.c_uint64), ("nonfinite", C.c_uint64), ("bin_ref", C.c_uint32),
+                ("y_ref", C.c_float), ("gain", C.c_float), ("reserved", C.c_uint32)]
+
+
+class Tone(C.Structure):
+    """srt_tone: the tone curve (0 linear, 1 extended Reinhard), the exposure gain and the white point (srt_c_api.h)"""
+    _fields_ = [("curve", C.c_uint32), ("gain", C.c_float), ("white", C.c_float), ("reserved", C.c_uint32 * 5)]
+
+
+class ToneResult(C.Structure):
+    """srt_tone_result: the pixels the tone kernel counted as blown, crushed and non-finite (srt_c_api.h)"""
+    _fields_ = [("blown", C.c_uint64), ("crushed", C.c_uint64), ("nonfinite", C.c_uint64)]
+
+
 class TreeTuning(C.Structure):
     """srt_tree_tuning: what srt_tune_tree_for_throughput found and did (srt_c_api.h)"""
     _fields_ = [("pixels_per_lane", C.c_double), ("throughput_bound", C.c_uint32), ("reinsertion", C.c_uint32),
@@ -79,6 +101,7 @@ class TileScheduleInfo(C.Structure):
 
 
 assert C.sizeof(Denoise) == 32 and C.sizeof(DenoiseVG) == 32
+assert C.sizeof(Meter) == 48 and C.sizeof(MeterResult) == 40 and C.sizeof(Tone) == 32 and C.sizeof(ToneResult) == 24
 assert C.sizeof(Adaptive) == 16 and C.sizeof(TreeTuning) == 40 and C.sizeof(TileScheduleInfo) == 32
 assert C.sizeof(Material) == 428 and C.sizeof(CameraData) == 84 and C.sizeof(TriIn) == 44
 
@@ -141,6 +164,12 @@ PROTOTYPES = {
     "srt_develop_spectral_srgb": (_i, [_vp, _fp, _f, _fp, _fp, _fp, _u32, _u32]),
     "srt_develop_kat": (_i, [_vp, _fp, _u32, _fp, _u32, _f, _fp]),
     "srt_develop_last_ms": (_i, [_vp, _fp, _fp]),
+    "srt_meter_decide": (_i, [C.POINTER(_u32), C.POINTER(Meter), C.POINTER(MeterResult)]),
+    "srt_meter_accum": (_i, [_vp, C.POINTER(Meter), C.POINTER(_u32), C.POINTER(MeterResult)]),
+    "srt_meter_kat": (_i, [_vp, C.POINTER(Meter), _fp, _u32, _u32, C.POINTER(_u32), C.POINTER(MeterResult)]),
+    "srt_expose_accum": (_i, [_vp, C.POINTER(Tone), _fp, _fp, _fp, C.POINTER(ToneResult), _u32, _u32]),
+    "srt_expose_kat": (_i, [_vp, C.POINTER(Tone), _fp, _u32, _u32, _fp, _fp, _fp, C.POINTER(ToneResult)]),
+    "srt_expose_last_ms": (_i, [_vp, _fp, _fp]),
     "srt_accum_reset_features": (_i, [_vp]),
     "srt_read_features": (_i, [_vp, _fp, _u32, _u32]),
     "srt_accum_reset_adaptive_features": (_i, [_vp, C.POINTER(Adaptive)]),

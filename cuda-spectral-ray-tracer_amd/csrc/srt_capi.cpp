@@ -150,6 +150,11 @@ struct srt_ctx {
     DeviceBuffer d_develop_in;                          // srt_develop_kat: the caller's film in 96-float rows
     hipEvent_t develop_ev[3] = {};                      // around the kernels of the last develop: contraction | sRGB epilogue (created on first use)
     bool develop_timed = false, develop_epilogue = false;
+    DeviceBuffer d_expose;                              // metering and tone mapping: the global histogram and the counters (ExposeLayout)
+    DeviceBuffer d_expose_in;                           // srt_meter_kat / srt_expose_kat: the caller's XYZ means
+    DeviceBuffer d_expose_out;                          // the tone kernel's three row-major images, grown when the rectangle grows
+    hipEvent_t expose_ev[4] = {};                       // around the last meter kernel [0, 1] and the last tone kernel [2, 3] (created on first use)
+    bool meter_timed = false, tone_timed = false;
     DeviceBuffer d_streams;                             // sample-parallel pixels (srt_accum_reset_streams, StreamPlanes)
     uint32_t streams_seeded = 0;                        // the K whose RNG streams d_streams holds, seeded since the last srt_init_device_params (0: none)
 };
@@ -608,6 +613,7 @@ void srt_destroy(srt_ctx *c) {
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (hipEvent_t e : c->denoise_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->develop_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->expose_ev) if (e) (void)hipEventDestroy(e);
     delete c;      // (every DeviceBuffer frees itself, on the device selected above)
 }
 
@@ -1327,6 +1333,257 @@ int srt_develop_last_ms(srt_ctx *c, float *contract_ms, float *epilogue_ms) {
     ms = 0.0f;
     if (c->develop_epilogue) HIP_TRY(c, hipEventElapsedTime(&ms, c->develop_ev[1], c->develop_ev[2]));
     if (epilogue_ms) *epilogue_ms = ms;
+    return SRT_OK;
+}
+
+// ---- exposure metering and tone mapping (srt_expose.hip) --------------------------------------------------------------------------
+namespace {
+
+// d_expose: [histogram: kMeterBins words | meter counters: metered, dark, non-finite | tone counters: blown, crushed, non-finite (u64 each)]
+struct ExposeLayout {
+    uint32_t *hist;
+    unsigned long long *meter_counts, *tone_counts;
+    static constexpr size_t kBytes = kMeterBins * sizeof(uint32_t) + 6 * sizeof(unsigned long long);
+    explicit ExposeLayout(const DeviceBuffer &d) : hist(d.as<uint32_t>()), meter_counts(reinterpret_cast<unsigned long long *>(hist + kMeterBins)), tone_counts(meter_counts + 3) {}
+};
+// d_expose_out: [out_xyz | out_lin | out_q], three floats per pixel each
+struct ExposeImages {
+    float *img[3];
+    static size_t bytes(size_t pixels) { return 9 * pixels * sizeof(float); }
+    ExposeImages(const DeviceBuffer &d, size_t pixels) : img{d.as<float>(), d.as<float>() + 3 * pixels, d.as<float>() + 6 * pixels} {}
+};
+
+// everything of a srt_meter but where its rectangle lies (the chunk decides that)
+const char *meter_cfg_error(const srt_meter *m) {
+    if (m->percentile_ppm < 1 || m->percentile_ppm > 1000000u) return "percentile_ppm must be in 1 .. 1000000";
+    if (!std::isfinite(m->key) || !(m->key > 0.0f)) return "key must be finite and > 0";
+    if (!std::isfinite(m->gain_min) || !std::isfinite(m->gain_max) || !(m->gain_min > 0.0f) || !(m->gain_min <= m->gain_max)) return "needs 0 < gain_min <= gain_max, both finite";
+    for (const uint32_t r : m->reserved) if (r) return "the reserved words must be 0";
+    const bool whole = !m->x0 && !m->y0 && !m->w && !m->h;
+    if (!whole && (m->w == 0 || m->h == 0)) return "the rectangle must be all zero (the whole chunk) or non-empty";
+    return nullptr;
+}
+// ... and the rectangle against a chunk of chunk_w x chunk_h pixels; rect receives the rectangle to meter
+const char *meter_rect_error(const srt_meter *m, uint32_t chunk_w, uint32_t chunk_h, uint32_t rect[4]) {
+    if (!m->x0 && !m->y0 && !m->w && !m->h) { rect[0] = 0; rect[1] = 0; rect[2] = chunk_w; rect[3] = chunk_h; return nullptr; }
+    if ((uint64_t)m->x0 + m->w > chunk_w || (uint64_t)m->y0 + m->h > chunk_h) return "the rectangle must lie inside the chunk";
+    rect[0] = m->x0; rect[1] = m->y0; rect[2] = m->w; rect[3] = m->h;
+    return nullptr;
+}
+const char *tone_cfg_error(const srt_tone *t) {
+    if (t->curve > 1u) return "curve must be 0 (linear) or 1 (extended Reinhard)";
+    if (!std::isfinite(t->gain) || !(t->gain > 0.0f)) return "gain must be finite and > 0";
+    if (!(t->white > 0.0f)) return "white must be > 0 (+inf allowed)";
+    for (const uint32_t r : t->reserved) if (r) return "the reserved words must be 0";
+    return nullptr;
+}
+
+// the decision of srt_meter_decide on a validated cfg; dark and nonfinite of *out are not touched
+void meter_decide(const uint32_t *hist, const srt_meter *m, srt_meter_result *out) {
+    uint64_t n = 0;
+    for (uint32_t b = 16; b < 4080; b++) n += hist[b];
+    uint32_t bin_ref = 0;
+    float y_ref = 0.0f, g = 1.0f;
+    if (n) {
+        const uint64_t target = std::max<uint64_t>(1, (n * m->percentile_ppm + 999999u) / 1000000u);
+        uint64_t run = 0;
+        for (uint32_t b = 16; b < 4080; b++) {
+            run += hist[b];
+            if (run >= target) { bin_ref = b; break; }
+        }
+        const uint32_t word = (bin_ref << 19) | (1u << 18);
+        memcpy(&y_ref, &word, sizeof(y_ref));
+        g = m->key / y_ref;
+    }
+    g = g < m->gain_min ? m->gain_min : g;
+    g = g > m->gain_max ? m->gain_max : g;
+    out->metered = n; out->bin_ref = bin_ref; out->y_ref = y_ref; out->gain = g; out->reserved = 0;
+}
+
+// The meter kernel over the lanes described by p (hist and counts are filled in here), the copy of histogram and counters to the
+// host, the decision.  Synchronises.
+int run_meter(srt_ctx *c, const char *who, MeterParams p, const srt_meter *cfg, uint32_t *hist_out, srt_meter_result *result) {
+    if (const int rc = develop_reserve(c, who, c->d_expose, ExposeLayout::kBytes)) return rc;
+    const ExposeLayout L(c->d_expose);
+    c->meter_timed = false;
+    for (int k = 0; k < 2; k++) if (!c->expose_ev[k]) HIP_TRY_AS(c, who, hipEventCreate(&c->expose_ev[k]));
+    HIP_TRY_AS(c, who, hipMemsetAsync(L.hist, 0, kMeterBins * sizeof(uint32_t) + 3 * sizeof(unsigned long long), nullptr));
+    p.hist = L.hist; p.counts = L.meter_counts;
+    HIP_TRY_AS(c, who, hipEventRecord(c->expose_ev[0], nullptr));
+    HIP_TRY_AS(c, who, launch_meter(p, (uint32_t)c->n_cu, nullptr));
+    HIP_TRY_AS(c, who, hipEventRecord(c->expose_ev[1], nullptr));
+    c->meter_timed = true;
+    std::vector<uint32_t> host(kMeterBins + 6);      // the histogram and the three 64-bit counters behind it
+    HIP_TRY_AS(c, who, hipMemcpy(host.data(), L.hist, host.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY_AS(c, who, hipDeviceSynchronize());
+    unsigned long long counts[3];
+    memcpy(counts, host.data() + kMeterBins, sizeof(counts));
+    meter_decide(host.data(), cfg, result);
+    result->metered = counts[0]; result->dark = counts[1]; result->nonfinite = counts[2];      // (the device's own count: the tests hold it to the histogram's sum)
+    if (hist_out) memcpy(hist_out, host.data(), kMeterBins * sizeof(uint32_t));
+    return SRT_OK;
+}
+
+// The tone kernel over the w x h rectangle described by p (outputs and counts are filled in here) into d_expose_out.  The caller copies
+// the images out and synchronises; counts are read here.
+int run_tone(srt_ctx *c, const char *who, ToneParams p, const srt_tone *tone, const bool want[3]) {
+    const size_t pixels = (size_t)p.w * p.h;
+    const ExposeLayout L(c->d_expose);
+    const ExposeImages I(c->d_expose_out, pixels);
+    c->tone_timed = false;
+    for (int k = 2; k < 4; k++) if (!c->expose_ev[k]) HIP_TRY_AS(c, who, hipEventCreate(&c->expose_ev[k]));
+    HIP_TRY_AS(c, who, hipMemsetAsync(L.tone_counts, 0, 3 * sizeof(unsigned long long), nullptr));
+    p.curve = tone->curve; p.gain = tone->gain; p.kw = tone->white * tone->white;
+    p.out_xyz = want[0] ? I.img[0] : nullptr; p.out_lin = want[1] ? I.img[1] : nullptr; p.out_q = want[2] ? I.img[2] : nullptr;
+    p.counts = L.tone_counts;
+    HIP_TRY_AS(c, who, hipEventRecord(c->expose_ev[2], nullptr));
+    HIP_TRY_AS(c, who, launch_tone(p, (uint32_t)c->n_cu, nullptr));
+    HIP_TRY_AS(c, who, hipEventRecord(c->expose_ev[3], nullptr));
+    c->tone_timed = true;
+    return SRT_OK;
+}
+int read_tone_counts(srt_ctx *c, const char *who, srt_tone_result *result) {
+    unsigned long long counts[3] = {0, 0, 0};
+    HIP_TRY_AS(c, who, hipMemcpy(counts, ExposeLayout(c->d_expose).tone_counts, sizeof(counts), hipMemcpyDeviceToHost));
+    result->blown = counts[0]; result->crushed = counts[1]; result->nonfinite = counts[2];
+    return SRT_OK;
+}
+
+// a caller's [h][w][3] array on the device (d_expose_in)
+int upload_kat_xyz(srt_ctx *c, const char *who, const float *xyz_mean, uint32_t w, uint32_t h) {
+    const size_t bytes = (size_t)w * h * 3 * sizeof(float);
+    if (const int rc = develop_reserve(c, who, c->d_expose_in, bytes)) return rc;
+    HIP_TRY_AS(c, who, hipMemcpy(c->d_expose_in.ptr, xyz_mean, bytes, hipMemcpyHostToDevice));
+    return SRT_OK;
+}
+
+}  // namespace
+
+int srt_meter_decide(const uint32_t *hist, const srt_meter *cfg, srt_meter_result *result) {
+    if (!hist || !cfg || !result) return fail(nullptr, SRT_ERR_INVALID, "srt_meter_decide: null argument");
+    if (const char *why = meter_cfg_error(cfg)) return fail(nullptr, SRT_ERR_INVALID, std::string("srt_meter_decide: ") + why);
+    meter_decide(hist, cfg, result);
+    return SRT_OK;
+}
+
+int srt_meter_accum(srt_ctx *c, const srt_meter *cfg, uint32_t *hist, srt_meter_result *result) {
+    const char *who = "srt_meter_accum";
+    if (!c || !cfg || !result) return fail(c, SRT_ERR_INVALID, "srt_meter_accum: null argument");
+    if (const char *why = meter_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_meter_accum: ") + why);
+    if (!c->accum.bound()) return fail(c, SRT_ERR_INVALID, "srt_meter_accum: no accumulation with a pass (srt_accum_reset* and srt_render_chunk_accum first)");
+    uint32_t rect[4];
+    if (const char *why = meter_rect_error(cfg, clipped_w(c), clipped_h(c), rect)) return fail(c, SRT_ERR_INVALID, std::string("srt_meter_accum: ") + why);
+    HIP_TRY(c, hipSetDevice(c->device));
+    MeterParams p = {};
+    p.y = AccumLayout(c).y; p.y_stride = 1; p.state = c->accum.adaptive() ? AdaptPlanes(c).state : nullptr;
+    p.samples = c->accum.total; p.normalise = 1;
+    p.n_lanes = c->n_lanes; p.tx = c->tx; p.ty = c->ty; p.bx = c->bx;
+    p.x0 = rect[0]; p.y0 = rect[1]; p.w = rect[2]; p.h = rect[3];
+    p.tiles_x = c->tiles_x; p.rank = c->rank; p.world = c->world;
+    srt_meter_result res = *result;
+    if (const int rc = run_meter(c, who, p, cfg, hist, &res)) return rc;
+    *result = res;
+    return SRT_OK;
+}
+
+int srt_meter_kat(srt_ctx *c, const srt_meter *cfg, const float *xyz_mean, uint32_t w, uint32_t h, uint32_t *hist, srt_meter_result *result) {
+    const char *who = "srt_meter_kat";
+    if (!c || !cfg || !xyz_mean || !result) return fail(c, SRT_ERR_INVALID, "srt_meter_kat: null argument");
+    if (w == 0 || h == 0 || (uint64_t)w * h > 0x7fffffffull) return fail(c, SRT_ERR_INVALID, "srt_meter_kat: w x h must be in 1 .. 2^31 - 1");
+    if (const char *why = meter_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_meter_kat: ") + why);
+    uint32_t rect[4];
+    if (const char *why = meter_rect_error(cfg, w, h, rect)) return fail(c, SRT_ERR_INVALID, std::string("srt_meter_kat: ") + why);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = upload_kat_xyz(c, who, xyz_mean, w, h)) return rc;
+    // a grid of one w x h block makes the block-linear lane the row-major pixel
+    MeterParams p = {};
+    p.y = c->d_expose_in.as<float>() + 1; p.y_stride = 3; p.state = nullptr; p.samples = 1; p.normalise = 0;
+    p.n_lanes = w * h; p.tx = w; p.ty = h; p.bx = 1;
+    p.x0 = rect[0]; p.y0 = rect[1]; p.w = rect[2]; p.h = rect[3];
+    p.tiles_x = (w + 7u) / 8u; p.rank = 0; p.world = 1;
+    srt_meter_result res = *result;
+    if (const int rc = run_meter(c, who, p, cfg, hist, &res)) return rc;
+    *result = res;
+    return SRT_OK;
+}
+
+int srt_expose_accum(srt_ctx *c, const srt_tone *tone, float *out_xyz, float *out_lin, float *out_q, srt_tone_result *result,
+                     uint32_t image_width, uint32_t image_height) {
+    const char *who = "srt_expose_accum";
+    if (!c || !tone) return fail(c, SRT_ERR_INVALID, "srt_expose_accum: null argument");
+    if ((!out_xyz && !out_lin && !out_q) || image_width == 0 || image_height == 0) return fail(c, SRT_ERR_INVALID, "srt_expose_accum: no output / empty image");
+    if (const char *why = tone_cfg_error(tone)) return fail(c, SRT_ERR_INVALID, std::string("srt_expose_accum: ") + why);
+    if (!c->accum.bound()) return fail(c, SRT_ERR_INVALID, "srt_expose_accum: no accumulation with a pass (srt_accum_reset* and srt_render_chunk_accum first)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the kernel runs on the chunk's rectangle (clipped to the reference grid); the image clips only what is copied out
+    const uint32_t w = clipped_w(c), h = clipped_h(c);
+    const size_t pixels = (size_t)w * h;
+    srt_tone_result res = {};
+    if (pixels) {
+        if (const int rc = develop_reserve(c, who, c->d_expose, ExposeLayout::kBytes)) return rc;
+        if (const int rc = develop_reserve(c, who, c->d_expose_out, ExposeImages::bytes(pixels))) return rc;
+        ToneParams p = {};
+        p.sums = AccumLayout(c).sums; p.comp_stride = c->n_lanes; p.state = c->accum.adaptive() ? AdaptPlanes(c).state : nullptr;
+        p.samples = c->accum.total; p.tx = c->tx; p.ty = c->ty; p.bx = c->bx; p.w = w; p.h = h;
+        p.tiles_x = c->tiles_x; p.rank = c->rank; p.world = c->world;
+        float *const host[3] = {out_xyz, out_lin, out_q};
+        const bool want[3] = {out_xyz != nullptr, out_lin != nullptr, out_q != nullptr};
+        if (const int rc = run_tone(c, who, p, tone, want)) return rc;
+        const ChunkRect rect = chunk_rect(c, image_width, image_height);
+        const ExposeImages I(c->d_expose_out, pixels);
+        for (int k = 0; k < 3; k++) {
+            const size_t row = (size_t)rect.w * 3 * sizeof(float), src_pitch = (size_t)w * 3 * sizeof(float), pitch = (size_t)image_width * 3 * sizeof(float);
+            if (host[k] && rect.w && rect.h) HIP_TRY(c, hipMemcpy2D(host[k] + rect.first * 3, pitch, I.img[k], src_pitch, row, rect.h, hipMemcpyDeviceToHost));
+        }
+        if (const int rc = read_tone_counts(c, who, &res)) return rc;
+    }
+    HIP_TRY(c, hipDeviceSynchronize());
+    if (result) *result = res;
+    return SRT_OK;
+}
+
+int srt_expose_kat(srt_ctx *c, const srt_tone *tone, const float *xyz_mean, uint32_t w, uint32_t h, float *out_xyz, float *out_lin, float *out_q,
+                   srt_tone_result *result) {
+    const char *who = "srt_expose_kat";
+    if (!c || !tone || !xyz_mean) return fail(c, SRT_ERR_INVALID, "srt_expose_kat: null argument");
+    if (!out_xyz && !out_lin && !out_q) return fail(c, SRT_ERR_INVALID, "srt_expose_kat: no output");
+    if (w == 0 || h == 0 || (uint64_t)w * h > 0x7fffffffull) return fail(c, SRT_ERR_INVALID, "srt_expose_kat: w x h must be in 1 .. 2^31 - 1");
+    if (const char *why = tone_cfg_error(tone)) return fail(c, SRT_ERR_INVALID, std::string("srt_expose_kat: ") + why);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t pixels = (size_t)w * h;
+    if (const int rc = develop_reserve(c, who, c->d_expose_out, ExposeImages::bytes(pixels))) return rc;      // (the larger block first)
+    if (const int rc = develop_reserve(c, who, c->d_expose, ExposeLayout::kBytes)) return rc;
+    if (const int rc = upload_kat_xyz(c, who, xyz_mean, w, h)) return rc;
+    ToneParams p = {};
+    p.xyz = c->d_expose_in.as<float>(); p.w = w; p.h = h; p.tiles_x = (w + 7u) / 8u; p.rank = 0; p.world = 1;
+    float *const host[3] = {out_xyz, out_lin, out_q};
+    const bool want[3] = {out_xyz != nullptr, out_lin != nullptr, out_q != nullptr};
+    if (const int rc = run_tone(c, who, p, tone, want)) return rc;
+    const ExposeImages I(c->d_expose_out, pixels);
+    for (int k = 0; k < 3; k++)
+        if (host[k]) HIP_TRY_AS(c, who, hipMemcpy(host[k], I.img[k], pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    srt_tone_result res = {};
+    if (const int rc = read_tone_counts(c, who, &res)) return rc;
+    HIP_TRY_AS(c, who, hipDeviceSynchronize());
+    if (result) *result = res;
+    return SRT_OK;
+}
+
+int srt_expose_last_ms(srt_ctx *c, float *meter_ms, float *tone_ms) {
+    if (!c) return fail(c, SRT_ERR_INVALID, "srt_expose_last_ms: null ctx");
+    if (!c->meter_timed && !c->tone_timed) return fail(c, SRT_ERR_INVALID, "srt_expose_last_ms: neither a meter nor a tone kernel has run on this context");
+    HIP_TRY(c, hipSetDevice(c->device));
+    float ms[2] = {0.0f, 0.0f};
+    if (c->meter_timed) {
+        HIP_TRY(c, hipEventSynchronize(c->expose_ev[1]));
+        HIP_TRY(c, hipEventElapsedTime(&ms[0], c->expose_ev[0], c->expose_ev[1]));
+    }
+    if (c->tone_timed) {
+        HIP_TRY(c, hipEventSynchronize(c->expose_ev[3]));
+        HIP_TRY(c, hipEventElapsedTime(&ms[1], c->expose_ev[2], c->expose_ev[3]));
+    }
+    if (meter_ms) *meter_ms = ms[0];
+    if (tone_ms) *tone_ms = ms[1];
     return SRT_OK;
 }
 

@@ -44,15 +44,6 @@ constexpr uint32_t kDevBatch = 24;                                       // load
 static_assert(kDevTileF4 % (kDevTilePixels * kDevBatch) == 0, "the tile is a whole number of load batches");
 static_assert(kFilmStride % 4u == 0, "a 16-byte slot never straddles two film rows");
 
-// the inverse of block_linear_idx: chunk pixel (i, j) of block-linear lane idx
-__device__ __forceinline__ PixelIJ block_linear_pixel(uint32_t idx, uint32_t tx, uint32_t ty, uint32_t bx) {
-    const uint32_t per = tx * ty;
-    const uint32_t block = idx / per, within = idx - block * per;
-    const uint32_t ly = within / tx, lx = within - ly * tx;
-    const uint32_t gby = block / bx, gbx = block - gby * bx;
-    return {gbx * tx + lx, gby * ty + ly};
-}
-
 template <int KC>
 __global__ __launch_bounds__(64) void develop_kernel(const DevelopParams P) {
     __shared__ float tile[kDevTilePixels * kDevPitch];

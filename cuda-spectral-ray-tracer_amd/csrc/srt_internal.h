@@ -318,6 +318,44 @@ struct DevelopSrgbCountsParams {
     uint32_t w, h;
 };
 hipError_t launch_develop_srgb_counts(const DevelopSrgbCountsParams &p, hipStream_t st);
+// Exposure metering and tone mapping (srt_expose.hip; every operation is stated in srt_c_api.h at srt_meter_decide and srt_expose_accum).
+// meter: lane idx of the grid [0, n_lanes) holds the luminance y[idx * y_stride] -- a Y sum that is multiplied by inv = 1.0f / (float)n
+// when `normalise` is set, n = `samples`, or with `state` the lane's own count state[idx] & ~kAdaptConverged (0 counts as 1) -- of chunk
+// pixel (i, j) = the inverse of block_linear_idx(i, j, tx, ty, bx).  The pixel is metered when it lies in the rectangle (x0, y0, w, h) and
+// its 8 x 8 tile t = (j / 8) * tiles_x + i / 8 has t % world == rank.  hist[kMeterBins] and counts[3] (metered, dark, non-finite) are ADDED
+// to: the caller zeroes them.  A caller's [h][w][3] array: y = its second component, y_stride = 3, tx = w, ty = h, bx = 1.
+constexpr uint32_t kMeterBins = 4096;           // SRT_METER_BINS (srt_c_api.h)
+constexpr uint32_t kMeterMaxBlocks = 1024;      // the grid's cap: the flush is at most this many workgroups' non-zero bins
+struct MeterParams {
+    const float *y;
+    size_t y_stride;
+    const uint32_t *state;
+    uint32_t samples, normalise;
+    uint32_t n_lanes, tx, ty, bx;
+    uint32_t x0, y0, w, h;
+    uint32_t tiles_x, rank, world;
+    uint32_t *hist;
+    unsigned long long *counts;
+};
+hipError_t launch_meter(const MeterParams &p, uint32_t n_cu, hipStream_t st);
+// tone: pixel (x, y) of the row-major w x h rectangle takes its XYZ mean from the sum planes (sums[idx + c * comp_stride], idx =
+// block_linear_idx(x, y, tx, ty, bx), times inv as above) or, with sums == null, from xyz[3 * pix + c]; gain, curve and kw = white * white
+// as stated in srt_c_api.h; out_xyz / out_lin / out_q (any may be null) are row-major, three floats per pixel.  counts[3] (blown, crushed,
+// non-finite) are ADDED to, for the pixels of this rank's tiles only.
+struct ToneParams {
+    const float *sums, *xyz;
+    size_t comp_stride;
+    const uint32_t *state;
+    uint32_t samples;
+    uint32_t tx, ty, bx;
+    uint32_t w, h;
+    uint32_t tiles_x, rank, world;
+    uint32_t curve;
+    float gain, kw;
+    float *out_xyz, *out_lin, *out_q;
+    unsigned long long *counts;
+};
+hipError_t launch_tone(const ToneParams &p, uint32_t n_cu, hipStream_t st);
 hipError_t launch_order_tiles(const uint32_t *cost, uint32_t *sorted, uint32_t *rows, uint32_t n, uint32_t n_waves,
                               uint32_t split_load_pct, uint32_t *queue_info, uint32_t order_max_pct, hipStream_t st);
 hipError_t launch_scatter(const ScatterParams &p, hipStream_t st);

@@ -93,6 +93,14 @@ __host__ __device__ __forceinline__ QueueRow queue_row_unpack(uint32_t row) {
 __device__ __forceinline__ bool queue_slot_in_share(uint32_t lt, uint32_t part, uint32_t s) { return (lt >> (6u - s)) == part; }
 
 struct PixelIJ { uint32_t i, j; };      // chunk-relative column and row (rendering.cu:156-157)
+// the inverse of block_linear_idx: chunk pixel (i, j) of block-linear lane idx (the develop and the meter kernels walk lanes and need the pixel)
+__device__ __forceinline__ PixelIJ block_linear_pixel(uint32_t idx, uint32_t tx, uint32_t ty, uint32_t bx) {
+    const uint32_t per = tx * ty;
+    const uint32_t block = idx / per, within = idx - block * per;
+    const uint32_t ly = within / tx, lx = within - ly * tx;
+    const uint32_t gby = block / bx, gbx = block - gby * bx;
+    return {gbx * tx + lx, gby * ty + ly};
+}
 __device__ __forceinline__ uint32_t queue_global_tile(uint32_t tile_local, uint32_t rank, uint32_t world) { return rank + world * tile_local; }
 __device__ __forceinline__ PixelIJ tile_slot_pixel(uint32_t tile, uint32_t lt, uint32_t tiles_x) {
     const uint32_t tile_x = tile % tiles_x, tile_y = tile / tiles_x;

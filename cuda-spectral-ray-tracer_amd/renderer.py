@@ -186,6 +186,69 @@ class Renderer:
         self._ck(B.lib().srt_develop_last_ms(self._h, C.byref(a), C.byref(b)))
         return dict(contract=a.value, epilogue=b.value)
 
+    def meter(self, with_hist=False, **cfg):
+        """the luminance histogram of the context's accumulation, of any kind, taken on the device, and the exposure decided from it
+        (srt_meter_accum; cfg: the keywords of meter_config): dict(metered, dark, nonfinite, bin_ref, y_ref, gain) -- with
+        with_hist=True also hist, the 4096 uint32 counts.  Under a partition only this rank's tiles are counted.  Reads the
+        accumulation, changes nothing of it."""
+        m, res = meter_config(**cfg), B.MeterResult()
+        hist = np.zeros(METER_BINS, np.uint32) if with_hist else None
+        self._ck(B.lib().srt_meter_accum(self._h, C.byref(m), None if hist is None else hist.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(res)))
+        return _meter_dict(res, hist)
+
+    def meter_kat(self, xyz_mean, with_hist=False, **cfg):
+        """the meter kernel on an explicit XYZ-mean image (srt_meter_kat): xyz_mean (h, w, 3) float32 -- a denoised or developed picture,
+        or a synthetic one -- -> the dict of meter().  Needs no scene and no accumulation."""
+        m, res = meter_config(**cfg), B.MeterResult()
+        img = _xyz_image("meter_kat", xyz_mean)
+        hist = np.zeros(METER_BINS, np.uint32) if with_hist else None
+        self._ck(B.lib().srt_meter_kat(self._h, C.byref(m), B.fptr(img), img.shape[1], img.shape[0],
+                                       None if hist is None else hist.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(res)))
+        return _meter_dict(res, hist)
+
+    def expose(self, image_width, image_height, gain=None, **cfg):
+        """the accumulation's picture at a metered (gain=None) or given exposure, through a tone curve and the usual conversion to sRGB, on
+        the device (srt_expose_accum; cfg: the keywords of meter_config and of tone_config, told apart by name): dict(xyz, lin, fb) of
+        (image_height, image_width, 3) float32 arrays -- the toned XYZ, its unquantised and its quantised sRGB, written in the chunk's
+        rectangle only -- plus meter (the dict of meter(), None when a gain was given) and clip = dict(blown, crushed, nonfinite).
+        Reads the accumulation, changes nothing of it."""
+        mcfg, tcfg = _split_expose_cfg(cfg)
+        meter = None
+        if gain is None:
+            tone_config(gain=1.0, **tcfg)          # (a bad tone is an error before the device is touched)
+            meter = self.meter(**mcfg)
+            gain = meter["gain"]
+        elif mcfg:
+            raise ValueError("expose: %s given with an explicit gain, which is not metered" % ", ".join(sorted(mcfg)))
+        t, res = tone_config(gain=gain, **tcfg), B.ToneResult()
+        out = [np.zeros((image_height, image_width, 3), np.float32) for _ in range(3)]
+        self._ck(B.lib().srt_expose_accum(self._h, C.byref(t), B.fptr(out[0]), B.fptr(out[1]), B.fptr(out[2]), C.byref(res), image_width, image_height))
+        return dict(xyz=out[0], lin=out[1], fb=out[2], meter=meter, clip=dict(blown=res.blown, crushed=res.crushed, nonfinite=res.nonfinite))
+
+    def expose_kat(self, xyz_mean, gain=None, **cfg):
+        """expose() on an explicit XYZ-mean image (srt_meter_kat when gain is None, then srt_expose_kat): xyz_mean (h, w, 3) float32 -> the
+        dict of expose() with (h, w, 3) images.  Needs no scene and no accumulation."""
+        mcfg, tcfg = _split_expose_cfg(cfg)
+        img = _xyz_image("expose_kat", xyz_mean)
+        meter = None
+        if gain is None:
+            tone_config(gain=1.0, **tcfg)
+            meter = self.meter_kat(img, **mcfg)
+            gain = meter["gain"]
+        elif mcfg:
+            raise ValueError("expose_kat: %s given with an explicit gain, which is not metered" % ", ".join(sorted(mcfg)))
+        t, res = tone_config(gain=gain, **tcfg), B.ToneResult()
+        out = [np.zeros(img.shape, np.float32) for _ in range(3)]
+        self._ck(B.lib().srt_expose_kat(self._h, C.byref(t), B.fptr(img), img.shape[1], img.shape[0], B.fptr(out[0]), B.fptr(out[1]), B.fptr(out[2]), C.byref(res)))
+        return dict(xyz=out[0], lin=out[1], fb=out[2], meter=meter, clip=dict(blown=res.blown, crushed=res.crushed, nonfinite=res.nonfinite))
+
+    def expose_last_ms(self):
+        """kernel-only ms of the context's last meter kernel and last tone kernel (srt_expose_last_ms): dict(meter, tone), 0 for one that
+        has not run"""
+        a, b = C.c_float(), C.c_float()
+        self._ck(B.lib().srt_expose_last_ms(self._h, C.byref(a), C.byref(b)))
+        return dict(meter=a.value, tone=b.value)
+
     def accum_reset_features(self):
         """start a FEATURED accumulation (srt_c_api.h): like accum_reset, and each later pass also adds, at the first hit of every
         sample's camera ray, the face-forwarded normal, the hit material's colour, the distance and 1 to the pixel's eight raw float32
@@ -677,6 +740,22 @@ class Comm:
             out = d if out is None else out + d
         return out
 
+    def meter(self, with_hist=False, **cfg):
+        """the frame metered over all ranks (Renderer.meter): the local ranks' histograms and counters are summed -- integers, so the
+        sum is the whole frame's histogram exactly -- and srt_meter_decide decides on the sum.  Single-process communicators (init_all)
+        only: on a process-per-GPU communicator the sum would need a reduction across processes (SrtError, SRT_ERR_UNSUPPORTED)."""
+        if not self._owns:
+            raise B.SrtError(-5, "Comm.meter: a process-per-GPU communicator cannot sum the ranks' histograms; meter every rank and reduce them yourself")
+        m = meter_config(**cfg)
+        hist = np.zeros(METER_BINS, np.uint64)
+        dark = nonfinite = 0
+        for r in self.renderers:
+            part = r.meter(with_hist=True, **cfg)
+            hist += part["hist"]
+            dark += part["dark"]
+            nonfinite += part["nonfinite"]
+        return meter_decide(hist, m, dark, nonfinite, with_hist)
+
     def render_frame_accum(self, width, height, spp_add, offx=0, offy=0):
         """render_frame with an accumulating pass of spp_add samples on every rank (Renderer.render_chunk_accum)"""
         self._ck(B.lib().srt_render_frame_multi_accum(self._h, width, height, offx, offy, spp_add))
@@ -1077,6 +1156,123 @@ def _features_passes(scene, cam, width, height, sched, bounce_limit, seed, devic
             r.render_chunk_accum(width, height, spp_add)
             r.scatter_tiles()
             yield r.accum_samples, _collect(r, width, height), r.read_features(width, height)
+
+
+METER_BINS = 4096      # SRT_METER_BINS (srt_c_api.h)
+_METER_KEYS = ("rect", "percentile_ppm", "key", "gain_min", "gain_max")
+_TONE_KEYS = ("curve", "white")
+CURVES = {"linear": 0, "reinhard": 1}
+
+
+def _expose_number(who, name, v):
+    """v as a float32 held in a Python float (a value beyond float32 becomes inf); ValueError for what is no number"""
+    try:
+        if isinstance(v, bool):
+            raise TypeError
+        with np.errstate(over="ignore"):
+            return float(np.float32(v))
+    except (TypeError, ValueError):
+        raise ValueError("%s: %s must be a number, got %r" % (who, name, v))
+
+
+def meter_config(rect=None, percentile_ppm=500000, key=0.18, gain_min=2.0 ** -24, gain_max=2.0 ** 24):
+    """srt_meter from Python numbers, checked as the library checks it (ValueError): rect None -- the whole chunk -- or (x0, y0, w, h) in
+    chunk pixels, non-empty (the library checks it against the chunk); percentile_ppm a whole number in [1, 1000000], the percentile of
+    the metered luminances, in parts per million, whose bin is anchored at key; key finite and > 0; 0 < gain_min <= gain_max, finite.
+    The defaults -- the median anchored at 0.18, gains within 2^-24 .. 2^24 -- are starting values, untuned."""
+    if isinstance(percentile_ppm, bool) or not isinstance(percentile_ppm, (int, np.integer)) or not 1 <= percentile_ppm <= 1000000:
+        raise ValueError("meter: percentile_ppm must be a whole number in [1, 1000000], got %r" % (percentile_ppm,))
+    k, lo, hi = (_expose_number("meter", n, v) for n, v in (("key", key), ("gain_min", gain_min), ("gain_max", gain_max)))
+    if not (np.isfinite(k) and k > 0.0):
+        raise ValueError("meter: key must be finite and > 0 in float32, got %r" % (key,))
+    if not (np.isfinite(lo) and np.isfinite(hi) and 0.0 < lo <= hi):
+        raise ValueError("meter: needs 0 < gain_min <= gain_max, both finite in float32, got %r, %r" % (gain_min, gain_max))
+    if rect is None:
+        rect = (0, 0, 0, 0)
+    else:
+        rect = tuple(rect)
+        if len(rect) != 4 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v < 2 ** 32 for v in rect) or rect[2] == 0 or rect[3] == 0:
+            raise ValueError("meter: rect must be None or (x0, y0, w, h) of whole numbers with w > 0 and h > 0, got %r" % (rect,))
+    return B.Meter(int(rect[0]), int(rect[1]), int(rect[2]), int(rect[3]), int(percentile_ppm), k, lo, hi, (C.c_uint32 * 4)(0, 0, 0, 0))
+
+
+def tone_config(gain=1.0, curve="reinhard", white=4.0):
+    """srt_tone from Python numbers, checked as the library checks it (ValueError): gain finite and > 0 in float32 (what meter() decided,
+    or the caller's own); curve "linear" (0) or "reinhard" (1: extended Reinhard on luminance); white > 0, the luminance after the gain
+    that the curve maps to 1 (inf: plain Reinhard).  curve and white = 4 are starting values, untuned."""
+    if isinstance(curve, str):
+        if curve not in CURVES:
+            raise ValueError("tone: curve must be one of %s (or 0, 1), got %r" % (sorted(CURVES), curve))
+        curve = CURVES[curve]
+    if isinstance(curve, bool) or not isinstance(curve, (int, np.integer)) or curve not in (0, 1):
+        raise ValueError("tone: curve must be 0 (linear) or 1 (reinhard), got %r" % (curve,))
+    g, w = _expose_number("tone", "gain", gain), _expose_number("tone", "white", white)
+    if not (np.isfinite(g) and g > 0.0):
+        raise ValueError("tone: gain must be finite and > 0 in float32, got %r" % (gain,))
+    if not w > 0.0:
+        raise ValueError("tone: white must be > 0 in float32 (inf allowed), got %r" % (white,))
+    return B.Tone(int(curve), g, w, (C.c_uint32 * 5)(0, 0, 0, 0, 0))
+
+
+def _split_expose_cfg(cfg):
+    """(meter keywords, tone keywords) of expose()'s cfg; TypeError for a name that is neither"""
+    unknown = sorted(set(cfg) - set(_METER_KEYS) - set(_TONE_KEYS))
+    if unknown:
+        raise TypeError("expose: unknown keyword(s) %s (meter: %s; tone: %s)" % (", ".join(unknown), ", ".join(_METER_KEYS), ", ".join(_TONE_KEYS)))
+    return {k: v for k, v in cfg.items() if k in _METER_KEYS}, {k: v for k, v in cfg.items() if k in _TONE_KEYS}
+
+
+def _xyz_image(who, xyz_mean):
+    img = np.ascontiguousarray(xyz_mean, np.float32)
+    if img.ndim != 3 or img.shape[2] != 3 or img.shape[0] == 0 or img.shape[1] == 0:
+        raise ValueError("%s: needs an XYZ-mean image (h, w, 3) with h, w >= 1, got %r" % (who, img.shape))
+    return img
+
+
+def _meter_dict(res, hist=None):
+    out = dict(metered=res.metered, dark=res.dark, nonfinite=res.nonfinite, bin_ref=res.bin_ref, y_ref=res.y_ref, gain=res.gain)
+    if hist is not None:
+        out["hist"] = hist
+    return out
+
+
+def meter_decide(hist, cfg=None, dark=0, nonfinite=0, with_hist=False):
+    """the exposure decided from a luminance histogram on the host (srt_meter_decide; needs no GPU): hist 4096 counts, each below 2^32 --
+    one context's, or the sum of the histograms of a partition's ranks; cfg a meter_config() (None: the defaults) -> the dict of
+    Renderer.meter, dark and nonfinite passed through."""
+    h = np.asarray(hist)
+    if h.shape != (METER_BINS,) or h.dtype.kind not in "iu" or (h < 0).any() or (h >= 2 ** 32).any():
+        raise ValueError("meter_decide: needs %d whole counts in [0, 2^32)" % METER_BINS)
+    h32 = np.ascontiguousarray(h, np.uint32)
+    res = B.MeterResult(0, int(dark), int(nonfinite), 0, 0.0, 0.0, 0)
+    m = meter_config() if cfg is None else cfg
+    B.check(B.lib().srt_meter_decide(h32.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(m), C.byref(res)))
+    return _meter_dict(res, h32 if with_hist else None)
+
+
+def render_exposed(scene, cam, width, height, passes, bounce_limit, gain=None, seed=1984, device=0, renderer=None, **cfg):
+    """render_progressive with the exposure metered and the picture toned on the device behind every pass: a generator of (spp_total,
+    result, meter, exposed) -- `result` with the keys of render_image, `exposed` the dict of Renderer.expose (cfg: the keywords of
+    meter_config and tone_config) and `meter` its metering (None with an explicit gain).  Metering and toning only read the
+    accumulation, so result is render_progressive's bit for bit.  Schedule and cfg are checked here, before any device is touched."""
+    sched = progressive_schedule(passes)
+    mcfg, tcfg = _split_expose_cfg(cfg)
+    meter_config(**mcfg)
+    tone_config(gain=1.0 if gain is None else gain, **tcfg)
+    if gain is not None and mcfg:
+        raise ValueError("render_exposed: %s given with an explicit gain, which is not metered" % ", ".join(sorted(mcfg)))
+    return _exposed_passes(scene, cam, width, height, sched, bounce_limit, seed, device, renderer, gain, cfg)
+
+
+def _exposed_passes(scene, cam, width, height, sched, bounce_limit, seed, device, renderer, gain, cfg):
+    with _image_session(scene, cam, width, height, sum(sched), bounce_limit, seed, device, renderer) as r:
+        r.accum_reset()
+        for spp_add in sched:
+            r.render_chunk_accum(width, height, spp_add)
+            r.scatter_tiles()
+            out = _collect(r, width, height)
+            exposed = r.expose(width, height, gain, **cfg)
+            yield r.accum_samples, out, exposed["meter"], exposed
 
 
 MAX_DENOISE_LEVELS = 8

@@ -357,6 +357,77 @@ SRT_API int srt_develop_kat(srt_ctx *ctx, const float *film, uint32_t n_pixels, 
                             float *out);
 SRT_API int srt_develop_last_ms(srt_ctx *ctx, float *contract_ms, float *epilogue_ms);
 
+/* Exposure metering and tone mapping on the device (no reference counterpart: the reference clamps whatever it is given; kernels in
+ * csrc/srt_expose.hip).  A luminance histogram is taken where the sums live, an exposure gain is decided from it on the host, and a tone
+ * curve runs in front of the conversion every other picture ends in (xyz_mean_to_srgb: linear sRGB clamped to [0, 1], gamma-encoded,
+ * quantised).  Operation by operation -- everything fp32, not contracted, left to right, selects and never fmax; the restatement is
+ * tests/expose_reference.py, which the device equals in every integer and every bit:
+ *   Luminance of a pixel.  From an accumulation: Y_p = inv * S_y with S_y the pixel's Y sum and inv = 1.0f / (float)n, n the sample
+ *     total -- on an adaptive kind the pixel's own count n_p = state & 0x7fffffff, and inv = 1 where n_p == 0 -- as the epilogues
+ *     normalise.  From a caller's XYZ-mean array [h][w][3]: Y_p is the second component, untouched.
+ *   Classification of a pixel inside the metered rectangle, the tests in this order:
+ *     1. non-finite when (Y - Y) == 0 is false;
+ *     2. otherwise dark when Y >= FLT_MIN (1.17549435e-38f) is false: zeros of both signs, negatives, denormals;
+ *     3. otherwise metered, into bin b = float_as_uint(Y) >> 19: the 8 exponent bits and the top 4 mantissa bits, 16 bins per octave,
+ *        b in [16, 4080); a histogram has SRT_METER_BINS = 4096 uint32 counts.
+ *   Ownership.  Pixel (i, j) of the chunk lies in the 8 x 8 tile t = (j / 8) * tiles_x + i / 8 (tiles_x = ceil(tx * bx / 8), the tiles of
+ *     srt_set_partition).  A pixel of a tile this rank does not own (t % world != rank) is skipped: counted in no bin and in no counter.
+ *     So the histograms and counters of the ranks of a partition add up to those of partition (0, 1), exactly -- they are integers.
+ *   Decision (srt_meter_decide: host only, no context, no GPU), from hist[4096] and cfg:
+ *     n = sum of hist[16 .. 4079] in uint64.  n == 0: bin_ref = 0, y_ref = 0, g = 1.0f.  Otherwise
+ *       target = max(1, (n * percentile_ppm + 999999) / 1000000)  (uint64);  bin_ref = the smallest B with sum of hist[16 .. B] >= target;
+ *       y_ref = uint_as_float((bin_ref << 19) | (1 << 18)), the bin's midpoint;  g = key / y_ref.
+ *     In every case  g = g < gain_min ? gain_min : g;  g = g > gain_max ? gain_max : g.  result->metered = n; dark and nonfinite are
+ *     left as the caller passed them in (the histogram does not hold them).
+ *     What follows: metering is scale invariant for powers of two -- a picture scaled by 2^k (no overflow, no underflow, no clamp of the
+ *     gain) shifts its histogram by 16 k bins and gets exactly 2^-k times the gain, so its exposed picture is the same, bit for bit.
+ *   cfg (srt_meter), validated by every entry point that takes one, else SRT_ERR_INVALID: 1 <= percentile_ppm <= 1000000; key finite and
+ *     > 0; 0 < gain_min <= gain_max, both finite; the reserved words 0; the rectangle (x0, y0, w, h) in chunk pixels either all zero --
+ *     the whole chunk -- or non-empty (w > 0 and h > 0) and, where there is a chunk, inside it.
+ *   Tone (srt_tone), per pixel with XYZ mean c, g = gain and kw = white * white formed once on the host:
+ *     c' = (g * c.x, g * c.y, g * c.z);  y = c'.y
+ *     curve 0 (linear):  o = c'
+ *     curve 1 (extended Reinhard on luminance):  t = y / kw;  num = 1.0f + t;  den = 1.0f + y;  s = num / den;  s = (y > 0) ? s : 1.0f;
+ *       o = (s * c'.x, s * c'.y, s * c'.z)      -- white = +inf: t = 0 and the curve is plain Reinhard
+ *     o goes through xyz_mean_to_srgb unchanged: out_xyz = o, out_lin the unquantised and out_q the quantised sRGB.  A non-finite pixel
+ *     propagates as the arithmetic says and touches no other pixel.  The kernel counts, over the pixels of this rank's tiles, with
+ *     integer atomics after a wave-level reduction: blown -- any quantised channel equals 255; crushed -- all three equal 0; nonfinite --
+ *     (v - v) == 0 is false for a component v of o.  With curve 0 and gain 1, out_lin and out_q are the frame's own planes.
+ *     Validated, else SRT_ERR_INVALID: curve 0 or 1; gain finite and > 0; white > 0 (+inf allowed, NaN not); the reserved words 0.
+ *   srt_meter_decide      as above.  SRT_ERR_INVALID for a null pointer or a bad cfg (the rectangle: all zero or non-empty).
+ *   srt_meter_accum       meters the context's bound accumulation of ANY kind -- streamed included: every kind keeps its XYZ sums in the
+ *                         same planes -- under any partition, decides, and fills *result (counters included); hist, unless NULL,
+ *                         receives the 4096 counts.  Synchronises.  Only reads the accumulation.  SRT_ERR_INVALID, nothing changed, for
+ *                         no accumulation with at least one pass, a bad cfg (a rectangle outside the chunk clipped to the reference
+ *                         grid included) or a null ctx / cfg / result; SRT_ERR_HIP for a failed allocation.
+ *   srt_meter_kat         the same kernel on a caller's row-major host array xyz_mean[h][w][3] (the chunk is w x h, one rank).  Needs
+ *                         neither a scene nor an accumulation and touches neither: also the door for denoised and developed XYZ means.
+ *                         SRT_ERR_INVALID also for a null array, an empty image or w x h >= 2^31.
+ *   srt_expose_accum      the tone kernel on the bound accumulation.  Placement and clipping are srt_develop_spectral_srgb's: the kernel
+ *                         runs on the chunk's rectangle and the images receive the part of it inside image_width x image_height at the
+ *                         chunk's offset; nothing else of them is written.  Any of out_xyz / out_lin / out_q may be NULL, not all;
+ *                         result may be NULL.  Synchronises; only reads the accumulation.  Pixels of another rank's tiles hold +0 sums
+ *                         and come out as +0.  SRT_ERR_INVALID for no accumulation with a pass, a bad srt_tone, all outputs NULL, an
+ *                         empty image, a null ctx / tone; SRT_ERR_HIP for a failed allocation.
+ *   srt_expose_kat        the same kernel on xyz_mean[h][w][3]; outputs [h][w][3]; refusals as srt_meter_kat's and srt_expose_accum's.
+ *   srt_expose_last_ms    kernel-only times in ms, from HIP events, of the context's last meter kernel and last tone kernel (0 for one
+ *                         that has not run); SRT_ERR_INVALID before either has run.  Either pointer may be NULL.
+ * Working blocks (the global histogram and counters, 16 KiB; nine floats per pixel of the rectangle for the images; three per pixel for a
+ * KAT input) belong to the context and are reused.  No call here invalidates or alters an accumulation, the frame or the RNG state. */
+#define SRT_METER_BINS 4096
+typedef struct srt_meter { uint32_t x0, y0, w, h; uint32_t percentile_ppm; float key, gain_min, gain_max; uint32_t reserved[4]; } srt_meter;
+typedef struct srt_meter_result { uint64_t metered, dark, nonfinite; uint32_t bin_ref; float y_ref, gain; uint32_t reserved; } srt_meter_result;
+typedef struct srt_tone { uint32_t curve; float gain, white; uint32_t reserved[5]; } srt_tone;
+typedef struct srt_tone_result { uint64_t blown, crushed, nonfinite; } srt_tone_result;
+SRT_API int srt_meter_decide(const uint32_t *hist, const srt_meter *cfg, srt_meter_result *result);
+SRT_API int srt_meter_accum(srt_ctx *ctx, const srt_meter *cfg, uint32_t *hist, srt_meter_result *result);
+SRT_API int srt_meter_kat(srt_ctx *ctx, const srt_meter *cfg, const float *xyz_mean, uint32_t w, uint32_t h, uint32_t *hist, srt_meter_result *result);
+SRT_API int srt_expose_accum(srt_ctx *ctx, const srt_tone *tone, float *out_xyz, float *out_lin, float *out_q, srt_tone_result *result,
+                             uint32_t image_width, uint32_t image_height);
+SRT_API int srt_expose_kat(srt_ctx *ctx, const srt_tone *tone, const float *xyz_mean, uint32_t w, uint32_t h,
+                           float *out_xyz, float *out_lin, float *out_q, srt_tone_result *result);
+SRT_API int srt_expose_last_ms(srt_ctx *ctx, float *meter_ms, float *tone_ms);
+
 /* First-hit feature buffers (no reference counterpart): the geometric side channels a denoiser or compositor takes as input.  A FEATURED
  * accumulation is a plain progressive accumulation (the semantics of srt_accum_reset: passes of s1 .. sk samples equal one launch of
  * their sum in every output above, RNG state included) that also keeps, per pixel, 8 raw fp32 sums F[0..7]:
