@@ -1,0 +1,773 @@
+"""Independent float64 ground truth for ray hits and radiometry.  TEST INFRASTRUCTURE ONLY.
+
+numpy float64 and nothing else: this module imports neither the product nor the oracle, restates no random number generator and
+walks no tree.  Its inputs are the float32 values the renderer is given (vertices, rays, 95-sample spectra, the four CIE / D65 rows
+of srt_color_tables, the camera struct), widened to float64; its outputs are what geometry and radiometry say about them:
+
+  closest_hit    brute-force two-sided Moeller-Trumbore over all triangles
+  t_bound        a-priori float32 error bound of t = (D - n.o) / (n.d)
+  path_moments   mean and variance of one path's XYZ contribution for a given end spectrum (7 stratified wavelengths, or the hero alone)
+  form_factor    Lambert's closed form for the cosine-weighted form factor of a polygon seen from a point
+  lane_index, footprint_average, project_points, polygon_area, coverage_map     pixel helpers
+  soup, bumpy_sheet, axis_aligned_set, ... , to_structs                          scene builders on raw arrays
+  assert_hits_hold, assert_edge_aimed_hold, builtin_report, assert_radiometry_holds
+                 the conditions both suites apply: tests/test_ground_truth_reference.py to the oracle (CPU), tests/test_ground_truth.py
+                 to the device (GPU), on the same inputs and with the same thresholds
+
+The scene builders return plain dicts of numpy arrays; to_structs() fills the caller's ctypes classes (the product's or the oracle's:
+they are byte-compatible), so a scene reaches either implementation without this module knowing it.  Where a helper needs the package
+(its raw-array boundary, its colour tables, its built-in scenes) the caller passes it in.  One material per triangle, so that mat_index
+names the triangle hit; spectra and the background are set DIRECTLY to non-flat tables (a ramp, a bump): the reference's baked greys
+are nearly flat (0.73 bakes to a spectrum of about 1) and would hide an indexing error."""
+import numpy as np
+
+U = 2.0 ** -24                    # unit roundoff of float32
+N_GRID = 95                       # samples of the 5 nm grid, 360 .. 830 nm
+LAMBDA_MIN, LAMBDA_MAX = 360.0, 830.0
+N_WAVELENGTHS = 7
+STEP = (LAMBDA_MAX - LAMBDA_MIN) / N_WAVELENGTHS          # distance of a path's wavelengths, and the weight of each in the XYZ sum
+TX, TY = 28, 16                   # the block of the frame buffer's block-linear layout
+
+MAT_LAMBERTIAN, MAT_METALLIC, MAT_DIELECTRIC, MAT_EMISSIVE = 0, 1, 2, 4      # materials/material.cuh
+AAP_NONE, AAP_XY, AAP_YZ, AAP_XZ = 0, 1, 2, 3                                # primitives/tri.cuh
+PROJECTED_AXIS = {AAP_NONE: 2, AAP_XY: 2, AAP_YZ: 0, AAP_XZ: 1}              # the axis the interior test drops (Q12)
+MIN_PROJECTED_NORMAL = 0.05       # below this component of the unit normal a triangle's projection counts as degenerate
+
+BK7_B = (1.03961212, 0.231792344, 1.01046945)             # Schott N-BK7, Sellmeier coefficients (C in um^2)
+BK7_C = (0.00600069867, 0.0200179144, 103.560653)
+
+
+# ---- hits ---------------------------------------------------------------------------------------------------------------------
+def f64(a):
+    """float32 values widened to float64 (the inputs are what the renderer gets, not what a float64 builder meant)"""
+    return np.asarray(a, np.float32).astype(np.float64)
+
+
+def normals(V):
+    """unnormalised and unit normals (v1 - v0) x (v2 - v0) of triangles V (n, 3, 3)"""
+    n = np.cross(V[:, 1] - V[:, 0], V[:, 2] - V[:, 0])
+    with np.errstate(all="ignore"):
+        return n, n / np.linalg.norm(n, axis=1)[:, None]
+
+
+BARY_ROUNDING = 1e-12   # the truth's own float64 rounding: a point this close to an edge belongs to the triangles on both sides of it
+
+
+def _scan(V, o, d):
+    V, o, d = np.asarray(V, np.float64), np.asarray(o, np.float64), np.asarray(d, np.float64)
+    m = o.shape[0]
+    best_t, best_i, best_b, near = np.full(m, np.inf), np.full(m, -1, np.int64), np.full(m, np.nan), np.full(m, np.inf)
+    all_t = np.full((V.shape[0], m), np.inf)
+    e1, e2 = V[:, 1] - V[:, 0], V[:, 2] - V[:, 0]
+    with np.errstate(all="ignore"):
+        for k in range(V.shape[0]):
+            p = np.cross(d, e2[k])
+            det = p @ e1[k]
+            inv = 1.0 / det
+            tv = o - V[k, 0]
+            u = (tv * p).sum(1) * inv
+            q = np.cross(tv, e1[k])
+            v = (d * q).sum(1) * inv
+            t = (q @ e2[k]) * inv
+            mb = np.minimum(np.minimum(u, v), 1.0 - u - v)
+            ok = (det != 0) & np.isfinite(t) & (t >= 0)
+            near = np.where(ok & (np.abs(mb) < near), np.abs(mb), near)
+            inside = ok & (mb >= -BARY_ROUNDING)
+            all_t[k] = np.where(inside, t, np.inf)
+            hit = inside & (t < best_t)
+            best_t = np.where(hit, t, best_t); best_i = np.where(hit, k, best_i); best_b = np.where(hit, mb, best_b)
+    return best_t, best_i, best_b, near, all_t
+
+
+def closest_hit(V, o, d):
+    """Two-sided Moeller-Trumbore of rays (o, d) (m, 3) against ALL triangles V (n, 3, 3), t >= 0, brute force.
+    Returns t (inf on a miss), tri (-1 on a miss), bary = the smallest barycentric coordinate at the hit (NaN on a miss) and
+    near = the smallest |min barycentric| over every triangle PLANE the ray meets at t >= 0: how close the ray passes to any edge
+    of any triangle, hit or not (inf when it meets no plane)."""
+    return _scan(V, o, d)[:4]
+
+
+def later_crossings(V, o, d):
+    """per ray, the number of triangles it passes through clearly BEHIND its closest hit (t > t_closest + 1e-3 (1 + t_closest))"""
+    t, _, _, _, all_t = _scan(V, o, d)
+    with np.errstate(all="ignore"):
+        return (np.isfinite(all_t) & (all_t > (t + 1e-3 * (1 + t))[None, :])).sum(0)
+
+
+def plane_t(V, k, o, d):
+    """t at which rays (o, d) meet the plane of triangle k[i] of V, float64"""
+    V = np.asarray(V, np.float64)
+    n, _ = normals(V)
+    nk = n[k]
+    with np.errstate(all="ignore"):
+        return ((V[k, 0] - o) * nk).sum(1) / (nk * d).sum(1)
+
+
+def t_bound(n, v0, o, d, t):
+    """A-priori float32 error bound of t = (D - n.o) / (n.d), D = n.v0, up to its constant factor c (measured on the oracle, fixed at
+    twice the measurement: tests/test_ground_truth_reference.py): u (sum|n_k v0_k| + sum|n_k o_k| + t sum|n_k d_k|) / |n.d|.
+    Every rounding in D, in n.o and in their difference is bounded by u times the first two sums; those of n.d and of the quotient by
+    u t times the third.  n: unit normals, one per ray."""
+    n, v0, o, d, t = (np.asarray(a, np.float64) for a in (n, v0, o, d, t))
+    num = np.abs(n * v0).sum(-1) + np.abs(n * o).sum(-1) + t * np.abs(n * d).sum(-1)
+    return U * num / np.abs((n * d).sum(-1))
+
+
+def front_face(V, tri, d):
+    """front_face of the reference's hit record: the ray runs against the triangle's normal (v1 - v0) x (v2 - v0)"""
+    n, _ = normals(np.asarray(V, np.float64))
+    return (n[tri] * d).sum(1) < 0
+
+
+def effective_aa_plane(V, aa_plane):
+    """the projection plane tri::init leaves a triangle with (Q12): the plane of an axis-aligned normal, else the value it came with"""
+    _, nu = normals(np.asarray(V, np.float64))
+    perp = np.abs(nu) < 1e-8
+    out = np.array(aa_plane, np.int64).copy()
+    out[perp[:, 1] & perp[:, 2]] = AAP_YZ
+    out[perp[:, 0] & perp[:, 2] & ~(perp[:, 1] & perp[:, 2])] = AAP_XZ
+    out[perp[:, 0] & perp[:, 1] & ~perp[:, 2]] = AAP_XY
+    return out
+
+
+def projected_normal(V, aa_plane):
+    """|component of the unit normal along the axis the interior test drops|: 0 means the projected triangle is a segment"""
+    _, nu = normals(np.asarray(V, np.float64))
+    ax = np.array([PROJECTED_AXIS[int(a)] for a in effective_aa_plane(V, aa_plane)])
+    with np.errstate(all="ignore"):
+        return np.where(np.isfinite(nu).all(1), np.abs(nu[np.arange(len(ax)), ax]), 0.0)
+
+
+def compare_hits(V, rays, got, mat_of_tri=None):
+    """An implementation's closest hits `got` (m, 4: t, -1 on a miss, front_face, mat_index -- the layout of srt_trace_rays) against the
+    truth for the same float32 rays (m, 6).  mat_of_tri: the material of every triangle (default: its own number, the builders' rule).
+    Returns a dict of per-ray arrays: want_hit, got_hit, same (hit / miss and the material of the triangle hit agree), both (both hit the
+    same material), ratio = |t - t_truth| / t_bound and front_ok where `both`, near, tri (the truth's)."""
+    V = np.asarray(V, np.float64)
+    o, d = f64(rays[:, :3]), f64(rays[:, 3:])
+    t, tri, _, near = closest_hit(V, o, d)
+    mat_of_tri = np.arange(len(V)) if mat_of_tri is None else np.asarray(mat_of_tri)
+    want_hit, got_hit = tri >= 0, got[:, 1] >= 0
+    both = want_hit & got_hit & (got[:, 3].astype(np.int64) == mat_of_tri[np.maximum(tri, 0)])
+    same = both | (~want_hit & ~got_hit)
+    _, nu = normals(V)
+    k = np.maximum(tri, 0)
+    with np.errstate(all="ignore"):
+        ratio = np.where(both, np.abs(got[:, 0].astype(np.float64) - t) / t_bound(nu[k], V[k, 0], o, d, t), 0.0)
+    front_ok = ~both | ((got[:, 2] != 0) == front_face(V, k, d))
+    return dict(want_hit=want_hit, got_hit=got_hit, same=same, both=both, ratio=ratio, front_ok=front_ok, near=near, tri=tri, t=t)
+
+
+# Measured on the oracle by tests/test_ground_truth_reference.py (the numbers stand in its docstrings and in DESIGN section 2):
+C_T = 6.9               # twice the largest |t - t_truth| / t_bound over all agreeing hits (measured 3.44, on a sliver triangle)
+EDGE_MARGIN = 1.7e-6    # four times the largest `near` of a ray on which oracle and truth disagree (measured 4.23e-7, edge-aimed rays)
+MAX_EXCLUDED = 0.005    # at most this share of a random population may lie inside the margin
+
+
+def assert_hits_hold(V, rays, got, what, mat_of_tri=None):
+    """the conditions of the random populations: every ray at least EDGE_MARGIN from every edge agrees with the truth in hit / miss and in
+    the triangle; every agreeing hit has |t - t_truth| <= C_T t_bound and the truth's front_face; at most MAX_EXCLUDED of the rays are
+    left out.  Returns the comparison and a summary for the test's printed line."""
+    r = compare_hits(V, rays, got, mat_of_tri)
+    held = r["near"] >= EDGE_MARGIN
+    bad = held & ~r["same"]
+    assert not bad.any(), "%s: %d rays away from every edge differ from the truth, first %d" % (what, bad.sum(), np.nonzero(bad)[0][0])
+    assert r["ratio"].max() <= C_T, "%s: |dt| / t_bound = %.3g at ray %d" % (what, r["ratio"].max(), r["ratio"].argmax())
+    assert r["front_ok"].all(), "%s: front_face differs from sign(n.d) at ray %d" % (what, np.nonzero(~r["front_ok"])[0][0])
+    assert (~held).mean() <= MAX_EXCLUDED, "%s: %.3g of the rays lie inside the edge margin" % (what, (~held).mean())
+    summary = dict(rays=len(rays), hit_share=float(r["want_hit"].mean()), excluded=int((~held).sum()), differ=int((~r["same"]).sum()),
+                   max_ratio=float(r["ratio"].max()), max_near_differ=float(r["near"][~r["same"]].max()) if (~r["same"]).any() else 0.0)
+    return r, summary
+
+
+def assert_edge_aimed_hold(V, rays, adjacent, got, what):
+    """the conditions of the edge-aimed rays: a ray hits a triangle adjacent to its target, within the t bound, or it misses (a leak);
+    it never hits another triangle.  Returns the leak share."""
+    r = compare_hits(V, rays, got)
+    hit = got[:, 1] >= 0
+    tri = got[:, 3].astype(np.int64)
+    ok = ~hit | adjacent[np.arange(len(rays)), np.clip(tri, 0, adjacent.shape[1] - 1)]
+    assert ok.all(), "%s: ray %d hits triangle %d, not adjacent to its target" % (what, np.nonzero(~ok)[0][0], tri[np.nonzero(~ok)[0][0]])
+    # t against the plane of the triangle actually hit (the truth may have picked the neighbour across the edge)
+    o, d = f64(rays[:, :3]), f64(rays[:, 3:])
+    Vd = np.asarray(V, np.float64)
+    k = np.where(hit, tri, 0)
+    tp = plane_t(Vd, k, o, d)
+    _, nu = normals(Vd)
+    with np.errstate(all="ignore"):
+        ratio = np.where(hit, np.abs(got[:, 0].astype(np.float64) - tp) / t_bound(nu[k], Vd[k, 0], o, d, tp), 0.0)
+    assert ratio.max() <= C_T, "%s: |dt| / t_bound = %.3g at ray %d" % (what, ratio.max(), ratio.argmax())
+    assert r["want_hit"].all()
+    return dict(rays=len(rays), leaks=int((~hit).sum()), leak_share=float((~hit).mean()), max_ratio=float(ratio.max()),
+                max_near_leak=float(r["near"][~hit].max()) if (~hit).any() else 0.0)
+
+
+# ---- radiometry ---------------------------------------------------------------------------------------------------------------
+def interp(table, lam):
+    """linear interpolation of a 95-sample table on the 5 nm grid"""
+    x = (np.asarray(lam, np.float64) - LAMBDA_MIN) / 5.0
+    i = np.clip(np.floor(x).astype(np.int64), 0, N_GRID - 2)
+    w = x - i
+    return (1.0 - w) * table[i] + w * table[i + 1]
+
+
+def path_wavelengths(h):
+    """the seven wavelengths of a path with hero wavelength h: h + i 470/7 wrapped into [360, 830]"""
+    lam = np.asarray(h, np.float64)[None, :] + np.arange(N_WAVELENGTHS)[:, None] * STEP
+    return np.where(lam > LAMBDA_MAX, LAMBDA_MIN + (lam - LAMBDA_MAX), lam)
+
+
+def path_moments(cmf, factors, hero_only=False, prob=None, nodes=200000):
+    """E and Var (3,) of ONE path's XYZ contribution when every contributing path ends with the power spectrum p = product of the
+    linear interpolants of `factors` (95-sample tables).  The hero wavelength h is uniform on [360, 830]; each of the path's seven
+    wavelengths adds cmf(l) p(l) 470/7, so E = integral of cmf p over the grid.  hero_only: the path carries h alone (after a
+    refraction) and adds cmf(h) p(h) 470/7.  prob: a function of h, the probability that the path contributes at all (it adds 0
+    otherwise).  Midpoint quadrature over h with `nodes` nodes; cmf: rows x, y, z of the colour tables, (3, 95) float64."""
+    h = LAMBDA_MIN + (np.arange(nodes) + 0.5) * (LAMBDA_MAX - LAMBDA_MIN) / nodes
+    lam = h[None, :] if hero_only else path_wavelengths(h)
+    p = np.ones_like(lam)
+    for tab in factors:
+        p = p * interp(np.asarray(tab, np.float64), lam)
+    f = np.stack([(interp(cmf[c], lam) * p).sum(0) * STEP for c in range(3)])
+    w = np.ones_like(h) if prob is None else prob(h)
+    E = (f * w).mean(1)
+    return E, (f * f * w).mean(1) - E * E
+
+
+def exact_integral(cmf, factors):
+    """integral over [360, 830] of cmf times the interpolants of `factors`, (3,): three-point Gauss-Legendre in every 5 nm cell, exact
+    for the piecewise polynomial of degree 1 + len(factors) <= 5 the integrand is"""
+    assert 1 + len(factors) <= 5
+    x = np.array([-np.sqrt(0.6), 0.0, np.sqrt(0.6)]) * 0.5 + 0.5
+    wq = np.array([5.0, 8.0, 5.0]) / 18.0
+    out = np.zeros(3)
+    for s, w in zip(x, wq):
+        p = np.ones(N_GRID - 1)
+        for tab in factors:
+            tab = np.asarray(tab, np.float64)
+            p = p * ((1 - s) * tab[:-1] + s * tab[1:])
+        out += w * 5.0 * (((1 - s) * cmf[:3, :-1] + s * cmf[:3, 1:]) * p).sum(1)
+    return out
+
+
+def sellmeier_index(B, C, lam_nm):
+    """n(lambda) of the Sellmeier formula, lambda in nm, C in um^2"""
+    l2 = (np.asarray(lam_nm, np.float64) * 1e-3) ** 2
+    return np.sqrt(1.0 + sum(b * l2 / (l2 - c) for b, c in zip(B, C)))
+
+
+def schlick(cosine, ref_idx):
+    """Schlick's term as the reference documents it (materials/material.cu:39-53): ref_idx is the refraction RATIO of the interface,
+    the cosine is taken on the incoming side"""
+    r0 = ((1.0 - ref_idx) / (1.0 + ref_idx)) ** 2
+    return r0 + (1.0 - r0) * (1.0 - cosine) ** 5
+
+
+def slab_transmission(n, cos_in, bounce_limit):
+    """Probability that a path entering a plane-parallel slab of index n at cos_in leaves through the far face and reaches an emitter
+    behind it within the bounce limit: (1 - R1)(1 - R2) sum_{k <= K} R2^(2k).  R1 = Schlick(cos_in, 1/n) entering; inside, every
+    interface is met at the refracted angle with ratio n, R2 = Schlick(cos_t, n).  A path with k internal round trips needs 3 + 2k hits."""
+    sin_t = np.sqrt(1.0 - cos_in ** 2) / n
+    cos_t = np.sqrt(1.0 - sin_t ** 2)
+    R1, R2 = schlick(cos_in, 1.0 / n), schlick(cos_t, n)
+    K = (bounce_limit - 3) // 2
+    assert K >= 0 and np.all(n * sin_t <= 1.0)
+    return (1.0 - R1) * (1.0 - R2) * sum(R2 ** (2 * k) for k in range(K + 1))
+
+
+def form_factor(x, n, polygon):
+    """Lambert's closed form for the cosine-weighted form factor of a planar polygon (k, 3) seen from points x (m, 3) with unit normal n:
+    F = |sum_i gamma_i (r_i x r_i+1) . n / |r_i x r_i+1|| / (2 pi), gamma_i the angle the edge subtends.  F is the probability that a
+    cosine-distributed direction about n hits the polygon.  The polygon must lie wholly above the receiver's horizon."""
+    x, n, polygon = np.asarray(x, np.float64), np.asarray(n, np.float64), np.asarray(polygon, np.float64)
+    r = polygon[None, :, :] - x[:, None, :]
+    assert ((r @ n) > 0).all(), "form_factor: polygon below the horizon"
+    r = r / np.linalg.norm(r, axis=2)[:, :, None]
+    F = np.zeros(x.shape[0])
+    k = polygon.shape[0]
+    for i in range(k):
+        a, b = r[:, i], r[:, (i + 1) % k]
+        cr = np.cross(a, b)
+        nc = np.linalg.norm(cr, axis=1)
+        F += np.arctan2(nc, (a * b).sum(1)) * (cr @ n) / nc
+    return np.abs(F) / (2.0 * np.pi)
+
+
+# ---- pixels -------------------------------------------------------------------------------------------------------------------
+def lane_index(W, H, tx=TX, ty=TY):
+    """index of pixel (x, y) in the block-linear planes of a W x H frame (blocks of tx x ty, W // tx + 1 blocks per row), shape (H, W)"""
+    bx = W // tx + 1
+    y, x = np.mgrid[0:H, 0:W]
+    return ((y // ty) * bx + x // tx) * tx * ty + (y % ty) * tx + x % tx
+
+
+def camera_arrays(cam):
+    """eye, pixel00, delta_u, delta_v of a camera struct, float64"""
+    g = lambda name: np.array(getattr(cam, name)[:], np.float64)
+    return g("camera_center"), g("pixel00_loc"), g("pixel_delta_u"), g("pixel_delta_v")
+
+
+def pixel_rays(cam, W, H, fx=0.0, fy=0.0):
+    """origin (3,) and directions (H * W, 3) of the rays through pixel (i + fx, j + fy), row-major; (0, 0) is the pixel centre"""
+    eye, p00, du, dv = camera_arrays(cam)
+    j, i = np.mgrid[0:H, 0:W]
+    px = p00[None, :] + (i.ravel()[:, None] + fx) * du[None, :] + (j.ravel()[:, None] + fy) * dv[None, :]
+    return eye, px - eye[None, :]
+
+
+def footprint_average(fn, cam, W, H, k):
+    """average of fn(eye, directions) -> (H * W,) over every pixel's jitter square, k x k midpoint sub-samples"""
+    acc = np.zeros(W * H)
+    for a in range(k):
+        for b in range(k):
+            eye, d = pixel_rays(cam, W, H, (a + 0.5) / k - 0.5, (b + 0.5) / k - 0.5)
+            acc += fn(eye, d)
+    return acc / (k * k)
+
+
+def project_points(cam, P):
+    """perspective projection of points P (k, 3) into continuous pixel coordinates (i, j): pixel (x, y) is the square
+    [x - 0.5, x + 0.5] x [y - 0.5, y + 0.5].  Also returns the depth s (eye + s (P - eye) lies on the image plane; s > 0 in front)."""
+    eye, p00, du, dv = camera_arrays(cam)
+    out = np.zeros((len(P), 2)); depth = np.zeros(len(P))
+    for k, p in enumerate(np.asarray(P, np.float64)):
+        i, j, s = np.linalg.solve(np.stack([du, dv, -(p - eye)], axis=1), eye - p00)
+        out[k] = (i, j); depth[k] = s
+    return out, depth
+
+
+def polygon_area(Q):
+    """area of a planar polygon (k, 2), shoelace formula"""
+    x, y = Q[:, 0], Q[:, 1]
+    return 0.5 * abs(np.dot(x, np.roll(y, -1)) - np.dot(y, np.roll(x, -1)))
+
+
+def coverage_map(Q, W, H, k):
+    """share of every pixel's square inside the triangle Q (3, 2) of pixel coordinates, k x k midpoint sub-samples, shape (H * W,)"""
+    j, i = np.mgrid[0:H, 0:W]
+    acc = np.zeros(W * H)
+    e = lambda a, b, px, py: (b[0] - a[0]) * (py - a[1]) - (b[1] - a[1]) * (px - a[0])
+    for a in range(k):
+        for b in range(k):
+            px, py = i.ravel() + (a + 0.5) / k - 0.5, j.ravel() + (b + 0.5) / k - 0.5
+            s = [e(Q[0], Q[1], px, py), e(Q[1], Q[2], px, py), e(Q[2], Q[0], px, py)]
+            acc += (((s[0] >= 0) & (s[1] >= 0) & (s[2] >= 0)) | ((s[0] <= 0) & (s[1] <= 0) & (s[2] <= 0)))
+    return acc / (k * k)
+
+
+def mirror_y(P):
+    """points mirrored in the plane y = 0"""
+    return np.asarray(P, np.float64) * np.array([1.0, -1.0, 1.0])
+
+
+def z_scores(xyz_planes, W, H, spp, E, Var, min_expected=None, p_contribute=None, E_sum=None):
+    """z_img (3,) = (sum measured - sum E) / sqrt(sum Var / spp) of the per-pixel means, the allowance sum E spp 2^-24 of the float32
+    sums in the same units, the per-pixel z (3, n) over the pixels with spp P(contribute) >= min_expected (all if None).
+    xyz_planes: the three block-linear planes of XYZ sums; E, Var: (3,) or (3, H * W) per path; E_sum: the image total of E where a
+    closed form knows it better than the sum of the sub-sampled per-pixel values (the mirror's projected area)."""
+    ln = lane_index(W, H).ravel()
+    E = np.broadcast_to(np.asarray(E, np.float64).reshape(3, -1), (3, W * H))
+    Var = np.broadcast_to(np.asarray(Var, np.float64).reshape(3, -1), (3, W * H))
+    m = np.stack([np.asarray(xyz_planes[c], np.float64)[ln] / spp for c in range(3)])
+    sigma = np.sqrt(Var.sum(1) / spp)
+    total = E.sum(1) if E_sum is None else np.asarray(E_sum, np.float64)
+    z_img = (m.sum(1) - total) / sigma
+    allowance = spp * U * np.abs(total) / sigma
+    sel = np.ones(W * H, bool) if min_expected is None else spp * np.asarray(p_contribute) >= min_expected
+    with np.errstate(all="ignore"):
+        z_px = (m[:, sel] - E[:, sel]) / np.sqrt(Var[:, sel] / spp)
+    return z_img, allowance, z_px
+
+
+# ---- spectra ------------------------------------------------------------------------------------------------------------------
+def ramp(lo=0.2, hi=0.9):
+    return np.linspace(lo, hi, N_GRID).astype(np.float32)
+
+
+def bump(base=0.3, height=0.6, centre=560.0, width=60.0):
+    lam = LAMBDA_MIN + 5.0 * np.arange(N_GRID)
+    return (base + height * np.exp(-0.5 * ((lam - centre) / width) ** 2)).astype(np.float32)
+
+
+def baked_emission(d65n, power):
+    """what the reference bakes for a white emitter of the given power: power^2 D65n, sampled at 360 + i 470/95 (Q4: the bake steps by
+    470/95 while the grid it is read back on steps by 470/94), float64"""
+    lam = LAMBDA_MIN + np.arange(N_GRID) * (LAMBDA_MAX - LAMBDA_MIN) / N_GRID
+    return float(power) ** 2 * interp(np.asarray(d65n, np.float64), lam)
+
+
+# ---- scenes on raw arrays -----------------------------------------------------------------------------------------------------
+def material(mtype, spectrum, fuzz=0.0, power=0.0, B=BK7_B, C=BK7_C, bake=False, col=(1.0, 1.0, 1.0)):
+    """one material; spectrum: 95 floats set DIRECTLY into spectral_distribution (bake=True: left to the implementation's own bake of
+    `col` / `power`, for the test of that bake)"""
+    return dict(type=int(mtype), spectrum=None if bake else np.asarray(spectrum, np.float32), fuzz=float(fuzz), power=float(power),
+                B=tuple(B), C=tuple(C), bake=bool(bake), col=tuple(col))
+
+
+def scene(V, mats, mat_index=None, aa_plane=None, background=None):
+    """a scene as plain arrays: V (n, 3, 3) float32; mat_index defaults to one material per triangle (mat_index then NAMES the triangle
+    hit: mats may be one material, repeated); background: 95 floats, default black"""
+    V = np.asarray(V, np.float32).reshape(-1, 3, 3)
+    n = V.shape[0]
+    if mat_index is None:
+        mat_index = np.arange(n)
+        if len(mats) == 1:
+            mats = list(mats) * n
+    assert len(mat_index) == n and max(mat_index) < len(mats)
+    return dict(V=V, mats=list(mats), mat_index=np.asarray(mat_index, np.int64),
+                aa_plane=np.zeros(n, np.int64) if aa_plane is None else np.asarray(aa_plane, np.int64),
+                background=np.zeros(N_GRID, np.float32) if background is None else np.asarray(background, np.float32))
+
+
+def to_structs(sc, TriIn, Material, bake):
+    """ctypes arrays (TriIn * n, Material * m) and the background of a scene, in the caller's struct classes; bake(byref-able Material)
+    is called for the materials that ask for the implementation's own bake"""
+    T = (TriIn * len(sc["V"]))()
+    for k, v in enumerate(sc["V"]):
+        T[k].v0[:] = [float(x) for x in v[0]]; T[k].v1[:] = [float(x) for x in v[1]]; T[k].v2[:] = [float(x) for x in v[2]]
+        T[k].mat_index = int(sc["mat_index"][k]); T[k].aa_plane = int(sc["aa_plane"][k])
+    M = (Material * len(sc["mats"]))()
+    for k, m in enumerate(sc["mats"]):
+        M[k].col[:] = m["col"]; M[k].reflection_fuzz = m["fuzz"]; M[k].material_type = m["type"]; M[k].emission_power = m["power"]
+        M[k].sellmeier_B[:] = m["B"]; M[k].sellmeier_C[:] = m["C"]
+        if m["bake"]:
+            bake(M[k])
+        else:
+            M[k].spectral_distribution[:] = [float(x) for x in m["spectrum"]]
+    return T, M, sc["background"]
+
+
+def product_scene(srt, sc, mode, seed=1984):
+    """the scene handed to the package `srt` (passed in: nothing is imported here) through its raw-array boundary, tree built by `mode`"""
+    import ctypes as C
+    B = srt.binding
+    T, M, bg = to_structs(sc, B.TriIn, B.Material, lambda m: B.check(B.lib().srt_material_bake(C.byref(m))))
+    return srt.Scene.from_arrays(T, M, bg).build_bvh(mode, seed)
+
+
+def color_tables(srt):
+    """rows x, y, z, normalised D65 of srt_color_tables, (4, 95) float64"""
+    B = srt.binding
+    cmf, m = np.zeros(N_GRID * 4, np.float32), np.zeros(9, np.float32)
+    B.check(B.lib().srt_color_tables(B.fptr(cmf), B.fptr(m)))
+    return cmf.reshape(N_GRID, 4).T.astype(np.float64)
+
+
+GREY = material(MAT_LAMBERTIAN, ramp())
+
+
+def quad(a, b, c, d):
+    """two triangles a b c, a c d"""
+    return [[a, b, c], [a, c, d]]
+
+
+def soup(seed, n, spread):
+    """n random triangles: vertices normally spread about centres in [-5, 5]^3; triangles whose projection (XY: aa_plane NONE) is
+    degenerate (|n_z| < 0.05) are drawn again"""
+    rng = np.random.default_rng(seed)
+    V = np.zeros((n, 3, 3), np.float32)
+    k = 0
+    while k < n:
+        v = (rng.uniform(-5, 5, 3)[None, :] + rng.normal(0, spread, (3, 3))).astype(np.float32)
+        if projected_normal(v[None], [AAP_NONE])[0] >= MIN_PROJECTED_NORMAL:
+            V[k] = v; k += 1
+    return scene(V, [GREY])
+
+
+SHEET_N = 12
+
+
+def sheet_vertices(seed=7, n=SHEET_N):
+    """(n + 1)^2 vertices of a bumpy sheet over [-5, 5]^2: grid points moved by +-0.15 in x and y, z = bumps of +-0.25 (a height
+    field: every |n_z| is far above 0.05, and a ray steeper than its slopes crosses it once)"""
+    rng = np.random.default_rng(seed)
+    g = np.linspace(-5, 5, n + 1)
+    x, y = np.meshgrid(g, g, indexing="ij")
+    x = x + np.where((np.abs(x) < 5), rng.uniform(-0.15, 0.15, x.shape), 0)
+    y = y + np.where((np.abs(y) < 5), rng.uniform(-0.15, 0.15, y.shape), 0)
+    return np.stack([x, y, rng.uniform(-0.25, 0.25, x.shape)], axis=-1).astype(np.float32)
+
+
+def bumpy_sheet(seed=7, n=SHEET_N):
+    """closed n x n sheet of 2 n^2 triangles sharing the grid's vertices bit for bit.  Returns the scene and idx (2 n^2, 3), the grid
+    vertex numbers (a * (n + 1) + b) of every triangle."""
+    P = sheet_vertices(seed, n)
+    vid = lambda a, b: a * (n + 1) + b
+    idx = []
+    for a in range(n):
+        for b in range(n):
+            idx += [(vid(a, b), vid(a + 1, b), vid(a + 1, b + 1)), (vid(a, b), vid(a + 1, b + 1), vid(a, b + 1))]
+    idx = np.array(idx)
+    return scene(P.reshape(-1, 3)[idx], [GREY]), idx
+
+
+def random_rays(seed, m):
+    """m rays from origins in [-12, 12]^3 aimed at points of [-5, 5]^3, float32 (m, 6)"""
+    rng = np.random.default_rng(seed)
+    o = rng.uniform(-12, 12, (m, 3)).astype(np.float32)
+    tgt = rng.uniform(-5, 5, (m, 3)).astype(np.float32)
+    return np.concatenate([o, tgt - o], axis=1).astype(np.float32)
+
+
+def edge_aimed_rays(seed=17, reps=8):
+    """rays aimed EXACTLY (up to the float32 rounding of the direction) at interior vertices, interior edge midpoints and random points
+    of interior edges of the bumpy sheet, `reps` origins per target, from either side and steeper than the sheet's slopes (one
+    crossing).  Returns rays (m, 6) and, per ray, the boolean row of the triangles adjacent to its target: those that share the
+    vertex, or both ends of the edge -- every triangle that contains the target point."""
+    sc, idx = bumpy_sheet()
+    n = SHEET_N
+    P = sheet_vertices().reshape(-1, 3).astype(np.float64)
+    rng = np.random.default_rng(seed)
+    interior = lambda v: 0 < v // (n + 1) < n and 0 < v % (n + 1) < n
+    edges = set()
+    for tri in idx:
+        for a, b in ((0, 1), (1, 2), (2, 0)):
+            e = (min(tri[a], tri[b]), max(tri[a], tri[b]))
+            if interior(e[0]) or interior(e[1]):
+                edges.add(e)
+    edges = sorted(edges)
+    targets, adjacent = [], []
+    for v in range((n + 1) ** 2):
+        if interior(v):
+            targets.append(P[v]); adjacent.append((idx == v).any(1))
+    for a, b in edges:
+        both = (idx == a).any(1) & (idx == b).any(1)
+        # a ray aimed at an edge point can, after rounding, pass either side of it, and so through any triangle at the edge
+        for s in [0.5] + list(rng.uniform(0.02, 0.98, 2)):
+            targets.append((1 - s) * P[a] + s * P[b]); adjacent.append(both)
+    targets, adjacent = np.array(targets), np.array(adjacent)
+    targets, adjacent = np.repeat(targets, reps, axis=0), np.repeat(adjacent, reps, axis=0)
+    m = len(targets)
+    o = np.concatenate([targets[:, :2] + rng.uniform(-2.5, 2.5, (m, 2)), rng.choice([-1.0, 1.0], m)[:, None] * rng.uniform(4, 12, (m, 1))], axis=1)
+    o = o.astype(np.float32)
+    d = (targets.astype(np.float32) - o).astype(np.float32)
+    return np.concatenate([o, d], axis=1), adjacent
+
+
+def axis_aligned_set(seed=11):
+    """explicit axis-aligned triangles in the planes XY / YZ / XZ (flagged as such, and flagged NONE: tri::init finds the plane
+    itself), and STICKY ones: rotated about an axis so that the normal is no longer axis aligned while the flag keeps YZ or XZ, as the
+    side quads of PRISM do (Q12).  Every projection is non-degenerate (component >= 0.05)."""
+    rng = np.random.default_rng(seed)
+    V, aa = [], []
+    for plane, axis in ((AAP_XY, 2), (AAP_YZ, 0), (AAP_XZ, 1)):
+        for flag in (plane, AAP_NONE, plane):
+            v = rng.uniform(-4, 4, (3, 3))
+            v[:, axis] = np.float32(rng.uniform(-4, 4))
+            V.append(v); aa.append(flag)
+    for plane, axis in ((AAP_YZ, 0), (AAP_XZ, 1)):
+        for angle in (10.0, 35.0, 60.0, 80.0):
+            v = rng.uniform(-4, 4, (3, 3))
+            v[:, axis] = rng.uniform(-4, 4)
+            c, s = np.cos(np.radians(angle)), np.sin(np.radians(angle))
+            other = 2 if axis == 0 else 0                        # rotate about the remaining axis: the normal tilts from `axis` to `other`
+            a, b = v[:, axis].copy(), v[:, other].copy()
+            v[:, axis], v[:, other] = c * a - s * b, s * a + c * b
+            V.append(v); aa.append(plane)
+    sc = scene(np.array(V), [GREY], aa_plane=aa)
+    assert (projected_normal(sc["V"], sc["aa_plane"]) >= MIN_PROJECTED_NORMAL).all()
+    return sc
+
+
+def degenerate_walls(seed=13, n=60):
+    """n vertical walls (n_z = 0) that are NOT axis aligned: flagged NONE they are projected onto XY, where they are segments"""
+    rng = np.random.default_rng(seed)
+    V = []
+    for _ in range(n):
+        c = rng.uniform(-5, 5, 3); a = rng.uniform(0.3, np.pi / 2 - 0.3) + rng.integers(0, 4) * np.pi / 2
+        e = np.array([np.cos(a), np.sin(a), 0.0]) * rng.uniform(1, 3)
+        V.append([c - e, c + e, c + np.array([0, 0, rng.uniform(1, 3)])])
+    return scene(np.array(V), [GREY])
+
+
+# the random populations of both suites: name -> (scene builder, seed of the N_RAYS rays)
+POPULATIONS = {
+    "soup_30_spread_0.5": (lambda: soup(101, 30, 0.5), 201),
+    "soup_30_spread_2.0": (lambda: soup(102, 30, 2.0), 202),
+    "soup_200_spread_0.5": (lambda: soup(103, 200, 0.5), 203),
+    "soup_200_spread_2.0": (lambda: soup(104, 200, 2.0), 204),
+    "sheet_12x12": (lambda: bumpy_sheet()[0], 205),
+    "axis_aligned_and_sticky": (axis_aligned_set, 206),      # explicit XY / YZ / XZ triangles and rotated ones that keep YZ / XZ (Q12)
+}
+N_RAYS = 20000
+BUILTINS = ("CORNELL", "PRISM", "TRIS")
+_cache = {}
+
+
+def cached(key, make):
+    """scenes, rays and their truth inputs are built once per session and shared (nothing mutates them)"""
+    if key not in _cache:
+        _cache[key] = make()
+    return _cache[key]
+
+
+def population(name):
+    build, seed = POPULATIONS[name]
+    return cached(("pop", name), lambda: (build(), random_rays(seed, N_RAYS)))
+
+
+def builtin_report(srt, scene_id, trace):
+    """4 000 camera rays (pixel centres of the 80 x 50 default view) of a built-in scene of the package `srt` against the truth;
+    trace(scene, rays) -> (m, 4) is the implementation.  A ray DIFFERS when hit / miss or the material differs or t is off by more
+    than C_T t_bound.  Returns the listed triangles (degenerate projection), the number of differing rays and {truth's triangle: count};
+    asserts that every differing ray is near an edge or involves a listed triangle."""
+    scene = srt.Scene.builtin(getattr(srt, "SCENE_" + scene_id)).build_bvh(srt.BVH_REFERENCE, 1984)
+    T = scene.triangles()
+    V = np.array([[t.v0[:], t.v1[:], t.v2[:]] for t in T], np.float32)
+    aa = np.array([t.aa_plane for t in T]); mat = np.array([t.mat_index for t in T])
+    listed = np.nonzero(projected_normal(V, aa) < MIN_PROJECTED_NORMAL)[0]
+    cam = scene.default_camera(80, 50)
+    eye, d = pixel_rays(cam, 80, 50)
+    rays = np.concatenate([np.broadcast_to(eye, d.shape), d], 1).astype(np.float32)
+    got = trace(scene, rays)
+    Vd = f64(V)
+    r = compare_hits(Vd, rays, got, mat)
+    differ = ~r["same"] | (r["ratio"] > C_T)
+    o, dd = f64(rays[:, :3]), f64(rays[:, 3:])
+    involved = np.isin(r["tri"], listed)
+    for k in listed:                 # the implementation hit a listed triangle: its t lies on that plane and its material is that one's
+        tp = plane_t(Vd, np.full(len(rays), k), o, dd)
+        with np.errstate(all="ignore"):
+            involved |= r["got_hit"] & (got[:, 3] == mat[k]) & (np.abs(got[:, 0] - tp) <= 1e-4 * np.abs(tp))
+    unexplained = differ & ~involved & (r["near"] >= EDGE_MARGIN)
+    assert not unexplained.any(), (scene_id, np.nonzero(unexplained)[0][:5], r["tri"][unexplained][:5])
+    by_tri = {}
+    for k in r["tri"][differ]:
+        by_tri[int(k)] = by_tri.get(int(k), 0) + 1
+    return dict(scene=scene_id, triangles=len(V), hit_share=round(float(r["want_hit"].mean()), 3), listed=listed.tolist(),
+                differ=int(differ.sum()), near_edge=int((differ & ~involved).sum()), by_truth_triangle=by_tri)
+
+
+# radiometry scenes: (scene, camera arguments (vfov, eye, look-at), W, H, spp, depth)
+FAR_TRIANGLE = [[[100, 100, 100], [101, 100, 100], [100, 101, 100]]]
+FLOOR = quad([-50, 0, -40], [50, 0, -40], [50, 0, 60], [-50, 0, 60])     # y = 0; its diagonal passes x = 0 at z = 10, outside every view
+
+
+def sky_only():
+    bg = bump(0.2, 0.8, 520.0, 70.0)
+    return scene(FAR_TRIANGLE, [GREY], background=bg), (40.0, (0, 1, 5), (0, 0, 0)), 48, 32, 64, 4
+
+
+def floor_under_sky():
+    return scene(FLOOR, [material(MAT_LAMBERTIAN, ramp())], mat_index=[0, 0], background=bump()), (30.0, (0, 3, 4), (0, 0, 0)), 48, 32, 64, 2
+
+
+WALL_POWER = 2.0
+
+
+def emissive_wall():
+    wall = quad([-50, -40, 0], [50, -40, 0], [50, 60, 0], [-50, 60, 0])
+    return (scene(wall, [material(MAT_EMISSIVE, None, power=WALL_POWER, bake=True)], mat_index=[0, 0]), (30.0, (0, 0, 5), (0, 0, 0)),
+            48, 32, 64, 4)
+
+
+LIGHT = np.array([(-1.0, 2.0, -0.5), (1.5, 2.5, 0.0), (0.0, 1.5, 1.5)], np.float32)
+
+
+def cosine_law():
+    V = FLOOR + [LIGHT]
+    mats = [material(MAT_LAMBERTIAN, ramp()), material(MAT_EMISSIVE, bump(0.5, 6.0, 600.0, 80.0))]
+    return scene(V, mats, mat_index=[0, 0, 1]), (25.0, (0, 1.5, 6), (0, 0, 1.5)), 40, 24, 256, 2
+
+
+MIRROR_LIGHT = np.array([(-0.8, 2.2, -4.6), (0.9, 2.0, -4.2), (0.1, 2.8, -3.4)], np.float32)
+
+
+def mirror():
+    """a perfect mirror floor; the light is outside the view, its mirror image (y -> -y) wholly inside"""
+    V = FLOOR + [MIRROR_LIGHT]
+    mats = [material(MAT_METALLIC, ramp(0.9, 0.3)), material(MAT_EMISSIVE, bump(0.5, 4.0, 480.0, 50.0))]
+    return scene(V, mats, mat_index=[0, 0, 1]), (30.0, (0, 2, 6), (0, 0, 0)), 48, 32, 64, 2
+
+
+SLAB_DEPTH = 16      # the bounce limit: K = 6 internal round trips
+
+
+def slab(incidence_deg, spp):
+    """BK7 slab 0 >= z >= -1 (true Sellmeier C, spectrum 1, outward normals) in front of an emissive wall at z = -5, black background,
+    a 2 degree view onto the origin at the given angle of incidence.  At 55 degrees Schlick's fifth power moves the transmission by
+    2 % against a fourth power: 1 024 samples per pixel put the image's standard error at 0.12 % (64 would leave that at 4 sigma)."""
+    front = quad([-50, -40, 0], [50, -40, 0], [50, 60, 0], [-50, 60, 0])              # normal +z
+    back = quad([-50, -40, -1], [-50, 60, -1], [50, 60, -1], [50, -40, -1])           # normal -z
+    wall = quad([-200, -190, -5], [200, -190, -5], [200, 210, -5], [-200, 210, -5])
+    glass = material(MAT_DIELECTRIC, np.ones(N_GRID, np.float32), B=BK7_B, C=BK7_C)
+    a = np.radians(incidence_deg)
+    eye = (6.0 * np.sin(a), 0.0, 6.0 * np.cos(a))
+    return (scene(front + back + wall, [glass, material(MAT_EMISSIVE, bump(0.5, 3.0, 540.0, 90.0))], mat_index=[0, 0, 0, 0, 1, 1]),
+            (2.0, eye, (0, 0, 0)), 48, 32, spp, SLAB_DEPTH)
+
+
+RADIOMETRY = {"sky_only": sky_only, "floor_under_sky": floor_under_sky, "emissive_wall": emissive_wall, "cosine_law": cosine_law,
+              "mirror": mirror, "slab_0": lambda: slab(0.0, 64), "slab_55": lambda: slab(55.0, 1024)}
+Z_IMG_MAX = 5.0                      # statistical constants, not measurements
+RMS_Z_RANGE = (0.8, 1.2)
+MIN_EXPECTED = 10.0                  # per-pixel z only where spp P(contribute) >= 10
+
+
+def floor_points(eye, d):
+    """where rays from eye meet the plane y = 0; every ray must run downwards onto FLOOR"""
+    assert (d[:, 1] < 0).all()
+    x = eye[None, :] - (eye[1] / d[:, 1])[:, None] * d
+    assert (np.abs(x[:, 0]) < 50).all() and (x[:, 2] > -40).all() and (x[:, 2] < 60).all()
+    return x
+
+
+def expectation(name, cmf, cam, sc, W, H, depth):
+    """closed-form E and Var per path of every pixel ((3,) when all pixels are alike, else (3, H * W)), P = the probability that a path
+    of the pixel contributes (None: 1), E_sum = the exact image total where it is known better than the sum of the per-pixel values"""
+    spec = lambda k: f64(sc["mats"][k]["spectrum"])
+    bg = f64(sc["background"])
+    if name == "sky_only":
+        E, V = path_moments(cmf, [bg])
+        return dict(E=E, Var=V, P=None, E_sum=None)
+    if name == "floor_under_sky":
+        footprint_average(lambda eye, d: floor_points(eye, d)[:, 0], cam, W, H, 2)          # (asserts: every ray lands on the floor)
+        E, V = path_moments(cmf, [spec(0), bg])
+        return dict(E=E, Var=V, P=None, E_sum=None)
+    if name == "emissive_wall":
+        E, V = path_moments(cmf, [baked_emission(cmf[3], sc["mats"][0]["power"])])
+        return dict(E=E, Var=V, P=None, E_sum=None)
+    if name == "cosine_law":
+        E1, V1 = path_moments(cmf, [spec(0), spec(1)])
+        F = footprint_average(lambda eye, d: form_factor(floor_points(eye, d), (0.0, 1.0, 0.0), f64(LIGHT)), cam, W, H, 6)
+        E = E1[:, None] * F[None, :]
+        return dict(E=E, Var=(V1 + E1 ** 2)[:, None] * F[None, :] - E ** 2, P=F, E_sum=None)
+    if name == "mirror":
+        E1, V1 = path_moments(cmf, [spec(0), spec(1)])
+        real, depth_real = project_points(cam, f64(MIRROR_LIGHT))
+        Q, depth_q = project_points(cam, mirror_y(f64(MIRROR_LIGHT)))
+        inside = lambda q: (q[:, 0] > -0.5) & (q[:, 0] < W - 0.5) & (q[:, 1] > -0.5) & (q[:, 1] < H - 0.5)
+        assert (depth_q > 0).all() and inside(Q).all(), "mirror: the virtual triangle must lie wholly inside the view"
+        assert (depth_real > 0).all() and ((real[:, 1] < -0.5).all() or (real[:, 1] > H - 0.5).all()), "mirror: the light itself must be out of view"
+        cov = coverage_map(Q, W, H, 8)
+        E = E1[:, None] * cov[None, :]
+        return dict(E=E, Var=(V1 + E1 ** 2)[:, None] * cov[None, :] - E ** 2, P=cov, E_sum=E1 * polygon_area(Q), area=polygon_area(Q), cov=cov)
+    assert name.startswith("slab_"), name
+    # only transmitted paths contribute, and they carry the hero wavelength alone; the angle of incidence varies a little over the
+    # 2 degree view: moments on 9 cosines spanning the view, interpolated to every pixel's centre ray
+    eye, d = pixel_rays(cam, W, H)
+    cos_px = np.abs(d[:, 2]) / np.linalg.norm(d, axis=1)
+    eye, dc = pixel_rays(cam, W, H, 0.5, 0.5)
+    corners = np.concatenate([np.abs(dc[:, 2]) / np.linalg.norm(dc, axis=1), cos_px])
+    grid = np.linspace(min(corners.min(), cos_px.min()) - 1e-4, min(1.0, corners.max() + 1e-4), 9)
+    em, glass = spec(1), sc["mats"][0]
+    B, C = f64(glass["B"]), f64(glass["C"])
+    mom = [path_moments(cmf, [em], hero_only=True, nodes=50000,
+                        prob=lambda h, c=c: slab_transmission(sellmeier_index(B, C, h), c, depth)) for c in grid]
+    E = np.stack([np.interp(cos_px, grid, [m[0][ch] for m in mom]) for ch in range(3)])
+    Var = np.stack([np.interp(cos_px, grid, [m[1][ch] for m in mom]) for ch in range(3)])
+    return dict(E=E, Var=Var, P=None, E_sum=None)
+
+
+def assert_radiometry_holds(name, xyz_planes, W, H, spp, exp, what):
+    """|z_img| <= 5 + the float32 summation allowance in all three channels, and for the cosine law 0.8 <= rms per-pixel z <= 1.2 over
+    the pixels with spp P >= 10.  Returns the z values for the test's printed line."""
+    z_img, allowance, z_px = z_scores(xyz_planes, W, H, spp, exp["E"], exp["Var"], MIN_EXPECTED if exp["P"] is not None else None,
+                                      exp["P"], exp["E_sum"])
+    out = dict(z_img=[round(float(z), 2) for z in z_img], max_z_px=round(float(np.abs(z_px).max()), 2), pixels=int(z_px.shape[1]),
+               rms_z=[round(float(np.sqrt((z_px[c] ** 2).mean())), 3) for c in range(3)])
+    assert (np.abs(z_img) <= Z_IMG_MAX + allowance).all(), "%s %s: z_img %s" % (what, name, out)
+    if name == "cosine_law":
+        assert z_px.shape[1] >= 100, (what, name, z_px.shape)
+        assert all(RMS_Z_RANGE[0] <= r <= RMS_Z_RANGE[1] for r in out["rms_z"]), "%s %s: rms z %s" % (what, name, out)
+    return out
