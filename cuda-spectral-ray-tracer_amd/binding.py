@@ -87,6 +87,21 @@ class ToneResult(C.Structure):
     _fields_ = [("blown", C.c_uint64), ("crushed", C.c_uint64), ("nonfinite", C.c_uint64)]
 
 
+PRESENT_SOURCES = {"accum": 0, "denoise": 1, "denoise_vg": 2, "denoise_mv": 3, "develop": 4}      # SRT_PRESENT_* (srt_c_api.h)
+
+
+class PresentCfg(C.Structure):
+    """srt_present_cfg: the source of a presented picture, its exposure (metered or given), its tone curve and the configuration of the
+    stage the source runs (srt_c_api.h)"""
+    _fields_ = [("source", C.c_uint32), ("metered", C.c_uint32), ("meter", Meter), ("tone", Tone), ("denoise", Denoise), ("denoise_vg", DenoiseVG),
+                ("response3", C.POINTER(C.c_float)), ("scale", C.c_float), ("reserved", C.c_uint32 * 5)]
+
+
+class PresentResult(C.Structure):
+    """srt_present_result: the metering (zero when the gain was given) and the tone counters of a presented picture (srt_c_api.h)"""
+    _fields_ = [("meter", MeterResult), ("tone", ToneResult)]
+
+
 class TreeTuning(C.Structure):
     """srt_tree_tuning: what srt_tune_tree_for_throughput found and did (srt_c_api.h)"""
     _fields_ = [("pixels_per_lane", C.c_double), ("throughput_bound", C.c_uint32), ("reinsertion", C.c_uint32),
@@ -102,6 +117,7 @@ class TileScheduleInfo(C.Structure):
 
 assert C.sizeof(Denoise) == 32 and C.sizeof(DenoiseVG) == 32
 assert C.sizeof(Meter) == 48 and C.sizeof(MeterResult) == 40 and C.sizeof(Tone) == 32 and C.sizeof(ToneResult) == 24
+assert C.sizeof(PresentCfg) == 184 and C.sizeof(PresentResult) == 64
 assert C.sizeof(Adaptive) == 16 and C.sizeof(TreeTuning) == 40 and C.sizeof(TileScheduleInfo) == 32
 assert C.sizeof(Material) == 428 and C.sizeof(CameraData) == 84 and C.sizeof(TriIn) == 44
 
@@ -170,6 +186,9 @@ PROTOTYPES = {
     "srt_expose_accum": (_i, [_vp, C.POINTER(Tone), _fp, _fp, _fp, C.POINTER(ToneResult), _u32, _u32]),
     "srt_expose_kat": (_i, [_vp, C.POINTER(Tone), _fp, _u32, _u32, _fp, _fp, _fp, C.POINTER(ToneResult)]),
     "srt_expose_last_ms": (_i, [_vp, _fp, _fp]),
+    "srt_present": (_i, [_vp, C.POINTER(PresentCfg), C.POINTER(C.c_uint8), _sz, _u32, _u32, C.POINTER(PresentResult)]),
+    "srt_present_kat": (_i, [_vp, C.POINTER(Tone), _fp, _u32, _u32, C.POINTER(C.c_uint8), C.POINTER(ToneResult)]),
+    "srt_present_last_ms": (_i, [_vp, _fp]),
     "srt_accum_reset_features": (_i, [_vp]),
     "srt_read_features": (_i, [_vp, _fp, _u32, _u32]),
     "srt_accum_reset_adaptive_features": (_i, [_vp, C.POINTER(Adaptive)]),

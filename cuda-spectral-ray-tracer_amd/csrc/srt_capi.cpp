@@ -51,6 +51,24 @@ struct DeviceBuffer {
     explicit operator bool() const { return ptr != nullptr; }
 };
 
+// An owning block of pinned host memory (hipHostMalloc), DeviceBuffer's policy: reserve() never shrinks, and growing loses the contents.
+struct PinnedBuffer {
+    void *ptr = nullptr;
+    size_t bytes = 0;
+    PinnedBuffer() = default;
+    PinnedBuffer(const PinnedBuffer &) = delete;
+    PinnedBuffer &operator=(const PinnedBuffer &) = delete;
+    ~PinnedBuffer() { release(); }
+    void release() { if (ptr) (void)hipHostFree(ptr); ptr = nullptr; bytes = 0; }
+    hipError_t reserve(size_t n) {
+        if (n <= bytes) return hipSuccess;
+        release();
+        const hipError_t e = hipHostMalloc(&ptr, n, hipHostMallocDefault);
+        if (e == hipSuccess) bytes = n; else ptr = nullptr;
+        return e;
+    }
+};
+
 struct srt_ctx {
     int device = 0;
     std::string err;
@@ -155,7 +173,12 @@ struct srt_ctx {
     DeviceBuffer d_expose_out;                          // the tone kernel's three row-major images, grown when the rectangle grows
     hipEvent_t expose_ev[4] = {};                       // around the last meter kernel [0, 1] and the last tone kernel [2, 3] (created on first use)
     bool meter_timed = false, tone_timed = false;
-    DeviceBuffer d_streams;                             // sample-parallel pixels (srt_accum_reset_streams, StreamPlanes)
+    DeviceBuffer d_present;                             // the presented picture: one packed word per pixel, and a developed source's XYZ mean (PresentLayout)
+    PinnedBuffer h_present;                             // its pinned staging block on the host: the packed rectangle, the three tone counters behind it
+    hipEvent_t present_ev[2] = {};                      // around the last present kernel (created on first use)
+    bool present_timed = false;
+    bool present_scalar = false;                        // test knob (env SRT_PRESENT_SCALAR under SRT_TEST_KNOBS=1): present_kernel's scalar path alone
+    DeviceBuffer d_streams;                            // sample-parallel pixels (srt_accum_reset_streams, StreamPlanes)
     uint32_t streams_seeded = 0;                        // the K whose RNG streams d_streams holds, seeded since the last srt_init_device_params (0: none)
 };
 
@@ -581,6 +604,7 @@ int srt_create(int device, srt_ctx **out) {
     if (const char *ev = getenv("SRT_SCORE_FRINGE")) c->score_fringe = (uint32_t)std::max(1, atoi(ev));   // 0 would starve fringe lanes
     if (const char *tk = getenv("SRT_TEST_KNOBS")) if (atoi(tk) == 1) {
         if (const char *ev = getenv("SRT_DEBUG_LANE_LIMIT")) { c->debug_lane_limit = (uint32_t)std::max(0, atoi(ev)); c->knobs_from_env = true; }
+        if (const char *ev = getenv("SRT_PRESENT_SCALAR")) c->present_scalar = atoi(ev) != 0;      // (no render kernel depends on it: not a plan knob)
         if (const char *ev = getenv("SRT_WIDE_REFS")) { c->knobs.wide_refs = atoi(ev) != 0; c->knobs_from_env = true; }
         if (const char *ev = getenv("SRT_LDS_CACHE_MAX")) { c->knobs.lds_cache_max = std::max(0, atoi(ev)); c->knobs_from_env = true; }
     }
@@ -614,7 +638,8 @@ void srt_destroy(srt_ctx *c) {
     for (hipEvent_t e : c->denoise_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->develop_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->expose_ev) if (e) (void)hipEventDestroy(e);
-    delete c;      // (every DeviceBuffer frees itself, on the device selected above)
+    for (hipEvent_t e : c->present_ev) if (e) (void)hipEventDestroy(e);
+    delete c;      // (every DeviceBuffer, and the pinned staging block, frees itself, on the device selected above)
 }
 
 int srt_ctx_device(const srt_ctx *ctx) { return ctx ? ctx->device : -1; }
@@ -1204,6 +1229,14 @@ const char *develop_args_error(const float *response, uint32_t channels, float s
     return nullptr;
 }
 
+// the colour-matching rows x, y, z of srt_color_tables as three response curves [3][kFilmSamples]
+void cie_response_rows(float cie[3 * kFilmSamples]) {
+    float rows[96 * 4];
+    cmf_rows(rows);
+    for (uint32_t k = 0; k < 3; k++)
+        for (uint32_t j = 0; j < kFilmSamples; j++) cie[k * kFilmSamples + j] = rows[4 * j + k];
+}
+
 // grows a working block; a refused allocation is SRT_ERR_HIP and leaves no error behind for the next launch's hipGetLastError
 int develop_reserve(srt_ctx *c, const char *who, DeviceBuffer &d, size_t bytes) {
     if (const hipError_t e = d.reserve(bytes)) {
@@ -1289,10 +1322,7 @@ int srt_develop_spectral_srgb(srt_ctx *c, const float *response3, float scale, f
     // response3 == NULL: the colour-matching rows x, y, z of srt_color_tables
     float cie[3 * kFilmSamples];
     if (!response3) {
-        float rows[96 * 4];
-        cmf_rows(rows);
-        for (uint32_t k = 0; k < 3; k++)
-            for (uint32_t j = 0; j < kFilmSamples; j++) cie[k * kFilmSamples + j] = rows[4 * j + k];
+        cie_response_rows(cie);
         response3 = cie;
     }
     if (const char *why = develop_args_error(response3, 3, scale)) return fail(c, SRT_ERR_INVALID, std::string("srt_develop_spectral_srgb: ") + why);
@@ -1703,7 +1733,8 @@ int run_denoise(srt_ctx *c, const char *who, const DenoisePlan &plan, DenoisePre
 }
 
 // srt_denoise_features / srt_denoise_features_vg behind their argument checks: host[0 .. 2] the three colour outputs, host[3] the variance
-int denoise_features(srt_ctx *c, const char *who, const DenoisePlan &plan, float *const host[4], uint32_t image_width, uint32_t image_height) {
+// what a denoise of the context's accumulation needs of it and of the partition; SRT_OK or the refusal
+int denoise_accumulation_refusal(srt_ctx *c, const char *who, const DenoisePlan &plan) {
     const std::string w_(who);
     if (!c->accum.featured() || !c->accum.bound())
         return fail(c, SRT_ERR_INVALID, w_ + ": no featured accumulation with a pass (srt_accum_reset_features and srt_render_chunk_accum first)");
@@ -1712,19 +1743,29 @@ int denoise_features(srt_ctx *c, const char *who, const DenoisePlan &plan, float
                                              "measured variance of the mean needs S2 and two samples)");
     if (c->rank != 0 || c->world != 1)
         return fail(c, SRT_ERR_UNSUPPORTED, w_ + ": needs the whole chunk on this context (partition (0, 1)): pixels of other ranks read +0");
+    return SRT_OK;
+}
+
+// run_denoise on the accumulation's w x h rectangle (not empty): the results are left in DenoiseLayout(c->d_denoise, w * h)
+int denoise_accumulation(srt_ctx *c, const char *who, const DenoisePlan &plan, uint32_t w, uint32_t h) {
+    HIP_TRY(c, c->d_denoise.reserve(DenoiseLayout::bytes((size_t)w * h, plan.vg)));
+    DenoisePrepassParams pre = {};
+    pre.sums = AccumLayout(c).sums; pre.sum_pixel_stride = 1; pre.sum_comp_stride = c->n_lanes;
+    pre.rows = reinterpret_cast<const float4 *>(feature_rows(c));
+    pre.tx = c->tx; pre.ty = c->ty; pre.bx = c->bx; pre.w = w; pre.h = h; pre.samples = c->accum.total;
+    // (an adaptive featured accumulation: every pixel of the chunk is normalised by its own count, the samples field of its state word)
+    if (c->accum.adaptive()) pre.counts = AdaptPlanes(c).state;
+    return run_denoise(c, who, plan, pre, c->accum.adaptive() ? AdaptPlanes(c).sum2 : nullptr);
+}
+
+int denoise_features(srt_ctx *c, const char *who, const DenoisePlan &plan, float *const host[4], uint32_t image_width, uint32_t image_height) {
+    if (const int rc = denoise_accumulation_refusal(c, who, plan)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     // the filter runs on the chunk's rectangle (clipped to the reference grid); the image clips only what is copied out
     const uint32_t w = clipped_w(c), h = clipped_h(c);
     const size_t pixels = (size_t)w * h;
     if (pixels) {
-        HIP_TRY(c, c->d_denoise.reserve(DenoiseLayout::bytes(pixels, plan.vg)));
-        DenoisePrepassParams pre = {};
-        pre.sums = AccumLayout(c).sums; pre.sum_pixel_stride = 1; pre.sum_comp_stride = c->n_lanes;
-        pre.rows = reinterpret_cast<const float4 *>(feature_rows(c));
-        pre.tx = c->tx; pre.ty = c->ty; pre.bx = c->bx; pre.w = w; pre.h = h; pre.samples = c->accum.total;
-        // (an adaptive featured accumulation: every pixel of the chunk is normalised by its own count, the samples field of its state word)
-        if (c->accum.adaptive()) pre.counts = AdaptPlanes(c).state;
-        if (const int rc = run_denoise(c, who, plan, pre, c->accum.adaptive() ? AdaptPlanes(c).sum2 : nullptr)) return rc;
+        if (const int rc = denoise_accumulation(c, who, plan, w, h)) return rc;
         const ChunkRect rect = chunk_rect(c, image_width, image_height);
         const DenoiseLayout L(c->d_denoise, pixels);
         for (int k = 0; k < 4; k++) {
@@ -2002,6 +2043,170 @@ int srt_denoise_estimate_last_ms(srt_ctx *c, float *ms) {
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipEventSynchronize(c->denoise_ev[2]));
     HIP_TRY(c, hipEventElapsedTime(ms, c->denoise_ev[1], c->denoise_ev[2]));
+    return SRT_OK;
+}
+
+// ---- the presented picture (srt_present.hip) -------------------------------------------------------------------------------------
+namespace {
+
+// d_present: [the packed picture: one word per pixel, padded to 16 bytes | a developed source only: its XYZ mean, three floats per pixel]
+struct PresentLayout {
+    uint32_t *rgba;
+    float *mean;
+    static size_t rgba_bytes(size_t pixels) { return (pixels * sizeof(uint32_t) + 15) & ~(size_t)15; }
+    static size_t bytes(size_t pixels, bool mean) { return rgba_bytes(pixels) + (mean ? 3 * pixels * sizeof(float) : 0); }
+    PresentLayout(const DeviceBuffer &d, size_t pixels) : rgba(d.as<uint32_t>()), mean(reinterpret_cast<float *>(d.as<char>() + rgba_bytes(pixels))) {}
+};
+
+// The present kernel over the w x h rectangle described by p (curve, gain, output and counters are filled in here) into PresentLayout::rgba;
+// then rows [0, copy_h) x columns [0, copy_w) of it and the three counters through the pinned staging block, one synchronise, and the rows
+// into the caller's buffer at `pitch` bytes per row.  d_present and d_expose are reserved by the caller.
+int run_present(srt_ctx *c, const char *who, PresentParams p, const srt_tone *tone, float gain, uint32_t copy_w, uint32_t copy_h, uint8_t *out, size_t pitch,
+                srt_tone_result *result) {
+    const size_t pixels = (size_t)p.w * p.h, row = (size_t)copy_w * sizeof(uint32_t), image = (row * copy_h + 7) & ~(size_t)7;
+    if (const hipError_t e = c->h_present.reserve(image + 3 * sizeof(unsigned long long))) {
+        (void)hipGetLastError();
+        return hip_fail(c, e, who);
+    }
+    const ExposeLayout L(c->d_expose);
+    const PresentLayout I(c->d_present, pixels);
+    c->present_timed = false;
+    for (hipEvent_t &e : c->present_ev) if (!e) HIP_TRY_AS(c, who, hipEventCreate(&e));
+    HIP_TRY_AS(c, who, hipMemsetAsync(L.tone_counts, 0, 3 * sizeof(unsigned long long), nullptr));
+    p.curve = tone->curve; p.gain = gain; p.kw = tone->white * tone->white;
+    p.out = I.rgba; p.counts = L.tone_counts;
+    HIP_TRY_AS(c, who, hipEventRecord(c->present_ev[0], nullptr));
+    HIP_TRY_AS(c, who, launch_present(p, (uint32_t)c->n_cu, !c->present_scalar, nullptr));
+    HIP_TRY_AS(c, who, hipEventRecord(c->present_ev[1], nullptr));
+    c->present_timed = true;
+    char *stage = static_cast<char *>(c->h_present.ptr);
+    if (copy_w && copy_h) {
+        if (copy_w == p.w) HIP_TRY_AS(c, who, hipMemcpyAsync(stage, I.rgba, row * copy_h, hipMemcpyDeviceToHost, nullptr));
+        else HIP_TRY_AS(c, who, hipMemcpy2DAsync(stage, row, I.rgba, (size_t)p.w * sizeof(uint32_t), row, copy_h, hipMemcpyDeviceToHost, nullptr));
+    }
+    HIP_TRY_AS(c, who, hipMemcpyAsync(stage + image, L.tone_counts, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY_AS(c, who, hipStreamSynchronize(nullptr));
+    for (uint32_t j = 0; j < copy_h && copy_w; j++) memcpy(out + j * pitch, stage + j * row, row);
+    unsigned long long counts[3];
+    memcpy(counts, stage + image, sizeof(counts));
+    result->blown = counts[0]; result->crushed = counts[1]; result->nonfinite = counts[2];
+    return SRT_OK;
+}
+
+}  // namespace
+
+int srt_present(srt_ctx *c, const srt_present_cfg *cfg, uint8_t *out_rgba8, size_t pitch_bytes, uint32_t image_width, uint32_t image_height,
+                srt_present_result *result) {
+    const char *who = "srt_present";
+    const std::string w_("srt_present: ");
+    if (!c || !cfg || !out_rgba8) return fail(c, SRT_ERR_INVALID, w_ + "null argument");
+    for (const uint32_t r : cfg->reserved) if (r) return fail(c, SRT_ERR_INVALID, w_ + "the reserved words must be 0");
+    if (cfg->source > SRT_PRESENT_DEVELOP) return fail(c, SRT_ERR_INVALID, w_ + "unknown source (SRT_PRESENT_ACCUM .. SRT_PRESENT_DEVELOP)");
+    if (image_width == 0 || image_height == 0) return fail(c, SRT_ERR_INVALID, w_ + "empty image");
+    if (pitch_bytes < (size_t)image_width * 4) return fail(c, SRT_ERR_INVALID, w_ + "pitch_bytes must be at least 4 * image_width");
+    if (const char *why = tone_cfg_error(&cfg->tone)) return fail(c, SRT_ERR_INVALID, w_ + why);
+    if (cfg->metered) if (const char *why = meter_cfg_error(&cfg->meter)) return fail(c, SRT_ERR_INVALID, w_ + why);
+    const bool denoised = cfg->source == SRT_PRESENT_DENOISE || cfg->source == SRT_PRESENT_DENOISE_VG || cfg->source == SRT_PRESENT_DENOISE_MV;
+    const bool developed = cfg->source == SRT_PRESENT_DEVELOP;
+    DenoisePlan plan = {};
+    if (cfg->source == SRT_PRESENT_DENOISE) {
+        if (const char *why = denoise_cfg_error(&cfg->denoise)) return fail(c, SRT_ERR_INVALID, w_ + why);
+        plan = denoise_plan(&cfg->denoise);
+    } else if (denoised) {
+        if (const char *why = denoise_vg_cfg_error(&cfg->denoise_vg)) return fail(c, SRT_ERR_INVALID, w_ + why);
+        plan = denoise_vg_plan(&cfg->denoise_vg);
+        plan.measured = cfg->source == SRT_PRESENT_DENOISE_MV;
+    }
+    float cie[3 * kFilmSamples];
+    const float *response3 = cfg->response3;
+    if (developed) {
+        if (!response3) {
+            cie_response_rows(cie);
+            response3 = cie;
+        }
+        if (const char *why = develop_args_error(response3, 3, cfg->scale)) return fail(c, SRT_ERR_INVALID, w_ + why);
+    }
+    if (!c->accum.bound()) return fail(c, SRT_ERR_INVALID, w_ + "no accumulation with a pass (srt_accum_reset* and srt_render_chunk_accum first)");
+    if (denoised) if (const int rc = denoise_accumulation_refusal(c, who, plan)) return rc;
+    if (developed && !c->accum.spectral()) return fail(c, SRT_ERR_INVALID, w_ + "SRT_PRESENT_DEVELOP needs a spectral accumulation (srt_accum_reset_spectral*)");
+    uint32_t rect[4] = {0, 0, 0, 0};
+    if (cfg->metered) if (const char *why = meter_rect_error(&cfg->meter, clipped_w(c), clipped_h(c), rect)) return fail(c, SRT_ERR_INVALID, w_ + why);
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the chain runs on the chunk's rectangle (clipped to the reference grid); the image clips only what is copied out
+    const uint32_t w = clipped_w(c), h = clipped_h(c);
+    const size_t pixels = (size_t)w * h;
+    srt_present_result res = {};
+    if (pixels) {
+        if (const int rc = develop_reserve(c, who, c->d_expose, ExposeLayout::kBytes)) return rc;
+        if (const int rc = develop_reserve(c, who, c->d_present, PresentLayout::bytes(pixels, developed))) return rc;
+        const uint32_t *state = c->accum.adaptive() ? AdaptPlanes(c).state : nullptr;
+        // the source: null for the sums themselves, else a [h][w][3] XYZ mean on the device
+        const float *picture = nullptr;
+        if (denoised) {
+            if (const int rc = denoise_accumulation(c, who, plan, w, h)) return rc;
+            picture = DenoiseLayout(c->d_denoise, pixels).out[0];
+        } else if (developed) {
+            if (const int rc = develop_reserve(c, who, c->d_develop, DevelopLayout::bytes(pixels, 3, false))) return rc;
+            if (const int rc = run_develop(c, who, c->d_film.as<float>(), c->n_lanes, c->tx, c->ty, c->bx, w, h, response3, 3, cfg->scale, 0u)) return rc;
+            PresentNormaliseParams np = {};
+            np.developed = DevelopLayout(c->d_develop, pixels, 3).out; np.mean = PresentLayout(c->d_present, pixels).mean;
+            np.counts = state; np.samples = c->accum.total; np.tx = c->tx; np.ty = c->ty; np.bx = c->bx; np.w = w; np.h = h;
+            HIP_TRY_AS(c, who, launch_present_normalise(np, nullptr));
+            picture = np.mean;
+        }
+        float gain = cfg->tone.gain;
+        if (cfg->metered) {
+            MeterParams m = {};
+            if (picture) {      // a grid of one w x h block makes the block-linear lane the row-major pixel, as srt_meter_kat's
+                m.y = picture + 1; m.y_stride = 3; m.samples = 1; m.normalise = 0;
+                m.n_lanes = (uint32_t)pixels; m.tx = w; m.ty = h; m.bx = 1;
+            } else {
+                m.y = AccumLayout(c).y; m.y_stride = 1; m.state = state; m.samples = c->accum.total; m.normalise = 1;
+                m.n_lanes = c->n_lanes; m.tx = c->tx; m.ty = c->ty; m.bx = c->bx;
+            }
+            m.x0 = rect[0]; m.y0 = rect[1]; m.w = rect[2]; m.h = rect[3];
+            m.tiles_x = c->tiles_x; m.rank = c->rank; m.world = c->world;
+            if (const int rc = run_meter(c, who, m, &cfg->meter, nullptr, &res.meter)) return rc;
+            gain = res.meter.gain;
+        }
+        PresentParams p = {};
+        if (picture) p.xyz = picture;
+        else { p.sums = AccumLayout(c).sums; p.comp_stride = c->n_lanes; p.state = state; p.samples = c->accum.total; }
+        p.tx = c->tx; p.ty = c->ty; p.bx = c->bx; p.w = w; p.h = h;
+        p.tiles_x = c->tiles_x; p.rank = c->rank; p.world = c->world;
+        const ChunkRect place = chunk_rect(c, image_width, image_height);
+        uint8_t *first = out_rgba8 + (size_t)c->last_offy * pitch_bytes + (size_t)c->last_offx * 4;      // (not formed into an address when nothing is copied)
+        if (const int rc = run_present(c, who, p, &cfg->tone, gain, place.w, place.h, place.w && place.h ? first : out_rgba8, pitch_bytes, &res.tone)) return rc;
+    }
+    HIP_TRY(c, hipDeviceSynchronize());
+    if (result) *result = res;
+    return SRT_OK;
+}
+
+int srt_present_kat(srt_ctx *c, const srt_tone *tone, const float *xyz_mean, uint32_t w, uint32_t h, uint8_t *out_rgba8, srt_tone_result *result) {
+    const char *who = "srt_present_kat";
+    if (!c || !tone || !xyz_mean || !out_rgba8) return fail(c, SRT_ERR_INVALID, "srt_present_kat: null argument");
+    if (w == 0 || h == 0 || (uint64_t)w * h > 0x7fffffffull) return fail(c, SRT_ERR_INVALID, "srt_present_kat: w x h must be in 1 .. 2^31 - 1");
+    if (const char *why = tone_cfg_error(tone)) return fail(c, SRT_ERR_INVALID, std::string("srt_present_kat: ") + why);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t pixels = (size_t)w * h;
+    if (const int rc = develop_reserve(c, who, c->d_present, PresentLayout::bytes(pixels, false))) return rc;
+    if (const int rc = develop_reserve(c, who, c->d_expose, ExposeLayout::kBytes)) return rc;
+    if (const int rc = upload_kat_xyz(c, who, xyz_mean, w, h)) return rc;
+    PresentParams p = {};
+    p.xyz = c->d_expose_in.as<float>(); p.w = w; p.h = h; p.tiles_x = (w + 7u) / 8u; p.rank = 0; p.world = 1;
+    srt_tone_result res = {};
+    if (const int rc = run_present(c, who, p, tone, tone->gain, w, h, out_rgba8, (size_t)w * 4, &res)) return rc;
+    if (result) *result = res;
+    return SRT_OK;
+}
+
+int srt_present_last_ms(srt_ctx *c, float *ms) {
+    if (!c || !ms) return fail(c, SRT_ERR_INVALID, "srt_present_last_ms: null argument");
+    if (!c->present_timed) return fail(c, SRT_ERR_INVALID, "srt_present_last_ms: no present kernel has run on this context");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipEventSynchronize(c->present_ev[1]));
+    HIP_TRY(c, hipEventElapsedTime(ms, c->present_ev[0], c->present_ev[1]));
     return SRT_OK;
 }
 

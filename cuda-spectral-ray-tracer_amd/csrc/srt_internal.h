@@ -356,6 +356,35 @@ struct ToneParams {
     unsigned long long *counts;
 };
 hipError_t launch_tone(const ToneParams &p, uint32_t n_cu, hipStream_t st);
+// The presented picture (srt_present.hip; stated in srt_c_api.h at srt_present).  present: ToneParams' sources, curve and counters with one
+// output -- out[y * w + x] = R | G << 8 | B << 16 | 255 << 24, the quantised sRGB of tone's out_q as bytes.  vec is the launcher's: groups of
+// four pixels use 16-byte accesses where they are whole and aligned (allow_vector = false: never, the scalar path alone).
+struct PresentParams {
+    const float *sums, *xyz;
+    size_t comp_stride;
+    const uint32_t *state;
+    uint32_t samples;
+    uint32_t tx, ty, bx;
+    uint32_t w, h;
+    uint32_t tiles_x, rank, world;
+    uint32_t curve;
+    float gain, kw;
+    uint32_t vec;
+    uint32_t *out;
+    unsigned long long *counts;
+};
+hipError_t launch_present(const PresentParams &p, uint32_t n_cu, bool allow_vector, hipStream_t st);
+// mean[3 pix + c] = inv * developed[3 pix + c] over the row-major w x h pixels, inv = 1.0f / (float)samples -- with counts the pixel's own
+// count counts[block_linear_idx(x, y, tx, ty, bx)] & ~kAdaptConverged (0 counts as 1), as DevelopSrgbCountsParams::counts is read.
+struct PresentNormaliseParams {
+    const float *developed;
+    float *mean;
+    const uint32_t *counts;
+    uint32_t samples;
+    uint32_t tx, ty, bx;
+    uint32_t w, h;
+};
+hipError_t launch_present_normalise(const PresentNormaliseParams &p, hipStream_t st);
 hipError_t launch_order_tiles(const uint32_t *cost, uint32_t *sorted, uint32_t *rows, uint32_t n, uint32_t n_waves,
                               uint32_t split_load_pct, uint32_t *queue_info, uint32_t order_max_pct, hipStream_t st);
 hipError_t launch_scatter(const ScatterParams &p, hipStream_t st);

@@ -249,6 +249,41 @@ class Renderer:
         self._ck(B.lib().srt_expose_last_ms(self._h, C.byref(a), C.byref(b)))
         return dict(meter=a.value, tone=b.value)
 
+    def present(self, image_width, image_height, source="accum", gain=None, **cfg):
+        """the accumulation's picture presented on the device (srt_present; the arguments of present_config): the source -- the sums, a
+        denoised or a developed picture -- metered (gain=None) or at the given gain, toned, converted and packed without leaving the
+        device: dict(rgba (image_height, image_width, 4) uint8 -- R, G, B and A = 255, written in the chunk's rectangle only, zeros
+        elsewhere --, meter (the dict of meter(), None when a gain was given), clip = dict(blown, crushed, nonfinite)).  The bytes are
+        those of expose()'s / expose_kat()'s fb on the same picture.  Reads the accumulation, changes nothing of it."""
+        p, res = present_config(source, gain, **cfg), B.PresentResult()
+        out = np.zeros((image_height, image_width, 4), np.uint8)
+        self._ck(B.lib().srt_present(self._h, C.byref(p), out.ctypes.data_as(C.POINTER(C.c_uint8)), 4 * image_width, image_width, image_height, C.byref(res)))
+        return dict(rgba=out, meter=_meter_dict(res.meter) if gain is None else None,
+                    clip=dict(blown=res.tone.blown, crushed=res.tone.crushed, nonfinite=res.tone.nonfinite))
+
+    def present_kat(self, xyz_mean, gain=None, **cfg):
+        """present() on an explicit XYZ-mean image (srt_meter_kat when gain is None, then srt_present_kat): xyz_mean (h, w, 3) float32 ->
+        the dict of present() with an (h, w, 4) picture.  Needs no scene and no accumulation."""
+        mcfg, tcfg = _split_expose_cfg(cfg)
+        img = _xyz_image("present_kat", xyz_mean)
+        meter = None
+        if gain is None:
+            tone_config(gain=1.0, **tcfg)
+            meter = self.meter_kat(img, **mcfg)
+            gain = meter["gain"]
+        elif mcfg:
+            raise ValueError("present_kat: %s given with an explicit gain, which is not metered" % ", ".join(sorted(mcfg)))
+        t, res = tone_config(gain=gain, **tcfg), B.ToneResult()
+        out = np.zeros(img.shape[:2] + (4,), np.uint8)
+        self._ck(B.lib().srt_present_kat(self._h, C.byref(t), B.fptr(img), img.shape[1], img.shape[0], out.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(res)))
+        return dict(rgba=out, meter=meter, clip=dict(blown=res.blown, crushed=res.crushed, nonfinite=res.nonfinite))
+
+    def present_last_ms(self):
+        """kernel-only ms of the context's last present kernel (srt_present_last_ms)"""
+        ms = C.c_float()
+        self._ck(B.lib().srt_present_last_ms(self._h, C.byref(ms)))
+        return ms.value
+
     def accum_reset_features(self):
         """start a FEATURED accumulation (srt_c_api.h): like accum_reset, and each later pass also adds, at the first hit of every
         sample's camera ray, the face-forwarded normal, the hit material's colour, the distance and 1 to the pixel's eight raw float32
@@ -1460,3 +1495,84 @@ def _adaptive_spectral_passes(scene, cam, width, height, bounce_limit, acfg, sch
                 yield r.accum_samples, active, out, radiance
             if active == 0:
                 break
+
+
+PRESENT_SOURCES = tuple(B.PRESENT_SOURCES)      # "accum", "denoise", "denoise_vg", "denoise_mv", "develop"
+_DENOISE_KEYS = ("levels", "sigma_color", "sigma_normal", "sigma_albedo", "sigma_depth")
+_DENOISE_VG_KEYS = ("levels", "sigma_variance", "sigma_normal", "sigma_albedo", "sigma_depth", "variance_floor")
+_DEVELOP_KEYS = ("response", "filter", "scale")
+_PRESENT_STAGE_KEYS = {"accum": (), "denoise": _DENOISE_KEYS, "denoise_vg": _DENOISE_VG_KEYS, "denoise_mv": _DENOISE_VG_KEYS, "develop": _DEVELOP_KEYS}
+
+
+def present_config(source="accum", gain=None, **cfg):
+    """srt_present_cfg from Python values, checked as the library checks it, before any device is touched.  source: "accum" (the sums),
+    "denoise", "denoise_vg", "denoise_mv" (the three filters) or "develop" (the film through three curves taken as X, Y, Z).  gain None:
+    the exposure is metered on the source picture; else the gain.  cfg is told apart by name: the keywords of meter_config (only without a
+    gain), of tone_config (curve, white), of denoise_config / denoise_vg_config (only on the source that runs that filter) and response,
+    filter, scale as Renderer.develop_spectral_srgb takes them (only on "develop").  TypeError for a name that is none of them; ValueError
+    for an unknown source, meter keywords with an explicit gain, a stage's keywords on a source that does not run it, and every value its
+    own config function refuses."""
+    if not isinstance(source, str) or source not in B.PRESENT_SOURCES:
+        raise ValueError("present: source must be one of %s, got %r" % (", ".join(PRESENT_SOURCES), source))
+    known = set(_METER_KEYS) | set(_TONE_KEYS) | set(_DENOISE_KEYS) | set(_DENOISE_VG_KEYS) | set(_DEVELOP_KEYS)
+    unknown = sorted(set(cfg) - known)
+    if unknown:
+        raise TypeError("present: unknown keyword(s) %s" % ", ".join(unknown))
+    mcfg = {k: v for k, v in cfg.items() if k in _METER_KEYS}
+    tcfg = {k: v for k, v in cfg.items() if k in _TONE_KEYS}
+    scfg = {k: v for k, v in cfg.items() if k not in _METER_KEYS and k not in _TONE_KEYS}
+    if gain is not None and mcfg:
+        raise ValueError("present: %s given with an explicit gain, which is not metered" % ", ".join(sorted(mcfg)))
+    stray = sorted(set(scfg) - set(_PRESENT_STAGE_KEYS[source]))
+    if stray:
+        raise ValueError("present: %s given with source %r, which does not run that stage" % (", ".join(stray), source))
+    p = B.PresentCfg()
+    p.source = B.PRESENT_SOURCES[source]
+    p.metered = 1 if gain is None else 0
+    p.meter = meter_config(**mcfg)
+    p.tone = tone_config(gain=1.0 if gain is None else gain, **tcfg)
+    p.denoise = denoise_config(**(scfg if source == "denoise" else {}))
+    p.denoise_vg = denoise_vg_config(**(scfg if source in ("denoise_vg", "denoise_mv") else {}))
+    p.scale = CIE_SCALE
+    if source == "develop":
+        response, filter = scfg.get("response"), scfg.get("filter")
+        if response is not None or filter is not None:
+            resp = sensor_response(cie_response() if response is None else response, filter)
+            if resp.shape[0] != 3:
+                raise ValueError("present: needs three response curves (taken as X, Y, Z), got %d" % resp.shape[0])
+            p._response = resp      # (the struct only points at the curves)
+            p.response3 = B.fptr(resp)
+        if scfg.get("scale") is not None:
+            p.scale = _develop_scale(scfg["scale"])
+    return p
+
+
+def render_presented(scene, cam, width, height, passes, bounce_limit, source="accum", gain=None, seed=1984, device=0, renderer=None,
+                     rel_tol=0.02, abs_tol=0.0, min_spp=16, **cfg):
+    """render_progressive with the picture presented on the device behind every pass: a generator of (spp_total, result, presented) --
+    `result` with the keys of render_image, `presented` the dict of Renderer.present(width, height, source, gain, **cfg).  The
+    accumulation is the kind the source needs: plain for "accum", featured for "denoise" and "denoise_vg", adaptive featured for
+    "denoise_mv" (rel_tol, abs_tol, min_spp: its stopping rule, read by no other source; the first pass must hold at least 2 samples),
+    spectral for "develop".  Presenting only reads the accumulation, so result is that kind's own generator's bit for bit.  Schedule and
+    cfg are checked here, before any device is touched."""
+    sched = progressive_schedule(passes)
+    present_config(source, gain, **cfg)
+    acfg = adaptive_config(rel_tol, abs_tol, min_spp) if source == "denoise_mv" else None
+    return _presented_passes(scene, cam, width, height, sched, bounce_limit, seed, device, renderer, source, gain, acfg, cfg)
+
+
+def _presented_passes(scene, cam, width, height, sched, bounce_limit, seed, device, renderer, source, gain, acfg, cfg):
+    with _image_session(scene, cam, width, height, sum(sched), bounce_limit, seed, device, renderer) as r:
+        if source == "accum":
+            r.accum_reset()
+        elif source == "develop":
+            r.accum_reset_spectral()
+        elif source == "denoise_mv":
+            r._ck(B.lib().srt_accum_reset_adaptive_features(r._h, C.byref(acfg)))      # (after the session has set the planes)
+        else:
+            r.accum_reset_features()
+        for spp_add in sched:
+            r.render_chunk_accum(width, height, spp_add)
+            r.scatter_tiles()
+            out = _collect(r, width, height)
+            yield r.accum_samples, out, r.present(width, height, source, gain, **cfg)

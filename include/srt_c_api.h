@@ -710,6 +710,71 @@ SRT_API int srt_denoise_developed_counts_kat(srt_ctx *ctx, const srt_denoise *cf
                                              const float *developed, uint32_t channels, const uint32_t *samples, uint32_t w, uint32_t h,
                                              float *out_dev, float *out_xyz);
 
+/* The presented picture (no reference counterpart; kernels in csrc/srt_present.hip): the bound accumulation through a chosen chain --
+ * nothing, a denoiser or a develop; then the meter or a given gain; then the tone curve -- without leaving the device, into the 4 bytes per
+ * pixel a display, an encoder or an image writer wants.  Only the packed picture crosses the bus (and the three counters, and the 16 KiB
+ * histogram when metering), through a pinned staging block of the context.  Operation by operation:
+ *   Source (cfg->source), each stage the existing call's kernels on the chunk's rectangle (clipped to the reference grid), w x h pixels:
+ *     SRT_PRESENT_ACCUM        the XYZ sums, normalised in present_kernel as the tone kernel normalises them: inv = 1.0f / (float)n, n the
+ *                              sample total, on an adaptive kind the pixel's own count (0 counts as 1); c = inv * S per component.
+ *     SRT_PRESENT_DENOISE      srt_denoise_features' filter (cfg->denoise); the picture is its out_xyz, left on the device.
+ *     SRT_PRESENT_DENOISE_VG   srt_denoise_features_vg's (cfg->denoise_vg); SRT_PRESENT_DENOISE_MV: srt_denoise_features_mv's.
+ *     SRT_PRESENT_DEVELOP      srt_develop_spectral_srgb's contraction of the film with cfg->response3 (three curves [3][95] taken as X,
+ *                              Y, Z; NULL: the colour-matching rows of srt_color_tables) and cfg->scale, D; then m = inv * D per component
+ *                              with the inv of that call's epilogue (the sample total, or the pixel's own count, 0 counting as 1): the
+ *                              XYZ mean its out_lin / out_q are made of.  (out_xyz of that call is D, the sums: m = inv * out_xyz.)
+ *   Exposure: cfg->metered != 0 meters the source picture -- srt_meter_accum on SRT_PRESENT_ACCUM, else the meter kernel on the device
+ *     array as srt_meter_kat runs it on a host array, under the context's partition -- with cfg->meter, decides as srt_meter_decide decides
+ *     and takes the gain decided; cfg->tone.gain is validated but not used.  cfg->metered == 0: the gain is cfg->tone.gain.
+ *   Tone and pack, per pixel with XYZ mean c: o = Tone(c) and (lin, q) = xyz_mean_to_srgb(o) exactly as stated at "Tone" above; q holds
+ *     whole numbers in 0 .. 255 always (a NaN channel fails every compare of the transfer function and comes out 255), and the pixel's
+ *     word is  (uint32)q.r | (uint32)q.g << 8 | (uint32)q.b << 16 | 255 << 24:  byte 0 R, byte 1 G, byte 2 B, byte 3 A = 255 -- the bytes of
+ *     srt_expose_accum's / srt_expose_kat's out_q.  blown, crushed and nonfinite are counted as the tone kernel counts them, over the
+ *     pixels of this rank's tiles.  A pixel of another rank's tile holds +0 and comes out as (0, 0, 0, 255).
+ *     The kernel handles four consecutive pixels of a row per thread with 16-byte accesses where the group is whole and 16-byte aligned
+ *     and pixel by pixel elsewhere; the bytes do not depend on the path.
+ *   srt_present           runs the chain and writes row j of the picture at out_rgba8 + (offy + j) * pitch_bytes + 4 * offx.  Placement
+ *                         and clipping are srt_expose_accum's: the image receives the part of the chunk's rectangle inside image_width x
+ *                         image_height at the chunk's offset, and no other byte of the caller's buffer -- padding included -- is written.
+ *                         *result, unless NULL, receives the metering (all zero when the gain was given) and the counters.  Synchronises;
+ *                         only reads the accumulation.  Refusals are those of the calls it chains, nothing changed and nothing written:
+ *                         SRT_ERR_INVALID for a null ctx / cfg / out_rgba8, non-zero reserved words, an unknown source, an empty image,
+ *                         pitch_bytes < 4 * image_width, a bad srt_tone, with metering a bad srt_meter (a rectangle outside the chunk
+ *                         included), a bad srt_denoise / srt_denoise_vg of a denoising source, non-finite curves or scale of
+ *                         SRT_PRESENT_DEVELOP, no accumulation with a pass, a denoising source without a featured accumulation
+ *                         (SRT_PRESENT_DENOISE_MV: an adaptive featured one holding at least 2 samples), SRT_PRESENT_DEVELOP without a
+ *                         film; SRT_ERR_UNSUPPORTED for a denoising source under a partition other than (0, 1); SRT_ERR_HIP for a failed
+ *                         allocation.  The configuration of a stage the source does not run is not read.
+ *   srt_present_kat       present_kernel on a caller's row-major host array xyz_mean[h][w][3] at tone->gain; out_rgba8[h][w][4], tightly
+ *                         packed; result may be NULL.  Needs neither a scene nor an accumulation.  Refusals as srt_expose_kat's.
+ *   srt_present_last_ms   kernel-only time in ms, from HIP events, of the context's last present_kernel; SRT_ERR_INVALID before one has
+ *                         run.  srt_denoise_last_ms, srt_develop_last_ms and srt_expose_last_ms report the stages srt_present ran.
+ * Working blocks (four bytes per pixel on the device and in pinned host memory, grown on demand; twelve more per pixel on the device for a
+ * developed mean) belong to the context and are freed with it.  No call here invalidates or alters an accumulation, the frame or the
+ * RNG state. */
+#define SRT_PRESENT_ACCUM 0
+#define SRT_PRESENT_DENOISE 1
+#define SRT_PRESENT_DENOISE_VG 2
+#define SRT_PRESENT_DENOISE_MV 3
+#define SRT_PRESENT_DEVELOP 4
+typedef struct srt_present_cfg {
+    uint32_t source;               /* SRT_PRESENT_* */
+    uint32_t metered;              /* != 0: the gain is metered with `meter`; 0: tone.gain */
+    srt_meter meter;
+    srt_tone tone;
+    srt_denoise denoise;           /* SRT_PRESENT_DENOISE */
+    srt_denoise_vg denoise_vg;     /* SRT_PRESENT_DENOISE_VG, SRT_PRESENT_DENOISE_MV */
+    const float *response3;        /* SRT_PRESENT_DEVELOP: [3][95], NULL = the colour-matching rows */
+    float scale;                   /* SRT_PRESENT_DEVELOP */
+    uint32_t reserved[5];          /* must be 0 */
+} srt_present_cfg;
+typedef struct srt_present_result { srt_meter_result meter; srt_tone_result tone; } srt_present_result;
+SRT_API int srt_present(srt_ctx *ctx, const srt_present_cfg *cfg, uint8_t *out_rgba8, size_t pitch_bytes, uint32_t image_width,
+                        uint32_t image_height, srt_present_result *result);
+SRT_API int srt_present_kat(srt_ctx *ctx, const srt_tone *tone, const float *xyz_mean, uint32_t w, uint32_t h, uint8_t *out_rgba8,
+                            srt_tone_result *result);
+SRT_API int srt_present_last_ms(srt_ctx *ctx, float *ms);
+
 /* Sample-parallel pixels (no reference counterpart; a deliberate departure from its one RNG stream per pixel, so opt-in).  A STREAMED
  * accumulation gives every pixel K independent RNG streams, each with its own state and its own XYZ sum, so that any lane of any wave
  * can render a stream while others render the pixel's other streams: the longest sequential chain of a pass is spp_add / K samples.
