@@ -102,6 +102,16 @@ class PresentResult(C.Structure):
     _fields_ = [("meter", MeterResult), ("tone", ToneResult)]
 
 
+class Despeckle(C.Structure):
+    """srt_despeckle: window radius, rank (parts per million), gain and floor of the firefly filter (srt_c_api.h)"""
+    _fields_ = [("radius", C.c_uint32), ("rank_ppm", C.c_uint32), ("gain", C.c_float), ("floor", C.c_float), ("reserved", C.c_uint32 * 4)]
+
+
+class DespeckleResult(C.Structure):
+    """srt_despeckle_result: the pixels the firefly filter clamped, found non-finite and found without a valid neighbour (srt_c_api.h)"""
+    _fields_ = [("clamped", C.c_uint64), ("nonfinite", C.c_uint64), ("alone", C.c_uint64)]
+
+
 class TreeTuning(C.Structure):
     """srt_tree_tuning: what srt_tune_tree_for_throughput found and did (srt_c_api.h)"""
     _fields_ = [("pixels_per_lane", C.c_double), ("throughput_bound", C.c_uint32), ("reinsertion", C.c_uint32),
@@ -118,6 +128,7 @@ class TileScheduleInfo(C.Structure):
 assert C.sizeof(Denoise) == 32 and C.sizeof(DenoiseVG) == 32
 assert C.sizeof(Meter) == 48 and C.sizeof(MeterResult) == 40 and C.sizeof(Tone) == 32 and C.sizeof(ToneResult) == 24
 assert C.sizeof(PresentCfg) == 184 and C.sizeof(PresentResult) == 64
+assert C.sizeof(Despeckle) == 32 and C.sizeof(DespeckleResult) == 24
 assert C.sizeof(Adaptive) == 16 and C.sizeof(TreeTuning) == 40 and C.sizeof(TileScheduleInfo) == 32
 assert C.sizeof(Material) == 428 and C.sizeof(CameraData) == 84 and C.sizeof(TriIn) == 44
 
@@ -189,6 +200,12 @@ PROTOTYPES = {
     "srt_present": (_i, [_vp, C.POINTER(PresentCfg), C.POINTER(C.c_uint8), _sz, _u32, _u32, C.POINTER(PresentResult)]),
     "srt_present_kat": (_i, [_vp, C.POINTER(Tone), _fp, _u32, _u32, C.POINTER(C.c_uint8), C.POINTER(ToneResult)]),
     "srt_present_last_ms": (_i, [_vp, _fp]),
+    "srt_despeckle_accum": (_i, [_vp, C.POINTER(Despeckle), _fp, _fp, _fp, _fp, C.POINTER(DespeckleResult), _u32, _u32]),
+    "srt_despeckle_kat": (_i, [_vp, C.POINTER(Despeckle), _fp, _u32, _u32, _fp, _fp, C.POINTER(DespeckleResult)]),
+    "srt_despeckle_last_ms": (_i, [_vp, _fp]),
+    "srt_denoise_features_ds": (_i, [_vp, C.POINTER(Despeckle), C.POINTER(Denoise), _fp, _fp, _fp, _u32, _u32]),
+    "srt_present_despeckled": (_i, [_vp, C.POINTER(PresentCfg), C.POINTER(Despeckle), C.POINTER(C.c_uint8), _sz, _u32, _u32, C.POINTER(PresentResult),
+                                C.POINTER(DespeckleResult)]),
     "srt_accum_reset_features": (_i, [_vp]),
     "srt_read_features": (_i, [_vp, _fp, _u32, _u32]),
     "srt_accum_reset_adaptive_features": (_i, [_vp, C.POINTER(Adaptive)]),

@@ -164,6 +164,7 @@ struct srt_ctx {
     uint32_t denoise_timed_levels = 0;                  // levels the events of the last denoise bracket
     uint32_t denoise_level_ev = 1;                      // the event level 0 starts at: 1, or 2 after a variance-guided denoise
     bool denoise_timed = false;
+    bool denoise_estimated = false;                     // the last denoise ran a variance estimator (the event pair [1, 2] brackets it)
     DeviceBuffer d_develop;                             // the developed film's working blocks (DevelopLayout), grown when the rectangle or the channels grow
     DeviceBuffer d_develop_in;                          // srt_develop_kat: the caller's film in 96-float rows
     hipEvent_t develop_ev[3] = {};                      // around the kernels of the last develop: contraction | sRGB epilogue (created on first use)
@@ -178,6 +179,9 @@ struct srt_ctx {
     hipEvent_t present_ev[2] = {};                      // around the last present kernel (created on first use)
     bool present_timed = false;
     bool present_scalar = false;                        // test knob (env SRT_PRESENT_SCALAR under SRT_TEST_KNOBS=1): present_kernel's scalar path alone
+    DeviceBuffer d_despeckle;                           // the firefly filter: its counters and its four row-major images (DespeckleLayout)
+    hipEvent_t despeckle_ev[2] = {};                    // around the last despeckle kernel (created on first use)
+    bool despeckle_timed = false;
     DeviceBuffer d_streams;                            // sample-parallel pixels (srt_accum_reset_streams, StreamPlanes)
     uint32_t streams_seeded = 0;                        // the K whose RNG streams d_streams holds, seeded since the last srt_init_device_params (0: none)
 };
@@ -639,6 +643,7 @@ void srt_destroy(srt_ctx *c) {
     for (hipEvent_t e : c->develop_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->expose_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->present_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->despeckle_ev) if (e) (void)hipEventDestroy(e);
     delete c;      // (every DeviceBuffer, and the pinned staging block, frees itself, on the device selected above)
 }
 
@@ -1617,6 +1622,134 @@ int srt_expose_last_ms(srt_ctx *c, float *meter_ms, float *tone_ms) {
     return SRT_OK;
 }
 
+// ---- the firefly filter (srt_despeckle.hip) ---------------------------------------------------------------------------------------
+namespace {
+
+// d_despeckle: [counters: clamped, non-finite, alone (u64 each), padded to 32 bytes | out_xyz | out_lin | out_q: three floats per pixel each
+//               | out_scale: one float per pixel]
+struct DespeckleLayout {
+    unsigned long long *counts;
+    float *img[3], *scale;
+    static constexpr size_t kHeadBytes = 32;
+    static size_t bytes(size_t pixels) { return kHeadBytes + 10 * pixels * sizeof(float); }
+    DespeckleLayout(const DeviceBuffer &d, size_t pixels) : counts(d.as<unsigned long long>()) {
+        img[0] = reinterpret_cast<float *>(d.as<char>() + kHeadBytes); img[1] = img[0] + 3 * pixels; img[2] = img[1] + 3 * pixels;
+        scale = img[2] + 3 * pixels;      // (the images: inside the buffer only when it was reserved with pixels)
+    }
+};
+
+const char *despeckle_cfg_error(const srt_despeckle *d) {
+    if (d->radius != 1u && d->radius != 2u) return "despeckle: radius must be 1 or 2";
+    if (d->rank_ppm > 1000000u) return "despeckle: rank_ppm must be in 0 .. 1000000";
+    if (!std::isfinite(d->gain) || !(d->gain >= 0.0f)) return "despeckle: gain must be finite and >= 0";
+    if (!(d->floor >= 0.0f)) return "despeckle: floor must be >= 0 (+inf switches the filter off)";
+    for (const uint32_t r : d->reserved) if (r) return "despeckle: the reserved words must be 0";
+    return nullptr;
+}
+
+// The despeckle kernel over the w x h rectangle described by p (its source and outputs set by the caller; cfg and counters are filled in
+// here), between the context's two despeckle events.  d_despeckle is reserved by the caller.  Enqueues; the caller synchronises.
+int run_despeckle(srt_ctx *c, const char *who, DespeckleParams p, const srt_despeckle *cfg) {
+    const DespeckleLayout L(c->d_despeckle, 0);
+    c->despeckle_timed = false;
+    for (hipEvent_t &e : c->despeckle_ev) if (!e) HIP_TRY_AS(c, who, hipEventCreate(&e));
+    HIP_TRY_AS(c, who, hipMemsetAsync(L.counts, 0, 3 * sizeof(unsigned long long), nullptr));
+    p.radius = cfg->radius; p.rank_ppm = cfg->rank_ppm; p.gain = cfg->gain; p.floor = cfg->floor;
+    p.counts = L.counts;
+    HIP_TRY_AS(c, who, hipEventRecord(c->despeckle_ev[0], nullptr));
+    HIP_TRY_AS(c, who, launch_despeckle(p, nullptr));
+    HIP_TRY_AS(c, who, hipEventRecord(c->despeckle_ev[1], nullptr));
+    c->despeckle_timed = true;
+    return SRT_OK;
+}
+int read_despeckle_counts(srt_ctx *c, const char *who, srt_despeckle_result *result) {
+    unsigned long long counts[3] = {0, 0, 0};
+    HIP_TRY_AS(c, who, hipMemcpy(counts, DespeckleLayout(c->d_despeckle, 0).counts, sizeof(counts), hipMemcpyDeviceToHost));
+    result->clamped = counts[0]; result->nonfinite = counts[1]; result->alone = counts[2];
+    return SRT_OK;
+}
+
+// the accumulation's sum planes as the kernel's source, its chunk rectangle w x h
+DespeckleParams despeckle_accum_source(const srt_ctx *c, uint32_t w, uint32_t h) {
+    DespeckleParams p = {};
+    p.sums = AccumLayout(c).sums; p.comp_stride = c->n_lanes; p.state = c->accum.adaptive() ? AdaptPlanes(c).state : nullptr;
+    p.samples = c->accum.total; p.tx = c->tx; p.ty = c->ty; p.bx = c->bx; p.w = w; p.h = h;
+    return p;
+}
+
+}  // namespace
+
+int srt_despeckle_accum(srt_ctx *c, const srt_despeckle *cfg, float *out_xyz, float *out_lin, float *out_q, float *out_scale, srt_despeckle_result *result,
+                        uint32_t image_width, uint32_t image_height) {
+    const char *who = "srt_despeckle_accum";
+    if (!c || !cfg) return fail(c, SRT_ERR_INVALID, "srt_despeckle_accum: null argument");
+    if ((!out_xyz && !out_lin && !out_q && !out_scale && !result) || image_width == 0 || image_height == 0)
+        return fail(c, SRT_ERR_INVALID, "srt_despeckle_accum: no output / empty image");
+    if (const char *why = despeckle_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_despeckle_accum: ") + why);
+    if (!c->accum.bound()) return fail(c, SRT_ERR_INVALID, "srt_despeckle_accum: no accumulation with a pass (srt_accum_reset* and srt_render_chunk_accum first)");
+    if (c->rank != 0 || c->world != 1)
+        return fail(c, SRT_ERR_UNSUPPORTED, "srt_despeckle_accum: needs the whole chunk on this context (partition (0, 1)): pixels of other ranks read +0");
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the kernel runs on the chunk's rectangle (clipped to the reference grid); the image clips only what is copied out
+    const uint32_t w = clipped_w(c), h = clipped_h(c);
+    const size_t pixels = (size_t)w * h;
+    srt_despeckle_result res = {};
+    if (pixels) {
+        if (const int rc = develop_reserve(c, who, c->d_despeckle, DespeckleLayout::bytes(pixels))) return rc;
+        const DespeckleLayout L(c->d_despeckle, pixels);
+        DespeckleParams p = despeckle_accum_source(c, w, h);
+        p.out_xyz = out_xyz ? L.img[0] : nullptr; p.out_lin = out_lin ? L.img[1] : nullptr; p.out_q = out_q ? L.img[2] : nullptr;
+        p.out_scale = out_scale ? L.scale : nullptr;
+        if (const int rc = run_despeckle(c, who, p, cfg)) return rc;
+        const ChunkRect rect = chunk_rect(c, image_width, image_height);
+        float *const host[4] = {out_xyz, out_lin, out_q, out_scale};
+        const float *const src[4] = {L.img[0], L.img[1], L.img[2], L.scale};
+        for (int k = 0; k < 4; k++) {
+            const size_t ch = k < 3 ? 3 : 1;      // floats per pixel
+            const size_t row = (size_t)rect.w * ch * sizeof(float), src_pitch = (size_t)w * ch * sizeof(float), pitch = (size_t)image_width * ch * sizeof(float);
+            if (host[k] && rect.w && rect.h) HIP_TRY(c, hipMemcpy2D(host[k] + rect.first * ch, pitch, src[k], src_pitch, row, rect.h, hipMemcpyDeviceToHost));
+        }
+        if (const int rc = read_despeckle_counts(c, who, &res)) return rc;
+    }
+    HIP_TRY(c, hipDeviceSynchronize());
+    if (result) *result = res;
+    return SRT_OK;
+}
+
+int srt_despeckle_kat(srt_ctx *c, const srt_despeckle *cfg, const float *xyz_mean, uint32_t w, uint32_t h, float *out_xyz, float *out_scale,
+                      srt_despeckle_result *result) {
+    const char *who = "srt_despeckle_kat";
+    if (!c || !cfg || !xyz_mean) return fail(c, SRT_ERR_INVALID, "srt_despeckle_kat: null argument");
+    if (!out_xyz && !out_scale && !result) return fail(c, SRT_ERR_INVALID, "srt_despeckle_kat: no output");
+    if (w == 0 || h == 0 || (uint64_t)w * h > 0x7fffffffull) return fail(c, SRT_ERR_INVALID, "srt_despeckle_kat: w x h must be in 1 .. 2^31 - 1");
+    if (const char *why = despeckle_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_despeckle_kat: ") + why);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t pixels = (size_t)w * h;
+    if (const int rc = develop_reserve(c, who, c->d_despeckle, DespeckleLayout::bytes(pixels))) return rc;
+    if (const int rc = upload_kat_xyz(c, who, xyz_mean, w, h)) return rc;
+    const DespeckleLayout L(c->d_despeckle, pixels);
+    DespeckleParams p = {};
+    p.xyz = c->d_expose_in.as<float>(); p.w = w; p.h = h;
+    p.out_xyz = out_xyz ? L.img[0] : nullptr; p.out_scale = out_scale ? L.scale : nullptr;
+    if (const int rc = run_despeckle(c, who, p, cfg)) return rc;
+    if (out_xyz) HIP_TRY_AS(c, who, hipMemcpy(out_xyz, L.img[0], pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_scale) HIP_TRY_AS(c, who, hipMemcpy(out_scale, L.scale, pixels * sizeof(float), hipMemcpyDeviceToHost));
+    srt_despeckle_result res = {};
+    if (const int rc = read_despeckle_counts(c, who, &res)) return rc;
+    HIP_TRY_AS(c, who, hipDeviceSynchronize());
+    if (result) *result = res;
+    return SRT_OK;
+}
+
+int srt_despeckle_last_ms(srt_ctx *c, float *ms) {
+    if (!c || !ms) return fail(c, SRT_ERR_INVALID, "srt_despeckle_last_ms: null argument");
+    if (!c->despeckle_timed) return fail(c, SRT_ERR_INVALID, "srt_despeckle_last_ms: no despeckle kernel has run on this context");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipEventSynchronize(c->despeckle_ev[1]));
+    HIP_TRY(c, hipEventElapsedTime(ms, c->despeckle_ev[0], c->despeckle_ev[1]));
+    return SRT_OK;
+}
+
 // ---- the denoiser (srt_denoise.hip) ---------------------------------------------------------------------------------------------
 namespace {
 
@@ -1680,7 +1813,9 @@ DenoisePlan denoise_vg_plan(const srt_denoise_vg *cfg) {
 // DenoiseLayout::out / var.  Enqueues on the default stream; the caller synchronises.
 // Events: [0] prepass [1] (variance-guided: estimator [2]) level 0 .. epilogue: denoise_level_ev is the event level 0 starts at.
 // sum_y2: the S2 words of a measured plan (indexed like pre.counts), else unused.
-int run_denoise(srt_ctx *c, const char *who, const DenoisePlan &plan, DenoisePrepassParams pre, const float *sum_y2 = nullptr) {
+// ds (plain plans only; the caller has reserved d_despeckle): the firefly filter between the prepass and level 0, colour[1] =
+// Despeckle(colour[0]), between its own events; one more denoise event behind it, so that level 0 is timed alone.
+int run_denoise(srt_ctx *c, const char *who, const DenoisePlan &plan, DenoisePrepassParams pre, const float *sum_y2 = nullptr, const srt_despeckle *ds = nullptr) {
     const size_t pixels = (size_t)pre.w * pre.h;
     const DenoiseLayout L(c->d_denoise, pixels);
     pre.guides = L.guides; pre.colour = L.colour[0];
@@ -1704,8 +1839,15 @@ int run_denoise(srt_ctx *c, const char *who, const DenoisePlan &plan, DenoisePre
         HIP_TRY_AS(c, who, launch_denoise_variance(vp, nullptr));
         HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
     }
-    const uint32_t level_ev = n_ev - 1;
     uint32_t cur = 0;
+    if (ds) {
+        DespeckleParams dp = {};
+        dp.src4 = L.colour[0]; dp.dst4 = L.colour[1]; dp.w = pre.w; dp.h = pre.h;
+        if (const int rc = run_despeckle(c, who, dp, ds)) return rc;
+        HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
+        cur = 1;
+    }
+    const uint32_t level_ev = n_ev - 1;
     for (uint32_t i = 0; i < plan.levels; i++) {
         if (plan.vg) {
             DenoiseLevelVgParams lp = {};
@@ -1728,7 +1870,7 @@ int run_denoise(srt_ctx *c, const char *who, const DenoisePlan &plan, DenoisePre
     HIP_TRY_AS(c, who, launch_denoise_epilogue(reinterpret_cast<const float *>(L.colour[cur]), L.out[0], L.out[1], L.out[2], pixels, nullptr));
     if (plan.vg) HIP_TRY_AS(c, who, launch_denoise_var_out(reinterpret_cast<const float *>(L.colour[cur]), L.var, pixels, nullptr));
     HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
-    c->denoise_timed_levels = plan.levels; c->denoise_level_ev = level_ev; c->denoise_timed = true;
+    c->denoise_timed_levels = plan.levels; c->denoise_level_ev = level_ev; c->denoise_estimated = plan.vg; c->denoise_timed = true;
     return SRT_OK;
 }
 
@@ -1747,25 +1889,27 @@ int denoise_accumulation_refusal(srt_ctx *c, const char *who, const DenoisePlan 
 }
 
 // run_denoise on the accumulation's w x h rectangle (not empty): the results are left in DenoiseLayout(c->d_denoise, w * h)
-int denoise_accumulation(srt_ctx *c, const char *who, const DenoisePlan &plan, uint32_t w, uint32_t h) {
+int denoise_accumulation(srt_ctx *c, const char *who, const DenoisePlan &plan, uint32_t w, uint32_t h, const srt_despeckle *ds = nullptr) {
     HIP_TRY(c, c->d_denoise.reserve(DenoiseLayout::bytes((size_t)w * h, plan.vg)));
+    if (ds) if (const int rc = develop_reserve(c, who, c->d_despeckle, DespeckleLayout::kHeadBytes)) return rc;
     DenoisePrepassParams pre = {};
     pre.sums = AccumLayout(c).sums; pre.sum_pixel_stride = 1; pre.sum_comp_stride = c->n_lanes;
     pre.rows = reinterpret_cast<const float4 *>(feature_rows(c));
     pre.tx = c->tx; pre.ty = c->ty; pre.bx = c->bx; pre.w = w; pre.h = h; pre.samples = c->accum.total;
     // (an adaptive featured accumulation: every pixel of the chunk is normalised by its own count, the samples field of its state word)
     if (c->accum.adaptive()) pre.counts = AdaptPlanes(c).state;
-    return run_denoise(c, who, plan, pre, c->accum.adaptive() ? AdaptPlanes(c).sum2 : nullptr);
+    return run_denoise(c, who, plan, pre, c->accum.adaptive() ? AdaptPlanes(c).sum2 : nullptr, ds);
 }
 
-int denoise_features(srt_ctx *c, const char *who, const DenoisePlan &plan, float *const host[4], uint32_t image_width, uint32_t image_height) {
+int denoise_features(srt_ctx *c, const char *who, const DenoisePlan &plan, float *const host[4], uint32_t image_width, uint32_t image_height,
+                     const srt_despeckle *ds = nullptr) {
     if (const int rc = denoise_accumulation_refusal(c, who, plan)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     // the filter runs on the chunk's rectangle (clipped to the reference grid); the image clips only what is copied out
     const uint32_t w = clipped_w(c), h = clipped_h(c);
     const size_t pixels = (size_t)w * h;
     if (pixels) {
-        if (const int rc = denoise_accumulation(c, who, plan, w, h)) return rc;
+        if (const int rc = denoise_accumulation(c, who, plan, w, h, ds)) return rc;
         const ChunkRect rect = chunk_rect(c, image_width, image_height);
         const DenoiseLayout L(c->d_denoise, pixels);
         for (int k = 0; k < 4; k++) {
@@ -1820,6 +1964,16 @@ int srt_denoise_features(srt_ctx *c, const srt_denoise *cfg, float *out_xyz, flo
     if (const char *why = denoise_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_denoise_features: ") + why);
     float *const host[4] = {out_xyz, out_lin, out_q, nullptr};
     return denoise_features(c, "srt_denoise_features", denoise_plan(cfg), host, image_width, image_height);
+}
+
+int srt_denoise_features_ds(srt_ctx *c, const srt_despeckle *despeckle_cfg, const srt_denoise *denoise_cfg, float *out_xyz, float *out_lin, float *out_q,
+                            uint32_t image_width, uint32_t image_height) {
+    if (!c || !despeckle_cfg || !denoise_cfg) return fail(c, SRT_ERR_INVALID, "srt_denoise_features_ds: null argument");
+    if ((!out_xyz && !out_lin && !out_q) || image_width == 0 || image_height == 0) return fail(c, SRT_ERR_INVALID, "srt_denoise_features_ds: no output / empty image");
+    if (const char *why = denoise_cfg_error(denoise_cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_denoise_features_ds: ") + why);
+    if (const char *why = despeckle_cfg_error(despeckle_cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_denoise_features_ds: ") + why);
+    float *const host[4] = {out_xyz, out_lin, out_q, nullptr};
+    return denoise_features(c, "srt_denoise_features_ds", denoise_plan(denoise_cfg), host, image_width, image_height, despeckle_cfg);
 }
 
 int srt_denoise_features_vg(srt_ctx *c, const srt_denoise_vg *cfg, float *out_xyz, float *out_lin, float *out_q, float *out_var, uint32_t image_width, uint32_t image_height) {
@@ -1922,7 +2076,7 @@ int run_denoise_developed(srt_ctx *c, const char *who, const DenoisePlan &plan, 
     HIP_TRY_AS(c, who, launch_denoise_epilogue(reinterpret_cast<const float *>(L.colour[cur]), L.out[0], L.out[1], L.out[2], pixels, nullptr));
     HIP_TRY_AS(c, who, launch_denoise_dev_out(D.payload[cur], D.out, channels, groups, pixels, nullptr));
     HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
-    c->denoise_timed_levels = plan.levels; c->denoise_level_ev = level_ev; c->denoise_timed = true;
+    c->denoise_timed_levels = plan.levels; c->denoise_level_ev = level_ev; c->denoise_estimated = false; c->denoise_timed = true;
     return SRT_OK;
 }
 
@@ -2039,7 +2193,7 @@ int srt_denoise_last_ms(srt_ctx *c, float *prepass_ms, float *level_ms, float *e
 
 int srt_denoise_estimate_last_ms(srt_ctx *c, float *ms) {
     if (!c || !ms) return fail(c, SRT_ERR_INVALID, "srt_denoise_estimate_last_ms: null argument");
-    if (!c->denoise_timed || c->denoise_level_ev != 2) return fail(c, SRT_ERR_INVALID, "srt_denoise_estimate_last_ms: the context's last denoise was not variance-guided");
+    if (!c->denoise_timed || !c->denoise_estimated) return fail(c, SRT_ERR_INVALID, "srt_denoise_estimate_last_ms: the context's last denoise was not variance-guided");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipEventSynchronize(c->denoise_ev[2]));
     HIP_TRY(c, hipEventElapsedTime(ms, c->denoise_ev[1], c->denoise_ev[2]));
@@ -2095,10 +2249,12 @@ int run_present(srt_ctx *c, const char *who, PresentParams p, const srt_tone *to
 
 }  // namespace
 
-int srt_present(srt_ctx *c, const srt_present_cfg *cfg, uint8_t *out_rgba8, size_t pitch_bytes, uint32_t image_width, uint32_t image_height,
-                srt_present_result *result) {
-    const char *who = "srt_present";
-    const std::string w_("srt_present: ");
+namespace {
+
+// srt_present (ds == null) and srt_present_despeckled (ds: the firefly filter in front of the chain; ds_result may be null)
+int present_chain(srt_ctx *c, const char *who, const srt_present_cfg *cfg, const srt_despeckle *ds, uint8_t *out_rgba8, size_t pitch_bytes, uint32_t image_width,
+                  uint32_t image_height, srt_present_result *result, srt_despeckle_result *ds_result) {
+    const std::string w_(std::string(who) + ": ");
     if (!c || !cfg || !out_rgba8) return fail(c, SRT_ERR_INVALID, w_ + "null argument");
     for (const uint32_t r : cfg->reserved) if (r) return fail(c, SRT_ERR_INVALID, w_ + "the reserved words must be 0");
     if (cfg->source > SRT_PRESENT_DEVELOP) return fail(c, SRT_ERR_INVALID, w_ + "unknown source (SRT_PRESENT_ACCUM .. SRT_PRESENT_DEVELOP)");
@@ -2106,6 +2262,11 @@ int srt_present(srt_ctx *c, const srt_present_cfg *cfg, uint8_t *out_rgba8, size
     if (pitch_bytes < (size_t)image_width * 4) return fail(c, SRT_ERR_INVALID, w_ + "pitch_bytes must be at least 4 * image_width");
     if (const char *why = tone_cfg_error(&cfg->tone)) return fail(c, SRT_ERR_INVALID, w_ + why);
     if (cfg->metered) if (const char *why = meter_cfg_error(&cfg->meter)) return fail(c, SRT_ERR_INVALID, w_ + why);
+    if (ds) {
+        if (const char *why = despeckle_cfg_error(ds)) return fail(c, SRT_ERR_INVALID, w_ + why);
+        if (cfg->source != SRT_PRESENT_ACCUM && cfg->source != SRT_PRESENT_DENOISE)
+            return fail(c, SRT_ERR_UNSUPPORTED, w_ + "the despeckled sources are SRT_PRESENT_ACCUM and SRT_PRESENT_DENOISE");
+    }
     const bool denoised = cfg->source == SRT_PRESENT_DENOISE || cfg->source == SRT_PRESENT_DENOISE_VG || cfg->source == SRT_PRESENT_DENOISE_MV;
     const bool developed = cfg->source == SRT_PRESENT_DEVELOP;
     DenoisePlan plan = {};
@@ -2128,6 +2289,8 @@ int srt_present(srt_ctx *c, const srt_present_cfg *cfg, uint8_t *out_rgba8, size
     }
     if (!c->accum.bound()) return fail(c, SRT_ERR_INVALID, w_ + "no accumulation with a pass (srt_accum_reset* and srt_render_chunk_accum first)");
     if (denoised) if (const int rc = denoise_accumulation_refusal(c, who, plan)) return rc;
+    if (ds && (c->rank != 0 || c->world != 1))
+        return fail(c, SRT_ERR_UNSUPPORTED, w_ + "needs the whole chunk on this context (partition (0, 1)): pixels of other ranks read +0");
     if (developed && !c->accum.spectral()) return fail(c, SRT_ERR_INVALID, w_ + "SRT_PRESENT_DEVELOP needs a spectral accumulation (srt_accum_reset_spectral*)");
     uint32_t rect[4] = {0, 0, 0, 0};
     if (cfg->metered) if (const char *why = meter_rect_error(&cfg->meter, clipped_w(c), clipped_h(c), rect)) return fail(c, SRT_ERR_INVALID, w_ + why);
@@ -2136,6 +2299,7 @@ int srt_present(srt_ctx *c, const srt_present_cfg *cfg, uint8_t *out_rgba8, size
     const uint32_t w = clipped_w(c), h = clipped_h(c);
     const size_t pixels = (size_t)w * h;
     srt_present_result res = {};
+    srt_despeckle_result ds_res = {};
     if (pixels) {
         if (const int rc = develop_reserve(c, who, c->d_expose, ExposeLayout::kBytes)) return rc;
         if (const int rc = develop_reserve(c, who, c->d_present, PresentLayout::bytes(pixels, developed))) return rc;
@@ -2143,8 +2307,14 @@ int srt_present(srt_ctx *c, const srt_present_cfg *cfg, uint8_t *out_rgba8, size
         // the source: null for the sums themselves, else a [h][w][3] XYZ mean on the device
         const float *picture = nullptr;
         if (denoised) {
-            if (const int rc = denoise_accumulation(c, who, plan, w, h)) return rc;
+            if (const int rc = denoise_accumulation(c, who, plan, w, h, ds)) return rc;
             picture = DenoiseLayout(c->d_denoise, pixels).out[0];
+        } else if (ds) {      // the despeckled mean, [h][w][3] on the device
+            if (const int rc = develop_reserve(c, who, c->d_despeckle, DespeckleLayout::bytes(pixels))) return rc;
+            DespeckleParams dp = despeckle_accum_source(c, w, h);
+            dp.out_xyz = DespeckleLayout(c->d_despeckle, pixels).img[0];
+            if (const int rc = run_despeckle(c, who, dp, ds)) return rc;
+            picture = dp.out_xyz;
         } else if (developed) {
             if (const int rc = develop_reserve(c, who, c->d_develop, DevelopLayout::bytes(pixels, 3, false))) return rc;
             if (const int rc = run_develop(c, who, c->d_film.as<float>(), c->n_lanes, c->tx, c->ty, c->bx, w, h, response3, 3, cfg->scale, 0u)) return rc;
@@ -2177,10 +2347,25 @@ int srt_present(srt_ctx *c, const srt_present_cfg *cfg, uint8_t *out_rgba8, size
         const ChunkRect place = chunk_rect(c, image_width, image_height);
         uint8_t *first = out_rgba8 + (size_t)c->last_offy * pitch_bytes + (size_t)c->last_offx * 4;      // (not formed into an address when nothing is copied)
         if (const int rc = run_present(c, who, p, &cfg->tone, gain, place.w, place.h, place.w && place.h ? first : out_rgba8, pitch_bytes, &res.tone)) return rc;
+        if (ds) if (const int rc = read_despeckle_counts(c, who, &ds_res)) return rc;
     }
     HIP_TRY(c, hipDeviceSynchronize());
     if (result) *result = res;
+    if (ds_result) *ds_result = ds_res;
     return SRT_OK;
+}
+
+}  // namespace
+
+int srt_present(srt_ctx *c, const srt_present_cfg *cfg, uint8_t *out_rgba8, size_t pitch_bytes, uint32_t image_width, uint32_t image_height,
+                srt_present_result *result) {
+    return present_chain(c, "srt_present", cfg, nullptr, out_rgba8, pitch_bytes, image_width, image_height, result, nullptr);
+}
+
+int srt_present_despeckled(srt_ctx *c, const srt_present_cfg *present_cfg, const srt_despeckle *despeckle_cfg, uint8_t *out_rgba8, size_t pitch_bytes,
+                           uint32_t image_width, uint32_t image_height, srt_present_result *result, srt_despeckle_result *despeckle_result) {
+    if (!despeckle_cfg) return fail(c, SRT_ERR_INVALID, "srt_present_despeckled: null argument");
+    return present_chain(c, "srt_present_despeckled", present_cfg, despeckle_cfg, out_rgba8, pitch_bytes, image_width, image_height, result, despeckle_result);
 }
 
 int srt_present_kat(srt_ctx *c, const srt_tone *tone, const float *xyz_mean, uint32_t w, uint32_t h, uint8_t *out_rgba8, srt_tone_result *result) {

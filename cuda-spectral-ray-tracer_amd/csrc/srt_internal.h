@@ -385,6 +385,27 @@ struct PresentNormaliseParams {
     uint32_t w, h;
 };
 hipError_t launch_present_normalise(const PresentNormaliseParams &p, hipStream_t st);
+// The firefly filter (srt_despeckle.hip; stated in srt_c_api.h at srt_despeckle_accum) over the row-major w x h rectangle.  Exactly one
+// source: sums (ToneParams' sum planes, comp_stride, state, samples and grid), xyz (a [h][w][3] XYZ mean) or src4 (the denoiser's float4
+// colour image).  radius, rank_ppm, gain, floor: srt_despeckle's.  Outputs, any may be null: out_xyz / out_lin / out_q three floats per
+// pixel, out_scale one, dst4 (never src4) the float4 image with the source's fourth word (+0 from another source).  counts[3] (clamped,
+// non-finite, alone) are ADDED to.
+struct DespeckleParams {
+    const float *sums, *xyz;
+    const float4 *src4;
+    size_t comp_stride;
+    const uint32_t *state;
+    uint32_t samples;
+    uint32_t tx, ty, bx;
+    uint32_t w, h;
+    uint32_t tiles_x;      // filled in by the launcher
+    uint32_t radius, rank_ppm;
+    float gain, floor;
+    float *out_xyz, *out_lin, *out_q, *out_scale;
+    float4 *dst4;
+    unsigned long long *counts;
+};
+hipError_t launch_despeckle(const DespeckleParams &p, hipStream_t st);
 hipError_t launch_order_tiles(const uint32_t *cost, uint32_t *sorted, uint32_t *rows, uint32_t n, uint32_t n_waves,
                               uint32_t split_load_pct, uint32_t *queue_info, uint32_t order_max_pct, hipStream_t st);
 hipError_t launch_scatter(const ScatterParams &p, hipStream_t st);

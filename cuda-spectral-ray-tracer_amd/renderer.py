@@ -284,6 +284,72 @@ class Renderer:
         self._ck(B.lib().srt_present_last_ms(self._h, C.byref(ms)))
         return ms.value
 
+    def _despeckle_cfg(self, who, despeckle, picture=None):
+        """srt_despeckle from the keywords of despeckle_config; floor None: the lit pixels' median bin, metered on the accumulation or on
+        `picture` (its y_ref at percentile_ppm = 500000; 0 when nothing is metered)"""
+        kw = dict(despeckle or {})
+        unknown = sorted(set(kw) - set(_DESPECKLE_KEYS))
+        if unknown:
+            raise TypeError("%s: unknown despeckle keyword(s) %s (%s)" % (who, ", ".join(unknown), ", ".join(_DESPECKLE_KEYS)))
+        d = despeckle_config(**kw)          # (a bad value is an error before the device is touched)
+        if kw.get("floor") is None:
+            m = self.meter(percentile_ppm=500000) if picture is None else self.meter_kat(picture, percentile_ppm=500000)
+            d.floor = m["y_ref"]
+        return d
+
+    def despeckle(self, image_width, image_height, **cfg):
+        """the firefly filter over the context's accumulation, of any kind, on the device (srt_despeckle_accum; cfg: the keywords of
+        despeckle_config; floor=None meters first, as expose(gain=None) does): dict(xyz, lin, fb) of (image_height, image_width, 3)
+        float32 arrays -- the clamped XYZ mean, its unquantised and its quantised sRGB --, scale (image_height, image_width) -- the
+        factor every pixel was multiplied by, 1 where it was kept --, written in the chunk's rectangle only, clip = dict(clamped,
+        nonfinite, alone) and floor, the floor used.  Reads the accumulation, changes nothing of it."""
+        d, res = self._despeckle_cfg("despeckle", cfg), B.DespeckleResult()
+        out = [np.zeros((image_height, image_width, 3), np.float32) for _ in range(3)]
+        scale = np.zeros((image_height, image_width), np.float32)
+        self._ck(B.lib().srt_despeckle_accum(self._h, C.byref(d), B.fptr(out[0]), B.fptr(out[1]), B.fptr(out[2]), B.fptr(scale), C.byref(res), image_width, image_height))
+        return dict(xyz=out[0], lin=out[1], fb=out[2], scale=scale, floor=d.floor, clip=dict(clamped=res.clamped, nonfinite=res.nonfinite, alone=res.alone))
+
+    def despeckle_kat(self, xyz_mean, **cfg):
+        """the firefly filter on an explicit XYZ-mean image (srt_meter_kat when floor is None, then srt_despeckle_kat): xyz_mean (h, w, 3)
+        float32 -> dict(xyz (h, w, 3), scale (h, w), floor, clip).  Needs no scene and no accumulation."""
+        img = _xyz_image("despeckle_kat", xyz_mean)
+        d, res = self._despeckle_cfg("despeckle_kat", cfg, img), B.DespeckleResult()
+        out, scale = np.zeros(img.shape, np.float32), np.zeros(img.shape[:2], np.float32)
+        self._ck(B.lib().srt_despeckle_kat(self._h, C.byref(d), B.fptr(img), img.shape[1], img.shape[0], B.fptr(out), B.fptr(scale), C.byref(res)))
+        return dict(xyz=out, scale=scale, floor=d.floor, clip=dict(clamped=res.clamped, nonfinite=res.nonfinite, alone=res.alone))
+
+    def despeckle_last_ms(self):
+        """kernel-only ms of the context's last despeckle kernel (srt_despeckle_last_ms)"""
+        ms = C.c_float()
+        self._ck(B.lib().srt_despeckle_last_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def denoise_despeckled(self, image_width, image_height, despeckle=None, **cfg):
+        """denoise() with the firefly filter between the prepass and level 0 (srt_denoise_features_ds; despeckle: a dict of the keywords
+        of despeckle_config, None: the defaults; cfg: the keywords of denoise_config): the dict of denoise().  levels=0 returns the
+        despeckled mean; floor=inf equals denoise().  Reads the accumulation, changes nothing of it."""
+        c = denoise_config(**cfg)
+        d = self._despeckle_cfg("denoise_despeckled", despeckle)
+        out = [np.zeros((image_height, image_width, 3), np.float32) for _ in range(3)]
+        self._ck(B.lib().srt_denoise_features_ds(self._h, C.byref(d), C.byref(c), B.fptr(out[0]), B.fptr(out[1]), B.fptr(out[2]), image_width, image_height))
+        return dict(xyz=out[0], lin=out[1], fb=out[2])
+
+    def present_despeckled(self, image_width, image_height, source="accum", gain=None, despeckle=None, **cfg):
+        """present() with the firefly filter in front (srt_present_despeckled; source "accum" or "denoise"; despeckle: a dict of the
+        keywords of despeckle_config, None: the defaults; the other arguments are present_config's): the dict of present() plus
+        despeckle = dict(clamped, nonfinite, alone).  Metering (gain=None) meters the despeckled picture.  Reads the accumulation,
+        changes nothing of it."""
+        p, res, dres = present_config(source, gain, **cfg), B.PresentResult(), B.DespeckleResult()
+        if source not in ("accum", "denoise"):
+            raise ValueError("present_despeckled: source must be \"accum\" or \"denoise\", got %r" % (source,))
+        d = self._despeckle_cfg("present_despeckled", despeckle)
+        out = np.zeros((image_height, image_width, 4), np.uint8)
+        self._ck(B.lib().srt_present_despeckled(self._h, C.byref(p), C.byref(d), out.ctypes.data_as(C.POINTER(C.c_uint8)), 4 * image_width, image_width,
+                                                image_height, C.byref(res), C.byref(dres)))
+        return dict(rgba=out, meter=_meter_dict(res.meter) if gain is None else None,
+                    clip=dict(blown=res.tone.blown, crushed=res.tone.crushed, nonfinite=res.tone.nonfinite),
+                    despeckle=dict(clamped=dres.clamped, nonfinite=dres.nonfinite, alone=dres.alone))
+
     def accum_reset_features(self):
         """start a FEATURED accumulation (srt_c_api.h): like accum_reset, and each later pass also adds, at the first hit of every
         sample's camera ray, the face-forwarded normal, the hit material's colour, the distance and 1 to the pixel's eight raw float32
@@ -1308,6 +1374,59 @@ def _exposed_passes(scene, cam, width, height, sched, bounce_limit, seed, device
             out = _collect(r, width, height)
             exposed = r.expose(width, height, gain, **cfg)
             yield r.accum_samples, out, exposed["meter"], exposed
+
+
+_DESPECKLE_KEYS = ("radius", "rank_ppm", "gain", "floor")
+
+
+def despeckle_config(radius=2, rank_ppm=875000, gain=4.0, floor=None):
+    """srt_despeckle from Python numbers, checked as the library checks it (ValueError): radius 1 or 2, the window is (2 radius + 1)^2
+    pixels without its centre; rank_ppm a whole number in [0, 1000000], the rank of the reference neighbour in parts per million of
+    m - 1 (500000: the lower median; 875000: with 24 neighbours the 4th largest, which keeps a one-pixel-wide line; 1000000: the
+    largest); gain finite and >= 0 in float32; floor >= 0 in float32 (inf switches the filter off) or None.  A pixel is clamped to
+    limit = gain * reference + floor.  floor None stands for a metered floor: the struct holds 0, and the Renderer methods that take
+    these keywords put the median luminance bin of the lit pixels there (meter(percentile_ppm=500000)["y_ref"]), without which a
+    sparse picture -- most neighbours black -- is clamped to black.  The defaults are starting values, untuned."""
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or radius not in (1, 2):
+        raise ValueError("despeckle: radius must be 1 or 2, got %r" % (radius,))
+    if isinstance(rank_ppm, bool) or not isinstance(rank_ppm, (int, np.integer)) or not 0 <= rank_ppm <= 1000000:
+        raise ValueError("despeckle: rank_ppm must be a whole number in [0, 1000000], got %r" % (rank_ppm,))
+    g = _expose_number("despeckle", "gain", gain)
+    if not (np.isfinite(g) and g >= 0.0):
+        raise ValueError("despeckle: gain must be finite and >= 0 in float32, got %r" % (gain,))
+    f = 0.0 if floor is None else _expose_number("despeckle", "floor", floor)
+    if not f >= 0.0:
+        raise ValueError("despeckle: floor must be >= 0 in float32 (inf switches the filter off) or None (metered), got %r" % (floor,))
+    return B.Despeckle(int(radius), int(rank_ppm), g, f, (C.c_uint32 * 4)(0, 0, 0, 0))
+
+
+def render_despeckled(scene, cam, width, height, passes, bounce_limit, denoise=True, despeckle=None, seed=1984, device=0, renderer=None, **cfg):
+    """render_features with the firefly filter behind every pass: a generator of (spp_total, result, features, cleaned) -- with
+    denoise=True `cleaned` is the dict of Renderer.denoise_despeckled (cfg: the keywords of denoise_config), else the dict of
+    Renderer.despeckle (no cfg); despeckle: a dict of the keywords of despeckle_config, None: the defaults.  The filter only reads the
+    accumulation, so result and features are render_features' bit for bit.  Schedule and configurations are checked here, before any
+    device is touched."""
+    sched = progressive_schedule(passes)
+    kw = dict(despeckle or {})
+    unknown = sorted(set(kw) - set(_DESPECKLE_KEYS))
+    if unknown:
+        raise TypeError("render_despeckled: unknown despeckle keyword(s) %s (%s)" % (", ".join(unknown), ", ".join(_DESPECKLE_KEYS)))
+    despeckle_config(**kw)
+    if denoise:
+        denoise_config(**cfg)
+    elif cfg:
+        raise TypeError("render_despeckled: %s given with denoise=False, which runs no denoiser" % ", ".join(sorted(cfg)))
+    return _despeckled_passes(scene, cam, width, height, sched, bounce_limit, seed, device, renderer, bool(denoise), kw, cfg)
+
+
+def _despeckled_passes(scene, cam, width, height, sched, bounce_limit, seed, device, renderer, denoise, despeckle, cfg):
+    with _image_session(scene, cam, width, height, sum(sched), bounce_limit, seed, device, renderer) as r:
+        r.accum_reset_features()
+        for spp_add in sched:
+            r.render_chunk_accum(width, height, spp_add)
+            r.scatter_tiles()
+            cleaned = r.denoise_despeckled(width, height, despeckle, **cfg) if denoise else r.despeckle(width, height, **despeckle)
+            yield r.accum_samples, _collect(r, width, height), r.read_features(width, height), cleaned
 
 
 MAX_DENOISE_LEVELS = 8

@@ -775,6 +775,68 @@ SRT_API int srt_present_kat(srt_ctx *ctx, const srt_tone *tone, const float *xyz
                             srt_tone_result *result);
 SRT_API int srt_present_last_ms(srt_ctx *ctx, float *ms);
 
+/* The firefly filter (no reference counterpart; kernel in csrc/srt_despeckle.hip): a rank-based outlier clamp on the XYZ mean, ahead of the
+ * denoiser.  The path finds a light only by hitting it, so a sparse picture holds isolated pixels far above all their neighbours; the
+ * a-trous filter keeps such a pixel by construction (every tap's colour weight is 0, and it returns the pixel itself).  The clamp scales a
+ * pixel whose luminance exceeds a limit taken from a rank statistic of its neighbours down to that limit, keeping its chromaticity.
+ * Operation by operation -- everything fp32, not contracted, evaluated left to right, with compares and selects only; the restatement is
+ * tests/despeckle_reference.py, which the device equals in every integer and every bit:
+ *   The input is a w x h picture of XYZ means c.  From an accumulation it is c = inv * S with inv = 1.0f / (float)n, where n is the
+ *     sample total; on an adaptive kind n is the pixel's own count, and 0 counts as 1, as tone_kernel normalises.
+ *   cfg is srt_despeckle { uint32_t radius, rank_ppm; float gain, floor; uint32_t reserved[4]; }.
+ *   For pixel p, over the window of offsets (dx, dy) with |dx|, |dy| <= radius and the centre excluded:
+ *     valid(q)  :=  q inside the rectangle  &&  (Y_q - Y_q) == 0            (Y = the second component)
+ *     v_q        =  Y_q > 0 ? Y_q : +0.0f                                   (negatives and both zeros become +0)
+ *     m          =  number of valid q;   u_0 <= u_1 <= .. <= u_{m-1}  the v_q in ascending order
+ *     k          =  (uint64)(m - 1) * rank_ppm / 1000000;    ref = u_k      (500000: lower median; 1000000: the largest)
+ *     limit      =  gain * ref;   limit = limit + floor
+ *     classes, the tests in this order:
+ *       1. nonfinite: (v - v) == 0 is false for a component v of c_p   ->  o = c_p, s = 1.0f
+ *       2. alone:     m == 0                                           ->  o = c_p, s = 1.0f
+ *       3. clamped:   Y_p > limit    ->  s = limit / Y_p;  o = (s * c_p.x, s * c_p.y, s * c_p.z)
+ *       4. kept:      otherwise      ->  o = c_p (its bits), s = 1.0f
+ *   ref is a rank statistic of canonical non-negative values, where equal values have equal bits: it does not depend on the order in
+ *   which the window is read or sorted.  The counters clamped, nonfinite and alone are integers, added with atomics after a wave-level
+ *   reduction, as the tone kernel counts.  A non-finite pixel is neither repaired nor used as a neighbour.
+ *   What follows: a picture scaled by 2^k with floor scaled by 2^k (no overflow, no underflow) gives the same classes and exactly 2^k
+ *   times the output; flipping or transposing the picture commutes with the filter, bit for bit; floor = +inf makes limit = +inf and the
+ *   output the input, bit for bit.
+ *   cfg, validated by every entry point that takes one, else SRT_ERR_INVALID: radius 1 or 2; rank_ppm <= 1000000; gain finite and >= 0;
+ *     floor >= 0 and not NaN (+inf allowed: the filter is off); the reserved words 0.
+ *   srt_despeckle_accum     the filter on the bound accumulation of ANY kind, streamed included.  out_xyz is o, out_lin / out_q are
+ *                           xyz_mean_to_srgb(o) (three floats per pixel each), out_scale[h][w] is s; *result the three counters.  Any
+ *                           output may be NULL, but not all four together with result.  Placement, clipping, synchronisation and the
+ *                           read-only behaviour are srt_expose_accum's.  SRT_ERR_INVALID as srt_expose_accum's (a bad srt_despeckle in the
+ *                           place of a bad srt_tone); SRT_ERR_UNSUPPORTED under a partition other than (0, 1), as the denoisers':
+ *                           a pixel's neighbours must be on this context.
+ *   srt_despeckle_kat       the same kernel on a caller's row-major host array xyz_mean[h][w][3]; out_xyz [h][w][3], out_scale [h][w],
+ *                           either may be NULL, not both together with result.  Refusals as srt_expose_kat's.
+ *   srt_despeckle_last_ms   kernel-only time in ms, from HIP events, of the context's last despeckle kernel; SRT_ERR_INVALID before one ran.
+ *   srt_denoise_features_ds srt_denoise_features with one stage added between the prepass and level 0: colour[1] = Despeckle(colour[0])
+ *                           on the denoiser's float4 colour image (the fourth word carried through); the levels start from colour[1], the
+ *                           guides are untouched, and levels == 0 returns the despeckled mean.  Refusals are srt_denoise_features' plus a
+ *                           bad srt_despeckle.  At floor = +inf it equals srt_denoise_features, bit for bit.  srt_denoise_last_ms reports
+ *                           prepass, levels and epilogue as before; the stage's time is srt_despeckle_last_ms.
+ *   srt_present_despeckled  srt_present with the stage in front.  SRT_PRESENT_ACCUM presents -- and, when metering, meters -- the
+ *                           despeckled picture, which lies on the device as [h][w][3], as srt_meter_kat would; SRT_PRESENT_DENOISE runs
+ *                           the chain of srt_denoise_features_ds.  Other sources and every partition other than (0, 1) are
+ *                           SRT_ERR_UNSUPPORTED; the other refusals are srt_present's plus a bad or null srt_despeckle.  *despeckle_result,
+ *                           unless NULL, receives the stage's counters.
+ * Working blocks (32 bytes of counters and ten floats per pixel of the rectangle) belong to the context and are reused.  No call here
+ * invalidates or alters an accumulation, the frame or the RNG state. */
+typedef struct srt_despeckle { uint32_t radius, rank_ppm; float gain, floor; uint32_t reserved[4]; } srt_despeckle;
+typedef struct srt_despeckle_result { uint64_t clamped, nonfinite, alone; } srt_despeckle_result;
+SRT_API int srt_despeckle_accum(srt_ctx *ctx, const srt_despeckle *cfg, float *out_xyz, float *out_lin, float *out_q, float *out_scale,
+                                srt_despeckle_result *result, uint32_t image_width, uint32_t image_height);
+SRT_API int srt_despeckle_kat(srt_ctx *ctx, const srt_despeckle *cfg, const float *xyz_mean, uint32_t w, uint32_t h,
+                              float *out_xyz, float *out_scale, srt_despeckle_result *result);
+SRT_API int srt_despeckle_last_ms(srt_ctx *ctx, float *ms);
+SRT_API int srt_denoise_features_ds(srt_ctx *ctx, const srt_despeckle *despeckle_cfg, const srt_denoise *denoise_cfg,
+                                    float *out_xyz, float *out_lin, float *out_q, uint32_t image_width, uint32_t image_height);
+SRT_API int srt_present_despeckled(srt_ctx *ctx, const srt_present_cfg *present_cfg, const srt_despeckle *despeckle_cfg, uint8_t *out_rgba8,
+                                   size_t pitch_bytes, uint32_t image_width, uint32_t image_height, srt_present_result *result,
+                                   srt_despeckle_result *despeckle_result);
+
 /* Sample-parallel pixels (no reference counterpart; a deliberate departure from its one RNG stream per pixel, so opt-in).  A STREAMED
  * accumulation gives every pixel K independent RNG streams, each with its own state and its own XYZ sum, so that any lane of any wave
  * can render a stream while others render the pixel's other streams: the longest sequential chain of a pass is spp_add / K samples.
