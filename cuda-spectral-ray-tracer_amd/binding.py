@@ -112,6 +112,19 @@ class DespeckleResult(C.Structure):
     _fields_ = [("clamped", C.c_uint64), ("nonfinite", C.c_uint64), ("alone", C.c_uint64)]
 
 
+class Temporal(C.Structure):
+    """srt_temporal: the blend floor, the history cap and the three rejection thresholds of the temporal reprojection (srt_c_api.h)"""
+    _fields_ = [("alpha_min", C.c_float), ("max_len", C.c_float), ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float),
+                ("sigma_depth", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
+class TemporalResult(C.Structure):
+    """srt_temporal_result: the pixels the stage blended, took fresh (of those: off-screen, rejected) and found non-finite, the calls since
+    the history began and whether this call discarded a history of another rectangle (srt_c_api.h)"""
+    _fields_ = [("blended", C.c_uint64), ("fresh", C.c_uint64), ("offscreen", C.c_uint64), ("rejected", C.c_uint64), ("nonfinite", C.c_uint64),
+                ("history_frames", C.c_uint32), ("history_dropped", C.c_uint32)]
+
+
 class TreeTuning(C.Structure):
     """srt_tree_tuning: what srt_tune_tree_for_throughput found and did (srt_c_api.h)"""
     _fields_ = [("pixels_per_lane", C.c_double), ("throughput_bound", C.c_uint32), ("reinsertion", C.c_uint32),
@@ -129,6 +142,7 @@ assert C.sizeof(Denoise) == 32 and C.sizeof(DenoiseVG) == 32
 assert C.sizeof(Meter) == 48 and C.sizeof(MeterResult) == 40 and C.sizeof(Tone) == 32 and C.sizeof(ToneResult) == 24
 assert C.sizeof(PresentCfg) == 184 and C.sizeof(PresentResult) == 64
 assert C.sizeof(Despeckle) == 32 and C.sizeof(DespeckleResult) == 24
+assert C.sizeof(Temporal) == 32 and C.sizeof(TemporalResult) == 48
 assert C.sizeof(Adaptive) == 16 and C.sizeof(TreeTuning) == 40 and C.sizeof(TileScheduleInfo) == 32
 assert C.sizeof(Material) == 428 and C.sizeof(CameraData) == 84 and C.sizeof(TriIn) == 44
 
@@ -206,6 +220,15 @@ PROTOTYPES = {
     "srt_denoise_features_ds": (_i, [_vp, C.POINTER(Despeckle), C.POINTER(Denoise), _fp, _fp, _fp, _u32, _u32]),
     "srt_present_despeckled": (_i, [_vp, C.POINTER(PresentCfg), C.POINTER(Despeckle), C.POINTER(C.c_uint8), _sz, _u32, _u32, C.POINTER(PresentResult),
                                 C.POINTER(DespeckleResult)]),
+    "srt_temporal_reset": (_i, [_vp]),
+    "srt_temporal_accum": (_i, [_vp, C.POINTER(Temporal), _fp, _fp, _fp, _fp, _fp, C.POINTER(TemporalResult), _u32, _u32]),
+    "srt_temporal_kat": (_i, [_vp, C.POINTER(Temporal), C.POINTER(CameraData), C.POINTER(CameraData), _fp, _fp, _fp, _fp, _u32, _u32, _u32, _u32,
+                              _fp, _fp, _fp, C.POINTER(TemporalResult)]),
+    "srt_denoise_features_temporal": (_i, [_vp, C.POINTER(Temporal), C.POINTER(Despeckle), C.POINTER(Denoise), _fp, _fp, _fp, C.POINTER(TemporalResult),
+                                           _u32, _u32]),
+    "srt_present_temporal": (_i, [_vp, C.POINTER(PresentCfg), C.POINTER(Temporal), C.POINTER(Despeckle), C.POINTER(C.c_uint8), _sz, _u32, _u32,
+                                  C.POINTER(PresentResult), C.POINTER(TemporalResult)]),
+    "srt_temporal_last_ms": (_i, [_vp, _fp]),
     "srt_accum_reset_features": (_i, [_vp]),
     "srt_read_features": (_i, [_vp, _fp, _u32, _u32]),
     "srt_accum_reset_adaptive_features": (_i, [_vp, C.POINTER(Adaptive)]),

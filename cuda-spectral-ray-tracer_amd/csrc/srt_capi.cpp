@@ -160,7 +160,7 @@ struct srt_ctx {
     DeviceBuffer d_denoise;                             // the denoiser's working images (DenoiseLayout), grown when the rectangle grows
     DeviceBuffer d_denoise_in;                          // srt_denoise_kat: the caller's sums and feature rows
     DeviceBuffer d_denoise_dev;                         // srt_denoise_developed: the payload images (DenoiseDevLayout), grown when rectangle or channels grow
-    hipEvent_t denoise_ev[12] = {};                     // around the kernels of the last denoise: prepass | (estimator) | levels | epilogue (created on first use)
+    hipEvent_t denoise_ev[13] = {};                     // around the kernels of the last denoise: prepass | (estimator) | (despeckle) | (temporal) | levels | epilogue (created on first use)
     uint32_t denoise_timed_levels = 0;                  // levels the events of the last denoise bracket
     uint32_t denoise_level_ev = 1;                      // the event level 0 starts at: 1, or 2 after a variance-guided denoise
     bool denoise_timed = false;
@@ -182,6 +182,16 @@ struct srt_ctx {
     DeviceBuffer d_despeckle;                           // the firefly filter: its counters and its four row-major images (DespeckleLayout)
     hipEvent_t despeckle_ev[2] = {};                    // around the last despeckle kernel (created on first use)
     bool despeckle_timed = false;
+    // temporal reprojection (srt_temporal.hip): the history survives srt_set_camera and srt_accum_reset*, which is its point
+    DeviceBuffer d_temporal_hist;                       // the double-buffered history of the last rectangle (TemporalHistory): 96 bytes per pixel
+    DeviceBuffer d_temporal;                            // the stage's counters and its row-major output images (TemporalLayout)
+    DeviceBuffer d_temporal_kat;                        // srt_temporal_kat: the caller's arrays and the history it gets back (TemporalKatLayout)
+    uint32_t temporal_frames = 0;                       // calls since the history began (0: there is none)
+    uint32_t temporal_cur = 0;                          // the half of d_temporal_hist the last call wrote
+    uint32_t temporal_rect[4] = {0, 0, 0, 0};           // w, h, offx, offy of the history's rectangle
+    srt_camera_data temporal_cam = {};                  // the camera that was current when the history was written
+    hipEvent_t temporal_ev[2] = {};                     // around the last temporal kernel (created on first use)
+    bool temporal_timed = false;
     DeviceBuffer d_streams;                            // sample-parallel pixels (srt_accum_reset_streams, StreamPlanes)
     uint32_t streams_seeded = 0;                        // the K whose RNG streams d_streams holds, seeded since the last srt_init_device_params (0: none)
 };
@@ -644,6 +654,7 @@ void srt_destroy(srt_ctx *c) {
     for (hipEvent_t e : c->expose_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->present_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->despeckle_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->temporal_ev) if (e) (void)hipEventDestroy(e);
     delete c;      // (every DeviceBuffer, and the pinned staging block, frees itself, on the device selected above)
 }
 
@@ -655,6 +666,7 @@ const char *srt_last_error(const srt_ctx *ctx) { return ctx ? ctx->err.c_str() :
 int srt_upload_scene(srt_ctx *c, const srt_scene *s) {
     if (!c || !s) return fail(c, SRT_ERR_INVALID, "srt_upload_scene: null argument");
     c->accum.invalidate();
+    c->temporal_frames = 0;      // (the temporal history shows another scene)
     c->sched_probe_queue = false; c->sched_compacted_queue = false;      // (the queues of the last launch belong to the old set-up)
     HIP_TRY(c, hipSetDevice(c->device));
     FlatScene f;
@@ -758,6 +770,7 @@ int srt_internal_init_device_params(srt_ctx *c, uint32_t tx, uint32_t ty, uint32
     if (tx == 0 || ty == 0 || bx == 0 || by == 0 || chunk_w == 0 || chunk_h == 0)
         return fail(c, SRT_ERR_INVALID, "srt_init_device_params: zero dimension");
     c->accum.invalidate();
+    c->temporal_frames = 0;      // (the temporal history belongs to the old grid)
     c->sched_probe_queue = false; c->sched_compacted_queue = false;      // (the queues of the last launch belong to the old set-up)
     const uint64_t lanes = (uint64_t)tx * ty * bx * by;
     if (lanes > 0x7fffffffull) return fail(c, SRT_ERR_INVALID, "srt_init_device_params: grid too large");
@@ -785,6 +798,7 @@ int srt_init_device_params(srt_ctx *c, uint32_t tx, uint32_t ty, uint32_t bx, ui
 int srt_set_partition(srt_ctx *c, uint32_t rank, uint32_t world) {
     if (!c || world == 0 || rank >= world) return fail(c, SRT_ERR_INVALID, "srt_set_partition: need rank < world");
     c->accum.invalidate();
+    c->temporal_frames = 0;      // (the temporal history belongs to the old partition)
     c->sched_probe_queue = false; c->sched_compacted_queue = false;      // (the queues of the last launch belong to the old set-up)
     c->rank = rank; c->world = world;
     return SRT_OK;
@@ -1750,6 +1764,189 @@ int srt_despeckle_last_ms(srt_ctx *c, float *ms) {
     return SRT_OK;
 }
 
+// ---- temporal reprojection (srt_temporal.hip) -------------------------------------------------------------------------------------
+namespace {
+
+// d_temporal: [counters: blended, fresh, offscreen, rejected, non-finite (u64 each), padded to 64 bytes | out_xyz | out_lin | out_q: three
+//              floats per pixel each | out_len: one | out_motion: two]
+struct TemporalLayout {
+    unsigned long long *counts;
+    float *img[3], *len, *motion;
+    static constexpr size_t kHeadBytes = 64;
+    static size_t bytes(size_t pixels) { return kHeadBytes + 12 * pixels * sizeof(float); }
+    TemporalLayout(const DeviceBuffer &d, size_t pixels) : counts(d.as<unsigned long long>()) {
+        img[0] = reinterpret_cast<float *>(d.as<char>() + kHeadBytes); img[1] = img[0] + 3 * pixels; img[2] = img[1] + 3 * pixels;
+        len = img[2] + 3 * pixels; motion = len + pixels;      // (the images: inside the buffer only when it was reserved with pixels)
+    }
+};
+// d_temporal_hist: two halves of [Hc: one float4 per pixel | Hg: two]
+struct TemporalHistory {
+    float4 *colour[2], *guides[2];
+    static size_t bytes(size_t pixels) { return 6 * pixels * sizeof(float4); }
+    TemporalHistory(const DeviceBuffer &d, size_t pixels) {
+        for (int k = 0; k < 2; k++) { colour[k] = d.as<float4>() + 3 * pixels * k; guides[k] = colour[k] + pixels; }
+    }
+};
+// d_temporal_kat: [guides: 2 float4 per pixel | hist_c: 1 | hist_g: 2 | new_c: 1 | new_g: 2 | xyz: three floats per pixel]
+struct TemporalKatLayout {
+    float4 *guides, *hist_c, *hist_g, *new_c, *new_g;
+    float *xyz;
+    static size_t bytes(size_t pixels) { return pixels * (8 * sizeof(float4) + 3 * sizeof(float)); }
+    TemporalKatLayout(const DeviceBuffer &d, size_t pixels) : guides(d.as<float4>()) {
+        hist_c = guides + 2 * pixels; hist_g = hist_c + pixels; new_c = hist_g + 2 * pixels; new_g = new_c + pixels;
+        xyz = reinterpret_cast<float *>(new_g + 2 * pixels);
+    }
+};
+
+const char *temporal_cfg_error(const srt_temporal *t) {
+    if (!(t->alpha_min > 0.0f && t->alpha_min <= 1.0f)) return "temporal: alpha_min must be in (0, 1]";
+    if (!(t->max_len >= 1.0f) || !std::isfinite(t->max_len)) return "temporal: max_len must be finite and >= 1";
+    for (const float s : {t->sigma_normal, t->sigma_albedo, t->sigma_depth})
+        if (!(s > 0.0f)) return "temporal: every sigma must be greater than 0 (+inf switches its test off)";
+    for (const uint32_t r : t->reserved) if (r) return "temporal: the reserved words must be 0";
+    return nullptr;
+}
+
+// the host constants of srt_c_api.h, fp32, one rounding per operation (this unit is built without contraction)
+struct Vec3f { float x, y, z; };
+Vec3f vec3f(const float a[3]) { return {a[0], a[1], a[2]}; }
+float dot3f(Vec3f a, Vec3f b) { const float s = a.x * b.x + a.y * b.y; return s + a.z * b.z; }
+Vec3f cross3f(Vec3f a, Vec3f b) {
+    const float x0 = a.y * b.z, x1 = a.z * b.y, y0 = a.z * b.x, y1 = a.x * b.z, z0 = a.x * b.y, z1 = a.y * b.x;
+    return {x0 - x1, y0 - y1, z0 - z1};
+}
+void put3f(float dst[3], Vec3f v) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; }
+void temporal_cameras(TemporalParams &p, const srt_camera_data &cur, const srt_camera_data *prev) {
+    for (int k = 0; k < 3; k++) { p.du[k] = cur.pixel_delta_u[k]; p.dv[k] = cur.pixel_delta_v[k]; p.p00[k] = cur.pixel00_loc[k]; p.center[k] = cur.camera_center[k]; }
+    if (!prev) return;
+    const Vec3f du = vec3f(prev->pixel_delta_u), dv = vec3f(prev->pixel_delta_v), p00 = vec3f(prev->pixel00_loc), ce = vec3f(prev->camera_center);
+    const Vec3f n = cross3f(du, dv);
+    const Vec3f e = {p00.x - ce.x, p00.y - ce.y, p00.z - ce.z};
+    const Vec3f cu = cross3f(dv, n), cv = cross3f(n, du);
+    const float su = dot3f(du, cu), sv = dot3f(dv, cv);
+    put3f(p.pcenter, ce); put3f(p.pn, n); put3f(p.pe, e);
+    p.pk = dot3f(e, n);
+    put3f(p.pbu, {cu.x / su, cu.y / su, cu.z / su});
+    put3f(p.pbv, {cv.x / sv, cv.y / sv, cv.z / sv});
+}
+
+// The temporal kernel over the rectangle described by p (its sources, history, outputs and rectangle set by the caller; cfg, cameras and
+// counters are filled in here), between the context's two temporal events.  d_temporal is reserved by the caller.  Enqueues; the caller
+// synchronises.  prev: the camera of p's history (not read without one).
+int run_temporal_kernel(srt_ctx *c, const char *who, TemporalParams p, const srt_temporal *cfg, const srt_camera_data &cur, const srt_camera_data *prev) {
+    const TemporalLayout L(c->d_temporal, 0);
+    c->temporal_timed = false;
+    for (hipEvent_t &e : c->temporal_ev) if (!e) HIP_TRY_AS(c, who, hipEventCreate(&e));
+    HIP_TRY_AS(c, who, hipMemsetAsync(L.counts, 0, 5 * sizeof(unsigned long long), nullptr));
+    temporal_cameras(p, cur, p.hist_c ? prev : nullptr);
+    p.kn = cfg->sigma_normal * cfg->sigma_normal; p.ka = cfg->sigma_albedo * cfg->sigma_albedo; p.kz = cfg->sigma_depth * cfg->sigma_depth;
+    p.alpha_min = cfg->alpha_min; p.max_len = cfg->max_len;
+    p.counts = L.counts;
+    HIP_TRY_AS(c, who, hipEventRecord(c->temporal_ev[0], nullptr));
+    HIP_TRY_AS(c, who, launch_temporal(p, nullptr));
+    HIP_TRY_AS(c, who, hipEventRecord(c->temporal_ev[1], nullptr));
+    c->temporal_timed = true;
+    return SRT_OK;
+}
+
+// The stage on the context's history: p holds the sources, dst4 and outputs of the w x h rectangle of the last chunk.  A history of another
+// rectangle is discarded (res->history_dropped).  The history advances when the kernel has been enqueued.  d_temporal is reserved by the caller.
+int run_temporal_history(srt_ctx *c, const char *who, TemporalParams p, const srt_temporal *cfg, srt_temporal_result *res) {
+    const uint32_t rect[4] = {p.w, p.h, c->last_offx, c->last_offy};
+    const size_t pixels = (size_t)p.w * p.h;
+    res->history_dropped = 0;
+    if (c->temporal_frames && memcmp(rect, c->temporal_rect, sizeof(rect)) != 0) {
+        c->temporal_frames = 0;
+        res->history_dropped = 1;
+    }
+    if (!c->temporal_frames) {      // (only a first frame may grow the block: growing loses what it holds)
+        if (const int rc = develop_reserve(c, who, c->d_temporal_hist, TemporalHistory::bytes(pixels))) return rc;
+    }
+    const TemporalHistory H(c->d_temporal_hist, pixels);
+    const uint32_t old = c->temporal_cur, neu = old ^ 1u;
+    p.hist_c = c->temporal_frames ? H.colour[old] : nullptr; p.hist_g = c->temporal_frames ? H.guides[old] : nullptr;
+    p.new_c = H.colour[neu]; p.new_g = H.guides[neu];
+    p.ox = c->last_offx; p.oy = c->last_offy;
+    if (const int rc = run_temporal_kernel(c, who, p, cfg, c->cam, &c->temporal_cam)) {
+        c->temporal_frames = 0;      // (a launch that failed may have left half a history)
+        return rc;
+    }
+    c->temporal_cur = neu; c->temporal_frames++; c->temporal_cam = c->cam;
+    memcpy(c->temporal_rect, rect, sizeof(rect));
+    res->history_frames = c->temporal_frames;
+    return SRT_OK;
+}
+
+int read_temporal_counts(srt_ctx *c, const char *who, srt_temporal_result *result) {
+    unsigned long long counts[5] = {0, 0, 0, 0, 0};
+    HIP_TRY_AS(c, who, hipMemcpy(counts, TemporalLayout(c->d_temporal, 0).counts, sizeof(counts), hipMemcpyDeviceToHost));
+    result->blended = counts[0]; result->fresh = counts[1]; result->offscreen = counts[2]; result->rejected = counts[3]; result->nonfinite = counts[4];
+    return SRT_OK;
+}
+
+// what a chained call asks of the stage: its configuration, whether TemporalLayout's out_xyz is filled, and the result (history_frames and
+// history_dropped when the kernel is enqueued; the counters are read by the caller once the chain has run)
+struct TemporalStage {
+    const srt_temporal *cfg;
+    bool out_xyz;
+    srt_temporal_result res;
+};
+
+}  // namespace
+
+int srt_temporal_reset(srt_ctx *c) {
+    if (!c) return fail(c, SRT_ERR_INVALID, "srt_temporal_reset: null ctx");
+    c->temporal_frames = 0;
+    return SRT_OK;
+}
+
+int srt_temporal_kat(srt_ctx *c, const srt_temporal *cfg, const srt_camera_data *cur_cam, const srt_camera_data *prev_cam, const float *xyz_mean,
+                     const float *guides, const float *hist_colour, const float *hist_guides, uint32_t w, uint32_t h, uint32_t ox, uint32_t oy,
+                     float *out_colour, float *out_guides, float *out_motion, srt_temporal_result *result) {
+    const char *who = "srt_temporal_kat";
+    if (!c || !cfg || !cur_cam || !xyz_mean || !guides) return fail(c, SRT_ERR_INVALID, "srt_temporal_kat: null argument");
+    if (!out_colour && !out_guides && !out_motion && !result) return fail(c, SRT_ERR_INVALID, "srt_temporal_kat: no output");
+    if (w == 0 || h == 0 || (uint64_t)w * h > 0x7fffffffull) return fail(c, SRT_ERR_INVALID, "srt_temporal_kat: w x h must be in 1 .. 2^31 - 1");
+    if ((uint64_t)ox + w > (1ull << 24) || (uint64_t)oy + h > (1ull << 24)) return fail(c, SRT_ERR_INVALID, "srt_temporal_kat: ox + w and oy + h must not exceed 2^24");
+    if (const char *why = temporal_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_temporal_kat: ") + why);
+    const bool history = prev_cam && hist_colour && hist_guides;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t pixels = (size_t)w * h;
+    if (const int rc = develop_reserve(c, who, c->d_temporal, TemporalLayout::bytes(pixels))) return rc;
+    if (const int rc = develop_reserve(c, who, c->d_temporal_kat, TemporalKatLayout::bytes(pixels))) return rc;
+    const TemporalLayout L(c->d_temporal, pixels);
+    const TemporalKatLayout K(c->d_temporal_kat, pixels);
+    HIP_TRY_AS(c, who, hipMemcpy(K.xyz, xyz_mean, pixels * 3 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY_AS(c, who, hipMemcpy(K.guides, guides, pixels * 2 * sizeof(float4), hipMemcpyHostToDevice));
+    if (history) {
+        HIP_TRY_AS(c, who, hipMemcpy(K.hist_c, hist_colour, pixels * sizeof(float4), hipMemcpyHostToDevice));
+        HIP_TRY_AS(c, who, hipMemcpy(K.hist_g, hist_guides, pixels * 2 * sizeof(float4), hipMemcpyHostToDevice));
+    }
+    TemporalParams p = {};
+    p.xyz = K.xyz; p.guides = K.guides; p.hist_c = history ? K.hist_c : nullptr; p.hist_g = history ? K.hist_g : nullptr;
+    p.new_c = K.new_c; p.new_g = K.new_g; p.w = w; p.h = h; p.ox = ox; p.oy = oy;
+    p.out_motion = out_motion ? L.motion : nullptr;
+    if (const int rc = run_temporal_kernel(c, who, p, cfg, *cur_cam, prev_cam)) return rc;
+    if (out_colour) HIP_TRY_AS(c, who, hipMemcpy(out_colour, K.new_c, pixels * sizeof(float4), hipMemcpyDeviceToHost));
+    if (out_guides) HIP_TRY_AS(c, who, hipMemcpy(out_guides, K.new_g, pixels * 2 * sizeof(float4), hipMemcpyDeviceToHost));
+    if (out_motion) HIP_TRY_AS(c, who, hipMemcpy(out_motion, L.motion, pixels * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    srt_temporal_result res = {};
+    if (const int rc = read_temporal_counts(c, who, &res)) return rc;
+    res.history_frames = history ? 2u : 1u;
+    HIP_TRY_AS(c, who, hipDeviceSynchronize());
+    if (result) *result = res;
+    return SRT_OK;
+}
+
+int srt_temporal_last_ms(srt_ctx *c, float *ms) {
+    if (!c || !ms) return fail(c, SRT_ERR_INVALID, "srt_temporal_last_ms: null argument");
+    if (!c->temporal_timed) return fail(c, SRT_ERR_INVALID, "srt_temporal_last_ms: no temporal kernel has run on this context");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipEventSynchronize(c->temporal_ev[1]));
+    HIP_TRY(c, hipEventElapsedTime(ms, c->temporal_ev[0], c->temporal_ev[1]));
+    return SRT_OK;
+}
+
 // ---- the denoiser (srt_denoise.hip) ---------------------------------------------------------------------------------------------
 namespace {
 
@@ -1815,37 +2012,55 @@ DenoisePlan denoise_vg_plan(const srt_denoise_vg *cfg) {
 // sum_y2: the S2 words of a measured plan (indexed like pre.counts), else unused.
 // ds (plain plans only; the caller has reserved d_despeckle): the firefly filter between the prepass and level 0, colour[1] =
 // Despeckle(colour[0]), between its own events; one more denoise event behind it, so that level 0 is timed alone.
-int run_denoise(srt_ctx *c, const char *who, const DenoisePlan &plan, DenoisePrepassParams pre, const float *sum_y2 = nullptr, const srt_despeckle *ds = nullptr) {
+// ts (plain plans only; the caller has reserved d_temporal): the temporal stage behind that, colour[cur ^ 1] = Temporal(colour[cur]) on the
+// context's history, between its own events and with one more denoise event behind it.  ts_out (with ts): the stage's outputs; the run
+// stops behind the stage -- no level, no epilogue: srt_temporal_accum -- and records no denoise event, so the timing of the context's
+// last denoise stays what it was.
+int run_denoise(srt_ctx *c, const char *who, const DenoisePlan &plan, DenoisePrepassParams pre, const float *sum_y2 = nullptr, const srt_despeckle *ds = nullptr,
+                TemporalStage *ts = nullptr, const TemporalParams *ts_out = nullptr) {
     const size_t pixels = (size_t)pre.w * pre.h;
     const DenoiseLayout L(c->d_denoise, pixels);
     pre.guides = L.guides; pre.colour = L.colour[0];
-    c->denoise_timed = false;
-    for (hipEvent_t &e : c->denoise_ev) if (!e) HIP_TRY_AS(c, who, hipEventCreate(&e));
+    const bool timed = !ts_out;
+    if (timed) {
+        c->denoise_timed = false;
+        for (hipEvent_t &e : c->denoise_ev) if (!e) HIP_TRY_AS(c, who, hipEventCreate(&e));
+    }
     uint32_t n_ev = 0;
-    HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
+    const auto mark = [&]() { return timed ? hipEventRecord(c->denoise_ev[n_ev++], nullptr) : hipSuccess; };
+    HIP_TRY_AS(c, who, mark());
     HIP_TRY_AS(c, who, launch_denoise_prepass(pre, nullptr));
-    HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
+    HIP_TRY_AS(c, who, mark());
     if (plan.vg && plan.measured) {
         DenoiseMeasuredParams mp = {};
         mp.sum_y = pre.sums + pre.sum_comp_stride; mp.sum_y2 = sum_y2; mp.counts = pre.counts; mp.sum_pixel_stride = pre.sum_pixel_stride;
         mp.tx = pre.tx; mp.ty = pre.ty; mp.bx = pre.bx; mp.w = pre.w; mp.h = pre.h;
         mp.colour = reinterpret_cast<float *>(L.colour[0]); mp.out_var = L.var;
         HIP_TRY_AS(c, who, launch_denoise_measured(mp, nullptr));
-        HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
+        HIP_TRY_AS(c, who, mark());
     } else if (plan.vg) {
         DenoiseVarianceParams vp = {};
         vp.guides = L.guides; vp.colour = reinterpret_cast<float *>(L.colour[0]); vp.out_var = L.var;
         vp.w = pre.w; vp.h = pre.h; vp.kn = plan.kn; vp.ka = plan.ka; vp.kz = plan.kz;
         HIP_TRY_AS(c, who, launch_denoise_variance(vp, nullptr));
-        HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
+        HIP_TRY_AS(c, who, mark());
     }
     uint32_t cur = 0;
     if (ds) {
         DespeckleParams dp = {};
         dp.src4 = L.colour[0]; dp.dst4 = L.colour[1]; dp.w = pre.w; dp.h = pre.h;
         if (const int rc = run_despeckle(c, who, dp, ds)) return rc;
-        HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
+        HIP_TRY_AS(c, who, mark());
         cur = 1;
+    }
+    if (ts) {
+        TemporalParams tp = ts_out ? *ts_out : TemporalParams{};
+        tp.src4 = L.colour[cur]; tp.guides = L.guides; tp.dst4 = L.colour[cur ^ 1u]; tp.w = pre.w; tp.h = pre.h;
+        if (ts->out_xyz) tp.out_xyz = TemporalLayout(c->d_temporal, pixels).img[0];
+        if (const int rc = run_temporal_history(c, who, tp, ts->cfg, &ts->res)) return rc;
+        HIP_TRY_AS(c, who, mark());
+        cur ^= 1u;
+        if (ts_out) return SRT_OK;      // (the stage alone)
     }
     const uint32_t level_ev = n_ev - 1;
     for (uint32_t i = 0; i < plan.levels; i++) {
@@ -1864,12 +2079,12 @@ int run_denoise(srt_ctx *c, const char *who, const DenoisePlan &plan, DenoisePre
             lp.kn = plan.kn; lp.ka = plan.ka; lp.kz = plan.kz; lp.kc = sc * sc;
             HIP_TRY_AS(c, who, launch_denoise_level(lp, nullptr));
         }
-        HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
+        HIP_TRY_AS(c, who, mark());
         cur ^= 1u;
     }
     HIP_TRY_AS(c, who, launch_denoise_epilogue(reinterpret_cast<const float *>(L.colour[cur]), L.out[0], L.out[1], L.out[2], pixels, nullptr));
     if (plan.vg) HIP_TRY_AS(c, who, launch_denoise_var_out(reinterpret_cast<const float *>(L.colour[cur]), L.var, pixels, nullptr));
-    HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
+    HIP_TRY_AS(c, who, mark());
     c->denoise_timed_levels = plan.levels; c->denoise_level_ev = level_ev; c->denoise_estimated = plan.vg; c->denoise_timed = true;
     return SRT_OK;
 }
@@ -1889,27 +2104,30 @@ int denoise_accumulation_refusal(srt_ctx *c, const char *who, const DenoisePlan 
 }
 
 // run_denoise on the accumulation's w x h rectangle (not empty): the results are left in DenoiseLayout(c->d_denoise, w * h)
-int denoise_accumulation(srt_ctx *c, const char *who, const DenoisePlan &plan, uint32_t w, uint32_t h, const srt_despeckle *ds = nullptr) {
+// ts / ts_out: run_denoise's (ts_out: the stage alone, its outputs in TemporalLayout(c->d_temporal, w * h), which the caller has reserved)
+int denoise_accumulation(srt_ctx *c, const char *who, const DenoisePlan &plan, uint32_t w, uint32_t h, const srt_despeckle *ds = nullptr,
+                         TemporalStage *ts = nullptr, const TemporalParams *ts_out = nullptr) {
     HIP_TRY(c, c->d_denoise.reserve(DenoiseLayout::bytes((size_t)w * h, plan.vg)));
     if (ds) if (const int rc = develop_reserve(c, who, c->d_despeckle, DespeckleLayout::kHeadBytes)) return rc;
+    if (ts && !ts_out) if (const int rc = develop_reserve(c, who, c->d_temporal, ts->out_xyz ? TemporalLayout::bytes((size_t)w * h) : TemporalLayout::kHeadBytes)) return rc;
     DenoisePrepassParams pre = {};
     pre.sums = AccumLayout(c).sums; pre.sum_pixel_stride = 1; pre.sum_comp_stride = c->n_lanes;
     pre.rows = reinterpret_cast<const float4 *>(feature_rows(c));
     pre.tx = c->tx; pre.ty = c->ty; pre.bx = c->bx; pre.w = w; pre.h = h; pre.samples = c->accum.total;
     // (an adaptive featured accumulation: every pixel of the chunk is normalised by its own count, the samples field of its state word)
     if (c->accum.adaptive()) pre.counts = AdaptPlanes(c).state;
-    return run_denoise(c, who, plan, pre, c->accum.adaptive() ? AdaptPlanes(c).sum2 : nullptr, ds);
+    return run_denoise(c, who, plan, pre, c->accum.adaptive() ? AdaptPlanes(c).sum2 : nullptr, ds, ts, ts_out);
 }
 
 int denoise_features(srt_ctx *c, const char *who, const DenoisePlan &plan, float *const host[4], uint32_t image_width, uint32_t image_height,
-                     const srt_despeckle *ds = nullptr) {
+                     const srt_despeckle *ds = nullptr, TemporalStage *ts = nullptr) {
     if (const int rc = denoise_accumulation_refusal(c, who, plan)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     // the filter runs on the chunk's rectangle (clipped to the reference grid); the image clips only what is copied out
     const uint32_t w = clipped_w(c), h = clipped_h(c);
     const size_t pixels = (size_t)w * h;
     if (pixels) {
-        if (const int rc = denoise_accumulation(c, who, plan, w, h, ds)) return rc;
+        if (const int rc = denoise_accumulation(c, who, plan, w, h, ds, ts)) return rc;
         const ChunkRect rect = chunk_rect(c, image_width, image_height);
         const DenoiseLayout L(c->d_denoise, pixels);
         for (int k = 0; k < 4; k++) {
@@ -1918,6 +2136,7 @@ int denoise_features(srt_ctx *c, const char *who, const DenoisePlan &plan, float
             const size_t row = (size_t)rect.w * ch * sizeof(float), src_pitch = (size_t)w * ch * sizeof(float), pitch = (size_t)image_width * ch * sizeof(float);
             if (host[k] && rect.w && rect.h) HIP_TRY(c, hipMemcpy2D(host[k] + rect.first * ch, pitch, src, src_pitch, row, rect.h, hipMemcpyDeviceToHost));
         }
+        if (ts) if (const int rc = read_temporal_counts(c, who, &ts->res)) return rc;
     }
     HIP_TRY(c, hipDeviceSynchronize());
     return SRT_OK;
@@ -1974,6 +2193,58 @@ int srt_denoise_features_ds(srt_ctx *c, const srt_despeckle *despeckle_cfg, cons
     if (const char *why = despeckle_cfg_error(despeckle_cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_denoise_features_ds: ") + why);
     float *const host[4] = {out_xyz, out_lin, out_q, nullptr};
     return denoise_features(c, "srt_denoise_features_ds", denoise_plan(denoise_cfg), host, image_width, image_height, despeckle_cfg);
+}
+
+int srt_denoise_features_temporal(srt_ctx *c, const srt_temporal *temporal_cfg, const srt_despeckle *despeckle_cfg, const srt_denoise *denoise_cfg, float *out_xyz,
+                                  float *out_lin, float *out_q, srt_temporal_result *temporal_result, uint32_t image_width, uint32_t image_height) {
+    const char *who = "srt_denoise_features_temporal";
+    if (!c || !temporal_cfg || !denoise_cfg) return fail(c, SRT_ERR_INVALID, "srt_denoise_features_temporal: null argument");
+    if ((!out_xyz && !out_lin && !out_q) || image_width == 0 || image_height == 0) return fail(c, SRT_ERR_INVALID, "srt_denoise_features_temporal: no output / empty image");
+    if (const char *why = denoise_cfg_error(denoise_cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_denoise_features_temporal: ") + why);
+    if (despeckle_cfg) if (const char *why = despeckle_cfg_error(despeckle_cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_denoise_features_temporal: ") + why);
+    if (const char *why = temporal_cfg_error(temporal_cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_denoise_features_temporal: ") + why);
+    float *const host[4] = {out_xyz, out_lin, out_q, nullptr};
+    TemporalStage ts = {temporal_cfg, false, {}};
+    if (const int rc = denoise_features(c, who, denoise_plan(denoise_cfg), host, image_width, image_height, despeckle_cfg, &ts)) return rc;
+    if (temporal_result) *temporal_result = ts.res;
+    return SRT_OK;
+}
+
+int srt_temporal_accum(srt_ctx *c, const srt_temporal *cfg, float *out_xyz, float *out_lin, float *out_q, float *out_len, float *out_motion,
+                       srt_temporal_result *result, uint32_t image_width, uint32_t image_height) {
+    const char *who = "srt_temporal_accum";
+    if (!c || !cfg) return fail(c, SRT_ERR_INVALID, "srt_temporal_accum: null argument");
+    if ((!out_xyz && !out_lin && !out_q && !out_len && !out_motion && !result) || image_width == 0 || image_height == 0)
+        return fail(c, SRT_ERR_INVALID, "srt_temporal_accum: no output / empty image");
+    if (const char *why = temporal_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_temporal_accum: ") + why);
+    const DenoisePlan plan = {};      // (the prepass alone: no level runs)
+    if (const int rc = denoise_accumulation_refusal(c, who, plan)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the stage runs on the chunk's rectangle (clipped to the reference grid); the image clips only what is copied out
+    const uint32_t w = clipped_w(c), h = clipped_h(c);
+    const size_t pixels = (size_t)w * h;
+    TemporalStage ts = {cfg, false, {}};
+    if (pixels) {
+        if (const int rc = develop_reserve(c, who, c->d_temporal, TemporalLayout::bytes(pixels))) return rc;
+        const TemporalLayout L(c->d_temporal, pixels);
+        TemporalParams out = {};
+        out.out_xyz = out_xyz ? L.img[0] : nullptr; out.out_lin = out_lin ? L.img[1] : nullptr; out.out_q = out_q ? L.img[2] : nullptr;
+        out.out_len = out_len ? L.len : nullptr; out.out_motion = out_motion ? L.motion : nullptr;
+        if (const int rc = denoise_accumulation(c, who, plan, w, h, nullptr, &ts, &out)) return rc;
+        const ChunkRect rect = chunk_rect(c, image_width, image_height);
+        float *const host[5] = {out_xyz, out_lin, out_q, out_len, out_motion};
+        const float *const src[5] = {L.img[0], L.img[1], L.img[2], L.len, L.motion};
+        const size_t chans[5] = {3, 3, 3, 1, 2};      // floats per pixel
+        for (int k = 0; k < 5; k++) {
+            const size_t ch = chans[k];
+            const size_t row = (size_t)rect.w * ch * sizeof(float), src_pitch = (size_t)w * ch * sizeof(float), pitch = (size_t)image_width * ch * sizeof(float);
+            if (host[k] && rect.w && rect.h) HIP_TRY(c, hipMemcpy2D(host[k] + rect.first * ch, pitch, src[k], src_pitch, row, rect.h, hipMemcpyDeviceToHost));
+        }
+        if (const int rc = read_temporal_counts(c, who, &ts.res)) return rc;
+    }
+    HIP_TRY(c, hipDeviceSynchronize());
+    if (result) *result = ts.res;
+    return SRT_OK;
 }
 
 int srt_denoise_features_vg(srt_ctx *c, const srt_denoise_vg *cfg, float *out_xyz, float *out_lin, float *out_q, float *out_var, uint32_t image_width, uint32_t image_height) {
@@ -2251,9 +2522,11 @@ int run_present(srt_ctx *c, const char *who, PresentParams p, const srt_tone *to
 
 namespace {
 
-// srt_present (ds == null) and srt_present_despeckled (ds: the firefly filter in front of the chain; ds_result may be null)
+// srt_present (ds == null) and srt_present_despeckled (ds: the firefly filter in front of the chain; ds_result may be null);
+// srt_present_temporal (tcfg: the temporal stage in front of the chain, behind the firefly filter when there is one; ts_result may be null)
 int present_chain(srt_ctx *c, const char *who, const srt_present_cfg *cfg, const srt_despeckle *ds, uint8_t *out_rgba8, size_t pitch_bytes, uint32_t image_width,
-                  uint32_t image_height, srt_present_result *result, srt_despeckle_result *ds_result) {
+                  uint32_t image_height, srt_present_result *result, srt_despeckle_result *ds_result, const srt_temporal *tcfg = nullptr,
+                  srt_temporal_result *ts_result = nullptr) {
     const std::string w_(std::string(who) + ": ");
     if (!c || !cfg || !out_rgba8) return fail(c, SRT_ERR_INVALID, w_ + "null argument");
     for (const uint32_t r : cfg->reserved) if (r) return fail(c, SRT_ERR_INVALID, w_ + "the reserved words must be 0");
@@ -2266,6 +2539,11 @@ int present_chain(srt_ctx *c, const char *who, const srt_present_cfg *cfg, const
         if (const char *why = despeckle_cfg_error(ds)) return fail(c, SRT_ERR_INVALID, w_ + why);
         if (cfg->source != SRT_PRESENT_ACCUM && cfg->source != SRT_PRESENT_DENOISE)
             return fail(c, SRT_ERR_UNSUPPORTED, w_ + "the despeckled sources are SRT_PRESENT_ACCUM and SRT_PRESENT_DENOISE");
+    }
+    if (tcfg) {
+        if (const char *why = temporal_cfg_error(tcfg)) return fail(c, SRT_ERR_INVALID, w_ + why);
+        if (cfg->source != SRT_PRESENT_ACCUM && cfg->source != SRT_PRESENT_DENOISE)
+            return fail(c, SRT_ERR_UNSUPPORTED, w_ + "the temporal sources are SRT_PRESENT_ACCUM and SRT_PRESENT_DENOISE");
     }
     const bool denoised = cfg->source == SRT_PRESENT_DENOISE || cfg->source == SRT_PRESENT_DENOISE_VG || cfg->source == SRT_PRESENT_DENOISE_MV;
     const bool developed = cfg->source == SRT_PRESENT_DEVELOP;
@@ -2288,7 +2566,7 @@ int present_chain(srt_ctx *c, const char *who, const srt_present_cfg *cfg, const
         if (const char *why = develop_args_error(response3, 3, cfg->scale)) return fail(c, SRT_ERR_INVALID, w_ + why);
     }
     if (!c->accum.bound()) return fail(c, SRT_ERR_INVALID, w_ + "no accumulation with a pass (srt_accum_reset* and srt_render_chunk_accum first)");
-    if (denoised) if (const int rc = denoise_accumulation_refusal(c, who, plan)) return rc;
+    if (denoised || tcfg) if (const int rc = denoise_accumulation_refusal(c, who, plan)) return rc;      // (the stage needs the guides, whatever the source)
     if (ds && (c->rank != 0 || c->world != 1))
         return fail(c, SRT_ERR_UNSUPPORTED, w_ + "needs the whole chunk on this context (partition (0, 1)): pixels of other ranks read +0");
     if (developed && !c->accum.spectral()) return fail(c, SRT_ERR_INVALID, w_ + "SRT_PRESENT_DEVELOP needs a spectral accumulation (srt_accum_reset_spectral*)");
@@ -2300,6 +2578,7 @@ int present_chain(srt_ctx *c, const char *who, const srt_present_cfg *cfg, const
     const size_t pixels = (size_t)w * h;
     srt_present_result res = {};
     srt_despeckle_result ds_res = {};
+    TemporalStage ts = {tcfg, !denoised, {}};
     if (pixels) {
         if (const int rc = develop_reserve(c, who, c->d_expose, ExposeLayout::kBytes)) return rc;
         if (const int rc = develop_reserve(c, who, c->d_present, PresentLayout::bytes(pixels, developed))) return rc;
@@ -2307,8 +2586,14 @@ int present_chain(srt_ctx *c, const char *who, const srt_present_cfg *cfg, const
         // the source: null for the sums themselves, else a [h][w][3] XYZ mean on the device
         const float *picture = nullptr;
         if (denoised) {
-            if (const int rc = denoise_accumulation(c, who, plan, w, h, ds)) return rc;
+            if (const int rc = denoise_accumulation(c, who, plan, w, h, ds, tcfg ? &ts : nullptr)) return rc;
             picture = DenoiseLayout(c->d_denoise, pixels).out[0];
+        } else if (tcfg) {      // the prepass, the firefly filter if any, the stage: its output, [h][w][3] on the device
+            if (const int rc = develop_reserve(c, who, c->d_temporal, TemporalLayout::bytes(pixels))) return rc;
+            TemporalParams out = {};
+            out.out_xyz = TemporalLayout(c->d_temporal, pixels).img[0];
+            if (const int rc = denoise_accumulation(c, who, plan, w, h, ds, &ts, &out)) return rc;
+            picture = out.out_xyz;
         } else if (ds) {      // the despeckled mean, [h][w][3] on the device
             if (const int rc = develop_reserve(c, who, c->d_despeckle, DespeckleLayout::bytes(pixels))) return rc;
             DespeckleParams dp = despeckle_accum_source(c, w, h);
@@ -2348,10 +2633,12 @@ int present_chain(srt_ctx *c, const char *who, const srt_present_cfg *cfg, const
         uint8_t *first = out_rgba8 + (size_t)c->last_offy * pitch_bytes + (size_t)c->last_offx * 4;      // (not formed into an address when nothing is copied)
         if (const int rc = run_present(c, who, p, &cfg->tone, gain, place.w, place.h, place.w && place.h ? first : out_rgba8, pitch_bytes, &res.tone)) return rc;
         if (ds) if (const int rc = read_despeckle_counts(c, who, &ds_res)) return rc;
+        if (tcfg) if (const int rc = read_temporal_counts(c, who, &ts.res)) return rc;
     }
     HIP_TRY(c, hipDeviceSynchronize());
     if (result) *result = res;
     if (ds_result) *ds_result = ds_res;
+    if (ts_result) *ts_result = ts.res;
     return SRT_OK;
 }
 
@@ -2366,6 +2653,13 @@ int srt_present_despeckled(srt_ctx *c, const srt_present_cfg *present_cfg, const
                            uint32_t image_width, uint32_t image_height, srt_present_result *result, srt_despeckle_result *despeckle_result) {
     if (!despeckle_cfg) return fail(c, SRT_ERR_INVALID, "srt_present_despeckled: null argument");
     return present_chain(c, "srt_present_despeckled", present_cfg, despeckle_cfg, out_rgba8, pitch_bytes, image_width, image_height, result, despeckle_result);
+}
+
+int srt_present_temporal(srt_ctx *c, const srt_present_cfg *present_cfg, const srt_temporal *temporal_cfg, const srt_despeckle *despeckle_cfg, uint8_t *out_rgba8,
+                         size_t pitch_bytes, uint32_t image_width, uint32_t image_height, srt_present_result *result, srt_temporal_result *temporal_result) {
+    if (!temporal_cfg) return fail(c, SRT_ERR_INVALID, "srt_present_temporal: null argument");
+    return present_chain(c, "srt_present_temporal", present_cfg, despeckle_cfg, out_rgba8, pitch_bytes, image_width, image_height, result, nullptr, temporal_cfg,
+                         temporal_result);
 }
 
 int srt_present_kat(srt_ctx *c, const srt_tone *tone, const float *xyz_mean, uint32_t w, uint32_t h, uint8_t *out_rgba8, srt_tone_result *result) {

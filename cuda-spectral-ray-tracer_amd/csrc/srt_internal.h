@@ -406,6 +406,28 @@ struct DespeckleParams {
     unsigned long long *counts;
 };
 hipError_t launch_despeckle(const DespeckleParams &p, hipStream_t st);
+// Temporal reprojection (srt_temporal.hip; stated in srt_c_api.h at srt_temporal_accum) over the row-major w x h rectangle of the chunk at
+// image offset (ox, oy).  Exactly one colour source: xyz (a [h][w][3] XYZ mean) or src4 (the denoiser's float4 colour image); guides: two
+// float4 per pixel, (N, z) and (A, coverage).  du .. center: the current camera; pcenter, pn, pe, pk, pbu, pbv: the previous camera's centre
+// and its constants n', e', k', bu', bv'.  hist_c (one float4 per pixel: XYZ, len) and hist_g (two): the previous call's history, both
+// null for none; new_c / new_g (never the old ones) receive the new one.  kn, ka, kz: the squared thresholds.  Outputs, any may be null:
+// dst4 the float4 image with the source's fourth word (+0 from xyz), out_xyz / out_lin / out_q three floats per pixel, out_len one,
+// out_motion two.  counts[5] (blended, fresh, offscreen, rejected, non-finite) are ADDED to.
+struct TemporalParams {
+    const float *xyz;
+    const float4 *src4, *guides;
+    const float4 *hist_c, *hist_g;
+    float4 *new_c, *new_g;
+    uint32_t w, h, ox, oy;
+    uint32_t tiles_x;      // filled in by the launcher
+    float du[3], dv[3], p00[3], center[3];
+    float pcenter[3], pn[3], pe[3], pk, pbu[3], pbv[3];
+    float kn, ka, kz, alpha_min, max_len;
+    float4 *dst4;
+    float *out_xyz, *out_lin, *out_q, *out_len, *out_motion;
+    unsigned long long *counts;
+};
+hipError_t launch_temporal(const TemporalParams &p, hipStream_t st);
 hipError_t launch_order_tiles(const uint32_t *cost, uint32_t *sorted, uint32_t *rows, uint32_t n, uint32_t n_waves,
                               uint32_t split_load_pct, uint32_t *queue_info, uint32_t order_max_pct, hipStream_t st);
 hipError_t launch_scatter(const ScatterParams &p, hipStream_t st);

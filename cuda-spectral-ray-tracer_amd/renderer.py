@@ -350,6 +350,85 @@ class Renderer:
                     clip=dict(blown=res.tone.blown, crushed=res.tone.crushed, nonfinite=res.tone.nonfinite),
                     despeckle=dict(clamped=dres.clamped, nonfinite=dres.nonfinite, alone=dres.alone))
 
+    def temporal(self, image_width, image_height, **cfg):
+        """temporal reprojection of the context's featured accumulation, on the device (srt_temporal_accum; cfg: the keywords of
+        temporal_config): the picture blended into the history the previous call left, which survives set_camera and accum_reset*:
+        dict(xyz, lin, fb) of (image_height, image_width, 3) float32 arrays -- the blended XYZ mean, its unquantised and its quantised
+        sRGB --, len (image_height, image_width) -- the history length behind every pixel, 1 where it is fresh --, motion
+        (image_height, image_width, 2) -- where the pixel's surface lay in the previous frame minus where it lies now, in pixels, NaN
+        where that is nowhere --, written in the chunk's rectangle only, and stats, the dict of temporal_stats.  Reads the accumulation
+        and advances the history; changes nothing else."""
+        t, res = _temporal_cfg("temporal", cfg), B.TemporalResult()
+        out = [np.zeros((image_height, image_width, 3), np.float32) for _ in range(3)]
+        length, motion = np.zeros((image_height, image_width), np.float32), np.zeros((image_height, image_width, 2), np.float32)
+        self._ck(B.lib().srt_temporal_accum(self._h, C.byref(t), B.fptr(out[0]), B.fptr(out[1]), B.fptr(out[2]), B.fptr(length), B.fptr(motion), C.byref(res),
+                                            image_width, image_height))
+        return dict(xyz=out[0], lin=out[1], fb=out[2], len=length, motion=motion, stats=temporal_stats(res))
+
+    def temporal_kat(self, cur_cam, xyz_mean, guides, prev_cam=None, hist_colour=None, hist_guides=None, offx=0, offy=0, **cfg):
+        """the temporal kernel on explicit inputs (srt_temporal_kat): xyz_mean (h, w, 3), guides (h, w, 8) = (N, z, A, coverage) of the
+        rectangle at image offset (offx, offy) under the camera cur_cam; the history hist_colour (h, w, 4) = (XYZ, len), hist_guides
+        (h, w, 8) written under prev_cam -- all three None: no history.  dict(colour (h, w, 4), guides (h, w, 8) -- the new history --,
+        motion (h, w, 2), stats).  Needs no scene and no accumulation, and leaves the context's own history alone."""
+        t, res = _temporal_cfg("temporal_kat", cfg), B.TemporalResult()
+        img = _xyz_image("temporal_kat", xyz_mean)
+        g = np.ascontiguousarray(guides, np.float32)
+        if g.shape != img.shape[:2] + (8,):
+            raise ValueError("temporal_kat: needs guides %r, got %r" % (img.shape[:2] + (8,), g.shape))
+        given = [v is not None for v in (prev_cam, hist_colour, hist_guides)]
+        if any(given) and not all(given):
+            raise ValueError("temporal_kat: a history is prev_cam, hist_colour and hist_guides together")
+        hc = hg = None
+        if all(given):
+            hc, hg = np.ascontiguousarray(hist_colour, np.float32), np.ascontiguousarray(hist_guides, np.float32)
+            if hc.shape != img.shape[:2] + (4,) or hg.shape != g.shape:
+                raise ValueError("temporal_kat: needs hist_colour %r and hist_guides %r, got %r and %r" % (img.shape[:2] + (4,), g.shape, hc.shape, hg.shape))
+        colour, og, motion = np.zeros(img.shape[:2] + (4,), np.float32), np.zeros(g.shape, np.float32), np.zeros(img.shape[:2] + (2,), np.float32)
+        self._ck(B.lib().srt_temporal_kat(self._h, C.byref(t), C.byref(cur_cam), C.byref(prev_cam) if all(given) else None, B.fptr(img), B.fptr(g),
+                                          B.fptr(hc) if all(given) else None, B.fptr(hg) if all(given) else None, img.shape[1], img.shape[0],
+                                          int(offx), int(offy), B.fptr(colour), B.fptr(og), B.fptr(motion), C.byref(res)))
+        return dict(colour=colour, guides=og, motion=motion, stats=temporal_stats(res))
+
+    def temporal_reset(self):
+        """drop the temporal history: the next temporal call is a first frame (srt_temporal_reset).  upload_scene, init_device_params
+        and set_partition drop it too; set_camera and accum_reset* do not."""
+        self._ck(B.lib().srt_temporal_reset(self._h))
+
+    def temporal_last_ms(self):
+        """kernel-only ms of the context's last temporal kernel (srt_temporal_last_ms)"""
+        ms = C.c_float()
+        self._ck(B.lib().srt_temporal_last_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def denoise_temporal(self, image_width, image_height, temporal=None, despeckle=None, **cfg):
+        """denoise() with the temporal stage between the prepass and level 0 (srt_denoise_features_temporal; temporal: a dict of the
+        keywords of temporal_config, None: the defaults; despeckle: a dict of the keywords of despeckle_config -- the firefly filter
+        runs in front of the stage --, None: no firefly filter; cfg: the keywords of denoise_config): the dict of denoise() plus stats,
+        the dict of temporal_stats.  The history is the stage's output, not the filtered picture, and it is the one temporal() keeps.
+        With no history it equals denoise() / denoise_despeckled()."""
+        c, t, res = denoise_config(**cfg), _temporal_cfg("denoise_temporal", temporal), B.TemporalResult()
+        d = None if despeckle is None else self._despeckle_cfg("denoise_temporal", despeckle)
+        out = [np.zeros((image_height, image_width, 3), np.float32) for _ in range(3)]
+        self._ck(B.lib().srt_denoise_features_temporal(self._h, C.byref(t), None if d is None else C.byref(d), C.byref(c), B.fptr(out[0]), B.fptr(out[1]),
+                                                       B.fptr(out[2]), C.byref(res), image_width, image_height))
+        return dict(xyz=out[0], lin=out[1], fb=out[2], stats=temporal_stats(res))
+
+    def present_temporal(self, image_width, image_height, source="accum", gain=None, temporal=None, despeckle=None, **cfg):
+        """present() with the temporal stage in front (srt_present_temporal; source "accum" or "denoise", on a featured accumulation;
+        temporal and despeckle as denoise_temporal takes them; the other arguments are present_config's): the dict of present() plus
+        temporal, the dict of temporal_stats.  Metering (gain=None) meters the stage's output.  Reads the accumulation and advances
+        the history."""
+        p, res, tres = present_config(source, gain, **cfg), B.PresentResult(), B.TemporalResult()
+        if source not in ("accum", "denoise"):
+            raise ValueError("present_temporal: source must be \"accum\" or \"denoise\", got %r" % (source,))
+        t = _temporal_cfg("present_temporal", temporal)
+        d = None if despeckle is None else self._despeckle_cfg("present_temporal", despeckle)
+        out = np.zeros((image_height, image_width, 4), np.uint8)
+        self._ck(B.lib().srt_present_temporal(self._h, C.byref(p), C.byref(t), None if d is None else C.byref(d), out.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                              4 * image_width, image_width, image_height, C.byref(res), C.byref(tres)))
+        return dict(rgba=out, meter=_meter_dict(res.meter) if gain is None else None,
+                    clip=dict(blown=res.tone.blown, crushed=res.tone.crushed, nonfinite=res.tone.nonfinite), temporal=temporal_stats(tres))
+
     def accum_reset_features(self):
         """start a FEATURED accumulation (srt_c_api.h): like accum_reset, and each later pass also adds, at the first hit of every
         sample's camera ray, the face-forwarded normal, the hit material's colour, the distance and 1 to the pixel's eight raw float32
@@ -1427,6 +1506,91 @@ def _despeckled_passes(scene, cam, width, height, sched, bounce_limit, seed, dev
             r.scatter_tiles()
             cleaned = r.denoise_despeckled(width, height, despeckle, **cfg) if denoise else r.despeckle(width, height, **despeckle)
             yield r.accum_samples, _collect(r, width, height), r.read_features(width, height), cleaned
+
+
+_TEMPORAL_KEYS = ("alpha_min", "max_len", "sigma_normal", "sigma_albedo", "sigma_depth")
+
+
+def temporal_config(alpha_min=0.1, max_len=32, sigma_normal=0.5, sigma_albedo=0.25, sigma_depth=0.1):
+    """srt_temporal from Python numbers, checked as the library checks it (ValueError): alpha_min in (0, 1] in float32, the floor of the
+    blend weight (1 switches the blend off); max_len finite and >= 1, the cap of the history length (the weight of a new frame is
+    1 / len, so 32 frames of history weigh a new one at 1/32 before the floor); every sigma > 0 in float32 and not NaN (inf switches its
+    test off): a history tap is rejected when its normal or albedo differs from the pixel's by more than the sigma (Euclidean), or its
+    stored distance from the expected one by more than sigma_depth relative.  The defaults are starting values, untuned."""
+    vals = []
+    for name, v in zip(_TEMPORAL_KEYS, (alpha_min, max_len, sigma_normal, sigma_albedo, sigma_depth)):
+        vals.append(_expose_number("temporal", name, v))
+    a, m = vals[0], vals[1]
+    if not (a > 0.0 and a <= 1.0):
+        raise ValueError("temporal: alpha_min must be in (0, 1] in float32, got %r" % (alpha_min,))
+    if not (m >= 1.0 and np.isfinite(m)):
+        raise ValueError("temporal: max_len must be finite and >= 1 in float32, got %r" % (max_len,))
+    for name, f, v in zip(_TEMPORAL_KEYS[2:], vals[2:], (sigma_normal, sigma_albedo, sigma_depth)):
+        if not f > 0.0:
+            raise ValueError("temporal: %s must be > 0 in float32 (inf switches the test off), got %r" % (name, v))
+    return B.Temporal(a, m, vals[2], vals[3], vals[4], (C.c_uint32 * 3)(0, 0, 0))
+
+
+def _temporal_cfg(who, temporal):
+    """srt_temporal from a dict of the keywords of temporal_config (None: the defaults); TypeError for a name that is none of them"""
+    kw = dict(temporal or {})
+    unknown = sorted(set(kw) - set(_TEMPORAL_KEYS))
+    if unknown:
+        raise TypeError("%s: unknown temporal keyword(s) %s (%s)" % (who, ", ".join(unknown), ", ".join(_TEMPORAL_KEYS)))
+    return temporal_config(**kw)
+
+
+def temporal_stats(res):
+    """srt_temporal_result as a dict: the pixels blended, fresh (of those: offscreen, rejected) and nonfinite, history_frames (the calls
+    since the history began, this one included) and history_dropped (this call discarded a history of another rectangle)"""
+    return dict(blended=res.blended, fresh=res.fresh, offscreen=res.offscreen, rejected=res.rejected, nonfinite=res.nonfinite,
+                history_frames=res.history_frames, history_dropped=bool(res.history_dropped))
+
+
+def render_interactive(scene, cameras, width, height, spp, bounce_limit, denoise=True, despeckle=None, temporal=None, seed=1984, device=0, renderer=None,
+                       **cfg):
+    """A moving camera on one GPU: for every camera of `cameras` (CameraData, at least one) set_camera, accum_reset_features, one pass of
+    `spp` samples, then the chained call that carries the picture over from the previous camera -- denoise=True:
+    Renderer.denoise_temporal(width, height, temporal, despeckle, **cfg) (cfg: the keywords of denoise_config), else
+    Renderer.temporal(width, height, **temporal) (no cfg, no despeckle).  A generator of (index, result, features, picture, stats):
+    `result` with the keys of render_image, `features` the raw sums of read_features, `picture` the chained call's dict, `stats` its
+    temporal_stats.  The history starts with the first camera (temporal_reset).  Everything is checked here, before any device is
+    touched."""
+    cams = list(cameras)
+    if not cams:
+        raise ValueError("render_interactive: no camera (give at least one)")
+    for k, cam in enumerate(cams):
+        if not isinstance(cam, B.CameraData):
+            raise TypeError("render_interactive: cameras[%d] is no CameraData (camera_init makes one), got %r" % (k, type(cam).__name__))
+    sched = progressive_schedule([spp])
+    tkw = dict(temporal or {})
+    _temporal_cfg("render_interactive", tkw)
+    dkw = None
+    if despeckle is not None:
+        dkw = dict(despeckle)
+        unknown = sorted(set(dkw) - set(_DESPECKLE_KEYS))
+        if unknown:
+            raise TypeError("render_interactive: unknown despeckle keyword(s) %s (%s)" % (", ".join(unknown), ", ".join(_DESPECKLE_KEYS)))
+        despeckle_config(**dkw)
+    if denoise:
+        denoise_config(**cfg)
+    elif cfg:
+        raise TypeError("render_interactive: %s given with denoise=False, which runs no denoiser" % ", ".join(sorted(cfg)))
+    elif dkw is not None:
+        raise ValueError("render_interactive: despeckle given with denoise=False: the firefly filter runs in the denoiser's chain")
+    return _interactive_frames(scene, cams, width, height, sched[0], bounce_limit, seed, device, renderer, bool(denoise), dkw, tkw, cfg)
+
+
+def _interactive_frames(scene, cams, width, height, spp, bounce_limit, seed, device, renderer, denoise, despeckle, temporal, cfg):
+    with _image_session(scene, cams[0], width, height, spp, bounce_limit, seed, device, renderer) as r:
+        r.temporal_reset()
+        for k, cam in enumerate(cams):
+            r.set_camera(cam)
+            r.accum_reset_features()
+            r.render_chunk_accum(width, height, spp)
+            r.scatter_tiles()
+            picture = r.denoise_temporal(width, height, temporal, despeckle, **cfg) if denoise else r.temporal(width, height, **temporal)
+            yield k, _collect(r, width, height), r.read_features(width, height), picture, picture["stats"]
 
 
 MAX_DENOISE_LEVELS = 8

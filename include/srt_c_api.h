@@ -837,6 +837,115 @@ SRT_API int srt_present_despeckled(srt_ctx *ctx, const srt_present_cfg *present_
                                    size_t pitch_bytes, uint32_t image_width, uint32_t image_height, srt_present_result *result,
                                    srt_despeckle_result *despeckle_result);
 
+/* Temporal reprojection (no reference counterpart; kernel in csrc/srt_temporal.hip): the picture carried across camera moves.
+ * srt_set_camera invalidates the accumulation, so a moved camera starts its picture from nothing although nearly every surface it sees was
+ * seen a frame ago.  This stage finds, for every pixel, where its surface lay in the previous frame -- from the first-hit guides and the
+ * two cameras, which are plain data -- gathers the previous output there, and blends the new frame into it with a weight that falls as the
+ * history grows: the temporal half of an SVGF-style filter (Schied et al. 2017, section 4.1), next to the spatial and variance-guided
+ * halves above.  The motion vectors fall out of the same arithmetic.  The geometry is static; lens and jitter are ignored (the centre ray).
+ * Operation by operation -- everything fp32, not contracted, evaluated left to right, with only + - * /, sqrtf, floorf, float <-> int
+ * conversion, compares and selects; the restatement is tests/temporal_reference.py, which the device equals in every bit and every counter:
+ *   A dot product is  a.b = (a.x * b.x + a.y * b.y) + a.z * b.z;  a cross product is
+ *     a x b = (a.y * b.z - a.z * b.y,  a.z * b.x - a.x * b.z,  a.x * b.y - a.y * b.x);  a vector operation is done per component.
+ *   Inputs, for the w x h rectangle of the chunk at image offset (ox, oy): the current picture c_p (an XYZ mean), its guides
+ *     g0_p = (N, z) and g1_p = (A, cov) as srt_denoise_features' prepass defines them (on an adaptive kind with the pixel's own count), the
+ *     current camera C (du = pixel_delta_u, dv = pixel_delta_v, p00 = pixel00_loc, center = camera_center), and the HISTORY: three float4
+ *     images of the same rectangle written by the previous call -- Hc = (XYZ, len), Hg0, Hg1 (that call's guides) -- and the camera C'
+ *     that was current then.
+ *   cfg is srt_temporal { float alpha_min, max_len, sigma_normal, sigma_albedo, sigma_depth; uint32_t reserved[3]; }.
+ *   Host constants, fp32:  kn = sigma_normal * sigma_normal;  ka = sigma_albedo * sigma_albedo;  kz = sigma_depth * sigma_depth  (+inf
+ *     stays +inf and switches its test off);  and of the previous camera C':
+ *       n' = du' x dv';   e' = p00' - center';   k' = e'.n';
+ *       cu = dv' x n';    bu' = cu / (du'.cu);       cv = n' x du';    bv' = cv / (dv'.cv)
+ *     (the reciprocal basis of (du', dv') in the image plane: bu'.du' = 1, bu'.dv' = 0 and so on, also for a non-orthogonal camera).
+ *   Per pixel p = (x, y):
+ *     1. Class:  hit_p = cov_p >= 0.5f.
+ *     2. Centre ray of C, as the render kernel forms pixel_center, without jitter and lens:
+ *          fi = (float)(ox + x);  fj = (float)(oy + y);  pc = (p00 + fi * du) + fj * dv;  d = pc - center.
+ *     3. Point or direction.  hit_p:  L = sqrtf(d.d);  s = z_p / L;  P = center + s * d;  v = P - center';  zexp = sqrtf(v.v).
+ *          Otherwise (sky):  v = d.
+ *     4. Projection into C':  den = v.n';  t = k' / den.  If (t > 0) is false there is no history for p (behind the camera, a parallel ray, or
+ *          NaN), and its motion vector is (NaN, NaN).  Otherwise  q = t * v - e';  u = q.bu' - (float)ox;  w = q.bv' - (float)oy,  and the
+ *          motion vector is (u - (float)x, w - (float)y).
+ *     5. Bilinear gather:  x0 = floorf(u);  y0 = floorf(w);  fx = u - x0;  fy = w - y0.  The taps are (x0 + a, y0 + b) in the order
+ *          (a, b) = (0, 0), (1, 0), (0, 1), (1, 1), with  wt = (a ? fx : 1.0f - fx) * (b ? fy : 1.0f - fy).  A tap q = (tx, ty) is INSIDE when
+ *          tx >= 0 && tx < (float)w && ty >= 0 && ty < (float)h, tested in float: a huge or NaN coordinate is never converted, and no tap
+ *          outside is read.  A tap inside is ACCEPTED when  Hc_q.len > 0,  the three colour components of Hc_q are finite ((v - v) == 0),
+ *          and (Hg1_q.cov >= 0.5f) == hit_p;  for a hit pixel also
+ *            (N_p.x - N_q.x)^2 + (N_p.y - N_q.y)^2 + (N_p.z - N_q.z)^2 <= kn  (N_q of Hg0_q),   the same on A (of Hg1_q) <= ka,   and
+ *            m = zexp > z_q ? zexp : z_q;   r = m > 0 ? (zexp - z_q) / m : 0;   r * r <= kz      (z_q of Hg0_q).
+ *          An accepted tap with wt > 0:  sw += wt;  sc += wt * Hc_q.xyz;  sl += wt * Hc_q.len.
+ *     6. Result classes, the tests in this order:
+ *          nonfinite: (v - v) == 0 is false for a component v of c_p  ->  o = c_p, len' = 0.  The pixel is shown as it is and leaves no history.
+ *          fresh:     there is no history at all, step 4 failed, or (sw > 0) is false  ->  o = c_p, len' = 1.
+ *          blended:   h = sc / sw;  lh = sl / sw;  len' = lh + 1.0f;  len' = len' < max_len ? len' : max_len;  a = 1.0f / len';
+ *                     a = a > alpha_min ? a : alpha_min;   a >= 1 ? o = c_p (its bits) : o = h + a * (c_p - h).
+ *     7. New history:  Hc = (o, len'), Hg0 = g0_p, Hg1 = g1_p, camera = C.  The history is double-buffered -- a call reads the old one while
+ *          it writes the new --, costs 96 bytes per pixel of the rectangle and belongs to the context.
+ *   Counters (integers, added with atomics after a wave-level reduction, as the tone kernel counts): blended, fresh and nonfinite are the
+ *     classes; a fresh pixel is also counted as offscreen (step 4 failed or all four taps are outside) or else as rejected -- unless
+ *     there is no history at all, when it is neither.  With no history at all steps 2 - 5 are not run and every motion vector is NaN.
+ *   What follows: the first call after a reset returns the input picture bit for bit, with len = 1 (0 at a non-finite pixel);
+ *   alpha_min = 1 returns the input picture bit for bit, whatever the history; a constant picture under any camera move stays that constant
+ *   exactly where it blends (c - h = 0: h is a weighted mean of equal values only up to rounding, so this needs sc / sw to be that
+ *   constant: it is for one tap, and for a constant with few mantissa bits); a non-finite value never enters the history (the nonfinite
+ *   class stores len' = 0, which no later gather accepts; barring overflow in the sums) and never leaves it (a tap with non-finite colour
+ *   is not accepted).
+ *   cfg, validated by every entry point that takes one, else SRT_ERR_INVALID: 0 < alpha_min <= 1; max_len >= 1 and finite; every sigma > 0
+ *     and not NaN (+inf allowed); the reserved words 0.
+ *   srt_temporal_reset      drops the context's history: the next call is a first frame.  srt_upload_scene, srt_init_device_params and
+ *                           srt_set_partition drop it too; srt_set_camera and every srt_accum_reset* do NOT -- surviving them is the point.
+ *   srt_temporal_accum      the stage on the bound FEATURED accumulation of any kind the denoisers accept (plain, adaptive, spectral,
+ *                           adaptive spectral): srt_denoise_features' prepass forms c and the guides, C is the context's camera.  out_xyz
+ *                           is o, out_lin / out_q are xyz_mean_to_srgb(o) (three floats per pixel each), out_len[h][w] is len',
+ *                           out_motion[h][w][2] the motion vector; *result the counters.  Any output may be NULL, but not all five
+ *                           together with result.  Placement, clipping and synchronisation are srt_despeckle_accum's.  It reads the
+ *                           accumulation and ADVANCES THE HISTORY: frame, sums, rows, sample map and RNG state are untouched.  A history
+ *                           of another rectangle (w, h, ox, oy) is discarded -- history_dropped = 1 -- and the call is a first frame.
+ *                           Refusals are srt_denoise_features' (SRT_ERR_UNSUPPORTED under a partition other than (0, 1)) plus a bad cfg;
+ *                           a refused call leaves the history alone.
+ *   srt_temporal_kat        the same kernel on a caller's row-major host arrays: xyz_mean[h][w][3], guides[h][w][8] = (N, z, A, cov),
+ *                           hist_colour[h][w][4] = Hc, hist_guides[h][w][8] = (Hg0, Hg1), the rectangle's offset (ox, oy), both cameras.
+ *                           prev_cam == NULL or hist_colour == NULL or hist_guides == NULL: no history.  out_colour[h][w][4] the new Hc,
+ *                           out_guides[h][w][8] the new guides, out_motion[h][w][2]; any may be NULL, not all three together with result.
+ *                           It touches neither the context's history nor any accumulation.  SRT_ERR_INVALID for a null ctx / cfg /
+ *                           cur_cam / xyz_mean / guides, a bad cfg, an empty image, w x h >= 2^31, or ox + w or oy + h above 2^24 (where
+ *                           fi and fj stop being exact).  history_frames is 1 without a history and 2 with one.
+ *   srt_denoise_features_temporal  srt_denoise_features -- with despeckle_cfg not NULL: srt_denoise_features_ds -- with the stage between
+ *                           the prepass (and the despeckle) and level 0, on the denoiser's own images.  The history is the stage's output,
+ *                           not the filtered picture, and it is the history srt_temporal_accum keeps: the two calls may alternate.  With
+ *                           no history it equals srt_denoise_features / _ds bit for bit.  Refusals are theirs plus a bad srt_temporal.
+ *   srt_present_temporal    srt_present with the stage (behind the despeckle when despeckle_cfg is not NULL) in front, structured as
+ *                           srt_present_despeckled is: SRT_PRESENT_ACCUM presents -- and, when metering, meters -- the stage's output,
+ *                           which lies on the device as [h][w][3]; SRT_PRESENT_DENOISE runs the chain of srt_denoise_features_temporal.
+ *                           Other sources and every partition other than (0, 1) are SRT_ERR_UNSUPPORTED; the other refusals are
+ *                           srt_present's plus a null or bad srt_temporal, a bad srt_despeckle, and an accumulation that is not featured.
+ *   srt_temporal_last_ms    kernel-only time in ms, from HIP events, of the context's last temporal kernel; SRT_ERR_INVALID before one ran.
+ *                           srt_denoise_last_ms reports the chained call's prepass, levels and epilogue as before; srt_temporal_accum
+ *                           records no denoise event, so after it srt_denoise_last_ms still reports the context's last denoise.
+ * history_frames is the number of calls since the history began, this one included.  Working blocks (64 bytes of counters, the 96 bytes per
+ * pixel of the history, 48 more for the outputs, and the denoiser's images) belong to the context and are reused. */
+typedef struct srt_temporal { float alpha_min, max_len, sigma_normal, sigma_albedo, sigma_depth; uint32_t reserved[3]; } srt_temporal;
+typedef struct srt_temporal_result {
+    uint64_t blended, fresh, offscreen, rejected, nonfinite;
+    uint32_t history_frames;       /* calls since the history began, this one included */
+    uint32_t history_dropped;      /* 1: this call found a history of another rectangle and discarded it */
+} srt_temporal_result;
+SRT_API int srt_temporal_reset(srt_ctx *ctx);
+SRT_API int srt_temporal_accum(srt_ctx *ctx, const srt_temporal *cfg, float *out_xyz, float *out_lin, float *out_q, float *out_len,
+                               float *out_motion, srt_temporal_result *result, uint32_t image_width, uint32_t image_height);
+SRT_API int srt_temporal_kat(srt_ctx *ctx, const srt_temporal *cfg, const srt_camera_data *cur_cam, const srt_camera_data *prev_cam,
+                             const float *xyz_mean, const float *guides, const float *hist_colour, const float *hist_guides,
+                             uint32_t w, uint32_t h, uint32_t ox, uint32_t oy, float *out_colour, float *out_guides, float *out_motion,
+                             srt_temporal_result *result);
+SRT_API int srt_denoise_features_temporal(srt_ctx *ctx, const srt_temporal *temporal_cfg, const srt_despeckle *despeckle_cfg,
+                                          const srt_denoise *denoise_cfg, float *out_xyz, float *out_lin, float *out_q,
+                                          srt_temporal_result *temporal_result, uint32_t image_width, uint32_t image_height);
+SRT_API int srt_present_temporal(srt_ctx *ctx, const srt_present_cfg *present_cfg, const srt_temporal *temporal_cfg,
+                                 const srt_despeckle *despeckle_cfg, uint8_t *out_rgba8, size_t pitch_bytes, uint32_t image_width,
+                                 uint32_t image_height, srt_present_result *result, srt_temporal_result *temporal_result);
+SRT_API int srt_temporal_last_ms(srt_ctx *ctx, float *ms);
+
 /* Sample-parallel pixels (no reference counterpart; a deliberate departure from its one RNG stream per pixel, so opt-in).  A STREAMED
  * accumulation gives every pixel K independent RNG streams, each with its own state and its own XYZ sum, so that any lane of any wave
  * can render a stream while others render the pixel's other streams: the longest sequential chain of a pass is spp_add / K samples.
