@@ -127,6 +127,11 @@ struct srt_ctx {
     bool count_traversal = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
+    // The order of the context's calls (srt_c_api.h, "Order of a context's calls"; set_device, device_synchronize below): the stream of the
+    // work enqueued last, remembered until the context next waits for the device, and the event that carries the order over to another stream
+    hipStream_t order_stream = nullptr;
+    bool order_pending = false;                         // order_stream is remembered: work since the last device-wide wait may be in flight on it
+    hipEvent_t order_ev = nullptr;                      // (created on first use)
     DeviceBuffer d_rowmajor;                            // row-major staging image of srt_read_fb_rowmajor (3 planes), zeroed when its size changes
     uint32_t rowmajor_w = 0, rowmajor_h = 0;
     OrderProfile order_profile = {};                    // non-zero magic: the next instrumented launch collects the child-order profile
@@ -230,6 +235,31 @@ int hip_fail(srt_ctx *ctx, hipError_t e, const char *what) {
 }
 #define HIP_TRY_AS(ctx, what, expr) do { if (hipError_t _e = (expr)) return hip_fail(ctx, _e, what); } while (0)
 #define HIP_TRY(ctx, expr) HIP_TRY_AS(ctx, #expr, expr)
+
+// ---- the order of a context's calls (srt_c_api.h): they take effect in the order they were made, whichever streams they name --------
+// Passes, srt_copy_tile_buffer and srt_scatter_tiles run on the caller's stream, everything else on the null stream, and a blocking
+// copy orders against the null stream only -- which serialises with the caller's blocking streams, not with a hipStreamNonBlocking one.
+// So every entry point that enqueues selects the device through set_device(c, its stream): when the context's last work went to ANOTHER
+// stream and may still be in flight, the new stream first waits for an event recorded behind that work.  A caller that stays on one
+// stream never gets here: no HIP call is added.  The remembered stream is not touched again after the context's next device-wide wait
+// (device_synchronize), so the caller may destroy it then.
+hipError_t set_device(srt_ctx *c, hipStream_t st = nullptr) {
+    if (const hipError_t e = hipSetDevice(c->device)) return e;
+    if (c->order_pending && c->order_stream != st) {
+        if (!c->order_ev)
+            if (const hipError_t e = hipEventCreateWithFlags(&c->order_ev, hipEventDisableTiming)) return e;
+        if (const hipError_t e = hipEventRecord(c->order_ev, c->order_stream)) return e;
+        if (const hipError_t e = hipStreamWaitEvent(st, c->order_ev, 0)) return e;
+    }
+    c->order_stream = st; c->order_pending = true;
+    return hipSuccess;
+}
+// every device-wide wait of a context: nothing of it is in flight afterwards, on any stream
+hipError_t device_synchronize(srt_ctx *c) {
+    const hipError_t e = hipDeviceSynchronize();
+    c->order_stream = nullptr; c->order_pending = false;
+    return e;
+}
 
 int upload(srt_ctx *ctx, DeviceBuffer &dst, const std::vector<float> &src) {
     HIP_TRY(ctx, dst.reserve(src.size() * sizeof(float)));
@@ -576,7 +606,7 @@ int read_planes(srt_ctx *c, int first_plane, float *p0, float *p1, float *p2) {
 // Three block-linear planes of n_lanes words (bits copied as they are) -> the last chunk's rectangle of three row-major host images.
 // A null host plane is not copied (its source plane may be any valid one).
 int read_rowmajor(srt_ctx *c, const float *const src[3], float *const host[3], uint32_t image_width, uint32_t image_height) {
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     const size_t n = (size_t)image_width * image_height;
     // context-owned row-major staging image: the un-swizzle writes the chunk's pixels into it on the device and only the
     // chunk's rectangle travels to the caller's planes (update_fb touches nothing else either, render_manager.cuh:68-142)
@@ -591,7 +621,7 @@ int read_rowmajor(srt_ctx *c, const float *const src[3], float *const host[3], u
     const size_t pitch = (size_t)image_width * sizeof(float);
     for (int k = 0; k < 3 && rect.w && rect.h; k++)
         if (host[k]) HIP_TRY(c, hipMemcpy2D(host[k] + rect.first, pitch, dst[k] + rect.first, pitch, (size_t)rect.w * sizeof(float), rect.h, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, device_synchronize(c));
     return SRT_OK;
 }
 
@@ -649,6 +679,7 @@ void srt_destroy(srt_ctx *c) {
     (void)hipDeviceSynchronize();
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
+    if (c->order_ev) (void)hipEventDestroy(c->order_ev);
     for (hipEvent_t e : c->denoise_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->develop_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->expose_ev) if (e) (void)hipEventDestroy(e);
@@ -668,7 +699,7 @@ int srt_upload_scene(srt_ctx *c, const srt_scene *s) {
     c->accum.invalidate();
     c->temporal_frames = 0;      // (the temporal history shows another scene)
     c->sched_probe_queue = false; c->sched_compacted_queue = false;      // (the queues of the last launch belong to the old set-up)
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     FlatScene f;
     int rc = flatten_scene(*s, f);
     if (rc != SRT_OK) return fail(c, rc, global_error());
@@ -774,7 +805,7 @@ int srt_internal_init_device_params(srt_ctx *c, uint32_t tx, uint32_t ty, uint32
     c->sched_probe_queue = false; c->sched_compacted_queue = false;      // (the queues of the last launch belong to the old set-up)
     const uint64_t lanes = (uint64_t)tx * ty * bx * by;
     if (lanes > 0x7fffffffull) return fail(c, SRT_ERR_INVALID, "srt_init_device_params: grid too large");
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     c->tx = tx; c->ty = ty; c->bx = bx; c->by = by; c->chunk_w = chunk_w; c->chunk_h = chunk_h;
     c->spp = (uint16_t)spp; c->bounce = (uint16_t)bounce_limit;     // short_uint, rendering.cu:154 (Q17)
     c->seed = seed; c->n_lanes = (uint32_t)lanes;
@@ -784,7 +815,7 @@ int srt_internal_init_device_params(srt_ctx *c, uint32_t tx, uint32_t ty, uint32
     HIP_TRY(c, c->d_fb.reserve(kTilePlanes * lanes * sizeof(float)));
     HIP_TRY(c, hipMemset(c->d_fb.ptr, 0, kTilePlanes * lanes * sizeof(float)));
     HIP_TRY(c, launch_init_rng(c->d_rng.as<uint32_t>(), c->n_lanes, seed, nullptr));   // init_random_states, rendering.cu:330
-    if (wait) HIP_TRY(c, hipDeviceSynchronize());
+    if (wait) HIP_TRY(c, device_synchronize(c));
     c->fb_groups_valid = (uint32_t)kTileGroups;      // all nine planes are zero
     c->params_ready = true;
     return SRT_OK;
@@ -820,7 +851,7 @@ int srt_render_chunk(srt_ctx *c, uint32_t width, uint32_t height, uint32_t offx,
     if (!c->scene_ready || !c->camera_ready || !c->params_ready)
         return fail(c, SRT_ERR_INVALID, "srt_render_chunk: scene, camera and device parameters must be set first");
     c->accum.invalidate();      // its launch moves the RNG streams (and may rewrite the pixel queue) behind the sums
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c, (hipStream_t)stream));
     width = (uint16_t)width; height = (uint16_t)height; offx = (uint16_t)offx; offy = (uint16_t)offy;   // rendering.cu:245 (Q17)
     return render_chunk_impl(c, width, height, offx, offy, 0u, (hipStream_t)stream);
 }
@@ -828,12 +859,12 @@ int srt_render_chunk(srt_ctx *c, uint32_t width, uint32_t height, uint32_t offx,
 int srt_accum_reset(srt_ctx *c) {
     if (!c) return fail(c, SRT_ERR_INVALID, "srt_accum_reset: null ctx");
     if (!c->params_ready) return fail(c, SRT_ERR_INVALID, "srt_accum_reset: device parameters must be set first (srt_init_device_params)");
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     c->accum.invalidate();
     HIP_TRY(c, c->d_accum.reserve(AccumLayout::bytes(c->n_lanes)));
     // (null stream, then a wait: a pass on any stream of the caller's finds the sums zeroed)
     HIP_TRY(c, hipMemset(AccumLayout(c).sums, 0, AccumLayout::sums_bytes(c->n_lanes)));
-    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, device_synchronize(c));
     c->accum.total = 0;
     c->accum.begin(srt_ctx::Accumulation::Kind::Plain);
     return SRT_OK;
@@ -845,7 +876,7 @@ int srt_accum_reset_spectral(srt_ctx *c) {
     if (c->count_traversal)
         return fail(c, SRT_ERR_UNSUPPORTED, "srt_accum_reset_spectral: no instrumented accumulating kernel (srt_set_count_traversal(ctx, 0) first)");
     if (!c->params_ready) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_spectral: device parameters must be set first (srt_init_device_params)");
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     const size_t film_bytes = (size_t)c->n_lanes * kFilmStride * sizeof(float);
     if (c->d_film.bytes < film_bytes) {
         // (the new film is allocated before the old one goes: a failed allocation changes nothing)
@@ -860,7 +891,7 @@ int srt_accum_reset_spectral(srt_ctx *c) {
     // the film's slot of the header (the per-pass kernel rewrites only sums and spp_total)
     float *film = c->d_film.as<float>();
     HIP_TRY(c, hipMemcpy(&AccumLayout(c).header->film, &film, sizeof(film), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, device_synchronize(c));
     c->accum.begin(srt_ctx::Accumulation::Kind::Spectral);
     return SRT_OK;
 }
@@ -871,7 +902,7 @@ int srt_accum_reset_features(srt_ctx *c) {
     if (c->count_traversal)
         return fail(c, SRT_ERR_UNSUPPORTED, "srt_accum_reset_features: no instrumented accumulating kernel (srt_set_count_traversal(ctx, 0) first)");
     if (!c->params_ready) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_features: device parameters must be set first (srt_init_device_params)");
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     const size_t bytes = (size_t)c->n_lanes * kFeatureStride * sizeof(float);
     if (c->d_features.bytes < bytes) {
         // (the new rows are allocated before the old ones go: a failed allocation changes nothing)
@@ -888,7 +919,7 @@ int srt_accum_reset_features(srt_ctx *c) {
     h.features = c->d_features.as<float>(); h.mat_col = c->d_mat_col.as<const float>();
     const size_t tail = offsetof(AccumHeader, features);
     HIP_TRY(c, hipMemcpy(&AccumLayout(c).header->features, reinterpret_cast<const char *>(&h) + tail, sizeof(h) - tail, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, device_synchronize(c));
     c->accum.begin(srt_ctx::Accumulation::Kind::Features);
     return SRT_OK;
 }
@@ -899,7 +930,7 @@ int srt_accum_reset_spectral_features(srt_ctx *c) {
     if (c->count_traversal)
         return fail(c, SRT_ERR_UNSUPPORTED, "srt_accum_reset_spectral_features: no instrumented accumulating kernel (srt_set_count_traversal(ctx, 0) first)");
     if (!c->params_ready) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_spectral_features: device parameters must be set first (srt_init_device_params)");
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     // srt_accum_reset_spectral's rule for the film and srt_accum_reset_features' rule for the rows.  Both new blocks are allocated before
     // either old one goes: a failed allocation changes nothing, and leaves no error behind for the next launch's hipGetLastError
     const char *who = "srt_accum_reset_spectral_features";
@@ -923,7 +954,7 @@ int srt_accum_reset_spectral_features(srt_ctx *c) {
     h.features = c->d_features.as<float>(); h.mat_col = c->d_mat_col.as<const float>();
     const size_t tail = offsetof(AccumHeader, features);
     HIP_TRY(c, hipMemcpy(&AccumLayout(c).header->features, reinterpret_cast<const char *>(&h) + tail, sizeof(h) - tail, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, device_synchronize(c));
     c->accum.begin(srt_ctx::Accumulation::Kind::SpectralFeatures);
     return SRT_OK;
 }
@@ -937,7 +968,7 @@ int srt_accum_reset_streams(srt_ctx *c, uint32_t streams) {
     if (!c->params_ready) return fail(c, SRT_ERR_INVALID, "srt_accum_reset_streams: device parameters must be set first (srt_init_device_params)");
     if ((uint64_t)streams * c->n_lanes > 0x7fffffffull)
         return fail(c, SRT_ERR_INVALID, "srt_accum_reset_streams: streams x lanes of the grid must stay below 2^31 (the stream planes have 32-bit indices)");
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     const size_t bytes = StreamPlanes::bytes(c->n_lanes, streams);
     const bool seeded = c->streams_seeded == streams && c->d_streams.bytes >= bytes;
     if (c->d_streams.bytes < bytes) {
@@ -964,7 +995,7 @@ int srt_accum_reset_streams(srt_ctx *c, uint32_t streams) {
     h.stream_planes = sp.rng; h.streams = streams;
     const size_t tail = offsetof(AccumHeader, stream_planes);
     HIP_TRY(c, hipMemcpy(&AccumLayout(c).header->stream_planes, reinterpret_cast<const char *>(&h) + tail, sizeof(h) - tail, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, device_synchronize(c));
     c->streams_seeded = streams;
     c->accum.begin(srt_ctx::Accumulation::Kind::Streams, streams);
     return SRT_OK;
@@ -1026,7 +1057,7 @@ static int accum_reset_adaptive(srt_ctx *c, const srt_adaptive *cfg, bool featur
     if (features) { h.features = rows; h.mat_col = c->d_mat_col.as<const float>(); }
     const size_t tail = offsetof(AccumHeader, sum2);
     HIP_TRY(c, hipMemcpy(&AccumLayout(c).header->sum2, reinterpret_cast<const char *>(&h) + tail, sizeof(h) - tail, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, device_synchronize(c));
     using Kind = srt_ctx::Accumulation::Kind;
     c->accum.begin(spectral ? (features ? Kind::AdaptiveSpectralFeatures : Kind::AdaptiveSpectral) : features ? Kind::AdaptiveFeatures : Kind::Adaptive);
     return SRT_OK;
@@ -1088,7 +1119,7 @@ int srt_render_chunk_accum(srt_ctx *c, uint32_t width, uint32_t height, uint32_t
     width = (uint16_t)width; height = (uint16_t)height; offx = (uint16_t)offx; offy = (uint16_t)offy;   // rendering.cu:245 (Q17)
     if (c->accum.bound() && (width != c->accum.w || height != c->accum.h || offx != c->accum.offx || offy != c->accum.offy))
         return fail(c, SRT_ERR_INVALID, "srt_render_chunk_accum: the accumulation belongs to another chunk (one accumulation per context)");
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c, (hipStream_t)stream));
     hipStream_t st = (hipStream_t)stream;
     // (the header travels by value in the arguments of a one-lane kernel on the pass's stream: stream-ordered, no host buffer to keep alive)
     HIP_TRY(c, launch_accum_header(AccumLayout(c).header, AccumLayout(c).sums, c->accum.total + spp_add, st));
@@ -1103,7 +1134,7 @@ int srt_render_chunk_accum(srt_ctx *c, uint32_t width, uint32_t height, uint32_t
 int srt_synchronize(srt_ctx *c) {
     if (!c) return fail(c, SRT_ERR_INVALID, "srt_synchronize: null ctx");
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, device_synchronize(c));
     return SRT_OK;
 }
 
@@ -1118,7 +1149,7 @@ int srt_tile_buffer(srt_ctx *c, void **dev_ptr, size_t *n_floats, uint32_t *tile
 
 int srt_copy_tile_buffer(srt_ctx *c, void *dst_dev, void *stream) {
     if (!c || !c->d_tiles || !dst_dev) return fail(c, SRT_ERR_INVALID, "srt_copy_tile_buffer: nothing rendered yet / null destination");
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c, (hipStream_t)stream));
     HIP_TRY(c, hipMemcpyAsync(dst_dev, c->d_tiles.ptr, (size_t)c->tiles_padded * c->gather_planes * kTileLanes * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return SRT_OK;
 }
@@ -1130,7 +1161,7 @@ int srt_scatter_tiles(srt_ctx *c, const void *dev_gathered, void *stream) {
         if (c->world != 1) return fail(c, SRT_ERR_INVALID, "srt_scatter_tiles: a gathered buffer is required when world > 1");
         dev_gathered = c->d_tiles.ptr;      // the context's own tile buffer: group 0, and the parity groups when they were asked for
     }
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c, (hipStream_t)stream));
     ScatterParams sp = {};
     sp.gathered = (const float *)dev_gathered;
     sp.groups = groups;
@@ -1195,7 +1226,7 @@ int srt_read_spectral(srt_ctx *c, uint32_t first, uint32_t count, float *out, ui
         return fail(c, SRT_ERR_INVALID, "srt_read_spectral: the range [first, first + count) must be a non-empty part of the 95 grid samples");
     if (!c->accum.spectral() || !c->accum.bound())
         return fail(c, SRT_ERR_INVALID, "srt_read_spectral: no spectral accumulation with a pass (srt_accum_reset_spectral and srt_render_chunk_accum first)");
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     // the chunk's rectangle, clipped to the reference grid and the image (srt_read_fb_rowmajor's placement): un-swizzled on the device
     // into a [h][w][count] staging block, then one 2-D copy into the caller's [image_height][image_width][count] array
     const ChunkRect rect = chunk_rect(c, image_width, image_height);
@@ -1205,7 +1236,7 @@ int srt_read_spectral(srt_ctx *c, uint32_t first, uint32_t count, float *out, ui
         const size_t row = (size_t)rect.w * count * sizeof(float), pitch = (size_t)image_width * count * sizeof(float);
         HIP_TRY(c, hipMemcpy2D(out + rect.first * count, pitch, c->d_film_staging.ptr, row, row, rect.h, hipMemcpyDeviceToHost));
     }
-    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, device_synchronize(c));
     return SRT_OK;
 }
 
@@ -1213,7 +1244,7 @@ int srt_read_features(srt_ctx *c, float *out, uint32_t image_width, uint32_t ima
     if (!c || !out || image_width == 0 || image_height == 0) return fail(c, SRT_ERR_INVALID, "srt_read_features: bad argument");
     if (!c->accum.featured() || !c->accum.bound())
         return fail(c, SRT_ERR_INVALID, "srt_read_features: no featured accumulation with a pass (srt_accum_reset_features and srt_render_chunk_accum first)");
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     // the chunk's rectangle, clipped to the reference grid and the image (srt_read_fb_rowmajor's placement): un-swizzled on the device
     // into a [h][w][8] staging block, then one 2-D copy into the caller's [image_height][image_width][8] array
     const ChunkRect rect = chunk_rect(c, image_width, image_height);
@@ -1223,7 +1254,7 @@ int srt_read_features(srt_ctx *c, float *out, uint32_t image_width, uint32_t ima
         const size_t row = (size_t)rect.w * kFeatureStride * sizeof(float), pitch = (size_t)image_width * kFeatureStride * sizeof(float);
         HIP_TRY(c, hipMemcpy2D(out + rect.first * kFeatureStride, pitch, c->d_features_staging.ptr, row, row, rect.h, hipMemcpyDeviceToHost));
     }
-    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, device_synchronize(c));
     return SRT_OK;
 }
 
@@ -1305,7 +1336,7 @@ int develop_accumulation(srt_ctx *c, const char *who, const float *response, uin
                          uint32_t image_width, uint32_t image_height) {
     if (!c->accum.spectral() || !c->accum.bound())
         return fail(c, SRT_ERR_INVALID, std::string(who) + ": no spectral accumulation with a pass (srt_accum_reset_spectral and srt_render_chunk_accum first)");
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     // the kernel runs on the chunk's rectangle (clipped to the reference grid); the image clips only what is copied out
     const uint32_t w = clipped_w(c), h = clipped_h(c);
     const size_t pixels = (size_t)w * h;
@@ -1321,7 +1352,7 @@ int develop_accumulation(srt_ctx *c, const char *who, const float *response, uin
             if (host[k] && rect.w && rect.h) HIP_TRY(c, hipMemcpy2D(host[k] + rect.first * channels, pitch, src[k], src_pitch, row, rect.h, hipMemcpyDeviceToHost));
         }
     }
-    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, device_synchronize(c));
     return SRT_OK;
 }
 
@@ -1353,7 +1384,7 @@ int srt_develop_kat(srt_ctx *c, const float *film, uint32_t n_pixels, const floa
     if (!c || !film || !response || !out) return fail(c, SRT_ERR_INVALID, "srt_develop_kat: null argument");
     if (n_pixels == 0 || n_pixels > 0x7fffffffu) return fail(c, SRT_ERR_INVALID, "srt_develop_kat: n_pixels must be in 1 .. 2^31 - 1");
     if (const char *why = develop_args_error(response, channels, scale)) return fail(c, SRT_ERR_INVALID, std::string("srt_develop_kat: ") + why);
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     const char *who = "srt_develop_kat";
     if (const int rc = develop_reserve(c, who, c->d_develop_in, (size_t)n_pixels * kFilmStride * sizeof(float))) return rc;      // (the larger block first)
     if (const int rc = develop_reserve(c, who, c->d_develop, DevelopLayout::bytes(n_pixels, channels, false))) return rc;
@@ -1367,7 +1398,7 @@ int srt_develop_kat(srt_ctx *c, const float *film, uint32_t n_pixels, const floa
     // a grid of one n x 1 block makes the block-linear lane the pixel
     if (const int rc = run_develop(c, who, c->d_develop_in.as<float>(), n_pixels, n_pixels, 1, 1, n_pixels, 1, response, channels, scale, 0)) return rc;
     HIP_TRY_AS(c, who, hipMemcpy(out, DevelopLayout(c->d_develop, n_pixels, channels).out, (size_t)n_pixels * channels * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY_AS(c, who, hipDeviceSynchronize());
+    HIP_TRY_AS(c, who, device_synchronize(c));
     return SRT_OK;
 }
 
@@ -1464,7 +1495,7 @@ int run_meter(srt_ctx *c, const char *who, MeterParams p, const srt_meter *cfg, 
     c->meter_timed = true;
     std::vector<uint32_t> host(kMeterBins + 6);      // the histogram and the three 64-bit counters behind it
     HIP_TRY_AS(c, who, hipMemcpy(host.data(), L.hist, host.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIP_TRY_AS(c, who, hipDeviceSynchronize());
+    HIP_TRY_AS(c, who, device_synchronize(c));
     unsigned long long counts[3];
     memcpy(counts, host.data() + kMeterBins, sizeof(counts));
     meter_decide(host.data(), cfg, result);
@@ -1522,7 +1553,7 @@ int srt_meter_accum(srt_ctx *c, const srt_meter *cfg, uint32_t *hist, srt_meter_
     if (!c->accum.bound()) return fail(c, SRT_ERR_INVALID, "srt_meter_accum: no accumulation with a pass (srt_accum_reset* and srt_render_chunk_accum first)");
     uint32_t rect[4];
     if (const char *why = meter_rect_error(cfg, clipped_w(c), clipped_h(c), rect)) return fail(c, SRT_ERR_INVALID, std::string("srt_meter_accum: ") + why);
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     MeterParams p = {};
     p.y = AccumLayout(c).y; p.y_stride = 1; p.state = c->accum.adaptive() ? AdaptPlanes(c).state : nullptr;
     p.samples = c->accum.total; p.normalise = 1;
@@ -1542,7 +1573,7 @@ int srt_meter_kat(srt_ctx *c, const srt_meter *cfg, const float *xyz_mean, uint3
     if (const char *why = meter_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_meter_kat: ") + why);
     uint32_t rect[4];
     if (const char *why = meter_rect_error(cfg, w, h, rect)) return fail(c, SRT_ERR_INVALID, std::string("srt_meter_kat: ") + why);
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     if (const int rc = upload_kat_xyz(c, who, xyz_mean, w, h)) return rc;
     // a grid of one w x h block makes the block-linear lane the row-major pixel
     MeterParams p = {};
@@ -1563,7 +1594,7 @@ int srt_expose_accum(srt_ctx *c, const srt_tone *tone, float *out_xyz, float *ou
     if ((!out_xyz && !out_lin && !out_q) || image_width == 0 || image_height == 0) return fail(c, SRT_ERR_INVALID, "srt_expose_accum: no output / empty image");
     if (const char *why = tone_cfg_error(tone)) return fail(c, SRT_ERR_INVALID, std::string("srt_expose_accum: ") + why);
     if (!c->accum.bound()) return fail(c, SRT_ERR_INVALID, "srt_expose_accum: no accumulation with a pass (srt_accum_reset* and srt_render_chunk_accum first)");
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     // the kernel runs on the chunk's rectangle (clipped to the reference grid); the image clips only what is copied out
     const uint32_t w = clipped_w(c), h = clipped_h(c);
     const size_t pixels = (size_t)w * h;
@@ -1586,7 +1617,7 @@ int srt_expose_accum(srt_ctx *c, const srt_tone *tone, float *out_xyz, float *ou
         }
         if (const int rc = read_tone_counts(c, who, &res)) return rc;
     }
-    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, device_synchronize(c));
     if (result) *result = res;
     return SRT_OK;
 }
@@ -1598,7 +1629,7 @@ int srt_expose_kat(srt_ctx *c, const srt_tone *tone, const float *xyz_mean, uint
     if (!out_xyz && !out_lin && !out_q) return fail(c, SRT_ERR_INVALID, "srt_expose_kat: no output");
     if (w == 0 || h == 0 || (uint64_t)w * h > 0x7fffffffull) return fail(c, SRT_ERR_INVALID, "srt_expose_kat: w x h must be in 1 .. 2^31 - 1");
     if (const char *why = tone_cfg_error(tone)) return fail(c, SRT_ERR_INVALID, std::string("srt_expose_kat: ") + why);
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     const size_t pixels = (size_t)w * h;
     if (const int rc = develop_reserve(c, who, c->d_expose_out, ExposeImages::bytes(pixels))) return rc;      // (the larger block first)
     if (const int rc = develop_reserve(c, who, c->d_expose, ExposeLayout::kBytes)) return rc;
@@ -1613,7 +1644,7 @@ int srt_expose_kat(srt_ctx *c, const srt_tone *tone, const float *xyz_mean, uint
         if (host[k]) HIP_TRY_AS(c, who, hipMemcpy(host[k], I.img[k], pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
     srt_tone_result res = {};
     if (const int rc = read_tone_counts(c, who, &res)) return rc;
-    HIP_TRY_AS(c, who, hipDeviceSynchronize());
+    HIP_TRY_AS(c, who, device_synchronize(c));
     if (result) *result = res;
     return SRT_OK;
 }
@@ -1703,7 +1734,7 @@ int srt_despeckle_accum(srt_ctx *c, const srt_despeckle *cfg, float *out_xyz, fl
     if (!c->accum.bound()) return fail(c, SRT_ERR_INVALID, "srt_despeckle_accum: no accumulation with a pass (srt_accum_reset* and srt_render_chunk_accum first)");
     if (c->rank != 0 || c->world != 1)
         return fail(c, SRT_ERR_UNSUPPORTED, "srt_despeckle_accum: needs the whole chunk on this context (partition (0, 1)): pixels of other ranks read +0");
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     // the kernel runs on the chunk's rectangle (clipped to the reference grid); the image clips only what is copied out
     const uint32_t w = clipped_w(c), h = clipped_h(c);
     const size_t pixels = (size_t)w * h;
@@ -1725,7 +1756,7 @@ int srt_despeckle_accum(srt_ctx *c, const srt_despeckle *cfg, float *out_xyz, fl
         }
         if (const int rc = read_despeckle_counts(c, who, &res)) return rc;
     }
-    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, device_synchronize(c));
     if (result) *result = res;
     return SRT_OK;
 }
@@ -1737,7 +1768,7 @@ int srt_despeckle_kat(srt_ctx *c, const srt_despeckle *cfg, const float *xyz_mea
     if (!out_xyz && !out_scale && !result) return fail(c, SRT_ERR_INVALID, "srt_despeckle_kat: no output");
     if (w == 0 || h == 0 || (uint64_t)w * h > 0x7fffffffull) return fail(c, SRT_ERR_INVALID, "srt_despeckle_kat: w x h must be in 1 .. 2^31 - 1");
     if (const char *why = despeckle_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_despeckle_kat: ") + why);
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     const size_t pixels = (size_t)w * h;
     if (const int rc = develop_reserve(c, who, c->d_despeckle, DespeckleLayout::bytes(pixels))) return rc;
     if (const int rc = upload_kat_xyz(c, who, xyz_mean, w, h)) return rc;
@@ -1750,7 +1781,7 @@ int srt_despeckle_kat(srt_ctx *c, const srt_despeckle *cfg, const float *xyz_mea
     if (out_scale) HIP_TRY_AS(c, who, hipMemcpy(out_scale, L.scale, pixels * sizeof(float), hipMemcpyDeviceToHost));
     srt_despeckle_result res = {};
     if (const int rc = read_despeckle_counts(c, who, &res)) return rc;
-    HIP_TRY_AS(c, who, hipDeviceSynchronize());
+    HIP_TRY_AS(c, who, device_synchronize(c));
     if (result) *result = res;
     return SRT_OK;
 }
@@ -1910,7 +1941,7 @@ int srt_temporal_kat(srt_ctx *c, const srt_temporal *cfg, const srt_camera_data 
     if ((uint64_t)ox + w > (1ull << 24) || (uint64_t)oy + h > (1ull << 24)) return fail(c, SRT_ERR_INVALID, "srt_temporal_kat: ox + w and oy + h must not exceed 2^24");
     if (const char *why = temporal_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_temporal_kat: ") + why);
     const bool history = prev_cam && hist_colour && hist_guides;
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     const size_t pixels = (size_t)w * h;
     if (const int rc = develop_reserve(c, who, c->d_temporal, TemporalLayout::bytes(pixels))) return rc;
     if (const int rc = develop_reserve(c, who, c->d_temporal_kat, TemporalKatLayout::bytes(pixels))) return rc;
@@ -1933,7 +1964,7 @@ int srt_temporal_kat(srt_ctx *c, const srt_temporal *cfg, const srt_camera_data 
     srt_temporal_result res = {};
     if (const int rc = read_temporal_counts(c, who, &res)) return rc;
     res.history_frames = history ? 2u : 1u;
-    HIP_TRY_AS(c, who, hipDeviceSynchronize());
+    HIP_TRY_AS(c, who, device_synchronize(c));
     if (result) *result = res;
     return SRT_OK;
 }
@@ -2122,7 +2153,7 @@ int denoise_accumulation(srt_ctx *c, const char *who, const DenoisePlan &plan, u
 int denoise_features(srt_ctx *c, const char *who, const DenoisePlan &plan, float *const host[4], uint32_t image_width, uint32_t image_height,
                      const srt_despeckle *ds = nullptr, TemporalStage *ts = nullptr) {
     if (const int rc = denoise_accumulation_refusal(c, who, plan)) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     // the filter runs on the chunk's rectangle (clipped to the reference grid); the image clips only what is copied out
     const uint32_t w = clipped_w(c), h = clipped_h(c);
     const size_t pixels = (size_t)w * h;
@@ -2138,7 +2169,7 @@ int denoise_features(srt_ctx *c, const char *who, const DenoisePlan &plan, float
         }
         if (ts) if (const int rc = read_temporal_counts(c, who, &ts->res)) return rc;
     }
-    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, device_synchronize(c));
     return SRT_OK;
 }
 
@@ -2151,7 +2182,7 @@ int denoise_kat(srt_ctx *c, const char *who, const DenoisePlan &plan, const floa
     if (sample_map)
         for (size_t k = 0; k < pixels; k++)
             if ((sample_map[k] & ~kAdaptConverged) == 0) return fail(c, SRT_ERR_INVALID, std::string(who) + ": a zero in samples (every pixel must hold at least one sample)");
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     HIP_TRY_AS(c, who, c->d_denoise.reserve(DenoiseLayout::bytes(pixels, plan.vg)));
     HIP_TRY_AS(c, who, c->d_denoise_in.reserve(pixels * (kFeatureStride + 3 + 2) * sizeof(float)));
     float *d_rows = c->d_denoise_in.as<float>(), *d_sums = d_rows + pixels * kFeatureStride, *d_map = d_sums + pixels * 3, *d_s2 = d_map + pixels;
@@ -2171,7 +2202,7 @@ int denoise_kat(srt_ctx *c, const char *who, const DenoisePlan &plan, const floa
     const DenoiseLayout L(c->d_denoise, pixels);
     HIP_TRY_AS(c, who, hipMemcpy(out_xyz, L.out[0], pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
     if (out_var) HIP_TRY_AS(c, who, hipMemcpy(out_var, L.var, pixels * 2 * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY_AS(c, who, hipDeviceSynchronize());
+    HIP_TRY_AS(c, who, device_synchronize(c));
     return SRT_OK;
 }
 
@@ -2219,7 +2250,7 @@ int srt_temporal_accum(srt_ctx *c, const srt_temporal *cfg, float *out_xyz, floa
     if (const char *why = temporal_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_temporal_accum: ") + why);
     const DenoisePlan plan = {};      // (the prepass alone: no level runs)
     if (const int rc = denoise_accumulation_refusal(c, who, plan)) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     // the stage runs on the chunk's rectangle (clipped to the reference grid); the image clips only what is copied out
     const uint32_t w = clipped_w(c), h = clipped_h(c);
     const size_t pixels = (size_t)w * h;
@@ -2242,7 +2273,7 @@ int srt_temporal_accum(srt_ctx *c, const srt_temporal *cfg, float *out_xyz, floa
         }
         if (const int rc = read_temporal_counts(c, who, &ts.res)) return rc;
     }
-    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, device_synchronize(c));
     if (result) *result = ts.res;
     return SRT_OK;
 }
@@ -2365,7 +2396,7 @@ int srt_denoise_developed(srt_ctx *c, const srt_denoise *cfg, const float *respo
                                         "srt_accum_reset_adaptive_spectral_features, and srt_render_chunk_accum first)");
     if (c->rank != 0 || c->world != 1)
         return fail(c, SRT_ERR_UNSUPPORTED, "srt_denoise_developed: needs the whole chunk on this context (partition (0, 1)): pixels of other ranks read +0");
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     // develop and filter run on the chunk's rectangle (clipped to the reference grid); the image clips only what is copied out
     const uint32_t w = clipped_w(c), h = clipped_h(c);
     const size_t pixels = (size_t)w * h;
@@ -2390,7 +2421,7 @@ int srt_denoise_developed(srt_ctx *c, const srt_denoise *cfg, const float *respo
             if (host[k] && rect.w && rect.h) HIP_TRY(c, hipMemcpy2D(host[k] + rect.first * ch, pitch, src[k], src_pitch, row, rect.h, hipMemcpyDeviceToHost));
         }
     }
-    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, device_synchronize(c));
     return SRT_OK;
 }
 
@@ -2406,7 +2437,7 @@ static int denoise_developed_kat(srt_ctx *c, const char *who, const srt_denoise 
     if (sample_map)
         for (size_t k = 0; k < pixels; k++)
             if ((sample_map[k] & ~kAdaptConverged) == 0) return fail(c, SRT_ERR_INVALID, w_ + ": a zero in samples (every pixel must hold at least one sample)");
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     if (const int rc = develop_reserve(c, who, c->d_denoise, DenoiseLayout::bytes(pixels, false))) return rc;
     if (const int rc = develop_reserve(c, who, c->d_denoise_dev, DenoiseDevLayout::bytes(pixels, channels, true))) return rc;
     if (const int rc = develop_reserve(c, who, c->d_denoise_in, pixels * (kFeatureStride + 3 + 1) * sizeof(float))) return rc;
@@ -2425,7 +2456,7 @@ static int denoise_developed_kat(srt_ctx *c, const char *who, const srt_denoise 
     if (const int rc = run_denoise_developed(c, who, denoise_plan(cfg), pre, D.in, channels)) return rc;
     if (out_dev) HIP_TRY_AS(c, who, hipMemcpy(out_dev, D.out, pixels * channels * sizeof(float), hipMemcpyDeviceToHost));
     if (out_xyz) HIP_TRY_AS(c, who, hipMemcpy(out_xyz, DenoiseLayout(c->d_denoise, pixels).out[0], pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY_AS(c, who, hipDeviceSynchronize());
+    HIP_TRY_AS(c, who, device_synchronize(c));
     return SRT_OK;
 }
 
@@ -2572,7 +2603,7 @@ int present_chain(srt_ctx *c, const char *who, const srt_present_cfg *cfg, const
     if (developed && !c->accum.spectral()) return fail(c, SRT_ERR_INVALID, w_ + "SRT_PRESENT_DEVELOP needs a spectral accumulation (srt_accum_reset_spectral*)");
     uint32_t rect[4] = {0, 0, 0, 0};
     if (cfg->metered) if (const char *why = meter_rect_error(&cfg->meter, clipped_w(c), clipped_h(c), rect)) return fail(c, SRT_ERR_INVALID, w_ + why);
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     // the chain runs on the chunk's rectangle (clipped to the reference grid); the image clips only what is copied out
     const uint32_t w = clipped_w(c), h = clipped_h(c);
     const size_t pixels = (size_t)w * h;
@@ -2635,7 +2666,7 @@ int present_chain(srt_ctx *c, const char *who, const srt_present_cfg *cfg, const
         if (ds) if (const int rc = read_despeckle_counts(c, who, &ds_res)) return rc;
         if (tcfg) if (const int rc = read_temporal_counts(c, who, &ts.res)) return rc;
     }
-    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, device_synchronize(c));
     if (result) *result = res;
     if (ds_result) *ds_result = ds_res;
     if (ts_result) *ts_result = ts.res;
@@ -2667,7 +2698,7 @@ int srt_present_kat(srt_ctx *c, const srt_tone *tone, const float *xyz_mean, uin
     if (!c || !tone || !xyz_mean || !out_rgba8) return fail(c, SRT_ERR_INVALID, "srt_present_kat: null argument");
     if (w == 0 || h == 0 || (uint64_t)w * h > 0x7fffffffull) return fail(c, SRT_ERR_INVALID, "srt_present_kat: w x h must be in 1 .. 2^31 - 1");
     if (const char *why = tone_cfg_error(tone)) return fail(c, SRT_ERR_INVALID, std::string("srt_present_kat: ") + why);
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     const size_t pixels = (size_t)w * h;
     if (const int rc = develop_reserve(c, who, c->d_present, PresentLayout::bytes(pixels, false))) return rc;
     if (const int rc = develop_reserve(c, who, c->d_expose, ExposeLayout::kBytes)) return rc;
@@ -2766,7 +2797,7 @@ int srt_order_children_by_profile(srt_ctx *c, srt_scene *s, uint32_t width, uint
         memcpy(&sibbox[6 * (size_t)nd.left], s->nodes[(size_t)nd.right].box, 6 * sizeof(float));
         memcpy(&sibbox[6 * (size_t)nd.right], s->nodes[(size_t)nd.left].box, 6 * sizeof(float));
     }
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     DeviceBuffer d_leaf, d_up, d_sib, d_cnt;      // (the probe frames' c->order_profile points at them: probe_frame clears it before it returns)
     const char *what = "srt_order_children_by_profile: device buffers";
     HIP_TRY_AS(c, what, d_leaf.reserve(std::max<size_t>(n_tris, 1) * sizeof(int32_t)));
@@ -2892,7 +2923,7 @@ int srt_last_kernel_ms(srt_ctx *c, float *ms) {
 int srt_trace_rays(srt_ctx *c, const float *rays, size_t n, float *out) {
     if (!c || !c->scene_ready || (!rays && n) || (!out && n)) return fail(c, SRT_ERR_INVALID, "srt_trace_rays: scene not uploaded / bad argument");
     if (n == 0) return SRT_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     DeviceBuffer d_in, d_out;
     HIP_TRY_AS(c, "srt_trace_rays", d_in.reserve(6 * n * sizeof(float)));
     HIP_TRY_AS(c, "srt_trace_rays", d_out.reserve(4 * n * sizeof(float)));
@@ -2900,7 +2931,7 @@ int srt_trace_rays(srt_ctx *c, const float *rays, size_t n, float *out) {
     RenderParams p;
     fill_params(c, p);
     HIP_TRY_AS(c, "srt_trace_rays", launch_trace(p, d_in.as<float>(), n, d_out.as<float>(), nullptr));
-    HIP_TRY_AS(c, "srt_trace_rays", hipDeviceSynchronize());
+    HIP_TRY_AS(c, "srt_trace_rays", device_synchronize(c));
     HIP_TRY_AS(c, "srt_trace_rays", hipMemcpy(out, d_out.ptr, 4 * n * sizeof(float), hipMemcpyDeviceToHost));
     return SRT_OK;
 }
@@ -2908,14 +2939,14 @@ int srt_trace_rays(srt_ctx *c, const float *rays, size_t n, float *out) {
 int srt_device_op_sweep(srt_ctx *c, int which, const float *a, const float *b, size_t n, float *out) {
     if (!c || !a || !b || !out) return fail(c, SRT_ERR_INVALID, "srt_device_op_sweep: null argument");
     if (n == 0) return SRT_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     DeviceBuffer buf;      // a | b | out
     HIP_TRY_AS(c, "srt_device_op_sweep", buf.reserve(3 * n * sizeof(float)));
     float *d = buf.as<float>();
     HIP_TRY_AS(c, "srt_device_op_sweep", hipMemcpy(d, a, n * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY_AS(c, "srt_device_op_sweep", hipMemcpy(d + n, b, n * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY_AS(c, "srt_device_op_sweep", launch_op_sweep(which, d, d + n, n, d + 2 * n, nullptr));
-    HIP_TRY_AS(c, "srt_device_op_sweep", hipDeviceSynchronize());
+    HIP_TRY_AS(c, "srt_device_op_sweep", device_synchronize(c));
     HIP_TRY_AS(c, "srt_device_op_sweep", hipMemcpy(out, d + 2 * n, n * sizeof(float), hipMemcpyDeviceToHost));
     return SRT_OK;
 }
@@ -2926,7 +2957,7 @@ int srt_order_tiles_kat(srt_ctx *c, const uint32_t *cost, uint32_t n, uint32_t n
     // (beyond 2^20 tiles the kernel must not split; one that wrongly did would write past any buffer sized for what it should do)
     if (n == 0 || n > (1u << 20)) return fail(c, SRT_ERR_INVALID, "srt_order_tiles_kat: n must be in 1 .. 2^20");
     if (rows_cap < (size_t)n * 64 + 64) return fail(c, SRT_ERR_INVALID, "srt_order_tiles_kat: rows_cap must be at least 64 * n + 64 (the largest queue and 64 guard words)");
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     DeviceBuffer d_cost, d_rows, d_sorted, d_info;
     HIP_TRY_AS(c, "srt_order_tiles_kat", d_cost.reserve(TileSchedule::cost_bytes(n)));
     HIP_TRY_AS(c, "srt_order_tiles_kat", d_rows.reserve(rows_cap * sizeof(uint32_t)));
@@ -2938,7 +2969,7 @@ int srt_order_tiles_kat(srt_ctx *c, const uint32_t *cost, uint32_t n, uint32_t n
     HIP_TRY_AS(c, "srt_order_tiles_kat", hipMemset(d_info.ptr, 0xff, 4 * sizeof(uint32_t)));
     HIP_TRY_AS(c, "srt_order_tiles_kat", launch_order_tiles(d_cost.as<uint32_t>(), d_sorted.as<uint32_t>(), d_rows.as<uint32_t>(), n, n_waves, split_load_pct,
                                                             d_info.as<uint32_t>(), order_max_pct, nullptr));
-    HIP_TRY_AS(c, "srt_order_tiles_kat", hipDeviceSynchronize());
+    HIP_TRY_AS(c, "srt_order_tiles_kat", device_synchronize(c));
     HIP_TRY_AS(c, "srt_order_tiles_kat", hipMemcpy(rows_out, d_rows.ptr, rows_cap * sizeof(uint32_t), hipMemcpyDeviceToHost));
     HIP_TRY_AS(c, "srt_order_tiles_kat", hipMemcpy(sorted_out, d_sorted.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     HIP_TRY_AS(c, "srt_order_tiles_kat", hipMemcpy(info_out, d_info.ptr, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -2968,7 +2999,7 @@ int srt_read_tile_schedule(srt_ctx *c, int which, uint32_t *rows_out, size_t row
 int srt_calibrate(srt_ctx *c, int kind, uint32_t waves_per_simd, uint32_t iters, srt_calibration *out) {
     if (!c || !out || kind < 0 || kind >= calib_kinds() || waves_per_simd < 1 || waves_per_simd > 4 || iters == 0)
         return fail(c, SRT_ERR_INVALID, "srt_calibrate: bad argument");
-    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, set_device(c));
     const uint32_t threads = waves_per_simd * 256u, n_blocks = (uint32_t)c->n_cu, n_waves = n_blocks * threads / 64u;
     DeviceBuffer d_cyc, d_sink, d_table;
     HIP_TRY_AS(c, "srt_calibrate", d_cyc.reserve(n_waves * sizeof(unsigned long long)));

@@ -226,7 +226,8 @@ void srt_comm_destroy(srt_comm *c) {
     if (!c) return;
     RcclApi &R = rccl();
     for (size_t i = 0; i < c->ctx.size(); i++) {
-        if (c->ctx[i]) { (void)hipSetDevice(device_of(c->ctx[i])); (void)hipDeviceSynchronize(); }
+        // (through the context: a borrowed one outlives the stream destroyed below, and forgets it at this wait -- srt_c_api.h, "Order of a context's calls")
+        if (c->ctx[i]) (void)srt_synchronize(c->ctx[i]);
         if (c->nccl[i] && R.handle) (void)R.CommDestroy(c->nccl[i]);
         if (c->stream[i]) (void)hipStreamDestroy(c->stream[i]);
         if (i < c->ev_g0.size() && c->ev_g0[i]) (void)hipEventDestroy(c->ev_g0[i]);

@@ -232,7 +232,24 @@ SRT_API int srt_set_partition(srt_ctx *ctx, uint32_t rank, uint32_t world);
 
 /* renderer::render(w,h,offx,offy) -> call_render_kernel (rendering.cu:244-277).  Asynchronous on `stream`
  * (a hipStream_t passed as void*, NULL = default stream); the reference's device-wide sync is srt_synchronize.
- * Renders this rank's tiles into the context's compact tile buffer. */
+ * Renders this rank's tiles into the context's compact tile buffer.
+ *
+ * Order of a context's calls.  A context's calls take effect in the order they were made, whichever streams they name.  A stream
+ * handed to a call must stay valid until the next call on that context that synchronises.
+ * The calls that take a stream are srt_render_chunk, srt_render_chunk_accum, srt_copy_tile_buffer and srt_scatter_tiles; every other
+ * call works on the NULL stream.  The context remembers the stream of the work it enqueued last: a call that enqueues on another
+ * stream -- the NULL stream included, and a hipStreamNonBlocking stream as well as a blocking one -- first makes its stream wait for
+ * an event recorded behind that work, so a pass on one stream may be followed at once by a pass on another, a reset, a stage or a
+ * read-back.  A caller that stays on one stream pays nothing for this.  The calls that synchronise -- they return with nothing of the
+ * context in flight on any stream, and the remembered stream is not touched again after them, so it may be destroyed -- are
+ * srt_synchronize; every read-back (srt_read_fb, srt_read_fb_aux, srt_read_fb_rowmajor, srt_read_accum_stats, srt_read_spectral,
+ * srt_read_features, srt_accum_active on a bound accumulation, srt_get_stats, srt_get_tile_costs, srt_get_wave_debug,
+ * srt_read_tile_schedule); every stage call that returns host data (srt_meter_*, srt_expose_*, srt_develop_*, srt_despeckle_*,
+ * srt_temporal_*, srt_denoise_*, srt_present* -- not their *_last_ms timing queries, which wait for their own events alone);
+ * srt_init_device_params and every srt_accum_reset*.  srt_comm_synchronize waits for the
+ * communicator's own streams only and is none of them; srt_comm_destroy synchronises every context before it destroys those streams.
+ * What is NOT ordered: work the caller itself enqueues on its streams (a copy out of srt_dev_fb, say) against later calls of the
+ * context on other streams -- the context cannot see it. */
 SRT_API int srt_render_chunk(srt_ctx *ctx, uint32_t width, uint32_t height, uint32_t offx, uint32_t offy, void *stream);
 SRT_API int srt_synchronize(srt_ctx *ctx);
 

@@ -341,7 +341,7 @@ def stream_prediction(srt, gpu, orc, name, workload, n, K, seed=SEED, must_diffe
 def run_mock_transport_child(body, ok_token, timeout):
     """Runs `body` (Python source; `srt` is the imported package, tests/ is on sys.path) in a FRESH process with the test transport
     (tests/cpp/mock_rccl.cpp) in place of RCCL and all ranks on device 0, and asserts that it exits with 0 after printing ok_token.
-    A child process because the library caches its RCCL handle per process."""
+    A child process because the library caches its RCCL handle per process.  Returns what the child printed."""
     mock = os.path.join(ROOT, "tests", "cpp", "_build", "libmock_rccl.so")
     assert os.path.exists(mock), "tests/cpp/_build/libmock_rccl.so is built by __graft_entry__.build()"
     code = """
@@ -352,6 +352,7 @@ srt = importlib.import_module('cuda-spectral-ray-tracer_amd')
     env = dict(os.environ, SRT_RCCL_LIB=mock, SRT_COMM_TEST_SAME_DEVICE="1", SRT_TEST_KNOBS="1")
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=timeout)
     assert out.returncode == 0 and ok_token in out.stdout, (out.stdout[-1500:], out.stderr[-3000:])
+    return out.stdout
 
 
 def comm_accumulations(srt, world, planes, scene, cam, W, H, depth, spp, reset, passes):
