@@ -87,6 +87,7 @@ class ToneResult(C.Structure):
     _fields_ = [("blown", C.c_uint64), ("crushed", C.c_uint64), ("nonfinite", C.c_uint64)]
 
 
+SCENE_IMAGES = {"nodes": 0, "nodes_sw": 1, "fringe": 2, "tris": 3, "shade": 4}      # SRT_IMAGE_* (srt_c_api.h)
 PRESENT_SOURCES = {"accum": 0, "denoise": 1, "denoise_vg": 2, "denoise_mv": 3, "develop": 4}      # SRT_PRESENT_* (srt_c_api.h)
 
 
@@ -172,6 +173,8 @@ PROTOTYPES = {
     "srt_color_tables": (_i, [_fp, _fp]),
     "srt_background_spectrum": (_i, [_fp, _fp]),
     "srt_rotation_matrix": (_i, [_f, _i, _fp]),
+    "srt_scene_refit": (_i, [_vp, _fp, _sz]),
+    "srt_scene_refit_schedule": (_i, [_vp, C.POINTER(_u32), _sz, C.POINTER(_u32)]),
     "srt_scene_build_bvh": (_i, [_vp, _i, _u64]),
     "srt_scene_order_children": (_i, [_vp, _fp]),
     "srt_scene_optimise_bvh": (_i, [_vp, C.c_int]),
@@ -183,6 +186,10 @@ PROTOTYPES = {
     "srt_destroy": (None, [_vp]),
     "srt_last_error": (C.c_char_p, [_vp]),
     "srt_upload_scene": (_i, [_vp, _vp]),
+    "srt_refit_vertices": (_i, [_vp, _fp, _sz]),
+    "srt_refit_vertices_dev": (_i, [_vp, _vp, _sz]),
+    "srt_refit_last_ms": (_i, [_vp, _fp, _fp, C.POINTER(_u32)]),
+    "srt_read_scene_image": (_i, [_vp, _i, _vp, _sz, C.POINTER(_sz)]),
     "srt_set_camera": (_i, [_vp, C.POINTER(CameraData)]),
     "srt_launch_plan": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "srt_launch_paired": (_i, [_vp, C.POINTER(_i)]),
@@ -284,6 +291,7 @@ PROTOTYPES = {
     "srt_comm_ctx": (_vp, [_vp, _u32]),
     "srt_comm_root_ctx": (_vp, [_vp]),
     "srt_comm_upload_scene": (_i, [_vp, _vp]),
+    "srt_comm_refit_vertices": (_i, [_vp, _fp, _sz]),
     "srt_comm_set_camera": (_i, [_vp, C.POINTER(CameraData)]),
     "srt_comm_init_device_params": (_i, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u64]),
     "srt_render_frame_multi": (_i, [_vp, _u32, _u32, _u32, _u32]),

@@ -197,6 +197,20 @@ struct srt_ctx {
     srt_camera_data temporal_cam = {};                  // the camera that was current when the history was written
     hipEvent_t temporal_ev[2] = {};                     // around the last temporal kernel (created on first use)
     bool temporal_timed = false;
+    // BVH refit (srt_refit.hip).  The topology tables are made on the host by srt_upload_scene (RefitParams states them), copied to the
+    // device by the first refit after an upload; tables, scratch and staging belong to the context and are reused.
+    std::vector<uint32_t> refit_tri_tab, refit_sched;   // two words per triangle; the record indices grouped by height
+    std::vector<int32_t> refit_child;                   // two references per record
+    std::vector<uint32_t> refit_level_first;            // height h (1 ..) owns sched[first[h - 1] .. first[h])
+    bool refit_tables_ok = false;                       // the tables describe the uploaded scene
+    bool refit_tables_on_device = false;                // ... and d_refit_tab holds them
+    DeviceBuffer d_refit_tab;                           // RefitTables
+    DeviceBuffer d_refit_scratch;                       // RefitScratch: the validation count, the leaf boxes, the records' own boxes
+    DeviceBuffer d_refit_verts;                         // srt_refit_vertices: the caller's vertices
+    size_t image_bytes[5] = {0, 0, 0, 0, 0};            // bytes of the uploaded scene images, by SRT_IMAGE_* (0: the plan keeps none)
+    hipEvent_t refit_ev[3] = {};                        // around the last refit's triangle kernel [0, 1] and its level launches [1, 2] (created on first use)
+    uint32_t refit_timed_levels = 0;
+    bool refit_timed = false;
     DeviceBuffer d_streams;                            // sample-parallel pixels (srt_accum_reset_streams, StreamPlanes)
     uint32_t streams_seeded = 0;                        // the K whose RNG streams d_streams holds, seeded since the last srt_init_device_params (0: none)
 };
@@ -268,6 +282,33 @@ int upload(srt_ctx *ctx, DeviceBuffer &dst, const std::vector<float> &src) {
 }
 
 // ---- the layouts of the composite buffers: each is taken apart here and nowhere else ------------------------------------------
+
+// The refit's topology tables on the device: [tri_tab: 2 words per triangle | child: 2 per record | sched: 1 per record]
+struct RefitTables {
+    uint32_t *tri_tab, *sched;
+    int32_t *child;
+    static size_t bytes(size_t n_tris, size_t n_records) { return (2 * n_tris + 3 * n_records) * sizeof(uint32_t); }
+    RefitTables(const DeviceBuffer &d, size_t n_tris, size_t n_records)
+        : tri_tab(d.as<uint32_t>()), sched(tri_tab + 2 * n_tris + 2 * n_records), child(reinterpret_cast<int32_t *>(tri_tab + 2 * n_tris)) {}
+};
+// The refit's scratch: [count: the validation kernel's word, 256 B | leaf boxes: 6 floats per triangle | own boxes: 6 per record]
+struct RefitScratch {
+    static constexpr size_t kCountBytes = 256;
+    uint32_t *count;
+    float *leaf_box, *rec_box;
+    static size_t bytes(size_t n_tris, size_t n_records) { return kCountBytes + 6 * (n_tris + n_records) * sizeof(float); }
+    RefitScratch(const DeviceBuffer &d, size_t n_tris)
+        : count(d.as<uint32_t>()), leaf_box(reinterpret_cast<float *>(d.as<char>() + kCountBytes)), rec_box(leaf_box + 6 * n_tris) {}
+};
+
+// The refit's tables (refit_topology, srt_host.cpp) into the context; host only
+void build_refit_tables(srt_ctx *c, const FlatScene &f, const srt_scene &s) {
+    static_assert(kRefitNoSlot == kRefitTopologyNoSlot, "the kernel's and the host's marker of a triangle without a FRINGE block");
+    RefitTopology t;
+    refit_topology(f, s, t);
+    c->refit_tri_tab.swap(t.tri_tab); c->refit_child.swap(t.child); c->refit_sched.swap(t.sched); c->refit_level_first.swap(t.level_first);
+    c->refit_tables_ok = t.ok;
+}
 
 // The cost probe's schedule.  d_tile_order: [rows: up to 64 per tile][sorted tile ids][queue_info 4 words]; d_tile_cost: per local tile
 // its cost, then the cost of its most expensive pixel.
@@ -686,6 +727,7 @@ void srt_destroy(srt_ctx *c) {
     for (hipEvent_t e : c->present_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->despeckle_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->temporal_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->refit_ev) if (e) (void)hipEventDestroy(e);
     delete c;      // (every DeviceBuffer, and the pinned staging block, frees itself, on the device selected above)
 }
 
@@ -699,6 +741,7 @@ int srt_upload_scene(srt_ctx *c, const srt_scene *s) {
     c->accum.invalidate();
     c->temporal_frames = 0;      // (the temporal history shows another scene)
     c->sched_probe_queue = false; c->sched_compacted_queue = false;      // (the queues of the last launch belong to the old set-up)
+    c->refit_tables_ok = false; c->refit_tables_on_device = false;      // (the refit's tables describe the old tree)
     HIP_TRY(c, set_device(c));
     FlatScene f;
     int rc = flatten_scene(*s, f);
@@ -722,6 +765,8 @@ int srt_upload_scene(srt_ctx *c, const srt_scene *s) {
         }
         if ((rc = upload(c, c->d_fringe, stride == 96u ? f.fringe : padded)) != SRT_OK) return rc;
         c->fringe_stride = stride;
+        c->image_bytes[SRT_IMAGE_FRINGE] = (stride == 96u ? f.fringe.size() : padded.size()) * sizeof(float);
+        c->image_bytes[SRT_IMAGE_NODES_SW] = plan.all_cached ? 0 : f.nodes_sw.size() * sizeof(float);
         // (the pre-swizzled copy of the INNER records: only trees whose INNER visits read memory need it)
         c->d_nodes_sw.release();
         if (!plan.all_cached && (rc = upload(c, c->d_nodes_sw, f.nodes_sw)) != SRT_OK) return rc;
@@ -739,7 +784,132 @@ int srt_upload_scene(srt_ctx *c, const srt_scene *s) {
     c->root_ref = f.root_ref; c->stack_depth = f.stack_depth; c->n_materials = (uint32_t)s->mats.size();
     c->n_inner = f.n_inner; c->n_records = f.n_records; c->n_tris = (uint32_t)s->raw.size();
     c->paired = tree_is_paired(*s);
+    c->image_bytes[SRT_IMAGE_NODES] = f.nodes.size() * sizeof(float);
+    c->image_bytes[SRT_IMAGE_TRIS] = f.tris.size() * sizeof(float);
+    c->image_bytes[SRT_IMAGE_SHADE] = f.shade.size() * sizeof(float);
+    build_refit_tables(c, f, *s);      // (host only: nothing is enqueued or allocated on the device for a caller who never refits)
     c->scene_ready = true;
+    return SRT_OK;
+}
+
+// ---- BVH refit (srt_refit.hip; srt_c_api.h states it at srt_refit_vertices) ---------------------------------------------------------
+namespace {
+
+int develop_reserve(srt_ctx *c, const char *who, DeviceBuffer &d, size_t bytes);      // (below, with the stages' working blocks)
+
+// the refit: the device copy of the tables is made now if this is the first refit since the upload, then one triangle kernel and one
+// level launch per height, bottom up, on the NULL stream; d_verts holds 9 * n_tris validated floats on the device
+int refit_run(srt_ctx *c, const char *who, const float *d_verts) {
+    const size_t n_tris = c->n_tris, n_rec = (size_t)c->n_records;
+    if (const int rc = develop_reserve(c, who, c->d_refit_tab, RefitTables::bytes(n_tris, n_rec))) return rc;
+    if (const int rc = develop_reserve(c, who, c->d_refit_scratch, RefitScratch::bytes(n_tris, n_rec))) return rc;
+    for (hipEvent_t &e : c->refit_ev)
+        if (!e) HIP_TRY_AS(c, who, hipEventCreate(&e));
+    const RefitTables T(c->d_refit_tab, n_tris, n_rec);
+    const RefitScratch S(c->d_refit_scratch, n_tris);
+    if (!c->refit_tables_on_device) {
+        HIP_TRY_AS(c, who, hipMemcpy(T.tri_tab, c->refit_tri_tab.data(), c->refit_tri_tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (n_rec) {
+            HIP_TRY_AS(c, who, hipMemcpy(T.child, c->refit_child.data(), c->refit_child.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+            HIP_TRY_AS(c, who, hipMemcpy(T.sched, c->refit_sched.data(), c->refit_sched.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        }
+        c->refit_tables_on_device = true;
+    }
+    RefitParams p = {};
+    p.verts = d_verts; p.tri_tab = T.tri_tab; p.child = T.child; p.sched = T.sched;
+    p.tris = c->d_tris.as<float>(); p.shade = c->d_shade.as<float>(); p.fringe = c->d_fringe.as<float>(); p.nodes = c->d_nodes.as<float>();
+    p.nodes_sw = c->image_bytes[SRT_IMAGE_NODES_SW] ? c->d_nodes_sw.as<float>() : nullptr;
+    p.leaf_box = S.leaf_box; p.rec_box = S.rec_box;
+    p.n_tris = c->n_tris; p.n_inner = (uint32_t)c->n_inner; p.fringe_stride = c->fringe_stride / (uint32_t)sizeof(float);
+    // from here on the images change: what shows the old geometry goes, as at srt_upload_scene
+    c->accum.invalidate();
+    c->temporal_frames = 0;
+    c->sched_probe_queue = false; c->sched_compacted_queue = false;
+    c->refit_timed = false;
+    HIP_TRY_AS(c, who, hipEventRecord(c->refit_ev[0], nullptr));
+    HIP_TRY_AS(c, who, launch_refit_triangles(p, nullptr));
+    HIP_TRY_AS(c, who, hipEventRecord(c->refit_ev[1], nullptr));
+    const uint32_t n_levels = c->refit_level_first.empty() ? 0u : (uint32_t)c->refit_level_first.size() - 1u;
+    for (uint32_t h = 0; h < n_levels; h++)
+        HIP_TRY_AS(c, who, launch_refit_level(p, c->refit_level_first[h], c->refit_level_first[h + 1] - c->refit_level_first[h], nullptr));
+    HIP_TRY_AS(c, who, hipEventRecord(c->refit_ev[2], nullptr));
+    HIP_TRY_AS(c, who, device_synchronize(c));
+    c->refit_timed = true; c->refit_timed_levels = n_levels;
+    return SRT_OK;
+}
+
+const char *refit_refusal(const srt_ctx *c, const void *verts, size_t n_tris) {
+    if (!c->scene_ready) return "no scene uploaded";
+    if (!c->refit_tables_ok) return "the uploaded records do not form a tree the refit can schedule (internal error)";
+    if (!verts) return "null vertices";
+    if (n_tris != c->n_tris) return "n_tris is not the uploaded scene's triangle count";
+    return nullptr;
+}
+
+}  // namespace
+
+int srt_refit_vertices(srt_ctx *c, const float *verts, size_t n_tris) { return srt_internal_refit_vertices(c, verts, n_tris, 0); }
+
+int srt_internal_refit_vertices(srt_ctx *c, const float *verts, size_t n_tris, int scanned) {
+    const char *who = "srt_refit_vertices";
+    if (!c) return fail(c, SRT_ERR_INVALID, "srt_refit_vertices: null ctx");
+    if (const char *why = refit_refusal(c, verts, n_tris)) return fail(c, SRT_ERR_INVALID, std::string("srt_refit_vertices: ") + why);
+    for (size_t k = 0; !scanned && k < 9 * n_tris; k++)
+        if (!std::isfinite(verts[k])) return fail(c, SRT_ERR_INVALID, "srt_refit_vertices: a coordinate is not finite");
+    HIP_TRY(c, set_device(c));
+    if (const int rc = develop_reserve(c, who, c->d_refit_verts, 9 * n_tris * sizeof(float))) return rc;
+    HIP_TRY_AS(c, who, hipMemcpy(c->d_refit_verts.ptr, verts, 9 * n_tris * sizeof(float), hipMemcpyHostToDevice));
+    return refit_run(c, who, c->d_refit_verts.as<float>());
+}
+
+int srt_refit_vertices_dev(srt_ctx *c, const float *verts_dev, size_t n_tris) {
+    const char *who = "srt_refit_vertices_dev";
+    if (!c) return fail(c, SRT_ERR_INVALID, "srt_refit_vertices_dev: null ctx");
+    if (const char *why = refit_refusal(c, verts_dev, n_tris)) return fail(c, SRT_ERR_INVALID, std::string("srt_refit_vertices_dev: ") + why);
+    HIP_TRY(c, set_device(c));
+    if (const int rc = develop_reserve(c, who, c->d_refit_scratch, RefitScratch::bytes(n_tris, (size_t)c->n_records))) return rc;
+    // the validation: the count of coordinates that are not finite comes back, 4 bytes, before anything is written
+    const RefitScratch S(c->d_refit_scratch, n_tris);
+    uint32_t bad = 0;
+    HIP_TRY_AS(c, who, hipMemsetAsync(S.count, 0, sizeof(uint32_t), nullptr));
+    HIP_TRY_AS(c, who, launch_refit_validate(verts_dev, 9 * n_tris, S.count, nullptr));
+    HIP_TRY_AS(c, who, hipMemcpy(&bad, S.count, sizeof(bad), hipMemcpyDeviceToHost));
+    if (bad) {
+        HIP_TRY_AS(c, who, device_synchronize(c));
+        return fail(c, SRT_ERR_INVALID, "srt_refit_vertices_dev: a coordinate is not finite");
+    }
+    return refit_run(c, who, verts_dev);
+}
+
+int srt_refit_last_ms(srt_ctx *c, float *tri_ms, float *levels_ms, uint32_t *n_levels) {
+    if (!c) return fail(c, SRT_ERR_INVALID, "srt_refit_last_ms: null ctx");
+    if (!c->refit_timed) return fail(c, SRT_ERR_INVALID, "srt_refit_last_ms: no refit has run on this context");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipEventSynchronize(c->refit_ev[2]));
+    if (tri_ms) HIP_TRY(c, hipEventElapsedTime(tri_ms, c->refit_ev[0], c->refit_ev[1]));
+    if (levels_ms) HIP_TRY(c, hipEventElapsedTime(levels_ms, c->refit_ev[1], c->refit_ev[2]));
+    if (n_levels) *n_levels = c->refit_timed_levels;
+    return SRT_OK;
+}
+
+int srt_read_scene_image(srt_ctx *c, int which, void *out, size_t cap_bytes, size_t *n_bytes) {
+    if (!c || !n_bytes) return fail(c, SRT_ERR_INVALID, "srt_read_scene_image: null argument");
+    if (!c->scene_ready) return fail(c, SRT_ERR_INVALID, "srt_read_scene_image: no scene uploaded");
+    const DeviceBuffer *src = nullptr;
+    switch (which) {
+    case SRT_IMAGE_NODES: src = &c->d_nodes; break;
+    case SRT_IMAGE_NODES_SW: src = &c->d_nodes_sw; break;
+    case SRT_IMAGE_FRINGE: src = &c->d_fringe; break;
+    case SRT_IMAGE_TRIS: src = &c->d_tris; break;
+    case SRT_IMAGE_SHADE: src = &c->d_shade; break;
+    default: return fail(c, SRT_ERR_INVALID, "srt_read_scene_image: unknown image");
+    }
+    const size_t n = c->image_bytes[which];
+    if (out && cap_bytes < n) return fail(c, SRT_ERR_INVALID, "srt_read_scene_image: the image does not fit cap_bytes");
+    HIP_TRY(c, set_device(c));
+    HIP_TRY(c, device_synchronize(c));
+    if (out && n) HIP_TRY(c, hipMemcpy(out, src->ptr, n, hipMemcpyDeviceToHost));
+    *n_bytes = n;
     return SRT_OK;
 }
 

@@ -250,6 +250,17 @@ int srt_comm_upload_scene(srt_comm *c, const srt_scene *s) {
     for (srt_ctx *x : c->ctx) { int rc = srt_upload_scene(x, s); if (rc != SRT_OK) return cfail(c, rc, srt_last_error(x)); }
     return SRT_OK;
 }
+// (every context holds the same scene, so an argument the first one refuses is refused before any context has changed)
+int srt_comm_refit_vertices(srt_comm *c, const float *verts, size_t n_tris) {
+    if (!c || !verts) return cfail(c, SRT_ERR_INVALID, "srt_comm_refit_vertices: null argument");
+    bool first = true;      // (the first context scans the coordinates, for all of them)
+    for (srt_ctx *x : c->ctx) {
+        int rc = srt_internal_refit_vertices(x, verts, n_tris, first ? 0 : 1);
+        if (rc != SRT_OK) return cfail(c, rc, srt_last_error(x));
+        first = false;
+    }
+    return SRT_OK;
+}
 int srt_comm_set_camera(srt_comm *c, const srt_camera_data *cam) {
     if (!c || !cam) return cfail(c, SRT_ERR_INVALID, "srt_comm_set_camera: null argument");
     for (srt_ctx *x : c->ctx) { int rc = srt_set_camera(x, cam); if (rc != SRT_OK) return cfail(c, rc, srt_last_error(x)); }

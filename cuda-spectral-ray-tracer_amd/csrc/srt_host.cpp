@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <mutex>
 
 #include "srt_cie_data.h"
@@ -703,6 +704,61 @@ int flatten_scene(const srt_scene &s, FlatScene &out) {
     return SRT_OK;
 }
 
+// The refit's tables from the flattened scene (RefitTopology states them): the references are read back out of the records flatten_scene
+// made, so the tables describe exactly the images that were uploaded.  Record indices say nothing about who is whose child -- every
+// INNER record lies in front of every FRINGE record, and a FRINGE node with one leaf child may have an INNER node as the other -- so
+// the heights come from a walk over the references from the root: parents before children, then that order backwards.  What is checked
+// is what the kernels rely on: every reference in range, every record the child of exactly one record (the root of none) and reached
+// from the root, every triangle placed exactly once.  flatten_scene's output always passes; a failure is reported as such by the refit.
+void refit_topology(const FlatScene &f, const srt_scene &s, RefitTopology &out) {
+    const size_t n_tris = s.raw.size(), n_rec = (size_t)f.n_records, n_in = (size_t)f.n_inner;
+    out.tri_tab.assign(2 * n_tris, kRefitTopologyNoSlot);
+    for (size_t k = 0; k < n_tris; k++) out.tri_tab[2 * k] = s.raw[k].aa_plane;
+    out.child.assign(2 * n_rec, 0);
+    bool ok = true;
+    size_t placed = 0;
+    std::vector<uint32_t> parents(n_rec, 0u);
+    for (size_t r = 0; r < n_rec; r++)
+        for (size_t k = 0; k < 2; k++) {
+            int32_t ref;
+            memcpy(&ref, r < n_in ? &f.nodes[16 * r + 12 + k] : &f.fringe[24 * (r - n_in) + 22 + k], sizeof(ref));
+            out.child[2 * r + k] = ref;
+            if (ref < 0) {
+                const size_t tri = (size_t)(uint32_t)~ref;
+                if (r < n_in || tri >= n_tris || out.tri_tab[2 * tri + 1] != kRefitTopologyNoSlot) { ok = false; continue; }
+                out.tri_tab[2 * tri + 1] = (uint32_t)(2 * (r - n_in) + k);
+                placed++;
+            } else if ((size_t)ref >= n_rec || (size_t)ref == r || ++parents[(size_t)ref] > 1u) ok = false;
+        }
+    ok = ok && (n_rec ? placed == n_tris && f.root_ref >= 0 && (size_t)f.root_ref < n_rec && parents[(size_t)f.root_ref] == 0u : n_tris == 1);
+    std::vector<uint32_t> height(n_rec, 1u), walk;
+    uint32_t n_levels = 0;
+    if (ok && n_rec) {
+        walk.reserve(n_rec);
+        walk.push_back((uint32_t)f.root_ref);
+        for (size_t at = 0; at < walk.size(); at++)      // (one parent each and none for the root: no record can come up twice)
+            for (size_t k = 0; k < 2; k++)
+                if (out.child[2 * (size_t)walk[at] + k] >= 0) walk.push_back((uint32_t)out.child[2 * (size_t)walk[at] + k]);
+        ok = walk.size() == n_rec;
+        for (size_t at = walk.size(); ok && at-- > 0;) {
+            const size_t r = walk[at];
+            for (size_t k = 0; k < 2; k++)
+                if (out.child[2 * r + k] >= 0) height[r] = std::max(height[r], 1u + height[(size_t)out.child[2 * r + k]]);
+            n_levels = std::max(n_levels, height[r]);
+        }
+    }
+    if (!ok) n_levels = 0;
+    out.level_first.assign(n_levels + 1, 0u);
+    out.sched.assign(n_rec, 0u);
+    if (ok) {
+        for (size_t r = 0; r < n_rec; r++) out.level_first[height[r]]++;
+        for (uint32_t h = 1; h <= n_levels; h++) out.level_first[h] += out.level_first[h - 1];      // first[h] = records of height <= h
+        std::vector<uint32_t> next(out.level_first.begin(), out.level_first.end());
+        for (size_t r = 0; r < n_rec; r++) out.sched[next[height[r] - 1]++] = (uint32_t)r;
+    }
+    out.ok = ok;
+}
+
 static float g_cie[4][SRT_N_CIE_SAMPLES];
 static std::once_flag g_cie_once;
 static void cie_init() {
@@ -1324,6 +1380,40 @@ int srt_scene_set_triangles(srt_scene *s, const srt_tri_in *tris, size_t n) {
     s->rec.resize(n);
     for (size_t k = 0; k < n; k++) tri_precompute(s->raw[k], s->rec[k]);
     s->nodes.clear(); s->bvh_valid = false;
+    return SRT_OK;
+}
+// Refit: new vertices on the built topology (srt_c_api.h).  Everything that depends on the vertices is recomputed with the functions
+// the build itself used, so the scene equals, in every bit, one built from the moved triangles with this topology; what the refit on
+// the device (srt_refit.hip) restates.  mat_index and the sticky aa_plane of every triangle are inputs and stay.
+int srt_scene_refit(srt_scene *s, const float *verts, size_t n_tris) {
+    if (!s || !verts) { set_global_error("srt_scene_refit: null argument"); return SRT_ERR_INVALID; }
+    if (!s->bvh_valid) { set_global_error("srt_scene_refit: BVH not built"); return SRT_ERR_INVALID; }
+    if (n_tris != s->raw.size()) { set_global_error("srt_scene_refit: n_tris is not the scene's triangle count"); return SRT_ERR_INVALID; }
+    for (size_t k = 0; k < 9 * n_tris; k++)
+        if (!std::isfinite(verts[k])) { set_global_error("srt_scene_refit: a coordinate is not finite"); return SRT_ERR_INVALID; }
+    for (size_t k = 0; k < n_tris; k++) {
+        srt_tri_in &t = s->raw[k];
+        memcpy(t.v0, verts + 9 * k, 3 * sizeof(float));
+        memcpy(t.v1, verts + 9 * k + 3, 3 * sizeof(float));
+        memcpy(t.v2, verts + 9 * k + 6, 3 * sizeof(float));
+        tri_precompute(t, s->rec[k]);
+    }
+    finish_boxes_and_depth(*s);
+    return SRT_OK;
+}
+// The level schedule a refit of this scene runs on the device (tests and tools): the records of every height, bottom up.
+int srt_scene_refit_schedule(const srt_scene *s, uint32_t *level_counts, size_t cap, uint32_t *n_levels) {
+    if (!s || !n_levels) { set_global_error("srt_scene_refit_schedule: null argument"); return SRT_ERR_INVALID; }
+    FlatScene f;
+    const int rc = flatten_scene(*s, f);
+    if (rc != SRT_OK) return rc;
+    RefitTopology t;
+    refit_topology(f, *s, t);
+    if (!t.ok) { set_global_error("srt_scene_refit_schedule: the records do not form a tree the refit can schedule (internal error)"); return SRT_ERR_INVALID; }
+    const size_t n = t.level_first.size() - 1;
+    if (level_counts && cap < n) { set_global_error("srt_scene_refit_schedule: cap is smaller than the number of levels"); return SRT_ERR_INVALID; }
+    for (size_t k = 0; level_counts && k < n; k++) level_counts[k] = t.level_first[k + 1] - t.level_first[k];
+    *n_levels = (uint32_t)n;
     return SRT_OK;
 }
 int srt_scene_set_materials(srt_scene *s, const srt_material *mats, size_t m) {

@@ -92,6 +92,18 @@ struct FlatScene {
     int n_records = 0;
 };
 int flatten_scene(const srt_scene &s, FlatScene &out);
+// The topology tables of the BVH refit (srt_refit.hip), from the flattened scene and the scene: tri_tab two words per triangle -- its raw
+// aa_plane, then its slot 2 f + side, the FRINGE record f (an index into the FRINGE image) and the side whose block holds the triangle's
+// copy, kRefitTopologyNoSlot when the root is a leaf; child two references per record (a record index, or ~triangle); sched the record
+// indices grouped by height (1 + the largest height of a child record, a leaf child counting 0), height h owning
+// sched[level_first[h - 1] .. level_first[h]).  ok: the records form a tree and every triangle is placed once (always, for flatten_scene's output).
+constexpr uint32_t kRefitTopologyNoSlot = 0xffffffffu;
+struct RefitTopology {
+    std::vector<uint32_t> tri_tab, sched, level_first;
+    std::vector<int32_t> child;
+    bool ok = false;
+};
+void refit_topology(const FlatScene &f, const srt_scene &s, RefitTopology &out);
 // srt_scene_optimise_bvh with a veto: runs its `passes` rounds, flattens the tree as it was and as it has become, and keeps the new
 // tree only if `keep` says so (or if a tree cannot be flattened: then the old one stays) -- otherwise nodes, root, depth and ordering
 // viewpoint are put back exactly as they were.  Returns whether the optimised tree was kept.  Host only: no upload, no device.

@@ -8,6 +8,8 @@ struct srt_ctx;
 extern "C" int srt_internal_init_device_params(srt_ctx *c, uint32_t tx, uint32_t ty, uint32_t bx, uint32_t by, uint32_t chunk_w, uint32_t chunk_h,
                                                uint32_t spp, uint32_t bounce_limit, uint64_t seed, int wait);      // not exported (hidden visibility)
 
+// srt_refit_vertices; scanned != 0: the caller has already found every coordinate finite (a communicator scans once for all its contexts)
+extern "C" int srt_internal_refit_vertices(srt_ctx *c, const float *verts, size_t n_tris, int scanned);
 extern "C" uint32_t srt_internal_gather_planes(const srt_ctx *c);      // planes of the context's exchange unit (3 or 9); not exported
 
 namespace srt {
@@ -428,6 +430,26 @@ struct TemporalParams {
     unsigned long long *counts;
 };
 hipError_t launch_temporal(const TemporalParams &p, hipStream_t st);
+// BVH refit (srt_refit.hip; stated in srt_c_api.h at srt_scene_refit and srt_refit_vertices).  verts: 9 floats per triangle.  The topology
+// tables, made on the host at srt_upload_scene: tri_tab two words per triangle -- its raw aa_plane, then its slot 2 f + side, the FRINGE
+// record f (an index into the FRINGE image) and the side whose block holds the triangle's copy, kRefitNoSlot when the root is a leaf; child
+// two references per record (a record index, or ~triangle); sched the record indices grouped by height.  tris, shade, fringe (fringe_stride
+// FLOATS between records), nodes, nodes_sw (null when the plan keeps none): the scene images.  leaf_box / rec_box: six floats per triangle
+// / per record of scratch.  launch_refit_level handles the records sched[first .. first + count): one height.
+constexpr uint32_t kRefitNoSlot = 0xffffffffu;
+struct RefitParams {
+    const float *verts;
+    const uint32_t *tri_tab;
+    const int32_t *child;
+    const uint32_t *sched;
+    float *tris, *shade, *fringe, *nodes, *nodes_sw;
+    float *leaf_box, *rec_box;
+    uint32_t n_tris, n_inner, fringe_stride;
+};
+// *count += the floats of verts[0 .. n_floats) that are not finite
+hipError_t launch_refit_validate(const float *verts, size_t n_floats, uint32_t *count, hipStream_t st);
+hipError_t launch_refit_triangles(const RefitParams &p, hipStream_t st);
+hipError_t launch_refit_level(const RefitParams &p, uint32_t first, uint32_t count, hipStream_t st);
 hipError_t launch_order_tiles(const uint32_t *cost, uint32_t *sorted, uint32_t *rows, uint32_t n, uint32_t n_waves,
                               uint32_t split_load_pct, uint32_t *queue_info, uint32_t order_max_pct, hipStream_t st);
 hipError_t launch_scatter(const ScatterParams &p, hipStream_t st);

@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import binding as B
+from .scene import refit_vertices
 
 DEFAULT_TX, DEFAULT_TY = 28, 16   # render_manager.cu:93-94
 FEATURE_CHANNELS = 8              # first-hit sums per pixel: normal xyz, albedo rgb, distance, hits (srt_c_api.h, srt_accum_reset_features)
@@ -68,6 +69,49 @@ class Renderer:
 
     def set_camera(self, cam):
         self._ck(B.lib().srt_set_camera(self._h, C.byref(cam)))
+
+    def refit(self, vertices):
+        """BVH refit on the device (srt_refit_vertices / srt_refit_vertices_dev): new vertices (n_tris, 3, 3) float32 for the uploaded
+        scene, its topology kept -- no scene build, no upload.  A numpy array goes through the host entry; a torch tensor must live on
+        this renderer's device, be contiguous and float32, and goes through the device-pointer entry without visiting the host (its
+        stream is waited for first).  Shapes and dtypes are checked here, before any device is touched.  Afterwards the accumulation
+        and the temporal history are invalid, as after upload_scene; camera and device parameters stay."""
+        if isinstance(vertices, np.ndarray):
+            v = refit_vertices("Renderer.refit", vertices)
+            self._ck(B.lib().srt_refit_vertices(self._h, B.fptr(v), v.shape[0]))
+            return
+        t = vertices
+        if not all(hasattr(t, a) for a in ("data_ptr", "is_contiguous", "device", "dtype", "shape")):
+            raise TypeError("Renderer.refit: vertices must be a numpy array or a torch tensor (n_tris, 3, 3) float32, got %r" % type(t).__name__)
+        import torch
+        if t.dtype != torch.float32:
+            raise TypeError("Renderer.refit: the tensor must be float32, got %s" % t.dtype)
+        if t.dim() != 3 or tuple(t.shape[1:]) != (3, 3) or t.shape[0] == 0:
+            raise ValueError("Renderer.refit: the tensor must have shape (n_tris, 3, 3) with n_tris >= 1, got %r" % (tuple(t.shape),))
+        if t.device.type != "cuda" or (t.device.index or 0) != self.device:
+            raise ValueError("Renderer.refit: the tensor lives on %s, the renderer on GPU %d" % (t.device, self.device))
+        if not t.is_contiguous():
+            raise ValueError("Renderer.refit: the tensor must be contiguous")
+        torch.cuda.current_stream(t.device).synchronize()      # (the entry works on the NULL stream: the tensor must be complete)
+        self._ck(B.lib().srt_refit_vertices_dev(self._h, C.c_void_p(t.data_ptr()), t.shape[0]))
+
+    def refit_last_ms(self):
+        """kernel-only ms of the context's last refit (srt_refit_last_ms): dict(triangles, levels, n_levels)"""
+        a, b, n = C.c_float(), C.c_float(), C.c_uint32()
+        self._ck(B.lib().srt_refit_last_ms(self._h, C.byref(a), C.byref(b), C.byref(n)))
+        return dict(triangles=a.value, levels=b.value, n_levels=n.value)
+
+    def scene_image(self, which):
+        """read-back of one scene image (srt_read_scene_image; tests and tools): which = "nodes", "nodes_sw", "fringe", "tris" or "shade"
+        -> its words as a uint32 array, empty for an image the launch plan does not keep.  Synchronises, only reads."""
+        if which not in B.SCENE_IMAGES:
+            raise ValueError("scene_image: unknown image %r (%s)" % (which, ", ".join(B.SCENE_IMAGES)))
+        n = C.c_size_t()
+        self._ck(B.lib().srt_read_scene_image(self._h, B.SCENE_IMAGES[which], None, 0, C.byref(n)))
+        out = np.zeros(n.value // 4, np.uint32)
+        if out.size:
+            self._ck(B.lib().srt_read_scene_image(self._h, B.SCENE_IMAGES[which], out.ctypes.data_as(C.c_void_p), out.nbytes, C.byref(n)))
+        return out
 
     def init_device_params(self, chunk_w, chunk_h, spp, bounce_limit, seed=1984, tx=DEFAULT_TX, ty=DEFAULT_TY, bx=None, by=None):
         if bx is None or by is None:
@@ -831,6 +875,11 @@ class Comm:
     def set_camera(self, cam):
         self._ck(B.lib().srt_comm_set_camera(self._h, C.byref(cam)))
 
+    def refit(self, vertices):
+        """Renderer.refit with a numpy array on every local rank (srt_comm_refit_vertices), as upload_scene uploads to them"""
+        v = refit_vertices("Comm.refit", vertices)
+        self._ck(B.lib().srt_comm_refit_vertices(self._h, B.fptr(v), v.shape[0]))
+
     def init_device_params(self, chunk_w, chunk_h, spp, bounce_limit, seed=1984, tx=DEFAULT_TX, ty=DEFAULT_TY, bx=None, by=None):
         if bx is None or by is None:
             bx, by = reference_grid(chunk_w, chunk_h, tx, ty)
@@ -1586,6 +1635,52 @@ def _interactive_frames(scene, cams, width, height, spp, bounce_limit, seed, dev
         r.temporal_reset()
         for k, cam in enumerate(cams):
             r.set_camera(cam)
+            r.accum_reset_features()
+            r.render_chunk_accum(width, height, spp)
+            r.scatter_tiles()
+            picture = r.denoise_temporal(width, height, temporal, despeckle, **cfg) if denoise else r.temporal(width, height, **temporal)
+            yield k, _collect(r, width, height), r.read_features(width, height), picture, picture["stats"]
+
+
+def render_animated(scene, cam, frames, width, height, spp, bounce_limit, denoise=True, despeckle=None, temporal=None, seed=1984, device=0,
+                    renderer=None, **cfg):
+    """Moving geometry on one GPU: the scene is uploaded once; for every vertex array of `frames` ((n_tris, 3, 3) float32: numpy, or a
+    torch tensor on the device -- Renderer.refit) refit, accum_reset_features, one pass of `spp` samples, then the chained presentation
+    call of render_interactive (denoise, despeckle, temporal and cfg are its arguments).  The temporal history is dropped at every refit --
+    the reprojection knows camera motion, not object motion -- so every frame is a first frame to the temporal stage.  A generator of
+    (index, result, features, picture, stats), as render_interactive's.  The scene object itself is not changed.  Everything that can be
+    checked without a device is checked here."""
+    if not isinstance(cam, B.CameraData):
+        raise TypeError("render_animated: cam is no CameraData (camera_init makes one), got %r" % type(cam).__name__)
+    frames = list(frames)
+    if not frames:
+        raise ValueError("render_animated: no frame (give at least one vertex array)")
+    for k, v in enumerate(frames):
+        if isinstance(v, np.ndarray):
+            frames[k] = refit_vertices("render_animated: frames[%d]" % k, v)
+    sched = progressive_schedule([spp])
+    tkw = dict(temporal or {})
+    _temporal_cfg("render_animated", tkw)
+    dkw = None
+    if despeckle is not None:
+        dkw = dict(despeckle)
+        unknown = sorted(set(dkw) - set(_DESPECKLE_KEYS))
+        if unknown:
+            raise TypeError("render_animated: unknown despeckle keyword(s) %s (%s)" % (", ".join(unknown), ", ".join(_DESPECKLE_KEYS)))
+        despeckle_config(**dkw)
+    if denoise:
+        denoise_config(**cfg)
+    elif cfg:
+        raise TypeError("render_animated: %s given with denoise=False, which runs no denoiser" % ", ".join(sorted(cfg)))
+    elif dkw is not None:
+        raise ValueError("render_animated: despeckle given with denoise=False: the firefly filter runs in the denoiser's chain")
+    return _animated_frames(scene, cam, frames, width, height, sched[0], bounce_limit, seed, device, renderer, bool(denoise), dkw, tkw, cfg)
+
+
+def _animated_frames(scene, cam, frames, width, height, spp, bounce_limit, seed, device, renderer, denoise, despeckle, temporal, cfg):
+    with _image_session(scene, cam, width, height, spp, bounce_limit, seed, device, renderer) as r:
+        for k, v in enumerate(frames):
+            r.refit(v)      # (invalidates the accumulation and drops the temporal history, as an upload does)
             r.accum_reset_features()
             r.render_chunk_accum(width, height, spp)
             r.scatter_tiles()

@@ -15,6 +15,17 @@ def camera_init(width, height, vfov, lookfrom, lookat, vup=(0, 1, 0), defocus_an
     return cam
 
 
+def refit_vertices(who, vertices):
+    """the (n, 3, 3) float32 vertex array of a refit, C-contiguous; anything else is refused here, before any library call"""
+    if not isinstance(vertices, np.ndarray):
+        raise TypeError("%s: vertices must be a numpy array (n_tris, 3, 3) float32, got %r" % (who, type(vertices).__name__))
+    if vertices.dtype != np.float32:
+        raise TypeError("%s: vertices must be float32, got %s" % (who, vertices.dtype))
+    if vertices.ndim != 3 or vertices.shape[1:] != (3, 3) or vertices.shape[0] == 0:
+        raise ValueError("%s: vertices must have shape (n_tris, 3, 3) with n_tris >= 1, got %r" % (who, vertices.shape))
+    return np.ascontiguousarray(vertices)
+
+
 class Scene:
     def __init__(self, handle):
         if not handle:
@@ -82,6 +93,30 @@ class Scene:
     def build_bvh(self, mode=B.BVH_REFERENCE, seed=1984):
         B.check(B.lib().srt_scene_build_bvh(self._h, int(mode), int(seed)))
         return self
+
+    def refit(self, vertices):
+        """new vertices on the built topology (srt_scene_refit): vertices (n_tris, 3, 3) float32, v0 v1 v2 of every triangle.  Triangle
+        products, node boxes and depth are recomputed; topology, child order, materials and the stored aa_plane stay.  Upload the scene
+        afterwards, or give the same vertices to Renderer.refit on a renderer that holds it."""
+        v = refit_vertices("Scene.refit", vertices)
+        B.check(B.lib().srt_scene_refit(self._h, B.fptr(v), v.shape[0]))
+        return self
+
+    def vertices(self):
+        """the triangles' vertices as the (n_tris, 3, 3) float32 array refit() takes (a copy)"""
+        t = self.triangles()
+        words = np.frombuffer(t, np.float32).reshape(len(t), C.sizeof(B.TriIn) // 4)      # 9 vertex floats, then mat_index and aa_plane
+        return np.ascontiguousarray(words[:, :9]).reshape(len(t), 3, 3)
+
+    def refit_schedule(self):
+        """the records of every height a device refit of this scene handles in one launch each, bottom up (srt_scene_refit_schedule):
+        a uint32 array, empty when the root is a leaf"""
+        n = C.c_uint32()
+        B.check(B.lib().srt_scene_refit_schedule(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.uint32)
+        if out.size:
+            B.check(B.lib().srt_scene_refit_schedule(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size, C.byref(n)))
+        return out
 
     def optimise_bvh(self, passes=3):
         """insertion-based topology optimisation of the built tree (srt_scene_optimise_bvh): for throughput-bound launches"""

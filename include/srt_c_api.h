@@ -185,6 +185,23 @@ SRT_API int srt_scene_bvh_depth(const srt_scene *s);
 /* Pre-order dump (same convention as the oracle): left/right = pre-order ranks or -1, prim = original
  * triangle index for leaves else -1, boxes = 6 floats per node (xmin xmax ymin ymax zmin zmax). */
 SRT_API int srt_scene_get_bvh(const srt_scene *s, int32_t *left, int32_t *right, int32_t *prim, float *boxes);
+/* BVH refit (no reference counterpart: the reference's world is static): new vertices on the built topology, for geometry that deforms.
+ * verts[n_tris][9] = v0 v1 v2 of every triangle, each xyz.  In this order: the vertices of every triangle are replaced -- its mat_index
+ * and its stored aa_plane are inputs and stay -- and its tri::init products (normal, D, projection plane, winding, padded box) are
+ * recomputed exactly as srt_scene_set_triangles computes them; then every node's box, leaves from their triangle's box and internal nodes
+ * from their children's in one post-order sweep, and the depth, exactly as srt_scene_build_bvh finishes a tree.  Topology, child order, the
+ * ordering viewpoint and the built state are not touched, so the scene equals in every bit one built from the moved triangles with this
+ * topology.  SRT_ERR_INVALID with nothing changed: a null pointer, a BVH that is not built, n_tris != srt_scene_tri_count, a coordinate
+ * that is not finite.  Host only; srt_upload_scene afterwards, or srt_refit_vertices with the same vertices on a context that holds the
+ * scene.  Out of scope: changes of topology and any heuristic for when a tree degraded by motion should be rebuilt (build it again),
+ * motion vectors for moving objects (the temporal stage knows camera motion only), and refit of materials. */
+SRT_API int srt_scene_refit(srt_scene *s, const float *verts, size_t n_tris);
+/* The level schedule a refit of this scene runs on the device (tests and tools; host only): *n_levels receives the number of record
+ * heights -- height = 1 + the largest height of a child record, a leaf child counting 0; 0 when the root is a leaf -- and
+ * level_counts[k], when not NULL (cap >= *n_levels, else SRT_ERR_INVALID), the records of height k + 1, one level launch each, bottom up.
+ * Record indices do not order parents and children (every INNER record precedes every FRINGE record, and a FRINGE node may have an INNER
+ * child), so the heights come from a walk over the references.  SRT_ERR_INVALID for a null argument or a BVH that is not built. */
+SRT_API int srt_scene_refit_schedule(const srt_scene *s, uint32_t *level_counts, size_t cap, uint32_t *n_levels);
 
 /* ---------------------------------------------------------------------------------------------------
  * Device side.  Replaces `renderer` (rendering/rendering.cuh:39-155) + the device half of
@@ -198,6 +215,41 @@ SRT_API const char *srt_last_error(const srt_ctx *ctx);   /* ctx may be NULL: la
 /* Uploads triangles, paired-child BVH records, material spectra and background to HBM
  * (replaces the device-heap world behind bvh** / material*, scene.cuh:163-170).  The BVH must be built. */
 SRT_API int srt_upload_scene(srt_ctx *ctx, const srt_scene *s);
+/* BVH refit on the device (srt_refit.hip; no reference counterpart): srt_scene_refit's operation applied to the scene images a context
+ * holds, without a scene build or an upload.  The images are a function of the vertices and the topology alone; the topology -- record
+ * order, references, root, stack depth, pairedness, launch plan, LDS residency and kernel variant -- stays, so only these are rewritten:
+ * the triangle records, words 0 .. 2 (the normal) of every shading record, every triangle's inline copy in its FRINGE block (flag bits
+ * included, the reference word kept), the children's boxes in every INNER record (and in its pre-swizzled copy where the plan keeps one)
+ * and the box words of internal children in FRINGE records, at either FRINGE stride (padding words stay +0).
+ *   Order.  (1) srt_refit_vertices_dev only: a kernel counts the coordinates that are not finite and the count is read back.  (2) One
+ * thread per triangle restates tri::init operation by operation -- the cross product, the division by the length with the host's order of
+ * sums, D, the perpendicularity tests with the three-term dots, the plane choice, the signed area, the padded box.  (3) Records are grouped
+ * by height (1 + the largest height of a child record, a leaf child counting 0); one launch per height, bottom up, one thread per record,
+ * writes the children's boxes and keeps the record's own box, the union taken as (left, right), for the launch above.
+ *   Value equality.  The device takes minima and maxima as a compare and a select, (b < a) ? b : a and (b > a) ? b : a, where the host
+ * calls fminf / fmaxf: they agree on all finite inputs except for the sign of a zero when +0 meets -0, and a degenerate triangle's NaN
+ * normal may carry other bits than the host's.  The images therefore equal those srt_upload_scene makes of the host-refitted scene AS
+ * VALUES: two words are equal when their bits are equal, or both are NaN, or both are zero.  Ray hits and frames are bit-identical.
+ *   A successful refit invalidates what srt_upload_scene invalidates -- the accumulation (the next pass fails until a reset), the temporal
+ * history, the scheduler's remembered queues -- and leaves camera, device parameters, partition, knobs and RNG state alone.  Both entries
+ * work on the NULL stream under the order of a context's calls, and both synchronise.  verts_dev is a device pointer (a torch tensor's
+ * data_ptr(), say) whose contents must be complete, or ordered before the NULL stream, when the call is made.
+ *   Refused with SRT_ERR_INVALID and nothing changed on the device: no scene uploaded (srt_set_test_knobs ends an upload too), a null
+ * pointer, n_tris other than the uploaded scene's, a coordinate that is not finite -- nothing changed means the scene images and the
+ * context's state; a refused srt_refit_vertices_dev may have allocated the context's scratch block, which the validation kernel counts
+ * into.  A failed allocation: SRT_ERR_HIP.  The topology
+ * tables are made on the host at srt_upload_scene and reach the device with the first refit; srt_upload_scene itself enqueues and
+ * allocates nothing for them.  Out of scope as at srt_scene_refit: topology changes, object motion vectors, materials.
+ *   srt_refit_last_ms     kernel-only times in ms, from HIP events, of the context's last refit: the triangle kernel, all level launches
+ *                         together, and their number.  Any pointer may be NULL.  SRT_ERR_INVALID before a refit has run.
+ *   srt_read_scene_image  read-back of one scene image for tests and tools; synchronises, only reads.  *n_bytes receives the image's size
+ *                         (0 for an image the plan does not keep: SRT_IMAGE_NODES_SW of an LDS-resident tree); out may be NULL to ask
+ *                         for the size alone, else cap_bytes must hold it (SRT_ERR_INVALID). */
+enum { SRT_IMAGE_NODES = 0, SRT_IMAGE_NODES_SW = 1, SRT_IMAGE_FRINGE = 2, SRT_IMAGE_TRIS = 3, SRT_IMAGE_SHADE = 4 };
+SRT_API int srt_refit_vertices(srt_ctx *ctx, const float *verts_host, size_t n_tris);
+SRT_API int srt_refit_vertices_dev(srt_ctx *ctx, const float *verts_dev, size_t n_tris);
+SRT_API int srt_refit_last_ms(srt_ctx *ctx, float *tri_ms, float *levels_ms, uint32_t *n_levels);
+SRT_API int srt_read_scene_image(srt_ctx *ctx, int which, void *out, size_t cap_bytes, size_t *n_bytes);
 /* renderer::assign_cam_data, rendering/rendering.cu:237-242 */
 SRT_API int srt_set_camera(srt_ctx *ctx, const srt_camera_data *cam);
 /* What the render launch of the uploaded scene looks like (diagnostics / measurement bookkeeping): persistent waves per CU, inner
@@ -244,7 +296,7 @@ SRT_API int srt_set_partition(srt_ctx *ctx, uint32_t rank, uint32_t world);
  * context in flight on any stream, and the remembered stream is not touched again after them, so it may be destroyed -- are
  * srt_synchronize; every read-back (srt_read_fb, srt_read_fb_aux, srt_read_fb_rowmajor, srt_read_accum_stats, srt_read_spectral,
  * srt_read_features, srt_accum_active on a bound accumulation, srt_get_stats, srt_get_tile_costs, srt_get_wave_debug,
- * srt_read_tile_schedule); every stage call that returns host data (srt_meter_*, srt_expose_*, srt_develop_*, srt_despeckle_*,
+ * srt_read_tile_schedule, srt_read_scene_image); srt_refit_vertices and srt_refit_vertices_dev; every stage call that returns host data (srt_meter_*, srt_expose_*, srt_develop_*, srt_despeckle_*,
  * srt_temporal_*, srt_denoise_*, srt_present* -- not their *_last_ms timing queries, which wait for their own events alone);
  * srt_init_device_params and every srt_accum_reset*.  srt_comm_synchronize waits for the
  * communicator's own streams only and is none of them; srt_comm_destroy synchronises every context before it destroys those streams.
@@ -1145,6 +1197,8 @@ SRT_API srt_ctx *srt_comm_root_ctx(srt_comm *comm);            /* rank 0's conte
 /* srt_upload_scene / srt_set_camera / srt_init_device_params on every local context (the scene is replicated). */
 SRT_API int srt_comm_upload_scene(srt_comm *comm, const srt_scene *s);
 SRT_API int srt_comm_set_camera(srt_comm *comm, const srt_camera_data *cam);
+/* srt_refit_vertices on every local context, as srt_comm_upload_scene uploads to them. */
+SRT_API int srt_comm_refit_vertices(srt_comm *comm, const float *verts_host, size_t n_tris);
 SRT_API int srt_comm_init_device_params(srt_comm *comm, uint32_t tx, uint32_t ty, uint32_t bx, uint32_t by, uint32_t chunk_w,
                                         uint32_t chunk_h, uint32_t spp, uint32_t bounce_limit, uint64_t seed);
 /* renderer::render(w,h,offx,offy) on W GPUs: render kernels on every local rank's stream, one ncclGather of the tile
