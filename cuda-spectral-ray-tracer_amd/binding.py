@@ -130,7 +130,7 @@ class TreeTuning(C.Structure):
     """srt_tree_tuning: what srt_tune_tree_for_throughput found and did (srt_c_api.h)"""
     _fields_ = [("pixels_per_lane", C.c_double), ("throughput_bound", C.c_uint32), ("reinsertion", C.c_uint32),
                 ("probe_width", C.c_uint32), ("probe_height", C.c_uint32), ("probe_spp", C.c_uint32), ("nodes_swapped", C.c_uint32),
-                ("order_status", C.c_int32)]
+                ("order_status", C.c_int32), ("segments", C.c_uint32)]
 
 
 class TileScheduleInfo(C.Structure):
@@ -178,6 +178,8 @@ PROTOTYPES = {
     "srt_scene_build_bvh": (_i, [_vp, _i, _u64]),
     "srt_scene_order_children": (_i, [_vp, _fp]),
     "srt_scene_optimise_bvh": (_i, [_vp, C.c_int]),
+    "srt_scene_optimise_bvh_for_rays": (_i, [_vp, C.c_int, _fp, _sz]),
+    "srt_scene_bvh_ray_cost": (_i, [_vp, _fp, _sz, C.POINTER(C.c_double)]),
     "srt_scene_is_paired": (_i, [_vp]),
     "srt_scene_node_count": (_sz, [_vp]),
     "srt_scene_bvh_depth": (_i, [_vp]),
@@ -267,6 +269,8 @@ PROTOTYPES = {
     "srt_order_children_by_profile": (_i, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "srt_pixels_per_lane": (_i, [_vp, _u32, _u32, _u32, C.POINTER(C.c_double)]),
     "srt_tune_tree_for_throughput": (_i, [_vp, _vp, _u32, _u32, _u32, _u32, _i, C.POINTER(TreeTuning)]),
+    "srt_tune_tree_with_segments": (_i, [_vp, _vp, _u32, _u32, _u32, _u32, _i, _fp, _sz, C.POINTER(TreeTuning)]),
+    "srt_collect_ray_segments": (_i, [_vp, _u32, _u32, _u32, _u32, _u32, _u64, _fp, _sz, C.POINTER(_sz), C.POINTER(_u64)]),
     "srt_get_stats": (_i, [_vp, C.POINTER(Stats)]),
     "srt_set_count_traversal": (_i, [_vp, _i]),
     "srt_get_wave_debug": (_i, [_vp, C.POINTER(C.c_uint32), _sz]),

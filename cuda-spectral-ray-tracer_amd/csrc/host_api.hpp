@@ -146,11 +146,15 @@ public:
         if (srt_tune_tree_for_throughput(probe, s, (uint32_t)xr, (uint32_t)yr, (uint32_t)(n_gpus < 1 ? 1 : n_gpus), bounce_limit, 1, &t) == SRT_OK) {
             if (!t.throughput_bound) what = "tree as built (chain-bound launch: fewer than 6 pixels per lane)";
             else {
-                what = t.reinsertion == 1 ? "3 reinsertion passes; " : t.reinsertion == 2 ? "reinsertion undone (the deeper tree would no longer be LDS resident); " : "";
+                what = t.reinsertion == 1 ? std::string("3 reinsertion passes; ") : t.reinsertion == 2 ? "reinsertion undone (the deeper tree would no longer be LDS resident); " :
+                       t.reinsertion == 3 ? "3 reinsertion passes; " :
+                       t.reinsertion == 4 ? "ray-weighted reinsertion vetoed (the sampled frame's work counters did not fall); " :
+                       t.reinsertion == 5 ? "no usable ray segment in the sample; " : "";
                 if (t.order_status != SRT_OK) what += std::string("child order not profiled: ") + srt_last_error(probe);
                 else what += (t.nodes_swapped ? "child order profiled (" + std::to_string(t.probe_width) + "x" + std::to_string(t.probe_height) + " x " + std::to_string(t.probe_spp) +
                                                     " spp probe): " + std::to_string(t.nodes_swapped) + " nodes swapped"
                                               : std::string("builder's child order kept"));
+                if (t.reinsertion == 3) what += "; reinsertion priced by " + std::to_string(t.segments) + " sampled ray segments";
             }
         }
         srt_destroy(probe);

@@ -2,11 +2,13 @@
 // (replaces `renderer`, rendering/rendering.cuh:39-155, and the device half of render_manager::step).
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstddef>
 #include <string>
@@ -560,7 +562,7 @@ int bind_wave_debug(srt_ctx *c, const Pass &ps, RenderParams &p) {
     HIP_TRY(c, c->d_wave_debug.reserve(wave_debug_bytes(most_waves)));
     HIP_TRY(c, hipMemsetAsync(c->d_wave_debug.ptr, 0, c->d_wave_debug.bytes, ps.st));
     p.wave_debug = c->d_wave_debug.as<uint32_t>();
-    if (c->order_profile.magic == kOrderProfileMagic)
+    if (c->order_profile.magic == kOrderProfileMagic || c->order_profile.seg != nullptr)
         HIP_TRY(c, hipMemcpyAsync(c->d_wave_debug.ptr, &c->order_profile, sizeof(OrderProfile), hipMemcpyHostToDevice, ps.st));
     return SRT_OK;
 }
@@ -3040,29 +3042,159 @@ int srt_pixels_per_lane(const srt_ctx *c, uint32_t width, uint32_t height, uint3
     return SRT_OK;
 }
 
+// One instrumented frame of the context's camera and uploaded scene on this context alone, as srt_order_children_by_profile's probe frames
+// are rendered (the reference's grid; partition and counter setting restored afterwards; srt_init_device_params comes next).  segs != null:
+// the frame samples its closest-hit queries (OrderProfile::seg, srt_internal.h) and *segs receives the sampled segments, 7 floats each, in
+// canonical order -- ascending by the bit patterns of their seven words, so that the array does not depend on the order in which the waves
+// took their tickets.  work (optional): node records + 2 x triangle tests of the frame.
+static int segment_frame(srt_ctx *c, uint32_t width, uint32_t height, uint32_t spp, uint32_t bounce_limit, uint32_t stride, uint32_t phase,
+                         size_t capacity, std::vector<float> *segs, uint64_t *n_queries, unsigned long long *work) {
+    const char *what = "srt_collect_ray_segments: device buffers";
+    // a launch draws at most one query per path and bounce: the tickets fit 32 bits, and so does ticket + phase
+    const unsigned long long most_queries = (unsigned long long)width * height * spp * std::max<uint32_t>(bounce_limit, 1u);
+    if (most_queries + stride >= (1ull << 32)) return fail(c, SRT_ERR_INVALID, "srt_collect_ray_segments: the frame may cast 2^32 queries or more");
+    const size_t slots = segs ? (size_t)std::min<unsigned long long>(capacity, most_queries / stride + 1) : 0;
+    HIP_TRY(c, set_device(c));
+    DeviceBuffer d_seg, d_tickets;      // (the frame's c->order_profile points at them: cleared before this function returns)
+    if (segs) {
+        HIP_TRY_AS(c, what, d_seg.reserve(std::max<size_t>(slots, 1) * 2 * sizeof(float4)));
+        HIP_TRY_AS(c, what, d_tickets.reserve(4 * sizeof(uint32_t)));
+        HIP_TRY_AS(c, what, hipMemset(d_tickets.ptr, 0, 4 * sizeof(uint32_t)));
+    }
+    const bool counting = c->count_traversal;
+    const uint32_t rank = c->rank, world = c->world;
+    const uint32_t tx = 28, ty = 16, bx = width / tx + 1, by = height / ty + 1;      // the reference's grid (render_manager.cu:84-94)
+    c->order_profile = OrderProfile{};
+    if (segs) {
+        c->order_profile.seg = d_seg.as<float4>(); c->order_profile.seg_tickets = d_tickets.as<uint32_t>();
+        c->order_profile.seg_stride = stride; c->order_profile.seg_phase = phase; c->order_profile.seg_capacity = slots;
+    }
+    c->count_traversal = true; c->rank = 0; c->world = 1;
+    int r = srt_init_device_params(c, tx, ty, bx, by, width, height, spp, bounce_limit, SRT_DEFAULT_SEED);
+    if (r == SRT_OK) r = srt_render_chunk(c, width, height, 0, 0, nullptr);
+    if (r == SRT_OK) r = srt_synchronize(c);
+    c->count_traversal = counting; c->rank = rank; c->world = world;
+    c->order_profile = OrderProfile{};
+    c->params_ready = false;      // (the frame's RNG state and grid are not the caller's: srt_init_device_params comes next)
+    if (r != SRT_OK) return r;
+    unsigned long long h[kCounters];
+    HIP_TRY_AS(c, "srt_collect_ray_segments: counters", hipMemcpy(h, c->d_counters.ptr, sizeof(h), hipMemcpyDeviceToHost));
+    if (work) *work = h[1] + 2ull * h[2];
+    if (!segs) return SRT_OK;
+    uint32_t tickets = 0;
+    HIP_TRY_AS(c, "srt_collect_ray_segments: read back", hipMemcpy(&tickets, d_tickets.ptr, sizeof(tickets), hipMemcpyDeviceToHost));
+    if (n_queries) *n_queries = tickets;
+    // sampled tickets: t in [0, tickets) with (t + phase) % stride == 0
+    const unsigned long long sampled = tickets ? ((unsigned long long)tickets - 1 + phase) / stride - (phase ? 1 : 0) + 1 : 0;
+    const size_t n = (size_t)std::min<unsigned long long>(sampled, slots);
+    std::vector<float> raw(8 * n);
+    if (n) HIP_TRY_AS(c, "srt_collect_ray_segments: read back", hipMemcpy(raw.data(), d_seg.ptr, raw.size() * sizeof(float), hipMemcpyDeviceToHost));
+    std::vector<std::array<uint32_t, kSegmentFloats>> rows(n);
+    for (size_t k = 0; k < n; k++) memcpy(rows[k].data(), &raw[8 * k], kSegmentFloats * sizeof(float));
+    std::sort(rows.begin(), rows.end());
+    segs->resize(kSegmentFloats * n);
+    for (size_t k = 0; k < n; k++) memcpy(&(*segs)[kSegmentFloats * k], rows[k].data(), kSegmentFloats * sizeof(float));
+    return SRT_OK;
+}
+
+int srt_collect_ray_segments(srt_ctx *c, uint32_t width, uint32_t height, uint32_t spp, uint32_t bounce_limit, uint32_t stride, uint64_t seed,
+                             float *segments, size_t capacity, size_t *n_segments, uint64_t *n_queries) {
+    if (n_segments) *n_segments = 0;
+    if (n_queries) *n_queries = 0;
+    if (!c || !n_segments || (!segments && capacity)) return fail(c, SRT_ERR_INVALID, "srt_collect_ray_segments: null argument");
+    c->accum.invalidate();
+    if (!c->scene_ready || !c->camera_ready) return fail(c, SRT_ERR_INVALID, "srt_collect_ray_segments: upload a scene and set the camera first");
+    if (width == 0 || height == 0 || spp == 0 || stride == 0) return fail(c, SRT_ERR_INVALID, "srt_collect_ray_segments: empty frame / stride 0");
+    std::vector<float> segs;
+    const int rc = segment_frame(c, width, height, spp, bounce_limit, stride, (uint32_t)(seed % stride), capacity, &segs, n_queries, nullptr);
+    if (rc != SRT_OK) return rc;
+    *n_segments = segs.size() / kSegmentFloats;
+    if (!segs.empty()) memcpy(segments, segs.data(), segs.size() * sizeof(float));
+    return SRT_OK;
+}
+
 // The throughput tree-tuning recipe (include/srt_c_api.h): every constant of it, once.
 static constexpr double kTunePixelsPerLane = 6.0;        // fewer: the launch is bound by its longest pixel chain and keeps the tree as built
 static constexpr size_t kTuneReinsertionMaxTris = 8192;  // larger trees: measured no gain from reinsertion
 static constexpr int kTuneReinsertionPasses = 3;         // (they converge)
 static constexpr uint32_t kTuneProbeDivisor = 4, kTuneProbeMinSide = 32, kTuneProbeSpp = 8;      // probe frame: a quarter of the frame's size, 8 spp
 static constexpr uint32_t kTuneDecidingRays = 16;        // a node's children are re-ordered from at least this many deciding rays
+// the ray-weighted reinsertion of a throughput-bound launch: every query of a 1 spp frame at a twelfth of the frame's size (stride 1: the set
+// does not depend on the waves' order), thinned evenly to 2048 segments in canonical order (the host time is linear in passes x segments:
+// profiles/tree_rays/)
+static constexpr uint32_t kTuneSegmentDivisor = 12, kTuneSegmentSpp = 1;
+static constexpr size_t kTuneSegments = 2048;
 
-int srt_tune_tree_for_throughput(srt_ctx *c, srt_scene *s, uint32_t width, uint32_t height, uint32_t world, uint32_t bounce_limit,
-                                 int only_if_throughput_bound, srt_tree_tuning *out) {
-    if (out) memset(out, 0, sizeof(*out));
-    if (!c || !s || !out || !s->bvh_valid || width == 0 || height == 0)
-        return fail(c, SRT_ERR_INVALID, "srt_tune_tree_for_throughput: null argument / BVH not built / empty frame");
+static int tune_tree(srt_ctx *c, srt_scene *s, uint32_t width, uint32_t height, uint32_t world, uint32_t bounce_limit, int only_if_throughput_bound,
+                     const float *user_segments, size_t n_user_segments, bool sample_given, srt_tree_tuning *out) {
     int rc = srt_upload_scene(c, s);
     if (rc == SRT_OK) rc = srt_pixels_per_lane(c, width, height, world, &out->pixels_per_lane);
     if (rc != SRT_OK) return rc;
     out->throughput_bound = out->pixels_per_lane >= kTunePixelsPerLane ? 1u : 0u;
     if (only_if_throughput_bound && !out->throughput_bound) return SRT_OK;
-    if (s->raw.size() <= kTuneReinsertionMaxTris) {
-        // (reinsertion may deepen the tree: deeper LDS stacks, fewer cached records -- a tree that just fitted LDS no longer does, which
-        // costs far more than the passes return.  The plan is a host function of the flattened tree: nothing is uploaded to decide)
-        auto resident = [&](const FlatScene &f) { LaunchPlan lp; render_launch_plan(f.stack_depth, f.n_records, f.n_inner, c->knobs, lp); return lp.all_cached; };
-        const bool kept = optimise_bvh_unless(*s, kTuneReinsertionPasses, [&](const FlatScene &before, const FlatScene &after) { return !(resident(before) && !resident(after)); });
-        out->reinsertion = kept ? 1u : 2u;
+    // (reinsertion may deepen the tree: deeper LDS stacks, fewer cached records -- a tree that just fitted LDS no longer does, which
+    // costs far more than the passes return.  The plan is a host function of the flattened tree: nothing is uploaded to decide)
+    auto resident = [&](const FlatScene &f) { LaunchPlan lp; render_launch_plan(f.stack_depth, f.n_records, f.n_inner, c->knobs, lp); return lp.all_cached; };
+    auto stays_resident = [&](const FlatScene &before, const FlatScene &after) { return !(resident(before) && !resident(after)); };
+    if (s->raw.size() <= kTuneReinsertionMaxTris && !out->throughput_bound) {
+        // asked for a launch that is bound by its longest pixel: box areas, as ever (no sample of total work is taken for it)
+        out->reinsertion = optimise_bvh_unless(*s, kTuneReinsertionPasses, stays_resident) ? 1u : 2u;
+    } else if (s->raw.size() <= kTuneReinsertionMaxTris) {
+        // throughput-bound: the passes count the frame's own queries.  Frame 1 (the tree that walked in) samples them and sets the work to
+        // beat; frame 2 (the new tree, same frame) must come out cheaper, or the tree that walked in is put back.
+        const uint32_t sw = std::max(width / kTuneSegmentDivisor, kTuneProbeMinSide), sh = std::max(height / kTuneSegmentDivisor, kTuneProbeMinSide);
+        srt_camera_data seg_cam{};
+        rc = srt_scene_default_camera(s, (int)sw, (int)sh, &seg_cam);
+        if (rc == SRT_OK) rc = srt_set_camera(c, &seg_cam);
+        else fail(c, rc, global_error());
+        std::vector<float> all, segs;
+        unsigned long long work_before = 0, work_after = 0;
+        if (rc == SRT_OK) {
+            c->accum.invalidate();
+            const size_t cap = (size_t)sw * sh * kTuneSegmentSpp * std::max<uint32_t>(bounce_limit, 1u);
+            rc = segment_frame(c, sw, sh, kTuneSegmentSpp, bounce_limit, 1, 0, cap, sample_given ? nullptr : &all, nullptr, &work_before);
+        }
+        if (rc == SRT_OK) {
+            const float *src = sample_given ? user_segments : all.data();
+            const size_t n_src = sample_given ? n_user_segments : all.size() / kSegmentFloats, n_use = std::min(n_src, kTuneSegments);
+            segs.resize(kSegmentFloats * n_use);
+            for (size_t k = 0; k < n_use; k++)      // evenly through the canonical order
+                memcpy(&segs[kSegmentFloats * k], src + kSegmentFloats * (size_t)((unsigned long long)k * n_src / n_use), kSegmentFloats * sizeof(float));
+            out->segments = (uint32_t)usable_ray_segments(segs.data(), n_use);
+            if (out->segments == 0) {
+                out->reinsertion = 5u;      // nothing measured: the topology is not touched
+            } else {
+                const std::vector<BvhNode> nodes = s->nodes;
+                const int32_t root = s->root;
+                const int depth = s->depth;
+                const bool has_order_eye = s->has_order_eye;
+                float order_eye[3];
+                memcpy(order_eye, s->order_eye, sizeof(order_eye));
+                // the measured objective likes deeper trees than box areas do: the passes take no position that would push the stack bound
+                // past the deepest one this tree's launch plan still keeps LDS resident (stays_resident keeps the last word)
+                int max_internal_depth = INT_MAX;
+                FlatScene flat;
+                if (flatten_scene(*s, flat) == SRT_OK && resident(flat)) {
+                    int d = flat.stack_depth;
+                    auto resident_at = [&](int stack_depth) { LaunchPlan lp; render_launch_plan(stack_depth, flat.n_records, flat.n_inner, c->knobs, lp); return lp.all_cached; };
+                    while (d < 1024 && resident_at(d + 1)) d++;
+                    max_internal_depth = d + 1;      // (the last internal node of a path has a leaf child and needs no stack slot)
+                }
+                if (!optimise_bvh_unless(*s, kTuneReinsertionPasses, stays_resident, segs.data(), n_use, max_internal_depth)) {
+                    out->reinsertion = 2u;
+                } else {
+                    rc = srt_upload_scene(c, s);
+                    if (rc == SRT_OK) rc = segment_frame(c, sw, sh, kTuneSegmentSpp, bounce_limit, 1, 0, 0, nullptr, nullptr, &work_after);
+                    out->reinsertion = 3u;
+                    if (rc != SRT_OK || work_after >= work_before) {      // the veto: the work counters of the same frame did not fall
+                        s->nodes = nodes; s->root = root; s->depth = depth; s->has_order_eye = has_order_eye;
+                        memcpy(s->order_eye, order_eye, sizeof(order_eye));
+                        out->reinsertion = 4u;
+                    }
+                }
+            }
+        }
+        if (rc != SRT_OK) { out->order_status = rc; return SRT_OK; }
     }
     const uint32_t pw = std::max(width / kTuneProbeDivisor, kTuneProbeMinSide), ph = std::max(height / kTuneProbeDivisor, kTuneProbeMinSide);
     srt_camera_data probe_cam{};
@@ -3074,6 +3206,22 @@ int srt_tune_tree_for_throughput(srt_ctx *c, srt_scene *s, uint32_t width, uint3
     } else fail(c, rc, global_error());      // (the scene's message, where the front ends look for it)
     out->order_status = rc;
     return SRT_OK;
+}
+
+int srt_tune_tree_for_throughput(srt_ctx *c, srt_scene *s, uint32_t width, uint32_t height, uint32_t world, uint32_t bounce_limit,
+                                 int only_if_throughput_bound, srt_tree_tuning *out) {
+    if (out) memset(out, 0, sizeof(*out));
+    if (!c || !s || !out || !s->bvh_valid || width == 0 || height == 0)
+        return fail(c, SRT_ERR_INVALID, "srt_tune_tree_for_throughput: null argument / BVH not built / empty frame");
+    return tune_tree(c, s, width, height, world, bounce_limit, only_if_throughput_bound, nullptr, 0, false, out);
+}
+
+int srt_tune_tree_with_segments(srt_ctx *c, srt_scene *s, uint32_t width, uint32_t height, uint32_t world, uint32_t bounce_limit,
+                                int only_if_throughput_bound, const float *segments, size_t n_segments, srt_tree_tuning *out) {
+    if (out) memset(out, 0, sizeof(*out));
+    if (!c || !s || !out || !s->bvh_valid || width == 0 || height == 0 || (!segments && n_segments))
+        return fail(c, SRT_ERR_INVALID, "srt_tune_tree_with_segments: null argument / BVH not built / empty frame");
+    return tune_tree(c, s, width, height, world, bounce_limit, only_if_throughput_bound, segments, n_segments, true, out);
 }
 
 int srt_set_count_traversal(srt_ctx *c, int on) {

@@ -7,6 +7,7 @@
 
 #include <math.h>
 #include <float.h>
+#include <limits.h>
 #include <string.h>
 
 #include <algorithm>
@@ -217,9 +218,98 @@ bool tree_is_paired(const srt_scene &s) {
     return true;
 }
 
-static void optimise_bvh_by_reinsertion(srt_scene &s, int passes) {
+// The rays a tree is tuned against (srt_scene_optimise_bvh_for_rays): closest-hit queries as segments (origin, direction, t_end), t_end
+// the closest hit or the query's upper limit.  A segment MEETS a box when the traversal's box test passes for it with closest_so_far =
+// t_end: e = max(0, near planes), m = min(far planes), !(min(t_end, m) <= e) -- a box beyond the hit costs the query nothing.  Segments
+// with a NaN or infinite origin, a NaN or all-zero direction or a t_end that is not positive are left out (the GPU never walks the tree
+// for a NaN direction, and a segment without length meets nothing).
+struct RaySample {
+    struct Seg { float o[3], inv[3], t; };
+    std::vector<Seg> segs;
+    std::vector<uint32_t> all;      // 0 .. segs.size() - 1
+    RaySample(const float *data, size_t n) {
+        for (size_t k = 0; data && k < n; k++) {
+            const float *f = data + 7 * k;
+            bool ok = std::isfinite(f[0]) && std::isfinite(f[1]) && std::isfinite(f[2]) && f[6] > 0.0f;
+            ok = ok && !std::isnan(f[3]) && !std::isnan(f[4]) && !std::isnan(f[5]) && !(f[3] == 0.0f && f[4] == 0.0f && f[5] == 0.0f);
+            if (!ok) continue;
+            Seg g;
+            for (int a = 0; a < 3; a++) { g.o[a] = f[a]; g.inv[a] = 1.0f / f[3 + a]; }      // aabb.cu:17, as the kernel hoists it
+            g.t = f[6];
+            segs.push_back(g);
+        }
+        all.resize(segs.size());
+        for (size_t k = 0; k < all.size(); k++) all[k] = (uint32_t)k;
+    }
+    bool empty() const { return segs.empty(); }
+    bool meets(uint32_t k, const float *b) const {
+        const Seg &g = segs[k];
+        const float x0 = (b[0] - g.o[0]) * g.inv[0], x1 = (b[1] - g.o[0]) * g.inv[0];
+        const float y0 = (b[2] - g.o[1]) * g.inv[1], y1 = (b[3] - g.o[1]) * g.inv[1];
+        const float z0 = (b[4] - g.o[2]) * g.inv[2], z1 = (b[5] - g.o[2]) * g.inv[2];
+        // (selects, not fminf / fmaxf: a NaN -- 0 x inf, an origin on a slab's plane of a ray that runs along it -- drops out of e and m
+        // as it does there, and this test is most of the optimiser's time)
+        const float nx = x0 < x1 ? x0 : x1, fx = x0 < x1 ? x1 : x0, ny = y0 < y1 ? y0 : y1, fy = y0 < y1 ? y1 : y0, nz = z0 < z1 ? z0 : z1, fz = z0 < z1 ? z1 : z0;
+        float e = 0.0f, m = g.t;
+        e = nx > e ? nx : e; e = ny > e ? ny : e; e = nz > e ? nz : e;
+        m = fx < m ? fx : m; m = fy < m ? fy : m; m = fz < m ? fz : m;
+        return !(m <= e);
+    }
+    // dst = the segments of src (ascending) that meet the box; a box inside another one is met only by segments that meet the outer one,
+    // so a node's list is filtered from its parent's
+    void filter(const std::vector<uint32_t> &src, const float *box, std::vector<uint32_t> &dst) const {
+        dst.resize(src.size());      // (compaction without a branch on the test's outcome, which is as good as random)
+        size_t n = 0;
+        for (uint32_t k : src) { dst[n] = k; n += meets(k, box) ? 1u : 0u; }
+        dst.resize(n);
+    }
+};
+
+size_t usable_ray_segments(const float *segments, size_t n_segments) { return RaySample(segments, n_segments).segs.size(); }
+
+// Price of one sampled segment against box areas: a box costs area + mu x (segments that meet it), mu = kRayWeight x area(root box) /
+// segments.  area / area(root) is the chance that a uniformly random line through the scene meets the box, segments met / segments the
+// measured chance for the frame's own queries, so kRayWeight is the weight of the measurement against the prior; the prior keeps a
+// region no sample reached from degenerating and breaks ties between positions no segment tells apart.  4: the headline frame has two
+// plateaus, 0.25 .. 4 and 16 .. 1024; the second walks 2.4 % less (V + 2 T) and renders 0.9 ms SLOWER (profiles/tree_rays/weights.txt).
+// SRT_BVH_RAY_WEIGHT overrides (experiments).
+static double ray_weight() { return getenv("SRT_BVH_RAY_WEIGHT") ? std::max(0.0, atof(getenv("SRT_BVH_RAY_WEIGHT"))) : 4.0; }
+static double fringe_weight() { return getenv("SRT_BVH_FRINGE_WEIGHT") ? std::max(1.0, atof(getenv("SRT_BVH_FRINGE_WEIGHT"))) : 2.5; }
+static double box_area(const float *b) { const double dx = (double)b[1] - b[0], dy = (double)b[3] - b[2], dz = (double)b[5] - b[4]; return 2.0 * (dx * dy + dy * dz + dz * dx); }
+
+// The objective of optimise_bvh_by_reinsertion for a tree and a sample: the sum over the internal nodes of price x visit cost (FRINGE weight
+// for a node with a leaf child, 1 otherwise).
+double tree_ray_cost(const srt_scene &s, const float *segments, size_t n_segments) {
+    if (s.root < 0 || s.nodes.empty()) return 0.0;
+    const RaySample rays(segments, n_segments);
+    const double cf = fringe_weight();
+    const double mu = rays.empty() ? 0.0 : ray_weight() * box_area(s.nodes[s.root].box) / (double)rays.segs.size();
+    struct Item { int32_t node; std::vector<uint32_t> met; };
+    std::vector<Item> st;
+    st.push_back({s.root, {}});
+    rays.filter(rays.all, s.nodes[s.root].box, st.back().met);
+    double sum = 0.0;
+    while (!st.empty()) {
+        Item it = std::move(st.back()); st.pop_back();
+        const BvhNode &nd = s.nodes[it.node];
+        if (nd.prim >= 0) continue;
+        const bool leafy = s.nodes[nd.left].prim >= 0 || s.nodes[nd.right].prim >= 0;
+        sum += (box_area(nd.box) + mu * (double)it.met.size()) * (leafy ? cf : 1.0);
+        for (int32_t ch : {nd.left, nd.right}) {
+            if (s.nodes[ch].prim >= 0) continue;
+            st.push_back({ch, {}});
+            rays.filter(it.met, s.nodes[ch].box, st.back().met);
+        }
+    }
+    return sum;
+}
+
+// max_internal_depth: no position is taken that would put more internal nodes on a root-to-leaf path (INT_MAX: no limit).  The last
+// internal node of every path has a leaf child, so the INNER nodes of a path -- the traversal's stack bound -- are at most that minus one.
+static void optimise_bvh_by_reinsertion(srt_scene &s, int passes, const RaySample &rays, int max_internal_depth) {
     const int32_t n = (int32_t)s.nodes.size();
     if (passes <= 0 || n < 7) return;
+    const bool sampled = !rays.empty();
     // renumber: parents before children, the two children of a node next to each other (what the builders produce and
     // finish_boxes_and_depth relies on)
     auto renumber = [&](int32_t from_root) {
@@ -255,11 +345,34 @@ static void optimise_bvh_by_reinsertion(srt_scene &s, int passes) {
     std::vector<int32_t> parent(n, -1);
     for (int32_t k = 0; k < n; k++)
         if (s.nodes[k].prim < 0) { parent[s.nodes[k].left] = k; parent[s.nodes[k].right] = k; }
-    auto area_of = [](const float *b) { const double dx = (double)b[1] - b[0], dy = (double)b[3] - b[2], dz = (double)b[5] - b[4]; return 2.0 * (dx * dy + dy * dz + dz * dx); };
+    auto area_of = [](const float *b) { return box_area(b); };
+    // `area` is a box's PRICE: its surface area, plus mu for every sampled segment that meets it (see ray_weight; without a sample the
+    // plain area, bit for bit).  met[k]: those segments, ascending, for every node that is in the tree.
+    const double mu = sampled ? ray_weight() * area_of(s.nodes[s.root].box) / (double)rays.segs.size() : 0.0;
+    std::vector<std::vector<uint32_t>> met(sampled ? n : 0);
+    if (sampled) {
+        rays.filter(rays.all, s.nodes[0].box, met[0]);
+        for (int32_t k = 0; k < n; k++)      // (parents come before their children)
+            if (s.nodes[k].prim < 0) { rays.filter(met[k], s.nodes[s.nodes[k].left].box, met[s.nodes[k].left]); rays.filter(met[k], s.nodes[s.nodes[k].right].box, met[s.nodes[k].right]); }
+    }
     std::vector<double> area(n);
-    for (int32_t k = 0; k < n; k++) area[k] = area_of(s.nodes[k].box);
+    for (int32_t k = 0; k < n; k++) area[k] = area_of(s.nodes[k].box) + (sampled ? mu * (double)met[k].size() : 0.0);
     int32_t root = s.root;
+    // height[k]: the most internal nodes on a path from k down to a leaf, k included (a leaf: 0)
+    std::vector<int> height(n, 0);
+    for (int32_t k = n; k-- > 0;)
+        if (s.nodes[k].prim < 0) height[k] = 1 + std::max(height[s.nodes[k].left], height[s.nodes[k].right]);
+    auto heights_up = [&](int32_t k) {      // from node k to the root (stops where a height does not change)
+        while (k >= 0) {
+            const int h = 1 + std::max(height[s.nodes[k].left], height[s.nodes[k].right]);
+            if (h == height[k]) break;
+            height[k] = h;
+            k = parent[k];
+        }
+    };
+    std::vector<int32_t> changed;
     auto refit_up = [&](int32_t k) {      // recompute the boxes from node k to the root (stops when a box does not change)
+        changed.clear();
         while (k >= 0) {
             BvhNode &nd = s.nodes[k];
             const BvhNode &l = s.nodes[nd.left], &r = s.nodes[nd.right];
@@ -267,8 +380,13 @@ static void optimise_bvh_by_reinsertion(srt_scene &s, int passes) {
             for (int a = 0; a < 3; a++) { nb[2 * a] = fminf(l.box[2 * a], r.box[2 * a]); nb[2 * a + 1] = fmaxf(l.box[2 * a + 1], r.box[2 * a + 1]); }
             if (memcmp(nb, nd.box, sizeof(nb)) == 0) break;
             memcpy(nd.box, nb, sizeof(nb));
-            area[k] = area_of(nb);
+            changed.push_back(k);
             k = parent[k];
+        }
+        for (size_t i = changed.size(); i-- > 0;) {      // prices top-down: a node's segments are among its parent's
+            const int32_t c = changed[i];
+            if (sampled) rays.filter(parent[c] >= 0 ? met[parent[c]] : rays.all, s.nodes[c].box, met[c]);
+            area[c] = area_of(s.nodes[c].box) + (sampled ? mu * (double)met[c].size() : 0.0);
         }
     };
     auto replace_child = [&](int32_t p, int32_t old_c, int32_t new_c) {
@@ -277,14 +395,18 @@ static void optimise_bvh_by_reinsertion(srt_scene &s, int passes) {
         else s.nodes[p].right = new_c;
         parent[new_c] = p;
     };
-    struct Cand { double induced; int32_t node; bool operator<(const Cand &o) const { return induced > o.induced; } };
+    // from: the segments that meet the union box of the position above this one (>= 0: an index into `pool`, -1: every segment,
+    // <= -2: met[-2 - from], that position's own list): the union box of a position lies inside the one above it
+    // level: the internal nodes above the position
+    struct Cand { double induced; int32_t node; int32_t from; int level; bool operator<(const Cand &o) const { return induced > o.induced; } };
     std::vector<Cand> heap;
+    std::vector<std::vector<uint32_t>> pool;
     // Not every node costs the same to visit: a node with a leaf child is a FRINGE record (box + triangle tests) and the kernel's
     // instruction budget prices a FRINGE visit at 2.5 INNER visits (27 % of the vector instructions for 3.9 visits per ray against
     // 36 % for 13.0).  So the objective is sum(area x visit cost), with cf for nodes that have a leaf child -- it
     // pairs leaves up and turns leaf + subtree nodes into INNER ones where that is cheap: T 3.99 -> 3.95 triangle tests per ray at
     // the same V on cfg 3's scene, another -1.3 % (SRT_BVH_FRINGE_WEIGHT overrides; 1 = plain surface area).
-    const double cf = getenv("SRT_BVH_FRINGE_WEIGHT") ? std::max(1.0, atof(getenv("SRT_BVH_FRINGE_WEIGHT"))) : 2.5;
+    const double cf = fringe_weight();
     auto is_leaf = [&](int32_t k) { return s.nodes[k].prim >= 0; };
     // A PAIRED tree (every internal node has two leaf children or none: build_bvh_sah's even splits) stays paired: only internal
     // subtrees move (their triangle count is even) and only next to internal nodes -- a leaf is never taken out of, or put into, a pair.
@@ -302,11 +424,13 @@ static void optimise_bvh_by_reinsertion(srt_scene &s, int passes) {
             const int32_t S = s.nodes[P].left == N ? s.nodes[P].right : s.nodes[P].left;
             replace_child(G, P, S);                    // take N (and P) out
             refit_up(G);
+            heights_up(G);
             const float *nb = s.nodes[N].box;
             const double a_n = area[N];
             double best_cost = DBL_MAX; int32_t best = S;
             heap.clear();
-            heap.push_back({0.0, root});
+            heap.push_back({0.0, root, -1, 0});
+            size_t pool_used = 0;
             while (!heap.empty()) {
                 std::pop_heap(heap.begin(), heap.end());
                 const Cand c = heap.back(); heap.pop_back();
@@ -315,9 +439,24 @@ static void optimise_bvh_by_reinsertion(srt_scene &s, int passes) {
                 if (c.induced + a_n - credit_max >= best_cost) break;      // every remaining position costs at least that
                 const BvhNode &x = s.nodes[c.node];
                 if (paired && x.prim >= 0) continue;      // (not a position: a leaf stays with its partner)
+                if (c.level + 1 + height[N] > max_internal_depth) continue;      // (too deep for N, here and everywhere below)
+                const bool too_deep = c.level + 1 + height[c.node] > max_internal_depth;      // (x would sink too far: only positions below it)
                 float u[6];
                 for (int a = 0; a < 3; a++) { u[2 * a] = fminf(x.box[2 * a], nb[2 * a]); u[2 * a + 1] = fmaxf(x.box[2 * a + 1], nb[2 * a + 1]); }
-                const double ua = area_of(u);
+                int32_t u_met = -1;
+                size_t u_count = 0;
+                if (sampled) {
+                    if (memcmp(u, x.box, sizeof(u)) == 0) {      // N lies inside x's box (most positions near the root): x's own list
+                        u_met = -2 - c.node;
+                        u_count = met[c.node].size();
+                    } else {
+                        if (pool_used == pool.size()) pool.emplace_back();
+                        u_met = (int32_t)pool_used++;
+                        rays.filter(c.from >= 0 ? pool[c.from] : (c.from == -1 ? rays.all : met[-2 - c.from]), u, pool[u_met]);
+                        u_count = pool[u_met].size();
+                    }
+                }
+                const double ua = area_of(u) + (sampled ? mu * (double)u_count : 0.0);
                 double direct = ua;
                 if (cf > 1.0) {
                     direct = ua * ((is_leaf(c.node) || is_leaf(N)) ? cf : 1.0);
@@ -327,11 +466,11 @@ static void optimise_bvh_by_reinsertion(srt_scene &s, int passes) {
                         if (!is_leaf(other)) direct -= (cf - 1.0) * area[gx];
                     }
                 }
-                if (c.induced + direct < best_cost) { best_cost = c.induced + direct; best = c.node; }
+                if (!too_deep && c.induced + direct < best_cost) { best_cost = c.induced + direct; best = c.node; }
                 const double below = c.induced + (ua - area[c.node]) * (cf > 1.0 ? wgt(c.node) : 1.0);      // what the ancestors of a position below x pay
                 if (x.prim < 0 && below + a_n - (cf > 1.0 ? (cf - 1.0) * area[c.node] : 0.0) < best_cost) {
-                    heap.push_back({below, x.left}); std::push_heap(heap.begin(), heap.end());
-                    heap.push_back({below, x.right}); std::push_heap(heap.begin(), heap.end());
+                    heap.push_back({below, x.left, u_met, c.level + 1}); std::push_heap(heap.begin(), heap.end());
+                    heap.push_back({below, x.right, u_met, c.level + 1}); std::push_heap(heap.begin(), heap.end());
                 }
             }
             const int32_t GX = parent[best];           // put P back as the parent of (best, N)
@@ -340,6 +479,8 @@ static void optimise_bvh_by_reinsertion(srt_scene &s, int passes) {
             parent[best] = P; parent[N] = P;
             s.nodes[P].box[0] = FLT_MAX;               // (force the refit of P itself)
             refit_up(P);
+            height[P] = -1;
+            heights_up(P);
         }
     }
     renumber(root);
@@ -347,8 +488,8 @@ static void optimise_bvh_by_reinsertion(srt_scene &s, int passes) {
 
 // srt_scene_optimise_bvh: the reinsertion passes, boxes and depth again, then the builder's child order (the nearer child of every
 // node to the scene's ordering viewpoint on the left).
-static void optimise_built_tree(srt_scene &s, int passes) {
-    optimise_bvh_by_reinsertion(s, passes);
+static void optimise_built_tree(srt_scene &s, int passes, const RaySample &rays, int max_internal_depth = INT_MAX) {
+    optimise_bvh_by_reinsertion(s, passes, rays, max_internal_depth);
     finish_boxes_and_depth(s);
     auto dist2 = [&](const float *bx) {
         double d2 = 0;
@@ -363,7 +504,9 @@ static void optimise_built_tree(srt_scene &s, int passes) {
         if (nd.prim < 0 && dist2(s.nodes[nd.right].box) < dist2(s.nodes[nd.left].box)) std::swap(nd.left, nd.right);
 }
 
-bool optimise_bvh_unless(srt_scene &s, int passes, const std::function<bool(const FlatScene &before, const FlatScene &after)> &keep) {
+bool optimise_bvh_unless(srt_scene &s, int passes, const std::function<bool(const FlatScene &before, const FlatScene &after)> &keep,
+                         const float *segments, size_t n_segments, int max_internal_depth) {
+    const RaySample rays(segments, n_segments);
     const std::vector<BvhNode> nodes = s.nodes;
     const int32_t root = s.root;
     const int depth = s.depth;
@@ -372,8 +515,12 @@ bool optimise_bvh_unless(srt_scene &s, int passes, const std::function<bool(cons
     memcpy(order_eye, s.order_eye, sizeof(order_eye));
     FlatScene before, after;
     const bool flat_before = flatten_scene(s, before) == SRT_OK;
-    if (flat_before && passes > 0) optimise_built_tree(s, passes);
-    if (flat_before && flatten_scene(s, after) == SRT_OK && keep(before, after)) return true;
+    // with a sample the objective is measured on both trees: the steps' bookkeeping of the FRINGE weight is local (see above), so the
+    // guarantee that the sum does not rise is checked here and not assumed
+    const double cost_before = rays.empty() ? 0.0 : tree_ray_cost(s, segments, n_segments);
+    if (flat_before && passes > 0) optimise_built_tree(s, passes, rays, max_internal_depth);
+    const bool not_worse = rays.empty() || tree_ray_cost(s, segments, n_segments) <= cost_before;
+    if (flat_before && not_worse && flatten_scene(s, after) == SRT_OK && keep(before, after)) return true;
     s.nodes = nodes; s.root = root; s.depth = depth; s.has_order_eye = has_order_eye;
     memcpy(s.order_eye, order_eye, sizeof(order_eye));
     return false;
@@ -540,7 +687,7 @@ int build_bvh_sah(srt_scene &s) {
     finish_boxes_and_depth(s);
     if (const char *ev = getenv("SRT_BVH_OPT_PASSES")) {      // experiment knob: srt_scene_optimise_bvh as part of the build
         s.bvh_valid = true;
-        if (atoi(ev) > 0) optimise_built_tree(s, atoi(ev));
+        if (atoi(ev) > 0) optimise_built_tree(s, atoi(ev), RaySample(nullptr, 0));
     }
     s.bvh_valid = true;
     return SRT_OK;
@@ -1529,7 +1676,20 @@ int srt_scene_order_children(srt_scene *s, const float eye[3]) {
 // its own, for the caller that knows its launch has many pixels per lane, and not part of srt_scene_build_bvh.
 int srt_scene_optimise_bvh(srt_scene *s, int passes) {
     if (!s || !s->bvh_valid) { set_global_error("srt_scene_optimise_bvh: BVH not built"); return SRT_ERR_INVALID; }
-    if (passes > 0) optimise_built_tree(*s, passes);
+    if (passes > 0) optimise_built_tree(*s, passes, RaySample(nullptr, 0));
+    return SRT_OK;
+}
+// srt_scene_optimise_bvh against a sample of the frame's own closest-hit queries instead of box areas alone (include/srt_c_api.h).
+int srt_scene_optimise_bvh_for_rays(srt_scene *s, int passes, const float *segments, size_t n_segments) {
+    if (!s || !s->bvh_valid || (!segments && n_segments)) { set_global_error("srt_scene_optimise_bvh_for_rays: BVH not built / null segments"); return SRT_ERR_INVALID; }
+    // (experiment knob: the limit the tuning recipe derives from the launch plan, by hand)
+    const int max_depth = getenv("SRT_BVH_MAX_DEPTH") ? std::max(1, atoi(getenv("SRT_BVH_MAX_DEPTH"))) : INT_MAX;
+    if (passes > 0) optimise_bvh_unless(*s, passes, [](const FlatScene &, const FlatScene &) { return true; }, segments, n_segments, max_depth);
+    return SRT_OK;
+}
+int srt_scene_bvh_ray_cost(const srt_scene *s, const float *segments, size_t n_segments, double *cost) {
+    if (!s || !s->bvh_valid || !cost || (!segments && n_segments)) { set_global_error("srt_scene_bvh_ray_cost: BVH not built / null argument"); return SRT_ERR_INVALID; }
+    *cost = tree_ray_cost(*s, segments, n_segments);
     return SRT_OK;
 }
 int srt_rotation_matrix(float theta, int axis, float m[9]) {

@@ -107,7 +107,14 @@ void refit_topology(const FlatScene &f, const srt_scene &s, RefitTopology &out);
 // srt_scene_optimise_bvh with a veto: runs its `passes` rounds, flattens the tree as it was and as it has become, and keeps the new
 // tree only if `keep` says so (or if a tree cannot be flattened: then the old one stays) -- otherwise nodes, root, depth and ordering
 // viewpoint are put back exactly as they were.  Returns whether the optimised tree was kept.  Host only: no upload, no device.
-bool optimise_bvh_unless(srt_scene &s, int passes, const std::function<bool(const FlatScene &before, const FlatScene &after)> &keep);
+// segments (7 floats each: origin, direction, t_end; srt_scene_optimise_bvh_for_rays): the passes price a box by the sampled segments
+// that meet it on top of its area, and a tree whose objective for the sample (tree_ray_cost) came out higher is put back as well.
+// max_internal_depth: the passes take no position that puts more internal nodes on a root-to-leaf path (FlatScene::stack_depth, the INNER
+// nodes of the longest path, is at most that minus one: the last internal node of a path has a leaf child).
+bool optimise_bvh_unless(srt_scene &s, int passes, const std::function<bool(const FlatScene &before, const FlatScene &after)> &keep,
+                         const float *segments = nullptr, size_t n_segments = 0, int max_internal_depth = 0x7fffffff);
+double tree_ray_cost(const srt_scene &s, const float *segments, size_t n_segments);
+size_t usable_ray_segments(const float *segments, size_t n_segments);      // the segments the two calls above do not leave out
 void cmf_rows(float *rows96x4);   // { x_bar, y_bar, z_bar, D65n } per 5 nm sample
 
 }  // namespace srt

@@ -86,8 +86,18 @@ struct OrderProfile {
     const float *sibbox;       // per node: the box of its sibling (xmin xmax ymin ymax zmin zmax)
     uint32_t *cnt;             // [parent * 2 + side]: closest hits found under that child while the sibling's box lay on the ray beyond the hit
     unsigned long long n_nodes;
+    // Segment dump (srt_collect_ray_segments), independent of magic: seg != null marks a launch that samples its closest-hit queries.
+    // Every finished query whose direction is not NaN takes a ticket from seg_tickets[0] (one wave-aggregated atomic); ticket t is
+    // sampled when (t + seg_phase) % seg_stride == 0 and then owns slot (t + seg_phase) / seg_stride - (seg_phase ? 1 : 0) -- the number
+    // of sampled tickets before it -- which it writes, when slot < seg_capacity, as two float4: (origin, dir.x) (dir.y, dir.z, t_end,
+    // bits of the triangle found or -1).  t_end: the closest hit, FLT_MAX for a miss.
+    float4 *seg;
+    uint32_t *seg_tickets;
+    uint32_t seg_stride, seg_phase;      // seg_stride >= 1, seg_phase < seg_stride
+    unsigned long long seg_capacity;     // slots of seg
 };
 constexpr unsigned long long kOrderProfileMagic = 0x5352544f52444552ull;
+constexpr uint32_t kSegmentFloats = 7;      // origin, direction, t_end: what the host calls exchange (the device slot has an eighth word)
 
 // Accumulating launch (render_kernel MODE 3, srt_render_chunk_accum): RenderParams::wave_debug -- which no other production launch
 // reads -- points at this header instead of the instrumented build's OrderProfile, so that RenderParams and with it the machine code of

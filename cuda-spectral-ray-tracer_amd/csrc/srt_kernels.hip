@@ -326,7 +326,7 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
     // done -- a wave that refilled itself with other pixels would slow the expensive chains down again.
     bool parked = false, exclusive = false;
     OrderProfile prof;      // instrumented build only: see srt_internal.h
-    prof.magic = 0;
+    prof.magic = 0; prof.seg = nullptr;
     if (COUNT && P.wave_debug) prof = *reinterpret_cast<const OrderProfile *>(P.wave_debug);      // (fixed place: in front of the per-wave words)
     unsigned long long t_shade = 0, t_inner = 0, t_fringe = 0, t_mark = 0;   // instrumented build: wave cycles per phase
     if (COUNT) t_mark = __builtin_amdgcn_s_memtime();
@@ -353,6 +353,25 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
             // ---- S1: shade a finished closest-hit query: one iteration of ray_bounce's loop (rendering.cu:22-36)
             if (!dead && tv.node == kTravDone) {
                 tv.node = kTravIdle;
+                if (COUNT && P.wave_debug && prof.seg != nullptr) {
+                    // segment dump (OrderProfile, srt_internal.h): ro / rd are still the query's.  NaN directions never walked the tree.
+                    const bool walked = !(rd.x != rd.x || rd.y != rd.y || rd.z != rd.z);
+                    const unsigned long long m = __ballot(walked);
+                    if (walked) {
+                        const int leader = __ffsll((long long)m) - 1;
+                        uint32_t base = 0;
+                        if ((int)lane == leader) base = atomicAdd(prof.seg_tickets, (uint32_t)__popcll(m));
+                        base = (uint32_t)__shfl((int)base, leader, 64);
+                        const uint32_t ticket = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+                        const uint32_t key = ticket + prof.seg_phase;      // (a launch has fewer than 2^32 - stride queries: the host checks)
+                        const uint32_t slot = key / prof.seg_stride - (prof.seg_phase ? 1u : 0u);
+                        if (key % prof.seg_stride == 0u && (unsigned long long)slot < prof.seg_capacity) {
+                            const float t_end = tv.hit < 0 ? kFltMax : tv.c;
+                            prof.seg[2 * (size_t)slot] = make_float4(ro.x, ro.y, ro.z, rd.x);
+                            prof.seg[2 * (size_t)slot + 1] = make_float4(rd.y, rd.z, t_end, __int_as_float(tv.hit));
+                        }
+                    }
+                }
                 float wl[kWavelengths];
                 hero_expand(hero, wl);
                 // the spectrum this segment multiplies into the path: the background on a miss (rendering.cu:24-27), the hit

@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import binding as B
-from .scene import refit_vertices
+from .scene import ray_segments, refit_vertices
 
 DEFAULT_TX, DEFAULT_TY = 28, 16   # render_manager.cu:93-94
 FEATURE_CHANNELS = 8              # first-hit sums per pixel: normal xyz, albedo rgb, distance, hits (srt_c_api.h, srt_accum_reset_features)
@@ -731,6 +731,17 @@ class Renderer:
         self._ck(B.lib().srt_order_children_by_profile(self._h, scene.handle, width, height, spp, bounce_limit, min_samples, C.byref(n)))
         return n.value
 
+    def collect_ray_segments(self, width, height, spp, bounce_limit, stride=1, seed=0, capacity=None):
+        """a sample of the closest-hit queries of one instrumented frame of this context's camera and uploaded scene
+        (srt_collect_ray_segments): (segments (n, 7) float32 -- origin, direction, t_end --, queries that took a ticket).  capacity: the
+        most segments to return (default: every one the frame can sample).  init_device_params comes next."""
+        if capacity is None:
+            capacity = width * height * spp * max(bounce_limit, 1) // max(stride, 1) + 1
+        out = np.zeros((capacity, 7), np.float32)
+        n, q = C.c_size_t(0), C.c_uint64(0)
+        self._ck(B.lib().srt_collect_ray_segments(self._h, width, height, spp, bounce_limit, stride, seed, B.fptr(out), capacity, C.byref(n), C.byref(q)))
+        return out[:n.value].copy(), q.value
+
     def stats(self):
         st = B.Stats()
         self._ck(B.lib().srt_get_stats(self._h, C.byref(st)))
@@ -1006,27 +1017,38 @@ def pixels_per_lane(renderer, width, height, world=1):
     return out.value
 
 
-def tree_tuning(renderer, scene, width, height, bounce_limit, world=1, gate=False):
+def tree_tuning(renderer, scene, width, height, bounce_limit, world=1, gate=False, segments=None):
     """srt_tune_tree_for_throughput (srt_c_api.h holds the recipe) as a dict of srt_tree_tuning's fields; gate: leave the tree of a
-    launch with fewer than 6 pixels per lane untouched.  The scene is left uploaded; init_device_params comes next."""
+    launch with fewer than 6 pixels per lane untouched; segments: the caller's (n, 7) sample in place of the recorded one
+    (srt_tune_tree_with_segments).  The scene is left uploaded; init_device_params comes next."""
     t = B.TreeTuning()
-    renderer._ck(B.lib().srt_tune_tree_for_throughput(renderer._h, scene.handle, width, height, max(world, 1), bounce_limit, 1 if gate else 0, C.byref(t)))
+    if segments is None:
+        renderer._ck(B.lib().srt_tune_tree_for_throughput(renderer._h, scene.handle, width, height, max(world, 1), bounce_limit, 1 if gate else 0, C.byref(t)))
+    else:
+        seg = ray_segments("tree_tuning", segments)
+        renderer._ck(B.lib().srt_tune_tree_with_segments(renderer._h, scene.handle, width, height, max(world, 1), bounce_limit, 1 if gate else 0,
+                                                         B.fptr(seg), seg.shape[0], C.byref(t)))
     return {name: getattr(t, name) for name, _ in B.TreeTuning._fields_}
 
 
-def tune_tree_for_throughput(renderer, scene, width, height, bounce_limit, world=1, gate=False):
+def tune_tree_for_throughput(renderer, scene, width, height, bounce_limit, world=1, gate=False, segments=None):
     """Tree preparation for a THROUGHPUT-bound launch of a width x height frame on this build's own SAH tree (tree_tuning): insertion-based
     topology optimisation and the child order from a probe frame.  Not for launches with few pixels per lane (see pixels_per_lane): less
     total work is not a cheaper longest pixel -- measured 5-10 % slower there; gate=True leaves their tree as built.
     Returns a description for the record.  Deterministic: every rank arrives at the same tree."""
-    t = tree_tuning(renderer, scene, width, height, bounce_limit, world, gate)
+    t = tree_tuning(renderer, scene, width, height, bounce_limit, world, gate, segments)
     if gate and not t["throughput_bound"]:
         return "tree as built (chain-bound launch: fewer than 6 pixels per lane)"
     renderer._ck(t["order_status"])
-    notes = {1: ["3 reinsertion passes"], 2: ["reinsertion undone (the deeper tree would no longer be LDS resident)"]}.get(t["reinsertion"], [])
+    notes = {1: ["3 reinsertion passes"], 2: ["reinsertion undone (the deeper tree would no longer be LDS resident)"],
+             3: ["3 reinsertion passes"],
+             4: ["ray-weighted reinsertion vetoed (the sampled frame's work counters did not fall): tree as it walked in"],
+             5: ["no usable ray segment in the sample: topology as it walked in"]}.get(t["reinsertion"], [])
     probe = (t["probe_width"], t["probe_height"], t["probe_spp"])
     notes.append(("child order profiled on a %dx%d x %d spp probe frame: %d nodes swapped" % (probe + (t["nodes_swapped"],))) if t["nodes_swapped"] else
                  ("builder's child order kept (the %dx%d x %d spp probe frame was not cheaper with the profiled one)" % probe))
+    if t["reinsertion"] == 3:
+        notes.append("reinsertion priced by %d sampled ray segments" % t["segments"])
     return "; ".join(notes)
 
 

@@ -26,6 +26,16 @@ def refit_vertices(who, vertices):
     return np.ascontiguousarray(vertices)
 
 
+def ray_segments(who, segments):
+    """the (n, 7) float32 segment array of the ray-tuned tree calls -- origin, direction, t_end --, C-contiguous; n may be 0"""
+    seg = np.asarray(segments, np.float32)
+    if seg.size == 0:
+        return np.zeros((0, 7), np.float32)
+    if seg.ndim != 2 or seg.shape[1] != 7:
+        raise ValueError("%s: segments must have shape (n, 7), got %r" % (who, seg.shape))
+    return np.ascontiguousarray(seg)
+
+
 class Scene:
     def __init__(self, handle):
         if not handle:
@@ -122,6 +132,20 @@ class Scene:
         """insertion-based topology optimisation of the built tree (srt_scene_optimise_bvh): for throughput-bound launches"""
         B.check(B.lib().srt_scene_optimise_bvh(self._h, passes))
         return self
+
+    def optimise_bvh_for_rays(self, segments, passes=3):
+        """srt_scene_optimise_bvh against a sample of a frame's closest-hit queries (srt_scene_optimise_bvh_for_rays): segments (n, 7)
+        float32 -- origin, direction, t_end -- as Renderer.collect_ray_segments returns them; an empty array is optimise_bvh"""
+        seg = ray_segments("Scene.optimise_bvh_for_rays", segments)
+        B.check(B.lib().srt_scene_optimise_bvh_for_rays(self._h, passes, B.fptr(seg), seg.shape[0]))
+        return self
+
+    def bvh_ray_cost(self, segments):
+        """the objective of optimise_bvh_for_rays for the built tree and a sample (srt_scene_bvh_ray_cost)"""
+        seg = ray_segments("Scene.bvh_ray_cost", segments)
+        cost = C.c_double()
+        B.check(B.lib().srt_scene_bvh_ray_cost(self._h, B.fptr(seg), seg.shape[0], C.byref(cost)))
+        return cost.value
 
     def order_children(self, eye):
         """Re-order every node's children for a viewpoint (nearer child first); upload the scene again afterwards."""

@@ -176,7 +176,19 @@ SRT_API int srt_scene_order_children(srt_scene *s, const float eye[3]);
  * ray on average; NOT a cheaper worst pixel -- measured slower on launches bound by their longest pixel (few pixels per lane), so it
  * is a call of its own and not part of srt_scene_build_bvh.  Upload the scene afterwards. */
 SRT_API int srt_scene_optimise_bvh(srt_scene *s, int passes);
-/* 1 when every internal node of the built tree has two leaf children or none ("paired": what SRT_BVH_SAH builds for an even triangle
+/* srt_scene_optimise_bvh against the rays of a frame instead of box areas alone (host only, driven by the caller's array: no device).
+ * segments[n_segments][7] = origin xyz, direction xyz (not normalised), t_end of a closest-hit query -- t_end the hit, or the query's
+ * upper limit for a miss -- as srt_collect_ray_segments returns them.  The search, the canonical form, the paired-tree rules and the
+ * FRINGE weight are srt_scene_optimise_bvh's; the price of a box is area + mu x (segments [0, t_end] that meet it, by the traversal's own
+ * box test with closest_so_far = t_end: a box beyond the hit costs nothing), mu = 4 x area(root box) / segments used, so the area stays
+ * as a prior of one fifth where every segment meets a box, and alone where none does.  Segments with a NaN or infinite origin, a
+ * NaN or all-zero direction or t_end <= 0 are not used.  With no usable segment this IS srt_scene_optimise_bvh, bit for bit.  The
+ * objective (srt_scene_bvh_ray_cost) never comes out higher than on the tree that walked in: a result that would is put back.  The same
+ * segments in the same order give the same tree: single-threaded, integer counts.  Cost: about passes x nodes x segments box tests. */
+SRT_API int srt_scene_optimise_bvh_for_rays(srt_scene *s, int passes, const float *segments, size_t n_segments);
+/* The objective of srt_scene_optimise_bvh_for_rays for the built tree and a sample: the sum over the internal nodes of price x visit cost
+ * (2.5 for a node with a leaf child, a FRINGE record, 1 otherwise). */
+SRT_API int srt_scene_bvh_ray_cost(const srt_scene *s, const float *segments, size_t n_segments, double *cost);/* 1 when every internal node of the built tree has two leaf children or none ("paired": what SRT_BVH_SAH builds for an even triangle
  * count -- it cuts every span into two even halves -- and what srt_scene_optimise_bvh preserves).  The render launch of such a tree uses
  * the kernel variant whose FRINGE visit carries no box test (a node with one leaf child is the only kind that needs it). */
 SRT_API int srt_scene_is_paired(const srt_scene *s);
@@ -1099,15 +1111,24 @@ SRT_API int srt_pixels_per_lane(const srt_ctx *ctx, uint32_t width, uint32_t hei
 typedef struct srt_tree_tuning {
     double   pixels_per_lane;      /* width*height / world / (CUs * waves per CU * 64) of the scene's launch on ctx */
     uint32_t throughput_bound;     /* pixels_per_lane >= 6 */
-    uint32_t reinsertion;          /* 0 not tried (more than 8192 triangles, or not tuned), 1 kept (3 passes), 2 undone: tree restored */
+    uint32_t reinsertion;          /* 0 not tried (more than 8192 triangles, or not tuned), 1 kept (3 passes against box areas), 2 undone:
+                                    * tree restored (it would leave LDS, or its objective rose), 3 kept (3 passes against the frame's sampled
+                                    * queries), 4 vetoed: the sampled frame's work counters did not fall on the new tree, the tree is as it
+                                    * walked in, 5 no usable segment in the sample: the topology is as it walked in */
     uint32_t probe_width, probe_height, probe_spp;   /* 0 when no probe frame ran */
     uint32_t nodes_swapped;
     int32_t  order_status;         /* SRT_OK, or what srt_order_children_by_profile returned (its message in srt_last_error) */
+    uint32_t segments;             /* usable segments the ray-weighted passes counted (0 when they did not run) */
 } srt_tree_tuning;
 /* Tree tuning for a THROUGHPUT-bound render of a width x height frame on `world` ranks (no reference counterpart: the tree is an
  * input of bvh::hit, bvh/bvh.cu:98-166) -- the one recipe of every front end, so that they traverse the same tree for
  * the same workload.  When a rank's launch has at least 6 pixels per persistent lane, a tree of up to 8 192 triangles is post-optimised
- * by 3 reinsertion passes (srt_scene_optimise_bvh; put back exactly as it was if the deeper tree would no longer be LDS resident) and
+ * against the frame's own rays: one instrumented frame of the scene's default camera at a twelfth of the frame's size (at least 32 x 32),
+ * 1 sample per pixel, records every closest-hit query (srt_collect_ray_segments, stride 1), 2 048 of them, taken evenly through their
+ * canonical order, drive 3 reinsertion passes (srt_scene_optimise_bvh_for_rays; put back exactly as it was if the deeper tree would no
+ * longer be LDS resident), and the same frame is rendered again on the new tree: unless its work counters (node records + 2 x triangle
+ * tests) fell, the tree that walked in is put back (out->reinsertion tells).  A launch with fewer pixels per lane that is tuned all the
+ * same (only_if_throughput_bound == 0) gets the 3 passes against box areas it always got (srt_scene_optimise_bvh, same LDS rule).  Then
  * the child order is measured on one instrumented probe frame of the scene's default camera at a quarter of the frame's size (at least
  * 32 x 32), 8 samples per pixel, nodes with at least 16 deciding rays (srt_order_children_by_profile, which undoes itself when the
  * probe frame did not get cheaper).  Launches with fewer pixels per lane are bound by their longest pixel, which a tree with less total
@@ -1117,6 +1138,22 @@ typedef struct srt_tree_tuning {
  * accumulation is invalidated, and srt_init_device_params comes next. */
 SRT_API int srt_tune_tree_for_throughput(srt_ctx *ctx, srt_scene *scene, uint32_t width, uint32_t height, uint32_t world,
                                          uint32_t bounce_limit, int only_if_throughput_bound, srt_tree_tuning *out);
+/* The same recipe with the caller's sample in place of the recorded one (segments[n_segments][7] as srt_collect_ray_segments returns them;
+ * thinned to 2 048 like the recorded sample): what the recipe does with a sample can be checked without depending on what a frame casts.
+ * The two frames that decide the veto are rendered as ever. */
+SRT_API int srt_tune_tree_with_segments(srt_ctx *ctx, srt_scene *scene, uint32_t width, uint32_t height, uint32_t world, uint32_t bounce_limit,
+                                        int only_if_throughput_bound, const float *segments, size_t n_segments, srt_tree_tuning *out);
+/* A sample of a frame's closest-hit queries (no reference counterpart; instrumented kernel).  Renders ONE instrumented frame of the
+ * context's camera and uploaded scene (width x height, spp, bounce_limit; the grid and seed of srt_order_children_by_profile's probe
+ * frames) in which every finished closest-hit query whose direction is not NaN -- those never walk the tree -- takes a ticket 0, 1, 2 ..
+ * from one counter; ticket t is recorded when (t + seed % stride) % stride == 0, as origin xyz, direction xyz (not normalised) and t_end:
+ * the closest hit, FLT_MAX for a miss.  *n_queries (optional) = tickets taken = srt_stats.rays - srt_stats.util[2] of the frame;
+ * *n_segments = the recorded ones, at most `capacity` (the later ones are dropped), written to segments[*n_segments][7] in ascending
+ * order of their bit patterns.  With stride 1 every query is recorded and the array is the same in every run; with a larger stride WHICH
+ * queries hold the sampled tickets depends on the order in which the waves finish them.  The production kernels are not involved; the
+ * context's frame buffer, RNG state and grid are the frame's afterwards: srt_init_device_params comes next. */
+SRT_API int srt_collect_ray_segments(srt_ctx *ctx, uint32_t width, uint32_t height, uint32_t spp, uint32_t bounce_limit, uint32_t stride,
+                                     uint64_t seed, float *segments, size_t capacity, size_t *n_segments, uint64_t *n_queries);
 SRT_API int srt_get_stats(srt_ctx *ctx, srt_stats *out);       /* counters of the last srt_render_chunk (or _accum pass) */
 SRT_API int srt_set_count_traversal(srt_ctx *ctx, int on);     /* 1: instrumented kernel also counts V / T */
 /* Instrumented launches only (diagnostics of the tail of a launch): 4 words per persistent wave -- [0] its life time and [1] the
