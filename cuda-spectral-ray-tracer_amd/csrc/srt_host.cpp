@@ -133,6 +133,99 @@ static void finish_boxes_and_depth(srt_scene &s) {
     s.depth = s.root >= 0 ? internal_depth[s.root] : 0;
 }
 
+// A box the traversal's slab test cannot resolve (this build's own builders only; no reference counterpart).  aabb::hit (aabb.cu:7-40)
+// rejects a box when the two planes of an axis give max <= min.  Two coplanar axis-aligned triangles far from the origin -- a wall of a
+// Cornell box at 555 -- have padded boxes one ulp thick (the pad is 1e-4 / 2, ulp(555) = 6e-5), and so has a node that holds just the two:
+// from an origin 1 355 away (b - o) * inv rounds both planes to one t and every ray loses the wall behind that node, while the leaves
+// themselves carry no box test.  The planes stay apart when the extent w is above about 2 ulp(|b - o|); with origins up to 16 times the
+// box's own coordinates m away that is w >= 2^-18 m, the bound used here.  (Below |m| = 26 the pad of 1e-4 alone meets it.)
+static bool box_too_thin_for_slab_test(const float *b) {
+    for (int a = 0; a < 3; a++) {
+        const float lo = b[2 * a], hi = b[2 * a + 1], m = std::max(fabsf(lo), fabsf(hi));
+        if ((hi - lo) < m * 0x1p-18f) return true;
+    }
+    return false;
+}
+
+static double box_area_of(const float *b) {
+    const double dx = (double)b[1] - b[0], dy = (double)b[3] - b[2], dz = (double)b[5] - b[4];
+    return 2.0 * (dx * dy + dy * dz + dz * dx);
+}
+
+// Where a node with two leaf children has such a box, one of its triangles changes places with a triangle of a nearby pair of leaves
+// (found in the sibling subtrees of up to four ancestors, nearest first; the exchange with the smallest sum of the two new areas among
+// those that leave neither box too thin).  Only triangles move between leaves: node numbering, pairing and depth stay.  A flat cluster of
+// more than two such triangles cannot be helped by topology and keeps its boxes.  Needs current boxes; returns whether anything moved
+// (the caller brings boxes, depth and child order up to date).
+static bool split_pairs_too_thin_for_slab_test(srt_scene &s) {
+    const size_t n = s.nodes.size();
+    std::vector<int32_t> parent(n, -1);
+    for (size_t k = 0; k < n; k++)
+        if (s.nodes[k].prim < 0) { parent[(size_t)s.nodes[k].left] = (int32_t)k; parent[(size_t)s.nodes[k].right] = (int32_t)k; }
+    auto leaf_pair = [&](int32_t k) { const BvhNode &nd = s.nodes[(size_t)k]; return nd.prim < 0 && s.nodes[(size_t)nd.left].prim >= 0 && s.nodes[(size_t)nd.right].prim >= 0; };
+    auto unite = [](const float *x, const float *y, float *out) {
+        for (int a = 0; a < 3; a++) { out[2 * a] = fminf(x[2 * a], y[2 * a]); out[2 * a + 1] = fmaxf(x[2 * a + 1], y[2 * a + 1]); }
+    };
+    bool moved = false;
+    std::vector<int32_t> todo;
+    for (size_t k = 0; k < n; k++) {
+        if (!leaf_pair((int32_t)k) || !box_too_thin_for_slab_test(s.nodes[k].box)) continue;
+        const int32_t A = s.nodes[k].left, B = s.nodes[k].right;
+        int32_t best_leaf = -1, best_pair = -1;
+        double best_area = 0.0;
+        float best_n[6] = {0}, best_m[6] = {0};
+        int32_t cur = (int32_t)k;
+        for (int up = 0; up < 4 && parent[(size_t)cur] >= 0 && best_leaf < 0; up++) {
+            const int32_t P = parent[(size_t)cur];
+            todo.assign(1, s.nodes[(size_t)P].left == cur ? s.nodes[(size_t)P].right : s.nodes[(size_t)P].left);
+            for (size_t visited = 0; !todo.empty() && visited < 256; visited++) {
+                const int32_t M = todo.back();
+                todo.pop_back();
+                if (s.nodes[(size_t)M].prim >= 0) continue;
+                if (!leaf_pair(M)) { todo.push_back(s.nodes[(size_t)M].right); todo.push_back(s.nodes[(size_t)M].left); continue; }
+                for (int side = 0; side < 2; side++) {      // B changes places with c; d stays
+                    const int32_t c = side ? s.nodes[(size_t)M].right : s.nodes[(size_t)M].left, d = side ? s.nodes[(size_t)M].left : s.nodes[(size_t)M].right;
+                    float nb[6], mb[6];
+                    unite(s.nodes[(size_t)A].box, s.nodes[(size_t)c].box, nb);
+                    unite(s.nodes[(size_t)B].box, s.nodes[(size_t)d].box, mb);
+                    if (box_too_thin_for_slab_test(nb) || box_too_thin_for_slab_test(mb)) continue;
+                    const double area = box_area_of(nb) + box_area_of(mb);
+                    if (best_leaf < 0 || area < best_area) {
+                        best_leaf = c; best_pair = M; best_area = area;
+                        memcpy(best_n, nb, sizeof(nb)); memcpy(best_m, mb, sizeof(mb));
+                    }
+                }
+            }
+            cur = P;
+        }
+        if (best_leaf < 0) continue;
+        std::swap(s.nodes[(size_t)B].prim, s.nodes[(size_t)best_leaf].prim);
+        float tmp[6];
+        memcpy(tmp, s.nodes[(size_t)B].box, sizeof(tmp));
+        memcpy(s.nodes[(size_t)B].box, s.nodes[(size_t)best_leaf].box, sizeof(tmp));
+        memcpy(s.nodes[(size_t)best_leaf].box, tmp, sizeof(tmp));
+        memcpy(s.nodes[k].box, best_n, sizeof(best_n));
+        memcpy(s.nodes[(size_t)best_pair].box, best_m, sizeof(best_m));
+        moved = true;
+    }
+    return moved;
+}
+
+// the builders' child order: the nearer child of every node to the scene's ordering viewpoint on the left
+static void order_children_by_distance(srt_scene &s) {
+    auto dist2 = [&](const float *bx) {
+        double d2 = 0;
+        for (int ax = 0; ax < 3; ax++) {
+            const double p = s.has_order_eye ? s.order_eye[ax] : s.cam.lookfrom[ax], lo = bx[2 * ax], hi = bx[2 * ax + 1];
+            const double d = p < lo ? lo - p : (p > hi ? p - hi : 0.0);
+            d2 += d * d;
+        }
+        return d2;
+    };
+    for (BvhNode &nd : s.nodes)
+        if (nd.prim < 0 && dist2(s.nodes[nd.right].box) < dist2(s.nodes[nd.left].box)) std::swap(nd.left, nd.right);
+}
+
 // bvh::build_bvh (bvh/bvh.cu:206-309) on a permutation of triangle indices instead of tri* pointers.
 int build_bvh_reference(srt_scene &s, uint64_t seed) {
     s.nodes.clear(); s.root = -1; s.bvh_valid = false; s.depth = 0;
@@ -491,17 +584,8 @@ static void optimise_bvh_by_reinsertion(srt_scene &s, int passes, const RaySampl
 static void optimise_built_tree(srt_scene &s, int passes, const RaySample &rays, int max_internal_depth = INT_MAX) {
     optimise_bvh_by_reinsertion(s, passes, rays, max_internal_depth);
     finish_boxes_and_depth(s);
-    auto dist2 = [&](const float *bx) {
-        double d2 = 0;
-        for (int ax = 0; ax < 3; ax++) {
-            const double p = s.has_order_eye ? s.order_eye[ax] : s.cam.lookfrom[ax], lo = bx[2 * ax], hi = bx[2 * ax + 1];
-            const double d = p < lo ? lo - p : (p > hi ? p - hi : 0.0);
-            d2 += d * d;
-        }
-        return d2;
-    };
-    for (BvhNode &nd : s.nodes)
-        if (nd.prim < 0 && dist2(s.nodes[nd.right].box) < dist2(s.nodes[nd.left].box)) std::swap(nd.left, nd.right);
+    if (split_pairs_too_thin_for_slab_test(s)) finish_boxes_and_depth(s);
+    order_children_by_distance(s);
 }
 
 bool optimise_bvh_unless(srt_scene &s, int passes, const std::function<bool(const FlatScene &before, const FlatScene &after)> &keep,
@@ -685,6 +769,7 @@ int build_bvh_sah(srt_scene &s) {
         }
     }
     finish_boxes_and_depth(s);
+    if (split_pairs_too_thin_for_slab_test(s)) { finish_boxes_and_depth(s); order_children_by_distance(s); }
     if (const char *ev = getenv("SRT_BVH_OPT_PASSES")) {      // experiment knob: srt_scene_optimise_bvh as part of the build
         s.bvh_valid = true;
         if (atoi(ev) > 0) optimise_built_tree(s, atoi(ev), RaySample(nullptr, 0));

@@ -164,7 +164,9 @@ SRT_API int srt_rotation_matrix(float theta, int axis, float m[9]);
 
 /* BVH: `mode` SRT_BVH_REFERENCE reproduces create_bvh_kernel (fresh XORWOW(seed), bvh/bvh.cu:206-346);
  * SRT_BVH_SAH is this build's builder.  Either way the node semantics are the reference's: binary tree,
- * one triangle per leaf, leaf box = padded triangle box, internal box = union of children (Q22). */
+ * one triangle per leaf, leaf box = padded triangle box, internal box = union of children (Q22).  SRT_BVH_SAH (and srt_scene_optimise_bvh*)
+ * leaves no node with two leaf children whose box is thinner on an axis than 2^-18 of its largest coordinate where another pair of leaves
+ * is near enough to exchange a triangle with: the reference's slab test rejects such a box from afar. */
 SRT_API int srt_scene_build_bvh(srt_scene *s, int mode, uint64_t seed);
 /* The traversal is the reference's left-first walk, so the child order is part of the tree; SRT_BVH_SAH orders every node's
  * children by distance to the scene's default camera.  For another viewpoint: re-order the built tree for `eye` (the nearer

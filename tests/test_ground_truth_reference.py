@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import ground_truth as G
+import tree_truth_cases as TC
 from ground_truth import BUILTINS, N_RAYS, POPULATIONS, builtin_report, cached, population
 from helpers import oracle_scene_for
 
@@ -277,6 +278,81 @@ def test_oracle_builtin_scenes(srt, orc, scene_id):
     (smallest projected normal component 0.276 / 0.087 / 0.276: PRISM's rotated side quads keep YZ, Q12, and stay clear of 0.05), 57.6 %
     of the rays hit, and 0 rays differ from the truth."""
     print(builtin_report(srt, scene_id, lambda scene, rays: oracle_hits(orc, oracle_scene_for(orc, scene, 0), rays)))
+
+
+# ---- the oracle on transformed trees against the truth (the device's turn: tests/test_tree_truth.py) -----------------------------------
+@pytest.mark.parametrize("tuning", TC.TUNINGS)
+@pytest.mark.parametrize("name", TC.TUNED_POPULATIONS)
+def test_oracle_holds_on_tuned_trees(srt, orc, name, tuning):
+    """The populations' SAH trees after srt_scene_optimise_bvh (3 passes), after srt_scene_optimise_bvh_for_rays (3 passes against the
+    first 2 048 rays cut at the truth's t) and after srt_scene_order_children for an eye on the far side; the tree's hash changed in the
+    first two for all four populations.  The oracle walks the imported topology; the truth walks none: a triangle the reinsertion unhooked
+    fails here.  Measured (area, rays and order alike): 0 of 20 000 rays differ; inside the margin 1 (soup_200_spread_0.5), 0, 0, 0;
+    largest |dt| / t_bound 1.64, 1.82 (sheet), 3.44 (axis-aligned), 1.80."""
+    scene = TC.tuned_scene(srt, name, tuning)
+    got = oracle_hits(orc, oracle_scene_for(orc, scene, 1), population(name)[1])
+    print(name, tuning, TC.hold(name, population(name)[0]["V"], got, "oracle %s after %s tuning" % (name, tuning)))
+
+
+def _refit_sequence(srt, orc, scene, name, what):
+    out = []
+    for motion in TC.REFIT_POPULATIONS[name]:
+        v = TC.moved_vertices(name, motion)
+        scene.refit(v)
+        got = oracle_hits(orc, oracle_scene_for(orc, scene, 1), population(name)[1])
+        out.append((motion, TC.hold(name, v, got, "oracle %s %s after refit(%s)" % (name, what, motion))))
+    return out
+
+
+@pytest.mark.parametrize("mode", TC.BUILDERS)
+@pytest.mark.parametrize("name", list(TC.REFIT_POPULATIONS))
+def test_oracle_holds_on_refitted_trees(srt, orc, name, mode):
+    """srt_scene_refit on the built topology of both builders -- every vertex jittered by N(0, 0.1), then the smooth sine deformation, then
+    the vertices it was built from -- with the truth computed on the MOVED vertices: a refit that gives a record the wrong vertex fails.
+    Measured (both builders alike): 0 rays differ in all 28 cases; inside the margin at most 2 of 20 000; largest |dt| / t_bound 2.02,
+    after the return 3.44 (the axis-aligned set, as before any refit).
+    The smooth motion of the axis-aligned set is left out: the ORACLE itself reaches |dt| / t_bound = 8.27 there, above C_T = 6.9 (the
+    deformation tilts triangles that keep their stored YZ / XZ projection until it is nearly degenerate); C_T is measured on unmoved
+    scenes and stays."""
+    scene = G.product_scene(srt, population(name)[0], mode)
+    for motion, summary in _refit_sequence(srt, orc, scene, name, "mode %d" % mode):
+        print(name, mode, motion, summary)
+
+
+def test_oracle_holds_on_a_tuned_then_refitted_tree(srt, orc):
+    """soup_200_spread_0.5: the ray-weighted reinsertion, then the jitter refit on the new topology.  Measured: 0 of 20 000 rays
+    differ, 0 inside the margin, largest |dt| / t_bound 2.02."""
+    name = "soup_200_spread_0.5"
+    scene = TC.tuned_scene(srt, name, "rays")
+    v = TC.moved_vertices(name, "jitter")
+    scene.refit(v)
+    got = oracle_hits(orc, oracle_scene_for(orc, scene, 1), population(name)[1])
+    print(name, TC.hold(name, v, got, "oracle %s, ray tuned then refitted" % name))
+
+
+@pytest.mark.parametrize("tuned", [False, True], ids=["built", "area tuned"])
+@pytest.mark.parametrize("scene_id", BUILTINS)
+def test_oracle_builtin_scenes_on_sah_trees(srt, orc, scene_id, tuned):
+    """The 4 000 camera rays of test_oracle_builtin_scenes on this build's SAH trees, as built and after srt_scene_optimise_bvh: every ray
+    away from the edges agrees with the truth in hit / miss, and no node with two leaf children is thinner on an axis than 2^-18 of its
+    largest coordinate.  Before the builder split such pairs, the SAH tree of CORNELL held the back wall's two coplanar triangles
+    (z = 555) alone under a node whose box was two ulps thick: aabb::hit rejected it from the camera, 1 355 away, and 18 % of the camera
+    rays lost the wall, in oracle and kernel alike.  Measured now: 0 rays differ in all six cases."""
+    scene = srt.Scene.builtin(getattr(srt, "SCENE_" + scene_id)).build_bvh(srt.BVH_SAH, 1984)
+    if tuned:
+        scene.optimise_bvh(3)
+    left, right, prim, boxes = scene.bvh()
+    pairs = np.nonzero(prim < 0)[0]
+    pairs = pairs[(prim[left[pairs]] >= 0) & (prim[right[pairs]] >= 0)]
+    extent, largest = boxes[pairs, 1::2] - boxes[pairs, 0::2], np.abs(boxes[pairs]).reshape(len(pairs), 3, 2).max(2)
+    assert len(pairs) and (extent >= largest * np.float32(2.0 ** -18)).all(), pairs[(extent < largest * np.float32(2.0 ** -18)).any(1)]
+    eye, d = G.pixel_rays(scene.default_camera(80, 50), 80, 50)
+    rays = np.concatenate([np.broadcast_to(eye, d.shape), d], 1).astype(np.float32)
+    got = oracle_hits(orc, oracle_scene_for(orc, scene, 1), rays)
+    _, tri, _, near = G.closest_hit(G.f64(scene.vertices()), G.f64(rays[:, :3]), G.f64(rays[:, 3:]))
+    bad = (near >= G.EDGE_MARGIN) & ((got[:, 1] >= 0) != (tri >= 0))
+    print(scene_id, "tuned" if tuned else "built", "%d of %d rays hit in the truth, %d differ in hit / miss" % ((tri >= 0).sum(), len(rays), bad.sum()))
+    assert not bad.any(), (scene_id, int(bad.sum()), sorted(set(tri[bad].tolist())))
 
 
 # ---- the oracle against the truth: radiometry ----------------------------------------------------------------------------------
