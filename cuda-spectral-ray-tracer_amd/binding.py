@@ -126,6 +126,12 @@ class TemporalResult(C.Structure):
                 ("history_frames", C.c_uint32), ("history_dropped", C.c_uint32)]
 
 
+class MotionResult(C.Structure):
+    """srt_motion_result: the pixels whose centre ray hit and missed, the hit pixels whose triangle moved, and of those the ones whose
+    previous point could not be formed (srt_c_api.h)"""
+    _fields_ = [("hit", C.c_uint64), ("miss", C.c_uint64), ("moved", C.c_uint64), ("degenerate", C.c_uint64)]
+
+
 class TreeTuning(C.Structure):
     """srt_tree_tuning: what srt_tune_tree_for_throughput found and did (srt_c_api.h)"""
     _fields_ = [("pixels_per_lane", C.c_double), ("throughput_bound", C.c_uint32), ("reinsertion", C.c_uint32),
@@ -143,7 +149,7 @@ assert C.sizeof(Denoise) == 32 and C.sizeof(DenoiseVG) == 32
 assert C.sizeof(Meter) == 48 and C.sizeof(MeterResult) == 40 and C.sizeof(Tone) == 32 and C.sizeof(ToneResult) == 24
 assert C.sizeof(PresentCfg) == 184 and C.sizeof(PresentResult) == 64
 assert C.sizeof(Despeckle) == 32 and C.sizeof(DespeckleResult) == 24
-assert C.sizeof(Temporal) == 32 and C.sizeof(TemporalResult) == 48
+assert C.sizeof(Temporal) == 32 and C.sizeof(TemporalResult) == 48 and C.sizeof(MotionResult) == 32
 assert C.sizeof(Adaptive) == 16 and C.sizeof(TreeTuning) == 40 and C.sizeof(TileScheduleInfo) == 32
 assert C.sizeof(Material) == 428 and C.sizeof(CameraData) == 84 and C.sizeof(TriIn) == 44
 
@@ -238,6 +244,19 @@ PROTOTYPES = {
     "srt_present_temporal": (_i, [_vp, C.POINTER(PresentCfg), C.POINTER(Temporal), C.POINTER(Despeckle), C.POINTER(C.c_uint8), _sz, _u32, _u32,
                                   C.POINTER(PresentResult), C.POINTER(TemporalResult)]),
     "srt_temporal_last_ms": (_i, [_vp, _fp]),
+    "srt_temporal_track_motion": (_i, [_vp, _i]),
+    "srt_temporal_tracking": (_i, [_vp, C.POINTER(_i), C.POINTER(_u32)]),
+    "srt_surface_motion": (_i, [_vp, _u32, _u32, _u32, _u32, _fp, C.POINTER(C.c_int32), _fp, C.POINTER(MotionResult)]),
+    "srt_surface_motion_kat": (_i, [_vp, C.POINTER(CameraData), _fp, _fp, _sz, _u32, _u32, _u32, _u32, _fp, C.POINTER(C.c_int32), _fp,
+                                    C.POINTER(MotionResult)]),
+    "srt_motion_last_ms": (_i, [_vp, _fp]),
+    "srt_temporal_accum_moving": (_i, [_vp, C.POINTER(Temporal), _fp, _fp, _fp, _fp, _fp, C.POINTER(TemporalResult), _u32, _u32, C.POINTER(MotionResult)]),
+    "srt_temporal_moving_kat": (_i, [_vp, C.POINTER(Temporal), C.POINTER(CameraData), C.POINTER(CameraData), _fp, _fp, _fp, _fp, _u32, _u32, _u32, _u32,
+                                     _fp, _fp, _fp, C.POINTER(TemporalResult), _fp]),
+    "srt_denoise_features_temporal_moving": (_i, [_vp, C.POINTER(Temporal), C.POINTER(Despeckle), C.POINTER(Denoise), _fp, _fp, _fp,
+                                                  C.POINTER(TemporalResult), _u32, _u32, C.POINTER(MotionResult)]),
+    "srt_present_temporal_moving": (_i, [_vp, C.POINTER(PresentCfg), C.POINTER(Temporal), C.POINTER(Despeckle), C.POINTER(C.c_uint8), _sz, _u32, _u32,
+                                         C.POINTER(PresentResult), C.POINTER(TemporalResult), C.POINTER(MotionResult)]),
     "srt_accum_reset_features": (_i, [_vp]),
     "srt_read_features": (_i, [_vp, _fp, _u32, _u32]),
     "srt_accum_reset_adaptive_features": (_i, [_vp, C.POINTER(Adaptive)]),

@@ -213,6 +213,17 @@ struct srt_ctx {
     hipEvent_t refit_ev[3] = {};                        // around the last refit's triangle kernel [0, 1] and its level launches [1, 2] (created on first use)
     uint32_t refit_timed_levels = 0;
     bool refit_timed = false;
+    // surface motion (srt_motion.hip; srt_c_api.h states the vertex state at "Surface motion").  Nothing below exists while tracking is off.
+    bool track_motion = false;                          // srt_temporal_track_motion
+    enum class Verts { Unknown, Host, Device } verts = Verts::Unknown;      // where V_cur is: nowhere, in track_verts (since an upload), in d_verts_cur
+    std::vector<float> track_verts;                     // V_cur between srt_upload_scene and its first use: 9 floats per triangle
+    DeviceBuffer d_verts_cur, d_verts_hist;             // V_cur and V_hist on the device
+    bool verts_hist = false;                            // V_hist is not "none" (none = equal to V_cur)
+    uint32_t refits_pending = 0;                        // successful refits since the history was last written
+    DeviceBuffer d_motion;                              // the pass's counters and its row-major outputs (MotionLayout)
+    DeviceBuffer d_motion_kat;                          // srt_surface_motion_kat: the caller's two vertex arrays
+    hipEvent_t motion_ev[2] = {};                       // around the last motion kernel (created on first use)
+    bool motion_timed = false;
     DeviceBuffer d_streams;                            // sample-parallel pixels (srt_accum_reset_streams, StreamPlanes)
     uint32_t streams_seeded = 0;                        // the K whose RNG streams d_streams holds, seeded since the last srt_init_device_params (0: none)
 };
@@ -790,6 +801,15 @@ int srt_upload_scene(srt_ctx *c, const srt_scene *s) {
     c->image_bytes[SRT_IMAGE_TRIS] = f.tris.size() * sizeof(float);
     c->image_bytes[SRT_IMAGE_SHADE] = f.shade.size() * sizeof(float);
     build_refit_tables(c, f, *s);      // (host only: nothing is enqueued or allocated on the device for a caller who never refits)
+    if (c->track_motion) {      // V_cur = the scene's vertices, on the host until first use; V_hist = none
+        c->track_verts.resize(9 * s->raw.size());
+        for (size_t k = 0; k < s->raw.size(); k++) {
+            memcpy(&c->track_verts[9 * k], s->raw[k].v0, 3 * sizeof(float));
+            memcpy(&c->track_verts[9 * k + 3], s->raw[k].v1, 3 * sizeof(float));
+            memcpy(&c->track_verts[9 * k + 6], s->raw[k].v2, 3 * sizeof(float));
+        }
+        c->verts = srt_ctx::Verts::Host; c->verts_hist = false; c->refits_pending = 0;
+    }
     c->scene_ready = true;
     return SRT_OK;
 }
@@ -801,8 +821,28 @@ int develop_reserve(srt_ctx *c, const char *who, DeviceBuffer &d, size_t bytes);
 
 // the refit: the device copy of the tables is made now if this is the first refit since the upload, then one triangle kernel and one
 // level launch per height, bottom up, on the NULL stream; d_verts holds 9 * n_tris validated floats on the device
-int refit_run(srt_ctx *c, const char *who, const float *d_verts) {
+// V_cur of a tracking context on the device (it waits on the host from an upload until its first use); the vertices are known
+int track_verts_to_device(srt_ctx *c, const char *who) {
+    if (c->verts != srt_ctx::Verts::Host) return SRT_OK;
+    const size_t bytes = c->track_verts.size() * sizeof(float);
+    if (const int rc = develop_reserve(c, who, c->d_verts_cur, bytes)) return rc;
+    HIP_TRY_AS(c, who, hipMemcpy(c->d_verts_cur.ptr, c->track_verts.data(), bytes, hipMemcpyHostToDevice));
+    c->track_verts.clear(); c->track_verts.shrink_to_fit();
+    c->verts = srt_ctx::Verts::Device;
+    return SRT_OK;
+}
+
+// (h_verts: the caller's host array when the vertices came through the host entry, else null; a tracking context copies V_cur from it)
+int refit_run(srt_ctx *c, const char *who, const float *d_verts, const float *h_verts) {
     const size_t n_tris = c->n_tris, n_rec = (size_t)c->n_records;
+    const bool keep_history = c->track_motion && c->verts != srt_ctx::Verts::Unknown && c->temporal_frames > 0;
+    if (c->track_motion) {
+        if (keep_history && !c->verts_hist) {      // V_hist = the old V_cur: the blocks change places
+            if (const int rc = track_verts_to_device(c, who)) return rc;
+            if (const int rc = develop_reserve(c, who, c->d_verts_hist, 9 * n_tris * sizeof(float))) return rc;
+        }
+        if (c->verts != srt_ctx::Verts::Device) if (const int rc = develop_reserve(c, who, c->d_verts_cur, 9 * n_tris * sizeof(float))) return rc;
+    }
     if (const int rc = develop_reserve(c, who, c->d_refit_tab, RefitTables::bytes(n_tris, n_rec))) return rc;
     if (const int rc = develop_reserve(c, who, c->d_refit_scratch, RefitScratch::bytes(n_tris, n_rec))) return rc;
     for (hipEvent_t &e : c->refit_ev)
@@ -825,9 +865,18 @@ int refit_run(srt_ctx *c, const char *who, const float *d_verts) {
     p.n_tris = c->n_tris; p.n_inner = (uint32_t)c->n_inner; p.fringe_stride = c->fringe_stride / (uint32_t)sizeof(float);
     // from here on the images change: what shows the old geometry goes, as at srt_upload_scene
     c->accum.invalidate();
-    c->temporal_frames = 0;
+    if (!keep_history) c->temporal_frames = 0;      // (a tracking context keeps it: the *_moving calls reproject across the refit)
     c->sched_probe_queue = false; c->sched_compacted_queue = false;
     c->refit_timed = false;
+    if (c->track_motion) {
+        if (keep_history && !c->verts_hist) { c->d_verts_cur.swap(c->d_verts_hist); c->verts_hist = true; }
+        if (!keep_history) c->verts_hist = false;
+        if (h_verts) HIP_TRY_AS(c, who, hipMemcpyAsync(c->d_verts_cur.ptr, h_verts, 9 * n_tris * sizeof(float), hipMemcpyHostToDevice, nullptr));
+        else HIP_TRY_AS(c, who, hipMemcpyAsync(c->d_verts_cur.ptr, d_verts, 9 * n_tris * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
+        c->track_verts.clear();
+        c->verts = srt_ctx::Verts::Device;
+        c->refits_pending = keep_history ? c->refits_pending + 1u : 0u;
+    }
     HIP_TRY_AS(c, who, hipEventRecord(c->refit_ev[0], nullptr));
     HIP_TRY_AS(c, who, launch_refit_triangles(p, nullptr));
     HIP_TRY_AS(c, who, hipEventRecord(c->refit_ev[1], nullptr));
@@ -861,7 +910,7 @@ int srt_internal_refit_vertices(srt_ctx *c, const float *verts, size_t n_tris, i
     HIP_TRY(c, set_device(c));
     if (const int rc = develop_reserve(c, who, c->d_refit_verts, 9 * n_tris * sizeof(float))) return rc;
     HIP_TRY_AS(c, who, hipMemcpy(c->d_refit_verts.ptr, verts, 9 * n_tris * sizeof(float), hipMemcpyHostToDevice));
-    return refit_run(c, who, c->d_refit_verts.as<float>());
+    return refit_run(c, who, c->d_refit_verts.as<float>(), verts);
 }
 
 int srt_refit_vertices_dev(srt_ctx *c, const float *verts_dev, size_t n_tris) {
@@ -880,7 +929,7 @@ int srt_refit_vertices_dev(srt_ctx *c, const float *verts_dev, size_t n_tris) {
         HIP_TRY_AS(c, who, device_synchronize(c));
         return fail(c, SRT_ERR_INVALID, "srt_refit_vertices_dev: a coordinate is not finite");
     }
-    return refit_run(c, who, verts_dev);
+    return refit_run(c, who, verts_dev, nullptr);
 }
 
 int srt_refit_last_ms(srt_ctx *c, float *tri_ms, float *levels_ms, uint32_t *n_levels) {
@@ -974,6 +1023,7 @@ int srt_internal_init_device_params(srt_ctx *c, uint32_t tx, uint32_t ty, uint32
         return fail(c, SRT_ERR_INVALID, "srt_init_device_params: zero dimension");
     c->accum.invalidate();
     c->temporal_frames = 0;      // (the temporal history belongs to the old grid)
+    c->verts_hist = false; c->refits_pending = 0;
     c->sched_probe_queue = false; c->sched_compacted_queue = false;      // (the queues of the last launch belong to the old set-up)
     const uint64_t lanes = (uint64_t)tx * ty * bx * by;
     if (lanes > 0x7fffffffull) return fail(c, SRT_ERR_INVALID, "srt_init_device_params: grid too large");
@@ -1002,6 +1052,7 @@ int srt_set_partition(srt_ctx *c, uint32_t rank, uint32_t world) {
     if (!c || world == 0 || rank >= world) return fail(c, SRT_ERR_INVALID, "srt_set_partition: need rank < world");
     c->accum.invalidate();
     c->temporal_frames = 0;      // (the temporal history belongs to the old partition)
+    c->verts_hist = false; c->refits_pending = 0;
     c->sched_probe_queue = false; c->sched_compacted_queue = false;      // (the queues of the last launch belong to the old set-up)
     c->rank = rank; c->world = world;
     return SRT_OK;
@@ -1990,16 +2041,89 @@ struct TemporalHistory {
         for (int k = 0; k < 2; k++) { colour[k] = d.as<float4>() + 3 * pixels * k; guides[k] = colour[k] + pixels; }
     }
 };
-// d_temporal_kat: [guides: 2 float4 per pixel | hist_c: 1 | hist_g: 2 | new_c: 1 | new_g: 2 | xyz: three floats per pixel]
+// d_temporal_kat: [guides: 2 float4 per pixel | hist_c: 1 | hist_g: 2 | new_c: 1 | new_g: 2 | (moving: prev_point: 1) | xyz: three floats per pixel]
 struct TemporalKatLayout {
     float4 *guides, *hist_c, *hist_g, *new_c, *new_g;
     float *xyz;
-    static size_t bytes(size_t pixels) { return pixels * (8 * sizeof(float4) + 3 * sizeof(float)); }
-    TemporalKatLayout(const DeviceBuffer &d, size_t pixels) : guides(d.as<float4>()) {
+    float4 *prev_point;      // (srt_temporal_moving_kat only, else null)
+    static size_t bytes(size_t pixels, bool moving = false) { return pixels * ((moving ? 9 : 8) * sizeof(float4) + 3 * sizeof(float)); }
+    TemporalKatLayout(const DeviceBuffer &d, size_t pixels, bool moving = false) : guides(d.as<float4>()) {
         hist_c = guides + 2 * pixels; hist_g = hist_c + pixels; new_c = hist_g + 2 * pixels; new_g = new_c + pixels;
-        xyz = reinterpret_cast<float *>(new_g + 2 * pixels);
+        prev_point = moving ? new_g + 2 * pixels : nullptr;
+        xyz = reinterpret_cast<float *>(new_g + (moving ? 3 : 2) * pixels);
     }
 };
+// d_motion: [counters: hit, miss, moved, degenerate (u64 each), padded to 64 bytes | point: one float4 per pixel | tri: one word | bary: three floats]
+struct MotionLayout {
+    unsigned long long *counts;
+    float4 *point;
+    int32_t *tri;
+    float *bary;
+    static constexpr size_t kHeadBytes = 64;
+    static size_t bytes(size_t pixels) { return kHeadBytes + pixels * (sizeof(float4) + 4 * sizeof(float)); }
+    MotionLayout(const DeviceBuffer &d, size_t pixels) : counts(d.as<unsigned long long>()) {
+        point = reinterpret_cast<float4 *>(d.as<char>() + kHeadBytes); tri = reinterpret_cast<int32_t *>(point + pixels);
+        bary = reinterpret_cast<float *>(tri + pixels);
+    }
+};
+
+const char *motion_rect_error(uint32_t w, uint32_t h, uint32_t ox, uint32_t oy) {
+    if (w == 0 || h == 0 || (uint64_t)w * h > 0x7fffffffull) return "w x h must be in 1 .. 2^31 - 1";
+    if ((uint64_t)ox + w > (1ull << 24) || (uint64_t)oy + h > (1ull << 24)) return "ox + w and oy + h must not exceed 2^24";
+    return nullptr;
+}
+// what the bound motion pass needs of the context
+const char *motion_bound_refusal(const srt_ctx *c) {
+    if (!c->track_motion) return "motion tracking is off (srt_temporal_track_motion first)";
+    if (!c->scene_ready || c->verts == srt_ctx::Verts::Unknown) return "the vertices are unknown (srt_upload_scene or a refit after tracking was switched)";
+    if (!c->camera_ready) return "no camera set";
+    return nullptr;
+}
+// The motion kernel over the w x h rectangle at (ox, oy) on the uploaded scene under `cam`, between the context's two motion events; the
+// outputs are left in MotionLayout(c->d_motion, w * h), which is reserved here.  Enqueues; the caller synchronises.
+int run_motion_kernel(srt_ctx *c, const char *who, const srt_camera_data &cam, const float *v_cur, const float *v_prev, uint32_t w, uint32_t h, uint32_t ox, uint32_t oy) {
+    const size_t pixels = (size_t)w * h;
+    if (const int rc = develop_reserve(c, who, c->d_motion, MotionLayout::bytes(pixels))) return rc;
+    const MotionLayout L(c->d_motion, pixels);
+    c->motion_timed = false;
+    for (hipEvent_t &e : c->motion_ev) if (!e) HIP_TRY_AS(c, who, hipEventCreate(&e));
+    MotionParams p = {};
+    p.nodes = c->d_nodes.as<const float4>(); p.fringe = c->d_fringe.as<const float4>(); p.tris = c->d_tris.as<const float4>();
+    p.root_ref = c->root_ref; p.stack_depth = c->stack_depth; p.n_inner = c->n_inner; p.n_records = c->n_records;
+    p.fringe_stride = c->fringe_stride; p.n_tris = c->n_tris;
+    p.v_cur = v_cur; p.v_prev = v_prev;
+    p.w = w; p.h = h; p.ox = ox; p.oy = oy;
+    for (int k = 0; k < 3; k++) { p.du[k] = cam.pixel_delta_u[k]; p.dv[k] = cam.pixel_delta_v[k]; p.p00[k] = cam.pixel00_loc[k]; p.center[k] = cam.camera_center[k]; }
+    p.out_point = L.point; p.out_tri = L.tri; p.out_bary = L.bary; p.counts = L.counts;
+    HIP_TRY_AS(c, who, hipMemsetAsync(L.counts, 0, 4 * sizeof(unsigned long long), nullptr));
+    HIP_TRY_AS(c, who, hipEventRecord(c->motion_ev[0], nullptr));
+    HIP_TRY_AS(c, who, launch_motion(p, nullptr));
+    HIP_TRY_AS(c, who, hipEventRecord(c->motion_ev[1], nullptr));
+    c->motion_timed = true;
+    return SRT_OK;
+}
+// the pass on the context's own camera and vertex state: V_prev = V_hist, or V_cur when V_hist is none
+int run_motion_bound(srt_ctx *c, const char *who, uint32_t w, uint32_t h, uint32_t ox, uint32_t oy) {
+    if (const int rc = track_verts_to_device(c, who)) return rc;
+    return run_motion_kernel(c, who, c->cam, c->d_verts_cur.as<float>(), c->verts_hist ? c->d_verts_hist.as<float>() : nullptr, w, h, ox, oy);
+}
+int read_motion_counts(srt_ctx *c, const char *who, srt_motion_result *result) {
+    unsigned long long counts[4] = {0, 0, 0, 0};
+    HIP_TRY_AS(c, who, hipMemcpy(counts, MotionLayout(c->d_motion, 0).counts, sizeof(counts), hipMemcpyDeviceToHost));
+    result->hit = counts[0]; result->miss = counts[1]; result->moved = counts[2]; result->degenerate = counts[3];
+    return SRT_OK;
+}
+int read_motion_outputs(srt_ctx *c, const char *who, size_t pixels, float *out_point, int32_t *out_tri, float *out_bary, srt_motion_result *result) {
+    const MotionLayout L(c->d_motion, pixels);
+    if (out_point) HIP_TRY_AS(c, who, hipMemcpy(out_point, L.point, pixels * sizeof(float4), hipMemcpyDeviceToHost));
+    if (out_tri) HIP_TRY_AS(c, who, hipMemcpy(out_tri, L.tri, pixels * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (out_bary) HIP_TRY_AS(c, who, hipMemcpy(out_bary, L.bary, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    srt_motion_result res = {};
+    if (const int rc = read_motion_counts(c, who, &res)) return rc;
+    HIP_TRY_AS(c, who, device_synchronize(c));
+    if (result) *result = res;
+    return SRT_OK;
+}
 
 const char *temporal_cfg_error(const srt_temporal *t) {
     if (!(t->alpha_min > 0.0f && t->alpha_min <= 1.0f)) return "temporal: alpha_min must be in (0, 1]";
@@ -2058,6 +2182,7 @@ int run_temporal_history(srt_ctx *c, const char *who, TemporalParams p, const sr
     const uint32_t rect[4] = {p.w, p.h, c->last_offx, c->last_offy};
     const size_t pixels = (size_t)p.w * p.h;
     res->history_dropped = 0;
+    if (!p.prev_point && c->refits_pending) c->temporal_frames = 0;      // (a tracking context's static call: the history shows geometry that has moved)
     if (c->temporal_frames && memcmp(rect, c->temporal_rect, sizeof(rect)) != 0) {
         c->temporal_frames = 0;
         res->history_dropped = 1;
@@ -2075,6 +2200,7 @@ int run_temporal_history(srt_ctx *c, const char *who, TemporalParams p, const sr
         return rc;
     }
     c->temporal_cur = neu; c->temporal_frames++; c->temporal_cam = c->cam;
+    c->verts_hist = false; c->refits_pending = 0;      // (the new history shows V_cur)
     memcpy(c->temporal_rect, rect, sizeof(rect));
     res->history_frames = c->temporal_frames;
     return SRT_OK;
@@ -2093,6 +2219,8 @@ struct TemporalStage {
     const srt_temporal *cfg;
     bool out_xyz;
     srt_temporal_result res;
+    bool moving = false;      // the *_moving calls: the motion pass on the rectangle first, then the moving stage on its points
+    srt_motion_result mres = {};
 };
 
 }  // namespace
@@ -2100,25 +2228,28 @@ struct TemporalStage {
 int srt_temporal_reset(srt_ctx *c) {
     if (!c) return fail(c, SRT_ERR_INVALID, "srt_temporal_reset: null ctx");
     c->temporal_frames = 0;
+    c->verts_hist = false; c->refits_pending = 0;
     return SRT_OK;
 }
 
-int srt_temporal_kat(srt_ctx *c, const srt_temporal *cfg, const srt_camera_data *cur_cam, const srt_camera_data *prev_cam, const float *xyz_mean,
-                     const float *guides, const float *hist_colour, const float *hist_guides, uint32_t w, uint32_t h, uint32_t ox, uint32_t oy,
-                     float *out_colour, float *out_guides, float *out_motion, srt_temporal_result *result) {
-    const char *who = "srt_temporal_kat";
-    if (!c || !cfg || !cur_cam || !xyz_mean || !guides) return fail(c, SRT_ERR_INVALID, "srt_temporal_kat: null argument");
-    if (!out_colour && !out_guides && !out_motion && !result) return fail(c, SRT_ERR_INVALID, "srt_temporal_kat: no output");
-    if (w == 0 || h == 0 || (uint64_t)w * h > 0x7fffffffull) return fail(c, SRT_ERR_INVALID, "srt_temporal_kat: w x h must be in 1 .. 2^31 - 1");
-    if ((uint64_t)ox + w > (1ull << 24) || (uint64_t)oy + h > (1ull << 24)) return fail(c, SRT_ERR_INVALID, "srt_temporal_kat: ox + w and oy + h must not exceed 2^24");
-    if (const char *why = temporal_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_temporal_kat: ") + why);
+// srt_temporal_kat (moving false, prev_point not read) and srt_temporal_moving_kat (moving true: prev_point[h][w][4], not null)
+static int temporal_kat(srt_ctx *c, const char *who, const srt_temporal *cfg, const srt_camera_data *cur_cam, const srt_camera_data *prev_cam, const float *xyz_mean,
+                        const float *guides, const float *hist_colour, const float *hist_guides, uint32_t w, uint32_t h, uint32_t ox, uint32_t oy,
+                        float *out_colour, float *out_guides, float *out_motion, srt_temporal_result *result, bool moving, const float *prev_point) {
+    const std::string w_(std::string(who) + ": ");
+    if (!c || !cfg || !cur_cam || !xyz_mean || !guides || (moving && !prev_point)) return fail(c, SRT_ERR_INVALID, w_ + "null argument");
+    if (!out_colour && !out_guides && !out_motion && !result) return fail(c, SRT_ERR_INVALID, w_ + "no output");
+    if (w == 0 || h == 0 || (uint64_t)w * h > 0x7fffffffull) return fail(c, SRT_ERR_INVALID, w_ + "w x h must be in 1 .. 2^31 - 1");
+    if ((uint64_t)ox + w > (1ull << 24) || (uint64_t)oy + h > (1ull << 24)) return fail(c, SRT_ERR_INVALID, w_ + "ox + w and oy + h must not exceed 2^24");
+    if (const char *why = temporal_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, w_ + why);
     const bool history = prev_cam && hist_colour && hist_guides;
     HIP_TRY(c, set_device(c));
     const size_t pixels = (size_t)w * h;
     if (const int rc = develop_reserve(c, who, c->d_temporal, TemporalLayout::bytes(pixels))) return rc;
-    if (const int rc = develop_reserve(c, who, c->d_temporal_kat, TemporalKatLayout::bytes(pixels))) return rc;
+    if (const int rc = develop_reserve(c, who, c->d_temporal_kat, TemporalKatLayout::bytes(pixels, moving))) return rc;
     const TemporalLayout L(c->d_temporal, pixels);
-    const TemporalKatLayout K(c->d_temporal_kat, pixels);
+    const TemporalKatLayout K(c->d_temporal_kat, pixels, moving);
+    if (moving) HIP_TRY_AS(c, who, hipMemcpy(K.prev_point, prev_point, pixels * sizeof(float4), hipMemcpyHostToDevice));
     HIP_TRY_AS(c, who, hipMemcpy(K.xyz, xyz_mean, pixels * 3 * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY_AS(c, who, hipMemcpy(K.guides, guides, pixels * 2 * sizeof(float4), hipMemcpyHostToDevice));
     if (history) {
@@ -2129,6 +2260,7 @@ int srt_temporal_kat(srt_ctx *c, const srt_temporal *cfg, const srt_camera_data 
     p.xyz = K.xyz; p.guides = K.guides; p.hist_c = history ? K.hist_c : nullptr; p.hist_g = history ? K.hist_g : nullptr;
     p.new_c = K.new_c; p.new_g = K.new_g; p.w = w; p.h = h; p.ox = ox; p.oy = oy;
     p.out_motion = out_motion ? L.motion : nullptr;
+    p.prev_point = K.prev_point;
     if (const int rc = run_temporal_kernel(c, who, p, cfg, *cur_cam, prev_cam)) return rc;
     if (out_colour) HIP_TRY_AS(c, who, hipMemcpy(out_colour, K.new_c, pixels * sizeof(float4), hipMemcpyDeviceToHost));
     if (out_guides) HIP_TRY_AS(c, who, hipMemcpy(out_guides, K.new_g, pixels * 2 * sizeof(float4), hipMemcpyDeviceToHost));
@@ -2138,6 +2270,83 @@ int srt_temporal_kat(srt_ctx *c, const srt_temporal *cfg, const srt_camera_data 
     res.history_frames = history ? 2u : 1u;
     HIP_TRY_AS(c, who, device_synchronize(c));
     if (result) *result = res;
+    return SRT_OK;
+}
+
+int srt_temporal_kat(srt_ctx *c, const srt_temporal *cfg, const srt_camera_data *cur_cam, const srt_camera_data *prev_cam, const float *xyz_mean,
+                     const float *guides, const float *hist_colour, const float *hist_guides, uint32_t w, uint32_t h, uint32_t ox, uint32_t oy,
+                     float *out_colour, float *out_guides, float *out_motion, srt_temporal_result *result) {
+    return temporal_kat(c, "srt_temporal_kat", cfg, cur_cam, prev_cam, xyz_mean, guides, hist_colour, hist_guides, w, h, ox, oy, out_colour, out_guides, out_motion,
+                        result, false, nullptr);
+}
+
+int srt_temporal_moving_kat(srt_ctx *c, const srt_temporal *cfg, const srt_camera_data *cur_cam, const srt_camera_data *prev_cam, const float *xyz_mean,
+                            const float *guides, const float *hist_colour, const float *hist_guides, uint32_t w, uint32_t h, uint32_t ox, uint32_t oy,
+                            float *out_colour, float *out_guides, float *out_motion, srt_temporal_result *result, const float *prev_point) {
+    return temporal_kat(c, "srt_temporal_moving_kat", cfg, cur_cam, prev_cam, xyz_mean, guides, hist_colour, hist_guides, w, h, ox, oy, out_colour, out_guides,
+                        out_motion, result, true, prev_point);
+}
+
+// ---- surface motion (srt_motion.hip) ---------------------------------------------------------------------------------------------
+int srt_temporal_track_motion(srt_ctx *c, int on) {
+    if (!c) return fail(c, SRT_ERR_INVALID, "srt_temporal_track_motion: null ctx");
+    if ((on != 0) == c->track_motion) return SRT_OK;
+    c->track_motion = on != 0;
+    c->temporal_frames = 0;      // (the history was written under the other rule)
+    c->verts = srt_ctx::Verts::Unknown; c->verts_hist = false; c->refits_pending = 0;
+    c->track_verts.clear();
+    if (!c->track_motion) {      // with tracking off none of this state exists
+        HIP_TRY(c, set_device(c));
+        c->d_verts_cur.release(); c->d_verts_hist.release();
+    }
+    return SRT_OK;
+}
+
+int srt_temporal_tracking(const srt_ctx *c, int *on, uint32_t *refits_pending) {
+    if (!c) return fail(nullptr, SRT_ERR_INVALID, "srt_temporal_tracking: null ctx");
+    if (on) *on = c->track_motion ? 1 : 0;
+    if (refits_pending) *refits_pending = c->refits_pending;
+    return SRT_OK;
+}
+
+int srt_surface_motion(srt_ctx *c, uint32_t w, uint32_t h, uint32_t ox, uint32_t oy, float *out_point, int32_t *out_tri, float *out_bary, srt_motion_result *result) {
+    const char *who = "srt_surface_motion";
+    if (!c) return fail(c, SRT_ERR_INVALID, "srt_surface_motion: null ctx");
+    if (!out_point && !out_tri && !out_bary && !result) return fail(c, SRT_ERR_INVALID, "srt_surface_motion: no output");
+    if (const char *why = motion_rect_error(w, h, ox, oy)) return fail(c, SRT_ERR_INVALID, std::string("srt_surface_motion: ") + why);
+    if (const char *why = motion_bound_refusal(c)) return fail(c, SRT_ERR_INVALID, std::string("srt_surface_motion: ") + why);
+    HIP_TRY(c, set_device(c));
+    if (const int rc = run_motion_bound(c, who, w, h, ox, oy)) return rc;
+    return read_motion_outputs(c, who, (size_t)w * h, out_point, out_tri, out_bary, result);
+}
+
+int srt_surface_motion_kat(srt_ctx *c, const srt_camera_data *cam, const float *prev_verts, const float *cur_verts, size_t n_tris, uint32_t w, uint32_t h, uint32_t ox,
+                           uint32_t oy, float *out_point, int32_t *out_tri, float *out_bary, srt_motion_result *result) {
+    const char *who = "srt_surface_motion_kat";
+    if (!c || !cam || !cur_verts) return fail(c, SRT_ERR_INVALID, "srt_surface_motion_kat: null argument");
+    if (!c->scene_ready) return fail(c, SRT_ERR_INVALID, "srt_surface_motion_kat: no scene uploaded");
+    if (n_tris != c->n_tris) return fail(c, SRT_ERR_INVALID, "srt_surface_motion_kat: n_tris is not the uploaded scene's triangle count");
+    if (!out_point && !out_tri && !out_bary && !result) return fail(c, SRT_ERR_INVALID, "srt_surface_motion_kat: no output");
+    if (const char *why = motion_rect_error(w, h, ox, oy)) return fail(c, SRT_ERR_INVALID, std::string("srt_surface_motion_kat: ") + why);
+    for (const float *v : {cur_verts, prev_verts})
+        for (size_t k = 0; v && k < 9 * n_tris; k++)
+            if (!std::isfinite(v[k])) return fail(c, SRT_ERR_INVALID, "srt_surface_motion_kat: a coordinate is not finite");
+    HIP_TRY(c, set_device(c));
+    const size_t block = 9 * n_tris * sizeof(float);
+    if (const int rc = develop_reserve(c, who, c->d_motion_kat, 2 * block)) return rc;
+    float *d_cur = c->d_motion_kat.as<float>(), *d_prev = d_cur + 9 * n_tris;
+    HIP_TRY_AS(c, who, hipMemcpy(d_cur, cur_verts, block, hipMemcpyHostToDevice));
+    if (prev_verts) HIP_TRY_AS(c, who, hipMemcpy(d_prev, prev_verts, block, hipMemcpyHostToDevice));
+    if (const int rc = run_motion_kernel(c, who, *cam, d_cur, prev_verts ? d_prev : nullptr, w, h, ox, oy)) return rc;
+    return read_motion_outputs(c, who, (size_t)w * h, out_point, out_tri, out_bary, result);
+}
+
+int srt_motion_last_ms(srt_ctx *c, float *ms) {
+    if (!c || !ms) return fail(c, SRT_ERR_INVALID, "srt_motion_last_ms: null argument");
+    if (!c->motion_timed) return fail(c, SRT_ERR_INVALID, "srt_motion_last_ms: no motion kernel has run on this context");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipEventSynchronize(c->motion_ev[1]));
+    HIP_TRY(c, hipEventElapsedTime(ms, c->motion_ev[0], c->motion_ev[1]));
     return SRT_OK;
 }
 
@@ -2260,6 +2469,10 @@ int run_denoise(srt_ctx *c, const char *who, const DenoisePlan &plan, DenoisePre
         TemporalParams tp = ts_out ? *ts_out : TemporalParams{};
         tp.src4 = L.colour[cur]; tp.guides = L.guides; tp.dst4 = L.colour[cur ^ 1u]; tp.w = pre.w; tp.h = pre.h;
         if (ts->out_xyz) tp.out_xyz = TemporalLayout(c->d_temporal, pixels).img[0];
+        if (ts->moving) {
+            if (const int rc = run_motion_bound(c, who, pre.w, pre.h, c->last_offx, c->last_offy)) return rc;
+            tp.prev_point = MotionLayout(c->d_motion, pixels).point;
+        }
         if (const int rc = run_temporal_history(c, who, tp, ts->cfg, &ts->res)) return rc;
         HIP_TRY_AS(c, who, mark());
         cur ^= 1u;
@@ -2340,6 +2553,7 @@ int denoise_features(srt_ctx *c, const char *who, const DenoisePlan &plan, float
             if (host[k] && rect.w && rect.h) HIP_TRY(c, hipMemcpy2D(host[k] + rect.first * ch, pitch, src, src_pitch, row, rect.h, hipMemcpyDeviceToHost));
         }
         if (ts) if (const int rc = read_temporal_counts(c, who, &ts->res)) return rc;
+        if (ts && ts->moving) if (const int rc = read_motion_counts(c, who, &ts->mres)) return rc;
     }
     HIP_TRY(c, device_synchronize(c));
     return SRT_OK;
@@ -2398,35 +2612,54 @@ int srt_denoise_features_ds(srt_ctx *c, const srt_despeckle *despeckle_cfg, cons
     return denoise_features(c, "srt_denoise_features_ds", denoise_plan(denoise_cfg), host, image_width, image_height, despeckle_cfg);
 }
 
-int srt_denoise_features_temporal(srt_ctx *c, const srt_temporal *temporal_cfg, const srt_despeckle *despeckle_cfg, const srt_denoise *denoise_cfg, float *out_xyz,
-                                  float *out_lin, float *out_q, srt_temporal_result *temporal_result, uint32_t image_width, uint32_t image_height) {
-    const char *who = "srt_denoise_features_temporal";
-    if (!c || !temporal_cfg || !denoise_cfg) return fail(c, SRT_ERR_INVALID, "srt_denoise_features_temporal: null argument");
-    if ((!out_xyz && !out_lin && !out_q) || image_width == 0 || image_height == 0) return fail(c, SRT_ERR_INVALID, "srt_denoise_features_temporal: no output / empty image");
-    if (const char *why = denoise_cfg_error(denoise_cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_denoise_features_temporal: ") + why);
-    if (despeckle_cfg) if (const char *why = despeckle_cfg_error(despeckle_cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_denoise_features_temporal: ") + why);
-    if (const char *why = temporal_cfg_error(temporal_cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_denoise_features_temporal: ") + why);
+static int denoise_features_temporal(srt_ctx *c, const char *who, const srt_temporal *temporal_cfg, const srt_despeckle *despeckle_cfg, const srt_denoise *denoise_cfg,
+                                     float *out_xyz, float *out_lin, float *out_q, srt_temporal_result *temporal_result, uint32_t image_width, uint32_t image_height,
+                                     bool moving, srt_motion_result *motion_result) {
+    const std::string w_(std::string(who) + ": ");
+    if (!c || !temporal_cfg || !denoise_cfg) return fail(c, SRT_ERR_INVALID, w_ + "null argument");
+    if ((!out_xyz && !out_lin && !out_q) || image_width == 0 || image_height == 0) return fail(c, SRT_ERR_INVALID, w_ + "no output / empty image");
+    if (const char *why = denoise_cfg_error(denoise_cfg)) return fail(c, SRT_ERR_INVALID, w_ + why);
+    if (despeckle_cfg) if (const char *why = despeckle_cfg_error(despeckle_cfg)) return fail(c, SRT_ERR_INVALID, w_ + why);
+    if (const char *why = temporal_cfg_error(temporal_cfg)) return fail(c, SRT_ERR_INVALID, w_ + why);
+    if (moving) if (const char *why = motion_bound_refusal(c)) return fail(c, SRT_ERR_INVALID, w_ + why);
     float *const host[4] = {out_xyz, out_lin, out_q, nullptr};
     TemporalStage ts = {temporal_cfg, false, {}};
+    ts.moving = moving;
     if (const int rc = denoise_features(c, who, denoise_plan(denoise_cfg), host, image_width, image_height, despeckle_cfg, &ts)) return rc;
     if (temporal_result) *temporal_result = ts.res;
+    if (motion_result) *motion_result = ts.mres;
     return SRT_OK;
 }
 
-int srt_temporal_accum(srt_ctx *c, const srt_temporal *cfg, float *out_xyz, float *out_lin, float *out_q, float *out_len, float *out_motion,
-                       srt_temporal_result *result, uint32_t image_width, uint32_t image_height) {
-    const char *who = "srt_temporal_accum";
-    if (!c || !cfg) return fail(c, SRT_ERR_INVALID, "srt_temporal_accum: null argument");
+int srt_denoise_features_temporal(srt_ctx *c, const srt_temporal *temporal_cfg, const srt_despeckle *despeckle_cfg, const srt_denoise *denoise_cfg, float *out_xyz,
+                                  float *out_lin, float *out_q, srt_temporal_result *temporal_result, uint32_t image_width, uint32_t image_height) {
+    return denoise_features_temporal(c, "srt_denoise_features_temporal", temporal_cfg, despeckle_cfg, denoise_cfg, out_xyz, out_lin, out_q, temporal_result, image_width,
+                                     image_height, false, nullptr);
+}
+
+int srt_denoise_features_temporal_moving(srt_ctx *c, const srt_temporal *temporal_cfg, const srt_despeckle *despeckle_cfg, const srt_denoise *denoise_cfg, float *out_xyz,
+                                         float *out_lin, float *out_q, srt_temporal_result *temporal_result, uint32_t image_width, uint32_t image_height,
+                                         srt_motion_result *motion_result) {
+    return denoise_features_temporal(c, "srt_denoise_features_temporal_moving", temporal_cfg, despeckle_cfg, denoise_cfg, out_xyz, out_lin, out_q, temporal_result,
+                                     image_width, image_height, true, motion_result);
+}
+
+static int temporal_accum(srt_ctx *c, const char *who, const srt_temporal *cfg, float *out_xyz, float *out_lin, float *out_q, float *out_len, float *out_motion,
+                          srt_temporal_result *result, uint32_t image_width, uint32_t image_height, bool moving, srt_motion_result *motion_result) {
+    const std::string w_(std::string(who) + ": ");
+    if (!c || !cfg) return fail(c, SRT_ERR_INVALID, w_ + "null argument");
     if ((!out_xyz && !out_lin && !out_q && !out_len && !out_motion && !result) || image_width == 0 || image_height == 0)
-        return fail(c, SRT_ERR_INVALID, "srt_temporal_accum: no output / empty image");
-    if (const char *why = temporal_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_temporal_accum: ") + why);
+        return fail(c, SRT_ERR_INVALID, w_ + "no output / empty image");
+    if (const char *why = temporal_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, w_ + why);
     const DenoisePlan plan = {};      // (the prepass alone: no level runs)
     if (const int rc = denoise_accumulation_refusal(c, who, plan)) return rc;
+    if (moving) if (const char *why = motion_bound_refusal(c)) return fail(c, SRT_ERR_INVALID, w_ + why);
     HIP_TRY(c, set_device(c));
     // the stage runs on the chunk's rectangle (clipped to the reference grid); the image clips only what is copied out
     const uint32_t w = clipped_w(c), h = clipped_h(c);
     const size_t pixels = (size_t)w * h;
     TemporalStage ts = {cfg, false, {}};
+    ts.moving = moving;
     if (pixels) {
         if (const int rc = develop_reserve(c, who, c->d_temporal, TemporalLayout::bytes(pixels))) return rc;
         const TemporalLayout L(c->d_temporal, pixels);
@@ -2444,10 +2677,22 @@ int srt_temporal_accum(srt_ctx *c, const srt_temporal *cfg, float *out_xyz, floa
             if (host[k] && rect.w && rect.h) HIP_TRY(c, hipMemcpy2D(host[k] + rect.first * ch, pitch, src[k], src_pitch, row, rect.h, hipMemcpyDeviceToHost));
         }
         if (const int rc = read_temporal_counts(c, who, &ts.res)) return rc;
+        if (moving) if (const int rc = read_motion_counts(c, who, &ts.mres)) return rc;
     }
     HIP_TRY(c, device_synchronize(c));
     if (result) *result = ts.res;
+    if (motion_result) *motion_result = ts.mres;
     return SRT_OK;
+}
+
+int srt_temporal_accum(srt_ctx *c, const srt_temporal *cfg, float *out_xyz, float *out_lin, float *out_q, float *out_len, float *out_motion,
+                       srt_temporal_result *result, uint32_t image_width, uint32_t image_height) {
+    return temporal_accum(c, "srt_temporal_accum", cfg, out_xyz, out_lin, out_q, out_len, out_motion, result, image_width, image_height, false, nullptr);
+}
+
+int srt_temporal_accum_moving(srt_ctx *c, const srt_temporal *cfg, float *out_xyz, float *out_lin, float *out_q, float *out_len, float *out_motion,
+                              srt_temporal_result *result, uint32_t image_width, uint32_t image_height, srt_motion_result *motion_result) {
+    return temporal_accum(c, "srt_temporal_accum_moving", cfg, out_xyz, out_lin, out_q, out_len, out_motion, result, image_width, image_height, true, motion_result);
 }
 
 int srt_denoise_features_vg(srt_ctx *c, const srt_denoise_vg *cfg, float *out_xyz, float *out_lin, float *out_q, float *out_var, uint32_t image_width, uint32_t image_height) {
@@ -2729,7 +2974,7 @@ namespace {
 // srt_present_temporal (tcfg: the temporal stage in front of the chain, behind the firefly filter when there is one; ts_result may be null)
 int present_chain(srt_ctx *c, const char *who, const srt_present_cfg *cfg, const srt_despeckle *ds, uint8_t *out_rgba8, size_t pitch_bytes, uint32_t image_width,
                   uint32_t image_height, srt_present_result *result, srt_despeckle_result *ds_result, const srt_temporal *tcfg = nullptr,
-                  srt_temporal_result *ts_result = nullptr) {
+                  srt_temporal_result *ts_result = nullptr, bool moving = false, srt_motion_result *mo_result = nullptr) {
     const std::string w_(std::string(who) + ": ");
     if (!c || !cfg || !out_rgba8) return fail(c, SRT_ERR_INVALID, w_ + "null argument");
     for (const uint32_t r : cfg->reserved) if (r) return fail(c, SRT_ERR_INVALID, w_ + "the reserved words must be 0");
@@ -2770,6 +3015,7 @@ int present_chain(srt_ctx *c, const char *who, const srt_present_cfg *cfg, const
     }
     if (!c->accum.bound()) return fail(c, SRT_ERR_INVALID, w_ + "no accumulation with a pass (srt_accum_reset* and srt_render_chunk_accum first)");
     if (denoised || tcfg) if (const int rc = denoise_accumulation_refusal(c, who, plan)) return rc;      // (the stage needs the guides, whatever the source)
+    if (moving) if (const char *why = motion_bound_refusal(c)) return fail(c, SRT_ERR_INVALID, w_ + why);
     if (ds && (c->rank != 0 || c->world != 1))
         return fail(c, SRT_ERR_UNSUPPORTED, w_ + "needs the whole chunk on this context (partition (0, 1)): pixels of other ranks read +0");
     if (developed && !c->accum.spectral()) return fail(c, SRT_ERR_INVALID, w_ + "SRT_PRESENT_DEVELOP needs a spectral accumulation (srt_accum_reset_spectral*)");
@@ -2782,6 +3028,7 @@ int present_chain(srt_ctx *c, const char *who, const srt_present_cfg *cfg, const
     srt_present_result res = {};
     srt_despeckle_result ds_res = {};
     TemporalStage ts = {tcfg, !denoised, {}};
+    ts.moving = moving;
     if (pixels) {
         if (const int rc = develop_reserve(c, who, c->d_expose, ExposeLayout::kBytes)) return rc;
         if (const int rc = develop_reserve(c, who, c->d_present, PresentLayout::bytes(pixels, developed))) return rc;
@@ -2837,11 +3084,13 @@ int present_chain(srt_ctx *c, const char *who, const srt_present_cfg *cfg, const
         if (const int rc = run_present(c, who, p, &cfg->tone, gain, place.w, place.h, place.w && place.h ? first : out_rgba8, pitch_bytes, &res.tone)) return rc;
         if (ds) if (const int rc = read_despeckle_counts(c, who, &ds_res)) return rc;
         if (tcfg) if (const int rc = read_temporal_counts(c, who, &ts.res)) return rc;
+        if (moving) if (const int rc = read_motion_counts(c, who, &ts.mres)) return rc;
     }
     HIP_TRY(c, device_synchronize(c));
     if (result) *result = res;
     if (ds_result) *ds_result = ds_res;
     if (ts_result) *ts_result = ts.res;
+    if (mo_result) *mo_result = ts.mres;
     return SRT_OK;
 }
 
@@ -2863,6 +3112,14 @@ int srt_present_temporal(srt_ctx *c, const srt_present_cfg *present_cfg, const s
     if (!temporal_cfg) return fail(c, SRT_ERR_INVALID, "srt_present_temporal: null argument");
     return present_chain(c, "srt_present_temporal", present_cfg, despeckle_cfg, out_rgba8, pitch_bytes, image_width, image_height, result, nullptr, temporal_cfg,
                          temporal_result);
+}
+
+int srt_present_temporal_moving(srt_ctx *c, const srt_present_cfg *present_cfg, const srt_temporal *temporal_cfg, const srt_despeckle *despeckle_cfg, uint8_t *out_rgba8,
+                                size_t pitch_bytes, uint32_t image_width, uint32_t image_height, srt_present_result *result, srt_temporal_result *temporal_result,
+                                srt_motion_result *motion_result) {
+    if (!temporal_cfg) return fail(c, SRT_ERR_INVALID, "srt_present_temporal_moving: null argument");
+    return present_chain(c, "srt_present_temporal_moving", present_cfg, despeckle_cfg, out_rgba8, pitch_bytes, image_width, image_height, result, nullptr, temporal_cfg,
+                         temporal_result, true, motion_result);
 }
 
 int srt_present_kat(srt_ctx *c, const srt_tone *tone, const float *xyz_mean, uint32_t w, uint32_t h, uint8_t *out_rgba8, srt_tone_result *result) {

@@ -438,8 +438,30 @@ struct TemporalParams {
     float4 *dst4;
     float *out_xyz, *out_lin, *out_q, *out_len, *out_motion;
     unsigned long long *counts;
+    // the moving variant (srt_temporal_*_moving; null: the static stage): per pixel (Pprev, valid) of the surface-motion pass, which a hit
+    // pixel projects in the place of the point it would reconstruct from the distance guide
+    const float4 *prev_point;
 };
 hipError_t launch_temporal(const TemporalParams &p, hipStream_t st);
+// The surface-motion pass (srt_motion.hip; stated in srt_c_api.h at srt_surface_motion) over the row-major w x h rectangle at image offset
+// (ox, oy): the closest hit of every pixel's centre ray on the scene images (nodes, fringe, tris: RenderParams'), then the hit point moved
+// from the triangle's row of v_cur to its row of v_prev (9 floats per triangle each; v_prev null: nothing moved).  Outputs, any may be
+// null: out_point (Pprev, valid) one float4 per pixel, out_tri one word, out_bary (t, beta, gamma) three floats.  counts[4] (hit, miss,
+// moved, degenerate) are ADDED to.
+struct MotionParams {
+    const float4 *nodes, *fringe, *tris;
+    int root_ref, stack_depth, n_inner, n_records;
+    uint32_t fringe_stride, n_tris;
+    const float *v_cur, *v_prev;
+    uint32_t w, h, ox, oy;
+    uint32_t tiles_x, stack_slots;      // filled in by the launcher
+    float du[3], dv[3], p00[3], center[3];
+    float4 *out_point;
+    int32_t *out_tri;
+    float *out_bary;
+    unsigned long long *counts;
+};
+hipError_t launch_motion(const MotionParams &p, hipStream_t st);
 // BVH refit (srt_refit.hip; stated in srt_c_api.h at srt_scene_refit and srt_refit_vertices).  verts: 9 floats per triangle.  The topology
 // tables, made on the host at srt_upload_scene: tri_tab two words per triangle -- its raw aa_plane, then its slot 2 f + side, the FRINGE
 // record f (an index into the FRINGE image) and the side whose block holds the triangle's copy, kRefitNoSlot when the root is a leaf; child

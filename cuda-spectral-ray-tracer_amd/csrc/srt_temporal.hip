@@ -7,7 +7,7 @@
 // rounded division and square root): every product, quotient and root below is rounded once, in the order written, so the restatement
 // predicts the device's bits.
 //
-// One kernel, temporal_kernel<SRC>: a 256-lane workgroup handles a 32 x 8 tile of the row-major w x h rectangle, one pixel per lane.  A
+// One kernel, temporal_kernel<SRC> (two load paths, each static or moving): a 256-lane workgroup handles a 32 x 8 tile of the row-major w x h rectangle, one pixel per lane.  A
 // wave owns a 16 x 4 sub-tile (lane l at (l & 15, l >> 4)), so that under a small camera move the wave's twelve 16-byte gathers -- four
 // taps of three float4 history images -- fall on about five neighbouring rows of three 128-byte lines each, whichever way the picture moves.
 //   Arithmetic. temporal_pixel() holds everything from the centre ray to (o, len', motion, class); both load paths call it.
@@ -29,7 +29,9 @@ constexpr uint32_t kTpTileW = 32, kTpTileH = 8, kTpThreads = kTpTileW * kTpTileH
 constexpr uint32_t kTpCounters = 5;
 constexpr float kTpNaN = __builtin_nanf("");
 
-enum TemporalSource { Quads = 0, Rows = 1 };
+// bit 1 of SRC: the moving variant (srt_temporal_*_moving), which projects the tracked point P.prev_point[p] of a hit pixel.  The flag
+// rides in SRC so that the two static instantiations keep their symbols, and with them a by-symbol comparison of their machine code.
+enum TemporalSource { Quads = 0, Rows = 1, QuadsMoving = 2, RowsMoving = 3 };
 
 __device__ __forceinline__ V3 ld3(const float (&a)[3]) { return mk(a[0], a[1], a[2]); }
 __device__ __forceinline__ bool finite3(float x, float y, float z) { return ((x - x) == 0.0f) & ((y - y) == 0.0f) & ((z - z) == 0.0f); }
@@ -42,6 +44,8 @@ struct TemporalOut {
 
 // The stage of pixel (x, y) with XYZ mean c and guides g0 = (N, z), g1 = (A, coverage), as srt_c_api.h states it: class, centre ray, point
 // or direction, projection into the previous camera, bilinear gather with the acceptance tests, the result classes in their order.
+// MOVING: step 3 of a hit pixel reads M = P.prev_point[p] -- M.w == 1: v = M.xyz - center'; otherwise step 4 counts as failed.
+template <bool MOVING>
 __device__ __forceinline__ TemporalOut temporal_pixel(const TemporalParams &P, uint32_t x, uint32_t y, V3 c, float4 g0, float4 g1) {
     TemporalOut r;
     r.o = c; r.len = 1.0f; r.mu = kTpNaN; r.mv = kTpNaN;
@@ -57,17 +61,25 @@ __device__ __forceinline__ TemporalOut temporal_pixel(const TemporalParams &P, u
         const V3 d = pc - centre;
         V3 v = d;
         float zexp = 0.0f;
+        bool tracked = true;
         if (hit) {
-            const float L = sqrtf(dot(d, d));
-            const float s = g0.w / L;
-            const V3 pt = centre + s * d;
-            v = pt - ld3(P.pcenter);
-            zexp = sqrtf(dot(v, v));
+            if constexpr (MOVING) {
+                const float4 m = P.prev_point[(size_t)y * P.w + x];
+                tracked = m.w == 1.0f;
+                v = mk(m.x, m.y, m.z) - ld3(P.pcenter);
+                zexp = sqrtf(dot(v, v));
+            } else {
+                const float L = sqrtf(dot(d, d));
+                const float s = g0.w / L;
+                const V3 pt = centre + s * d;
+                v = pt - ld3(P.pcenter);
+                zexp = sqrtf(dot(v, v));
+            }
         }
         const V3 pn = ld3(P.pn), pe = ld3(P.pe);
         const float den = dot(v, pn);
         const float t = P.pk / den;
-        projected = t > 0.0f;
+        projected = MOVING ? (t > 0.0f) & tracked : t > 0.0f;
         if (projected) {
             const V3 q = t * v - pe;
             const float u = dot(q, ld3(P.pbu)) - (float)P.ox;
@@ -143,14 +155,14 @@ __global__ __launch_bounds__(kTpThreads) void temporal_kernel(const TemporalPara
         const size_t pix = (size_t)y * P.w + x;
         V3 c;
         float w4 = 0.0f;
-        if constexpr (SRC == Quads) {
+        if constexpr ((SRC & 1) == Quads) {
             const float4 v = P.src4[pix];
             c = mk(v.x, v.y, v.z); w4 = v.w;
         } else {
             c = mk(P.xyz[3 * pix + 0], P.xyz[3 * pix + 1], P.xyz[3 * pix + 2]);
         }
         const float4 g0 = P.guides[2 * pix + 0], g1 = P.guides[2 * pix + 1];
-        const TemporalOut r = temporal_pixel(P, x, y, c, g0, g1);
+        const TemporalOut r = temporal_pixel<(SRC & 2) != 0>(P, x, y, c, g0, g1);
         n[0] = r.blended; n[1] = r.fresh; n[2] = r.offscreen; n[3] = r.rejected; n[4] = r.nonfinite;
         P.new_c[pix] = make_float4(r.o.x, r.o.y, r.o.z, r.len);
         P.new_g[2 * pix + 0] = g0; P.new_g[2 * pix + 1] = g1;
@@ -186,7 +198,9 @@ hipError_t launch_temporal(const TemporalParams &p_in, hipStream_t st) {
     p.tiles_x = (p.w + kTpTileW - 1u) / kTpTileW;
     const uint64_t blocks = (uint64_t)p.tiles_x * ((p.h + kTpTileH - 1u) / kTpTileH);
     if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    if (p.src4) hipLaunchKernelGGL((temporal_kernel<Quads>), dim3((uint32_t)blocks), dim3(kTpThreads), 0, st, p);
+    if (p.prev_point && p.src4) hipLaunchKernelGGL((temporal_kernel<QuadsMoving>), dim3((uint32_t)blocks), dim3(kTpThreads), 0, st, p);
+    else if (p.prev_point) hipLaunchKernelGGL((temporal_kernel<RowsMoving>), dim3((uint32_t)blocks), dim3(kTpThreads), 0, st, p);
+    else if (p.src4) hipLaunchKernelGGL((temporal_kernel<Quads>), dim3((uint32_t)blocks), dim3(kTpThreads), 0, st, p);
     else hipLaunchKernelGGL((temporal_kernel<Rows>), dim3((uint32_t)blocks), dim3(kTpThreads), 0, st, p);
     return hipGetLastError();
 }

@@ -75,7 +75,8 @@ class Renderer:
         scene, its topology kept -- no scene build, no upload.  A numpy array goes through the host entry; a torch tensor must live on
         this renderer's device, be contiguous and float32, and goes through the device-pointer entry without visiting the host (its
         stream is waited for first).  Shapes and dtypes are checked here, before any device is touched.  Afterwards the accumulation
-        and the temporal history are invalid, as after upload_scene; camera and device parameters stay."""
+        and the temporal history are invalid, as after upload_scene (a renderer that tracks motion keeps the history: track_motion);
+        camera and device parameters stay."""
         if isinstance(vertices, np.ndarray):
             v = refit_vertices("Renderer.refit", vertices)
             self._ck(B.lib().srt_refit_vertices(self._h, B.fptr(v), v.shape[0]))
@@ -472,6 +473,113 @@ class Renderer:
                                               4 * image_width, image_width, image_height, C.byref(res), C.byref(tres)))
         return dict(rgba=out, meter=_meter_dict(res.meter) if gain is None else None,
                     clip=dict(blown=res.tone.blown, crushed=res.tone.crushed, nonfinite=res.tone.nonfinite), temporal=temporal_stats(tres))
+
+    # ---- surface motion: the temporal history carried across refits (srt_c_api.h, "Surface motion") ----
+    def track_motion(self, on=True):
+        """switch motion tracking (srt_temporal_track_motion; off by default): with it on the context keeps the vertices of its scene and
+        of its temporal history, a refit KEEPS the history, and the *_moving calls reproject across it.  Switching drops the history and
+        leaves the vertices unknown until the next upload_scene or refit."""
+        self._ck(B.lib().srt_temporal_track_motion(self._h, 1 if on else 0))
+
+    @property
+    def tracking(self):
+        """(on, refits_pending) of srt_temporal_tracking: the switch, and the refits since the history was last written"""
+        on, n = C.c_int(), C.c_uint32()
+        self._ck(B.lib().srt_temporal_tracking(self._h, C.byref(on), C.byref(n)))
+        return bool(on.value), n.value
+
+    def surface_motion(self, w, h, ox=0, oy=0):
+        """the surface-motion pass on the context's camera, scene and tracked vertices (srt_surface_motion) over the w x h rectangle at
+        image offset (ox, oy): dict(point (h, w, 4) float32 -- where the surface point the pixel's centre ray sees lay when the history
+        was written, and 1 where that is known --, tri (h, w) int32 -- the triangle, -1 for a miss --, bary (h, w, 3) float32 --
+        (t, beta, gamma) --, stats = motion_stats).  Needs tracking on and known vertices; only reads."""
+        w, h, ox, oy = _motion_rect("surface_motion", w, h, ox, oy)
+        point, tri, bary, res = np.zeros((h, w, 4), np.float32), np.zeros((h, w), np.int32), np.zeros((h, w, 3), np.float32), B.MotionResult()
+        self._ck(B.lib().srt_surface_motion(self._h, w, h, ox, oy, B.fptr(point), tri.ctypes.data_as(C.POINTER(C.c_int32)), B.fptr(bary), C.byref(res)))
+        return dict(point=point, tri=tri, bary=bary, stats=motion_stats(res))
+
+    def surface_motion_kat(self, cam, cur_verts, w, h, ox=0, oy=0, prev_verts=None):
+        """the same kernel on the uploaded scene, the camera `cam` and explicit vertex arrays (srt_surface_motion_kat): cur_verts
+        (n_tris, 3, 3) float32 MUST be the vertices the uploaded scene was made from (the caller's promise), prev_verts the same
+        triangles when the history was written (None: nothing moved).  The dict of surface_motion.  Works with tracking off and
+        touches no context state."""
+        if not isinstance(cam, B.CameraData):
+            raise TypeError("surface_motion_kat: cam is no CameraData (camera_init makes one), got %r" % type(cam).__name__)
+        w, h, ox, oy = _motion_rect("surface_motion_kat", w, h, ox, oy)
+        cur = refit_vertices("surface_motion_kat: cur_verts", cur_verts)
+        prev = None
+        if prev_verts is not None:
+            prev = refit_vertices("surface_motion_kat: prev_verts", prev_verts)
+            if prev.shape != cur.shape:
+                raise ValueError("surface_motion_kat: prev_verts %r and cur_verts %r differ in shape" % (prev.shape, cur.shape))
+        point, tri, bary, res = np.zeros((h, w, 4), np.float32), np.zeros((h, w), np.int32), np.zeros((h, w, 3), np.float32), B.MotionResult()
+        self._ck(B.lib().srt_surface_motion_kat(self._h, C.byref(cam), None if prev is None else B.fptr(prev), B.fptr(cur), cur.shape[0], w, h, ox, oy,
+                                                B.fptr(point), tri.ctypes.data_as(C.POINTER(C.c_int32)), B.fptr(bary), C.byref(res)))
+        return dict(point=point, tri=tri, bary=bary, stats=motion_stats(res))
+
+    def motion_last_ms(self):
+        """kernel-only ms of the context's last motion kernel (srt_motion_last_ms)"""
+        ms = C.c_float()
+        self._ck(B.lib().srt_motion_last_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def temporal_moving(self, image_width, image_height, **cfg):
+        """temporal() across refits (srt_temporal_accum_moving): the motion pass on the accumulation's rectangle, then the stage on the
+        points it tracked.  The dict of temporal() plus surface, the dict of motion_stats.  Needs tracking on and known vertices."""
+        t, res, mres = _temporal_cfg("temporal_moving", cfg), B.TemporalResult(), B.MotionResult()
+        out = [np.zeros((image_height, image_width, 3), np.float32) for _ in range(3)]
+        length, motion = np.zeros((image_height, image_width), np.float32), np.zeros((image_height, image_width, 2), np.float32)
+        self._ck(B.lib().srt_temporal_accum_moving(self._h, C.byref(t), B.fptr(out[0]), B.fptr(out[1]), B.fptr(out[2]), B.fptr(length), B.fptr(motion),
+                                                   C.byref(res), image_width, image_height, C.byref(mres)))
+        return dict(xyz=out[0], lin=out[1], fb=out[2], len=length, motion=motion, stats=temporal_stats(res), surface=motion_stats(mres))
+
+    def temporal_moving_kat(self, cur_cam, xyz_mean, guides, prev_point, prev_cam=None, hist_colour=None, hist_guides=None, offx=0, offy=0, **cfg):
+        """temporal_kat with the tracked points prev_point (h, w, 4) = (Pprev, valid) of surface_motion (srt_temporal_moving_kat): a hit
+        pixel projects its tracked point, or has no history where valid is not 1.  The dict of temporal_kat."""
+        t, res = _temporal_cfg("temporal_moving_kat", cfg), B.TemporalResult()
+        img = _xyz_image("temporal_moving_kat", xyz_mean)
+        g = np.ascontiguousarray(guides, np.float32)
+        if g.shape != img.shape[:2] + (8,):
+            raise ValueError("temporal_moving_kat: needs guides %r, got %r" % (img.shape[:2] + (8,), g.shape))
+        pp = np.ascontiguousarray(prev_point, np.float32)
+        if pp.shape != img.shape[:2] + (4,):
+            raise ValueError("temporal_moving_kat: needs prev_point %r, got %r" % (img.shape[:2] + (4,), pp.shape))
+        given = [v is not None for v in (prev_cam, hist_colour, hist_guides)]
+        if any(given) and not all(given):
+            raise ValueError("temporal_moving_kat: a history is prev_cam, hist_colour and hist_guides together")
+        hc = hg = None
+        if all(given):
+            hc, hg = np.ascontiguousarray(hist_colour, np.float32), np.ascontiguousarray(hist_guides, np.float32)
+            if hc.shape != img.shape[:2] + (4,) or hg.shape != g.shape:
+                raise ValueError("temporal_moving_kat: needs hist_colour %r and hist_guides %r, got %r and %r" % (img.shape[:2] + (4,), g.shape, hc.shape, hg.shape))
+        colour, og, motion = np.zeros(img.shape[:2] + (4,), np.float32), np.zeros(g.shape, np.float32), np.zeros(img.shape[:2] + (2,), np.float32)
+        self._ck(B.lib().srt_temporal_moving_kat(self._h, C.byref(t), C.byref(cur_cam), C.byref(prev_cam) if all(given) else None, B.fptr(img), B.fptr(g),
+                                                 B.fptr(hc) if all(given) else None, B.fptr(hg) if all(given) else None, img.shape[1], img.shape[0],
+                                                 int(offx), int(offy), B.fptr(colour), B.fptr(og), B.fptr(motion), C.byref(res), B.fptr(pp)))
+        return dict(colour=colour, guides=og, motion=motion, stats=temporal_stats(res))
+
+    def denoise_temporal_moving(self, image_width, image_height, temporal=None, despeckle=None, **cfg):
+        """denoise_temporal across refits (srt_denoise_features_temporal_moving): its dict plus surface, the dict of motion_stats"""
+        c, t, res, mres = denoise_config(**cfg), _temporal_cfg("denoise_temporal_moving", temporal), B.TemporalResult(), B.MotionResult()
+        d = None if despeckle is None else self._despeckle_cfg("denoise_temporal_moving", despeckle)
+        out = [np.zeros((image_height, image_width, 3), np.float32) for _ in range(3)]
+        self._ck(B.lib().srt_denoise_features_temporal_moving(self._h, C.byref(t), None if d is None else C.byref(d), C.byref(c), B.fptr(out[0]), B.fptr(out[1]),
+                                                              B.fptr(out[2]), C.byref(res), image_width, image_height, C.byref(mres)))
+        return dict(xyz=out[0], lin=out[1], fb=out[2], stats=temporal_stats(res), surface=motion_stats(mres))
+
+    def present_temporal_moving(self, image_width, image_height, source="accum", gain=None, temporal=None, despeckle=None, **cfg):
+        """present_temporal across refits (srt_present_temporal_moving): its dict plus surface, the dict of motion_stats"""
+        p, res, tres, mres = present_config(source, gain, **cfg), B.PresentResult(), B.TemporalResult(), B.MotionResult()
+        if source not in ("accum", "denoise"):
+            raise ValueError("present_temporal_moving: source must be \"accum\" or \"denoise\", got %r" % (source,))
+        t = _temporal_cfg("present_temporal_moving", temporal)
+        d = None if despeckle is None else self._despeckle_cfg("present_temporal_moving", despeckle)
+        out = np.zeros((image_height, image_width, 4), np.uint8)
+        self._ck(B.lib().srt_present_temporal_moving(self._h, C.byref(p), C.byref(t), None if d is None else C.byref(d), out.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                     4 * image_width, image_width, image_height, C.byref(res), C.byref(tres), C.byref(mres)))
+        return dict(rgba=out, meter=_meter_dict(res.meter) if gain is None else None,
+                    clip=dict(blown=res.tone.blown, crushed=res.tone.crushed, nonfinite=res.tone.nonfinite), temporal=temporal_stats(tres),
+                    surface=motion_stats(mres))
 
     def accum_reset_features(self):
         """start a FEATURED accumulation (srt_c_api.h): like accum_reset, and each later pass also adds, at the first hit of every
@@ -1618,6 +1726,27 @@ def temporal_stats(res):
                 history_frames=res.history_frames, history_dropped=bool(res.history_dropped))
 
 
+def motion_stats(res):
+    """srt_motion_result as a dict: the pixels whose centre ray hit and missed, the hit pixels whose triangle moved, and of those the
+    degenerate ones (no previous point could be formed)"""
+    return dict(hit=res.hit, miss=res.miss, moved=res.moved, degenerate=res.degenerate)
+
+
+def _motion_rect(who, w, h, ox, oy):
+    """the rectangle of a motion pass as the library checks it (ValueError), before any library call"""
+    vals = []
+    for name, v in (("w", w), ("h", h), ("ox", ox), ("oy", oy)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise ValueError("%s: %s must be a non-negative integer, got %r" % (who, name, v))
+        vals.append(int(v))
+    w, h, ox, oy = vals
+    if w == 0 or h == 0 or w * h >= 2 ** 31:
+        raise ValueError("%s: w x h must be in 1 .. 2^31 - 1, got %d x %d" % (who, w, h))
+    if ox + w > 2 ** 24 or oy + h > 2 ** 24:
+        raise ValueError("%s: ox + w and oy + h must not exceed 2^24, got %d and %d" % (who, ox + w, oy + h))
+    return w, h, ox, oy
+
+
 def render_interactive(scene, cameras, width, height, spp, bounce_limit, denoise=True, despeckle=None, temporal=None, seed=1984, device=0, renderer=None,
                        **cfg):
     """A moving camera on one GPU: for every camera of `cameras` (CameraData, at least one) set_camera, accum_reset_features, one pass of
@@ -1665,13 +1794,17 @@ def _interactive_frames(scene, cams, width, height, spp, bounce_limit, seed, dev
 
 
 def render_animated(scene, cam, frames, width, height, spp, bounce_limit, denoise=True, despeckle=None, temporal=None, seed=1984, device=0,
-                    renderer=None, **cfg):
+                    renderer=None, track_motion=False, **cfg):
     """Moving geometry on one GPU: the scene is uploaded once; for every vertex array of `frames` ((n_tris, 3, 3) float32: numpy, or a
     torch tensor on the device -- Renderer.refit) refit, accum_reset_features, one pass of `spp` samples, then the chained presentation
     call of render_interactive (denoise, despeckle, temporal and cfg are its arguments).  The temporal history is dropped at every refit --
     the reprojection knows camera motion, not object motion -- so every frame is a first frame to the temporal stage.  A generator of
     (index, result, features, picture, stats), as render_interactive's.  The scene object itself is not changed.  Everything that can be
-    checked without a device is checked here."""
+    checked without a device is checked here.
+    track_motion=True switches motion tracking on before the upload (Renderer.track_motion; switched back off at the end) and uses the
+    *_moving chained call: the history survives the refits, every pixel reprojected along the motion of the triangle it sees."""
+    if not isinstance(track_motion, (bool, np.bool_)):
+        raise TypeError("render_animated: track_motion must be a bool, got %r" % (track_motion,))
     if not isinstance(cam, B.CameraData):
         raise TypeError("render_animated: cam is no CameraData (camera_init makes one), got %r" % type(cam).__name__)
     frames = list(frames)
@@ -1696,7 +1829,29 @@ def render_animated(scene, cam, frames, width, height, spp, bounce_limit, denois
         raise TypeError("render_animated: %s given with denoise=False, which runs no denoiser" % ", ".join(sorted(cfg)))
     elif dkw is not None:
         raise ValueError("render_animated: despeckle given with denoise=False: the firefly filter runs in the denoiser's chain")
+    if track_motion:
+        return _animated_frames_tracked(scene, cam, frames, width, height, sched[0], bounce_limit, seed, device, renderer, bool(denoise), dkw, tkw, cfg)
     return _animated_frames(scene, cam, frames, width, height, sched[0], bounce_limit, seed, device, renderer, bool(denoise), dkw, tkw, cfg)
+
+
+def _animated_frames_tracked(scene, cam, frames, width, height, spp, bounce_limit, seed, device, renderer, denoise, despeckle, temporal, cfg):
+    r = renderer or Renderer(device)
+    try:
+        r.track_motion(True)      # (before the upload: the upload is what makes the vertices known)
+        with _image_session(scene, cam, width, height, spp, bounce_limit, seed, device, r):
+            for k, v in enumerate(frames):
+                r.refit(v)      # (invalidates the accumulation; the temporal history stays)
+                r.accum_reset_features()
+                r.render_chunk_accum(width, height, spp)
+                r.scatter_tiles()
+                picture = (r.denoise_temporal_moving(width, height, temporal, despeckle, **cfg) if denoise
+                           else r.temporal_moving(width, height, **temporal))
+                yield k, _collect(r, width, height), r.read_features(width, height), picture, picture["stats"]
+    finally:
+        if r._h:
+            r.track_motion(False)
+        if renderer is None:
+            r.close()
 
 
 def _animated_frames(scene, cam, frames, width, height, spp, bounce_limit, seed, device, renderer, denoise, despeckle, temporal, cfg):

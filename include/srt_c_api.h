@@ -245,7 +245,7 @@ SRT_API int srt_upload_scene(srt_ctx *ctx, const srt_scene *s);
  * normal may carry other bits than the host's.  The images therefore equal those srt_upload_scene makes of the host-refitted scene AS
  * VALUES: two words are equal when their bits are equal, or both are NaN, or both are zero.  Ray hits and frames are bit-identical.
  *   A successful refit invalidates what srt_upload_scene invalidates -- the accumulation (the next pass fails until a reset), the temporal
- * history, the scheduler's remembered queues -- and leaves camera, device parameters, partition, knobs and RNG state alone.  Both entries
+ * history (kept on a context that tracks motion: "Surface motion" below), the scheduler's remembered queues -- and leaves camera, device parameters, partition, knobs and RNG state alone.  Both entries
  * work on the NULL stream under the order of a context's calls, and both synchronise.  verts_dev is a device pointer (a torch tensor's
  * data_ptr(), say) whose contents must be complete, or ordered before the NULL stream, when the call is made.
  *   Refused with SRT_ERR_INVALID and nothing changed on the device: no scene uploaded (srt_set_test_knobs ends an upload too), a null
@@ -253,7 +253,8 @@ SRT_API int srt_upload_scene(srt_ctx *ctx, const srt_scene *s);
  * context's state; a refused srt_refit_vertices_dev may have allocated the context's scratch block, which the validation kernel counts
  * into.  A failed allocation: SRT_ERR_HIP.  The topology
  * tables are made on the host at srt_upload_scene and reach the device with the first refit; srt_upload_scene itself enqueues and
- * allocates nothing for them.  Out of scope as at srt_scene_refit: topology changes, object motion vectors, materials.
+ * allocates nothing for them.  Out of scope as at srt_scene_refit: topology changes, object motion vectors (srt_temporal_track_motion
+ * adds them, opt-in), materials.
  *   srt_refit_last_ms     kernel-only times in ms, from HIP events, of the context's last refit: the triangle kernel, all level launches
  *                         together, and their number.  Any pointer may be NULL.  SRT_ERR_INVALID before a refit has run.
  *   srt_read_scene_image  read-back of one scene image for tests and tools; synchronises, only reads.  *n_bytes receives the image's size
@@ -1028,6 +1029,103 @@ SRT_API int srt_present_temporal(srt_ctx *ctx, const srt_present_cfg *present_cf
                                  const srt_despeckle *despeckle_cfg, uint8_t *out_rgba8, size_t pitch_bytes, uint32_t image_width,
                                  uint32_t image_height, srt_present_result *result, srt_temporal_result *temporal_result);
 SRT_API int srt_temporal_last_ms(srt_ctx *ctx, float *ms);
+
+/* Surface motion (no reference counterpart; kernel in csrc/srt_motion.hip): the temporal history carried across refits.  The stage above
+ * knows camera motion only, so a refit drops its history.  With TRACKING on, a context keeps the vertices its scene images were last made
+ * from and the vertices at the moment the history was written; one pass finds, for every pixel, the surface point its centre ray sees and
+ * moves that point back to where the same point of the same triangle lay then; the *_moving variants of the temporal calls project that
+ * point in the place of the one they would reconstruct from the distance guide.  The same pass is a primary-visibility buffer (triangle,
+ * barycentrics, distance per pixel) for picking and compositing.  Tracking is opt-in and off by default: with it off nothing of this
+ * state exists and every call above behaves as stated above.
+ * Operation by operation -- fp32, not contracted, left to right, dot products as the temporal section defines them; the restatement is
+ * tests/surface_motion_reference.py, which the device equals in every bit and every counter -- for pixel (x, y) of the w x h rectangle at
+ * image offset (ox, oy), camera C, the vertex blocks V_cur and V_prev (n_tris x 9 floats, row k = triangle k = the index srt_trace_rays
+ * reports = srt_refit_vertices' row k):
+ *     1. Centre ray, as temporal step 2:  fi = (float)(ox + x);  fj = (float)(oy + y);  pc = (p00 + fi * du) + fj * dv;  d = pc - center;
+ *          origin center.
+ *     2. Closest hit:  (t, k) as srt_trace_rays answers the ray (center, d): the same traversal on the same records.  t is in units of
+ *          the unnormalised d; k = -1 is a miss.
+ *     3. Miss:  point = (0, 0, 0, 0), tri = -1, bary = (0, 0, 0).  No vertex row is read.
+ *     4. Hit:  P = center + t * d;  (a, b, c) = row k of V_cur, (a', b', c') = row k of V_prev;
+ *          e1 = b - a;  e2 = c - a;  r = P - a;  d11 = e1.e1;  d12 = e1.e2;  d22 = e2.e2;  r1 = r.e1;  r2 = r.e2;
+ *          den = d11 * d22 - d12 * d12;  beta = (d22 * r1 - d12 * r2) / den;  gamma = (d11 * r2 - d12 * r1) / den;
+ *          Da = a' - a;  Db = b' - b;  Dc = c' - c;  moved = one of their nine components is != 0.
+ *          Not moved:  Pprev = P (its bits), valid = 1.
+ *          Moved:  disp = (Da + beta * (Db - Da)) + gamma * (Dc - Da);  Pprev = P + disp;  valid = den > 0 and beta, gamma and the three
+ *            components of Pprev are finite ((v - v) == 0).
+ *          point = (Pprev, valid ? 1.0f : 0.0f), the three coordinates +0 when not valid;  tri = k;  bary = (t, beta, gamma).
+ *   Counters (integers: a wave sum, the workgroup's word in LDS, one atomic per workgroup and non-zero counter): hit, miss, moved (hit
+ *   pixels whose triangle moved), degenerate (moved and not valid).  A triangle that is degenerate in V_prev alone stays valid: den is
+ *   V_cur's.
+ * The vertex state of a tracking context, always in the order of the context's calls on the NULL stream:
+ *   srt_temporal_track_motion(on)  switches tracking (default 0).  Switching on or off drops the temporal history and forgets both blocks:
+ *                           until the next srt_upload_scene or successful refit the vertices are UNKNOWN, and srt_surface_motion and the
+ *                           three bound *_moving calls refuse with SRT_ERR_INVALID.  Setting the value it already has changes nothing.
+ *   srt_temporal_tracking   reports the switch and refits_pending, the successful refits since the history was last written.
+ *   srt_upload_scene        V_cur = the scene's vertices, kept on the host until first use (an upload enqueues and allocates nothing for
+ *                           this, as for the refit's tables); V_hist = none; the history is dropped, as always.
+ *   a successful refit      V_cur = the new vertices (a device-to-device copy from srt_refit_vertices_dev, host-to-device otherwise); if
+ *                           V_hist was none and a history exists, V_hist first becomes the old V_cur; refits_pending += 1; THE TEMPORAL
+ *                           HISTORY IS KEPT -- the one thing tracking changes about a refit; everything else is invalidated as stated at
+ *                           srt_refit_vertices.  A refused refit changes nothing.
+ *   a *_moving call that advances the history  uses V_prev = V_hist, or V_cur when V_hist is none; afterwards V_hist = none ("equal to
+ *                           V_cur": no copy) and refits_pending = 0.
+ *   srt_temporal_accum, srt_denoise_features_temporal, srt_present_temporal with refits_pending > 0  discard the history, which shows
+ *                           geometry that has moved, and are a first frame (history_frames == 1) -- what they are after a refit without
+ *                           tracking; afterwards V_hist = none and refits_pending = 0.
+ *   srt_temporal_reset, srt_init_device_params, srt_set_partition  drop the history as always; V_hist = none, refits_pending = 0.
+ * Entry points:
+ *   srt_surface_motion      the pass on the context's camera, the uploaded scene and V_prev as defined above, for any rectangle and under
+ *                           any partition (a query, not a render: tiles of other ranks are traced like the rest).  out_point[h][w][4],
+ *                           out_tri[h][w] (int32), out_bary[h][w][3], *result; any may be NULL, not all three together with result.  Needs
+ *                           tracking on, known vertices and a camera.  Synchronises.  It only reads: neither history nor refits_pending
+ *                           nor any image, sum or RNG state moves.
+ *   srt_surface_motion_kat  the same kernel on the uploaded scene, the camera cam and the caller's vertex arrays: prev_verts_host (NULL:
+ *                           nothing moved) and cur_verts_host, n_tris x 9 floats each.  cur_verts_host must be the vertices the uploaded
+ *                           scene images were made from: THE CALLER'S PROMISE, which nothing checks.  Works with tracking off and touches
+ *                           no context state.  SRT_ERR_INVALID: no scene uploaded, a null ctx / cam / cur_verts_host, n_tris not the
+ *                           scene's, a coordinate that is not finite, an empty rectangle, no output, ox + w or oy + h above 2^24,
+ *                           w x h >= 2^31.
+ *   srt_motion_last_ms      kernel-only time in ms, from HIP events, of the context's last motion kernel; SRT_ERR_INVALID before one ran.
+ *   srt_temporal_moving_kat srt_temporal_kat plus prev_point[h][w][4] (not NULL): the moving stage.  It is srt_temporal_accum's stage in
+ *                           every operation except that step 3 of a hit pixel (cov_p >= 0.5f) reads M = prev_point[p]:
+ *                             M.w == 1:  v = M.xyz - center';  zexp = sqrtf(v.v).
+ *                             Otherwise step 4 counts as failed: no history for p, motion vector (NaN, NaN), fresh and offscreen.
+ *                           Sky pixels take v = d as before.  Fed the point the static stage reconstructs it equals srt_temporal_kat bit
+ *                           for bit.  The normal and albedo tests still compare the current guides with the history's: a surface that
+ *                           turns by more than sigma_normal between two frames is rejected and starts fresh -- safe, and a stated
+ *                           limitation (no expected-normal correction).
+ *   srt_temporal_accum_moving, srt_denoise_features_temporal_moving, srt_present_temporal_moving  their siblings with the motion pass on
+ *                           the accumulation's rectangle in front of the moving stage; *motion_result (may be NULL) receives the pass's
+ *                           counters.  They advance the history and the vertex state as stated above.  Refusals are their siblings' plus
+ *                           tracking off or vertices unknown (SRT_ERR_INVALID); a refused call leaves history and vertex state alone.
+ * Working blocks (two vertex blocks of 36 bytes per triangle, 64 bytes of counters, 32 bytes per pixel of the rectangle) belong to the
+ * context and are reused.  Out of scope: an expected-normal correction, lens- and jitter-aware reprojection, motion of materials, topology
+ * changes, a gathered (multi-rank) temporal stage. */
+typedef struct srt_motion_result { uint64_t hit, miss, moved, degenerate; } srt_motion_result;
+SRT_API int srt_temporal_track_motion(srt_ctx *ctx, int on);
+SRT_API int srt_temporal_tracking(const srt_ctx *ctx, int *on, uint32_t *refits_pending);
+SRT_API int srt_surface_motion(srt_ctx *ctx, uint32_t w, uint32_t h, uint32_t ox, uint32_t oy, float *out_point, int32_t *out_tri,
+                               float *out_bary, srt_motion_result *result);
+SRT_API int srt_surface_motion_kat(srt_ctx *ctx, const srt_camera_data *cam, const float *prev_verts_host, const float *cur_verts_host,
+                                   size_t n_tris, uint32_t w, uint32_t h, uint32_t ox, uint32_t oy, float *out_point, int32_t *out_tri,
+                                   float *out_bary, srt_motion_result *result);
+SRT_API int srt_motion_last_ms(srt_ctx *ctx, float *ms);
+SRT_API int srt_temporal_accum_moving(srt_ctx *ctx, const srt_temporal *cfg, float *out_xyz, float *out_lin, float *out_q, float *out_len,
+                                      float *out_motion, srt_temporal_result *result, uint32_t image_width, uint32_t image_height,
+                                      srt_motion_result *motion_result);
+SRT_API int srt_temporal_moving_kat(srt_ctx *ctx, const srt_temporal *cfg, const srt_camera_data *cur_cam, const srt_camera_data *prev_cam,
+                                    const float *xyz_mean, const float *guides, const float *hist_colour, const float *hist_guides,
+                                    uint32_t w, uint32_t h, uint32_t ox, uint32_t oy, float *out_colour, float *out_guides,
+                                    float *out_motion, srt_temporal_result *result, const float *prev_point);
+SRT_API int srt_denoise_features_temporal_moving(srt_ctx *ctx, const srt_temporal *temporal_cfg, const srt_despeckle *despeckle_cfg,
+                                                 const srt_denoise *denoise_cfg, float *out_xyz, float *out_lin, float *out_q,
+                                                 srt_temporal_result *temporal_result, uint32_t image_width, uint32_t image_height,
+                                                 srt_motion_result *motion_result);
+SRT_API int srt_present_temporal_moving(srt_ctx *ctx, const srt_present_cfg *present_cfg, const srt_temporal *temporal_cfg,
+                                        const srt_despeckle *despeckle_cfg, uint8_t *out_rgba8, size_t pitch_bytes, uint32_t image_width,
+                                        uint32_t image_height, srt_present_result *result, srt_temporal_result *temporal_result,
+                                        srt_motion_result *motion_result);
 
 /* Sample-parallel pixels (no reference counterpart; a deliberate departure from its one RNG stream per pixel, so opt-in).  A STREAMED
  * accumulation gives every pixel K independent RNG streams, each with its own state and its own XYZ sum, so that any lane of any wave
