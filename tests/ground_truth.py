@@ -8,6 +8,9 @@ of srt_color_tables, the camera struct), widened to float64; its outputs are wha
   t_bound        a-priori float32 error bound of t = (D - n.o) / (n.d)
   path_moments   mean and variance of one path's XYZ contribution for a given end spectrum (7 stratified wavelengths, or the hero alone)
   form_factor    Lambert's closed form for the cosine-weighted form factor of a polygon seen from a point
+  glass_paths    the probability that a path through flat glass faces ends on the emitter, by enumeration (refraction, total reflection)
+  fuzz_share, fuzz_light_share, lens_coverage
+                 where a fuzzed metal and a thin lens send the light (the *_sampled twins state the same quantities as plain counts)
   lane_index, footprint_average, project_points, polygon_area, coverage_map     pixel helpers
   soup, bumpy_sheet, axis_aligned_set, ... , to_structs                          scene builders on raw arrays
   assert_hits_hold, assert_edge_aimed_hold, builtin_report, assert_radiometry_holds
@@ -41,6 +44,11 @@ BK7_C = (0.00600069867, 0.0200179144, 103.560653)
 def f64(a):
     """float32 values widened to float64 (the inputs are what the renderer gets, not what a float64 builder meant)"""
     return np.asarray(a, np.float32).astype(np.float64)
+
+
+def unit(d):
+    """rows of d (m, 3) scaled to length 1"""
+    return d / np.linalg.norm(d, axis=1)[:, None]
 
 
 def normals(V):
@@ -275,6 +283,338 @@ def slab_transmission(n, cos_in, bounce_limit):
     return (1.0 - R1) * (1.0 - R2) * sum(R2 ** (2 * k) for k in range(K + 1))
 
 
+GLASS, EMITTER = 0, 1               # kinds of the polygons of glass_paths
+EDGE_ROUNDING = 1e-9                # a point this close to a polygon's edge (scene units) counts as inside it
+
+
+def polygon_planes(polys):
+    """per planar convex polygon (k, 3): the unit normal N of its winding ((v1 - v0) x (v2 - v0)), c = N . v0, and the inward edge
+    normals G (3, k) with their offsets h (k,): a point p of the plane lies inside when p @ G - h >= 0"""
+    out = []
+    for v in polys:
+        v = np.asarray(v, np.float64)
+        N = np.cross(v[1] - v[0], v[2] - v[0]); N = N / np.linalg.norm(N)
+        G = np.stack([np.cross(N, np.roll(v, -1, 0)[i] - v[i]) for i in range(len(v))], 1)
+        G = G / np.linalg.norm(G, axis=0)[None, :]
+        out.append((N, N @ v[0], G, (G * v.T).sum(0)))
+    return out
+
+
+def nearest_polygon(planes, o, d, last):
+    """the nearest polygon rays (o, d) (m, 3) meet at t > 0, brute force over ALL of them but the one each ray starts on (last (m,),
+    -1: none; a straight ray cannot meet the planar polygon it leaves again): every ray takes its plane crossings in the order of t
+    until one lies inside its polygon.  Returns t (inf on a miss) and the polygon (-1)."""
+    m = o.shape[0]
+    N, c = np.stack([p[0] for p in planes], 1), np.array([p[1] for p in planes])
+    dn = d @ N
+    with np.errstate(all="ignore"):
+        t = (c[None, :] - o @ N) / dn
+    t[~((dn != 0) & (t > 0))] = np.inf
+    t[np.nonzero(last >= 0)[0], last[last >= 0]] = np.inf
+    best_t, best_i = np.full(m, np.inf), np.full(m, -1, np.int64)
+    todo = np.arange(m)
+    while len(todo):
+        i = t[todo].argmin(1)
+        ti = t[todo, i]
+        todo, i, ti = todo[np.isfinite(ti)], i[np.isfinite(ti)], ti[np.isfinite(ti)]
+        p = o[todo] + ti[:, None] * d[todo]
+        inside = np.zeros(len(todo), bool)
+        for k in np.unique(i):
+            inside[i == k] = ((p[i == k] @ planes[k][2] - planes[k][3]) >= -EDGE_ROUNDING).all(1)
+        best_t[todo[inside]], best_i[todo[inside]] = ti[inside], i[inside]
+        t[todo[~inside], i[~inside]] = np.inf
+        todo = todo[~inside]
+    return best_t, best_i
+
+
+def snell(d, nrm, cos, ratio):
+    """the refracted unit direction of Snell's law: the tangential part of d scaled by the ratio of the indices, the rest along -nrm
+    (nrm: the unit normal against the ray, cos = -d . nrm; the caller has excluded total reflection)"""
+    tang = ratio[:, None] * (d + cos[:, None] * nrm)
+    return tang - np.sqrt(1.0 - (tang * tang).sum(1))[:, None] * nrm
+
+
+def outside_convex(glass, polygon):
+    """True when the convex planar polygon (k, 3) shares no point with the closed convex body bounded by the polygons `glass` (outward
+    windings): clipping it against every face's inner half space (Sutherland-Hodgman) leaves nothing"""
+    pts = [np.asarray(p, np.float64) for p in polygon]
+    for N, c, _, _ in polygon_planes(glass):
+        nxt = []
+        for a, b in zip(pts, pts[1:] + pts[:1]):
+            sa, sb = N @ a - c, N @ b - c
+            if sa <= 0:
+                nxt.append(a)
+            if (sa <= 0) != (sb <= 0):
+                nxt.append(a + (b - a) * sa / (sa - sb))
+        pts = nxt
+        if not pts:
+            return True
+    return False
+
+
+CHUNK = 1 << 14
+
+
+def glass_paths(polys, kinds, o, d, n, bounce_limit, record=None):
+    """The probability that a camera path ends on the emitter, by enumeration, for scenes of flat faces: planar convex polygons `polys`,
+    kinds[i] GLASS (one body of glass, windings outward) or EMITTER, black background.  o, d (m, 3): origins and UNIT directions, n (m,):
+    the refractive index of each ray's hero wavelength (rays x wavelengths, flattened by the caller).  Float64, numpy only.
+    Every step takes the nearest hit over all polygons.  At a glass face, as the reference documents its dielectric (the model
+    slab_transmission restates): the cosine on the incoming side, the ratio 1 / n entering and n leaving; ratio sin > 1 reflects with
+    probability 1, otherwise the ray reflects with probability R = schlick(cos, ratio) and refracts by Snell with 1 - R.  The path that
+    stays inside the glass is followed on (its weight is the product of its R); every refracted branch that leaves is scored at once: it
+    runs straight to the emitter, whose hit must be hit number <= bounce_limit, or to nothing.  ASSERTED, not assumed: a camera ray meets
+    glass first or nothing; the branch reflected off the outside meets nothing (such a path would carry seven wavelengths: not this
+    function's case); a ray inside the glass meets glass, from inside (the body is closed and holds no emitter); a ray that has left the
+    glass does not enter it again.  The 1e-4 offset along the normal that the renderer gives every scattered origin is IGNORED: it moves
+    a path sideways by at most 1e-4 tan(angle) per hit, far below a pixel's footprint on any face here.
+    record: a list that receives (hit number of the exit, rows of the input, exit point, exit direction, weight) per scored branch."""
+    if len(o) > CHUNK and record is None:               # (arrays that stay in the cache: the work is bound by memory)
+        return np.concatenate([glass_paths(polys, kinds, o[a:a + CHUNK], d[a:a + CHUNK], n[a:a + CHUNK], bounce_limit)
+                               for a in range(0, len(o), CHUNK)])
+    planes = polygon_planes(polys)
+    kinds = np.asarray(kinds)
+    normal = np.stack([p[0] for p in planes])
+    o, d, n = np.array(o, np.float64), np.array(d, np.float64), np.array(n, np.float64)
+    P = np.zeros(o.shape[0])
+    t, i = nearest_polygon(planes, o, d, np.full(o.shape[0], -1))
+    rows = np.nonzero(i >= 0)[0]
+    if bounce_limit < 3 or not len(rows):
+        return P
+    o, d, n, t, i = o[rows], d[rows], n[rows], t[rows], i[rows]
+    assert (kinds[i] == GLASS).all(), "glass_paths: a camera ray meets the emitter directly"
+    N = normal[i]
+    cos = np.minimum(-(d * N).sum(1), 1.0)
+    assert (cos > 0).all(), "glass_paths: a camera ray meets the glass from inside"
+    ratio = 1.0 / n
+    assert (ratio * np.sqrt(1.0 - cos * cos) <= 1.0).all()
+    w = 1.0 - schlick(cos, ratio)
+    o = o + t[:, None] * d
+    assert (nearest_polygon(planes, o, d + 2.0 * cos[:, None] * N, i)[1] < 0).all(), "glass_paths: a reflection off the outside meets something"
+    d, last = snell(d, N, cos, ratio), i
+    for hit in range(2, bounce_limit):                   # the exit is hit number `hit`, the emitter's hit + 1 <= bounce_limit
+        t, i = nearest_polygon(planes, o, d, last)
+        assert (i >= 0).all(), "glass_paths: a ray inside the glass meets nothing (the body is open)"
+        assert (kinds[i] == GLASS).all(), "glass_paths: the emitter is met from inside the glass"
+        N = normal[i]
+        cos = np.minimum((d * N).sum(1), 1.0)
+        assert (cos > 0).all(), "glass_paths: a ray inside the glass meets a face from outside"
+        o = o + t[:, None] * d
+        goes = n * np.sqrt(1.0 - cos * cos) <= 1.0       # the reference reflects when ratio sin > 1
+        R = np.where(goes, schlick(cos, n), 1.0)
+        k = np.nonzero(goes)[0]
+        if len(k):
+            out = snell(d[k], -N[k], cos[k], n[k])
+            j = nearest_polygon(planes, o[k], out, i[k])[1]
+            assert (kinds[j[j >= 0]] == EMITTER).all(), "glass_paths: a ray that has left the glass enters it again"
+            P[rows[k]] += w[k] * (1.0 - R[k]) * (j >= 0)
+            if record is not None:
+                record.append((hit, rows[k], o[k], out, w[k] * (1.0 - R[k])))
+        d, last, w = d - 2.0 * cos[:, None] * N, i, w * R
+    return P
+
+
+JUMP = 0.02       # a change of P between neighbouring hero nodes above this counts as a jump (smooth changes are far below it)
+
+
+def hero_moments(cmf, factors, prob, rays, nodes, refine):
+    """E and the raw second moment (3, rays) of one path's XYZ contribution, and P (rays,) that it contributes, for paths that carry the
+    hero wavelength alone (path_moments(hero_only=True)) and contribute with probability prob(ray numbers, hero wavelengths), which is
+    piecewise smooth in the wavelength and JUMPS where a path changes its faces (total reflection, an emitter's edge).  Midpoint
+    quadrature over hero_nodes(nodes); every cell next to a pair of nodes between which prob changes by more than JUMP is evaluated
+    again on `refine` midpoints of its own, so that a jump is located to 470 / (nodes refine) nm."""
+    def f(h):
+        p = np.ones_like(h)
+        for tab in factors:
+            p = p * interp(np.asarray(tab, np.float64), h)
+        return np.stack([interp(cmf[c], h) * p * STEP for c in range(3)])
+    h0 = hero_nodes(nodes)
+    P0 = prob(np.repeat(np.arange(rays), nodes), np.tile(h0, rays)).reshape(rays, nodes)
+    jump = np.abs(np.diff(P0, axis=1)) > JUMP
+    fine = np.zeros((rays, nodes), bool)
+    fine[:, :-1] |= jump; fine[:, 1:] |= jump
+    f0 = f(h0)
+    coarse = np.where(fine, 0.0, P0)
+    E, M2, P = f0 @ coarse.T / nodes, (f0 * f0) @ coarse.T / nodes, coarse.mean(1)
+    r, k = np.nonzero(fine)
+    if len(r) and refine > 1:
+        h1 = LAMBDA_MIN + (k[:, None] + (np.arange(refine)[None, :] + 0.5) / refine) * (LAMBDA_MAX - LAMBDA_MIN) / nodes
+        P1 = prob(np.repeat(r, refine), h1.ravel()).reshape(len(r), refine)
+        f1 = f(h1.ravel()).reshape(3, len(r), refine)
+        for c in range(3):
+            E[c] += np.bincount(r, (f1[c] * P1).sum(1), rays) / (nodes * refine)
+            M2[c] += np.bincount(r, (f1[c] ** 2 * P1).sum(1), rays) / (nodes * refine)
+        P += np.bincount(r, P1.sum(1), rays) / (nodes * refine)
+    else:
+        E, M2, P = f0 @ P0.T / nodes, (f0 * f0) @ P0.T / nodes, P0.mean(1)
+    return E, M2, P
+
+
+def hero_nodes(nodes):
+    """the midpoint nodes of path_moments over the hero wavelength"""
+    return LAMBDA_MIN + (np.arange(nodes) + 0.5) * (LAMBDA_MAX - LAMBDA_MIN) / nodes
+
+
+def fuzz_share(cos, fuzz):
+    """the share of a fuzzed metal's reflections that scatter: reflected + fuzz u, u uniform on the unit sphere, is absorbed when it
+    points into the surface.  u . n is uniform on [-1, 1] (Archimedes), reflected . n = cos: 1 - max(0, (1 - cos / fuzz) / 2)"""
+    return 1.0 - np.maximum(0.0, (1.0 - np.asarray(cos, np.float64) / fuzz) / 2.0)
+
+
+def sphere_nodes(nh, na):
+    """nh x na unit vectors, midpoints of a grid uniform in the height along y and in the azimuth: equal areas of the unit sphere"""
+    c = -1.0 + (np.arange(nh) + 0.5) * 2.0 / nh
+    a = (np.arange(na) + 0.5) * 2.0 * np.pi / na
+    s = np.sqrt(1.0 - c * c)
+    return np.stack([np.outer(s, np.cos(a)), np.outer(c, np.ones(na)), np.outer(s, np.sin(a))], -1).reshape(-1, 3)
+
+
+def light_in_reach(x, r, fuzz, light):
+    """False for the points x whose cone of directions r + fuzz u (within asin(fuzz) of r) cannot reach the cap that holds the triangle"""
+    v = light[None, :, :] - x[:, None, :]
+    vu = v / np.linalg.norm(v, axis=2)[:, :, None]
+    cu = unit(vu.mean(1))
+    cap = np.arccos(np.clip((vu * cu[:, None, :]).sum(2), -1, 1)).max(1)      # the spherical triangle lies in this cap about cu
+    return np.arccos(np.clip((r * cu).sum(1), -1, 1)) <= np.arcsin(fuzz) + cap + 1e-9
+
+
+def fuzz_light_share_sampled(x, r, fuzz, light, nh, na):
+    """per floor point x (m, 3) (normal +y) with unit reflected direction r: the share of the unit sphere of u for which r + fuzz u points
+    above the floor and meets the triangle `light` (3, 3), wholly above it, by counting sphere_nodes(nh, na): the plain statement of the
+    quantity, which fuzz_light_share is checked against (its error falls only like 1 / sqrt(nh na): too slow for the cases).  A point
+    whose cone of directions (within asin(fuzz) of r) cannot reach the cap that holds the light has share exactly 0 and is skipped."""
+    assert fuzz < 1.0 and (light[:, 1] > 0).all()
+    v = light[None, :, :] - x[:, None, :]                                     # (m, 3, 3) the corners as seen from x
+    share = np.zeros(x.shape[0])
+    k = np.nonzero(light_in_reach(x, r, fuzz, light))[0]
+    if not len(k):
+        return share
+    # a direction D from x meets the triangle when it lies in the cone of its corners: D . (v_i x v_i+1) all have the sign of det(v)
+    edge = np.cross(v[k], np.roll(v[k], -1, axis=1))                          # (m', 3, 3)
+    det = (edge[:, 0] * v[k][:, 2]).sum(1)
+    edge = edge * np.sign(det)[:, None, None]
+    u = fuzz * sphere_nodes(nh, na)
+    for a in range(0, len(k), 256):
+        D = r[k[a:a + 256], None, :] + u[None, :, :]                          # (b, K, 3)
+        s = np.einsum("bkc,bec->bke", D, edge[a:a + 256])
+        share[k[a:a + 256]] = ((s >= 0).all(2) & (D[:, :, 1] > 0)).mean(1)
+    return share
+
+
+def fuzz_light_share(x, r, fuzz, light, na):
+    """the same share, exact along one variable.  With u = cos(psi) r + sin(psi) e, e the unit vector across r at the azimuth phi and psi
+    in [0, pi], the sphere's area element is sin(psi) dpsi dphi, and r + fuzz u stays in the half plane of r and e, at the angle
+    theta = atan2(fuzz sin psi, 1 + fuzz cos psi) from r.  That half plane cuts the triangle in a segment, which spans an interval of
+    theta; every theta in it below asin(fuzz) is reached by two psi, fuzz sin(psi - theta) = sin(theta), and the integral of sin(psi)
+    over both pre-images is elementary.  Midpoint quadrature over na azimuths of the arc the triangle spans about r (all of them when
+    r points into the triangle); the integrand is continuous in phi."""
+    assert fuzz < 1.0 and (light[:, 1] > 0).all() and (np.abs(r[:, 1]) < 0.999).all()
+    reach = light_in_reach(x, r, fuzz, light)
+    if not reach.all():                                                         # (the others' share is exactly 0)
+        out = np.zeros(x.shape[0])
+        if reach.any():
+            out[reach] = fuzz_light_share(x[reach], r[reach], fuzz, light, na)
+        return out
+    v = light[None, :, :] - x[:, None, :]                                       # (m, 3, 3) the corners as seen from x
+    assert (v[:, :, 1] > 0).all()                                               # (the light is above the floor: so is every direction to it)
+    e1 = unit(np.cross(r, np.array([0.0, 1.0, 0.0]))); e2 = np.cross(r, e1)
+    az = np.arctan2(np.einsum("mkc,mc->mk", v, e2), np.einsum("mkc,mc->mk", v, e1))
+    rel = (az - az[:, :1] + np.pi) % (2.0 * np.pi) - np.pi                      # the corners' azimuths about r, from the first one's
+    side = np.einsum("mkc,mc->mk", np.cross(v, np.roll(v, -1, axis=1)), r)
+    within = (side >= 0).all(1) | (side <= 0).all(1)                            # r points into the triangle
+    start = np.where(within, 0.0, az[:, 0] + rel.min(1))
+    width = np.where(within, 2.0 * np.pi, rel.max(1) - rel.min(1))
+    tmax = np.arcsin(fuzz)
+    near = lambda t: t + np.arcsin(np.clip(np.sin(t) / fuzz, -1, 1))
+    far = lambda t: t + np.pi - np.arcsin(np.clip(np.sin(t) / fuzz, -1, 1))
+    share = np.zeros(x.shape[0])
+    for q in range(na):
+        phi = start + (q + 0.5) / na * width
+        e = np.cos(phi)[:, None] * e1 + np.sin(phi)[:, None] * e2
+        w = np.einsum("mkc,mc->mk", v, np.cross(r, e))                          # the corners' distances from the plane of r and e
+        cut = np.zeros(v.shape[:1] + (2, 3)); found = np.zeros(v.shape[0], np.int64)
+        for i, j in ((0, 1), (1, 2), (2, 0)):
+            k = np.nonzero(((w[:, i] <= 0) != (w[:, j] <= 0)) & (found < 2))[0]
+            s = w[k, i] / (w[k, i] - w[k, j])
+            cut[k, found[k]] = v[k, i] + s[:, None] * (v[k, j] - v[k, i]); found[k] += 1
+        k = np.nonzero(found == 2)[0]
+        a, b = np.einsum("kpc,kc->kp", cut[k], r[k]), np.einsum("kpc,kc->kp", cut[k], e[k])
+        k, a, b = k[(b > 0).any(1)], a[(b > 0).any(1)], b[(b > 0).any(1)]
+        # the part of the segment in the half plane b >= 0: an end behind it moves to the crossing of the axis, theta = 0
+        s = np.where(b < 0, b / (b - b[:, ::-1]), 0.0)
+        a, b = a + s * (a[:, ::-1] - a), np.where(b < 0, 0.0, b)
+        th = np.clip(np.arctan2(b, a), 0.0, tmax)
+        lo, hi = th.min(1), th.max(1)
+        share[k] += ((np.cos(near(lo)) - np.cos(near(hi))) + (np.cos(far(hi)) - np.cos(far(lo)))) * width[k] / na
+    return share / (4.0 * np.pi)
+
+
+def disk_polygon_area(Q):
+    """area of the intersection of the unit disk about the origin with polygons Q (m, k, 2): per edge A -> B the signed area between the
+    origin and the edge clipped to the disk, a triangle where the edge runs inside and a sector where it runs outside"""
+    total = np.zeros(Q.shape[0])
+    cross = lambda a, b: a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]
+    sector = lambda a, b: 0.5 * np.arctan2(cross(a, b), (a * b).sum(1))
+    for i in range(Q.shape[1]):
+        A, B = Q[:, i], Q[:, (i + 1) % Q.shape[1]]
+        d = B - A
+        a, b, c = (d * d).sum(1), 2.0 * (A * d).sum(1), (A * A).sum(1) - 1.0
+        disc = b * b - 4.0 * a * c
+        root = np.sqrt(np.maximum(disc, 0.0))
+        t1 = np.where(disc > 0, np.clip((-b - root) / (2.0 * a), 0.0, 1.0), 0.0)
+        t2 = np.where(disc > 0, np.clip((-b + root) / (2.0 * a), 0.0, 1.0), 0.0)
+        P1, P2 = A + t1[:, None] * d, A + t2[:, None] * d
+        total += sector(A, P1) + 0.5 * cross(P1, P2) + sector(P2, B)
+    return np.where(np.abs(total) < 1e-12, 0.0, np.abs(total))              # (sectors alone: a rounding residue of the winding number 0)
+
+
+def lens_coverage(cam, tri, W, H, k):
+    """the same P, exact over the lens: from a point p of the pixel grid the triangle `tri`, between lens and grid, projects onto the lens
+    plane as a triangle, and the share of the lens disk from which the ray to p meets it is the area the two have in common / pi.
+    Averaged over k x k midpoint sub-samples of every pixel's square."""
+    g = lambda name: np.array(getattr(cam, name)[:], np.float64)
+    C, U, V = g("camera_center"), g("defocus_disk_u"), g("defocus_disk_v")
+    _, p00, du, dv = camera_arrays(cam)
+    j, i = np.mgrid[0:H, 0:W]
+    acc = np.zeros(W * H)
+    for a in range(k):
+        for b in range(k):
+            p = p00[None, :] + (i.ravel()[:, None] + (a + 0.5) / k - 0.5) * du[None, :] + (j.ravel()[:, None] + (b + 0.5) / k - 0.5) * dv[None, :]
+            Q = np.zeros((W * H, 3, 2))
+            for c in range(3):                             # C + a U + b V = p + s (corner - p)
+                M = np.stack([np.broadcast_to(U, p.shape), np.broadcast_to(V, p.shape), p - tri[c][None, :]], axis=2)
+                sol = np.linalg.solve(M, (p - C[None, :])[:, :, None])[:, :, 0]
+                assert (sol[:, 2] > 1).all(), "lens: the triangle must lie between the lens and the pixel grid"
+                Q[:, c] = sol[:, :2]
+            acc += disk_polygon_area(Q) / np.pi
+    return acc / (k * k)
+
+
+def lens_points(cam, nr, na):
+    """nr x na points of the thin lens, midpoints of a polar grid of equal areas: camera_center + p_x defocus_disk_u + p_y defocus_disk_v
+    with p uniform on the unit disk (the reference's documented disk sample)"""
+    g = lambda name: np.array(getattr(cam, name)[:], np.float64)
+    rad = np.sqrt((np.arange(nr) + 0.5) / nr)
+    a = (np.arange(na) + 0.5) * 2.0 * np.pi / na
+    px, py = np.outer(rad, np.cos(a)).ravel(), np.outer(rad, np.sin(a)).ravel()
+    return g("camera_center")[None, :] + px[:, None] * g("defocus_disk_u")[None, :] + py[:, None] * g("defocus_disk_v")[None, :]
+
+
+def lens_coverage_sampled(cam, tri, W, H, nr, na, k):
+    """P (H * W,) that a camera ray of each pixel meets the triangle `tri` (3, 3), nothing else in its way, through the thin lens: the ray
+    runs from a lens point L to the pixel sample ON THE PIXEL GRID, which lies in the focus plane, so that from L the triangle covers
+    its central projection from L onto the grid.  The mean of coverage_map of that projection over lens_points(nr, na): the plain
+    statement of the quantity, which lens_coverage is checked against.  Also returns the image total, the mean of polygon_area: the
+    projection is affine in L, the area quadratic, and the polar midpoint grid integrates a quadratic exactly (nr >= 1, na >= 3)."""
+    cov, area = np.zeros(W * H), 0.0
+    L = lens_points(cam, nr, na)
+    for eye in L:
+        Q, depth = project_points(cam, tri, eye)
+        assert (depth > 0).all() and (Q.min(0) > -0.5).all() and (Q[:, 0].max() < W - 0.5) and (Q[:, 1].max() < H - 0.5), "lens: out of view"
+        cov += coverage_map(Q, W, H, k); area += polygon_area(Q)
+    return cov / len(L), area / len(L)
+
+
 def form_factor(x, n, polygon):
     """Lambert's closed form for the cosine-weighted form factor of a planar polygon (k, 3) seen from points x (m, 3) with unit normal n:
     F = |sum_i gamma_i (r_i x r_i+1) . n / |r_i x r_i+1|| / (2 pi), gamma_i the angle the edge subtends.  F is the probability that a
@@ -325,10 +665,12 @@ def footprint_average(fn, cam, W, H, k):
     return acc / (k * k)
 
 
-def project_points(cam, P):
+def project_points(cam, P, eye=None):
     """perspective projection of points P (k, 3) into continuous pixel coordinates (i, j): pixel (x, y) is the square
-    [x - 0.5, x + 0.5] x [y - 0.5, y + 0.5].  Also returns the depth s (eye + s (P - eye) lies on the image plane; s > 0 in front)."""
-    eye, p00, du, dv = camera_arrays(cam)
+    [x - 0.5, x + 0.5] x [y - 0.5, y + 0.5].  Also returns the depth s (eye + s (P - eye) lies on the image plane; s > 0 in front).
+    eye: the centre of projection (default: the camera's centre; a lens point projects onto the same pixel grid)."""
+    centre, p00, du, dv = camera_arrays(cam)
+    eye = centre if eye is None else np.asarray(eye, np.float64)
     out = np.zeros((len(P), 2)); depth = np.zeros(len(P))
     for k, p in enumerate(np.asarray(P, np.float64)):
         i, j, s = np.linalg.solve(np.stack([du, dv, -(p - eye)], axis=1), eye - p00)
@@ -353,6 +695,30 @@ def coverage_map(Q, W, H, k):
             s = [e(Q[0], Q[1], px, py), e(Q[1], Q[2], px, py), e(Q[2], Q[0], px, py)]
             acc += (((s[0] >= 0) & (s[1] >= 0) & (s[2] >= 0)) | ((s[0] <= 0) & (s[1] <= 0) & (s[2] <= 0)))
     return acc / (k * k)
+
+
+def coverage_exact(Q, W, H):
+    """share of every pixel's square inside the convex polygon Q (k, 2) of pixel coordinates, exact: the polygon clipped to the square
+    (Sutherland-Hodgman), shape (H * W,).  Where a pixel's variance hangs on 1 - P, sub-samples are too coarse."""
+    out = np.zeros((H, W))
+    Q = np.asarray(Q, np.float64)
+    for y in range(max(0, int(np.floor(Q[:, 1].min() + 0.5))), min(H, int(np.ceil(Q[:, 1].max() + 0.5)))):
+        for x in range(max(0, int(np.floor(Q[:, 0].min() + 0.5))), min(W, int(np.ceil(Q[:, 0].max() + 0.5)))):
+            pts = [q for q in Q]
+            for axis, bound, sign in ((0, x - 0.5, 1.0), (0, x + 0.5, -1.0), (1, y - 0.5, 1.0), (1, y + 0.5, -1.0)):
+                nxt = []
+                for a, b in zip(pts, pts[1:] + pts[:1]):
+                    sa, sb = sign * (a[axis] - bound), sign * (b[axis] - bound)
+                    if sa >= 0:
+                        nxt.append(a)
+                    if (sa >= 0) != (sb >= 0):
+                        nxt.append(a + (b - a) * sa / (sa - sb))
+                pts = nxt
+                if not pts:
+                    break
+            if len(pts) >= 3:
+                out[y, x] = polygon_area(np.array(pts))
+    return out.ravel()
 
 
 def mirror_y(P):
@@ -697,11 +1063,100 @@ def slab(incidence_deg, spp):
             (2.0, eye, (0, 0, 0)), 48, 32, spp, SLAB_DEPTH)
 
 
+def prism_polygons(apex_deg, a=2.0, b=2.0, h=10.0):
+    """a closed prism as five convex polygons wound outwards, float32 corners: the front face in z = 0 (normal +z) from the refracting
+    edge x = -a to the base x = b, the back face falling from that edge at the apex angle, the base x = b, and the caps y = -+h"""
+    zb = -(a + b) * np.tan(np.radians(apex_deg))
+    e0, e1, f0, f1, k0, k1 = (-a, -h, 0), (-a, h, 0), (b, -h, 0), (b, h, 0), (b, -h, zb), (b, h, zb)
+    polys = [[e0, f0, f1, e1], [e0, e1, k1, k0], [f0, k0, k1, f1], [e0, k0, f0], [e1, f1, k1]]
+    return [f64(p) for p in polys]
+
+
+def polygon_scene(polys, kinds, glass, emitter):
+    """the triangles of planar polygons (a fan from the first corner), material 0 = glass, 1 = emitter; keeps the polygons for the truth"""
+    V, idx = [], []
+    for p, k in zip(polys, kinds):
+        for j in range(1, len(p) - 1):
+            V.append([p[0], p[j], p[j + 1]]); idx.append(int(k))
+    sc = scene(V, [glass, emitter], mat_index=idx)
+    sc["polys"], sc["kinds"] = polys, list(kinds)
+    assert (f64(sc["V"]) == np.array(V)).all()            # the truth's corners are the float32 corners the renderer gets
+    return sc
+
+
+def wedge(apex_deg, emitter_polygon, camera, W, H, spp):
+    """a closed BK7 prism (true Sellmeier C, spectrum 1), its front face normal to the view, and one emissive polygon beyond its back
+    face, black background; the eye stands off the principal plane y = 0, so that every ray is skew"""
+    glass = material(MAT_DIELECTRIC, np.ones(N_GRID, np.float32), B=BK7_B, C=BK7_C)
+    polys = prism_polygons(apex_deg) + [f64(emitter_polygon)]
+    return (polygon_scene(polys, [GLASS] * 5 + [EMITTER], glass, material(MAT_EMISSIVE, bump(0.5, 3.0, 540.0, 90.0))),
+            camera, W, H, spp, WEDGE_DEPTH)
+
+
+WEDGE_DEPTH = 8
+STRIPE = [(6.66, -30, -20), (6.78, -30, -20), (6.78, 30, -20), (6.66, 30, -20)]        # 0.12 wide, 20 behind the front face
+TIR_WALL = [(5, -50, -25), (60, -50, -25), (60, 50, -25), (5, 50, -25)]               # below the back face; the base's exits pass above it
+
+
+def wedge_dispersion():
+    """apex 30 degrees: the deviation runs from 19.03 (830 nm) to 20.23 degrees (360 nm), 0.44 wide on the stripe's plane: the stripe
+    is a quarter of that, so every pixel column sees its own band of wavelengths"""
+    return wedge(30.0, STRIPE, (0.25, (0, 0.4, 6), (-0.005, 0, 0)), 44, 10, 256)
+
+
+def wedge_tir():
+    """apex 41 degrees: BK7's critical angle is 40.58 (360 nm) to 41.47 degrees (830 nm), and the view sweeps the internal angle of
+    incidence across that range: from black through red to white"""
+    return wedge(41.0, TIR_WALL, (0.7875, (0, 0.4, 6), (-0.012, 0, 0)), 32, 14, 128)
+
+
+FUZZ_ABSORBED, FUZZ_DIRECTED = 0.8, 0.3
+FUZZ_DEPTH = 4       # at 2 a reflection INTO the floor would meet it again and end at the bounce limit, absorbed or not: the absorption would go untested
+
+
+def fuzz_absorbed():
+    """a fuzzed metal floor under the sky, seen at 11 degrees above grazing: 32 to 44 % of the reflections point into the floor"""
+    return (scene(FLOOR, [material(MAT_METALLIC, ramp(0.9, 0.3), fuzz=FUZZ_ABSORBED)], mat_index=[0, 0], background=bump()),
+            (12.0, (0, 1.2, 6), (0, 0, 0)), 48, 32, 64, FUZZ_DEPTH)
+
+
+def fuzz_directed():
+    """the mirror case with fuzz 0.3 and 256 samples: the light's mirror image is smeared over the floor"""
+    sc, camera, W, H, _, _ = mirror()
+    sc["mats"][0] = material(MAT_METALLIC, ramp(0.9, 0.3), fuzz=FUZZ_DIRECTED)
+    return sc, camera, W, H, 256, FUZZ_DEPTH
+
+
+LENS_NEAR = np.array([(-0.825, -0.45, 5.0), (0.375, -0.3375, 5.3), (-0.3, 0.45, 4.8)], np.float32)     # 3 in front of the lens: blurred
+LENS_FOCUS = np.array([(1.7, -1.4, 0.0), (2.5, -1.2, 0.0), (2.0, -0.4, 0.0)], np.float32)             # in the focus plane: sharp
+
+
+def lens():
+    """two emissive triangles through a thin lens (defocus angle 4 degrees, focus distance 8: radius 0.28), black background"""
+    mats = [material(MAT_EMISSIVE, bump(0.5, 4.0, 480.0, 50.0)), material(MAT_EMISSIVE, bump(0.5, 3.0, 600.0, 80.0))]
+    return scene([LENS_NEAR, LENS_FOCUS], mats), (24.0, (0, 0, 8), (0, 0, 0), 4.0, 8.0), 64, 40, 64, 2
+
+
 RADIOMETRY = {"sky_only": sky_only, "floor_under_sky": floor_under_sky, "emissive_wall": emissive_wall, "cosine_law": cosine_law,
-              "mirror": mirror, "slab_0": lambda: slab(0.0, 64), "slab_55": lambda: slab(55.0, 1024)}
+              "mirror": mirror, "slab_0": lambda: slab(0.0, 64), "slab_55": lambda: slab(55.0, 1024),
+              "wedge_dispersion": wedge_dispersion, "wedge_tir": wedge_tir, "fuzz_absorbed": fuzz_absorbed, "fuzz_directed": fuzz_directed,
+              "lens": lens}
+# the cases held per pixel as well (rms z, at least MIN_PIXELS pixels, dark pixels exactly 0), and their quadratures: the smallest
+# for which halving any one resolution moves no held pixel's E by 0.1 of its standard error (test_quadratures_are_converged)
+PER_PIXEL = ("wedge_dispersion", "wedge_tir", "fuzz_absorbed", "fuzz_directed", "lens")
+QUADRATURE = {"wedge_dispersion": dict(nodes=128, refine=16, sub_x=8, sub_y=1), "wedge_tir": dict(nodes=64, refine=32, sub_x=16, sub_y=1), "fuzz_absorbed": dict(sub=2),
+              "fuzz_directed": dict(na=64, sub=8), "lens": dict(sub=4)}
 Z_IMG_MAX = 5.0                      # statistical constants, not measurements
 RMS_Z_RANGE = (0.8, 1.2)
 MIN_EXPECTED = 10.0                  # per-pixel z only where spp P(contribute) >= 10
+MIN_PIXELS = 300                     # of them: the rms of correct code then scatters by 1 / sqrt(2 x 300) = 0.04
+
+
+def camera(srt, args, W, H):
+    """the camera of a radiometry case: (vfov, eye, look-at) and, for a thin lens, (defocus_angle, focus_dist) after them"""
+    vfov, eye, at = args[:3]
+    lens_args = dict(zip(("defocus_angle", "focus_dist"), args[3:]))
+    return srt.camera_init(W, H, vfov, eye, at, **lens_args)
 
 
 def floor_points(eye, d):
@@ -712,11 +1167,62 @@ def floor_points(eye, d):
     return x
 
 
-def expectation(name, cmf, cam, sc, W, H, depth):
+def bernoulli(E1, V1, P):
+    """E, Var (3, m) of a path that contributes, with moments E1, V1 (3,), with probability P (m,) and adds 0 otherwise"""
+    E = E1[:, None] * P[None, :]
+    return E, (V1 + E1 ** 2)[:, None] * P[None, :] - E ** 2
+
+
+def expectation(name, cmf, cam, sc, W, H, depth, res=None):
     """closed-form E and Var per path of every pixel ((3,) when all pixels are alike, else (3, H * W)), P = the probability that a path
-    of the pixel contributes (None: 1), E_sum = the exact image total where it is known better than the sum of the per-pixel values"""
+    of the pixel contributes (None: 1), E_sum = the exact image total where it is known better than the sum of the per-pixel values.
+    res: the resolutions of the case's quadrature (default QUADRATURE[name])"""
     spec = lambda k: f64(sc["mats"][k]["spectrum"])
     bg = f64(sc["background"])
+    q = res or QUADRATURE.get(name)
+    if name.startswith("wedge_"):
+        # every contributing path has crossed the glass and carries the hero wavelength alone; P per pixel and hero wavelength by
+        # enumeration, averaged over the pixel's footprint
+        polys, kinds = sc["polys"], sc["kinds"]
+        glass = [p for p, k in zip(polys, kinds) if k == GLASS]
+        assert all(outside_convex(glass, p) for p, k in zip(polys, kinds) if k == EMITTER), "the emitter must lie wholly outside the glass"
+        assert (spec(0) == 1).all() and not bg.any()
+        B, C = f64(sc["mats"][0]["B"]), f64(sc["mats"][0]["C"])
+        sub = [((a + 0.5) / q["sub_x"] - 0.5, (b + 0.5) / q["sub_y"] - 0.5) for a in range(q["sub_x"]) for b in range(q["sub_y"])]
+        d = np.concatenate([unit(pixel_rays(cam, W, H, fx, fy)[1]) for fx, fy in sub])              # (sub-samples x pixels, 3)
+        eye = camera_arrays(cam)[0]
+        prob = lambda r, h: glass_paths(polys, kinds, np.broadcast_to(eye, (len(r), 3)), d[r], sellmeier_index(B, C, h), depth)
+        E, M2, P = (m.reshape(m.shape[:-1] + (len(sub), W * H)).mean(-2)
+                    for m in hero_moments(cmf, [spec(1)], prob, len(d), q["nodes"], q["refine"]))
+        Var = M2 - E * E
+        return dict(E=E, Var=Var, P=P, E_sum=None)
+    if name == "fuzz_absorbed":
+        assert sc["mats"][0]["fuzz"] == FUZZ_ABSORBED
+        def share(eye, d):
+            floor_points(eye, d)                                      # (asserts: every ray lands on the floor)
+            return fuzz_share(-unit(d)[:, 1], FUZZ_ABSORBED)
+        P = footprint_average(share, cam, W, H, q["sub"])
+        E, Var = bernoulli(*path_moments(cmf, [spec(0), bg]), P)
+        return dict(E=E, Var=Var, P=P, E_sum=None)
+    if name == "fuzz_directed":
+        assert sc["mats"][0]["fuzz"] == FUZZ_DIRECTED and not bg.any()
+        P = footprint_average(lambda eye, d: fuzz_light_share(floor_points(eye, d), unit(d) * np.array([1.0, -1.0, 1.0]), FUZZ_DIRECTED,
+                                                               f64(MIRROR_LIGHT), q["na"]), cam, W, H, q["sub"])
+        E, Var = bernoulli(*path_moments(cmf, [spec(0), spec(1)]), P)
+        return dict(E=E, Var=Var, P=P, E_sum=None)
+    if name == "lens":
+        assert not bg.any() and cam.defocus_angle > 0
+        Pa = lens_coverage(cam, f64(LENS_NEAR), W, H, q["sub"])
+        area_a = lens_coverage_sampled(cam, f64(LENS_NEAR), W, H, 2, 8, 1)[1]             # (exact: see there; also asserts "in view")
+        Qb, depth_b = project_points(cam, f64(LENS_FOCUS))
+        assert np.abs(depth_b - 1.0).max() < 1e-6, "lens: the second triangle must lie in the focus plane, which holds the pixel grid"
+        Pb = coverage_exact(Qb, W, H)
+        assert not ((Pa > 0) & (Pb > 0)).any(), "lens: the two images must not overlap (no ray can then meet both triangles)"
+        (Ea, Va), (Eb, Vb) = bernoulli(*path_moments(cmf, [spec(0)]), Pa), bernoulli(*path_moments(cmf, [spec(1)]), Pb)
+        E = Ea + Eb
+        Var = (Va + Ea ** 2) + (Vb + Eb ** 2) - E ** 2
+        return dict(E=E, Var=Var, P=Pa + Pb, E_sum=path_moments(cmf, [spec(0)])[0] * area_a + path_moments(cmf, [spec(1)])[0] * polygon_area(Qb),
+                    near=Pa, focus=Pb)
     if name == "sky_only":
         E, V = path_moments(cmf, [bg])
         return dict(E=E, Var=V, P=None, E_sum=None)
@@ -761,13 +1267,24 @@ def expectation(name, cmf, cam, sc, W, H, depth):
 
 def assert_radiometry_holds(name, xyz_planes, W, H, spp, exp, what):
     """|z_img| <= 5 + the float32 summation allowance in all three channels, and for the cosine law 0.8 <= rms per-pixel z <= 1.2 over
-    the pixels with spp P >= 10.  Returns the z values for the test's printed line."""
+    the pixels with spp P >= 10.  For every case of PER_PIXEL -- the cases about WHERE the light goes, to which z_img is blind -- the same
+    range holds in all three channels over the pixels with spp P >= 10, of which there must be at least MIN_PIXELS, and a pixel whose P
+    is 0, like that of its eight neighbours, has all three XYZ sums exactly 0.  Returns the z values for the test's printed line."""
     z_img, allowance, z_px = z_scores(xyz_planes, W, H, spp, exp["E"], exp["Var"], MIN_EXPECTED if exp["P"] is not None else None,
                                       exp["P"], exp["E_sum"])
-    out = dict(z_img=[round(float(z), 2) for z in z_img], max_z_px=round(float(np.abs(z_px).max()), 2), pixels=int(z_px.shape[1]),
-               rms_z=[round(float(np.sqrt((z_px[c] ** 2).mean())), 3) for c in range(3)])
+    held = ~np.isnan(z_px)               # 0 / 0: a channel the truth gives this pixel nothing in, and that got nothing, has no z (x / 0 has)
+    out = dict(z_img=[round(float(z), 2) for z in z_img], max_z_px=round(float(np.abs(z_px[held]).max()), 2), pixels=int(z_px.shape[1]),
+               rms_z=[round(float(np.sqrt((z_px[c][held[c]] ** 2).mean())), 3) for c in range(3)])
     assert (np.abs(z_img) <= Z_IMG_MAX + allowance).all(), "%s %s: z_img %s" % (what, name, out)
     if name == "cosine_law":
         assert z_px.shape[1] >= 100, (what, name, z_px.shape)
         assert all(RMS_Z_RANGE[0] <= r <= RMS_Z_RANGE[1] for r in out["rms_z"]), "%s %s: rms z %s" % (what, name, out)
+    if name in PER_PIXEL:
+        assert held.sum(1).min() >= MIN_PIXELS, (what, name, held.sum(1))
+        assert all(RMS_Z_RANGE[0] <= r <= RMS_Z_RANGE[1] for r in out["rms_z"]), "%s %s: rms z %s" % (what, name, out)
+        lit = np.pad(np.asarray(exp["P"]).reshape(H, W) > 0, 1)
+        dark = ~np.any([lit[a:a + H, b:b + W] for a in range(3) for b in range(3)], axis=0)
+        out["dark"] = int(dark.sum())
+        sums = np.stack([np.asarray(xyz_planes[c])[lane_index(W, H)] for c in range(3)])
+        assert not sums[:, dark].any(), "%s %s: %d dark pixels are lit" % (what, name, (sums[:, dark] != 0).any(0).sum())
     return out
