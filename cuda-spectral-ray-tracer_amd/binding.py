@@ -126,6 +126,12 @@ class TemporalResult(C.Structure):
                 ("history_frames", C.c_uint32), ("history_dropped", C.c_uint32)]
 
 
+class TemporalVG(C.Structure):
+    """srt_temporal_vg: the moments length from which the variance measured across frames guides the filter, and whether the stage is the
+    moving one (srt_c_api.h)"""
+    _fields_ = [("min_len", C.c_uint32), ("moving", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 class MotionResult(C.Structure):
     """srt_motion_result: the pixels whose centre ray hit and missed, the hit pixels whose triangle moved, and of those the ones whose
     previous point could not be formed (srt_c_api.h)"""
@@ -149,7 +155,7 @@ assert C.sizeof(Denoise) == 32 and C.sizeof(DenoiseVG) == 32
 assert C.sizeof(Meter) == 48 and C.sizeof(MeterResult) == 40 and C.sizeof(Tone) == 32 and C.sizeof(ToneResult) == 24
 assert C.sizeof(PresentCfg) == 184 and C.sizeof(PresentResult) == 64
 assert C.sizeof(Despeckle) == 32 and C.sizeof(DespeckleResult) == 24
-assert C.sizeof(Temporal) == 32 and C.sizeof(TemporalResult) == 48 and C.sizeof(MotionResult) == 32
+assert C.sizeof(Temporal) == 32 and C.sizeof(TemporalResult) == 48 and C.sizeof(MotionResult) == 32 and C.sizeof(TemporalVG) == 16
 assert C.sizeof(Adaptive) == 16 and C.sizeof(TreeTuning) == 40 and C.sizeof(TileScheduleInfo) == 32
 assert C.sizeof(Material) == 428 and C.sizeof(CameraData) == 84 and C.sizeof(TriIn) == 44
 
@@ -257,6 +263,15 @@ PROTOTYPES = {
                                                   C.POINTER(TemporalResult), _u32, _u32, C.POINTER(MotionResult)]),
     "srt_present_temporal_moving": (_i, [_vp, C.POINTER(PresentCfg), C.POINTER(Temporal), C.POINTER(Despeckle), C.POINTER(C.c_uint8), _sz, _u32, _u32,
                                          C.POINTER(PresentResult), C.POINTER(TemporalResult), C.POINTER(MotionResult)]),
+    "srt_denoise_features_temporal_vg": (_i, [_vp, C.POINTER(Temporal), C.POINTER(Despeckle), C.POINTER(DenoiseVG), C.POINTER(TemporalVG), _fp, _fp, _fp, _fp,
+                                              C.POINTER(TemporalResult), C.POINTER(_u64), C.POINTER(MotionResult), _u32, _u32]),
+    "srt_present_temporal_vg": (_i, [_vp, C.POINTER(PresentCfg), C.POINTER(Temporal), C.POINTER(Despeckle), C.POINTER(TemporalVG), C.POINTER(C.c_uint8), _sz,
+                                     _u32, _u32, C.POINTER(PresentResult), C.POINTER(TemporalResult), C.POINTER(_u64), C.POINTER(MotionResult)]),
+    "srt_temporal_moments_kat": (_i, [_vp, C.POINTER(Temporal), C.POINTER(CameraData), C.POINTER(CameraData), _fp, _fp, _fp, _fp, _u32, _u32, _u32, _u32,
+                                      _fp, _fp, _fp, C.POINTER(TemporalResult), _fp, _fp, _fp]),
+    "srt_temporal_variance_kat": (_i, [_vp, _fp, _fp, _fp, _u32, _u32, _u32, _fp, C.POINTER(_u64)]),
+    "srt_read_temporal_moments": (_i, [_vp, _fp, _u32, _u32]),
+    "srt_temporal_variance_last_ms": (_i, [_vp, _fp]),
     "srt_accum_reset_features": (_i, [_vp]),
     "srt_read_features": (_i, [_vp, _fp, _u32, _u32]),
     "srt_accum_reset_adaptive_features": (_i, [_vp, C.POINTER(Adaptive)]),

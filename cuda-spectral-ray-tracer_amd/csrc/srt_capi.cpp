@@ -167,11 +167,12 @@ struct srt_ctx {
     DeviceBuffer d_denoise;                             // the denoiser's working images (DenoiseLayout), grown when the rectangle grows
     DeviceBuffer d_denoise_in;                          // srt_denoise_kat: the caller's sums and feature rows
     DeviceBuffer d_denoise_dev;                         // srt_denoise_developed: the payload images (DenoiseDevLayout), grown when rectangle or channels grow
-    hipEvent_t denoise_ev[13] = {};                     // around the kernels of the last denoise: prepass | (estimator) | (despeckle) | (temporal) | levels | epilogue (created on first use)
+    hipEvent_t denoise_ev[16] = {};                     // around the kernels of the last denoise: prepass | (estimator) | (despeckle) | (temporal) | (estimator | choice: srt_*_temporal_vg) | levels | epilogue (created on first use)
     uint32_t denoise_timed_levels = 0;                  // levels the events of the last denoise bracket
     uint32_t denoise_level_ev = 1;                      // the event level 0 starts at: 1, or 2 after a variance-guided denoise
     bool denoise_timed = false;
-    bool denoise_estimated = false;                     // the last denoise ran a variance estimator (the event pair [1, 2] brackets it)
+    bool denoise_estimated = false;                     // the last denoise ran a variance estimator (the event pair [denoise_est_ev, + 1] brackets it)
+    uint32_t denoise_est_ev = 1;                        // the event the estimator starts at: 1, or behind the stage in srt_*_temporal_vg
     DeviceBuffer d_develop;                             // the developed film's working blocks (DevelopLayout), grown when the rectangle or the channels grow
     DeviceBuffer d_develop_in;                          // srt_develop_kat: the caller's film in 96-float rows
     hipEvent_t develop_ev[3] = {};                      // around the kernels of the last develop: contraction | sRGB epilogue (created on first use)
@@ -199,6 +200,12 @@ struct srt_ctx {
     srt_camera_data temporal_cam = {};                  // the camera that was current when the history was written
     hipEvent_t temporal_ev[2] = {};                     // around the last temporal kernel (created on first use)
     bool temporal_timed = false;
+    // ... its moments (srt_*_temporal_vg): allocated by the first call that asks for them
+    DeviceBuffer d_temporal_mom;                        // the double-buffered moments history Hm (TemporalMoments): 32 bytes per pixel, halves indexed as d_temporal_hist's
+    bool temporal_moments = false;                      // the last call that advanced the history wrote Hm (it is present while temporal_frames > 0)
+    DeviceBuffer d_temporal_var;                        // the choice kernel's counter; srt_temporal_variance_kat: and the caller's arrays (TemporalVarianceKatLayout)
+    hipEvent_t temporal_var_ev[2] = {};                 // around the last choice kernel (created on first use)
+    bool temporal_var_timed = false;
     // BVH refit (srt_refit.hip).  The topology tables are made on the host by srt_upload_scene (RefitParams states them), copied to the
     // device by the first refit after an upload; tables, scratch and staging belong to the context and are reused.
     std::vector<uint32_t> refit_tri_tab, refit_sched;   // two words per triangle; the record indices grouped by height
@@ -740,6 +747,7 @@ void srt_destroy(srt_ctx *c) {
     for (hipEvent_t e : c->present_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->despeckle_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->temporal_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->temporal_var_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->refit_ev) if (e) (void)hipEventDestroy(e);
     delete c;      // (every DeviceBuffer, and the pinned staging block, frees itself, on the device selected above)
 }
@@ -2041,16 +2049,43 @@ struct TemporalHistory {
         for (int k = 0; k < 2; k++) { colour[k] = d.as<float4>() + 3 * pixels * k; guides[k] = colour[k] + pixels; }
     }
 };
-// d_temporal_kat: [guides: 2 float4 per pixel | hist_c: 1 | hist_g: 2 | new_c: 1 | new_g: 2 | (moving: prev_point: 1) | xyz: three floats per pixel]
+// d_temporal_mom: two halves of [Hm: one float4 per pixel], the half k written together with half k of d_temporal_hist
+struct TemporalMoments {
+    float4 *m[2];
+    static size_t bytes(size_t pixels) { return 2 * pixels * sizeof(float4); }
+    TemporalMoments(const DeviceBuffer &d, size_t pixels) { m[0] = d.as<float4>(); m[1] = m[0] + pixels; }
+};
+// d_temporal_var: [the choice kernel's counter (u64), padded to 64 bytes | srt_temporal_variance_kat only: moments: 1 float4 per pixel |
+//                  len | spatial | out: one float per pixel each]
+struct TemporalVarianceLayout {
+    unsigned long long *count;
+    float4 *moments;
+    float *len, *spatial, *out;
+    static constexpr size_t kHeadBytes = 64;
+    static size_t bytes(size_t pixels) { return kHeadBytes + pixels * (sizeof(float4) + 3 * sizeof(float)); }
+    TemporalVarianceLayout(const DeviceBuffer &d, size_t pixels) : count(d.as<unsigned long long>()) {
+        moments = reinterpret_cast<float4 *>(d.as<char>() + kHeadBytes); len = reinterpret_cast<float *>(moments + pixels);
+        spatial = len + pixels; out = spatial + pixels;      // (inside the buffer only when it was reserved with pixels)
+    }
+};
+// d_temporal_kat: [guides: 2 float4 per pixel | hist_c: 1 | hist_g: 2 | new_c: 1 | new_g: 2 | (moving: prev_point: 1) | (moments: hist_m: 1 |
+//                  new_m: 1) | xyz: three floats per pixel]
 struct TemporalKatLayout {
     float4 *guides, *hist_c, *hist_g, *new_c, *new_g;
     float *xyz;
-    float4 *prev_point;      // (srt_temporal_moving_kat only, else null)
-    static size_t bytes(size_t pixels, bool moving = false) { return pixels * ((moving ? 9 : 8) * sizeof(float4) + 3 * sizeof(float)); }
-    TemporalKatLayout(const DeviceBuffer &d, size_t pixels, bool moving = false) : guides(d.as<float4>()) {
+    float4 *prev_point;      // (the moving stage only, else null)
+    float4 *hist_m, *new_m;  // (srt_temporal_moments_kat only, else null)
+    static size_t bytes(size_t pixels, bool moving = false, bool moments = false) {
+        return pixels * ((8 + (moving ? 1 : 0) + (moments ? 2 : 0)) * sizeof(float4) + 3 * sizeof(float));
+    }
+    TemporalKatLayout(const DeviceBuffer &d, size_t pixels, bool moving = false, bool moments = false) : guides(d.as<float4>()) {
         hist_c = guides + 2 * pixels; hist_g = hist_c + pixels; new_c = hist_g + 2 * pixels; new_g = new_c + pixels;
-        prev_point = moving ? new_g + 2 * pixels : nullptr;
-        xyz = reinterpret_cast<float *>(new_g + (moving ? 3 : 2) * pixels);
+        float4 *next = new_g + 2 * pixels;
+        prev_point = moving ? next : nullptr;
+        if (moving) next += pixels;
+        hist_m = moments ? next : nullptr; new_m = moments ? next + pixels : nullptr;
+        if (moments) next += 2 * pixels;
+        xyz = reinterpret_cast<float *>(next);
     }
 };
 // d_motion: [counters: hit, miss, moved, degenerate (u64 each), padded to 64 bytes | point: one float4 per pixel | tri: one word | bary: three floats]
@@ -2134,6 +2169,13 @@ const char *temporal_cfg_error(const srt_temporal *t) {
     return nullptr;
 }
 
+const char *temporal_vg_cfg_error(const srt_temporal_vg *t) {
+    if (t->min_len < 2u || t->min_len > (1u << 24)) return "temporal_vg: min_len must be in 2 .. 2^24";
+    if (t->moving > 1u) return "temporal_vg: moving must be 0 or 1";
+    if (t->reserved[0] | t->reserved[1]) return "temporal_vg: the reserved words must be 0";
+    return nullptr;
+}
+
 // the host constants of srt_c_api.h, fp32, one rounding per operation (this unit is built without contraction)
 struct Vec3f { float x, y, z; };
 Vec3f vec3f(const float a[3]) { return {a[0], a[1], a[2]}; }
@@ -2178,7 +2220,8 @@ int run_temporal_kernel(srt_ctx *c, const char *who, TemporalParams p, const srt
 
 // The stage on the context's history: p holds the sources, dst4 and outputs of the w x h rectangle of the last chunk.  A history of another
 // rectangle is discarded (res->history_dropped).  The history advances when the kernel has been enqueued.  d_temporal is reserved by the caller.
-int run_temporal_history(srt_ctx *c, const char *who, TemporalParams p, const srt_temporal *cfg, srt_temporal_result *res) {
+// moments: the call carries Hm (srt_*_temporal_vg) -- gathered when the previous call wrote one, seeded otherwise; a call without marks it absent.
+int run_temporal_history(srt_ctx *c, const char *who, TemporalParams p, const srt_temporal *cfg, srt_temporal_result *res, bool moments = false) {
     const uint32_t rect[4] = {p.w, p.h, c->last_offx, c->last_offy};
     const size_t pixels = (size_t)p.w * p.h;
     res->history_dropped = 0;
@@ -2194,12 +2237,18 @@ int run_temporal_history(srt_ctx *c, const char *who, TemporalParams p, const sr
     const uint32_t old = c->temporal_cur, neu = old ^ 1u;
     p.hist_c = c->temporal_frames ? H.colour[old] : nullptr; p.hist_g = c->temporal_frames ? H.guides[old] : nullptr;
     p.new_c = H.colour[neu]; p.new_g = H.guides[neu];
+    if (moments) {      // (allocated by the first call that asks; growing happens only where no Hm is present: a present one has this rectangle)
+        if (const int rc = develop_reserve(c, who, c->d_temporal_mom, TemporalMoments::bytes(pixels))) return rc;
+        const TemporalMoments M(c->d_temporal_mom, pixels);
+        p.hist_m = (c->temporal_frames && c->temporal_moments) ? M.m[old] : nullptr; p.new_m = M.m[neu];
+    }
     p.ox = c->last_offx; p.oy = c->last_offy;
     if (const int rc = run_temporal_kernel(c, who, p, cfg, c->cam, &c->temporal_cam)) {
         c->temporal_frames = 0;      // (a launch that failed may have left half a history)
         return rc;
     }
     c->temporal_cur = neu; c->temporal_frames++; c->temporal_cam = c->cam;
+    c->temporal_moments = moments;
     c->verts_hist = false; c->refits_pending = 0;      // (the new history shows V_cur)
     memcpy(c->temporal_rect, rect, sizeof(rect));
     res->history_frames = c->temporal_frames;
@@ -2221,7 +2270,27 @@ struct TemporalStage {
     srt_temporal_result res;
     bool moving = false;      // the *_moving calls: the motion pass on the rectangle first, then the moving stage on its points
     srt_motion_result mres = {};
+    const srt_temporal_vg *tv = nullptr;      // srt_*_temporal_vg (variance-guided plans only): the moments stage, then the estimator and the choice
+    unsigned long long n_temporal = 0;        // ... the pixels that took the temporal variance (read by the caller with the counters)
 };
+
+// The choice kernel on p (everything but the counter set by the caller), between the context's two events of its own.  d_temporal_var is
+// reserved by the caller.  Enqueues; the caller synchronises.
+int run_temporal_variance(srt_ctx *c, const char *who, TemporalVarianceParams p) {
+    c->temporal_var_timed = false;
+    for (hipEvent_t &e : c->temporal_var_ev) if (!e) HIP_TRY_AS(c, who, hipEventCreate(&e));
+    p.count = TemporalVarianceLayout(c->d_temporal_var, 0).count;
+    HIP_TRY_AS(c, who, hipMemsetAsync(p.count, 0, sizeof(unsigned long long), nullptr));
+    HIP_TRY_AS(c, who, hipEventRecord(c->temporal_var_ev[0], nullptr));
+    HIP_TRY_AS(c, who, launch_temporal_variance(p, nullptr));
+    HIP_TRY_AS(c, who, hipEventRecord(c->temporal_var_ev[1], nullptr));
+    c->temporal_var_timed = true;
+    return SRT_OK;
+}
+int read_temporal_variance_count(srt_ctx *c, const char *who, unsigned long long *n) {
+    HIP_TRY_AS(c, who, hipMemcpy(n, TemporalVarianceLayout(c->d_temporal_var, 0).count, sizeof(*n), hipMemcpyDeviceToHost));
+    return SRT_OK;
+}
 
 }  // namespace
 
@@ -2232,13 +2301,15 @@ int srt_temporal_reset(srt_ctx *c) {
     return SRT_OK;
 }
 
-// srt_temporal_kat (moving false, prev_point not read) and srt_temporal_moving_kat (moving true: prev_point[h][w][4], not null)
+// srt_temporal_kat (moving false, prev_point not read) and srt_temporal_moving_kat (moving true: prev_point[h][w][4], not null);
+// srt_temporal_moments_kat (moments true: hist_moments[h][w][4], read with a history only and null for none, and out_moments[h][w][4])
 static int temporal_kat(srt_ctx *c, const char *who, const srt_temporal *cfg, const srt_camera_data *cur_cam, const srt_camera_data *prev_cam, const float *xyz_mean,
                         const float *guides, const float *hist_colour, const float *hist_guides, uint32_t w, uint32_t h, uint32_t ox, uint32_t oy,
-                        float *out_colour, float *out_guides, float *out_motion, srt_temporal_result *result, bool moving, const float *prev_point) {
+                        float *out_colour, float *out_guides, float *out_motion, srt_temporal_result *result, bool moving, const float *prev_point,
+                        bool moments = false, const float *hist_moments = nullptr, float *out_moments = nullptr) {
     const std::string w_(std::string(who) + ": ");
     if (!c || !cfg || !cur_cam || !xyz_mean || !guides || (moving && !prev_point)) return fail(c, SRT_ERR_INVALID, w_ + "null argument");
-    if (!out_colour && !out_guides && !out_motion && !result) return fail(c, SRT_ERR_INVALID, w_ + "no output");
+    if (!out_colour && !out_guides && !out_motion && !out_moments && !result) return fail(c, SRT_ERR_INVALID, w_ + "no output");
     if (w == 0 || h == 0 || (uint64_t)w * h > 0x7fffffffull) return fail(c, SRT_ERR_INVALID, w_ + "w x h must be in 1 .. 2^31 - 1");
     if ((uint64_t)ox + w > (1ull << 24) || (uint64_t)oy + h > (1ull << 24)) return fail(c, SRT_ERR_INVALID, w_ + "ox + w and oy + h must not exceed 2^24");
     if (const char *why = temporal_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, w_ + why);
@@ -2246,22 +2317,25 @@ static int temporal_kat(srt_ctx *c, const char *who, const srt_temporal *cfg, co
     HIP_TRY(c, set_device(c));
     const size_t pixels = (size_t)w * h;
     if (const int rc = develop_reserve(c, who, c->d_temporal, TemporalLayout::bytes(pixels))) return rc;
-    if (const int rc = develop_reserve(c, who, c->d_temporal_kat, TemporalKatLayout::bytes(pixels, moving))) return rc;
+    if (const int rc = develop_reserve(c, who, c->d_temporal_kat, TemporalKatLayout::bytes(pixels, moving, moments))) return rc;
     const TemporalLayout L(c->d_temporal, pixels);
-    const TemporalKatLayout K(c->d_temporal_kat, pixels, moving);
+    const TemporalKatLayout K(c->d_temporal_kat, pixels, moving, moments);
     if (moving) HIP_TRY_AS(c, who, hipMemcpy(K.prev_point, prev_point, pixels * sizeof(float4), hipMemcpyHostToDevice));
     HIP_TRY_AS(c, who, hipMemcpy(K.xyz, xyz_mean, pixels * 3 * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY_AS(c, who, hipMemcpy(K.guides, guides, pixels * 2 * sizeof(float4), hipMemcpyHostToDevice));
     if (history) {
         HIP_TRY_AS(c, who, hipMemcpy(K.hist_c, hist_colour, pixels * sizeof(float4), hipMemcpyHostToDevice));
         HIP_TRY_AS(c, who, hipMemcpy(K.hist_g, hist_guides, pixels * 2 * sizeof(float4), hipMemcpyHostToDevice));
+        if (moments && hist_moments) HIP_TRY_AS(c, who, hipMemcpy(K.hist_m, hist_moments, pixels * sizeof(float4), hipMemcpyHostToDevice));
     }
     TemporalParams p = {};
     p.xyz = K.xyz; p.guides = K.guides; p.hist_c = history ? K.hist_c : nullptr; p.hist_g = history ? K.hist_g : nullptr;
     p.new_c = K.new_c; p.new_g = K.new_g; p.w = w; p.h = h; p.ox = ox; p.oy = oy;
     p.out_motion = out_motion ? L.motion : nullptr;
     p.prev_point = K.prev_point;
+    p.hist_m = (history && hist_moments) ? K.hist_m : nullptr; p.new_m = K.new_m;
     if (const int rc = run_temporal_kernel(c, who, p, cfg, *cur_cam, prev_cam)) return rc;
+    if (out_moments) HIP_TRY_AS(c, who, hipMemcpy(out_moments, K.new_m, pixels * sizeof(float4), hipMemcpyDeviceToHost));
     if (out_colour) HIP_TRY_AS(c, who, hipMemcpy(out_colour, K.new_c, pixels * sizeof(float4), hipMemcpyDeviceToHost));
     if (out_guides) HIP_TRY_AS(c, who, hipMemcpy(out_guides, K.new_g, pixels * 2 * sizeof(float4), hipMemcpyDeviceToHost));
     if (out_motion) HIP_TRY_AS(c, who, hipMemcpy(out_motion, L.motion, pixels * 2 * sizeof(float), hipMemcpyDeviceToHost));
@@ -2285,6 +2359,65 @@ int srt_temporal_moving_kat(srt_ctx *c, const srt_temporal *cfg, const srt_camer
                             float *out_colour, float *out_guides, float *out_motion, srt_temporal_result *result, const float *prev_point) {
     return temporal_kat(c, "srt_temporal_moving_kat", cfg, cur_cam, prev_cam, xyz_mean, guides, hist_colour, hist_guides, w, h, ox, oy, out_colour, out_guides,
                         out_motion, result, true, prev_point);
+}
+
+int srt_temporal_moments_kat(srt_ctx *c, const srt_temporal *cfg, const srt_camera_data *cur_cam, const srt_camera_data *prev_cam, const float *xyz_mean,
+                             const float *guides, const float *hist_colour, const float *hist_guides, uint32_t w, uint32_t h, uint32_t ox, uint32_t oy,
+                             float *out_colour, float *out_guides, float *out_motion, srt_temporal_result *result, const float *prev_point,
+                             const float *hist_moments, float *out_moments) {
+    return temporal_kat(c, "srt_temporal_moments_kat", cfg, cur_cam, prev_cam, xyz_mean, guides, hist_colour, hist_guides, w, h, ox, oy, out_colour, out_guides,
+                        out_motion, result, prev_point != nullptr, prev_point, true, hist_moments, out_moments);
+}
+
+int srt_temporal_variance_kat(srt_ctx *c, const float *moments, const float *len, const float *spatial_var, uint32_t min_len, uint32_t w, uint32_t h,
+                              float *out_var, uint64_t *n_temporal) {
+    const char *who = "srt_temporal_variance_kat";
+    if (!c || !moments || !len || !spatial_var) return fail(c, SRT_ERR_INVALID, "srt_temporal_variance_kat: null argument");
+    if (!out_var && !n_temporal) return fail(c, SRT_ERR_INVALID, "srt_temporal_variance_kat: no output");
+    if (w == 0 || h == 0 || (uint64_t)w * h > 0x7fffffffull) return fail(c, SRT_ERR_INVALID, "srt_temporal_variance_kat: w x h must be in 1 .. 2^31 - 1");
+    if (min_len < 2u || min_len > (1u << 24)) return fail(c, SRT_ERR_INVALID, "srt_temporal_variance_kat: min_len must be in 2 .. 2^24");
+    HIP_TRY(c, set_device(c));
+    const size_t pixels = (size_t)w * h;
+    if (const int rc = develop_reserve(c, who, c->d_temporal_var, TemporalVarianceLayout::bytes(pixels))) return rc;
+    const TemporalVarianceLayout V(c->d_temporal_var, pixels);
+    HIP_TRY_AS(c, who, hipMemcpy(V.moments, moments, pixels * sizeof(float4), hipMemcpyHostToDevice));
+    HIP_TRY_AS(c, who, hipMemcpy(V.len, len, pixels * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY_AS(c, who, hipMemcpy(V.spatial, spatial_var, pixels * sizeof(float), hipMemcpyHostToDevice));
+    TemporalVarianceParams p = {};
+    p.moments = V.moments; p.len = V.len; p.spatial = V.spatial; p.len_stride = 1; p.spatial_stride = 1; p.out_stride = 1;
+    p.ml_min = (float)min_len; p.n = (uint32_t)pixels; p.out_var = V.out;
+    if (const int rc = run_temporal_variance(c, who, p)) return rc;
+    if (out_var) HIP_TRY_AS(c, who, hipMemcpy(out_var, V.out, pixels * sizeof(float), hipMemcpyDeviceToHost));
+    unsigned long long n = 0;
+    if (const int rc = read_temporal_variance_count(c, who, &n)) return rc;
+    HIP_TRY_AS(c, who, device_synchronize(c));
+    if (n_temporal) *n_temporal = n;
+    return SRT_OK;
+}
+
+int srt_read_temporal_moments(srt_ctx *c, float *out, uint32_t image_width, uint32_t image_height) {
+    const char *who = "srt_read_temporal_moments";
+    if (!c || !out || image_width == 0 || image_height == 0) return fail(c, SRT_ERR_INVALID, "srt_read_temporal_moments: null argument / empty image");
+    if (!c->temporal_frames || !c->temporal_moments) return fail(c, SRT_ERR_INVALID, "srt_read_temporal_moments: the context holds no moments history");
+    HIP_TRY(c, set_device(c));
+    const uint32_t w = c->temporal_rect[0], h = c->temporal_rect[1], ox = c->temporal_rect[2], oy = c->temporal_rect[3];
+    if (ox < image_width && oy < image_height) {      // the history's rectangle, placed and clipped as the stage's outputs are
+        const uint32_t cw = std::min<uint32_t>(w, image_width - ox), ch = std::min<uint32_t>(h, image_height - oy);
+        const float4 *src = TemporalMoments(c->d_temporal_mom, (size_t)w * h).m[c->temporal_cur];
+        HIP_TRY_AS(c, who, hipMemcpy2D(out + ((size_t)oy * image_width + ox) * 4, (size_t)image_width * sizeof(float4), src, (size_t)w * sizeof(float4),
+                                       (size_t)cw * sizeof(float4), ch, hipMemcpyDeviceToHost));
+    }
+    HIP_TRY_AS(c, who, device_synchronize(c));
+    return SRT_OK;
+}
+
+int srt_temporal_variance_last_ms(srt_ctx *c, float *ms) {
+    if (!c || !ms) return fail(c, SRT_ERR_INVALID, "srt_temporal_variance_last_ms: null argument");
+    if (!c->temporal_var_timed) return fail(c, SRT_ERR_INVALID, "srt_temporal_variance_last_ms: no choice kernel has run on this context");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipEventSynchronize(c->temporal_var_ev[1]));
+    HIP_TRY(c, hipEventElapsedTime(ms, c->temporal_var_ev[0], c->temporal_var_ev[1]));
+    return SRT_OK;
 }
 
 // ---- surface motion (srt_motion.hip) ---------------------------------------------------------------------------------------------
@@ -2428,6 +2561,9 @@ DenoisePlan denoise_vg_plan(const srt_denoise_vg *cfg) {
 // context's history, between its own events and with one more denoise event behind it.  ts_out (with ts): the stage's outputs; the run
 // stops behind the stage -- no level, no epilogue: srt_temporal_accum -- and records no denoise event, so the timing of the context's
 // last denoise stays what it was.
+// ts->tv (variance-guided plans; the caller has reserved d_temporal_var): the stage carries the moments, the spatial estimator runs behind
+// it, on its output, and the choice kernel puts the temporal variance where it holds: prepass | (despeckle) | stage | estimator | choice |
+// levels | epilogue.  denoise_est_ev is the event the estimator starts at.
 int run_denoise(srt_ctx *c, const char *who, const DenoisePlan &plan, DenoisePrepassParams pre, const float *sum_y2 = nullptr, const srt_despeckle *ds = nullptr,
                 TemporalStage *ts = nullptr, const TemporalParams *ts_out = nullptr) {
     const size_t pixels = (size_t)pre.w * pre.h;
@@ -2450,7 +2586,7 @@ int run_denoise(srt_ctx *c, const char *who, const DenoisePlan &plan, DenoisePre
         mp.colour = reinterpret_cast<float *>(L.colour[0]); mp.out_var = L.var;
         HIP_TRY_AS(c, who, launch_denoise_measured(mp, nullptr));
         HIP_TRY_AS(c, who, mark());
-    } else if (plan.vg) {
+    } else if (plan.vg && !(ts && ts->tv)) {
         DenoiseVarianceParams vp = {};
         vp.guides = L.guides; vp.colour = reinterpret_cast<float *>(L.colour[0]); vp.out_var = L.var;
         vp.w = pre.w; vp.h = pre.h; vp.kn = plan.kn; vp.ka = plan.ka; vp.kz = plan.kz;
@@ -2473,10 +2609,27 @@ int run_denoise(srt_ctx *c, const char *who, const DenoisePlan &plan, DenoisePre
             if (const int rc = run_motion_bound(c, who, pre.w, pre.h, c->last_offx, c->last_offy)) return rc;
             tp.prev_point = MotionLayout(c->d_motion, pixels).point;
         }
-        if (const int rc = run_temporal_history(c, who, tp, ts->cfg, &ts->res)) return rc;
+        if (const int rc = run_temporal_history(c, who, tp, ts->cfg, &ts->res, ts->tv != nullptr)) return rc;
         HIP_TRY_AS(c, who, mark());
         cur ^= 1u;
         if (ts_out) return SRT_OK;      // (the stage alone)
+    }
+    uint32_t est_ev = 1;
+    if (ts && ts->tv) {      // the spatial estimate of the stage's output, then the choice between it and the moments' variance
+        est_ev = n_ev - 1;
+        DenoiseVarianceParams vp = {};
+        vp.guides = L.guides; vp.colour = reinterpret_cast<float *>(L.colour[cur]); vp.out_var = L.var;
+        vp.w = pre.w; vp.h = pre.h; vp.kn = plan.kn; vp.ka = plan.ka; vp.kz = plan.kz;
+        HIP_TRY_AS(c, who, launch_denoise_variance(vp, nullptr));
+        HIP_TRY_AS(c, who, mark());
+        TemporalVarianceParams cp = {};
+        cp.moments = TemporalMoments(c->d_temporal_mom, pixels).m[c->temporal_cur];
+        cp.len = reinterpret_cast<const float *>(TemporalHistory(c->d_temporal_hist, pixels).colour[c->temporal_cur]) + 3; cp.len_stride = 4;
+        cp.spatial = vp.colour + 3; cp.spatial_stride = 4; cp.colour_w = vp.colour + 3;
+        cp.out_var = L.var; cp.out_stride = 2;
+        cp.ml_min = (float)ts->tv->min_len; cp.n = (uint32_t)pixels;
+        if (const int rc = run_temporal_variance(c, who, cp)) return rc;
+        HIP_TRY_AS(c, who, mark());
     }
     const uint32_t level_ev = n_ev - 1;
     for (uint32_t i = 0; i < plan.levels; i++) {
@@ -2501,7 +2654,7 @@ int run_denoise(srt_ctx *c, const char *who, const DenoisePlan &plan, DenoisePre
     HIP_TRY_AS(c, who, launch_denoise_epilogue(reinterpret_cast<const float *>(L.colour[cur]), L.out[0], L.out[1], L.out[2], pixels, nullptr));
     if (plan.vg) HIP_TRY_AS(c, who, launch_denoise_var_out(reinterpret_cast<const float *>(L.colour[cur]), L.var, pixels, nullptr));
     HIP_TRY_AS(c, who, mark());
-    c->denoise_timed_levels = plan.levels; c->denoise_level_ev = level_ev; c->denoise_estimated = plan.vg; c->denoise_timed = true;
+    c->denoise_timed_levels = plan.levels; c->denoise_level_ev = level_ev; c->denoise_estimated = plan.vg; c->denoise_est_ev = est_ev; c->denoise_timed = true;
     return SRT_OK;
 }
 
@@ -2526,6 +2679,7 @@ int denoise_accumulation(srt_ctx *c, const char *who, const DenoisePlan &plan, u
     HIP_TRY(c, c->d_denoise.reserve(DenoiseLayout::bytes((size_t)w * h, plan.vg)));
     if (ds) if (const int rc = develop_reserve(c, who, c->d_despeckle, DespeckleLayout::kHeadBytes)) return rc;
     if (ts && !ts_out) if (const int rc = develop_reserve(c, who, c->d_temporal, ts->out_xyz ? TemporalLayout::bytes((size_t)w * h) : TemporalLayout::kHeadBytes)) return rc;
+    if (ts && ts->tv) if (const int rc = develop_reserve(c, who, c->d_temporal_var, TemporalVarianceLayout::kHeadBytes)) return rc;
     DenoisePrepassParams pre = {};
     pre.sums = AccumLayout(c).sums; pre.sum_pixel_stride = 1; pre.sum_comp_stride = c->n_lanes;
     pre.rows = reinterpret_cast<const float4 *>(feature_rows(c));
@@ -2554,6 +2708,7 @@ int denoise_features(srt_ctx *c, const char *who, const DenoisePlan &plan, float
         }
         if (ts) if (const int rc = read_temporal_counts(c, who, &ts->res)) return rc;
         if (ts && ts->moving) if (const int rc = read_motion_counts(c, who, &ts->mres)) return rc;
+        if (ts && ts->tv) if (const int rc = read_temporal_variance_count(c, who, &ts->n_temporal)) return rc;
     }
     HIP_TRY(c, device_synchronize(c));
     return SRT_OK;
@@ -2642,6 +2797,28 @@ int srt_denoise_features_temporal_moving(srt_ctx *c, const srt_temporal *tempora
                                          srt_motion_result *motion_result) {
     return denoise_features_temporal(c, "srt_denoise_features_temporal_moving", temporal_cfg, despeckle_cfg, denoise_cfg, out_xyz, out_lin, out_q, temporal_result,
                                      image_width, image_height, true, motion_result);
+}
+
+int srt_denoise_features_temporal_vg(srt_ctx *c, const srt_temporal *temporal_cfg, const srt_despeckle *despeckle_cfg, const srt_denoise_vg *vg_cfg,
+                                     const srt_temporal_vg *tv_cfg, float *out_xyz, float *out_lin, float *out_q, float *out_var, srt_temporal_result *temporal_result,
+                                     uint64_t *n_temporal, srt_motion_result *motion_result, uint32_t image_width, uint32_t image_height) {
+    const char *who = "srt_denoise_features_temporal_vg";
+    const std::string w_(std::string(who) + ": ");
+    if (!c || !temporal_cfg || !vg_cfg || !tv_cfg) return fail(c, SRT_ERR_INVALID, w_ + "null argument");
+    if ((!out_xyz && !out_lin && !out_q && !out_var) || image_width == 0 || image_height == 0) return fail(c, SRT_ERR_INVALID, w_ + "no output / empty image");
+    if (const char *why = denoise_vg_cfg_error(vg_cfg)) return fail(c, SRT_ERR_INVALID, w_ + why);
+    if (despeckle_cfg) if (const char *why = despeckle_cfg_error(despeckle_cfg)) return fail(c, SRT_ERR_INVALID, w_ + why);
+    if (const char *why = temporal_cfg_error(temporal_cfg)) return fail(c, SRT_ERR_INVALID, w_ + why);
+    if (const char *why = temporal_vg_cfg_error(tv_cfg)) return fail(c, SRT_ERR_INVALID, w_ + why);
+    if (tv_cfg->moving) if (const char *why = motion_bound_refusal(c)) return fail(c, SRT_ERR_INVALID, w_ + why);
+    float *const host[4] = {out_xyz, out_lin, out_q, out_var};
+    TemporalStage ts = {temporal_cfg, false, {}};
+    ts.moving = tv_cfg->moving != 0; ts.tv = tv_cfg;
+    if (const int rc = denoise_features(c, who, denoise_vg_plan(vg_cfg), host, image_width, image_height, despeckle_cfg, &ts)) return rc;
+    if (temporal_result) *temporal_result = ts.res;
+    if (n_temporal) *n_temporal = ts.n_temporal;
+    if (motion_result) *motion_result = ts.mres;
+    return SRT_OK;
 }
 
 static int temporal_accum(srt_ctx *c, const char *who, const srt_temporal *cfg, float *out_xyz, float *out_lin, float *out_q, float *out_len, float *out_motion,
@@ -2795,7 +2972,7 @@ int run_denoise_developed(srt_ctx *c, const char *who, const DenoisePlan &plan, 
     HIP_TRY_AS(c, who, launch_denoise_epilogue(reinterpret_cast<const float *>(L.colour[cur]), L.out[0], L.out[1], L.out[2], pixels, nullptr));
     HIP_TRY_AS(c, who, launch_denoise_dev_out(D.payload[cur], D.out, channels, groups, pixels, nullptr));
     HIP_TRY_AS(c, who, hipEventRecord(c->denoise_ev[n_ev++], nullptr));
-    c->denoise_timed_levels = plan.levels; c->denoise_level_ev = level_ev; c->denoise_estimated = false; c->denoise_timed = true;
+    c->denoise_timed_levels = plan.levels; c->denoise_level_ev = level_ev; c->denoise_estimated = false; c->denoise_est_ev = 1; c->denoise_timed = true;
     return SRT_OK;
 }
 
@@ -2914,8 +3091,8 @@ int srt_denoise_estimate_last_ms(srt_ctx *c, float *ms) {
     if (!c || !ms) return fail(c, SRT_ERR_INVALID, "srt_denoise_estimate_last_ms: null argument");
     if (!c->denoise_timed || !c->denoise_estimated) return fail(c, SRT_ERR_INVALID, "srt_denoise_estimate_last_ms: the context's last denoise was not variance-guided");
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipEventSynchronize(c->denoise_ev[2]));
-    HIP_TRY(c, hipEventElapsedTime(ms, c->denoise_ev[1], c->denoise_ev[2]));
+    HIP_TRY(c, hipEventSynchronize(c->denoise_ev[c->denoise_est_ev + 1]));
+    HIP_TRY(c, hipEventElapsedTime(ms, c->denoise_ev[c->denoise_est_ev], c->denoise_ev[c->denoise_est_ev + 1]));
     return SRT_OK;
 }
 
@@ -2974,7 +3151,8 @@ namespace {
 // srt_present_temporal (tcfg: the temporal stage in front of the chain, behind the firefly filter when there is one; ts_result may be null)
 int present_chain(srt_ctx *c, const char *who, const srt_present_cfg *cfg, const srt_despeckle *ds, uint8_t *out_rgba8, size_t pitch_bytes, uint32_t image_width,
                   uint32_t image_height, srt_present_result *result, srt_despeckle_result *ds_result, const srt_temporal *tcfg = nullptr,
-                  srt_temporal_result *ts_result = nullptr, bool moving = false, srt_motion_result *mo_result = nullptr) {
+                  srt_temporal_result *ts_result = nullptr, bool moving = false, srt_motion_result *mo_result = nullptr, const srt_temporal_vg *tv = nullptr,
+                  uint64_t *n_temporal = nullptr) {
     const std::string w_(std::string(who) + ": ");
     if (!c || !cfg || !out_rgba8) return fail(c, SRT_ERR_INVALID, w_ + "null argument");
     for (const uint32_t r : cfg->reserved) if (r) return fail(c, SRT_ERR_INVALID, w_ + "the reserved words must be 0");
@@ -2985,12 +3163,15 @@ int present_chain(srt_ctx *c, const char *who, const srt_present_cfg *cfg, const
     if (cfg->metered) if (const char *why = meter_cfg_error(&cfg->meter)) return fail(c, SRT_ERR_INVALID, w_ + why);
     if (ds) {
         if (const char *why = despeckle_cfg_error(ds)) return fail(c, SRT_ERR_INVALID, w_ + why);
-        if (cfg->source != SRT_PRESENT_ACCUM && cfg->source != SRT_PRESENT_DENOISE)
+        if (cfg->source != SRT_PRESENT_ACCUM && cfg->source != SRT_PRESENT_DENOISE && !(tv && cfg->source == SRT_PRESENT_DENOISE_VG))
             return fail(c, SRT_ERR_UNSUPPORTED, w_ + "the despeckled sources are SRT_PRESENT_ACCUM and SRT_PRESENT_DENOISE");
     }
     if (tcfg) {
         if (const char *why = temporal_cfg_error(tcfg)) return fail(c, SRT_ERR_INVALID, w_ + why);
-        if (cfg->source != SRT_PRESENT_ACCUM && cfg->source != SRT_PRESENT_DENOISE)
+        if (tv) {      // srt_present_temporal_vg
+            if (const char *why = temporal_vg_cfg_error(tv)) return fail(c, SRT_ERR_INVALID, w_ + why);
+            if (cfg->source != SRT_PRESENT_DENOISE_VG) return fail(c, SRT_ERR_UNSUPPORTED, w_ + "the one source is SRT_PRESENT_DENOISE_VG");
+        } else if (cfg->source != SRT_PRESENT_ACCUM && cfg->source != SRT_PRESENT_DENOISE)
             return fail(c, SRT_ERR_UNSUPPORTED, w_ + "the temporal sources are SRT_PRESENT_ACCUM and SRT_PRESENT_DENOISE");
     }
     const bool denoised = cfg->source == SRT_PRESENT_DENOISE || cfg->source == SRT_PRESENT_DENOISE_VG || cfg->source == SRT_PRESENT_DENOISE_MV;
@@ -3028,7 +3209,7 @@ int present_chain(srt_ctx *c, const char *who, const srt_present_cfg *cfg, const
     srt_present_result res = {};
     srt_despeckle_result ds_res = {};
     TemporalStage ts = {tcfg, !denoised, {}};
-    ts.moving = moving;
+    ts.moving = moving; ts.tv = tv;
     if (pixels) {
         if (const int rc = develop_reserve(c, who, c->d_expose, ExposeLayout::kBytes)) return rc;
         if (const int rc = develop_reserve(c, who, c->d_present, PresentLayout::bytes(pixels, developed))) return rc;
@@ -3085,12 +3266,14 @@ int present_chain(srt_ctx *c, const char *who, const srt_present_cfg *cfg, const
         if (ds) if (const int rc = read_despeckle_counts(c, who, &ds_res)) return rc;
         if (tcfg) if (const int rc = read_temporal_counts(c, who, &ts.res)) return rc;
         if (moving) if (const int rc = read_motion_counts(c, who, &ts.mres)) return rc;
+        if (tv) if (const int rc = read_temporal_variance_count(c, who, &ts.n_temporal)) return rc;
     }
     HIP_TRY(c, device_synchronize(c));
     if (result) *result = res;
     if (ds_result) *ds_result = ds_res;
     if (ts_result) *ts_result = ts.res;
     if (mo_result) *mo_result = ts.mres;
+    if (n_temporal) *n_temporal = ts.n_temporal;
     return SRT_OK;
 }
 
@@ -3120,6 +3303,14 @@ int srt_present_temporal_moving(srt_ctx *c, const srt_present_cfg *present_cfg, 
     if (!temporal_cfg) return fail(c, SRT_ERR_INVALID, "srt_present_temporal_moving: null argument");
     return present_chain(c, "srt_present_temporal_moving", present_cfg, despeckle_cfg, out_rgba8, pitch_bytes, image_width, image_height, result, nullptr, temporal_cfg,
                          temporal_result, true, motion_result);
+}
+
+int srt_present_temporal_vg(srt_ctx *c, const srt_present_cfg *present_cfg, const srt_temporal *temporal_cfg, const srt_despeckle *despeckle_cfg,
+                            const srt_temporal_vg *tv_cfg, uint8_t *out_rgba8, size_t pitch_bytes, uint32_t image_width, uint32_t image_height,
+                            srt_present_result *result, srt_temporal_result *temporal_result, uint64_t *n_temporal, srt_motion_result *motion_result) {
+    if (!temporal_cfg || !tv_cfg) return fail(c, SRT_ERR_INVALID, "srt_present_temporal_vg: null argument");
+    return present_chain(c, "srt_present_temporal_vg", present_cfg, despeckle_cfg, out_rgba8, pitch_bytes, image_width, image_height, result, nullptr, temporal_cfg,
+                         temporal_result, tv_cfg->moving == 1u, motion_result, tv_cfg, n_temporal);
 }
 
 int srt_present_kat(srt_ctx *c, const srt_tone *tone, const float *xyz_mean, uint32_t w, uint32_t h, uint8_t *out_rgba8, srt_tone_result *result) {

@@ -441,8 +441,28 @@ struct TemporalParams {
     // the moving variant (srt_temporal_*_moving; null: the static stage): per pixel (Pprev, valid) of the surface-motion pass, which a hit
     // pixel projects in the place of the point it would reconstruct from the distance guide
     const float4 *prev_point;
+    // the moments variant (srt_*_temporal_vg, srt_temporal_moments_kat; new_m null: the stage without moments): one float4 per pixel,
+    // (m1, m2, mlen, 0) -- the first and second luminance moment carried through the colour's taps with the colour's weights, and their
+    // own length.  hist_m: the previous call's (null: none, every finite pixel is seeded with (Y, Y * Y, 1, 0)); new_m (never hist_m)
+    // receives the new one.
+    const float4 *hist_m;
+    float4 *new_m;
 };
 hipError_t launch_temporal(const TemporalParams &p, hipStream_t st);
+// The choice of the variance behind the moments stage (srt_temporal.hip; stated in srt_c_api.h at srt_denoise_features_temporal_vg), over n
+// pixels: moments[p] = Hm', len[len_stride * p] = len', spatial[spatial_stride * p] = vs_p, ml_min = (float)min_len.  v_p goes to
+// out_var[out_stride * p] and, when colour_w is not null, to colour_w[4 * p] (the fourth word of the denoiser's colour image, which may be
+// where `spatial` is read: the kernel is elementwise).  *count is ADDED to: the pixels that took the temporal variance.
+struct TemporalVarianceParams {
+    const float4 *moments;
+    const float *len, *spatial;
+    uint32_t len_stride, spatial_stride, out_stride;
+    float ml_min;
+    uint32_t n;
+    float *colour_w, *out_var;
+    unsigned long long *count;
+};
+hipError_t launch_temporal_variance(const TemporalVarianceParams &p, hipStream_t st);
 // The surface-motion pass (srt_motion.hip; stated in srt_c_api.h at srt_surface_motion) over the row-major w x h rectangle at image offset
 // (ox, oy): the closest hit of every pixel's centre ray on the scene images (nodes, fringe, tris: RenderParams'), then the hit point moved
 // from the triangle's row of v_cur to its row of v_prev (9 floats per triangle each; v_prev null: nothing moved).  Outputs, any may be

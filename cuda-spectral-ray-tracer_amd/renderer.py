@@ -581,6 +581,116 @@ class Renderer:
                     clip=dict(blown=res.tone.blown, crushed=res.tone.crushed, nonfinite=res.tone.nonfinite), temporal=temporal_stats(tres),
                     surface=motion_stats(mres))
 
+    # ---- variance measured across frames: the moments in the history guide the filter (srt_c_api.h, "Variance measured across frames") ----
+    def denoise_temporal_vg(self, image_width, image_height, temporal=None, despeckle=None, min_len=4, moving=False, **vg_cfg):
+        """denoise_vg() behind the temporal stage, guided by the variance the history measured (srt_denoise_features_temporal_vg;
+        temporal and despeckle as denoise_temporal takes them; min_len and moving: the keywords of temporal_vg_config; vg_cfg: the
+        keywords of denoise_vg_config): the stage also carries the first and second luminance moment, and where their own history is at
+        least min_len frames long the levels are guided by the variance they measure, elsewhere by the spatial estimate of the stage's
+        output.  dict(xyz, lin, fb, var -- var[..., 0] the variance chosen --, stats = temporal_stats, n_temporal -- the pixels that
+        took the temporal variance; moving=True: and surface = motion_stats).  The history is the stage's output and the one temporal()
+        keeps; a moment-less temporal call in between restarts the moments, not the colour."""
+        c, t, v = denoise_vg_config(**vg_cfg), _temporal_cfg("denoise_temporal_vg", temporal), temporal_vg_config(min_len, moving)
+        d = None if despeckle is None else self._despeckle_cfg("denoise_temporal_vg", despeckle)
+        res, mres, n = B.TemporalResult(), B.MotionResult(), C.c_uint64()
+        out = [np.zeros((image_height, image_width, 3), np.float32) for _ in range(3)]
+        var = np.zeros((image_height, image_width, 2), np.float32)
+        self._ck(B.lib().srt_denoise_features_temporal_vg(self._h, C.byref(t), None if d is None else C.byref(d), C.byref(c), C.byref(v), B.fptr(out[0]),
+                                                          B.fptr(out[1]), B.fptr(out[2]), B.fptr(var), C.byref(res), C.byref(n), C.byref(mres), image_width,
+                                                          image_height))
+        self._moments_image = (image_width, image_height)
+        picture = dict(xyz=out[0], lin=out[1], fb=out[2], var=var, stats=temporal_stats(res), n_temporal=n.value)
+        if v.moving:
+            picture["surface"] = motion_stats(mres)
+        return picture
+
+    def present_temporal_vg(self, image_width, image_height, gain=None, temporal=None, despeckle=None, min_len=4, moving=False, **cfg):
+        """present() of the chain of denoise_temporal_vg (srt_present_temporal_vg; the source is "denoise_vg", cfg the other keywords of
+        present_config): the dict of present_temporal plus n_temporal (moving=True: and surface)."""
+        p, res, tres, mres, n = present_config("denoise_vg", gain, **cfg), B.PresentResult(), B.TemporalResult(), B.MotionResult(), C.c_uint64()
+        t, v = _temporal_cfg("present_temporal_vg", temporal), temporal_vg_config(min_len, moving)
+        d = None if despeckle is None else self._despeckle_cfg("present_temporal_vg", despeckle)
+        out = np.zeros((image_height, image_width, 4), np.uint8)
+        self._ck(B.lib().srt_present_temporal_vg(self._h, C.byref(p), C.byref(t), None if d is None else C.byref(d), C.byref(v),
+                                                 out.ctypes.data_as(C.POINTER(C.c_uint8)), 4 * image_width, image_width, image_height, C.byref(res), C.byref(tres),
+                                                 C.byref(n), C.byref(mres)))
+        self._moments_image = (image_width, image_height)
+        picture = dict(rgba=out, meter=_meter_dict(res.meter) if gain is None else None,
+                       clip=dict(blown=res.tone.blown, crushed=res.tone.crushed, nonfinite=res.tone.nonfinite), temporal=temporal_stats(tres),
+                       n_temporal=n.value)
+        if v.moving:
+            picture["surface"] = motion_stats(mres)
+        return picture
+
+    def temporal_moments_kat(self, cur_cam, xyz_mean, guides, prev_cam=None, hist_colour=None, hist_guides=None, hist_moments=None, prev_point=None,
+                             offx=0, offy=0, **cfg):
+        """temporal_kat with the moments (srt_temporal_moments_kat): hist_moments (h, w, 4) = (m1, m2, mlen, 0) of the previous call, None
+        for none; prev_point (h, w, 4): the moving stage of temporal_moving_kat, None: the static one.  The dict of temporal_kat plus
+        moments (h, w, 4), the new moments history."""
+        t, res = _temporal_cfg("temporal_moments_kat", cfg), B.TemporalResult()
+        img = _xyz_image("temporal_moments_kat", xyz_mean)
+        g = np.ascontiguousarray(guides, np.float32)
+        if g.shape != img.shape[:2] + (8,):
+            raise ValueError("temporal_moments_kat: needs guides %r, got %r" % (img.shape[:2] + (8,), g.shape))
+        given = [v is not None for v in (prev_cam, hist_colour, hist_guides)]
+        if any(given) and not all(given):
+            raise ValueError("temporal_moments_kat: a history is prev_cam, hist_colour and hist_guides together")
+        hc = hg = hm = pp = None
+        if all(given):
+            hc, hg = np.ascontiguousarray(hist_colour, np.float32), np.ascontiguousarray(hist_guides, np.float32)
+            if hc.shape != img.shape[:2] + (4,) or hg.shape != g.shape:
+                raise ValueError("temporal_moments_kat: needs hist_colour %r and hist_guides %r, got %r and %r" % (img.shape[:2] + (4,), g.shape, hc.shape, hg.shape))
+        for name, v in (("hist_moments", hist_moments), ("prev_point", prev_point)):
+            if v is not None and np.shape(v) != img.shape[:2] + (4,):
+                raise ValueError("temporal_moments_kat: needs %s %r, got %r" % (name, img.shape[:2] + (4,), np.shape(v)))
+        if hist_moments is not None:
+            if not all(given):
+                raise ValueError("temporal_moments_kat: hist_moments given without a colour history")
+            hm = np.ascontiguousarray(hist_moments, np.float32)
+        if prev_point is not None:
+            pp = np.ascontiguousarray(prev_point, np.float32)
+        colour, og, motion = np.zeros(img.shape[:2] + (4,), np.float32), np.zeros(g.shape, np.float32), np.zeros(img.shape[:2] + (2,), np.float32)
+        moments = np.zeros(img.shape[:2] + (4,), np.float32)
+        self._ck(B.lib().srt_temporal_moments_kat(self._h, C.byref(t), C.byref(cur_cam), C.byref(prev_cam) if all(given) else None, B.fptr(img), B.fptr(g),
+                                                  B.fptr(hc) if all(given) else None, B.fptr(hg) if all(given) else None, img.shape[1], img.shape[0],
+                                                  int(offx), int(offy), B.fptr(colour), B.fptr(og), B.fptr(motion), C.byref(res),
+                                                  None if pp is None else B.fptr(pp), None if hm is None else B.fptr(hm), B.fptr(moments)))
+        return dict(colour=colour, guides=og, motion=motion, moments=moments, stats=temporal_stats(res))
+
+    def temporal_variance_kat(self, moments, length, spatial_var, min_len=4):
+        """the choice of the variance on explicit inputs (srt_temporal_variance_kat): moments (h, w, 4) and length (h, w) as the stage
+        left them, spatial_var (h, w) the spatial estimate -> (var (h, w) float32, n_temporal): the moments' variance of the mean,
+        (m2 - m1^2) / len, where the moments are at least min_len frames long, spatial_var elsewhere, and the number of the former."""
+        v = temporal_vg_config(min_len)
+        m = np.ascontiguousarray(moments, np.float32)
+        if m.ndim != 3 or m.shape[2] != 4 or m.shape[0] == 0 or m.shape[1] == 0:
+            raise ValueError("temporal_variance_kat: needs moments (h, w, 4), got %r" % (m.shape,))
+        ln, vs = np.ascontiguousarray(length, np.float32), np.ascontiguousarray(spatial_var, np.float32)
+        if ln.shape != m.shape[:2] or vs.shape != m.shape[:2]:
+            raise ValueError("temporal_variance_kat: needs length and spatial_var %r, got %r and %r" % (m.shape[:2], ln.shape, vs.shape))
+        out, n = np.zeros(m.shape[:2], np.float32), C.c_uint64()
+        self._ck(B.lib().srt_temporal_variance_kat(self._h, B.fptr(m), B.fptr(ln), B.fptr(vs), v.min_len, m.shape[1], m.shape[0], B.fptr(out), C.byref(n)))
+        return out, n.value
+
+    def temporal_moments(self, image_width=None, image_height=None):
+        """the context's current moments history (srt_read_temporal_moments): (image_height, image_width, 4) float32 = (m1, m2, mlen, 0),
+        written in the history's rectangle only; without arguments the image of this renderer's last denoise_temporal_vg /
+        present_temporal_vg.  SrtError when the context holds none (no moments call since the history began, or a moment-less
+        temporal call since)."""
+        if image_width is None or image_height is None:
+            if getattr(self, "_moments_image", None) is None:
+                raise ValueError("temporal_moments: no image size given and no denoise_temporal_vg / present_temporal_vg call to take it from")
+            image_width, image_height = self._moments_image
+        out = np.zeros((image_height, image_width, 4), np.float32)
+        self._ck(B.lib().srt_read_temporal_moments(self._h, B.fptr(out), image_width, image_height))
+        return out
+
+    def temporal_variance_last_ms(self):
+        """kernel-only ms of the context's last choice kernel (srt_temporal_variance_last_ms)"""
+        ms = C.c_float()
+        self._ck(B.lib().srt_temporal_variance_last_ms(self._h, C.byref(ms)))
+        return ms.value
+
     def accum_reset_features(self):
         """start a FEATURED accumulation (srt_c_api.h): like accum_reset, and each later pass also adds, at the first hit of every
         sample's camera ray, the face-forwarded normal, the hit material's colour, the distance and 1 to the pixel's eight raw float32
@@ -1719,6 +1829,21 @@ def _temporal_cfg(who, temporal):
     return temporal_config(**kw)
 
 
+MAX_TEMPORAL_MIN_LEN = 2 ** 24
+
+
+def temporal_vg_config(min_len=4, moving=False):
+    """srt_temporal_vg from Python values, checked as the library checks it (ValueError): min_len a whole number in [2, 2^24] -- the
+    moments' own history length from which a pixel's filter is guided by the variance measured across frames instead of the spatial
+    estimate (above the stage's max_len: never); moving a bool -- the moving stage, which needs tracking on.  min_len = 4 is a starting
+    value, untuned."""
+    if isinstance(min_len, bool) or not isinstance(min_len, (int, np.integer)) or not 2 <= min_len <= MAX_TEMPORAL_MIN_LEN:
+        raise ValueError("temporal_vg: min_len must be a whole number in [2, 2^24], got %r" % (min_len,))
+    if not isinstance(moving, (bool, np.bool_)):
+        raise ValueError("temporal_vg: moving must be a bool, got %r" % (moving,))
+    return B.TemporalVG(int(min_len), 1 if moving else 0, (C.c_uint32 * 2)(0, 0))
+
+
 def temporal_stats(res):
     """srt_temporal_result as a dict: the pixels blended, fresh (of those: offscreen, rejected) and nonfinite, history_frames (the calls
     since the history began, this one included) and history_dropped (this call discarded a history of another rectangle)"""
@@ -1747,15 +1872,34 @@ def _motion_rect(who, w, h, ox, oy):
     return w, h, ox, oy
 
 
+def _variance_guided_cfg(who, variance_guided, denoise, cfg):
+    """render_interactive's / render_animated's variance_guided=True: cfg holds min_len and the keywords of denoise_vg_config; both are
+    checked here.  (min_len, the rest of cfg)"""
+    if not isinstance(variance_guided, (bool, np.bool_)):
+        raise TypeError("%s: variance_guided must be a bool, got %r" % (who, variance_guided))
+    if not variance_guided:
+        return None, cfg
+    if not denoise:
+        raise ValueError("%s: variance_guided=True with denoise=False: the variance guides the denoiser" % who)
+    rest = dict(cfg)
+    min_len = rest.pop("min_len", 4)
+    temporal_vg_config(min_len)
+    denoise_vg_config(**rest)
+    return min_len, rest
+
+
 def render_interactive(scene, cameras, width, height, spp, bounce_limit, denoise=True, despeckle=None, temporal=None, seed=1984, device=0, renderer=None,
-                       **cfg):
+                       variance_guided=False, **cfg):
     """A moving camera on one GPU: for every camera of `cameras` (CameraData, at least one) set_camera, accum_reset_features, one pass of
     `spp` samples, then the chained call that carries the picture over from the previous camera -- denoise=True:
     Renderer.denoise_temporal(width, height, temporal, despeckle, **cfg) (cfg: the keywords of denoise_config), else
     Renderer.temporal(width, height, **temporal) (no cfg, no despeckle).  A generator of (index, result, features, picture, stats):
     `result` with the keys of render_image, `features` the raw sums of read_features, `picture` the chained call's dict, `stats` its
     temporal_stats.  The history starts with the first camera (temporal_reset).  Everything is checked here, before any device is
-    touched."""
+    touched.
+    variance_guided=True (with denoise=True) uses Renderer.denoise_temporal_vg in the chained call's place: cfg then holds min_len and the
+    keywords of denoise_vg_config, and `picture` gains var and n_temporal."""
+    min_len, cfg = _variance_guided_cfg("render_interactive", variance_guided, denoise, cfg)
     cams = list(cameras)
     if not cams:
         raise ValueError("render_interactive: no camera (give at least one)")
@@ -1772,6 +1916,8 @@ def render_interactive(scene, cameras, width, height, spp, bounce_limit, denoise
         if unknown:
             raise TypeError("render_interactive: unknown despeckle keyword(s) %s (%s)" % (", ".join(unknown), ", ".join(_DESPECKLE_KEYS)))
         despeckle_config(**dkw)
+    if min_len is not None:
+        return _interactive_frames_vg(scene, cams, width, height, sched[0], bounce_limit, seed, device, renderer, dkw, tkw, min_len, cfg)
     if denoise:
         denoise_config(**cfg)
     elif cfg:
@@ -1793,8 +1939,20 @@ def _interactive_frames(scene, cams, width, height, spp, bounce_limit, seed, dev
             yield k, _collect(r, width, height), r.read_features(width, height), picture, picture["stats"]
 
 
+def _interactive_frames_vg(scene, cams, width, height, spp, bounce_limit, seed, device, renderer, despeckle, temporal, min_len, cfg):
+    with _image_session(scene, cams[0], width, height, spp, bounce_limit, seed, device, renderer) as r:
+        r.temporal_reset()
+        for k, cam in enumerate(cams):
+            r.set_camera(cam)
+            r.accum_reset_features()
+            r.render_chunk_accum(width, height, spp)
+            r.scatter_tiles()
+            picture = r.denoise_temporal_vg(width, height, temporal, despeckle, min_len, False, **cfg)
+            yield k, _collect(r, width, height), r.read_features(width, height), picture, picture["stats"]
+
+
 def render_animated(scene, cam, frames, width, height, spp, bounce_limit, denoise=True, despeckle=None, temporal=None, seed=1984, device=0,
-                    renderer=None, track_motion=False, **cfg):
+                    renderer=None, track_motion=False, variance_guided=False, **cfg):
     """Moving geometry on one GPU: the scene is uploaded once; for every vertex array of `frames` ((n_tris, 3, 3) float32: numpy, or a
     torch tensor on the device -- Renderer.refit) refit, accum_reset_features, one pass of `spp` samples, then the chained presentation
     call of render_interactive (denoise, despeckle, temporal and cfg are its arguments).  The temporal history is dropped at every refit --
@@ -1802,9 +1960,12 @@ def render_animated(scene, cam, frames, width, height, spp, bounce_limit, denois
     (index, result, features, picture, stats), as render_interactive's.  The scene object itself is not changed.  Everything that can be
     checked without a device is checked here.
     track_motion=True switches motion tracking on before the upload (Renderer.track_motion; switched back off at the end) and uses the
-    *_moving chained call: the history survives the refits, every pixel reprojected along the motion of the triangle it sees."""
+    *_moving chained call: the history survives the refits, every pixel reprojected along the motion of the triangle it sees.
+    variance_guided=True (with denoise=True) uses Renderer.denoise_temporal_vg in the chained call's place, as render_interactive does;
+    track_motion=True then selects its moving stage."""
     if not isinstance(track_motion, (bool, np.bool_)):
         raise TypeError("render_animated: track_motion must be a bool, got %r" % (track_motion,))
+    min_len, cfg = _variance_guided_cfg("render_animated", variance_guided, denoise, cfg)
     if not isinstance(cam, B.CameraData):
         raise TypeError("render_animated: cam is no CameraData (camera_init makes one), got %r" % type(cam).__name__)
     frames = list(frames)
@@ -1823,18 +1984,21 @@ def render_animated(scene, cam, frames, width, height, spp, bounce_limit, denois
         if unknown:
             raise TypeError("render_animated: unknown despeckle keyword(s) %s (%s)" % (", ".join(unknown), ", ".join(_DESPECKLE_KEYS)))
         despeckle_config(**dkw)
-    if denoise:
+    vg = None if min_len is None else dict(cfg, min_len=min_len)      # (checked above)
+    if vg is not None:
+        pass
+    elif denoise:
         denoise_config(**cfg)
     elif cfg:
         raise TypeError("render_animated: %s given with denoise=False, which runs no denoiser" % ", ".join(sorted(cfg)))
     elif dkw is not None:
         raise ValueError("render_animated: despeckle given with denoise=False: the firefly filter runs in the denoiser's chain")
     if track_motion:
-        return _animated_frames_tracked(scene, cam, frames, width, height, sched[0], bounce_limit, seed, device, renderer, bool(denoise), dkw, tkw, cfg)
-    return _animated_frames(scene, cam, frames, width, height, sched[0], bounce_limit, seed, device, renderer, bool(denoise), dkw, tkw, cfg)
+        return _animated_frames_tracked(scene, cam, frames, width, height, sched[0], bounce_limit, seed, device, renderer, bool(denoise), dkw, tkw, cfg, vg)
+    return _animated_frames(scene, cam, frames, width, height, sched[0], bounce_limit, seed, device, renderer, bool(denoise), dkw, tkw, cfg, vg)
 
 
-def _animated_frames_tracked(scene, cam, frames, width, height, spp, bounce_limit, seed, device, renderer, denoise, despeckle, temporal, cfg):
+def _animated_frames_tracked(scene, cam, frames, width, height, spp, bounce_limit, seed, device, renderer, denoise, despeckle, temporal, cfg, vg=None):
     r = renderer or Renderer(device)
     try:
         r.track_motion(True)      # (before the upload: the upload is what makes the vertices known)
@@ -1844,8 +2008,11 @@ def _animated_frames_tracked(scene, cam, frames, width, height, spp, bounce_limi
                 r.accum_reset_features()
                 r.render_chunk_accum(width, height, spp)
                 r.scatter_tiles()
-                picture = (r.denoise_temporal_moving(width, height, temporal, despeckle, **cfg) if denoise
-                           else r.temporal_moving(width, height, **temporal))
+                if vg is not None:
+                    picture = r.denoise_temporal_vg(width, height, temporal, despeckle, moving=True, **vg)
+                else:
+                    picture = (r.denoise_temporal_moving(width, height, temporal, despeckle, **cfg) if denoise
+                               else r.temporal_moving(width, height, **temporal))
                 yield k, _collect(r, width, height), r.read_features(width, height), picture, picture["stats"]
     finally:
         if r._h:
@@ -1854,14 +2021,17 @@ def _animated_frames_tracked(scene, cam, frames, width, height, spp, bounce_limi
             r.close()
 
 
-def _animated_frames(scene, cam, frames, width, height, spp, bounce_limit, seed, device, renderer, denoise, despeckle, temporal, cfg):
+def _animated_frames(scene, cam, frames, width, height, spp, bounce_limit, seed, device, renderer, denoise, despeckle, temporal, cfg, vg=None):
     with _image_session(scene, cam, width, height, spp, bounce_limit, seed, device, renderer) as r:
         for k, v in enumerate(frames):
             r.refit(v)      # (invalidates the accumulation and drops the temporal history, as an upload does)
             r.accum_reset_features()
             r.render_chunk_accum(width, height, spp)
             r.scatter_tiles()
-            picture = r.denoise_temporal(width, height, temporal, despeckle, **cfg) if denoise else r.temporal(width, height, **temporal)
+            if vg is not None:
+                picture = r.denoise_temporal_vg(width, height, temporal, despeckle, **vg)
+            else:
+                picture = r.denoise_temporal(width, height, temporal, despeckle, **cfg) if denoise else r.temporal(width, height, **temporal)
             yield k, _collect(r, width, height), r.read_features(width, height), picture, picture["stats"]
 
 

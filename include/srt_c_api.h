@@ -1127,6 +1127,83 @@ SRT_API int srt_present_temporal_moving(srt_ctx *ctx, const srt_present_cfg *pre
                                         uint32_t image_height, srt_present_result *result, srt_temporal_result *temporal_result,
                                         srt_motion_result *motion_result);
 
+/* Variance measured across frames (no reference counterpart; kernels in csrc/srt_temporal.hip): the two halves of the SVGF-style filter
+ * joined.  The temporal stage above carries colour and length; the variance-guided filter has only a spatial guess of the noise, a 7x7
+ * window of one frame.  Here the stage also carries the first and second LUMINANCE MOMENTS through the same reprojection (Schied et al.
+ * 2017, section 4.2), and the a-trous levels are guided by the variance those moments measure wherever the history is long enough, by the
+ * spatial estimate elsewhere: a pixel with a long history is filtered gently, a disoccluded one hard.  Opt-in: every call above keeps
+ * its results, its history bytes and its refusals.
+ * The moments history Hm: a second, optional, double-buffered image of the history's rectangle, one float4 per pixel, (m1, m2, mlen, 0) --
+ * 32 bytes per pixel more, allocated by the first call that asks for it.  mlen is the moments' own length: it lets a colour history that
+ * moment-less calls advanced be joined later.
+ * The moments ride on the stage of srt_temporal_accum (the moving variant: of srt_temporal_moving_kat) exactly: taps, acceptance tests,
+ * weights wt, classes, alpha_min and max_len are unchanged, and the colour, the length, the guides, the motion vectors and the counters
+ * are that stage's, bit for bit.  Everything fp32, not contracted, left to right, compares and selects only; the restatement is
+ * tests/temporal_vg_reference.py.  Y = c_p.y and Q = Y * Y, c_p the stage's input picture (in the chained call: behind the firefly clamp).
+ *     Step 5, for every tap the colour takes (accepted, wt > 0), when a moments history exists:
+ *          s1 += wt * Hm_q.x;  s2 += wt * Hm_q.y;  sm += wt * Hm_q.z.
+ *     Step 6:
+ *          nonfinite:  Hm' = (0, 0, 0, 0).
+ *          fresh, or blended with no moments history:  Hm' = (Y, Q, 1, 0).
+ *          blended with a moments history:  g1 = s1 / sw;  g2 = s2 / sw;  lm = sm / sw;  ml = lm + 1.0f;  ml = ml < max_len ? ml : max_len;
+ *                     b = 1.0f / ml;  b = b > alpha_min ? b : alpha_min;
+ *                     b >= 1 ? (m1', m2') = (Y, Q) : (m1', m2') = (g1 + b * (Y - g1), g2 + b * (Q - g2));   Hm' = (m1', m2', ml, 0).
+ *   Rules of the moments history: any of the moment-less temporal calls above advances Hc / Hg as always and marks Hm ABSENT; the next
+ *   moments call then seeds Hm' = (Y, Q, 1, 0) at every finite pixel, so the two families may alternate; whatever drops the colour
+ *   history (srt_temporal_reset, an upload, another rectangle, ...) drops the moments with it.
+ * The choice of the variance, a small elementwise kernel of its own.  Per pixel, from Hm' and len' of the stage, vs_p of the spatial
+ * estimator of srt_denoise_features_vg run on the stage's output o (and its guides), and ml_min = (float)min_len:
+ *          d = m2' - m1' * m1';  d = d > 0 ? d : 0;  vt = d / len';
+ *          use = (mlen' >= ml_min) && (len' > 0) && ((vt - vt) == 0);   v_p = use ? vt : vs_p.
+ *   d / len' is the variance of a mean of len' frames: exact while the blend weight is a = 1 / len', an approximation once alpha_min or
+ *   max_len holds a up -- the mean then forgets old frames and its variance stops falling; sigma_variance absorbs the constant.  v_p goes
+ *   where the estimator's result goes: the colour image's fourth word and out_var[..][0].  n_temporal, the number of pixels with `use`, is
+ *   an integer counter reduced per wave, then per workgroup, as the stage's counters are.
+ * typedef struct srt_temporal_vg { uint32_t min_len; uint32_t moving; uint32_t reserved[2]; }: valid when 2 <= min_len <= 2^24, moving is 0
+ *   or 1 and the reserved words are 0, else SRT_ERR_INVALID.  min_len > max_len: the variance is always the spatial one (n_temporal = 0).
+ *   moving = 1 needs what srt_denoise_features_temporal_moving needs and is refused as that call refuses.  min_len = 4 and
+ *   sigma_variance = 2 are starting values, untuned.
+ *   srt_denoise_features_temporal_vg  the chain: srt_denoise_features' prepass, the firefly filter when despeckle_cfg is not NULL, the
+ *                           moments stage (moving = 1: the surface-motion pass and the moving variant), the spatial estimator on o, the
+ *                           choice, the levels of srt_denoise_features_vg from (o, v), the epilogue.  out_xyz / out_lin / out_q as
+ *                           srt_denoise_features_vg's; out_var[h][w][2] is laid out as that call's: [0] the variance chosen, [1] the
+ *                           variance behind the last level.  *temporal_result the stage's counters, *n_temporal (uint64_t, may be NULL)
+ *                           the choice's, *motion_result (may be NULL) the motion pass's when moving.  The history stays the stage's
+ *                           output, not the filtered picture.  Refusals are the union of the chained calls' (srt_denoise_features_vg,
+ *                           srt_denoise_features_temporal(_moving), a bad srt_despeckle) plus a null or bad srt_temporal_vg; a refused call
+ *                           leaves both histories alone.  srt_temporal_result does not grow: that is why n_temporal is a parameter.
+ *   srt_present_temporal_vg srt_present_temporal with the chain above for the source SRT_PRESENT_DENOISE_VG (cfg->denoise_vg); every other
+ *                           source is SRT_ERR_UNSUPPORTED.
+ *   srt_temporal_moments_kat  srt_temporal_kat plus prev_point[h][w][4] (NULL: the static stage, else srt_temporal_moving_kat's),
+ *                           hist_moments[h][w][4] (NULL: no moments history; not read without a colour history) and out_moments[h][w][4],
+ *                           the new Hm.  It touches no context history.
+ *   srt_temporal_variance_kat  the choice kernel alone on host arrays: moments[h][w][4] = Hm', len[h][w] = len', spatial_var[h][w] = vs;
+ *                           out_var[h][w] = v and *n_temporal; either may be NULL, not both.  SRT_ERR_INVALID for a null input, an empty
+ *                           image, w x h >= 2^31, min_len outside 2 .. 2^24.
+ *   srt_read_temporal_moments  the context's current Hm as out[h][w][4], placed and clipped as srt_temporal_accum's outputs are.
+ *                           SRT_ERR_INVALID when Hm is absent.
+ *   srt_temporal_variance_last_ms  kernel-only time in ms of the context's last choice kernel; SRT_ERR_INVALID before one ran.
+ *                           srt_temporal_last_ms, srt_denoise_last_ms and srt_denoise_estimate_last_ms keep reporting their kernels
+ *                           after the new calls. */
+typedef struct srt_temporal_vg { uint32_t min_len; uint32_t moving; uint32_t reserved[2]; } srt_temporal_vg;
+SRT_API int srt_denoise_features_temporal_vg(srt_ctx *ctx, const srt_temporal *temporal_cfg, const srt_despeckle *despeckle_cfg,
+                                             const srt_denoise_vg *vg_cfg, const srt_temporal_vg *tv_cfg, float *out_xyz, float *out_lin,
+                                             float *out_q, float *out_var, srt_temporal_result *temporal_result, uint64_t *n_temporal,
+                                             srt_motion_result *motion_result, uint32_t image_width, uint32_t image_height);
+SRT_API int srt_present_temporal_vg(srt_ctx *ctx, const srt_present_cfg *present_cfg, const srt_temporal *temporal_cfg,
+                                    const srt_despeckle *despeckle_cfg, const srt_temporal_vg *tv_cfg, uint8_t *out_rgba8,
+                                    size_t pitch_bytes, uint32_t image_width, uint32_t image_height, srt_present_result *result,
+                                    srt_temporal_result *temporal_result, uint64_t *n_temporal, srt_motion_result *motion_result);
+SRT_API int srt_temporal_moments_kat(srt_ctx *ctx, const srt_temporal *cfg, const srt_camera_data *cur_cam, const srt_camera_data *prev_cam,
+                                     const float *xyz_mean, const float *guides, const float *hist_colour, const float *hist_guides,
+                                     uint32_t w, uint32_t h, uint32_t ox, uint32_t oy, float *out_colour, float *out_guides,
+                                     float *out_motion, srt_temporal_result *result, const float *prev_point, const float *hist_moments,
+                                     float *out_moments);
+SRT_API int srt_temporal_variance_kat(srt_ctx *ctx, const float *moments, const float *len, const float *spatial_var, uint32_t min_len,
+                                      uint32_t w, uint32_t h, float *out_var, uint64_t *n_temporal);
+SRT_API int srt_read_temporal_moments(srt_ctx *ctx, float *out, uint32_t image_width, uint32_t image_height);
+SRT_API int srt_temporal_variance_last_ms(srt_ctx *ctx, float *ms);
+
 /* Sample-parallel pixels (no reference counterpart; a deliberate departure from its one RNG stream per pixel, so opt-in).  A STREAMED
  * accumulation gives every pixel K independent RNG streams, each with its own state and its own XYZ sum, so that any lane of any wave
  * can render a stream while others render the pixel's other streams: the longest sequential chain of a pass is spp_add / K samples.
