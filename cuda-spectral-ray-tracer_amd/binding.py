@@ -88,6 +88,7 @@ class ToneResult(C.Structure):
 
 
 SCENE_IMAGES = {"nodes": 0, "nodes_sw": 1, "fringe": 2, "tris": 3, "shade": 4}      # SRT_IMAGE_* (srt_c_api.h)
+GATHER_PARTS = {"sums": 1, "counts": 2, "features": 4, "film": 8}      # SRT_GATHER_* (srt_c_api.h)
 PRESENT_SOURCES = {"accum": 0, "denoise": 1, "denoise_vg": 2, "denoise_mv": 3, "develop": 4}      # SRT_PRESENT_* (srt_c_api.h)
 
 
@@ -295,6 +296,12 @@ PROTOTYPES = {
     "srt_tile_buffer": (_i, [_vp, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_u32), C.POINTER(_u32)]),
     "srt_copy_tile_buffer": (_i, [_vp, _vp, _vp]),
     "srt_scatter_tiles": (_i, [_vp, _vp, _vp]),
+    "srt_accum_exchange_size": (_i, [_vp, _u32, C.POINTER(_sz)]),
+    "srt_pack_accum": (_i, [_vp, _u32, _vp, _vp]),
+    "srt_unpack_accum": (_i, [_vp, _u32, _vp, _vp]),
+    "srt_accum_gathered": (_i, [_vp, C.POINTER(_u32)]),
+    "srt_accum_whole": (_i, [_vp, _u32, C.POINTER(_i)]),
+    "srt_gather_last_ms": (_i, [_vp, _fp, _fp]),
     "srt_dev_fb": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz)]),
     "srt_read_fb": (_i, [_vp, _fp, _fp, _fp]),
     "srt_read_fb_rowmajor": (_i, [_vp, _fp, _fp, _fp, _u32, _u32]),
@@ -322,6 +329,8 @@ PROTOTYPES = {
     "srt_comm_available": (_i, []),
     "srt_comm_set_gather_planes": (_i, [_vp, _u32]),
     "srt_comm_last_gather_ms": (_i, [_vp, C.POINTER(_f)]),
+    "srt_comm_gather_accum": (_i, [_vp, _u32]),
+    "srt_comm_last_accum_gather_ms": (_i, [_vp, _fp, _fp, _fp]),
     "srt_comm_destroy": (None, [_vp]),
     "srt_comm_last_error": (C.c_char_p, [_vp]),
     "srt_comm_world": (_u32, [_vp]),

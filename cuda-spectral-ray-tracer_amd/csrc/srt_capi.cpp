@@ -147,8 +147,9 @@ struct srt_ctx {
         uint32_t total = 0;                             // samples per pixel in the sums (streamed: over all streams)
         uint32_t n_streams = 1;                         // streamed: the RNG streams per pixel (K); 1 otherwise
         uint32_t w = 0, h = 0, offx = 0, offy = 0;      // the chunk of the first pass
-        void invalidate() { state = State::Invalid; }
-        void begin(Kind k, uint32_t streams_per_pixel = 1) { kind = k; n_streams = streams_per_pixel; state = State::Empty; }      // (srt_accum_reset has zeroed the total)
+        uint32_t gathered = 0;                          // SRT_GATHER_*: what the last srt_unpack_accum since the last pass brought (whole_for)
+        void invalidate() { state = State::Invalid; gathered = 0; }
+        void begin(Kind k, uint32_t streams_per_pixel = 1) { kind = k; n_streams = streams_per_pixel; state = State::Empty; gathered = 0; }      // (srt_accum_reset has zeroed the total)
         bool valid() const { return state != State::Invalid; }
         bool bound() const { return state == State::Bound; }
         bool adaptive() const { return kind == Kind::Adaptive || kind == Kind::AdaptiveFeatures || kind == Kind::AdaptiveSpectral || kind == Kind::AdaptiveSpectralFeatures; }
@@ -187,6 +188,10 @@ struct srt_ctx {
     hipEvent_t present_ev[2] = {};                      // around the last present kernel (created on first use)
     bool present_timed = false;
     bool present_scalar = false;                        // test knob (env SRT_PRESENT_SCALAR under SRT_TEST_KNOBS=1): present_kernel's scalar path alone
+    DeviceBuffer d_gather_unit;                         // srt_comm_gather_accum: this context's packed exchange unit (srt_internal_pack_accum_own)
+    hipEvent_t gather_ev[4] = {};                       // around the last pack kernel [0, 1] and the last unpack kernel [2, 3] (created on first use)
+    bool pack_timed = false, unpack_timed = false;
+    bool gather_scalar = false;                         // test knob (env SRT_GATHER_SCALAR under SRT_TEST_KNOBS=1): gather_kernel's 4-byte paths alone
     DeviceBuffer d_despeckle;                           // the firefly filter: its counters and its four row-major images (DespeckleLayout)
     hipEvent_t despeckle_ev[2] = {};                    // around the last despeckle kernel (created on first use)
     bool despeckle_timed = false;
@@ -710,6 +715,7 @@ int srt_create(int device, srt_ctx **out) {
     if (const char *tk = getenv("SRT_TEST_KNOBS")) if (atoi(tk) == 1) {
         if (const char *ev = getenv("SRT_DEBUG_LANE_LIMIT")) { c->debug_lane_limit = (uint32_t)std::max(0, atoi(ev)); c->knobs_from_env = true; }
         if (const char *ev = getenv("SRT_PRESENT_SCALAR")) c->present_scalar = atoi(ev) != 0;      // (no render kernel depends on it: not a plan knob)
+        if (const char *ev = getenv("SRT_GATHER_SCALAR")) c->gather_scalar = atoi(ev) != 0;        // (likewise)
         if (const char *ev = getenv("SRT_WIDE_REFS")) { c->knobs.wide_refs = atoi(ev) != 0; c->knobs_from_env = true; }
         if (const char *ev = getenv("SRT_LDS_CACHE_MAX")) { c->knobs.lds_cache_max = std::max(0, atoi(ev)); c->knobs_from_env = true; }
     }
@@ -745,6 +751,7 @@ void srt_destroy(srt_ctx *c) {
     for (hipEvent_t e : c->develop_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->expose_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->present_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->gather_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->despeckle_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->temporal_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->temporal_var_ev) if (e) (void)hipEventDestroy(e);
@@ -1300,6 +1307,23 @@ static float *feature_rows(const srt_ctx *c) {
     return c->accum.kind == srt_ctx::Accumulation::Kind::AdaptiveSpectralFeatures ? c->d_film.as<float>() + (size_t)c->n_lanes * kFilmStride : c->d_features.as<float>();
 }
 
+// ---- a gathered accumulation (srt_gather.hip; srt_c_api.h at srt_pack_accum) ---------------------------------------------------------
+// the parts the accumulation's kind holds
+static uint32_t gather_parts_held(const srt_ctx *c) {
+    return SRT_GATHER_SUMS | (c->accum.adaptive() ? SRT_GATHER_COUNTS : 0u) | (c->accum.featured() ? SRT_GATHER_FEATURES : 0u) | (c->accum.spectral() ? SRT_GATHER_FILM : 0u);
+}
+// Is the context whole for a stage that reads the sums (and the counts of an adaptive accumulation), the rows when `features`, the film
+// when `film`?  Partition (0, 1), or the last unpack since the last pass brought all of that.
+static bool whole_for(const srt_ctx *c, bool features, bool film) {
+    if (c->rank == 0 && c->world == 1) return true;
+    const uint32_t need = (gather_parts_held(c) & (SRT_GATHER_SUMS | SRT_GATHER_COUNTS)) | (features ? SRT_GATHER_FEATURES : 0u) | (film ? SRT_GATHER_FILM : 0u);
+    return c->accum.bound() && (c->accum.gathered & need) == need;
+}
+static const char *const kNotWhole = "needs the whole chunk on this context (partition (0, 1)): pixels of other ranks read +0 (or srt_comm_gather_accum first)";
+// whose pixels the per-rank counters of the meter, tone and present kernels count: this rank's, or everybody's on a whole context
+static uint32_t counted_rank(const srt_ctx *c) { return whole_for(c, false, false) ? 0u : c->rank; }
+static uint32_t counted_world(const srt_ctx *c) { return whole_for(c, false, false) ? 1u : c->world; }
+
 int srt_accum_reset_adaptive(srt_ctx *c, const srt_adaptive *cfg) { return accum_reset_adaptive(c, cfg, false, false, "srt_accum_reset_adaptive"); }
 
 int srt_accum_reset_adaptive_features(srt_ctx *c, const srt_adaptive *cfg) { return accum_reset_adaptive(c, cfg, true, false, "srt_accum_reset_adaptive_features"); }
@@ -1352,6 +1376,7 @@ int srt_render_chunk_accum(srt_ctx *c, uint32_t width, uint32_t height, uint32_t
         return fail(c, SRT_ERR_INVALID, "srt_render_chunk_accum: the accumulation belongs to another chunk (one accumulation per context)");
     HIP_TRY(c, set_device(c, (hipStream_t)stream));
     hipStream_t st = (hipStream_t)stream;
+    c->accum.gathered = 0;      // (the pass moves this rank's records on: what an unpack brought of the others is stale from here)
     // (the header travels by value in the arguments of a one-lane kernel on the pass's stream: stream-ordered, no host buffer to keep alive)
     HIP_TRY(c, launch_accum_header(AccumLayout(c).header, AccumLayout(c).sums, c->accum.total + spp_add, st));
     const int rc = render_chunk_impl(c, width, height, offx, offy, spp_add, st);
@@ -1403,6 +1428,134 @@ int srt_scatter_tiles(srt_ctx *c, const void *dev_gathered, void *stream) {
     HIP_TRY(c, launch_scatter(sp, (hipStream_t)stream));
     c->fb_groups_valid = groups;      // with a 3-plane exchange unit the parity planes of d_fb are NOT those of this frame
     return SRT_OK;
+}
+
+// What a pack / unpack of `parts` needs of the context: the refusal (null: none) and, in *resolved, the parts that travel.  Host only.
+static const char *gather_refusal(const srt_ctx *c, uint32_t parts, uint32_t *resolved, int *code) {
+    *code = SRT_ERR_INVALID;
+    if (!c->accum.bound()) return "no accumulation with a pass (srt_accum_reset* and srt_render_chunk_accum first)";
+    if (c->count_traversal) { *code = SRT_ERR_UNSUPPORTED; return "not on an instrumented context (srt_set_count_traversal(ctx, 0) first)"; }
+    const uint32_t held = gather_parts_held(c);
+    if (parts & ~(SRT_GATHER_SUMS | SRT_GATHER_COUNTS | SRT_GATHER_FEATURES | SRT_GATHER_FILM)) return "unknown part (SRT_GATHER_SUMS .. SRT_GATHER_FILM)";
+    if (parts & ~held) return "the accumulation's kind does not hold that part (COUNTS: adaptive; FEATURES: featured; FILM: spectral)";
+    *resolved = parts ? (parts | SRT_GATHER_SUMS) : (held & ~SRT_GATHER_FILM);
+    return nullptr;
+}
+static GatherParams gather_params(const srt_ctx *c, uint32_t resolved, void *unit) {
+    GatherParams p = {};
+    p.unit = static_cast<uint32_t *>(unit);
+    p.sums = reinterpret_cast<uint32_t *>(AccumLayout(c).sums);
+    p.n_planes = 3;
+    if (resolved & SRT_GATHER_COUNTS) { p.state = AdaptPlanes(c).state; p.sum2 = reinterpret_cast<uint32_t *>(AdaptPlanes(c).sum2); p.n_planes = 5; }
+    if (resolved & SRT_GATHER_FEATURES) p.features = reinterpret_cast<uint32_t *>(feature_rows(c));
+    if (resolved & SRT_GATHER_FILM) p.film = c->d_film.as<uint32_t>();
+    p.tile_words = gather_tile_words(p.n_planes, p.features != nullptr, p.film != nullptr);
+    p.n_lanes = c->n_lanes;
+    p.width = c->accum.w; p.height = c->accum.h;      // (the bound chunk: the last pass's)
+    p.tx = c->tx; p.ty = c->ty; p.bx = c->bx; p.by = c->by;
+    p.tiles_x = c->tiles_x; p.n_tiles = c->n_tiles; p.rank = c->rank; p.world = c->world; p.tiles_padded = c->tiles_padded;
+    return p;
+}
+static size_t gather_unit_floats(const srt_ctx *c, uint32_t resolved) {
+    return (size_t)c->tiles_padded * gather_tile_words((resolved & SRT_GATHER_COUNTS) ? 5u : 3u, (resolved & SRT_GATHER_FEATURES) != 0, (resolved & SRT_GATHER_FILM) != 0);
+}
+
+int srt_accum_exchange_size(srt_ctx *c, uint32_t parts, size_t *n_floats) {
+    if (!c || !n_floats) return fail(c, SRT_ERR_INVALID, "srt_accum_exchange_size: null argument");
+    uint32_t resolved = 0; int code = 0;
+    if (const char *why = gather_refusal(c, parts, &resolved, &code)) return fail(c, code, std::string("srt_accum_exchange_size: ") + why);
+    *n_floats = gather_unit_floats(c, resolved);
+    return SRT_OK;
+}
+
+int srt_pack_accum(srt_ctx *c, uint32_t parts, void *dst_dev, void *stream) {
+    if (!c || !dst_dev) return fail(c, SRT_ERR_INVALID, "srt_pack_accum: null argument");
+    uint32_t resolved = 0; int code = 0;
+    if (const char *why = gather_refusal(c, parts, &resolved, &code)) return fail(c, code, std::string("srt_pack_accum: ") + why);
+    HIP_TRY(c, set_device(c, (hipStream_t)stream));
+    c->pack_timed = false;
+    for (int k = 0; k < 2; k++) if (!c->gather_ev[k]) HIP_TRY(c, hipEventCreate(&c->gather_ev[k]));
+    HIP_TRY(c, hipEventRecord(c->gather_ev[0], (hipStream_t)stream));
+    HIP_TRY(c, launch_gather(gather_params(c, resolved, dst_dev), false, !c->gather_scalar, (hipStream_t)stream));
+    HIP_TRY(c, hipEventRecord(c->gather_ev[1], (hipStream_t)stream));
+    c->pack_timed = true;
+    return SRT_OK;
+}
+
+int srt_internal_gather_reserve(srt_ctx *c, size_t n_floats) {
+    if (!c) return fail(c, SRT_ERR_INVALID, "srt_pack_accum: null argument");
+    if (n_floats * sizeof(float) > c->d_gather_unit.bytes) {      // (growing frees the old block: a transport may still be reading it)
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, device_synchronize(c));
+        HIP_TRY(c, c->d_gather_unit.reserve(std::max<size_t>(n_floats, 1) * sizeof(float)));
+    }
+    for (hipEvent_t &e : c->gather_ev) if (!e) { HIP_TRY(c, hipSetDevice(c->device)); HIP_TRY(c, hipEventCreate(&e)); }
+    return SRT_OK;
+}
+
+int srt_internal_pack_accum_own(srt_ctx *c, uint32_t parts, void *stream, void **unit_dev, size_t *n_floats) {
+    if (!c || !unit_dev || !n_floats) return fail(c, SRT_ERR_INVALID, "srt_pack_accum: null argument");
+    uint32_t resolved = 0; int code = 0;
+    if (const char *why = gather_refusal(c, parts, &resolved, &code)) return fail(c, code, std::string("srt_pack_accum: ") + why);
+    const size_t n = gather_unit_floats(c, resolved);
+    if (const int rc = srt_internal_gather_reserve(c, n)) return rc;
+    *unit_dev = c->d_gather_unit.ptr; *n_floats = n;
+    return srt_pack_accum(c, parts, c->d_gather_unit.ptr, stream);
+}
+
+int srt_unpack_accum(srt_ctx *c, uint32_t parts, const void *dev_gathered, void *stream) {
+    if (!c || !dev_gathered) return fail(c, SRT_ERR_INVALID, "srt_unpack_accum: null argument");
+    uint32_t resolved = 0; int code = 0;
+    if (const char *why = gather_refusal(c, parts, &resolved, &code)) return fail(c, code, std::string("srt_unpack_accum: ") + why);
+    if (c->world > 1) {
+        HIP_TRY(c, set_device(c, (hipStream_t)stream));
+        c->unpack_timed = false;
+        for (int k = 2; k < 4; k++) if (!c->gather_ev[k]) HIP_TRY(c, hipEventCreate(&c->gather_ev[k]));
+        HIP_TRY(c, hipEventRecord(c->gather_ev[2], (hipStream_t)stream));
+        HIP_TRY(c, launch_gather(gather_params(c, resolved, const_cast<void *>(dev_gathered)), true, !c->gather_scalar, (hipStream_t)stream));
+        HIP_TRY(c, hipEventRecord(c->gather_ev[3], (hipStream_t)stream));
+        c->unpack_timed = true;
+    }
+    c->accum.gathered = resolved;
+    return SRT_OK;
+}
+
+int srt_accum_gathered(const srt_ctx *c, uint32_t *parts) {
+    if (!c || !parts) return fail(nullptr, SRT_ERR_INVALID, "srt_accum_gathered: null argument");
+    *parts = c->accum.bound() ? c->accum.gathered : 0u;
+    return SRT_OK;
+}
+
+int srt_accum_whole(const srt_ctx *c, uint32_t parts, int *whole) {
+    if (!c || !whole) return fail(nullptr, SRT_ERR_INVALID, "srt_accum_whole: null argument");
+    if (parts & ~(SRT_GATHER_SUMS | SRT_GATHER_COUNTS | SRT_GATHER_FEATURES | SRT_GATHER_FILM)) return fail(nullptr, SRT_ERR_INVALID, "srt_accum_whole: unknown part (SRT_GATHER_SUMS .. SRT_GATHER_FILM)");
+    *whole = whole_for(c, (parts & SRT_GATHER_FEATURES) != 0, (parts & SRT_GATHER_FILM) != 0) ? 1 : 0;
+    return SRT_OK;
+}
+
+int srt_gather_last_ms(srt_ctx *c, float *pack_ms, float *unpack_ms) {
+    if (!c || (!pack_ms && !unpack_ms)) return fail(c, SRT_ERR_INVALID, "srt_gather_last_ms: null argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (pack_ms) {
+        *pack_ms = 0.f;
+        if (c->pack_timed) { HIP_TRY(c, hipEventSynchronize(c->gather_ev[1])); HIP_TRY(c, hipEventElapsedTime(pack_ms, c->gather_ev[0], c->gather_ev[1])); }
+    }
+    if (unpack_ms) {
+        *unpack_ms = 0.f;
+        if (c->unpack_timed) { HIP_TRY(c, hipEventSynchronize(c->gather_ev[3])); HIP_TRY(c, hipEventElapsedTime(unpack_ms, c->gather_ev[2], c->gather_ev[3])); }
+    }
+    return SRT_OK;
+}
+
+void srt_internal_gather_descriptor(const srt_ctx *c, uint32_t parts, uint32_t out[kGatherDescriptorWords]) {
+    uint32_t resolved = 0; int code = 0;
+    const bool ok = c && !gather_refusal(c, parts, &resolved, &code);
+    memset(out, 0, kGatherDescriptorWords * sizeof(uint32_t));
+    if (!c) return;
+    out[0] = ok ? 1u : 0u; out[1] = (uint32_t)c->accum.kind; out[2] = c->accum.total; out[3] = c->accum.n_streams;
+    out[4] = c->accum.w; out[5] = c->accum.h; out[6] = c->accum.offx; out[7] = c->accum.offy;
+    const uint64_t unit = ok ? (uint64_t)gather_unit_floats(c, resolved) : 0u;
+    out[8] = ok ? resolved : parts; out[9] = (uint32_t)unit; out[10] = (uint32_t)(unit >> 32);
 }
 
 int srt_dev_fb(srt_ctx *c, void **r, void **g, void **b, size_t *n_floats) {
@@ -1790,7 +1943,7 @@ int srt_meter_accum(srt_ctx *c, const srt_meter *cfg, uint32_t *hist, srt_meter_
     p.samples = c->accum.total; p.normalise = 1;
     p.n_lanes = c->n_lanes; p.tx = c->tx; p.ty = c->ty; p.bx = c->bx;
     p.x0 = rect[0]; p.y0 = rect[1]; p.w = rect[2]; p.h = rect[3];
-    p.tiles_x = c->tiles_x; p.rank = c->rank; p.world = c->world;
+    p.tiles_x = c->tiles_x; p.rank = counted_rank(c); p.world = counted_world(c);
     srt_meter_result res = *result;
     if (const int rc = run_meter(c, who, p, cfg, hist, &res)) return rc;
     *result = res;
@@ -1836,7 +1989,7 @@ int srt_expose_accum(srt_ctx *c, const srt_tone *tone, float *out_xyz, float *ou
         ToneParams p = {};
         p.sums = AccumLayout(c).sums; p.comp_stride = c->n_lanes; p.state = c->accum.adaptive() ? AdaptPlanes(c).state : nullptr;
         p.samples = c->accum.total; p.tx = c->tx; p.ty = c->ty; p.bx = c->bx; p.w = w; p.h = h;
-        p.tiles_x = c->tiles_x; p.rank = c->rank; p.world = c->world;
+        p.tiles_x = c->tiles_x; p.rank = counted_rank(c); p.world = counted_world(c);
         float *const host[3] = {out_xyz, out_lin, out_q};
         const bool want[3] = {out_xyz != nullptr, out_lin != nullptr, out_q != nullptr};
         if (const int rc = run_tone(c, who, p, tone, want)) return rc;
@@ -1963,8 +2116,8 @@ int srt_despeckle_accum(srt_ctx *c, const srt_despeckle *cfg, float *out_xyz, fl
         return fail(c, SRT_ERR_INVALID, "srt_despeckle_accum: no output / empty image");
     if (const char *why = despeckle_cfg_error(cfg)) return fail(c, SRT_ERR_INVALID, std::string("srt_despeckle_accum: ") + why);
     if (!c->accum.bound()) return fail(c, SRT_ERR_INVALID, "srt_despeckle_accum: no accumulation with a pass (srt_accum_reset* and srt_render_chunk_accum first)");
-    if (c->rank != 0 || c->world != 1)
-        return fail(c, SRT_ERR_UNSUPPORTED, "srt_despeckle_accum: needs the whole chunk on this context (partition (0, 1)): pixels of other ranks read +0");
+    if (!whole_for(c, false, false))
+        return fail(c, SRT_ERR_UNSUPPORTED, std::string("srt_despeckle_accum: ") + kNotWhole);
     HIP_TRY(c, set_device(c));
     // the kernel runs on the chunk's rectangle (clipped to the reference grid); the image clips only what is copied out
     const uint32_t w = clipped_w(c), h = clipped_h(c);
@@ -2667,8 +2820,8 @@ int denoise_accumulation_refusal(srt_ctx *c, const char *who, const DenoisePlan 
     if (plan.measured && (!c->accum.adaptive() || c->accum.total < 2))
         return fail(c, SRT_ERR_INVALID, w_ + ": needs an adaptive featured accumulation holding at least 2 samples (srt_accum_reset_adaptive_features; the "
                                              "measured variance of the mean needs S2 and two samples)");
-    if (c->rank != 0 || c->world != 1)
-        return fail(c, SRT_ERR_UNSUPPORTED, w_ + ": needs the whole chunk on this context (partition (0, 1)): pixels of other ranks read +0");
+    if (!whole_for(c, true, false))
+        return fail(c, SRT_ERR_UNSUPPORTED, w_ + ": " + kNotWhole);
     return SRT_OK;
 }
 
@@ -2988,8 +3141,8 @@ int srt_denoise_developed(srt_ctx *c, const srt_denoise *cfg, const float *respo
     if (!c->accum.spectral() || !c->accum.featured() || !c->accum.bound())
         return fail(c, SRT_ERR_INVALID, "srt_denoise_developed: no spectral featured accumulation with a pass (srt_accum_reset_spectral_features or "
                                         "srt_accum_reset_adaptive_spectral_features, and srt_render_chunk_accum first)");
-    if (c->rank != 0 || c->world != 1)
-        return fail(c, SRT_ERR_UNSUPPORTED, "srt_denoise_developed: needs the whole chunk on this context (partition (0, 1)): pixels of other ranks read +0");
+    if (!whole_for(c, true, true))
+        return fail(c, SRT_ERR_UNSUPPORTED, std::string("srt_denoise_developed: ") + kNotWhole);
     HIP_TRY(c, set_device(c));
     // develop and filter run on the chunk's rectangle (clipped to the reference grid); the image clips only what is copied out
     const uint32_t w = clipped_w(c), h = clipped_h(c);
@@ -3197,8 +3350,8 @@ int present_chain(srt_ctx *c, const char *who, const srt_present_cfg *cfg, const
     if (!c->accum.bound()) return fail(c, SRT_ERR_INVALID, w_ + "no accumulation with a pass (srt_accum_reset* and srt_render_chunk_accum first)");
     if (denoised || tcfg) if (const int rc = denoise_accumulation_refusal(c, who, plan)) return rc;      // (the stage needs the guides, whatever the source)
     if (moving) if (const char *why = motion_bound_refusal(c)) return fail(c, SRT_ERR_INVALID, w_ + why);
-    if (ds && (c->rank != 0 || c->world != 1))
-        return fail(c, SRT_ERR_UNSUPPORTED, w_ + "needs the whole chunk on this context (partition (0, 1)): pixels of other ranks read +0");
+    if (ds && !whole_for(c, false, false))
+        return fail(c, SRT_ERR_UNSUPPORTED, w_ + kNotWhole);
     if (developed && !c->accum.spectral()) return fail(c, SRT_ERR_INVALID, w_ + "SRT_PRESENT_DEVELOP needs a spectral accumulation (srt_accum_reset_spectral*)");
     uint32_t rect[4] = {0, 0, 0, 0};
     if (cfg->metered) if (const char *why = meter_rect_error(&cfg->meter, clipped_w(c), clipped_h(c), rect)) return fail(c, SRT_ERR_INVALID, w_ + why);
@@ -3251,7 +3404,7 @@ int present_chain(srt_ctx *c, const char *who, const srt_present_cfg *cfg, const
                 m.n_lanes = c->n_lanes; m.tx = c->tx; m.ty = c->ty; m.bx = c->bx;
             }
             m.x0 = rect[0]; m.y0 = rect[1]; m.w = rect[2]; m.h = rect[3];
-            m.tiles_x = c->tiles_x; m.rank = c->rank; m.world = c->world;
+            m.tiles_x = c->tiles_x; m.rank = counted_rank(c); m.world = counted_world(c);
             if (const int rc = run_meter(c, who, m, &cfg->meter, nullptr, &res.meter)) return rc;
             gain = res.meter.gain;
         }
@@ -3259,7 +3412,7 @@ int present_chain(srt_ctx *c, const char *who, const srt_present_cfg *cfg, const
         if (picture) p.xyz = picture;
         else { p.sums = AccumLayout(c).sums; p.comp_stride = c->n_lanes; p.state = state; p.samples = c->accum.total; }
         p.tx = c->tx; p.ty = c->ty; p.bx = c->bx; p.w = w; p.h = h;
-        p.tiles_x = c->tiles_x; p.rank = c->rank; p.world = c->world;
+        p.tiles_x = c->tiles_x; p.rank = counted_rank(c); p.world = counted_world(c);
         const ChunkRect place = chunk_rect(c, image_width, image_height);
         uint8_t *first = out_rgba8 + (size_t)c->last_offy * pitch_bytes + (size_t)c->last_offx * 4;      // (not formed into an address when nothing is copied)
         if (const int rc = run_present(c, who, p, &cfg->tone, gain, place.w, place.h, place.w && place.h ? first : out_rgba8, pitch_bytes, &res.tone)) return rc;

@@ -114,6 +114,14 @@ struct srt_comm {
     uint32_t *d_agree = nullptr;       // world words on this rank's device
     std::vector<hipEvent_t> ev_g0, ev_g1;   // per local context: around the gather (+ scatter on rank 0) of the last frame
     bool gather_timed = false;
+    // srt_comm_gather_accum: the ranks' accumulation units on rank 0's device, rank-major -- a buffer of its own, not d_gathered, whose
+    // scatter may still be in flight on the root's stream; the descriptors the ranks agree on (process-per-GPU: world + 1 of them on
+    // this rank's device); per local context the events around pack [0, 1], exchange [1, 2] and unpack [2, 3]
+    float *d_accum_gathered = nullptr;
+    size_t accum_gathered_capacity = 0;
+    uint32_t *d_accum_agree = nullptr;
+    std::vector<hipEvent_t> ev_a[4];
+    bool accum_gather_timed = false;
     std::string err;
 };
 
@@ -233,7 +241,10 @@ void srt_comm_destroy(srt_comm *c) {
         if (i < c->ev_g0.size() && c->ev_g0[i]) (void)hipEventDestroy(c->ev_g0[i]);
         if (i < c->ev_g1.size() && c->ev_g1[i]) (void)hipEventDestroy(c->ev_g1[i]);
     }
+    for (auto &evs : c->ev_a) for (size_t i = 0; i < evs.size(); i++) if (evs[i]) { if (c->ctx[i]) (void)hipSetDevice(device_of(c->ctx[i])); (void)hipEventDestroy(evs[i]); }
     if (c->d_gathered && c->root_local >= 0) { (void)hipSetDevice(device_of(c->ctx[c->root_local])); (void)hipFree(c->d_gathered); }
+    if (c->d_accum_gathered && c->root_local >= 0) { (void)hipSetDevice(device_of(c->ctx[c->root_local])); (void)hipFree(c->d_accum_gathered); }
+    if (c->d_accum_agree && !c->ctx.empty() && c->ctx[0]) { (void)hipSetDevice(device_of(c->ctx[0])); (void)hipFree(c->d_accum_agree); }
     if (c->d_agree && !c->ctx.empty() && c->ctx[0]) { (void)hipSetDevice(device_of(c->ctx[0])); (void)hipFree(c->d_agree); }
     if (c->owns_ctx) for (srt_ctx *x : c->ctx) if (x) srt_destroy(x);
     delete c;
@@ -462,6 +473,132 @@ int srt_comm_last_gather_ms(srt_comm *c, float *ms) {
         COMM_HIP(c, hipEventSynchronize(c->ev_g1[i]));
         COMM_HIP(c, hipEventElapsedTime(&t, c->ev_g0[i], c->ev_g1[i]));
         *ms = t > *ms ? t : *ms;
+    }
+    return SRT_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// What srt_comm_gather_accum needs of local rank i for units of n_floats, made before the ranks agree: its events, the buffer it packs
+// into and, on rank 0, the buffer of all the units.
+int prepare_accum_gather(srt_comm *c, size_t i, size_t n_floats) {
+    COMM_HIP(c, hipSetDevice(device_of(c->ctx[i])));
+    for (auto &evs : c->ev_a) {
+        evs.resize(c->ctx.size(), nullptr);
+        if (!evs[i]) COMM_HIP(c, hipEventCreate(&evs[i]));
+    }
+    const int rc = srt_internal_gather_reserve(c->ctx[i], n_floats);
+    if (rc != SRT_OK) return cfail(c, rc, srt_last_error(c->ctx[i]));
+    if ((int)i == c->root_local && (size_t)c->world * n_floats > c->accum_gathered_capacity) {
+        COMM_HIP(c, hipStreamSynchronize(c->stream[i]));   // an unpack of the previous gather may still read it
+        if (c->d_accum_gathered) { (void)hipFree(c->d_accum_gathered); c->d_accum_gathered = nullptr; c->accum_gathered_capacity = 0; }
+        COMM_HIP(c, hipMalloc((void **)&c->d_accum_gathered, (size_t)c->world * n_floats * sizeof(float)));
+        c->accum_gathered_capacity = (size_t)c->world * n_floats;
+    }
+    return SRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// The ranks' accumulations on rank 0 (srt_c_api.h).  Agreement first, on the host and before anything is enqueued; then the packs, ONE
+// gather, the root's unpack, all stream-ordered behind the ranks' passes.
+int srt_comm_gather_accum(srt_comm *c, uint32_t parts) {
+    if (!c) return cfail(c, SRT_ERR_INVALID, "srt_comm_gather_accum: null comm");
+    RcclApi &R = rccl();
+    const size_t n_local = c->ctx.size();
+    const uint32_t D = (uint32_t)kGatherDescriptorWords;
+    // Every local rank's descriptor, and -- BEFORE the ranks agree -- everything of this call that can fail for want of memory: a rank that
+    // cannot allocate says so in word 0 of its descriptor, and the ranks fail together instead of leaving the others in the gather.
+    std::vector<uint32_t> all((size_t)c->world * D), mine(n_local * D);
+    int prep_rc = SRT_OK;
+    std::string prep_error;
+    for (size_t i = 0; i < n_local; i++) {
+        uint32_t *d = &mine[i * D];
+        srt_internal_gather_descriptor(c->ctx[i], parts, d);
+        if (!d[0] || c->world == 1) continue;
+        const int rc = prepare_accum_gather(c, i, (size_t)((uint64_t)d[9] | ((uint64_t)d[10] << 32)));
+        if (rc != SRT_OK) { d[0] = 0; prep_rc = rc; prep_error = c->err; }
+    }
+    if (c->owns_ctx || c->world == 1) {
+        for (size_t i = 0; i < n_local; i++) memcpy(&all[(size_t)c->rank[i] * D], &mine[i * D], D * sizeof(uint32_t));
+    } else {
+        // process-per-GPU: the same small collective on every rank, whatever its own context says (a rank that would refuse takes part
+        // and says so in its descriptor) -- as the plane-count agreement of srt_render_frame_multi
+        COMM_HIP(c, hipSetDevice(device_of(c->ctx[0])));
+        if (!c->d_accum_agree) COMM_HIP(c, hipMalloc((void **)&c->d_accum_agree, (size_t)(c->world + 1) * D * sizeof(uint32_t)));
+        uint32_t *d_mine = c->d_accum_agree + (size_t)c->world * D;
+        COMM_HIP(c, hipMemcpyAsync(d_mine, mine.data(), D * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream[0]));
+        COMM_NCCL(c, R.AllGather(d_mine, c->d_accum_agree, D, ncclUint32, c->nccl[0], c->stream[0]));
+        COMM_HIP(c, hipMemcpyAsync(all.data(), c->d_accum_agree, all.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream[0]));
+        COMM_HIP(c, hipStreamSynchronize(c->stream[0]));
+    }
+    static const char *const field[kGatherDescriptorWords] = {"whether it holds an accumulation that can be gathered (and could allocate its buffers)", "the accumulation's kind",
+                                                              "the sample total", "the streams", "the chunk's width", "the chunk's height", "the chunk's x offset",
+                                                              "the chunk's y offset", "the parts", "the size of the exchange unit", "the size of the exchange unit", "a reserved word"};
+    for (uint32_t r = 1; r < c->world; r++)
+        for (uint32_t k = 0; k < D; k++)
+            if (all[(size_t)r * D + k] != all[k])
+                return cfail(c, SRT_ERR_INVALID, std::string("srt_comm_gather_accum: the ranks disagree on the accumulation to gather: rank ") + std::to_string(r) +
+                                                     " differs from rank 0 in " + field[k] + " (" + std::to_string(all[(size_t)r * D + k]) + " against " + std::to_string(all[k]) +
+                                                     "); nothing was enqueued");
+    if (!all[0]) {      // every rank refuses alike: its failed allocation, or the context's own words
+        if (prep_rc != SRT_OK) return cfail(c, prep_rc, "srt_comm_gather_accum: " + prep_error);
+        size_t n = 0;
+        const int rc = srt_accum_exchange_size(c->ctx[0], parts, &n);
+        return cfail(c, rc != SRT_OK ? rc : SRT_ERR_INVALID, std::string("srt_comm_gather_accum: ") + srt_last_error(c->ctx[0]));
+    }
+    if (c->world == 1) return SRT_OK;
+    const size_t n_floats = (size_t)((uint64_t)all[9] | ((uint64_t)all[10] << 32));
+    c->accum_gather_timed = false;
+    std::vector<void *> unit(n_local, nullptr);
+    for (size_t i = 0; i < n_local; i++) {
+        size_t nf = 0;
+        COMM_HIP(c, hipSetDevice(device_of(c->ctx[i])));
+        COMM_HIP(c, hipEventRecord(c->ev_a[0][i], c->stream[i]));
+        const int rc = srt_internal_pack_accum_own(c->ctx[i], parts, c->stream[i], &unit[i], &nf);
+        if (rc != SRT_OK) return cfail(c, rc, srt_last_error(c->ctx[i]));
+        if (nf != n_floats) return cfail(c, SRT_ERR_INVALID, "srt_comm_gather_accum: exchange units of the ranks differ in size");
+        COMM_HIP(c, hipEventRecord(c->ev_a[1][i], c->stream[i]));
+    }
+    COMM_NCCL(c, R.GroupStart());
+    for (size_t i = 0; i < n_local; i++) {
+        ncclResult_t r = R.Gather(unit[i], (int)i == c->root_local ? c->d_accum_gathered : nullptr, n_floats, ncclFloat, 0, c->nccl[i], c->stream[i]);
+        if (r != ncclSuccess) { (void)R.GroupEnd(); return cfail(c, SRT_ERR_HIP, std::string("ncclGather: ") + R.GetErrorString(r)); }
+    }
+    COMM_NCCL(c, R.GroupEnd());
+    for (size_t i = 0; i < n_local; i++) {
+        COMM_HIP(c, hipSetDevice(device_of(c->ctx[i])));
+        COMM_HIP(c, hipEventRecord(c->ev_a[2][i], c->stream[i]));
+    }
+    if (c->root_local >= 0) {
+        const int rc = srt_unpack_accum(c->ctx[c->root_local], parts, c->d_accum_gathered, c->stream[c->root_local]);
+        if (rc != SRT_OK) return cfail(c, rc, srt_last_error(c->ctx[c->root_local]));
+        COMM_HIP(c, hipEventRecord(c->ev_a[3][c->root_local], c->stream[c->root_local]));
+    }
+    c->accum_gather_timed = true;
+    return SRT_OK;
+}
+
+int srt_comm_last_accum_gather_ms(srt_comm *c, float *pack_ms, float *exchange_ms, float *unpack_ms) {
+    if (!c || !pack_ms || !exchange_ms || !unpack_ms) return cfail(c, SRT_ERR_INVALID, "srt_comm_last_accum_gather_ms: null argument");
+    *pack_ms = *exchange_ms = *unpack_ms = 0.f;
+    if (c->world == 1 || !c->accum_gather_timed) return SRT_OK;
+    for (size_t i = 0; i < c->ctx.size(); i++) {
+        float a = 0.f, b = 0.f;
+        COMM_HIP(c, hipSetDevice(device_of(c->ctx[i])));
+        COMM_HIP(c, hipEventSynchronize(c->ev_a[2][i]));
+        COMM_HIP(c, hipEventElapsedTime(&a, c->ev_a[0][i], c->ev_a[1][i]));
+        COMM_HIP(c, hipEventElapsedTime(&b, c->ev_a[1][i], c->ev_a[2][i]));
+        *pack_ms = a > *pack_ms ? a : *pack_ms;
+        *exchange_ms = b > *exchange_ms ? b : *exchange_ms;
+        if ((int)i == c->root_local) {
+            COMM_HIP(c, hipEventSynchronize(c->ev_a[3][i]));
+            COMM_HIP(c, hipEventElapsedTime(unpack_ms, c->ev_a[2][i], c->ev_a[3][i]));
+        }
     }
     return SRT_OK;
 }

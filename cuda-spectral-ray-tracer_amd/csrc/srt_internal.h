@@ -12,6 +12,18 @@ extern "C" int srt_internal_init_device_params(srt_ctx *c, uint32_t tx, uint32_t
 extern "C" int srt_internal_refit_vertices(srt_ctx *c, const float *verts, size_t n_tris, int scanned);
 extern "C" uint32_t srt_internal_gather_planes(const srt_ctx *c);      // planes of the context's exchange unit (3 or 9); not exported
 
+// srt_comm_gather_accum's view of a context (not exported).  The descriptor is what the ranks must agree on before anybody packs: [0] 1
+// when srt_pack_accum(ctx, parts) would be accepted, [1] the accumulation's kind, [2] its total, [3] its streams, [4] .. [7] w, h, offx, offy
+// of its chunk, [8] the parts resolved against the kind, [9] and [10] the low and the high word of the floats of its exchange unit, [11] 0.
+// It never fails: a context that would refuse says so in word 0 and the others see it.
+constexpr int kGatherDescriptorWords = 12;
+extern "C" void srt_internal_gather_descriptor(const srt_ctx *c, uint32_t parts, uint32_t out[kGatherDescriptorWords]);
+// the buffer srt_internal_pack_accum_own packs into, grown to n_floats: called BEFORE the ranks agree, so that a failed allocation is one
+// more thing a rank says in word 0 of its descriptor
+extern "C" int srt_internal_gather_reserve(srt_ctx *c, size_t n_floats);
+// srt_pack_accum into a buffer the context owns (grown as needed); *unit_dev / *n_floats: where the unit lies and its size
+extern "C" int srt_internal_pack_accum_own(srt_ctx *c, uint32_t parts, void *stream, void **unit_dev, size_t *n_floats);
+
 namespace srt {
 
 constexpr int kTilePlanes = 9;      // quantised rgb | unquantised sRGB | XYZ sums
@@ -502,6 +514,28 @@ struct RefitParams {
 hipError_t launch_refit_validate(const float *verts, size_t n_floats, uint32_t *count, hipStream_t st);
 hipError_t launch_refit_triangles(const RefitParams &p, hipStream_t st);
 hipError_t launch_refit_level(const RefitParams &p, uint32_t first, uint32_t count, hipStream_t st);
+// The exchange unit of an accumulation (srt_gather.hip; srt_pack_accum / srt_unpack_accum in srt_c_api.h).  Internal, not ABI.
+// The unit of rank r is tiles_padded tile records, the same size on every rank; record t is local tile t = global tile r + world * t, and
+// slot lt of a tile is pixel tile_slot_pixel(tile, lt, tiles_x).  A record is tile_words 32-bit words, in this order:
+//   plane words [word][slot], 64 each: the X, Y, Z sums; with n_planes == 5 (SRT_GATHER_COUNTS) then the state word and S2
+//   features != null (SRT_GATHER_FEATURES): the feature rows [slot][kFeatureStride]
+//   film != null (SRT_GATHER_FILM): the film rows [slot][kFilmStride], the unused word included
+// so tile_words = 64 * (3 + 2 a + 8 f + 96 s).  Every word travels as its bit pattern (a transport is told ncclFloat).  Slots outside the
+// chunk (queue_slot_in_chunk false) and tiles beyond the rank's tiles_local are +0 in a packed unit and ignored by the unpack.
+// pack: `unit` receives the unit of (rank, world).  unpack: `unit` is `world` units, rank-major; the records of every rank but `rank` are
+// written into the buffers, those of `rank` itself are not read.  vec is the launcher's (allow_vector = false: the 4-byte paths alone).
+struct GatherParams {
+    uint32_t *unit;
+    uint32_t *sums;            // AccumLayout::sums: three planes of n_lanes words
+    uint32_t *state, *sum2;    // AdaptPlanes (n_planes == 5), else null
+    uint32_t *features, *film; // feature_rows(c) / d_film, null where the part does not travel
+    uint32_t n_planes, tile_words, n_lanes;
+    uint32_t width, height, tx, ty, bx, by;
+    uint32_t tiles_x, n_tiles, rank, world, tiles_padded;
+    uint32_t vec;
+};
+uint32_t gather_tile_words(uint32_t n_planes, bool features, bool film);
+hipError_t launch_gather(const GatherParams &p, bool unpack, bool allow_vector, hipStream_t st);
 hipError_t launch_order_tiles(const uint32_t *cost, uint32_t *sorted, uint32_t *rows, uint32_t n, uint32_t n_waves,
                               uint32_t split_load_pct, uint32_t *queue_info, uint32_t order_max_pct, hipStream_t st);
 hipError_t launch_scatter(const ScatterParams &p, hipStream_t st);

@@ -911,6 +911,42 @@ class Renderer:
     def scatter_tiles(self, gathered_ptr=None, stream=None):
         self._ck(B.lib().srt_scatter_tiles(self._h, C.c_void_p(gathered_ptr or 0), C.c_void_p(stream or 0)))
 
+    def accum_exchange_size(self, parts=None):
+        """floats of this context's accumulation exchange unit for `parts` (gather_parts: names, a mask or None; srt_accum_exchange_size)"""
+        n = C.c_size_t()
+        self._ck(B.lib().srt_accum_exchange_size(self._h, gather_parts(parts), C.byref(n)))
+        return n.value
+
+    def pack_accum(self, dst_ptr, parts=None, hip_stream=None):
+        """this rank's own tile records out of the accumulation buffers into device memory at dst_ptr (accum_exchange_size floats);
+        asynchronous on the stream `hip_stream`, a handle as render_chunk_accum's `stream` (srt_pack_accum)"""
+        self._ck(B.lib().srt_pack_accum(self._h, gather_parts(parts), C.c_void_p(dst_ptr or 0), C.c_void_p(hip_stream or 0)))
+
+    def unpack_accum(self, gathered_ptr, parts=None, hip_stream=None):
+        """`world` units, rank-major, in device memory at gathered_ptr into this context's accumulation buffers, for every tile it does not
+        own: it then holds what a partition (0, 1) context would hold, until its next pass (srt_unpack_accum)"""
+        self._ck(B.lib().srt_unpack_accum(self._h, gather_parts(parts), C.c_void_p(gathered_ptr or 0), C.c_void_p(hip_stream or 0)))
+
+    def accum_gathered(self):
+        """the SRT_GATHER_* mask the last unpack_accum since the last pass brought (0: nothing)"""
+        m = C.c_uint32()
+        self._ck(B.lib().srt_accum_gathered(self._h, C.byref(m)))
+        return m.value
+
+    def accum_whole(self, parts=None):
+        """True when the context holds the whole chunk for a stage that reads `parts` (gather_parts; the sums, and the counts of an adaptive
+        accumulation, are implied): its partition is (0, 1), or the last unpack_accum since its last pass brought all of it
+        (srt_accum_whole)"""
+        w = C.c_int()
+        self._ck(B.lib().srt_accum_whole(self._h, gather_parts(parts), C.byref(w)))
+        return bool(w.value)
+
+    def gather_last_ms(self):
+        """(pack_ms, unpack_ms) of the context's last pack and unpack kernels, 0 where there was none"""
+        a, b = C.c_float(), C.c_float()
+        self._ck(B.lib().srt_gather_last_ms(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def dev_fb(self):
         r, g, b, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t()
         self._ck(B.lib().srt_dev_fb(self._h, C.byref(r), C.byref(g), C.byref(b), C.byref(n)))
@@ -1042,8 +1078,10 @@ class Comm:
     Comm.init_all(devices): one process drives several GPUs.  Comm.init_rank(renderer, id, rank, world): one process per
     GPU, `id` from Comm.unique_id() on rank 0."""
 
-    def __init__(self, handle, renderers, owns):
+    def __init__(self, handle, renderers, owns, ranks=None):
         self._h, self.renderers, self._owns = handle, renderers, owns
+        self.ranks = list(range(len(renderers))) if ranks is None else list(ranks)      # the global rank of every local renderer
+        self._offset = (0, 0)                                                            # image offset of the last frame's chunk
         self.world = B.lib().srt_comm_world(handle)
 
     @staticmethod
@@ -1070,7 +1108,7 @@ class Comm:
         buf = (C.c_ubyte * B.COMM_ID_BYTES).from_buffer_copy(comm_id)
         h = C.c_void_p()
         B.check_comm(B.lib().srt_comm_init_rank(renderer._h, buf, rank, world, C.byref(h)))
-        return cls(h, [renderer], False)
+        return cls(h, [renderer], False, [rank])
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1128,6 +1166,7 @@ class Comm:
 
     def render_frame(self, width, height, offx=0, offy=0):
         self._ck(B.lib().srt_render_frame_multi(self._h, width, height, offx, offy))
+        self._offset = (offx & 0xffff, offy & 0xffff)
 
     def accum_reset(self):
         """Renderer.accum_reset on every local rank"""
@@ -1145,69 +1184,92 @@ class Comm:
         return n.value
 
     def accum_reset_spectral(self):
-        """Renderer.accum_reset_spectral on every local rank"""
+        """Renderer.accum_reset_spectral on every local rank; the films stay with their ranks until gather_accum(("film", ...))"""
         self._ck(B.lib().srt_comm_accum_reset_spectral(self._h))
 
     def accum_reset_features(self):
         """Renderer.accum_reset_features on every local rank (any communicator: no decision crosses ranks); the rows stay with their
-        ranks (Renderer.read_features per context: each pixel is owned by one rank and reads +0 on the others)"""
+        ranks (Renderer.read_features per context: each pixel is owned by one rank and reads +0 on the others) until gather_accum
+        brings them to the root"""
         self._ck(B.lib().srt_comm_accum_reset_features(self._h))
 
     def accum_reset_adaptive_features(self, rel_tol, abs_tol=0.0, min_spp=16):
         """Renderer.accum_reset_adaptive_features on every local rank (not on a process-per-GPU communicator: SrtError); the rows stay
-        with their ranks, as for accum_reset_features"""
+        with their ranks until gather_accum, as for accum_reset_features"""
         self._ck(B.lib().srt_comm_accum_reset_adaptive_features(self._h, C.byref(adaptive_config(rel_tol, abs_tol, min_spp))))
 
     def accum_reset_spectral_features(self):
-        """Renderer.accum_reset_spectral_features on every local rank; film and rows stay with their ranks, as for accum_reset_spectral
-        and accum_reset_features"""
+        """Renderer.accum_reset_spectral_features on every local rank; film and rows stay with their ranks until gather_accum
+        (the film only when it is asked for), as for accum_reset_spectral and accum_reset_features"""
         self._ck(B.lib().srt_comm_accum_reset_spectral_features(self._h))
 
     def accum_reset_adaptive_spectral(self, rel_tol, abs_tol=0.0, min_spp=16):
-        """Renderer.accum_reset_adaptive_spectral on every local rank (single-process communicators only); the films stay with their ranks"""
+        """Renderer.accum_reset_adaptive_spectral on every local rank (single-process communicators only); the films stay with their ranks
+        until gather_accum(("film", ...))"""
         self._ck(B.lib().srt_comm_accum_reset_adaptive_spectral(self._h, C.byref(adaptive_config(rel_tol, abs_tol, min_spp))))
 
     def accum_reset_adaptive_spectral_features(self, rel_tol, abs_tol=0.0, min_spp=16):
         """Renderer.accum_reset_adaptive_spectral_features on every local rank (single-process communicators only); films and rows stay
-        with their ranks"""
+        with their ranks until gather_accum"""
         self._ck(B.lib().srt_comm_accum_reset_adaptive_spectral_features(self._h, C.byref(adaptive_config(rel_tol, abs_tol, min_spp))))
 
     def accum_reset_streams(self, k):
         """Renderer.accum_reset_streams on every local rank (any communicator: no decision crosses ranks)"""
         self._ck(B.lib().srt_comm_accum_reset_streams(self._h, int(k)))
 
-    def read_spectral(self, image_width, image_height, first=0, count=None):
-        """the film of the frame (Renderer.read_spectral): on a single-process communicator (init_all) the sum of the local ranks' films,
-        which is exact -- every pixel is owned by one rank and reads +0 on the others; on a process-per-GPU communicator (init_rank) THIS
-        rank's film only (its own pixels, +0 elsewhere): there is no gathered film"""
-        count = FILM_SAMPLES - first if count is None else count
+    def _own_pixels(self, k, image_width, image_height):
+        """(image_height, image_width) bool: the pixels of the last frame's chunk that lie in the 8 x 8 tiles local renderer k owns --
+        tile (j // 8) * tiles_x + i // 8 of chunk pixel (i, j), tiles numbered over the whole reference grid, belongs to rank tile % world"""
+        g = self.renderers[k].geom
+        tiles_x = (g["tx"] * g["bx"] + 7) // 8
+        i = np.arange(image_width, dtype=np.int64)[None, :] - self._offset[0]
+        j = np.arange(image_height, dtype=np.int64)[:, None] - self._offset[1]
+        return (i >= 0) & (j >= 0) & (((j // 8) * tiles_x + i // 8) % self.world == self.ranks[k])
+
+    def _sum_of_own_pixels(self, image_width, image_height, read):
+        """The frame's film or developed film from per-rank read-backs.  Where the root is local and whole for the film (after gather_accum,
+        until its next pass) it holds the frame: its read-back alone.  Otherwise every local rank contributes the pixels of its OWN tiles
+        and nothing else: a pixel of another rank reads +0 on a context that never gathered, and a STALE copy on a root that gathered
+        before its last pass -- neither may enter the sum."""
+        root = self.root
+        if root is not None and root.accum_whole("film"):
+            return read(root)
         out = None
-        for r in self.renderers:
-            f = r.read_spectral(image_width, image_height, first, count)
-            out = f if out is None else out + f
+        for k, r in enumerate(self.renderers):
+            part = read(r)
+            part = np.where(self._own_pixels(k, image_width, image_height)[..., None], part, np.zeros((), part.dtype))
+            out = part if out is None else out + part
         return out
+
+    def read_spectral(self, image_width, image_height, first=0, count=None):
+        """the film of the frame (Renderer.read_spectral): on a single-process communicator (init_all) the sum over the local ranks of the
+        film of each rank's OWN pixels, which is exact -- every pixel is owned by one rank; after gather_accum(("film", ...)), until the
+        next pass, the root's film alone, which then holds every pixel (a root that gathered the film before its last pass keeps stale
+        copies of the other ranks' pixels: they never enter the sum).  On a process-per-GPU communicator (init_rank) THIS rank's own
+        pixels, +0 elsewhere -- except on a root that is whole for the film, which returns the frame's."""
+        count = FILM_SAMPLES - first if count is None else count
+        return self._sum_of_own_pixels(image_width, image_height, lambda r: r.read_spectral(image_width, image_height, first, count))
 
     def develop_spectral(self, image_width, image_height, response, scale=1.0, filter=None):
-        """the developed film of the frame (Renderer.develop_spectral): on a single-process communicator (init_all) the sum of the local
-        ranks' results, which is exact -- every pixel is non-zero on one rank only; on a process-per-GPU communicator (init_rank) THIS
-        rank's part (its own pixels, zeros elsewhere), as read_spectral documents for the film"""
+        """the developed film of the frame (Renderer.develop_spectral), put together as read_spectral puts the film together: the sum of
+        every local rank's own pixels, or the root's result alone while the root is whole for the film; on a process-per-GPU
+        communicator (init_rank) THIS rank's own pixels, zeros elsewhere, unless it is such a root"""
         resp = sensor_response(response, filter)
-        out = None
-        for r in self.renderers:
-            d = r.develop_spectral(image_width, image_height, resp, scale)
-            out = d if out is None else out + d
-        return out
+        return self._sum_of_own_pixels(image_width, image_height, lambda r: r.develop_spectral(image_width, image_height, resp, scale))
 
     def meter(self, with_hist=False, **cfg):
-        """the frame metered over all ranks (Renderer.meter): the local ranks' histograms and counters are summed -- integers, so the
-        sum is the whole frame's histogram exactly -- and srt_meter_decide decides on the sum.  Single-process communicators (init_all)
-        only: on a process-per-GPU communicator the sum would need a reduction across processes (SrtError, SRT_ERR_UNSUPPORTED)."""
+        """the frame metered over all ranks (Renderer.meter): the local ranks' histograms and counters are summed -- integers, and each
+        rank meters the pixels of its own tiles only, so the sum is the whole frame's histogram exactly -- and srt_meter_decide decides
+        on the sum.  While the root is whole (after gather_accum, until its next pass) its meter counts every pixel of the frame: then the
+        root's metering alone is returned, and nothing is added to it.  Single-process communicators (init_all) only: on a
+        process-per-GPU communicator the sum would need a reduction across processes (SrtError, SRT_ERR_UNSUPPORTED)."""
         if not self._owns:
             raise B.SrtError(-5, "Comm.meter: a process-per-GPU communicator cannot sum the ranks' histograms; meter every rank and reduce them yourself")
         m = meter_config(**cfg)
+        whole = self.world > 1 and self.root.accum_whole()
         hist = np.zeros(METER_BINS, np.uint64)
         dark = nonfinite = 0
-        for r in self.renderers:
+        for r in ([self.root] if whole else self.renderers):
             part = r.meter(with_hist=True, **cfg)
             hist += part["hist"]
             dark += part["dark"]
@@ -1217,6 +1279,20 @@ class Comm:
     def render_frame_accum(self, width, height, spp_add, offx=0, offy=0):
         """render_frame with an accumulating pass of spp_add samples on every rank (Renderer.render_chunk_accum)"""
         self._ck(B.lib().srt_render_frame_multi_accum(self._h, width, height, offx, offy, spp_add))
+        self._offset = (offx & 0xffff, offy & 0xffff)      # (the library's 16-bit chunk arguments, Q17)
+
+    def gather_accum(self, parts=None):
+        """the ranks' accumulations gathered on rank 0 (srt_comm_gather_accum; parts: gather_parts' names, a mask or None): afterwards
+        the root runs every stage as a single context would -- until the next pass.  Asynchronous.  Returns Comm.root (None where rank
+        0 lives in another process)."""
+        self._ck(B.lib().srt_comm_gather_accum(self._h, gather_parts(parts)))
+        return self.root
+
+    def last_accum_gather_ms(self):
+        """(pack_ms, exchange_ms, unpack_ms) of the last gather_accum (srt_comm_last_accum_gather_ms)"""
+        a, b, c = C.c_float(), C.c_float(), C.c_float()
+        self._ck(B.lib().srt_comm_last_accum_gather_ms(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
 
     def synchronize(self):
         self._ck(B.lib().srt_comm_synchronize(self._h))
@@ -1225,6 +1301,32 @@ class Comm:
         rays, paths, ms = C.c_uint64(), C.c_uint64(), C.c_float()
         self._ck(B.lib().srt_comm_stats(self._h, C.byref(rays), C.byref(paths), C.byref(ms)))
         return dict(rays=rays.value, paths=paths.value, max_kernel_ms=ms.value)
+
+
+GATHER_PARTS = B.GATHER_PARTS      # name -> SRT_GATHER_* bit (srt_c_api.h, srt_pack_accum)
+
+
+def gather_parts(parts=None):
+    """The SRT_GATHER_* mask of `parts`: None or 0 (everything the accumulation's kind holds except the film), a mask of the known bits,
+    one name or an iterable of names out of GATHER_PARTS ("sums", "counts", "features", "film").  Anything else is refused here, before
+    a device is touched."""
+    known = sum(B.GATHER_PARTS.values())
+    if parts is None:
+        return 0
+    if isinstance(parts, (bool, np.bool_)):
+        raise TypeError("gather_parts: parts must be names, a mask or None, got %r" % (parts,))
+    if isinstance(parts, (int, np.integer)):
+        parts = int(parts)
+        if parts < 0 or parts & ~known:
+            raise ValueError("gather_parts: unknown bit(s) in mask %d (the parts are %s)" % (parts, ", ".join("%s = %d" % kv for kv in B.GATHER_PARTS.items())))
+        return int(parts)
+    names = [parts] if isinstance(parts, str) else list(parts)
+    mask = 0
+    for name in names:
+        if not isinstance(name, str) or name not in B.GATHER_PARTS:
+            raise ValueError("gather_parts: unknown part %r (the parts are %s)" % (name, ", ".join(B.GATHER_PARTS)))
+        mask |= B.GATHER_PARTS[name]
+    return mask
 
 
 def pixels_per_lane(renderer, width, height, world=1):
@@ -1949,6 +2051,75 @@ def _interactive_frames_vg(scene, cams, width, height, spp, bounce_limit, seed, 
             r.scatter_tiles()
             picture = r.denoise_temporal_vg(width, height, temporal, despeckle, min_len, False, **cfg)
             yield k, _collect(r, width, height), r.read_features(width, height), picture, picture["stats"]
+
+
+def render_interactive_multi(scene, cameras, width, height, spp, bounce_limit, devices=None, comm=None, denoise=True, despeckle=None, temporal=None,
+                             variance_guided=False, seed=1984, **cfg):
+    """render_interactive on several GPUs: for every camera Comm.set_camera, accum_reset_features, one render_frame_accum of `spp`
+    samples on every rank's own tiles, Comm.gather_accum, then render_interactive's chained call on the root, which holds the whole
+    accumulation.  `comm` (a single-process communicator, left open) or `devices` (Comm.init_all, closed at the end; None: device 0
+    alone).  Yields what render_interactive yields -- the same bits, whatever the number of ranks; `stats` of `result` are the root's
+    own with rays and paths summed over the ranks.  Everything is checked here, before any device is touched."""
+    who = "render_interactive_multi"
+    min_len, cfg = _variance_guided_cfg(who, variance_guided, denoise, cfg)
+    cams = list(cameras)
+    if not cams:
+        raise ValueError("%s: no camera (give at least one)" % who)
+    for k, cam in enumerate(cams):
+        if not isinstance(cam, B.CameraData):
+            raise TypeError("%s: cameras[%d] is no CameraData (camera_init makes one), got %r" % (who, k, type(cam).__name__))
+    if comm is not None and devices is not None:
+        raise ValueError("%s: give comm or devices, not both" % who)
+    if comm is not None and (not isinstance(comm, Comm) or not comm._owns):
+        raise TypeError("%s: comm must be a single-process Comm (Comm.init_all): the root runs the chain and collects the frame" % who)
+    spp = progressive_schedule([spp])[0]
+    tkw = dict(temporal or {})
+    _temporal_cfg(who, tkw)
+    dkw = None
+    if despeckle is not None:
+        dkw = dict(despeckle)
+        unknown = sorted(set(dkw) - set(_DESPECKLE_KEYS))
+        if unknown:
+            raise TypeError("%s: unknown despeckle keyword(s) %s (%s)" % (who, ", ".join(unknown), ", ".join(_DESPECKLE_KEYS)))
+        despeckle_config(**dkw)
+    if min_len is None:
+        if denoise:
+            denoise_config(**cfg)
+        elif cfg:
+            raise TypeError("%s: %s given with denoise=False, which runs no denoiser" % (who, ", ".join(sorted(cfg))))
+        elif dkw is not None:
+            raise ValueError("%s: despeckle given with denoise=False: the firefly filter runs in the denoiser's chain" % who)
+    return _interactive_frames_multi(scene, cams, width, height, spp, bounce_limit, seed, devices, comm, bool(denoise), dkw, tkw, min_len, cfg)
+
+
+def _interactive_frames_multi(scene, cams, width, height, spp, bounce_limit, seed, devices, comm, denoise, despeckle, temporal, min_len, cfg):
+    c = comm or Comm.init_all(list(devices) if devices is not None else [0])
+    planes_before = c.renderers[0].gather_planes
+    try:
+        c.upload_scene(scene)
+        c.set_camera(cams[0])
+        c.init_device_params(width, height, spp, bounce_limit, seed)
+        c.set_gather_planes(9)            # the parity planes are part of what the frames return (as _image_session)
+        root = c.root
+        root.temporal_reset()
+        for k, cam in enumerate(cams):
+            c.set_camera(cam)
+            c.accum_reset_features()
+            c.render_frame_accum(width, height, spp)
+            c.gather_accum()
+            if min_len is not None:
+                picture = root.denoise_temporal_vg(width, height, temporal, despeckle, min_len, False, **cfg)
+            else:
+                picture = root.denoise_temporal(width, height, temporal, despeckle, **cfg) if denoise else root.temporal(width, height, **temporal)
+            result = _collect(root, width, height)
+            total = c.stats()
+            result["stats"]["rays"], result["stats"]["paths"] = total["rays"], total["paths"]
+            yield k, result, root.read_features(width, height), picture, picture["stats"]
+    finally:
+        if comm is None:
+            c.close()
+        elif c._h:
+            c.set_gather_planes(planes_before)
 
 
 def render_animated(scene, cam, frames, width, height, spp, bounce_limit, denoise=True, despeckle=None, temporal=None, seed=1984, device=0,

@@ -303,7 +303,7 @@ SRT_API int srt_set_partition(srt_ctx *ctx, uint32_t rank, uint32_t world);
  *
  * Order of a context's calls.  A context's calls take effect in the order they were made, whichever streams they name.  A stream
  * handed to a call must stay valid until the next call on that context that synchronises.
- * The calls that take a stream are srt_render_chunk, srt_render_chunk_accum, srt_copy_tile_buffer and srt_scatter_tiles; every other
+ * The calls that take a stream are srt_render_chunk, srt_render_chunk_accum, srt_copy_tile_buffer, srt_scatter_tiles, srt_pack_accum and srt_unpack_accum; every other
  * call works on the NULL stream.  The context remembers the stream of the work it enqueued last: a call that enqueues on another
  * stream -- the NULL stream included, and a hipStreamNonBlocking stream as well as a blocking one -- first makes its stream wait for
  * an event recorded behind that work, so a pass on one stream may be followed at once by a pass on another, a reset, a stage or a
@@ -658,7 +658,7 @@ SRT_API int srt_accum_reset_adaptive_spectral_features(srt_ctx *ctx, const srt_a
  *                         with the chunk.  Refused, the accumulation unchanged: null ctx / cfg, all outputs NULL, no featured accumulation
  *                         with at least one pass, levels > 8, a sigma that is NaN or <= 0 (+inf is allowed and switches its term off),
  *                         non-zero reserved words (SRT_ERR_INVALID); a partition other than (0, 1) (SRT_ERR_UNSUPPORTED: the neighbours
- *                         other ranks own read +0 here; a gathered denoise is out of scope, and srt_comm has no entry point for it); a
+ *                         other ranks own read +0 here -- unless srt_unpack_accum / srt_comm_gather_accum has made the context whole); a
  *                         failed allocation (SRT_ERR_HIP).
  *   srt_denoise_kat       KAT entry point, like srt_order_tiles_kat: the same prepass, level and epilogue kernels on caller-supplied
  *                         row-major host arrays xyz_sums[h][w][3] and features[h][w][8] holding `samples` samples; out_xyz[h][w][3]
@@ -1256,6 +1256,56 @@ SRT_API int srt_copy_tile_buffer(srt_ctx *ctx, void *dst_dev, void *stream);
  * written.  With world == 1 pass NULL: the context's own tile buffer (its first `planes` planes) is scattered. */
 SRT_API int srt_scatter_tiles(srt_ctx *ctx, const void *dev_gathered, void *stream);
 
+/* Gathering an accumulation (no reference counterpart).  The tile buffer above carries the finished picture of a partition; the
+ * accumulation itself -- XYZ sums, sample map and S2, feature rows, film -- stays in the block-linear buffers of the context that
+ * rendered it, and a pixel another rank owns reads +0 there.  Every such buffer is indexed by the lane of the WHOLE grid on every rank,
+ * and a pass touches only its own tiles, so the records of the other ranks' tiles can be copied into a context's own buffers: it then
+ * holds exactly the accumulation a partition (0, 1) context would hold after the same passes, and every stage runs on it unchanged.
+ * These three calls mirror srt_tile_buffer / srt_copy_tile_buffer / srt_scatter_tiles for a caller with a transport of its own;
+ * srt_comm_gather_accum is the same over RCCL.
+ *   parts                   SRT_GATHER_*: what travels.  The sums always do (SRT_GATHER_SUMS is implied); COUNTS is the per-pixel state
+ *                           word (samples held | converged flag) and S2 of an adaptive accumulation, FEATURES the first-hit rows of a
+ *                           featured one, FILM the film of a spectral one (384 B per pixel: it moves only when it is asked for).
+ *                           parts == 0 stands for everything the accumulation's kind holds except the film.  A streamed accumulation
+ *                           holds -- and moves -- its combined sums only: the per-stream sums and RNG states stay where they are.
+ *   srt_accum_exchange_size *n_floats = the exchange unit for `parts`: tiles_padded * 64 * (3 + 2 a + 8 f + 96 s) floats, a, f, s = 1
+ *                           where COUNTS, FEATURES, FILM travel; the same on every rank of the partition.
+ *   srt_pack_accum          this rank's own tiles, out of the accumulation buffers into dst_dev (device memory, n_floats floats; 16-byte
+ *                           aligned memory takes the wide path).  Slots outside the chunk and tile records past the rank's last tile
+ *                           are +0: the unit is a function of the accumulation alone.  Words that are not floats travel as their bit
+ *                           patterns in float slots (hand a transport ncclFloat).
+ *   srt_unpack_accum        dev_gathered = `world` units, rank-major (what ncclGather leaves at its root), into this context's
+ *                           accumulation buffers, for every tile the context does not own.  Its own records are neither read nor
+ *                           written, and its RNG state is untouched: its next pass continues as if nothing had happened.  With
+ *                           world == 1 it succeeds and enqueues nothing.
+ *   srt_accum_gathered      *parts = what the last unpack since the last pass brought (0: nothing).
+ *   srt_accum_whole         *whole = 1 when the context is whole (below) for a stage that reads `parts` -- FEATURES and FILM as the
+ *                           stage needs them; the sums, and the counts of an adaptive accumulation, are implied -- else 0.
+ *   srt_gather_last_ms      the kernel times of the context's last pack and last unpack (0 where there was none).
+ * Pack and unpack are asynchronous on `hip_stream` (a hipStream_t passed as void*, NULL = default stream, as srt_render_chunk's `stream`)
+ * and belong to the calls that take a stream ("Order of a context's calls").
+ * A context is WHOLE for a stage when its partition is (0, 1), or when the last unpack since its last pass brought every part that
+ * stage reads (the sums; COUNTS for an adaptive accumulation; FEATURES for the denoisers and the temporal stage; FILM and FEATURES for
+ * srt_denoise_developed).  The stages that refuse a partition -- srt_despeckle_accum, srt_denoise_features*, srt_denoise_developed,
+ * srt_temporal_accum*, the chained srt_present_* calls -- run on a whole context, and the per-rank counters of srt_meter_accum,
+ * srt_expose_accum and srt_present* then count every pixel, as under partition (0, 1): results and counters equal that context's.
+ * The mark is cleared by every pass on the context, by every srt_accum_reset* and by everything that invalidates the accumulation.
+ * After a later pass the pixels of the other ranks are STALE until the next gather: the stages that need the whole chunk refuse again,
+ * and the stages that accept a partition see the stale records where they used to see +0.  Gather before you look.
+ * The temporal history belongs to the context and survives all of this, as it survives srt_set_camera.
+ * Refused with nothing changed: no accumulation with a pass, a part the kind does not hold, an unknown bit, a null pointer
+ * (SRT_ERR_INVALID); an instrumented context (SRT_ERR_UNSUPPORTED). */
+#define SRT_GATHER_SUMS 1u
+#define SRT_GATHER_COUNTS 2u
+#define SRT_GATHER_FEATURES 4u
+#define SRT_GATHER_FILM 8u
+SRT_API int srt_accum_exchange_size(srt_ctx *ctx, uint32_t parts, size_t *n_floats);
+SRT_API int srt_pack_accum(srt_ctx *ctx, uint32_t parts, void *dst_dev, void *hip_stream);
+SRT_API int srt_unpack_accum(srt_ctx *ctx, uint32_t parts, const void *dev_gathered, void *hip_stream);
+SRT_API int srt_accum_gathered(const srt_ctx *ctx, uint32_t *parts);
+SRT_API int srt_accum_whole(const srt_ctx *ctx, uint32_t parts, int *whole);
+SRT_API int srt_gather_last_ms(srt_ctx *ctx, float *pack_ms, float *unpack_ms);
+
 /* renderer::getDevFBr/g/b (rendering.cuh:87-97): device pointers to the block-linear planes (tx*bx*ty*by floats). */
 SRT_API int srt_dev_fb(srt_ctx *ctx, void **r, void **g, void **b, size_t *n_floats);
 /* The three cudaMemcpyAsync D2H of render_manager::step (render_manager.cu:41-45): block-linear, grid sized. */
@@ -1429,20 +1479,22 @@ SRT_API int srt_render_frame_multi_accum(srt_comm *comm, uint32_t width, uint32_
 SRT_API int srt_comm_accum_reset_adaptive(srt_comm *comm, const srt_adaptive *cfg);
 SRT_API int srt_comm_accum_active(srt_comm *comm, uint64_t *active);
 /* Spectral film on W GPUs: srt_accum_reset_spectral on every local context; srt_render_frame_multi_accum then runs MODE 5 on each rank.
- * The films stay with their ranks (srt_read_spectral per context; each pixel is owned by one rank and reads +0 on the others). */
+ * The films stay with their ranks (srt_read_spectral per context; each pixel is owned by one rank and reads +0 on the others) until
+ * srt_comm_gather_accum(comm, SRT_GATHER_FILM | ..) brings them to rank 0. */
 SRT_API int srt_comm_accum_reset_spectral(srt_comm *comm);
 /* First-hit features on W GPUs: srt_accum_reset_features on every local context; srt_render_frame_multi_accum then runs MODE 7 on each
- * rank.  The rows stay with their ranks (srt_read_features per context; each pixel is owned by one rank and reads +0 on the others).  On
- * process-per-GPU communicators too: no decision crosses ranks. */
+ * rank.  The rows stay with their ranks (srt_read_features per context; each pixel is owned by one rank and reads +0 on the others) until
+ * srt_comm_gather_accum brings them to rank 0.  On process-per-GPU communicators too: no decision crosses ranks. */
 SRT_API int srt_comm_accum_reset_features(srt_comm *comm);
 /* srt_accum_reset_adaptive_features on every local rank; like srt_comm_accum_reset_adaptive, SRT_ERR_UNSUPPORTED on a process-per-GPU
- * communicator.  The rows stay with their ranks, as for srt_comm_accum_reset_features. */
+ * communicator.  The rows stay with their ranks until srt_comm_gather_accum, as for srt_comm_accum_reset_features. */
 SRT_API int srt_comm_accum_reset_adaptive_features(srt_comm *comm, const srt_adaptive *cfg);
 /* srt_accum_reset_spectral_features on every local rank (any communicator: no decision crosses ranks); film and rows stay with their
- * ranks, as for srt_comm_accum_reset_spectral and srt_comm_accum_reset_features.  There is no srt_comm denoise: a gathered denoise is out of scope. */
+ * ranks, as for srt_comm_accum_reset_spectral and srt_comm_accum_reset_features.  A denoise of the whole frame: srt_comm_gather_accum, then the
+ * stage on srt_comm_root_ctx. */
 SRT_API int srt_comm_accum_reset_spectral_features(srt_comm *comm);
 /* srt_accum_reset_adaptive_spectral / _features on every local rank; like srt_comm_accum_reset_adaptive, SRT_ERR_UNSUPPORTED on a
- * process-per-GPU communicator.  Film and rows stay with their ranks; srt_comm_accum_active sums the active pixels. */
+ * process-per-GPU communicator.  Film and rows stay with their ranks until srt_comm_gather_accum; srt_comm_accum_active sums the active pixels. */
 SRT_API int srt_comm_accum_reset_adaptive_spectral(srt_comm *comm, const srt_adaptive *cfg);
 SRT_API int srt_comm_accum_reset_adaptive_spectral_features(srt_comm *comm, const srt_adaptive *cfg);
 /* Sample-parallel pixels on W GPUs: srt_accum_reset_streams on every local context; srt_render_frame_multi_accum then runs MODE 6 on each
@@ -1454,6 +1506,19 @@ SRT_API int srt_comm_stats(srt_comm *comm, uint64_t *rays, uint64_t *paths, floa
 /* Time between the end of a local rank's render kernel and the end of the exchange of the last frame (gather + waiting for
  * the slowest rank + the scatter on rank 0), max over the local ranks, ms; 0 in a 1-rank world. */
 SRT_API int srt_comm_last_gather_ms(srt_comm *comm, float *ms);
+/* The accumulations of the ranks gathered on rank 0 (srt_pack_accum on every local rank's stream, ONE ncclGather of the units into a
+ * buffer of their own, srt_unpack_accum on rank 0): afterwards srt_comm_root_ctx is whole for every stage that reads `parts` -- the
+ * denoisers, the temporal stage, srt_present_* -- and computes what a single context would compute, bit for bit.  parts: SRT_GATHER_*
+ * as for srt_pack_accum (0: everything the kind holds except the film).  Asynchronous like srt_render_frame_multi, and to be repeated
+ * after every further pass: callers gather before they look.  With world == 1 it succeeds and does nothing.
+ * Before anything is enqueued the ranks must agree on kind, sample total, streams, chunk and offset, and parts (srt_comm_init_all
+ * compares its contexts; srt_comm_init_rank all-gathers a 32-byte descriptor, the same collective on every rank): a mismatch -- or a
+ * rank whose context would refuse the pack -- returns SRT_ERR_INVALID on EVERY rank, and no rank enters the gather alone. */
+SRT_API int srt_comm_gather_accum(srt_comm *comm, uint32_t parts);
+/* Of the last srt_comm_gather_accum, ms: the slowest local pack kernel, the exchange (end of a local pack to the end of the gather,
+ * waiting for the slowest rank included; max over the local ranks) and rank 0's unpack kernel (0 where rank 0 is not local).
+ * All 0 in a 1-rank world. */
+SRT_API int srt_comm_last_accum_gather_ms(srt_comm *comm, float *pack_ms, float *exchange_ms, float *unpack_ms);
 
 /* Issue-rate calibration (no reference counterpart: measurement support for bench.py's roofline).  Runs microkernel
  * `kind` (csrc/srt_calib.hip: 0 v_add_f32, 1 v_pk_mul_f32, 2 v_fma_f32, 3 dependent v_add_f32 chain, 4 s_add_u32,
