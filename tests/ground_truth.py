@@ -13,7 +13,11 @@ of srt_color_tables, the camera struct), widened to float64; its outputs are wha
                  where a fuzzed metal and a thin lens send the light (the *_sampled twins state the same quantities as plain counts)
   lane_index, footprint_average, project_points, polygon_area, coverage_map     pixel helpers
   soup, bumpy_sheet, axis_aligned_set, ... , to_structs                          scene builders on raw arrays
-  assert_hits_hold, assert_edge_aimed_hold, builtin_report, assert_radiometry_holds
+  hat, film_integrals, hero_film_moments, film_expectation
+                 one path's deposit into every bin of the spectral film: tents on the 5 nm grid, integrated exactly per cell
+  plates, feature_expectation
+                 the first-hit features: exact coverage of each triangle, the normal turned towards the camera, col, the distance
+  assert_hits_hold, assert_edge_aimed_hold, builtin_report, assert_radiometry_holds, assert_film_holds, assert_features_hold
                  the conditions both suites apply: tests/test_ground_truth_reference.py to the oracle (CPU), tests/test_ground_truth.py
                  to the device (GPU), on the same inputs and with the same thresholds
 
@@ -1014,6 +1018,20 @@ def sky_only():
     return scene(FAR_TRIANGLE, [GREY], background=bg), (40.0, (0, 1, 5), (0, 0, 0)), 48, 32, 64, 4
 
 
+SPIKES = {0: 0.875, 37: 0.625, 60: 0.3125, 61: 0.75, 94: 0.4375}      # grid sample -> value: isolated tents, one pair of neighbours
+
+
+def sky_spikes():
+    """sky_only under a background that is 0 but at five grid samples: its interpolant is a few tents, so the film is non-zero in bins
+    0, 1, 36 .. 38, 59 .. 62, 93 and 94 only, in fixed ratios -- the test of the bin geometry, the clamped last cell and the end bins"""
+    bg = np.zeros(N_GRID, np.float32)
+    for j, v in SPIKES.items():
+        bg[j] = v
+    sc, camera, W, H, spp, depth = sky_only()
+    sc["background"] = bg
+    return sc, camera, W, H, spp, depth
+
+
 def floor_under_sky():
     return scene(FLOOR, [material(MAT_LAMBERTIAN, ramp())], mat_index=[0, 0], background=bump()), (30.0, (0, 3, 4), (0, 0, 0)), 48, 32, 64, 2
 
@@ -1144,8 +1162,13 @@ RADIOMETRY = {"sky_only": sky_only, "floor_under_sky": floor_under_sky, "emissiv
 # the cases held per pixel as well (rms z, at least MIN_PIXELS pixels, dark pixels exactly 0), and their quadratures: the smallest
 # for which halving any one resolution moves no held pixel's E by 0.1 of its standard error (test_quadratures_are_converged)
 PER_PIXEL = ("wedge_dispersion", "wedge_tir", "fuzz_absorbed", "fuzz_directed", "lens")
-QUADRATURE = {"wedge_dispersion": dict(nodes=128, refine=16, sub_x=8, sub_y=1), "wedge_tir": dict(nodes=64, refine=32, sub_x=16, sub_y=1), "fuzz_absorbed": dict(sub=2),
-              "fuzz_directed": dict(na=64, sub=8), "lens": dict(sub=4)}
+# The film's wedges (film_expectation) have resolutions of their own (film_*: hero intervals per 5 nm cell, bisections that place a
+# jump, sub-pixels across and down), held to the same rule for the film's entries (test_film_quadratures_are_converged); the film
+# shares the other cases' resolutions with the XYZ sums.
+QUADRATURE = {"wedge_dispersion": dict(nodes=128, refine=16, sub_x=8, sub_y=1, film_cell=1, film_bisect=8, film_sub_x=16, film_sub_y=1),
+              "wedge_tir": dict(nodes=64, refine=32, sub_x=16, sub_y=1, film_cell=1, film_bisect=8, film_sub_x=8, film_sub_y=1),
+              "fuzz_absorbed": dict(sub=2), "fuzz_directed": dict(na=64, sub=8), "lens": dict(sub=4)}
+XYZ_ONLY, FILM_ONLY = ("nodes", "refine", "sub_x", "sub_y"), ("film_cell", "film_bisect", "film_sub_x", "film_sub_y")
 Z_IMG_MAX = 5.0                      # statistical constants, not measurements
 RMS_Z_RANGE = (0.8, 1.2)
 MIN_EXPECTED = 10.0                  # per-pixel z only where spp P(contribute) >= 10
@@ -1223,7 +1246,7 @@ def expectation(name, cmf, cam, sc, W, H, depth, res=None):
         Var = (Va + Ea ** 2) + (Vb + Eb ** 2) - E ** 2
         return dict(E=E, Var=Var, P=Pa + Pb, E_sum=path_moments(cmf, [spec(0)])[0] * area_a + path_moments(cmf, [spec(1)])[0] * polygon_area(Qb),
                     near=Pa, focus=Pb)
-    if name == "sky_only":
+    if name in ("sky_only", "sky_spikes"):
         E, V = path_moments(cmf, [bg])
         return dict(E=E, Var=V, P=None, E_sum=None)
     if name == "floor_under_sky":
@@ -1287,4 +1310,380 @@ def assert_radiometry_holds(name, xyz_planes, W, H, spp, exp, what):
         out["dark"] = int(dark.sum())
         sums = np.stack([np.asarray(xyz_planes[c])[lane_index(W, H)] for c in range(3)])
         assert not sums[:, dark].any(), "%s %s: %d dark pixels are lit" % (what, name, (sums[:, dark] != 0).any(0).sum())
+    return out
+
+
+# ---- the spectral film ------------------------------------------------------------------------------------------------------------
+GRID = LAMBDA_MIN + 5.0 * np.arange(N_GRID)          # lambda_j = 360 + 5 j: the tent of film bin j peaks there
+FILM_GL = 4                   # Gauss-Legendre nodes per 5 nm cell: exact to degree 7 (hat^2 p^2 with two linear factors has degree 6)
+FILM_JUMP = 0.005             # hero_film_moments' JUMP: a film entry sees 10 nm of the hero, so smaller steps of P must be placed too
+FILM_MIN_ENTRIES = 3000      # entries (pixel, bin) with spp Pdep >= MIN_EXPECTED a per-entry hold needs, in at least MIN_PIXELS pixels
+PER_BIN_ONLY = ("mirror",)    # 33 lit pixels: held per bin over the image alone
+FILM_CASES = dict(RADIOMETRY, sky_spikes=sky_spikes)
+
+
+def hat(j, lam):
+    """the tent of film bin j: 1 at lambda_j, 0 from 5 nm away; the grid's ends cut the tents of bins 0 and 94 in half"""
+    lam = np.asarray(lam, np.float64)
+    inside = (lam >= LAMBDA_MIN) & (lam <= LAMBDA_MAX)
+    return np.where(inside, np.maximum(0.0, 1.0 - np.abs(lam - GRID[j]) / 5.0), 0.0)
+
+
+def film_integrals(factors, prob=None):
+    """per bin j (3, 95): the integrals over lambda of hat_j P p, of hat_j^2 P p^2 and of P over the part of hat_j's support where p > 0,
+    p the product of the linear interpolants of `factors` (non-negative 95-sample tables) and P = prob(lambda) (default 1).  In a 5 nm
+    cell the two tents that meet there and every factor are linear: FILM_GL-point Gauss-Legendre per cell is exact for P = 1.  A linear
+    factor is > 0 on a whole open cell unless both its ends are 0, so the length where p > 0 is exact as well."""
+    x, wq = np.polynomial.legendre.leggauss(FILM_GL)
+    s, wq = 0.5 * (x + 1.0), 2.5 * wq                                        # nodes in [0, 1] across a cell, weights in nm
+    p, pos = np.ones((FILM_GL, N_GRID - 1)), np.ones(N_GRID - 1, bool)
+    for tab in factors:
+        tab = np.asarray(tab, np.float64)
+        assert (tab >= 0).all()
+        p = p * ((1.0 - s)[:, None] * tab[None, :-1] + s[:, None] * tab[None, 1:])
+        pos &= np.maximum(tab[:-1], tab[1:]) > 0
+    P = np.ones_like(p) if prob is None else prob(GRID[None, :-1] + 5.0 * s[:, None])
+    out = np.zeros((3, N_GRID))
+    for k, tent in ((0, 1.0 - s), (1, s)):                                  # the cell's left bin (k = 0) and right bin (k = 1)
+        w = (wq * tent)[:, None] * P
+        out[0, k:N_GRID - 1 + k] += (w * p).sum(0)
+        out[1, k:N_GRID - 1 + k] += (w * tent[:, None] * p * p).sum(0)
+        out[2, k:N_GRID - 1 + k] += (wq[:, None] * P).sum(0) * pos
+    return out
+
+
+def hero_film_moments(factors, prob, rays, cell, bisect):
+    """E, M2 and Pdep (rays, 95) of one hero-only path's deposit into every bin when it contributes with probability prob(ray numbers,
+    hero wavelengths) (hero_moments' setting): (1 / 470) times the integrals of film_integrals.  The hero's range is cut into `cell`
+    equal intervals per 5 nm cell, so that each lies inside one cell and meets the two tents of that cell; prob is taken at an
+    interval's midpoint and held there, while the tents and the spectrum are integrated over it exactly (film_integrals' Gauss-Legendre
+    rule).  Where prob changes by more than FILM_JUMP between neighbouring midpoints (or between an end of the range and its
+    midpoint), the jump is placed by `bisect` bisections, and the interval that holds it is split there into two, each with prob at its
+    own midpoint.  ASSERTED: no interval holds two jumps."""
+    N = (N_GRID - 1) * cell
+    x, wq = np.polynomial.legendre.leggauss(FILM_GL)
+
+    def weights(lo, width):
+        """per interval [lo, lo + width] inside one cell: the cell and the integrals of tent x p, (tent x p)^2 and [p > 0] for the
+        cell's left and right bin, (2, 3, m)"""
+        off = np.minimum(np.floor((lo - LAMBDA_MIN) / 5.0 + 1e-9).astype(np.int64), N_GRID - 2)
+        out = np.zeros((2, 3, len(lo)))
+        for xq, wt in zip(0.5 * (x + 1.0), 0.5 * wq):
+            lam = lo + xq * width
+            s = (lam - GRID[off]) / 5.0
+            p = np.ones_like(lam)
+            for tab in factors:
+                p = p * interp(np.asarray(tab, np.float64), lam)
+            for side, tent in ((0, 1.0 - s), (1, s)):
+                out[side] += wt * width * np.stack([tent * p, (tent * p) ** 2, (tent > 0) * (p > 0)])
+        return off, out
+
+    width = (LAMBDA_MAX - LAMBDA_MIN) / N
+    h0 = hero_nodes(N)
+    P0 = prob(np.repeat(np.arange(rays), N), np.tile(h0, rays)).reshape(rays, N)
+    ends = prob(np.repeat(np.arange(rays), 2), np.tile([LAMBDA_MIN, LAMBDA_MAX], rays)).reshape(rays, 2)
+    Pe, he = np.concatenate([ends[:, :1], P0, ends[:, 1:]], 1), np.concatenate([[LAMBDA_MIN], h0, [LAMBDA_MAX]])
+    r, i = np.nonzero(np.abs(np.diff(Pe, axis=1)) > FILM_JUMP)
+    lo, hi, plo, phi = he[i], he[i + 1], Pe[r, i], Pe[r, i + 1]
+    for _ in range(bisect):
+        mid = 0.5 * (lo + hi)
+        pm = prob(r, mid)
+        left = np.abs(pm - plo) > np.abs(pm - phi)               # the jump lies below mid
+        lo, hi = np.where(left, lo, mid), np.where(left, mid, hi)
+    at = 0.5 * (lo + hi)
+    k = np.clip(np.floor((at - LAMBDA_MIN) / width).astype(np.int64), 0, N - 1)
+    assert len(set(zip(r.tolist(), k.tolist()))) == len(r), "hero_film_moments: two jumps in one interval (raise the cells' nodes)"
+    split = np.zeros((rays, N), bool)
+    split[r, k] = True
+    coarse = np.where(split, 0.0, P0) / (LAMBDA_MAX - LAMBDA_MIN)
+    off, w = weights(h0 - 0.5 * width, np.full(N, width))
+    A = np.zeros((3, N, N_GRID))
+    for side in (0, 1):
+        A[:, np.arange(N), off + side] = w[side]
+    E, M2, D = (coarse @ A[q] for q in range(3))
+    a = LAMBDA_MIN + k * width
+    for start, part in ((a, at - a), (at, a + width - at)):
+        Pp = prob(r, start + 0.5 * part) / (LAMBDA_MAX - LAMBDA_MIN)
+        off, w = weights(start, part)
+        for q, out in enumerate((E, M2, D)):
+            for side in (0, 1):
+                np.add.at(out, (r, off + side), Pp * w[side, q])
+    return E, M2, D
+
+
+def _share(name, cam, sc, W, H, q):
+    """(H * W,) the probability that a path of each pixel contributes, for the cases whose paths keep all seven wavelengths and whose
+    P does not depend on the wavelength: the quantities expectation() computes, with exact coverages for the two projected triangles"""
+    bg = f64(sc["background"])
+    if name in ("sky_only", "sky_spikes", "emissive_wall"):
+        return np.ones(W * H)
+    if name == "floor_under_sky":
+        footprint_average(lambda eye, d: floor_points(eye, d)[:, 0], cam, W, H, 2)          # (asserts: every ray lands on the floor)
+        return np.ones(W * H)
+    if name == "cosine_law":
+        return footprint_average(lambda eye, d: form_factor(floor_points(eye, d), (0.0, 1.0, 0.0), f64(LIGHT)), cam, W, H, 6)
+    if name == "mirror":
+        return coverage_exact(project_points(cam, mirror_y(f64(MIRROR_LIGHT)))[0], W, H)
+    if name == "fuzz_absorbed":
+        def share(eye, d):
+            floor_points(eye, d)                                      # (asserts: every ray lands on the floor)
+            return fuzz_share(-unit(d)[:, 1], FUZZ_ABSORBED)
+        return footprint_average(share, cam, W, H, q["sub"])
+    assert name == "fuzz_directed" and not bg.any(), name
+    return footprint_average(lambda eye, d: fuzz_light_share(floor_points(eye, d), unit(d) * np.array([1.0, -1.0, 1.0]), FUZZ_DIRECTED,
+                                                              f64(MIRROR_LIGHT), q["na"]), cam, W, H, q["sub"])
+
+
+def film_expectation(name, cam, sc, W, H, depth, res=None, d65n=None):
+    """E, Var and Pdep (H * W, 95) of ONE path's deposit into every film bin of every pixel of a case of FILM_CASES (Pdep: the
+    probability that the deposit is non-zero), and all_seven (the paths keep their seven wavelengths; P does not depend on them).
+    A path deposits hat_j(l) p(l) at each of its m valid wavelengths l, each marginally uniform on [360, 830], at most one of them in a
+    tent's support (they lie 470/7 apart): E_j = (m / 470) int hat_j P p, M2_j = (m / 470) int hat_j^2 P p^2, Pdep_j = (m / 470)
+    int over supp hat_j of P [p > 0]; m = 7, or 1 for a path that refracted (slab_*, wedge_*: the hero alone).  res: the resolutions
+    of the case's quadrature (default QUADRATURE[name]); d65n: the normalised D65 row of the colour tables (emissive_wall's bake)."""
+    spec = lambda k: f64(sc["mats"][k]["spectrum"])
+    bg = f64(sc["background"])
+    q = res or QUADRATURE.get(name)
+    if name.startswith("wedge_"):
+        polys, kinds = sc["polys"], sc["kinds"]
+        glass = [p for p, k in zip(polys, kinds) if k == GLASS]
+        assert all(outside_convex(glass, p) for p, k in zip(polys, kinds) if k == EMITTER), "the emitter must lie wholly outside the glass"
+        assert (spec(0) == 1).all() and not bg.any()
+        B, C = f64(sc["mats"][0]["B"]), f64(sc["mats"][0]["C"])
+        nx, ny = q["film_sub_x"], q["film_sub_y"]
+        sub = [((a + 0.5) / nx - 0.5, (b + 0.5) / ny - 0.5) for a in range(nx) for b in range(ny)]
+        d = np.concatenate([unit(pixel_rays(cam, W, H, fx, fy)[1]) for fx, fy in sub])
+        eye = camera_arrays(cam)[0]
+        prob = lambda r, h: glass_paths(polys, kinds, np.broadcast_to(eye, (len(r), 3)), d[r], sellmeier_index(B, C, h), depth)
+        E, M2, D = (m.reshape(len(sub), W * H, N_GRID).mean(0)
+                    for m in hero_film_moments([spec(1)], prob, len(d), q["film_cell"], q["film_bisect"]))
+        return dict(E=E, Var=M2 - E * E, Pdep=D, all_seven=False)
+    if name.startswith("slab_"):
+        # the slab_ case of expectation(): moments on 9 cosines spanning the view, interpolated to every pixel's centre ray
+        eye, d = pixel_rays(cam, W, H)
+        cos_px = np.abs(d[:, 2]) / np.linalg.norm(d, axis=1)
+        eye, dc = pixel_rays(cam, W, H, 0.5, 0.5)
+        corners = np.concatenate([np.abs(dc[:, 2]) / np.linalg.norm(dc, axis=1), cos_px])
+        grid = np.linspace(min(corners.min(), cos_px.min()) - 1e-4, min(1.0, corners.max() + 1e-4), 9)
+        B, C = f64(sc["mats"][0]["B"]), f64(sc["mats"][0]["C"])
+        mom = np.stack([film_integrals([spec(1)], lambda l, c=c: slab_transmission(sellmeier_index(B, C, l), c, depth)) for c in grid])
+        E, M2, D = (np.stack([np.interp(cos_px, grid, mom[:, i, j]) for j in range(N_GRID)], 1) / (LAMBDA_MAX - LAMBDA_MIN) for i in range(3))
+        return dict(E=E, Var=M2 - E * E, Pdep=D, all_seven=False)
+    scale = N_WAVELENGTHS / (LAMBDA_MAX - LAMBDA_MIN)
+    if name == "lens":
+        assert not bg.any() and cam.defocus_angle > 0
+        Qb, depth_b = project_points(cam, f64(LENS_FOCUS))
+        assert np.abs(depth_b - 1.0).max() < 1e-6
+        terms = [(lens_coverage(cam, f64(LENS_NEAR), W, H, q["sub"]), [spec(0)]), (coverage_exact(Qb, W, H), [spec(1)])]
+        assert not ((terms[0][0] > 0) & (terms[1][0] > 0)).any(), "lens: the two images must not overlap"
+    elif name == "emissive_wall":
+        assert d65n is not None, "emissive_wall: the bake needs the D65 row"
+        terms = [(_share(name, cam, sc, W, H, q), [baked_emission(d65n, sc["mats"][0]["power"])])]
+    else:
+        ends = {"sky_only": ("bg",), "sky_spikes": ("bg",), "floor_under_sky": (0, "bg"), "cosine_law": (0, 1), "mirror": (0, 1),
+                "fuzz_absorbed": (0, "bg"), "fuzz_directed": (0, 1)}[name]              # the tables a contributing path's power multiplies
+        terms = [(_share(name, cam, sc, W, H, q), [bg if k == "bg" else spec(k) for k in ends])]
+    E, M2, D = (np.zeros((W * H, N_GRID)) for _ in range(3))
+    for P, factors in terms:                     # the terms are exclusive: a path ends on one of the triangles, or on none
+        I = film_integrals(factors) * scale
+        E += P[:, None] * I[0]; M2 += P[:, None] * I[1]; D += P[:, None] * I[2]
+    return dict(E=E, Var=M2 - E * E, Pdep=D, all_seven=True)
+
+
+def film_spp(name, spp, fexp):
+    """the film run's samples per pixel: the case's spp, raised to the smallest power of two at which the entries with spp Pdep >=
+    MIN_EXPECTED number at least FILM_MIN_ENTRIES in at least MIN_PIXELS pixels (the case's own for PER_BIN_ONLY)"""
+    if name in PER_BIN_ONLY:
+        return spp
+    for k in range(6):
+        held = spp * 2 ** k * fexp["Pdep"] >= MIN_EXPECTED
+        if held.sum() >= FILM_MIN_ENTRIES and held.any(1).sum() >= MIN_PIXELS:
+            return spp * 2 ** k
+    raise AssertionError("%s: no spp up to %d meets the per-entry counts" % (name, spp * 32))
+
+
+def film_case(srt, name, res=None):
+    """scene, camera, frame, the film run's spp, depth and film_expectation (with its CPU time in `seconds`) of a case of FILM_CASES,
+    computed once per session and shared by both builders (res: other resolutions of the quadrature)"""
+    import time
+    sc, args, W, H, spp, depth = FILM_CASES[name]()
+    cam = camera(srt, args, W, H)
+
+    def make():
+        t = time.process_time()
+        exp = film_expectation(name, cam, sc, W, H, depth, res, color_tables(srt)[3])
+        exp["seconds"] = round(time.process_time() - t, 2)
+        return exp
+    exp = cached(("film", name) if res is None else ("film", name, tuple(sorted(res.items()))), make)
+    return sc, cam, W, H, film_spp(name, spp, exp), depth, exp
+
+
+def neighbourhood_lit(lit):
+    """lit (a, b, c) -> whether any of the 3 x 3 x 3 entries around each is lit"""
+    a, b, c = lit.shape
+    pad = np.pad(lit, 1)
+    return np.any([pad[i:i + a, j:j + b, k:k + c] for i in range(3) for j in range(3) for k in range(3)], axis=0)
+
+
+def assert_film_holds(name, film, W, H, spp, exp, what, radiance=None):
+    """The conditions on a film (H, W, 95) of raw sums after spp samples of every pixel, against film_expectation `exp`:
+      per bin over the image   |z_bin| <= Z_IMG_MAX + the float32 summation allowance (spp 2^-24 of the expected total) for every bin
+                               with Var > 0, z_bin = (sum F_j - spp sum E_j) / sqrt(spp sum Var_j);
+      per entry (pixel, bin)   RMS_Z_RANGE holds the rms z over the entries with spp Pdep >= MIN_EXPECTED, of which there are at least
+                               FILM_MIN_ENTRIES in at least MIN_PIXELS pixels (not for PER_BIN_ONLY);
+      dark entries             a sum is exactly 0 where E is 0 at the entry and at its 26 neighbours (3 x 3 pixels x bin -+ 1); where
+                               P does not depend on the wavelength, every bin whose E is 0 in every pixel holds 0 everywhere;
+      estimator                radiance (srt.spectral_radiance, for sky_only and sky_spikes): the image mean at bin j is the hat average
+                               of the background, int hat_j b / int hat_j (5 nm, 2.5 at the ends), within the same bound.
+    Returns the figures for the test's printed line."""
+    F = np.asarray(film, np.float64).reshape(H * W, N_GRID)
+    E, Var, Pdep = exp["E"], exp["Var"], exp["Pdep"]
+    sE, sV = E.sum(0), Var.sum(0)
+    bins = sV > 0
+    sd = np.sqrt(spp * sV[bins])
+    z_bin = (F.sum(0)[bins] - spp * sE[bins]) / sd
+    allowance = spp * U * spp * sE[bins] / sd
+    out = dict(spp=spp, max_z_bin=round(float(np.abs(z_bin).max()), 2), rms_z_bin=round(float(np.sqrt((z_bin ** 2).mean())), 3))
+    assert (np.abs(z_bin) <= Z_IMG_MAX + allowance).all(), "%s %s: z_bin %s at bin %d" % (what, name, out, np.nonzero(bins)[0][np.abs(z_bin).argmax()])
+    if name not in PER_BIN_ONLY:
+        held = spp * Pdep >= MIN_EXPECTED
+        z = (F[held] - spp * E[held]) / np.sqrt(spp * Var[held])
+        out.update(entries=int(held.sum()), pixels=int(held.any(1).sum()), rms_z=round(float(np.sqrt((z ** 2).mean())), 3),
+                   max_z=round(float(np.abs(z).max()), 2))
+        assert held.sum() >= FILM_MIN_ENTRIES and held.any(1).sum() >= MIN_PIXELS, (what, name, out)
+        assert RMS_Z_RANGE[0] <= out["rms_z"] <= RMS_Z_RANGE[1], "%s %s: rms z %s" % (what, name, out)
+    dark = ~neighbourhood_lit((E > 0).reshape(H, W, N_GRID)).reshape(H * W, N_GRID)
+    out["dark"] = int(dark.sum())
+    assert not F[dark].any(), "%s %s: %d dark entries are non-zero" % (what, name, (F[dark] != 0).sum())
+    if exp["all_seven"]:
+        unlit = ~(E > 0).any(0)
+        out["unlit_bins"] = int(unlit.sum())
+        assert not F[:, unlit].any(), "%s %s: unlit bins %s hold deposits" % (what, name, np.nonzero(unlit & (F != 0).any(0))[0])
+    if radiance is not None:
+        assert name in ("sky_only", "sky_spikes")
+        width = np.where((np.arange(N_GRID) == 0) | (np.arange(N_GRID) == N_GRID - 1), 2.5, 5.0)
+        want = film_integrals([f64(FILM_CASES[name]()[0]["background"])])[0] / width
+        scale = (LAMBDA_MAX - LAMBDA_MIN) / 35.0 * 5.0 / width / (W * H * spp)      # image mean of the estimator per raw sum
+        got = np.asarray(radiance(film, spp), np.float64).reshape(H * W, N_GRID).mean(0)
+        z_est = (got[bins] - want[bins]) / (scale[bins] * sd)
+        out["max_z_estimator"] = round(float(np.abs(z_est).max()), 2)
+        assert (np.abs(z_est) <= Z_IMG_MAX + allowance).all(), "%s %s: estimator z %s at bin %d" % (what, name, out, np.nonzero(bins)[0][np.abs(z_est).argmax()])
+        assert not got[~bins].any(), (what, name, "estimator non-zero in an unlit bin")
+    return out
+
+
+# ---- first-hit features ------------------------------------------------------------------------------------------------------------
+PLATE_IMAGES = np.array([[(2.0, 2.0), (29.0, 3.0), (6.0, 17.0)], [(34.0, 2.0), (61.0, 5.0), (50.0, 18.0)],        # pixel coordinates
+                         [(3.0, 21.0), (28.0, 23.0), (14.0, 37.0)], [(36.0, 22.0), (61.0, 21.0), (45.0, 37.0)]])
+PLATE_PLANES = [((0.0, 0.0, 0.0), (0.3, 0.2, 1.0)), ((0.0, 0.0, -1.5), (-0.4, 0.1, 1.0)),                             # point, normal
+                ((0.0, 0.0, 1.0), (0.2, -0.5, 1.0)), ((0.0, 0.0, -3.0), (0.1, 0.35, 1.0))]
+PLATE_COLS = [(0.5, 0.25, 0.75), (0.125, 0.625, 0.375), (0.875, 0.0625, 0.5625), (0.3125, 0.9375, 0.1875)]     # dyadic: n col is exact
+PLATE_CAMERA = (30.0, (0.0, 0.0, 10.0), (0.0, 0.0, 0.0))
+FEATURE_SUB = 16              # k x k sub-samples of the distance truth (test_feature_distance_is_converged)
+MIN_EDGE_PIXELS = 100         # pixels with n P >= MIN_EXPECTED and n (1 - P) >= MIN_EXPECTED that hold the binomial rms
+NORMAL_TOL = 1.15e-6            # twice the largest |normal sum / hits - unit normal| the oracle's prediction shows (tests/test_ground_truth_reference.py)
+
+
+def plates(srt):
+    """four triangles seen by a pinhole camera under a bumped sky, 64 x 40 pixels x 64 samples: each the camera's central projection of
+    the pixel triangle PLATE_IMAGES[k] onto a tilted plane PLATE_PLANES[k] at its own depth, so that the images are known and pairwise
+    disjoint; the last is wound away from the camera.  Materials Lambertian, metallic, dielectric, emissive, their col distinct dyadic
+    fractions.  Needs the package's camera (srt) to place the corners."""
+    W, H = 64, 40
+    cam = camera(srt, PLATE_CAMERA, W, H)
+    eye, p00, du, dv = camera_arrays(cam)
+    V = []
+    for img, (pt, nrm) in zip(PLATE_IMAGES, PLATE_PLANES):
+        pt, nrm = np.array(pt), np.array(nrm)
+        d = p00[None, :] + img[:, :1] * du[None, :] + img[:, 1:] * dv[None, :] - eye[None, :]
+        V.append(eye[None, :] + (((pt - eye) @ nrm) / (d @ nrm))[:, None] * d)
+    V = np.array([v[::-1] for v in V[:3]] + V[3:])                 # (the image's y runs down: the corners as listed are wound away)
+    toward = (np.cross(V[:, 1] - V[:, 0], V[:, 2] - V[:, 0]) * (eye[None, :] - V[:, 0])).sum(1) > 0
+    assert toward.tolist() == [True, True, True, False], toward
+    mats = [material(MAT_LAMBERTIAN, ramp(), col=PLATE_COLS[0]), material(MAT_METALLIC, ramp(0.9, 0.3), col=PLATE_COLS[1]),
+            material(MAT_DIELECTRIC, np.ones(N_GRID, np.float32), col=PLATE_COLS[2]),
+            material(MAT_EMISSIVE, bump(0.5, 3.0, 540.0, 90.0), col=PLATE_COLS[3])]
+    return scene(V, mats, background=bump()), PLATE_CAMERA, W, H, 64, 4
+
+
+def feature_expectation(name, cam, sc, W, H, sub=FEATURE_SUB, lens_sub=None):
+    """per triangle k: P (K, H * W) that a camera ray of the pixel meets it first, the unit normal turned towards the camera (K, 3) and
+    the material's col as float32 (K, 3); for the pinhole case (plates) also the footprint mean and variance of |hit - eye| over
+    sub x sub sub-samples (dist, dist_var: (H * W,), NaN where a sub-sample misses), with the hits from closest_hit"""
+    Vd = f64(sc["V"])
+    _, nu = normals(Vd)
+    eye = camera_arrays(cam)[0]
+    toward = np.sign(((eye[None, :] - Vd[:, 0]) * nu).sum(1))
+    # a thin lens moves the origin by its radius at most: every lens point must lie on the same side of every plane
+    radius = np.linalg.norm(np.array(cam.defocus_disk_u[:], np.float64)) if cam.defocus_angle > 0 else 0.0
+    assert (np.abs(((eye[None, :] - Vd[:, 0]) * nu).sum(1)) > radius).all()
+    col = np.array([sc["mats"][m]["col"] for m in sc["mat_index"]], np.float32)
+    out = dict(normal=nu * toward[:, None], col=col, facing=toward)
+    if name == "lens":
+        out["P"] = np.stack([lens_coverage(cam, Vd[0], W, H, lens_sub or QUADRATURE["lens"]["sub"]),
+                             coverage_exact(project_points(cam, Vd[1])[0], W, H)])
+        return out
+    assert name == "plates" and cam.defocus_angle == 0
+    out["P"] = np.stack([coverage_exact(project_points(cam, v)[0], W, H) for v in Vd])
+    m1, m2 = np.zeros(W * H), np.zeros(W * H)
+    for a in range(sub):
+        for b in range(sub):
+            e, d = pixel_rays(cam, W, H, (a + 0.5) / sub - 0.5, (b + 0.5) / sub - 0.5)
+            t, tri, _, _ = closest_hit(Vd, np.broadcast_to(e, d.shape), d)
+            r = np.where(tri >= 0, t * np.linalg.norm(d, axis=1), np.nan)
+            m1 += r; m2 += r * r
+    m1, m2 = m1 / sub ** 2, m2 / sub ** 2
+    out["dist"], out["dist_var"] = m1, m2 - m1 * m1
+    return out
+
+
+FEATURE_CASES = ("plates", "lens")
+
+
+def feature_case(srt, name, sub=FEATURE_SUB):
+    """scene, camera, frame, samples, depth and feature_expectation of plates or lens, computed once per session"""
+    sc, args, W, H, n, depth = plates(srt) if name == "plates" else lens()
+    cam = camera(srt, args, W, H)
+    return sc, cam, W, H, n, depth, cached(("features", name, sub), lambda: feature_expectation(name, cam, sc, W, H, sub))
+
+
+def assert_features_hold(rows, n, exp, what):
+    """The conditions on feature rows (H, W, 8) of raw sums after n samples of every pixel, against feature_expectation `exp`:
+      hits     |z_img| <= Z_IMG_MAX against the sum of P; the rms of the binomial z in RMS_Z_RANGE over the pixels with n P >= 10 and
+               n (1 - P) >= 10, of which there are at least MIN_EDGE_PIXELS; hits == n where P == 1; all eight sums exactly 0 where P
+               is 0 at the pixel and its eight neighbours;
+      normal   normal sum / hits within NORMAL_TOL of the unit normal turned towards the camera, at every pixel that sees one triangle;
+      albedo   albedo sum == hits col exactly at those pixels;
+      distance (when exp holds one) at every pixel wholly inside one triangle, of which there are at least MIN_PIXELS, the rms of
+               (distance sum / n - mean) / sqrt(variance / n) in RMS_Z_RANGE.
+    Returns the figures for the test's printed line."""
+    Hh, Ww = rows.shape[:2]
+    R = np.asarray(rows, np.float64).reshape(-1, 8)
+    hits, Pk = R[:, 7], exp["P"]
+    P = Pk.sum(0)
+    assert P.max() <= 1.0 + 1e-9
+    z_img = (hits.sum() - n * P.sum()) / np.sqrt(n * (P * (1 - P)).sum())
+    edge = (n * P >= MIN_EXPECTED) & (n * (1 - P) >= MIN_EXPECTED)
+    z = (hits[edge] - n * P[edge]) / np.sqrt(n * P[edge] * (1 - P[edge]))
+    full = P >= 1.0 - 1e-12
+    lit = np.pad((P > 0).reshape(Hh, Ww), 1)
+    dark = ~np.any([lit[a:a + Hh, b:b + Ww] for a in range(3) for b in range(3)], axis=0).ravel()
+    out = dict(z_img=round(float(z_img), 2), edge_pixels=int(edge.sum()), rms_z_hits=round(float(np.sqrt((z ** 2).mean())), 3),
+               full=int(full.sum()), dark=int(dark.sum()))
+    assert abs(z_img) <= Z_IMG_MAX, "%s: hits z_img %s" % (what, out)
+    assert edge.sum() >= MIN_EDGE_PIXELS and RMS_Z_RANGE[0] <= out["rms_z_hits"] <= RMS_Z_RANGE[1], "%s: hits %s" % (what, out)
+    assert (hits[full] == n).all(), "%s: %d full pixels missed" % (what, (hits[full] != n).sum())
+    assert not R[dark].any(), "%s: %d dark pixels hold sums" % (what, R[dark].any(1).sum())
+    one = ((Pk > 0).sum(0) == 1) & (hits > 0)
+    k = Pk.argmax(0)[one]
+    dev = np.abs(R[one, 0:3] / hits[one, None] - exp["normal"][k]).max()
+    out.update(one_triangle=int(one.sum()), normal_dev=float("%.3g" % dev))
+    assert dev <= NORMAL_TOL, "%s: normal off by %.3g" % (what, dev)
+    albedo = R[one, 3:6] != hits[one, None] * exp["col"][k].astype(np.float64)
+    assert not albedo.any(), "%s: %d albedo sums differ from hits x col" % (what, albedo.any(1).sum())
+    if "dist" in exp:
+        inside = (Pk >= 1.0 - 1e-12).any(0)
+        zd = (R[inside, 6] / n - exp["dist"][inside]) / np.sqrt(exp["dist_var"][inside] / n)
+        out.update(inside=int(inside.sum()), rms_z_distance=round(float(np.sqrt((zd ** 2).mean())), 3))
+        assert inside.sum() >= MIN_PIXELS and RMS_Z_RANGE[0] <= out["rms_z_distance"] <= RMS_Z_RANGE[1], "%s: distance %s" % (what, out)
     return out

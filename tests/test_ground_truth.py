@@ -1,9 +1,12 @@
-"""The device against tests/ground_truth.py: ray hits (srt_trace_rays, both tree builders) and radiometry (render_image, both kernel
-builds and both tree builders) held to an independent float64 truth.  No oracle call: the conditions, inputs and thresholds are those
+"""The device against tests/ground_truth.py: ray hits (srt_trace_rays, both tree builders), radiometry (render_image, both kernel
+builds and both tree builders), the spectral film (MODE 5) and the first-hit feature rows (MODE 7) held to an independent float64
+truth.  No oracle call: the conditions, inputs and thresholds are those
 the CPU suite (tests/test_ground_truth_reference.py) holds the oracle to, where every threshold is measured."""
+import numpy as np
 import pytest
 
 import ground_truth as G
+from accum_helpers import fresh_context
 from ground_truth import BUILTINS, N_RAYS, POPULATIONS, builtin_report, cached, population
 
 pytestmark = pytest.mark.gpu
@@ -70,3 +73,38 @@ def test_radiometry_holds(srt, gpu, name):
     if name == "floor_under_sky":                      # at depth 1 every path ends at the bounce limit: every sum is exactly 0
         out = srt.render_image(scene, cam, W, H, spp, 1, renderer=gpu)
         assert all(not p.any() for p in out["xyz"])
+
+
+@pytest.mark.parametrize("name", list(G.FILM_CASES))
+def test_film_holds(srt, gpu, name):
+    """The spectral film (accum_reset_spectral, one render_chunk_accum of the case's film spp, read_spectral) against the film's float64
+    truth, both tree builders: per bin over the image |z_bin| <= 5 (+ the float32 summation allowance); per entry (pixel, bin) the rms z
+    in 0.8 .. 1.2 over at least 3 000 entries with spp Pdep >= 10 in at least 300 pixels (mirror: per bin only); entries dark in the
+    truth with their 26 neighbours exactly 0, and so are bins dark in every pixel; for sky_only and sky_spikes the image mean of
+    spectral_radiance is the hat average of the background at every bin.  Inputs, spp and thresholds are those the CPU suite holds
+    the oracle to (test_ground_truth_reference.test_oracle_film_holds, where the oracle's figures stand)."""
+    sc, cam, W, H, spp, depth, exp = G.film_case(srt, name)
+    radiance = srt.spectral_radiance if name in ("sky_only", "sky_spikes") else None
+    for mode in MODES:
+        fresh_context(gpu, G.product_scene(srt, sc, getattr(srt, mode)), cam, W, H, depth)
+        gpu.accum_reset_spectral()
+        gpu.render_chunk_accum(W, H, spp)
+        out = G.assert_film_holds(name, gpu.read_spectral(W, H), W, H, spp, exp, mode, radiance)
+        print(name, mode, "truth's CPU time %.2f s" % exp["seconds"], out)
+
+
+@pytest.mark.parametrize("name", G.FEATURE_CASES)
+def test_features_hold(srt, gpu, name):
+    """The first-hit feature rows (accum_reset_features, one render_chunk_accum of n samples, read_features) against the feature truth,
+    both tree builders: hits binomial in the exact coverage (z_img, rms z over the edge pixels, hits == n where P == 1, all eight sums 0
+    where the pixel and its neighbours are dark); normal sum / hits the unit normal turned towards the camera within NORMAL_TOL and
+    albedo sum == hits col exactly wherever a pixel sees one triangle; for plates the mean distance of every full pixel against the
+    footprint mean of |hit - eye| (rms z in 0.8 .. 1.2).  The oracle's figures stand in test_ground_truth_reference.test_oracle_features_hold."""
+    sc, cam, W, H, n, depth, exp = G.feature_case(srt, name)
+    for mode in MODES:
+        fresh_context(gpu, G.product_scene(srt, sc, getattr(srt, mode)), cam, W, H, depth)
+        gpu.accum_reset_features()
+        gpu.render_chunk_accum(W, H, n)
+        f = gpu.read_features(W, H)
+        rows = np.concatenate([f["normal"], f["albedo"], f["distance"][..., None], f["hits"][..., None]], axis=-1)
+        print(name, mode, G.assert_features_hold(rows, n, exp, "%s %s" % (name, mode)))
