@@ -152,6 +152,16 @@ class TileScheduleInfo(C.Structure):
                 ("split_load_pct", C.c_uint32), ("order_max_pct", C.c_uint32), ("streams", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class QueryInfo(C.Structure):
+    """srt_query_info: the last ray-query launch of a context -- kernel ms, persistent waves, inner records cached in LDS, the variant and
+    whether it was the any query (srt_c_api.h)"""
+    _fields_ = [("ms", C.c_float), ("waves", C.c_uint32), ("n_cached", C.c_uint32), ("narrow_refs", C.c_uint32), ("all_cached", C.c_uint32),
+                ("paired", C.c_uint32), ("any", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+QUERY_MAX_RAYS = 0x7fffffff      # SRT_QUERY_MAX_RAYS (srt_c_api.h)
+
+assert C.sizeof(QueryInfo) == 32
 assert C.sizeof(Denoise) == 32 and C.sizeof(DenoiseVG) == 32
 assert C.sizeof(Meter) == 48 and C.sizeof(MeterResult) == 40 and C.sizeof(Tone) == 32 and C.sizeof(ToneResult) == 24
 assert C.sizeof(PresentCfg) == 184 and C.sizeof(PresentResult) == 64
@@ -317,6 +327,12 @@ PROTOTYPES = {
     "srt_get_wave_debug": (_i, [_vp, C.POINTER(C.c_uint32), _sz]),
     "srt_last_kernel_ms": (_i, [_vp, C.POINTER(_f)]),
     "srt_trace_rays": (_i, [_vp, _fp, _sz, _fp]),
+    "srt_intersect_rays": (_i, [_vp, _fp, _sz, _fp]),
+    "srt_occluded_rays": (_i, [_vp, _fp, _sz, C.POINTER(C.c_uint8)]),
+    "srt_intersect_rays_dev": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "srt_occluded_rays_dev": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "srt_query_last": (_i, [_vp, C.POINTER(QueryInfo)]),
+    "srt_set_query_test_grid": (_i, [_vp, _u32]),
     "srt_device_op_sweep": (_i, [_vp, _i, _fp, _fp, _sz, _fp]),
     "srt_order_tiles_kat": (_i, [_vp, C.POINTER(_u32), _u32, _u32, _u32, _u32, C.POINTER(_u32), _sz, C.POINTER(_u32), C.POINTER(_u32)]),
     "srt_read_tile_schedule": (_i, [_vp, _i, C.POINTER(_u32), _sz, C.POINTER(TileScheduleInfo)]),

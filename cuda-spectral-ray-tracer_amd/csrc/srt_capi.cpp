@@ -236,6 +236,13 @@ struct srt_ctx {
     DeviceBuffer d_motion_kat;                          // srt_surface_motion_kat: the caller's two vertex arrays
     hipEvent_t motion_ev[2] = {};                       // around the last motion kernel (created on first use)
     bool motion_timed = false;
+    // batched ray queries (srt_query.hip; srt_c_api.h, "Ray queries")
+    DeviceBuffer d_query;                               // the kernel's 32-bit ray counter (256 B)
+    DeviceBuffer d_query_io;                            // the host entries' staging: the rays, then the answers
+    hipEvent_t query_ev[2] = {};                        // around the last query kernel (created on first use)
+    bool query_timed = false;
+    srt_query_info query_info = {};                     // the plan of the last query launch (ms filled in by srt_query_last)
+    uint32_t query_max_waves = 0;                       // srt_set_query_test_grid (0: fill the device)
     DeviceBuffer d_streams;                            // sample-parallel pixels (srt_accum_reset_streams, StreamPlanes)
     uint32_t streams_seeded = 0;                        // the K whose RNG streams d_streams holds, seeded since the last srt_init_device_params (0: none)
 };
@@ -756,6 +763,7 @@ void srt_destroy(srt_ctx *c) {
     for (hipEvent_t e : c->temporal_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->temporal_var_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->refit_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->query_ev) if (e) (void)hipEventDestroy(e);
     delete c;      // (every DeviceBuffer, and the pinned staging block, frees itself, on the device selected above)
 }
 
@@ -3852,6 +3860,101 @@ int srt_trace_rays(srt_ctx *c, const float *rays, size_t n, float *out) {
     HIP_TRY_AS(c, "srt_trace_rays", launch_trace(p, d_in.as<float>(), n, d_out.as<float>(), nullptr));
     HIP_TRY_AS(c, "srt_trace_rays", device_synchronize(c));
     HIP_TRY_AS(c, "srt_trace_rays", hipMemcpy(out, d_out.ptr, 4 * n * sizeof(float), hipMemcpyDeviceToHost));
+    return SRT_OK;
+}
+
+// ---- batched ray queries (srt_c_api.h, "Ray queries") ---------------------------------------------------------------------------
+namespace {
+
+// nullptr when the call may go ahead; else why it is refused (nothing enqueued, nothing written).  dev: the pointers are device pointers,
+// whose 16-byte alignment is required for rays and hits.
+const char *query_refusal(const srt_ctx *c, const void *rays, size_t n, const void *out, bool any, bool dev) {
+    if (!c->scene_ready) return "no scene uploaded";
+    if (n > 0 && (!rays || !out)) return "null pointer";
+    if (dev && (((uintptr_t)rays & 15u) != 0 || (!any && ((uintptr_t)out & 15u) != 0))) return "a device rays / hits pointer is not 16-byte aligned";
+    if (n > (size_t)SRT_QUERY_MAX_RAYS) return "n does not fit the 32-bit ray counter (n > SRT_QUERY_MAX_RAYS)";
+    return nullptr;
+}
+
+// Enqueue one query launch of n > 0 rays on `st` (the context's order already taken care of): counter reset, events, kernel.
+int query_enqueue(srt_ctx *c, const char *who, const float *rays_dev, size_t n, void *out_dev, bool any, hipStream_t st) {
+    if (const int rc = develop_reserve(c, who, c->d_query, 256)) return rc;
+    for (int k = 0; k < 2; k++) if (!c->query_ev[k]) HIP_TRY_AS(c, who, hipEventCreate(&c->query_ev[k]));
+    const LaunchPlan lp = plan_of(c);
+    const bool narrow = render_narrow_refs(c->n_records, c->knobs);
+    const bool paired = render_paired_variant(c->paired, narrow, lp.all_cached);
+    const QueryShape s = query_shape(lp, narrow, paired, c->stack_depth, c->n_records, c->knobs, (uint32_t)c->n_cu, c->query_max_waves, n);
+    QueryParams p;
+    memset(&p, 0, sizeof(p));
+    p.nodes = c->d_nodes.as<const float4>(); p.fringe = c->d_fringe.as<const float4>(); p.tris = c->d_tris.as<const float4>();
+    p.root_ref = c->root_ref; p.stack_depth = c->stack_depth; p.n_inner = c->n_inner; p.n_cached = s.n_cached; p.n_records = c->n_records;
+    p.fringe_stride = c->fringe_stride;
+    // the render launch's FRINGE weight for this plan (srt_render_chunk's choice, env SRT_SCORE_FRINGE included)
+    p.score_fringe = c->score_fringe ? c->score_fringe : (lp.all_cached ? (paired ? 400u : 280u) : kScoreFringeL2);
+    p.rays = reinterpret_cast<const float4 *>(rays_dev); p.n = (uint32_t)n;
+    p.counter = c->d_query.as<uint32_t>();
+    if (any) p.occluded = static_cast<uint8_t *>(out_dev); else p.hits = static_cast<float4 *>(out_dev);
+    c->query_timed = false;
+    HIP_TRY_AS(c, who, hipMemsetAsync(p.counter, 0, sizeof(uint32_t), st));
+    HIP_TRY_AS(c, who, hipEventRecord(c->query_ev[0], st));
+    HIP_TRY_AS(c, who, launch_query(p, s, any, st));
+    HIP_TRY_AS(c, who, hipEventRecord(c->query_ev[1], st));
+    c->query_timed = true;
+    c->query_info = srt_query_info{};
+    c->query_info.waves = s.waves; c->query_info.n_cached = (uint32_t)s.n_cached; c->query_info.narrow_refs = s.narrow ? 1u : 0u;
+    c->query_info.all_cached = s.all_cached ? 1u : 0u; c->query_info.paired = s.paired ? 1u : 0u; c->query_info.any = any ? 1u : 0u;
+    return SRT_OK;
+}
+
+// the host entries: rays in, answers out, through the context's staging block on the NULL stream; synchronises
+int query_host(srt_ctx *c, const char *who, const float *rays, size_t n, void *out, bool any) {
+    if (!c) return fail(c, SRT_ERR_INVALID, std::string(who) + ": null ctx");
+    if (const char *why = query_refusal(c, rays, n, out, any, false)) return fail(c, SRT_ERR_INVALID, std::string(who) + ": " + why);
+    if (n == 0) return SRT_OK;
+    HIP_TRY_AS(c, who, set_device(c));
+    const size_t in_bytes = 8 * n * sizeof(float), out_bytes = any ? n : 4 * n * sizeof(float);
+    if (const int rc = develop_reserve(c, who, c->d_query_io, in_bytes + out_bytes)) return rc;
+    HIP_TRY_AS(c, who, hipMemcpy(c->d_query_io.ptr, rays, in_bytes, hipMemcpyHostToDevice));
+    void *d_out = c->d_query_io.as<char>() + in_bytes;      // (in_bytes is a multiple of 32: the answers stay 16-byte aligned)
+    if (const int rc = query_enqueue(c, who, c->d_query_io.as<float>(), n, d_out, any, nullptr)) return rc;
+    HIP_TRY_AS(c, who, device_synchronize(c));
+    HIP_TRY_AS(c, who, hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));
+    return SRT_OK;
+}
+
+// the device entries: the caller's device pointers, on the caller's stream, under the order of the context's calls; no synchronisation
+int query_dev(srt_ctx *c, const char *who, const float *rays_dev, size_t n, void *out_dev, bool any, void *stream) {
+    if (!c) return fail(c, SRT_ERR_INVALID, std::string(who) + ": null ctx");
+    if (const char *why = query_refusal(c, rays_dev, n, out_dev, any, true)) return fail(c, SRT_ERR_INVALID, std::string(who) + ": " + why);
+    if (n == 0) return SRT_OK;
+    HIP_TRY_AS(c, who, set_device(c, (hipStream_t)stream));
+    return query_enqueue(c, who, rays_dev, n, out_dev, any, (hipStream_t)stream);
+}
+
+}  // namespace
+
+int srt_intersect_rays(srt_ctx *c, const float *rays, size_t n, float *hits) { return query_host(c, "srt_intersect_rays", rays, n, hits, false); }
+int srt_occluded_rays(srt_ctx *c, const float *rays, size_t n, uint8_t *occluded) { return query_host(c, "srt_occluded_rays", rays, n, occluded, true); }
+int srt_intersect_rays_dev(srt_ctx *c, const float *rays_dev, size_t n, float *hits_dev, void *query_stream) {
+    return query_dev(c, "srt_intersect_rays_dev", rays_dev, n, hits_dev, false, query_stream);
+}
+int srt_occluded_rays_dev(srt_ctx *c, const float *rays_dev, size_t n, uint8_t *occluded_dev, void *query_stream) {
+    return query_dev(c, "srt_occluded_rays_dev", rays_dev, n, occluded_dev, true, query_stream);
+}
+
+int srt_query_last(srt_ctx *c, srt_query_info *info) {
+    if (!c || !info) return fail(c, SRT_ERR_INVALID, "srt_query_last: null argument");
+    if (!c->query_timed) return fail(c, SRT_ERR_INVALID, "srt_query_last: no query kernel has run on this context");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipEventSynchronize(c->query_ev[1]));
+    *info = c->query_info;
+    HIP_TRY(c, hipEventElapsedTime(&info->ms, c->query_ev[0], c->query_ev[1]));
+    return SRT_OK;
+}
+
+int srt_set_query_test_grid(srt_ctx *c, uint32_t max_waves) {
+    if (!c) return fail(c, SRT_ERR_INVALID, "srt_set_query_test_grid: null ctx");
+    c->query_max_waves = max_waves;
     return SRT_OK;
 }
 

@@ -363,10 +363,14 @@ struct Trav {
 };
 constexpr int kTravDone = -1, kTravIdle = -2;
 
-// Start a closest-hit query (bvh.cu:101-119).  Returns true when the query is already finished (leaf root).
+// Start a closest-hit query (bvh.cu:101-119) over the interval [tmin, tmax].  Returns true when the query is already finished (leaf root).
+// The interval (srt_c_api.h, "Ray queries"): closest_so_far starts at fminf(tmax, FLT_MAX), so tmax = +inf is answered as FLT_MAX; tmin takes
+// the place of the literal 0 in the box and triangle tests (box_pair, trav_fringe_compute).  The renderer's callers pass the literals 0.0f
+// and kFltMax, which folds every added operation away: their machine code is the one without the arguments.
 template <bool COUNT>
-__device__ __forceinline__ bool trav_begin(Trav &tv, uint32_t stack_base, const float4 *__restrict__ tris, int root_ref, V3 o, V3 d, TravStats &ts) {
-    tv.c = kFltMax; tv.hit = -1; tv.sp = stack_base; tv.top = -1;
+__device__ __forceinline__ bool trav_begin(Trav &tv, uint32_t stack_base, const float4 *__restrict__ tris, int root_ref, V3 o, V3 d, float tmin, float tmax,
+                                           TravStats &ts) {
+    tv.c = fminf(tmax, kFltMax); tv.hit = -1; tv.sp = stack_base; tv.top = -1;
     // A direction with a NaN component can never hit anything: every product with it is NaN (0*NaN included), so
     // dot(n, dir) is NaN, `fabs(denom) < 1e-8` is false, t = x/NaN is NaN and `0 <= t` is false for EVERY triangle
     // (tri.cu:12-23), while every box test passes (all comparisons false, aabb.cu:30-36).  The reference therefore
@@ -377,10 +381,16 @@ __device__ __forceinline__ bool trav_begin(Trav &tv, uint32_t stack_base, const 
         tv.node = kTravDone;
         return true;
     }
+    // an empty interval (tmin > tmax) or a NaN bound accepts nothing: tmin <= t <= c <= tmax needs tmin <= tmax, and a NaN tmax would turn
+    // into c = FLT_MAX above -- the query is a miss without walking
+    if (!(tmin <= tmax)) {
+        tv.node = kTravDone;
+        return true;
+    }
     if (root_ref < 0) {   // root is a leaf: only one element
         float t;
         if (COUNT) ts.n_tri++;
-        if (tri_test(tris, ~root_ref, o, d, 0.0f, tv.c, t)) { tv.c = t; tv.hit = ~root_ref; }
+        if (tri_test(tris, ~root_ref, o, d, tmin, tv.c, t)) { tv.c = t; tv.hit = ~root_ref; }
         tv.node = kTravDone;
         return true;
     }
@@ -511,11 +521,11 @@ __device__ __forceinline__ void stack_init(const StackRef &st) {
 // The reference's per-axis early-outs are equivalent to this single final test because its running min only grows
 // and its running max only shrinks; NaN t0/t1 are ignored by both forms (comparisons false / fmaxf,fminf return the
 // other operand).
-__device__ __forceinline__ void box_pair(const BoxPairs &b, V3 o, V3 inv, float &e_l, float &m_l, float &e_r, float &m_r) {
+__device__ __forceinline__ void box_pair(const BoxPairs &b, V3 o, V3 inv, float tmin, float &e_l, float &m_l, float &e_r, float &m_r) {
     const f2 t0x = (b.nx - o.x) * inv.x, t1x = (b.fx - o.x) * inv.x;
     const f2 t0y = (b.ny - o.y) * inv.y, t1y = (b.fy - o.y) * inv.y;
     const f2 t0z = (b.nz - o.z) * inv.z, t1z = (b.fz - o.z) * inv.z;
-    e_l = fmaxf(fmaxf(fmaxf(0.0f, t0x.x), t0y.x), t0z.x); e_r = fmaxf(fmaxf(fmaxf(0.0f, t0x.y), t0y.y), t0z.y);
+    e_l = fmaxf(fmaxf(fmaxf(tmin, t0x.x), t0y.x), t0z.x); e_r = fmaxf(fmaxf(fmaxf(tmin, t0x.y), t0y.y), t0z.y);
     // min(c, t1x, t1y, t1z) = min(c, m) with m = min over the non-NaN t1 (fminf ignores NaNs in any order)
     m_l = fminf(fminf(t1x.x, t1y.x), t1z.x); m_r = fminf(fminf(t1x.y, t1y.y), t1z.y);
 }
@@ -556,7 +566,7 @@ __device__ __forceinline__ void trav_advance(Trav &tv, bool trav_l, bool trav_r,
 // Visit of an INNER record (both children internal): two box tests, no triangle work.  ALL_CACHED: the whole inner tree is
 // LDS resident (n_cached == n_inner), no global fall-back path in the step.
 template <bool COUNT, bool NARROW, bool ALL_CACHED>
-__device__ __forceinline__ void trav_step_inner(Trav &tv, const NodeSrc &ns, V3 o, V3 inv, const StackRef &stack, TravStats &ts) {
+__device__ __forceinline__ void trav_step_inner(Trav &tv, const NodeSrc &ns, V3 o, V3 inv, float tmin, const StackRef &stack, TravStats &ts) {
     BoxPairs b;
     int lref, rref;
     const int below = stack_exchange<NARROW>(tv.sp, tv.top);
@@ -574,7 +584,7 @@ __device__ __forceinline__ void trav_step_inner(Trav &tv, const NodeSrc &ns, V3 
     }
     if (COUNT) { ts.n_iters++; ts.n_box += 2u; }
     float e_l, m_l, e_r, m_r;
-    box_pair(b, o, inv, e_l, m_l, e_r, m_r);
+    box_pair(b, o, inv, tmin, e_l, m_l, e_r, m_r);
     const float c = tv.c;
     const bool trav_l = !(fminf(c, m_l) <= e_l);
     const bool trav_r = !(fminf(c, m_r) <= e_r);
@@ -925,7 +935,7 @@ __device__ __forceinline__ void trav_fringe_fetch(FringeFetch &ff, const Trav &t
 // holds two triangles: the slab test of "the internal child" and the descent into it -- a fifth of the visit's instructions, needed by
 // 5-9 % of the FRINGE visits of an unpaired tree -- are not compiled in, and the visit always ends with a pop.
 template <bool COUNT, bool NARROW, bool PAIRED = false>
-__device__ __forceinline__ void trav_fringe_compute(const FringeFetch &ff, Trav &tv, V3 o, V3 d, V3 inv, TravStats &ts) {
+__device__ __forceinline__ void trav_fringe_compute(const FringeFetch &ff, Trav &tv, V3 o, V3 d, V3 inv, float tmin, TravStats &ts) {
     const f4v q0 = ff.q0, q1 = ff.q1, q2 = ff.q2, q3 = ff.q3, q4 = ff.q4, q5 = ff.q5;
     const int below = ff.below;
     const f2 w0 = mk2(q0.x, q0.y), w1 = mk2(q0.z, q0.w), w2 = mk2(q1.x, q1.y), w3 = mk2(q1.z, q1.w), w4 = mk2(q2.x, q2.y), w5 = mk2(q2.z, q2.w);
@@ -948,7 +958,7 @@ __device__ __forceinline__ void trav_fringe_compute(const FringeFetch &ff, Trav 
         const float t0x = ((px ? xlo : xhi) - o.x) * inv.x, t1x = ((px ? xhi : xlo) - o.x) * inv.x;
         const float t0y = ((py ? ylo : yhi) - o.y) * inv.y, t1y = ((py ? yhi : ylo) - o.y) * inv.y;
         const float t0z = ((pz ? zlo : zhi) - o.z) * inv.z, t1z = ((pz ? zhi : zlo) - o.z) * inv.z;
-        e_box = fmaxf(fmaxf(fmaxf(0.0f, t0x), t0y), t0z);
+        e_box = fmaxf(fmaxf(fmaxf(tmin, t0x), t0y), t0z);
         m_box = fminf(fminf(t1x, t1y), t1z);
     }
 
@@ -978,8 +988,8 @@ __device__ __forceinline__ void trav_fringe_compute(const FringeFetch &ff, Trav 
     const bool in_l = inside_min3(m_l, a3.x, sl);
     const bool in_r = inside_min3(m_r, a3.y, sr);
     // plane not parallel, t >= tmin, inside (everything but `t <= c`)
-    const bool ok_l = leaf_l & !(fabsf(denom.x) < 1e-8f) & (0.0f <= t.x) & in_l;
-    const bool ok_r = leaf_r & !(fabsf(denom.y) < 1e-8f) & (0.0f <= t.y) & in_r;
+    const bool ok_l = leaf_l & !(fabsf(denom.x) < 1e-8f) & (tmin <= t.x) & in_l;
+    const bool ok_r = leaf_r & !(fabsf(denom.y) < 1e-8f) & (tmin <= t.y) & in_r;
 
     // ---- decisions in the reference's order (bvh.cu:128-160): left child with c, right child with the updated c -----------
     const float c0 = tv.c;
@@ -1006,10 +1016,10 @@ __device__ __forceinline__ void trav_fringe_compute(const FringeFetch &ff, Trav 
     tv.sp += (uint32_t)(go ? 0 : -kStackStride<NARROW>);
 }
 template <bool COUNT, bool NARROW, bool PAIRED = false>
-__device__ __forceinline__ void trav_step_fringe(Trav &tv, const NodeSrc &ns, V3 o, V3 d, V3 inv, const StackRef &stack, TravStats &ts) {
+__device__ __forceinline__ void trav_step_fringe(Trav &tv, const NodeSrc &ns, V3 o, V3 d, V3 inv, float tmin, const StackRef &stack, TravStats &ts) {
     FringeFetch ff;
     trav_fringe_fetch<NARROW>(ff, tv, ns, stack);
-    trav_fringe_compute<COUNT, NARROW, PAIRED>(ff, tv, o, d, inv, ts);
+    trav_fringe_compute<COUNT, NARROW, PAIRED>(ff, tv, o, d, inv, tmin, ts);
 }
 
 

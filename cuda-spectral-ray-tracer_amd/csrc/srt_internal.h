@@ -494,6 +494,20 @@ struct MotionParams {
     unsigned long long *counts;
 };
 hipError_t launch_motion(const MotionParams &p, hipStream_t st);
+// Batched ray queries (srt_query.hip; stated in srt_c_api.h at "Ray queries").  rays: two float4 per ray, (o, tmin) (d, tmax); the closest
+// query writes hits[k] = (t, tri or -1, front_face, mat) as srt_trace_rays does, the any query occluded[k] = 0 / 1.  counter: one 32-bit word,
+// zero when the kernel starts (the caller clears it on the same stream).  Scene fields: RenderParams'; n_cached: the plan's.
+struct QueryParams {
+    const float4 *nodes, *fringe, *tris;
+    int root_ref, stack_depth, n_inner, n_cached, n_records;
+    uint32_t fringe_stride;
+    uint32_t score_fringe;      // step choice: FRINGE lanes x score_fringe against INNER lanes x 256 (RenderParams')
+    const float4 *rays;
+    uint32_t n;
+    uint32_t *counter;
+    float4 *hits;
+    uint8_t *occluded;
+};
 // BVH refit (srt_refit.hip; stated in srt_c_api.h at srt_scene_refit and srt_refit_vertices).  verts: 9 floats per triangle.  The topology
 // tables, made on the host at srt_upload_scene: tri_tab two words per triangle -- its raw aa_plane, then its slot 2 f + side, the FRINGE
 // record f (an index into the FRINGE image) and the side whose block holds the triangle's copy, kRefitNoSlot when the root is a leaf; child
@@ -558,5 +572,12 @@ void render_launch_plan(int stack_depth, int n_records, int n_inner, const PlanK
 // waves_per_cu_override: RenderParams' experiment knob.  The launcher and whoever sizes a per-wave buffer both ask this function.
 struct RenderGrid { int waves_per_block; uint32_t n_blocks, waves; };
 RenderGrid render_launch_grid(const LaunchPlan &lp, uint32_t n_cu, uint32_t waves_per_cu_override, uint32_t queue_rows_bound);
+// The launch of n ray queries (QueryParams) for a plan (render_launch_plan's; narrow / paired: render_narrow_refs / render_paired_variant):
+// persistent workgroups of the plan's waves, every CU filled (n_cu x waves_per_cu), never more waves than rays / 64 rounded up or max_waves
+// (> 0: the test grid, srt_set_query_test_grid).  lds: the inner-record cache and one stack per wave, without the render workgroup's tables.
+struct QueryShape { bool narrow, all_cached, paired; int n_cached; uint32_t waves_per_block, n_blocks, waves; size_t lds; };
+QueryShape query_shape(const LaunchPlan &lp, bool narrow, bool paired, int stack_depth, int n_records, const PlanKnobs &knobs, uint32_t n_cu,
+                       uint32_t max_waves, size_t n_rays);
+hipError_t launch_query(const QueryParams &p, const QueryShape &s, bool any, hipStream_t st);
 
 }  // namespace srt

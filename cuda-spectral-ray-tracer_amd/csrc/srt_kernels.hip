@@ -813,7 +813,7 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
                 n_rays++;
                 inv = mk(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z);           // aabb.cu:17, hoisted out of the box test
                 ray_near_addresses(ns, inv, tv.nf);
-                (void)trav_begin<ITERS>(tv, stack_base<NARROW>(my_stack), P.tris, P.root_ref, ro, rd, ts);   // a query that finishes at once leaves kTravDone
+                (void)trav_begin<ITERS>(tv, stack_base<NARROW>(my_stack), P.tris, P.root_ref, ro, rd, 0.0f, kFltMax, ts);   // a query that finishes at once leaves kTravDone
             }
         }
 
@@ -832,8 +832,8 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
             // step-choice logic is on the critical path of the pixel that bounds a chain-bound launch.
             while (__ballot(tv.node >= 0) != 0ull) {
                 if (tv.node >= 0) {
-                    if ((uint32_t)tv.node < n_inner_u) trav_step_inner<ITERS, NARROW, ALL_CACHED>(tv, ns, ro, inv, my_stack, ts);
-                    else trav_step_fringe<ITERS, NARROW, PAIRED>(tv, ns, ro, rd, inv, my_stack, ts);
+                    if ((uint32_t)tv.node < n_inner_u) trav_step_inner<ITERS, NARROW, ALL_CACHED>(tv, ns, ro, inv, 0.0f, my_stack, ts);
+                    else trav_step_fringe<ITERS, NARROW, PAIRED>(tv, ns, ro, rd, inv, 0.0f, my_stack, ts);
                 }
             }
             continue;
@@ -842,7 +842,7 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
             // production build: the decision below and the INNER bursts it leads to are one assembly block (inner_phase_asm,
             // srt_device.h -- the same arithmetic); only the FRINGE visits come back here
             while (inner_phase_asm(tv, ns, ro, inv, n_inner_u, n_alive, w_shade, w_fringe) != 0u) {
-                if (tv.node >= (int)n_inner_u) trav_step_fringe<ITERS, NARROW, PAIRED>(tv, ns, ro, rd, inv, my_stack, ts);
+                if (tv.node >= (int)n_inner_u) trav_step_fringe<ITERS, NARROW, PAIRED>(tv, ns, ro, rd, inv, 0.0f, my_stack, ts);
             }
         } else
         for (;;) {
@@ -861,7 +861,7 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
             const bool do_fringe = s_fr > s_in;
             if (COUNT) { ts.w_iters++; ts.w_alive += n_alive; if (do_fringe) { ts.w_fringe++; ts.l_fringe += n_fringe; } else ts.l_inner += n_trav - n_fringe; }
             if (do_fringe) {
-                if (tv.node >= (int)n_inner_u) trav_step_fringe<ITERS, NARROW, PAIRED>(tv, ns, ro, rd, inv, my_stack, ts);
+                if (tv.node >= (int)n_inner_u) trav_step_fringe<ITERS, NARROW, PAIRED>(tv, ns, ro, rd, inv, 0.0f, my_stack, ts);
                 if (COUNT) { const unsigned long long now = __builtin_amdgcn_s_memtime(); t_fringe += now - t_mark; t_mark = now; }
             } else {
                 // a short burst of inner steps between two scheduling decisions: the ballots / popcounts of the loop head
@@ -880,7 +880,7 @@ __global__ __launch_bounds__(1024) void render_kernel(const RenderParams P) {
                 } else
 #pragma unroll
                 for (int burst = 0; burst < burst_len; burst++) {
-                    if (at_inner) trav_step_inner<ITERS, NARROW, ALL_CACHED>(tv, ns, ro, inv, my_stack, ts);
+                    if (at_inner) trav_step_inner<ITERS, NARROW, ALL_CACHED>(tv, ns, ro, inv, 0.0f, my_stack, ts);
                     at_inner = (uint32_t)tv.node < n_inner_u;
                     const unsigned long long m = __ballot(at_inner);
                     if (COUNT && burst > 0) { ts.w_iters++; ts.w_alive += n_alive; }
@@ -1118,7 +1118,7 @@ __global__ __launch_bounds__(64) void trace_rays_kernel(const RenderParams P, co
     const V3 inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
     StackRef my_stack; my_stack.s16 = nullptr; my_stack.s32 = (lds_i32 *)s_stack + lane;
     stack_init<false>(my_stack);
-    if (active) trav_begin<false>(tv, stack_base<false>(my_stack), P.tris, P.root_ref, o, d, ts);
+    if (active) trav_begin<false>(tv, stack_base<false>(my_stack), P.tris, P.root_ref, o, d, 0.0f, kFltMax, ts);
     NodeSrc ns;
     ns.global_nodes = make_rsrc(P.nodes, (uint32_t)P.n_inner * 64u);
     ns.global_fringe = make_rsrc(P.fringe, (uint32_t)(P.n_records - P.n_inner) * P.fringe_stride);
@@ -1127,8 +1127,8 @@ __global__ __launch_bounds__(64) void trace_rays_kernel(const RenderParams P, co
     ns.n_inner = P.n_inner;
     ns.lds_q0 = ns.lds_q1 = ns.lds_q2 = nullptr; ns.lds_r0 = ns.lds_r1 = nullptr; ns.n_cached = 0;
     while (__ballot(tv.node >= 0) != 0ull) {
-        if (tv.node >= P.n_inner) trav_step_fringe<false, false>(tv, ns, o, d, inv, my_stack, ts);
-        else if (tv.node >= 0) trav_step_inner<false, false, false>(tv, ns, o, inv, my_stack, ts);   // n_cached = 0: global records
+        if (tv.node >= P.n_inner) trav_step_fringe<false, false>(tv, ns, o, d, inv, 0.0f, my_stack, ts);
+        else if (tv.node >= 0) trav_step_inner<false, false, false>(tv, ns, o, inv, 0.0f, my_stack, ts);   // n_cached = 0: global records
     }
     const float t = tv.c;
     const int tri = tv.hit;

@@ -60,7 +60,7 @@ __global__ __launch_bounds__(kMoThreads) void motion_kernel(const MotionParams P
     // this wave's stack region, this lane's column of it
     StackRef my_stack; my_stack.s16 = nullptr; my_stack.s32 = (lds_i32 *)s_stack + (size_t)wv * P.stack_slots * 64u + lane;
     stack_init<false>(my_stack);
-    if (active) trav_begin<false>(tv, stack_base<false>(my_stack), P.tris, P.root_ref, o, d, ts);
+    if (active) trav_begin<false>(tv, stack_base<false>(my_stack), P.tris, P.root_ref, o, d, 0.0f, kFltMax, ts);
     NodeSrc ns;
     ns.global_nodes = make_rsrc(P.nodes, (uint32_t)P.n_inner * 64u);
     ns.global_fringe = make_rsrc(P.fringe, (uint32_t)(P.n_records - P.n_inner) * P.fringe_stride);
@@ -69,8 +69,8 @@ __global__ __launch_bounds__(kMoThreads) void motion_kernel(const MotionParams P
     ns.n_inner = P.n_inner;
     ns.lds_q0 = ns.lds_q1 = ns.lds_q2 = nullptr; ns.lds_r0 = ns.lds_r1 = nullptr; ns.n_cached = 0;
     while (__ballot(tv.node >= 0) != 0ull) {
-        if (tv.node >= P.n_inner) trav_step_fringe<false, false>(tv, ns, o, d, inv, my_stack, ts);
-        else if (tv.node >= 0) trav_step_inner<false, false, false>(tv, ns, o, inv, my_stack, ts);   // n_cached = 0: global records
+        if (tv.node >= P.n_inner) trav_step_fringe<false, false>(tv, ns, o, d, inv, 0.0f, my_stack, ts);
+        else if (tv.node >= 0) trav_step_inner<false, false, false>(tv, ns, o, inv, 0.0f, my_stack, ts);   // n_cached = 0: global records
     }
     uint32_t n[kMoCounters] = {0u, 0u, 0u, 0u};
     if (active) {

@@ -19,6 +19,39 @@ def reference_grid(chunk_w, chunk_h, tx=DEFAULT_TX, ty=DEFAULT_TY):
     return chunk_w // tx + 1, chunk_h // ty + 1
 
 
+FLT_MAX = float(np.finfo(np.float32).max)
+
+
+def ray_batch(origins, directions, tmin=0.0, tmax=None):
+    """The (n, 8) float32 rows of the ray queries (Renderer.intersect / occluded): ox oy oz tmin dx dy dz tmax.  origins and directions
+    (n, 3) -- or one origin (3,) for all --, tmin and tmax scalars or n values; tmax None means FLT_MAX.  numpy inputs give a numpy array, a
+    torch tensor among origins / directions gives a tensor on its device."""
+    if tmax is None:
+        tmax = FLT_MAX
+    tensor = next((a for a in (origins, directions) if not isinstance(a, np.ndarray) and hasattr(a, "data_ptr")), None)
+    if tensor is not None:
+        import torch
+        dev = tensor.device
+        d = torch.as_tensor(directions, dtype=torch.float32, device=dev)
+        if d.dim() != 2 or d.shape[1] != 3:
+            raise ValueError("ray_batch: directions must have shape (n, 3), got %r" % (tuple(d.shape),))
+        rows = torch.empty((d.shape[0], 8), dtype=torch.float32, device=dev)
+        rows[:, 0:3] = torch.as_tensor(origins, dtype=torch.float32, device=dev)
+        rows[:, 3] = torch.as_tensor(tmin, dtype=torch.float32, device=dev)
+        rows[:, 4:7] = d
+        rows[:, 7] = torch.as_tensor(tmax, dtype=torch.float32, device=dev)
+        return rows
+    d = np.asarray(directions, np.float32)
+    if d.ndim != 2 or d.shape[1] != 3:
+        raise ValueError("ray_batch: directions must have shape (n, 3), got %r" % (d.shape,))
+    rows = np.empty((d.shape[0], 8), np.float32)
+    rows[:, 0:3] = np.asarray(origins, np.float32)
+    rows[:, 3] = np.asarray(tmin, np.float32)
+    rows[:, 4:7] = d
+    rows[:, 7] = np.asarray(tmax, np.float32)
+    return rows
+
+
 class Renderer:
     def __init__(self, device=0, _borrowed=None):
         if _borrowed is not None:            # a context owned by a communicator (srt_comm_init_all)
@@ -1044,6 +1077,75 @@ class Renderer:
         out = np.zeros((rays.shape[0], 4), np.float32)
         self._ck(B.lib().srt_trace_rays(self._h, B.fptr(rays), rays.shape[0], B.fptr(out)))
         return out
+
+    def _query_rays(self, who, rays):
+        """('host', float32 (n, 8) C-contiguous array) or ('dev', tensor) for the query entries; every check before the device is touched"""
+        if isinstance(rays, np.ndarray):
+            if rays.dtype != np.float32:
+                raise TypeError("%s: the rays must be float32, got %s" % (who, rays.dtype))
+            if rays.ndim != 2 or rays.shape[1] != 8:
+                raise ValueError("%s: the rays must have shape (n, 8) -- ox oy oz tmin dx dy dz tmax --, got %r" % (who, rays.shape))
+            if rays.shape[0] > B.QUERY_MAX_RAYS:
+                raise ValueError("%s: %d rays do not fit the ray counter (at most %d)" % (who, rays.shape[0], B.QUERY_MAX_RAYS))
+            return "host", np.ascontiguousarray(rays)
+        t = rays
+        if not all(hasattr(t, a) for a in ("data_ptr", "is_contiguous", "device", "dtype", "shape")):
+            raise TypeError("%s: the rays must be a numpy array or a torch tensor (n, 8) float32, got %r" % (who, type(t).__name__))
+        import torch
+        if t.dtype != torch.float32:
+            raise TypeError("%s: the tensor must be float32, got %s" % (who, t.dtype))
+        if t.dim() != 2 or t.shape[1] != 8:
+            raise ValueError("%s: the tensor must have shape (n, 8) -- ox oy oz tmin dx dy dz tmax --, got %r" % (who, tuple(t.shape)))
+        if t.shape[0] > B.QUERY_MAX_RAYS:
+            raise ValueError("%s: %d rays do not fit the ray counter (at most %d)" % (who, t.shape[0], B.QUERY_MAX_RAYS))
+        if not t.is_contiguous():
+            raise ValueError("%s: the tensor must be contiguous" % who)
+        if t.shape[0] > 0 and t.data_ptr() % 16:
+            raise ValueError("%s: the tensor's data must be 16-byte aligned (a row is two 16-byte loads)" % who)
+        if t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != self.device:
+            raise ValueError("%s: the tensor lives on %s, the renderer on GPU %d" % (who, t.device, self.device))
+        return "dev", t
+
+    def intersect(self, rays):
+        """closest hits over each ray's interval (srt_intersect_rays / srt_intersect_rays_dev): rays (n, 8) float32 rows ox oy oz tmin dx dy dz
+        tmax (ray_batch makes them).  A numpy array goes through the host entry and gives numpy (n, 4) float32 rows in trace_rays' layout --
+        t (0 on a miss), tri or -1, front_face, mat_index.  A contiguous, 16-byte aligned float32 CUDA tensor on this renderer's device goes
+        through the device entry on torch.cuda.current_stream(), without a host synchronisation, and gives a tensor."""
+        kind, r = self._query_rays("Renderer.intersect", rays)
+        if kind == "host":
+            out = np.zeros((r.shape[0], 4), np.float32)
+            self._ck(B.lib().srt_intersect_rays(self._h, B.fptr(r), r.shape[0], B.fptr(out)))
+            return out
+        import torch
+        out = torch.empty((r.shape[0], 4), dtype=torch.float32, device=r.device)
+        stream = torch.cuda.current_stream(r.device).cuda_stream
+        self._ck(B.lib().srt_intersect_rays_dev(self._h, C.c_void_p(r.data_ptr()), r.shape[0], C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+        return out
+
+    def occluded(self, rays):
+        """any-hit occlusion over each ray's interval (srt_occluded_rays / srt_occluded_rays_dev): True where [tmin, tmax] holds a hit.  The
+        rays and the two paths as in intersect; the answer is a bool numpy array or a bool tensor of n entries."""
+        kind, r = self._query_rays("Renderer.occluded", rays)
+        if kind == "host":
+            out = np.zeros(r.shape[0], np.uint8)
+            self._ck(B.lib().srt_occluded_rays(self._h, B.fptr(r), r.shape[0], out.ctypes.data_as(C.POINTER(C.c_uint8))))
+            return out.astype(bool)
+        import torch
+        out = torch.empty(r.shape[0], dtype=torch.bool, device=r.device)      # (one byte per entry: the kernel writes 0 / 1)
+        stream = torch.cuda.current_stream(r.device).cuda_stream
+        self._ck(B.lib().srt_occluded_rays_dev(self._h, C.c_void_p(r.data_ptr()), r.shape[0], C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+        return out
+
+    def query_last(self):
+        """the last ray-query launch (srt_query_last): dict(ms, waves, n_cached, narrow_refs, all_cached, paired, any); waits for that kernel"""
+        q = B.QueryInfo()
+        self._ck(B.lib().srt_query_last(self._h, C.byref(q)))
+        return dict(ms=q.ms, waves=q.waves, n_cached=q.n_cached, narrow_refs=bool(q.narrow_refs), all_cached=bool(q.all_cached),
+                    paired=bool(q.paired), any=bool(q.any))
+
+    def set_query_test_grid(self, max_waves=0):
+        """tests / tools only (srt_set_query_test_grid): at most max_waves persistent waves per query launch; 0 fills the device"""
+        self._ck(B.lib().srt_set_query_test_grid(self._h, int(max_waves)))
 
     def op_sweep(self, which, a, b):
         a = np.ascontiguousarray(a, np.float32); b = np.ascontiguousarray(b, np.float32)

@@ -303,7 +303,8 @@ SRT_API int srt_set_partition(srt_ctx *ctx, uint32_t rank, uint32_t world);
  *
  * Order of a context's calls.  A context's calls take effect in the order they were made, whichever streams they name.  A stream
  * handed to a call must stay valid until the next call on that context that synchronises.
- * The calls that take a stream are srt_render_chunk, srt_render_chunk_accum, srt_copy_tile_buffer, srt_scatter_tiles, srt_pack_accum and srt_unpack_accum; every other
+ * The calls that take a stream are srt_render_chunk, srt_render_chunk_accum, srt_copy_tile_buffer, srt_scatter_tiles, the ray queries'
+ * device entries (srt_intersect_rays_dev, srt_occluded_rays_dev), srt_pack_accum and srt_unpack_accum; every other
  * call works on the NULL stream.  The context remembers the stream of the work it enqueued last: a call that enqueues on another
  * stream -- the NULL stream included, and a hipStreamNonBlocking stream as well as a blocking one -- first makes its stream wait for
  * an event recorded behind that work, so a pass on one stream may be followed at once by a pass on another, a reset, a stage or a
@@ -311,7 +312,7 @@ SRT_API int srt_set_partition(srt_ctx *ctx, uint32_t rank, uint32_t world);
  * context in flight on any stream, and the remembered stream is not touched again after them, so it may be destroyed -- are
  * srt_synchronize; every read-back (srt_read_fb, srt_read_fb_aux, srt_read_fb_rowmajor, srt_read_accum_stats, srt_read_spectral,
  * srt_read_features, srt_accum_active on a bound accumulation, srt_get_stats, srt_get_tile_costs, srt_get_wave_debug,
- * srt_read_tile_schedule, srt_read_scene_image); srt_refit_vertices and srt_refit_vertices_dev; every stage call that returns host data (srt_meter_*, srt_expose_*, srt_develop_*, srt_despeckle_*,
+ * srt_read_tile_schedule, srt_read_scene_image); srt_refit_vertices and srt_refit_vertices_dev; srt_intersect_rays and srt_occluded_rays; every stage call that returns host data (srt_meter_*, srt_expose_*, srt_develop_*, srt_despeckle_*,
  * srt_temporal_*, srt_denoise_*, srt_present* -- not their *_last_ms timing queries, which wait for their own events alone);
  * srt_init_device_params and every srt_accum_reset*.  srt_comm_synchronize waits for the
  * communicator's own streams only and is none of them; srt_comm_destroy synchronises every context before it destroys those streams.
@@ -1392,6 +1393,47 @@ SRT_API int srt_last_kernel_ms(srt_ctx *ctx, float *ms);
 /* Closest-hit query for explicit rays (bvh::hit, bvh/bvh.cu:98-166) -- KAT entry point.
  * rays: n * 6 floats (origin, direction); out: n * 4 floats (t, tri_index or -1, front_face, mat_index). */
 SRT_API int srt_trace_rays(srt_ctx *ctx, const float *rays, size_t n, float *out);
+/* Ray queries (no reference counterpart): batched closest-hit and any-hit queries over an interval of t, in one persistent kernel
+ * (srt_query.hip) in the shape of the scene's render launch plan -- the inner records the plan caches in LDS, 16- or 32-bit references,
+ * the PAIRED variant where srt_launch_paired says so; the test knobs apply.
+ *   Ray row.  rays[n][8] = ox, oy, oz, tmin, dx, dy, dz, tmax (float32; t in units of |d|, as everywhere).
+ *   The query is bvh::hit of srt_trace_rays with the interval as arguments, operation by operation (c = closest so far, m = min(t1x, t1y,
+ * t1z) and t0x .. t0z the slab entries of a child box, t and inside exactly what srt_trace_rays computes for a triangle):
+ *     start            c = fminf(tmax, FLT_MAX): tmax = +inf is answered exactly as FLT_MAX.
+ *     box passes       !(fminf(c, m) <= max(tmin, t0x, t0y, t0z)).
+ *     triangle accepted  !(|n.d| < 1e-8) && tmin <= t && t <= c && inside; c = t.
+ *     visit order      left child, then right with the updated c; push right when both pass -- as srt_trace_rays.  A tree whose root is a
+ *                      leaf tests that triangle with the same interval.
+ *     closest query    runs to the end: with [0, FLT_MAX] (or [0, +inf]) its answer is srt_trace_rays' word for word.
+ *     any query        stops after the first traversal step that accepted a triangle.  Up to that step it made the closest query's visits,
+ *                      so occluded == (the closest query's tri >= 0) for every ray and every interval.
+ *     special inputs   a direction with a NaN component is a miss (as srt_trace_rays); a NaN tmin or tmax, or tmin > tmax, accepts
+ *                      nothing: a miss.  A negative tmin lets the query accept crossings behind the origin.
+ *   A ray's answer depends on the ray and the tree alone, never on the order in which the kernel's lanes and waves take the rays.
+ *   srt_intersect_rays      host arrays; hits[n][4] in srt_trace_rays' layout: t (0 on a miss), tri or -1, front_face, mat_index.
+ *   srt_occluded_rays       host arrays; occluded[n] = 1 when the interval holds a hit, else 0.  Both host entries copy through a staging
+ *                           block of the context on the NULL stream and synchronise.
+ *   srt_intersect_rays_dev / srt_occluded_rays_dev  device pointers and a hipStream_t passed as void* (NULL = the NULL stream), under the
+ *                           order of a context's calls (srt_render_chunk): the counter reset and the kernel are enqueued on that stream,
+ *                           nothing synchronises.  rays_dev must stay valid and unchanged, and the answers are complete, once that stream
+ *                           reaches them.
+ *   Refused with SRT_ERR_INVALID, nothing enqueued or written: a null ctx, no scene uploaded (srt_set_test_knobs ends an upload too), a null
+ *   rays or output pointer with n > 0, a device rays / hits pointer that is not 16-byte aligned, n > SRT_QUERY_MAX_RAYS (the kernel's
+ *   32-bit ray counter).  n = 0 succeeds and touches nothing.  A failed allocation: SRT_ERR_HIP.  After srt_refit_vertices* the queries see
+ *   the refitted images.
+ *   srt_query_last          the last query launch of the context: kernel-only ms from HIP events (waits for that kernel alone), the
+ *                           persistent waves launched, the inner records cached in LDS, the variant (narrow_refs, all_cached, paired) and
+ *                           whether it was the any query.  SRT_ERR_INVALID before one ran.
+ *   srt_set_query_test_grid TEST HOOK (tests and tools only, like srt_set_test_knobs): at most max_waves persistent waves per launch (whole
+ *                           workgroups of at most the plan's size); 0 = fill the device (the default). */
+#define SRT_QUERY_MAX_RAYS 0x7fffffffu
+typedef struct srt_query_info { float ms; uint32_t waves, n_cached, narrow_refs, all_cached, paired, any, reserved; } srt_query_info;
+SRT_API int srt_intersect_rays(srt_ctx *ctx, const float *rays, size_t n, float *hits);
+SRT_API int srt_occluded_rays(srt_ctx *ctx, const float *rays, size_t n, uint8_t *occluded);
+SRT_API int srt_intersect_rays_dev(srt_ctx *ctx, const float *rays_dev, size_t n, float *hits_dev, void *query_stream);
+SRT_API int srt_occluded_rays_dev(srt_ctx *ctx, const float *rays_dev, size_t n, uint8_t *occluded_dev, void *query_stream);
+SRT_API int srt_query_last(srt_ctx *ctx, srt_query_info *info);
+SRT_API int srt_set_query_test_grid(srt_ctx *ctx, uint32_t max_waves);
 /* Device arithmetic self-test: evaluates op `which` on n operand pairs on the GPU (see DESIGN.md "primitive-op
  * sweep"); used to prove the device's + - * / sqrt fmin cast and srt_powf bits equal the host's. */
 SRT_API int srt_device_op_sweep(srt_ctx *ctx, int which, const float *a, const float *b, size_t n, float *out);
