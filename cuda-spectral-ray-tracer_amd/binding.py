@@ -161,6 +161,29 @@ class QueryInfo(C.Structure):
 
 QUERY_MAX_RAYS = 0x7fffffff      # SRT_QUERY_MAX_RAYS (srt_c_api.h)
 
+
+class Light(C.Structure):
+    """srt_light: samples, first sample index, parts (LIGHT_PARTS bits) and seed of a direct-light call (srt_c_api.h)"""
+    _fields_ = [("samples", C.c_uint32), ("first_sample", C.c_uint32), ("parts", C.c_uint32), ("reserved", C.c_uint32), ("seed", C.c_uint64)]
+
+
+class LightResult(C.Structure):
+    """srt_light_result: the sample counters of a direct-light call and the lights in the table (srt_c_api.h)"""
+    _fields_ = [("miss", C.c_uint64), ("emitted", C.c_uint64), ("specular", C.c_uint64), ("shaded", C.c_uint64), ("light_rows", C.c_uint64),
+                ("light_unoccluded", C.c_uint64), ("sky_rows", C.c_uint64), ("sky_unoccluded", C.c_uint64), ("lights", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class LightInfo(C.Structure):
+    """srt_light_info: kernel ms of the last direct-light call by kind, its rounds, rows per round and query launches (srt_c_api.h)"""
+    _fields_ = [("camera_ms", C.c_float), ("shade_ms", C.c_float), ("gather_ms", C.c_float), ("query_ms", C.c_float), ("rounds", C.c_uint32),
+                ("rows_per_round", C.c_uint32), ("query_launches", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+LIGHT_PARTS = {"emitted": 1, "lights": 2, "sky": 4}      # SRT_LIGHT_* (srt_c_api.h)
+LIGHT_MAX_SAMPLES = 65536                                 # SRT_LIGHT_MAX_SAMPLES
+assert C.sizeof(Light) == 24 and C.sizeof(LightResult) == 72 and C.sizeof(LightInfo) == 32
+
 assert C.sizeof(QueryInfo) == 32
 assert C.sizeof(Denoise) == 32 and C.sizeof(DenoiseVG) == 32
 assert C.sizeof(Meter) == 48 and C.sizeof(MeterResult) == 40 and C.sizeof(Tone) == 32 and C.sizeof(ToneResult) == 24
@@ -333,6 +356,12 @@ PROTOTYPES = {
     "srt_occluded_rays_dev": (_i, [_vp, _vp, _sz, _vp, _vp]),
     "srt_query_last": (_i, [_vp, C.POINTER(QueryInfo)]),
     "srt_set_query_test_grid": (_i, [_vp, _u32]),
+    "srt_direct_light": (_i, [_vp, C.POINTER(Light), _fp, _fp, C.POINTER(LightResult), _u32, _u32, _u32, _u32]),
+    "srt_direct_light_kat": (_i, [_vp, C.POINTER(Light), _fp, _fp, C.POINTER(LightResult), _u32, _u32, _u32, _u32, _fp, _fp, _fp, _fp,
+                                  C.POINTER(_u32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
+    "srt_read_light_table": (_i, [_vp, C.POINTER(_u32), C.POINTER(_u32), _fp, _sz]),
+    "srt_direct_light_last": (_i, [_vp, C.POINTER(LightInfo)]),
+    "srt_set_light_test_batch": (_i, [_vp, _u32]),
     "srt_device_op_sweep": (_i, [_vp, _i, _fp, _fp, _sz, _fp]),
     "srt_order_tiles_kat": (_i, [_vp, C.POINTER(_u32), _u32, _u32, _u32, _u32, C.POINTER(_u32), _sz, C.POINTER(_u32), C.POINTER(_u32)]),
     "srt_read_tile_schedule": (_i, [_vp, _i, C.POINTER(_u32), _sz, C.POINTER(TileScheduleInfo)]),

@@ -16,6 +16,7 @@
 
 #include "srt_host.h"
 #include "srt_internal.h"
+#include "srt_light.h"
 
 using namespace srt;
 
@@ -243,6 +244,28 @@ struct srt_ctx {
     bool query_timed = false;
     srt_query_info query_info = {};                     // the plan of the last query launch (ms filled in by srt_query_last)
     uint32_t query_max_waves = 0;                       // srt_set_query_test_grid (0: fill the device)
+    // direct lighting (srt_light.hip; srt_c_api.h, "Direct lighting").  The upload keeps what the host tables are made from; the tables
+    // and their device copy are made at the first use after it.
+    struct LightSource { uint32_t tri, mat; float v0[3], v1[3], v2[3], n[3]; };
+    std::vector<LightSource> light_src;                 // the triangles with an EMISSIVE material, in scene order
+    std::vector<srt_material> light_mats;               // the uploaded materials
+    float light_bg[SRT_N_CIE_SAMPLES] = {};             // the uploaded background
+    bool light_refitted = false;                        // a refit moved the vertices since the upload: the table's areas are stale
+    bool light_tables_ok = false;                       // the host tables below describe the uploaded scene
+    bool light_tables_on_device = false;                // ... and d_light_tab holds them
+    std::vector<uint32_t> light_thresholds;             // [lights + 1]
+    std::vector<float> light_records;                   // [lights][16]
+    std::vector<float> light_t_light, light_t_sky, light_t_emit;      // [mats][slots][3], [mats][3], [mats][3]
+    float light_t_bg[3] = {0.f, 0.f, 0.f};
+    uint32_t light_slots = 0;
+    bool light_bg_nonzero = false;
+    DeviceBuffer d_light_tab;                           // LightTables
+    DeviceBuffer d_light_work;                          // LightWork: the round's rows, records and occlusion bytes
+    DeviceBuffer d_light_out;                           // LightOut: the counters, sum and m2 of the call's rectangle
+    hipEvent_t light_ev[6] = {};                        // around the kernels of a round (created on first use)
+    srt_light_info light_info = {};
+    bool light_timed = false;
+    uint32_t light_max_rows = 0;                        // srt_set_light_test_batch (0: the budget)
     DeviceBuffer d_streams;                            // sample-parallel pixels (srt_accum_reset_streams, StreamPlanes)
     uint32_t streams_seeded = 0;                        // the K whose RNG streams d_streams holds, seeded since the last srt_init_device_params (0: none)
 };
@@ -340,6 +363,23 @@ void build_refit_tables(srt_ctx *c, const FlatScene &f, const srt_scene &s) {
     refit_topology(f, s, t);
     c->refit_tri_tab.swap(t.tri_tab); c->refit_child.swap(t.child); c->refit_sched.swap(t.sched); c->refit_level_first.swap(t.level_first);
     c->refit_tables_ok = t.ok;
+}
+
+// What the direct-light tables are made from (srt_c_api.h, "Direct lighting"), copied out of the scene; host only
+void keep_light_sources(srt_ctx *c, const srt_scene &s) {
+    c->light_tables_ok = false; c->light_tables_on_device = false; c->light_refitted = false;
+    c->light_mats = s.mats;
+    memcpy(c->light_bg, s.background, sizeof(c->light_bg));
+    c->light_src.clear();
+    for (size_t k = 0; k < s.raw.size(); k++) {
+        const uint32_t m = s.raw[k].mat_index;
+        if (m >= s.mats.size() || s.mats[m].material_type != (uint32_t)SRT_MAT_EMISSIVE) continue;
+        srt_ctx::LightSource l;
+        l.tri = (uint32_t)k; l.mat = m;
+        memcpy(l.v0, s.raw[k].v0, sizeof(l.v0)); memcpy(l.v1, s.raw[k].v1, sizeof(l.v1)); memcpy(l.v2, s.raw[k].v2, sizeof(l.v2));
+        memcpy(l.n, s.rec[k].n, sizeof(l.n));
+        c->light_src.push_back(l);
+    }
 }
 
 // The cost probe's schedule.  d_tile_order: [rows: up to 64 per tile][sorted tile ids][queue_info 4 words]; d_tile_cost: per local tile
@@ -764,6 +804,7 @@ void srt_destroy(srt_ctx *c) {
     for (hipEvent_t e : c->temporal_var_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->refit_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->query_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->light_ev) if (e) (void)hipEventDestroy(e);
     delete c;      // (every DeviceBuffer, and the pinned staging block, frees itself, on the device selected above)
 }
 
@@ -824,6 +865,7 @@ int srt_upload_scene(srt_ctx *c, const srt_scene *s) {
     c->image_bytes[SRT_IMAGE_TRIS] = f.tris.size() * sizeof(float);
     c->image_bytes[SRT_IMAGE_SHADE] = f.shade.size() * sizeof(float);
     build_refit_tables(c, f, *s);      // (host only: nothing is enqueued or allocated on the device for a caller who never refits)
+    keep_light_sources(c, *s);         // (host only as well: the direct-light tables are made at their first use)
     if (c->track_motion) {      // V_cur = the scene's vertices, on the host until first use; V_hist = none
         c->track_verts.resize(9 * s->raw.size());
         for (size_t k = 0; k < s->raw.size(); k++) {
@@ -891,6 +933,7 @@ int refit_run(srt_ctx *c, const char *who, const float *d_verts, const float *h_
     if (!keep_history) c->temporal_frames = 0;      // (a tracking context keeps it: the *_moving calls reproject across the refit)
     c->sched_probe_queue = false; c->sched_compacted_queue = false;
     c->refit_timed = false;
+    c->light_refitted = true;      // (the light table's areas describe the uploaded vertices)
     if (c->track_motion) {
         if (keep_history && !c->verts_hist) { c->d_verts_cur.swap(c->d_verts_hist); c->verts_hist = true; }
         if (!keep_history) c->verts_hist = false;
@@ -3955,6 +3998,302 @@ int srt_query_last(srt_ctx *c, srt_query_info *info) {
 int srt_set_query_test_grid(srt_ctx *c, uint32_t max_waves) {
     if (!c) return fail(c, SRT_ERR_INVALID, "srt_set_query_test_grid: null ctx");
     c->query_max_waves = max_waves;
+    return SRT_OK;
+}
+
+// ---- direct lighting (srt_light.hip; srt_c_api.h, "Direct lighting") ----------------------------------------------------------------
+namespace {
+
+constexpr uint32_t kLightDraws = 1u << 24;                       // N: the 24-bit draw
+constexpr size_t kLightRowBytes = 32 + 16 + 32 + 32 + 16 + 2;    // camera row, hit row, two shadow rows, record, two occlusion bytes
+constexpr size_t kLightBudgetBytes = 320u << 20;                  // the working buffers of a round stay under this (one sample at least)
+
+// The round's working buffers: [cam: 2 float4 per row][hits: 1][light rows: 2][sky rows: 2][records: 1 uint4][occ_light][occ_sky]
+struct LightWork {
+    float4 *cam, *hits, *light_rows, *sky_rows;
+    uint4 *records;
+    uint8_t *occ_light, *occ_sky;
+    static size_t bytes(size_t rows) { return rows * 128 + 2 * ((rows + 15) & ~(size_t)15); }
+    LightWork(const DeviceBuffer &d, size_t rows)
+        : cam(d.as<float4>()), hits(cam + 2 * rows), light_rows(hits + rows), sky_rows(light_rows + 2 * rows),
+          records(reinterpret_cast<uint4 *>(sky_rows + 2 * rows)), occ_light(reinterpret_cast<uint8_t *>(records + rows)),
+          occ_sky(occ_light + ((rows + 15) & ~(size_t)15)) {}
+};
+// The call's outputs: [counters: 8 u64][sum: 3 floats per pixel][m2: 3 per pixel]
+struct LightOut {
+    unsigned long long *counters;
+    float *sum, *m2;
+    static size_t bytes(size_t npix) { return 64 + 24 * npix; }
+    LightOut(const DeviceBuffer &d, size_t npix) : counters(d.as<unsigned long long>()), sum(reinterpret_cast<float *>(d.as<char>() + 64)), m2(sum + 3 * npix) {}
+};
+// The tables: [thresholds: L + 1 words, padded to 16 bytes][records: 16 floats per light][t_light][t_sky][t_emit]
+struct LightTables {
+    uint32_t *thresholds;
+    float *records, *t_light, *t_sky, *t_emit;
+    static size_t head(size_t lights) { return ((lights + 1) * 4 + 15) & ~(size_t)15; }
+    static size_t bytes(size_t lights, size_t mats, size_t slots) { return head(lights) + 4 * (16 * lights + 3 * mats * slots + 6 * mats) + 16; }
+    LightTables(const DeviceBuffer &d, size_t lights, size_t mats, size_t slots)
+        : thresholds(d.as<uint32_t>()), records(reinterpret_cast<float *>(d.as<char>() + head(lights))), t_light(records + 16 * lights),
+          t_sky(t_light + 3 * mats * slots), t_emit(t_sky + 3 * mats) {}
+};
+
+// integral over [360, 830] of cmf[ch] a b (linear interpolants on the 5 nm grid; a null factor is 1): Simpson's rule per cell, in double
+void light_integral(const float *cmf96x4, const float *a, const float *b, float out[3]) {
+    for (int ch = 0; ch < 3; ch++) {
+        double acc = 0.0;
+        for (int j = 0; j + 1 < SRT_N_CIE_SAMPLES; j++) {
+            const double c0 = cmf96x4[4 * j + ch], c1 = cmf96x4[4 * (j + 1) + ch];
+            const double a0 = a ? (double)a[j] : 1.0, a1 = a ? (double)a[j + 1] : 1.0;
+            const double b0 = b ? (double)b[j] : 1.0, b1 = b ? (double)b[j + 1] : 1.0;
+            const double fa = (c0 * a0) * b0, fb = (c1 * a1) * b1;
+            const double fm = (((c0 + c1) * 0.5) * ((a0 + a1) * 0.5)) * ((b0 + b1) * 0.5);
+            acc += ((fa + 4.0 * fm) + fb) * (5.0 / 6.0);
+        }
+        out[ch] = (float)acc;
+    }
+}
+
+// the host tables of the uploaded scene; SRT_ERR_UNSUPPORTED above 2^20 lights
+int build_light_tables(srt_ctx *c, const char *who) {
+    if (c->light_tables_ok) return SRT_OK;
+    std::vector<float> cmf(96 * 4);
+    cmf_rows(cmf.data());
+    const size_t n_mats = c->light_mats.size();
+    std::vector<float> t_emit(3 * n_mats), t_sky(3 * n_mats);
+    for (size_t m = 0; m < n_mats; m++) {
+        light_integral(cmf.data(), c->light_mats[m].spectral_distribution, nullptr, &t_emit[3 * m]);
+        light_integral(cmf.data(), c->light_mats[m].spectral_distribution, c->light_bg, &t_sky[3 * m]);
+    }
+    float t_bg[3];
+    light_integral(cmf.data(), c->light_bg, nullptr, t_bg);
+    bool bg_nonzero = false;
+    for (float v : c->light_bg) bg_nonzero |= v != 0.0f;
+    // the table's lights: area > 0 and T_emit.y > 0
+    std::vector<float> rec;
+    std::vector<double> g;
+    std::vector<uint32_t> slot_mat;
+    for (const srt_ctx::LightSource &l : c->light_src) {
+        float e1[3], e2[3];
+        for (int k = 0; k < 3; k++) { e1[k] = l.v1[k] - l.v0[k]; e2[k] = l.v2[k] - l.v0[k]; }
+        const double cx = (double)e1[1] * (double)e2[2] - (double)e1[2] * (double)e2[1];
+        const double cy = (double)e1[2] * (double)e2[0] - (double)e1[0] * (double)e2[2];
+        const double cz = (double)e1[0] * (double)e2[1] - (double)e1[1] * (double)e2[0];
+        const float area = (float)(0.5 * std::sqrt((cx * cx + cy * cy) + cz * cz));
+        const float ty = t_emit[3 * l.mat + 1];
+        if (!(area > 0.0f) || !(ty > 0.0f)) continue;
+        size_t slot = std::find(slot_mat.begin(), slot_mat.end(), l.mat) - slot_mat.begin();
+        if (slot == slot_mat.size()) slot_mat.push_back(l.mat);
+        const uint32_t words[3] = {l.mat, l.tri, (uint32_t)slot};
+        const float *rows[4] = {l.v0, e1, e2, l.n};
+        for (int r = 0; r < 4; r++) {
+            rec.insert(rec.end(), rows[r], rows[r] + 3);
+            float last = area;
+            if (r > 0) memcpy(&last, &words[r - 1], 4);
+            rec.push_back(last);
+        }
+        g.push_back((double)area * (double)ty);
+    }
+    const size_t L = g.size();
+    if (L > (size_t)SRT_LIGHT_MAX_LIGHTS) return fail(c, SRT_ERR_UNSUPPORTED, std::string(who) + ": more than 2^20 lights");
+    // thresholds by largest remainder, every light at least 1 wide
+    std::vector<uint32_t> th(L + 1, 0u);
+    if (L > 0) {
+        std::vector<char> pinned(L, 0);
+        size_t n_pinned = 0;
+        double G = 0.0, B = 0.0;
+        for (;;) {
+            G = 0.0;
+            for (size_t l = 0; l < L; l++) if (!pinned[l]) G += g[l];
+            B = (double)(kLightDraws - n_pinned);
+            bool changed = false;
+            for (size_t l = 0; l < L; l++)
+                if (!pinned[l] && g[l] / G * B < 1.0) { pinned[l] = 1; n_pinned++; changed = true; }
+            if (!changed) break;
+        }
+        std::vector<uint32_t> width(L, 1u);
+        std::vector<double> rem(L, -1.0);
+        std::vector<uint32_t> order;
+        uint64_t given = n_pinned;
+        for (size_t l = 0; l < L; l++) {
+            if (pinned[l]) continue;
+            const double ideal = g[l] / G * B, fl = std::floor(ideal);
+            width[l] = (uint32_t)fl; rem[l] = ideal - fl; given += width[l];
+            order.push_back((uint32_t)l);
+        }
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rem[a] > rem[b]; });
+        for (size_t k = 0; given < kLightDraws && !order.empty(); k++, given++) width[order[k % order.size()]]++;
+        for (size_t l = 0; l < L; l++) th[l + 1] = th[l] + width[l];
+        if (th[L] != kLightDraws) return fail(c, SRT_ERR_INVALID, std::string(who) + ": the light thresholds do not add up (internal error)");
+    }
+    const size_t n_slots = slot_mat.size();
+    std::vector<float> t_light(3 * n_mats * n_slots);
+    for (size_t m = 0; m < n_mats; m++)
+        for (size_t s = 0; s < n_slots; s++)
+            light_integral(cmf.data(), c->light_mats[m].spectral_distribution, c->light_mats[slot_mat[s]].spectral_distribution, &t_light[3 * (m * n_slots + s)]);
+    c->light_thresholds.swap(th); c->light_records.swap(rec);
+    c->light_t_light.swap(t_light); c->light_t_sky.swap(t_sky); c->light_t_emit.swap(t_emit);
+    memcpy(c->light_t_bg, t_bg, sizeof(t_bg));
+    c->light_slots = (uint32_t)n_slots; c->light_bg_nonzero = bg_nonzero;
+    c->light_tables_ok = true; c->light_tables_on_device = false;
+    return SRT_OK;
+}
+
+int light_tables_to_device(srt_ctx *c, const char *who) {
+    if (c->light_tables_on_device) return SRT_OK;
+    const size_t L = c->light_thresholds.size() - 1, mats = c->light_mats.size(), slots = c->light_slots;
+    if (const int rc = develop_reserve(c, who, c->d_light_tab, LightTables::bytes(L, mats, slots))) return rc;
+    const LightTables T(c->d_light_tab, L, mats, slots);
+    auto put = [&](void *dst, const void *src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess; };
+    HIP_TRY_AS(c, who, put(T.thresholds, c->light_thresholds.data(), (L + 1) * 4));
+    HIP_TRY_AS(c, who, put(T.records, c->light_records.data(), c->light_records.size() * 4));
+    HIP_TRY_AS(c, who, put(T.t_light, c->light_t_light.data(), c->light_t_light.size() * 4));
+    HIP_TRY_AS(c, who, put(T.t_sky, c->light_t_sky.data(), c->light_t_sky.size() * 4));
+    HIP_TRY_AS(c, who, put(T.t_emit, c->light_t_emit.data(), c->light_t_emit.size() * 4));
+    c->light_tables_on_device = true;
+    return SRT_OK;
+}
+
+struct LightKat { float *cam_rows, *hit_rows, *light_rows, *sky_rows; uint32_t *records; uint8_t *occ_light, *occ_sky; };
+
+int direct_light_run(srt_ctx *c, const char *who, const srt_light *cfg, float *out_sum, float *out_m2, srt_light_result *result, uint32_t w,
+                     uint32_t h, uint32_t ox, uint32_t oy, const LightKat *kat) {
+    if (!c) return fail(c, SRT_ERR_INVALID, std::string(who) + ": null ctx");
+    auto refuse = [&](const char *why) { return fail(c, SRT_ERR_INVALID, std::string(who) + ": " + why); };
+    if (!cfg || !out_sum || !result) return refuse("null argument");
+    if (!c->scene_ready) return refuse("no scene uploaded");
+    if (!c->camera_ready) return refuse("no camera set");
+    if (cfg->samples < 1 || cfg->samples > SRT_LIGHT_MAX_SAMPLES) return refuse("samples outside 1 .. 65536");
+    if (kat && cfg->samples != 1) return refuse("the KAT entry runs one sample");
+    const uint32_t all_parts = SRT_LIGHT_EMITTED | SRT_LIGHT_LIGHTS | SRT_LIGHT_SKY;
+    if (cfg->parts == 0 || (cfg->parts & ~all_parts)) return refuse("parts is 0 or has unknown bits");
+    if ((uint64_t)cfg->first_sample + cfg->samples > (1ull << 32)) return refuse("first_sample + samples does not fit 32 bits");
+    if (w == 0 || h == 0) return refuse("empty rectangle");
+    if ((uint64_t)ox + w > c->cam.width || (uint64_t)oy + h > c->cam.height) return refuse("the rectangle sticks out of the camera's image");
+    if ((uint64_t)w * h > (1ull << 28)) return refuse("more than 2^28 pixels");
+    if ((cfg->parts & SRT_LIGHT_LIGHTS) && c->light_refitted)
+        return fail(c, SRT_ERR_UNSUPPORTED, std::string(who) + ": LIGHTS on a scene refitted since its upload (the light table's areas are stale)");
+    if (const int rc = build_light_tables(c, who)) return rc;
+    HIP_TRY_AS(c, who, set_device(c));
+    if (const int rc = light_tables_to_device(c, who)) return rc;
+    const size_t L = c->light_thresholds.size() - 1, mats = c->light_mats.size(), slots = c->light_slots;
+    const LightTables T(c->d_light_tab, L, mats, slots);
+    const bool lights_on = (cfg->parts & SRT_LIGHT_LIGHTS) && L > 0, sky_on = (cfg->parts & SRT_LIGHT_SKY) && c->light_bg_nonzero;
+    const uint32_t parts = (cfg->parts & SRT_LIGHT_EMITTED) | (lights_on ? SRT_LIGHT_LIGHTS : 0u) | (sky_on ? SRT_LIGHT_SKY : 0u);
+    const size_t npix = (size_t)w * h;
+    const size_t max_rows = c->light_max_rows ? (size_t)c->light_max_rows : kLightBudgetBytes / kLightRowBytes;
+    const uint32_t per_round = (uint32_t)std::max<size_t>(1, std::min<size_t>(cfg->samples, max_rows / npix));
+    const size_t rows_cap = npix * per_round;
+    if (rows_cap > (size_t)SRT_QUERY_MAX_RAYS) return refuse("a round of one sample has more rows than a query launch takes");
+    if (const int rc = develop_reserve(c, who, c->d_light_work, LightWork::bytes(rows_cap))) return rc;
+    if (const int rc = develop_reserve(c, who, c->d_light_out, LightOut::bytes(npix))) return rc;
+    for (hipEvent_t &e : c->light_ev) if (!e) HIP_TRY_AS(c, who, hipEventCreate(&e));
+    const LightWork W(c->d_light_work, rows_cap);
+    const LightOut O(c->d_light_out, npix);
+    HIP_TRY_AS(c, who, hipMemsetAsync(c->d_light_out.ptr, 0, LightOut::bytes(npix), nullptr));
+    LightCamera cam;
+    memcpy(cam.du, c->cam.pixel_delta_u, 12); memcpy(cam.dv, c->cam.pixel_delta_v, 12); memcpy(cam.p00, c->cam.pixel00_loc, 12);
+    memcpy(cam.center, c->cam.camera_center, 12); memcpy(cam.disk_u, c->cam.defocus_disk_u, 12); memcpy(cam.disk_v, c->cam.defocus_disk_v, 12);
+    cam.defocus_angle = c->cam.defocus_angle;
+    c->light_timed = false;
+    srt_light_info info = {};
+    info.rows_per_round = (uint32_t)std::min<size_t>(rows_cap, 0xffffffffu);
+    for (uint32_t done = 0; done < cfg->samples; done += per_round) {
+        LightRound r;
+        r.w = w; r.h = h; r.ox = ox; r.oy = oy; r.image_w = c->cam.width;
+        r.n_samples = std::min(per_round, cfg->samples - done); r.first_sample = cfg->first_sample + done;
+        r.seed_lo = (uint32_t)cfg->seed; r.seed_hi = (uint32_t)(cfg->seed >> 32); r.parts = parts;
+        const size_t rows = npix * r.n_samples;
+        HIP_TRY_AS(c, who, hipEventRecord(c->light_ev[0], nullptr));
+        HIP_TRY_AS(c, who, launch_light_camera(r, cam, W.cam, nullptr));
+        HIP_TRY_AS(c, who, hipEventRecord(c->light_ev[1], nullptr));
+        if (const int rc = query_enqueue(c, who, reinterpret_cast<const float *>(W.cam), rows, W.hits, false, nullptr)) return rc;
+        HIP_TRY_AS(c, who, hipEventRecord(c->light_ev[2], nullptr));
+        LightShadeParams sp = {};
+        sp.r = r; sp.cam_rows = W.cam; sp.hits = W.hits; sp.shade = c->d_shade.as<const float4>(); sp.n_tris = c->n_tris;
+        sp.thresholds = T.thresholds; sp.lights = reinterpret_cast<const float4 *>(T.records); sp.n_lights = (uint32_t)L;
+        sp.light_rows = lights_on ? W.light_rows : nullptr; sp.sky_rows = sky_on ? W.sky_rows : nullptr; sp.records = W.records;
+        HIP_TRY_AS(c, who, launch_light_shade(sp, nullptr));
+        HIP_TRY_AS(c, who, hipEventRecord(c->light_ev[3], nullptr));
+        if (lights_on) if (const int rc = query_enqueue(c, who, reinterpret_cast<const float *>(W.light_rows), rows, W.occ_light, true, nullptr)) return rc;
+        if (sky_on) if (const int rc = query_enqueue(c, who, reinterpret_cast<const float *>(W.sky_rows), rows, W.occ_sky, true, nullptr)) return rc;
+        HIP_TRY_AS(c, who, hipEventRecord(c->light_ev[4], nullptr));
+        LightGatherParams gp = {};
+        gp.r = r; gp.records = W.records; gp.occ_light = lights_on ? W.occ_light : nullptr; gp.occ_sky = sky_on ? W.occ_sky : nullptr;
+        gp.lights = reinterpret_cast<const float4 *>(T.records); gp.t_light = T.t_light; gp.t_sky = T.t_sky; gp.t_emit = T.t_emit;
+        memcpy(gp.t_bg, c->light_t_bg, sizeof(gp.t_bg));
+        gp.n_materials = (uint32_t)mats; gp.n_slots = (uint32_t)slots;
+        gp.sum = O.sum; gp.m2 = out_m2 ? O.m2 : nullptr; gp.counters = O.counters;
+        HIP_TRY_AS(c, who, launch_light_gather(gp, nullptr));
+        HIP_TRY_AS(c, who, hipEventRecord(c->light_ev[5], nullptr));
+        HIP_TRY_AS(c, who, device_synchronize(c));
+        float ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int k = 0; k < 5; k++) HIP_TRY_AS(c, who, hipEventElapsedTime(&ms[k], c->light_ev[k], c->light_ev[k + 1]));
+        info.camera_ms += ms[0]; info.query_ms += ms[1] + ms[3]; info.shade_ms += ms[2]; info.gather_ms += ms[4];
+        info.rounds++; info.query_launches += 1u + (lights_on ? 1u : 0u) + (sky_on ? 1u : 0u);
+        if (kat) {
+            auto get = [&](void *dst, const void *src, size_t bytes, bool valid) {
+                if (!dst) return hipSuccess;
+                if (!valid) { memset(dst, 0, bytes); return hipSuccess; }
+                return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
+            };
+            HIP_TRY_AS(c, who, get(kat->cam_rows, W.cam, 32 * rows, true));
+            HIP_TRY_AS(c, who, get(kat->hit_rows, W.hits, 16 * rows, true));
+            HIP_TRY_AS(c, who, get(kat->light_rows, W.light_rows, 32 * rows, lights_on));
+            HIP_TRY_AS(c, who, get(kat->sky_rows, W.sky_rows, 32 * rows, sky_on));
+            HIP_TRY_AS(c, who, get(kat->records, W.records, 16 * rows, true));
+            HIP_TRY_AS(c, who, get(kat->occ_light, W.occ_light, rows, lights_on));
+            HIP_TRY_AS(c, who, get(kat->occ_sky, W.occ_sky, rows, sky_on));
+        }
+    }
+    unsigned long long counts[kLightCounters];
+    HIP_TRY_AS(c, who, hipMemcpy(counts, O.counters, sizeof(counts), hipMemcpyDeviceToHost));
+    HIP_TRY_AS(c, who, hipMemcpy(out_sum, O.sum, 12 * npix, hipMemcpyDeviceToHost));
+    if (out_m2) HIP_TRY_AS(c, who, hipMemcpy(out_m2, O.m2, 12 * npix, hipMemcpyDeviceToHost));
+    srt_light_result res = {};
+    res.miss = counts[0]; res.emitted = counts[1]; res.specular = counts[2]; res.shaded = counts[3];
+    res.light_rows = counts[4]; res.light_unoccluded = counts[5]; res.sky_rows = counts[6]; res.sky_unoccluded = counts[7];
+    res.lights = (uint32_t)L;
+    *result = res;
+    c->light_info = info; c->light_timed = true;
+    return SRT_OK;
+}
+
+}  // namespace
+
+int srt_direct_light(srt_ctx *c, const srt_light *cfg, float *out_sum, float *out_m2, srt_light_result *result, uint32_t w, uint32_t h,
+                     uint32_t ox, uint32_t oy) {
+    return direct_light_run(c, "srt_direct_light", cfg, out_sum, out_m2, result, w, h, ox, oy, nullptr);
+}
+
+int srt_direct_light_kat(srt_ctx *c, const srt_light *cfg, float *out_sum, float *out_m2, srt_light_result *result, uint32_t w, uint32_t h,
+                         uint32_t ox, uint32_t oy, float *cam_rows, float *hit_rows, float *light_rows, float *sky_rows, uint32_t *records,
+                         uint8_t *occ_light, uint8_t *occ_sky) {
+    const LightKat kat = {cam_rows, hit_rows, light_rows, sky_rows, records, occ_light, occ_sky};
+    return direct_light_run(c, "srt_direct_light_kat", cfg, out_sum, out_m2, result, w, h, ox, oy, &kat);
+}
+
+int srt_read_light_table(srt_ctx *c, uint32_t *n_lights, uint32_t *thresholds, float *records, size_t cap) {
+    if (!c || !n_lights) return fail(c, SRT_ERR_INVALID, "srt_read_light_table: null argument");
+    if (!c->scene_ready) return fail(c, SRT_ERR_INVALID, "srt_read_light_table: no scene uploaded");
+    if (const int rc = build_light_tables(c, "srt_read_light_table")) return rc;
+    const size_t L = c->light_thresholds.size() - 1;
+    *n_lights = (uint32_t)L;
+    if ((thresholds || records) && cap < L) return fail(c, SRT_ERR_INVALID, "srt_read_light_table: cap is smaller than the table");
+    if (thresholds) memcpy(thresholds, c->light_thresholds.data(), (L + 1) * sizeof(uint32_t));
+    if (records && L) memcpy(records, c->light_records.data(), 16 * L * sizeof(float));
+    return SRT_OK;
+}
+
+int srt_direct_light_last(srt_ctx *c, srt_light_info *info) {
+    if (!c || !info) return fail(c, SRT_ERR_INVALID, "srt_direct_light_last: null argument");
+    if (!c->light_timed) return fail(c, SRT_ERR_INVALID, "srt_direct_light_last: no direct-light call has run on this context");
+    *info = c->light_info;
+    return SRT_OK;
+}
+
+int srt_set_light_test_batch(srt_ctx *c, uint32_t max_rows) {
+    if (!c) return fail(c, SRT_ERR_INVALID, "srt_set_light_test_batch: null ctx");
+    c->light_max_rows = max_rows;
     return SRT_OK;
 }
 

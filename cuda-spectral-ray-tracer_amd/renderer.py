@@ -1147,6 +1147,58 @@ class Renderer:
         """tests / tools only (srt_set_query_test_grid): at most max_waves persistent waves per query launch; 0 fills the device"""
         self._ck(B.lib().srt_set_query_test_grid(self._h, int(max_waves)))
 
+    def direct_light(self, w, h, ox=0, oy=0, **cfg):
+        """the deferred direct-light pass (srt_direct_light) over the w x h rectangle at (ox, oy) of the context's camera image, on the
+        uploaded scene: dict(sum, m2, mean, stats) -- sum and m2 (h, w, 3) float32 XYZ sums over the call's samples of the contributions
+        and of their squares, mean = sum / samples, stats = light_stats.  cfg: direct_light_config's arguments.  Reads only: no frame,
+        accumulation or RNG state moves."""
+        light = direct_light_config(**cfg)
+        w, h, ox, oy = _motion_rect("Renderer.direct_light", w, h, ox, oy)
+        s, m2, res = np.zeros((h, w, 3), np.float32), np.zeros((h, w, 3), np.float32), B.LightResult()
+        self._ck(B.lib().srt_direct_light(self._h, C.byref(light), B.fptr(s), B.fptr(m2), C.byref(res), w, h, ox, oy))
+        return dict(sum=s, m2=m2, mean=s / np.float32(light.samples), stats=light_stats(res))
+
+    def direct_light_kat(self, w, h, ox=0, oy=0, sample=0, **cfg):
+        """one round of the sample index `sample` (srt_direct_light_kat): direct_light's dict and the round's device buffers copied out --
+        cam_rows (n, 8), hit_rows (n, 4), light_rows (n, 8), sky_rows (n, 8) float32, records (n, 4) uint32 (bits of the weight, surface
+        material, light index, kind | 4 light row traced | 8 sky row traced), occ_light, occ_sky (n,) bool; n = w h, row-major"""
+        light = direct_light_config(samples=1, first_sample=sample, **cfg)
+        w, h, ox, oy = _motion_rect("Renderer.direct_light_kat", w, h, ox, oy)
+        n = w * h
+        s, m2, res = np.zeros((h, w, 3), np.float32), np.zeros((h, w, 3), np.float32), B.LightResult()
+        cam, hits, lrows, srows = (np.zeros((n, k), np.float32) for k in (8, 4, 8, 8))
+        rec, ol, os_ = np.zeros((n, 4), np.uint32), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        u8 = C.POINTER(C.c_uint8)
+        self._ck(B.lib().srt_direct_light_kat(self._h, C.byref(light), B.fptr(s), B.fptr(m2), C.byref(res), w, h, ox, oy, B.fptr(cam), B.fptr(hits),
+                                              B.fptr(lrows), B.fptr(srows), rec.ctypes.data_as(C.POINTER(C.c_uint32)), ol.ctypes.data_as(u8),
+                                              os_.ctypes.data_as(u8)))
+        return dict(sum=s, m2=m2, mean=s.copy(), stats=light_stats(res), cam_rows=cam, hit_rows=hits, light_rows=lrows, sky_rows=srows,
+                    records=rec, occ_light=ol.astype(bool), occ_sky=os_.astype(bool))
+
+    def light_table(self):
+        """the light table of the uploaded scene (srt_read_light_table): dict(thresholds (L + 1,) uint32, v0, e1, e2, normal (L, 3) float32,
+        area (L,) float32, mat, tri, slot (L,) uint32)"""
+        n = C.c_uint32(0)
+        self._ck(B.lib().srt_read_light_table(self._h, C.byref(n), None, None, 0))
+        L = n.value
+        th, rec = np.zeros(L + 1, np.uint32), np.zeros((L, 16), np.float32)
+        self._ck(B.lib().srt_read_light_table(self._h, C.byref(n), th.ctypes.data_as(C.POINTER(C.c_uint32)), B.fptr(rec), L))
+        words = rec.view(np.uint32)
+        return dict(thresholds=th, v0=rec[:, 0:3].copy(), area=rec[:, 3].copy(), e1=rec[:, 4:7].copy(), mat=words[:, 7].copy(),
+                    e2=rec[:, 8:11].copy(), tri=words[:, 11].copy(), normal=rec[:, 12:15].copy(), slot=words[:, 15].copy())
+
+    def direct_light_last(self):
+        """kernel ms of the last direct-light call by kind (srt_direct_light_last): dict(camera_ms, shade_ms, gather_ms, query_ms, rounds,
+        rows_per_round, query_launches)"""
+        q = B.LightInfo()
+        self._ck(B.lib().srt_direct_light_last(self._h, C.byref(q)))
+        return dict(camera_ms=q.camera_ms, shade_ms=q.shade_ms, gather_ms=q.gather_ms, query_ms=q.query_ms, rounds=q.rounds,
+                    rows_per_round=q.rows_per_round, query_launches=q.query_launches)
+
+    def set_light_test_batch(self, max_rows=0):
+        """tests / tools only (srt_set_light_test_batch): rounds of at most max_rows rows (one sample at least); 0 = the budget"""
+        self._ck(B.lib().srt_set_light_test_batch(self._h, int(max_rows)))
+
     def op_sweep(self, which, a, b):
         a = np.ascontiguousarray(a, np.float32); b = np.ascontiguousarray(b, np.float32)
         out = np.zeros_like(a)
@@ -2059,6 +2111,65 @@ def motion_stats(res):
     """srt_motion_result as a dict: the pixels whose centre ray hit and missed, the hit pixels whose triangle moved, and of those the
     degenerate ones (no previous point could be formed)"""
     return dict(hit=res.hit, miss=res.miss, moved=res.moved, degenerate=res.degenerate)
+
+
+def light_stats(res):
+    """srt_light_result as a dict: the samples that missed, saw an emitter, met a specular surface and were shaded, the traced light and
+    sky rows and the unoccluded ones among them, and the lights in the table"""
+    return {k: int(getattr(res, k)) for k in ("miss", "emitted", "specular", "shaded", "light_rows", "light_unoccluded", "sky_rows",
+                                                "sky_unoccluded", "lights")}
+
+
+def direct_light_config(samples=16, seed=0, first_sample=0, parts=("emitted", "lights", "sky")):
+    """srt_light, checked as the library checks it (ValueError) before any library call: samples 1 .. 65536, first_sample + samples at
+    most 2^32, seed below 2^64, parts a non-empty collection of "emitted", "lights", "sky" """
+    for name, v, hi in (("samples", samples, B.LIGHT_MAX_SAMPLES), ("seed", seed, 2 ** 64 - 1), ("first_sample", first_sample, 2 ** 32 - 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0 or v > hi:
+            raise ValueError("direct_light_config: %s must be an integer in 0 .. %d, got %r" % (name, hi, v))
+    if samples < 1:
+        raise ValueError("direct_light_config: samples must be at least 1")
+    if first_sample + samples > 2 ** 32:
+        raise ValueError("direct_light_config: first_sample + samples must not exceed 2^32")
+    if isinstance(parts, str):
+        parts = (parts,)
+    parts = tuple(parts)
+    if not parts or any(p not in B.LIGHT_PARTS for p in parts):
+        raise ValueError("direct_light_config: parts must name at least one of %s, got %r" % (sorted(B.LIGHT_PARTS), parts))
+    mask = 0
+    for p in parts:
+        mask |= B.LIGHT_PARTS[p]
+    return B.Light(samples=int(samples), first_sample=int(first_sample), parts=mask, reserved=0, seed=int(seed))
+
+
+def render_direct(scene, cam, width, height, passes, samples=16, device=0, renderer=None, **cfg):
+    """Direct-lighting preview of the whole image on one GPU: a generator that runs `passes` calls of `samples` samples each, advancing
+    first_sample, and yields (samples_total, mean, stats) after each -- mean (height, width, 3) float32 XYZ of all samples so far, stats
+    the counters summed.  The mean goes through expose_kat / present_kat / despeckle_kat as any XYZ mean does.  The arguments are checked
+    here, when the generator is made, before any device is touched."""
+    if isinstance(passes, bool) or not isinstance(passes, (int, np.integer)) or passes < 1:
+        raise ValueError("render_direct: passes must be a positive integer, got %r" % (passes,))
+    first = int(cfg.pop("first_sample", 0))
+    for k in range(int(passes)):
+        direct_light_config(samples=samples, first_sample=first + k * samples, **cfg)
+    return _direct_passes(scene, cam, int(width), int(height), int(passes), int(samples), first, device, renderer, cfg)
+
+
+def _direct_passes(scene, cam, width, height, passes, samples, first, device, renderer, cfg):
+    r = renderer or Renderer(device)
+    try:
+        r.upload_scene(scene)
+        r.set_camera(cam)
+        total = np.zeros((height, width, 3), np.float64)
+        stats = None
+        for k in range(passes):
+            out = r.direct_light(width, height, samples=samples, first_sample=first + k * samples, **cfg)
+            total += out["sum"]
+            stats = out["stats"] if stats is None else {n: (v if n == "lights" else v + stats[n]) for n, v in out["stats"].items()}
+            done = (k + 1) * samples
+            yield done, (total / done).astype(np.float32), stats
+    finally:
+        if renderer is None:
+            r.close()
 
 
 def _motion_rect(who, w, h, ox, oy):

@@ -312,7 +312,7 @@ SRT_API int srt_set_partition(srt_ctx *ctx, uint32_t rank, uint32_t world);
  * context in flight on any stream, and the remembered stream is not touched again after them, so it may be destroyed -- are
  * srt_synchronize; every read-back (srt_read_fb, srt_read_fb_aux, srt_read_fb_rowmajor, srt_read_accum_stats, srt_read_spectral,
  * srt_read_features, srt_accum_active on a bound accumulation, srt_get_stats, srt_get_tile_costs, srt_get_wave_debug,
- * srt_read_tile_schedule, srt_read_scene_image); srt_refit_vertices and srt_refit_vertices_dev; srt_intersect_rays and srt_occluded_rays; every stage call that returns host data (srt_meter_*, srt_expose_*, srt_develop_*, srt_despeckle_*,
+ * srt_read_tile_schedule, srt_read_scene_image); srt_refit_vertices and srt_refit_vertices_dev; srt_intersect_rays and srt_occluded_rays; srt_direct_light and srt_direct_light_kat; every stage call that returns host data (srt_meter_*, srt_expose_*, srt_develop_*, srt_despeckle_*,
  * srt_temporal_*, srt_denoise_*, srt_present* -- not their *_last_ms timing queries, which wait for their own events alone);
  * srt_init_device_params and every srt_accum_reset*.  srt_comm_synchronize waits for the
  * communicator's own streams only and is none of them; srt_comm_destroy synchronises every context before it destroys those streams.
@@ -1434,6 +1434,104 @@ SRT_API int srt_intersect_rays_dev(srt_ctx *ctx, const float *rays_dev, size_t n
 SRT_API int srt_occluded_rays_dev(srt_ctx *ctx, const float *rays_dev, size_t n, uint8_t *occluded_dev, void *query_stream);
 SRT_API int srt_query_last(srt_ctx *ctx, srt_query_info *info);
 SRT_API int srt_set_query_test_grid(srt_ctx *ctx, uint32_t max_waves);
+/* Direct lighting (no reference counterpart: material::scatter has no next-event estimation): a deferred pass over a rectangle of the
+ * image, built from a light sampler and the ray queries above (srt_light.hip).  Per sample: camera ray -> closest hit -> one shadow
+ * segment to a sampled light and one cosine-distributed sky ray -> any-hit occlusion -> a sum.  In expectation the picture is what the
+ * path tracer computes at bounce_limit = 2 on pixels whose first hit is not specular.  render_kernel is not involved.
+ *
+ *   Spectra collapse on the host.  A two-segment path camera -> Lambertian ms -> end e contributes, in expectation, the integral over
+ *   [360, 830] nm of cmf(l) rho_ms(l) L_e(l), all three linear interpolants on the 5 nm grid (srt_color_tables' cmf rows x, y, z; the
+ *   materials' spectral_distribution and the background as uploaded, a bake included; emission_power is not read).  Per 5 nm cell
+ *   [a, b] Simpson's rule, exact for the cubic: 5/6 (f(a) + 4 f(m) + f(b)), f(m) the product of the factors' means (p(a) + p(b)) / 2;
+ *   cells added in ascending order, all in double, the result rounded to float32 once.  At the first use after srt_upload_scene (the
+ *   upload itself enqueues nothing and allocates nothing on the device for this):
+ *     T_light[ms][ml][3]  surface material x emissive material    T_sky[ms][3]  surface material x background
+ *     T_emit[m][3]        a material alone                         T_bg[3]       the background alone
+ *   (on the device T_light is stored per emissive material that owns a light: its "slot").  The device part carries XYZ triples only.
+ *
+ *   Light table.  Every triangle, in scene order, with an EMISSIVE material, area > 0 and T_emit[mat].y > 0; both faces emit.  e1 = v1 - v0,
+ *   e2 = v2 - v0 in float32; area = float32(0.5 sqrt(cx^2 + cy^2 + cz^2)), c = e1 x e2, evaluated in double from the float32 edges; n_l
+ *   the triangle's unit normal of srt_scene_get_tri_records.  Weight g_l = double(area) x double(T_emit.y).  Integer thresholds
+ *   c_0 = 0 <= ... <= c_L = N = 2^24 by largest remainder with every light at least 1 wide: start with all lights "free" and repeat
+ *   { G = sum of g over the free lights in table order; B = N - (number of pinned lights); a free light with g / G * B < 1 becomes
+ *   pinned (width 1) } until no light changes; a free light's width is floor(g / G * B), and the B - sum of these that remain go, one
+ *   each, to the free lights with the largest remainders g / G * B - floor(.), ties to the lower index.  A 24-bit draw k picks the
+ *   light with c_l <= k < c_l+1 (binary search: a = 0, b = L; while b - a > 1 { m = (a + b) >> 1; c_m <= k ? a = m : b = m }); its
+ *   probability is exactly p_l = (c_l+1 - c_l) 2^-24, float32 exactly.  More than 2^20 lights: SRT_ERR_UNSUPPORTED.
+ *
+ *   Random numbers.  Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC11): multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57, key increments
+ *   0x9E3779B9, 0xBB67AE85; ten rounds of (c0, c1, c2, c3) <- (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)), the
+ *   key incremented between rounds.  The all-zero counter and key give 6627e8d5 e169c58d bc57ac4c 9b00dbd8.  Key = (seed low word,
+ *   seed high word); counter = (pixel = global y * image width + global x, first_sample + s, purpose, try).  A sample's numbers depend
+ *   on these and on nothing else: not on lane, wave, rectangle, round or which parts are on.  u(x) = (x >> 8) 2^-24; s(x) = 2 u(x) - 1.
+ *   Purposes: 0 pixel jitter (try 0; words 0, 1), 1 lens disk (try t; words 0, 1), 2 light (try 0; word 0 >> 8 is the draw k, words 1,
+ *   2 the point), 3 sky sphere (try t; words 0, 1, 2).
+ *
+ *   One sample, float32 throughout: + - x / sqrtf, conversions, compares, selects and integer operations only, not contracted, left to
+ *   right; vectors componentwise; a . b = (a.x b.x + a.y b.y) + a.z b.z.
+ *     Camera ray (renderer::get_ray as render_kernel states it).  px = -0.5 + u, py = -0.5 + u: jitter in [-0.5, 0.5)^2;
+ *       pc = (pixel00_loc + float(X) pixel_delta_u) + float(Y) pixel_delta_v; ps = pc + (px pixel_delta_u + py pixel_delta_v); origin =
+ *       camera_center, or when !(defocus_angle <= 0): (camera_center + dx defocus_disk_u) + dy defocus_disk_v with (dx, dy) = (s, s) of
+ *       the first try t < 16 with dx dx + dy dy < 1, and (0, 0) when all 16 fail (probability (1 - pi/4)^16 = 2.0e-11: a bias bound,
+ *       not tested).  Row (origin, 0, ps - origin, FLT_MAX).
+ *     Closest hit: srt_intersect_rays_dev's kernel on the camera rows.
+ *       miss                                      add T_bg (part EMITTED)
+ *       EMISSIVE first hit                        add T_emit[mat] (part EMITTED)
+ *       METALLIC or DIELECTRIC first hit          nothing; the sample counts as specular
+ *       every other material type                 p = o + t d; n = the triangle's unit normal n_g (the shading record's) when d . n_g < 0,
+ *                                                 else -n_g; o' = p + 0.0001 n (kEpsilon); then
+ *         LIGHTS (the table is not empty)  pick l; (u1, u2) = (u, u); if u1 + u2 > 1: u1 = 1 - u1, u2 = 1 - u2; q = (v0 + u1 e1) + u2 e2;
+ *                    dl = q - o'; nd = n . dl; r2 = dl . dl; cl = |n_l . dl|; the row is (o', 0, dl, 1 - 2^-10) and
+ *                    w = ((nd cl) / ((r2 r2) pi)) (area / p_l), pi = 0x40490fdb, when nd > 0 and r2 > 0; else it is not traced and
+ *                    w = 0.  Unoccluded: add w T_light[ms][ml].
+ *         SKY        (x, y, z) = (s, s, s) of the first try t < 32 with 0 < len2 = (x x + y y) + z z < 1; v = (1 / sqrtf(len2)) (x, y,
+ *                    z); when all 32 fail v = n (probability (1 - pi/6)^32 = 5.0e-11: a bias bound, not tested; 16 tries would leave
+ *                    7.0e-6).  dir = n + v, and dir = n when all three |components| < 1e-8 (lambertian_scatter).  Row (o', 0, dir,
+ *                    FLT_MAX).  Unoccluded: add T_sky[ms].
+ *     A row that is not traced is written (.., tmin = 1, .., tmax = 0): the query answers it as a miss without a walk, and its
+ *     contribution is masked.  Occlusion: srt_occluded_rays_dev's kernel on each buffer of shadow rows.
+ *     Per pixel, samples in ascending order: with e, l, k the EMITTED, LIGHTS and SKY terms (0 where they do not apply),
+ *     sum[c] = ((sum[c] + e[c]) + l[c]) + k[c]; t[c] = (e[c] + l[c]) + k[c]; m2[c] = m2[c] + t[c] t[c].  sum and m2 are SUMS over the
+ *     call's samples, like the accumulation's.
+ *   Rounds.  The work runs in rounds of a whole number of samples of the whole rectangle, sized so that the context's working buffers
+ *   (130 bytes per row) stay under 320 MiB, one sample at least; sums carry over in sample order, so no answer depends on the round size.
+ *
+ *   srt_direct_light         on the context's camera and uploaded scene, any rectangle inside the camera's image, any partition; a query
+ *                            like srt_surface_motion: NULL stream, synchronises, and only reads -- no frame, sum, history or RNG state moves.
+ *                            out_sum[h][w][3], out_m2[h][w][3] (or NULL) row-major; result: the counters over all samples (light_rows and
+ *                            sky_rows count traced rows) and the lights in the table.
+ *   srt_direct_light_kat     the same for cfg->samples = 1 (one round of the sample index first_sample); also copies out, each when not
+ *                            NULL and n = w h: cam_rows[n][8], hit_rows[n][4], light_rows[n][8], sky_rows[n][8] (zero when the part is
+ *                            off), records[n][4] = bits(w), surface material (the first hit's), light index, kind (0 miss, 1 emitted,
+ *                            2 specular, 3 shaded) | 4 light row traced | 8 sky row traced, and occ_light[n], occ_sky[n].
+ *   srt_read_light_table     *n_lights; thresholds[L + 1] and records[L][16] = v0 area | e1 bits(mat) | e2 bits(tri) | n_l bits(slot)
+ *                            when not NULL and cap >= L (else SRT_ERR_INVALID).  Host only once the table exists.
+ *   srt_direct_light_last    kernel-only ms of the last call, summed over its rounds: camera, shade, gather kernels, the query launches;
+ *                            and its rounds.
+ *   srt_set_light_test_batch TEST HOOK: rounds of at most max_rows rows (one sample at least); 0 = the budget.
+ *   Refused, nothing changed or written: SRT_ERR_INVALID for a null argument, no scene or no camera, samples outside 1 .. 65536, parts 0
+ *   or with unknown bits, first_sample + samples > 2^32, an empty rectangle, one that sticks out of the camera's image or has more than
+ *   2^28 pixels, (kat) samples != 1; SRT_ERR_UNSUPPORTED for more than 2^20 lights, and for LIGHTS on a context whose scene was refitted
+ *   since its upload (the table's areas are stale; EMITTED and SKY work on refitted trees). */
+#define SRT_LIGHT_EMITTED 1u
+#define SRT_LIGHT_LIGHTS 2u
+#define SRT_LIGHT_SKY 4u
+#define SRT_LIGHT_MAX_SAMPLES 65536u
+#define SRT_LIGHT_MAX_LIGHTS (1u << 20)
+typedef struct srt_light { uint32_t samples, first_sample, parts, reserved; uint64_t seed; } srt_light;
+typedef struct srt_light_result {
+    uint64_t miss, emitted, specular, shaded, light_rows, light_unoccluded, sky_rows, sky_unoccluded;
+    uint32_t lights, reserved;
+} srt_light_result;
+typedef struct srt_light_info { float camera_ms, shade_ms, gather_ms, query_ms; uint32_t rounds, rows_per_round, query_launches, reserved; } srt_light_info;
+SRT_API int srt_direct_light(srt_ctx *ctx, const srt_light *cfg, float *out_sum, float *out_m2, srt_light_result *result,
+                             uint32_t w, uint32_t h, uint32_t ox, uint32_t oy);
+SRT_API int srt_direct_light_kat(srt_ctx *ctx, const srt_light *cfg, float *out_sum, float *out_m2, srt_light_result *result,
+                                 uint32_t w, uint32_t h, uint32_t ox, uint32_t oy, float *cam_rows, float *hit_rows, float *light_rows,
+                                 float *sky_rows, uint32_t *records, uint8_t *occ_light, uint8_t *occ_sky);
+SRT_API int srt_read_light_table(srt_ctx *ctx, uint32_t *n_lights, uint32_t *thresholds, float *records, size_t cap);
+SRT_API int srt_direct_light_last(srt_ctx *ctx, srt_light_info *info);
+SRT_API int srt_set_light_test_batch(srt_ctx *ctx, uint32_t max_rows);
 /* Device arithmetic self-test: evaluates op `which` on n operand pairs on the GPU (see DESIGN.md "primitive-op
  * sweep"); used to prove the device's + - * / sqrt fmin cast and srt_powf bits equal the host's. */
 SRT_API int srt_device_op_sweep(srt_ctx *ctx, int which, const float *a, const float *b, size_t n, float *out);
