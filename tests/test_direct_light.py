@@ -2,9 +2,12 @@
 
 Bit identity: the device equals tests/direct_light_reference.py in every bit of sum and m2, in every counter and, through the KAT entry, in
 every intermediate row; the restatement's two queries are Renderer.intersect / occluded on its own rows.  On the truth scenes of
-tests/direct_light_cases.py, scene 0 (CORNELL) and scene TRIS; rectangles 1 x 1, 67 x 35 and an offset chunk; under every knob set of
-tests/test_query.py; with rounds forced small; with first_sample; with single parts.
-Truth: the conditions of tests/direct_light_cases.py on the device's output, no restatement in between.
+tests/direct_light_cases.py, scene 0 (CORNELL), scene TRIS and RANDOM_SPHERES (a lens, a sky, metals and glass together); rectangles 1 x 1,
+67 x 35 and an offset chunk; under every knob set of tests/test_query.py; with rounds forced small; with first_sample; with single parts.
+The light table with its slots, on 37 lights with pinned ones (many_lights) and on two emitters whose slot order is not their material order.
+Truth: the conditions of tests/direct_light_cases.py on the device's output, no restatement in between.  test_fixed_draw: the two committed
+draws of many_lights, a pinned light's single value and a wide light's first value, through the KAT entry.  test_black_sky: SKY asked for
+under a black background.  test_lens_rows_hold_to_geometry: the device's own camera rows under a thin lens, held to the disk and the footprint.
 State: a call between two passes of a bound accumulation changes nothing; after a refit SKY follows the refitted geometry and LIGHTS is
 refused; every other refusal.
 End to end: CORNELL against the product's own path tracer at bounce_limit = 2 (test_path_tracer_agrees)."""
@@ -22,7 +25,7 @@ from test_traversal_limits import KNOBS, _knob_id, _knobs
 pytestmark = pytest.mark.gpu
 
 SEED = 0x5eed0123456789ab
-BUILTIN = {"cornell": "SCENE_CORNELL", "tris": "SCENE_TRIS"}
+BUILTIN = {"cornell": "SCENE_CORNELL", "tris": "SCENE_TRIS", "random_spheres": "SCENE_RANDOM_SPHERES"}
 IDENTITY_SCENES = DC.NAMES + tuple(BUILTIN)
 
 
@@ -72,7 +75,8 @@ def test_bit_identity(srt, gpu, name):
     want = _restate(gpu, c, c["W"], c["H"], samples=4, seed=SEED)
     _assert_same(got, want, name)
     st = got["stats"]
-    assert st["miss"] + st["emitted"] + st["specular"] + st["shaded"] == 4 * c["W"] * c["H"] and st["shaded"] > 0
+    assert st["miss"] + st["emitted"] + st["specular"] + st["shaded"] == 4 * c["W"] * c["H"]
+    assert (st["shaded"] > 0) != (name == "emitters_in_view")          # (that one looks up from under the floor's lights: nothing is shaded)
     assert np.array_equal(bits(got["mean"]), bits(got["sum"] / np.float32(4)))
     # the light table, bit for bit
     tab, dev = want["tab"], gpu.light_table()
@@ -80,6 +84,8 @@ def test_bit_identity(srt, gpu, name):
     for k in ("v0", "e1", "e2", "normal", "area"):
         assert np.array_equal(bits(dev[k]), bits(tab[k])), (name, k)
     assert np.array_equal(dev["mat"], tab["mat"]) and np.array_equal(dev["tri"], tab["tri"])
+    first = list(dict.fromkeys(tab["mat"].tolist()))          # slots number the emissive materials by their first light
+    assert dev["slot"].tolist() == [first.index(m) for m in tab["mat"].tolist()], (name, dev["slot"])
     # one round of sample 2 through the KAT entry: every intermediate row
     kat = gpu.direct_light_kat(c["W"], c["H"], sample=2, seed=SEED)
     ref = _restate(gpu, c, c["W"], c["H"], samples=1, first_sample=2, seed=SEED, keep=True)
@@ -168,8 +174,69 @@ def test_truth_on_the_device(srt, gpu, name):
     c = DC.case(srt, name)
     _setup(gpu, c)
     out = gpu.direct_light(c["W"], c["H"], samples=c["samples"], seed=SEED, parts=c["parts"])
+    if name in DC.ALL_HELD:          # every camera ray meets the floor, under a lens too, and nothing stands between the floor and its lights
+        n = c["W"] * c["H"] * c["samples"]
+        assert out["stats"]["shaded"] == out["stats"]["light_rows"] == out["stats"]["light_unoccluded"] == n, (name, out["stats"])
     print(name, out["stats"], DC.assert_holds(name, DC.expectation(srt, name), out["sum"], out["m2"], c["samples"], c["W"], c["H"], "device"),
           gpu.direct_light_last())
+
+
+@pytest.mark.parametrize("which", ["pinned", "edge"])
+def test_fixed_draw(srt, gpu, which):
+    """many_lights' two committed draws (tests/test_direct_light_reference.py re-derives them) through the KAT entry on their 1 x 1
+    rectangle: "pinned" draws thresholds[a] of a light of width 1, "edge" thresholds[m] of a wider one.  The device picks that light,
+    traces the row, equals the restatement in every bit, and its weight is the float64 one within DC.assert_weight_holds' bound."""
+    c = DC.case(srt, "many_lights")
+    _setup(gpu, c)
+    (x, y), s = DC.DRAW_PIXEL, DC.DRAW_S[which]
+    kat = gpu.direct_light_kat(1, 1, x, y, sample=s, seed=DC.DRAW_SEED, parts=("lights",))
+    ref = _restate(gpu, c, 1, 1, x, y, samples=1, first_sample=s, seed=DC.DRAW_SEED, parts=("lights",), keep=True)
+    tab = ref["tab"]
+    k = int(R.philox(np.array([y * c["W"] + x], np.uint32), np.uint32(s), 2, 0, *R.seed_key(DC.DRAW_SEED))[0][0] >> np.uint32(8))
+    a = int(np.nonzero(tab["thresholds"] == k)[0][0])
+    width = int(tab["thresholds"][a + 1]) - int(tab["thresholds"][a])
+    assert width == 1 if which == "pinned" else (width > 1 and a > 0), (which, a, width)
+    assert np.array_equal(gpu.light_table()["thresholds"], tab["thresholds"])
+    _assert_same(kat, ref, which + " draw")
+    assert np.array_equal(kat["records"], ref["rounds"][0]["records"]) and np.array_equal(bits(kat["light_rows"]), bits(ref["rounds"][0]["light_rows"]))
+    assert kat["stats"]["light_rows"] == 1
+    print(which, "light %d of width %d, draw %d; weight off by %.3g, allowed %.3g" % (
+        (a, width, k) + DC.assert_weight_holds(tab, kat["records"][0], kat["light_rows"][0], a, which + " on the device")))
+
+
+def test_black_sky(srt, gpu):
+    """cosine_law's background is black.  SKY alone: the sums are 0, no sky row is made and every round launches the closest query alone;
+    LIGHTS with SKY is LIGHTS alone in every bit and counter.  All of it is the restatement's as well."""
+    c = DC.case(srt, "cosine_law")
+    _setup(gpu, c)
+    W, H = c["W"], c["H"]
+    try:
+        gpu.set_light_test_batch(W * H)          # rounds of one sample: three rounds
+        sky = gpu.direct_light(W, H, samples=3, seed=SEED, parts=("sky",))
+        info = gpu.direct_light_last()
+    finally:
+        gpu.set_light_test_batch(0)
+    assert not sky["sum"].any() and not sky["m2"].any() and sky["stats"]["sky_rows"] == 0 and sky["stats"]["shaded"] == 3 * W * H
+    assert info["rounds"] == 3 and info["query_launches"] == info["rounds"], info
+    _assert_same(sky, _restate(gpu, c, W, H, samples=3, seed=SEED, parts=("sky",)), "sky alone under a black sky")
+    kat = gpu.direct_light_kat(W, H, sample=1, seed=SEED, parts=("sky",))
+    assert not kat["sky_rows"].any() and not kat["occ_sky"].any() and not (kat["records"][:, 3] & R.ROW_SKY).any()
+    both, lights = gpu.direct_light(W, H, samples=3, seed=SEED, parts=("lights", "sky")), gpu.direct_light(W, H, samples=3, seed=SEED, parts=("lights",))
+    assert gpu.direct_light_last()["query_launches"] == 2 * gpu.direct_light_last()["rounds"]
+    _assert_same(both, lights, "lights with a black sky")
+    _assert_same(both, _restate(gpu, c, W, H, samples=3, seed=SEED, parts=("lights", "sky")), "lights and sky under a black sky")
+    assert lights["stats"]["light_unoccluded"] > 0 and lights["sum"].any()
+
+
+@pytest.mark.parametrize("name", DC.LENS_CAMERAS)
+def test_lens_rows_hold_to_geometry(srt, gpu, name):
+    """the device's own camera rows of samples 0 .. 3 under a thin lens, through the KAT entry, held to the geometry
+    DC.assert_lens_rows_hold states: no restatement in between"""
+    c = _case(srt, name)
+    _setup(gpu, c)
+    assert c["cam"].defocus_angle > 0
+    rows = np.stack([gpu.direct_light_kat(c["W"], c["H"], sample=s, seed=SEED, parts=("emitted",))["cam_rows"] for s in range(4)])
+    print(name, DC.assert_lens_rows_hold(c["cam"], c["W"], c["H"], rows, name + " on the device"))
 
 
 def test_a_call_moves_no_state(srt, gpu):

@@ -14,6 +14,33 @@ Deliberate breaks of the restatement, each tried once on test_truth_scene (what 
   * n not face-forwarded                        cosine_law, split_light, occluded_light: every sum 0 (the floor's own normal points down,
                                                 away from camera and light); sky_blocker z_img = 98.  floor_under_sky stays green:
                                                 a sky ray leaves on either side of a floor with nothing around it.
+
+Cases that reach what the five above cannot (each also runs on the device, tests/test_direct_light.py):
+  many_lights        37 lights, eight pinned at width 1 (test_many_lights_table states the scene before anything is sampled): a binary
+                     search of several unequal halves, thresholds by largest remainder with pinned entries, the weight area / p_l over
+                     seven decades of area.  test_fixed_draw re-derives two committed draws with one Philox call each -- one equal to
+                     thresholds[a] of a pinned light a, one equal to thresholds[m] of a wide light m, which must pick m and not m - 1 --
+                     and holds the weight of that sample to its float64 value within a bound counted from the rounded operations.
+  two_emitters       two emissive materials whose slot order is not their material order, over a floor of two materials: a swapped or
+                     mis-strided t_light index.  Deliberate breaks of the expectation, each tried once (test_two_emitters_tells_its_
+                     tables_apart keeps both red): the two emitters' T swapped, z_img = 196 (channel 0, allowed 5); the floor materials'
+                     rows swapped, z_img = 35 (channel 0).
+  emitters_in_view   EMITTED: T_emit[material] on each of two emitters and T_bg on the sky, to the rounding of S equal terms, at least
+                     MIN_PIXELS pixels of each; the tables themselves against the exact integral (test_tables_hold_the_exact_integral).
+  test_black_sky     SKY under a black background: no sky row, no occlusion query, sums 0; LIGHTS with SKY is LIGHTS alone.
+  the lens           floor_under_sky_lens (every pixel still T_sky: every lens ray meets the floor) and cosine_law_lens (F averaged over
+                     footprint and lens; test_lens_quadrature_is_converged: the two resolutions differ by 0.004 of the smallest per-pixel
+                     standard error, the pinhole's expectation by 43 of them).
+  lens rows          test_lens_rows_hold_to_geometry, float64 on the rows of samples 0 .. 3: origin - centre = a disk_u + b disk_v by
+                     least squares with a residual within the four rounded operations' 4 x 2^-24 M per component (M the largest
+                     coordinate of the centre plus the disk vectors'), a^2 + b^2 < 1 up to that; origin + d lies in the pixel's own
+                     footprint [-0.5, 0.5)^2 in the (du, dv) basis to the nine rounded operations behind it (this fails where d is not
+                     taken from the moved origin); over the N rows |mean a|, |mean b| <= 5 x 0.5 / sqrt(N) and
+                     |mean (a^2 + b^2) - 0.5| <= 5 sqrt(1/12) / sqrt(N), a uniform disk's own moments; no row starts at the centre.
+                     Two breaks of the rows, each tried once on both cameras: d taken from the centre puts origin + d up to 1.2 (1.4)
+                     pixels off the centre of its pixel, allowed 0.5; a disk of 0.7 of the radius gives mean (a^2 + b^2) = 0.25.
+Not reached, and not faked: the fallbacks after 16 disk tries and 32 sphere tries and the guard for n + ruv ~ 0 have a probability of about
+1e-11 per row; no search finds them in a sitting.
 """
 import numpy as np
 import pytest
@@ -21,6 +48,7 @@ import pytest
 import direct_light_cases as DC
 import direct_light_reference as R
 import ground_truth as G
+from helpers import bits
 
 
 def test_philox_known_answers():
@@ -43,7 +71,7 @@ def test_uniforms_are_exact_dyadics():
     assert R.seed_key(0x123456789abcdef0) == (0x9abcdef0, 0x12345678)
 
 
-@pytest.mark.parametrize("name", ["cosine_law", "sky_blocker"])
+@pytest.mark.parametrize("name", ["cosine_law", "sky_blocker", "two_emitters", "emitters_in_view"])
 def test_tables_hold_the_exact_integral(srt, name):
     """every T entry against three-point Gauss-Legendre in float64: one float32 rounding (2^-24 relative) plus the doubles' own (1e-12)"""
     c = DC.case(srt, name)
@@ -92,11 +120,15 @@ def test_thresholds_are_exact():
 
 
 def _restated(srt, name, **over):
+    """the restatement's run of a truth scene under the float64 queries, computed once per set of arguments"""
     c = DC.case(srt, name)
-    intersect, occluded = R.truth_queries(c["desc"])
-    kw = dict(samples=c["samples"], seed=11, parts=c["parts"])
-    kw.update(over)
-    return c, R.run(c["desc"], c["cam"], c["W"], c["H"], 0, 0, intersect, occluded, **kw)
+
+    def make():
+        intersect, occluded = R.truth_queries(c["desc"])
+        kw = dict(samples=c["samples"], seed=11, parts=c["parts"])
+        kw.update(over)
+        return R.run(c["desc"], c["cam"], c["W"], c["H"], 0, 0, intersect, occluded, **kw)
+    return c, G.cached(("direct light restated", name, tuple(sorted(over.items()))), make)
 
 
 @pytest.mark.parametrize("name", DC.NAMES)
@@ -106,7 +138,138 @@ def test_truth_scene(srt, name):
     n = c["W"] * c["H"] * c["samples"]
     st = out["stats"]
     assert st["miss"] + st["emitted"] + st["specular"] + st["shaded"] == n
+    if name in DC.EXACT + DC.ALL_HELD:          # under a lens too: every camera ray's first hit is the floor
+        assert st["shaded"] == n, (name, st)
+    if name in DC.ALL_HELD:                     # nothing stands between the floor and its lights
+        assert st["light_rows"] == st["light_unoccluded"] == n, (name, st)
+    if name == "emitters_in_view":
+        assert st["shaded"] == 0 and st["emitted"] > 0 and st["miss"] > 0, st
     print(name, st, DC.assert_holds(name, DC.expectation(srt, name), out["sum"], out["m2"], c["samples"], c["W"], c["H"], "restatement"))
+
+
+def test_many_lights_table(srt):
+    """the many_lights scene is what tests/direct_light_cases.py says, before anything is sampled on it: 37 lights of positive float32
+    area, exactly the eight at TINY pinned at width 1, the tiny triangles' float32 sides within 1 % of the sides asked for, the wide ones'
+    areas over three decades, every pixel held; and the binary search as the header states it picks, at both ends of every light's
+    interval of draws, the light the interval belongs to"""
+    c = DC.case(srt, "many_lights")
+    tab = R.tables(c["desc"])
+    th = tab["thresholds"]
+    width = np.diff(th.astype(np.int64))
+    assert len(tab["area"]) == DC.N_MANY and tab["area"].dtype == np.float32 and (tab["area"] > 0).all()
+    assert np.nonzero(width == 1)[0].tolist() == list(DC.TINY) and (width == 1).sum() == 8 and width.sum() == R.N_DRAWS
+    wide = np.delete(tab["area"].astype(np.float64), DC.TINY)
+    assert wide.max() / wide.min() >= 1e3, wide.max() / wide.min()
+    V, e = G.f64(DC.many_lights()), np.linalg.norm(G.f64(G.LIGHT[1:] - G.LIGHT[0]), axis=1)
+    for k in DC.TINY:
+        for a, b, edge in ((1, 0, 0), (2, 0, 1)) if k % 3 != 1 else ((1, 2, 0), (0, 2, 1)):
+            assert abs(np.linalg.norm(V[k, a] - V[k, b]) / (DC.TINY_SIDE * e[edge]) - 1.0) < 0.01, (k, a, b)
+    normal = tab["normal"].astype(np.float64)
+    assert (normal[:, 1] > 0).any() and (normal[:, 1] < 0).any(), "both windings"
+    held = DC.expectation(srt, "many_lights")["held"]
+    assert held.all() and held.sum() == c["W"] * c["H"]
+    for a in range(DC.N_MANY):
+        assert _device_pick(th, int(th[a])) == a and _device_pick(th, int(th[a + 1]) - 1) == a, a
+
+
+@pytest.mark.parametrize("which", ["pinned", "edge"])
+def test_fixed_draw(srt, which):
+    """the two committed draws of many_lights (DC.DRAW_S, found once by DC.find_draw), re-derived with one Philox call: "pinned" equals
+    thresholds[a] of a light of width 1, "edge" equals thresholds[m] of a light wider than 1 and must pick m, not m - 1.  The restatement
+    of that one sample under the float64 queries then picks the light, traces the row and weighs it within the bound
+    DC.assert_weight_holds derives."""
+    c = DC.case(srt, "many_lights")
+    tab = R.tables(c["desc"])
+    th = tab["thresholds"]
+    (x, y), s = DC.DRAW_PIXEL, DC.DRAW_S[which]
+    k = int(R.philox(np.array([y * c["W"] + x], np.uint32), np.uint32(s), 2, 0, *R.seed_key(DC.DRAW_SEED))[0][0] >> np.uint32(8))
+    a = int(np.nonzero(th == k)[0][0]) if (th == k).any() else -1
+    assert a >= 0 and k in DC.draw_targets(th)[which].tolist(), (which, k)
+    width = int(th[a + 1]) - int(th[a])
+    assert (width == 1 and a in DC.TINY) if which == "pinned" else (width > 1 and a > 0), (which, a, width)
+    assert _device_pick(th, k) == a
+    assert DC.find_draw(DC.draw_targets(th)[which], y * c["W"] + x, DC.DRAW_SEED, start=s - 5, limit=s + 5) == (s, k)
+    assert DC.expectation(srt, "many_lights")["held"][y * c["W"] + x]
+    intersect, occluded = R.truth_queries(c["desc"])
+    out = R.run(c["desc"], c["cam"], 1, 1, x, y, intersect, occluded, samples=1, first_sample=s, seed=DC.DRAW_SEED, parts=("lights",), keep=True)
+    assert (c["desc"]["normal"][0:2] == np.array([0, 1, 0], np.float32)).all(1).all() or (c["desc"]["normal"][0:2] == np.array([0, -1, 0], np.float32)).all(1).all()
+    rnd = out["rounds"][0]
+    print(which, "light %d of width %d, draw %d; weight off by %.3g, allowed %.3g" % (
+        (a, width, k) + DC.assert_weight_holds(tab, rnd["records"][0], rnd["light_rows"][0], a, which)))
+
+
+def test_two_emitters_tells_its_tables_apart(srt):
+    """both floor materials are in view, and each of the two deliberate breaks of the expectation (module docstring) turns it red"""
+    c, out = _restated(srt, "two_emitters")
+    tri = DC.first_hits(c, 0.0, 0.0)[0]
+    assert min((tri == 0).sum(), (tri == 1).sum()) >= G.MIN_PIXELS, ((tri == 0).sum(), (tri == 1).sum())
+    tab = out["tab"]
+    assert tab["mat"].tolist() == [3, 1], "the red emitter (material 3) comes first: slot order is not material order"
+    assert abs(float(tab["area"][0]) / float(tab["area"][1]) - 1.0) > 0.2, "unequal areas"
+    exp = DC.expectation(srt, "two_emitters")
+    for broken in ("emitters", "floors"):
+        wrong = dict(exp, **DC.two_emitters_expectation(c, tab, broken))
+        with pytest.raises(AssertionError) as e:
+            DC.assert_holds("two_emitters", wrong, out["sum"], out["m2"], c["samples"], c["W"], c["H"], broken + " swapped")
+        print(broken, "swapped:", e.value)
+
+
+def test_black_sky(srt):
+    """cosine_law has a black background.  SKY alone: no sky row is made, no occlusion query asked, every sum 0.  LIGHTS with SKY is
+    LIGHTS alone in every bit and counter."""
+    c = DC.case(srt, "cosine_law")
+    intersect, occluded = R.truth_queries(c["desc"])
+    calls = dict(intersect=0, occluded=0)
+
+    def counted(fn, name):
+        def call(rows):
+            calls[name] += 1
+            return fn(rows)
+        return call
+    run = lambda **kw: R.run(c["desc"], c["cam"], c["W"], c["H"], 0, 0, counted(intersect, "intersect"), counted(occluded, "occluded"), samples=3, seed=11, **kw)
+    sky = run(parts=("sky",), keep=True)
+    assert not R.tables(c["desc"])["bg_nonzero"]
+    assert calls == dict(intersect=3, occluded=0)
+    assert not sky["sum"].any() and not sky["m2"].any() and sky["stats"]["sky_rows"] == 0 and sky["stats"]["light_rows"] == 0
+    assert sky["stats"]["shaded"] == 3 * c["W"] * c["H"]
+    assert all(not r["sky_rows"].any() and not (r["records"][:, 3] & R.ROW_SKY).any() for r in sky["rounds"])
+    both, lights = run(parts=("lights", "sky")), run(parts=("lights",))
+    assert calls == dict(intersect=9, occluded=6)
+    assert np.array_equal(bits(both["sum"]), bits(lights["sum"])) and np.array_equal(bits(both["m2"]), bits(lights["m2"]))
+    assert both["stats"] == lights["stats"] and lights["stats"]["light_unoccluded"] > 0
+
+
+def lens_camera(srt, name):
+    """(cam, W, H): RANDOM_SPHERES' default camera at 64 x 48 (defocus angle 0.6 degrees) or a lens case's own"""
+    if name == "random_spheres":
+        return srt.Scene.builtin(srt.SCENE_RANDOM_SPHERES).default_camera(64, 48), 64, 48
+    c = DC.case(srt, name)
+    return c["cam"], c["W"], c["H"]
+
+
+@pytest.mark.parametrize("name", DC.LENS_CAMERAS)
+def test_lens_rows_hold_to_geometry(srt, name):
+    """the restatement's camera rows of samples 0 .. 3 under a thin lens (module docstring, "lens rows")"""
+    cam, W, H = lens_camera(srt, name)
+    assert cam.defocus_angle > 0
+    gx, gy, pid = R.pixels(cam, W, H, 0, 0)
+    rows = np.stack([R.camera_rows(cam, gx, gy, pid, np.uint32(s), R.seed_key(11)) for s in range(4)])
+    print(name, DC.assert_lens_rows_hold(cam, W, H, rows, name))
+
+
+def test_lens_quadrature_is_converged(srt):
+    """cosine_law_lens' expectation at LENS_COARSE and at LENS_FINE: the finer one is used, and the two differ by less than a tenth of the
+    smallest per-pixel standard error of the test in every channel"""
+    c, out = _restated(srt, "cosine_law_lens")
+    S = c["samples"]
+    coarse, fine = DC.lens_share(c, *DC.LENS_COARSE), DC.expectation(srt, "cosine_law_lens")["share"]
+    T = out["tab"]["t_light"][0, 1].astype(np.float64)
+    mean = out["sum"].reshape(-1, 3).astype(np.float64) / S
+    se = np.sqrt(np.maximum(out["m2"].reshape(-1, 3).astype(np.float64) - S * mean * mean, 0.0) / (S - 1) / S)
+    worst = (np.abs(fine - coarse).max() * T) / se.min(0)
+    pinhole = np.abs(fine - DC.expectation(srt, "cosine_law")["share"]).max() * T / se.min(0)
+    print("lens quadrature: max |fine - coarse| / min standard error per channel", worst, "; against the pinhole's expectation", pinhole)
+    assert (se > 0).all() and (worst < 0.1).all(), worst
 
 
 def test_occluded_truth_converges(srt):
